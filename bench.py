@@ -13,11 +13,12 @@ scores, taking its table offsets from a chained scan across workgroups; --two-pa
 count -> tile scan -> emit+score launch sequence instead) over the rank's arena, with the packed
 genome already resident in HBM.  Contigs are independent, so at N > 1 the steps run with NO
 collective on the data path; the path's one exchange -- the FINAL RCCL gatherv of the per-rank hit
-tables to rank 0 (crp_gather_hits) -- runs once after the timed steps and is reported on its own
+tables to rank 0 (crp_gather_hits) -- runs (--full) once after the timed steps and is reported on its own
 (`gatherv`), together with the whole-job rate that includes it (`value_with_final_gatherv` = gRNAs of all
 ranks / (one step + the one exchange): the number a scaling curve should be built from, since `value`'s
 steps hold no collective; `per_rank` lists every rank's kernel time and share).
---gather-every-step puts it inside every step instead.  A failed exchange still prints the line
+--gather-every-step puts it inside every step instead (plain runs too).  Without --full and without
+--gather-every-step, an N > 1 line has no exchange at all: weak-scaling headline and `per_rank` only.  A failed exchange still prints the line
 (`gatherv_ok: false`) and then exits non-zero; one that never RETURNS is ended by rank 0's watchdog after
 --collective-timeout seconds, the line printed with the scan's numbers first.  If the RCCL communicator cannot be CREATED
 (or its bootstrap does not return within CROPSR_COMM_INIT_TIMEOUT_S; every rank
@@ -25,17 +26,29 @@ learns that together, before any collective), the measurement still runs -- the 
 collective -- with the control sockets as fence and the host transport for the final exchange; the
 line then carries `rccl_error` and names the transport in `config.parallelism`, and stderr says so.
 The W warm-up steps run immediately before the timed region and are followed by further untimed steps
-until --preheat-ms (60) have passed: the GPU's clocks drop during the side measurements that precede
-them (a 0.6 GB copy of the tables to the host), and K = 20 steps of 0.5 ms are over before they are
-back up.  `untimed_steps_before` reports how many steps ran untimed in all.
+until --preheat-ms (60) have passed: with --full, the GPU's clocks drop during the side measurements that
+precede them (a 0.6 GB copy of the tables to the host), and K = 20 steps of 0.5 ms are over before they
+are back up; a plain run reaches them straight from the first scan, and the preheat steps keep the same
+steady clocks in front of its timed region.  `untimed_steps_before` reports how many steps ran untimed in all.
 Workload at N = 1: the >= 1 Gb crop genome BASELINE.json's target is quoted on
 ("switchgrass-like", SURVEY.md 8d cfg 5, seeded synthetic).  Weak scaling: N ranks
 process N such genomes (seeds 0..N-1), contigs dealt to ranks by LPT.
 
 Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` (HIP-event timing of
-the emit+score kernel on the library's stream), `offtarget` (the opt-in genome-wide seed scan of
-cfg 5 on the same resident genome, its own steps and roofline) and, at N = 1, `cpu_baseline` (the
-reference-faithful numpy port on a bounded sample: one core, and all cores for BLAS).
+the emit+score kernel on the library's stream, inside the timed steps).  A plain run does only what that
+line's headline needs: set-up, warm-up, the K timed steps, --dump-outputs if given, the line.  --full
+adds every other measurement: `pcie_inclusive` (the tables to the host, and the same genome through the
+pipelined crp_scan_stream), the three-launch kernels and the live stream-read ceiling beside the roofline,
+`offtarget` (the opt-in genome-wide seed scan of cfg 5 on the same resident genome, its own steps and
+roofline), `annotate` (the opt-in annotation join), at N > 1 the final gatherv, the strong-scaling block
+and rank 0's node-handle block, and at N = 1 `cpu_baseline` (the reference-faithful numpy port on a
+bounded sample: one core, and all cores for BLAS).  In the three-launch mode (--two-pass, or a chain
+time-out that fell back to it) the count and tile-scan kernel times come from that side run only, so
+a plain line's `roofline.all_kernels_ms` is null there (`kernel_ms`, the emit kernel's, is always set).
+
+--dump-outputs DIR (N = 1) writes what the last timed step computed -- the hit tables a caller of the path
+receives, both strands' arena positions and scores -- as float64 .npy files (see dump_outputs).  The
+workload is seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -117,7 +130,39 @@ def parse_args():
     ap.add_argument("--cpu-sample-bases", type=int, default=40000000,
                     help="upper bound on the bases of the same workload timed on the CPU port; the actual "
                          "sample is sized for about 12 s of CPU work per leg (0 = skip)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="every measurement besides the headline: the host-buffer boundary and the pipelined scan, the "
+                         "three-launch side run, the off-target and annotation blocks, the CPU baseline, and at N > 1 the final "
+                         "gatherv, the strong-scaling and node-handle blocks (a plain run: set-up, warm-up, timed steps, line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="N = 1: after the timed steps, write the hit tables of the last one as DIR/<name>.npy (float64; a fixed, "
+                         "seeded sample of rows when a table is longer than %d)" % DUMP_ROWS)
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and (args.gpus != 1 or args.single_process):
+        ap.error("--dump-outputs needs --gpus 1 without --single-process")
+    return args
+
+
+DUMP_ROWS = 1 << 20  # per table: 4 columns x 8 B x 2^20 rows = 32 MiB in all, inside the 64 MB a dump may take
+DUMP_SEED = 20240917
+
+
+def dump_outputs(out_dir, cols, n_scored):
+    """The tables one step of the path leaves for its caller (Arena.fetch's columns: positions u32, scores f64 per strand)
+    as out_dir/{pos,score}_{plus,minus}.npy in float64 (positions are exact in it), plus counts.npy = [n_plus, n_minus,
+    n_scored].  A table longer than DUMP_ROWS is sampled at the same sorted, seeded rows on every run of the same length."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"counts": np.array([cols[0].size, cols[3].size, n_scored], dtype=np.float64)}
+    for strand, pos, score in (("plus", cols[0], cols[2]), ("minus", cols[3], cols[5])):
+        rows = slice(None) if pos.size <= DUMP_ROWS else \
+            np.sort(np.random.default_rng(DUMP_SEED).choice(pos.size, DUMP_ROWS, replace=False))
+        arrays["pos_" + strand] = pos[rows].astype(np.float64)
+        arrays["score_" + strand] = score[rows].astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 class FastaWorkload:
@@ -593,7 +638,7 @@ def main_single_process(args):
     strings = [s for g in per_genome for s in g]
     bases_all = sum(spec.length for wl in genomes for spec in wl.specs)
     t_gen = time.perf_counter() - t_gen
-    sample = bytes(strings[0][:args.cpu_sample_bases + 1]).decode("ascii", "replace") if strings else ""
+    sample = bytes(strings[0][:args.cpu_sample_bases + 1]).decode("ascii", "replace") if (strings and args.full) else ""
     t_upload = time.perf_counter()
     node.load(strings)  # cut + one host thread per device: H2D + pack
     t_upload = time.perf_counter() - t_upload
@@ -717,19 +762,20 @@ def main_single_process(args):
         return {"ms": best["ms_total"], "ms_exchange": best["ms_exchange"], "bytes_to_root": best["bytes_to_root"],
                 "transport": best["transport"], "ms_all": [round(r["ms_total"], 4) for r in reps], "note": best["note"]}
 
-    # ---- the path's one exchange
+    # ---- the path's one exchange (timed with --full; a plain run gathers once, untimed, for the headline's exact counts)
     gather_info = None
     if world > 1 and not args.no_gather:
         guard("crp_node_gather", lambda why: build_line({"error": why}))
         try:
-            packed = time_gather(pos16=True)
-            raw = time_gather(pos16=False)
-            gather_info = {"s": packed["ms"] * 1e-3, "transport": packed["transport"], "bytes_to_root": packed["bytes_to_root"],
-                           "GB_per_s_into_root": packed["bytes_to_root"] / (packed["ms_exchange"] * 1e-3) / 1e9 if packed["ms_exchange"] else None,
-                           "positions": "16 bits per hit + one word per 65 536 arena positions (CRP_GATHER_POS16)",
-                           "pos16": packed, "raw_u32_positions": raw}
-            if packed["transport"].startswith("RCCL"):
-                gather_info["device_to_device_copies"] = time_gather(pos16=True, peer_copy=True)
+            if args.full:
+                packed = time_gather(pos16=True)
+                raw = time_gather(pos16=False)
+                gather_info = {"s": packed["ms"] * 1e-3, "transport": packed["transport"], "bytes_to_root": packed["bytes_to_root"],
+                               "GB_per_s_into_root": packed["bytes_to_root"] / (packed["ms_exchange"] * 1e-3) / 1e9 if packed["ms_exchange"] else None,
+                               "positions": "16 bits per hit + one word per 65 536 arena positions (CRP_GATHER_POS16)",
+                               "pos16": packed, "raw_u32_positions": raw}
+                if packed["transport"].startswith("RCCL"):
+                    gather_info["device_to_device_copies"] = time_gather(pos16=True, peer_copy=True)
             node.gather(0)
             _, gp, gm = node.counts()
             partial["hits_all"] = gp + gm
@@ -744,7 +790,7 @@ def main_single_process(args):
 
     # ---- strong scaling: ONE genome over the N devices, checked against device 0 alone
     strong = None
-    if world > 1 and not args.no_strong and not (gather_info and "error" in gather_info):
+    if args.full and world > 1 and not args.no_strong and not (gather_info and "error" in gather_info):
         guard("strong-scaling block", lambda why: build_line(gather_info, {"error": why}))
         try:
             strong = node_strong_block(args, node, devices, genomes[0].name, strings_of(genomes[0]), n_warm)
@@ -755,7 +801,7 @@ def main_single_process(args):
         unguard()
 
     line = build_line(gather_info, strong)
-    if world == 1 and args.cpu_sample_bases > 0:
+    if args.full and world == 1 and args.cpu_sample_bases > 0:
         from oracle import oracle as _o
         _o.lib()
         line["cpu_baseline"] = cpu_baseline(sample, args.cpu_sample_bases)
@@ -828,12 +874,12 @@ def main():
     sample = None
     my_bases = 0
     t_upload = 0.0
-    keep_strings = world == 1 and not args.no_pipelined  # (the pipelined host-to-host block below sends them through again)
+    keep_strings = args.full and world == 1 and not args.no_pipelined  # (the pipelined host-to-host block below sends them through again)
     kept_strings = []
     for i in mine:
         g, k = all_specs[i]
         s = genomes[g].contig_string(k)
-        if sample is None and rank == 0:
+        if sample is None and rank == 0 and args.full:
             sample = bytes(s[:args.cpu_sample_bases + 1]).decode("ascii", "replace")  # keeps the leading quote
         t_up = time.perf_counter()
         builder.add(s)  # characters over PCIe + the ballot pack kernel, synchronous
@@ -854,7 +900,8 @@ def main():
         return parallel.gather_host(group, [dict(zip(("pos_plus", "score_plus", "pos_minus", "score_minus"),
                                                       (cols[0], cols[2], cols[3], cols[5])))], 0)
 
-    want_gather = world > 1 and not args.no_gather
+    # (a plain run at N > 1 has the exchange only when it is part of every step)
+    want_gather = world > 1 and not args.no_gather and (args.full or args.gather_every_step)
 
     def step():
         n_plus, n_minus = arena.scan_score_device(20, want_pre=False)
@@ -879,7 +926,7 @@ def main():
     scored = arena.count_scored()
     t_fetch = time.perf_counter()
     t_fetch_again = None
-    if rank == 0:
+    if rank == 0 and args.full:
         host_cols = arena.fetch(n_plus, n_minus)  # D2H of the tables into FRESH pageable numpy arrays (outside the timed region)
         t_fetch = time.perf_counter() - t_fetch
         t_fetch_again = time.perf_counter()
@@ -947,31 +994,32 @@ def main():
     del host_cols
     kept_strings = []
 
-    # count / scan kernel times from a few extra steps outside the timed region; inside it only the
+    # (--full) count / scan kernel times from a few extra steps outside the timed region; inside it only the
     # emit+score kernel (the one the roofline is quoted on) is bracketed by HIP events
-    eng.profile(2)
-    eng.profile_read(reset=True)
-    for _ in range(3):
-        arena.scan_score_device(20, want_pre=False)
-    side = eng.profile_read(reset=True)
-    # the box's practical HBM ceiling, measured live: the count kernel of the three-launch mode is a pure
-    # streaming read of the four planes (0.5 B per character, nothing written but 8 B per tile)
     stream_GBs = None
     three_launch_side = None  # the count / tile-scan / emit kernels of the three-launch mode, measured apart from the timed steps
-    if not args.two_pass:
-        eng.configure(two_pass=True)
-        for _ in range(5):
+    if args.full:
+        eng.profile(2)
+        eng.profile_read(reset=True)
+        for _ in range(3):
             arena.scan_score_device(20, want_pre=False)
-        three = eng.profile_read(reset=True)
-        eng.configure(two_pass=False)  # (back to what the run was started with: this branch is the not --two-pass one)
-        three_launch_side = {k: three[k]["ms"] / max(1, three[k]["launches"]) for k in ("count", "tile_scan", "emit_score")}
-        cnt = three["count"]
-        if cnt["launches"]:
-            stream_GBs = (arena.stats()["n_chars"] / 2.0) / (cnt["ms"] / cnt["launches"] * 1e-3) / 1e9
-    else:
-        three_launch_side = {k: side[k]["ms"] / max(1, side[k]["launches"]) for k in ("count", "tile_scan", "emit_score")}
-    eng.profile(0)
-    # The W warm-up steps run HERE, right before the timed region: the side measurements above (a 0.6 GB
+        side = eng.profile_read(reset=True)
+        # the box's practical HBM ceiling, measured live: the count kernel of the three-launch mode is a pure
+        # streaming read of the four planes (0.5 B per character, nothing written but 8 B per tile)
+        if not args.two_pass:
+            eng.configure(two_pass=True)
+            for _ in range(5):
+                arena.scan_score_device(20, want_pre=False)
+            three = eng.profile_read(reset=True)
+            eng.configure(two_pass=False)  # (back to what the run was started with: this branch is the not --two-pass one)
+            three_launch_side = {k: three[k]["ms"] / max(1, three[k]["launches"]) for k in ("count", "tile_scan", "emit_score")}
+            cnt = three["count"]
+            if cnt["launches"]:
+                stream_GBs = (arena.stats()["n_chars"] / 2.0) / (cnt["ms"] / cnt["launches"] * 1e-3) / 1e9
+        else:
+            three_launch_side = {k: side[k]["ms"] / max(1, side[k]["launches"]) for k in ("count", "tile_scan", "emit_score")}
+        eng.profile(0)
+    # The W warm-up steps run HERE, right before the timed region: with --full, the side measurements above (a 0.6 GB
     # device-to-host copy among them) leave the GPU idle long enough for its clocks to drop, and a timed region
     # of 20 x 0.5 ms is over before they are back up (measured: 0.547 ms per kernel with 20 timed steps against
     # 0.489 with 200 on one box, whatever W had been before the copy).  --preheat-ms adds untimed steps until about
@@ -991,12 +1039,14 @@ def main():
     fence()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        last = step()
     fence()
     dt = time.perf_counter() - t0
     prof = eng.profile_read(reset=True)
     eng.profile(0)
     state = eng.query()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, arena.fetch(*last), arena.count_scored())
 
     dt = reduce([dt], "max")[0]
     scored_all, bases_all, hits_all = reduce([scored, my_bases, n_plus + n_minus], "sum")
@@ -1029,8 +1079,13 @@ def main():
         facts, facts_src = load_profile_facts(build_id, genomes[0].name)
         three_launches = bool(args.two_pass or state["two_pass_active"])
         # the kernels that ran inside the timed steps: one in the single-launch mode, three otherwise -- the
-        # count and tile-scan times of the three-launch mode come from the side run and are reported under `three_launch`
-        path_ms = emit_ms + ((three_launch_side["count"] + three_launch_side["tile_scan"]) if three_launches else 0.0)
+        # count and tile-scan times of the three-launch mode come from the side run (--full) and are reported under `three_launch`
+        if not three_launches:
+            path_ms = emit_ms
+        elif three_launch_side is not None:
+            path_ms = emit_ms + three_launch_side["count"] + three_launch_side["tile_scan"]
+        else:
+            path_ms = None  # (a plain run in the three-launch mode: not measured, rather than the emit kernel alone)
         roof = {"bound": "hbm",
                 "kernel": "emit_kernel (scan+compact+score)" if three_launches else
                           "emit_kernel, single launch (masks + chained tile offsets + compact + score)",
@@ -1040,12 +1095,13 @@ def main():
                 "algorithmic_bytes": "ceil(N/4) + 2*ceil(N/8) + 12*H" if planes_counted else
                                      "ceil(N/4) + 12*H (entirely upper-case ACGT input: SURVEY.md 8d leaves the two bit-planes out)",
                 "characters": {"N": int(n_chars), "upper_case_acgt": composition["n_plain"], "other": composition["n_other"]},
-                # a pure streaming read of the same planes on this box (the count kernel): the practical ceiling beside the 8 TB/s spec
-                "measured_stream_read_GBs": stream_GBs,
-                "kernel_ms": emit_ms, "all_kernels_ms": path_ms,
-                # CRP_OPT_TWO_PASS = 1's kernels on the same arena, from a side run outside the timed region
-                "three_launch": {"count_kernel_ms": three_launch_side["count"], "tile_scan_ms": three_launch_side["tile_scan"],
-                                 "emit_kernel_ms": three_launch_side["emit_score"]}}
+                "kernel_ms": emit_ms, "all_kernels_ms": path_ms}
+        if args.full:
+            # a pure streaming read of the same planes on this box (the count kernel): the practical ceiling beside the 8 TB/s spec
+            roof["measured_stream_read_GBs"] = stream_GBs
+            # CRP_OPT_TWO_PASS = 1's kernels on the same arena, from a side run outside the timed region
+            roof["three_launch"] = {"count_kernel_ms": three_launch_side["count"], "tile_scan_ms": three_launch_side["tile_scan"],
+                                    "emit_kernel_ms": three_launch_side["emit_score"]}
         if facts and facts.get("valu_insts_per_launch") and facts.get("kernel_cycles_per_launch"):
             # the second, honest ceiling: the kernel is VALU-issue bound (one wave64 VALU instruction
             # holds its SIMD for 4 cycles on average here): issue slots used / issue slots there were
@@ -1076,12 +1132,13 @@ def main():
             "per_rank": per_rank,
             "roofline": roof,
             "setup_s": {"generate_pack_upload": t_gen},
-            # host-buffer boundary: characters H2D + pack, one scan, tables D2H (never `value`)
-            "pcie_inclusive": {"upload_pack_s": t_upload, "fetch_tables_s": t_fetch,
-                               # the same fetch into the SAME host arrays (pages already touched): the link's rate
-                               "fetch_tables_into_reused_arrays_s": t_fetch_again,
-                               "gRNAs_per_s": scored / (t_upload + dt / args.steps + t_fetch)},
         }
+        if args.full:
+            # host-buffer boundary: characters H2D + pack, one scan, tables D2H (never `value`)
+            line["pcie_inclusive"] = {"upload_pack_s": t_upload, "fetch_tables_s": t_fetch,
+                                      # the same fetch into the SAME host arrays (pages already touched): the link's rate
+                                      "fetch_tables_into_reused_arrays_s": t_fetch_again,
+                                      "gRNAs_per_s": scored / (t_upload + dt / args.steps + t_fetch)}
         if pipelined is not None:
             line["pcie_inclusive"].update(pipelined)
             if "pipelined_s" in pipelined:
@@ -1184,7 +1241,7 @@ def main():
         unguard()
 
     # ---- strong scaling: ONE genome over the N ranks (the headline above stays weak scaling)
-    if world > 1 and not args.no_strong and not (gather_info and "error" in gather_info):
+    if args.full and world > 1 and not args.no_strong and not (gather_info and "error" in gather_info):
         guard("strong-scaling block")
         try:
             strong = strong_scaling_block(args, eng, group, use_rccl, fence, reduce)
@@ -1204,7 +1261,7 @@ def main():
     # not a thread: whatever goes wrong in there (a crash inside RCCL, a bootstrap that never returns: the child is killed
     # after --collective-timeout) cannot take this rank or its line down.
     node_block = None
-    if world > 1 and not args.no_node_block and not args.no_strong:
+    if args.full and world > 1 and not args.no_node_block and not args.no_strong:
         if rank == 0:
             import subprocess
             cmd = [sys.executable, os.path.abspath(__file__), "--gpus", str(world), "--single-process", "--strong-only",
@@ -1244,9 +1301,9 @@ def main():
 
     # ---- the opt-in off-target seed scan of cfg 5 on the same resident genome and hit tables
     ot = None
-    if args.offtarget_steps > 0 and rccl_error and world > 1:
+    if args.full and args.offtarget_steps > 0 and rccl_error and world > 1:
         ot = {"skipped": "the site histogram is summed over the ranks by an RCCL all-reduce, and RCCL is unavailable here"}
-    elif args.offtarget_steps > 0 and not (gather_info and "error" in gather_info):
+    elif args.full and args.offtarget_steps > 0 and not (gather_info and "error" in gather_info):
         guard("off-target block (site-histogram all-reduce)")
         try:
             # The scan hands the seed words over (CRP_SCAN_SEEDS: the emit kernel writes them from the windows it
@@ -1325,7 +1382,7 @@ def main():
 
     # ---- the opt-in annotation join (BASELINE.json configs[2], [3] name a GFF) on the same resident tables
     ann_block = None
-    if args.annotate_steps > 0 and world == 1 and (not is_real or args.gff):
+    if args.full and args.annotate_steps > 0 and world == 1 and (not is_real or args.gff):
         try:
             import shutil
             import tempfile
@@ -1400,7 +1457,7 @@ def main():
             line["annotate"] = ann_block
         if node_block is not None:
             line["single_process_node"] = node_block
-        if world == 1 and args.cpu_sample_bases > 0:
+        if args.full and world == 1 and args.cpu_sample_bases > 0:
             from oracle import oracle as _o
             _o.lib()
             line["cpu_baseline"] = cpu_baseline(sample, args.cpu_sample_bases)

@@ -10,27 +10,27 @@ RAW=gpurun_out/prof_$TAG
 OUT=gpurun_out/profiles_$TAG
 mkdir -p "$RAW" "$OUT"
 
-# the bench with no flags (CPU baseline legs included) and with the driver's flags, plain and under the kernel trace
-python3 bench.py > $OUT/bench_default_run.json 2> $RAW/default.err
+# the whole bench (--full: CPU baseline legs included), and a plain run with the driver's flags, alone and under the kernel trace
+python3 bench.py --full > $OUT/bench_default_run.json 2> $RAW/default.err
 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_flags_run.json 2> $RAW/driver.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $RAW/driver_trace -- python3 bench.py --gpus 1 --steps 20 --warmup 5 \
     > $OUT/bench_driver_flags_under_trace.json 2> $RAW/driver_trace.err
 cp $RAW/driver_trace/*/*_kernel_stats.csv $OUT/kernel_stats_driver_flags.csv
 # the smaller configs of BASELINE.json (parity cases, not the headline)
-python3 bench.py --workload tair10 --cpu-sample-bases 0 > $OUT/bench_tair10_like.json 2> $RAW/tair10.err
-python3 bench.py --workload ecoli --cpu-sample-bases 0 > $OUT/bench_ecoli_like.json 2> $RAW/ecoli.err
+python3 bench.py --full --workload tair10 --cpu-sample-bases 0 > $OUT/bench_tair10_like.json 2> $RAW/tair10.err
+python3 bench.py --full --workload ecoli --cpu-sample-bases 0 > $OUT/bench_ecoli_like.json 2> $RAW/ecoli.err
 # N = 2 started by the program itself, both ranks on this one GPU (host transport for fences and the final gatherv)
-python3 bench.py --gpus 2 --share-gpu0 --scale 0.25 --steps 10 --warmup 3 --cpu-sample-bases 0 \
+python3 bench.py --full --gpus 2 --share-gpu0 --scale 0.25 --steps 10 --warmup 3 --cpu-sample-bases 0 \
     > $OUT/bench_2ranks_self_launched_one_gpu.json 2> $RAW/2ranks.err
 # six ranks on the one GPU (the most processes the pool lets one job keep on a card: no room for rank 0's node-block child),
 # weak headline + strong-scaling block
-python3 bench.py --gpus 6 --share-gpu0 --scale 0.25 --steps 10 --warmup 3 --cpu-sample-bases 0 --offtarget-steps 0 --no-node-block \
+python3 bench.py --full --gpus 6 --share-gpu0 --scale 0.25 --steps 10 --warmup 3 --cpu-sample-bases 0 --offtarget-steps 0 --no-node-block \
     > $OUT/bench_6ranks_self_launched_one_gpu.json 2> $RAW/6ranks.err
 # ONE process over four logical devices (the library's node handle; on this one-GPU box they are GPU 0 four times, the exchange
 # runs as device-to-device copies): weak headline of 4 x 0.25 genomes, gatherv packed / raw, strong block with digest check
-python3 bench.py --gpus 4 --single-process --share-gpu0 --scale 0.25 --steps 10 --warmup 3 --cpu-sample-bases 0 \
+python3 bench.py --full --gpus 4 --single-process --share-gpu0 --scale 0.25 --steps 10 --warmup 3 --cpu-sample-bases 0 \
     > $OUT/bench_single_process_4_logical_devices.json 2> $RAW/sp4.err
-python3 bench.py --gpus 4 --single-process --share-gpu0 --steps 10 --warmup 3 --cpu-sample-bases 0 \
+python3 bench.py --full --gpus 4 --single-process --share-gpu0 --steps 10 --warmup 3 --cpu-sample-bases 0 \
     > $OUT/bench_single_process_4_logical_devices_full_size.json 2> $RAW/sp4full.err
 # the whole CLI end to end (FASTA in, CSV out)
 python3 tools/e2e_cli.py switchgrass > $OUT/e2e_cli_switchgrass_first_process_on_the_box.json 2> $RAW/e2e0.err

@@ -454,7 +454,7 @@ def test_bench_strong_block_on_rccl_double():
     with fake_rccl.Session(CROPSR_BENCH_FORCE_RCCL="1", CRP_NODE_TRANSPORT="try") as s:
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "3", "--master-addr", "127.0.0.1",
                "--master-port", "29571", os.path.join(ROOT, "bench.py"), "--gpus", "3", "--share-gpu0", "--scale", "0.02", "--steps", "2",
-               "--warmup", "1", "--offtarget-steps", "1"]
+               "--warmup", "1", "--offtarget-steps", "1", "--full"]
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=ROOT, env=s.env())
         assert p.returncode == 0, p.stderr[-4000:]
         lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

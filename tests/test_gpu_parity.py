@@ -828,7 +828,7 @@ def test_bench_line_contract():
     import sys
     from conftest import ROOT
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--scale", "0.01", "--steps", "2", "--warmup", "1",
-                        "--cpu-sample-bases", "20000"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+                        "--cpu-sample-bases", "20000", "--full"], capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1
@@ -850,6 +850,47 @@ def test_bench_line_contract():
     assert o["value"] > 0 and o["roofline"]["bound"] == "hbm" and o["sites_total"] > 0 and "error" not in o
 
 
+def test_bench_plain_run_dumps_the_last_steps_tables(_engine, tmp_path):
+    """A plain bench run (no --full) prints the headline line without the side blocks, and --dump-outputs writes the
+    tables of its last timed step: bit for bit the tables of the same seeded genome scanned here through the same arena
+    builder."""
+    import argparse
+    import json
+    import subprocess
+    import sys
+    import bench
+    from conftest import ROOT
+    out = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--scale", "0.01", "--steps", "3",
+                        "--warmup", "1", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["metric"] == "gRNAs scored/sec" and d["unit"] == "gRNAs/s" and d["higher_is_better"] is True and d["dtype"] == "f64"
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["roofline"]["kernel_ms"] > 0
+    for key in ("cpu_baseline", "offtarget", "annotate", "pcie_inclusive"):
+        assert key not in d, key
+    assert "three_launch" not in d["roofline"]
+    got = {f.stem: np.load(f) for f in out.glob("*.npy")}
+    assert set(got) == {"counts", "pos_plus", "score_plus", "pos_minus", "score_minus"}
+    assert all(a.dtype == np.float64 for a in got.values()) and sum(a.nbytes for a in got.values()) <= 64 << 20
+    wl = bench.make_workload(argparse.Namespace(fasta=None, workload="switchgrass", scale=0.01), 0)
+    _engine.configure(two_pass=False, geometry="auto")
+    builder = _engine.arena_builder([wl.string_length(k) for k in range(len(wl.specs))])
+    for k in range(len(wl.specs)):
+        builder.add(wl.contig_string(k))
+    arena = builder.seal()
+    n_plus, n_minus = arena.scan_score_device(20, want_pre=False)
+    cols = arena.fetch(n_plus, n_minus)
+    assert got["counts"].tolist() == [n_plus, n_minus, arena.count_scored()] and d["config"]["kept_hits_total"] == n_plus + n_minus
+    arena.close()
+    assert max(n_plus, n_minus) <= bench.DUMP_ROWS  # (small enough to be dumped whole)
+    assert (got["pos_plus"] == cols[0]).all() and (got["pos_minus"] == cols[3]).all()
+    assert (got["score_plus"].view(np.uint64) == cols[2].view(np.uint64)).all()
+    assert (got["score_minus"].view(np.uint64) == cols[5].view(np.uint64)).all()
+
+
 @pytest.mark.parametrize("launcher", ["none", "torch.distributed.run"])
 def test_bench_starts_its_own_ranks(launcher):
     """`python bench.py --gpus 2` with NO launcher in the environment (what the driver's N > 1 command looks
@@ -867,7 +908,7 @@ def test_bench_starts_its_own_ranks(launcher):
         [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
          "--master-port", "29547"]
     p = subprocess.run(head + [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu0", "--scale", "0.02",
-                               "--steps", "3", "--warmup", "1", "--offtarget-steps", "0"],
+                               "--steps", "3", "--warmup", "1", "--offtarget-steps", "0", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -909,7 +950,7 @@ def test_bench_four_ranks_on_the_one_gpu():
     # (--no-node-block: rank 0's closing block is one more process on the card -- four ranks, the child and this test runner
     # would be the six the pool allows; the two-rank test above runs it)
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--share-gpu0", "--scale", "0.05",
-                        "--steps", "3", "--warmup", "1", "--offtarget-steps", "0", "--no-node-block"],
+                        "--steps", "3", "--warmup", "1", "--offtarget-steps", "0", "--no-node-block", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -989,7 +1030,7 @@ def test_bench_prints_its_line_when_the_exchange_never_returns():
     env["CROPSR_BENCH_TEST_STALL"] = "1:gatherv"
     t0 = time.time()
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu0", "--scale", "0.02",
-                        "--steps", "3", "--warmup", "1", "--offtarget-steps", "0", "--collective-timeout", "5"],
+                        "--steps", "3", "--warmup", "1", "--offtarget-steps", "0", "--collective-timeout", "5", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode != 0 and time.time() - t0 < 600
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -1012,7 +1053,7 @@ def test_bench_goes_on_when_the_rccl_bootstrap_never_returns():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "CROPSR_LAUNCHED")}
     env.update(CROPSR_BENCH_FORCE_RCCL="1", CROPSR_TEST_HOOKS="1", CROPSR_TEST_COMM_INIT_STALL="1", CROPSR_COMM_INIT_TIMEOUT_S="5")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu0", "--scale", "0.02",
-                        "--steps", "3", "--warmup", "1", "--offtarget-steps", "0"],
+                        "--steps", "3", "--warmup", "1", "--offtarget-steps", "0", "--full"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

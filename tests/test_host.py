@@ -59,6 +59,27 @@ def test_product_and_bench_import_no_pytorch():
         assert not re.search(r"^\s*(import|from)\s+torch\b", open(f).read(), flags=re.M), f
 
 
+def test_bench_dump_outputs_samples_long_tables_the_same_way(tmp_path):
+    """bench.py --dump-outputs: a table longer than DUMP_ROWS is cut to the same sorted, seeded rows on every run (two
+    builds can be compared row for row), positions exact in float64, and the whole dump stays within 64 MB."""
+    import bench
+    n = bench.DUMP_ROWS + 12345
+    pos = np.arange(n, dtype=np.uint32) * 7 + np.uint32(4000000000 - 7 * n)
+    score = np.linspace(-1.0, 1.0, n)
+    cols = [pos, None, score, pos[:100].copy(), None, score[:100].copy()]
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), cols, 777)
+    a = {f.name: np.load(f) for f in (tmp_path / "a").iterdir()}
+    b = {f.name: np.load(f) for f in (tmp_path / "b").iterdir()}
+    assert sorted(a) == ["counts.npy", "pos_minus.npy", "pos_plus.npy", "score_minus.npy", "score_plus.npy"]
+    assert all(x.dtype == np.float64 and (x == b[k]).all() for k, x in a.items())
+    assert a["counts.npy"].tolist() == [n, 100, 777] and sum(x.nbytes for x in a.values()) <= 64 << 20
+    assert a["pos_plus.npy"].size == bench.DUMP_ROWS and (np.diff(a["pos_plus.npy"]) > 0).all()
+    rows = ((a["pos_plus.npy"] - float(pos[0])) / 7).astype(np.int64)  # the rows the sample took, back from the positions
+    assert (pos[rows].astype(np.float64) == a["pos_plus.npy"]).all() and (score[rows] == a["score_plus.npy"]).all()
+    assert (a["pos_minus.npy"] == pos[:100]).all() and (a["score_minus.npy"] == score[:100]).all()
+
+
 def test_product_never_imports_oracle():
     """The oracle is test infrastructure: nothing under cropsr_amd/ may touch it."""
     for base, _, files in os.walk(os.path.join(ROOT, "cropsr_amd")):

@@ -320,7 +320,7 @@ def test_bench_single_process_four_logical_devices():
     """`bench.py --gpus 4 --single-process`: the same line through the node handle -- ONE process, no launcher, no sockets.
     On the one-GPU box the four devices are GPU 0 four times (--share-gpu0): four contexts, four arenas, the exchange as
     device-to-device copies; the strong block's stitched tables equal device 0's own N = 1 scan, contig by contig."""
-    d = _bench("--gpus", "4", "--single-process", "--share-gpu0", "--scale", "0.05", "--steps", "3", "--warmup", "1")
+    d = _bench("--gpus", "4", "--single-process", "--share-gpu0", "--scale", "0.05", "--steps", "3", "--warmup", "1", "--full")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline"):
         assert key in d, key
@@ -342,6 +342,25 @@ def test_bench_single_process_four_logical_devices():
 
 
 @pytest.mark.gpu
+def test_bench_plain_runs_at_two_devices():
+    """A plain bench run (no --full) at N = 2, both ways -- two self-launched ranks on GPU 0, and the node handle over GPU 0
+    twice: the headline line alone (no exchange block, no strong or side blocks), and the same exact hit count of the two
+    seeded genomes either way (the ranks hold whole contigs; the node handle's shares overlap by their halos and are
+    counted after its one untimed gather)."""
+    ranks = _bench("--gpus", "2", "--share-gpu0", "--scale", "0.02", "--steps", "3", "--warmup", "1")
+    node = _bench("--gpus", "2", "--single-process", "--share-gpu0", "--scale", "0.02", "--steps", "3", "--warmup", "1")
+    for d in (ranks, node):
+        assert d["n_gpus"] == 2 and d["steps"] == 3 and d["value"] > 0 and d["ms_per_step"] > 0 and d["scaling"] == "weak"
+        assert [r["rank"] for r in d["per_rank"]] == [0, 1] and all(r["kernel_ms"] > 0 for r in d["per_rank"])
+        for key in ("gatherv", "gatherv_ok", "value_with_final_gatherv", "strong", "single_process_node", "offtarget",
+                    "annotate", "cpu_baseline", "pcie_inclusive"):
+            assert key not in d, key
+    assert "gatherv" not in ranks["config"]["parallelism"]
+    assert ranks["config"]["bases_total"] == node["config"]["bases_total"]
+    assert ranks["config"]["kept_hits_total"] == node["config"]["kept_hits_total"] > 0
+
+
+@pytest.mark.gpu
 def test_bench_real_fasta_and_bytes_per_survey_8d(tmp_path):
     """--fasta: a REAL genome through the bench (SURVEY.md 8d "real FASTA may be substituted"): the reference's own sample
     (sample_data/sample_genome.fa, committed here gzipped as a fixture) gives its 17 314 kept hits, `data` says real and the
@@ -352,7 +371,7 @@ def test_bench_real_fasta_and_bytes_per_survey_8d(tmp_path):
     fa = tmp_path / "sample_genome.fa"
     with gzip.open(os.path.join(GOLDEN, "sample_genome.fa.gz"), "rb") as f:
         fa.write_bytes(f.read())
-    d = _bench("--fasta", str(fa), "--steps", "3", "--warmup", "1", "--cpu-sample-bases", "20000", "--offtarget-steps", "1")
+    d = _bench("--fasta", str(fa), "--steps", "3", "--warmup", "1", "--cpu-sample-bases", "20000", "--offtarget-steps", "1", "--full")
     assert d["data"] == "real" and d["config"]["kept_hits_total"] == 17314 and d["config"]["workload"].startswith("sample_genome.fa")
     assert d["config"]["bases_total"] == 230218 and "annotate" not in d and d["cpu_baseline"]["value"] > 0
     r = d["roofline"]
@@ -361,11 +380,11 @@ def test_bench_real_fasta_and_bytes_per_survey_8d(tmp_path):
     assert r["algorithmic_bytes_per_launch"] == (n + 3) // 4 + 2 * ((n + 7) // 8) + 12 * 17314
     # with its GFF: the annotate block joins the user's own annotation
     d = _bench("--fasta", str(fa), "--gff", os.path.join(GOLDEN, "sample_head.gff"), "--steps", "2", "--warmup", "1",
-               "--cpu-sample-bases", "0", "--offtarget-steps", "0")
+               "--cpu-sample-bases", "0", "--offtarget-steps", "0", "--full")
     assert d["annotate"]["gff"]["data"] == "sample_head.gff" and d["annotate"]["roofline"]["frac"] > 0
     # cfg 2: upper-case ACGT only
     d = _bench("--workload", "ecoli", "--steps", "3", "--warmup", "1", "--cpu-sample-bases", "0", "--offtarget-steps", "0",
-               "--annotate-steps", "0")
+               "--annotate-steps", "0", "--full")
     r = d["roofline"]
     n, h = r["characters"]["N"], d["config"]["kept_hits_total"]
     assert n == 4641652 + 4 and r["characters"]["other"] == 4
@@ -801,7 +820,8 @@ def test_node_threaded_scan_forced_on_one_gpu(tmp_path):
 def test_bench_single_process_one_device_and_strong_only():
     """`--single-process` with ONE device is the N = 1 line through the node handle (CPU baseline included); `--strong-only`
     is what rank 0 of a process-per-GPU run starts as its closing node block: just the strong block, digest-checked."""
-    d = _bench("--gpus", "1", "--single-process", "--scale", "0.01", "--steps", "3", "--warmup", "1", "--cpu-sample-bases", "20000")
+    d = _bench("--gpus", "1", "--single-process", "--scale", "0.01", "--steps", "3", "--warmup", "1", "--cpu-sample-bases", "20000",
+               "--full")
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["cpu_baseline"]["kind"] == "port" and d["gpu_over_cpu"] > 10
     assert "gatherv" not in d and "strong" not in d and d["roofline"]["frac"] > 0 and d["roofline"]["traffic_source"]
     d = _bench("--gpus", "3", "--single-process", "--strong-only", "--share-gpu0", "--scale", "0.02", "--steps", "2", "--warmup", "1")
