@@ -118,6 +118,14 @@ SIGNATURES = {
     "crp_offtarget_solve": (ctypes.c_int, [ctypes.c_void_p]),
     "crp_offtarget_counts": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p]),
     "crp_offtarget_seeds": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p]),
+    "crp_search_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, voidpp]),
+    "crp_search_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "crp_search_set_budget": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64]),
+    "crp_search_set_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint64]),
+    "crp_search_candidates": (ctypes.c_int, [ctypes.c_void_p, u64p, u64p]),
+    "crp_search_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, u32p, u64p]),
+    "crp_search_fetch": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, u8p, u8p, ctypes.c_uint64]),
+    "crp_search_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_configure": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]),
     "crp_query": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     "crp_build_id": (ctypes.c_char_p, []),
@@ -148,7 +156,9 @@ SCAN_PRE, SCAN_SEEDS = 1, 2
 OT_SEEDS = 1 << 24
 OT_NOT_A_SITE, OT_NOT_OWNED = 0xFFFFFFFF, 0xFFFFFFFE
 ABI_VERSION = 6
+CRP_ERR_INVALID = -1
 CRP_ERR_NO_DEVICE = -2
+CRP_ERR_UNSUPPORTED = -7
 CRP_ERR_CAPACITY = -6
 CRP_ERR_IO = -8
 CRP_ERR_COMM = -9

@@ -1,0 +1,377 @@
+// crp_search.cpp -- host side of the off-target search of given guides (include/cropsr_hip.h crp_search_*; kernels in
+// crp_search.hip).
+//
+// create   validates the pattern, counts the candidates of every workgroup of the arena (one launch) and plans the
+//          chunks: consecutive workgroups whose candidates fit the budget.
+// run      per chunk: extraction (skipped when the one chunk of the plan is still in HBM from an earlier run), then the
+//          compare in query batches of at most kPairsPerLaunch pairs and kBatchQueries queries per launch.  The site list
+//          is copied back and sorted by (query, arena position, strand): the atomics' order never reaches the caller.
+#include <algorithm>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "crp_internal.h"
+#include "crp_search.h"
+
+namespace {
+
+constexpr uint64_t kCandBytes = 16;                   // hi, lo, nb, pos
+constexpr uint64_t kPairsPerLaunch = 1ull << 36;      // ~7e10 pairs: a few ms at the issue floor, ~10-20 ms as measured
+constexpr uint64_t kBatchQueries = 4096;              // and at most this many queries, i.e. loop trips per lane, when candidates are few
+constexpr uint64_t kMinChunk = crp::SEARCH_WORDS * 64 * 2;  // one workgroup's most candidates (all-N pattern)
+constexpr uint64_t kMaxChunk = 1ull << 31;            // chunk-relative offsets are 32-bit
+constexpr uint64_t kSiteStart = 1ull << 20;           // device site slots of a first run (grows to what a run needs)
+constexpr uint64_t kMaxQueries = 1ull << 28;          // query index << 4 | mismatches in 32 bits
+
+// base set of an IUPAC letter (bit = code: A=0 T=1 C=2 G=3), 0 = not a letter of the pattern alphabet
+uint32_t iupac_set(char c)
+{
+    switch (c | 0x20) {
+        case 'a': return 1;
+        case 't': return 2;
+        case 'c': return 4;
+        case 'g': return 8;
+        case 'r': return 1 | 8;
+        case 'y': return 4 | 2;
+        case 's': return 4 | 8;
+        case 'w': return 1 | 2;
+        case 'k': return 8 | 2;
+        case 'm': return 1 | 4;
+        case 'b': return 4 | 8 | 2;
+        case 'd': return 1 | 8 | 2;
+        case 'h': return 1 | 4 | 2;
+        case 'v': return 1 | 4 | 8;
+        case 'n': return 15;
+        default: return 0;
+    }
+}
+
+uint32_t complement_set(uint32_t s) { return ((s & 1) << 1) | ((s & 2) >> 1) | ((s & 4) << 1) | ((s & 8) >> 1); }
+
+}  // namespace
+
+struct crp_search {
+    crp_arena *arena = nullptr;
+    crp_ctx *ctx = nullptr;
+    crp::SearchSets sets = {};
+    uint64_t n_plus = 0, n_minus = 0;
+    std::vector<uint2> block_cnt;  // per extraction workgroup: {'+', '-'} candidates
+    uint64_t budget = CRP_SEARCH_DEFAULT_BUDGET;
+    uint64_t batch_queries = kBatchQueries;  // crp_search_set_limits
+    uint64_t site_start = kSiteStart;
+    // plan: chunk c covers workgroups [chunk_first[c], chunk_first[c + 1]) with chunk_n[c] candidates
+    std::vector<uint32_t> chunk_first;
+    std::vector<uint64_t> chunk_n;
+    bool planned = false;
+    uint32_t *d_block_off = nullptr;  // per workgroup: first candidate, relative to its chunk
+    uint64_t block_off_cap = 0;
+    uint32_t *d_cand = nullptr;  // 4 x cand_cap uint32 (SoA)
+    uint64_t cand_cap = 0;
+    int cached_chunk = -1;  // the chunk whose candidates d_cand holds
+    // run
+    uint4 *d_queries = nullptr;
+    uint64_t q_cap = 0;
+    uint32_t *d_counts = nullptr;
+    uint64_t counts_cap = 0;
+    uint2 *d_sites = nullptr;
+    uint64_t sites_cap = 0;
+    unsigned long long *d_ctr = nullptr;
+    std::vector<uint64_t> keys;  // sites of the last successful run: query << 36 | pos << 5 | strand << 4 | mismatches
+    bool have_sites = false;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
+    double ms_extract = 0, ms_compare = 0;
+    uint64_t n_extract = 0, n_compare = 0;
+
+    crp::SearchCands cands() const
+    {
+        return crp::SearchCands{d_cand, d_cand + cand_cap, d_cand + 2 * cand_cap, d_cand + 3 * cand_cap};
+    }
+};
+
+namespace {
+
+double elapsed(hipEvent_t a, hipEvent_t b)
+{
+    float ms = 0.f;
+    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.0;
+}
+
+int plan(crp_search *s)
+{
+    crp_ctx *ctx = s->ctx;
+    const uint64_t cap = std::min(kMaxChunk, std::max(kMinChunk, s->budget / kCandBytes));
+    const uint32_t n_blocks = (uint32_t)s->block_cnt.size();
+    std::vector<uint32_t> off(n_blocks);
+    s->chunk_first.assign(1, 0);
+    s->chunk_n.clear();
+    uint64_t cur = 0, biggest = 0;
+    for (uint32_t b = 0; b < n_blocks; ++b) {
+        const uint64_t n = (uint64_t)s->block_cnt[b].x + s->block_cnt[b].y;
+        if (cur + n > cap) {
+            s->chunk_first.push_back(b);
+            s->chunk_n.push_back(cur);
+            biggest = std::max(biggest, cur);
+            cur = 0;
+        }
+        off[b] = (uint32_t)cur;
+        cur += n;
+    }
+    s->chunk_first.push_back(n_blocks);
+    s->chunk_n.push_back(cur);
+    biggest = std::max(biggest, cur);
+    if (n_blocks) {
+        int rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_block_off), &s->block_off_cap, n_blocks, sizeof(uint32_t));
+        if (rc != CRP_OK) return rc;
+        CRP_HIP(ctx, hipMemcpy(s->d_block_off, off.data(), n_blocks * sizeof(uint32_t), hipMemcpyHostToDevice));
+    }
+    // the candidate buffer holds the biggest chunk, exactly (not grow(): its slack would leave the budget)
+    if (s->cand_cap < biggest || s->cand_cap > std::max<uint64_t>(biggest, 1) * 2) {
+        (void)hipFree(s->d_cand);
+        s->d_cand = nullptr;
+        s->cand_cap = 0;
+        if (biggest) {
+            CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->d_cand), biggest * kCandBytes));
+            s->cand_cap = biggest;
+        }
+    }
+    s->cached_chunk = -1;
+    s->planned = true;
+    return CRP_OK;
+}
+
+// one pass over every chunk: counts and sites accumulate on the device
+int run_pass(crp_search *s, uint32_t n_queries, int max_mm, uint64_t dev_sites)
+{
+    crp_ctx *ctx = s->ctx;
+    crp_arena *a = s->arena;
+    const crp::Planes pl{{a->d_plane[0], a->d_plane[1], a->d_plane[2], a->d_plane[3]}};
+    CRP_HIP(ctx, hipMemsetAsync(s->d_counts, 0, (size_t)n_queries * (max_mm + 1) * sizeof(uint32_t), ctx->stream));
+    CRP_HIP(ctx, hipMemsetAsync(s->d_ctr, 0, sizeof(unsigned long long), ctx->stream));
+    const int n_chunks = (int)s->chunk_n.size();
+    for (int c = 0; c < n_chunks; ++c) {
+        const uint64_t n = s->chunk_n[c];
+        if (!n) continue;
+        const bool extract = s->cached_chunk != c;
+        CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+        if (extract) {
+            s->cached_chunk = -1;
+            CRP_HIP(ctx, crp::launch_search_emit(ctx->stream, pl, a->used_words, s->sets, s->chunk_first[c],
+                                                 s->chunk_first[c + 1] - s->chunk_first[c], s->d_block_off, s->cands()));
+        }
+        CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+        const uint32_t batch = (uint32_t)std::max<uint64_t>(1, std::min({(uint64_t)n_queries, kPairsPerLaunch / n, s->batch_queries}));
+        uint64_t launches = 0;
+        for (uint32_t q0 = 0; q0 < n_queries; q0 += batch) {
+            const uint32_t nq = std::min(batch, n_queries - q0);
+            CRP_HIP(ctx, crp::launch_search_compare(ctx->stream, s->cands(), (uint32_t)n, s->d_queries, q0, nq, max_mm, s->d_counts,
+                                                    s->d_sites, dev_sites, s->d_ctr));
+            ++launches;
+        }
+        CRP_HIP(ctx, hipEventRecord(s->ev[2], ctx->stream));
+        CRP_HIP(ctx, hipEventSynchronize(s->ev[2]));
+        if (extract) {
+            s->cached_chunk = c;
+            s->ms_extract += elapsed(s->ev[0], s->ev[1]);
+            s->n_extract += 1;
+        }
+        s->ms_compare += elapsed(s->ev[1], s->ev[2]);
+        s->n_compare += launches;
+    }
+    return CRP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int crp_search_create(crp_arena *a, const char *pattern, int T, crp_search **out)
+{
+    if (!a || !pattern || !out) return CRP_ERR_INVALID;
+    *out = nullptr;
+    if (T < 1 || T > CRP_SEARCH_MAX_T) return CRP_ERR_UNSUPPORTED;
+    crp::SearchSets sets = {};
+    sets.T = T;
+    for (int o = 0; o < T; ++o) {
+        const uint32_t sp = iupac_set(pattern[o]), sm = iupac_set(pattern[T - 1 - o]);
+        if (!sp || !sm) return CRP_ERR_INVALID;
+        sets.plus[o >> 4] |= (uint64_t)sp << ((o & 15) * 4);
+        sets.minus[o >> 4] |= (uint64_t)complement_set(sm) << ((o & 15) * 4);
+    }
+    if (!a->sealed) return CRP_ERR_STATE;
+    crp_ctx *ctx = a->ctx;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    crp_search *s = new (std::nothrow) crp_search;
+    if (!s) return CRP_ERR_NOMEM;
+    s->arena = a;
+    s->ctx = ctx;
+    s->sets = sets;
+    int rc = CRP_OK;
+    for (int k = 0; k < 3 && rc == CRP_OK; ++k)
+        if (hipEventCreate(&s->ev[k]) != hipSuccess) rc = CRP_ERR_HIP;
+    const uint64_t n_blocks = (a->used_words + crp::SEARCH_WORDS - 1) / crp::SEARCH_WORDS;
+    uint2 *d_cnt = nullptr;
+    if (rc == CRP_OK && n_blocks) {
+        s->block_cnt.resize(n_blocks);
+        const crp::Planes pl{{a->d_plane[0], a->d_plane[1], a->d_plane[2], a->d_plane[3]}};
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&d_cnt), n_blocks * sizeof(uint2));
+        if (e == hipSuccess) e = hipEventRecord(s->ev[0], ctx->stream);
+        if (e == hipSuccess) e = crp::launch_search_count(ctx->stream, pl, a->used_words, sets, d_cnt);
+        if (e == hipSuccess) e = hipEventRecord(s->ev[1], ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(s->block_cnt.data(), d_cnt, n_blocks * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        if (e != hipSuccess) {
+            ctx->last_error = std::string("crp_search_create: ") + hipGetErrorString(e);
+            rc = e == hipErrorOutOfMemory ? CRP_ERR_NOMEM : CRP_ERR_HIP;
+        } else {
+            s->ms_extract += elapsed(s->ev[0], s->ev[1]);
+            s->n_extract += 1;
+        }
+        (void)hipFree(d_cnt);
+    }
+    for (const uint2 &c : s->block_cnt) {
+        s->n_plus += c.x;
+        s->n_minus += c.y;
+    }
+    if (rc != CRP_OK) {
+        crp_search_destroy(s);
+        return rc;
+    }
+    *out = s;
+    return CRP_OK;
+}
+
+int crp_search_destroy(crp_search *s)
+{
+    if (!s) return CRP_ERR_INVALID;
+    (void)hipSetDevice(s->ctx->device);
+    (void)hipFree(s->d_block_off);
+    (void)hipFree(s->d_cand);
+    (void)hipFree(s->d_queries);
+    (void)hipFree(s->d_counts);
+    (void)hipFree(s->d_sites);
+    (void)hipFree(s->d_ctr);
+    for (hipEvent_t e : s->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete s;
+    return CRP_OK;
+}
+
+int crp_search_set_budget(crp_search *s, uint64_t bytes)
+{
+    if (!s) return CRP_ERR_INVALID;
+    s->budget = bytes ? bytes : CRP_SEARCH_DEFAULT_BUDGET;
+    s->planned = false;
+    return CRP_OK;
+}
+
+int crp_search_set_limits(crp_search *s, uint64_t batch_queries, uint64_t first_site_slots)
+{
+    if (!s) return CRP_ERR_INVALID;
+    s->batch_queries = batch_queries ? batch_queries : kBatchQueries;
+    s->site_start = first_site_slots ? first_site_slots : kSiteStart;
+    return CRP_OK;
+}
+
+int crp_search_candidates(const crp_search *s, uint64_t *n_plus, uint64_t *n_minus)
+{
+    if (!s) return CRP_ERR_INVALID;
+    if (n_plus) *n_plus = s->n_plus;
+    if (n_minus) *n_minus = s->n_minus;
+    return CRP_OK;
+}
+
+int crp_search_run(crp_search *s, const char *queries, uint64_t n_queries, int max_mm, uint64_t site_cap, uint32_t *counts,
+                   uint64_t *n_sites)
+{
+    if (!s || !n_sites || (n_queries && !queries)) return CRP_ERR_INVALID;
+    if (max_mm < 0 || max_mm > CRP_SEARCH_MAX_MM || n_queries >= kMaxQueries) return CRP_ERR_UNSUPPORTED;
+    const int T = s->sets.T;
+    std::vector<uint4> enc(n_queries);
+    for (uint64_t q = 0; q < n_queries; ++q) {
+        uint32_t h = 0, l = 0, m = 0;
+        for (int p = 0; p < T; ++p) {
+            uint32_t code;
+            switch (queries[q * T + p] | 0x20) {
+                case 'a': code = 0; break;
+                case 't': code = 1; break;
+                case 'c': code = 2; break;
+                case 'g': code = 3; break;
+                case 'n': continue;
+                default: return CRP_ERR_INVALID;
+            }
+            h |= (code >> 1) << p;
+            l |= (code & 1) << p;
+            m |= 1u << p;
+        }
+        enc[q] = make_uint4(h, l, m, 0);
+    }
+    s->have_sites = false;
+    s->keys.clear();
+    *n_sites = 0;
+    crp_ctx *ctx = s->ctx;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = CRP_OK;
+    if (!s->planned && (rc = plan(s)) != CRP_OK) return rc;
+    const uint64_t n_counts = n_queries * (uint64_t)(max_mm + 1);
+    if (!n_queries) {  // nothing to compare: an empty, fetchable list
+        s->have_sites = true;
+        return CRP_OK;
+    }
+    if ((rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_queries), &s->q_cap, n_queries, sizeof(uint4))) != CRP_OK) return rc;
+    if ((rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_counts), &s->counts_cap, n_counts, sizeof(uint32_t))) != CRP_OK) return rc;
+    if (!s->d_ctr) CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->d_ctr), sizeof(unsigned long long)));
+    uint64_t dev_sites = std::min(site_cap, std::max(s->sites_cap, s->site_start));
+    if (dev_sites && (rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_sites), &s->sites_cap, dev_sites, sizeof(uint2))) != CRP_OK)
+        return rc;
+    CRP_HIP(ctx, hipMemcpyAsync(s->d_queries, enc.data(), n_queries * sizeof(uint4), hipMemcpyHostToDevice, ctx->stream));
+    unsigned long long total = 0;
+    for (int pass = 0; pass < 2; ++pass) {
+        if ((rc = run_pass(s, (uint32_t)n_queries, max_mm, dev_sites)) != CRP_OK) return rc;
+        CRP_HIP(ctx, hipMemcpy(&total, s->d_ctr, sizeof(total), hipMemcpyDeviceToHost));
+        if (total <= dev_sites || total > site_cap) break;
+        // more sites than the device list had room for, fewer than the caller's: once more with room for all of them
+        dev_sites = total;
+        if ((rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_sites), &s->sites_cap, dev_sites, sizeof(uint2))) != CRP_OK)
+            return rc;
+    }
+    if (counts) CRP_HIP(ctx, hipMemcpy(counts, s->d_counts, n_counts * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    *n_sites = total;
+    if (total > site_cap) return CRP_ERR_CAPACITY;
+    std::vector<uint2> raw(total);
+    if (total) CRP_HIP(ctx, hipMemcpy(raw.data(), s->d_sites, total * sizeof(uint2), hipMemcpyDeviceToHost));
+    s->keys.resize(total);
+    for (uint64_t k = 0; k < total; ++k) {
+        const uint64_t q = raw[k].x >> 4, mm = raw[k].x & 15, pos = raw[k].y & 0x7fffffffu, strand = raw[k].y >> 31;
+        s->keys[k] = q << 36 | pos << 5 | strand << 4 | mm;
+    }
+    std::sort(s->keys.begin(), s->keys.end());
+    s->have_sites = true;
+    return CRP_OK;
+}
+
+int crp_search_fetch(const crp_search *s, uint32_t *query, uint32_t *arena_pos, uint8_t *strand, uint8_t *mismatches, uint64_t cap)
+{
+    if (!s) return CRP_ERR_INVALID;
+    if (!s->have_sites) return CRP_ERR_STATE;
+    if (cap < s->keys.size()) return CRP_ERR_CAPACITY;
+    for (uint64_t k = 0; k < s->keys.size(); ++k) {
+        const uint64_t key = s->keys[k];
+        if (query) query[k] = (uint32_t)(key >> 36);
+        if (arena_pos) arena_pos[k] = (uint32_t)(key >> 5) & 0x7fffffffu;
+        if (strand) strand[k] = (uint8_t)((key >> 4) & 1);
+        if (mismatches) mismatches[k] = (uint8_t)(key & 15);
+    }
+    return CRP_OK;
+}
+
+int crp_search_stats(const crp_search *s, double *out, int n)
+{
+    if (!s || (n && !out) || n < 0 || n > 6) return CRP_ERR_INVALID;
+    const double v[6] = {s->ms_extract, s->ms_compare, (double)s->n_extract, (double)s->n_compare,
+                         s->planned ? (double)s->chunk_n.size() : 0.0, (double)(s->cand_cap * kCandBytes)};
+    for (int k = 0; k < n; ++k) out[k] = v[k];
+    return CRP_OK;
+}
+
+}  // extern "C"

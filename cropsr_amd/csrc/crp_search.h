@@ -1,0 +1,42 @@
+// crp_search.h -- launch interface of crp_search.hip (the off-target search of given guides),
+// shared with its host side crp_search.cpp.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "crp_kernels.h"
+
+namespace crp {
+
+constexpr int SEARCH_WORDS = BLOCK;  // arena words per workgroup of the two extraction kernels (one word per thread)
+constexpr int SEARCH_CPL = 8;        // candidates per lane of the compare kernel
+constexpr int SEARCH_MAX_T = 32;
+constexpr int SEARCH_MAX_MM = 8;
+
+// The pattern as the extraction kernels read it: a 4-bit base set (bit = code, A=0 T=1 C=2 G=3; 15 = N, no base test)
+// per FORWARD window offset o, 16 sets per word.  plus: what the '+' site needs at offset o; minus: what the forward
+// character at offset o must be for the '-' site (the pattern letter at T - 1 - o, complemented).
+struct SearchSets {
+    uint64_t plus[2], minus[2];
+    int T;
+};
+
+// Candidate sites, SoA: the oriented window as three 32-bit fields (bit p = pattern position p) and where it is.
+struct SearchCands {
+    uint32_t *hi, *lo, *nb;  // base codes (high bit, low bit) and "not a base"
+    uint32_t *pos;           // forward start in the arena | strand << 31 ('-' = 1)
+};
+
+// Per workgroup of SEARCH_WORDS words: {'+' candidates, '-' candidates}.
+hipError_t launch_search_count(hipStream_t s, const Planes &pl, uint64_t used_words, const SearchSets &sets, uint2 *block_cnt);
+// Writes the candidates of workgroups [block_first, block_first + n_blocks): those of workgroup b start at block_off[b]
+// (relative to the chunk), in word order, each word's '+' starts ascending before its '-' starts.
+hipError_t launch_search_emit(hipStream_t s, const Planes &pl, uint64_t used_words, const SearchSets &sets, uint32_t block_first,
+                              uint32_t n_blocks, const uint32_t *block_off, SearchCands out);
+// Compares candidates [0, n) with queries [q0, q0 + nq) of `queries` ({hi, lo, compare mask, 0} per query): every pair
+// within max_mm adds one to counts[q * (max_mm + 1) + mm] and appends {q << 4 | mm, pos} to sites (slots >= site_cap are
+// counted in *site_ctr, not written).
+hipError_t launch_search_compare(hipStream_t s, const SearchCands &c, uint32_t n, const uint4 *queries, uint32_t q0, uint32_t nq,
+                                 int max_mm, uint32_t *counts, uint2 *sites, uint64_t site_cap, unsigned long long *site_ctr);
+
+}  // namespace crp

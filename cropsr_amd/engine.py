@@ -751,6 +751,12 @@ class Genome:
                 h.feat_plus, h.feat_minus = f
         return GenomeHits(self, per_arena)
 
+    def search(self, pattern, queries, max_mm, site_cap=None, budget=None, pam_len=None):
+        """Every site within max_mm mismatches of each query guide, over all arenas (search.search: the off-target
+        search of given guides).  Returns search.SearchResult (.counts, .sites)."""
+        from . import search
+        return search.search(self, pattern, queries, max_mm, site_cap=site_cap, budget=budget, pam_len=pam_len)
+
     def close(self):
         for a in self.arenas:
             a.close()

@@ -1,0 +1,353 @@
+"""Off-target search of given guides against the genome (not reference behaviour).
+
+A Cas-OFFinder-style search: a PAM pattern and query guides in, every site of the genome within M mismatches of each
+query out, on both strands.  The work runs in libcropsr_hip.so (crp_search_*, kernels in crp_search.hip) on the
+arenas the genome already sits in; this module validates input, maps arena positions back to contigs and writes TSV.
+
+    python -m cropsr_amd.search -f genome.fa --pattern NNNNNNNNNNNNNNNNNNNNNRG --pam-length 3 --guides guides.txt -m 4 \
+        -o sites.tsv
+
+Definition (what the tests check):
+  genome   FASTA records, parsed plainly (read_fasta): name = header up to its first whitespace, sequence = the
+           record's lines with all ASCII whitespace removed, positions 0-based in it
+  base     acgtACGT, and U (read as A); anything else (N, IUPAC codes, u, punctuation) is not a base
+  pattern  T (1..32) letters of ACGTRYSWKMBDHVN, 5' -> 3' on the target strand
+  site     the window of T characters at forward start i of a contig (strand '+'), or its reverse complement
+           (strand '-'); every pattern letter other than N needs a base of its set there (N: any character)
+  query    T letters of ACGTN; mismatches = positions where the query has a base and the oriented site does not
+           hold it (a non-base always mismatches); N positions are not compared
+  result   the sites with <= M (0..8) mismatches, ordered by query, contig, position, strand ('+' first), and
+           counts[q, k] = sites of query q with exactly k mismatches
+"""
+import argparse
+import ctypes
+import sys
+
+import numpy as np
+
+from . import _native as nat
+
+MAX_T = 32
+MAX_MM = 8
+IUPAC = "ACGTRYSWKMBDHVN"
+SITE_DTYPE = np.dtype([("query", "<u4"), ("contig", "<u4"), ("position", "<i8"), ("strand", "S1"), ("mismatches", "u1")])
+_WS = b" \t\n\r\x0b\x0c"
+
+
+class SearchInputError(ValueError):
+    """A pattern, guide or mismatch bound outside the definition."""
+
+
+class SiteCapacityError(RuntimeError):
+    """More sites than site_cap: .counts are exact, .n_sites is what a repeat needs."""
+
+    def __init__(self, counts, n_sites, site_cap):
+        self.counts, self.n_sites = counts, n_sites
+        super().__init__("%d sites exceed site_cap=%d" % (n_sites, site_cap))
+
+
+def check_pattern(pattern):
+    p = pattern.decode() if isinstance(pattern, bytes) else str(pattern)
+    p = p.upper()
+    if not 1 <= len(p) <= MAX_T:
+        raise SearchInputError("pattern must have 1..%d letters, not %d" % (MAX_T, len(p)))
+    bad = sorted(set(p) - set(IUPAC))
+    if bad:
+        raise SearchInputError("pattern %r: letters outside %s: %s" % (pattern, IUPAC, "".join(bad)))
+    return p
+
+
+def check_max_mm(max_mm):
+    if not isinstance(max_mm, (int, np.integer)) or not 0 <= int(max_mm) <= MAX_MM:
+        raise SearchInputError("mismatches must be an integer 0..%d, not %r" % (MAX_MM, max_mm))
+    return int(max_mm)
+
+
+def guide_run(pattern):
+    """(start, length) of the pattern's N letters when they form one contiguous run, else None."""
+    idx = [k for k, c in enumerate(pattern) if c == "N"]
+    if not idx or idx[-1] - idx[0] + 1 != len(idx):
+        return None
+    return idx[0], len(idx)
+
+
+def check_pam_len(pattern, pam_len):
+    T = len(pattern)
+    if not isinstance(pam_len, (int, np.integer)) or not 1 <= int(pam_len) < T:
+        raise SearchInputError("PAM length must be 1..%d for a pattern of %d letters, not %r" % (T - 1, T, pam_len))
+    return int(pam_len)
+
+
+def check_query(pattern, query, pam_len=None):
+    """A query of the pattern's length over ACGTN (upper-cased), or a shorter guide padded to one:
+
+    pam_len None  the guide is exactly as long as the pattern's single contiguous run of N and fills it; the other
+                  positions become N (21 letters for NNNNNNNNNNNNNNNNNNNNNGG, 23 for TTTVNNNNNNNNNNNNNNNNNNNNNNN)
+    pam_len P     the PAM is the pattern's last P letters (or its first P, for a PAM on the 5' side such as Cas12a's),
+                  every letter outside it is N, and a guide of at most T - P letters sits right next to it: a 20-nt
+                  or a truncated 18-nt guide with ...NGG and P = 3, a 21-nt one with ...NNGRRT and P = 6
+
+    The pattern alone cannot say which of its N letters belong to the PAM (NGG has one, NNGRRT two, TTTV none), so a
+    guide of any other length is refused rather than placed by a guess."""
+    q = query.decode() if isinstance(query, bytes) else str(query)
+    q = q.upper()
+    bad = sorted(set(q) - set("ACGTN"))
+    if bad or not q:
+        raise SearchInputError("guide %r: letters outside ACGTN: %s" % (query, "".join(bad)) if bad else "empty guide")
+    T = len(pattern)
+    if len(q) == T:
+        return q
+    if pam_len is None:
+        run = guide_run(pattern)
+        if run is not None and len(q) == run[1]:
+            return "N" * run[0] + q + "N" * (T - run[0] - len(q))
+        raise SearchInputError("guide %r has %d letters: the pattern has %d%s; a shorter guide needs the PAM's length "
+                               "(--pam-length) or N at the PAM positions" % (
+                                   query, len(q), T, "" if run is None else ", its N run %d" % run[1]))
+    P = check_pam_len(pattern, pam_len)
+    if set(pattern[:T - P]) <= {"N"}:  # PAM on the 3' side: the guide ends where it begins
+        at = T - P - len(q)
+    elif set(pattern[P:]) <= {"N"}:    # on the 5' side: the guide starts where it ends
+        at = P
+    else:
+        raise SearchInputError("pattern %s has letters other than N outside its first or last %d" % (pattern, P))
+    if len(q) > T - P:
+        raise SearchInputError("guide %r has %d letters: at most %d fit next to a PAM of %d in a pattern of %d" % (
+            query, len(q), T - P, P, T))
+    return "N" * at + q + "N" * (T - at - len(q))
+
+
+def parse_guides(text, pattern, pam_len=None):
+    """Guides file: one guide per non-empty line, `SEQUENCE [NAME]`; `#` starts a comment; the name defaults to the
+    1-based line number; shorter guides are padded by check_query.  Returns (names, queries)."""
+    if isinstance(text, bytes):
+        text = text.decode()
+    names, queries = [], []
+    for k, line in enumerate(text.splitlines(), 1):
+        fields = line.split("#", 1)[0].split()
+        if not fields:
+            continue
+        queries.append(check_query(pattern, fields[0], pam_len))
+        names.append(" ".join(fields[1:]) if len(fields) > 1 else str(k))
+    if not queries:
+        raise SearchInputError("no guides")
+    return names, queries
+
+
+def parse_fasta(data):
+    """FASTA bytes -> (names, sequences as bytes): name = header up to its first whitespace, sequence = the record's
+    lines with all ASCII whitespace removed."""
+    names, seqs, cur = [], [], None
+    for line in data.split(b"\n"):
+        if line.startswith(b">"):
+            if cur is not None:
+                seqs.append(b"".join(cur).translate(None, _WS))
+            head = line[1:].split()
+            names.append(head[0].decode("utf-8", "replace") if head else "")
+            cur = []
+        elif cur is not None:
+            cur.append(line)
+        elif line.strip(_WS):
+            raise SearchInputError("FASTA: sequence before the first '>' header")
+    if cur is not None:
+        seqs.append(b"".join(cur).translate(None, _WS))
+    return names, seqs
+
+
+def read_fasta(path):
+    with open(path, "rb") as f:
+        return parse_fasta(f.read())
+
+
+class ArenaSearch:
+    """One crp_search handle: the candidates of one arena for one pattern."""
+
+    def __init__(self, arena, pattern, budget=None):
+        self.pattern = check_pattern(pattern)
+        self._arena = arena  # (the handle reads the arena's planes: keep it alive)
+        h = ctypes.c_void_p()
+        nat.check(nat.lib().crp_search_create(arena._h, self.pattern.encode(), len(self.pattern), ctypes.byref(h)),
+                  "crp_search_create", arena._engine._ctx)
+        self._h = h
+        if budget is not None:
+            nat.check(nat.lib().crp_search_set_budget(self._h, int(budget)), "crp_search_set_budget")
+
+    def close(self):
+        if self._h:
+            nat.lib().crp_search_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def set_limits(self, batch_queries=0, first_site_slots=0):
+        """crp_search_set_limits: queries per compare launch and first device site slots (0: the defaults)."""
+        nat.check(nat.lib().crp_search_set_limits(self._h, int(batch_queries), int(first_site_slots)), "crp_search_set_limits")
+
+    def candidates(self):
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        nat.check(nat.lib().crp_search_candidates(self._h, ctypes.byref(a), ctypes.byref(b)), "crp_search_candidates")
+        return a.value, b.value
+
+    def run(self, queries, max_mm, site_cap):
+        """crp_search_run as it is: (status, counts (Q, M + 1) uint32, n_sites).  queries: already checked strings."""
+        Q = len(queries)
+        blob = "".join(queries).encode()
+        counts = np.zeros((Q, max_mm + 1), dtype=np.uint32)
+        n = ctypes.c_uint64()
+        st = nat.lib().crp_search_run(self._h, blob, Q, int(max_mm), int(site_cap), counts.ctypes.data_as(nat.u32p), ctypes.byref(n))
+        return st, counts, n.value
+
+    def fetch(self, n):
+        """(query u32, arena position u32, strand u8, mismatches u8) of the last run's n sites."""
+        cols = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, np.uint8), np.empty(n, np.uint8)
+        nat.check(nat.lib().crp_search_fetch(self._h, *[c.ctypes.data_as(p) for c, p in zip(cols, (nat.u32p, nat.u32p, nat.u8p, nat.u8p))], n),
+                  "crp_search_fetch")
+        return cols
+
+    def stats(self):
+        out = np.zeros(6, dtype=np.float64)
+        nat.check(nat.lib().crp_search_stats(self._h, out.ctypes.data_as(nat.f64p), 6), "crp_search_stats")
+        keys = ("extract_ms", "compare_ms", "extract_launches", "compare_launches", "chunks", "candidate_bytes")
+        return dict(zip(keys, (float(v) for v in out)))
+
+
+class SearchResult:
+    def __init__(self, counts, sites, candidates):
+        self.counts = counts          # (Q, M + 1) uint32
+        self.sites = sites            # SITE_DTYPE, ordered by query, contig, position, strand
+        self.candidates = candidates  # (n_plus, n_minus) over the whole genome
+
+
+def search(genome, pattern, queries, max_mm, site_cap=None, budget=None, pam_len=None):
+    """Every site of `genome` (engine.Genome) within max_mm mismatches of each query, over all its arenas.
+    site_cap=None: as many sites as there are; else SiteCapacityError (with exact counts) beyond it.  budget: device
+    bytes for one chunk of candidates (None: the library's default).  pam_len: how check_query pads shorter guides."""
+    pattern = check_pattern(pattern)
+    max_mm = check_max_mm(max_mm)
+    queries = [check_query(pattern, q, pam_len) for q in queries]
+    if any(len(q) != len(pattern) for q in queries):
+        raise SearchInputError("every query needs %d letters" % len(pattern))
+    Q = len(queries)
+    counts = np.zeros((Q, max_mm + 1), dtype=np.uint64)
+    parts, n_total, cand = [], 0, [0, 0]
+    unlimited = site_cap is None
+    for a, group in zip(genome.arenas, genome.groups):
+        s = ArenaSearch(a, pattern, budget)
+        try:
+            npl, nmi = s.candidates()
+            cand[0] += npl
+            cand[1] += nmi
+            cap = (1 << 62) if unlimited else max(0, int(site_cap) - n_total)
+            st, c, n = s.run(queries, max_mm, cap)
+            if st not in (nat.CRP_OK, nat.CRP_ERR_CAPACITY):
+                nat.check(st, "crp_search_run", a._engine._ctx)
+            counts += c
+            n_total += n
+            if st == nat.CRP_OK:  # (an arena after the cap was reached ran with cap 0: nothing to fetch)
+                qi, pos, strand, mm = s.fetch(n)
+                offs = np.asarray(a.offsets, dtype=np.int64)
+                j = np.searchsorted(offs, pos.astype(np.int64), "right") - 1
+                part = np.empty(n, SITE_DTYPE)
+                part["query"] = qi
+                part["contig"] = np.asarray(group, dtype=np.uint32)[j] if n else 0
+                part["position"] = pos.astype(np.int64) - offs[j]
+                part["strand"] = np.where(strand == 0, b"+", b"-")
+                part["mismatches"] = mm
+                parts.append(part)
+        finally:
+            s.close()
+    counts = counts.astype(np.uint32)
+    if not unlimited and n_total > int(site_cap):
+        raise SiteCapacityError(counts, n_total, int(site_cap))
+    sites = np.concatenate(parts) if parts else np.empty(0, SITE_DTYPE)
+    order = np.lexsort((sites["strand"] == b"-", sites["position"], sites["contig"], sites["query"]))
+    return SearchResult(counts, sites[order], tuple(cand))
+
+
+# ---------------------------------------------------------------- TSV
+_CODE = np.full(256, 4, dtype=np.uint8)  # 0..3 = A C G T, 4 = not a base
+for _c, _v in zip(b"ACGTUacgt", (0, 1, 2, 3, 0, 0, 1, 2, 3)):
+    _CODE[_c] = _v
+
+
+def site_string(contig, position, strand, query):
+    """The oriented window: bases upper case, mismatched positions lower case, non-base characters N (n where the
+    query compares them)."""
+    T = len(query)
+    codes = _CODE[np.frombuffer(contig[position:position + T], dtype=np.uint8)]
+    if strand in (b"-", "-"):
+        codes = np.where(codes == 4, 4, 3 - codes)[::-1]
+    out = []
+    for p, c in enumerate(codes):
+        ch = "ACGTN"[c]
+        q = query[p]
+        if q != "N" and (c == 4 or ch != q):
+            ch = ch.lower()
+        out.append(ch)
+    return "".join(out)
+
+
+def format_sites(names, queries, contig_names, contigs, sites):
+    lines = ["name\tquery\tcontig\tposition\tstrand\tmismatches\tsite\n"]
+    for s in sites:
+        q = int(s["query"])
+        k = int(s["contig"])
+        lines.append("%s\t%s\t%s\t%d\t%s\t%d\t%s\n" % (names[q], queries[q], contig_names[k], int(s["position"]),
+                                                      s["strand"].decode(), int(s["mismatches"]),
+                                                      site_string(contigs[k], int(s["position"]), s["strand"], queries[q])))
+    return "".join(lines)
+
+
+def format_counts(names, queries, counts):
+    M = counts.shape[1] - 1
+    lines = ["name\tquery\t" + "\t".join("mm%d" % k for k in range(M + 1)) + "\n"]
+    for q in range(len(queries)):
+        lines.append("%s\t%s\t%s\n" % (names[q], queries[q], "\t".join(str(int(v)) for v in counts[q])))
+    return "".join(lines)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m cropsr_amd.search",
+                                 description="Every genome site within M mismatches of each given guide, on both strands "
+                                             "(MI355X; DESIGN.md section 15).")
+    ap.add_argument("-f", "--fasta", required=True, help="genome FASTA")
+    ap.add_argument("--pattern", required=True, help="PAM pattern over ACGTRYSWKMBDHVN, e.g. NNNNNNNNNNNNNNNNNNNNNRG")
+    ap.add_argument("--guides", required=True, help="one guide per line: SEQUENCE [NAME]; '#' starts a comment")
+    ap.add_argument("--pam-length", type=int, default=None, metavar="P",
+                    help="the PAM is the pattern's last (or, for a 5' PAM, first) P letters: guides shorter than the pattern "
+                         "sit right next to it (3 for ...NGG, 6 for ...NNGRRT, 4 for TTTV...); without it a shorter guide "
+                         "must be exactly as long as the pattern's N run")
+    ap.add_argument("-m", "--mismatches", type=int, default=4, help="most mismatches reported (0..8, default 4)")
+    ap.add_argument("-o", "--output", required=True, help="sites TSV")
+    ap.add_argument("--counts", help="per-guide counts TSV (mm0..mmM)")
+    ap.add_argument("--device", type=int, default=0, help="HIP device")
+    args = ap.parse_args(argv)
+    try:
+        pattern = check_pattern(args.pattern)
+        max_mm = check_max_mm(args.mismatches)
+        if args.pam_length is not None:
+            check_pam_len(pattern, args.pam_length)
+        with open(args.guides, "rb") as f:
+            names, queries = parse_guides(f.read(), pattern, args.pam_length)
+        contig_names, contigs = read_fasta(args.fasta)
+    except (SearchInputError, OSError, UnicodeDecodeError) as e:
+        ap.error(str(e))
+    from .engine import Engine
+    with Engine(args.device) as eng:
+        g = eng.genome(contigs)
+        try:
+            res = search(g, pattern, queries, max_mm)
+        finally:
+            g.close()
+    with open(args.output, "w") as f:
+        f.write(format_sites(names, queries, contig_names, contigs, res.sites))
+    if args.counts:
+        with open(args.counts, "w") as f:
+            f.write(format_counts(names, queries, res.counts))
+    print("%d guides, %d + %d candidate sites, %d sites within %d mismatches" % (
+        len(queries), res.candidates[0], res.candidates[1], res.sites.size, max_mm), file=sys.stderr)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -565,6 +565,56 @@ int crp_offtarget_counts(crp_arena *arena, uint32_t *counts_plus, uint32_t *coun
  * to the PAM; 0xFFFFFFFF not a site, 0xFFFFFFFE a site outside own_ranges), for tests. */
 int crp_offtarget_seeds(crp_arena *arena, uint32_t *seeds_plus, uint32_t *seeds_minus);
 
+/* ---- off-target search of given guides --------------- */
+/* Every site of an arena that fits a PAM pattern, on both strands, within max_mm mismatches of each
+ * query guide (a Cas-OFFinder-style search; not reference behaviour).
+ *   pattern  T letters (1 <= T <= CRP_SEARCH_MAX_T) of ACGTRYSWKMBDHVN, either case, 5' -> 3' on the
+ *            target strand.
+ *   site     the window of T characters at forward arena start i (strand '+'), or its reverse complement
+ *            (strand '-'), inside one contig (no void character); every pattern position whose letter is
+ *            not N holds a base (acgtACGT, U read as A) of that letter's set.
+ *   query    T letters of ACGTN, either case; the mismatches at a site are the positions where the query
+ *            has a base and the oriented site does not hold that base (a non-base character always
+ *            mismatches); query N positions are not compared.
+ * A handle works on one sealed arena, which must outlive it.  Candidates (16 B each) are kept in HBM
+ * within a budget (crp_search_set_budget, default CRP_SEARCH_DEFAULT_BUDGET bytes): an arena with more
+ * candidates is processed in chunks, each run extracting them again.  Queries are compared in batches
+ * sized so that one launch stays in the tens of milliseconds (at most 2^36 pairs and 4096 queries).  Invalid input: CRP_ERR_INVALID (NULL,
+ * a letter outside the alphabet) or CRP_ERR_UNSUPPORTED (T outside 1..32, max_mm outside 0..8,
+ * 2^28 or more queries). */
+typedef struct crp_search crp_search;
+#define CRP_SEARCH_MAX_T 32
+#define CRP_SEARCH_MAX_MM 8
+#define CRP_SEARCH_DEFAULT_BUDGET (4ull << 30)
+/* Validates the pattern and counts the arena's candidates on the device (CRP_ERR_STATE: not sealed). */
+int crp_search_create(crp_arena *arena, const char *pattern, int pattern_len, crp_search **out);
+int crp_search_destroy(crp_search *search);
+/* Device bytes the candidates of one chunk may take (0 = the default; at least one workgroup's worth,
+ * 512 KiB, is always allowed).  Takes effect at the next run. */
+int crp_search_set_budget(crp_search *search, uint64_t bytes);
+/* At most batch_queries queries per compare launch (0 = the default, 4096; fewer launches than that
+ * also keep each launch within 2^36 pairs), and first_site_slots sites in the device list a run starts
+ * with (0 = the default, 2^20; a run that finds more repeats its compare once with room for all of
+ * them).  Results do not depend on either; they bound launch length and memory. */
+int crp_search_set_limits(crp_search *search, uint64_t batch_queries, uint64_t first_site_slots);
+/* Candidate sites of the arena on each strand. */
+int crp_search_candidates(const crp_search *search, uint64_t *n_plus, uint64_t *n_minus);
+/* Runs n_queries queries (n_queries * T characters, query after query).  counts (n_queries * (max_mm + 1)
+ * uint32, may be NULL) receives the sites per query with exactly k mismatches at [q * (max_mm + 1) + k];
+ * *n_sites the number of sites.  When that exceeds site_cap the counts are still exact, nothing can be
+ * fetched and the call returns CRP_ERR_CAPACITY: a run with site_cap >= *n_sites returns the full list. */
+int crp_search_run(crp_search *search, const char *queries, uint64_t n_queries, int max_mm, uint64_t site_cap,
+                   uint32_t *counts, uint64_t *n_sites);
+/* The sites of the last successful run, ordered by query, arena position, strand ('+' first): query
+ * index, forward arena start, strand (0 '+', 1 '-'), mismatches.  Any pointer may be NULL.
+ * CRP_ERR_CAPACITY when cap < the number of sites; CRP_ERR_STATE without such a run. */
+int crp_search_fetch(const crp_search *search, uint32_t *query, uint32_t *arena_pos, uint8_t *strand, uint8_t *mismatches,
+                     uint64_t cap);
+/* Measurement, accumulated since create: out[0] ms of candidate extraction (count and emit kernels),
+ * out[1] ms of compare kernels, out[2] extraction launches, out[3] compare launches, out[4] chunks of the
+ * current plan, out[5] device bytes of the candidate buffers.  n: how many of these to write (<= 6). */
+int crp_search_stats(const crp_search *search, double *out, int n);
+
 /* ---- options -------------------------------------------------------------- */
 /* CRP_OPT_TWO_PASS (value 0/1, default 0): with 0 crp_scan_score is ONE kernel launch; the
  * table offsets come from a chained scan across workgroups inside it (decoupled look-back

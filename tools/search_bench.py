@@ -1,0 +1,106 @@
+"""Times the off-target search of given guides on the 1.13 Gb switchgrass stand-in.
+
+Guides are drawn from real NGG sites of the stand-in (upper- or lower-case, 20 bases followed by NGG); its homeologous
+chromosome pairs are 3 %-substituted copies, so every guide has realistic 0..3-mismatch off-targets.  For M = 4 and the
+patterns ...NGG and ...NRG it times candidate extraction (count + emit kernels) and the compare kernels separately,
+with the library's HIP events (crp_search_stats), for Q = 64, 1 024 and 8 192 guides, and prints one JSON line.
+
+Issue floor of the compare kernel: pairs x VALU per pair / (256 CU x 128 lanes x 2.4 GHz).  VALU_PER_PAIR is read from
+the ISA of search_compare_kernel (hipcc -S --offload-arch=gfx950): the no-hit loop body is 41 VALU instructions for
+SEARCH_CPL = 8 candidates (9 v_xor_b32, 15 v_bitop3_b32, 1 v_or_b32, 8 v_bcnt_u32_b32, 8 v_cmp_le_i32).
+
+    python tools/search_bench.py [--scale 1.0] [--device 0]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import bench_workload as bw  # noqa: E402
+from cropsr_amd import Engine  # noqa: E402
+from cropsr_amd import _native as nat  # noqa: E402
+from cropsr_amd import search as srch  # noqa: E402
+
+VALU_PER_PAIR = 41 / 8
+ISSUE_RATE = 256 * 128 * 2.4e9  # lane-operations per second: 256 CUs x 4 SIMD-32 x 2.4 GHz
+PATTERNS = {"NGG": "N" * 21 + "GG", "NRG": "N" * 21 + "RG"}
+QS = (64, 1024, 8192)
+MAX_MM = 4
+
+
+def draw_guides(contigs, n, seed=3):
+    """n distinct 20-nt guides from real NGG sites ('+' strand) of the largest contigs."""
+    rng = np.random.default_rng(seed)
+    code = np.zeros(256, dtype=bool)
+    code[list(b"ACGTacgt")] = True
+    out = set()
+    big = sorted(range(len(contigs)), key=lambda k: -contigs[k].size)[:6]
+    while len(out) < n:
+        c = contigs[int(rng.choice(big))]
+        starts = rng.integers(0, c.size - 23, 4 * n)
+        for s in starts.tolist():
+            w = c[s:s + 23]
+            if code[w].all() and (w[21] | 0x20) == ord("g") and (w[22] | 0x20) == ord("g"):
+                out.add(bytes(w[:20]).upper().decode())
+                if len(out) == n:
+                    break
+    return sorted(out)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--scale", type=float, default=1.0)
+    ap.add_argument("--device", type=int, default=0)
+    args = ap.parse_args()
+    t0 = time.perf_counter()
+    wl = bw.switchgrass_like(0, args.scale)
+    contigs = [wl.bases(s) for s in wl.specs]
+    guides = draw_guides(contigs, max(QS))
+    gen_s = time.perf_counter() - t0
+    out = dict(workload=wl.name, chars=int(sum(c.size for c in contigs)), max_mm=MAX_MM, valu_per_pair=VALU_PER_PAIR,
+               generate_s=round(gen_s, 1), patterns={})
+    with Engine(args.device) as eng:
+        out["device"] = eng.device_info()["name"].strip()
+        g = eng.genome(contigs)
+        for name, pattern in PATTERNS.items():
+            queries = [srch.check_query(pattern, q, 3) for q in guides]  # 20-nt guides next to the 3-letter PAM
+            searches = [srch.ArenaSearch(a, pattern) for a in g.arenas]
+            cand = [sum(s.candidates()[k] for s in searches) for k in (0, 1)]
+            row = dict(candidates=cand[0] + cand[1], candidates_plus=cand[0], candidates_minus=cand[1], runs={})
+            for Q in QS:
+                before = [s.stats() for s in searches]
+                t = time.perf_counter()
+                n_sites = 0
+                for s in searches:
+                    st, counts, n = s.run(queries[:Q], MAX_MM, 1 << 40)
+                    nat.check(st, "crp_search_run")
+                    n_sites += n
+                wall = time.perf_counter() - t
+                after = [s.stats() for s in searches]
+                d = lambda k: sum(a[k] - b[k] for a, b in zip(after, before))
+                if Q == QS[0]:  # the count kernels ran at create, the emit kernel in this first run; later runs reuse them
+                    row["extract_ms"] = round(sum(a["extract_ms"] for a in after), 3)
+                compare_ms = d("compare_ms")
+                pairs = float(row["candidates"]) * Q
+                floor_ms = pairs * VALU_PER_PAIR / ISSUE_RATE * 1e3
+                row["runs"][str(Q)] = dict(
+                    compare_ms=round(compare_ms, 3), compare_launches=int(d("compare_launches")),
+                    pairs_per_s=pairs / (compare_ms * 1e-3), ms_per_query=round(compare_ms / Q, 5), sites=int(n_sites),
+                    run_wall_s=round(wall, 3), issue_floor_ms=round(floor_ms, 3), fraction_of_issue_floor=round(floor_ms / compare_ms, 3),
+                    gpu_ms_with_extraction=round(row["extract_ms"] + compare_ms, 3))
+            row["candidate_bytes"] = int(sum(s.stats()["candidate_bytes"] for s in searches))
+            for s in searches:
+                s.close()
+            out["patterns"][name] = row
+        g.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
