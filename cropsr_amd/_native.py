@@ -126,6 +126,9 @@ SIGNATURES = {
     "crp_search_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, u32p, u64p]),
     "crp_search_fetch": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, u8p, u8p, ctypes.c_uint64]),
     "crp_search_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
+    "crp_search_run_bulge": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, u8p,
+                                             ctypes.c_int, ctypes.c_uint64, u32p, u64p]),
+    "crp_search_fetch_bulge": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, u8p, u8p, u8p, ctypes.c_uint64]),
     "crp_configure": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]),
     "crp_query": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     "crp_build_id": (ctypes.c_char_p, []),
@@ -156,6 +159,7 @@ SCAN_PRE, SCAN_SEEDS = 1, 2
 OT_SEEDS = 1 << 24
 OT_NOT_A_SITE, OT_NOT_OWNED = 0xFFFFFFFF, 0xFFFFFFFE
 ABI_VERSION = 6
+SEARCH_BULGE_DNA, SEARCH_BULGE_RNA = 1, 2
 CRP_ERR_INVALID = -1
 CRP_ERR_NO_DEVICE = -2
 CRP_ERR_UNSUPPORTED = -7

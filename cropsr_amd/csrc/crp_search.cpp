@@ -6,6 +6,9 @@
 // run      per chunk: extraction (skipped when the one chunk of the plan is still in HBM from an earlier run), then the
 //          compare in query batches of at most kPairsPerLaunch pairs and kBatchQueries queries per launch.  The site list
 //          is copied back and sorted by (query, arena position, strand): the atomics' order never reaches the caller.
+// run_bulge the same with the bulge compare kernel, on a handle whose pattern is the window pattern of one bulge kind
+//          (Bulges).  Its launches cover at most kBulgePairsPerLaunch pairs, its site word and sort key
+//          carry the bulge's placement, and queries are limited to kMaxBulgeQueries.
 #include <algorithm>
 #include <cstring>
 #include <new>
@@ -23,6 +26,8 @@ constexpr uint64_t kMinChunk = crp::SEARCH_WORDS * 64 * 2;  // one workgroup's m
 constexpr uint64_t kMaxChunk = 1ull << 31;            // chunk-relative offsets are 32-bit
 constexpr uint64_t kSiteStart = 1ull << 20;           // device site slots of a first run (grows to what a run needs)
 constexpr uint64_t kMaxQueries = 1ull << 28;          // query index << 4 | mismatches in 32 bits
+constexpr uint64_t kBulgePairsPerLaunch = 1ull << 35;  // the bulge compare costs about twice the VALU per pair
+constexpr uint64_t kMaxBulgeQueries = 1ull << 23;     // query index << 9 | placement << 4 | mismatches in 32 bits
 
 // base set of an IUPAC letter (bit = code: A=0 T=1 C=2 G=3), 0 = not a letter of the pattern alphabet
 uint32_t iupac_set(char c)
@@ -78,7 +83,9 @@ struct crp_search {
     uint64_t sites_cap = 0;
     unsigned long long *d_ctr = nullptr;
     std::vector<uint64_t> keys;  // sites of the last successful run: query << 36 | pos << 5 | strand << 4 | mismatches
+                                 // (a bulge run: query << 41 | pos << 10 | strand << 9 | bulge_at << 4 | mismatches)
     bool have_sites = false;
+    bool keys_bulge = false;     // the last run was a bulge run
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     double ms_extract = 0, ms_compare = 0;
     uint64_t n_extract = 0, n_compare = 0;
@@ -141,7 +148,8 @@ int plan(crp_search *s)
 }
 
 // one pass over every chunk: counts and sites accumulate on the device
-int run_pass(crp_search *s, uint32_t n_queries, int max_mm, uint64_t dev_sites)
+// dna, rna: the bulge compare kernel for that bulge (both 0: the plain compare kernel)
+int run_pass(crp_search *s, uint32_t n_queries, int max_mm, uint64_t dev_sites, int dna, int rna)
 {
     crp_ctx *ctx = s->ctx;
     crp_arena *a = s->arena;
@@ -160,12 +168,18 @@ int run_pass(crp_search *s, uint32_t n_queries, int max_mm, uint64_t dev_sites)
                                                  s->chunk_first[c + 1] - s->chunk_first[c], s->d_block_off, s->cands()));
         }
         CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
-        const uint32_t batch = (uint32_t)std::max<uint64_t>(1, std::min({(uint64_t)n_queries, kPairsPerLaunch / n, s->batch_queries}));
+        const bool bulge = dna || rna;
+        const uint64_t pairs = bulge ? kBulgePairsPerLaunch : kPairsPerLaunch;
+        const uint32_t batch = (uint32_t)std::max<uint64_t>(1, std::min({(uint64_t)n_queries, pairs / n, s->batch_queries}));
         uint64_t launches = 0;
         for (uint32_t q0 = 0; q0 < n_queries; q0 += batch) {
             const uint32_t nq = std::min(batch, n_queries - q0);
-            CRP_HIP(ctx, crp::launch_search_compare(ctx->stream, s->cands(), (uint32_t)n, s->d_queries, q0, nq, max_mm, s->d_counts,
-                                                    s->d_sites, dev_sites, s->d_ctr));
+            if (bulge)
+                CRP_HIP(ctx, crp::launch_search_bulge_compare(ctx->stream, s->cands(), (uint32_t)n, s->d_queries, q0, nq, max_mm, dna, rna,
+                                                              s->d_counts, s->d_sites, dev_sites, s->d_ctr));
+            else
+                CRP_HIP(ctx, crp::launch_search_compare(ctx->stream, s->cands(), (uint32_t)n, s->d_queries, q0, nq, max_mm, s->d_counts,
+                                                        s->d_sites, dev_sites, s->d_ctr));
             ++launches;
         }
         CRP_HIP(ctx, hipEventRecord(s->ev[2], ctx->stream));
@@ -281,13 +295,14 @@ int crp_search_candidates(const crp_search *s, uint64_t *n_plus, uint64_t *n_min
     return CRP_OK;
 }
 
-int crp_search_run(crp_search *s, const char *queries, uint64_t n_queries, int max_mm, uint64_t site_cap, uint32_t *counts,
-                   uint64_t *n_sites)
+}  // extern "C"
+
+namespace {
+
+// queries (n_queries x T letters of ACGTN) -> {hi, lo, compare mask, 0} per query; false on another letter
+bool encode_queries(const char *queries, uint64_t n_queries, int T, std::vector<uint4> &enc)
 {
-    if (!s || !n_sites || (n_queries && !queries)) return CRP_ERR_INVALID;
-    if (max_mm < 0 || max_mm > CRP_SEARCH_MAX_MM || n_queries >= kMaxQueries) return CRP_ERR_UNSUPPORTED;
-    const int T = s->sets.T;
-    std::vector<uint4> enc(n_queries);
+    enc.resize(n_queries);
     for (uint64_t q = 0; q < n_queries; ++q) {
         uint32_t h = 0, l = 0, m = 0;
         for (int p = 0; p < T; ++p) {
@@ -298,7 +313,7 @@ int crp_search_run(crp_search *s, const char *queries, uint64_t n_queries, int m
                 case 'c': code = 2; break;
                 case 'g': code = 3; break;
                 case 'n': continue;
-                default: return CRP_ERR_INVALID;
+                default: return false;
             }
             h |= (code >> 1) << p;
             l |= (code & 1) << p;
@@ -306,6 +321,16 @@ int crp_search_run(crp_search *s, const char *queries, uint64_t n_queries, int m
         }
         enc[q] = make_uint4(h, l, m, 0);
     }
+    return true;
+}
+
+// the capacity protocol over encoded queries; dna, rna as in run_pass; span_first (bulge runs): per query, what
+// bulge_at counts from
+int run_encoded(crp_search *s, const std::vector<uint4> &enc, int max_mm, uint64_t site_cap, uint32_t *counts, uint64_t *n_sites,
+                int dna, int rna, const std::vector<uint8_t> &span_first)
+{
+    const uint64_t n_queries = enc.size();
+    const bool bulge = dna || rna;
     s->have_sites = false;
     s->keys.clear();
     *n_sites = 0;
@@ -327,7 +352,7 @@ int crp_search_run(crp_search *s, const char *queries, uint64_t n_queries, int m
     CRP_HIP(ctx, hipMemcpyAsync(s->d_queries, enc.data(), n_queries * sizeof(uint4), hipMemcpyHostToDevice, ctx->stream));
     unsigned long long total = 0;
     for (int pass = 0; pass < 2; ++pass) {
-        if ((rc = run_pass(s, (uint32_t)n_queries, max_mm, dev_sites)) != CRP_OK) return rc;
+        if ((rc = run_pass(s, (uint32_t)n_queries, max_mm, dev_sites, dna, rna)) != CRP_OK) return rc;
         CRP_HIP(ctx, hipMemcpy(&total, s->d_ctr, sizeof(total), hipMemcpyDeviceToHost));
         if (total <= dev_sites || total > site_cap) break;
         // more sites than the device list had room for, fewer than the caller's: once more with room for all of them
@@ -342,25 +367,78 @@ int crp_search_run(crp_search *s, const char *queries, uint64_t n_queries, int m
     if (total) CRP_HIP(ctx, hipMemcpy(raw.data(), s->d_sites, total * sizeof(uint2), hipMemcpyDeviceToHost));
     s->keys.resize(total);
     for (uint64_t k = 0; k < total; ++k) {
-        const uint64_t q = raw[k].x >> 4, mm = raw[k].x & 15, pos = raw[k].y & 0x7fffffffu, strand = raw[k].y >> 31;
-        s->keys[k] = q << 36 | pos << 5 | strand << 4 | mm;
+        const uint64_t pos = raw[k].y & 0x7fffffffu, strand = raw[k].y >> 31;
+        if (bulge) {
+            const uint64_t q = raw[k].x >> 9, at = ((raw[k].x >> 4) & 31) - span_first[q], mm = raw[k].x & 15;
+            s->keys[k] = q << 41 | pos << 10 | strand << 9 | at << 4 | mm;
+        } else {
+            const uint64_t q = raw[k].x >> 4, mm = raw[k].x & 15;
+            s->keys[k] = q << 36 | pos << 5 | strand << 4 | mm;
+        }
     }
     std::sort(s->keys.begin(), s->keys.end());
+    s->keys_bulge = bulge;
     s->have_sites = true;
     return CRP_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+int crp_search_run(crp_search *s, const char *queries, uint64_t n_queries, int max_mm, uint64_t site_cap, uint32_t *counts,
+                   uint64_t *n_sites)
+{
+    if (!s || !n_sites || (n_queries && !queries)) return CRP_ERR_INVALID;
+    if (max_mm < 0 || max_mm > CRP_SEARCH_MAX_MM || n_queries >= kMaxQueries) return CRP_ERR_UNSUPPORTED;
+    std::vector<uint4> enc;
+    if (!encode_queries(queries, n_queries, s->sets.T, enc)) return CRP_ERR_INVALID;
+    return run_encoded(s, enc, max_mm, site_cap, counts, n_sites, 0, 0, {});
+}
+
+int crp_search_run_bulge(crp_search *s, const char *queries, uint64_t n_queries, int kind, int size, const uint8_t *span, int max_mm,
+                         uint64_t site_cap, uint32_t *counts, uint64_t *n_sites)
+{
+    if (!s || !n_sites || (n_queries && (!queries || !span))) return CRP_ERR_INVALID;
+    if (kind != CRP_SEARCH_BULGE_DNA && kind != CRP_SEARCH_BULGE_RNA) return CRP_ERR_INVALID;
+    if (size < 1 || size > CRP_SEARCH_MAX_BULGE || max_mm < 0 || max_mm > CRP_SEARCH_MAX_MM || n_queries >= kMaxBulgeQueries)
+        return CRP_ERR_UNSUPPORTED;
+    const bool dna = kind == CRP_SEARCH_BULGE_DNA;
+    const int T = dna ? s->sets.T - size : s->sets.T + size;  // the query's length
+    if (T < 1 || T > CRP_SEARCH_MAX_T) return CRP_ERR_UNSUPPORTED;
+    std::vector<uint4> enc;
+    if (!encode_queries(queries, n_queries, T, enc)) return CRP_ERR_INVALID;
+    std::vector<uint8_t> span_first(n_queries);
+    for (uint64_t q = 0; q < n_queries; ++q) {
+        const int first = span[2 * q], last = span[2 * q + 1];
+        // placements: first < s <= last (DNA), first < s and s + size - 1 < last (RNA)
+        const int s_min = first + 1, s_max = dna ? last : last - size;
+        if (last >= T || s_min > s_max) return CRP_ERR_INVALID;
+        enc[q].w = (uint32_t)s_min | (uint32_t)s_max << 8;
+        span_first[q] = (uint8_t)first;
+    }
+    return run_encoded(s, enc, max_mm, site_cap, counts, n_sites, dna ? size : 0, dna ? 0 : size, span_first);
+}
+
 int crp_search_fetch(const crp_search *s, uint32_t *query, uint32_t *arena_pos, uint8_t *strand, uint8_t *mismatches, uint64_t cap)
+{
+    return crp_search_fetch_bulge(s, query, arena_pos, strand, mismatches, nullptr, cap);
+}
+
+int crp_search_fetch_bulge(const crp_search *s, uint32_t *query, uint32_t *arena_pos, uint8_t *strand, uint8_t *mismatches,
+                           uint8_t *bulge_at, uint64_t cap)
 {
     if (!s) return CRP_ERR_INVALID;
     if (!s->have_sites) return CRP_ERR_STATE;
     if (cap < s->keys.size()) return CRP_ERR_CAPACITY;
+    const int sh = s->keys_bulge ? 5 : 0;  // a bulge key has the 5-bit placement between strand and mismatches
     for (uint64_t k = 0; k < s->keys.size(); ++k) {
         const uint64_t key = s->keys[k];
-        if (query) query[k] = (uint32_t)(key >> 36);
-        if (arena_pos) arena_pos[k] = (uint32_t)(key >> 5) & 0x7fffffffu;
-        if (strand) strand[k] = (uint8_t)((key >> 4) & 1);
+        if (query) query[k] = (uint32_t)(key >> (36 + sh));
+        if (arena_pos) arena_pos[k] = (uint32_t)(key >> (5 + sh)) & 0x7fffffffu;
+        if (strand) strand[k] = (uint8_t)((key >> (4 + sh)) & 1);
         if (mismatches) mismatches[k] = (uint8_t)(key & 15);
+        if (bulge_at) bulge_at[k] = (uint8_t)(sh ? (key >> 4) & 31 : 0);
     }
     return CRP_OK;
 }

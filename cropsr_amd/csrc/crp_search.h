@@ -38,5 +38,13 @@ hipError_t launch_search_emit(hipStream_t s, const Planes &pl, uint64_t used_wor
 // counted in *site_ctr, not written).
 hipError_t launch_search_compare(hipStream_t s, const SearchCands &c, uint32_t n, const uint4 *queries, uint32_t q0, uint32_t nq,
                                  int max_mm, uint32_t *counts, uint2 *sites, uint64_t site_cap, unsigned long long *site_ctr);
+// The same for the windows of one bulge kind (Bulges): candidates of T + dna or T - rna characters
+// (one of dna, rna is 0, the other 1 or 2), queries of T letters as {hi, lo, compare mask, s_min | s_max << 8} (the
+// placements s of the bulge's first query position).  Every pair whose fewest mismatches over s is within max_mm adds
+// one to counts[q * (max_mm + 1) + mm] and appends {q << 9 | s << 4 | mm, pos}, s the smallest placement with mm
+// (q < 2^23).
+hipError_t launch_search_bulge_compare(hipStream_t s, const SearchCands &c, uint32_t n, const uint4 *queries, uint32_t q0, uint32_t nq,
+                                       int max_mm, int dna, int rna, uint32_t *counts, uint2 *sites, uint64_t site_cap,
+                                       unsigned long long *site_ctr);
 
 }  // namespace crp

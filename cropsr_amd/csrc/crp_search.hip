@@ -13,7 +13,8 @@
 //               with `lo` flipped for '-').
 //   compare     candidates in registers, SEARCH_CPL per lane; the queries of a batch are wave-uniform (scalar loads).
 //               Per pair: popc(((h ^ qh) | (l ^ ql) | nb) & qm) <= M.  Hits are rare: a wave ballots them and reserves
-//               its slots with one atomic.
+//               its slots with one atomic.  The bulge compare (DNA or RNA bulge of one size) takes, per pair, the best
+//               placement of the bulge inside the query's span; see search_bulge_compare_kernel.
 //
 // Only vector stores and vector atomics, like the rest of the library.
 #include "crp_search.h"
@@ -203,6 +204,92 @@ __global__ __launch_bounds__(BLOCK) void search_compare_kernel(SearchCands c, ui
     }
 }
 
+// (x ^ q) | y in one v_bitop3_b32 (truth table over x, q, y = 0xF0, 0xCC, 0xAA): the compiler leaves it as xor + or3
+__device__ __forceinline__ uint32_t xor_or(uint32_t x, uint32_t q, uint32_t y) { return __builtin_amdgcn_bitop3_b32(x, q, y, 0xBE); }
+
+// mismatch mask of a window's fields against a query's, over the window's positions
+__device__ __forceinline__ uint32_t mism(uint32_t h, uint32_t l, uint32_t nb, uint32_t qh, uint32_t ql) { return xor_or(h, qh, xor_or(l, ql, nb)); }
+
+// Bulge compare (Bulges).  Candidates are the windows of one bulge kind: T + d characters for a DNA
+// bulge of d, T - r for an RNA bulge of r, T the query length.  Per pair two mismatch masks over the query positions:
+// m0 against the window as it is (query i with window i) and m1 against the window moved by the bulge (query i with
+// window i + d, or i - r): the shifted fields h1, l1, nb1 are formed once per candidate.  For a placement s,
+//   mm(s) = popc(m0 & lo(s)) + popc(m1 & ~lo(s + r))      (r = 0 for a DNA bulge; bits s .. s + r - 1 are unpaired)
+// with s in [s_min, s_max], the query's split limits.  a = m0 below s_max, m1 above, and b = m0 below s_min, m1
+// above, give mm(s) = popc(a & lo(s)) + popc(b & ~lo(s + r)) for every such s, and every bit of a & b is counted in
+// mm(s) unless it is one of the r unpaired ones: popc(a & b & qm) - r <= mm(s).  Pairs pass that bound rarely at small
+// M; only a wave with a survivor scans s (wave-uniform bounds) for the minimum and the smallest s that reaches it.
+__global__ __launch_bounds__(BLOCK) void search_bulge_compare_kernel(SearchCands c, uint32_t n, const uint4 *__restrict__ queries,
+                                                                     uint32_t q0, uint32_t nq, int max_mm, int dna, int rna,
+                                                                     uint32_t *__restrict__ counts, uint2 *__restrict__ sites,
+                                                                     uint64_t site_cap, unsigned long long *__restrict__ site_ctr)
+{
+    const uint32_t first = blockIdx.x * (BLOCK * SEARCH_CPL) + threadIdx.x;
+    uint32_t h[SEARCH_CPL], l[SEARCH_CPL], nb[SEARCH_CPL], h1[SEARCH_CPL], l1[SEARCH_CPL], nb1[SEARCH_CPL];
+    int lim[SEARCH_CPL];  // max_mm + r, or -1 past the end
+#pragma unroll
+    for (int j = 0; j < SEARCH_CPL; ++j) {
+        const uint32_t i = first + j * BLOCK;
+        const bool ok = i < n;
+        h[j] = ok ? c.hi[i] : 0u;
+        l[j] = ok ? c.lo[i] : 0u;
+        nb[j] = ok ? c.nb[i] : 0u;
+        h1[j] = (h[j] >> dna) << rna;  // (one of dna, rna is 0)
+        l1[j] = (l[j] >> dna) << rna;
+        nb1[j] = (nb[j] >> dna) << rna;
+        lim[j] = ok ? max_mm + rna : -1;
+    }
+    const uint32_t stride = (uint32_t)max_mm + 1;
+    for (uint32_t qi = q0; qi < q0 + nq; ++qi) {
+        const uint4 q = queries[qi];  // wave-uniform: {hi, lo, compare mask, s_min | s_max << 8}
+        const int s_min = (int)(q.w & 255u), s_max = (int)((q.w >> 8) & 255u);
+        const uint32_t la = (1u << s_max) - 1u, lb = (1u << s_min) - 1u;
+        int bound[SEARCH_CPL];
+        bool any = false;
+#pragma unroll
+        for (int j = 0; j < SEARCH_CPL; ++j) {
+            const uint32_t m0 = mism(h[j], l[j], nb[j], q.x, q.y), m1 = mism(h1[j], l1[j], nb1[j], q.x, q.y);
+            const uint32_t a = (m0 & la) | (m1 & ~la), b = (m0 & lb) | (m1 & ~lb);
+            bound[j] = __popc(a & b & q.z);
+            any |= bound[j] <= lim[j];
+        }
+        if (__builtin_expect(any, 0)) {
+#pragma unroll
+            for (int j = 0; j < SEARCH_CPL; ++j) {
+                const bool cand = bound[j] <= lim[j];
+                if (!__ballot(cand)) continue;
+                int best = SEARCH_MAX_T + 1, at = s_min;
+                if (cand) {
+                    const uint32_t m0 = mism(h[j], l[j], nb[j], q.x, q.y), m1 = mism(h1[j], l1[j], nb1[j], q.x, q.y);
+                    const uint32_t a = ((m0 & la) | (m1 & ~la)) & q.z, b = ((m0 & lb) | (m1 & ~lb)) & q.z;
+                    int mm = __popc(a & lb) + __popc(b & ~((1u << (s_min + rna)) - 1u));
+                    best = mm;
+                    for (int s = s_min; s < s_max; ++s) {  // mm(s + 1) - mm(s) = a_s - b_(s + r)
+                        mm += (int)((a >> s) & 1u) - (int)((b >> (s + rna)) & 1u);
+                        if (mm < best) {
+                            best = mm;
+                            at = s + 1;
+                        }
+                    }
+                }
+                const bool hit = cand && best <= max_mm;
+                const uint64_t bal = __ballot(hit);
+                if (!bal) continue;
+                const int leader = __builtin_ctzll(bal);
+                unsigned long long slot = 0;
+                if ((int)(threadIdx.x & 63) == leader) slot = atomicAdd(site_ctr, (unsigned long long)__popcll(bal));
+                slot = __shfl(slot, leader);
+                if (hit) {
+                    slot += lane_rank(bal);
+                    atomicAdd(&counts[(uint64_t)qi * stride + best], 1u);
+                    if (slot < site_cap)
+                        sites[slot] = make_uint2(qi << 9 | (uint32_t)at << 4 | (uint32_t)best, c.pos[first + j * BLOCK]);
+                }
+            }
+        }
+    }
+}
+
 }  // namespace
 
 hipError_t launch_search_count(hipStream_t s, const Planes &pl, uint64_t used_words, const SearchSets &sets, uint2 *block_cnt)
@@ -227,6 +314,17 @@ hipError_t launch_search_compare(hipStream_t s, const SearchCands &c, uint32_t n
     if (!n || !nq) return hipSuccess;
     const uint32_t blocks = (uint32_t)(((uint64_t)n + BLOCK * SEARCH_CPL - 1) / (BLOCK * SEARCH_CPL));
     search_compare_kernel<<<dim3(blocks), dim3(BLOCK), 0, s>>>(c, n, queries, q0, nq, max_mm, counts, sites, site_cap, site_ctr);
+    return hipGetLastError();
+}
+
+hipError_t launch_search_bulge_compare(hipStream_t s, const SearchCands &c, uint32_t n, const uint4 *queries, uint32_t q0, uint32_t nq,
+                                       int max_mm, int dna, int rna, uint32_t *counts, uint2 *sites, uint64_t site_cap,
+                                       unsigned long long *site_ctr)
+{
+    if (!n || !nq) return hipSuccess;
+    const uint32_t blocks = (uint32_t)(((uint64_t)n + BLOCK * SEARCH_CPL - 1) / (BLOCK * SEARCH_CPL));
+    search_bulge_compare_kernel<<<dim3(blocks), dim3(BLOCK), 0, s>>>(c, n, queries, q0, nq, max_mm, dna, rna, counts, sites, site_cap,
+                                                                     site_ctr);
     return hipGetLastError();
 }
 

@@ -757,6 +757,12 @@ class Genome:
         from . import search
         return search.search(self, pattern, queries, max_mm, site_cap=site_cap, budget=budget, pam_len=pam_len)
 
+    def search_bulges(self, pattern, queries, max_mm, pam_len, dna_bulge, rna_bulge, site_cap=None, budget=None):
+        """search() plus the sites with a DNA or RNA bulge (search.search_bulges).  Returns search.BulgeSearchResult
+        (.counts (Q, kinds, M + 1), .sites with kind, bulge_size and bulge_at, .kinds)."""
+        from . import search
+        return search.search_bulges(self, pattern, queries, max_mm, pam_len, dna_bulge, rna_bulge, site_cap=site_cap, budget=budget)
+
     def close(self):
         for a in self.arenas:
             a.close()

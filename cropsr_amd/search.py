@@ -18,6 +18,21 @@ Definition (what the tests check):
            hold it (a non-base always mismatches); N positions are not compared
   result   the sites with <= M (0..8) mismatches, ordered by query, contig, position, strand ('+' first), and
            counts[q, k] = sites of query q with exactly k mismatches
+
+Bulges (search_bulges, --dna-bulge / --rna-bulge; DESIGN.md section 15, Bulges).  They need the PAM's length P: the
+guide region is the T - P positions outside the PAM (all N in the pattern), on its 5' side (...NGG) or 3' side (TTTV...).
+  span     a query's first to last ACGT letter inside the guide region; a bulge lies strictly inside it, starting
+           at query position s
+  DNA d    (1 <= d <= D) the site is an oriented window of T + d characters that fits the pattern with d more N in
+           its guide region; query position i pairs with window position i if i < s, else i + d, for
+           span_first < s <= span_last; window positions s .. s + d - 1 stay unpaired
+  RNA r    (1 <= r <= R) the window has T - r characters (r fewer N); query positions s .. s + r - 1 stay unpaired,
+           span_first < s and s + r - 1 < span_last; i < s pairs with i, i >= s + r with i - r
+  result   mismatches over the paired positions, by the rule above; one result per (query, kind, contig,
+           position, strand), kinds none, DNA 1..D, RNA 1..R, with the fewest mismatches over s (<= M) and
+           bulge_at = s - span_first for the smallest s that reaches them; ordered by query, kind, contig, position,
+           strand.  No merging across kinds.  D, R in 0..2 and T + D <= 32; a span too short for a bulge (DNA: 2
+           letters, RNA: r + 2) is refused
 """
 import argparse
 import ctypes
@@ -31,6 +46,9 @@ MAX_T = 32
 MAX_MM = 8
 IUPAC = "ACGTRYSWKMBDHVN"
 SITE_DTYPE = np.dtype([("query", "<u4"), ("contig", "<u4"), ("position", "<i8"), ("strand", "S1"), ("mismatches", "u1")])
+MAX_BULGE = 2
+BULGE_SITE_DTYPE = np.dtype([("query", "<u4"), ("kind", "u1"), ("bulge_size", "u1"), ("bulge_at", "u1"), ("contig", "<u4"),
+                             ("position", "<i8"), ("strand", "S1"), ("mismatches", "u1")])
 _WS = b" \t\n\r\x0b\x0c"
 
 
@@ -204,6 +222,26 @@ class ArenaSearch:
                   "crp_search_fetch")
         return cols
 
+    def run_bulge(self, queries, bulge, size, spans, max_mm, site_cap):
+        """crp_search_run_bulge as it is (this handle's pattern: the kind's window pattern).  bulge "DNA" / "RNA";
+        spans: (Q, 2) query positions of each span's first and last letter."""
+        Q = len(queries)
+        blob = "".join(queries).encode()
+        sp = np.ascontiguousarray(spans, dtype=np.uint8).reshape(Q, 2)
+        counts = np.zeros((Q, max_mm + 1), dtype=np.uint32)
+        n = ctypes.c_uint64()
+        kind = nat.SEARCH_BULGE_DNA if bulge == "DNA" else nat.SEARCH_BULGE_RNA
+        st = nat.lib().crp_search_run_bulge(self._h, blob, Q, kind, int(size), sp.ctypes.data_as(nat.u8p), int(max_mm), int(site_cap),
+                                            counts.ctypes.data_as(nat.u32p), ctypes.byref(n))
+        return st, counts, n.value
+
+    def fetch_bulge(self, n):
+        """(query u32, arena position u32, strand u8, mismatches u8, bulge_at u8) of the last run's n sites."""
+        cols = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, np.uint8), np.empty(n, np.uint8), np.empty(n, np.uint8)
+        ptrs = (nat.u32p, nat.u32p, nat.u8p, nat.u8p, nat.u8p)
+        nat.check(nat.lib().crp_search_fetch_bulge(self._h, *[c.ctypes.data_as(p) for c, p in zip(cols, ptrs)], n), "crp_search_fetch_bulge")
+        return cols
+
     def stats(self):
         out = np.zeros(6, dtype=np.float64)
         nat.check(nat.lib().crp_search_stats(self._h, out.ctypes.data_as(nat.f64p), 6), "crp_search_stats")
@@ -264,6 +302,127 @@ def search(genome, pattern, queries, max_mm, site_cap=None, budget=None, pam_len
     return SearchResult(counts, sites[order], tuple(cand))
 
 
+# ---------------------------------------------------------------- bulges
+def check_bulges(pattern, pam_len, dna_bulge, rna_bulge):
+    """(D, R) of a bulge search: each 0..2, the PAM's length given when either is not 0, T + D <= 32."""
+    for v, what in ((dna_bulge, "DNA"), (rna_bulge, "RNA")):
+        if not isinstance(v, (int, np.integer)) or not 0 <= int(v) <= MAX_BULGE:
+            raise SearchInputError("%s bulge size must be an integer 0..%d, not %r" % (what, MAX_BULGE, v))
+    D, R = int(dna_bulge), int(rna_bulge)
+    if D or R:
+        if pam_len is None:
+            raise SearchInputError("a bulge search needs the PAM's length (--pam-length)")
+        guide_region(pattern, pam_len)
+    if len(pattern) + D > MAX_T:
+        raise SearchInputError("a DNA bulge of %d needs windows of %d letters: at most %d" % (D, len(pattern) + D, MAX_T))
+    return D, R
+
+
+def guide_region(pattern, pam_len):
+    """(lo, hi, pam_3prime): the pattern positions [lo, hi) outside the PAM, all N; which side the PAM is on."""
+    T = len(pattern)
+    P = check_pam_len(pattern, pam_len)
+    if set(pattern[:T - P]) <= {"N"}:
+        return 0, T - P, True
+    if set(pattern[P:]) <= {"N"}:
+        return P, T, False
+    raise SearchInputError("pattern %s has letters other than N outside its first or last %d" % (pattern, P))
+
+
+def bulge_kinds(D, R):
+    """[(bulge, size)] in result order: ("-", 0), ("DNA", 1..D), ("RNA", 1..R)."""
+    return [("-", 0)] + [("DNA", d) for d in range(1, D + 1)] + [("RNA", r) for r in range(1, R + 1)]
+
+
+def kind_pattern(pattern, pam_len, bulge, size):
+    """The window pattern of one kind: the guide region's N run longer by a DNA bulge, shorter by an RNA bulge."""
+    lo, hi, pam3 = guide_region(pattern, pam_len)
+    n = hi - lo + (size if bulge == "DNA" else -size if bulge == "RNA" else 0)
+    return "N" * n + pattern[hi:] if pam3 else pattern[:lo] + "N" * n
+
+
+def query_spans(pattern, pam_len, queries, D, R):
+    """(Q, 2) uint8: each query's span (first, last ACGT position in the guide region); refuses a span too short."""
+    lo, hi, _ = guide_region(pattern, pam_len)
+    need = max(2 if D else 0, R + 2 if R else 0)
+    out = np.zeros((len(queries), 2), dtype=np.uint8)
+    for k, q in enumerate(queries):
+        idx = [i for i in range(lo, hi) if q[i] in "ACGT"]
+        if len(idx) == 0 or idx[-1] - idx[0] + 1 < need:
+            raise SearchInputError("guide %r: its span of %d letters is too short for the bulge (at least %d)" % (
+                q, idx[-1] - idx[0] + 1 if idx else 0, need))
+        out[k] = idx[0], idx[-1]
+    return out
+
+
+class BulgeSearchResult:
+    def __init__(self, counts, sites, kinds, spans, candidates):
+        self.counts = counts          # (Q, kinds, M + 1) uint32
+        self.sites = sites            # BULGE_SITE_DTYPE, ordered by query, kind, contig, position, strand
+        self.kinds = kinds            # [(bulge, size)]: kind k of .counts and .sites
+        self.spans = spans            # (Q, 2) uint8: each query's span (bulge_at counts from its first letter)
+        self.candidates = candidates  # per kind: (n_plus, n_minus) over the whole genome
+
+
+def search_bulges(genome, pattern, queries, max_mm, pam_len, dna_bulge, rna_bulge, site_cap=None, budget=None):
+    """search() plus every site with a DNA bulge of 1..dna_bulge or an RNA bulge of 1..rna_bulge (see the module's
+    docstring), over all arenas of `genome`: one library handle per kind and arena, on the kind's window pattern.
+    The kind-none slice is what search() returns.  site_cap counts the sites of all kinds together."""
+    pattern = check_pattern(pattern)
+    max_mm = check_max_mm(max_mm)
+    D, R = check_bulges(pattern, pam_len, dna_bulge, rna_bulge)
+    queries = [check_query(pattern, q, pam_len) for q in queries]
+    if any(len(q) != len(pattern) for q in queries):
+        raise SearchInputError("every query needs %d letters" % len(pattern))
+    spans = query_spans(pattern, pam_len, queries, D, R) if D or R else np.zeros((len(queries), 2), np.uint8)
+    kinds = bulge_kinds(D, R)
+    Q = len(queries)
+    counts = np.zeros((Q, len(kinds), max_mm + 1), dtype=np.uint64)
+    parts, n_total, cands = [], 0, []
+    unlimited = site_cap is None
+    for k, (bulge, size) in enumerate(kinds):
+        kp = kind_pattern(pattern, pam_len, bulge, size) if size else pattern
+        cand = [0, 0]
+        for a, group in zip(genome.arenas, genome.groups):
+            s = ArenaSearch(a, kp, budget)
+            try:
+                npl, nmi = s.candidates()
+                cand[0] += npl
+                cand[1] += nmi
+                cap = (1 << 62) if unlimited else max(0, int(site_cap) - n_total)
+                if size:
+                    st, c, n = s.run_bulge(queries, bulge, size, spans, max_mm, cap)
+                else:
+                    st, c, n = s.run(queries, max_mm, cap)
+                if st not in (nat.CRP_OK, nat.CRP_ERR_CAPACITY):
+                    nat.check(st, "crp_search_run_bulge" if size else "crp_search_run", a._engine._ctx)
+                counts[:, k] += c
+                n_total += n
+                if st == nat.CRP_OK:
+                    qi, pos, strand, mm, at = s.fetch_bulge(n)
+                    offs = np.asarray(a.offsets, dtype=np.int64)
+                    j = np.searchsorted(offs, pos.astype(np.int64), "right") - 1
+                    part = np.empty(n, BULGE_SITE_DTYPE)
+                    part["query"] = qi
+                    part["kind"] = k
+                    part["bulge_size"] = size
+                    part["bulge_at"] = at
+                    part["contig"] = np.asarray(group, dtype=np.uint32)[j] if n else 0
+                    part["position"] = pos.astype(np.int64) - offs[j]
+                    part["strand"] = np.where(strand == 0, b"+", b"-")
+                    part["mismatches"] = mm
+                    parts.append(part)
+            finally:
+                s.close()
+        cands.append(tuple(cand))
+    counts = counts.astype(np.uint32)
+    if not unlimited and n_total > int(site_cap):
+        raise SiteCapacityError(counts, n_total, int(site_cap))
+    sites = np.concatenate(parts) if parts else np.empty(0, BULGE_SITE_DTYPE)
+    order = np.lexsort((sites["strand"] == b"-", sites["position"], sites["contig"], sites["kind"], sites["query"]))
+    return BulgeSearchResult(counts, sites[order], kinds, spans, cands)
+
+
 # ---------------------------------------------------------------- TSV
 _CODE = np.full(256, 4, dtype=np.uint8)  # 0..3 = A C G T, 4 = not a base
 for _c, _v in zip(b"ACGTUacgt", (0, 1, 2, 3, 0, 0, 1, 2, 3)):
@@ -298,6 +457,55 @@ def format_sites(names, queries, contig_names, contigs, sites):
     return "".join(lines)
 
 
+def bulge_alignment(contig, position, strand, query, bulge, size, s):
+    """(site, query_aligned) of a site of one kind with its bulge at query position s: the oriented window with '-'
+    at RNA-bulge positions (case as site_string: paired mismatches in lower case; unpaired DNA-bulge characters upper
+    case), and the query with '-' at DNA-bulge positions."""
+    T = len(query)
+    W = T + size if bulge == "DNA" else T - size if bulge == "RNA" else T
+    codes = _CODE[np.frombuffer(contig[position:position + W], dtype=np.uint8)]
+    if strand in (b"-", "-"):
+        codes = np.where(codes == 4, 4, 3 - codes)[::-1]
+    win = ["ACGTN"[c] for c in codes]
+
+    def paired(ch, q):
+        return ch.lower() if q != "N" and ch != q else ch
+
+    if bulge == "DNA":
+        site = [ch if s <= p < s + size else paired(ch, query[p if p < s else p - size]) for p, ch in enumerate(win)]
+        return "".join(site), query[:s] + "-" * size + query[s:]
+    if bulge == "RNA":
+        site = [paired(win[i], query[i]) for i in range(s)] + ["-"] * size + \
+               [paired(win[i - size], query[i]) for i in range(s + size, T)]
+        return "".join(site), query
+    return "".join(paired(ch, query[p]) for p, ch in enumerate(win)), query
+
+
+def format_bulge_sites(names, queries, contig_names, contigs, res):
+    """The sites TSV of a bulge search (BulgeSearchResult): today's columns plus bulge (-, DNA, RNA), bulge_size,
+    bulge_at, and the aligned site and query."""
+    lines = ["name\tquery\tcontig\tposition\tstrand\tmismatches\tbulge\tbulge_size\tbulge_at\tsite\tquery_aligned\n"]
+    for r in res.sites:
+        q, k, kind = int(r["query"]), int(r["contig"]), int(r["kind"])
+        bulge, size = res.kinds[kind]
+        at = int(r["bulge_at"])
+        site, qa = bulge_alignment(contigs[k], int(r["position"]), r["strand"], queries[q], bulge, size,
+                                   int(res.spans[q, 0]) + at)
+        lines.append("%s\t%s\t%s\t%d\t%s\t%d\t%s\t%d\t%d\t%s\t%s\n" % (
+            names[q], queries[q], contig_names[k], int(r["position"]), r["strand"].decode(), int(r["mismatches"]),
+            bulge, size, at, site, qa))
+    return "".join(lines)
+
+
+def format_bulge_counts(names, queries, kinds, counts):
+    M = counts.shape[2] - 1
+    lines = ["name\tquery\tbulge\tbulge_size\t" + "\t".join("mm%d" % k for k in range(M + 1)) + "\n"]
+    for q in range(len(queries)):
+        for k, (bulge, size) in enumerate(kinds):
+            lines.append("%s\t%s\t%s\t%d\t%s\n" % (names[q], queries[q], bulge, size, "\t".join(str(int(v)) for v in counts[q, k])))
+    return "".join(lines)
+
+
 def format_counts(names, queries, counts):
     M = counts.shape[1] - 1
     lines = ["name\tquery\t" + "\t".join("mm%d" % k for k in range(M + 1)) + "\n"]
@@ -319,7 +527,13 @@ def main(argv=None):
                          "must be exactly as long as the pattern's N run")
     ap.add_argument("-m", "--mismatches", type=int, default=4, help="most mismatches reported (0..8, default 4)")
     ap.add_argument("-o", "--output", required=True, help="sites TSV")
-    ap.add_argument("--counts", help="per-guide counts TSV (mm0..mmM)")
+    ap.add_argument("--dna-bulge", type=int, default=0, metavar="D",
+                    help="also report sites with a DNA bulge (extra genomic bases) of 1..D (0..2, default 0); needs "
+                         "--pam-length; adds the columns bulge, bulge_size, bulge_at, query_aligned")
+    ap.add_argument("--rna-bulge", type=int, default=0, metavar="R",
+                    help="also report sites with an RNA bulge (unpaired guide letters) of 1..R (0..2, default 0); needs "
+                         "--pam-length")
+    ap.add_argument("--counts", help="per-guide counts TSV (mm0..mmM; with bulges one line per guide and kind)")
     ap.add_argument("--device", type=int, default=0, help="HIP device")
     args = ap.parse_args(argv)
     try:
@@ -327,8 +541,11 @@ def main(argv=None):
         max_mm = check_max_mm(args.mismatches)
         if args.pam_length is not None:
             check_pam_len(pattern, args.pam_length)
+        D, R = check_bulges(pattern, args.pam_length, args.dna_bulge, args.rna_bulge)
         with open(args.guides, "rb") as f:
             names, queries = parse_guides(f.read(), pattern, args.pam_length)
+        if D or R:
+            query_spans(pattern, args.pam_length, queries, D, R)
         contig_names, contigs = read_fasta(args.fasta)
     except (SearchInputError, OSError, UnicodeDecodeError) as e:
         ap.error(str(e))
@@ -336,9 +553,21 @@ def main(argv=None):
     with Engine(args.device) as eng:
         g = eng.genome(contigs)
         try:
-            res = search(g, pattern, queries, max_mm)
+            if D or R:
+                res = search_bulges(g, pattern, queries, max_mm, args.pam_length, D, R)
+            else:
+                res = search(g, pattern, queries, max_mm)
         finally:
             g.close()
+    if D or R:
+        with open(args.output, "w") as f:
+            f.write(format_bulge_sites(names, queries, contig_names, contigs, res))
+        if args.counts:
+            with open(args.counts, "w") as f:
+                f.write(format_bulge_counts(names, queries, res.kinds, res.counts))
+        print("%d guides, %d kinds, %d sites within %d mismatches" % (len(queries), len(res.kinds), res.sites.size, max_mm),
+              file=sys.stderr)
+        return 0
     with open(args.output, "w") as f:
         f.write(format_sites(names, queries, contig_names, contigs, res.sites))
     if args.counts:

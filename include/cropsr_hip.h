@@ -610,6 +610,29 @@ int crp_search_run(crp_search *search, const char *queries, uint64_t n_queries, 
  * CRP_ERR_CAPACITY when cap < the number of sites; CRP_ERR_STATE without such a run. */
 int crp_search_fetch(const crp_search *search, uint32_t *query, uint32_t *arena_pos, uint8_t *strand, uint8_t *mismatches,
                      uint64_t cap);
+/* Bulges (Bulges).  A DNA bulge of d is d genomic bases that stay unpaired, an RNA
+ * bulge of r is r query letters with no genomic partner.  The handle's pattern is the window pattern of one
+ * bulge kind: T + d letters (DNA) or T - r (RNA) for queries of T letters, i.e. the query's pattern with d more
+ * (r fewer) N in its guide region.  span: 2 bytes per query, the query positions of the first and last base of
+ * its span (the guide region's first to last ACGT letter).  A placement s is the query position where the
+ * bulge starts: span_first < s <= span_last (DNA), span_first < s and s + r - 1 < span_last (RNA).  Query
+ * position i pairs with window position i when i < s, else with i + d (DNA) or i - r (RNA; positions s ..
+ * s + r - 1 pair with nothing); mismatches count over the paired positions as in crp_search_run.  Each site
+ * keeps its fewest mismatches over s, reported when <= max_mm, with bulge_at = s - span_first for the smallest
+ * s that reaches them. */
+#define CRP_SEARCH_BULGE_DNA 1
+#define CRP_SEARCH_BULGE_RNA 2
+#define CRP_SEARCH_MAX_BULGE 2
+/* crp_search_run for one bulge kind (kind CRP_SEARCH_BULGE_DNA / _RNA, size 1..CRP_SEARCH_MAX_BULGE):
+ * n_queries queries of T letters (T = the pattern's length - size for DNA, + size for RNA, at most 32), counts
+ * and the capacity protocol as there.  One site per (query, position, strand).  Fewer than 2^23 queries (the
+ * site word also carries the placement).  CRP_ERR_INVALID: a span without a placement or past the query;
+ * CRP_ERR_UNSUPPORTED: kind size, max_mm, T or n_queries out of range.  Launches cover at most 2^35 pairs. */
+int crp_search_run_bulge(crp_search *search, const char *queries, uint64_t n_queries, int kind, int size, const uint8_t *span,
+                         int max_mm, uint64_t site_cap, uint32_t *counts, uint64_t *n_sites);
+/* crp_search_fetch plus bulge_at (0 after a crp_search_run); order: query, arena position, strand. */
+int crp_search_fetch_bulge(const crp_search *search, uint32_t *query, uint32_t *arena_pos, uint8_t *strand, uint8_t *mismatches,
+                           uint8_t *bulge_at, uint64_t cap);
 /* Measurement, accumulated since create: out[0] ms of candidate extraction (count and emit kernels),
  * out[1] ms of compare kernels, out[2] extraction launches, out[3] compare launches, out[4] chunks of the
  * current plan, out[5] device bytes of the candidate buffers.  n: how many of these to write (<= 6). */

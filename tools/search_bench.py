@@ -10,6 +10,13 @@ the ISA of search_compare_kernel (hipcc -S --offload-arch=gfx950): the no-hit lo
 SEARCH_CPL = 8 candidates (9 v_xor_b32, 15 v_bitop3_b32, 1 v_or_b32, 8 v_bcnt_u32_b32, 8 v_cmp_le_i32).
 
     python tools/search_bench.py [--scale 1.0] [--device 0]
+
+--bulge D,R times the search with bulges instead (Bulges): 1 024 of the same guides against ...NGG
+at M = 4, per kind (none, DNA 1..D, RNA 1..R) the extraction and compare times of its own handles, ms per query, the
+fraction of the issue floor, and the compare time of the expansion path for the same queries (every query expanded per
+bulge placement and run through the no-bulge compare kernel on the same candidates).  BULGE_VALU_PER_PAIR is read from
+the ISA of search_bulge_compare_kernel: its no-hit loop body is 72 VALU instructions for 8 candidates (40 v_bitop3_b32,
+16 v_bfi_b32, 8 v_bcnt_u32_b32, 8 v_cmp_le_i32).
 """
 import argparse
 import json
@@ -28,6 +35,8 @@ from cropsr_amd import _native as nat  # noqa: E402
 from cropsr_amd import search as srch  # noqa: E402
 
 VALU_PER_PAIR = 41 / 8
+BULGE_VALU_PER_PAIR = 72 / 8
+BULGE_Q = 1024
 ISSUE_RATE = 256 * 128 * 2.4e9  # lane-operations per second: 256 CUs x 4 SIMD-32 x 2.4 GHz
 PATTERNS = {"NGG": "N" * 21 + "GG", "NRG": "N" * 21 + "RG"}
 QS = (64, 1024, 8192)
@@ -53,16 +62,74 @@ def draw_guides(contigs, n, seed=3):
     return sorted(out)
 
 
+def bulge_main(args, contigs, guides, out):
+    D, R = (int(v) for v in args.bulge.split(","))
+    pattern, P = PATTERNS["NGG"], 3
+    queries = [srch.check_query(pattern, q, P) for q in guides[:BULGE_Q]]
+    spans = srch.query_spans(pattern, P, queries, D, R)
+    out.update(bulge_valu_per_pair=BULGE_VALU_PER_PAIR, queries=len(queries), dna_bulge=D, rna_bulge=R, pattern="NGG", kinds={})
+    total = 0.0
+    with Engine(args.device) as eng:
+        out["device"] = eng.device_info()["name"].strip()
+        g = eng.genome(contigs)
+        for bulge, size in srch.bulge_kinds(D, R):
+            kp = srch.kind_pattern(pattern, P, bulge, size)
+            searches = [srch.ArenaSearch(a, kp) for a in g.arenas]
+            cand = sum(sum(s.candidates()) for s in searches)
+            n_sites = 0
+            for s in searches:
+                st, _, n = s.run_bulge(queries, bulge, size, spans, MAX_MM, 1 << 40) if size else s.run(queries, MAX_MM, 1 << 40)
+                nat.check(st, "crp_search_run_bulge")
+                n_sites += n
+            st1 = [s.stats() for s in searches]
+            extract_ms = sum(x["extract_ms"] for x in st1)
+            compare_ms = sum(x["compare_ms"] for x in st1)
+            vpp = BULGE_VALU_PER_PAIR if size else VALU_PER_PAIR
+            floor_ms = float(cand) * len(queries) * vpp / ISSUE_RATE * 1e3
+            row = dict(window=len(kp), candidates=cand, extract_ms=round(extract_ms, 3), compare_ms=round(compare_ms, 3),
+                       compare_launches=int(sum(x["compare_launches"] for x in st1)), ms_per_query=round(compare_ms / len(queries), 5),
+                       sites=int(n_sites), issue_floor_ms=round(floor_ms, 3), fraction_of_issue_floor=round(floor_ms / compare_ms, 3),
+                       gpu_ms_with_extraction=round(extract_ms + compare_ms, 3))
+            total += extract_ms + compare_ms
+            if size:  # the expansion path on the same (resident) candidates
+                exp = []
+                for q, query in enumerate(queries):
+                    first, last = (int(v) for v in spans[q])
+                    hi = last if bulge == "DNA" else last - size
+                    for s_ in range(first + 1, hi + 1):
+                        exp.append(query[:s_] + "N" * size + query[s_:] if bulge == "DNA" else query[:s_] + query[s_ + size:])
+                n_exp = 0
+                for s in searches:
+                    st, _, n = s.run(exp, MAX_MM, 1 << 40)
+                    nat.check(st, "crp_search_run")
+                    n_exp += n
+                st2 = [s.stats() for s in searches]
+                exp_ms = sum(b["compare_ms"] - a["compare_ms"] for a, b in zip(st1, st2))
+                row.update(expansion_queries=len(exp), expansion_compare_ms=round(exp_ms, 3),
+                           expansion_launches=int(sum(b["compare_launches"] - a["compare_launches"] for a, b in zip(st1, st2))),
+                           expansion_sites=int(n_exp), speedup_vs_expansion=round(exp_ms / compare_ms, 2))
+            for s in searches:
+                s.close()
+            out["kinds"]["%s%d" % (bulge, size) if size else "none"] = row
+        g.close()
+    out["gpu_ms_all_kinds"] = round(total, 3)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--bulge", metavar="D,R", help="time the search with DNA bulges 1..D and RNA bulges 1..R instead")
     args = ap.parse_args()
     t0 = time.perf_counter()
     wl = bw.switchgrass_like(0, args.scale)
     contigs = [wl.bases(s) for s in wl.specs]
-    guides = draw_guides(contigs, max(QS))
+    guides = draw_guides(contigs, BULGE_Q if args.bulge else max(QS))
     gen_s = time.perf_counter() - t0
+    if args.bulge:
+        return bulge_main(args, contigs, guides, dict(workload=wl.name, chars=int(sum(c.size for c in contigs)), max_mm=MAX_MM,
+                                                      generate_s=round(gen_s, 1)))
     out = dict(workload=wl.name, chars=int(sum(c.size for c in contigs)), max_mm=MAX_MM, valu_per_pair=VALU_PER_PAIR,
                generate_s=round(gen_s, 1), patterns={})
     with Engine(args.device) as eng:
