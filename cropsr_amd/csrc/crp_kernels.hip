@@ -60,6 +60,18 @@ __device__ __forceinline__ uint64_t behind(uint64_t prev, uint64_t cur, int e)
     return pair64(funnel(c0, p1, 64 - e), funnel(p1, p0, 64 - e));
 }
 
+// Whole-wave DPP shifts by one lane: lane i reads lane i - 1 (WAVE_SHR1) or i + 1 (WAVE_SHL1); the lane without a
+// source keeps `edge`.  Two v_mov_b32_dpp, no lane-index arithmetic and no LDS crossbar.  Needs all 64 lanes active.
+constexpr int DPP_WAVE_SHL1 = 0x130, DPP_WAVE_SHR1 = 0x138;
+template <int CTRL>
+__device__ __forceinline__ uint64_t wave_shift(uint64_t x, uint64_t edge)
+{
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)edge, (int)(uint32_t)x, CTRL, 0xf, 0xf, false);
+    const uint32_t hi =
+        (uint32_t)__builtin_amdgcn_update_dpp((int)(uint32_t)(edge >> 32), (int)(uint32_t)(x >> 32), CTRL, 0xf, 0xf, false);
+    return pair64(hi, lo);
+}
+
 // 64-bit inclusive scan across the wave.
 __device__ __forceinline__ uint64_t wave_inclusive_scan(uint64_t v)
 {
@@ -72,9 +84,8 @@ __device__ __forceinline__ uint64_t wave_inclusive_scan(uint64_t v)
     return v;
 }
 
-// Block-wide exclusive scan of a packed (plus | minus << 32) count.
-// `wave_tot` is LDS scratch of WAVES entries.  Returns the exclusive prefix,
-// sets `total` to the block total.
+// Block-wide exclusive scan of a packed (plus | minus << 16) count.
+// `wave_tot` is LDS scratch of WAVES entries.
 // The per-lane counts are small (<= 128 per strand), so both fit one 32-bit
 // word as 16-bit fields and the wave scan is six DPP adds (row_shr 1,2,4,8 inside
 // each row of 16 lanes, then row_bcast:15 / row_bcast:31 across rows) instead of
@@ -97,24 +108,41 @@ __device__ __forceinline__ uint32_t wave_inclusive_scan_u32(uint32_t v)
     return v;
 }
 
-template <int WAVES>
-__device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t v, uint64_t *wave_tot, uint64_t &total)
+// Sum of a 32-bit value over the wave (mod 2^32): the inclusive scan's last lane, read as a scalar.  Needs all 64 lanes
+// active.
+__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v)
 {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const uint32_t v16 = (uint32_t)v | ((uint32_t)(v >> 32) << 16);  // plus | minus << 16
+    return (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_scan_u32(v), 63);
+}
+
+// The exclusive prefix of the tile's counts in each strand, per lane, and the tile's totals (wave-uniform).
+struct TileScan {
+    uint32_t ex_plus, ex_minus, n_plus, n_minus;
+};
+
+// A wave covers at most 8 192 positions, so its counts stay 16|16-packed to the end of the wave scan; only the
+// cross-wave part, where a tile's strand can reach 65 536, is widened.  That part is scalar: the wave index comes from
+// readfirstlane and the WAVES totals from LDS are read into SGPRs, so the compares and adds over them run on the SALU.
+template <int WAVES>
+__device__ __forceinline__ TileScan block_exclusive_scan(uint32_t v16, uint32_t *wave_tot)
+{
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t inc16 = wave_inclusive_scan_u32(v16);
-    const uint64_t inc = (uint64_t)(inc16 & 0xffffu) | ((uint64_t)(inc16 >> 16) << 32);
-    if (lane == 63) wave_tot[wave] = inc;
+    if (lane == 63) wave_tot[wave] = inc16;
     __syncthreads();
-    uint64_t base = 0, tot = 0;
+    uint32_t base_p = 0, base_m = 0, tot_p = 0, tot_m = 0;
 #pragma unroll
     for (int w = 0; w < WAVES; ++w) {
-        const uint64_t t = wave_tot[w];
-        if (w < wave) base += t;
-        tot += t;
+        const uint32_t t = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_tot[w]);
+        if (w < wave) {
+            base_p += t & 0xffffu;
+            base_m += t >> 16;
+        }
+        tot_p += t & 0xffffu;
+        tot_m += t >> 16;
     }
-    total = tot;
-    return base + inc - v;
+    const uint32_t ex16 = inc16 - v16;  // no borrow between the fields: inc16 >= v16 in each
+    return TileScan{base_p + (ex16 & 0xffffu), base_m + (ex16 >> 16), tot_p, tot_m};
 }
 
 // -------------------------------------------------------------- pass 1: count
@@ -179,11 +207,10 @@ __device__ __forceinline__ void own_words_and_masks(const Planes &pl, uint64_t n
     derive(q[0][0], q[1][0], q[2][0], q[3][0], ga, ca, va);
     derive(q[0][WPT - 1], q[1][WPT - 1], q[2][WPT - 1], q[3][WPT - 1], gb, cb, vb);  // (WPT = 1: the same word)
     derive(e[0], e[1], e[2], e[3], ge, ce, ve);
-    // left neighbour's last word, right neighbour's first word
-    uint64_t v_left = __shfl_up(vb, 1, 64);
-    uint64_t g_right = __shfl_down(ga, 1, 64), c_right = __shfl_down(ca, 1, 64), v_right = __shfl_down(va, 1, 64);
-    if (lane == 0) v_left = ve;
-    if (lane == 63) { g_right = ge; c_right = ce; v_right = ve; }
+    // left neighbour's last word, right neighbour's first word; lanes 0 / 63 keep the word outside the wave
+    const uint64_t v_left = wave_shift<DPP_WAVE_SHR1>(vb, ve);
+    const uint64_t g_right = wave_shift<DPP_WAVE_SHL1>(ga, ge), c_right = wave_shift<DPP_WAVE_SHL1>(ca, ce),
+                   v_right = wave_shift<DPP_WAVE_SHL1>(va, ve);
     if constexpr (WPT == 2) {
         masks_of(ga, gb, ca, cb, v_left, va, vb, l, mp[0], mm[0]);
         masks_of(gb, g_right, cb, c_right, va, vb, v_right, l, mp[WPT - 1], mm[WPT - 1]);
@@ -324,6 +351,14 @@ __device__ __forceinline__ uint32_t window31(const uint64_t *plane, uint32_t q)
     return __builtin_amdgcn_alignbit(p32[i + 1], p32[i], q & 31) & 0x7fffffffu;
 }
 
+// all 32 bits from bit position q on
+__device__ __forceinline__ uint32_t window32(const uint64_t *plane, uint32_t q)
+{
+    const uint32_t *p32 = reinterpret_cast<const uint32_t *>(plane);
+    const uint32_t i = q >> 5;
+    return __builtin_amdgcn_alignbit(p32[i + 1], p32[i], q & 31);
+}
+
 __device__ __forceinline__ uint32_t reverse30(uint32_t x) { return __brev(x) >> 2; }
 
 // Chained-scan descriptors (single-pass mode): one 64-bit word per tile,
@@ -436,9 +471,8 @@ __device__ __forceinline__ uint64_t lookback_resolve(uint64_t *desc, uint32_t ti
                 __builtin_amdgcn_s_sleep(8);
             }
         } else {
-#pragma unroll
-            for (int d = 32; d > 0; d >>= 1) contrib += __shfl_xor(contrib, d, 64);
-            excl += contrib;
+            // both fields of the sum stay below 2^31 (they are parts of a table total): one 32-bit wave sum per field
+            excl += pair64(wave_sum_u32((uint32_t)(contrib >> 32)), wave_sum_u32((uint32_t)contrib));
             if (found) break;
             base -= 64 * LB_DEPTH;
         }
@@ -486,7 +520,7 @@ __device__ __forceinline__ void chain_resolve(const ChainArgs &ch)
 }
 
 // exp table + chain-prefix tables as ONE image in global memory, in the order the emit kernel keeps them in LDS
-struct TabsImage {
+struct alignas(16) TabsImage {
     uint64_t exp_tab[256];
     double score_tab[CRP_SCORE_TAB_N];
 };
@@ -584,7 +618,8 @@ __device__ __forceinline__ void peel32(uint32_t m, uint32_t base, uint32_t &addr
 
 template <class G, bool PAM, bool CHAINED, bool PRE, bool SEEDS>
 __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16_t *list, uint64_t *exp_tab, double *score_tab,
-                                            const uint64_t (&mp)[G::WPT], const uint64_t (&mm)[G::WPT], uint64_t ex,
+                                            const uint64_t (&mp)[G::WPT], const uint64_t (&mm)[G::WPT], uint32_t ex_plus,
+                                            uint32_t ex_minus,
                                             uint32_t n_plus, uint32_t n_minus, int l, uint32_t tile_pos,
                                             uint64_t off_plus, uint64_t off_minus, const HitTables &out,
                                             const ChainArgs &ch);
@@ -616,10 +651,10 @@ __global__ __launch_bounds__(G::BLOCK) __attribute__((amdgpu_waves_per_eu(6, 8))
     constexpr int TW = G::WORDS;
     __shared__ uint64_t sh[4][TW + 2];
     // exp table (256 words) + chain-prefix tables of the scorer
-    __shared__ uint64_t tabs[256 + CRP_SCORE_TAB_N];
+    __shared__ __attribute__((aligned(16))) uint64_t tabs[256 + CRP_SCORE_TAB_N];
     uint64_t *const exp_tab = tabs;
     double *const score_tab = reinterpret_cast<double *>(tabs + 256);
-    __shared__ uint64_t wave_tot[G::BLOCK / 64];
+    __shared__ uint32_t wave_tot[G::BLOCK / 64];
     __shared__ uint64_t s_excl;
     __shared__ uint32_t s_flag;
     __shared__ uint16_t list[G::LIST];
@@ -658,13 +693,13 @@ __global__ __launch_bounds__(G::BLOCK) __attribute__((amdgpu_waves_per_eu(6, 8))
             else sh[p][0] = t0 > 0 ? pl.plane[p][t0 - 1] : voidw;
         }
     }
-    uint64_t c = 0;
+    uint32_t c16 = 0;  // plus | minus << 16
 #pragma unroll
-    for (int k = 0; k < G::WPT; ++k) c += (uint64_t)__popcll(mp[k]) | ((uint64_t)__popcll(mm[k]) << 32);
-    uint64_t total;
-    const uint64_t ex = block_exclusive_scan<G::BLOCK / 64>(c, wave_tot, total);
-    const uint32_t n_plus = (uint32_t)total, n_minus = (uint32_t)(total >> 32);
+    for (int k = 0; k < G::WPT; ++k) c16 += (uint32_t)__popcll(mp[k]) | ((uint32_t)__popcll(mm[k]) << 16);
+    const TileScan sc = block_exclusive_scan<G::BLOCK / 64>(c16, wave_tot);
+    const uint32_t n_plus = sc.n_plus, n_minus = sc.n_minus;
     const uint32_t n_all = n_plus + n_minus;
+    const uint64_t total = pair64(n_minus, n_plus);
     uint64_t off_plus = 0, off_minus = 0;
     ChainArgs ch{};
     if (CHAINED) {
@@ -694,17 +729,20 @@ __global__ __launch_bounds__(G::BLOCK) __attribute__((amdgpu_waves_per_eu(6, 8))
     // follows the hit-list build; staging them only now keeps them out of the way of the counts that later tiles wait
     // for (-3.5 %).  (Staging by LDS-DMA, or requesting the words earlier and writing them here, both measured
     // slower: profiles/EXPERIMENTS.md.)
-    for (int k = tid; k < 256; k += G::BLOCK) exp_tab[k] = CRP_TABS.exp_tab[k];
-    if (LFIX == 20)
-        for (int k = tid; k < CRP_SCORE_TAB_N; k += G::BLOCK) score_tab[k] = CRP_TABS.score_tab[k];
-    emit_rounds<G, LFIX == 20, CHAINED, PRE, SEEDS>(sh, list, exp_tab, score_tab, mp, mm, ex, n_plus, n_minus, l, (uint32_t)(t0 * 64),
+    // (16-byte units at 32-bit offsets; the chain tables for l = 20 only)
+    constexpr uint32_t TAB_UNITS = (LFIX == 20 ? sizeof(TabsImage) : sizeof(CRP_TABS.exp_tab)) / 16;
+    for (uint32_t k = tid; k < TAB_UNITS; k += G::BLOCK)
+        reinterpret_cast<uint4 *>(tabs)[k] = reinterpret_cast<const uint4 *>(&CRP_TABS)[k];
+    emit_rounds<G, LFIX == 20, CHAINED, PRE, SEEDS>(sh, list, exp_tab, score_tab, mp, mm, sc.ex_plus, sc.ex_minus, n_plus, n_minus, l,
+                                                 (uint32_t)(t0 * 64),
                                                  off_plus, off_minus, out, ch);
 }
 
 // Compact the kept hits of one staged tile and score them, G::LIST list entries per round.
 template <class G, bool PAM, bool CHAINED, bool PRE, bool SEEDS>
 __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16_t *list, uint64_t *exp_tab, double *score_tab,
-                                            const uint64_t (&mp)[G::WPT], const uint64_t (&mm)[G::WPT], uint64_t ex,
+                                            const uint64_t (&mp)[G::WPT], const uint64_t (&mm)[G::WPT], uint32_t ex_plus,
+                                            uint32_t ex_minus,
                                             uint32_t n_plus, uint32_t n_minus, int l, uint32_t tile_pos,
                                             uint64_t off_plus, uint64_t off_minus, const HitTables &out,
                                             const ChainArgs &ch)
@@ -725,8 +763,8 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
         hi_rank = by_strand ? (lo_rank == 0 ? n_plus : n_all) : min(lo_rank + CAP, n_all);
         if (lo_rank) __syncthreads();  // previous round's readers are done
         // ---- compact: rank -> tile-local position, '+' hits first, then '-'
-        const uint32_t rp0 = (uint32_t)ex - lo_rank;                    // window-relative rank of this thread's first '+' hit
-        const uint32_t rm0 = n_plus + (uint32_t)(ex >> 32) - lo_rank;  // same for '-'
+        const uint32_t rp0 = ex_plus - lo_rank;            // window-relative rank of this thread's first '+' hit
+        const uint32_t rm0 = ex_minus + (n_plus - lo_rank);  // same for '-'
         if (n_all <= CAP || by_strand) {
             // every entry of this round fits: no per-entry capacity test
             const bool with_plus = !by_strand || lo_rank == 0, with_minus = !by_strand || lo_rank != 0;
@@ -772,8 +810,15 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
             Fetched f{list[k], lo_rank + k, 0, 0, 0, 0};
             // '+': long_sequence = T(s[i-l-5 : i+5])       (CROPSR.py:421)
             // '-': long_sequence = T(R(s[j-2 : j+l+8]))     (CROPSR.py:432)
-            const uint32_t q = 64u + f.e - (f.r >= n_plus ? 2u : (uint32_t)(l + 5));
-            if (l >= 20) {
+            // PAM (l = 20): a '+' window is read from two positions earlier, so that it sits at bits 2..31 and a plain
+            // v_bfrev moves it to bits 0..29 reversed -- where the '-' window is read -- with no shift after it.
+            const uint32_t q = 64u + f.e - (f.r >= n_plus ? 2u : PAM ? 27u : (uint32_t)(l + 5));
+            if (PAM) {
+                f.h = window32(sh[0], q);
+                f.w = window32(sh[1], q);
+                f.u = window32(sh[2], q);
+                f.a = window32(sh[3], q);
+            } else if (l >= 20) {
                 f.h = window31(sh[0], q);
                 f.w = window31(sh[1], q);
                 f.u = window31(sh[2], q);
@@ -788,7 +833,31 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
             // has exactly 30 characters (CROPSR.py:458,466): for l = 20 a complete
             // window, for l > 20 a window cut to 30 by the end of the string, for
             // l < 20 never.
-            if (l >= 20) {
+            if (PAM) {
+                // Both strands' windows at bits 0..29 after the orientation; bits 30 and 31 hold characters next to the
+                // window, which no gate or table index of the PAM scorer reads (gen_score_terms.py), so they stay.
+                const uint32_t u = f.u;
+                uint32_t h = f.h, w = f.w, valid = f.a | u;  // acgtACGT, U, Z
+                if (!minus) {
+                    // get_gRNA_sequence (CROPSR.py:128): complement upper-case bases only, then reverse.
+                    h = __brev(h);
+                    w = __brev(w ^ u);
+                    valid = __brev(valid);
+                }
+                // void positions = h & w & ~u & ~a, oriented like the window ('+': u = 1 is valid, so w ^ u = w there)
+                const bool complete = (h & w & ~valid & 0x3fffffffu) == 0;
+                if (SEEDS) {
+                    // Off-target scan (crp_offtarget.hip): seed character k (k = 0 next to the PAM) is character k of the
+                    // `sequence` column -- '+': s[i-1-k] = window bit l+4-k = bit 25-l+k after the reversal; '-': s[j+3+k]
+                    // = window bit 5+k.  For l = 20 (the only length this variant is built for) both are bit 5+k.
+                    if (((valid >> 5) & 0xfffu) == 0xfffu) hit.seed = (((h >> 5) & 0xfffu) << 12) | ((w >> 5) & 0xfffu);
+                }
+                if (complete) {
+                    const uint32_t mG = h & w & valid, mC = h & ~w & valid;
+                    const uint32_t mT = ~h & w & valid, mA = ~h & ~w & valid;
+                    crp_score_masks<PAM>(mA, mT, mC, mG, exp_tab, score_tab, hit.pre, hit.score);
+                }
+            } else if (l >= 20) {
                 uint32_t h = f.h, w = f.w, u = f.u, a = f.a;
                 const uint32_t vd = h & w & ~u & ~a;  // void positions
                 const bool complete = (vd & 0x3fffffffu) == 0 && (l == 20 || (vd >> 30));
@@ -804,13 +873,7 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
                     w = reverse30(w ^ u);
                     valid = reverse30(valid);
                 }
-                if (SEEDS) {
-                    // Off-target scan (crp_offtarget.hip): seed character k (k = 0 next to the PAM) is character k of the
-                    // `sequence` column -- '+': s[i-1-k] = window bit l+4-k = bit 25-l+k after the reversal; '-': s[j+3+k]
-                    // = window bit 5+k.  For l = 20 (the only length this variant is built for) both are bit 5+k.
-                    static_assert(!SEEDS || PAM, "seed words are emitted by the l = 20 variant only");
-                    if (((valid >> 5) & 0xfffu) == 0xfffu) hit.seed = (((h >> 5) & 0xfffu) << 12) | ((w >> 5) & 0xfffu);
-                }
+                static_assert(!SEEDS || PAM, "seed words are emitted by the l = 20 variant only");
                 if (complete) {
                     const uint32_t mG = h & w & valid, mC = h & ~w & valid;
                     const uint32_t mT = ~h & w & valid, mA = ~h & ~w & valid;
