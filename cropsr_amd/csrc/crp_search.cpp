@@ -4,11 +4,11 @@
 // create   validates the pattern, counts the candidates of every workgroup of the arena (one launch) and plans the
 //          chunks: consecutive workgroups whose candidates fit the budget.
 // run      per chunk: extraction (skipped when the one chunk of the plan is still in HBM from an earlier run), then the
-//          compare in query batches of at most kPairsPerLaunch pairs and kBatchQueries queries per launch.  The site list
-//          is copied back and sorted by (query, arena position, strand): the atomics' order never reaches the caller.
-// run_bulge the same with the bulge compare kernel, on a handle whose pattern is the window pattern of one bulge kind
-//          (Bulges).  Its launches cover at most kBulgePairsPerLaunch pairs, its site word and sort key
-//          carry the bulge's placement, and queries are limited to kMaxBulgeQueries.
+//          compare in query batches of at most Kind::pairs_per_launch() pairs and kBatchQueries queries per launch.  The
+//          site list is copied back and sorted by (query, arena position, strand): the atomics' order never reaches the
+//          caller.  crp_search_run and crp_search_run_bulge are the same run of different kinds: plain, or a DNA or RNA
+//          bulge on a handle whose pattern is the window pattern of that bulge (Bulges).  The kind
+//          picks the compare kernel, the pairs per launch, the query limit and the site word and sort-key layout.
 #include <algorithm>
 #include <cstring>
 #include <new>
@@ -54,6 +54,42 @@ uint32_t iupac_set(char c)
 
 uint32_t complement_set(uint32_t s) { return ((s & 1) << 1) | ((s & 2) >> 1) | ((s & 4) << 1) | ((s & 8) >> 1); }
 
+// The kind of a run: plain (dna = rna = 0) or a DNA or an RNA bulge of that size.  It decides the compare kernel, the
+// pairs per launch, the query limit and the layout of the site word and the sort key: a bulge kind carries the bulge's
+// placement (at_bits() bits) between the strand and the mismatches.
+struct Kind {
+    int dna = 0, rna = 0;
+    bool bulge() const { return dna || rna; }
+    int at_bits() const { return bulge() ? 5 : 0; }
+    uint64_t pairs_per_launch() const { return bulge() ? kBulgePairsPerLaunch : kPairsPerLaunch; }
+    uint64_t max_queries() const { return bulge() ? kMaxBulgeQueries : kMaxQueries; }
+    hipError_t compare(hipStream_t st, const crp::SearchCands &c, uint32_t n, const uint4 *queries, uint32_t q0, uint32_t nq, int max_mm,
+                       uint32_t *counts, uint2 *sites, uint64_t site_cap, unsigned long long *site_ctr) const
+    {
+        if (bulge()) return crp::launch_search_bulge_compare(st, c, n, queries, q0, nq, max_mm, dna, rna, counts, sites, site_cap, site_ctr);
+        return crp::launch_search_compare(st, c, n, queries, q0, nq, max_mm, counts, sites, site_cap, site_ctr);
+    }
+};
+
+// One site: the kernels' site word is {query << (4 + at_bits) | placement << 4 | mismatches, strand << 31 | pos}; the
+// sort key packs query, arena position, strand, bulge_at and mismatches from the top bit down (36 + at_bits bits below
+// the query), so that sorted keys order the sites by query, position and strand.
+struct Site {
+    uint64_t query, pos, strand, at, mm;
+};
+
+uint64_t pack_key(const Site &x, Kind k)
+{
+    const int b = k.at_bits();
+    return x.query << (36 + b) | x.pos << (5 + b) | x.strand << (4 + b) | x.at << 4 | x.mm;
+}
+
+Site unpack_key(uint64_t key, Kind k)
+{
+    const int b = k.at_bits();
+    return Site{key >> (36 + b), (key >> (5 + b)) & 0x7fffffffu, (key >> (4 + b)) & 1, (key >> 4) & ((1u << b) - 1), key & 15};
+}
+
 }  // namespace
 
 struct crp_search {
@@ -82,10 +118,9 @@ struct crp_search {
     uint2 *d_sites = nullptr;
     uint64_t sites_cap = 0;
     unsigned long long *d_ctr = nullptr;
-    std::vector<uint64_t> keys;  // sites of the last successful run: query << 36 | pos << 5 | strand << 4 | mismatches
-                                 // (a bulge run: query << 41 | pos << 10 | strand << 9 | bulge_at << 4 | mismatches)
+    std::vector<uint64_t> keys;  // sites of the last successful run, as pack_key of its kind
     bool have_sites = false;
-    bool keys_bulge = false;     // the last run was a bulge run
+    Kind keys_kind;              // the kind of the last run
     hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
     double ms_extract = 0, ms_compare = 0;
     uint64_t n_extract = 0, n_compare = 0;
@@ -147,9 +182,8 @@ int plan(crp_search *s)
     return CRP_OK;
 }
 
-// one pass over every chunk: counts and sites accumulate on the device
-// dna, rna: the bulge compare kernel for that bulge (both 0: the plain compare kernel)
-int run_pass(crp_search *s, uint32_t n_queries, int max_mm, uint64_t dev_sites, int dna, int rna)
+// one pass over every chunk with the compare kernel of `kind`: counts and sites accumulate on the device
+int run_pass(crp_search *s, uint32_t n_queries, int max_mm, uint64_t dev_sites, Kind kind)
 {
     crp_ctx *ctx = s->ctx;
     crp_arena *a = s->arena;
@@ -168,18 +202,13 @@ int run_pass(crp_search *s, uint32_t n_queries, int max_mm, uint64_t dev_sites, 
                                                  s->chunk_first[c + 1] - s->chunk_first[c], s->d_block_off, s->cands()));
         }
         CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
-        const bool bulge = dna || rna;
-        const uint64_t pairs = bulge ? kBulgePairsPerLaunch : kPairsPerLaunch;
+        const uint64_t pairs = kind.pairs_per_launch();
         const uint32_t batch = (uint32_t)std::max<uint64_t>(1, std::min({(uint64_t)n_queries, pairs / n, s->batch_queries}));
         uint64_t launches = 0;
         for (uint32_t q0 = 0; q0 < n_queries; q0 += batch) {
             const uint32_t nq = std::min(batch, n_queries - q0);
-            if (bulge)
-                CRP_HIP(ctx, crp::launch_search_bulge_compare(ctx->stream, s->cands(), (uint32_t)n, s->d_queries, q0, nq, max_mm, dna, rna,
-                                                              s->d_counts, s->d_sites, dev_sites, s->d_ctr));
-            else
-                CRP_HIP(ctx, crp::launch_search_compare(ctx->stream, s->cands(), (uint32_t)n, s->d_queries, q0, nq, max_mm, s->d_counts,
-                                                        s->d_sites, dev_sites, s->d_ctr));
+            CRP_HIP(ctx, kind.compare(ctx->stream, s->cands(), (uint32_t)n, s->d_queries, q0, nq, max_mm, s->d_counts, s->d_sites, dev_sites,
+                                      s->d_ctr));
             ++launches;
         }
         CRP_HIP(ctx, hipEventRecord(s->ev[2], ctx->stream));
@@ -324,13 +353,11 @@ bool encode_queries(const char *queries, uint64_t n_queries, int T, std::vector<
     return true;
 }
 
-// the capacity protocol over encoded queries; dna, rna as in run_pass; span_first (bulge runs): per query, what
-// bulge_at counts from
-int run_encoded(crp_search *s, const std::vector<uint4> &enc, int max_mm, uint64_t site_cap, uint32_t *counts, uint64_t *n_sites,
-                int dna, int rna, const std::vector<uint8_t> &span_first)
+// the capacity protocol over encoded queries of one kind; span_first: per query, what bulge_at counts from
+int run_encoded(crp_search *s, const std::vector<uint4> &enc, Kind kind, const std::vector<uint8_t> &span_first, int max_mm,
+                uint64_t site_cap, uint32_t *counts, uint64_t *n_sites)
 {
     const uint64_t n_queries = enc.size();
-    const bool bulge = dna || rna;
     s->have_sites = false;
     s->keys.clear();
     *n_sites = 0;
@@ -352,7 +379,7 @@ int run_encoded(crp_search *s, const std::vector<uint4> &enc, int max_mm, uint64
     CRP_HIP(ctx, hipMemcpyAsync(s->d_queries, enc.data(), n_queries * sizeof(uint4), hipMemcpyHostToDevice, ctx->stream));
     unsigned long long total = 0;
     for (int pass = 0; pass < 2; ++pass) {
-        if ((rc = run_pass(s, (uint32_t)n_queries, max_mm, dev_sites, dna, rna)) != CRP_OK) return rc;
+        if ((rc = run_pass(s, (uint32_t)n_queries, max_mm, dev_sites, kind)) != CRP_OK) return rc;
         CRP_HIP(ctx, hipMemcpy(&total, s->d_ctr, sizeof(total), hipMemcpyDeviceToHost));
         if (total <= dev_sites || total > site_cap) break;
         // more sites than the device list had room for, fewer than the caller's: once more with room for all of them
@@ -366,20 +393,38 @@ int run_encoded(crp_search *s, const std::vector<uint4> &enc, int max_mm, uint64
     std::vector<uint2> raw(total);
     if (total) CRP_HIP(ctx, hipMemcpy(raw.data(), s->d_sites, total * sizeof(uint2), hipMemcpyDeviceToHost));
     s->keys.resize(total);
+    const int b = kind.at_bits();
     for (uint64_t k = 0; k < total; ++k) {
-        const uint64_t pos = raw[k].y & 0x7fffffffu, strand = raw[k].y >> 31;
-        if (bulge) {
-            const uint64_t q = raw[k].x >> 9, at = ((raw[k].x >> 4) & 31) - span_first[q], mm = raw[k].x & 15;
-            s->keys[k] = q << 41 | pos << 10 | strand << 9 | at << 4 | mm;
-        } else {
-            const uint64_t q = raw[k].x >> 4, mm = raw[k].x & 15;
-            s->keys[k] = q << 36 | pos << 5 | strand << 4 | mm;
-        }
+        const uint64_t q = raw[k].x >> (4 + b), at = ((raw[k].x >> 4) & ((1u << b) - 1)) - span_first[q];
+        s->keys[k] = pack_key(Site{q, raw[k].y & 0x7fffffffu, raw[k].y >> 31, at, raw[k].x & 15}, kind);
     }
     std::sort(s->keys.begin(), s->keys.end());
-    s->keys_bulge = bulge;
+    s->keys_kind = kind;
     s->have_sites = true;
     return CRP_OK;
+}
+
+// crp_search_run(_bulge) past the checks of its own arguments; span: per query, the first and last letter of its span
+// (bulge kinds only)
+int run_kind(crp_search *s, const char *queries, uint64_t n_queries, Kind kind, const uint8_t *span, int max_mm, uint64_t site_cap,
+             uint32_t *counts, uint64_t *n_sites)
+{
+    if (max_mm < 0 || max_mm > CRP_SEARCH_MAX_MM || n_queries >= kind.max_queries()) return CRP_ERR_UNSUPPORTED;
+    const int T = s->sets.T - kind.dna + kind.rna;  // the query's length
+    if (T < 1 || T > CRP_SEARCH_MAX_T) return CRP_ERR_UNSUPPORTED;
+    std::vector<uint4> enc;
+    if (!encode_queries(queries, n_queries, T, enc)) return CRP_ERR_INVALID;
+    std::vector<uint8_t> span_first(n_queries);  // (0 for a plain run: its sites have no placement)
+    if (kind.bulge())
+        for (uint64_t q = 0; q < n_queries; ++q) {
+            const int first = span[2 * q], last = span[2 * q + 1];
+            // placements: first < s <= last (DNA), first < s and s + size - 1 < last (RNA)
+            const int s_min = first + 1, s_max = last - kind.rna;
+            if (last >= T || s_min > s_max) return CRP_ERR_INVALID;
+            enc[q].w = (uint32_t)s_min | (uint32_t)s_max << 8;
+            span_first[q] = (uint8_t)first;
+        }
+    return run_encoded(s, enc, kind, span_first, max_mm, site_cap, counts, n_sites);
 }
 
 }  // namespace
@@ -390,10 +435,7 @@ int crp_search_run(crp_search *s, const char *queries, uint64_t n_queries, int m
                    uint64_t *n_sites)
 {
     if (!s || !n_sites || (n_queries && !queries)) return CRP_ERR_INVALID;
-    if (max_mm < 0 || max_mm > CRP_SEARCH_MAX_MM || n_queries >= kMaxQueries) return CRP_ERR_UNSUPPORTED;
-    std::vector<uint4> enc;
-    if (!encode_queries(queries, n_queries, s->sets.T, enc)) return CRP_ERR_INVALID;
-    return run_encoded(s, enc, max_mm, site_cap, counts, n_sites, 0, 0, {});
+    return run_kind(s, queries, n_queries, Kind{}, nullptr, max_mm, site_cap, counts, n_sites);
 }
 
 int crp_search_run_bulge(crp_search *s, const char *queries, uint64_t n_queries, int kind, int size, const uint8_t *span, int max_mm,
@@ -401,23 +443,9 @@ int crp_search_run_bulge(crp_search *s, const char *queries, uint64_t n_queries,
 {
     if (!s || !n_sites || (n_queries && (!queries || !span))) return CRP_ERR_INVALID;
     if (kind != CRP_SEARCH_BULGE_DNA && kind != CRP_SEARCH_BULGE_RNA) return CRP_ERR_INVALID;
-    if (size < 1 || size > CRP_SEARCH_MAX_BULGE || max_mm < 0 || max_mm > CRP_SEARCH_MAX_MM || n_queries >= kMaxBulgeQueries)
-        return CRP_ERR_UNSUPPORTED;
+    if (size < 1 || size > CRP_SEARCH_MAX_BULGE) return CRP_ERR_UNSUPPORTED;
     const bool dna = kind == CRP_SEARCH_BULGE_DNA;
-    const int T = dna ? s->sets.T - size : s->sets.T + size;  // the query's length
-    if (T < 1 || T > CRP_SEARCH_MAX_T) return CRP_ERR_UNSUPPORTED;
-    std::vector<uint4> enc;
-    if (!encode_queries(queries, n_queries, T, enc)) return CRP_ERR_INVALID;
-    std::vector<uint8_t> span_first(n_queries);
-    for (uint64_t q = 0; q < n_queries; ++q) {
-        const int first = span[2 * q], last = span[2 * q + 1];
-        // placements: first < s <= last (DNA), first < s and s + size - 1 < last (RNA)
-        const int s_min = first + 1, s_max = dna ? last : last - size;
-        if (last >= T || s_min > s_max) return CRP_ERR_INVALID;
-        enc[q].w = (uint32_t)s_min | (uint32_t)s_max << 8;
-        span_first[q] = (uint8_t)first;
-    }
-    return run_encoded(s, enc, max_mm, site_cap, counts, n_sites, dna ? size : 0, dna ? 0 : size, span_first);
+    return run_kind(s, queries, n_queries, Kind{dna ? size : 0, dna ? 0 : size}, span, max_mm, site_cap, counts, n_sites);
 }
 
 int crp_search_fetch(const crp_search *s, uint32_t *query, uint32_t *arena_pos, uint8_t *strand, uint8_t *mismatches, uint64_t cap)
@@ -431,14 +459,13 @@ int crp_search_fetch_bulge(const crp_search *s, uint32_t *query, uint32_t *arena
     if (!s) return CRP_ERR_INVALID;
     if (!s->have_sites) return CRP_ERR_STATE;
     if (cap < s->keys.size()) return CRP_ERR_CAPACITY;
-    const int sh = s->keys_bulge ? 5 : 0;  // a bulge key has the 5-bit placement between strand and mismatches
     for (uint64_t k = 0; k < s->keys.size(); ++k) {
-        const uint64_t key = s->keys[k];
-        if (query) query[k] = (uint32_t)(key >> (36 + sh));
-        if (arena_pos) arena_pos[k] = (uint32_t)(key >> (5 + sh)) & 0x7fffffffu;
-        if (strand) strand[k] = (uint8_t)((key >> (4 + sh)) & 1);
-        if (mismatches) mismatches[k] = (uint8_t)(key & 15);
-        if (bulge_at) bulge_at[k] = (uint8_t)(sh ? (key >> 4) & 31 : 0);
+        const Site x = unpack_key(s->keys[k], s->keys_kind);
+        if (query) query[k] = (uint32_t)x.query;
+        if (arena_pos) arena_pos[k] = (uint32_t)x.pos;
+        if (strand) strand[k] = (uint8_t)x.strand;
+        if (mismatches) mismatches[k] = (uint8_t)x.mm;
+        if (bulge_at) bulge_at[k] = (uint8_t)x.at;
     }
     return CRP_OK;
 }

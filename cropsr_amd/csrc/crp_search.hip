@@ -157,6 +157,26 @@ __device__ __forceinline__ uint32_t lane_rank(uint64_t mask)  // set bits of mas
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
+// Appends the wave's hits to the site list: one ballot, the leader reserves the wave's slots with one atomic.  A hit
+// counts for (qi, mm) and, while there is room, stores its site word with the candidate's position.  pos is read only
+// for a hit (loading it outside the branch changes the register allocation).
+__device__ __forceinline__ void append_hits(bool hit, uint32_t qi, int mm, uint32_t word, const uint32_t *pos, uint32_t stride,
+                                            uint32_t *__restrict__ counts, uint2 *__restrict__ sites, uint64_t site_cap,
+                                            unsigned long long *__restrict__ site_ctr)
+{
+    const uint64_t bal = __ballot(hit);
+    if (!bal) return;
+    const int leader = __builtin_ctzll(bal);
+    unsigned long long slot = 0;
+    if ((int)(threadIdx.x & 63) == leader) slot = atomicAdd(site_ctr, (unsigned long long)__popcll(bal));
+    slot = __shfl(slot, leader);
+    if (hit) {
+        slot += lane_rank(bal);
+        atomicAdd(&counts[(uint64_t)qi * stride + mm], 1u);
+        if (slot < site_cap) sites[slot] = make_uint2(word, *pos);
+    }
+}
+
 __global__ __launch_bounds__(BLOCK) void search_compare_kernel(SearchCands c, uint32_t n, const uint4 *__restrict__ queries, uint32_t q0,
                                                                uint32_t nq, int max_mm, uint32_t *__restrict__ counts,
                                                                uint2 *__restrict__ sites, uint64_t site_cap,
@@ -186,20 +206,9 @@ __global__ __launch_bounds__(BLOCK) void search_compare_kernel(SearchCands c, ui
         }
         if (__builtin_expect(any, 0)) {
 #pragma unroll
-            for (int j = 0; j < SEARCH_CPL; ++j) {
-                const bool hit = mm[j] <= lim[j];
-                const uint64_t bal = __ballot(hit);
-                if (!bal) continue;
-                const int leader = __builtin_ctzll(bal);
-                unsigned long long slot = 0;
-                if ((int)(threadIdx.x & 63) == leader) slot = atomicAdd(site_ctr, (unsigned long long)__popcll(bal));
-                slot = __shfl(slot, leader);
-                if (hit) {
-                    slot += lane_rank(bal);
-                    atomicAdd(&counts[(uint64_t)qi * stride + mm[j]], 1u);
-                    if (slot < site_cap) sites[slot] = make_uint2(qi << 4 | (uint32_t)mm[j], c.pos[first + j * BLOCK]);
-                }
-            }
+            for (int j = 0; j < SEARCH_CPL; ++j)
+                append_hits(mm[j] <= lim[j], qi, mm[j], qi << 4 | (uint32_t)mm[j], c.pos + (first + j * BLOCK), stride, counts, sites,
+                            site_cap, site_ctr);
         }
     }
 }
@@ -272,19 +281,8 @@ __global__ __launch_bounds__(BLOCK) void search_bulge_compare_kernel(SearchCands
                         }
                     }
                 }
-                const bool hit = cand && best <= max_mm;
-                const uint64_t bal = __ballot(hit);
-                if (!bal) continue;
-                const int leader = __builtin_ctzll(bal);
-                unsigned long long slot = 0;
-                if ((int)(threadIdx.x & 63) == leader) slot = atomicAdd(site_ctr, (unsigned long long)__popcll(bal));
-                slot = __shfl(slot, leader);
-                if (hit) {
-                    slot += lane_rank(bal);
-                    atomicAdd(&counts[(uint64_t)qi * stride + best], 1u);
-                    if (slot < site_cap)
-                        sites[slot] = make_uint2(qi << 9 | (uint32_t)at << 4 | (uint32_t)best, c.pos[first + j * BLOCK]);
-                }
+                append_hits(cand && best <= max_mm, qi, best, qi << 9 | (uint32_t)at << 4 | (uint32_t)best, c.pos + (first + j * BLOCK),
+                            stride, counts, sites, site_cap, site_ctr);
             }
         }
     }

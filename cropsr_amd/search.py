@@ -122,16 +122,11 @@ def check_query(pattern, query, pam_len=None):
         raise SearchInputError("guide %r has %d letters: the pattern has %d%s; a shorter guide needs the PAM's length "
                                "(--pam-length) or N at the PAM positions" % (
                                    query, len(q), T, "" if run is None else ", its N run %d" % run[1]))
-    P = check_pam_len(pattern, pam_len)
-    if set(pattern[:T - P]) <= {"N"}:  # PAM on the 3' side: the guide ends where it begins
-        at = T - P - len(q)
-    elif set(pattern[P:]) <= {"N"}:    # on the 5' side: the guide starts where it ends
-        at = P
-    else:
-        raise SearchInputError("pattern %s has letters other than N outside its first or last %d" % (pattern, P))
-    if len(q) > T - P:
+    lo, hi, pam3 = guide_region(pattern, pam_len)
+    if len(q) > hi - lo:
         raise SearchInputError("guide %r has %d letters: at most %d fit next to a PAM of %d in a pattern of %d" % (
-            query, len(q), T - P, P, T))
+            query, len(q), hi - lo, int(pam_len), T))
+    at = hi - len(q) if pam3 else lo  # the guide ends where a 3' PAM begins, starts where a 5' PAM ends
     return "N" * at + q + "N" * (T - at - len(q))
 
 
@@ -206,41 +201,32 @@ class ArenaSearch:
         nat.check(nat.lib().crp_search_candidates(self._h, ctypes.byref(a), ctypes.byref(b)), "crp_search_candidates")
         return a.value, b.value
 
-    def run(self, queries, max_mm, site_cap):
-        """crp_search_run as it is: (status, counts (Q, M + 1) uint32, n_sites).  queries: already checked strings."""
+    def run(self, queries, max_mm, site_cap, kind=("-", 0), spans=None):
+        """crp_search_run, or crp_search_run_bulge for a bulge kind (this handle's pattern: the kind's window pattern), as
+        it is: (status, counts (Q, M + 1) uint32, n_sites).  queries: already checked strings; spans (bulge kinds): (Q, 2)
+        query positions of each span's first and last letter."""
+        bulge, size = kind
         Q = len(queries)
         blob = "".join(queries).encode()
         counts = np.zeros((Q, max_mm + 1), dtype=np.uint32)
         n = ctypes.c_uint64()
-        st = nat.lib().crp_search_run(self._h, blob, Q, int(max_mm), int(site_cap), counts.ctypes.data_as(nat.u32p), ctypes.byref(n))
+        tail = (int(max_mm), int(site_cap), counts.ctypes.data_as(nat.u32p), ctypes.byref(n))
+        if size:
+            sp = np.ascontiguousarray(spans, dtype=np.uint8).reshape(Q, 2)
+            code = nat.SEARCH_BULGE_DNA if bulge == "DNA" else nat.SEARCH_BULGE_RNA
+            st = nat.lib().crp_search_run_bulge(self._h, blob, Q, code, int(size), sp.ctypes.data_as(nat.u8p), *tail)
+        else:
+            st = nat.lib().crp_search_run(self._h, blob, Q, *tail)
         return st, counts, n.value
 
-    def fetch(self, n):
-        """(query u32, arena position u32, strand u8, mismatches u8) of the last run's n sites."""
-        cols = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, np.uint8), np.empty(n, np.uint8)
-        nat.check(nat.lib().crp_search_fetch(self._h, *[c.ctypes.data_as(p) for c, p in zip(cols, (nat.u32p, nat.u32p, nat.u8p, nat.u8p))], n),
-                  "crp_search_fetch")
-        return cols
-
-    def run_bulge(self, queries, bulge, size, spans, max_mm, site_cap):
-        """crp_search_run_bulge as it is (this handle's pattern: the kind's window pattern).  bulge "DNA" / "RNA";
-        spans: (Q, 2) query positions of each span's first and last letter."""
-        Q = len(queries)
-        blob = "".join(queries).encode()
-        sp = np.ascontiguousarray(spans, dtype=np.uint8).reshape(Q, 2)
-        counts = np.zeros((Q, max_mm + 1), dtype=np.uint32)
-        n = ctypes.c_uint64()
-        kind = nat.SEARCH_BULGE_DNA if bulge == "DNA" else nat.SEARCH_BULGE_RNA
-        st = nat.lib().crp_search_run_bulge(self._h, blob, Q, kind, int(size), sp.ctypes.data_as(nat.u8p), int(max_mm), int(site_cap),
-                                            counts.ctypes.data_as(nat.u32p), ctypes.byref(n))
-        return st, counts, n.value
-
-    def fetch_bulge(self, n):
-        """(query u32, arena position u32, strand u8, mismatches u8, bulge_at u8) of the last run's n sites."""
-        cols = np.empty(n, np.uint32), np.empty(n, np.uint32), np.empty(n, np.uint8), np.empty(n, np.uint8), np.empty(n, np.uint8)
-        ptrs = (nat.u32p, nat.u32p, nat.u8p, nat.u8p, nat.u8p)
-        nat.check(nat.lib().crp_search_fetch_bulge(self._h, *[c.ctypes.data_as(p) for c, p in zip(cols, ptrs)], n), "crp_search_fetch_bulge")
-        return cols
+    def fetch(self, n, kind=("-", 0)):
+        """(query u32, arena position u32, strand u8, mismatches u8) of the last run's n sites, and bulge_at u8 after a run
+        of a bulge kind."""
+        cols = [np.empty(n, np.uint32), np.empty(n, np.uint32)] + [np.empty(n, np.uint8) for _ in range(3 if kind[1] else 2)]
+        ptrs = [c.ctypes.data_as(p) for c, p in zip(cols, (nat.u32p, nat.u32p, nat.u8p, nat.u8p, nat.u8p))]
+        name = "crp_search_fetch_bulge" if kind[1] else "crp_search_fetch"
+        nat.check(getattr(nat.lib(), name)(self._h, *ptrs, n), name)
+        return tuple(cols)
 
     def stats(self):
         out = np.zeros(6, dtype=np.float64)
@@ -263,43 +249,55 @@ def search(genome, pattern, queries, max_mm, site_cap=None, budget=None, pam_len
     pattern = check_pattern(pattern)
     max_mm = check_max_mm(max_mm)
     queries = [check_query(pattern, q, pam_len) for q in queries]
-    if any(len(q) != len(pattern) for q in queries):
-        raise SearchInputError("every query needs %d letters" % len(pattern))
-    Q = len(queries)
-    counts = np.zeros((Q, max_mm + 1), dtype=np.uint64)
-    parts, n_total, cand = [], 0, [0, 0]
-    unlimited = site_cap is None
-    for a, group in zip(genome.arenas, genome.groups):
-        s = ArenaSearch(a, pattern, budget)
-        try:
-            npl, nmi = s.candidates()
-            cand[0] += npl
-            cand[1] += nmi
-            cap = (1 << 62) if unlimited else max(0, int(site_cap) - n_total)
-            st, c, n = s.run(queries, max_mm, cap)
-            if st not in (nat.CRP_OK, nat.CRP_ERR_CAPACITY):
-                nat.check(st, "crp_search_run", a._engine._ctx)
-            counts += c
-            n_total += n
-            if st == nat.CRP_OK:  # (an arena after the cap was reached ran with cap 0: nothing to fetch)
-                qi, pos, strand, mm = s.fetch(n)
-                offs = np.asarray(a.offsets, dtype=np.int64)
-                j = np.searchsorted(offs, pos.astype(np.int64), "right") - 1
-                part = np.empty(n, SITE_DTYPE)
-                part["query"] = qi
-                part["contig"] = np.asarray(group, dtype=np.uint32)[j] if n else 0
-                part["position"] = pos.astype(np.int64) - offs[j]
-                part["strand"] = np.where(strand == 0, b"+", b"-")
-                part["mismatches"] = mm
-                parts.append(part)
-        finally:
-            s.close()
-    counts = counts.astype(np.uint32)
-    if not unlimited and n_total > int(site_cap):
-        raise SiteCapacityError(counts, n_total, int(site_cap))
-    sites = np.concatenate(parts) if parts else np.empty(0, SITE_DTYPE)
-    order = np.lexsort((sites["strand"] == b"-", sites["position"], sites["contig"], sites["query"]))
-    return SearchResult(counts, sites[order], tuple(cand))
+    counts, sites, cands, n_total = _search_kinds(genome, pattern, None, queries, max_mm, [("-", 0)], None, site_cap, budget)
+    if site_cap is not None and n_total > int(site_cap):
+        raise SiteCapacityError(counts[:, 0], n_total, int(site_cap))
+    return SearchResult(counts[:, 0], sites[list(SITE_DTYPE.names)].astype(SITE_DTYPE), cands[0])
+
+
+def _search_kinds(genome, pattern, pam_len, queries, max_mm, kinds, spans, site_cap, budget):
+    """Every kind of `kinds` over every arena of `genome`, on checked input: one library handle per kind and arena, on
+    the kind's window pattern, and site_cap counts the sites of all kinds together.  Returns (counts (Q, kinds, M + 1)
+    uint32, BULGE_SITE_DTYPE sites ordered by query, kind, contig, position, strand, per kind (n_plus, n_minus), the
+    number of sites); the sites are only complete when that number is within site_cap."""
+    counts = np.zeros((len(queries), len(kinds), max_mm + 1), dtype=np.uint64)
+    parts, n_total, cands = [], 0, []
+    for k, kind in enumerate(kinds):
+        size = kind[1]
+        kp = kind_pattern(pattern, pam_len, *kind) if size else pattern
+        cand = [0, 0]
+        for a, group in zip(genome.arenas, genome.groups):
+            s = ArenaSearch(a, kp, budget)
+            try:
+                npl, nmi = s.candidates()
+                cand[0] += npl
+                cand[1] += nmi
+                cap = (1 << 62) if site_cap is None else max(0, int(site_cap) - n_total)
+                st, c, n = s.run(queries, max_mm, cap, kind, spans)
+                if st not in (nat.CRP_OK, nat.CRP_ERR_CAPACITY):
+                    nat.check(st, "crp_search_run_bulge" if size else "crp_search_run", a._engine._ctx)
+                counts[:, k] += c
+                n_total += n
+                if st == nat.CRP_OK:  # (an arena after the cap was reached ran with cap 0: nothing to fetch)
+                    qi, pos, strand, mm, *at = s.fetch(n, kind)
+                    offs = np.asarray(a.offsets, dtype=np.int64)
+                    j = np.searchsorted(offs, pos.astype(np.int64), "right") - 1
+                    part = np.empty(n, BULGE_SITE_DTYPE)
+                    part["query"] = qi
+                    part["kind"] = k
+                    part["bulge_size"] = size
+                    part["bulge_at"] = at[0] if size else 0
+                    part["contig"] = np.asarray(group, dtype=np.uint32)[j] if n else 0
+                    part["position"] = pos.astype(np.int64) - offs[j]
+                    part["strand"] = np.where(strand == 0, b"+", b"-")
+                    part["mismatches"] = mm
+                    parts.append(part)
+            finally:
+                s.close()
+        cands.append(tuple(cand))
+    sites = np.concatenate(parts) if parts else np.empty(0, BULGE_SITE_DTYPE)
+    order = np.lexsort((sites["strand"] == b"-", sites["position"], sites["contig"], sites["kind"], sites["query"]))
+    return counts.astype(np.uint32), sites[order], cands, n_total
 
 
 # ---------------------------------------------------------------- bulges
@@ -372,55 +370,12 @@ def search_bulges(genome, pattern, queries, max_mm, pam_len, dna_bulge, rna_bulg
     max_mm = check_max_mm(max_mm)
     D, R = check_bulges(pattern, pam_len, dna_bulge, rna_bulge)
     queries = [check_query(pattern, q, pam_len) for q in queries]
-    if any(len(q) != len(pattern) for q in queries):
-        raise SearchInputError("every query needs %d letters" % len(pattern))
     spans = query_spans(pattern, pam_len, queries, D, R) if D or R else np.zeros((len(queries), 2), np.uint8)
     kinds = bulge_kinds(D, R)
-    Q = len(queries)
-    counts = np.zeros((Q, len(kinds), max_mm + 1), dtype=np.uint64)
-    parts, n_total, cands = [], 0, []
-    unlimited = site_cap is None
-    for k, (bulge, size) in enumerate(kinds):
-        kp = kind_pattern(pattern, pam_len, bulge, size) if size else pattern
-        cand = [0, 0]
-        for a, group in zip(genome.arenas, genome.groups):
-            s = ArenaSearch(a, kp, budget)
-            try:
-                npl, nmi = s.candidates()
-                cand[0] += npl
-                cand[1] += nmi
-                cap = (1 << 62) if unlimited else max(0, int(site_cap) - n_total)
-                if size:
-                    st, c, n = s.run_bulge(queries, bulge, size, spans, max_mm, cap)
-                else:
-                    st, c, n = s.run(queries, max_mm, cap)
-                if st not in (nat.CRP_OK, nat.CRP_ERR_CAPACITY):
-                    nat.check(st, "crp_search_run_bulge" if size else "crp_search_run", a._engine._ctx)
-                counts[:, k] += c
-                n_total += n
-                if st == nat.CRP_OK:
-                    qi, pos, strand, mm, at = s.fetch_bulge(n)
-                    offs = np.asarray(a.offsets, dtype=np.int64)
-                    j = np.searchsorted(offs, pos.astype(np.int64), "right") - 1
-                    part = np.empty(n, BULGE_SITE_DTYPE)
-                    part["query"] = qi
-                    part["kind"] = k
-                    part["bulge_size"] = size
-                    part["bulge_at"] = at
-                    part["contig"] = np.asarray(group, dtype=np.uint32)[j] if n else 0
-                    part["position"] = pos.astype(np.int64) - offs[j]
-                    part["strand"] = np.where(strand == 0, b"+", b"-")
-                    part["mismatches"] = mm
-                    parts.append(part)
-            finally:
-                s.close()
-        cands.append(tuple(cand))
-    counts = counts.astype(np.uint32)
-    if not unlimited and n_total > int(site_cap):
+    counts, sites, cands, n_total = _search_kinds(genome, pattern, pam_len, queries, max_mm, kinds, spans, site_cap, budget)
+    if site_cap is not None and n_total > int(site_cap):
         raise SiteCapacityError(counts, n_total, int(site_cap))
-    sites = np.concatenate(parts) if parts else np.empty(0, BULGE_SITE_DTYPE)
-    order = np.lexsort((sites["strand"] == b"-", sites["position"], sites["contig"], sites["kind"], sites["query"]))
-    return BulgeSearchResult(counts, sites[order], kinds, spans, cands)
+    return BulgeSearchResult(counts, sites, kinds, spans, cands)
 
 
 # ---------------------------------------------------------------- TSV
@@ -432,29 +387,11 @@ for _c, _v in zip(b"ACGTUacgt", (0, 1, 2, 3, 0, 0, 1, 2, 3)):
 def site_string(contig, position, strand, query):
     """The oriented window: bases upper case, mismatched positions lower case, non-base characters N (n where the
     query compares them)."""
-    T = len(query)
-    codes = _CODE[np.frombuffer(contig[position:position + T], dtype=np.uint8)]
-    if strand in (b"-", "-"):
-        codes = np.where(codes == 4, 4, 3 - codes)[::-1]
-    out = []
-    for p, c in enumerate(codes):
-        ch = "ACGTN"[c]
-        q = query[p]
-        if q != "N" and (c == 4 or ch != q):
-            ch = ch.lower()
-        out.append(ch)
-    return "".join(out)
+    return bulge_alignment(contig, position, strand, query, "-", 0, 0)[0]
 
 
 def format_sites(names, queries, contig_names, contigs, sites):
-    lines = ["name\tquery\tcontig\tposition\tstrand\tmismatches\tsite\n"]
-    for s in sites:
-        q = int(s["query"])
-        k = int(s["contig"])
-        lines.append("%s\t%s\t%s\t%d\t%s\t%d\t%s\n" % (names[q], queries[q], contig_names[k], int(s["position"]),
-                                                      s["strand"].decode(), int(s["mismatches"]),
-                                                      site_string(contigs[k], int(s["position"]), s["strand"], queries[q])))
-    return "".join(lines)
+    return _format_site_rows(names, queries, contig_names, contigs, sites, None, None)
 
 
 def bulge_alignment(contig, position, strand, query, bulge, size, s):
@@ -484,33 +421,42 @@ def bulge_alignment(contig, position, strand, query, bulge, size, s):
 def format_bulge_sites(names, queries, contig_names, contigs, res):
     """The sites TSV of a bulge search (BulgeSearchResult): today's columns plus bulge (-, DNA, RNA), bulge_size,
     bulge_at, and the aligned site and query."""
-    lines = ["name\tquery\tcontig\tposition\tstrand\tmismatches\tbulge\tbulge_size\tbulge_at\tsite\tquery_aligned\n"]
-    for r in res.sites:
-        q, k, kind = int(r["query"]), int(r["contig"]), int(r["kind"])
-        bulge, size = res.kinds[kind]
-        at = int(r["bulge_at"])
-        site, qa = bulge_alignment(contigs[k], int(r["position"]), r["strand"], queries[q], bulge, size,
-                                   int(res.spans[q, 0]) + at)
-        lines.append("%s\t%s\t%s\t%d\t%s\t%d\t%s\t%d\t%d\t%s\t%s\n" % (
-            names[q], queries[q], contig_names[k], int(r["position"]), r["strand"].decode(), int(r["mismatches"]),
-            bulge, size, at, site, qa))
+    return _format_site_rows(names, queries, contig_names, contigs, res.sites, res.kinds, res.spans)
+
+
+def _format_site_rows(names, queries, contig_names, contigs, sites, kinds, spans):
+    """The sites TSV; with the kinds and spans of a bulge search, the bulge columns and the aligned query too."""
+    head = ["name", "query", "contig", "position", "strand", "mismatches"]
+    lines = ["\t".join(head + (["bulge", "bulge_size", "bulge_at", "site", "query_aligned"] if kinds else ["site"])) + "\n"]
+    for r in sites:
+        q, k, pos, strand = int(r["query"]), int(r["contig"]), int(r["position"]), r["strand"]
+        row = [names[q], queries[q], contig_names[k], pos, strand.decode(), int(r["mismatches"])]
+        if kinds:
+            (bulge, size), at = kinds[int(r["kind"])], int(r["bulge_at"])
+            site, qa = bulge_alignment(contigs[k], pos, strand, queries[q], bulge, size, int(spans[q, 0]) + at)
+            row += [bulge, size, at, site, qa]
+        else:
+            row.append(site_string(contigs[k], pos, strand, queries[q]))
+        lines.append("\t".join(map(str, row)) + "\n")
     return "".join(lines)
 
 
 def format_bulge_counts(names, queries, kinds, counts):
-    M = counts.shape[2] - 1
-    lines = ["name\tquery\tbulge\tbulge_size\t" + "\t".join("mm%d" % k for k in range(M + 1)) + "\n"]
-    for q in range(len(queries)):
-        for k, (bulge, size) in enumerate(kinds):
-            lines.append("%s\t%s\t%s\t%d\t%s\n" % (names[q], queries[q], bulge, size, "\t".join(str(int(v)) for v in counts[q, k])))
-    return "".join(lines)
+    return _format_count_rows(names, queries, counts, kinds)
 
 
 def format_counts(names, queries, counts):
-    M = counts.shape[1] - 1
-    lines = ["name\tquery\t" + "\t".join("mm%d" % k for k in range(M + 1)) + "\n"]
+    return _format_count_rows(names, queries, counts[:, None], None)
+
+
+def _format_count_rows(names, queries, counts, kinds):
+    """The counts TSV of counts (Q, kinds, M + 1): one line per query and kind; with the kinds of a bulge search, the
+    bulge and bulge_size columns too."""
+    head = ["name", "query"] + (["bulge", "bulge_size"] if kinds else []) + ["mm%d" % k for k in range(counts.shape[2])]
+    lines = ["\t".join(head) + "\n"]
     for q in range(len(queries)):
-        lines.append("%s\t%s\t%s\n" % (names[q], queries[q], "\t".join(str(int(v)) for v in counts[q])))
+        for k, kind in enumerate(kinds or [()]):
+            lines.append("\t".join(map(str, [names[q], queries[q], *kind, *counts[q, k].tolist()])) + "\n")
     return "".join(lines)
 
 
@@ -553,28 +499,21 @@ def main(argv=None):
     with Engine(args.device) as eng:
         g = eng.genome(contigs)
         try:
-            if D or R:
-                res = search_bulges(g, pattern, queries, max_mm, args.pam_length, D, R)
-            else:
-                res = search(g, pattern, queries, max_mm)
+            res = search_bulges(g, pattern, queries, max_mm, args.pam_length, D, R)
         finally:
             g.close()
-    if D or R:
-        with open(args.output, "w") as f:
-            f.write(format_bulge_sites(names, queries, contig_names, contigs, res))
-        if args.counts:
-            with open(args.counts, "w") as f:
-                f.write(format_bulge_counts(names, queries, res.kinds, res.counts))
-        print("%d guides, %d kinds, %d sites within %d mismatches" % (len(queries), len(res.kinds), res.sites.size, max_mm),
-              file=sys.stderr)
-        return 0
+    kinds = res.kinds if D or R else None  # (None: the plain TSV columns)
     with open(args.output, "w") as f:
-        f.write(format_sites(names, queries, contig_names, contigs, res.sites))
+        f.write(_format_site_rows(names, queries, contig_names, contigs, res.sites, kinds, res.spans))
     if args.counts:
         with open(args.counts, "w") as f:
-            f.write(format_counts(names, queries, res.counts))
-    print("%d guides, %d + %d candidate sites, %d sites within %d mismatches" % (
-        len(queries), res.candidates[0], res.candidates[1], res.sites.size, max_mm), file=sys.stderr)
+            f.write(_format_count_rows(names, queries, res.counts, kinds))
+    if D or R:
+        print("%d guides, %d kinds, %d sites within %d mismatches" % (len(queries), len(res.kinds), res.sites.size, max_mm),
+              file=sys.stderr)
+    else:
+        print("%d guides, %d + %d candidate sites, %d sites within %d mismatches" % (
+            len(queries), res.candidates[0][0], res.candidates[0][1], res.sites.size, max_mm), file=sys.stderr)
     return 0
 
 

@@ -315,11 +315,11 @@ def test_gpu_bulges_arenas_chunks_launches(engine):
         try:
             h.set_limits(batch_queries=3, first_site_slots=8)
             spans = srch.query_spans(SPCAS9, 3, queries, 2, 0)
-            st, c, n = h.run_bulge(queries, "DNA", 2, spans, 3, 1 << 40)
+            st, c, n = h.run(queries, 3, 1 << 40, ("DNA", 2), spans)
             want = [r for r in rows if r[1] == 2]
             assert st == nat.CRP_OK and n == len(want) > 8 and (c == counts[:, 2]).all()
             assert h.stats()["compare_launches"] == 2 * 14
-            qi, pos, strand, mm, at = h.fetch_bulge(n)
+            qi, pos, strand, mm, at = h.fetch(n, ("DNA", 2))
             offs = np.asarray(one.arenas[0].offsets, dtype=np.int64)
             j = np.searchsorted(offs, pos.astype(np.int64), "right") - 1
             got = list(zip(qi.tolist(), [2] * n, j.tolist(), (pos.astype(np.int64) - offs[j]).tolist(), strand.tolist(),
@@ -347,11 +347,11 @@ def test_gpu_bulge_capacity_and_misuse(engine):
     try:
         spans = srch.query_spans(SPCAS9, 3, [q], 0, 1)
         n_rna = sum(1 for r in rows if r[1] == 2)
-        st, c, n = h.run_bulge([q], "RNA", 1, spans, 4, 10)
+        st, c, n = h.run([q], 4, 10, ("RNA", 1), spans)
         assert st == nat.CRP_ERR_CAPACITY and n == n_rna and (c == counts[:, 2]).all()
         with pytest.raises(nat.CropsrHipError):
-            h.fetch_bulge(n)
-        st, c, n = h.run_bulge([q], "RNA", 1, spans, 4, n_rna)
+            h.fetch(n, ("RNA", 1))
+        st, c, n = h.run([q], 4, n_rna, ("RNA", 1), spans)
         assert st == nat.CRP_OK and n == n_rna
         with pytest.raises(srch.SiteCapacityError) as e:
             g.search_bulges(SPCAS9, [q], 4, 3, 1, 1, site_cap=need - 1)

@@ -78,8 +78,8 @@ def bulge_main(args, contigs, guides, out):
             cand = sum(sum(s.candidates()) for s in searches)
             n_sites = 0
             for s in searches:
-                st, _, n = s.run_bulge(queries, bulge, size, spans, MAX_MM, 1 << 40) if size else s.run(queries, MAX_MM, 1 << 40)
-                nat.check(st, "crp_search_run_bulge")
+                st, _, n = s.run(queries, MAX_MM, 1 << 40, (bulge, size), spans)
+                nat.check(st, "crp_search_run")
                 n_sites += n
             st1 = [s.stats() for s in searches]
             extract_ms = sum(x["extract_ms"] for x in st1)
