@@ -129,6 +129,9 @@ SIGNATURES = {
     "crp_search_run_bulge": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, u8p,
                                              ctypes.c_int, ctypes.c_uint64, u32p, u64p]),
     "crp_search_fetch_bulge": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, u8p, u8p, u8p, ctypes.c_uint64]),
+    "crp_search_set_scheme": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int, ctypes.c_int, f64p]),
+    "crp_search_run_scored": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, u32p, u64p,
+                                              u64p]),
     "crp_configure": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]),
     "crp_query": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     "crp_build_id": (ctypes.c_char_p, []),
@@ -160,6 +163,8 @@ OT_SEEDS = 1 << 24
 OT_NOT_A_SITE, OT_NOT_OWNED = 0xFFFFFFFF, 0xFFFFFFFE
 ABI_VERSION = 6
 SEARCH_BULGE_DNA, SEARCH_BULGE_RNA = 1, 2
+SEARCH_PAM_3PRIME, SEARCH_PAM_5PRIME = 0, 1
+SEARCH_SHAPE_DOUBLES = 288
 CRP_ERR_INVALID = -1
 CRP_ERR_NO_DEVICE = -2
 CRP_ERR_UNSUPPORTED = -7

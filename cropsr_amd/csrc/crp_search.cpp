@@ -9,7 +9,11 @@
 //          caller.  crp_search_run and crp_search_run_bulge are the same run of different kinds: plain, or a DNA or RNA
 //          bulge on a handle whose pattern is the window pattern of that bulge (Bulges).  The kind
 //          picks the compare kernel, the pairs per launch, the query limit and the site word and sort-key layout.
+//          crp_search_run_scored is the plain kind with the scoring compare: per-query sums of hit values under the
+//          handle's scheme (crp_search_set_scheme; DESIGN section 15, Specificity score), zeroed with the counts at the
+//          start of every pass, so a repeated pass does not add a hit twice.
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -59,13 +63,15 @@ uint32_t complement_set(uint32_t s) { return ((s & 1) << 1) | ((s & 2) >> 1) | (
 // placement (at_bits() bits) between the strand and the mismatches.
 struct Kind {
     int dna = 0, rna = 0;
+    bool scored = false;  // (plain kind only) the scoring compare: also sums the hits' values
     bool bulge() const { return dna || rna; }
     int at_bits() const { return bulge() ? 5 : 0; }
     uint64_t pairs_per_launch() const { return bulge() ? kBulgePairsPerLaunch : kPairsPerLaunch; }
     uint64_t max_queries() const { return bulge() ? kMaxBulgeQueries : kMaxQueries; }
     hipError_t compare(hipStream_t st, const crp::SearchCands &c, uint32_t n, const uint4 *queries, uint32_t q0, uint32_t nq, int max_mm,
-                       uint32_t *counts, uint2 *sites, uint64_t site_cap, unsigned long long *site_ctr) const
+                       uint32_t *counts, uint2 *sites, uint64_t site_cap, unsigned long long *site_ctr, const crp::SearchScore &score) const
     {
+        if (scored) return crp::launch_search_score_compare(st, c, n, queries, q0, nq, max_mm, counts, sites, site_cap, site_ctr, score);
         if (bulge()) return crp::launch_search_bulge_compare(st, c, n, queries, q0, nq, max_mm, dna, rna, counts, sites, site_cap, site_ctr);
         return crp::launch_search_compare(st, c, n, queries, q0, nq, max_mm, counts, sites, site_cap, site_ctr);
     }
@@ -118,6 +124,13 @@ struct crp_search {
     uint2 *d_sites = nullptr;
     uint64_t sites_cap = 0;
     unsigned long long *d_ctr = nullptr;
+    // scheme (crp_search_set_scheme): the walk and shape tables on the device, the positions that have a factor
+    double *d_scheme = nullptr;
+    bool have_scheme = false;
+    int scheme_rev = 0;
+    uint32_t scheme_region = 0;
+    unsigned long long *d_hit_sum = nullptr;
+    uint64_t hit_sum_cap = 0;
     std::vector<uint64_t> keys;  // sites of the last successful run, as pack_key of its kind
     bool have_sites = false;
     Kind keys_kind;              // the kind of the last run
@@ -190,6 +203,8 @@ int run_pass(crp_search *s, uint32_t n_queries, int max_mm, uint64_t dev_sites, 
     const crp::Planes pl{{a->d_plane[0], a->d_plane[1], a->d_plane[2], a->d_plane[3]}};
     CRP_HIP(ctx, hipMemsetAsync(s->d_counts, 0, (size_t)n_queries * (max_mm + 1) * sizeof(uint32_t), ctx->stream));
     CRP_HIP(ctx, hipMemsetAsync(s->d_ctr, 0, sizeof(unsigned long long), ctx->stream));
+    if (kind.scored) CRP_HIP(ctx, hipMemsetAsync(s->d_hit_sum, 0, (size_t)n_queries * sizeof(unsigned long long), ctx->stream));
+    const crp::SearchScore score{s->d_scheme, s->scheme_rev, s->d_hit_sum};
     const int n_chunks = (int)s->chunk_n.size();
     for (int c = 0; c < n_chunks; ++c) {
         const uint64_t n = s->chunk_n[c];
@@ -208,7 +223,7 @@ int run_pass(crp_search *s, uint32_t n_queries, int max_mm, uint64_t dev_sites, 
         for (uint32_t q0 = 0; q0 < n_queries; q0 += batch) {
             const uint32_t nq = std::min(batch, n_queries - q0);
             CRP_HIP(ctx, kind.compare(ctx->stream, s->cands(), (uint32_t)n, s->d_queries, q0, nq, max_mm, s->d_counts, s->d_sites, dev_sites,
-                                      s->d_ctr));
+                                      s->d_ctr, score));
             ++launches;
         }
         CRP_HIP(ctx, hipEventRecord(s->ev[2], ctx->stream));
@@ -294,6 +309,8 @@ int crp_search_destroy(crp_search *s)
     (void)hipFree(s->d_counts);
     (void)hipFree(s->d_sites);
     (void)hipFree(s->d_ctr);
+    (void)hipFree(s->d_scheme);
+    (void)hipFree(s->d_hit_sum);
     for (hipEvent_t e : s->ev)
         if (e) (void)hipEventDestroy(e);
     delete s;
@@ -313,6 +330,39 @@ int crp_search_set_limits(crp_search *s, uint64_t batch_queries, uint64_t first_
     if (!s) return CRP_ERR_INVALID;
     s->batch_queries = batch_queries ? batch_queries : kBatchQueries;
     s->site_start = first_site_slots ? first_site_slots : kSiteStart;
+    return CRP_OK;
+}
+
+int crp_search_set_scheme(crp_search *s, const double *factor, int n_factor, int pam_side, const double *shape)
+{
+    if (!s) return CRP_ERR_INVALID;
+    if (!factor) {
+        s->have_scheme = false;
+        return CRP_OK;
+    }
+    const int T = s->sets.T;
+    if (!shape || n_factor < 1 || n_factor > T || (pam_side != CRP_SEARCH_PAM_3PRIME && pam_side != CRP_SEARCH_PAM_5PRIME))
+        return CRP_ERR_INVALID;
+    const auto in_unit = [](double v) { return std::isfinite(v) && v >= 0.0 && v <= 1.0; };
+    if (!std::all_of(factor, factor + n_factor, in_unit) || !std::all_of(shape, shape + CRP_SEARCH_SHAPE_DOUBLES, in_unit))
+        return CRP_ERR_INVALID;
+    // The walk table.  PAM on the 3' side: the guide region is positions 0 .. G - 1 and g is the position, so the mask is
+    // walked as it is.  PAM on the 5' side: the region is positions T - G .. T - 1 and g = T - 1 - position; the kernel
+    // walks the bit-reversed mask, where position p is bit 31 - p, so g = b - (32 - T) ascends with the bit again.
+    double tab[crp::SEARCH_SCORE_TAB];
+    std::fill(tab, tab + crp::SEARCH_SCORE_WALK, 1.0);
+    const int rev = pam_side == CRP_SEARCH_PAM_5PRIME;
+    for (int g = 0; g < n_factor; ++g) tab[rev ? g + 32 - T : g] = factor[g];
+    std::copy(shape, shape + CRP_SEARCH_SHAPE_DOUBLES, tab + crp::SEARCH_SCORE_WALK);
+    crp_ctx *ctx = s->ctx;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    if (!s->d_scheme) CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->d_scheme), sizeof(tab)));
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (no run of this handle's stream is in flight, but say so)
+    CRP_HIP(ctx, hipMemcpy(s->d_scheme, tab, sizeof(tab), hipMemcpyHostToDevice));
+    const uint32_t low = n_factor == 32 ? ~0u : (1u << n_factor) - 1u;
+    s->scheme_region = rev ? low << (T - n_factor) : low;
+    s->scheme_rev = rev;
+    s->have_scheme = true;
     return CRP_OK;
 }
 
@@ -355,7 +405,7 @@ bool encode_queries(const char *queries, uint64_t n_queries, int T, std::vector<
 
 // the capacity protocol over encoded queries of one kind; span_first: per query, what bulge_at counts from
 int run_encoded(crp_search *s, const std::vector<uint4> &enc, Kind kind, const std::vector<uint8_t> &span_first, int max_mm,
-                uint64_t site_cap, uint32_t *counts, uint64_t *n_sites)
+                uint64_t site_cap, uint32_t *counts, uint64_t *n_sites, uint64_t *hit_sum)
 {
     const uint64_t n_queries = enc.size();
     s->have_sites = false;
@@ -373,6 +423,9 @@ int run_encoded(crp_search *s, const std::vector<uint4> &enc, Kind kind, const s
     if ((rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_queries), &s->q_cap, n_queries, sizeof(uint4))) != CRP_OK) return rc;
     if ((rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_counts), &s->counts_cap, n_counts, sizeof(uint32_t))) != CRP_OK) return rc;
     if (!s->d_ctr) CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->d_ctr), sizeof(unsigned long long)));
+    if (kind.scored &&
+        (rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_hit_sum), &s->hit_sum_cap, n_queries, sizeof(unsigned long long))) != CRP_OK)
+        return rc;
     uint64_t dev_sites = std::min(site_cap, std::max(s->sites_cap, s->site_start));
     if (dev_sites && (rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_sites), &s->sites_cap, dev_sites, sizeof(uint2))) != CRP_OK)
         return rc;
@@ -388,6 +441,7 @@ int run_encoded(crp_search *s, const std::vector<uint4> &enc, Kind kind, const s
             return rc;
     }
     if (counts) CRP_HIP(ctx, hipMemcpy(counts, s->d_counts, n_counts * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    if (kind.scored) CRP_HIP(ctx, hipMemcpy(hit_sum, s->d_hit_sum, n_queries * sizeof(uint64_t), hipMemcpyDeviceToHost));
     *n_sites = total;
     if (total > site_cap) return CRP_ERR_CAPACITY;
     std::vector<uint2> raw(total);
@@ -407,13 +461,16 @@ int run_encoded(crp_search *s, const std::vector<uint4> &enc, Kind kind, const s
 // crp_search_run(_bulge) past the checks of its own arguments; span: per query, the first and last letter of its span
 // (bulge kinds only)
 int run_kind(crp_search *s, const char *queries, uint64_t n_queries, Kind kind, const uint8_t *span, int max_mm, uint64_t site_cap,
-             uint32_t *counts, uint64_t *n_sites)
+             uint32_t *counts, uint64_t *n_sites, uint64_t *hit_sum = nullptr)
 {
     if (max_mm < 0 || max_mm > CRP_SEARCH_MAX_MM || n_queries >= kind.max_queries()) return CRP_ERR_UNSUPPORTED;
     const int T = s->sets.T - kind.dna + kind.rna;  // the query's length
     if (T < 1 || T > CRP_SEARCH_MAX_T) return CRP_ERR_UNSUPPORTED;
     std::vector<uint4> enc;
     if (!encode_queries(queries, n_queries, T, enc)) return CRP_ERR_INVALID;
+    if (kind.scored)  // a base outside the guide region would mismatch where no factor is
+        for (const uint4 &q : enc)
+            if (q.z & ~s->scheme_region) return CRP_ERR_INVALID;
     std::vector<uint8_t> span_first(n_queries);  // (0 for a plain run: its sites have no placement)
     if (kind.bulge())
         for (uint64_t q = 0; q < n_queries; ++q) {
@@ -424,7 +481,7 @@ int run_kind(crp_search *s, const char *queries, uint64_t n_queries, Kind kind, 
             enc[q].w = (uint32_t)s_min | (uint32_t)s_max << 8;
             span_first[q] = (uint8_t)first;
         }
-    return run_encoded(s, enc, kind, span_first, max_mm, site_cap, counts, n_sites);
+    return run_encoded(s, enc, kind, span_first, max_mm, site_cap, counts, n_sites, hit_sum);
 }
 
 }  // namespace
@@ -436,6 +493,16 @@ int crp_search_run(crp_search *s, const char *queries, uint64_t n_queries, int m
 {
     if (!s || !n_sites || (n_queries && !queries)) return CRP_ERR_INVALID;
     return run_kind(s, queries, n_queries, Kind{}, nullptr, max_mm, site_cap, counts, n_sites);
+}
+
+int crp_search_run_scored(crp_search *s, const char *queries, uint64_t n_queries, int max_mm, uint64_t site_cap, uint32_t *counts,
+                          uint64_t *n_sites, uint64_t *hit_sum)
+{
+    if (!s || !n_sites || (n_queries && (!queries || !hit_sum))) return CRP_ERR_INVALID;
+    if (!s->have_scheme) return CRP_ERR_STATE;
+    Kind kind;
+    kind.scored = true;
+    return run_kind(s, queries, n_queries, kind, nullptr, max_mm, site_cap, counts, n_sites, hit_sum);
 }
 
 int crp_search_run_bulge(crp_search *s, const char *queries, uint64_t n_queries, int kind, int size, const uint8_t *span, int max_mm,

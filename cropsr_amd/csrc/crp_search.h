@@ -27,6 +27,19 @@ struct SearchCands {
     uint32_t *pos;           // forward start in the arena | strand << 31 ('-' = 1)
 };
 
+// A scoring scheme on the device (Specificity score) and where a scored run sums.  tab holds
+// SEARCH_SCORE_WALK factors in the order the kernel walks a mismatch mask (bit b of the mask, or of the bit-reversed mask
+// when rev: ascending g either way), then shape[n][d] for n = 0 .. SEARCH_MAX_MM mismatches over a spread of d positions.
+constexpr int SEARCH_SCORE_WALK = 32;
+constexpr int SEARCH_SCORE_SPREAD = 32;
+constexpr int SEARCH_SCORE_TAB = SEARCH_SCORE_WALK + (SEARCH_MAX_MM + 1) * SEARCH_SCORE_SPREAD;
+constexpr int SEARCH_SCORE_SHIFT = 30;  // a hit's value is rint(h * 2^30)
+struct SearchScore {
+    const double *tab;            // SEARCH_SCORE_TAB doubles, each in [0, 1]
+    int rev;                      // walk the bit-reversed mask (g descends with the pattern position: PAM on the 5' side)
+    unsigned long long *hit_sum;  // per query: the sum of its hits' values
+};
+
 // Per workgroup of SEARCH_WORDS words: {'+' candidates, '-' candidates}.
 hipError_t launch_search_count(hipStream_t s, const Planes &pl, uint64_t used_words, const SearchSets &sets, uint2 *block_cnt);
 // Writes the candidates of workgroups [block_first, block_first + n_blocks): those of workgroup b start at block_off[b]
@@ -38,6 +51,11 @@ hipError_t launch_search_emit(hipStream_t s, const Planes &pl, uint64_t used_wor
 // counted in *site_ctr, not written).
 hipError_t launch_search_compare(hipStream_t s, const SearchCands &c, uint32_t n, const uint4 *queries, uint32_t q0, uint32_t nq,
                                  int max_mm, uint32_t *counts, uint2 *sites, uint64_t site_cap, unsigned long long *site_ctr);
+// launch_search_compare plus the score: every pair with 1 .. max_mm mismatches also adds its value to score.hit_sum[q].
+// No query may have a base at a position without a factor (outside the guide region).
+hipError_t launch_search_score_compare(hipStream_t s, const SearchCands &c, uint32_t n, const uint4 *queries, uint32_t q0, uint32_t nq,
+                                       int max_mm, uint32_t *counts, uint2 *sites, uint64_t site_cap, unsigned long long *site_ctr,
+                                       const SearchScore &score);
 // The same for the windows of one bulge kind (Bulges): candidates of T + dna or T - rna characters
 // (one of dna, rna is 0, the other 1 or 2), queries of T letters as {hi, lo, compare mask, s_min | s_max << 8} (the
 // placements s of the bulge's first query position).  Every pair whose fewest mismatches over s is within max_mm adds

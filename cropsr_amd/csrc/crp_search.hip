@@ -14,7 +14,8 @@
 //   compare     candidates in registers, SEARCH_CPL per lane; the queries of a batch are wave-uniform (scalar loads).
 //               Per pair: popc(((h ^ qh) | (l ^ ql) | nb) & qm) <= M.  Hits are rare: a wave ballots them and reserves
 //               its slots with one atomic.  The bulge compare (DNA or RNA bulge of one size) takes, per pair, the best
-//               placement of the bulge inside the query's span; see search_bulge_compare_kernel.
+//               placement of the bulge inside the query's span; see search_bulge_compare_kernel.  The scoring compare
+//               (search_score_compare_kernel) also adds every hit's value under a weighting scheme to a per-query sum.
 //
 // Only vector stores and vector atomics, like the rest of the library.
 #include "crp_search.h"
@@ -213,6 +214,69 @@ __global__ __launch_bounds__(BLOCK) void search_compare_kernel(SearchCands c, ui
     }
 }
 
+// The value of one hit under the scheme (Specificity score): the factors of the mask's bits, walked
+// in ascending g, times shape[n][d], as round-to-nearest-even of h * 2^30.  Every step is one correctly rounded f64
+// multiply (__dmul_rn: nothing to fuse or reorder), so the host's numpy statement gives the same integer.  A handle
+// whose g runs against the bit order (PAM on the 5' side) walks the reversed mask; its walk table is laid out for that.
+__device__ __forceinline__ uint32_t hit_value(uint32_t mask, int n, const SearchScore &sc)
+{
+    uint32_t m = sc.rev ? __builtin_bitreverse32(mask) : mask;
+    const int d = 31 - __builtin_clz(mask) - __builtin_ctz(mask);  // last - first mismatching position (mask != 0)
+    double hv = 1.0;
+    while (m) {
+        hv = __dmul_rn(hv, sc.tab[__builtin_ctz(m)]);
+        m &= m - 1;
+    }
+    hv = __dmul_rn(hv, sc.tab[SEARCH_SCORE_WALK + n * SEARCH_SCORE_SPREAD + d]);
+    return (uint32_t)__builtin_rint(__dmul_rn(hv, (double)(1u << SEARCH_SCORE_SHIFT)));  // factors and shape are in [0, 1]: <= 2^30
+}
+
+// search_compare_kernel plus the per-query sum of hit values: the same candidates per lane and the same no-hit loop; a
+// lane with a hit of 1 .. max_mm mismatches forms its mask again and adds the hit's value to hit_sum[q] with one 64-bit
+// vector atomic.  The queries of a scored run have no base outside the guide region (checked on the host), so every
+// bit of the mask has a factor.
+__global__ __launch_bounds__(BLOCK) void search_score_compare_kernel(SearchCands c, uint32_t n, const uint4 *__restrict__ queries, uint32_t q0,
+                                                                     uint32_t nq, int max_mm, uint32_t *__restrict__ counts,
+                                                                     uint2 *__restrict__ sites, uint64_t site_cap,
+                                                                     unsigned long long *__restrict__ site_ctr, SearchScore sc)
+{
+    const uint32_t first = blockIdx.x * (BLOCK * SEARCH_CPL) + threadIdx.x;
+    uint32_t h[SEARCH_CPL], l[SEARCH_CPL], nb[SEARCH_CPL];
+    int lim[SEARCH_CPL];  // max_mm, or -1 past the end: a lane without a candidate never hits
+#pragma unroll
+    for (int j = 0; j < SEARCH_CPL; ++j) {
+        const uint32_t i = first + j * BLOCK;
+        const bool ok = i < n;
+        h[j] = ok ? c.hi[i] : 0u;
+        l[j] = ok ? c.lo[i] : 0u;
+        nb[j] = ok ? c.nb[i] : 0u;
+        lim[j] = ok ? max_mm : -1;
+    }
+    const uint32_t stride = (uint32_t)max_mm + 1;
+    for (uint32_t qi = q0; qi < q0 + nq; ++qi) {
+        const uint4 q = queries[qi];  // wave-uniform
+        int mm[SEARCH_CPL];
+        bool any = false;
+#pragma unroll
+        for (int j = 0; j < SEARCH_CPL; ++j) {
+            mm[j] = __popc(((h[j] ^ q.x) | (l[j] ^ q.y) | nb[j]) & q.z);
+            any |= mm[j] <= lim[j];
+        }
+        if (__builtin_expect(any, 0)) {
+#pragma unroll
+            for (int j = 0; j < SEARCH_CPL; ++j) {
+                const bool hit = mm[j] <= lim[j];
+                append_hits(hit, qi, mm[j], qi << 4 | (uint32_t)mm[j], c.pos + (first + j * BLOCK), stride, counts, sites, site_cap,
+                            site_ctr);
+                if (hit && mm[j] > 0) {
+                    const uint32_t mask = ((h[j] ^ q.x) | (l[j] ^ q.y) | nb[j]) & q.z;
+                    atomicAdd(&sc.hit_sum[qi], (unsigned long long)hit_value(mask, mm[j], sc));
+                }
+            }
+        }
+    }
+}
+
 // (x ^ q) | y in one v_bitop3_b32 (truth table over x, q, y = 0xF0, 0xCC, 0xAA): the compiler leaves it as xor + or3
 __device__ __forceinline__ uint32_t xor_or(uint32_t x, uint32_t q, uint32_t y) { return __builtin_amdgcn_bitop3_b32(x, q, y, 0xBE); }
 
@@ -312,6 +376,17 @@ hipError_t launch_search_compare(hipStream_t s, const SearchCands &c, uint32_t n
     if (!n || !nq) return hipSuccess;
     const uint32_t blocks = (uint32_t)(((uint64_t)n + BLOCK * SEARCH_CPL - 1) / (BLOCK * SEARCH_CPL));
     search_compare_kernel<<<dim3(blocks), dim3(BLOCK), 0, s>>>(c, n, queries, q0, nq, max_mm, counts, sites, site_cap, site_ctr);
+    return hipGetLastError();
+}
+
+hipError_t launch_search_score_compare(hipStream_t s, const SearchCands &c, uint32_t n, const uint4 *queries, uint32_t q0, uint32_t nq,
+                                       int max_mm, uint32_t *counts, uint2 *sites, uint64_t site_cap, unsigned long long *site_ctr,
+                                       const SearchScore &score)
+{
+    if (!n || !nq) return hipSuccess;
+    const uint32_t blocks = (uint32_t)(((uint64_t)n + BLOCK * SEARCH_CPL - 1) / (BLOCK * SEARCH_CPL));
+    search_score_compare_kernel<<<dim3(blocks), dim3(BLOCK), 0, s>>>(c, n, queries, q0, nq, max_mm, counts, sites, site_cap, site_ctr,
+                                                                     score);
     return hipGetLastError();
 }
 

@@ -751,17 +751,20 @@ class Genome:
                 h.feat_plus, h.feat_minus = f
         return GenomeHits(self, per_arena)
 
-    def search(self, pattern, queries, max_mm, site_cap=None, budget=None, pam_len=None):
+    def search(self, pattern, queries, max_mm, site_cap=None, budget=None, pam_len=None, score=None, sites=True):
         """Every site within max_mm mismatches of each query guide, over all arenas (search.search: the off-target
-        search of given guides).  Returns search.SearchResult (.counts, .sites)."""
+        search of given guides).  Returns search.SearchResult (.counts, .sites; with score= also .hit_sum and
+        .specificity, summed on the device; sites=False keeps no site list)."""
         from . import search
-        return search.search(self, pattern, queries, max_mm, site_cap=site_cap, budget=budget, pam_len=pam_len)
+        return search.search(self, pattern, queries, max_mm, site_cap=site_cap, budget=budget, pam_len=pam_len, score=score,
+                             sites=sites)
 
-    def search_bulges(self, pattern, queries, max_mm, pam_len, dna_bulge, rna_bulge, site_cap=None, budget=None):
+    def search_bulges(self, pattern, queries, max_mm, pam_len, dna_bulge, rna_bulge, site_cap=None, budget=None, score=None, sites=True):
         """search() plus the sites with a DNA or RNA bulge (search.search_bulges).  Returns search.BulgeSearchResult
         (.counts (Q, kinds, M + 1), .sites with kind, bulge_size and bulge_at, .kinds)."""
         from . import search
-        return search.search_bulges(self, pattern, queries, max_mm, pam_len, dna_bulge, rna_bulge, site_cap=site_cap, budget=budget)
+        return search.search_bulges(self, pattern, queries, max_mm, pam_len, dna_bulge, rna_bulge, site_cap=site_cap, budget=budget,
+                                    score=score, sites=sites)
 
     def close(self):
         for a in self.arenas:

@@ -6,6 +6,8 @@ arenas the genome already sits in; this module validates input, maps arena posit
 
     python -m cropsr_amd.search -f genome.fa --pattern NNNNNNNNNNNNNNNNNNNNNRG --pam-length 3 --guides guides.txt -m 4 \
         -o sites.tsv
+    python -m cropsr_amd.search -f genome.fa --pattern NNNNNNNNNNNNNNNNNNNNNGG --pam-length 3 --guides guides.txt -m 4 \
+        --score hsu2013 --no-sites --counts ranking.tsv
 
 Definition (what the tests check):
   genome   FASTA records, parsed plainly (read_fasta): name = header up to its first whitespace, sequence = the
@@ -33,6 +35,15 @@ guide region is the T - P positions outside the PAM (all N in the pattern), on i
            bulge_at = s - span_first for the smallest s that reaches them; ordered by query, kind, contig, position,
            strand.  No merging across kinds.  D, R in 0..2 and T + D <= 32; a span too short for a bulge (DNA: 2
            letters, RNA: r + 2) is refused
+
+Specificity score (score=, --score / --weights; DESIGN.md section 15, Specificity score).  It needs the PAM's length too.
+  g        the guide region's positions numbered 0 .. G - 1 from the PAM-distal end (3' PAM: g = pattern position;
+           5' PAM: g counts down from the pattern's last position), so g = G - 1 is next to the PAM on either side
+  scheme   factor[g] in [0, 1] and shape[n][d], n = 0..8 mismatches, d = 0..31 = last - first mismatching g
+  hit      for a site of kind none with n >= 1 mismatches at g1 < .. < gn: h = factor[g1] * .. * factor[gn] * shape[n][gn - g1]
+           (float64, left to right), v = rint(h * 2^30) as an integer; n = 0 (the target or a perfect copy) adds nothing
+  result   hit_sum[q] = the sum of v over the query's sites with 1..M mismatches (exact, summed on the device),
+           specificity[q] = 1 / (1 + hit_sum[q] / 2^30).  A query with a base at a PAM position is refused
 """
 import argparse
 import ctypes
@@ -47,6 +58,11 @@ MAX_MM = 8
 IUPAC = "ACGTRYSWKMBDHVN"
 SITE_DTYPE = np.dtype([("query", "<u4"), ("contig", "<u4"), ("position", "<i8"), ("strand", "S1"), ("mismatches", "u1")])
 MAX_BULGE = 2
+SCORE_SHIFT = 30   # a hit's value is rint(h * 2^SCORE_SHIFT)
+SHAPE_N, SHAPE_D = MAX_MM + 1, 32
+# Hsu et al. 2013 (Nat Biotechnol 31:827, "DNA targeting specificity of RNA-guided Cas9 nucleases"): the experimentally
+# determined mismatch weights of the 20 guide positions, PAM-distal first, as the MIT / CRISPOR specificity score uses them
+HSU2013_W = (0, 0, 0.014, 0, 0, 0.395, 0.317, 0, 0.389, 0.079, 0.445, 0.508, 0.613, 0.851, 0.732, 0.828, 0.615, 0.804, 0.685, 0.583)
 BULGE_SITE_DTYPE = np.dtype([("query", "<u4"), ("kind", "u1"), ("bulge_size", "u1"), ("bulge_at", "u1"), ("contig", "<u4"),
                              ("position", "<i8"), ("strand", "S1"), ("mismatches", "u1")])
 _WS = b" \t\n\r\x0b\x0c"
@@ -201,6 +217,28 @@ class ArenaSearch:
         nat.check(nat.lib().crp_search_candidates(self._h, ctypes.byref(a), ctypes.byref(b)), "crp_search_candidates")
         return a.value, b.value
 
+    def set_scheme(self, scheme):
+        """crp_search_set_scheme with a Scheme, or None to clear it."""
+        if scheme is None:
+            st = nat.lib().crp_search_set_scheme(self._h, None, 0, 0, None)
+        else:
+            f = np.ascontiguousarray(scheme.factor, dtype=np.float64)
+            sh = np.ascontiguousarray(scheme.shape, dtype=np.float64).reshape(-1)
+            st = nat.lib().crp_search_set_scheme(self._h, f.ctypes.data_as(nat.f64p), f.size,
+                                                 nat.SEARCH_PAM_3PRIME if scheme.pam3 else nat.SEARCH_PAM_5PRIME,
+                                                 sh.ctypes.data_as(nat.f64p))
+        nat.check(st, "crp_search_set_scheme", self._arena._engine._ctx)
+
+    def run_scored(self, queries, max_mm, site_cap):
+        """crp_search_run_scored as it is: (status, counts (Q, M + 1) uint32, n_sites, hit_sum (Q,) uint64)."""
+        Q = len(queries)
+        counts = np.zeros((Q, max_mm + 1), dtype=np.uint32)
+        hit_sum = np.zeros(Q, dtype=np.uint64)
+        n = ctypes.c_uint64()
+        st = nat.lib().crp_search_run_scored(self._h, "".join(queries).encode(), Q, int(max_mm), int(site_cap),
+                                             counts.ctypes.data_as(nat.u32p), ctypes.byref(n), hit_sum.ctypes.data_as(nat.u64p))
+        return st, counts, n.value, hit_sum
+
     def run(self, queries, max_mm, site_cap, kind=("-", 0), spans=None):
         """crp_search_run, or crp_search_run_bulge for a bulge kind (this handle's pattern: the kind's window pattern), as
         it is: (status, counts (Q, M + 1) uint32, n_sites).  queries: already checked strings; spans (bulge kinds): (Q, 2)
@@ -236,31 +274,42 @@ class ArenaSearch:
 
 
 class SearchResult:
-    def __init__(self, counts, sites, candidates):
+    def __init__(self, counts, sites, candidates, hit_sum=None):
         self.counts = counts          # (Q, M + 1) uint32
         self.sites = sites            # SITE_DTYPE, ordered by query, contig, position, strand
         self.candidates = candidates  # (n_plus, n_minus) over the whole genome
+        self.hit_sum = hit_sum        # (Q,) uint64: the sum of the hits' values (None without score=)
+        self.specificity = None if hit_sum is None else specificity(hit_sum)  # (Q,) float64
 
 
-def search(genome, pattern, queries, max_mm, site_cap=None, budget=None, pam_len=None):
+def search(genome, pattern, queries, max_mm, site_cap=None, budget=None, pam_len=None, score=None, sites=True):
     """Every site of `genome` (engine.Genome) within max_mm mismatches of each query, over all its arenas.
     site_cap=None: as many sites as there are; else SiteCapacityError (with exact counts) beyond it.  budget: device
-    bytes for one chunk of candidates (None: the library's default).  pam_len: how check_query pads shorter guides."""
+    bytes for one chunk of candidates (None: the library's default).  pam_len: how check_query pads shorter guides.
+    score: "hsu2013" or G weights (see check_score; needs pam_len): the result's .hit_sum and .specificity, summed on
+    the device.  sites=False: no site list is kept or fetched (.sites is empty, no SiteCapacityError): counts and sums
+    only."""
     pattern = check_pattern(pattern)
     max_mm = check_max_mm(max_mm)
     queries = [check_query(pattern, q, pam_len) for q in queries]
-    counts, sites, cands, n_total = _search_kinds(genome, pattern, None, queries, max_mm, [("-", 0)], None, site_cap, budget)
-    if site_cap is not None and n_total > int(site_cap):
+    scheme = check_score(pattern, pam_len, score, queries)
+    if not sites:
+        site_cap = 0
+    counts, rows, cands, n_total, hit_sum = _search_kinds(genome, pattern, None, queries, max_mm, [("-", 0)], None, site_cap, budget,
+                                                           scheme)
+    if sites and site_cap is not None and n_total > int(site_cap):
         raise SiteCapacityError(counts[:, 0], n_total, int(site_cap))
-    return SearchResult(counts[:, 0], sites[list(SITE_DTYPE.names)].astype(SITE_DTYPE), cands[0])
+    return SearchResult(counts[:, 0], rows[list(SITE_DTYPE.names)].astype(SITE_DTYPE), cands[0], hit_sum)
 
 
-def _search_kinds(genome, pattern, pam_len, queries, max_mm, kinds, spans, site_cap, budget):
+def _search_kinds(genome, pattern, pam_len, queries, max_mm, kinds, spans, site_cap, budget, scheme=None):
     """Every kind of `kinds` over every arena of `genome`, on checked input: one library handle per kind and arena, on
-    the kind's window pattern, and site_cap counts the sites of all kinds together.  Returns (counts (Q, kinds, M + 1)
-    uint32, BULGE_SITE_DTYPE sites ordered by query, kind, contig, position, strand, per kind (n_plus, n_minus), the
-    number of sites); the sites are only complete when that number is within site_cap."""
+    the kind's window pattern, and site_cap counts the sites of all kinds together.  With a scheme the kind-none runs
+    are scored.  Returns (counts (Q, kinds, M + 1) uint32, BULGE_SITE_DTYPE sites ordered by query, kind, contig,
+    position, strand, per kind (n_plus, n_minus), the number of sites, hit_sum (Q,) uint64 or None); the sites are only
+    complete when that number is within site_cap."""
     counts = np.zeros((len(queries), len(kinds), max_mm + 1), dtype=np.uint64)
+    hit_sum = None if scheme is None else np.zeros(len(queries), dtype=np.uint64)
     parts, n_total, cands = [], 0, []
     for k, kind in enumerate(kinds):
         size = kind[1]
@@ -273,7 +322,12 @@ def _search_kinds(genome, pattern, pam_len, queries, max_mm, kinds, spans, site_
                 cand[0] += npl
                 cand[1] += nmi
                 cap = (1 << 62) if site_cap is None else max(0, int(site_cap) - n_total)
-                st, c, n = s.run(queries, max_mm, cap, kind, spans)
+                if scheme is not None and not size:
+                    s.set_scheme(scheme)
+                    st, c, n, hs = s.run_scored(queries, max_mm, cap)
+                    hit_sum += hs  # (a handle's sum is below 2^62: the arenas are added here)
+                else:
+                    st, c, n = s.run(queries, max_mm, cap, kind, spans)
                 if st not in (nat.CRP_OK, nat.CRP_ERR_CAPACITY):
                     nat.check(st, "crp_search_run_bulge" if size else "crp_search_run", a._engine._ctx)
                 counts[:, k] += c
@@ -297,7 +351,140 @@ def _search_kinds(genome, pattern, pam_len, queries, max_mm, kinds, spans, site_
         cands.append(tuple(cand))
     sites = np.concatenate(parts) if parts else np.empty(0, BULGE_SITE_DTYPE)
     order = np.lexsort((sites["strand"] == b"-", sites["position"], sites["contig"], sites["kind"], sites["query"]))
-    return counts.astype(np.uint32), sites[order], cands, n_total
+    return counts.astype(np.uint32), sites[order], cands, n_total, hit_sum
+
+
+# ---------------------------------------------------------------- specificity score
+class Scheme:
+    """factor (G,) and shape (9, 32) float64 in [0, 1]; the guide region [lo, hi) of the pattern and the PAM's side."""
+
+    def __init__(self, factor, shape, lo, hi, pam3):
+        self.factor, self.shape, self.lo, self.hi, self.pam3 = factor, shape, lo, hi, pam3
+
+    def g_positions(self):
+        """(G,) the pattern position of g = 0 .. G - 1."""
+        return np.arange(self.lo, self.hi) if self.pam3 else np.arange(self.hi - 1, self.lo - 1, -1)
+
+
+def hsu_shape(G):
+    """shape[n][d] of the Hsu et al. 2013 score for a guide region of G: 1 for n = 0, 1 / n^2 for n = 1, and for n >= 2
+    1 / (((G - 1 - d / (n - 1)) / (G - 1)) * 4 + 1) / n^2, d / (n - 1) being the mean distance between consecutive
+    mismatches (0 where d < n - 1, which n mismatches cannot have, and where d > G - 1)."""
+    shape = np.zeros((SHAPE_N, SHAPE_D), dtype=np.float64)
+    shape[0, :] = 1.0
+    shape[1, :] = 1.0
+    for n in range(2, SHAPE_N):
+        for d in range(n - 1, min(G, SHAPE_D)):
+            shape[n, d] = 1.0 / (((float(G - 1) - d / float(n - 1)) / float(G - 1)) * 4.0 + 1.0) / float(n * n)
+    return shape
+
+
+def make_scheme(pattern, pam_len, score):
+    """The Scheme of score = "hsu2013" (G = 20 only) or a sequence of G weights W in [0, 1], PAM-distal first
+    (factor = 1 - W, the Hsu shape with 19 -> G - 1)."""
+    if pam_len is None:
+        raise SearchInputError("a specificity score needs the PAM's length (--pam-length)")
+    lo, hi, pam3 = guide_region(pattern, pam_len)
+    G = hi - lo
+    if isinstance(score, str):
+        if score != "hsu2013":
+            raise SearchInputError("unknown scoring scheme %r (hsu2013, or a list of weights)" % score)
+        if G != len(HSU2013_W):
+            raise SearchInputError("hsu2013 is defined for a guide region of %d positions, not %d" % (len(HSU2013_W), G))
+        w = np.array(HSU2013_W, dtype=np.float64)
+    else:
+        try:
+            w = np.array([float(v) for v in score], dtype=np.float64)
+        except (TypeError, ValueError):
+            raise SearchInputError("weights must be numbers: %r" % (score,)) from None
+        if w.size != G:
+            raise SearchInputError("%d weights for a guide region of %d positions" % (w.size, G))
+        if not (np.isfinite(w).all() and (w >= 0).all() and (w <= 1).all()):
+            raise SearchInputError("weights must be finite and in [0, 1]")
+    return Scheme(1.0 - w, hsu_shape(G), lo, hi, pam3)
+
+
+def check_score(pattern, pam_len, score, queries):
+    """None without a score; else its Scheme, after refusing every query with a base at a PAM position (a mismatch
+    there would have no g)."""
+    if score is None:
+        return None
+    scheme = make_scheme(pattern, pam_len, score)
+    for q in queries:
+        if set(q[:scheme.lo] + q[scheme.hi:]) - {"N"}:
+            raise SearchInputError("guide %r has a base at a PAM position: a scored search needs N there" % q)
+    return scheme
+
+
+def parse_weights(text):
+    """A weights file: numbers separated by whitespace or commas, PAM-distal first; `#` starts a comment."""
+    if isinstance(text, bytes):
+        text = text.decode()
+    fields = " ".join(line.split("#", 1)[0] for line in text.splitlines()).replace(",", " ").split()
+    try:
+        return [float(v) for v in fields]
+    except ValueError as e:
+        raise SearchInputError("weights file: %s" % e) from None
+
+
+def specificity(hit_sum):
+    """1 / (1 + hit_sum / 2^30), float64."""
+    return 1.0 / (1.0 + np.asarray(hit_sum, dtype=np.uint64).astype(np.float64) / float(1 << SCORE_SHIFT))
+
+
+def mask_values(masks, scheme):
+    """v of mismatch masks (bit g = a mismatch at guide-region position g), uint64: the definition in numpy.  The
+    product runs over g ascending, one float64 multiply per step, like the device's."""
+    masks = np.asarray(masks, dtype=np.uint64)
+    G = scheme.factor.size
+    h = np.ones(masks.shape, dtype=np.float64)
+    n = np.zeros(masks.shape, dtype=np.int64)
+    first = np.full(masks.shape, -1, dtype=np.int64)
+    last = np.zeros(masks.shape, dtype=np.int64)
+    for g in range(G):
+        bit = ((masks >> np.uint64(g)) & np.uint64(1)).astype(bool)
+        h = np.where(bit, h * scheme.factor[g], h)
+        n += bit
+        first = np.where(bit & (first < 0), g, first)
+        last = np.where(bit, g, last)
+    if (masks >> np.uint64(G)).any() or (n > MAX_MM).any():
+        raise ValueError("a mask outside the guide region or with more than %d mismatches" % MAX_MM)
+    d = np.where(n > 0, last - first, 0)
+    h = h * scheme.shape[n, d]
+    v = np.rint(h * float(1 << SCORE_SHIFT)).astype(np.uint64)
+    return np.where(n > 0, v, np.uint64(0))
+
+
+def site_masks(sites, queries, contigs, scheme):
+    """Per site its mismatch mask over g, from the site's letters (kind-none sites: SITE_DTYPE, or BULGE_SITE_DTYPE
+    rows of kind 0)."""
+    gpos = scheme.g_positions()
+    T = len(queries[0]) if queries else 0
+    qcodes = [np.array([_QCODE[ord(ch)] for ch in q], dtype=np.uint8) for q in queries]
+    w = np.uint64(1) << np.arange(gpos.size, dtype=np.uint64)
+    out = np.zeros(len(sites), dtype=np.uint64)
+    for k, r in enumerate(sites):
+        pos, contig = int(r["position"]), contigs[int(r["contig"])]
+        codes = _CODE[np.frombuffer(bytes(contig[pos:pos + T]), dtype=np.uint8)]
+        if r["strand"] in (b"-", "-"):
+            codes = np.where(codes == 4, 4, 3 - codes)[::-1]
+        qc = qcodes[int(r["query"])]
+        mism = (qc != 4) & (codes != qc)
+        out[k] = (mism[gpos].astype(np.uint64) * w).sum(dtype=np.uint64)
+    return out
+
+
+def hit_values(sites, queries, contigs, scheme):
+    """v of every fetched site (uint64), from the site's letters by the same integer definition as the device's sums:
+    the sum of a query's values is its hit_sum.  Sites of kind none only: a bulge kind's site (BULGE_SITE_DTYPE with
+    kind != 0) and a site without mismatches have the value 0."""
+    sites = np.asarray(sites)
+    v = np.zeros(sites.size, dtype=np.uint64)
+    plain = np.ones(sites.size, dtype=bool) if "kind" not in (sites.dtype.names or ()) else sites["kind"] == 0
+    idx = np.nonzero(plain)[0]
+    if idx.size:
+        v[idx] = mask_values(site_masks(sites[idx], queries, contigs, scheme), scheme)
+    return v
 
 
 # ---------------------------------------------------------------- bulges
@@ -354,7 +541,9 @@ def query_spans(pattern, pam_len, queries, D, R):
 
 
 class BulgeSearchResult:
-    def __init__(self, counts, sites, kinds, spans, candidates):
+    def __init__(self, counts, sites, kinds, spans, candidates, hit_sum=None):
+        self.hit_sum = hit_sum        # (Q,) uint64 over the sites of kind none (None without score=)
+        self.specificity = None if hit_sum is None else specificity(hit_sum)
         self.counts = counts          # (Q, kinds, M + 1) uint32
         self.sites = sites            # BULGE_SITE_DTYPE, ordered by query, kind, contig, position, strand
         self.kinds = kinds            # [(bulge, size)]: kind k of .counts and .sites
@@ -362,26 +551,33 @@ class BulgeSearchResult:
         self.candidates = candidates  # per kind: (n_plus, n_minus) over the whole genome
 
 
-def search_bulges(genome, pattern, queries, max_mm, pam_len, dna_bulge, rna_bulge, site_cap=None, budget=None):
+def search_bulges(genome, pattern, queries, max_mm, pam_len, dna_bulge, rna_bulge, site_cap=None, budget=None, score=None, sites=True):
     """search() plus every site with a DNA bulge of 1..dna_bulge or an RNA bulge of 1..rna_bulge (see the module's
     docstring), over all arenas of `genome`: one library handle per kind and arena, on the kind's window pattern.
-    The kind-none slice is what search() returns.  site_cap counts the sites of all kinds together."""
+    The kind-none slice is what search() returns.  site_cap counts the sites of all kinds together.  score, sites: as
+    in search(); .hit_sum and .specificity cover the sites of kind none only (a bulge site has no score)."""
     pattern = check_pattern(pattern)
     max_mm = check_max_mm(max_mm)
     D, R = check_bulges(pattern, pam_len, dna_bulge, rna_bulge)
     queries = [check_query(pattern, q, pam_len) for q in queries]
     spans = query_spans(pattern, pam_len, queries, D, R) if D or R else np.zeros((len(queries), 2), np.uint8)
     kinds = bulge_kinds(D, R)
-    counts, sites, cands, n_total = _search_kinds(genome, pattern, pam_len, queries, max_mm, kinds, spans, site_cap, budget)
-    if site_cap is not None and n_total > int(site_cap):
+    scheme = check_score(pattern, pam_len, score, queries)
+    if not sites:
+        site_cap = 0
+    counts, rows, cands, n_total, hit_sum = _search_kinds(genome, pattern, pam_len, queries, max_mm, kinds, spans, site_cap, budget, scheme)
+    if sites and site_cap is not None and n_total > int(site_cap):
         raise SiteCapacityError(counts, n_total, int(site_cap))
-    return BulgeSearchResult(counts, sites, kinds, spans, cands)
+    return BulgeSearchResult(counts, rows, kinds, spans, cands, hit_sum)
 
 
 # ---------------------------------------------------------------- TSV
 _CODE = np.full(256, 4, dtype=np.uint8)  # 0..3 = A C G T, 4 = not a base
 for _c, _v in zip(b"ACGTUacgt", (0, 1, 2, 3, 0, 0, 1, 2, 3)):
     _CODE[_c] = _v
+_QCODE = np.full(256, 4, dtype=np.uint8)  # a query's letters: N (not compared) = 4
+for _c, _v in zip(b"ACGT", (0, 1, 2, 3)):
+    _QCODE[_c] = _v
 
 
 def site_string(contig, position, strand, query):
@@ -424,11 +620,31 @@ def format_bulge_sites(names, queries, contig_names, contigs, res):
     return _format_site_rows(names, queries, contig_names, contigs, res.sites, res.kinds, res.spans)
 
 
-def _format_site_rows(names, queries, contig_names, contigs, sites, kinds, spans):
-    """The sites TSV; with the kinds and spans of a bulge search, the bulge columns and the aligned query too."""
+def format_scored_sites(names, queries, contig_names, contigs, res, scheme):
+    """The sites TSV of a scored search (SearchResult or BulgeSearchResult): the unscored columns plus hit_score."""
+    kinds, spans = getattr(res, "kinds", None), getattr(res, "spans", None)
+    if kinds is not None and len(kinds) == 1:
+        kinds = None
+    return _format_site_rows(names, queries, contig_names, contigs, res.sites, kinds, spans,
+                             hit_values(res.sites, queries, contigs, scheme))
+
+
+def format_scored_counts(names, queries, res):
+    """The counts TSV of a scored search: the unscored columns plus hit_sum and specificity."""
+    kinds = getattr(res, "kinds", None)
+    if kinds is None or len(kinds) == 1:
+        return _format_count_rows(names, queries, res.counts.reshape(len(queries), 1, -1), None, res.hit_sum)
+    return _format_count_rows(names, queries, res.counts, kinds, res.hit_sum)
+
+
+def _format_site_rows(names, queries, contig_names, contigs, sites, kinds, spans, values=None):
+    """The sites TSV; with the kinds and spans of a bulge search, the bulge columns and the aligned query too; with the
+    sites' hit values, a last column hit_score = v / 2^30 (empty for a bulge kind's site and for a site without
+    mismatches: neither is summed)."""
     head = ["name", "query", "contig", "position", "strand", "mismatches"]
-    lines = ["\t".join(head + (["bulge", "bulge_size", "bulge_at", "site", "query_aligned"] if kinds else ["site"])) + "\n"]
-    for r in sites:
+    head += ["bulge", "bulge_size", "bulge_at", "site", "query_aligned"] if kinds else ["site"]
+    lines = ["\t".join(head + ([] if values is None else ["hit_score"])) + "\n"]
+    for i, r in enumerate(sites):
         q, k, pos, strand = int(r["query"]), int(r["contig"]), int(r["position"]), r["strand"]
         row = [names[q], queries[q], contig_names[k], pos, strand.decode(), int(r["mismatches"])]
         if kinds:
@@ -437,6 +653,9 @@ def _format_site_rows(names, queries, contig_names, contigs, sites, kinds, spans
             row += [bulge, size, at, site, qa]
         else:
             row.append(site_string(contigs[k], pos, strand, queries[q]))
+        if values is not None:
+            scored = int(r["mismatches"]) > 0 and not (kinds and kinds[int(r["kind"])][1])
+            row.append("%.6f" % (int(values[i]) / float(1 << SCORE_SHIFT)) if scored else "")
         lines.append("\t".join(map(str, row)) + "\n")
     return "".join(lines)
 
@@ -449,14 +668,19 @@ def format_counts(names, queries, counts):
     return _format_count_rows(names, queries, counts[:, None], None)
 
 
-def _format_count_rows(names, queries, counts, kinds):
+def _format_count_rows(names, queries, counts, kinds, hit_sum=None):
     """The counts TSV of counts (Q, kinds, M + 1): one line per query and kind; with the kinds of a bulge search, the
-    bulge and bulge_size columns too."""
+    bulge and bulge_size columns too; with hit_sum, the columns hit_sum (as a sum of hit scores, hit_sum / 2^30) and
+    specificity, filled on the kind-none line only."""
     head = ["name", "query"] + (["bulge", "bulge_size"] if kinds else []) + ["mm%d" % k for k in range(counts.shape[2])]
-    lines = ["\t".join(head) + "\n"]
+    lines = ["\t".join(head + ([] if hit_sum is None else ["hit_sum", "specificity"])) + "\n"]
+    spec = None if hit_sum is None else specificity(hit_sum)
     for q in range(len(queries)):
         for k, kind in enumerate(kinds or [()]):
-            lines.append("\t".join(map(str, [names[q], queries[q], *kind, *counts[q, k].tolist()])) + "\n")
+            row = [names[q], queries[q], *kind, *counts[q, k].tolist()]
+            if hit_sum is not None:
+                row += ["%.6f" % (int(hit_sum[q]) / float(1 << SCORE_SHIFT)), "%.6f" % spec[q]] if k == 0 else ["", ""]
+            lines.append("\t".join(map(str, row)) + "\n")
     return "".join(lines)
 
 
@@ -472,7 +696,7 @@ def main(argv=None):
                          "sit right next to it (3 for ...NGG, 6 for ...NNGRRT, 4 for TTTV...); without it a shorter guide "
                          "must be exactly as long as the pattern's N run")
     ap.add_argument("-m", "--mismatches", type=int, default=4, help="most mismatches reported (0..8, default 4)")
-    ap.add_argument("-o", "--output", required=True, help="sites TSV")
+    ap.add_argument("-o", "--output", help="sites TSV (required without --no-sites)")
     ap.add_argument("--dna-bulge", type=int, default=0, metavar="D",
                     help="also report sites with a DNA bulge (extra genomic bases) of 1..D (0..2, default 0); needs "
                          "--pam-length; adds the columns bulge, bulge_size, bulge_at, query_aligned")
@@ -480,6 +704,15 @@ def main(argv=None):
                     help="also report sites with an RNA bulge (unpaired guide letters) of 1..R (0..2, default 0); needs "
                          "--pam-length")
     ap.add_argument("--counts", help="per-guide counts TSV (mm0..mmM; with bulges one line per guide and kind)")
+    sc = ap.add_mutually_exclusive_group()
+    sc.add_argument("--score", choices=["hsu2013"],
+                    help="per-guide specificity 1 / (1 + sum of hit scores), summed on the GPU over the sites with 1..M mismatches "
+                         "(hsu2013: the MIT score's weights, 20-nt guide regions); needs --pam-length; adds the column hit_score "
+                         "to the sites TSV, hit_sum and specificity to --counts")
+    sc.add_argument("--weights", metavar="FILE",
+                    help="the same with the weights of FILE in place of hsu2013's: one number in [0, 1] per guide-region "
+                         "position, PAM-distal first")
+    ap.add_argument("--no-sites", action="store_true", help="keep and write no site list: only --counts (with the scores, if asked for)")
     ap.add_argument("--device", type=int, default=0, help="HIP device")
     args = ap.parse_args(argv)
     try:
@@ -492,6 +725,15 @@ def main(argv=None):
             names, queries = parse_guides(f.read(), pattern, args.pam_length)
         if D or R:
             query_spans(pattern, args.pam_length, queries, D, R)
+        score = args.score
+        if args.weights:
+            with open(args.weights, "rb") as f:
+                score = parse_weights(f.read())
+        scheme = check_score(pattern, args.pam_length, score, queries)
+        if args.no_sites and (args.output or not args.counts):
+            raise SearchInputError("--no-sites writes only --counts: give --counts and no -o")
+        if not args.no_sites and not args.output:
+            raise SearchInputError("-o/--output is required (or --no-sites with --counts)")
         contig_names, contigs = read_fasta(args.fasta)
     except (SearchInputError, OSError, UnicodeDecodeError) as e:
         ap.error(str(e))
@@ -499,21 +741,23 @@ def main(argv=None):
     with Engine(args.device) as eng:
         g = eng.genome(contigs)
         try:
-            res = search_bulges(g, pattern, queries, max_mm, args.pam_length, D, R)
+            res = search_bulges(g, pattern, queries, max_mm, args.pam_length, D, R, score=score, sites=not args.no_sites)
         finally:
             g.close()
     kinds = res.kinds if D or R else None  # (None: the plain TSV columns)
-    with open(args.output, "w") as f:
-        f.write(_format_site_rows(names, queries, contig_names, contigs, res.sites, kinds, res.spans))
+    if not args.no_sites:
+        values = None if scheme is None else hit_values(res.sites, queries, contigs, scheme)
+        with open(args.output, "w") as f:
+            f.write(_format_site_rows(names, queries, contig_names, contigs, res.sites, kinds, res.spans, values))
     if args.counts:
         with open(args.counts, "w") as f:
-            f.write(_format_count_rows(names, queries, res.counts, kinds))
+            f.write(_format_count_rows(names, queries, res.counts, kinds, res.hit_sum))
     if D or R:
-        print("%d guides, %d kinds, %d sites within %d mismatches" % (len(queries), len(res.kinds), res.sites.size, max_mm),
+        print("%d guides, %d kinds, %d sites within %d mismatches" % (len(queries), len(res.kinds), int(res.counts.sum()), max_mm),
               file=sys.stderr)
     else:
         print("%d guides, %d + %d candidate sites, %d sites within %d mismatches" % (
-            len(queries), res.candidates[0][0], res.candidates[0][1], res.sites.size, max_mm), file=sys.stderr)
+            len(queries), res.candidates[0][0], res.candidates[0][1], int(res.counts.sum()), max_mm), file=sys.stderr)
     return 0
 
 

@@ -633,6 +633,29 @@ int crp_search_run_bulge(crp_search *search, const char *queries, uint64_t n_que
 /* crp_search_fetch plus bulge_at (0 after a crp_search_run); order: query, arena position, strand. */
 int crp_search_fetch_bulge(const crp_search *search, uint32_t *query, uint32_t *arena_pos, uint8_t *strand, uint8_t *mismatches,
                            uint8_t *bulge_at, uint64_t cap);
+/* Specificity score (Specificity score).  A scheme weighs every hit of a query by where its
+ * mismatches sit.  The guide region is the n_factor pattern positions outside the PAM, which is the pattern's last
+ * T - n_factor positions (CRP_SEARCH_PAM_3PRIME) or its first (CRP_SEARCH_PAM_5PRIME); its positions are numbered
+ * g = 0 .. n_factor - 1 from the PAM-distal end, so g = n_factor - 1 is next to the PAM on either side.  For a hit
+ * with n >= 1 mismatches at g1 < g2 < .. < gn,
+ *   h = factor[g1] * factor[g2] * .. * factor[gn] * shape[n * 32 + (gn - g1)]   (float64, left to right)
+ *   v = (uint64) rint(h * 2^30)                                                 (round to nearest even)
+ * and hit_sum[q] is the sum of v over the query's sites with 1 .. max_mm mismatches: exact integers, independent of
+ * the order the device finds them in.  Specificity = 1 / (1 + hit_sum / 2^30) is the caller's to form. */
+#define CRP_SEARCH_PAM_3PRIME 0
+#define CRP_SEARCH_PAM_5PRIME 1
+#define CRP_SEARCH_SHAPE_DOUBLES 288 /* shape[n][d]: n = 0..8 mismatches, d = 0..31 = last - first mismatching g */
+#define CRP_SEARCH_SCORE_ONE (1ull << 30)
+/* Sets the handle's scheme: factor[n_factor] (1 <= n_factor <= T) and shape[CRP_SEARCH_SHAPE_DOUBLES], every value
+ * finite and in [0, 1].  A NULL factor clears the scheme.  CRP_ERR_INVALID: a NULL shape, n_factor or pam_side out
+ * of range, a value outside [0, 1] or not finite. */
+int crp_search_set_scheme(crp_search *search, const double *factor, int n_factor, int pam_side, const double *shape);
+/* crp_search_run plus hit_sum (n_queries uint64).  The capacity protocol is crp_search_run's, and like the counts
+ * the sums are exact under CRP_ERR_CAPACITY: site_cap = 0 is the score-only run, which keeps no site list at all.
+ * CRP_ERR_STATE without a scheme; CRP_ERR_INVALID for a query with a base outside the guide region (its
+ * mismatches there would have no g). */
+int crp_search_run_scored(crp_search *search, const char *queries, uint64_t n_queries, int max_mm, uint64_t site_cap,
+                          uint32_t *counts, uint64_t *n_sites, uint64_t *hit_sum);
 /* Measurement, accumulated since create: out[0] ms of candidate extraction (count and emit kernels),
  * out[1] ms of compare kernels, out[2] extraction launches, out[3] compare launches, out[4] chunks of the
  * current plan, out[5] device bytes of the candidate buffers.  n: how many of these to write (<= 6). */

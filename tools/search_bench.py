@@ -17,6 +17,11 @@ fraction of the issue floor, and the compare time of the expansion path for the 
 bulge placement and run through the no-bulge compare kernel on the same candidates).  BULGE_VALU_PER_PAIR is read from
 the ISA of search_bulge_compare_kernel: its no-hit loop body is 72 VALU instructions for 8 candidates (40 v_bitop3_b32,
 16 v_bfi_b32, 8 v_bcnt_u32_b32, 8 v_cmp_le_i32).
+
+--score times the specificity score (Specificity score): the 1 024-guide ...NGG M = 4 case run plain
+(search_compare_kernel) and scored with hsu2013 (search_score_compare_kernel), interleaved in one process on the same
+resident candidates, three rounds each, compare times from crp_search_stats; plus the wall time of the plain run (with
+its fetch and sort of the site list) against the score-only run (site_cap 0: no site list at all).
 """
 import argparse
 import json
@@ -116,17 +121,89 @@ def bulge_main(args, contigs, guides, out):
     print(json.dumps(out))
 
 
+def score_main(args, contigs, guides, out):
+    pattern, P, rounds = PATTERNS["NGG"], 3, 3
+    queries = [srch.check_query(pattern, q, P) for q in guides[:BULGE_Q]]
+    scheme = srch.make_scheme(pattern, P, "hsu2013")
+    out.update(queries=len(queries), pattern="NGG", scheme="hsu2013", rounds=rounds)
+    with Engine(args.device) as eng:
+        out["device"] = eng.device_info()["name"].strip()
+        g = eng.genome(contigs)
+        searches = [srch.ArenaSearch(a, pattern) for a in g.arenas]
+        for s in searches:
+            s.set_scheme(scheme)
+        out["candidates"] = int(sum(sum(s.candidates()) for s in searches))
+
+        def timed(run):
+            """(compare ms, wall s, sites, counts, hit sums) of one run over every arena"""
+            before = [s.stats()["compare_ms"] for s in searches]
+            t = time.perf_counter()
+            res = [run(s) for s in searches]
+            wall = time.perf_counter() - t
+            for r in res:
+                if r[0] not in (nat.CRP_OK, nat.CRP_ERR_CAPACITY):
+                    nat.check(r[0], "crp_search_run")
+            ms = sum(s.stats()["compare_ms"] - b for s, b in zip(searches, before))
+            return ms, wall, sum(r[2] for r in res), sum(r[1].astype(np.uint64) for r in res), \
+                sum(r[3] for r in res) if len(res[0]) > 3 else None
+
+        def plain(s):
+            st, counts, n = s.run(queries, MAX_MM, 1 << 40)
+            if st == nat.CRP_OK:
+                s.fetch(n)
+            return st, counts, n
+
+        def scored(s):
+            return s.run_scored(queries, MAX_MM, 1 << 40)
+
+        def score_only(s):
+            return s.run_scored(queries, MAX_MM, 0)
+
+        timed(plain)  # warm-up: extraction, the site buffer's growth, both kernels' code objects
+        timed(scored)
+        rows = {"plain": [], "scored": [], "score_only": []}
+        ref_counts = ref_sums = None
+        for _ in range(rounds):
+            for name, run in (("plain", plain), ("scored", scored), ("score_only", score_only)):
+                ms, wall, n_sites, counts, sums = timed(run)
+                rows[name].append((ms, wall))
+                if ref_counts is None:
+                    ref_counts = counts
+                assert (counts == ref_counts).all(), name
+                if sums is not None:
+                    ref_sums = sums if ref_sums is None else ref_sums
+                    assert (sums == ref_sums).all(), name
+                out["sites"] = int(n_sites)
+        for name, r in rows.items():
+            out[name] = dict(compare_ms=[round(ms, 3) for ms, _ in r], run_wall_s=[round(w, 4) for _, w in r])
+        med = lambda name, k: float(np.median([x[k] for x in rows[name]]))
+        out["scored_over_plain_compare"] = round(med("scored", 0) / med("plain", 0), 4)
+        out["score_only_over_plain_compare"] = round(med("score_only", 0) / med("plain", 0), 4)
+        out["score_only_over_plain_wall"] = round(med("score_only", 1) / med("plain", 1), 4)
+        out["hit_sum_total"] = int(ref_sums.sum())
+        out["guides_with_hits"] = int((ref_sums > 0).sum())
+        out["median_specificity"] = round(float(np.median(srch.specificity(ref_sums))), 6)
+        for s in searches:
+            s.close()
+        g.close()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--bulge", metavar="D,R", help="time the search with DNA bulges 1..D and RNA bulges 1..R instead")
+    ap.add_argument("--score", action="store_true", help="time the scored compare against the plain one instead")
     args = ap.parse_args()
     t0 = time.perf_counter()
     wl = bw.switchgrass_like(0, args.scale)
     contigs = [wl.bases(s) for s in wl.specs]
-    guides = draw_guides(contigs, BULGE_Q if args.bulge else max(QS))
+    guides = draw_guides(contigs, BULGE_Q if args.bulge or args.score else max(QS))
     gen_s = time.perf_counter() - t0
+    if args.score:
+        return score_main(args, contigs, guides, dict(workload=wl.name, chars=int(sum(c.size for c in contigs)), max_mm=MAX_MM,
+                                                      generate_s=round(gen_s, 1)))
     if args.bulge:
         return bulge_main(args, contigs, guides, dict(workload=wl.name, chars=int(sum(c.size for c in contigs)), max_mm=MAX_MM,
                                                       generate_s=round(gen_s, 1)))
