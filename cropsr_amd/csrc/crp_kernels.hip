@@ -853,8 +853,10 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
                     if (((valid >> 5) & 0xfffu) == 0xfffu) hit.seed = (((h >> 5) & 0xfffu) << 12) | ((w >> 5) & 0xfffu);
                 }
                 if (complete) {
-                    const uint32_t mG = h & w & valid, mC = h & ~w & valid;
-                    const uint32_t mT = ~h & w & valid, mA = ~h & ~w & valid;
+                    // In a complete window an invalid character (N, IUPAC, ...) has h = w = 0 (void is excluded, and
+                    // its u = 0 leaves w alone on '+'), so only A, the letter with that code, needs `valid`.
+                    const uint32_t mG = h & w, mC = h & ~w;
+                    const uint32_t mT = ~h & w, mA = ~h & ~w & valid;
                     crp_score_masks<PAM>(mA, mT, mC, mG, exp_tab, score_tab, hit.pre, hit.score);
                 }
             } else if (l >= 20) {

@@ -92,15 +92,14 @@ for _kv in os.environ.get("CRP_TABLE_BITS", "").split(","):
         TABLE_BITS[_kv.split("=")[0].strip()] = int(_kv.split("=")[1])
 
 
-def find_gather(qs, rng_seed):
-    """bits at positions qs (chain order) of a 32-bit word -> (lo, magic, W): the table index of a
-    bit pattern is the top k bits of ((word >> lo) * magic) mod 2^W, one-to-one on all 2^k patterns.
-    W = 24 when the bits span fewer than 24 positions (v_mul_u32_u24, full rate), else 32."""
+def find_gather(qs, rng_seed, lo):
+    """bits at positions qs (chain order) of a 32-bit word -> (magic, W): the table index of a bit
+    pattern is the top k bits of ((word >> lo) * magic) mod 2^W, one-to-one on all 2^k patterns.
+    W = 24 when the shifted bits sit below bit 24 (v_mul_u32_u24, full rate, reads only those), else 32."""
     import random
 
     import numpy as np
     k = len(qs)
-    lo = min(qs)
     rel = np.array([q - lo for q in qs], dtype=np.uint64)
     W = 24 if int(rel.max()) < 24 else 32
     modmask = np.uint64((1 << W) - 1)
@@ -114,7 +113,7 @@ def find_gather(qs, rng_seed):
         idx.sort(axis=1)
         ok = (np.diff(idx.astype(np.int64), axis=1) != 0).all(axis=1) & (magic != 0)
         if ok.any():
-            return lo, int(magic[np.nonzero(ok)[0][0]]), W
+            return int(magic[np.nonzero(ok)[0][0]]), W
     raise RuntimeError("no gather constant found for bit positions %r" % (qs,))
 
 
@@ -127,6 +126,7 @@ def emit_table_scorer(out, live, init, wtable, emit_copies):
     data = []  # table entries (doubles), all chains back to back
     leftover = []
     lines.append("const uint32_t nA = (mA) >> 1, nT = (mT) >> 1, nC = (mC) >> 1, nG = (mG) >> 1; (void)nA; (void)nT; (void)nC; (void)nG;")
+    spec = collections.OrderedDict()
     for cname in ("fA", "fT", "fC", "fG", "sA", "sT", "sC", "sG"):
         terms = chains.get(cname, [])
         k = min(len(terms), TABLE_BITS[cname])
@@ -164,7 +164,24 @@ def emit_table_scorer(out, live, init, wtable, emit_copies):
                 part = "((m%s) & n%s & 0x%xu)" % (b1, x, sum(1 << p for p in ps))
                 parts.append("(%s << %d)" % (part, shift_of[b1]) if shift_of[b1] else part)
             src = "(" + " | ".join(parts) + ")"
-        lo, magic, W = find_gather(qs, "%s-%d" % (cname, k))
+        spec[cname] = (k, head, qs, src)
+    # No shift in front of the multiplication when the gate bits already sit below bit 24.  Otherwise a pair chain
+    # shifts down to its lowest bit, and a single-base chain by one more than the pair chain of its base does: its
+    # mask shifted so is (nX >> lo of sX), which that chain computes anyway -- or else by 1 (nX itself) if that is
+    # enough, or else to its lowest bit.
+    lo_of = {}
+    for cname, (k, head, qs, src) in spec.items():
+        if max(qs) < 24:
+            lo_of[cname] = 0
+        elif cname[0] == "s":
+            lo_of[cname] = min(qs)
+    for cname, (k, head, qs, src) in spec.items():
+        if cname not in lo_of:
+            cands = [1 + lo_of["s" + cname[1]]] if "s" + cname[1] in lo_of else []
+            lo_of[cname] = next(lo for lo in cands + [1, min(qs)] if lo <= min(qs) and max(qs) - lo < 24)
+    for cname, (k, head, qs, src) in spec.items():
+        lo = lo_of[cname]
+        magic, W = find_gather(qs, "%s-%d" % (cname, k), lo)
         # table: entry for every bit pattern, at the index the kernel will compute for it
         base = len(data)
         entries = [None] * (1 << k)
@@ -183,9 +200,20 @@ def emit_table_scorer(out, live, init, wtable, emit_copies):
         lines.append("%s = crp_tab_at(score_tab, %d, (%s >> %d) & 0x%xu); /* %d terms: %s */"
                      % (cname, 8 * base, mul, W - k - 3, ((1 << k) - 1) << 3, k,
                         " ".join(t[2].split("/*")[1].split()[0] for t in head)))
-    body = emit_copies(leftover) + lines
+    # The tables take each chain's first terms, so the gated FMAs left over test late positions.  A position p in
+    # 20..30 is already a high-word exponent bit of the unshifted masks: such a gate reads mX (or mB1 & nX) at bit p,
+    # with the weight scaled for that bit, and needs no shifted copy.  Other positions keep the a/b/c copies.
+    shifted = [t for t in leftover if not 20 <= t[1] // (16 if t[0] else 4) <= 30]
+    body = emit_copies(shifted) + lines
     for t in leftover:
-        body.append(t[2].replace("@W@", "CRP_WS(%d)" % wtable.index(t[3])))
+        if any(t is s for s in shifted):
+            body.append(t[2].replace("@W@", "CRP_WS(%d)" % wtable.index(t[3])))
+            continue
+        p, note = t[1] // (16 if t[0] else 4), t[2][t[2].index("/*"):]
+        if t[0] == 0:
+            body.append("CRP_TERM(%s, m%s, %2d, %s) %s" % (t[5], t[5][1], p, scaled(t[6], p), note))
+        else:
+            body.append("CRP_TERM2(%s, m%s, n%s, %2d, %s) %s" % (t[5], "ATCG"[(t[1] % 16) // 4], t[5][1], p, scaled(t[6], p), note))
     out.append("/* PAM variant with chain-prefix tables: %d of %d terms looked up, %d gated FMAs left */"
                % (len(live) - len(leftover), len(live), len(leftover)))
     out.append("#define CRP_SCORE_TAB_N %d" % len(data))
