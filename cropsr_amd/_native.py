@@ -132,6 +132,16 @@ SIGNATURES = {
     "crp_search_set_scheme": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int, ctypes.c_int, f64p]),
     "crp_search_run_scored": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, u32p, u64p,
                                               u64p]),
+    "crp_search_self_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               ctypes.c_uint64, u64p, voidpp]),
+    "crp_search_self_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "crp_search_self_set_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64]),
+    "crp_search_self_set_scheme": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int, f64p]),
+    "crp_search_self_sizes": (ctypes.c_int, [ctypes.c_void_p, u64p, u64p, u64p]),
+    "crp_search_self_order": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    "crp_search_self_compare": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "crp_search_self_fetch": (ctypes.c_int, [ctypes.c_void_p, u32p, u8p, u32p, u32p, u32p, u64p, ctypes.c_uint64]),
+    "crp_search_self_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_configure": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]),
     "crp_query": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     "crp_build_id": (ctypes.c_char_p, []),
@@ -165,6 +175,7 @@ ABI_VERSION = 6
 SEARCH_BULGE_DNA, SEARCH_BULGE_RNA = 1, 2
 SEARCH_PAM_3PRIME, SEARCH_PAM_5PRIME = 0, 1
 SEARCH_SHAPE_DOUBLES = 288
+SEARCH_SELF_MAX_MM = 4
 CRP_ERR_INVALID = -1
 CRP_ERR_NO_DEVICE = -2
 CRP_ERR_UNSUPPORTED = -7

@@ -1,0 +1,477 @@
+// crp_search_self.cpp -- host side of the self search (include/cropsr_hip.h crp_search_self_*; kernels in
+// crp_search_self.hip, extraction kernels of crp_search.hip; DESIGN section 15, Self search).
+//
+// create   validates the two patterns, extracts every candidate of the arena into HBM (count + emit, one chunk: the
+//          self search is not chunked, a budget too small is CRP_ERR_CAPACITY with the size it takes), flags the guide
+//          sites and zeroes one result row per candidate.
+// order    segment j: key + histogram kernel, bucket starts by a prefix sum on the host (which also keeps the bucket
+//          sizes: they are the work plan), scatter kernel.  One ordering is held at a time.
+// compare  guide sites of one handle against the candidates of another (or the same) in their current orderings, which
+//          must be of the same segment: per bucket, tiles of SELF_TILE queries x slices of candidates, cut into
+//          launches of at most pairs_per_launch pairs.  Hits add into the query handle's rows.
+// A genome of several arenas is every ordered pair of handles, segment by segment (cropsr_amd/search.py: search_self).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "crp_internal.h"
+#include "crp_search_self.h"
+
+namespace {
+
+constexpr uint64_t kPairsPerLaunch = 1ull << 36;  // the bound the given-guides compare keeps
+constexpr uint64_t kItemsPerLaunch = 1ull << 20;  // work items one upload holds
+constexpr uint32_t kSliceMin = 2048;              // candidates per slice of a bucket, at least
+constexpr uint32_t kSlicesMax = 64;               // slices per bucket, at most: a huge bucket is tiles x 64 workgroups
+constexpr uint64_t kMaxCands = (1ull << 32) - 2 * crp::SELF_PAD;
+
+uint32_t iupac_set(char c)  // bit = code: A=0 T=1 C=2 G=3
+{
+    switch (c | 0x20) {
+        case 'a': return 1;
+        case 't': return 2;
+        case 'c': return 4;
+        case 'g': return 8;
+        case 'r': return 1 | 8;
+        case 'y': return 4 | 2;
+        case 's': return 4 | 8;
+        case 'w': return 1 | 2;
+        case 'k': return 8 | 2;
+        case 'm': return 1 | 4;
+        case 'b': return 4 | 8 | 2;
+        case 'd': return 1 | 8 | 2;
+        case 'h': return 1 | 4 | 2;
+        case 'v': return 1 | 4 | 8;
+        case 'n': return 15;
+        default: return 0;
+    }
+}
+
+uint32_t complement_set(uint32_t s) { return ((s & 1) << 1) | ((s & 2) >> 1) | ((s & 4) << 1) | ((s & 8) >> 1); }
+
+double elapsed(hipEvent_t a, hipEvent_t b)
+{
+    float ms = 0.f;
+    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.0;
+}
+
+}  // namespace
+
+struct crp_search_self {
+    crp_arena *arena = nullptr;
+    crp_ctx *ctx = nullptr;
+    crp::SearchSets sets = {};
+    crp::SelfGuideRule rule = {};
+    int T = 0, pam_len = 0, max_mm = 0;
+    bool pam3 = true;
+    int seg_shift[crp::SELF_MAX_MM + 1] = {}, seg_len[crp::SELF_MAX_MM + 1] = {};
+    uint64_t n_plus = 0, n_minus = 0, n = 0, n_guides = 0, bytes = 0;
+    uint64_t pairs_per_launch = kPairsPerLaunch;
+    // device
+    uint32_t *d_cand = nullptr;   // 4 x n (SoA): hi, lo, nb, pos
+    uint8_t *d_flag = nullptr;    // n: a guide site
+    uint32_t *d_key = nullptr;    // n: the current segment's key
+    uint32_t *d_order = nullptr;  // 4 x (n + SELF_PAD): hi, lo, nb, idx of the current ordering
+    uint32_t *d_hist = nullptr;   // 2 x max keys: histogram, cursors
+    uint32_t *d_counts = nullptr;            // n x (max_mm + 1)
+    unsigned long long *d_hit_sum = nullptr;  // n
+    double *d_scheme = nullptr;
+    bool have_scheme = false;
+    int scheme_rev = 0;
+    uint4 *d_items = nullptr;
+    // the current ordering
+    int segment = -1;
+    std::vector<uint32_t> hist, start;  // per key: entries, first slot
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double ms_extract = 0, ms_order = 0, ms_compare = 0, ms_longest = 0;
+    uint64_t n_compare = 0, n_order = 0, pairs = 0;
+
+    crp::SearchCands cands() const { return crp::SearchCands{d_cand, d_cand + n, d_cand + 2 * n, d_cand + 3 * n}; }
+    crp::SelfOrder order() const
+    {
+        const uint64_t m = n + crp::SELF_PAD;
+        return crp::SelfOrder{d_order, d_order + m, d_order + 2 * m, d_order + 3 * m};
+    }
+    uint64_t max_keys() const { return 2ull << (2 * crp::SELF_MAX_SEG_LETTERS); }
+};
+
+namespace {
+
+int extract(crp_search_self *s, uint64_t budget, uint64_t *needed)
+{
+    crp_ctx *ctx = s->ctx;
+    crp_arena *a = s->arena;
+    const crp::Planes pl{{a->d_plane[0], a->d_plane[1], a->d_plane[2], a->d_plane[3]}};
+    const uint64_t n_blocks = (a->used_words + crp::SEARCH_WORDS - 1) / crp::SEARCH_WORDS;
+    std::vector<uint2> cnt(n_blocks);
+    uint2 *d_cnt = nullptr;
+    uint32_t *d_off = nullptr;
+    int rc = CRP_OK;
+    const auto fail = [&](hipError_t e, const char *what) {
+        ctx->last_error = std::string(what) + ": " + hipGetErrorString(e);
+        rc = e == hipErrorOutOfMemory ? CRP_ERR_NOMEM : CRP_ERR_HIP;
+    };
+    hipError_t e = hipSuccess;
+    if (n_blocks) {
+        e = hipMalloc(reinterpret_cast<void **>(&d_cnt), n_blocks * sizeof(uint2));
+        if (e == hipSuccess) e = hipEventRecord(s->ev[0], ctx->stream);
+        if (e == hipSuccess) e = crp::launch_search_count(ctx->stream, pl, a->used_words, s->sets, d_cnt);
+        if (e == hipSuccess) e = hipEventRecord(s->ev[1], ctx->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(cnt.data(), d_cnt, n_blocks * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+        (void)hipFree(d_cnt);
+        if (e != hipSuccess) {
+            fail(e, "crp_search_self_create (count)");
+            return rc;
+        }
+        s->ms_extract += elapsed(s->ev[0], s->ev[1]);
+    }
+    std::vector<uint32_t> off(n_blocks);
+    uint64_t total = 0;
+    for (uint64_t b = 0; b < n_blocks; ++b) {
+        off[b] = (uint32_t)total;
+        total += (uint64_t)cnt[b].x + cnt[b].y;
+        s->n_plus += cnt[b].x;
+        s->n_minus += cnt[b].y;
+    }
+    if (total > kMaxCands) return CRP_ERR_UNSUPPORTED;
+    s->n = total;
+    // what the handle holds per candidate: 16 B of fields, 16 B of the current ordering, key, flag, one result row
+    const uint64_t row = 4ull * (s->max_mm + 1) + 8;
+    s->bytes = total * (16 + 16 + 4 + 1 + row) + 16ull * crp::SELF_PAD + 2 * s->max_keys() * sizeof(uint32_t) +
+               kItemsPerLaunch * sizeof(uint4);
+    if (needed) *needed = s->bytes;
+    if (s->bytes > budget) return CRP_ERR_CAPACITY;
+    const uint64_t n1 = std::max<uint64_t>(total, 1);
+    CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->d_cand), n1 * 16));
+    CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->d_flag), n1));
+    CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->d_key), n1 * 4));
+    CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->d_order), (total + crp::SELF_PAD) * 16));
+    CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->d_hist), 2 * s->max_keys() * sizeof(uint32_t)));
+    CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->d_counts), n1 * 4 * (s->max_mm + 1)));
+    CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->d_hit_sum), n1 * 8));
+    CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->d_items), kItemsPerLaunch * sizeof(uint4)));
+    CRP_HIP(ctx, hipMemsetAsync(s->d_order, 0, (total + crp::SELF_PAD) * 16, ctx->stream));  // (the pad is read, never used)
+    CRP_HIP(ctx, hipMemsetAsync(s->d_counts, 0, n1 * 4 * (s->max_mm + 1), ctx->stream));
+    CRP_HIP(ctx, hipMemsetAsync(s->d_hit_sum, 0, n1 * 8, ctx->stream));
+    unsigned long long *d_ng = reinterpret_cast<unsigned long long *>(s->d_hist);  // (free until the first ordering)
+    CRP_HIP(ctx, hipMemsetAsync(d_ng, 0, sizeof(unsigned long long), ctx->stream));
+    if (total) {
+        CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&d_off), n_blocks * sizeof(uint32_t)));
+        e = hipMemcpyAsync(d_off, off.data(), n_blocks * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipEventRecord(s->ev[0], ctx->stream);
+        if (e == hipSuccess)
+            e = crp::launch_search_emit(ctx->stream, pl, a->used_words, s->sets, 0, (uint32_t)n_blocks, d_off, s->cands());
+        if (e == hipSuccess) e = crp::launch_self_flag(ctx->stream, s->cands(), (uint32_t)total, s->rule, s->d_flag, d_ng);
+        if (e == hipSuccess) e = hipEventRecord(s->ev[1], ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // (off is read until here)
+        (void)hipFree(d_off);
+        if (e != hipSuccess) {
+            fail(e, "crp_search_self_create (emit)");
+            return rc;
+        }
+        s->ms_extract += elapsed(s->ev[0], s->ev[1]);
+    }
+    unsigned long long ng = 0;
+    CRP_HIP(ctx, hipMemcpy(&ng, d_ng, sizeof(ng), hipMemcpyDeviceToHost));
+    s->n_guides = ng;
+    return CRP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int crp_search_self_create(crp_arena *a, const char *pattern, const char *guide_pattern, int T, int pam_len, int max_mm, uint64_t budget,
+                           uint64_t *needed_bytes, crp_search_self **out)
+{
+    if (!a || !pattern || !out) return CRP_ERR_INVALID;
+    *out = nullptr;
+    if (needed_bytes) *needed_bytes = 0;
+    if (!guide_pattern) guide_pattern = pattern;
+    if (T < 2 || T > CRP_SEARCH_MAX_T || max_mm < 0 || max_mm > CRP_SEARCH_SELF_MAX_MM) return CRP_ERR_UNSUPPORTED;
+    if (pam_len < 1 || pam_len >= T) return CRP_ERR_INVALID;
+    crp::SearchSets sets = {};
+    sets.T = T;
+    for (int o = 0; o < T; ++o) {
+        const uint32_t sp = iupac_set(pattern[o]), sm = iupac_set(pattern[T - 1 - o]);
+        if (!sp || !sm || !iupac_set(guide_pattern[o])) return CRP_ERR_INVALID;
+        sets.plus[o >> 4] |= (uint64_t)sp << ((o & 15) * 4);
+        sets.minus[o >> 4] |= (uint64_t)complement_set(sm) << ((o & 15) * 4);
+    }
+    // the guide region: all N on one side of the PAM, in both patterns
+    const int G = T - pam_len;
+    const auto all_n = [&](int lo, int hi) {
+        for (int p = lo; p < hi; ++p)
+            if (iupac_set(pattern[p]) != 15 || iupac_set(guide_pattern[p]) != 15) return false;
+        return true;
+    };
+    const bool pam3 = all_n(0, G);
+    if (!pam3 && !all_n(pam_len, T)) return CRP_ERR_INVALID;
+    if (G < max_mm + 1) return CRP_ERR_UNSUPPORTED;
+    const int glo = pam3 ? 0 : pam_len;
+    crp::SelfGuideRule rule = {};
+    rule.region = (G == 32 ? ~0u : (1u << G) - 1u) << glo;
+    for (int p = pam3 ? G : 0; p < (pam3 ? T : pam_len); ++p) {
+        const uint32_t sc = iupac_set(pattern[p]), sg = iupac_set(guide_pattern[p]);
+        if (sg & ~sc) return CRP_ERR_INVALID;  // a guide site must be a candidate
+        if (sg != sc) {
+            rule.pos[rule.n] = (uint8_t)p;
+            rule.set[rule.n] = (uint8_t)sg;
+            ++rule.n;
+        }
+    }
+    if (!a->sealed) return CRP_ERR_STATE;
+    crp_ctx *ctx = a->ctx;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    crp_search_self *s = new (std::nothrow) crp_search_self;
+    if (!s) return CRP_ERR_NOMEM;
+    s->arena = a;
+    s->ctx = ctx;
+    s->sets = sets;
+    s->rule = rule;
+    s->T = T;
+    s->pam_len = pam_len;
+    s->max_mm = max_mm;
+    s->pam3 = pam3;
+    // M + 1 segments from the region's first position, as even as they come, each at most SELF_MAX_SEG_LETTERS long
+    int at = glo;
+    for (int j = 0; j <= max_mm; ++j) {
+        const int len = std::min(crp::SELF_MAX_SEG_LETTERS, G / (max_mm + 1) + (j < G % (max_mm + 1) ? 1 : 0));
+        s->seg_shift[j] = at;
+        s->seg_len[j] = len;
+        at += len;
+    }
+    int rc = CRP_OK;
+    for (int k = 0; k < 2 && rc == CRP_OK; ++k)
+        if (hipEventCreate(&s->ev[k]) != hipSuccess) rc = CRP_ERR_HIP;
+    if (rc == CRP_OK) rc = extract(s, budget ? budget : CRP_SEARCH_SELF_DEFAULT_BUDGET, needed_bytes);
+    if (rc != CRP_OK) {
+        crp_search_self_destroy(s);
+        return rc;
+    }
+    *out = s;
+    return CRP_OK;
+}
+
+int crp_search_self_destroy(crp_search_self *s)
+{
+    if (!s) return CRP_ERR_INVALID;
+    (void)hipSetDevice(s->ctx->device);
+    (void)hipFree(s->d_cand);
+    (void)hipFree(s->d_flag);
+    (void)hipFree(s->d_key);
+    (void)hipFree(s->d_order);
+    (void)hipFree(s->d_hist);
+    (void)hipFree(s->d_counts);
+    (void)hipFree(s->d_hit_sum);
+    (void)hipFree(s->d_scheme);
+    (void)hipFree(s->d_items);
+    for (hipEvent_t e : s->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete s;
+    return CRP_OK;
+}
+
+int crp_search_self_set_limits(crp_search_self *s, uint64_t pairs_per_launch)
+{
+    if (!s) return CRP_ERR_INVALID;
+    s->pairs_per_launch = pairs_per_launch ? std::min(pairs_per_launch, kPairsPerLaunch) : kPairsPerLaunch;
+    return CRP_OK;
+}
+
+int crp_search_self_set_scheme(crp_search_self *s, const double *factor, int n_factor, const double *shape)
+{
+    if (!s) return CRP_ERR_INVALID;
+    if (!factor) {
+        s->have_scheme = false;
+        return CRP_OK;
+    }
+    const int T = s->T;
+    if (!shape || n_factor != T - s->pam_len) return CRP_ERR_INVALID;
+    const auto in_unit = [](double v) { return std::isfinite(v) && v >= 0.0 && v <= 1.0; };
+    if (!std::all_of(factor, factor + n_factor, in_unit) || !std::all_of(shape, shape + CRP_SEARCH_SHAPE_DOUBLES, in_unit))
+        return CRP_ERR_INVALID;
+    // the walk table of crp_search_set_scheme: g ascends with the bit (PAM on the 3' side) or with the bit of the
+    // reversed mask (5' side)
+    double tab[crp::SEARCH_SCORE_TAB];
+    std::fill(tab, tab + crp::SEARCH_SCORE_WALK, 1.0);
+    const int rev = s->pam3 ? 0 : 1;
+    for (int g = 0; g < n_factor; ++g) tab[rev ? g + 32 - T : g] = factor[g];
+    std::copy(shape, shape + CRP_SEARCH_SHAPE_DOUBLES, tab + crp::SEARCH_SCORE_WALK);
+    crp_ctx *ctx = s->ctx;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    if (!s->d_scheme) CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->d_scheme), sizeof(tab)));
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    CRP_HIP(ctx, hipMemcpy(s->d_scheme, tab, sizeof(tab), hipMemcpyHostToDevice));
+    s->scheme_rev = rev;
+    s->have_scheme = true;
+    return CRP_OK;
+}
+
+int crp_search_self_sizes(const crp_search_self *s, uint64_t *n_plus, uint64_t *n_minus, uint64_t *n_guides)
+{
+    if (!s) return CRP_ERR_INVALID;
+    if (n_plus) *n_plus = s->n_plus;
+    if (n_minus) *n_minus = s->n_minus;
+    if (n_guides) *n_guides = s->n_guides;
+    return CRP_OK;
+}
+
+int crp_search_self_order(crp_search_self *s, int segment)
+{
+    if (!s || segment < 0 || segment > s->max_mm) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    s->segment = -1;
+    const int len = s->seg_len[segment];
+    const uint64_t keys = 2ull << (2 * len);
+    s->hist.assign(keys, 0);
+    s->start.assign(keys, 0);
+    if (s->n) {
+        uint32_t *d_cursor = s->d_hist + s->max_keys();
+        CRP_HIP(ctx, hipMemsetAsync(s->d_hist, 0, keys * sizeof(uint32_t), ctx->stream));
+        CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+        CRP_HIP(ctx, crp::launch_self_key(ctx->stream, s->cands(), (uint32_t)s->n, s->d_flag, s->seg_shift[segment], len, s->d_key, s->d_hist));
+        CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+        CRP_HIP(ctx, hipMemcpyAsync(s->hist.data(), s->d_hist, keys * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        s->ms_order += elapsed(s->ev[0], s->ev[1]);
+        uint64_t at = 0;
+        for (uint64_t k = 0; k < keys; ++k) {
+            s->start[k] = (uint32_t)at;
+            at += s->hist[k];
+        }
+        if (at > s->n) {  // (cannot be: every candidate has at most one key)
+            ctx->last_error = "crp_search_self_order: histogram larger than the candidate list";
+            return CRP_ERR_HIP;
+        }
+        const crp::SelfOrder o = s->order();
+        CRP_HIP(ctx, hipMemcpyAsync(d_cursor, s->start.data(), keys * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream));
+        CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+        CRP_HIP(ctx, crp::launch_self_scatter(ctx->stream, s->cands(), (uint32_t)s->n, s->d_key, s->rule.region, d_cursor,
+                                              const_cast<uint32_t *>(o.hi), const_cast<uint32_t *>(o.lo), const_cast<uint32_t *>(o.nb),
+                                              const_cast<uint32_t *>(o.idx)));
+        CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+        CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        s->ms_order += elapsed(s->ev[0], s->ev[1]);
+        s->n_order += 2;
+    }
+    s->segment = segment;
+    return CRP_OK;
+}
+
+int crp_search_self_compare(crp_search_self *q, crp_search_self *c)
+{
+    if (!q || !c) return CRP_ERR_INVALID;
+    if (q->ctx != c->ctx || q->T != c->T || q->pam_len != c->pam_len || q->max_mm != c->max_mm || q->rule.region != c->rule.region)
+        return CRP_ERR_INVALID;
+    if (q->segment < 0 || q->segment != c->segment) return CRP_ERR_STATE;
+    crp_ctx *ctx = q->ctx;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    crp::SelfCompare cmp = {};
+    cmp.n_before = q->segment;
+    cmp.max_mm = q->max_mm;
+    cmp.skip_same = q == c;
+    for (int j = 0; j < q->segment; ++j) cmp.before[j] = ((1u << q->seg_len[j]) - 1u) << q->seg_shift[j];
+    crp::SearchScore score{q->d_scheme, q->scheme_rev, q->d_hit_sum};
+    const crp::SearchScore *sc = q->have_scheme ? &score : nullptr;
+    std::vector<uint4> items;
+    uint64_t pairs = 0;
+    const auto flush = [&]() -> int {
+        if (items.empty()) return CRP_OK;
+        CRP_HIP(ctx, hipMemcpy(q->d_items, items.data(), items.size() * sizeof(uint4), hipMemcpyHostToDevice));
+        CRP_HIP(ctx, hipEventRecord(q->ev[0], ctx->stream));
+        CRP_HIP(ctx, crp::launch_self_compare(ctx->stream, q->order(), c->order(), q->d_items, (uint32_t)items.size(), cmp, q->d_counts, sc));
+        CRP_HIP(ctx, hipEventRecord(q->ev[1], ctx->stream));
+        CRP_HIP(ctx, hipEventSynchronize(q->ev[1]));
+        const double ms = elapsed(q->ev[0], q->ev[1]);
+        q->ms_compare += ms;
+        q->ms_longest = std::max(q->ms_longest, ms);
+        q->n_compare += 1;
+        q->pairs += pairs;
+        items.clear();
+        pairs = 0;
+        return CRP_OK;
+    };
+    const uint64_t buckets = q->hist.size() / 2;
+    for (uint64_t b = 0; b < buckets; ++b) {
+        const uint32_t nq = q->hist[2 * b], nc = c->hist[2 * b] + c->hist[2 * b + 1];
+        if (!nq || !nc) continue;
+        const uint32_t slices = std::min<uint32_t>(kSlicesMax, (nc + kSliceMin - 1) / kSliceMin);
+        const uint32_t per = ((nc + slices - 1) / slices + crp::SELF_UNROLL - 1) / crp::SELF_UNROLL * crp::SELF_UNROLL;
+        for (uint32_t t = 0; t < nq; t += crp::SELF_TILE) {
+            const uint32_t tq = std::min<uint32_t>(crp::SELF_TILE, nq - t);
+            for (uint32_t c0 = 0; c0 < nc; c0 += per) {
+                const uint32_t tc = std::min(per, nc - c0);
+                const uint64_t p = (uint64_t)tq * tc;
+                if (!items.empty() && (pairs + p > q->pairs_per_launch || items.size() >= kItemsPerLaunch)) {
+                    const int rc = flush();
+                    if (rc != CRP_OK) return rc;
+                }
+                items.push_back(make_uint4(q->start[2 * b] + t, tq, c->start[2 * b] + c0, tc));
+                pairs += p;
+            }
+        }
+    }
+    return flush();
+}
+
+int crp_search_self_fetch(crp_search_self *s, uint32_t *arena_pos, uint8_t *strand, uint32_t *hi, uint32_t *lo, uint32_t *counts,
+                          uint64_t *hit_sum, uint64_t cap)
+{
+    if (!s) return CRP_ERR_INVALID;
+    if (cap < s->n_guides) return CRP_ERR_CAPACITY;
+    crp_ctx *ctx = s->ctx;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const uint64_t chunk = 1ull << 22, stride = (uint64_t)s->max_mm + 1;
+    std::vector<uint8_t> flag(chunk);
+    std::vector<uint32_t> w(chunk), cnt(counts ? chunk * stride : 0);
+    std::vector<uint64_t> hs(hit_sum ? chunk : 0);
+    const crp::SearchCands c = s->cands();
+    uint64_t k = 0;
+    for (uint64_t i0 = 0; i0 < s->n; i0 += chunk) {
+        const uint64_t m = std::min(chunk, s->n - i0);
+        CRP_HIP(ctx, hipMemcpy(flag.data(), s->d_flag + i0, m, hipMemcpyDeviceToHost));
+        const uint64_t k0 = k;
+        const auto column = [&](const uint32_t *src, auto put) -> int {
+            CRP_HIP(ctx, hipMemcpy(w.data(), src + i0, m * sizeof(uint32_t), hipMemcpyDeviceToHost));
+            uint64_t kk = k0;
+            for (uint64_t i = 0; i < m; ++i)
+                if (flag[i]) put(kk++, w[i]);
+            return CRP_OK;
+        };
+        int rc = CRP_OK;
+        if (arena_pos || strand)
+            rc = column(c.pos, [&](uint64_t kk, uint32_t v) {
+                if (arena_pos) arena_pos[kk] = v & 0x7fffffffu;
+                if (strand) strand[kk] = (uint8_t)(v >> 31);
+            });
+        if (rc == CRP_OK && hi) rc = column(c.hi, [&](uint64_t kk, uint32_t v) { hi[kk] = v; });
+        if (rc == CRP_OK && lo) rc = column(c.lo, [&](uint64_t kk, uint32_t v) { lo[kk] = v; });
+        if (rc != CRP_OK) return rc;
+        if (counts) CRP_HIP(ctx, hipMemcpy(cnt.data(), s->d_counts + i0 * stride, m * stride * sizeof(uint32_t), hipMemcpyDeviceToHost));
+        if (hit_sum) CRP_HIP(ctx, hipMemcpy(hs.data(), s->d_hit_sum + i0, m * sizeof(uint64_t), hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < m; ++i) {
+            if (!flag[i]) continue;
+            if (counts) std::memcpy(counts + k * stride, cnt.data() + i * stride, stride * sizeof(uint32_t));
+            if (hit_sum) hit_sum[k] = hs[i];
+            ++k;
+        }
+    }
+    return k == s->n_guides ? CRP_OK : CRP_ERR_HIP;
+}
+
+int crp_search_self_stats(const crp_search_self *s, double *out, int n)
+{
+    if (!s || (n && !out) || n < 0 || n > 8) return CRP_ERR_INVALID;
+    const double v[8] = {s->ms_extract, s->ms_order, s->ms_compare, (double)s->n_compare,
+                         s->ms_longest, (double)s->pairs, (double)s->bytes, (double)s->n_order};
+    for (int k = 0; k < n; ++k) out[k] = v[k];
+    return CRP_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,180 @@
+// crp_search_self.hip -- the self search (Self search): every guide site of an arena against every
+// candidate site, without visiting all pairs.
+//
+// Two windows within M mismatches agree exactly, on bases, in at least one of the first M + 1 segments of the guide
+// region.  So, per segment j:
+//
+//   order    a counting sort of the candidates by their 2-bit codes over segment j (self_key_kernel: key and
+//            histogram; the host turns the histogram into bucket starts; self_scatter_kernel: one slot per candidate
+//            through a cursor per key).  A bucket's guide sites come first: they are its queries.
+//   compare  per bucket its guide sites against its candidates, all pairs.  One query per lane, in registers with its
+//            M + 1 counters and its sum; the candidates of a slice are wave-uniform (scalar loads of 8 words per field).
+//            Per pair: popc((h ^ qh) | (l ^ ql) | nb) <= M over fields masked to the guide region when the ordering was
+//            written.  The no-hit loop has no atomics and no memory traffic of its own; a hit is counted only if its
+//            mask is non-zero in every segment before j (else that segment's bucket has counted it), and a lane adds
+//            its row to the result once, at the end of its slice.
+//
+// Only vector stores and vector atomics, like the rest of the library.
+#include "crp_search_self.h"
+
+namespace crp {
+
+namespace {
+
+// (x ^ q) | y in one v_bitop3_b32 (truth table over x, q, y = 0xF0, 0xCC, 0xAA)
+__device__ __forceinline__ uint32_t xor_or(uint32_t x, uint32_t q, uint32_t y) { return __builtin_amdgcn_bitop3_b32(x, q, y, 0xBE); }
+
+__global__ __launch_bounds__(BLOCK) void self_flag_kernel(SearchCands c, uint32_t n, SelfGuideRule rule, uint8_t *__restrict__ flag,
+                                                          unsigned long long *__restrict__ n_guides)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    bool guide = false;
+    if (i < n) {
+        const uint32_t h = c.hi[i], l = c.lo[i], nb = c.nb[i];
+        guide = (nb & rule.region) == 0;
+        for (int k = 0; k < rule.n; ++k) {  // (wave-uniform trip count)
+            const int p = rule.pos[k];
+            const uint32_t code = ((h >> p) & 1u) << 1 | ((l >> p) & 1u);
+            guide = guide && !((nb >> p) & 1u) && ((rule.set[k] >> code) & 1u);
+        }
+        flag[i] = guide ? 1 : 0;
+    }
+    const uint64_t bal = __ballot(guide);
+    if ((threadIdx.x & 63) == 0 && bal) atomicAdd(n_guides, (unsigned long long)__popcll(bal));
+}
+
+__global__ __launch_bounds__(BLOCK) void self_key_kernel(SearchCands c, uint32_t n, const uint8_t *__restrict__ flag, int shift, int len,
+                                                         uint32_t *__restrict__ key, uint32_t *__restrict__ hist)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t m = (1u << len) - 1u;
+    const uint32_t h = (c.hi[i] >> shift) & m, l = (c.lo[i] >> shift) & m, nb = (c.nb[i] >> shift) & m;
+    uint32_t k = SELF_NO_KEY;
+    if (!nb) {
+        k = ((h << len | l) << 1) | (flag[i] ? 0u : 1u);
+        atomicAdd(&hist[k], 1u);
+    }
+    key[i] = k;
+}
+
+__global__ __launch_bounds__(BLOCK) void self_scatter_kernel(SearchCands c, uint32_t n, const uint32_t *__restrict__ key, uint32_t region,
+                                                             uint32_t *__restrict__ cursor, uint32_t *__restrict__ hi,
+                                                             uint32_t *__restrict__ lo, uint32_t *__restrict__ nb, uint32_t *__restrict__ idx)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t k = key[i];
+    if (k == SELF_NO_KEY) return;
+    const uint32_t slot = atomicAdd(&cursor[k], 1u);  // (< n: the cursors start at the prefix sums of the histogram)
+    hi[slot] = c.hi[i] & region;
+    lo[slot] = c.lo[i] & region;
+    nb[slot] = c.nb[i] & region;
+    idx[slot] = i;
+}
+
+// The value of one hit under the scheme: the walk of search_score_compare_kernel (crp_search.hip), step for step.
+__device__ __forceinline__ uint32_t hit_value(uint32_t mask, int n, const SearchScore &sc)
+{
+    uint32_t m = sc.rev ? __builtin_bitreverse32(mask) : mask;
+    const int d = 31 - __builtin_clz(mask) - __builtin_ctz(mask);  // last - first mismatching position (mask != 0)
+    double hv = 1.0;
+    while (m) {
+        hv = __dmul_rn(hv, sc.tab[__builtin_ctz(m)]);
+        m &= m - 1;
+    }
+    hv = __dmul_rn(hv, sc.tab[SEARCH_SCORE_WALK + n * SEARCH_SCORE_SPREAD + d]);
+    return (uint32_t)__builtin_rint(__dmul_rn(hv, (double)(1u << SEARCH_SCORE_SHIFT)));
+}
+
+template <bool SCORED>
+__global__ __launch_bounds__(SELF_TILE) void search_self_compare_kernel(const uint32_t *__restrict__ q_hi, const uint32_t *__restrict__ q_lo,
+                                                                        const uint32_t *__restrict__ q_idx,
+                                                                        const uint32_t *__restrict__ c_hi, const uint32_t *__restrict__ c_lo,
+                                                                        const uint32_t *__restrict__ c_nb, const uint4 *__restrict__ items,
+                                                                        SelfCompare cmp, uint32_t *__restrict__ counts, SearchScore sc)
+{
+    const uint4 it = items[blockIdx.x];  // wave-uniform: {first query, queries, first candidate, candidates}
+    const bool have = threadIdx.x < it.y;
+    const uint32_t qi = it.x + threadIdx.x;
+    const uint32_t qh = have ? q_hi[qi] : 0u, ql = have ? q_lo[qi] : 0u;
+    const int lim = have ? cmp.max_mm : -1;  // a lane without a query never hits
+    const uint32_t self = cmp.skip_same ? qi : ~0u;
+    uint32_t cnt[SELF_MAX_MM + 1] = {};
+    unsigned long long sum = 0;
+    const uint32_t end = it.z + it.w;
+    for (uint32_t i = it.z; i < end; i += SELF_UNROLL) {  // (the words behind `end` belong to the next slice or the pad)
+        const uint32_t *ph = c_hi + i, *pl = c_lo + i, *pn = c_nb + i;  // 8 consecutive words each: one scalar load
+        int mm[SELF_UNROLL];
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < SELF_UNROLL; ++k) {
+            mm[k] = __popc(xor_or(qh, ph[k], xor_or(ql, pl[k], pn[k])));
+            any |= mm[k] <= lim;
+        }
+        if (__builtin_expect(any, 0)) {
+#pragma unroll
+            for (int k = 0; k < SELF_UNROLL; ++k) {
+                if (mm[k] > lim || i + k >= end || i + k == self) continue;
+                const uint32_t mask = xor_or(qh, ph[k], xor_or(ql, pl[k], pn[k]));
+                bool first = true;  // no earlier segment's bucket holds this pair
+#pragma unroll
+                for (int s = 0; s < SELF_MAX_MM; ++s) first = first && (s >= cmp.n_before || (mask & cmp.before[s]) != 0u);
+                if (!first) continue;
+#pragma unroll
+                for (int n = 0; n <= SELF_MAX_MM; ++n) cnt[n] += mm[k] == n ? 1u : 0u;
+                if (SCORED && mm[k] > 0) sum += hit_value(mask, mm[k], sc);
+            }
+        }
+    }
+    if (!have) return;
+    const uint32_t row = q_idx[qi];
+    const uint32_t stride = (uint32_t)cmp.max_mm + 1;
+#pragma unroll
+    for (int n = 0; n <= SELF_MAX_MM; ++n)
+        if (n <= cmp.max_mm && cnt[n]) atomicAdd(&counts[(uint64_t)row * stride + n], cnt[n]);
+    if (SCORED && sum) atomicAdd(&sc.hit_sum[row], sum);
+}
+
+inline uint32_t blocks_for(uint32_t n) { return (uint32_t)(((uint64_t)n + BLOCK - 1) / BLOCK); }
+
+}  // namespace
+
+hipError_t launch_self_flag(hipStream_t s, const SearchCands &c, uint32_t n, const SelfGuideRule &rule, uint8_t *flag,
+                            unsigned long long *n_guides)
+{
+    if (!n) return hipSuccess;
+    self_flag_kernel<<<dim3(blocks_for(n)), dim3(BLOCK), 0, s>>>(c, n, rule, flag, n_guides);
+    return hipGetLastError();
+}
+
+hipError_t launch_self_key(hipStream_t s, const SearchCands &c, uint32_t n, const uint8_t *flag, int shift, int len, uint32_t *key,
+                           uint32_t *hist)
+{
+    if (!n) return hipSuccess;
+    self_key_kernel<<<dim3(blocks_for(n)), dim3(BLOCK), 0, s>>>(c, n, flag, shift, len, key, hist);
+    return hipGetLastError();
+}
+
+hipError_t launch_self_scatter(hipStream_t s, const SearchCands &c, uint32_t n, const uint32_t *key, uint32_t region, uint32_t *cursor,
+                               uint32_t *hi, uint32_t *lo, uint32_t *nb, uint32_t *idx)
+{
+    if (!n) return hipSuccess;
+    self_scatter_kernel<<<dim3(blocks_for(n)), dim3(BLOCK), 0, s>>>(c, n, key, region, cursor, hi, lo, nb, idx);
+    return hipGetLastError();
+}
+
+hipError_t launch_self_compare(hipStream_t s, const SelfOrder &q, const SelfOrder &c, const uint4 *items, uint32_t n_items,
+                               const SelfCompare &cmp, uint32_t *counts, const SearchScore *score)
+{
+    if (!n_items) return hipSuccess;
+    if (score)
+        search_self_compare_kernel<true><<<dim3(n_items), dim3(SELF_TILE), 0, s>>>(q.hi, q.lo, q.idx, c.hi, c.lo, c.nb, items, cmp, counts,
+                                                                                  *score);
+    else
+        search_self_compare_kernel<false><<<dim3(n_items), dim3(SELF_TILE), 0, s>>>(q.hi, q.lo, q.idx, c.hi, c.lo, c.nb, items, cmp, counts,
+                                                                                   SearchScore{nullptr, 0, nullptr});
+    return hipGetLastError();
+}
+
+}  // namespace crp

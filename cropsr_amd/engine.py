@@ -766,6 +766,13 @@ class Genome:
         return search.search_bulges(self, pattern, queries, max_mm, pam_len, dna_bulge, rna_bulge, site_cap=site_cap, budget=budget,
                                     score=score, sites=sites)
 
+    def search_self(self, pattern, max_mm, pam_len, guide_pattern=None, score=None, budget=None, pairs_per_launch=None):
+        """Every guide site of the genome against every candidate site (search.search_self: the self search).  Returns
+        search.SelfSearchResult (.sites, .guides, .counts (n, M + 1), .hit_sum, .specificity, .candidates, .pairs)."""
+        from . import search
+        return search.search_self(self, pattern, max_mm, pam_len, guide_pattern=guide_pattern, score=score, budget=budget,
+                                  pairs_per_launch=pairs_per_launch)
+
     def close(self):
         for a in self.arenas:
             a.close()

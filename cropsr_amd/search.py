@@ -44,6 +44,22 @@ Specificity score (score=, --score / --weights; DESIGN.md section 15, Specificit
            (float64, left to right), v = rint(h * 2^30) as an integer; n = 0 (the target or a perfect copy) adds nothing
   result   hit_sum[q] = the sum of v over the query's sites with 1..M mismatches (exact, summed on the device),
            specificity[q] = 1 / (1 + hit_sum[q] / 2^30).  A query with a base at a PAM position is refused
+
+Self search (search_self, --self; DESIGN.md section 15, Self search): every guide site of the genome is a query.
+  input    the (candidate) pattern, the PAM's length P (required), M in 0..4, optionally a guide pattern of the same
+           length (default: the pattern) and a score.  The guide pattern has the same guide region (all N there) and at
+           every PAM position a letter whose base set is contained in the pattern's (...NGG guides against ...NRG
+           candidates); anything else is refused
+  guide    a guide site is a site of the guide pattern, either strand, whose G guide-region characters are all bases;
+           its query is those G letters (upper case, U as A) with N at the PAM positions
+  result   per guide site s, ordered by contig, position, strand ('+' first): counts[s][k], k = 0..M = the candidate
+           sites other than s itself (same contig, position and strand) with exactly k mismatches against s's query;
+           hit_sum[s] = the sum of v over those with 1..M mismatches; specificity[s] = 1 / (1 + hit_sum[s] / 2^30).
+           The site on the other strand of the same position, and perfect copies elsewhere, count like any site: row s
+           is search(genome, pattern, [query of s], M, pam_len=P, score=.., sites=False) with 1 taken off counts[0]
+
+    python -m cropsr_amd.search -f genome.fa --pattern NNNNNNNNNNNNNNNNNNNNNRG --guide-pattern NNNNNNNNNNNNNNNNNNNNNGG \
+        --pam-length 3 --self -m 3 --score hsu2013 -o guides.tsv
 """
 import argparse
 import ctypes
@@ -571,6 +587,206 @@ def search_bulges(genome, pattern, queries, max_mm, pam_len, dna_bulge, rna_bulg
     return BulgeSearchResult(counts, rows, kinds, spans, cands, hit_sum)
 
 
+# ---------------------------------------------------------------- self search
+MAX_SELF_MM = 4
+SELF_SITE_DTYPE = np.dtype([("contig", "<u4"), ("position", "<i8"), ("strand", "S1")])
+_IUPAC_SETS = {"A": "A", "C": "C", "G": "G", "T": "T", "R": "AG", "Y": "CT", "S": "CG", "W": "AT", "K": "GT", "M": "AC",
+               "B": "CGT", "D": "AGT", "H": "ACT", "V": "ACG", "N": "ACGT"}
+
+
+class SelfCapacityError(RuntimeError):
+    """The self search of an arena needs more device memory than the budget: .needed bytes."""
+
+    def __init__(self, needed, budget):
+        self.needed, self.budget = int(needed), budget
+        super().__init__("the self search needs %d bytes of device memory for one arena: more than the budget%s" % (
+            needed, "" if budget is None else " of %d" % budget))
+
+
+def check_self(pattern, max_mm, pam_len, guide_pattern=None, score=None):
+    """The checked input of a self search: (pattern, guide pattern, M, P, Scheme or None).  Refuses a missing PAM
+    length, M outside 0..4, a guide pattern that is not the pattern narrowed at PAM positions, and score input that
+    check_score refuses."""
+    pattern = check_pattern(pattern)
+    if pam_len is None:
+        raise SearchInputError("the self search needs the PAM's length (--pam-length)")
+    lo, hi, _ = guide_region(pattern, pam_len)
+    if not isinstance(max_mm, (int, np.integer)) or not 0 <= int(max_mm) <= MAX_SELF_MM:
+        raise SearchInputError("mismatches of a self search must be an integer 0..%d, not %r" % (MAX_SELF_MM, max_mm))
+    if hi - lo < int(max_mm) + 1:
+        raise SearchInputError("a guide region of %d positions is too short for %d mismatches" % (hi - lo, max_mm))
+    gp = pattern if guide_pattern is None else check_pattern(guide_pattern)
+    if len(gp) != len(pattern):
+        raise SearchInputError("guide pattern %s has %d letters, the pattern %d" % (gp, len(gp), len(pattern)))
+    if set(gp[lo:hi]) != {"N"}:
+        raise SearchInputError("guide pattern %s has letters other than N in the guide region" % gp)
+    for p, (g, c) in enumerate(zip(gp, pattern)):
+        if not set(_IUPAC_SETS[g]) <= set(_IUPAC_SETS[c]):
+            raise SearchInputError("guide pattern %s: %s at position %d accepts bases that %s of the pattern does not" % (gp, g, p, c))
+    scheme = check_score(pattern, pam_len, score, [])
+    return pattern, gp, int(max_mm), int(pam_len), scheme
+
+
+class ArenaSelfSearch:
+    """One crp_search_self handle: the candidates, guide flags and result rows of one arena."""
+
+    def __init__(self, arena, pattern, guide_pattern, pam_len, max_mm, budget=None):
+        self._arena = arena
+        self.max_mm = int(max_mm)
+        h, need = ctypes.c_void_p(), ctypes.c_uint64()
+        st = nat.lib().crp_search_self_create(arena._h, pattern.encode(), guide_pattern.encode(), len(pattern), int(pam_len), self.max_mm,
+                                              0 if budget is None else max(1, int(budget)), ctypes.byref(need), ctypes.byref(h))
+        self._h = None
+        if st == nat.CRP_ERR_CAPACITY:
+            raise SelfCapacityError(need.value, budget)
+        nat.check(st, "crp_search_self_create", arena._engine._ctx)
+        self._h = h
+        self.needed = need.value
+
+    def close(self):
+        if self._h:
+            nat.lib().crp_search_self_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def _check(self, st, what):
+        nat.check(st, what, self._arena._engine._ctx)
+
+    def set_limits(self, pairs_per_launch=0):
+        self._check(nat.lib().crp_search_self_set_limits(self._h, int(pairs_per_launch)), "crp_search_self_set_limits")
+
+    def set_scheme(self, scheme):
+        f = np.ascontiguousarray(scheme.factor, dtype=np.float64)
+        sh = np.ascontiguousarray(scheme.shape, dtype=np.float64).reshape(-1)
+        self._check(nat.lib().crp_search_self_set_scheme(self._h, f.ctypes.data_as(nat.f64p), f.size, sh.ctypes.data_as(nat.f64p)),
+                    "crp_search_self_set_scheme")
+
+    def sizes(self):
+        a, b, g = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(nat.lib().crp_search_self_sizes(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(g)), "crp_search_self_sizes")
+        return a.value, b.value, g.value
+
+    def order(self, segment):
+        self._check(nat.lib().crp_search_self_order(self._h, int(segment)), "crp_search_self_order")
+
+    def compare(self, other):
+        self._check(nat.lib().crp_search_self_compare(self._h, other._h), "crp_search_self_compare")
+
+    def fetch(self, scored):
+        """(arena position u32, strand u8, hi u32, lo u32, counts (n, M + 1) u32, hit_sum u64 or None) of the guide sites."""
+        n = self.sizes()[2]
+        pos, strand = np.empty(n, np.uint32), np.empty(n, np.uint8)
+        hi, lo = np.empty(n, np.uint32), np.empty(n, np.uint32)
+        counts = np.empty((n, self.max_mm + 1), np.uint32)
+        hs = np.empty(n, np.uint64) if scored else None
+        self._check(nat.lib().crp_search_self_fetch(self._h, pos.ctypes.data_as(nat.u32p), strand.ctypes.data_as(nat.u8p),
+                                                    hi.ctypes.data_as(nat.u32p), lo.ctypes.data_as(nat.u32p), counts.ctypes.data_as(nat.u32p),
+                                                    hs.ctypes.data_as(nat.u64p) if scored else None, n), "crp_search_self_fetch")
+        return pos, strand, hi, lo, counts, hs
+
+    def stats(self):
+        out = np.zeros(8, dtype=np.float64)
+        self._check(nat.lib().crp_search_self_stats(self._h, out.ctypes.data_as(nat.f64p), 8), "crp_search_self_stats")
+        keys = ("extract_ms", "order_ms", "compare_ms", "compare_launches", "longest_launch_ms", "pairs", "device_bytes", "order_launches")
+        return dict(zip(keys, (float(v) for v in out)))
+
+
+class SelfSearchResult:
+    def __init__(self, sites, guides, counts, hit_sum, candidates, pairs, stats=None):
+        self.sites = sites            # SELF_SITE_DTYPE, ordered by contig, position, strand
+        self.guides = guides          # (n,) S<G>: each guide site's G guide-region letters
+        self.counts = counts          # (n, M + 1) uint32
+        self.hit_sum = hit_sum        # (n,) uint64 (None without score=)
+        self.specificity = None if hit_sum is None else specificity(hit_sum)
+        self.candidates = candidates  # (n_plus, n_minus) over the whole genome
+        self.pairs = pairs            # (compared, brute force = guide sites x candidates)
+        self.stats = stats or {}      # the handles' times and launch counts, summed over the arenas
+
+
+def _guide_letters(hi, lo, lo_pos, G):
+    """(n,) S<G> from the windows' code bits over pattern positions lo_pos .. lo_pos + G - 1 (A=00 T=01 C=10 G=11)."""
+    out = np.empty((hi.size, G), dtype=np.uint8)
+    table = np.frombuffer(b"ATCG", dtype=np.uint8)
+    for k in range(G):  # (a column at a time: a real genome has 10^8 rows)
+        code = (((hi >> np.uint32(lo_pos + k)) & np.uint32(1)) << np.uint32(1) | ((lo >> np.uint32(lo_pos + k)) & np.uint32(1))).astype(np.uint8)
+        out[:, k] = table[code]
+    return out.view("S%d" % G).reshape(-1)
+
+
+def search_self(genome, pattern, max_mm, pam_len, guide_pattern=None, score=None, budget=None, pairs_per_launch=None):
+    """The self search over all arenas of `genome` (engine.Genome): see the module's docstring.  budget: device bytes
+    one arena's handle may take (None: the library's default); SelfCapacityError (.needed) beyond it.
+    pairs_per_launch: lowers the pairs one compare launch covers (results do not depend on it)."""
+    pattern, gp, max_mm, pam_len, scheme = check_self(pattern, max_mm, pam_len, guide_pattern, score)
+    lo, hi, _ = guide_region(pattern, pam_len)
+    handles = []
+    try:
+        for a in genome.arenas:
+            h = ArenaSelfSearch(a, pattern, gp, pam_len, max_mm, budget)
+            handles.append(h)
+            if scheme is not None:
+                h.set_scheme(scheme)
+            if pairs_per_launch:
+                h.set_limits(pairs_per_launch)
+        for j in range(max_mm + 1):
+            for h in handles:
+                h.order(j)
+            for hq in handles:  # the guide sites of one arena against the buckets of every arena
+                for hc in handles:
+                    hq.compare(hc)
+        parts, guides, counts, sums = [], [], [], []
+        cand, n_guides, stats = [0, 0], 0, {}
+        for h, a, group in zip(handles, genome.arenas, genome.groups):
+            npl, nmi, ng = h.sizes()
+            cand[0] += npl
+            cand[1] += nmi
+            n_guides += ng
+            pos, strand, fh, fl, c, hs = h.fetch(scheme is not None)
+            offs = np.asarray(a.offsets, dtype=np.int64)
+            k = np.searchsorted(offs, pos.astype(np.int64), "right") - 1
+            part = np.empty(ng, SELF_SITE_DTYPE)
+            part["contig"] = np.asarray(group, dtype=np.uint32)[k] if ng else 0
+            part["position"] = pos.astype(np.int64) - offs[k]
+            part["strand"] = np.where(strand == 0, b"+", b"-")
+            parts.append(part)
+            guides.append(_guide_letters(fh, fl, lo, hi - lo))
+            counts.append(c)
+            if hs is not None:
+                sums.append(hs)
+            for key, v in h.stats().items():
+                stats[key] = max(stats.get(key, 0.0), v) if key == "longest_launch_ms" else stats.get(key, 0.0) + v
+    finally:
+        for h in handles:
+            h.close()
+    sites = np.concatenate(parts) if parts else np.empty(0, SELF_SITE_DTYPE)
+    order = np.lexsort((sites["strand"] == b"-", sites["position"], sites["contig"]))
+    return SelfSearchResult(sites[order], np.concatenate(guides)[order], np.concatenate(counts)[order],
+                            np.concatenate(sums)[order] if scheme is not None else None, tuple(cand),
+                            (int(stats.get("pairs", 0)), n_guides * (cand[0] + cand[1])), stats)
+
+
+def format_self(contig_names, res, block=1 << 16):
+    """The TSV of a self search, as an iterator of text blocks: contig, position, strand, guide, n0 .. nM and, when
+    scored, hit_sum (as a sum of hit scores, hit_sum / 2^30) and specificity.  The columns are formatted with numpy, a
+    block of rows at a time."""
+    M1 = res.counts.shape[1]
+    head = ["contig", "position", "strand", "guide"] + ["n%d" % k for k in range(M1)]
+    yield "\t".join(head + ([] if res.hit_sum is None else ["hit_sum", "specificity"])) + "\n"
+    names = np.array(list(contig_names) or [""], dtype=object)
+    for i0 in range(0, len(res.sites), block):
+        s = res.sites[i0:i0 + block]
+        cols = [names[s["contig"]].astype(str), s["position"].astype(str), s["strand"].astype(str), res.guides[i0:i0 + block].astype(str)]
+        cols += [res.counts[i0:i0 + block, k].astype(str) for k in range(M1)]
+        if res.hit_sum is not None:
+            hs = res.hit_sum[i0:i0 + block].astype(np.float64) / float(1 << SCORE_SHIFT)
+            cols += [np.char.mod("%.6f", hs), np.char.mod("%.6f", res.specificity[i0:i0 + block])]
+        line = cols[0]
+        for c in cols[1:]:
+            line = np.char.add(np.char.add(line, "\t"), c)
+        yield "\n".join(line.tolist()) + "\n"
+
+
 # ---------------------------------------------------------------- TSV
 _CODE = np.full(256, 4, dtype=np.uint8)  # 0..3 = A C G T, 4 = not a base
 for _c, _v in zip(b"ACGTUacgt", (0, 1, 2, 3, 0, 0, 1, 2, 3)):
@@ -690,7 +906,13 @@ def main(argv=None):
                                              "(MI355X; DESIGN.md section 15).")
     ap.add_argument("-f", "--fasta", required=True, help="genome FASTA")
     ap.add_argument("--pattern", required=True, help="PAM pattern over ACGTRYSWKMBDHVN, e.g. NNNNNNNNNNNNNNNNNNNNNRG")
-    ap.add_argument("--guides", required=True, help="one guide per line: SEQUENCE [NAME]; '#' starts a comment")
+    ap.add_argument("--guides", help="one guide per line: SEQUENCE [NAME]; '#' starts a comment (required without --self)")
+    ap.add_argument("--self", dest="self_search", action="store_true",
+                    help="the self search: every guide site of the genome is a query; -o gets one line per guide site (contig, "
+                         "position, strand, guide, n0..nM and, when scored, hit_sum and specificity); needs --pam-length, -m 0..4; "
+                         "not with --guides, --dna-bulge, --rna-bulge, --no-sites or --counts")
+    ap.add_argument("--guide-pattern", help="with --self: the pattern of the guide sites (default: --pattern), e.g. ...NGG guides "
+                                            "against ...NRG candidates")
     ap.add_argument("--pam-length", type=int, default=None, metavar="P",
                     help="the PAM is the pattern's last (or, for a 5' PAM, first) P letters: guides shorter than the pattern "
                          "sit right next to it (3 for ...NGG, 6 for ...NNGRRT, 4 for TTTV...); without it a shorter guide "
@@ -715,6 +937,12 @@ def main(argv=None):
     ap.add_argument("--no-sites", action="store_true", help="keep and write no site list: only --counts (with the scores, if asked for)")
     ap.add_argument("--device", type=int, default=0, help="HIP device")
     args = ap.parse_args(argv)
+    if args.self_search:
+        return _main_self(ap, args)
+    if not args.guides:
+        ap.error("the following arguments are required: --guides (or --self)")
+    if args.guide_pattern:
+        ap.error("--guide-pattern belongs to --self")
     try:
         pattern = check_pattern(args.pattern)
         max_mm = check_max_mm(args.mismatches)
@@ -758,6 +986,38 @@ def main(argv=None):
     else:
         print("%d guides, %d + %d candidate sites, %d sites within %d mismatches" % (
             len(queries), res.candidates[0][0], res.candidates[0][1], int(res.counts.sum()), max_mm), file=sys.stderr)
+    return 0
+
+
+def _main_self(ap, args):
+    """--self: checks, then search_self and the TSV."""
+    try:
+        for opt, given in (("--guides", args.guides), ("--dna-bulge", args.dna_bulge), ("--rna-bulge", args.rna_bulge),
+                           ("--no-sites", args.no_sites), ("--counts", args.counts)):
+            if given:
+                raise SearchInputError("--self does not go with %s" % opt)
+        if not args.output:
+            raise SearchInputError("--self needs -o/--output")
+        score = args.score
+        if args.weights:
+            with open(args.weights, "rb") as f:
+                score = parse_weights(f.read())
+        pattern, gp, max_mm, pam_len, _ = check_self(args.pattern, args.mismatches, args.pam_length, args.guide_pattern, score)
+        contig_names, contigs = read_fasta(args.fasta)
+    except (SearchInputError, OSError, UnicodeDecodeError) as e:
+        ap.error(str(e))
+    from .engine import Engine
+    with Engine(args.device) as eng:
+        g = eng.genome(contigs)
+        try:
+            res = search_self(g, pattern, max_mm, pam_len, guide_pattern=gp, score=score)
+        finally:
+            g.close()
+    with open(args.output, "w") as f:
+        for text in format_self(contig_names, res):
+            f.write(text)
+    print("%d guide sites, %d + %d candidate sites, %d of %d pairs compared" % (
+        len(res.sites), res.candidates[0], res.candidates[1], res.pairs[0], res.pairs[1]), file=sys.stderr)
     return 0
 
 

@@ -661,6 +661,52 @@ int crp_search_run_scored(crp_search *search, const char *queries, uint64_t n_qu
  * current plan, out[5] device bytes of the candidate buffers.  n: how many of these to write (<= 6). */
 int crp_search_stats(const crp_search *search, double *out, int n);
 
+/* ---- self search: every guide site of the genome against every candidate site (Self search) -- */
+/* A guide site is a site of guide_pattern (NULL: the pattern itself) whose guide region -- the pattern_len - pam_len
+ * positions outside the PAM, all N in both patterns, the PAM being the last pam_len letters or, failing that, the
+ * first -- holds bases only; every PAM letter of guide_pattern accepts a subset of what the pattern's accepts.  Its
+ * row counts, for k = 0 .. max_mm, the candidate sites other than itself with exactly k mismatches over the guide
+ * region, and with a scheme sums their values as crp_search_run_scored does.  The pairs are found through
+ * max_mm + 1 orderings of the candidates, one per segment of the guide region (two windows within max_mm mismatches
+ * agree in one of them), never by visiting all pairs.  A handle holds all candidates of its arena, one ordering and
+ * one row per candidate in HBM: 45 + 4 (max_mm + 1) bytes per candidate. */
+typedef struct crp_search_self crp_search_self;
+#define CRP_SEARCH_SELF_MAX_MM 4
+#define CRP_SEARCH_SELF_DEFAULT_BUDGET (64ull << 30)
+/* Extracts the candidates and flags the guide sites.  budget: device bytes the handle may take (0 = the default);
+ * *needed_bytes (may be NULL) receives what it takes, also when that exceeds the budget: CRP_ERR_CAPACITY, no
+ * handle.  CRP_ERR_INVALID: a letter outside the alphabet, a guide region that is not all N, a guide pattern wider
+ * than the pattern; CRP_ERR_UNSUPPORTED: max_mm outside 0..4, pattern_len outside 2..32, a guide region shorter than
+ * max_mm + 1; CRP_ERR_STATE: arena not sealed. */
+int crp_search_self_create(crp_arena *arena, const char *pattern, const char *guide_pattern, int pattern_len, int pam_len,
+                           int max_mm, uint64_t budget, uint64_t *needed_bytes, crp_search_self **out);
+int crp_search_self_destroy(crp_search_self *self);
+/* At most pairs_per_launch pairs per compare launch (0 = the default and the most, 2^36; a launch holds at least one
+ * work item of up to 256 guide sites x one slice of a bucket).  Results do not depend on it. */
+int crp_search_self_set_limits(crp_search_self *self, uint64_t pairs_per_launch);
+/* crp_search_set_scheme for the handle's rows: n_factor must be the guide region's length; the PAM's side is the
+ * handle's.  A NULL factor clears the scheme. */
+int crp_search_self_set_scheme(crp_search_self *self, const double *factor, int n_factor, const double *shape);
+int crp_search_self_sizes(const crp_search_self *self, uint64_t *n_plus, uint64_t *n_minus, uint64_t *n_guides);
+/* Orders the handle's candidates by segment 0 .. max_mm of the guide region (replaces the ordering it held). */
+int crp_search_self_order(crp_search_self *self, int segment);
+/* The guide sites of `guides` against the candidates of `candidates` (the same handle, or another arena's with the
+ * same patterns and max_mm), both ordered by the same segment (else CRP_ERR_STATE): every pair within max_mm
+ * mismatches that agrees in this segment and in no earlier one adds to the row of its guide site.  A full search is,
+ * for every segment, the orderings of all handles and then every ordered pair of handles. */
+int crp_search_self_compare(crp_search_self *guides, crp_search_self *candidates);
+/* The guide sites in extraction order (ascending 64-position word; within a word '+' sites ascending, then '-'):
+ * forward arena start, strand (0 '+', 1 '-'), the oriented window's base codes (bit p of hi, lo = the high and low
+ * code bit of pattern position p; A=00 T=01 C=10 G=11), counts (max_mm + 1 per site) and hit_sum.  Any pointer may
+ * be NULL.  CRP_ERR_CAPACITY when cap < the number of guide sites. */
+int crp_search_self_fetch(crp_search_self *self, uint32_t *arena_pos, uint8_t *strand, uint32_t *hi, uint32_t *lo,
+                          uint32_t *counts, uint64_t *hit_sum, uint64_t cap);
+/* Measurement, accumulated since create (compare figures on the `guides` handle): out[0] ms of extraction (count,
+ * emit, guide flags), out[1] ms of ordering kernels, out[2] ms of compare kernels, out[3] compare launches, out[4]
+ * the longest compare launch in ms, out[5] pairs compared, out[6] device bytes of the handle, out[7] ordering
+ * launches.  n: how many of these to write (<= 8). */
+int crp_search_self_stats(const crp_search_self *self, double *out, int n);
+
 /* ---- options -------------------------------------------------------------- */
 /* CRP_OPT_TWO_PASS (value 0/1, default 0): with 0 crp_scan_score is ONE kernel launch; the
  * table offsets come from a chained scan across workgroups inside it (decoupled look-back

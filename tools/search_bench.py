@@ -22,6 +22,14 @@ the ISA of search_bulge_compare_kernel: its no-hit loop body is 72 VALU instruct
 (search_compare_kernel) and scored with hsu2013 (search_score_compare_kernel), interleaved in one process on the same
 resident candidates, three rounds each, compare times from crp_search_stats; plus the wall time of the plain run (with
 its fetch and sort of the site list) against the score-only run (site_cap 0: no site list at all).
+
+--self times the self search (Self search): ...NGG, hsu2013, M = 3 and M = 4, a warm-up and three
+rounds each in one process, times from the handles' stats (HIP events): extraction, the M + 1 orderings, the compare
+(launches, longest launch), pairs compared against Q x C and the compare's fraction of its issue floor.
+SELF_VALU_PER_PAIR is read from the ISA of search_self_compare_kernel (37 VALU instructions per 8 pairs).  In the same
+run 8 192 of the guide sites' queries go through search(sites=False, score="hsu2013") and are scaled to all guide
+sites: the existing path's figure for the same question.  The run checks itself: 2 048 seeded rows and the 64 rows with
+the largest counts against search(), exactly.
 """
 import argparse
 import json
@@ -41,6 +49,9 @@ from cropsr_amd import search as srch  # noqa: E402
 
 VALU_PER_PAIR = 41 / 8
 BULGE_VALU_PER_PAIR = 72 / 8
+SELF_VALU_PER_PAIR = 37 / 8
+SELF_MMS = (3, 4)
+SELF_BRUTE_Q = 8192
 BULGE_Q = 1024
 ISSUE_RATE = 256 * 128 * 2.4e9  # lane-operations per second: 256 CUs x 4 SIMD-32 x 2.4 GHz
 PATTERNS = {"NGG": "N" * 21 + "GG", "NRG": "N" * 21 + "RG"}
@@ -189,16 +200,83 @@ def score_main(args, contigs, guides, out):
     print(json.dumps(out))
 
 
+def self_main(args, contigs, out):
+    pattern, P, rounds = PATTERNS["NGG"], 3, 3
+    out.update(pattern="NGG", scheme="hsu2013", rounds=rounds, self_valu_per_pair=SELF_VALU_PER_PAIR, runs={})
+    out.pop("max_mm")
+    rng = np.random.default_rng(5)
+    with Engine(args.device) as eng:
+        out["device"] = eng.device_info()["name"].strip()
+        g = eng.genome(contigs)
+        for M in SELF_MMS:
+            rows, res = [], None
+            for r in range(rounds + 1):  # (the first is the warm-up)
+                t = time.perf_counter()
+                res = srch.search_self(g, pattern, M, P, score="hsu2013")
+                wall = time.perf_counter() - t
+                if r:
+                    rows.append(dict(res.stats, wall_s=wall))
+            n, cand = len(res.sites), sum(res.candidates)
+            med = lambda k: float(np.median([x[k] for x in rows]))
+            floor_ms = res.pairs[0] * SELF_VALU_PER_PAIR / ISSUE_RATE * 1e3
+            gpu_ms = med("extract_ms") + med("order_ms") + med("compare_ms")
+            row = dict(guide_sites=n, candidates=cand, pairs=res.pairs[0], pairs_brute_force=res.pairs[1],
+                       pairs_fraction=res.pairs[0] / max(1, res.pairs[1]), device_bytes=int(rows[0]["device_bytes"]),
+                       extract_ms=[round(x["extract_ms"], 3) for x in rows], order_ms=[round(x["order_ms"], 3) for x in rows],
+                       compare_ms=[round(x["compare_ms"], 3) for x in rows], compare_launches=int(rows[0]["compare_launches"]),
+                       longest_launch_ms=[round(x["longest_launch_ms"], 3) for x in rows], gpu_ms=round(gpu_ms, 3),
+                       wall_s=[round(x["wall_s"], 2) for x in rows], issue_floor_ms=round(floor_ms, 3),
+                       fraction_of_issue_floor=round(floor_ms / med("compare_ms"), 3),
+                       median_specificity=round(float(np.median(res.specificity)), 6))
+            # the existing path: a sample of the guide sites' queries through the given-guides compare, scaled to all of them
+            pick = np.sort(rng.choice(n, min(n, SELF_BRUTE_Q), replace=False))
+            searches = [srch.ArenaSearch(a, pattern) for a in g.arenas]
+            scheme = srch.make_scheme(pattern, P, "hsu2013")
+            queries = [srch.check_query(pattern, res.guides[i].decode(), P) for i in pick]
+            counts = np.zeros((len(queries), M + 1), np.int64)
+            sums = np.zeros(len(queries), np.uint64)
+            for s in searches:
+                s.set_scheme(scheme)
+                st, c, _, hs = s.run_scored(queries, M, 0)
+                if st not in (nat.CRP_OK, nat.CRP_ERR_CAPACITY):
+                    nat.check(st, "crp_search_run_scored")
+                counts += c
+                sums += hs
+            brute_ms = sum(s.stats()["compare_ms"] for s in searches)
+            for s in searches:
+                s.close()
+            counts[:, 0] -= 1
+            # the run checks itself: 2 048 of the sampled rows and the 64 rows with the largest counts, exactly
+            assert (res.counts[pick[:2048]] == counts[:2048]).all() and (res.hit_sum[pick[:2048]] == sums[:2048]).all(), "sampled rows differ"
+            top = np.argsort(res.counts.sum(axis=1), kind="stable")[-64:]
+            big = srch.search(g, pattern, [srch.check_query(pattern, res.guides[i].decode(), P) for i in top], M, pam_len=P, score="hsu2013",
+                              sites=False)
+            bc = big.counts.astype(np.int64)
+            bc[:, 0] -= 1
+            assert (res.counts[top] == bc).all() and (res.hit_sum[top] == big.hit_sum).all(), "largest rows differ"
+            scaled_s = brute_ms * 1e-3 * n / len(queries)
+            row.update(brute_queries=len(queries), brute_compare_ms=round(brute_ms, 3), brute_scaled_s=round(scaled_s, 1),
+                       speedup_vs_scaled_brute=round(scaled_s / (gpu_ms * 1e-3), 1), rows_checked=int(min(2048, len(queries)) + top.size))
+            out["runs"]["M%d" % M] = row
+            print("M = %d: %s" % (M, json.dumps(row)), file=sys.stderr, flush=True)
+        g.close()
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--bulge", metavar="D,R", help="time the search with DNA bulges 1..D and RNA bulges 1..R instead")
     ap.add_argument("--score", action="store_true", help="time the scored compare against the plain one instead")
+    ap.add_argument("--self", dest="self_search", action="store_true", help="time the self search (every guide site a query) instead")
     args = ap.parse_args()
     t0 = time.perf_counter()
     wl = bw.switchgrass_like(0, args.scale)
     contigs = [wl.bases(s) for s in wl.specs]
+    if args.self_search:
+        return self_main(args, contigs, dict(workload=wl.name, chars=int(sum(c.size for c in contigs)), max_mm=MAX_MM,
+                                             generate_s=round(time.perf_counter() - t0, 1)))
     guides = draw_guides(contigs, BULGE_Q if args.bulge or args.score else max(QS))
     gen_s = time.perf_counter() - t0
     if args.score:
