@@ -14,6 +14,7 @@ u8p = ctypes.POINTER(ctypes.c_uint8)
 u32p = ctypes.POINTER(ctypes.c_uint32)
 u64p = ctypes.POINTER(ctypes.c_uint64)
 f64p = ctypes.POINTER(ctypes.c_double)
+i32p = ctypes.POINTER(ctypes.c_int)
 
 
 class RowSegment(ctypes.Structure):
@@ -132,6 +133,8 @@ SIGNATURES = {
     "crp_search_set_scheme": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int, ctypes.c_int, f64p]),
     "crp_search_run_scored": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int, ctypes.c_uint64, u32p, u64p,
                                               u64p]),
+    "crp_search_set_pair_scheme": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int, ctypes.c_int, i32p, ctypes.c_int, f64p]),
+    "crp_search_self_set_pair_scheme": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int, i32p, ctypes.c_int, f64p]),
     "crp_search_self_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                ctypes.c_uint64, u64p, voidpp]),
     "crp_search_self_destroy": (ctypes.c_int, [ctypes.c_void_p]),
@@ -176,6 +179,7 @@ SEARCH_BULGE_DNA, SEARCH_BULGE_RNA = 1, 2
 SEARCH_PAM_3PRIME, SEARCH_PAM_5PRIME = 0, 1
 SEARCH_SHAPE_DOUBLES = 288
 SEARCH_SELF_MAX_MM = 4
+SEARCH_PAIR_MAX_PAM = 3
 CRP_ERR_INVALID = -1
 CRP_ERR_NO_DEVICE = -2
 CRP_ERR_UNSUPPORTED = -7

@@ -11,7 +11,8 @@
 //          picks the compare kernel, the pairs per launch, the query limit and the site word and sort-key layout.
 //          crp_search_run_scored is the plain kind with the scoring compare: per-query sums of hit values under the
 //          handle's scheme (crp_search_set_scheme; DESIGN section 15, Specificity score), zeroed with the counts at the
-//          start of every pass, so a repeated pass does not add a hit twice.
+//          start of every pass, so a repeated pass does not add a hit twice.  With a pair table instead of a scheme
+//          (crp_search_set_pair_scheme; DESIGN section 15, Pair tables) the same call runs search_pair_compare_kernel.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -64,13 +65,16 @@ uint32_t complement_set(uint32_t s) { return ((s & 1) << 1) | ((s & 2) >> 1) | (
 struct Kind {
     int dna = 0, rna = 0;
     bool scored = false;  // (plain kind only) the scoring compare: also sums the hits' values
+    bool by_pair = false;  // (scored only) under the handle's pair table, not its weighting scheme
     bool bulge() const { return dna || rna; }
     int at_bits() const { return bulge() ? 5 : 0; }
     uint64_t pairs_per_launch() const { return bulge() ? kBulgePairsPerLaunch : kPairsPerLaunch; }
     uint64_t max_queries() const { return bulge() ? kMaxBulgeQueries : kMaxQueries; }
     hipError_t compare(hipStream_t st, const crp::SearchCands &c, uint32_t n, const uint4 *queries, uint32_t q0, uint32_t nq, int max_mm,
-                       uint32_t *counts, uint2 *sites, uint64_t site_cap, unsigned long long *site_ctr, const crp::SearchScore &score) const
+                       uint32_t *counts, uint2 *sites, uint64_t site_cap, unsigned long long *site_ctr, const crp::SearchScore &score,
+                       const crp::SearchPair &pair) const
     {
+        if (scored && by_pair) return crp::launch_search_pair_compare(st, c, n, queries, q0, nq, max_mm, counts, sites, site_cap, site_ctr, pair);
         if (scored) return crp::launch_search_score_compare(st, c, n, queries, q0, nq, max_mm, counts, sites, site_cap, site_ctr, score);
         if (bulge()) return crp::launch_search_bulge_compare(st, c, n, queries, q0, nq, max_mm, dna, rna, counts, sites, site_cap, site_ctr);
         return crp::launch_search_compare(st, c, n, queries, q0, nq, max_mm, counts, sites, site_cap, site_ctr);
@@ -97,6 +101,55 @@ Site unpack_key(uint64_t key, Kind k)
 }
 
 }  // namespace
+
+namespace crp {
+
+bool search_pair_layout(const SearchSets &sets, const double *pair, int n_factor, bool pam3, const int *pam_offsets, int n_pam_offsets,
+                        const double *pam, double *tab, uint32_t *pam_pos)
+{
+    const int T = sets.T;
+    if (!pair || n_factor < 1 || n_factor > T || n_pam_offsets < 0 || n_pam_offsets > SEARCH_PAIR_MAX_PAM) return false;
+    if (n_pam_offsets && (!pam_offsets || !pam)) return false;
+    const int P = T - n_factor, glo = pam3 ? 0 : P;
+    const auto set_at = [&](int o) { return (uint32_t)(sets.plus[o >> 4] >> ((o & 15) * 4)) & 15u; };
+    for (int p = glo; p < glo + n_factor; ++p)
+        if (set_at(p) != 15u) return false;
+    const auto in_unit = [](double v) { return std::isfinite(v) && v >= 0.0 && v <= 1.0; };
+    static const int dev[4] = {0, 2, 3, 1};  // A, C, G, T in the planes' coding (A=00 T=01 C=10 G=11)
+    std::fill(tab, tab + SEARCH_PAIR_WALK * 16, 1.0);
+    std::fill(tab + SEARCH_PAIR_WALK * 16, tab + SEARCH_PAIR_TAB, 0.0);
+    // the walk order of crp_search_set_scheme: bit g of the mask (PAM on the 3' side), bit g + 32 - T of the reversed mask
+    for (int g = 0; g < n_factor; ++g)
+        for (int a = 0; a < 4; ++a)
+            for (int b = 0; b < 4; ++b) {
+                if (a == b) continue;
+                const double v = pair[(g * 4 + a) * 4 + b];
+                if (!in_unit(v)) return false;
+                tab[(pam3 ? g : g + 32 - T) * 16 + (dev[a] << 2 | dev[b])] = v;
+            }
+    *pam_pos = 0;
+    for (int k = 0; k < n_pam_offsets; ++k) {
+        const int off = pam_offsets[k];
+        if (off < 0 || off >= P || (k && off <= pam_offsets[k - 1])) return false;
+        const int p = pam3 ? n_factor + off : off;
+        if (set_at(p) == 15u) return false;  // an N of the pattern: the site may hold a non-base there
+        *pam_pos |= (uint32_t)p << (8 * k);
+    }
+    const int n_pam = 1 << (2 * n_pam_offsets);
+    for (int i = 0; i < n_pam; ++i) {
+        if (!n_pam_offsets) {
+            tab[SEARCH_PAIR_WALK * 16] = 1.0;
+            break;
+        }
+        if (!in_unit(pam[i])) return false;
+        int at = 0;
+        for (int k = 0; k < n_pam_offsets; ++k) at = at << 2 | dev[(i >> (2 * (n_pam_offsets - 1 - k))) & 3];
+        tab[SEARCH_PAIR_WALK * 16 + at] = pam[i];
+    }
+    return true;
+}
+
+}  // namespace crp
 
 struct crp_search {
     crp_arena *arena = nullptr;
@@ -129,6 +182,11 @@ struct crp_search {
     bool have_scheme = false;
     int scheme_rev = 0;
     uint32_t scheme_region = 0;
+    // pair table (crp_search_set_pair_scheme): setting either clears the other
+    double *d_pair = nullptr;
+    bool have_pair = false;
+    int pair_n_pam = 0;
+    uint32_t pair_pam_pos = 0;
     unsigned long long *d_hit_sum = nullptr;
     uint64_t hit_sum_cap = 0;
     std::vector<uint64_t> keys;  // sites of the last successful run, as pack_key of its kind
@@ -205,6 +263,7 @@ int run_pass(crp_search *s, uint32_t n_queries, int max_mm, uint64_t dev_sites, 
     CRP_HIP(ctx, hipMemsetAsync(s->d_ctr, 0, sizeof(unsigned long long), ctx->stream));
     if (kind.scored) CRP_HIP(ctx, hipMemsetAsync(s->d_hit_sum, 0, (size_t)n_queries * sizeof(unsigned long long), ctx->stream));
     const crp::SearchScore score{s->d_scheme, s->scheme_rev, s->d_hit_sum};
+    const crp::SearchPair pair{s->d_pair, s->scheme_rev, s->pair_n_pam, s->pair_pam_pos, s->d_hit_sum};
     const int n_chunks = (int)s->chunk_n.size();
     for (int c = 0; c < n_chunks; ++c) {
         const uint64_t n = s->chunk_n[c];
@@ -223,7 +282,7 @@ int run_pass(crp_search *s, uint32_t n_queries, int max_mm, uint64_t dev_sites, 
         for (uint32_t q0 = 0; q0 < n_queries; q0 += batch) {
             const uint32_t nq = std::min(batch, n_queries - q0);
             CRP_HIP(ctx, kind.compare(ctx->stream, s->cands(), (uint32_t)n, s->d_queries, q0, nq, max_mm, s->d_counts, s->d_sites, dev_sites,
-                                      s->d_ctr, score));
+                                      s->d_ctr, score, pair));
             ++launches;
         }
         CRP_HIP(ctx, hipEventRecord(s->ev[2], ctx->stream));
@@ -310,6 +369,7 @@ int crp_search_destroy(crp_search *s)
     (void)hipFree(s->d_sites);
     (void)hipFree(s->d_ctr);
     (void)hipFree(s->d_scheme);
+    (void)hipFree(s->d_pair);
     (void)hipFree(s->d_hit_sum);
     for (hipEvent_t e : s->ev)
         if (e) (void)hipEventDestroy(e);
@@ -337,7 +397,7 @@ int crp_search_set_scheme(crp_search *s, const double *factor, int n_factor, int
 {
     if (!s) return CRP_ERR_INVALID;
     if (!factor) {
-        s->have_scheme = false;
+        s->have_scheme = s->have_pair = false;
         return CRP_OK;
     }
     const int T = s->sets.T;
@@ -363,6 +423,36 @@ int crp_search_set_scheme(crp_search *s, const double *factor, int n_factor, int
     s->scheme_region = rev ? low << (T - n_factor) : low;
     s->scheme_rev = rev;
     s->have_scheme = true;
+    s->have_pair = false;
+    return CRP_OK;
+}
+
+int crp_search_set_pair_scheme(crp_search *s, const double *pair, int n_factor, int pam_side, const int *pam_offsets, int n_pam_offsets,
+                               const double *pam)
+{
+    if (!s) return CRP_ERR_INVALID;
+    if (!pair) {
+        s->have_scheme = s->have_pair = false;
+        return CRP_OK;
+    }
+    if (pam_side != CRP_SEARCH_PAM_3PRIME && pam_side != CRP_SEARCH_PAM_5PRIME) return CRP_ERR_INVALID;
+    const int T = s->sets.T;
+    const int rev = pam_side == CRP_SEARCH_PAM_5PRIME;
+    double tab[crp::SEARCH_PAIR_TAB];
+    uint32_t pam_pos = 0;
+    if (!crp::search_pair_layout(s->sets, pair, n_factor, !rev, pam_offsets, n_pam_offsets, pam, tab, &pam_pos)) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    if (!s->d_pair) CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->d_pair), sizeof(tab)));
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (no run of this handle's stream is in flight, but say so)
+    CRP_HIP(ctx, hipMemcpy(s->d_pair, tab, sizeof(tab), hipMemcpyHostToDevice));
+    const uint32_t low = n_factor == 32 ? ~0u : (1u << n_factor) - 1u;
+    s->scheme_region = rev ? low << (T - n_factor) : low;
+    s->scheme_rev = rev;
+    s->pair_n_pam = n_pam_offsets;
+    s->pair_pam_pos = pam_pos;
+    s->have_pair = true;
+    s->have_scheme = false;
     return CRP_OK;
 }
 
@@ -499,9 +589,10 @@ int crp_search_run_scored(crp_search *s, const char *queries, uint64_t n_queries
                           uint64_t *n_sites, uint64_t *hit_sum)
 {
     if (!s || !n_sites || (n_queries && (!queries || !hit_sum))) return CRP_ERR_INVALID;
-    if (!s->have_scheme) return CRP_ERR_STATE;
+    if (!s->have_scheme && !s->have_pair) return CRP_ERR_STATE;
     Kind kind;
     kind.scored = true;
+    kind.by_pair = s->have_pair;
     return run_kind(s, queries, n_queries, kind, nullptr, max_mm, site_cap, counts, n_sites, hit_sum);
 }
 

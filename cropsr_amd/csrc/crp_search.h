@@ -40,6 +40,65 @@ struct SearchScore {
     unsigned long long *hit_sum;  // per query: the sum of its hits' values
 };
 
+// A pair table on the device (Pair tables): a hit's value depends on which query letter faces which
+// site letter at every mismatching position, and on the site's PAM letters.  tab holds SEARCH_PAIR_WALK x 16 pair values
+// in walk order (bit b of the mask, or of the bit-reversed mask when rev: ascending g either way), each block indexed
+// by query code << 2 | site code in the planes' coding (A=00 T=01 C=10 G=11), then SEARCH_PAIR_PAM PAM values indexed by
+// the site's codes at the n_pam pattern positions of pam_pos (8 bits each, first position in the low byte and most
+// significant in the index; entry 0 is 1.0 when n_pam is 0).
+constexpr int SEARCH_PAIR_WALK = 32;
+constexpr int SEARCH_PAIR_MAX_PAM = 3;
+constexpr int SEARCH_PAIR_PAM = 64;
+constexpr int SEARCH_PAIR_TAB = SEARCH_PAIR_WALK * 16 + SEARCH_PAIR_PAM;
+struct SearchPair {
+    const double *tab;            // SEARCH_PAIR_TAB doubles, each in [0, 1]
+    int rev;                      // walk the bit-reversed mask (PAM on the 5' side)
+    int n_pam;                    // 0 .. SEARCH_PAIR_MAX_PAM
+    uint32_t pam_pos;             // pattern positions of the PAM letters that index the PAM values
+    unsigned long long *hit_sum;  // per query: the sum of its hits' values
+};
+
+// The 2-bit code of a window's letter at pattern position p.
+__device__ __forceinline__ uint32_t search_code_at(uint32_t h, uint32_t l, uint32_t p) { return ((h >> p) & 1u) << 1 | ((l >> p) & 1u); }
+
+// The pair factors of a mismatch mask (not 0), walked in ascending g, one correctly rounded f64 multiply per step
+// (__dmul_rn: nothing to fuse or reorder), from the window's and the query's code bits behind every set bit.
+__device__ __forceinline__ double search_pair_walk(uint32_t mask, uint32_t h, uint32_t l, uint32_t qh, uint32_t ql, const SearchPair &sp)
+{
+    uint32_t m = sp.rev ? __builtin_bitreverse32(mask) : mask;
+    const uint32_t flip = sp.rev ? 31u : 0u;  // bit b of the reversed mask is pattern position 31 - b
+    double hv = 1.0;
+    while (m) {
+        const uint32_t b = (uint32_t)__builtin_ctz(m), p = b ^ flip;
+        hv = __dmul_rn(hv, sp.tab[b * 16u + (search_code_at(qh, ql, p) << 2 | search_code_at(h, l, p))]);
+        m &= m - 1;
+    }
+    return hv;
+}
+
+// The window's PAM value: h, l must hold the PAM positions (the extraction's fields, not an ordering's masked ones).
+__device__ __forceinline__ double search_pair_pam(uint32_t h, uint32_t l, const SearchPair &sp)
+{
+    uint32_t at = 0;
+    for (int k = 0; k < sp.n_pam; ++k) at = at << 2 | search_code_at(h, l, (sp.pam_pos >> (8 * k)) & 255u);
+    return sp.tab[SEARCH_PAIR_WALK * 16 + at];
+}
+
+// v = rint(walk * pam * 2^30); every value is in [0, 1], so v <= 2^30.
+__device__ __forceinline__ uint32_t search_pair_value(double walk, double pam)
+{
+    return (uint32_t)__builtin_rint(__dmul_rn(__dmul_rn(walk, pam), (double)(1u << SEARCH_SCORE_SHIFT)));
+}
+
+// Host side of a pair table (crp_search.cpp), shared by the two handles.  pair[n_factor][4][4] (query letter, site letter
+// over A, C, G, T; the diagonal is ignored) and pam[4^n_pam_offsets] (the site's letters at those offsets inside the PAM,
+// first offset most significant) become tab[SEARCH_PAIR_TAB] and *pam_pos as SearchPair wants them.  False when the
+// input is outside the definition: a value outside [0, 1] or not finite, a guide region of n_factor positions on that
+// side that is not all N, more than SEARCH_PAIR_MAX_PAM offsets, an offset outside the PAM, not strictly ascending, or on
+// a pattern letter N.
+bool search_pair_layout(const SearchSets &sets, const double *pair, int n_factor, bool pam3, const int *pam_offsets, int n_pam_offsets,
+                        const double *pam, double *tab, uint32_t *pam_pos);
+
 // Per workgroup of SEARCH_WORDS words: {'+' candidates, '-' candidates}.
 hipError_t launch_search_count(hipStream_t s, const Planes &pl, uint64_t used_words, const SearchSets &sets, uint2 *block_cnt);
 // Writes the candidates of workgroups [block_first, block_first + n_blocks): those of workgroup b start at block_off[b]
@@ -56,6 +115,11 @@ hipError_t launch_search_compare(hipStream_t s, const SearchCands &c, uint32_t n
 hipError_t launch_search_score_compare(hipStream_t s, const SearchCands &c, uint32_t n, const uint4 *queries, uint32_t q0, uint32_t nq,
                                        int max_mm, uint32_t *counts, uint2 *sites, uint64_t site_cap, unsigned long long *site_ctr,
                                        const SearchScore &score);
+// launch_search_score_compare under a pair table: every pair with 1 .. max_mm mismatches adds its value to
+// pair.hit_sum[q] (0 when a mismatching position of the site holds a non-base).
+hipError_t launch_search_pair_compare(hipStream_t s, const SearchCands &c, uint32_t n, const uint4 *queries, uint32_t q0, uint32_t nq,
+                                      int max_mm, uint32_t *counts, uint2 *sites, uint64_t site_cap, unsigned long long *site_ctr,
+                                      const SearchPair &pair);
 // The same for the windows of one bulge kind (Bulges): candidates of T + dna or T - rna characters
 // (one of dna, rna is 0, the other 1 or 2), queries of T letters as {hi, lo, compare mask, s_min | s_max << 8} (the
 // placements s of the bulge's first query position).  Every pair whose fewest mismatches over s is within max_mm adds

@@ -15,7 +15,8 @@
 //               Per pair: popc(((h ^ qh) | (l ^ ql) | nb) & qm) <= M.  Hits are rare: a wave ballots them and reserves
 //               its slots with one atomic.  The bulge compare (DNA or RNA bulge of one size) takes, per pair, the best
 //               placement of the bulge inside the query's span; see search_bulge_compare_kernel.  The scoring compare
-//               (search_score_compare_kernel) also adds every hit's value under a weighting scheme to a per-query sum.
+//               (search_score_compare_kernel) also adds every hit's value under a weighting scheme to a per-query sum;
+//               search_pair_compare_kernel does so under a pair table (values per base pair and per PAM).
 //
 // Only vector stores and vector atomics, like the rest of the library.
 #include "crp_search.h"
@@ -277,6 +278,55 @@ __global__ __launch_bounds__(BLOCK) void search_score_compare_kernel(SearchCands
     }
 }
 
+// search_score_compare_kernel under a pair table (Pair tables): the same candidates per lane and the
+// same no-hit loop.  A lane with a hit of 1 .. max_mm mismatches has the candidate's oriented fields, PAM positions
+// included, and the query's in hand: per set bit of its mask it looks up the pair value of the two letters, then the
+// value of the site's PAM letters, and adds the hit's value with one 64-bit vector atomic.  A non-base at a mismatching
+// position gives 0.  The table is read on this path only.
+__global__ __launch_bounds__(BLOCK) void search_pair_compare_kernel(SearchCands c, uint32_t n, const uint4 *__restrict__ queries, uint32_t q0,
+                                                                    uint32_t nq, int max_mm, uint32_t *__restrict__ counts,
+                                                                    uint2 *__restrict__ sites, uint64_t site_cap,
+                                                                    unsigned long long *__restrict__ site_ctr, SearchPair sp)
+{
+    const uint32_t first = blockIdx.x * (BLOCK * SEARCH_CPL) + threadIdx.x;
+    uint32_t h[SEARCH_CPL], l[SEARCH_CPL], nb[SEARCH_CPL];
+    int lim[SEARCH_CPL];  // max_mm, or -1 past the end: a lane without a candidate never hits
+#pragma unroll
+    for (int j = 0; j < SEARCH_CPL; ++j) {
+        const uint32_t i = first + j * BLOCK;
+        const bool ok = i < n;
+        h[j] = ok ? c.hi[i] : 0u;
+        l[j] = ok ? c.lo[i] : 0u;
+        nb[j] = ok ? c.nb[i] : 0u;
+        lim[j] = ok ? max_mm : -1;
+    }
+    const uint32_t stride = (uint32_t)max_mm + 1;
+    for (uint32_t qi = q0; qi < q0 + nq; ++qi) {
+        const uint4 q = queries[qi];  // wave-uniform
+        int mm[SEARCH_CPL];
+        bool any = false;
+#pragma unroll
+        for (int j = 0; j < SEARCH_CPL; ++j) {
+            mm[j] = __popc(((h[j] ^ q.x) | (l[j] ^ q.y) | nb[j]) & q.z);
+            any |= mm[j] <= lim[j];
+        }
+        if (__builtin_expect(any, 0)) {
+#pragma unroll
+            for (int j = 0; j < SEARCH_CPL; ++j) {
+                const bool hit = mm[j] <= lim[j];
+                append_hits(hit, qi, mm[j], qi << 4 | (uint32_t)mm[j], c.pos + (first + j * BLOCK), stride, counts, sites, site_cap,
+                            site_ctr);
+                if (hit && mm[j] > 0) {
+                    const uint32_t mask = ((h[j] ^ q.x) | (l[j] ^ q.y) | nb[j]) & q.z;
+                    if (mask & nb[j]) continue;  // a non-base where the query has a base: counted, worth nothing
+                    const uint32_t v = search_pair_value(search_pair_walk(mask, h[j], l[j], q.x, q.y, sp), search_pair_pam(h[j], l[j], sp));
+                    atomicAdd(&sp.hit_sum[qi], (unsigned long long)v);
+                }
+            }
+        }
+    }
+}
+
 // (x ^ q) | y in one v_bitop3_b32 (truth table over x, q, y = 0xF0, 0xCC, 0xAA): the compiler leaves it as xor + or3
 __device__ __forceinline__ uint32_t xor_or(uint32_t x, uint32_t q, uint32_t y) { return __builtin_amdgcn_bitop3_b32(x, q, y, 0xBE); }
 
@@ -390,7 +440,17 @@ hipError_t launch_search_score_compare(hipStream_t s, const SearchCands &c, uint
     return hipGetLastError();
 }
 
-hipError_t launch_search_bulge_compare(hipStream_t s, const SearchCands &c, uint32_t n, const uint4 *queries, uint32_t q0, uint32_t nq,
+hipError_t launch_search_pair_compare(hipStream_t s, const SearchCands &c, uint32_t n, const uint4 *queries, uint32_t q0, uint32_t nq,
+                                      int max_mm, uint32_t *counts, uint2 *sites, uint64_t site_cap, unsigned long long *site_ctr,
+                                      const SearchPair &pair)
+{
+    if (!n || !nq) return hipSuccess;
+    const uint32_t blocks = (uint32_t)(((uint64_t)n + BLOCK * SEARCH_CPL - 1) / (BLOCK * SEARCH_CPL));
+    search_pair_compare_kernel<<<dim3(blocks), dim3(BLOCK), 0, s>>>(c, n, queries, q0, nq, max_mm, counts, sites, site_cap, site_ctr, pair);
+    return hipGetLastError();
+}
+
+hipError_t launch_search_bulge_compare(hipStream_t s,const SearchCands &c, uint32_t n, const uint4 *queries, uint32_t q0, uint32_t nq,
                                        int max_mm, int dna, int rna, uint32_t *counts, uint2 *sites, uint64_t site_cap,
                                        unsigned long long *site_ctr)
 {

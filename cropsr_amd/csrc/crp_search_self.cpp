@@ -80,6 +80,11 @@ struct crp_search_self {
     double *d_scheme = nullptr;
     bool have_scheme = false;
     int scheme_rev = 0;
+    // pair table (crp_search_self_set_pair_scheme): setting either clears the other
+    double *d_pair = nullptr;
+    bool have_pair = false;
+    int pair_n_pam = 0;
+    uint32_t pair_pam_pos = 0;
     uint4 *d_items = nullptr;
     // the current ordering
     int segment = -1;
@@ -268,6 +273,7 @@ int crp_search_self_destroy(crp_search_self *s)
     (void)hipFree(s->d_counts);
     (void)hipFree(s->d_hit_sum);
     (void)hipFree(s->d_scheme);
+    (void)hipFree(s->d_pair);
     (void)hipFree(s->d_items);
     for (hipEvent_t e : s->ev)
         if (e) (void)hipEventDestroy(e);
@@ -286,7 +292,7 @@ int crp_search_self_set_scheme(crp_search_self *s, const double *factor, int n_f
 {
     if (!s) return CRP_ERR_INVALID;
     if (!factor) {
-        s->have_scheme = false;
+        s->have_scheme = s->have_pair = false;
         return CRP_OK;
     }
     const int T = s->T;
@@ -308,6 +314,32 @@ int crp_search_self_set_scheme(crp_search_self *s, const double *factor, int n_f
     CRP_HIP(ctx, hipMemcpy(s->d_scheme, tab, sizeof(tab), hipMemcpyHostToDevice));
     s->scheme_rev = rev;
     s->have_scheme = true;
+    s->have_pair = false;
+    return CRP_OK;
+}
+
+int crp_search_self_set_pair_scheme(crp_search_self *s, const double *pair, int n_factor, const int *pam_offsets, int n_pam_offsets,
+                                    const double *pam)
+{
+    if (!s) return CRP_ERR_INVALID;
+    if (!pair) {
+        s->have_scheme = s->have_pair = false;
+        return CRP_OK;
+    }
+    if (n_factor != s->T - s->pam_len) return CRP_ERR_INVALID;
+    double tab[crp::SEARCH_PAIR_TAB];
+    uint32_t pam_pos = 0;
+    if (!crp::search_pair_layout(s->sets, pair, n_factor, s->pam3, pam_offsets, n_pam_offsets, pam, tab, &pam_pos)) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    if (!s->d_pair) CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->d_pair), sizeof(tab)));
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    CRP_HIP(ctx, hipMemcpy(s->d_pair, tab, sizeof(tab), hipMemcpyHostToDevice));
+    s->scheme_rev = s->pam3 ? 0 : 1;
+    s->pair_n_pam = n_pam_offsets;
+    s->pair_pam_pos = pam_pos;
+    s->have_pair = true;
+    s->have_scheme = false;
     return CRP_OK;
 }
 
@@ -378,13 +410,19 @@ int crp_search_self_compare(crp_search_self *q, crp_search_self *c)
     for (int j = 0; j < q->segment; ++j) cmp.before[j] = ((1u << q->seg_len[j]) - 1u) << q->seg_shift[j];
     crp::SearchScore score{q->d_scheme, q->scheme_rev, q->d_hit_sum};
     const crp::SearchScore *sc = q->have_scheme ? &score : nullptr;
+    // under a pair table the candidates' PAM letters are read from the candidates' handle: its fields, through its ordering
+    const crp::SearchPair pair{q->d_pair, q->scheme_rev, q->pair_n_pam, q->pair_pam_pos, q->d_hit_sum};
     std::vector<uint4> items;
     uint64_t pairs = 0;
     const auto flush = [&]() -> int {
         if (items.empty()) return CRP_OK;
         CRP_HIP(ctx, hipMemcpy(q->d_items, items.data(), items.size() * sizeof(uint4), hipMemcpyHostToDevice));
         CRP_HIP(ctx, hipEventRecord(q->ev[0], ctx->stream));
-        CRP_HIP(ctx, crp::launch_self_compare(ctx->stream, q->order(), c->order(), q->d_items, (uint32_t)items.size(), cmp, q->d_counts, sc));
+        if (q->have_pair)
+            CRP_HIP(ctx, crp::launch_self_pair_compare(ctx->stream, q->order(), c->order(), c->cands(), q->d_items, (uint32_t)items.size(), cmp,
+                                                       q->d_counts, pair));
+        else
+            CRP_HIP(ctx, crp::launch_self_compare(ctx->stream, q->order(), c->order(), q->d_items, (uint32_t)items.size(), cmp, q->d_counts, sc));
         CRP_HIP(ctx, hipEventRecord(q->ev[1], ctx->stream));
         CRP_HIP(ctx, hipEventSynchronize(q->ev[1]));
         const double ms = elapsed(q->ev[0], q->ev[1]);

@@ -53,5 +53,9 @@ hipError_t launch_self_scatter(hipStream_t s, const SearchCands &c, uint32_t n, 
 // score table, its value to hit_sum[row], row = q.idx of the query.
 hipError_t launch_self_compare(hipStream_t s, const SelfOrder &q, const SelfOrder &c, const uint4 *items, uint32_t n_items,
                                const SelfCompare &cmp, uint32_t *counts, const SearchScore *score);
+// launch_self_compare under a pair table: c_fields are the unmasked fields, in extraction order, of the handle whose
+// ordering c is (c.idx indexes them): the candidates' PAM letters are read there.  Values add to pair.hit_sum[row].
+hipError_t launch_self_pair_compare(hipStream_t s, const SelfOrder &q, const SelfOrder &c, const SearchCands &c_fields, const uint4 *items,
+                                    uint32_t n_items, const SelfCompare &cmp, uint32_t *counts, const SearchPair &pair);
 
 }  // namespace crp

@@ -136,6 +136,64 @@ __global__ __launch_bounds__(SELF_TILE) void search_self_compare_kernel(const ui
     if (SCORED && sum) atomicAdd(&sc.hit_sum[row], sum);
 }
 
+// search_self_compare_kernel<true> under a pair table (Pair tables): one query per lane, the same
+// scalar candidate loads and the same no-hit loop.  The ordering's fields are masked to the guide region, which is all a
+// mismatch's two letters need; the candidate's PAM letters come, on the hit path only, from its unmasked fields in
+// extraction order (f_hi, f_lo of the candidates' handle) through the ordering's row index.  The candidate is
+// wave-uniform, so that gather and the PAM value are scalar loads.
+__global__ __launch_bounds__(SELF_TILE) void search_self_pair_compare_kernel(const uint32_t *__restrict__ q_hi, const uint32_t *__restrict__ q_lo,
+                                                                             const uint32_t *__restrict__ q_idx,
+                                                                             const uint32_t *__restrict__ c_hi, const uint32_t *__restrict__ c_lo,
+                                                                             const uint32_t *__restrict__ c_nb, const uint32_t *__restrict__ c_idx,
+                                                                             const uint32_t *__restrict__ f_hi, const uint32_t *__restrict__ f_lo,
+                                                                             const uint4 *__restrict__ items, SelfCompare cmp,
+                                                                             uint32_t *__restrict__ counts, SearchPair sp)
+{
+    const uint4 it = items[blockIdx.x];  // wave-uniform: {first query, queries, first candidate, candidates}
+    const bool have = threadIdx.x < it.y;
+    const uint32_t qi = it.x + threadIdx.x;
+    const uint32_t qh = have ? q_hi[qi] : 0u, ql = have ? q_lo[qi] : 0u;
+    const int lim = have ? cmp.max_mm : -1;  // a lane without a query never hits
+    const uint32_t self = cmp.skip_same ? qi : ~0u;
+    uint32_t cnt[SELF_MAX_MM + 1] = {};
+    unsigned long long sum = 0;
+    const uint32_t end = it.z + it.w;
+    for (uint32_t i = it.z; i < end; i += SELF_UNROLL) {  // (the words behind `end` belong to the next slice or the pad)
+        const uint32_t *ph = c_hi + i, *pl = c_lo + i, *pn = c_nb + i;  // 8 consecutive words each: one scalar load
+        int mm[SELF_UNROLL];
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < SELF_UNROLL; ++k) {
+            mm[k] = __popc(xor_or(qh, ph[k], xor_or(ql, pl[k], pn[k])));
+            any |= mm[k] <= lim;
+        }
+        if (__builtin_expect(any, 0)) {
+#pragma unroll
+            for (int k = 0; k < SELF_UNROLL; ++k) {
+                if (mm[k] > lim || i + k >= end || i + k == self) continue;
+                const uint32_t mask = xor_or(qh, ph[k], xor_or(ql, pl[k], pn[k]));
+                bool first = true;  // no earlier segment's bucket holds this pair
+#pragma unroll
+                for (int s = 0; s < SELF_MAX_MM; ++s) first = first && (s >= cmp.n_before || (mask & cmp.before[s]) != 0u);
+                if (!first) continue;
+#pragma unroll
+                for (int n = 0; n <= SELF_MAX_MM; ++n) cnt[n] += mm[k] == n ? 1u : 0u;
+                if (mm[k] > 0 && !(mask & pn[k])) {  // (a non-base at a mismatching position: counted, worth nothing)
+                    const uint32_t row = c_idx[i + k];  // (i + k < end: an entry of the ordering, its index below the handle's n)
+                    sum += search_pair_value(search_pair_walk(mask, ph[k], pl[k], qh, ql, sp), search_pair_pam(f_hi[row], f_lo[row], sp));
+                }
+            }
+        }
+    }
+    if (!have) return;
+    const uint32_t row = q_idx[qi];
+    const uint32_t stride = (uint32_t)cmp.max_mm + 1;
+#pragma unroll
+    for (int n = 0; n <= SELF_MAX_MM; ++n)
+        if (n <= cmp.max_mm && cnt[n]) atomicAdd(&counts[(uint64_t)row * stride + n], cnt[n]);
+    if (sum) atomicAdd(&sp.hit_sum[row], sum);
+}
+
 inline uint32_t blocks_for(uint32_t n) { return (uint32_t)(((uint64_t)n + BLOCK - 1) / BLOCK); }
 
 }  // namespace
@@ -174,6 +232,15 @@ hipError_t launch_self_compare(hipStream_t s, const SelfOrder &q, const SelfOrde
     else
         search_self_compare_kernel<false><<<dim3(n_items), dim3(SELF_TILE), 0, s>>>(q.hi, q.lo, q.idx, c.hi, c.lo, c.nb, items, cmp, counts,
                                                                                    SearchScore{nullptr, 0, nullptr});
+    return hipGetLastError();
+}
+
+hipError_t launch_self_pair_compare(hipStream_t s, const SelfOrder &q, const SelfOrder &c, const SearchCands &c_fields, const uint4 *items,
+                                    uint32_t n_items, const SelfCompare &cmp, uint32_t *counts, const SearchPair &pair)
+{
+    if (!n_items) return hipSuccess;
+    search_self_pair_compare_kernel<<<dim3(n_items), dim3(SELF_TILE), 0, s>>>(q.hi, q.lo, q.idx, c.hi, c.lo, c.nb, c.idx, c_fields.hi,
+                                                                              c_fields.lo, items, cmp, counts, pair);
     return hipGetLastError();
 }
 

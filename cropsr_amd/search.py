@@ -45,6 +45,22 @@ Specificity score (score=, --score / --weights; DESIGN.md section 15, Specificit
   result   hit_sum[q] = the sum of v over the query's sites with 1..M mismatches (exact, summed on the device),
            specificity[q] = 1 / (1 + hit_sum[q] / 2^30).  A query with a base at a PAM position is refused
 
+Pair table (score=PairTable(..), --score-table; DESIGN.md section 15, Pair tables): the CFD form of a hit's value, next
+to the scheme above.  It needs the PAM's length P; G, g, hit_sum and specificity are as above, there is no shape term.
+  pair     pair[g][a][b] in [0, 1]: a the query's letter at g, b the oriented site's letter, both over A, C, G, T in
+           that order and both read 5' -> 3' on the target strand's sense (as the sites TSV prints them); the 12 entries
+           with a != b matter, the diagonal is ignored
+  pam      pam_offsets: k = 0..3 offsets inside the PAM, strictly ascending, 0 = the PAM's 5'-most letter, each on a
+           pattern letter other than N (so the site holds a base there); pam: 4^k values in [0, 1] indexed by the site's
+           letters at those offsets, first offset most significant, A, C, G, T = 0..3; with k = 0 the PAM factor is 1.0
+  hit      for a site of kind none with n >= 1 mismatches at g1 < .. < gn: h = 1.0; h = h * pair[g][query letter][site
+           letter] for g = g1 .. gn; h = h * pam[index of the site's PAM letters] (float64, one correctly rounded multiply
+           per step); v = rint(h * 2^30) as an integer.  A non-base site character at a mismatching position: v = 0 (the
+           site still counts).  n = 0 adds nothing; a query with a base at a PAM position is refused
+
+    python -m cropsr_amd.search -f genome.fa --pattern NNNNNNNNNNNNNNNNNNNNNRG --pam-length 3 --guides guides.txt -m 4 \
+        --score-table cfd.txt --no-sites --counts ranking.tsv
+
 Self search (search_self, --self; DESIGN.md section 15, Self search): every guide site of the genome is a query.
   input    the (candidate) pattern, the PAM's length P (required), M in 0..4, optionally a guide pattern of the same
            length (default: the pattern) and a score.  The guide pattern has the same guide region (all N there) and at
@@ -234,16 +250,20 @@ class ArenaSearch:
         return a.value, b.value
 
     def set_scheme(self, scheme):
-        """crp_search_set_scheme with a Scheme, or None to clear it."""
+        """crp_search_set_scheme with a Scheme, crp_search_set_pair_scheme with a PairScheme, or None to clear either."""
         if scheme is None:
             st = nat.lib().crp_search_set_scheme(self._h, None, 0, 0, None)
+        elif isinstance(scheme, PairScheme):
+            pair, G, offs, k, pam = scheme.native_args()
+            st = nat.lib().crp_search_set_pair_scheme(self._h, pair, G, nat.SEARCH_PAM_3PRIME if scheme.pam3 else nat.SEARCH_PAM_5PRIME,
+                                                      offs, k, pam)
         else:
             f = np.ascontiguousarray(scheme.factor, dtype=np.float64)
             sh = np.ascontiguousarray(scheme.shape, dtype=np.float64).reshape(-1)
             st = nat.lib().crp_search_set_scheme(self._h, f.ctypes.data_as(nat.f64p), f.size,
                                                  nat.SEARCH_PAM_3PRIME if scheme.pam3 else nat.SEARCH_PAM_5PRIME,
                                                  sh.ctypes.data_as(nat.f64p))
-        nat.check(st, "crp_search_set_scheme", self._arena._engine._ctx)
+        nat.check(st, "crp_search_set_pair_scheme" if isinstance(scheme, PairScheme) else "crp_search_set_scheme", self._arena._engine._ctx)
 
     def run_scored(self, queries, max_mm, site_cap):
         """crp_search_run_scored as it is: (status, counts (Q, M + 1) uint32, n_sites, hit_sum (Q,) uint64)."""
@@ -302,7 +322,7 @@ def search(genome, pattern, queries, max_mm, site_cap=None, budget=None, pam_len
     """Every site of `genome` (engine.Genome) within max_mm mismatches of each query, over all its arenas.
     site_cap=None: as many sites as there are; else SiteCapacityError (with exact counts) beyond it.  budget: device
     bytes for one chunk of candidates (None: the library's default).  pam_len: how check_query pads shorter guides.
-    score: "hsu2013" or G weights (see check_score; needs pam_len): the result's .hit_sum and .specificity, summed on
+    score: "hsu2013", G weights or a PairTable (see check_score; needs pam_len): the result's .hit_sum and .specificity, summed on
     the device.  sites=False: no site list is kept or fetched (.sites is empty, no SiteCapacityError): counts and sums
     only."""
     pattern = check_pattern(pattern)
@@ -382,6 +402,82 @@ class Scheme:
         return np.arange(self.lo, self.hi) if self.pam3 else np.arange(self.hi - 1, self.lo - 1, -1)
 
 
+class PairTable:
+    """The score= argument of the pair-table form (see the module's docstring): pair (G, 4, 4), pam_offsets (k offsets
+    inside the PAM) and pam (4^k values, or None with no offsets).  make_scheme checks it against a pattern."""
+
+    def __init__(self, pair, pam_offsets=(), pam=None):
+        self.pair, self.pam_offsets, self.pam = pair, pam_offsets, pam
+
+
+class PairScheme:
+    """A checked PairTable on a pattern: pair (G, 4, 4) float64 with 1.0 on the diagonal, pam_offsets, pam (4^k,), the
+    PAM letters' pattern positions, the guide region [lo, hi) of the pattern and the PAM's side."""
+
+    def __init__(self, pair, pam_offsets, pam, pam_positions, lo, hi, pam3):
+        self.pair, self.pam_offsets, self.pam, self.pam_positions = pair, pam_offsets, pam, pam_positions
+        self.lo, self.hi, self.pam3 = lo, hi, pam3
+
+    g_positions = Scheme.g_positions
+
+    def native_args(self):
+        """(pair, G, pam_offsets, k, pam) as crp_search_set_pair_scheme takes them."""
+        self._c = (np.ascontiguousarray(self.pair, dtype=np.float64).reshape(-1), np.array(self.pam_offsets, dtype=np.intc),
+                   np.ascontiguousarray(self.pam, dtype=np.float64))  # (kept alive while the call runs)
+        k = len(self.pam_offsets)
+        return (self._c[0].ctypes.data_as(nat.f64p), self.pair.shape[0], self._c[1].ctypes.data_as(nat.i32p) if k else None, k,
+                self._c[2].ctypes.data_as(nat.f64p) if k else None)
+
+
+MAX_PAM_OFFSETS = 3
+
+
+def _make_pair_scheme(pattern, pam_len, table):
+    lo, hi, pam3 = guide_region(pattern, pam_len)
+    G, P = hi - lo, int(pam_len)
+    try:
+        pair = np.array(table.pair, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise SearchInputError("pair table: the pair values must be numbers, G x 4 x 4 of them") from None
+    if pair.ndim != 3 or pair.shape[1:] != (4, 4):
+        raise SearchInputError("pair table: the pair values must be G x 4 x 4, not %s" % (pair.shape,))
+    if pair.shape[0] != G:
+        raise SearchInputError("pair table for a guide region of %d positions: the pattern's has %d" % (pair.shape[0], G))
+    pair = pair.copy()
+    pair[:, np.arange(4), np.arange(4)] = 1.0  # (the diagonal is ignored)
+    if not (np.isfinite(pair).all() and (pair >= 0).all() and (pair <= 1).all()):
+        raise SearchInputError("pair table: every pair value (12 per position) must be present, finite and in [0, 1]")
+    try:
+        offs = tuple(table.pam_offsets)
+    except TypeError:
+        raise SearchInputError("pair table: pam_offsets must be a sequence of integers") from None
+    if len(offs) > MAX_PAM_OFFSETS:
+        raise SearchInputError("pair table: at most %d PAM offsets, not %d" % (MAX_PAM_OFFSETS, len(offs)))
+    pam_at = hi if pam3 else 0
+    for k, o in enumerate(offs):
+        if not isinstance(o, (int, np.integer)) or not 0 <= int(o) < P:
+            raise SearchInputError("pair table: PAM offset %r outside 0..%d" % (o, P - 1))
+        if k and int(o) <= int(offs[k - 1]):
+            raise SearchInputError("pair table: PAM offsets must be strictly ascending")
+        if pattern[pam_at + int(o)] == "N":
+            raise SearchInputError("pair table: PAM offset %d is on an N of pattern %s: a site may hold no base there" % (o, pattern))
+    offs = tuple(int(o) for o in offs)
+    if table.pam is None:
+        if offs:
+            raise SearchInputError("pair table: PAM offsets without PAM values")
+        pam = np.ones(1, dtype=np.float64)
+    else:
+        try:
+            pam = np.array(table.pam, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError):
+            raise SearchInputError("pair table: the PAM values must be numbers") from None
+        if not offs or pam.size != 4 ** len(offs):
+            raise SearchInputError("pair table: %d PAM values for %d offsets (4^k of them; none without offsets)" % (pam.size, len(offs)))
+        if not (np.isfinite(pam).all() and (pam >= 0).all() and (pam <= 1).all()):
+            raise SearchInputError("pair table: PAM values must be finite and in [0, 1]")
+    return PairScheme(pair, offs, pam, tuple(pam_at + o for o in offs), lo, hi, pam3)
+
+
 def hsu_shape(G):
     """shape[n][d] of the Hsu et al. 2013 score for a guide region of G: 1 for n = 0, 1 / n^2 for n = 1, and for n >= 2
     1 / (((G - 1 - d / (n - 1)) / (G - 1)) * 4 + 1) / n^2, d / (n - 1) being the mean distance between consecutive
@@ -397,9 +493,11 @@ def hsu_shape(G):
 
 def make_scheme(pattern, pam_len, score):
     """The Scheme of score = "hsu2013" (G = 20 only) or a sequence of G weights W in [0, 1], PAM-distal first
-    (factor = 1 - W, the Hsu shape with 19 -> G - 1)."""
+    (factor = 1 - W, the Hsu shape with 19 -> G - 1); the PairScheme of a PairTable."""
     if pam_len is None:
         raise SearchInputError("a specificity score needs the PAM's length (--pam-length)")
+    if isinstance(score, PairTable):
+        return _make_pair_scheme(pattern, pam_len, score)
     lo, hi, pam3 = guide_region(pattern, pam_len)
     G = hi - lo
     if isinstance(score, str):
@@ -441,6 +539,101 @@ def parse_weights(text):
         return [float(v) for v in fields]
     except ValueError as e:
         raise SearchInputError("weights file: %s" % e) from None
+
+
+def parse_pair_table(text):
+    """A pair-table file -> PairTable.  One statement per line, `#` starts a comment:
+
+        pam-offsets 1 2        optional, once; absent = no PAM factor
+        pam AG 0.25            one line per combination of letters at those offsets; unlisted combinations are 0
+        pair 19 A C 0.5        g (0-based, PAM-distal first), query letter, site letter, value
+
+    G is the largest g + 1; all 12 G pair values with different letters must be present (a line with equal letters is
+    read and ignored, like the diagonal)."""
+    if isinstance(text, bytes):
+        text = text.decode()
+    offs, pams, pairs = None, {}, {}
+    for no, line in enumerate(text.splitlines(), 1):
+        f = line.split("#", 1)[0].split()
+        if not f:
+            continue
+        try:
+            if f[0] == "pam-offsets" and offs is None:
+                offs = tuple(int(v) for v in f[1:])
+            elif f[0] == "pam" and len(f) == 3 and set(f[1].upper()) <= set("ACGT") and f[1].upper() not in pams:
+                pams[f[1].upper()] = float(f[2])
+            elif f[0] == "pair" and len(f) == 5 and f[2].upper() in "ACGT" and f[3].upper() in "ACGT" and len(f[2]) == len(f[3]) == 1:
+                key = (int(f[1]), "ACGT".index(f[2].upper()), "ACGT".index(f[3].upper()))
+                if key in pairs or not 0 <= key[0] < MAX_T:
+                    raise ValueError("a repeated entry or g outside 0..%d" % (MAX_T - 1))
+                pairs[key] = float(f[4])
+            else:
+                raise ValueError("not a pam-offsets, pam or pair statement (or a repeated one)")
+        except ValueError as e:
+            raise SearchInputError("pair table, line %d: %s" % (no, e)) from None
+    if not pairs:
+        raise SearchInputError("pair table: no pair entries")
+    G = max(k[0] for k in pairs) + 1
+    pair = np.full((G, 4, 4), np.nan)
+    for (g, a, b), v in pairs.items():
+        pair[g, a, b] = v
+    missing = [(g, a, b) for g in range(G) for a in range(4) for b in range(4) if a != b and np.isnan(pair[g, a, b])]
+    if missing:
+        g, a, b = missing[0]
+        raise SearchInputError("pair table: %d of the %d pair entries are missing or not numbers, the first: pair %d %s %s" % (
+            len(missing), 12 * G, g, "ACGT"[a], "ACGT"[b]))
+    if pams and not offs:
+        raise SearchInputError("pair table: pam lines without pam-offsets")
+    pam = None
+    if offs:
+        pam = np.zeros(4 ** len(offs) if len(offs) <= MAX_PAM_OFFSETS else 1)
+        for letters, v in pams.items():
+            if len(letters) != len(offs):
+                raise SearchInputError("pair table: pam %s has %d letters for %d offsets" % (letters, len(letters), len(offs)))
+            if pam.size > 1:
+                pam[sum("ACGT".index(c) << (2 * (len(offs) - 1 - k)) for k, c in enumerate(letters))] = v
+    return PairTable(pair, offs or (), pam)
+
+
+def pair_values(qcodes, scodes, pam_index, scheme):
+    """v under a PairScheme, uint64: the definition in numpy.  qcodes, scodes: (m, G) letters of the query and of the
+    oriented site at g = 0 .. G - 1 as codes 0..3 = A, C, G, T; 4 = N in the query (not compared), a non-base in the
+    site.  pam_index: (m,) the index of each site's PAM letters into scheme.pam (0 without offsets).  The product runs
+    over g ascending, one float64 multiply per step, then the PAM value, like the device's."""
+    q = np.asarray(qcodes, dtype=np.int64).reshape(-1, scheme.pair.shape[0])
+    s = np.asarray(scodes, dtype=np.int64).reshape(q.shape)
+    h = np.ones(q.shape[0], dtype=np.float64)
+    n = np.zeros(q.shape[0], dtype=np.int64)
+    dead = np.zeros(q.shape[0], dtype=bool)
+    for g in range(q.shape[1]):
+        mis = (q[:, g] != 4) & (s[:, g] != q[:, g])
+        h = np.where(mis, h * scheme.pair[g][np.minimum(q[:, g], 3), np.minimum(s[:, g], 3)], h)
+        dead |= mis & (s[:, g] == 4)
+        n += mis
+    h = h * scheme.pam[np.asarray(pam_index, dtype=np.int64).reshape(-1)]
+    v = np.rint(h * float(1 << SCORE_SHIFT)).astype(np.uint64)
+    return np.where((n > 0) & ~dead, v, np.uint64(0))
+
+
+def site_codes(sites, queries, contigs, scheme):
+    """(qcodes (m, G), scodes (m, G), pam_index (m,)) of kind-none sites, from the sites' letters: what pair_values takes."""
+    gpos = scheme.g_positions()
+    T = len(queries[0]) if queries else 0
+    qall = [np.array([_QCODE[ord(ch)] for ch in q], dtype=np.uint8) for q in queries]
+    qc = np.zeros((len(sites), gpos.size), dtype=np.uint8)
+    sc = np.zeros((len(sites), gpos.size), dtype=np.uint8)
+    at = np.zeros(len(sites), dtype=np.int64)
+    for k, r in enumerate(sites):
+        pos, contig = int(r["position"]), contigs[int(r["contig"])]
+        codes = _CODE[np.frombuffer(bytes(contig[pos:pos + T]), dtype=np.uint8)]
+        if r["strand"] in (b"-", "-"):
+            codes = np.where(codes == 4, 4, 3 - codes)[::-1]
+        qc[k], sc[k] = qall[int(r["query"])][gpos], codes[gpos]
+        for p in scheme.pam_positions:
+            if codes[p] == 4:
+                raise ValueError("a site without a base at PAM position %d" % p)
+            at[k] = at[k] << 2 | int(codes[p])
+    return qc, sc, at
 
 
 def specificity(hit_sum):
@@ -498,7 +691,9 @@ def hit_values(sites, queries, contigs, scheme):
     v = np.zeros(sites.size, dtype=np.uint64)
     plain = np.ones(sites.size, dtype=bool) if "kind" not in (sites.dtype.names or ()) else sites["kind"] == 0
     idx = np.nonzero(plain)[0]
-    if idx.size:
+    if idx.size and isinstance(scheme, PairScheme):
+        v[idx] = pair_values(*site_codes(sites[idx], queries, contigs, scheme), scheme)
+    elif idx.size:
         v[idx] = mask_values(site_masks(sites[idx], queries, contigs, scheme), scheme)
     return v
 
@@ -657,6 +852,10 @@ class ArenaSelfSearch:
         self._check(nat.lib().crp_search_self_set_limits(self._h, int(pairs_per_launch)), "crp_search_self_set_limits")
 
     def set_scheme(self, scheme):
+        if isinstance(scheme, PairScheme):
+            pair, G, offs, k, pam = scheme.native_args()
+            self._check(nat.lib().crp_search_self_set_pair_scheme(self._h, pair, G, offs, k, pam), "crp_search_self_set_pair_scheme")
+            return
         f = np.ascontiguousarray(scheme.factor, dtype=np.float64)
         sh = np.ascontiguousarray(scheme.shape, dtype=np.float64).reshape(-1)
         self._check(nat.lib().crp_search_self_set_scheme(self._h, f.ctypes.data_as(nat.f64p), f.size, sh.ctypes.data_as(nat.f64p)),
@@ -934,6 +1133,9 @@ def main(argv=None):
     sc.add_argument("--weights", metavar="FILE",
                     help="the same with the weights of FILE in place of hsu2013's: one number in [0, 1] per guide-region "
                          "position, PAM-distal first")
+    sc.add_argument("--score-table", metavar="FILE",
+                    help="the same with a hit score of the CFD form: the pair table of FILE (pair values per position, query "
+                         "letter and site letter; values per PAM letters; see parse_pair_table, tools/cfd_to_table.py)")
     ap.add_argument("--no-sites", action="store_true", help="keep and write no site list: only --counts (with the scores, if asked for)")
     ap.add_argument("--device", type=int, default=0, help="HIP device")
     args = ap.parse_args(argv)
@@ -957,6 +1159,9 @@ def main(argv=None):
         if args.weights:
             with open(args.weights, "rb") as f:
                 score = parse_weights(f.read())
+        if args.score_table:
+            with open(args.score_table, "rb") as f:
+                score = parse_pair_table(f.read())
         scheme = check_score(pattern, args.pam_length, score, queries)
         if args.no_sites and (args.output or not args.counts):
             raise SearchInputError("--no-sites writes only --counts: give --counts and no -o")
@@ -1002,6 +1207,9 @@ def _main_self(ap, args):
         if args.weights:
             with open(args.weights, "rb") as f:
                 score = parse_weights(f.read())
+        if args.score_table:
+            with open(args.score_table, "rb") as f:
+                score = parse_pair_table(f.read())
         pattern, gp, max_mm, pam_len, _ = check_self(args.pattern, args.mismatches, args.pam_length, args.guide_pattern, score)
         contig_names, contigs = read_fasta(args.fasta)
     except (SearchInputError, OSError, UnicodeDecodeError) as e:

@@ -656,6 +656,21 @@ int crp_search_set_scheme(crp_search *search, const double *factor, int n_factor
  * mismatches there would have no g). */
 int crp_search_run_scored(crp_search *search, const char *queries, uint64_t n_queries, int max_mm, uint64_t site_cap,
                           uint32_t *counts, uint64_t *n_sites, uint64_t *hit_sum);
+/* Pair table (Pair tables): the other form of a scheme, in which a mismatch costs by which query
+ * letter faces which site letter, and the site's PAM letters weigh the whole hit (the CFD form).  pair[n_factor][4][4]
+ * is indexed by g (as above), the query's letter and the oriented site's letter, both over A, C, G, T in that order; the
+ * diagonal is ignored.  pam_offsets[n_pam_offsets] (0 .. CRP_SEARCH_PAIR_MAX_PAM of them, strictly ascending) are offsets
+ * inside the PAM, 0 its 5'-most letter, each on a pattern letter other than N; pam[4^n_pam_offsets] is indexed by the
+ * site's letters there, first offset most significant (no offsets: the PAM factor is 1, pam may be NULL).  For a hit
+ * with n >= 1 mismatches at g1 < .. < gn,
+ *   h = 1; h = h * pair[g][query letter][site letter] for g = g1 .. gn; h = h * pam[..]   (float64, one multiply a step)
+ *   v = (uint64) rint(h * 2^30), and v = 0 when a mismatching position of the site holds no base.
+ * Setting a pair table clears the handle's scheme and the other way round; crp_search_run_scored serves whichever is
+ * set.  A NULL pair clears both.  CRP_ERR_INVALID: pam_side out of range, a guide region of n_factor positions on that
+ * side that is not all N in the handle's pattern, a value outside [0, 1] or not finite, offsets outside the rule. */
+#define CRP_SEARCH_PAIR_MAX_PAM 3
+int crp_search_set_pair_scheme(crp_search *search, const double *pair, int n_factor, int pam_side, const int *pam_offsets,
+                               int n_pam_offsets, const double *pam);
 /* Measurement, accumulated since create: out[0] ms of candidate extraction (count and emit kernels),
  * out[1] ms of compare kernels, out[2] extraction launches, out[3] compare launches, out[4] chunks of the
  * current plan, out[5] device bytes of the candidate buffers.  n: how many of these to write (<= 6). */
@@ -687,6 +702,10 @@ int crp_search_self_set_limits(crp_search_self *self, uint64_t pairs_per_launch)
 /* crp_search_set_scheme for the handle's rows: n_factor must be the guide region's length; the PAM's side is the
  * handle's.  A NULL factor clears the scheme. */
 int crp_search_self_set_scheme(crp_search_self *self, const double *factor, int n_factor, const double *shape);
+/* crp_search_set_pair_scheme for the handle's rows (n_factor: the guide region's length; the PAM's side is the
+ * handle's).  The candidates' PAM letters are read from the candidates' handle at compare time. */
+int crp_search_self_set_pair_scheme(crp_search_self *self, const double *pair, int n_factor, const int *pam_offsets,
+                                    int n_pam_offsets, const double *pam);
 int crp_search_self_sizes(const crp_search_self *self, uint64_t *n_plus, uint64_t *n_minus, uint64_t *n_guides);
 /* Orders the handle's candidates by segment 0 .. max_mm of the guide region (replaces the ordering it held). */
 int crp_search_self_order(crp_search_self *self, int segment);

@@ -23,6 +23,12 @@ the ISA of search_bulge_compare_kernel: its no-hit loop body is 72 VALU instruct
 resident candidates, three rounds each, compare times from crp_search_stats; plus the wall time of the plain run (with
 its fetch and sort of the site list) against the score-only run (site_cap 0: no site list at all).
 
+--score --score-table FILE adds the pair-table run (search_pair_compare_kernel; DESIGN.md section 15, Pair tables) to the
+same interleaving: FILE is a pair-table file for a 20 + 3 pattern (search.parse_pair_table), set on the same handles in
+turn with hsu2013, so all runs use the same resident candidates; pair_over_scored_compare is its compare time over the
+hsu2013 scored kernel's.  --self --score-table FILE runs every M under hsu2013 and under the table, and reports the
+compare time and the longest launch of both (the hit path is not rare there: a low-complexity bucket is all hits).
+
 --self times the self search (Self search): ...NGG, hsu2013, M = 3 and M = 4, a warm-up and three
 rounds each in one process, times from the handles' stats (HIP events): extraction, the M + 1 orderings, the compare
 (launches, longest launch), pairs compared against Q x C and the compare's fraction of its issue floor.
@@ -136,6 +142,10 @@ def score_main(args, contigs, guides, out):
     pattern, P, rounds = PATTERNS["NGG"], 3, 3
     queries = [srch.check_query(pattern, q, P) for q in guides[:BULGE_Q]]
     scheme = srch.make_scheme(pattern, P, "hsu2013")
+    pair_scheme = None
+    if args.score_table:
+        with open(args.score_table, "rb") as f:
+            pair_scheme = srch.make_scheme(pattern, P, srch.parse_pair_table(f.read()))
     out.update(queries=len(queries), pattern="NGG", scheme="hsu2013", rounds=rounds)
     with Engine(args.device) as eng:
         out["device"] = eng.device_info()["name"].strip()
@@ -170,18 +180,31 @@ def score_main(args, contigs, guides, out):
         def score_only(s):
             return s.run_scored(queries, MAX_MM, 0)
 
-        timed(plain)  # warm-up: extraction, the site buffer's growth, both kernels' code objects
+        def pair(s):  # (the handle holds one scheme at a time: the upload is outside the compare's events)
+            s.set_scheme(pair_scheme)
+            try:
+                return s.run_scored(queries, MAX_MM, 1 << 40)
+            finally:
+                s.set_scheme(scheme)
+
+        runs = [("plain", plain), ("scored", scored), ("score_only", score_only)] + ([("pair", pair)] if pair_scheme else [])
+        timed(plain)  # warm-up: extraction, the site buffer's growth, the kernels' code objects
         timed(scored)
-        rows = {"plain": [], "scored": [], "score_only": []}
-        ref_counts = ref_sums = None
+        if pair_scheme:
+            timed(pair)
+        rows = {name: [] for name, _ in runs}
+        ref_counts = ref_sums = pair_sums = None
         for _ in range(rounds):
-            for name, run in (("plain", plain), ("scored", scored), ("score_only", score_only)):
+            for name, run in runs:
                 ms, wall, n_sites, counts, sums = timed(run)
                 rows[name].append((ms, wall))
                 if ref_counts is None:
                     ref_counts = counts
                 assert (counts == ref_counts).all(), name
-                if sums is not None:
+                if name == "pair":
+                    pair_sums = sums if pair_sums is None else pair_sums
+                    assert (sums == pair_sums).all(), name
+                elif sums is not None:
                     ref_sums = sums if ref_sums is None else ref_sums
                     assert (sums == ref_sums).all(), name
                 out["sites"] = int(n_sites)
@@ -191,6 +214,10 @@ def score_main(args, contigs, guides, out):
         out["scored_over_plain_compare"] = round(med("scored", 0) / med("plain", 0), 4)
         out["score_only_over_plain_compare"] = round(med("score_only", 0) / med("plain", 0), 4)
         out["score_only_over_plain_wall"] = round(med("score_only", 1) / med("plain", 1), 4)
+        if pair_scheme:
+            out["pair_over_scored_compare"] = round(med("pair", 0) / med("scored", 0), 4)
+            out["pair_over_plain_compare"] = round(med("pair", 0) / med("plain", 0), 4)
+            out["pair_hit_sum_total"] = int(pair_sums.sum())
         out["hit_sum_total"] = int(ref_sums.sum())
         out["guides_with_hits"] = int((ref_sums > 0).sum())
         out["median_specificity"] = round(float(np.median(srch.specificity(ref_sums))), 6)
@@ -208,14 +235,24 @@ def self_main(args, contigs, out):
     with Engine(args.device) as eng:
         out["device"] = eng.device_info()["name"].strip()
         g = eng.genome(contigs)
+        table = None
+        if args.score_table:
+            with open(args.score_table, "rb") as f:
+                table = srch.parse_pair_table(f.read())
+            srch.make_scheme(pattern, P, table)
         for M in SELF_MMS:
-            rows, res = [], None
+            rows, res, pair_rows = [], None, []
             for r in range(rounds + 1):  # (the first is the warm-up)
                 t = time.perf_counter()
                 res = srch.search_self(g, pattern, M, P, score="hsu2013")
                 wall = time.perf_counter() - t
                 if r:
                     rows.append(dict(res.stats, wall_s=wall))
+                if table is not None:  # the pair table on the same genome and M, interleaved
+                    pres = srch.search_self(g, pattern, M, P, score=table)
+                    assert (pres.counts == res.counts).all(), "the counts do not depend on the scheme"
+                    if r:
+                        pair_rows.append(pres.stats)
             n, cand = len(res.sites), sum(res.candidates)
             med = lambda k: float(np.median([x[k] for x in rows]))
             floor_ms = res.pairs[0] * SELF_VALU_PER_PAIR / ISSUE_RATE * 1e3
@@ -228,6 +265,11 @@ def self_main(args, contigs, out):
                        wall_s=[round(x["wall_s"], 2) for x in rows], issue_floor_ms=round(floor_ms, 3),
                        fraction_of_issue_floor=round(floor_ms / med("compare_ms"), 3),
                        median_specificity=round(float(np.median(res.specificity)), 6))
+            if pair_rows:
+                pm = float(np.median([x["compare_ms"] for x in pair_rows]))
+                row.update(pair_compare_ms=[round(x["compare_ms"], 3) for x in pair_rows],
+                           pair_longest_launch_ms=[round(x["longest_launch_ms"], 3) for x in pair_rows],
+                           pair_over_scored_compare=round(pm / med("compare_ms"), 4))
             # the existing path: a sample of the guide sites' queries through the given-guides compare, scaled to all of them
             pick = np.sort(rng.choice(n, min(n, SELF_BRUTE_Q), replace=False))
             searches = [srch.ArenaSearch(a, pattern) for a in g.arenas]
@@ -270,7 +312,10 @@ def main():
     ap.add_argument("--bulge", metavar="D,R", help="time the search with DNA bulges 1..D and RNA bulges 1..R instead")
     ap.add_argument("--score", action="store_true", help="time the scored compare against the plain one instead")
     ap.add_argument("--self", dest="self_search", action="store_true", help="time the self search (every guide site a query) instead")
+    ap.add_argument("--score-table", metavar="FILE", help="with --score or --self: also time the pair table of FILE (20 + NGG)")
     args = ap.parse_args()
+    if args.score_table and not (args.score or args.self_search):
+        ap.error("--score-table goes with --score or --self")
     t0 = time.perf_counter()
     wl = bw.switchgrass_like(0, args.scale)
     contigs = [wl.bases(s) for s in wl.specs]
