@@ -64,21 +64,12 @@ uint32_t complement_set(uint32_t s) { return ((s & 1) << 1) | ((s & 2) >> 1) | (
 // placement (at_bits() bits) between the strand and the mismatches.
 struct Kind {
     int dna = 0, rna = 0;
-    bool scored = false;  // (plain kind only) the scoring compare: also sums the hits' values
-    bool by_pair = false;  // (scored only) under the handle's pair table, not its weighting scheme
+    enum Value { NONE, SCHEME, PAIR } value = NONE;  // (plain kind only) what the compare sums per query, and under which table
     bool bulge() const { return dna || rna; }
+    bool scored() const { return value != NONE; }
     int at_bits() const { return bulge() ? 5 : 0; }
     uint64_t pairs_per_launch() const { return bulge() ? kBulgePairsPerLaunch : kPairsPerLaunch; }
     uint64_t max_queries() const { return bulge() ? kMaxBulgeQueries : kMaxQueries; }
-    hipError_t compare(hipStream_t st, const crp::SearchCands &c, uint32_t n, const uint4 *queries, uint32_t q0, uint32_t nq, int max_mm,
-                       uint32_t *counts, uint2 *sites, uint64_t site_cap, unsigned long long *site_ctr, const crp::SearchScore &score,
-                       const crp::SearchPair &pair) const
-    {
-        if (scored && by_pair) return crp::launch_search_pair_compare(st, c, n, queries, q0, nq, max_mm, counts, sites, site_cap, site_ctr, pair);
-        if (scored) return crp::launch_search_score_compare(st, c, n, queries, q0, nq, max_mm, counts, sites, site_cap, site_ctr, score);
-        if (bulge()) return crp::launch_search_bulge_compare(st, c, n, queries, q0, nq, max_mm, dna, rna, counts, sites, site_cap, site_ctr);
-        return crp::launch_search_compare(st, c, n, queries, q0, nq, max_mm, counts, sites, site_cap, site_ctr);
-    }
 };
 
 // One site: the kernels' site word is {query << (4 + at_bits) | placement << 4 | mismatches, strand << 31 | pos}; the
@@ -104,6 +95,76 @@ Site unpack_key(uint64_t key, Kind k)
 
 namespace crp {
 
+namespace {
+
+bool in_unit(double v) { return std::isfinite(v) && v >= 0.0 && v <= 1.0; }
+
+// a laid-out table to the device, allocated on first use
+int upload(crp_ctx *ctx, double **d, const double *tab, size_t bytes)
+{
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    if (!*d) CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(d), bytes));
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (no run of this handle's stream is in flight, but say so)
+    CRP_HIP(ctx, hipMemcpy(*d, tab, bytes, hipMemcpyHostToDevice));
+    return CRP_OK;
+}
+
+uint32_t factor_region(int T, int n_factor, bool pam3)
+{
+    const uint32_t low = n_factor == 32 ? ~0u : (1u << n_factor) - 1u;
+    return pam3 ? low : low << (T - n_factor);
+}
+
+}  // namespace
+
+bool search_scheme_layout(int T, const double *factor, int n_factor, bool pam3, const double *shape, double *tab)
+{
+    if (!shape || n_factor < 1 || n_factor > T) return false;
+    if (!std::all_of(factor, factor + n_factor, in_unit) || !std::all_of(shape, shape + CRP_SEARCH_SHAPE_DOUBLES, in_unit)) return false;
+    std::fill(tab, tab + SEARCH_SCORE_WALK, 1.0);
+    for (int g = 0; g < n_factor; ++g) tab[pam3 ? g : g + 32 - T] = factor[g];
+    std::copy(shape, shape + CRP_SEARCH_SHAPE_DOUBLES, tab + SEARCH_SCORE_WALK);
+    return true;
+}
+
+int SearchValueState::set_scheme(crp_ctx *ctx, int T, const double *factor, int n_factor, bool pam3, const double *shape)
+{
+    double tab[SEARCH_SCORE_TAB];
+    if (!search_scheme_layout(T, factor, n_factor, pam3, shape, tab)) return CRP_ERR_INVALID;
+    const int rc = upload(ctx, &d_scheme, tab, sizeof(tab));
+    if (rc != CRP_OK) return rc;
+    region = factor_region(T, n_factor, pam3);
+    rev = pam3 ? 0 : 1;
+    have_scheme = true;
+    have_pair = false;
+    return CRP_OK;
+}
+
+int SearchValueState::set_pair(crp_ctx *ctx, const SearchSets &sets, const double *pair, int n_factor, bool pam3, const int *pam_offsets,
+                               int n_pam_offsets, const double *pam)
+{
+    double tab[SEARCH_PAIR_TAB];
+    uint32_t pos = 0;
+    if (!search_pair_layout(sets, pair, n_factor, pam3, pam_offsets, n_pam_offsets, pam, tab, &pos)) return CRP_ERR_INVALID;
+    const int rc = upload(ctx, &d_pair, tab, sizeof(tab));
+    if (rc != CRP_OK) return rc;
+    region = factor_region(sets.T, n_factor, pam3);
+    rev = pam3 ? 0 : 1;
+    n_pam = n_pam_offsets;
+    pam_pos = pos;
+    have_pair = true;
+    have_scheme = false;
+    return CRP_OK;
+}
+
+void SearchValueState::free()
+{
+    (void)hipFree(d_scheme);
+    (void)hipFree(d_pair);
+    d_scheme = d_pair = nullptr;
+    clear();
+}
+
 bool search_pair_layout(const SearchSets &sets, const double *pair, int n_factor, bool pam3, const int *pam_offsets, int n_pam_offsets,
                         const double *pam, double *tab, uint32_t *pam_pos)
 {
@@ -114,11 +175,10 @@ bool search_pair_layout(const SearchSets &sets, const double *pair, int n_factor
     const auto set_at = [&](int o) { return (uint32_t)(sets.plus[o >> 4] >> ((o & 15) * 4)) & 15u; };
     for (int p = glo; p < glo + n_factor; ++p)
         if (set_at(p) != 15u) return false;
-    const auto in_unit = [](double v) { return std::isfinite(v) && v >= 0.0 && v <= 1.0; };
     static const int dev[4] = {0, 2, 3, 1};  // A, C, G, T in the planes' coding (A=00 T=01 C=10 G=11)
     std::fill(tab, tab + SEARCH_PAIR_WALK * 16, 1.0);
     std::fill(tab + SEARCH_PAIR_WALK * 16, tab + SEARCH_PAIR_TAB, 0.0);
-    // the walk order of crp_search_set_scheme: bit g of the mask (PAM on the 3' side), bit g + 32 - T of the reversed mask
+    // the walk order of search_scheme_layout: bit g of the mask (PAM on the 3' side), bit g + 32 - T of the reversed mask
     for (int g = 0; g < n_factor; ++g)
         for (int a = 0; a < 4; ++a)
             for (int b = 0; b < 4; ++b) {
@@ -177,16 +237,7 @@ struct crp_search {
     uint2 *d_sites = nullptr;
     uint64_t sites_cap = 0;
     unsigned long long *d_ctr = nullptr;
-    // scheme (crp_search_set_scheme): the walk and shape tables on the device, the positions that have a factor
-    double *d_scheme = nullptr;
-    bool have_scheme = false;
-    int scheme_rev = 0;
-    uint32_t scheme_region = 0;
-    // pair table (crp_search_set_pair_scheme): setting either clears the other
-    double *d_pair = nullptr;
-    bool have_pair = false;
-    int pair_n_pam = 0;
-    uint32_t pair_pam_pos = 0;
+    crp::SearchValueState value;  // crp_search_set_scheme / crp_search_set_pair_scheme
     unsigned long long *d_hit_sum = nullptr;
     uint64_t hit_sum_cap = 0;
     std::vector<uint64_t> keys;  // sites of the last successful run, as pack_key of its kind
@@ -253,6 +304,23 @@ int plan(crp_search *s)
     return CRP_OK;
 }
 
+// the compare kernel of `kind` over the cached chunk's n candidates and queries [q0, q0 + nq)
+hipError_t compare(crp_search *s, Kind kind, uint32_t n, uint32_t q0, uint32_t nq, int max_mm, uint64_t site_cap)
+{
+    const hipStream_t st = s->ctx->stream;
+    const crp::SearchCands c = s->cands();
+    if (kind.value == Kind::PAIR)
+        return crp::launch_search_pair_compare(st, c, n, s->d_queries, q0, nq, max_mm, s->d_counts, s->d_sites, site_cap, s->d_ctr,
+                                               s->value.pair(s->d_hit_sum));
+    if (kind.value == Kind::SCHEME)
+        return crp::launch_search_score_compare(st, c, n, s->d_queries, q0, nq, max_mm, s->d_counts, s->d_sites, site_cap, s->d_ctr,
+                                                s->value.score(s->d_hit_sum));
+    if (kind.bulge())
+        return crp::launch_search_bulge_compare(st, c, n, s->d_queries, q0, nq, max_mm, kind.dna, kind.rna, s->d_counts, s->d_sites, site_cap,
+                                                s->d_ctr);
+    return crp::launch_search_compare(st, c, n, s->d_queries, q0, nq, max_mm, s->d_counts, s->d_sites, site_cap, s->d_ctr);
+}
+
 // one pass over every chunk with the compare kernel of `kind`: counts and sites accumulate on the device
 int run_pass(crp_search *s, uint32_t n_queries, int max_mm, uint64_t dev_sites, Kind kind)
 {
@@ -261,9 +329,7 @@ int run_pass(crp_search *s, uint32_t n_queries, int max_mm, uint64_t dev_sites, 
     const crp::Planes pl{{a->d_plane[0], a->d_plane[1], a->d_plane[2], a->d_plane[3]}};
     CRP_HIP(ctx, hipMemsetAsync(s->d_counts, 0, (size_t)n_queries * (max_mm + 1) * sizeof(uint32_t), ctx->stream));
     CRP_HIP(ctx, hipMemsetAsync(s->d_ctr, 0, sizeof(unsigned long long), ctx->stream));
-    if (kind.scored) CRP_HIP(ctx, hipMemsetAsync(s->d_hit_sum, 0, (size_t)n_queries * sizeof(unsigned long long), ctx->stream));
-    const crp::SearchScore score{s->d_scheme, s->scheme_rev, s->d_hit_sum};
-    const crp::SearchPair pair{s->d_pair, s->scheme_rev, s->pair_n_pam, s->pair_pam_pos, s->d_hit_sum};
+    if (kind.scored()) CRP_HIP(ctx, hipMemsetAsync(s->d_hit_sum, 0, (size_t)n_queries * sizeof(unsigned long long), ctx->stream));
     const int n_chunks = (int)s->chunk_n.size();
     for (int c = 0; c < n_chunks; ++c) {
         const uint64_t n = s->chunk_n[c];
@@ -281,8 +347,7 @@ int run_pass(crp_search *s, uint32_t n_queries, int max_mm, uint64_t dev_sites, 
         uint64_t launches = 0;
         for (uint32_t q0 = 0; q0 < n_queries; q0 += batch) {
             const uint32_t nq = std::min(batch, n_queries - q0);
-            CRP_HIP(ctx, kind.compare(ctx->stream, s->cands(), (uint32_t)n, s->d_queries, q0, nq, max_mm, s->d_counts, s->d_sites, dev_sites,
-                                      s->d_ctr, score, pair));
+            CRP_HIP(ctx, compare(s, kind, (uint32_t)n, q0, nq, max_mm, dev_sites));
             ++launches;
         }
         CRP_HIP(ctx, hipEventRecord(s->ev[2], ctx->stream));
@@ -368,8 +433,7 @@ int crp_search_destroy(crp_search *s)
     (void)hipFree(s->d_counts);
     (void)hipFree(s->d_sites);
     (void)hipFree(s->d_ctr);
-    (void)hipFree(s->d_scheme);
-    (void)hipFree(s->d_pair);
+    s->value.free();
     (void)hipFree(s->d_hit_sum);
     for (hipEvent_t e : s->ev)
         if (e) (void)hipEventDestroy(e);
@@ -397,34 +461,11 @@ int crp_search_set_scheme(crp_search *s, const double *factor, int n_factor, int
 {
     if (!s) return CRP_ERR_INVALID;
     if (!factor) {
-        s->have_scheme = s->have_pair = false;
+        s->value.clear();
         return CRP_OK;
     }
-    const int T = s->sets.T;
-    if (!shape || n_factor < 1 || n_factor > T || (pam_side != CRP_SEARCH_PAM_3PRIME && pam_side != CRP_SEARCH_PAM_5PRIME))
-        return CRP_ERR_INVALID;
-    const auto in_unit = [](double v) { return std::isfinite(v) && v >= 0.0 && v <= 1.0; };
-    if (!std::all_of(factor, factor + n_factor, in_unit) || !std::all_of(shape, shape + CRP_SEARCH_SHAPE_DOUBLES, in_unit))
-        return CRP_ERR_INVALID;
-    // The walk table.  PAM on the 3' side: the guide region is positions 0 .. G - 1 and g is the position, so the mask is
-    // walked as it is.  PAM on the 5' side: the region is positions T - G .. T - 1 and g = T - 1 - position; the kernel
-    // walks the bit-reversed mask, where position p is bit 31 - p, so g = b - (32 - T) ascends with the bit again.
-    double tab[crp::SEARCH_SCORE_TAB];
-    std::fill(tab, tab + crp::SEARCH_SCORE_WALK, 1.0);
-    const int rev = pam_side == CRP_SEARCH_PAM_5PRIME;
-    for (int g = 0; g < n_factor; ++g) tab[rev ? g + 32 - T : g] = factor[g];
-    std::copy(shape, shape + CRP_SEARCH_SHAPE_DOUBLES, tab + crp::SEARCH_SCORE_WALK);
-    crp_ctx *ctx = s->ctx;
-    CRP_HIP(ctx, hipSetDevice(ctx->device));
-    if (!s->d_scheme) CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->d_scheme), sizeof(tab)));
-    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (no run of this handle's stream is in flight, but say so)
-    CRP_HIP(ctx, hipMemcpy(s->d_scheme, tab, sizeof(tab), hipMemcpyHostToDevice));
-    const uint32_t low = n_factor == 32 ? ~0u : (1u << n_factor) - 1u;
-    s->scheme_region = rev ? low << (T - n_factor) : low;
-    s->scheme_rev = rev;
-    s->have_scheme = true;
-    s->have_pair = false;
-    return CRP_OK;
+    if (pam_side != CRP_SEARCH_PAM_3PRIME && pam_side != CRP_SEARCH_PAM_5PRIME) return CRP_ERR_INVALID;
+    return s->value.set_scheme(s->ctx, s->sets.T, factor, n_factor, pam_side == CRP_SEARCH_PAM_3PRIME, shape);
 }
 
 int crp_search_set_pair_scheme(crp_search *s, const double *pair, int n_factor, int pam_side, const int *pam_offsets, int n_pam_offsets,
@@ -432,28 +473,11 @@ int crp_search_set_pair_scheme(crp_search *s, const double *pair, int n_factor, 
 {
     if (!s) return CRP_ERR_INVALID;
     if (!pair) {
-        s->have_scheme = s->have_pair = false;
+        s->value.clear();
         return CRP_OK;
     }
     if (pam_side != CRP_SEARCH_PAM_3PRIME && pam_side != CRP_SEARCH_PAM_5PRIME) return CRP_ERR_INVALID;
-    const int T = s->sets.T;
-    const int rev = pam_side == CRP_SEARCH_PAM_5PRIME;
-    double tab[crp::SEARCH_PAIR_TAB];
-    uint32_t pam_pos = 0;
-    if (!crp::search_pair_layout(s->sets, pair, n_factor, !rev, pam_offsets, n_pam_offsets, pam, tab, &pam_pos)) return CRP_ERR_INVALID;
-    crp_ctx *ctx = s->ctx;
-    CRP_HIP(ctx, hipSetDevice(ctx->device));
-    if (!s->d_pair) CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->d_pair), sizeof(tab)));
-    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (no run of this handle's stream is in flight, but say so)
-    CRP_HIP(ctx, hipMemcpy(s->d_pair, tab, sizeof(tab), hipMemcpyHostToDevice));
-    const uint32_t low = n_factor == 32 ? ~0u : (1u << n_factor) - 1u;
-    s->scheme_region = rev ? low << (T - n_factor) : low;
-    s->scheme_rev = rev;
-    s->pair_n_pam = n_pam_offsets;
-    s->pair_pam_pos = pam_pos;
-    s->have_pair = true;
-    s->have_scheme = false;
-    return CRP_OK;
+    return s->value.set_pair(s->ctx, s->sets, pair, n_factor, pam_side == CRP_SEARCH_PAM_3PRIME, pam_offsets, n_pam_offsets, pam);
 }
 
 int crp_search_candidates(const crp_search *s, uint64_t *n_plus, uint64_t *n_minus)
@@ -513,7 +537,7 @@ int run_encoded(crp_search *s, const std::vector<uint4> &enc, Kind kind, const s
     if ((rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_queries), &s->q_cap, n_queries, sizeof(uint4))) != CRP_OK) return rc;
     if ((rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_counts), &s->counts_cap, n_counts, sizeof(uint32_t))) != CRP_OK) return rc;
     if (!s->d_ctr) CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->d_ctr), sizeof(unsigned long long)));
-    if (kind.scored &&
+    if (kind.scored() &&
         (rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_hit_sum), &s->hit_sum_cap, n_queries, sizeof(unsigned long long))) != CRP_OK)
         return rc;
     uint64_t dev_sites = std::min(site_cap, std::max(s->sites_cap, s->site_start));
@@ -531,7 +555,7 @@ int run_encoded(crp_search *s, const std::vector<uint4> &enc, Kind kind, const s
             return rc;
     }
     if (counts) CRP_HIP(ctx, hipMemcpy(counts, s->d_counts, n_counts * sizeof(uint32_t), hipMemcpyDeviceToHost));
-    if (kind.scored) CRP_HIP(ctx, hipMemcpy(hit_sum, s->d_hit_sum, n_queries * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    if (kind.scored()) CRP_HIP(ctx, hipMemcpy(hit_sum, s->d_hit_sum, n_queries * sizeof(uint64_t), hipMemcpyDeviceToHost));
     *n_sites = total;
     if (total > site_cap) return CRP_ERR_CAPACITY;
     std::vector<uint2> raw(total);
@@ -558,9 +582,9 @@ int run_kind(crp_search *s, const char *queries, uint64_t n_queries, Kind kind, 
     if (T < 1 || T > CRP_SEARCH_MAX_T) return CRP_ERR_UNSUPPORTED;
     std::vector<uint4> enc;
     if (!encode_queries(queries, n_queries, T, enc)) return CRP_ERR_INVALID;
-    if (kind.scored)  // a base outside the guide region would mismatch where no factor is
+    if (kind.scored())  // a base outside the guide region would mismatch where no factor is
         for (const uint4 &q : enc)
-            if (q.z & ~s->scheme_region) return CRP_ERR_INVALID;
+            if (q.z & ~s->value.region) return CRP_ERR_INVALID;
     std::vector<uint8_t> span_first(n_queries);  // (0 for a plain run: its sites have no placement)
     if (kind.bulge())
         for (uint64_t q = 0; q < n_queries; ++q) {
@@ -589,10 +613,9 @@ int crp_search_run_scored(crp_search *s, const char *queries, uint64_t n_queries
                           uint64_t *n_sites, uint64_t *hit_sum)
 {
     if (!s || !n_sites || (n_queries && (!queries || !hit_sum))) return CRP_ERR_INVALID;
-    if (!s->have_scheme && !s->have_pair) return CRP_ERR_STATE;
+    if (!s->value.any()) return CRP_ERR_STATE;
     Kind kind;
-    kind.scored = true;
-    kind.by_pair = s->have_pair;
+    kind.value = s->value.have_pair ? Kind::PAIR : Kind::SCHEME;
     return run_kind(s, queries, n_queries, kind, nullptr, max_mm, site_cap, counts, n_sites, hit_sum);
 }
 

@@ -6,6 +6,8 @@
 
 #include "crp_kernels.h"
 
+struct crp_ctx;
+
 namespace crp {
 
 constexpr int SEARCH_WORDS = BLOCK;  // arena words per workgroup of the two extraction kernels (one word per thread)
@@ -58,6 +60,26 @@ struct SearchPair {
     unsigned long long *hit_sum;  // per query: the sum of its hits' values
 };
 
+// (x ^ q) | y in one v_bitop3_b32 (truth table over x, q, y = 0xF0, 0xCC, 0xAA): the compiler leaves it as xor + or3
+__device__ __forceinline__ uint32_t xor_or(uint32_t x, uint32_t q, uint32_t y) { return __builtin_amdgcn_bitop3_b32(x, q, y, 0xBE); }
+
+// The value of one hit under the scheme (Specificity score): the factors of the mask's bits, walked
+// in ascending g, times shape[n][d], as round-to-nearest-even of h * 2^30.  Every step is one correctly rounded f64
+// multiply (__dmul_rn: nothing to fuse or reorder), so the host's numpy statement gives the same integer.  A handle
+// whose g runs against the bit order (PAM on the 5' side) walks the reversed mask; its walk table is laid out for that.
+__device__ __forceinline__ uint32_t hit_value(uint32_t mask, int n, const SearchScore &sc)
+{
+    uint32_t m = sc.rev ? __builtin_bitreverse32(mask) : mask;
+    const int d = 31 - __builtin_clz(mask) - __builtin_ctz(mask);  // last - first mismatching position (mask != 0)
+    double hv = 1.0;
+    while (m) {
+        hv = __dmul_rn(hv, sc.tab[__builtin_ctz(m)]);
+        m &= m - 1;
+    }
+    hv = __dmul_rn(hv, sc.tab[SEARCH_SCORE_WALK + n * SEARCH_SCORE_SPREAD + d]);
+    return (uint32_t)__builtin_rint(__dmul_rn(hv, (double)(1u << SEARCH_SCORE_SHIFT)));  // factors and shape are in [0, 1]: <= 2^30
+}
+
 // The 2-bit code of a window's letter at pattern position p.
 __device__ __forceinline__ uint32_t search_code_at(uint32_t h, uint32_t l, uint32_t p) { return ((h >> p) & 1u) << 1 | ((l >> p) & 1u); }
 
@@ -90,7 +112,15 @@ __device__ __forceinline__ uint32_t search_pair_value(double walk, double pam)
     return (uint32_t)__builtin_rint(__dmul_rn(__dmul_rn(walk, pam), (double)(1u << SEARCH_SCORE_SHIFT)));
 }
 
-// Host side of a pair table (crp_search.cpp), shared by the two handles.  pair[n_factor][4][4] (query letter, site letter
+// Host side of a scheme (crp_search.cpp), shared by the two handles.  factor[n_factor] and shape[] (CRP_SEARCH_SHAPE_DOUBLES
+// values) become tab[SEARCH_SCORE_TAB] as SearchScore wants it.  The walk table: with the PAM on the 3' side the guide
+// region is positions 0 .. G - 1 and g is the position, so the mask is walked as it is.  On the 5' side the region is
+// positions T - G .. T - 1 and g = T - 1 - position; the kernel walks the bit-reversed mask, where position p is bit
+// 31 - p, so g = b - (32 - T) ascends with the bit again.  False when shape is missing, n_factor is outside 1 .. T or a
+// value is outside [0, 1] or not finite.
+bool search_scheme_layout(int T, const double *factor, int n_factor, bool pam3, const double *shape, double *tab);
+
+// Host side of a pair table, likewise.  pair[n_factor][4][4] (query letter, site letter
 // over A, C, G, T; the diagonal is ignored) and pam[4^n_pam_offsets] (the site's letters at those offsets inside the PAM,
 // first offset most significant) become tab[SEARCH_PAIR_TAB] and *pam_pos as SearchPair wants them.  False when the
 // input is outside the definition: a value outside [0, 1] or not finite, a guide region of n_factor positions on that
@@ -98,6 +128,28 @@ __device__ __forceinline__ uint32_t search_pair_value(double walk, double pam)
 // a pattern letter N.
 bool search_pair_layout(const SearchSets &sets, const double *pair, int n_factor, bool pam3, const int *pam_offsets, int n_pam_offsets,
                         const double *pam, double *tab, uint32_t *pam_pos);
+
+// What a handle knows about how its hits are valued: a scheme or a pair table on the device (one at a time: setting one
+// clears the other), the side the walk starts from and the positions that have a factor.  Both handles embed one.  The
+// setters return CRP_* codes (CRP_ERR_INVALID for an input the layout functions reject); the callers check what is
+// theirs alone (which n_factor and which side the handle allows) before.
+struct SearchValueState {
+    double *d_scheme = nullptr, *d_pair = nullptr;  // SEARCH_SCORE_TAB / SEARCH_PAIR_TAB doubles, allocated on first use
+    bool have_scheme = false, have_pair = false;
+    int rev = 0;          // PAM on the 5' side
+    uint32_t region = 0;  // the pattern positions that have a factor
+    int n_pam = 0;
+    uint32_t pam_pos = 0;
+
+    bool any() const { return have_scheme || have_pair; }
+    void clear() { have_scheme = have_pair = false; }
+    int set_scheme(crp_ctx *ctx, int T, const double *factor, int n_factor, bool pam3, const double *shape);
+    int set_pair(crp_ctx *ctx, const SearchSets &sets, const double *pair, int n_factor, bool pam3, const int *pam_offsets, int n_pam_offsets,
+                 const double *pam);
+    void free();
+    SearchScore score(unsigned long long *hit_sum) const { return SearchScore{d_scheme, rev, hit_sum}; }
+    SearchPair pair(unsigned long long *hit_sum) const { return SearchPair{d_pair, rev, n_pam, pam_pos, hit_sum}; }
+};
 
 // Per workgroup of SEARCH_WORDS words: {'+' candidates, '-' candidates}.
 hipError_t launch_search_count(hipStream_t s, const Planes &pl, uint64_t used_words, const SearchSets &sets, uint2 *block_cnt);

@@ -14,9 +14,10 @@
 //   compare     candidates in registers, SEARCH_CPL per lane; the queries of a batch are wave-uniform (scalar loads).
 //               Per pair: popc(((h ^ qh) | (l ^ ql) | nb) & qm) <= M.  Hits are rare: a wave ballots them and reserves
 //               its slots with one atomic.  The bulge compare (DNA or RNA bulge of one size) takes, per pair, the best
-//               placement of the bulge inside the query's span; see search_bulge_compare_kernel.  The scoring compare
-//               (search_score_compare_kernel) also adds every hit's value under a weighting scheme to a per-query sum;
-//               search_pair_compare_kernel does so under a pair table (values per base pair and per PAM).
+//               placement of the bulge inside the query's span; see search_bulge_compare_kernel.  The plain compare is
+//               written once (compare<Value>) and instantiated with three values of a hit: none (search_compare_kernel),
+//               the hit's value under a weighting scheme, added to a per-query sum (search_score_compare_kernel), and
+//               its value under a pair table, values per base pair and per PAM (search_pair_compare_kernel).
 //
 // Only vector stores and vector atomics, like the rest of the library.
 #include "crp_search.h"
@@ -179,156 +180,98 @@ __device__ __forceinline__ void append_hits(bool hit, uint32_t qi, int mm, uint3
     }
 }
 
+// What a hit of 1 .. max_mm mismatches is worth: the compare's one template parameter.  add() gets the lane's mismatch
+// mask (not 0), its candidate's oriented fields, the query's and the number of mismatches.
+struct NoValue {  // counts and sites only
+    __device__ __forceinline__ void add(uint32_t, uint32_t, uint32_t, uint32_t, const uint4 &, uint32_t, int) const {}
+};
+
+// The hit's value under a weighting scheme, added to hit_sum[q] with one 64-bit vector atomic.  The queries of a scored
+// run have no base outside the guide region (checked on the host), so every bit of the mask has a factor.
+struct SchemeValue {
+    SearchScore sc;
+    __device__ __forceinline__ void add(uint32_t mask, uint32_t, uint32_t, uint32_t, const uint4 &, uint32_t qi, int mm) const
+    {
+        atomicAdd(&sc.hit_sum[qi], (unsigned long long)hit_value(mask, mm, sc));
+    }
+};
+
+// The hit's value under a pair table (Pair tables): the lane has the candidate's oriented fields, PAM
+// positions included, and the query's in hand: per set bit of its mask it looks up the pair value of the two letters,
+// then the value of the site's PAM letters.  The table is read on this path only.
+struct PairValue {
+    SearchPair sp;
+    __device__ __forceinline__ void add(uint32_t mask, uint32_t h, uint32_t l, uint32_t nb, const uint4 &q, uint32_t qi, int) const
+    {
+        if (mask & nb) return;  // a non-base where the query has a base: counted, worth nothing
+        const uint32_t v = search_pair_value(search_pair_walk(mask, h, l, q.x, q.y, sp), search_pair_pam(h, l, sp));
+        atomicAdd(&sp.hit_sum[qi], (unsigned long long)v);
+    }
+};
+
+// The compare of the three kernels below: SEARCH_CPL candidates per lane in registers, the no-hit loop over the batch's
+// queries, and for a wave with a hit the append and the value.
+template <class Value>
+__device__ __forceinline__ void compare(SearchCands c, uint32_t n, const uint4 *queries, uint32_t q0, uint32_t nq, int max_mm, uint32_t *counts,
+                                        uint2 *sites, uint64_t site_cap, unsigned long long *site_ctr, Value value)
+{
+    const uint32_t first = blockIdx.x * (BLOCK * SEARCH_CPL) + threadIdx.x;
+    uint32_t h[SEARCH_CPL], l[SEARCH_CPL], nb[SEARCH_CPL];
+    int lim[SEARCH_CPL];  // max_mm, or -1 past the end: a lane without a candidate never hits
+#pragma unroll
+    for (int j = 0; j < SEARCH_CPL; ++j) {
+        const uint32_t i = first + j * BLOCK;
+        const bool ok = i < n;
+        h[j] = ok ? c.hi[i] : 0u;
+        nb[j] = ok ? c.nb[i] : 0u;
+        l[j] = ok ? c.lo[i] : 0u;  // (after nb: the loop's first instruction then needs the last load, one s_waitcnt instead of two)
+        lim[j] = ok ? max_mm : -1;
+    }
+    const uint32_t stride = (uint32_t)max_mm + 1;
+    for (uint32_t qi = q0; qi < q0 + nq; ++qi) {
+        const uint4 q = queries[qi];  // wave-uniform
+        int mm[SEARCH_CPL];
+        bool any = false;
+#pragma unroll
+        for (int j = 0; j < SEARCH_CPL; ++j) {
+            mm[j] = __popc(((h[j] ^ q.x) | (l[j] ^ q.y) | nb[j]) & q.z);  // (the compiler's xor + or3, not xor_or: as measured)
+            any |= mm[j] <= lim[j];
+        }
+        if (__builtin_expect(any, 0)) {
+#pragma unroll
+            for (int j = 0; j < SEARCH_CPL; ++j) {
+                const bool hit = mm[j] <= lim[j];
+                append_hits(hit, qi, mm[j], qi << 4 | (uint32_t)mm[j], c.pos + (first + j * BLOCK), stride, counts, sites, site_cap,
+                            site_ctr);
+                if (hit && mm[j] > 0) value.add(((h[j] ^ q.x) | (l[j] ^ q.y) | nb[j]) & q.z, h[j], l[j], nb[j], q, qi, mm[j]);
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(BLOCK) void search_compare_kernel(SearchCands c, uint32_t n, const uint4 *__restrict__ queries, uint32_t q0,
                                                                uint32_t nq, int max_mm, uint32_t *__restrict__ counts,
                                                                uint2 *__restrict__ sites, uint64_t site_cap,
                                                                unsigned long long *__restrict__ site_ctr)
 {
-    const uint32_t first = blockIdx.x * (BLOCK * SEARCH_CPL) + threadIdx.x;
-    uint32_t h[SEARCH_CPL], l[SEARCH_CPL], nb[SEARCH_CPL];
-    int lim[SEARCH_CPL];  // max_mm, or -1 past the end: a lane without a candidate never hits
-#pragma unroll
-    for (int j = 0; j < SEARCH_CPL; ++j) {
-        const uint32_t i = first + j * BLOCK;
-        const bool ok = i < n;
-        h[j] = ok ? c.hi[i] : 0u;
-        l[j] = ok ? c.lo[i] : 0u;
-        nb[j] = ok ? c.nb[i] : 0u;
-        lim[j] = ok ? max_mm : -1;
-    }
-    const uint32_t stride = (uint32_t)max_mm + 1;
-    for (uint32_t qi = q0; qi < q0 + nq; ++qi) {
-        const uint4 q = queries[qi];  // wave-uniform
-        int mm[SEARCH_CPL];
-        bool any = false;
-#pragma unroll
-        for (int j = 0; j < SEARCH_CPL; ++j) {
-            mm[j] = __popc(((h[j] ^ q.x) | (l[j] ^ q.y) | nb[j]) & q.z);
-            any |= mm[j] <= lim[j];
-        }
-        if (__builtin_expect(any, 0)) {
-#pragma unroll
-            for (int j = 0; j < SEARCH_CPL; ++j)
-                append_hits(mm[j] <= lim[j], qi, mm[j], qi << 4 | (uint32_t)mm[j], c.pos + (first + j * BLOCK), stride, counts, sites,
-                            site_cap, site_ctr);
-        }
-    }
+    compare(c, n, queries, q0, nq, max_mm, counts, sites, site_cap, site_ctr, NoValue{});
 }
 
-// The value of one hit under the scheme (Specificity score): the factors of the mask's bits, walked
-// in ascending g, times shape[n][d], as round-to-nearest-even of h * 2^30.  Every step is one correctly rounded f64
-// multiply (__dmul_rn: nothing to fuse or reorder), so the host's numpy statement gives the same integer.  A handle
-// whose g runs against the bit order (PAM on the 5' side) walks the reversed mask; its walk table is laid out for that.
-__device__ __forceinline__ uint32_t hit_value(uint32_t mask, int n, const SearchScore &sc)
-{
-    uint32_t m = sc.rev ? __builtin_bitreverse32(mask) : mask;
-    const int d = 31 - __builtin_clz(mask) - __builtin_ctz(mask);  // last - first mismatching position (mask != 0)
-    double hv = 1.0;
-    while (m) {
-        hv = __dmul_rn(hv, sc.tab[__builtin_ctz(m)]);
-        m &= m - 1;
-    }
-    hv = __dmul_rn(hv, sc.tab[SEARCH_SCORE_WALK + n * SEARCH_SCORE_SPREAD + d]);
-    return (uint32_t)__builtin_rint(__dmul_rn(hv, (double)(1u << SEARCH_SCORE_SHIFT)));  // factors and shape are in [0, 1]: <= 2^30
-}
-
-// search_compare_kernel plus the per-query sum of hit values: the same candidates per lane and the same no-hit loop; a
-// lane with a hit of 1 .. max_mm mismatches forms its mask again and adds the hit's value to hit_sum[q] with one 64-bit
-// vector atomic.  The queries of a scored run have no base outside the guide region (checked on the host), so every
-// bit of the mask has a factor.
 __global__ __launch_bounds__(BLOCK) void search_score_compare_kernel(SearchCands c, uint32_t n, const uint4 *__restrict__ queries, uint32_t q0,
                                                                      uint32_t nq, int max_mm, uint32_t *__restrict__ counts,
                                                                      uint2 *__restrict__ sites, uint64_t site_cap,
                                                                      unsigned long long *__restrict__ site_ctr, SearchScore sc)
 {
-    const uint32_t first = blockIdx.x * (BLOCK * SEARCH_CPL) + threadIdx.x;
-    uint32_t h[SEARCH_CPL], l[SEARCH_CPL], nb[SEARCH_CPL];
-    int lim[SEARCH_CPL];  // max_mm, or -1 past the end: a lane without a candidate never hits
-#pragma unroll
-    for (int j = 0; j < SEARCH_CPL; ++j) {
-        const uint32_t i = first + j * BLOCK;
-        const bool ok = i < n;
-        h[j] = ok ? c.hi[i] : 0u;
-        l[j] = ok ? c.lo[i] : 0u;
-        nb[j] = ok ? c.nb[i] : 0u;
-        lim[j] = ok ? max_mm : -1;
-    }
-    const uint32_t stride = (uint32_t)max_mm + 1;
-    for (uint32_t qi = q0; qi < q0 + nq; ++qi) {
-        const uint4 q = queries[qi];  // wave-uniform
-        int mm[SEARCH_CPL];
-        bool any = false;
-#pragma unroll
-        for (int j = 0; j < SEARCH_CPL; ++j) {
-            mm[j] = __popc(((h[j] ^ q.x) | (l[j] ^ q.y) | nb[j]) & q.z);
-            any |= mm[j] <= lim[j];
-        }
-        if (__builtin_expect(any, 0)) {
-#pragma unroll
-            for (int j = 0; j < SEARCH_CPL; ++j) {
-                const bool hit = mm[j] <= lim[j];
-                append_hits(hit, qi, mm[j], qi << 4 | (uint32_t)mm[j], c.pos + (first + j * BLOCK), stride, counts, sites, site_cap,
-                            site_ctr);
-                if (hit && mm[j] > 0) {
-                    const uint32_t mask = ((h[j] ^ q.x) | (l[j] ^ q.y) | nb[j]) & q.z;
-                    atomicAdd(&sc.hit_sum[qi], (unsigned long long)hit_value(mask, mm[j], sc));
-                }
-            }
-        }
-    }
+    compare(c, n, queries, q0, nq, max_mm, counts, sites, site_cap, site_ctr, SchemeValue{sc});
 }
 
-// search_score_compare_kernel under a pair table (Pair tables): the same candidates per lane and the
-// same no-hit loop.  A lane with a hit of 1 .. max_mm mismatches has the candidate's oriented fields, PAM positions
-// included, and the query's in hand: per set bit of its mask it looks up the pair value of the two letters, then the
-// value of the site's PAM letters, and adds the hit's value with one 64-bit vector atomic.  A non-base at a mismatching
-// position gives 0.  The table is read on this path only.
 __global__ __launch_bounds__(BLOCK) void search_pair_compare_kernel(SearchCands c, uint32_t n, const uint4 *__restrict__ queries, uint32_t q0,
                                                                     uint32_t nq, int max_mm, uint32_t *__restrict__ counts,
                                                                     uint2 *__restrict__ sites, uint64_t site_cap,
                                                                     unsigned long long *__restrict__ site_ctr, SearchPair sp)
 {
-    const uint32_t first = blockIdx.x * (BLOCK * SEARCH_CPL) + threadIdx.x;
-    uint32_t h[SEARCH_CPL], l[SEARCH_CPL], nb[SEARCH_CPL];
-    int lim[SEARCH_CPL];  // max_mm, or -1 past the end: a lane without a candidate never hits
-#pragma unroll
-    for (int j = 0; j < SEARCH_CPL; ++j) {
-        const uint32_t i = first + j * BLOCK;
-        const bool ok = i < n;
-        h[j] = ok ? c.hi[i] : 0u;
-        l[j] = ok ? c.lo[i] : 0u;
-        nb[j] = ok ? c.nb[i] : 0u;
-        lim[j] = ok ? max_mm : -1;
-    }
-    const uint32_t stride = (uint32_t)max_mm + 1;
-    for (uint32_t qi = q0; qi < q0 + nq; ++qi) {
-        const uint4 q = queries[qi];  // wave-uniform
-        int mm[SEARCH_CPL];
-        bool any = false;
-#pragma unroll
-        for (int j = 0; j < SEARCH_CPL; ++j) {
-            mm[j] = __popc(((h[j] ^ q.x) | (l[j] ^ q.y) | nb[j]) & q.z);
-            any |= mm[j] <= lim[j];
-        }
-        if (__builtin_expect(any, 0)) {
-#pragma unroll
-            for (int j = 0; j < SEARCH_CPL; ++j) {
-                const bool hit = mm[j] <= lim[j];
-                append_hits(hit, qi, mm[j], qi << 4 | (uint32_t)mm[j], c.pos + (first + j * BLOCK), stride, counts, sites, site_cap,
-                            site_ctr);
-                if (hit && mm[j] > 0) {
-                    const uint32_t mask = ((h[j] ^ q.x) | (l[j] ^ q.y) | nb[j]) & q.z;
-                    if (mask & nb[j]) continue;  // a non-base where the query has a base: counted, worth nothing
-                    const uint32_t v = search_pair_value(search_pair_walk(mask, h[j], l[j], q.x, q.y, sp), search_pair_pam(h[j], l[j], sp));
-                    atomicAdd(&sp.hit_sum[qi], (unsigned long long)v);
-                }
-            }
-        }
-    }
+    compare(c, n, queries, q0, nq, max_mm, counts, sites, site_cap, site_ctr, PairValue{sp});
 }
-
-// (x ^ q) | y in one v_bitop3_b32 (truth table over x, q, y = 0xF0, 0xCC, 0xAA): the compiler leaves it as xor + or3
-__device__ __forceinline__ uint32_t xor_or(uint32_t x, uint32_t q, uint32_t y) { return __builtin_amdgcn_bitop3_b32(x, q, y, 0xBE); }
 
 // mismatch mask of a window's fields against a query's, over the window's positions
 __device__ __forceinline__ uint32_t mism(uint32_t h, uint32_t l, uint32_t nb, uint32_t qh, uint32_t ql) { return xor_or(h, qh, xor_or(l, ql, nb)); }
@@ -420,12 +363,14 @@ hipError_t launch_search_emit(hipStream_t s, const Planes &pl, uint64_t used_wor
     return hipGetLastError();
 }
 
+// workgroups of a compare kernel over n candidates: BLOCK lanes of SEARCH_CPL candidates each
+static uint32_t compare_blocks(uint32_t n) { return (uint32_t)(((uint64_t)n + BLOCK * SEARCH_CPL - 1) / (BLOCK * SEARCH_CPL)); }
+
 hipError_t launch_search_compare(hipStream_t s, const SearchCands &c, uint32_t n, const uint4 *queries, uint32_t q0, uint32_t nq,
                                  int max_mm, uint32_t *counts, uint2 *sites, uint64_t site_cap, unsigned long long *site_ctr)
 {
     if (!n || !nq) return hipSuccess;
-    const uint32_t blocks = (uint32_t)(((uint64_t)n + BLOCK * SEARCH_CPL - 1) / (BLOCK * SEARCH_CPL));
-    search_compare_kernel<<<dim3(blocks), dim3(BLOCK), 0, s>>>(c, n, queries, q0, nq, max_mm, counts, sites, site_cap, site_ctr);
+    search_compare_kernel<<<dim3(compare_blocks(n)), dim3(BLOCK), 0, s>>>(c, n, queries, q0, nq, max_mm, counts, sites, site_cap, site_ctr);
     return hipGetLastError();
 }
 
@@ -434,9 +379,8 @@ hipError_t launch_search_score_compare(hipStream_t s, const SearchCands &c, uint
                                        const SearchScore &score)
 {
     if (!n || !nq) return hipSuccess;
-    const uint32_t blocks = (uint32_t)(((uint64_t)n + BLOCK * SEARCH_CPL - 1) / (BLOCK * SEARCH_CPL));
-    search_score_compare_kernel<<<dim3(blocks), dim3(BLOCK), 0, s>>>(c, n, queries, q0, nq, max_mm, counts, sites, site_cap, site_ctr,
-                                                                     score);
+    search_score_compare_kernel<<<dim3(compare_blocks(n)), dim3(BLOCK), 0, s>>>(c, n, queries, q0, nq, max_mm, counts, sites, site_cap,
+                                                                                site_ctr, score);
     return hipGetLastError();
 }
 
@@ -445,8 +389,8 @@ hipError_t launch_search_pair_compare(hipStream_t s, const SearchCands &c, uint3
                                       const SearchPair &pair)
 {
     if (!n || !nq) return hipSuccess;
-    const uint32_t blocks = (uint32_t)(((uint64_t)n + BLOCK * SEARCH_CPL - 1) / (BLOCK * SEARCH_CPL));
-    search_pair_compare_kernel<<<dim3(blocks), dim3(BLOCK), 0, s>>>(c, n, queries, q0, nq, max_mm, counts, sites, site_cap, site_ctr, pair);
+    search_pair_compare_kernel<<<dim3(compare_blocks(n)), dim3(BLOCK), 0, s>>>(c, n, queries, q0, nq, max_mm, counts, sites, site_cap,
+                                                                               site_ctr, pair);
     return hipGetLastError();
 }
 
@@ -455,9 +399,8 @@ hipError_t launch_search_bulge_compare(hipStream_t s,const SearchCands &c, uint3
                                        unsigned long long *site_ctr)
 {
     if (!n || !nq) return hipSuccess;
-    const uint32_t blocks = (uint32_t)(((uint64_t)n + BLOCK * SEARCH_CPL - 1) / (BLOCK * SEARCH_CPL));
-    search_bulge_compare_kernel<<<dim3(blocks), dim3(BLOCK), 0, s>>>(c, n, queries, q0, nq, max_mm, dna, rna, counts, sites, site_cap,
-                                                                     site_ctr);
+    search_bulge_compare_kernel<<<dim3(compare_blocks(n)), dim3(BLOCK), 0, s>>>(c, n, queries, q0, nq, max_mm, dna, rna, counts, sites,
+                                                                                site_cap, site_ctr);
     return hipGetLastError();
 }
 

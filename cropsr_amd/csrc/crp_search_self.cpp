@@ -77,14 +77,7 @@ struct crp_search_self {
     uint32_t *d_hist = nullptr;   // 2 x max keys: histogram, cursors
     uint32_t *d_counts = nullptr;            // n x (max_mm + 1)
     unsigned long long *d_hit_sum = nullptr;  // n
-    double *d_scheme = nullptr;
-    bool have_scheme = false;
-    int scheme_rev = 0;
-    // pair table (crp_search_self_set_pair_scheme): setting either clears the other
-    double *d_pair = nullptr;
-    bool have_pair = false;
-    int pair_n_pam = 0;
-    uint32_t pair_pam_pos = 0;
+    crp::SearchValueState value;  // crp_search_self_set_scheme / crp_search_self_set_pair_scheme
     uint4 *d_items = nullptr;
     // the current ordering
     int segment = -1;
@@ -272,8 +265,7 @@ int crp_search_self_destroy(crp_search_self *s)
     (void)hipFree(s->d_hist);
     (void)hipFree(s->d_counts);
     (void)hipFree(s->d_hit_sum);
-    (void)hipFree(s->d_scheme);
-    (void)hipFree(s->d_pair);
+    s->value.free();
     (void)hipFree(s->d_items);
     for (hipEvent_t e : s->ev)
         if (e) (void)hipEventDestroy(e);
@@ -292,30 +284,11 @@ int crp_search_self_set_scheme(crp_search_self *s, const double *factor, int n_f
 {
     if (!s) return CRP_ERR_INVALID;
     if (!factor) {
-        s->have_scheme = s->have_pair = false;
+        s->value.clear();
         return CRP_OK;
     }
-    const int T = s->T;
-    if (!shape || n_factor != T - s->pam_len) return CRP_ERR_INVALID;
-    const auto in_unit = [](double v) { return std::isfinite(v) && v >= 0.0 && v <= 1.0; };
-    if (!std::all_of(factor, factor + n_factor, in_unit) || !std::all_of(shape, shape + CRP_SEARCH_SHAPE_DOUBLES, in_unit))
-        return CRP_ERR_INVALID;
-    // the walk table of crp_search_set_scheme: g ascends with the bit (PAM on the 3' side) or with the bit of the
-    // reversed mask (5' side)
-    double tab[crp::SEARCH_SCORE_TAB];
-    std::fill(tab, tab + crp::SEARCH_SCORE_WALK, 1.0);
-    const int rev = s->pam3 ? 0 : 1;
-    for (int g = 0; g < n_factor; ++g) tab[rev ? g + 32 - T : g] = factor[g];
-    std::copy(shape, shape + CRP_SEARCH_SHAPE_DOUBLES, tab + crp::SEARCH_SCORE_WALK);
-    crp_ctx *ctx = s->ctx;
-    CRP_HIP(ctx, hipSetDevice(ctx->device));
-    if (!s->d_scheme) CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->d_scheme), sizeof(tab)));
-    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    CRP_HIP(ctx, hipMemcpy(s->d_scheme, tab, sizeof(tab), hipMemcpyHostToDevice));
-    s->scheme_rev = rev;
-    s->have_scheme = true;
-    s->have_pair = false;
-    return CRP_OK;
+    if (n_factor != s->T - s->pam_len) return CRP_ERR_INVALID;
+    return s->value.set_scheme(s->ctx, s->T, factor, n_factor, s->pam3, shape);
 }
 
 int crp_search_self_set_pair_scheme(crp_search_self *s, const double *pair, int n_factor, const int *pam_offsets, int n_pam_offsets,
@@ -323,24 +296,11 @@ int crp_search_self_set_pair_scheme(crp_search_self *s, const double *pair, int 
 {
     if (!s) return CRP_ERR_INVALID;
     if (!pair) {
-        s->have_scheme = s->have_pair = false;
+        s->value.clear();
         return CRP_OK;
     }
     if (n_factor != s->T - s->pam_len) return CRP_ERR_INVALID;
-    double tab[crp::SEARCH_PAIR_TAB];
-    uint32_t pam_pos = 0;
-    if (!crp::search_pair_layout(s->sets, pair, n_factor, s->pam3, pam_offsets, n_pam_offsets, pam, tab, &pam_pos)) return CRP_ERR_INVALID;
-    crp_ctx *ctx = s->ctx;
-    CRP_HIP(ctx, hipSetDevice(ctx->device));
-    if (!s->d_pair) CRP_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&s->d_pair), sizeof(tab)));
-    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    CRP_HIP(ctx, hipMemcpy(s->d_pair, tab, sizeof(tab), hipMemcpyHostToDevice));
-    s->scheme_rev = s->pam3 ? 0 : 1;
-    s->pair_n_pam = n_pam_offsets;
-    s->pair_pam_pos = pam_pos;
-    s->have_pair = true;
-    s->have_scheme = false;
-    return CRP_OK;
+    return s->value.set_pair(s->ctx, s->sets, pair, n_factor, s->pam3, pam_offsets, n_pam_offsets, pam);
 }
 
 int crp_search_self_sizes(const crp_search_self *s, uint64_t *n_plus, uint64_t *n_minus, uint64_t *n_guides)
@@ -408,17 +368,17 @@ int crp_search_self_compare(crp_search_self *q, crp_search_self *c)
     cmp.max_mm = q->max_mm;
     cmp.skip_same = q == c;
     for (int j = 0; j < q->segment; ++j) cmp.before[j] = ((1u << q->seg_len[j]) - 1u) << q->seg_shift[j];
-    crp::SearchScore score{q->d_scheme, q->scheme_rev, q->d_hit_sum};
-    const crp::SearchScore *sc = q->have_scheme ? &score : nullptr;
+    const crp::SearchScore score = q->value.score(q->d_hit_sum);
+    const crp::SearchScore *sc = q->value.have_scheme ? &score : nullptr;
     // under a pair table the candidates' PAM letters are read from the candidates' handle: its fields, through its ordering
-    const crp::SearchPair pair{q->d_pair, q->scheme_rev, q->pair_n_pam, q->pair_pam_pos, q->d_hit_sum};
+    const crp::SearchPair pair = q->value.pair(q->d_hit_sum);
     std::vector<uint4> items;
     uint64_t pairs = 0;
     const auto flush = [&]() -> int {
         if (items.empty()) return CRP_OK;
         CRP_HIP(ctx, hipMemcpy(q->d_items, items.data(), items.size() * sizeof(uint4), hipMemcpyHostToDevice));
         CRP_HIP(ctx, hipEventRecord(q->ev[0], ctx->stream));
-        if (q->have_pair)
+        if (q->value.have_pair)
             CRP_HIP(ctx, crp::launch_self_pair_compare(ctx->stream, q->order(), c->order(), c->cands(), q->d_items, (uint32_t)items.size(), cmp,
                                                        q->d_counts, pair));
         else

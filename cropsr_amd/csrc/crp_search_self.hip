@@ -21,9 +21,6 @@ namespace crp {
 
 namespace {
 
-// (x ^ q) | y in one v_bitop3_b32 (truth table over x, q, y = 0xF0, 0xCC, 0xAA)
-__device__ __forceinline__ uint32_t xor_or(uint32_t x, uint32_t q, uint32_t y) { return __builtin_amdgcn_bitop3_b32(x, q, y, 0xBE); }
-
 __global__ __launch_bounds__(BLOCK) void self_flag_kernel(SearchCands c, uint32_t n, SelfGuideRule rule, uint8_t *__restrict__ flag,
                                                           unsigned long long *__restrict__ n_guides)
 {
@@ -73,18 +70,96 @@ __global__ __launch_bounds__(BLOCK) void self_scatter_kernel(SearchCands c, uint
     idx[slot] = i;
 }
 
-// The value of one hit under the scheme: the walk of search_score_compare_kernel (crp_search.hip), step for step.
-__device__ __forceinline__ uint32_t hit_value(uint32_t mask, int n, const SearchScore &sc)
-{
-    uint32_t m = sc.rev ? __builtin_bitreverse32(mask) : mask;
-    const int d = 31 - __builtin_clz(mask) - __builtin_ctz(mask);  // last - first mismatching position (mask != 0)
-    double hv = 1.0;
-    while (m) {
-        hv = __dmul_rn(hv, sc.tab[__builtin_ctz(m)]);
-        m &= m - 1;
+// What a counted pair of 1 .. max_mm mismatches is worth: the compare's one template parameter.  of() gets the pair's
+// mismatch mask (not 0) and number of mismatches, the query's fields, the candidate's (masked to the guide region, like
+// the query's) and the candidate's entry of its ordering; add() gets a lane's sum at the end of its slice.
+struct SelfNoValue {  // counts only
+    __device__ __forceinline__ uint32_t of(uint32_t, int, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t) const { return 0; }
+    __device__ __forceinline__ void add(uint32_t, unsigned long long) const {}
+};
+
+struct SelfSchemeValue {  // hit_value, as the given-guides search has it
+    SearchScore sc;
+    __device__ __forceinline__ uint32_t of(uint32_t mask, int mm, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t, uint32_t) const
+    {
+        return hit_value(mask, mm, sc);
     }
-    hv = __dmul_rn(hv, sc.tab[SEARCH_SCORE_WALK + n * SEARCH_SCORE_SPREAD + d]);
-    return (uint32_t)__builtin_rint(__dmul_rn(hv, (double)(1u << SEARCH_SCORE_SHIFT)));
+    __device__ __forceinline__ void add(uint32_t row, unsigned long long sum) const
+    {
+        if (sum) atomicAdd(&sc.hit_sum[row], sum);
+    }
+};
+
+// Under a pair table (Pair tables).  The ordering's fields are masked to the guide region, which is
+// all a mismatch's two letters need; the candidate's PAM letters come, on the hit path only, from its unmasked fields in
+// extraction order (f_hi, f_lo of the candidates' handle) through the ordering's row index c_idx.  The candidate is
+// wave-uniform, so that gather and the PAM value are scalar loads.
+struct SelfPairValue {
+    SearchPair sp;
+    const uint32_t *__restrict__ c_idx, *__restrict__ f_hi, *__restrict__ f_lo;
+    __device__ __forceinline__ uint32_t of(uint32_t mask, int, uint32_t qh, uint32_t ql, uint32_t ch, uint32_t cl, uint32_t cn, uint32_t at) const
+    {
+        if (mask & cn) return 0;  // a non-base at a mismatching position: counted, worth nothing
+        const uint32_t row = c_idx[at];  // (an entry of the ordering, its index below the handle's n)
+        return search_pair_value(search_pair_walk(mask, ch, cl, qh, ql, sp), search_pair_pam(f_hi[row], f_lo[row], sp));
+    }
+    __device__ __forceinline__ void add(uint32_t row, unsigned long long sum) const
+    {
+        if (sum) atomicAdd(&sp.hit_sum[row], sum);
+    }
+};
+
+// The compare of the three kernels below: one query per lane, scalar candidate loads, the no-hit loop, and for a wave
+// with a hit the segment test, the counters and the value.
+template <class Value>
+__device__ __forceinline__ void self_compare(const uint32_t *q_hi, const uint32_t *q_lo, const uint32_t *q_idx, const uint32_t *c_hi,
+                                             const uint32_t *c_lo, const uint32_t *c_nb, const uint4 *items, SelfCompare cmp, uint32_t *counts,
+                                             Value value)
+{
+    const uint4 it = items[blockIdx.x];  // wave-uniform: {first query, queries, first candidate, candidates}
+    const bool have = threadIdx.x < it.y;
+    const uint32_t qi = it.x + threadIdx.x;
+    const uint32_t qh = have ? q_hi[qi] : 0u, ql = have ? q_lo[qi] : 0u;
+    const int lim = have ? cmp.max_mm : -1;  // a lane without a query never hits
+    const uint32_t self = cmp.skip_same ? qi : ~0u;
+    uint32_t cnt[SELF_MAX_MM + 1] = {};
+    unsigned long long sum = 0;
+    const uint32_t end = it.z + it.w;
+    // 8 consecutive words per field and trip: one scalar load each (the words behind `end` belong to the next slice or the
+    // pad).  The pointers are stepped, not formed from i: their first use is then before the loop, and so is the wait for
+    // the kernel arguments they come from.
+    const uint32_t *ph = c_hi + it.z, *pl = c_lo + it.z, *pn = c_nb + it.z;
+    for (uint32_t i = it.z; i < end; i += SELF_UNROLL, ph += SELF_UNROLL, pl += SELF_UNROLL, pn += SELF_UNROLL) {
+        int mm[SELF_UNROLL];
+        bool any = false;
+#pragma unroll
+        for (int k = 0; k < SELF_UNROLL; ++k) {
+            mm[k] = __popc(xor_or(qh, ph[k], xor_or(ql, pl[k], pn[k])));
+            any |= mm[k] <= lim;
+        }
+        if (__builtin_expect(any, 0)) {
+#pragma unroll
+            for (int k = 0; k < SELF_UNROLL; ++k) {
+                if (mm[k] > lim || i + k >= end || i + k == self) continue;
+                const uint32_t mask = xor_or(qh, ph[k], xor_or(ql, pl[k], pn[k]));
+                bool first = true;  // no earlier segment's bucket holds this pair
+#pragma unroll
+                for (int s = 0; s < SELF_MAX_MM; ++s)  // (| and &=, not || and &&: nothing to skip, and it compiles to scalar mask logic)
+                    first &= (s >= cmp.n_before) | ((mask & cmp.before[s]) != 0u);
+                if (!first) continue;
+#pragma unroll
+                for (int n = 0; n <= SELF_MAX_MM; ++n) cnt[n] += mm[k] == n ? 1u : 0u;
+                if (mm[k] > 0) sum += value.of(mask, mm[k], qh, ql, ph[k], pl[k], pn[k], i + k);
+            }
+        }
+    }
+    if (!have) return;
+    const uint32_t row = q_idx[qi];
+    const uint32_t stride = (uint32_t)cmp.max_mm + 1;
+#pragma unroll
+    for (int n = 0; n <= SELF_MAX_MM; ++n)
+        if (n <= cmp.max_mm && cnt[n]) atomicAdd(&counts[(uint64_t)row * stride + n], cnt[n]);
+    value.add(row, sum);
 }
 
 template <bool SCORED>
@@ -94,53 +169,12 @@ __global__ __launch_bounds__(SELF_TILE) void search_self_compare_kernel(const ui
                                                                         const uint32_t *__restrict__ c_nb, const uint4 *__restrict__ items,
                                                                         SelfCompare cmp, uint32_t *__restrict__ counts, SearchScore sc)
 {
-    const uint4 it = items[blockIdx.x];  // wave-uniform: {first query, queries, first candidate, candidates}
-    const bool have = threadIdx.x < it.y;
-    const uint32_t qi = it.x + threadIdx.x;
-    const uint32_t qh = have ? q_hi[qi] : 0u, ql = have ? q_lo[qi] : 0u;
-    const int lim = have ? cmp.max_mm : -1;  // a lane without a query never hits
-    const uint32_t self = cmp.skip_same ? qi : ~0u;
-    uint32_t cnt[SELF_MAX_MM + 1] = {};
-    unsigned long long sum = 0;
-    const uint32_t end = it.z + it.w;
-    for (uint32_t i = it.z; i < end; i += SELF_UNROLL) {  // (the words behind `end` belong to the next slice or the pad)
-        const uint32_t *ph = c_hi + i, *pl = c_lo + i, *pn = c_nb + i;  // 8 consecutive words each: one scalar load
-        int mm[SELF_UNROLL];
-        bool any = false;
-#pragma unroll
-        for (int k = 0; k < SELF_UNROLL; ++k) {
-            mm[k] = __popc(xor_or(qh, ph[k], xor_or(ql, pl[k], pn[k])));
-            any |= mm[k] <= lim;
-        }
-        if (__builtin_expect(any, 0)) {
-#pragma unroll
-            for (int k = 0; k < SELF_UNROLL; ++k) {
-                if (mm[k] > lim || i + k >= end || i + k == self) continue;
-                const uint32_t mask = xor_or(qh, ph[k], xor_or(ql, pl[k], pn[k]));
-                bool first = true;  // no earlier segment's bucket holds this pair
-#pragma unroll
-                for (int s = 0; s < SELF_MAX_MM; ++s) first = first && (s >= cmp.n_before || (mask & cmp.before[s]) != 0u);
-                if (!first) continue;
-#pragma unroll
-                for (int n = 0; n <= SELF_MAX_MM; ++n) cnt[n] += mm[k] == n ? 1u : 0u;
-                if (SCORED && mm[k] > 0) sum += hit_value(mask, mm[k], sc);
-            }
-        }
-    }
-    if (!have) return;
-    const uint32_t row = q_idx[qi];
-    const uint32_t stride = (uint32_t)cmp.max_mm + 1;
-#pragma unroll
-    for (int n = 0; n <= SELF_MAX_MM; ++n)
-        if (n <= cmp.max_mm && cnt[n]) atomicAdd(&counts[(uint64_t)row * stride + n], cnt[n]);
-    if (SCORED && sum) atomicAdd(&sc.hit_sum[row], sum);
+    if (SCORED)
+        self_compare(q_hi, q_lo, q_idx, c_hi, c_lo, c_nb, items, cmp, counts, SelfSchemeValue{sc});
+    else
+        self_compare(q_hi, q_lo, q_idx, c_hi, c_lo, c_nb, items, cmp, counts, SelfNoValue{});
 }
 
-// search_self_compare_kernel<true> under a pair table (Pair tables): one query per lane, the same
-// scalar candidate loads and the same no-hit loop.  The ordering's fields are masked to the guide region, which is all a
-// mismatch's two letters need; the candidate's PAM letters come, on the hit path only, from its unmasked fields in
-// extraction order (f_hi, f_lo of the candidates' handle) through the ordering's row index.  The candidate is
-// wave-uniform, so that gather and the PAM value are scalar loads.
 __global__ __launch_bounds__(SELF_TILE) void search_self_pair_compare_kernel(const uint32_t *__restrict__ q_hi, const uint32_t *__restrict__ q_lo,
                                                                              const uint32_t *__restrict__ q_idx,
                                                                              const uint32_t *__restrict__ c_hi, const uint32_t *__restrict__ c_lo,
@@ -149,49 +183,7 @@ __global__ __launch_bounds__(SELF_TILE) void search_self_pair_compare_kernel(con
                                                                              const uint4 *__restrict__ items, SelfCompare cmp,
                                                                              uint32_t *__restrict__ counts, SearchPair sp)
 {
-    const uint4 it = items[blockIdx.x];  // wave-uniform: {first query, queries, first candidate, candidates}
-    const bool have = threadIdx.x < it.y;
-    const uint32_t qi = it.x + threadIdx.x;
-    const uint32_t qh = have ? q_hi[qi] : 0u, ql = have ? q_lo[qi] : 0u;
-    const int lim = have ? cmp.max_mm : -1;  // a lane without a query never hits
-    const uint32_t self = cmp.skip_same ? qi : ~0u;
-    uint32_t cnt[SELF_MAX_MM + 1] = {};
-    unsigned long long sum = 0;
-    const uint32_t end = it.z + it.w;
-    for (uint32_t i = it.z; i < end; i += SELF_UNROLL) {  // (the words behind `end` belong to the next slice or the pad)
-        const uint32_t *ph = c_hi + i, *pl = c_lo + i, *pn = c_nb + i;  // 8 consecutive words each: one scalar load
-        int mm[SELF_UNROLL];
-        bool any = false;
-#pragma unroll
-        for (int k = 0; k < SELF_UNROLL; ++k) {
-            mm[k] = __popc(xor_or(qh, ph[k], xor_or(ql, pl[k], pn[k])));
-            any |= mm[k] <= lim;
-        }
-        if (__builtin_expect(any, 0)) {
-#pragma unroll
-            for (int k = 0; k < SELF_UNROLL; ++k) {
-                if (mm[k] > lim || i + k >= end || i + k == self) continue;
-                const uint32_t mask = xor_or(qh, ph[k], xor_or(ql, pl[k], pn[k]));
-                bool first = true;  // no earlier segment's bucket holds this pair
-#pragma unroll
-                for (int s = 0; s < SELF_MAX_MM; ++s) first = first && (s >= cmp.n_before || (mask & cmp.before[s]) != 0u);
-                if (!first) continue;
-#pragma unroll
-                for (int n = 0; n <= SELF_MAX_MM; ++n) cnt[n] += mm[k] == n ? 1u : 0u;
-                if (mm[k] > 0 && !(mask & pn[k])) {  // (a non-base at a mismatching position: counted, worth nothing)
-                    const uint32_t row = c_idx[i + k];  // (i + k < end: an entry of the ordering, its index below the handle's n)
-                    sum += search_pair_value(search_pair_walk(mask, ph[k], pl[k], qh, ql, sp), search_pair_pam(f_hi[row], f_lo[row], sp));
-                }
-            }
-        }
-    }
-    if (!have) return;
-    const uint32_t row = q_idx[qi];
-    const uint32_t stride = (uint32_t)cmp.max_mm + 1;
-#pragma unroll
-    for (int n = 0; n <= SELF_MAX_MM; ++n)
-        if (n <= cmp.max_mm && cnt[n]) atomicAdd(&counts[(uint64_t)row * stride + n], cnt[n]);
-    if (sum) atomicAdd(&sp.hit_sum[row], sum);
+    self_compare(q_hi, q_lo, q_idx, c_hi, c_lo, c_nb, items, cmp, counts, SelfPairValue{sp, c_idx, f_hi, f_lo});
 }
 
 inline uint32_t blocks_for(uint32_t n) { return (uint32_t)(((uint64_t)n + BLOCK - 1) / BLOCK); }
