@@ -149,8 +149,8 @@ __device__ __forceinline__ TileScan block_exclusive_scan(uint32_t v16, uint32_t 
 // Pure streaming pass: no LDS staging, no barrier before the loads.  A wavefront
 // covers 128 consecutive words (two per lane, one 16-byte load per plane and lane
 // = 64 bytes in flight per lane); the words a lane does not own come from its
-// neighbours by wave shuffles of the DERIVED G / C / void masks, and only lanes 0
-// and 63 touch memory for the words just outside the wave.  A workgroup of eight
+// neighbours by wave shuffles of the DERIVED G / C / void masks, and the words
+// just outside the wave are two wave-uniform loads per plane.  A workgroup of eight
 // waves produces the counts of one emit tile.
 __device__ __forceinline__ void derive(uint64_t hi, uint64_t lo, uint64_t up, uint64_t ac, uint64_t &g,
                                        uint64_t &c, uint64_t &v)
@@ -174,43 +174,80 @@ __device__ __forceinline__ void masks_of(uint64_t g_c, uint64_t g_n, uint64_t c_
     mminus = m;
 }
 
+// One word of a plane at a wave-uniform index, by a scalar load (SCALAR = true).  The planes are read-only for the whole
+// launch, which the constant address space states (a uniform address alone does not make the compiler choose the scalar
+// unit: the kernel writes its tables through other pointers).
+// SCALAR = false: the same uniform address through the vector unit (one address for all lanes, no divergence) -- for the
+// streaming kernels of the three-launch mode, where the scalar cache's misses cost more than the VALU work they save
+// (count kernel 0.103 -> 0.139 ms with scalar loads: profiles/EXPERIMENTS.md).
+template <bool SCALAR>
+__device__ __forceinline__ uint64_t uniform_word(const uint64_t *plane, uint64_t w)
+{
+    if constexpr (SCALAR) {
+        typedef const uint64_t __attribute__((address_space(4))) *ConstWords;
+        return ((ConstWords)(uintptr_t)plane)[w];
+    } else {
+        uint32_t zero = 0;
+        asm volatile("" : "+v"(zero));  // a lane-held zero: with nothing stored ahead of the load the compiler goes scalar by itself
+        return plane[w + zero];
+    }
+}
+
+// One word per plane just outside a wave's words on each side, as wave-uniform values (void beyond the arena).
+struct EdgeWords {
+    uint64_t left[4], right[4];
+};
+
 // The words a lane owns (WPT = 2: one 16-byte load per plane; WPT = 1: one 8-byte load) and the kept-hit masks of those
-// words.  w0 = first word of the lane's WAVE, which covers 64 * WPT consecutive words; the neighbouring words' derived
-// masks come from the adjacent lanes, and lanes 0 / 63 read the word just outside the wave from memory (void beyond the
-// arena).  Must be called by whole waves.
-template <int WPT>
+// words.  w0 = first word of the lane's WAVE, which covers 64 * WPT consecutive words, and must be wave-uniform
+// (readfirstlane).  The neighbouring words' derived masks come from the adjacent lanes.  The word just outside the wave
+// on either side is one value per wave: its address and its range test are uniform, so it is read by scalar loads
+// (SCALAR: the single-launch emit kernel, whose tile head every later tile waits for; see uniform_word) --
+// in flight together with the lanes' own loads, whose latency covers theirs (pinning them ahead of those delays the
+// vector loads and measured +1.6 %: profiles/EXPERIMENTS.md) --, its masks are derived on the SALU, and lanes 0 / 63
+// get them as the value the wave shifts leave in the lane that has no source.  The planes are read-only for the
+// whole launch.  `edge` returns the eight words (a tile's halo is its first wave's left and its last wave's right ones).
+// Must be called by whole waves.
+template <int WPT, bool SCALAR>
 __device__ __forceinline__ void own_words_and_masks(const Planes &pl, uint64_t n_words_padded, uint64_t w0, int lane, int l,
-                                                    uint64_t (&q)[4][WPT], uint64_t (&mp)[WPT], uint64_t (&mm)[WPT])
+                                                    uint64_t (&q)[4][WPT], uint64_t (&mp)[WPT], uint64_t (&mm)[WPT],
+                                                    EdgeWords &edge)
 {
     static_assert(WPT == 1 || WPT == 2, "one or two words per owning lane");
-    const uint64_t wa = w0 + (uint64_t)WPT * lane;
+    // always a word of the arena (w0 < n_words_padded), so the loads need no branch; out of range -> void below
+    const bool has_left = w0 > 0, has_right = w0 + 64 * WPT < n_words_padded;
+    const uint64_t wl = has_left ? w0 - 1 : 0, wr = has_right ? w0 + 64 * WPT : w0;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) {
+        edge.left[p] = uniform_word<SCALAR>(pl.plane[p], wl);
+        edge.right[p] = uniform_word<SCALAR>(pl.plane[p], wr);
+    }
     if constexpr (WPT == 2) {
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            const ulonglong2 v = *reinterpret_cast<const ulonglong2 *>(pl.plane[p] + wa);
+            const ulonglong2 v = reinterpret_cast<const ulonglong2 *>(pl.plane[p] + w0)[lane];
             q[p][0] = v.x;
             q[p][WPT - 1] = v.y;
         }
     } else {
 #pragma unroll
-        for (int p = 0; p < 4; ++p) q[p][0] = pl.plane[p][wa];
+        for (int p = 0; p < 4; ++p) q[p][0] = (pl.plane[p] + w0)[lane];
     }
-    uint64_t e[4] = {ALL, ALL, 0, 0};  // void beyond the arena
-    if (lane == 0 && w0 > 0) {
 #pragma unroll
-        for (int p = 0; p < 4; ++p) e[p] = pl.plane[p][w0 - 1];
-    } else if (lane == 63 && w0 + 64 * WPT < n_words_padded) {
-#pragma unroll
-        for (int p = 0; p < 4; ++p) e[p] = pl.plane[p][w0 + 64 * WPT];
+    for (int p = 0; p < 4; ++p) {
+        const uint64_t voidw = p < 2 ? ALL : 0ull;  // void beyond the arena
+        if (!has_left) edge.left[p] = voidw;
+        if (!has_right) edge.right[p] = voidw;
     }
-    uint64_t ga, ca, va, gb, cb, vb, ge, ce, ve;
+    uint64_t ga, ca, va, gb, cb, vb, gl, cl, vl, gr, cr, vr;
     derive(q[0][0], q[1][0], q[2][0], q[3][0], ga, ca, va);
     derive(q[0][WPT - 1], q[1][WPT - 1], q[2][WPT - 1], q[3][WPT - 1], gb, cb, vb);  // (WPT = 1: the same word)
-    derive(e[0], e[1], e[2], e[3], ge, ce, ve);
+    derive(edge.left[0], edge.left[1], edge.left[2], edge.left[3], gl, cl, vl);  // scalar; only vl is used
+    derive(edge.right[0], edge.right[1], edge.right[2], edge.right[3], gr, cr, vr);
     // left neighbour's last word, right neighbour's first word; lanes 0 / 63 keep the word outside the wave
-    const uint64_t v_left = wave_shift<DPP_WAVE_SHR1>(vb, ve);
-    const uint64_t g_right = wave_shift<DPP_WAVE_SHL1>(ga, ge), c_right = wave_shift<DPP_WAVE_SHL1>(ca, ce),
-                   v_right = wave_shift<DPP_WAVE_SHL1>(va, ve);
+    const uint64_t v_left = wave_shift<DPP_WAVE_SHR1>(vb, vl);
+    const uint64_t g_right = wave_shift<DPP_WAVE_SHL1>(ga, gr), c_right = wave_shift<DPP_WAVE_SHL1>(ca, cr),
+                   v_right = wave_shift<DPP_WAVE_SHL1>(va, vr);
     if constexpr (WPT == 2) {
         masks_of(ga, gb, ca, cb, v_left, va, vb, l, mp[0], mm[0]);
         masks_of(gb, g_right, cb, c_right, va, vb, v_right, l, mp[WPT - 1], mm[WPT - 1]);
@@ -229,12 +266,13 @@ __global__ __launch_bounds__(G::BLOCK) void count_kernel(Planes pl, uint64_t n_w
     const int l = LFIX > 0 ? LFIX : l_arg;
     const uint32_t tile = blockIdx.x;
     __shared__ uint64_t wave_tot[G::BLOCK / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     uint64_t c = 0;
-    const uint64_t w0 = (uint64_t)tile * G::WORDS + (uint64_t)wave * 64 * G::WPT;  // first word of this wave
+    const uint64_t w0 = (uint64_t)tile * G::WORDS + (uint64_t)wave * 64 * G::WPT;  // first word of this wave (uniform)
     if (wave < G::OWNERS / 64 && w0 < n_words_padded) {
         uint64_t q[4][G::WPT], mp[G::WPT], mm[G::WPT];
-        own_words_and_masks<G::WPT>(pl, n_words_padded, w0, lane, l, q, mp, mm);
+        EdgeWords edge;
+        own_words_and_masks<G::WPT, false>(pl, n_words_padded, w0, lane, l, q, mp, mm, edge);
 #pragma unroll
         for (int k = 0; k < G::WPT; ++k) c += (uint64_t)__popcll(mp[k]) | ((uint64_t)__popcll(mm[k]) << 32);
     }
@@ -670,27 +708,37 @@ __global__ __launch_bounds__(G::BLOCK) __attribute__((amdgpu_waves_per_eu(6, 8))
     if (CHAINED) __builtin_amdgcn_s_setprio(3);
     // Every owning thread loads the words it owns of each plane (one load per plane) and derives
     // its hit masks from those REGISTERS, taking the neighbouring words' G / C / void masks from the
-    // adjacent lanes by wave shuffles (lanes 0 and 63 read the word just outside the wave from
-    // memory) -- the count pass's scheme.  The words also go to LDS, but only the window extraction
+    // adjacent lanes by wave shuffles (the words just outside the wave are wave-uniform: scalar
+    // loads in the single-launch kernel) -- the count pass's scheme.  The words also go to LDS, but only the window extraction
     // after the block scan reads them there: no barrier and no LDS round trip stand between the loads
     // and the tile's counts.
     uint64_t mp[G::WPT], mm[G::WPT];
 #pragma unroll
     for (int k = 0; k < G::WPT; ++k) mp[k] = mm[k] = 0;
-    if (G::OWNERS == G::BLOCK || tid < G::OWNERS) {  // (whole waves: OWNERS is a multiple of 64)
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    if (G::OWNERS == G::BLOCK || wave < G::OWNERS / 64) {  // (whole waves: OWNERS is a multiple of 64)
         const int lane = tid & 63;
-        const uint64_t w0 = t0 + (uint64_t)(64 * G::WPT) * (uint64_t)(tid >> 6);  // first word of this wave
+        const uint64_t w0 = t0 + (uint64_t)(64 * G::WPT) * (uint64_t)wave;  // first word of this wave (uniform)
         uint64_t q[4][G::WPT];
-        own_words_and_masks<G::WPT>(pl, n_words_padded, w0, lane, l, q, mp, mm);
+        EdgeWords edge;
+        own_words_and_masks<G::WPT, CHAINED>(pl, n_words_padded, w0, lane, l, q, mp, mm, edge);
 #pragma unroll
         for (int p = 0; p < 4; ++p)
 #pragma unroll
             for (int k = 0; k < G::WPT; ++k) sh[p][1 + G::WPT * tid + k] = q[p][k];
-        if (tid < 8) {  // the tile's own halo words, for windows that reach across its ends
-            const int p = tid >> 1;
-            const uint64_t voidw = (p < 2) ? ALL : 0ull;
-            if (tid & 1) sh[p][TW + 1] = t0 + TW < n_words_padded ? pl.plane[p][t0 + TW] : voidw;
-            else sh[p][0] = t0 > 0 ? pl.plane[p][t0 - 1] : voidw;
+        // the tile's own halo words, for windows that reach across its ends: the first wave's left edge words and the
+        // last owner wave's right ones, one lane each
+        if (wave == 0) {
+            if (lane == 0) {
+#pragma unroll
+                for (int p = 0; p < 4; ++p) sh[p][0] = edge.left[p];
+            }
+        }
+        if (wave == G::OWNERS / 64 - 1) {
+            if (lane == 63) {
+#pragma unroll
+                for (int p = 0; p < 4; ++p) sh[p][TW + 1] = edge.right[p];
+            }
         }
     }
     uint32_t c16 = 0;  // plus | minus << 16
