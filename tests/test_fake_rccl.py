@@ -66,6 +66,18 @@ def _child_logical_devices(out, world):
     _write(out, {"hits": total, "stats": stats})
 
 
+def _child_sparse_genome(out, world):
+    """tests/test_sparse_genomes.py's node genome on RCCL: devices whose share has no hit send nothing, and the bucket
+    starts of the 16-bit positions cross with buckets that hold no row."""
+    import fake_rccl
+    import test_sparse_genomes as sg
+    from cropsr_amd import node as nd
+    from oracle import oracle
+    with nd.Node([0] * world) as node:
+        total, cond = sg.check_node_genome(node, world, oracle, transport=RCCL_NAME)
+    _write(out, {"hits": total, "no_hit": cond["no_hit"], "stats": fake_rccl.in_process_stats()})
+
+
 def _child_offtarget_annotation(out, world, gff_path):
     """The two opt-in steps through the node on RCCL: the 64 MiB histogram all-reduce on N communicators in one group, and
     the off-target / label-set columns inside the grouped send/recv."""
@@ -264,6 +276,19 @@ def test_node_logical_devices_on_rccl_double(world):
         assert r["hits"] > 100_000
         st = r["stats"]
         assert st["pairs"] > 50 and st["mismatches"] == 0 and st["inits"] == 1 and st["p2p_bytes"] > 1_000_000, st
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("world", [4, 7])
+def test_node_sparse_genome_on_rccl_double(world):
+    """A genome whose second half is one gap (tests/sparse_genome_cases.node_genome): the RCCL call sites see senders with
+    no row and position buckets without a hit; the oracle's rows, every send matched by a receive of the same size."""
+    import fake_rccl
+    with fake_rccl.Session(CRP_NODE_TRANSPORT="rccl") as s:
+        p, r = s.run_child("_child_sparse_genome", world)
+        assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+        assert r["hits"] > 5000 and len(r["no_hit"]) >= world // 2
+        assert r["stats"]["mismatches"] == 0 and r["stats"]["inits"] == 1 and r["stats"]["pairs"] > 0, r["stats"]
 
 
 @pytest.mark.gpu
