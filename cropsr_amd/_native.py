@@ -24,6 +24,13 @@ class RowSegment(ctypes.Structure):
                 ("n_rows", ctypes.c_uint64), ("feat_blob", ctypes.c_void_p), ("feat_off", ctypes.c_void_p), ("feat_idx", ctypes.c_void_p),
                 ("offtarget", ctypes.c_void_p)]
 
+
+
+class RowExtra(ctypes.Structure):
+    """crp_row_extra (include/cropsr_hip.h): the CSV join's columns of one segment, as crp_write_segments_cols takes them."""
+    _fields_ = [("self_counts", ctypes.c_void_p), ("n_counts", ctypes.c_int), ("self_hit_sum", ctypes.c_void_p)]
+
+
 voidpp = ctypes.POINTER(ctypes.c_void_p)
 
 # every symbol include/cropsr_hip.h declares: name -> (restype, argtypes)
@@ -64,6 +71,7 @@ SIGNATURES = {
     "crp_write_rows_ex": (ctypes.c_int, [ctypes.c_int, u8p, ctypes.c_uint64, u8p, ctypes.c_uint64, ctypes.c_int, u32p, u8p,
                                          f64p, u8p, ctypes.c_uint64, u8p, u64p, u32p, u32p, u64p, ctypes.c_int]),
     "crp_write_segments": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, u64p, ctypes.c_int]),
+    "crp_write_segments_cols": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, u64p, ctypes.c_int]),
     "crp_comm_unique_id": (ctypes.c_int, [u8p]),
     "crp_comm_init": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_int, ctypes.c_int]),
     "crp_comm_destroy": (ctypes.c_int, [ctypes.c_void_p]),
@@ -145,6 +153,8 @@ SIGNATURES = {
     "crp_search_self_compare": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "crp_search_self_fetch": (ctypes.c_int, [ctypes.c_void_p, u32p, u8p, u32p, u32p, u32p, u64p, ctypes.c_uint64]),
     "crp_search_self_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
+    "crp_search_self_join_hits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, u32p, u64p, u32p, u64p]),
+    "crp_search_self_join_device": (ctypes.c_int, [ctypes.c_void_p, voidpp, voidpp, voidpp, voidpp]),
     "crp_configure": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]),
     "crp_query": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     "crp_build_id": (ctypes.c_char_p, []),
@@ -180,6 +190,7 @@ SEARCH_PAM_3PRIME, SEARCH_PAM_5PRIME = 0, 1
 SEARCH_SHAPE_DOUBLES = 288
 SEARCH_SELF_MAX_MM = 4
 SEARCH_PAIR_MAX_PAM = 3
+SELF_UNJOINED_COUNT, SELF_UNJOINED_SUM = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF  # crp_search_self_join_hits: a hit without a guide site's row
 CRP_ERR_INVALID = -1
 CRP_ERR_NO_DEVICE = -2
 CRP_ERR_UNSUPPORTED = -7

@@ -88,6 +88,24 @@ def build_parser():
                      help="NOT in the reference: genome-wide off-target seed scan; appends four columns "
                           "offtarget_seed_mm0..3 (other PAM-adjacent sites whose 12-nt PAM-proximal seed differs in "
                           "0..3 places; -1 where the guide has no 12-base seed)")
+    eng.add_argument("--specificity", action="store_true",
+                     help="NOT in the reference: genome-wide specificity of every guide, full length: every row's guide against "
+                          "every candidate site of the genome (the self search of cropsr_amd.search, joined onto the rows on the "
+                          "GPU); appends the columns self_mm0..self_mmM (other candidate sites with exactly that many mismatches), "
+                          "self_hit_sum and specificity = 1 / (1 + self_hit_sum / 2^30); -1 where the row's guide is no guide site "
+                          "(a character that is no base, a window the contig end cuts); one GPU")
+    eng.add_argument("--specificity-mismatches", type=int, default=None, metavar="M",
+                     help="with --specificity: most mismatches counted (0..4, default 3)")
+    eng.add_argument("--specificity-pam", default=None, metavar="PAM",
+                     help="with --specificity: the PAM of the candidate sites, 3 letters over ACGTRYSWKMBDHVN that accept what NGG "
+                          "accepts (default NRG: NAG sites count as off-targets)")
+    # (the two exclude each other: specificity_request refuses the pair with the other refusals, in one voice)
+    eng.add_argument("--specificity-weights", metavar="FILE", default=None,
+                     help="with --specificity: mismatch weights, one number in [0, 1] per guide position, PAM-distal first, in "
+                          "place of the Hsu 2013 weights (which exist for -l 20 only); not with --specificity-table")
+    eng.add_argument("--specificity-table", metavar="FILE", default=None,
+                     help="with --specificity: a hit score of the CFD form, the pair table of FILE (cropsr_amd.search "
+                          "parse_pair_table, tools/cfd_to_table.py); not with --specificity-weights")
     eng.add_argument("--annotate", action="store_true",
                      help="NOT in the reference (which parses the GFF and drops it, CROPSR.py:375): fill the "
                           "`features` column with the gene/CDS rows of the GFF (-g) that contain the cut site, "
@@ -217,6 +235,7 @@ class EngineBackend:
         self.transport = os.environ.get("CROPSR_GATHER", "rccl")
         self.last_annotate_s = None  # --bench-json: seconds the last annotation join took on this rank
         self.last_stream = None      # --bench-json: crp_scan_stream's own numbers for the last plain scan
+        self.last_specificity = None  # --bench-json: the self-search handles' times of the last --specificity scan
 
     def connect(self):
         """Collective over the group: create the RCCL communicator (transport "rccl")."""
@@ -250,15 +269,16 @@ class EngineBackend:
             # code object (17-25 ms, otherwise paid by the genome's first slice)
             self.engine.scan_stream([np.frombuffer(b"ACGTTGCAAGGCCTTA" * 40, dtype=np.uint8)], 20)
 
-    def scan(self, contig_strings, guide_len, offtarget=False, annotation=None):
+    def scan(self, contig_strings, guide_len, offtarget=False, annotation=None, specificity=None):
         """One pass on the GPU for all contig strings (seam 1 + 2).  The plain scan goes through crp_scan_stream -- upload,
         scan and table fetch as a pipeline over slices of the genome, the host link busy in both directions (the reference's
         loop is produce-and-consume per contig too, CROPSR.py:409-474); CROPSR_STREAM=0, or the opt-in steps that work on
         resident tables (offtarget, annotation), take the arena calls: upload, one scan, fetch.  annotation
         (annotate.Request): the hit dicts also carry feat_plus / feat_minus, the label-set id of every row, joined on the GPU
-        while the tables are resident."""
+        while the tables are resident.  specificity (the arguments of search.specificity_columns): the hit dicts also carry
+        self_counts_* / self_sum_*, the self search's rows joined onto the resident tables."""
         import os
-        if not offtarget and annotation is None and os.environ.get("CROPSR_STREAM", "1") != "0":
+        if not offtarget and annotation is None and specificity is None and os.environ.get("CROPSR_STREAM", "1") != "0":
             want_pre = self.finalize == "host"
             hits = self.engine.scan_stream(contig_strings, guide_len, want_pre=want_pre)
             self.last_stream = hits.stream_stats  # (--bench-json)
@@ -271,10 +291,14 @@ class EngineBackend:
             self.last_annotate_s = None
             return out
         genome = self.engine.genome(contig_strings)  # as many arenas as the genome needs
-        hits = genome.scan_score(guide_len, want_pre=self.finalize == "host", offtarget=offtarget, annotation=annotation)
-        out = [self._finalize(hits.contig(k)) for k in range(len(contig_strings))]
-        self.last_annotate_s = genome.annotate_s
-        genome.close()
+        try:
+            hits = genome.scan_score(guide_len, want_pre=self.finalize == "host", offtarget=offtarget, annotation=annotation,
+                                     specificity=specificity)
+            out = [self._finalize(hits.contig(k)) for k in range(len(contig_strings))]
+            self.last_annotate_s = genome.annotate_s
+            self.last_specificity = getattr(hits.columns, "stats", None)  # (--bench-json)
+        finally:
+            genome.close()
         return out
 
     def scan_resident(self, texts, guide_len, offtarget=False):
@@ -405,6 +429,63 @@ def refilter_hits(hits, n, l):
     return out
 
 
+SPECIFICITY_MISMATCHES, SPECIFICITY_PAM = 3, "NRG"
+
+
+def _device_list(args):
+    return [d for d in str(getattr(args, "devices", None) or "").split(",") if d.strip()]
+
+
+def specificity_request(args):
+    """--specificity and its options, checked: None without it, else the arguments of search.specificity_columns
+    (max_mm, candidate_pam, score).  Everything the command line alone can get wrong ends the run here, with a message,
+    before any file is written or the GPU opened."""
+    def refuse(msg):
+        sys.exit("cropsr_amd: --specificity: " + msg)
+
+    given = [o for o, k in (("--specificity-mismatches", "specificity_mismatches"), ("--specificity-pam", "specificity_pam"),
+                            ("--specificity-weights", "specificity_weights"), ("--specificity-table", "specificity_table"))
+             if getattr(args, k, None) is not None]
+    if not getattr(args, "specificity", False):
+        if given:
+            sys.exit("cropsr_amd: %s belongs to --specificity" % given[0])
+        return None
+    from . import search
+    M = getattr(args, "specificity_mismatches", None)
+    M = SPECIFICITY_MISMATCHES if M is None else M
+    pam = getattr(args, "specificity_pam", None) or SPECIFICITY_PAM
+    wfile, tfile = getattr(args, "specificity_weights", None), getattr(args, "specificity_table", None)
+    if wfile and tfile:
+        refuse("--specificity-weights and --specificity-table are two forms of the hit score: give one of them")
+    if not 0 <= M <= search.MAX_SELF_MM:
+        refuse("--specificity-mismatches must be 0..%d, not %d" % (search.MAX_SELF_MM, M))
+    l = args.l
+    if l + search.SPECIFICITY_PAM_LEN > search.MAX_T:
+        refuse("guide and PAM are compared as one pattern of at most %d letters: -l %d is more than %d" % (
+            search.MAX_T, l, search.MAX_T - search.SPECIFICITY_PAM_LEN))
+    if l < M + 1:
+        refuse("-l %d is too short for %d mismatches (a guide of at least %d letters)" % (l, M, M + 1))
+    if len(_device_list(args)) > 1:
+        refuse("the self search runs on one GPU: --devices names %d" % len(_device_list(args)))
+    if getattr(args, "gpus", 1) > 1:
+        refuse("the self search runs on one GPU: drop --gpus %d" % args.gpus)
+    score = "hsu2013"
+    try:
+        if wfile:
+            with open(wfile, "rb") as f:
+                score = search.parse_weights(f.read())
+        elif tfile:
+            with open(tfile, "rb") as f:
+                score = search.parse_pair_table(f.read())
+        elif l != len(search.HSU2013_W):
+            refuse("the Hsu 2013 weights are defined for -l %d, not %d: give --specificity-weights or --specificity-table" % (
+                len(search.HSU2013_W), l))
+        search.check_specificity(l, M, pam, score)
+    except (search.SearchInputError, OSError, UnicodeDecodeError) as e:
+        refuse(str(e))
+    return dict(max_mm=M, candidate_pam=pam.upper(), score=score)
+
+
 class _Early:
     """fn() on a helper thread; get() joins and returns its result or raises what it raised."""
 
@@ -453,6 +534,7 @@ def run(args, backend=None, out=sys.stdout, group=None):
     l_dev = device_guide_length(args.l)
     if offtarget and not NATIVE_GUIDE_LENGTHS[0] <= args.l <= NATIVE_GUIDE_LENGTHS[1]:  # (before any side effect, on every rank)
         sys.exit("cropsr_amd: --offtarget needs a guide length between %d and %d (got %d)" % (NATIVE_GUIDE_LENGTHS + (args.l,)))
+    spec = specificity_request(args)  # (before any side effect, on every rank)
     finalize = getattr(args, "score_finalize", "gpu")
     stages = {}  # --bench-json
     own_group = group is None
@@ -465,10 +547,15 @@ def run(args, backend=None, out=sys.stdout, group=None):
         sys.exit("cropsr_amd: --devices (one process over several GPUs) cannot run under a launcher that started %d ranks "
                  "(one process per GPU): give one of them" % group.world)
 
+    if spec is not None and group is not None and group.world > 1:
+        sys.exit("cropsr_amd: --specificity: the self search runs on one GPU, and a launcher started %d ranks" % group.world)
+
     def make_backend():
-        if getattr(args, "devices", None):
+        if getattr(args, "devices", None) and not (spec is not None and len(_device_list(args)) == 1):
             return NodeBackend([int(d) for d in str(args.devices).split(",")], finalize)
         device = getattr(args, "device", None)
+        if spec is not None and getattr(args, "devices", None):  # (one device named the --devices way: the arena path on it)
+            device = int(_device_list(args)[0])
         if device is None:
             device = group.local_rank if group is not None else 0
         b = EngineBackend(device, group, finalize)
@@ -476,7 +563,7 @@ def run(args, backend=None, out=sys.stdout, group=None):
             big = isinstance(args.f, str) and os.path.getsize(args.f) >= (256 << 20)
         except OSError:
             big = False
-        if big and not offtarget and not getattr(args, "annotate", False):
+        if big and not offtarget and spec is None and not getattr(args, "annotate", False):
             b.warm_up()
         return b
 
@@ -599,7 +686,7 @@ def run(args, backend=None, out=sys.stdout, group=None):
     if getattr(args, "seed", None) is not None:
         np.random.seed(args.seed)
 
-    rows.write_header(args.o, offtarget=offtarget)  # CROPSR.py:402-405
+    rows.write_header(args.o, offtarget=offtarget, specificity=None if spec is None else spec["max_mm"])  # CROPSR.py:402-405
 
     names = [k for k, _ in table]
     strings = [v for _, v in table]  # contig strings as bytes, one byte per character
@@ -613,7 +700,14 @@ def run(args, backend=None, out=sys.stdout, group=None):
         extra = dict(offtarget=True) if offtarget else {}
         if request is not None:
             extra["annotation"] = request
-        all_hits = backend.scan(strings, l_dev, **extra)
+        if spec is not None:
+            extra["specificity"] = spec
+        from .search import SelfCapacityError
+        try:
+            all_hits = backend.scan(strings, l_dev, **extra)
+        except SelfCapacityError as e:
+            sys.exit("cropsr_amd: --specificity: the self search needs %d bytes of device memory for one arena of this genome: "
+                     "more than it may take" % e.needed)
     else:  # contigs (cut where longer than a rank's share) over all GPUs, tables gathered here
         from . import parallel
         err = None
@@ -743,6 +837,8 @@ def run(args, backend=None, out=sys.stdout, group=None):
         ids.close()
     if getattr(backend, "last_stream", None):  # the pipelined scan's own account of the upload + scan + fetch stage
         stages["scan_stream"] = backend.last_stream
+    if getattr(backend, "last_specificity", None):  # --specificity: the handles' kernel times, the join's among them
+        stages["specificity"] = backend.last_specificity
     if getattr(backend, "last_gather", None):  # one process over several devices (--devices): the node's gatherv, in numbers
         stages["node_gatherv"] = backend.last_gather
         stages["devices"] = list(backend.node.devices)
@@ -783,6 +879,7 @@ def main(argv=None):
     if getattr(args, "devices", None) and getattr(args, "gpus", 1) > 1:
         sys.exit("cropsr_amd: --devices (one process over several GPUs) and --gpus N (one process per GPU) are two ways to the "
                  "same result: give one of them")
+    specificity_request(args)  # (--gpus N: refused here, before any rank is started)
     if launch.wanted(getattr(args, "gpus", 1)):
         # no launcher in the environment: this process (which never touches the GPU) starts the ranks as fresh
         # children of the same command line and leaves with their status (cropsr_amd/launch.py)

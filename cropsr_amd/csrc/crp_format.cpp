@@ -174,6 +174,10 @@ struct Job {
     const uint64_t *feat_off = nullptr;
     const uint32_t *feat_idx = nullptr;
     const uint32_t *offtarget = nullptr;
+    // opt-in: the CSV join's columns (crp_write_segments_cols)
+    const uint32_t *self_counts = nullptr;
+    int n_counts = 0;
+    const uint64_t *self_hit_sum = nullptr;
     std::string chrom_field;  // the chromosome column as csv writes it
     size_t row_bound;         // no row is longer than this
 
@@ -243,6 +247,22 @@ char *format_range(const Job &j, uint64_t r0, uint64_t r1, char *o)
                 const uint32_t v = j.offtarget[4 * r + k];
                 *o++ = ',';
                 o = v == 0xffffffffu ? PUT_LIT(o, "-1") : put_int(o, (int64_t)v);
+            }
+        }
+        if (j.self_counts) {  // opt-in: n_counts + 2 more columns
+            for (int k = 0; k < j.n_counts; ++k) {
+                const uint32_t v = j.self_counts[(uint64_t)j.n_counts * r + k];
+                *o++ = ',';
+                o = v == 0xffffffffu ? PUT_LIT(o, "-1") : put_int(o, (int64_t)v);
+            }
+            const uint64_t hs = j.self_hit_sum ? j.self_hit_sum[r] : ~0ull;
+            if (hs == ~0ull) {
+                o = PUT_LIT(o, ",-1,-1");
+            } else {
+                *o++ = ',';
+                o = std::to_chars(o, o + 24, hs).ptr;
+                *o++ = ',';
+                o = put_repr(o, 1.0 / (1.0 + (double)hs / 1073741824.0));  // search.specificity
             }
         }
         o = PUT_LIT(o, "\r\n");
@@ -331,10 +351,13 @@ extern "C" int crp_format_rows(const uint8_t *contig_text, uint64_t contig_len, 
 // worker formats into its buffer and commits with one write(2), in order -- holds up to kBlockRows rows and may span several
 // short segments, so a run of small contigs costs what one contig of their total size costs (the CLI used to make one call per
 // contig: 626 scaffold passes of 3 500 rows each, formatted by ONE thread and joined, took a fifth of the CSV stage).
-extern "C" int crp_write_segments(int fd, int guide_len, const crp_row_segment *segs, uint64_t n_segs, uint64_t *bytes_written, int n_threads)
+extern "C" int crp_write_segments_cols(int fd, int guide_len, const crp_row_segment *segs, const crp_row_extra *extras, uint64_t n_segs,
+                                       uint64_t *bytes_written, int n_threads)
 {
     crp::Range roctx_range("crp: format + write rows");
     if (fd < 0 || (n_segs && !segs)) return CRP_ERR_INVALID;
+    for (uint64_t k = 0; extras && k < n_segs; ++k)
+        if (extras[k].self_counts && (extras[k].n_counts < 1 || extras[k].n_counts > 16)) return CRP_ERR_INVALID;
     if (bytes_written) *bytes_written = 0;
     for (uint64_t k = 0; k < n_segs; ++k) {
         const crp_row_segment &g = segs[k];
@@ -369,6 +392,12 @@ extern "C" int crp_write_segments(int fd, int guide_len, const crp_row_segment *
             job.feat_idx = g.feat_idx;
             job.offtarget = g.offtarget;
             if (g.offtarget) job.row_bound += 4 * 11;
+            if (extras && extras[k].self_counts) {
+                job.self_counts = extras[k].self_counts;
+                job.n_counts = extras[k].n_counts;
+                job.self_hit_sum = extras[k].self_hit_sum;
+                job.row_bound += 11 * (size_t)job.n_counts + 21 + 25;
+            }
             if (g.feat_idx) {  // the longest features entry a row can carry, quoted
                 uint64_t longest = 0;
                 for (uint64_t r = 0; r < g.n_rows; ++r)
@@ -432,6 +461,11 @@ extern "C" int crp_write_segments(int fd, int guide_len, const crp_row_segment *
     } catch (...) {
         return CRP_ERR_NOMEM;
     }
+}
+
+extern "C" int crp_write_segments(int fd, int guide_len, const crp_row_segment *segs, uint64_t n_segs, uint64_t *bytes_written, int n_threads)
+{
+    return crp_write_segments_cols(fd, guide_len, segs, nullptr, n_segs, bytes_written, n_threads);
 }
 
 extern "C" int crp_write_rows_ex(int fd, const uint8_t *contig_text, uint64_t contig_len, const uint8_t *chrom,

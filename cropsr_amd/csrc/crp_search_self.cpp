@@ -9,11 +9,14 @@
 // compare  guide sites of one handle against the candidates of another (or the same) in their current orderings, which
 //          must be of the same segment: per bucket, tiles of SELF_TILE queries x slices of candidates, cut into
 //          launches of at most pairs_per_launch pairs.  Hits add into the query handle's rows.
+// join     the rows of the guide sites onto the hit tables of the arena's last scan (CSV join): one
+//          launch per strand, the joined columns stay on the handle.
 // A genome of several arenas is every ordered pair of handles, segment by segment (cropsr_amd/search.py: search_self).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <new>
+#include <string>
 #include <vector>
 
 #include "crp_internal.h"
@@ -85,6 +88,12 @@ struct crp_search_self {
     hipEvent_t ev[2] = {nullptr, nullptr};
     double ms_extract = 0, ms_order = 0, ms_compare = 0, ms_longest = 0;
     uint64_t n_compare = 0, n_order = 0, pairs = 0;
+    // the joined columns of the last crp_search_self_join_hits, in hit-table order: [0] = '+', [1] = '-'
+    uint32_t *d_join_counts[2] = {nullptr, nullptr};
+    unsigned long long *d_join_sum[2] = {nullptr, nullptr};
+    uint64_t join_counts_cap[2] = {0, 0}, join_sum_cap[2] = {0, 0};
+    bool have_join = false;
+    double ms_join = 0;
 
     crp::SearchCands cands() const { return crp::SearchCands{d_cand, d_cand + n, d_cand + 2 * n, d_cand + 3 * n}; }
     crp::SelfOrder order() const
@@ -267,6 +276,10 @@ int crp_search_self_destroy(crp_search_self *s)
     (void)hipFree(s->d_hit_sum);
     s->value.free();
     (void)hipFree(s->d_items);
+    for (int k = 0; k < 2; ++k) {
+        (void)hipFree(s->d_join_counts[k]);
+        (void)hipFree(s->d_join_sum[k]);
+    }
     for (hipEvent_t e : s->ev)
         if (e) (void)hipEventDestroy(e);
     delete s;
@@ -463,11 +476,72 @@ int crp_search_self_fetch(crp_search_self *s, uint32_t *arena_pos, uint8_t *stra
     return k == s->n_guides ? CRP_OK : CRP_ERR_HIP;
 }
 
+int crp_search_self_join_hits(crp_search_self *s, int guide_len, uint32_t *counts_plus, uint64_t *hit_sum_plus, uint32_t *counts_minus,
+                              uint64_t *hit_sum_minus)
+{
+    if (!s) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    crp_arena *a = s->arena;
+    s->have_join = false;
+    if (s->T != guide_len + 3) {
+        ctx->last_error = "crp_search_self_join_hits: a pattern of " + std::to_string(s->T) + " letters does not join hits of guide length " +
+                          std::to_string(guide_len) + " (pattern_len must be guide_len + 3)";
+        return CRP_ERR_INVALID;
+    }
+    if (!s->pam3 || s->pam_len != 3) {
+        ctx->last_error = "crp_search_self_join_hits: the handle's PAM must be the pattern's last 3 letters";
+        return CRP_ERR_INVALID;
+    }
+    if (!a->have_hits || a->pend_guide_len != guide_len) {
+        ctx->last_error = "crp_search_self_join_hits: the arena has no hit tables of guide length " + std::to_string(guide_len);
+        return CRP_ERR_INVALID;
+    }
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t stride = (uint64_t)s->max_mm + 1;
+    for (int k = 0; k < 2; ++k) {
+        int rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_join_counts[k]), &s->join_counts_cap[k], a->n_hits[k] * stride, sizeof(uint32_t));
+        if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_join_sum[k]), &s->join_sum_cap[k], a->n_hits[k], sizeof(uint64_t));
+        if (rc != CRP_OK) return rc;
+    }
+    const unsigned long long *sums = s->value.any() ? s->d_hit_sum : nullptr;  // an unscored handle joins counts only
+    CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    for (int k = 0; k < 2; ++k)  // (a table has fewer rows than the arena positions: below 2^31)
+        CRP_HIP(ctx, crp::launch_self_join(ctx->stream, a->d_pos[k], (uint32_t)a->n_hits[k], k, guide_len, s->cands(), (uint32_t)s->n, s->d_flag,
+                                           s->d_counts, sums, s->max_mm, s->d_join_counts[k], s->d_join_sum[k]));
+    CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s->ms_join += elapsed(s->ev[0], s->ev[1]);
+    s->have_join = true;
+    uint32_t *hc[2] = {counts_plus, counts_minus};
+    uint64_t *hs[2] = {hit_sum_plus, hit_sum_minus};
+    for (int k = 0; k < 2; ++k) {
+        const uint64_t n = a->n_hits[k];
+        if (!n) continue;
+        int rc = CRP_OK;
+        if (hc[k]) rc = crp::staged_d2h(ctx, hc[k], s->d_join_counts[k], n * stride * sizeof(uint32_t));
+        if (rc == CRP_OK && hs[k]) rc = crp::staged_d2h(ctx, hs[k], s->d_join_sum[k], n * sizeof(uint64_t));
+        if (rc != CRP_OK) return rc;
+    }
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CRP_OK;
+}
+
+int crp_search_self_join_device(crp_search_self *s, void **counts_plus, void **hit_sum_plus, void **counts_minus, void **hit_sum_minus)
+{
+    if (!s) return CRP_ERR_INVALID;
+    if (!s->have_join) return CRP_ERR_STATE;
+    if (counts_plus) *counts_plus = s->d_join_counts[0];
+    if (hit_sum_plus) *hit_sum_plus = s->d_join_sum[0];
+    if (counts_minus) *counts_minus = s->d_join_counts[1];
+    if (hit_sum_minus) *hit_sum_minus = s->d_join_sum[1];
+    return CRP_OK;
+}
+
 int crp_search_self_stats(const crp_search_self *s, double *out, int n)
 {
-    if (!s || (n && !out) || n < 0 || n > 8) return CRP_ERR_INVALID;
-    const double v[8] = {s->ms_extract, s->ms_order, s->ms_compare, (double)s->n_compare,
-                         s->ms_longest, (double)s->pairs, (double)s->bytes, (double)s->n_order};
+    if (!s || (n && !out) || n < 0 || n > 9) return CRP_ERR_INVALID;
+    const double v[9] = {s->ms_extract, s->ms_order, s->ms_compare, (double)s->n_compare, s->ms_longest,
+                         (double)s->pairs, (double)s->bytes, (double)s->n_order, s->ms_join};
     for (int k = 0; k < n; ++k) out[k] = v[k];
     return CRP_OK;
 }

@@ -57,5 +57,12 @@ hipError_t launch_self_compare(hipStream_t s, const SelfOrder &q, const SelfOrde
 // ordering c is (c.idx indexes them): the candidates' PAM letters are read there.  Values add to pair.hit_sum[row].
 hipError_t launch_self_pair_compare(hipStream_t s, const SelfOrder &q, const SelfOrder &c, const SearchCands &c_fields, const uint4 *items,
                                     uint32_t n_items, const SelfCompare &cmp, uint32_t *counts, const SearchPair &pair);
+// The CSV join: hit k of a strand's scan table (hit_pos ascending arena match indices; strand 0 '+', 1 '-'; the scan's
+// guide length) gets the row of its site -- forward start hit_pos - guide_len for '+', hit_pos for '-' -- when that is a
+// guide site among the n_cand candidates c (extraction order): out_counts[k * (max_mm + 1) ..] and out_sum[k]; all-ones
+// otherwise, and an all-ones out_sum with hit_sum == nullptr (an unscored handle).
+hipError_t launch_self_join(hipStream_t s, const uint32_t *hit_pos, uint32_t n_hits, int strand, int guide_len, const SearchCands &c, uint32_t n_cand,
+                            const uint8_t *flag, const uint32_t *counts, const unsigned long long *hit_sum, int max_mm, uint32_t *out_counts,
+                            unsigned long long *out_sum);
 
 }  // namespace crp

@@ -14,6 +14,9 @@
 //            mask is non-zero in every segment before j (else that segment's bucket has counted it), and a lane adds
 //            its row to the result once, at the end of its slice.
 //
+// The CSV join (CSV join; self_join_kernel) hands the rows to the hits of a scan: one lane per hit of
+// a strand's table, a binary search for the hit's site among the candidates in extraction order, the row copied.
+//
 // Only vector stores and vector atomics, like the rest of the library.
 #include "crp_search_self.h"
 
@@ -186,6 +189,44 @@ __global__ __launch_bounds__(SELF_TILE) void search_self_pair_compare_kernel(con
     self_compare(q_hi, q_lo, q_idx, c_hi, c_lo, c_nb, items, cmp, counts, SelfPairValue{sp, c_idx, f_hi, f_lo});
 }
 
+// Extraction order as one ascending word: candidates come by 64-position word, within a word the '+' starts ascending
+// and then the '-' starts (search_emit_kernel), so (word, strand, bit) ascends with the index.  pos = start | strand << 31
+// with start < 2^31: the key has 32 bits.
+__device__ __forceinline__ uint32_t join_key(uint32_t pos) { return ((pos & 0x7fffffc0u) << 1) | ((pos >> 31) << 6) | (pos & 63u); }
+
+// One lane per hit of one strand's table (ascending arena match indices): '+' hit i has the site at forward start
+// i - guide_len, '-' hit j the site at j.  The site's row, if it is a guide site of the handle, goes to the hit's
+// columns; every other hit gets all-ones.  Reads only; writes its own slots only.
+__global__ __launch_bounds__(BLOCK) void self_join_kernel(const uint32_t *__restrict__ hit_pos, uint32_t n_hits, uint32_t strand, uint32_t guide_len,
+                                                          const uint32_t *__restrict__ cand_pos, uint32_t n_cand,
+                                                          const uint8_t *__restrict__ flag, const uint32_t *__restrict__ counts,
+                                                          const unsigned long long *__restrict__ hit_sum, uint32_t stride,
+                                                          uint32_t *__restrict__ out_counts, unsigned long long *__restrict__ out_sum)
+{
+    const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n_hits) return;
+    const uint32_t p = hit_pos[i];
+    uint32_t row = n_cand;  // none
+    if (strand || p >= guide_len) {
+        const uint32_t site = (strand ? p : p - guide_len) | strand << 31;
+        const uint32_t key = join_key(site);
+        uint32_t lo = 0, hi = n_cand;  // the first candidate whose key is not below the site's
+        while (lo < hi) {
+            const uint32_t mid = lo + (hi - lo) / 2;
+            if (join_key(cand_pos[mid]) < key)
+                lo = mid + 1;
+            else
+                hi = mid;
+        }
+        if (lo < n_cand && cand_pos[lo] == site && flag[lo]) row = lo;
+    }
+    const bool joined = row < n_cand;
+#pragma unroll
+    for (uint32_t n = 0; n <= (uint32_t)SELF_MAX_MM; ++n)
+        if (n < stride) out_counts[(uint64_t)i * stride + n] = joined ? counts[(uint64_t)row * stride + n] : 0xFFFFFFFFu;
+    out_sum[i] = joined && hit_sum ? hit_sum[row] : ~0ull;
+}
+
 inline uint32_t blocks_for(uint32_t n) { return (uint32_t)(((uint64_t)n + BLOCK - 1) / BLOCK); }
 
 }  // namespace
@@ -211,6 +252,16 @@ hipError_t launch_self_scatter(hipStream_t s, const SearchCands &c, uint32_t n, 
 {
     if (!n) return hipSuccess;
     self_scatter_kernel<<<dim3(blocks_for(n)), dim3(BLOCK), 0, s>>>(c, n, key, region, cursor, hi, lo, nb, idx);
+    return hipGetLastError();
+}
+
+hipError_t launch_self_join(hipStream_t s, const uint32_t *hit_pos, uint32_t n_hits, int strand, int guide_len, const SearchCands &c, uint32_t n_cand,
+                            const uint8_t *flag, const uint32_t *counts, const unsigned long long *hit_sum, int max_mm, uint32_t *out_counts,
+                            unsigned long long *out_sum)
+{
+    if (!n_hits) return hipSuccess;
+    self_join_kernel<<<dim3(blocks_for(n_hits)), dim3(BLOCK), 0, s>>>(hit_pos, n_hits, (uint32_t)strand, (uint32_t)guide_len, c.pos, n_cand, flag,
+                                                                      counts, hit_sum, (uint32_t)max_mm + 1, out_counts, out_sum);
     return hipGetLastError();
 }
 

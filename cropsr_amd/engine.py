@@ -722,11 +722,25 @@ class Genome:
         self.annotate_s = time.perf_counter() - t0  # track lay-out + upload + look-up (+ the copy of the ids to the host)
         return out if fetch else None
 
-    def scan_score(self, guide_len=20, want_pre=False, offtarget=False, seeds_from_scan=True, annotation=None):
+    def specificity_columns(self, guide_len=20, max_mm=3, candidate_pam="NRG", score="hsu2013", budget=None):
+        """The genome-wide specificity of every hit of the last scan at guide_len, joined on the GPU
+        (search.specificity_columns): per contig self_counts_plus / _minus (n, M + 1) and self_sum_plus / _minus."""
+        from . import search
+        return search.specificity_columns(self, guide_len, max_mm=max_mm, candidate_pam=candidate_pam, score=score, budget=budget)
+
+    def scan_score(self, guide_len=20, want_pre=False, offtarget=False, seeds_from_scan=True, annotation=None, specificity=None):
         """Seam 1 + 2 for every contig.  offtarget=True also runs the genome-wide seed scan over all
         arenas (single process: no reduce) and attaches (n, 4) counts to every contig's hits;
         seeds_from_scan=False makes the off-target step derive its seeds from the planes itself (the
-        path guide lengths other than 20 always take) instead of receiving them from the scan."""
+        path guide lengths other than 20 always take) instead of receiving them from the scan.
+        specificity (a dict of specificity_columns' arguments, {} for the defaults): every contig's hits also carry the
+        self search's counts and sums, joined on the GPU while the tables are resident."""
+        hits = self._scan_score(guide_len, want_pre, offtarget, seeds_from_scan, annotation)
+        if specificity is not None:  # (the tables of an arena stay valid until its next scan)
+            hits.columns = self.specificity_columns(guide_len, **specificity)
+        return hits
+
+    def _scan_score(self, guide_len, want_pre, offtarget, seeds_from_scan, annotation):
         if not offtarget:
             per_arena = [a.scan_score(guide_len, want_pre) for a in self.arenas]
             if annotation is not None:  # (the tables of an arena stay valid until its next scan)
@@ -784,10 +798,14 @@ class GenomeHits:
         self.per_arena = per_arena
         self.n_plus = sum(h.n_plus for h in per_arena)
         self.n_minus = sum(h.n_minus for h in per_arena)
+        self.columns = None  # per contig, further columns of its rows (Genome.scan_score(specificity=..))
 
     def contig(self, k):
         a, j = self._genome._where[k]
-        return self.per_arena[a].contig(j)
+        out = self.per_arena[a].contig(j)
+        if self.columns is not None:
+            out.update(self.columns[k])
+        return out
 
 
 def pack_ascii(text, n_threads=1):

@@ -25,6 +25,24 @@ HEADER = ["crispr_id", "crispr_sys", "sequence", "long_sequence", "chromosome", 
           "end_pos", "cutsite", "strand", "on_site_score", "features", "status"]
 OFFTARGET_HEADER = ["offtarget_seed_mm0", "offtarget_seed_mm1", "offtarget_seed_mm2", "offtarget_seed_mm3"]  # --offtarget
 NO_FEATURE = 0xFFFFFFFF
+UNJOINED_COUNT, UNJOINED_SUM = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF  # --specificity: a hit without a guide site's row (search.py, CSV join)
+
+
+def SPECIFICITY_HEADER(M):
+    """The M + 3 opt-in column names of --specificity at M mismatches: self_mm0 .. self_mmM, self_hit_sum, specificity."""
+    return ["self_mm%d" % k for k in range(int(M) + 1)] + ["self_hit_sum", "specificity"]
+
+
+def _self_columns(hits):
+    """(counts (n, M + 1) uint32, hit_sum (n,) uint64) of a contig's rows ('+' rows, then '-' rows) when its hits carry the
+    CSV join's columns (search.specificity_columns), else (None, None)."""
+    if hits.get("self_counts_plus") is None:
+        return None, None
+    cp, cm = np.asarray(hits["self_counts_plus"], dtype=np.uint32), np.asarray(hits["self_counts_minus"], dtype=np.uint32)
+    width = cp.shape[1] if cp.ndim == 2 else cm.shape[1]
+    counts = np.ascontiguousarray(np.concatenate([cp.reshape(-1, width), cm.reshape(-1, width)]), dtype=np.uint32)
+    sums = np.ascontiguousarray(np.concatenate([hits["self_sum_plus"], hits["self_sum_minus"]]), dtype=np.uint64)
+    return counts, sums
 CHUNK = 1000000  # CROPSR.py:453
 ORDER_BODY4, ORDER_TAIL2, ORDER_DOT1 = 0, 1, 2  # include/cropsr_hip.h CRP_ORDER_*
 
@@ -79,6 +97,7 @@ class ContigRows:
         if hits.get("ot_plus") is not None:
             self.ot = np.concatenate([hits["ot_plus"].reshape(-1, 4), hits["ot_minus"].reshape(-1, 4)]).astype(np.int64)
             self.ot[self.ot == 0xFFFFFFFF] = -1
+        self.self_counts, self.self_sum = _self_columns(hits)  # (--specificity)
         ip = hits["pos_plus"].astype(np.int64)
         jm = hits["pos_minus"].astype(np.int64)
         self.n = int(ip.size + jm.size)
@@ -101,6 +120,10 @@ class ContigRows:
     def row(self, k, crispr_id):
         strand = "+" if k < self.n_plus else "-"
         extra = () if self.ot is None else tuple(int(v) for v in self.ot[k])
+        if self.self_counts is not None:  # n counts, hit_sum, specificity (search.specificity's expression; csv writes repr(float))
+            extra += tuple(-1 if int(v) == UNJOINED_COUNT else int(v) for v in self.self_counts[k])
+            hs = int(self.self_sum[k])
+            extra += (-1, -1) if hs == UNJOINED_SUM else (hs, float(1.0 / (1.0 + np.float64(np.uint64(hs)) / float(1 << 30))))
         if len(self.long[k]) == 30:  # CROPSR.py:466
             feat = ""
             if self.features is not None and self.features[1][k] != NO_FEATURE:
@@ -195,10 +218,11 @@ class Dataset:
         return out
 
 
-def write_header(path, offtarget=False):
-    """CROPSR.py:402-405 (plus the four opt-in off-target column names)."""
+def write_header(path, offtarget=False, specificity=None):
+    """CROPSR.py:402-405 (plus the four opt-in off-target column names, then the opt-in --specificity names for
+    specificity = M mismatches)."""
     with open(path, "w", newline="") as f:
-        csv.writer(f).writerow(HEADER + (OFFTARGET_HEADER if offtarget else []))
+        csv.writer(f).writerow(HEADER + (OFFTARGET_HEADER if offtarget else []) + ([] if specificity is None else SPECIFICITY_HEADER(specificity)))
 
 
 def write_pass(path, dataset, rescore):
@@ -237,6 +261,7 @@ class ContigTable:
         if hits.get("ot_plus") is not None:
             self.ot = np.ascontiguousarray(np.concatenate([hits["ot_plus"].reshape(-1, 4), hits["ot_minus"].reshape(-1, 4)]),
                                            dtype=np.uint32)
+        self.self_counts, self.self_sum = _self_columns(hits)  # (--specificity)
         self.chrom = name_token[1:].encode("utf-8")
         self.chrom_u8 = np.frombuffer(self.chrom, dtype=np.uint8)  # (the pointer crp_write_segments reads the name through)
         self.text = np.frombuffer(s.encode("ascii", "replace") if isinstance(s, str) else s, dtype=np.uint8)
@@ -322,7 +347,8 @@ class NativeDataset:
                         t = blk.long_text(k0 + j).replace("U", "T").upper()  # CROPSR.py:458
                         seqs[r] = np.frombuffer(t.encode("ascii", "replace"), dtype=np.uint8)
                     score[fix] = rescore(seqs, order)
-                extras = (None if blk.feat_idx is None else blk.feat_idx[k0:k1], None if blk.ot is None else blk.ot[k0:k1])
+                extras = (None if blk.feat_idx is None else blk.feat_idx[k0:k1], None if blk.ot is None else blk.ot[k0:k1],
+                          None if blk.self_counts is None else (blk.self_counts[k0:k1], blk.self_sum[k0:k1]))
                 yield blk, blk.pos[k0:k1], blk.minus[k0:k1], score, np.ascontiguousarray(sel[g - lo:g - lo + m]), extras
             g = base + blk.n
             b += 1
@@ -333,7 +359,7 @@ class NativeDataset:
         L = nat.lib()
         out = []
         for blk, pos, minus, score, ids_part, extras in self._segments(lo, count, ids_u8, index_range, rescore, ids_rev):
-            if extras[0] is not None or extras[1] is not None:
+            if any(e is not None for e in extras):
                 raise ValueError("chunk_bytes formats the reference's columns only (use chunk_to_fd)")
             m = pos.size
             cap = m * (170 + 2 * len(blk.chrom)) + 64
@@ -358,7 +384,7 @@ class NativeDataset:
         """The same chunk as crp_row_segment entries appended to `segs` (for write_segments); every array a segment points
         into is appended to `keep` and must outlive the call that writes them."""
         from . import _native as nat
-        for blk, pos, minus, score, ids_part, (feat_idx, ot) in self._segments(lo, count, ids_u8, index_range, rescore, ids_rev):
+        for blk, pos, minus, score, ids_part, (feat_idx, ot, joined) in self._segments(lo, count, ids_u8, index_range, rescore, ids_rev):
             g = nat.RowSegment()
             score = np.ascontiguousarray(score)
             keep.extend((blk, pos, minus, score, ids_part))
@@ -373,6 +399,10 @@ class NativeDataset:
                 ot = np.ascontiguousarray(ot)
                 keep.append(ot)
                 g.offtarget = ot.ctypes.data
+            if joined is not None:  # the segment's crp_row_extra travels with it (write_segments lays them out side by side)
+                counts, sums = np.ascontiguousarray(joined[0]), np.ascontiguousarray(joined[1])
+                keep.extend((counts, sums))
+                g.extra = nat.RowExtra(counts.ctypes.data, counts.shape[1], sums.ctypes.data)
             segs.append(g)
 
     def chunk_to_fd(self, fd, lo, count, ids_u8, index_range, rescore, ids_rev=None):
@@ -390,11 +420,19 @@ def write_segments(fd, segs, guide_len, n_threads):
         return 0
     arr = (nat.RowSegment * len(segs))(*segs)
     written = ctypes.c_uint64()
-    st = nat.lib().crp_write_segments(fd, guide_len, ctypes.cast(arr, ctypes.c_void_p), len(segs), ctypes.byref(written), n_threads)
+    extras = [getattr(g, "extra", None) for g in segs]  # (--specificity: chunk_segments hangs a RowExtra on the segment)
+    if any(e is not None for e in extras):
+        what = "crp_write_segments_cols"
+        ext = (nat.RowExtra * len(segs))(*[e if e is not None else nat.RowExtra() for e in extras])
+        st = nat.lib().crp_write_segments_cols(fd, guide_len, ctypes.cast(arr, ctypes.c_void_p), ctypes.cast(ext, ctypes.c_void_p), len(segs),
+                                               ctypes.byref(written), n_threads)
+    else:
+        what = "crp_write_segments"
+        st = nat.lib().crp_write_segments(fd, guide_len, ctypes.cast(arr, ctypes.c_void_p), len(segs), ctypes.byref(written), n_threads)
     if st == nat.CRP_ERR_IO:
         err = ctypes.get_errno()
-        raise OSError(err, "crp_write_segments: " + os.strerror(err))
-    nat.check(st, "crp_write_segments")
+        raise OSError(err, what + ": " + os.strerror(err))
+    nat.check(st, what)
     return written.value
 
 

@@ -76,6 +76,19 @@ Self search (search_self, --self; DESIGN.md section 15, Self search): every guid
 
     python -m cropsr_amd.search -f genome.fa --pattern NNNNNNNNNNNNNNNNNNNNNRG --guide-pattern NNNNNNNNNNNNNNNNNNNNNGG \
         --pam-length 3 --self -m 3 --score hsu2013 -o guides.tsv
+
+CSV join (specificity_columns, ArenaSelfSearch.join_hits, crp_search_self_join_hits; `python -m cropsr_amd --specificity`;
+DESIGN.md section 15, CSV join): the self search's rows handed to the hits of the guide table's scan, on the GPU.
+  between  the last scan of an arena at guide length l (crp_scan_score: the kept .GG / CC. hits, positions = regex match
+           indices shifted by the contig's arena offset) and a self-search handle of the same arena whose candidate pattern
+           has T = l + 3 letters, P = 3 and its PAM on the 3' side: its guide region is the l letters the scan calls `sequence`
+  '+' hit  match index i (guide s[i-l:i], PAM s[i:i+3]): its site is forward start i - l, strand '+'
+  '-' hit  match index j (CC. at j, guide s[j+3:j+3+l]): its site is forward start j, strand '-'
+  joined   if that site is a guide site of the handle, the hit gets that site's counts[0..M] and hit_sum
+  unjoined every count is 0xFFFFFFFF and hit_sum 2^64 - 1: the site is only a candidate; a guide-region character is not
+           a base; a '-' hit whose window the contig end cuts (the reference keeps those up to len + 10)
+  where    positions are arena positions throughout; a hit and its site always lie in the same contig.  A handle without
+           a score joins the counts only (hit_sum all-ones).  specificity comes from hit_sum on the host (specificity())
 """
 import argparse
 import ctypes
@@ -885,10 +898,35 @@ class ArenaSelfSearch:
         return pos, strand, hi, lo, counts, hs
 
     def stats(self):
-        out = np.zeros(8, dtype=np.float64)
-        self._check(nat.lib().crp_search_self_stats(self._h, out.ctypes.data_as(nat.f64p), 8), "crp_search_self_stats")
-        keys = ("extract_ms", "order_ms", "compare_ms", "compare_launches", "longest_launch_ms", "pairs", "device_bytes", "order_launches")
+        out = np.zeros(9, dtype=np.float64)
+        self._check(nat.lib().crp_search_self_stats(self._h, out.ctypes.data_as(nat.f64p), 9), "crp_search_self_stats")
+        keys = ("extract_ms", "order_ms", "compare_ms", "compare_launches", "longest_launch_ms", "pairs", "device_bytes", "order_launches",
+                "join_ms")
         return dict(zip(keys, (float(v) for v in out)))
+
+    def join_hits(self, guide_len, fetch=True):
+        """crp_search_self_join_hits: this handle's rows handed to the hits of its arena's last scan at guide_len (the
+        module's docstring, CSV join).  Returns (counts_plus (n_plus, M + 1) uint32, sum_plus (n_plus,) uint64, counts_minus,
+        sum_minus) in hit-table order; fetch=False leaves the columns in HBM (join_device) and returns None."""
+        L = nat.lib()
+        if not fetch:
+            self._check(L.crp_search_self_join_hits(self._h, int(guide_len), None, None, None, None), "crp_search_self_join_hits")
+            return None
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        nat.check(L.crp_hits_counts(self._arena._h, ctypes.byref(a), ctypes.byref(b)), "crp_hits_counts")
+        cols = []
+        for n in (a.value, b.value):
+            cols += [np.empty((n, self.max_mm + 1), np.uint32), np.empty(n, np.uint64)]
+        self._check(L.crp_search_self_join_hits(self._h, int(guide_len), cols[0].ctypes.data_as(nat.u32p), cols[1].ctypes.data_as(nat.u64p),
+                                                cols[2].ctypes.data_as(nat.u32p), cols[3].ctypes.data_as(nat.u64p)),
+                    "crp_search_self_join_hits")
+        return tuple(cols)
+
+    def join_device(self):
+        """Device addresses (counts_plus, sum_plus, counts_minus, sum_minus) of the last join_hits."""
+        p = [ctypes.c_void_p() for _ in range(4)]
+        self._check(nat.lib().crp_search_self_join_device(self._h, *[ctypes.byref(x) for x in p]), "crp_search_self_join_device")
+        return tuple(x.value for x in p)
 
 
 class SelfSearchResult:
@@ -913,6 +951,28 @@ def _guide_letters(hi, lo, lo_pos, G):
     return out.view("S%d" % G).reshape(-1)
 
 
+def _self_handles(genome, pattern, gp, pam_len, max_mm, scheme, budget, pairs_per_launch, handles):
+    """One handle per arena of `genome`, appended to `handles` as they are made (the caller closes them)."""
+    for a in genome.arenas:
+        h = ArenaSelfSearch(a, pattern, gp, pam_len, max_mm, budget)
+        handles.append(h)
+        if scheme is not None:
+            h.set_scheme(scheme)
+        if pairs_per_launch:
+            h.set_limits(pairs_per_launch)
+
+
+def _self_compare_all(handles, max_mm):
+    """The whole search over the handles of a genome: segment by segment, every handle's ordering, then the guide sites of
+    each arena against the buckets of every arena."""
+    for j in range(max_mm + 1):
+        for h in handles:
+            h.order(j)
+        for hq in handles:
+            for hc in handles:
+                hq.compare(hc)
+
+
 def search_self(genome, pattern, max_mm, pam_len, guide_pattern=None, score=None, budget=None, pairs_per_launch=None):
     """The self search over all arenas of `genome` (engine.Genome): see the module's docstring.  budget: device bytes
     one arena's handle may take (None: the library's default); SelfCapacityError (.needed) beyond it.
@@ -921,19 +981,8 @@ def search_self(genome, pattern, max_mm, pam_len, guide_pattern=None, score=None
     lo, hi, _ = guide_region(pattern, pam_len)
     handles = []
     try:
-        for a in genome.arenas:
-            h = ArenaSelfSearch(a, pattern, gp, pam_len, max_mm, budget)
-            handles.append(h)
-            if scheme is not None:
-                h.set_scheme(scheme)
-            if pairs_per_launch:
-                h.set_limits(pairs_per_launch)
-        for j in range(max_mm + 1):
-            for h in handles:
-                h.order(j)
-            for hq in handles:  # the guide sites of one arena against the buckets of every arena
-                for hc in handles:
-                    hq.compare(hc)
+        _self_handles(genome, pattern, gp, pam_len, max_mm, scheme, budget, pairs_per_launch, handles)
+        _self_compare_all(handles, max_mm)
         parts, guides, counts, sums = [], [], [], []
         cand, n_guides, stats = [0, 0], 0, {}
         for h, a, group in zip(handles, genome.arenas, genome.groups):
@@ -963,6 +1012,64 @@ def search_self(genome, pattern, max_mm, pam_len, guide_pattern=None, score=None
     return SelfSearchResult(sites[order], np.concatenate(guides)[order], np.concatenate(counts)[order],
                             np.concatenate(sums)[order] if scheme is not None else None, tuple(cand),
                             (int(stats.get("pairs", 0)), n_guides * (cand[0] + cand[1])), stats)
+
+
+SPECIFICITY_PAM_LEN = 3  # the scan's PAM: .GG / CC.
+
+
+def check_specificity(guide_len, max_mm=3, candidate_pam="NRG", score="hsu2013"):
+    """The checked input of the CSV join for a scan at guide_len: (candidate pattern, guide pattern, M, Scheme or None).
+    The guide pattern is N * l + NGG, the candidate pattern N * l + candidate_pam (3 letters that accept what NGG accepts);
+    refuses l + 3 > 32, l < M + 1, M outside 0..4, hsu2013 with l != 20 and whatever else check_self refuses."""
+    if not isinstance(guide_len, (int, np.integer)) or int(guide_len) < 1:
+        raise SearchInputError("the specificity join needs a guide length of at least 1, not %r" % (guide_len,))
+    l = int(guide_len)
+    if l + SPECIFICITY_PAM_LEN > MAX_T:
+        raise SearchInputError("the specificity join compares guide and PAM as one pattern of at most %d letters: guide length %d is "
+                               "more than %d" % (MAX_T, l, MAX_T - SPECIFICITY_PAM_LEN))
+    pam = candidate_pam.decode() if isinstance(candidate_pam, bytes) else str(candidate_pam)
+    if len(pam) != SPECIFICITY_PAM_LEN:
+        raise SearchInputError("the candidate PAM must have %d letters, not %r" % (SPECIFICITY_PAM_LEN, candidate_pam))
+    pattern, gp, M, _, scheme = check_self("N" * l + pam, max_mm, SPECIFICITY_PAM_LEN, "N" * l + "NGG", score)
+    return pattern, gp, M, scheme
+
+
+def specificity_columns(genome, guide_len, max_mm=3, candidate_pam="NRG", score="hsu2013", budget=None):
+    """The genome-wide specificity of every hit of a scanned `genome` (engine.Genome whose arenas hold the tables of a scan
+    at guide_len): the self search of N * l + NGG guides among N * l + candidate_pam candidates over all arenas, then each
+    arena's tables joined against its own handle on the GPU (the module's docstring, CSV join).  Returns one dict per
+    contig, in contig order: self_counts_plus / self_counts_minus (n, M + 1) uint32 and self_sum_plus / self_sum_minus (n,)
+    uint64, rows as Hits.contig(k) has them.  score=None: counts only (the sums are all-ones).  The dicts' list carries
+    .stats, the handles' times summed over the arenas (join_ms among them)."""
+    pattern, gp, M, scheme = check_specificity(guide_len, max_mm, candidate_pam, score)
+    out = [None] * genome.n_contigs
+    handles, stats = [], {}
+    try:
+        _self_handles(genome, pattern, gp, SPECIFICITY_PAM_LEN, M, scheme, budget, None, handles)
+        _self_compare_all(handles, M)
+        for h, a, group in zip(handles, genome.arenas, genome.groups):
+            cp, sp, cm, sm = h.join_hits(guide_len)
+            pos_plus, pos_minus = np.empty(len(sp), np.uint32), np.empty(len(sm), np.uint32)
+            nat.check(nat.lib().crp_fetch_hits(a._h, pos_plus.ctypes.data_as(nat.u32p), None, None, pos_minus.ctypes.data_as(nat.u32p), None,
+                                               None), "crp_fetch_hits", a._engine._ctx)
+            ends = (np.asarray(a.offsets) + np.asarray(a.lengths)).astype(np.uint32)
+            starts = np.asarray(a.offsets).astype(np.uint32)
+            for j, k in enumerate(group):  # (the tables ascend in arena position: a contig's rows are one slice)
+                p0, p1 = np.searchsorted(pos_plus, [starts[j], ends[j]], "left")
+                m0, m1 = np.searchsorted(pos_minus, [starts[j], ends[j]], "left")
+                out[k] = dict(self_counts_plus=cp[p0:p1], self_sum_plus=sp[p0:p1], self_counts_minus=cm[m0:m1], self_sum_minus=sm[m0:m1])
+            for key, v in h.stats().items():
+                stats[key] = max(stats.get(key, 0.0), v) if key == "longest_launch_ms" else stats.get(key, 0.0) + v
+    finally:
+        for h in handles:
+            h.close()
+    out = _Columns(out)
+    out.stats = stats
+    return out
+
+
+class _Columns(list):
+    """specificity_columns' result: the per-contig dicts, with .stats."""
 
 
 def format_self(contig_names, res, block=1 << 16):

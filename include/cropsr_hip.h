@@ -266,6 +266,20 @@ typedef struct crp_row_segment {
 } crp_row_segment;
 int crp_write_segments(int fd, int guide_len, const crp_row_segment *segs, uint64_t n_segs, uint64_t *bytes_written, int n_threads);
 
+/* The same with the OPT-IN genome-wide specificity columns of the CSV join (crp_search_self_join_hits; DESIGN.md section
+ * 15, CSV join): extras, when not NULL, is an array parallel to segs.  An entry with self_counts == NULL adds nothing;
+ * with extras == NULL the call is crp_write_segments.  Otherwise every row of the segment -- the 11-field rows too --
+ * gets n_counts + 2 more fields, after the off-target fields if present: its n_counts counts (self_counts, n_counts per
+ * row; 0xFFFFFFFF prints as -1), hit_sum (self_hit_sum, one per row, a decimal integer) and the specificity
+ * 1 / (1 + hit_sum / 2^30) as repr(float); a hit_sum of 2^64 - 1, or self_hit_sum == NULL, prints -1 in both. */
+typedef struct crp_row_extra {
+    const uint32_t *self_counts;
+    int n_counts;
+    const uint64_t *self_hit_sum;
+} crp_row_extra;
+int crp_write_segments_cols(int fd, int guide_len, const crp_row_segment *segs, const crp_row_extra *extras, uint64_t n_segs,
+                            uint64_t *bytes_written, int n_threads);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ------------------------ */
 /* The reference has no parallelism (its only hint is the dead cropsr_functions.py:256-273).  The path
  * shards by contig with no collective on the data path; the one exchange is the final gatherv of the
@@ -723,8 +737,26 @@ int crp_search_self_fetch(crp_search_self *self, uint32_t *arena_pos, uint8_t *s
 /* Measurement, accumulated since create (compare figures on the `guides` handle): out[0] ms of extraction (count,
  * emit, guide flags), out[1] ms of ordering kernels, out[2] ms of compare kernels, out[3] compare launches, out[4]
  * the longest compare launch in ms, out[5] pairs compared, out[6] device bytes of the handle, out[7] ordering
- * launches.  n: how many of these to write (<= 8). */
+ * launches, out[8] ms of the join kernels (crp_search_self_join_hits).  n: how many of these to write (<= 9). */
 int crp_search_self_stats(const crp_search_self *self, double *out, int n);
+/* The CSV join (CSV join): the rows of the handle's guide sites, handed to the hits of the arena's
+ * last crp_scan_score at guide length guide_len, after the handle's orders and compares.  The handle's pattern must have
+ * guide_len + 3 letters with a PAM of 3 on the 3' side, so its guide region is what the scan calls `sequence`:
+ *   '+' hit, match index i  its site is forward start i - guide_len, strand '+'
+ *   '-' hit, match index j  its site is forward start j, strand '-'
+ * A hit whose site is a guide site of the handle gets that site's counts[0 .. max_mm] and hit_sum; every other hit (its
+ * site only a candidate, a guide-region character that is no base, a '-' window the contig end cuts) gets 0xFFFFFFFF in
+ * every count and 2^64 - 1 as hit_sum.  A handle without a scheme joins the counts; its hit_sum column is all-ones.
+ * The columns are in hit-table order ((max_mm + 1) counts per hit), stay in HBM on the handle until the next join or
+ * destroy, and are copied to the host pointers given (each may be NULL).  One kernel lane per hit: a binary search over
+ * the candidates in extraction order, no atomics.  CRP_ERR_INVALID with a crp_last_error text: pattern_len is not
+ * guide_len + 3, the PAM is on the 5' side or not 3 letters, the arena has no tables of that guide length. */
+int crp_search_self_join_hits(crp_search_self *self, int guide_len, uint32_t *counts_plus, uint64_t *hit_sum_plus,
+                              uint32_t *counts_minus, uint64_t *hit_sum_minus);
+/* Device addresses of the joined columns of the last crp_search_self_join_hits (CRP_ERR_STATE without one); any pointer
+ * may be NULL. */
+int crp_search_self_join_device(crp_search_self *self, void **counts_plus, void **hit_sum_plus, void **counts_minus,
+                                void **hit_sum_minus);
 
 /* ---- options -------------------------------------------------------------- */
 /* CRP_OPT_TWO_PASS (value 0/1, default 0): with 0 crp_scan_score is ONE kernel launch; the

@@ -299,6 +299,15 @@ def self_main(args, contigs, out):
             scaled_s = brute_ms * 1e-3 * n / len(queries)
             row.update(brute_queries=len(queries), brute_compare_ms=round(brute_ms, 3), brute_scaled_s=round(scaled_s, 1),
                        speedup_vs_scaled_brute=round(scaled_s / (gpu_ms * 1e-3), 1), rows_checked=int(min(2048, len(queries)) + top.size))
+            # the CSV join: the stand-in's hit tables (a scan at l = 20) against the rows of one more search, its own compare_ms
+            # next to it
+            n_hits = sum(sum(a.scan_score_device(20)) for a in g.arenas)
+            cols = srch.specificity_columns(g, 20, max_mm=M, candidate_pam=pattern[20:], score="hsu2013")
+            joined = sum(int((c["self_sum_plus"] != nat.SELF_UNJOINED_SUM).sum() + (c["self_sum_minus"] != nat.SELF_UNJOINED_SUM).sum())
+                         for c in cols)
+            row.update(join_hits=int(n_hits), join_joined=joined, join_ms=round(cols.stats["join_ms"], 3),
+                       join_run_compare_ms=round(cols.stats["compare_ms"], 3),
+                       join_over_compare=round(cols.stats["join_ms"] / max(1e-9, cols.stats["compare_ms"]), 5))
             out["runs"]["M%d" % M] = row
             print("M = %d: %s" % (M, json.dumps(row)), file=sys.stderr, flush=True)
         g.close()
