@@ -21,6 +21,7 @@
 #include <string>
 #include <vector>
 
+#include "crp_gather_cols.h"
 #include "crp_internal.h"
 #include "crp_rccl.h"
 #include "crp_roctx.h"
@@ -83,17 +84,13 @@ struct crp_comm {
     int test_fail = 0;             // test hook, environment CRP_TEST_GATHER_FAIL: 1 = the root's receive buffers
                                    // "do not fit", 2 = the last rank's arena "has no tables", 3 = the last rank sends
                                    // one row too few of its score column (a protocol error only a checking transport sees)
-    // root's receive side of the last crp_gather_hits: column-wise, peers back to back in rank order
-    uint32_t *d_gpos[2] = {nullptr, nullptr};
-    double *d_gscore[2] = {nullptr, nullptr};
-    uint4 *d_got[2] = {nullptr, nullptr};  // CRP_GATHER_OFFTARGET: per-hit counts
-    uint32_t *d_gfeat[2] = {nullptr, nullptr};  // CRP_GATHER_FEATURES: per-hit label-set ids
-    uint64_t gpos_cap[2] = {0, 0}, gscore_cap[2] = {0, 0}, got_cap[2] = {0, 0}, gfeat_cap[2] = {0, 0};
-    // CRP_GATHER_POS16 (crp_gather.hip): a peer's packed positions and bucket starts; at the root the staging area they
-    // arrive in, peer after peer (every peer's rows at a multiple of 8)
-    uint16_t *d_lo16[2] = {nullptr, nullptr}, *d_glo16[2] = {nullptr, nullptr};
-    uint32_t *d_bstart[2] = {nullptr, nullptr}, *d_gbstart[2] = {nullptr, nullptr};
-    uint64_t lo16_cap[2] = {0, 0}, bstart_cap[2] = {0, 0}, glo16_cap[2] = {0, 0}, gbstart_cap[2] = {0, 0};
+    // root's receive side of the last crp_gather_hits: column-wise, peers back to back in rank order; with
+    // CRP_GATHER_POS16 its staging area takes the packed positions, peer after peer (every peer's rows at a multiple of 8)
+    crp::GatherTables tables;
+    // CRP_GATHER_POS16 (crp_gather.hip): a peer's packed positions and bucket starts
+    uint16_t *d_lo16[2] = {nullptr, nullptr};
+    uint32_t *d_bstart[2] = {nullptr, nullptr};
+    uint64_t lo16_cap[2] = {0, 0}, bstart_cap[2] = {0, 0};
     uint64_t bytes_to_root = 0;  // of the last gather: what this rank sent (peer) or received (root)
     int gflags = 0;
     std::vector<uint64_t> goff[2];  // element offset of every rank's slice (root's own slice: unused)
@@ -120,15 +117,10 @@ void comm_release(crp_ctx *ctx)
     if (c->comm && rccl()) (void)rccl()->CommDestroy(c->comm);
     (void)hipFree(c->d_counts);
     (void)hipFree(c->d_small);
+    c->tables.free();
     for (int s = 0; s < 2; ++s) {
-        (void)hipFree(c->d_gpos[s]);
-        (void)hipFree(c->d_gscore[s]);
-        (void)hipFree(c->d_got[s]);
-        (void)hipFree(c->d_gfeat[s]);
         (void)hipFree(c->d_lo16[s]);
-        (void)hipFree(c->d_glo16[s]);
         (void)hipFree(c->d_bstart[s]);
-        (void)hipFree(c->d_gbstart[s]);
     }
     delete c;
     ctx->comm = nullptr;
@@ -261,18 +253,12 @@ int crp_gather_hits(crp_ctx *ctx, crp_arena *a, int root, int flags, uint64_t *c
     // (arguments that are the same on every rank by contract: a bad one fails everywhere alike)
     if (root < 0 || root >= c->world || (flags & ~(CRP_GATHER_OFFTARGET | CRP_GATHER_PRE | CRP_GATHER_FEATURES | CRP_GATHER_POS16)))
         return CRP_ERR_INVALID;
-    const bool send_pre = (flags & CRP_GATHER_PRE) != 0;
-    const bool with_ot = (flags & CRP_GATHER_OFFTARGET) != 0;
-    const bool with_feat = (flags & CRP_GATHER_FEATURES) != 0;
-    const bool pos16 = (flags & CRP_GATHER_POS16) != 0;
+    const crp::GatherCols cols = crp::gather_cols(flags);
     // What can differ from rank to rank -- the state of this rank's arena, the root's allocation -- is never
     // answered with an early return: a rank that left here alone would leave its peers inside a collective
     // that cannot complete.  Each rank's status travels WITH its counts, and everyone acts on all of them.
     int local = CRP_OK;
-    if (a && (a->ctx != ctx || !a->have_hits)) local = CRP_ERR_STATE;
-    else if (send_pre && a && !a->have_pre) local = CRP_ERR_STATE;
-    else if (with_ot && a && (!ctx->ot_solved || a->ot_epoch != ctx->ot_epoch)) local = CRP_ERR_STATE;
-    else if (with_feat && a && !a->have_feat) local = CRP_ERR_STATE;
+    if (a && (a->ctx != ctx || !crp::tables_present(cols, a))) local = CRP_ERR_STATE;
     if (c->test_fail == 2 && c->rank == c->world - 1) local = CRP_ERR_STATE;  // test hook (CRP_TEST_GATHER_FAIL)
     const Rccl *r = rccl();
     CRP_HIP(ctx, hipSetDevice(ctx->device));
@@ -299,46 +285,33 @@ int crp_gather_hits(crp_ctx *ctx, crp_arena *a, int root, int flags, uint64_t *c
     int alloc = CRP_OK;
     std::vector<uint64_t> soff[2], boff[2];  // CRP_GATHER_POS16: every peer's place in the root's staging area
     if (c->rank == root) {
-        for (int s = 0; s < 2 && alloc == CRP_OK; ++s) {
+        uint64_t total[2] = {0, 0}, lo_total[2] = {0, 0}, b_total[2] = {0, 0};
+        for (int s = 0; s < 2; ++s) {
             c->goff[s].assign(W, 0);
             soff[s].assign(W, 0);
             boff[s].assign(W, 0);
-            uint64_t total = 0, lo_total = 0, b_total = 0;
             for (int p = 0; p < c->world; ++p) {
-                c->goff[s][(size_t)p] = total;
-                soff[s][(size_t)p] = lo_total;
-                boff[s][(size_t)p] = b_total;
+                c->goff[s][(size_t)p] = total[s];
+                soff[s][(size_t)p] = lo_total[s];
+                boff[s][(size_t)p] = b_total[s];
                 if (p == root) continue;
-                total += c->counts[2 * (size_t)p + s];
-                lo_total += (c->counts[2 * (size_t)p + s] + 7) & ~(uint64_t)7;
-                b_total += buckets[(size_t)p];
+                total[s] += c->counts[2 * (size_t)p + s];
+                if (!cols.pos16) continue;
+                lo_total[s] += (c->counts[2 * (size_t)p + s] + 7) & ~(uint64_t)7;
+                b_total[s] += buckets[(size_t)p];
             }
-            if (pos16 && lo_total) {
-                alloc = crp::grow(ctx, reinterpret_cast<void **>(&c->d_glo16[s]), &c->glo16_cap[s], lo_total, sizeof(uint16_t));
-                if (alloc == CRP_OK)
-                    alloc = crp::grow(ctx, reinterpret_cast<void **>(&c->d_gbstart[s]), &c->gbstart_cap[s], b_total, sizeof(uint32_t));
-                if (alloc != CRP_OK) break;
-            }
-            alloc = crp::grow(ctx, reinterpret_cast<void **>(&c->d_gpos[s]), &c->gpos_cap[s], total, sizeof(uint32_t));
-            if (alloc == CRP_OK)
-                alloc = crp::grow(ctx, reinterpret_cast<void **>(&c->d_gscore[s]), &c->gscore_cap[s], total, sizeof(double));
-            if (alloc == CRP_OK && with_ot)
-                alloc = crp::grow(ctx, reinterpret_cast<void **>(&c->d_got[s]), &c->got_cap[s], total, sizeof(uint4));
-            if (alloc == CRP_OK && with_feat)
-                alloc = crp::grow(ctx, reinterpret_cast<void **>(&c->d_gfeat[s]), &c->gfeat_cap[s], total, sizeof(uint32_t));
         }
-    } else if (pos16 && a) {  // a peer's packed positions
+        alloc = c->tables.reserve(ctx, total, lo_total, b_total, cols);
+    } else if (cols.pos16 && a) {  // a peer's packed positions
         for (int s = 0; s < 2 && alloc == CRP_OK; ++s) {
             alloc = crp::grow(ctx, reinterpret_cast<void **>(&c->d_lo16[s]), &c->lo16_cap[s], (mine[s] + 7) & ~(uint64_t)7, sizeof(uint16_t));
             if (alloc == CRP_OK)
                 alloc = crp::grow(ctx, reinterpret_cast<void **>(&c->d_bstart[s]), &c->bstart_cap[s], my_buckets, sizeof(uint32_t));
         }
     }
-    if (c->rank == root) {
-        if (c->test_fail == 1) {  // test hook: as if the receive buffers did not fit
-            alloc = CRP_ERR_NOMEM;
-            ctx->last_error = "gatherv receive buffers: out of memory (injected by CRP_TEST_GATHER_FAIL)";
-        }
+    if (c->rank == root && c->test_fail == 1) {  // test hook: as if the receive buffers did not fit
+        alloc = CRP_ERR_NOMEM;
+        ctx->last_error = "gatherv receive buffers: out of memory (injected by CRP_TEST_GATHER_FAIL)";
     }
     const uint64_t word = (uint64_t)(-alloc);
     uint64_t *d_status = c->d_counts + 4 * W;
@@ -351,59 +324,47 @@ int crp_gather_hits(crp_ctx *ctx, crp_arena *a, int root, int flags, uint64_t *c
     // 3. the tables: grouped point-to-point, peers -> root
     crp::prof_begin(ctx, CRP_K_GATHER);
     uint64_t moved = 0;
-    if (pos16 && c->rank != root && a)  // (on the stream the sends are queued on: packed before they read)
+    if (cols.pos16 && c->rank != root && a)  // (on the stream the sends are queued on: packed before they read)
         for (int s = 0; s < 2; ++s) {
             CRP_HIP(ctx, crp::launch_pos16_buckets(ctx->stream, a->d_pos[s], mine[s], 0, mine[s], c->d_bstart[s], my_buckets));
             CRP_HIP(ctx, crp::launch_pos16_pack(ctx->stream, a->d_pos[s], mine[s], c->d_lo16[s]));
         }
     CRP_NCCL(ctx, r->GroupStart());
     ncclResult_t st = ncclSuccess;
+    // (every message is counted in bytes, the same list on both sides: crp::wire_msgs)
+    crp::WireMsg msg[crp::MAX_WIRE_MSGS];
     if (c->rank == root) {
         for (int p = 0; p < c->world && st == ncclSuccess; ++p) {
             if (p == root) continue;
             for (int s = 0; s < 2 && st == ncclSuccess; ++s) {
-                const uint64_t n = c->counts[2 * (size_t)p + s];
-                if (!n) continue;
-                moved += n * ((pos16 ? 2 : 4) + 8 + (with_ot ? 16 : 0) + (with_feat ? 4 : 0)) + (pos16 ? 4ull * buckets[(size_t)p] : 0);
-                if (pos16) {
-                    st = r->Recv(c->d_glo16[s] + soff[s][(size_t)p], 2 * n, ncclUint8, p, c->comm, ctx->stream);
-                    if (st == ncclSuccess)
-                        st = r->Recv(c->d_gbstart[s] + boff[s][(size_t)p], buckets[(size_t)p], ncclUint32, p, c->comm, ctx->stream);
-                } else {
-                    st = r->Recv(c->d_gpos[s] + c->goff[s][(size_t)p], n, ncclUint32, p, c->comm, ctx->stream);
+                const crp::GatherDst dst{&c->tables, c->goff[s][(size_t)p], soff[s][(size_t)p], boff[s][(size_t)p]};
+                const int nm = crp::wire_msgs(cols, s, c->counts[2 * (size_t)p + s], buckets[(size_t)p], nullptr, &dst, msg);
+                for (int m = 0; m < nm && st == ncclSuccess; ++m) {
+                    moved += msg[m].bytes;
+                    st = r->Recv(msg[m].dst, msg[m].bytes, ncclUint8, p, c->comm, ctx->stream);
                 }
-                if (st == ncclSuccess)
-                    st = r->Recv(c->d_gscore[s] + c->goff[s][(size_t)p], n, ncclDouble, p, c->comm, ctx->stream);
-                if (st == ncclSuccess && with_ot)
-                    st = r->Recv(c->d_got[s] + c->goff[s][(size_t)p], 4 * n, ncclUint32, p, c->comm, ctx->stream);
-                if (st == ncclSuccess && with_feat)
-                    st = r->Recv(c->d_gfeat[s] + c->goff[s][(size_t)p], n, ncclUint32, p, c->comm, ctx->stream);
             }
         }
     } else {
+        // test hook (CRP_TEST_GATHER_FAIL=3): the last rank's value column leaves one element short
+        const uint64_t short_by = c->test_fail == 3 && c->rank == c->world - 1 ? sizeof(double) : 0;
         for (int s = 0; s < 2 && st == ncclSuccess; ++s) {
-            if (!mine[s]) continue;
-            moved += mine[s] * ((pos16 ? 2 : 4) + 8 + (with_ot ? 16 : 0) + (with_feat ? 4 : 0)) + (pos16 ? 4ull * my_buckets : 0);
-            if (pos16) {
-                st = r->Send(c->d_lo16[s], 2 * mine[s], ncclUint8, root, c->comm, ctx->stream);
-                if (st == ncclSuccess) st = r->Send(c->d_bstart[s], my_buckets, ncclUint32, root, c->comm, ctx->stream);
-            } else {
-                st = r->Send(a->d_pos[s], mine[s], ncclUint32, root, c->comm, ctx->stream);
+            const crp::GatherSrc src{a, 0, c->d_lo16[s], c->d_bstart[s]};
+            const int nm = crp::wire_msgs(cols, s, mine[s], my_buckets, &src, nullptr, msg);
+            for (int m = 0; m < nm && st == ncclSuccess; ++m) {
+                moved += msg[m].bytes;
+                st = r->Send(msg[m].src, msg[m].bytes - (msg[m].col == crp::COL_VALUE ? short_by : 0), ncclUint8, root, c->comm, ctx->stream);
             }
-            if (st == ncclSuccess)
-                st = r->Send(send_pre ? a->d_pre[s] : a->d_score[s], mine[s] - (c->test_fail == 3 && c->rank == c->world - 1 ? 1 : 0), ncclDouble,
-                             root, c->comm, ctx->stream);
-            if (st == ncclSuccess && with_ot) st = r->Send(a->d_ot_cnt[s], 4 * mine[s], ncclUint32, root, c->comm, ctx->stream);
-            if (st == ncclSuccess && with_feat) st = r->Send(a->d_feat[s], mine[s], ncclUint32, root, c->comm, ctx->stream);
         }
     }
     const ncclResult_t st_end = r->GroupEnd();
-    if (pos16 && c->rank == root && st == ncclSuccess && st_end == ncclSuccess)  // packed -> the root's position tables
+    if (cols.pos16 && c->rank == root && st == ncclSuccess && st_end == ncclSuccess)  // packed -> the root's position tables
         for (int p = 0; p < c->world; ++p)
             for (int s = 0; s < 2 && p != root; ++s) {
                 const uint64_t n = c->counts[2 * (size_t)p + s];
-                CRP_HIP(ctx, crp::launch_pos16_expand(ctx->stream, c->d_glo16[s] + soff[s][(size_t)p], n, c->d_gbstart[s] + boff[s][(size_t)p],
-                                                      buckets[(size_t)p], crp::PieceMap{nullptr, nullptr, 0}, c->d_gpos[s] + c->goff[s][(size_t)p]));
+                CRP_HIP(ctx, crp::launch_pos16_expand(ctx->stream, c->tables.d_lo16[s] + soff[s][(size_t)p], n, c->tables.d_bstart[s] + boff[s][(size_t)p],
+                                                      buckets[(size_t)p], crp::PieceMap{nullptr, nullptr, 0},
+                                                      reinterpret_cast<uint32_t *>(c->tables.at(crp::COL_POS, s, c->goff[s][(size_t)p]))));
             }
     crp::prof_end(ctx, CRP_K_GATHER);
     if (st != ncclSuccess || st_end != ncclSuccess) {
@@ -423,6 +384,26 @@ int crp_gather_hits(crp_ctx *ctx, crp_arena *a, int root, int flags, uint64_t *c
     return CRP_OK;
 }
 
+// Columns of rank `rank`'s slice of the last gather to the caller's arrays: the root's own rows never moved and come out
+// of its arena, everyone else's out of the gathered tables at goff.
+static int fetch_cols(crp_ctx *ctx, const crp_comm *c, int rank, const crp::HostCol *want, int n_want)
+{
+    const crp::GatherCols cols = crp::gather_cols(c->gflags);
+    const bool own = rank == c->groot;
+    for (int s = 0; s < 2; ++s)
+        for (int i = 0; i < n_want; ++i) {
+            const int col = want[i].col;
+            const uint64_t n = c->counts[2 * (size_t)rank + s];
+            if (!n || !want[i].host[s]) continue;
+            if (own && (!c->garena || !(col == crp::COL_FEAT ? c->garena->have_feat : c->garena->have_hits))) return CRP_ERR_STATE;
+            const void *d = own ? crp::col_src(cols, col, c->garena, s, 0) : c->tables.at(col, s, c->goff[s][(size_t)rank]);
+            const int rc = crp::staged_d2h(ctx, want[i].host[s], d, n * crp::COL_BYTES[col]);
+            if (rc != CRP_OK) return rc;
+        }
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CRP_OK;
+}
+
 int crp_gathered_fetch(crp_ctx *ctx, int rank, uint32_t *pos_plus, double *score_plus, uint32_t *ot_plus,
                        uint32_t *pos_minus, double *score_minus, uint32_t *ot_minus)
 {
@@ -431,34 +412,9 @@ int crp_gathered_fetch(crp_ctx *ctx, int rank, uint32_t *pos_plus, double *score
     if (!c || !c->have_gather || c->rank != c->groot) return CRP_ERR_STATE;
     if (rank < 0 || rank >= c->world) return CRP_ERR_INVALID;
     CRP_HIP(ctx, hipSetDevice(ctx->device));
-    uint32_t *hp[2] = {pos_plus, pos_minus};
-    double *hs[2] = {score_plus, score_minus};
-    uint32_t *ho[2] = {ot_plus, ot_minus};
     if ((ot_plus || ot_minus) && !(c->gflags & CRP_GATHER_OFFTARGET)) return CRP_ERR_STATE;
-    for (int s = 0; s < 2; ++s) {
-        const uint64_t n = c->counts[2 * (size_t)rank + s];
-        if (!n) continue;
-        const uint32_t *dp;
-        const double *ds;
-        const uint4 *dt = nullptr;
-        if (rank == c->groot) {  // root's own rows never moved
-            if (!c->garena || !c->garena->have_hits) return CRP_ERR_STATE;
-            dp = c->garena->d_pos[s];
-            ds = (c->gflags & CRP_GATHER_PRE) ? c->garena->d_pre[s] : c->garena->d_score[s];
-            dt = c->garena->d_ot_cnt[s];
-        } else {
-            dp = c->d_gpos[s] + c->goff[s][(size_t)rank];
-            ds = c->d_gscore[s] + c->goff[s][(size_t)rank];
-            if (c->gflags & CRP_GATHER_OFFTARGET) dt = c->d_got[s] + c->goff[s][(size_t)rank];
-        }
-        int rc = CRP_OK;
-        if (ho[s]) rc = crp::staged_d2h(ctx, ho[s], dt, n * sizeof(uint4));
-        if (rc == CRP_OK && hp[s]) rc = crp::staged_d2h(ctx, hp[s], dp, n * sizeof(uint32_t));
-        if (rc == CRP_OK && hs[s]) rc = crp::staged_d2h(ctx, hs[s], ds, n * sizeof(double));
-        if (rc != CRP_OK) return rc;
-    }
-    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CRP_OK;
+    const crp::HostCol want[3] = {{crp::COL_OT, {ot_plus, ot_minus}}, {crp::COL_POS, {pos_plus, pos_minus}}, {crp::COL_VALUE, {score_plus, score_minus}}};
+    return fetch_cols(ctx, c, rank, want, 3);
 }
 
 int crp_gathered_fetch_features(crp_ctx *ctx, int rank, uint32_t *feat_plus, uint32_t *feat_minus)
@@ -468,22 +424,8 @@ int crp_gathered_fetch_features(crp_ctx *ctx, int rank, uint32_t *feat_plus, uin
     if (!c || !c->have_gather || c->rank != c->groot || !(c->gflags & CRP_GATHER_FEATURES)) return CRP_ERR_STATE;
     if (rank < 0 || rank >= c->world) return CRP_ERR_INVALID;
     CRP_HIP(ctx, hipSetDevice(ctx->device));
-    uint32_t *hf[2] = {feat_plus, feat_minus};
-    for (int s = 0; s < 2; ++s) {
-        const uint64_t n = c->counts[2 * (size_t)rank + s];
-        if (!n || !hf[s]) continue;
-        const uint32_t *df;
-        if (rank == c->groot) {  // root's own rows never moved
-            if (!c->garena || !c->garena->have_feat) return CRP_ERR_STATE;
-            df = c->garena->d_feat[s];
-        } else {
-            df = c->d_gfeat[s] + c->goff[s][(size_t)rank];
-        }
-        const int rc = crp::staged_d2h(ctx, hf[s], df, n * sizeof(uint32_t));
-        if (rc != CRP_OK) return rc;
-    }
-    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return CRP_OK;
+    const crp::HostCol want{crp::COL_FEAT, {feat_plus, feat_minus}};
+    return fetch_cols(ctx, c, rank, &want, 1);
 }
 
 }  // extern "C"

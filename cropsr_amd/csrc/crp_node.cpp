@@ -43,6 +43,7 @@
 #include <thread>
 #include <vector>
 
+#include "crp_gather_cols.h"
 #include "crp_internal.h"
 #include "crp_plan.h"
 #include "crp_rccl.h"
@@ -209,17 +210,8 @@ struct crp_node {
     std::string comms_error;  // why RCCL is not (or no longer) in use; crp_node_transport_note
     // root side of the last gather
     int root = -1;        // the device the buffers below live on
-    uint32_t *d_fpos[2] = {nullptr, nullptr};
-    double *d_fscore[2] = {nullptr, nullptr};
-    uint64_t fpos_cap[2] = {0, 0}, fscore_cap[2] = {0, 0};
-    uint4 *d_fot[2] = {nullptr, nullptr};        // CRP_GATHER_OFFTARGET: per-hit off-target counts
-    uint32_t *d_ffeat[2] = {nullptr, nullptr};   // CRP_GATHER_FEATURES: per-hit label-set ids
-    uint64_t fot_cap[2] = {0, 0}, ffeat_cap[2] = {0, 0};
-    int gflags = 0;                              // flags of the last gather
-    bool host_mode = false;                      // the last gather was CRP_NODE_HOST_GATHER: the rows wait on their own devices
-    uint16_t *d_slo16[2] = {nullptr, nullptr};   // staging: the peers' packed positions, slot by slot (each at a multiple of 8)
-    uint32_t *d_sbstart[2] = {nullptr, nullptr};  // and their bucket starts
-    uint64_t slo16_cap[2] = {0, 0}, sbstart_cap[2] = {0, 0};
+    crp::GatherTables tables;  // ONE table per strand and column, contig order; the peers' packed positions slot by slot
+    int gflags = 0;  // flags of the last gather (CRP_NODE_HOST_GATHER: the rows wait on their own devices)
     uint32_t *d_map = nullptr;  // every slot's piece map {begin[], sub[]}, slot after slot
     uint64_t map_cap = 0;
     std::vector<uint32_t> h_map;
@@ -282,22 +274,7 @@ void free_root_side(crp_node *node)
 {
     if (node->root < 0) return;
     (void)hipSetDevice(node->dev[(size_t)node->root].device);
-    for (int s = 0; s < 2; ++s) {
-        (void)hipFree(node->d_fpos[s]);
-        (void)hipFree(node->d_fscore[s]);
-        (void)hipFree(node->d_slo16[s]);
-        (void)hipFree(node->d_sbstart[s]);
-        (void)hipFree(node->d_fot[s]);
-        (void)hipFree(node->d_ffeat[s]);
-        node->d_fot[s] = nullptr;
-        node->d_ffeat[s] = nullptr;
-        node->fot_cap[s] = node->ffeat_cap[s] = 0;
-        node->d_fpos[s] = nullptr;
-        node->d_fscore[s] = nullptr;
-        node->d_slo16[s] = nullptr;
-        node->d_sbstart[s] = nullptr;
-        node->fpos_cap[s] = node->fscore_cap[s] = node->slo16_cap[s] = node->sbstart_cap[s] = 0;
-    }
+    node->tables.free();
     (void)hipFree(node->d_map);
     node->d_map = nullptr;
     node->map_cap = 0;
@@ -521,6 +498,60 @@ std::string timeout_text(const crp_node *node, const char *stage)
     std::snprintf(text, sizeof text, "%s did not complete within %.3g s (CRP_NODE_COLLECTIVE_TIMEOUT_S): the RCCL communicators were aborted", stage,
                   node->collective_timeout_s);
     return text;
+}
+
+// RCCL or not, for a step of `what`.  A device listed twice: RCCL refuses the clique, so it is not even asked -- unless it was
+// asked for by name, which is how the tests put a loop-back double of librccl.so under this very code (and why a one-device
+// node then still creates its communicator).  Where RCCL cannot be had the step goes without (crp_node_transport_note says
+// why; crp_node_gather_stats reports the transport that ran) -- unless it was asked for by name: CRP_ERR_COMM.
+int choose_transport(crp_node *node, int flags, const char *what, bool *use_rccl)
+{
+    *use_rccl = false;
+    const bool by_name = node->transport_env == CRP_TRANSPORT_RCCL;
+    if ((node->duplicates && !by_name && !node->try_rccl) || (flags & CRP_NODE_PEER_COPY) || node->transport_env == CRP_TRANSPORT_PEER_COPY) return CRP_OK;
+    if (node->dev.size() < 2 && !by_name) return CRP_OK;
+    *use_rccl = ensure_comms(node);
+    if (*use_rccl || !by_name) return CRP_OK;
+    node->last_error = std::string(what) + ": RCCL asked for (CRP_NODE_TRANSPORT=rccl) but unavailable: " + node->comms_error;
+    return CRP_ERR_COMM;
+}
+
+// How a bounded wait on a collective ended.  One that ran out: the communicators are aborted and the stage named; unless
+// RCCL was asked for by name, `again` then runs the step once more without RCCL, and its success keeps the message.
+template <class F>
+int after_collective(crp_node *node, int waited, const char *stage, const char *instead, F again)
+{
+    if (waited == WAIT_OK) return CRP_OK;
+    if (waited == WAIT_ERROR) return CRP_ERR_HIP;
+    const std::string why = timeout_text(node, stage);
+    if (!abort_comms(node, why)) return CRP_ERR_COMM;
+    node->last_error = why;
+    if (node->transport_env == CRP_TRANSPORT_RCCL) return CRP_ERR_COMM;
+    node->last_error += instead;
+    const std::string keep = node->last_error;
+    const int rc = again();
+    if (rc == CRP_OK) node->last_error = keep;
+    return rc;
+}
+
+// a group that was refused: nothing of it is on any stream, but the communicators are in an unknown state
+int group_refused(crp_node *node, const char *what, ncclResult_t st)
+{
+    const std::string why = std::string(what) + crp::rccl()->GetErrorString(st);
+    (void)abort_comms(node, why);
+    node->last_error = why;
+    return CRP_ERR_COMM;
+}
+
+// everything queued so far on every device that holds an arena
+int sync_devices(crp_node *node)
+{
+    for (NodeDev &d : node->dev) {
+        if (!d.n_slots) continue;
+        NODE_HIP(node, hipSetDevice(d.device));
+        NODE_HIP(node, hipStreamSynchronize(d.ctx->stream));
+    }
+    return CRP_OK;
 }
 
 }  // namespace
@@ -869,30 +900,26 @@ static int node_scan_score_impl(crp_node *node, int guide_len, int flags, uint64
     return CRP_OK;
 }
 
-static int node_gather_impl(crp_node *node, int root, int flags)
-{
-    crp::Range roctx_range("crp: node gatherv");
-    if (!node || root < 0 || (size_t)root >= node->dev.size() ||
-        (flags & ~(CRP_GATHER_PRE | CRP_GATHER_POS16 | CRP_NODE_PEER_COPY | CRP_GATHER_OFFTARGET | CRP_GATHER_FEATURES | CRP_NODE_HOST_GATHER)))
-        return CRP_ERR_INVALID;
-    if (!node->loaded) return CRP_ERR_STATE;
-    const bool send_pre = (flags & CRP_GATHER_PRE) != 0, pos16 = (flags & CRP_GATHER_POS16) != 0;
-    const bool with_ot = (flags & CRP_GATHER_OFFTARGET) != 0, with_feat = (flags & CRP_GATHER_FEATURES) != 0;
-    const int world = (int)node->dev.size();
-    const std::vector<SlotRef> act = active_slots(node);
-    for (const SlotRef &a : act) {
-        const crp_arena *ar = a.sl->arena;
-        if (!ar->have_hits || (send_pre && !ar->have_pre) || (with_feat && !ar->have_feat) ||
-            (with_ot && (!ar->ctx->ot_solved || ar->ot_epoch != ar->ctx->ot_epoch || !ar->d_ot_cnt[0]))) {
-            node->last_error = "crp_node_gather: logical device " + std::to_string(a.k) + " has no (matching) tables: scan first";
-            return CRP_ERR_STATE;
-        }
-    }
-    node->have_gather = false;
-    const auto t_call = std::chrono::steady_clock::now();
+// ---- crp_node_gather, phase by phase.  What one gather carries from phase to phase (its results go into the node: total,
+// contig_counts, bytes_to_root; none of them is read before have_gather is set again):
+struct Gather {
+    int root;
+    crp::GatherCols cols;
+    std::vector<SlotRef> act;
+    std::vector<uint64_t> soff[2], boff[2];  // per slot: element offsets into the root's staging buffers
+    std::vector<uint64_t> map_off;           // per slot: offset of its begin[] in d_map (sub[] follows)
+    bool rccl = false;                       // the transport: one RCCL group, or the root's pull streams
+    std::chrono::steady_clock::time_point t_call, t_x;
+    NodeDev &R(crp_node *node) const { return node->dev[(size_t)root]; }
+};
 
-    // ---- 1. ownership cuts: per arena and strand, the index of the first row at or after every needle
-    for (const SlotRef &a : act) {
+static inline uint64_t owned_rows(const NodeSlot &sl, int s) { return sl.last[s] - sl.first[s]; }
+
+// ownership cuts: per arena and strand, the index of the first row at or after every needle; from them every slot's
+// owned run, its place in the final tables, and the per-contig counts
+static int gather_cuts(crp_node *node, Gather &g)
+{
+    for (const SlotRef &a : g.act) {
         NodeDev &d = node->dev[(size_t)a.k];
         NodeSlot &sl = *a.sl;
         const uint32_t nn = (uint32_t)(2 * sl.pieces.size());
@@ -901,22 +928,18 @@ static int node_gather_impl(crp_node *node, int root, int flags)
             NODE_HIP(node, crp::launch_lower_bound(d.ctx->stream, sl.arena->d_pos[s], sl.arena->n_hits[s], sl.d_needles, nn, sl.d_bounds + (size_t)s * nn));
         NODE_HIP(node, hipMemcpyAsync(sl.h_bounds, sl.d_bounds, 2 * (size_t)nn * sizeof(uint32_t), hipMemcpyDeviceToHost, d.ctx->stream));
     }
-    for (int k = 0; k < world; ++k) {
-        NodeDev &d = node->dev[(size_t)k];
-        if (!d.n_slots) continue;
-        NODE_HIP(node, hipSetDevice(d.device));
-        NODE_HIP(node, hipStreamSynchronize(d.ctx->stream));
-    }
+    const int rc = sync_devices(node);
+    if (rc != CRP_OK) return rc;
     std::fill(node->contig_counts.begin(), node->contig_counts.end(), 0);
-    uint64_t total[2] = {0, 0};
-    for (const SlotRef &a : act) {
+    node->total[0] = node->total[1] = 0;
+    for (const SlotRef &a : g.act) {
         NodeSlot &sl = *a.sl;
         const size_t np = sl.pieces.size();
         for (int s = 0; s < 2; ++s) {
             const uint32_t *b = sl.h_bounds + (size_t)s * 2 * np;
             sl.first[s] = b[0];
             sl.last[s] = b[2 * np - 1];
-            sl.foff[s] = total[s];
+            sl.foff[s] = node->total[s];
             for (size_t j = 0; j < np; ++j) {
                 // contiguous shares: only an arena's first piece has a left halo and only its last a right one, so its
                 // owned rows are ONE run of each table
@@ -926,119 +949,80 @@ static int node_gather_impl(crp_node *node, int root, int flags)
                 }
                 node->contig_counts[2 * node->pieces[sl.pieces[j]].contig + (size_t)s] += b[2 * j + 1] - b[2 * j];
             }
-            total[s] += sl.last[s] - sl.first[s];
+            node->total[s] += owned_rows(sl, s);
         }
     }
+    return CRP_OK;
+}
 
-    // ---- CRP_NODE_HOST_GATHER: nothing crosses xGMI.  Every device rebases the positions of its owned rows where they
-    // lie; crp_node_fetch then pulls every device's rows over that device's OWN PCIe link straight into their place in the
-    // caller's arrays -- N links instead of the root's one, for a consumer that lives on the host (the CSV writer).
-    if (flags & CRP_NODE_HOST_GATHER) {
-        const auto t_x = std::chrono::steady_clock::now();
-        for (const SlotRef &a : act) {
-            NodeDev &d = node->dev[(size_t)a.k];
-            NodeSlot &sl = *a.sl;
-            crp_ctx *ctx = d.ctx;
-            NODE_HIP(node, hipSetDevice(d.device));
-            const size_t np = sl.pieces.size();
-            for (int s = 0; s < 2; ++s) {
-                const uint64_t n = sl.last[s] - sl.first[s];
-                const int rc = crp::grow(ctx, reinterpret_cast<void **>(&sl.d_lpos[s]), &sl.lpos_cap[s], n, sizeof(uint32_t));
-                if (rc != CRP_OK) return dev_fail(node, a.k, rc, "crp_node_gather (rebased positions)");
-                NODE_HIP(node, crp::launch_pos_rebase(ctx->stream, sl.arena->d_pos[s] + sl.first[s], n,
-                                                      crp::PieceMap{sl.d_map_self, sl.d_map_self + np, (uint32_t)np}, sl.d_lpos[s]));
-            }
+// CRP_NODE_HOST_GATHER: nothing crosses xGMI.  Every device rebases the positions of its owned rows where they lie;
+// crp_node_fetch then pulls every device's rows over that device's OWN PCIe link straight into their place in the
+// caller's arrays -- N links instead of the root's one, for a consumer that lives on the host (the CSV writer).
+static int gather_on_hosts(crp_node *node, Gather &g)
+{
+    g.t_x = std::chrono::steady_clock::now();
+    node->bytes_to_root = 0;
+    for (const SlotRef &a : g.act) {
+        NodeDev &d = node->dev[(size_t)a.k];
+        NodeSlot &sl = *a.sl;
+        crp_ctx *ctx = d.ctx;
+        NODE_HIP(node, hipSetDevice(d.device));
+        const size_t np = sl.pieces.size();
+        for (int s = 0; s < 2; ++s) {
+            const uint64_t n = owned_rows(sl, s);
+            const int rc = crp::grow(ctx, reinterpret_cast<void **>(&sl.d_lpos[s]), &sl.lpos_cap[s], n, sizeof(uint32_t));
+            if (rc != CRP_OK) return dev_fail(node, a.k, rc, "crp_node_gather (rebased positions)");
+            NODE_HIP(node, crp::launch_pos_rebase(ctx->stream, sl.arena->d_pos[s] + sl.first[s], n,
+                                                  crp::PieceMap{sl.d_map_self, sl.d_map_self + np, (uint32_t)np}, sl.d_lpos[s]));
         }
-        for (int k = 0; k < world; ++k) {
-            NodeDev &d = node->dev[(size_t)k];
-            if (!d.n_slots) continue;
-            NODE_HIP(node, hipSetDevice(d.device));
-            NODE_HIP(node, hipStreamSynchronize(d.ctx->stream));
-        }
-        node->ms_exchange = ms_since(t_x);
-        node->ms_total = ms_since(t_call);
-        node->bytes_to_root = 0;
-        node->transport = CRP_TRANSPORT_HOST_LINKS;
-        node->total[0] = total[0];
-        node->total[1] = total[1];
-        node->gflags = flags;
-        node->host_mode = true;
-        node->have_gather = true;
-        return CRP_OK;
     }
-    node->host_mode = false;
+    return sync_devices(node);
+}
 
-    // ---- 2. transport, and the root's side: final tables, staging, piece maps
-    // (a device listed twice: RCCL refuses the clique, so it is not even asked -- unless it was asked for by name, which is
-    // how the tests put a loop-back double of librccl.so under this very code)
-    bool peer_copy = (node->duplicates && node->transport_env != CRP_TRANSPORT_RCCL && !node->try_rccl) || (flags & CRP_NODE_PEER_COPY) ||
-                     node->transport_env == CRP_TRANSPORT_PEER_COPY;
-    // (a one-device node has no peer; CRP_NODE_TRANSPORT=rccl still creates its communicator, for tests of the RCCL path)
-    const bool want_comms = !peer_copy && (world > 1 || node->transport_env == CRP_TRANSPORT_RCCL);
-    if (want_comms && !ensure_comms(node)) {
-        if (node->transport_env == CRP_TRANSPORT_RCCL) {
-            node->last_error = "crp_node_gather: RCCL asked for (CRP_NODE_TRANSPORT=rccl) but unavailable: " + node->comms_error;
-            return CRP_ERR_COMM;
-        }
-        peer_copy = true;  // (crp_node_gather_stats reports the transport that ran; crp_node_transport_note says why)
-    }
-    if (node->root != root) free_root_side(node);
-    node->root = root;
-    NodeDev &R = node->dev[(size_t)root];
-    crp_ctx *rctx = R.ctx;
-    NODE_HIP(node, hipSetDevice(R.device));
-    const size_t n_act = act.size();
-    std::vector<uint64_t> soff[2], boff[2];  // per slot: element offsets into the staging buffers
+// the root's side: final tables, staging, piece maps, pull streams.  The exchange is timed from its end.
+static int gather_reserve_root(crp_node *node, Gather &g)
+{
+    const int world = (int)node->dev.size();
+    if (node->root != g.root) free_root_side(node);
+    node->root = g.root;
+    crp_ctx *rctx = g.R(node).ctx;
+    NODE_HIP(node, hipSetDevice(rctx->device));
+    uint64_t lo_total[2] = {0, 0}, b_total[2] = {0, 0};
     for (int s = 0; s < 2; ++s) {
-        soff[s].assign(n_act, 0);
-        boff[s].assign(n_act, 0);
-        uint64_t lo_total = 0, b_total = 0;
-        for (const SlotRef &a : act) {
-            if (a.k == root || !pos16) continue;
-            soff[s][a.flat] = lo_total;
-            boff[s][a.flat] = b_total;
-            lo_total += round_up8(a.sl->last[s] - a.sl->first[s]);
-            b_total += a.sl->n_buckets;
+        g.soff[s].assign(g.act.size(), 0);
+        g.boff[s].assign(g.act.size(), 0);
+        for (const SlotRef &a : g.act) {
+            if (a.k == g.root || !g.cols.pos16) continue;
+            g.soff[s][a.flat] = lo_total[s];
+            g.boff[s][a.flat] = b_total[s];
+            lo_total[s] += round_up8(owned_rows(*a.sl, s));
+            b_total[s] += a.sl->n_buckets;
         }
-        int rc = crp::grow(rctx, reinterpret_cast<void **>(&node->d_fpos[s]), &node->fpos_cap[s], total[s], sizeof(uint32_t));
-        if (rc == CRP_OK) rc = crp::grow(rctx, reinterpret_cast<void **>(&node->d_fscore[s]), &node->fscore_cap[s], total[s], sizeof(double));
-        if (rc == CRP_OK && with_ot) rc = crp::grow(rctx, reinterpret_cast<void **>(&node->d_fot[s]), &node->fot_cap[s], total[s], sizeof(uint4));
-        if (rc == CRP_OK && with_feat) rc = crp::grow(rctx, reinterpret_cast<void **>(&node->d_ffeat[s]), &node->ffeat_cap[s], total[s], sizeof(uint32_t));
-        if (rc == CRP_OK && lo_total) rc = crp::grow(rctx, reinterpret_cast<void **>(&node->d_slo16[s]), &node->slo16_cap[s], lo_total, sizeof(uint16_t));
-        if (rc == CRP_OK && b_total) rc = crp::grow(rctx, reinterpret_cast<void **>(&node->d_sbstart[s]), &node->sbstart_cap[s], b_total, sizeof(uint32_t));
-        if (rc != CRP_OK) return dev_fail(node, root, rc, "crp_node_gather (root's tables)");
     }
-    std::vector<uint64_t> map_off(n_act, 0);  // per slot: offset of its begin[] in d_map (sub[] follows)
-    {   // piece maps: begin[] and sub[] per slot, one upload
-        node->h_map.clear();
-        for (const SlotRef &a : act) {
-            map_off[a.flat] = node->h_map.size();
+    int rc = node->tables.reserve(rctx, node->total, lo_total, b_total, g.cols);
+    if (rc != CRP_OK) return dev_fail(node, g.root, rc, "crp_node_gather (root's tables)");
+    // piece maps: begin[] and sub[] per slot, one upload
+    g.map_off.assign(g.act.size(), 0);
+    node->h_map.clear();
+    for (const SlotRef &a : g.act) {
+        g.map_off[a.flat] = node->h_map.size();
+        for (int sub = 0; sub < 2; ++sub)
             for (uint32_t q : a.sl->pieces) {
                 const NodePiece &p = node->pieces[q];
-                node->h_map.push_back((uint32_t)(p.arena_off + (p.start - p.text_lo)));
+                node->h_map.push_back((uint32_t)(p.arena_off + (p.start - p.text_lo) - (sub ? p.start : 0)));  // (mod 2^32)
             }
-            for (uint32_t q : a.sl->pieces) {
-                const NodePiece &p = node->pieces[q];
-                node->h_map.push_back((uint32_t)(p.arena_off + (p.start - p.text_lo) - p.start));  // (mod 2^32)
-            }
-        }
-        int rc = crp::grow(rctx, reinterpret_cast<void **>(&node->d_map), &node->map_cap, node->h_map.size(), sizeof(uint32_t));
-        if (rc != CRP_OK) return dev_fail(node, root, rc, "crp_node_gather (piece maps)");
-        if (!node->h_map.empty())
-            NODE_HIP(node, hipMemcpyAsync(node->d_map, node->h_map.data(), node->h_map.size() * sizeof(uint32_t), hipMemcpyHostToDevice,
-                                          rctx->stream));
     }
-    auto map_of = [&](const SlotRef &a) {
-        const size_t np = a.sl->pieces.size();
-        return crp::PieceMap{node->d_map + map_off[a.flat], node->d_map + map_off[a.flat] + np, (uint32_t)np};
-    };
-    if (peer_copy && node->pull.size() != (size_t)world) {
+    rc = crp::grow(rctx, reinterpret_cast<void **>(&node->d_map), &node->map_cap, node->h_map.size(), sizeof(uint32_t));
+    if (rc != CRP_OK) return dev_fail(node, g.root, rc, "crp_node_gather (piece maps)");
+    if (!node->h_map.empty())
+        NODE_HIP(node, hipMemcpyAsync(node->d_map, node->h_map.data(), node->h_map.size() * sizeof(uint32_t), hipMemcpyHostToDevice, rctx->stream));
+    if (!g.rccl && node->pull.size() != (size_t)world) {
         free_pull_streams(node);
         node->pull.assign((size_t)world, nullptr);
         node->pulled.assign((size_t)world, nullptr);
         hipError_t e = hipSuccess;
         for (int k = 0; k < world && e == hipSuccess; ++k) {
-            if (k == root) continue;
+            if (k == g.root) continue;
             e = hipStreamCreateWithFlags(&node->pull[(size_t)k], hipStreamNonBlocking);
             if (e == hipSuccess) e = hipEventCreateWithFlags(&node->pulled[(size_t)k], hipEventDisableTiming);
         }
@@ -1049,17 +1033,21 @@ static int node_gather_impl(crp_node *node, int root, int flags)
         }
     }
     NODE_HIP(node, hipStreamSynchronize(rctx->stream));  // (the maps are in place; the exchange is timed from here)
-    const auto t_x = std::chrono::steady_clock::now();
+    g.t_x = std::chrono::steady_clock::now();
+    return CRP_OK;
+}
 
-    // ---- 3. the peers' side: pack the positions of the owned rows
-    for (const SlotRef &a : act) {
-        if (a.k == root || !pos16) continue;
+// the peers' side: pack the positions of the owned rows; a peer's pull stream starts once the peer's side is in place
+static int gather_pack_peers(crp_node *node, const Gather &g)
+{
+    for (const SlotRef &a : g.act) {
+        if (a.k == g.root || !g.cols.pos16) continue;
         NodeDev &d = node->dev[(size_t)a.k];
         NodeSlot &sl = *a.sl;
         crp_ctx *ctx = d.ctx;
         NODE_HIP(node, hipSetDevice(d.device));
         for (int s = 0; s < 2; ++s) {
-            const uint64_t n = sl.last[s] - sl.first[s];
+            const uint64_t n = owned_rows(sl, s);
             int rc = crp::grow(ctx, reinterpret_cast<void **>(&sl.d_lo16[s]), &sl.lo16_cap[s], round_up8(n), sizeof(uint16_t));
             if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&sl.d_bstart[s]), &sl.bstart_cap[s], sl.n_buckets, sizeof(uint32_t));
             if (rc != CRP_OK) return dev_fail(node, a.k, rc, "crp_node_gather (packed positions)");
@@ -1068,138 +1056,152 @@ static int node_gather_impl(crp_node *node, int root, int flags)
             NODE_HIP(node, crp::launch_pos16_pack(ctx->stream, sl.arena->d_pos[s] + sl.first[s], n, sl.d_lo16[s]));
         }
     }
-    if (peer_copy)
-        for (int k = 0; k < world; ++k) {
-            NodeDev &d = node->dev[(size_t)k];
-            if (k == root || !d.n_slots) continue;
-            NODE_HIP(node, hipSetDevice(d.device));
-            NODE_HIP(node, hipEventRecord(d.ready, d.ctx->stream));
-            // this peer's pull stream starts once the peer's side is in place
-            NODE_HIP(node, hipSetDevice(R.device));
-            NODE_HIP(node, hipStreamWaitEvent(node->pull[(size_t)k], d.ready, 0));
-        }
+    for (size_t k = 0; k < node->dev.size() && !g.rccl; ++k) {
+        NodeDev &d = node->dev[k];
+        if ((int)k == g.root || !d.n_slots) continue;
+        NODE_HIP(node, hipSetDevice(d.device));
+        NODE_HIP(node, hipEventRecord(d.ready, d.ctx->stream));
+        NODE_HIP(node, hipSetDevice(g.R(node).device));
+        NODE_HIP(node, hipStreamWaitEvent(node->pull[k], d.ready, 0));
+    }
+    return CRP_OK;
+}
 
-    // ---- 4. the exchange
-    uint64_t moved = 0;
-    const crp::Rccl *r = (want_comms && !peer_copy) ? crp::rccl() : nullptr;
+// the exchange: every message of every peer's strands (crp::wire_msgs) as a send/recv pair inside ONE RCCL group, or as a
+// copy on the root's pull stream for that peer
+static int gather_exchange(crp_node *node, Gather &g)
+{
+    NodeDev &R = g.R(node);
+    crp_ctx *rctx = R.ctx;
+    const crp::Rccl *r = g.rccl ? crp::rccl() : nullptr;
     ncclResult_t st = ncclSuccess, st_end = ncclSuccess;
     int miscount = r ? node->test_miscount : 0;
+    node->bytes_to_root = 0;
     if (r) st = r->GroupStart();
-    for (const SlotRef &a : act) {
+    for (const SlotRef &a : g.act) {
         if (st != ncclSuccess) break;
-        if (a.k == root) continue;
+        if (a.k == g.root) continue;
         NodeDev &d = node->dev[(size_t)a.k];
         NodeSlot &sl = *a.sl;
         for (int s = 0; s < 2 && st == ncclSuccess; ++s) {
-            const uint64_t n = sl.last[s] - sl.first[s];
-            if (!n) continue;
-            // packed positions + bucket starts (or raw positions), the f64 column, and the two optional ones
-            struct Col {
-                const void *src;
-                void *dst;
-                uint64_t bytes;
-            } cols[5];
-            int nc = 0;
-            if (pos16) {
-                cols[nc++] = Col{sl.d_lo16[s], node->d_slo16[s] + soff[s][a.flat], n * sizeof(uint16_t)};
-                cols[nc++] = Col{sl.d_bstart[s], node->d_sbstart[s] + boff[s][a.flat], (uint64_t)sl.n_buckets * sizeof(uint32_t)};
-            } else {
-                cols[nc++] = Col{sl.arena->d_pos[s] + sl.first[s], node->d_fpos[s] + sl.foff[s], n * sizeof(uint32_t)};
-            }
-            cols[nc++] = Col{(send_pre ? sl.arena->d_pre[s] : sl.arena->d_score[s]) + sl.first[s], node->d_fscore[s] + sl.foff[s], n * sizeof(double)};
-            if (with_ot) cols[nc++] = Col{sl.arena->d_ot_cnt[s] + sl.first[s], node->d_fot[s] + sl.foff[s], n * sizeof(uint4)};
-            if (with_feat) cols[nc++] = Col{sl.arena->d_feat[s] + sl.first[s], node->d_ffeat[s] + sl.foff[s], n * sizeof(uint32_t)};
-            for (int c = 0; c < nc && st == ncclSuccess; ++c) {
-                moved += cols[c].bytes;
+            const crp::GatherSrc src{sl.arena, sl.first[s], sl.d_lo16[s], sl.d_bstart[s]};
+            const crp::GatherDst dst{&node->tables, sl.foff[s], g.soff[s][a.flat], g.boff[s][a.flat]};
+            crp::WireMsg msg[crp::MAX_WIRE_MSGS];
+            const int nm = crp::wire_msgs(g.cols, s, owned_rows(sl, s), sl.n_buckets, &src, &dst, msg);
+            for (int m = 0; m < nm && st == ncclSuccess; ++m) {
+                node->bytes_to_root += msg[m].bytes;
                 if (r) {
-                    uint64_t expect = cols[c].bytes;
+                    uint64_t expect = msg[m].bytes;
                     if (miscount && expect > 8) {  // test hook (CRP_TEST_NODE_MISCOUNT): ONE receive of this gather is posted 8 bytes short
                         expect -= 8;
                         miscount = 0;
                     }
-                    st = r->Send(cols[c].src, cols[c].bytes, ncclUint8, root, node->comms[(size_t)a.k], d.ctx->stream);
-                    if (st == ncclSuccess) st = r->Recv(cols[c].dst, expect, ncclUint8, a.k, node->comms[(size_t)root], rctx->stream);
+                    st = r->Send(msg[m].src, msg[m].bytes, ncclUint8, g.root, node->comms[(size_t)a.k], d.ctx->stream);
+                    if (st == ncclSuccess) st = r->Recv(msg[m].dst, expect, ncclUint8, a.k, node->comms[(size_t)g.root], rctx->stream);
                 } else {
-                    hipStream_t ps = node->pull[(size_t)a.k];
                     NODE_HIP(node, hipSetDevice(R.device));
                     if (d.device == R.device)
-                        NODE_HIP(node, hipMemcpyAsync(cols[c].dst, cols[c].src, cols[c].bytes, hipMemcpyDeviceToDevice, ps));
+                        NODE_HIP(node, hipMemcpyAsync(msg[m].dst, msg[m].src, msg[m].bytes, hipMemcpyDeviceToDevice, node->pull[(size_t)a.k]));
                     else
-                        NODE_HIP(node, hipMemcpyPeerAsync(cols[c].dst, R.device, cols[c].src, d.device, cols[c].bytes, ps));
+                        NODE_HIP(node, hipMemcpyPeerAsync(msg[m].dst, R.device, msg[m].src, d.device, msg[m].bytes, node->pull[(size_t)a.k]));
                 }
             }
         }
     }
     if (r) st_end = r->GroupEnd();
-    if (st != ncclSuccess || st_end != ncclSuccess) {
-        // the group was refused: nothing of it is on any stream, but the communicators are in an unknown state
-        const std::string why = std::string("crp_node_gather send/recv: ") + r->GetErrorString(st != ncclSuccess ? st : st_end);
-        (void)abort_comms(node, why);
-        node->last_error = why;
-        return CRP_ERR_COMM;
+    if (st != ncclSuccess || st_end != ncclSuccess) return group_refused(node, "crp_node_gather send/recv: ", st != ncclSuccess ? st : st_end);
+    for (size_t k = 0; k < node->dev.size() && !r; ++k) {  // the root's stream goes on once every peer's rows have landed
+        if ((int)k == g.root || !node->dev[k].n_slots) continue;
+        NODE_HIP(node, hipSetDevice(R.device));
+        NODE_HIP(node, hipEventRecord(node->pulled[k], node->pull[k]));
+        NODE_HIP(node, hipStreamWaitEvent(rctx->stream, node->pulled[k], 0));
     }
-    if (!r)
-        for (int k = 0; k < world; ++k) {  // the root's stream goes on once every peer's rows have landed
-            if (k == root || !node->dev[(size_t)k].n_slots) continue;
-            NODE_HIP(node, hipSetDevice(R.device));
-            NODE_HIP(node, hipEventRecord(node->pulled[(size_t)k], node->pull[(size_t)k]));
-            NODE_HIP(node, hipStreamWaitEvent(rctx->stream, node->pulled[(size_t)k], 0));
-        }
+    return CRP_OK;
+}
 
-    // ---- 5. the root's side: expand / rebase into the final tables (its own rows never cross a link)
-    NODE_HIP(node, hipSetDevice(R.device));
-    for (const SlotRef &a : act) {
+// the root's side: expand / rebase into the final tables (its own rows never cross a link)
+static int gather_expand(crp_node *node, const Gather &g)
+{
+    crp_ctx *rctx = g.R(node).ctx;
+    NODE_HIP(node, hipSetDevice(rctx->device));
+    for (const SlotRef &a : g.act) {
         NodeSlot &sl = *a.sl;
+        const size_t np = sl.pieces.size();
+        const crp::PieceMap map{node->d_map + g.map_off[a.flat], node->d_map + g.map_off[a.flat] + np, (uint32_t)np};
         for (int s = 0; s < 2; ++s) {
-            const uint64_t n = sl.last[s] - sl.first[s];
+            const uint64_t n = owned_rows(sl, s);
             if (!n) continue;
-            uint32_t *out = node->d_fpos[s] + sl.foff[s];
-            if (a.k == root) {
-                NODE_HIP(node, crp::launch_pos_rebase(rctx->stream, sl.arena->d_pos[s] + sl.first[s], n, map_of(a), out));
-                NODE_HIP(node, hipMemcpyAsync(node->d_fscore[s] + sl.foff[s], (send_pre ? sl.arena->d_pre[s] : sl.arena->d_score[s]) + sl.first[s],
-                                              n * sizeof(double), hipMemcpyDeviceToDevice, rctx->stream));
-                if (with_ot)
-                    NODE_HIP(node, hipMemcpyAsync(node->d_fot[s] + sl.foff[s], sl.arena->d_ot_cnt[s] + sl.first[s], n * sizeof(uint4),
-                                                  hipMemcpyDeviceToDevice, rctx->stream));
-                if (with_feat)
-                    NODE_HIP(node, hipMemcpyAsync(node->d_ffeat[s] + sl.foff[s], sl.arena->d_feat[s] + sl.first[s], n * sizeof(uint32_t),
-                                                  hipMemcpyDeviceToDevice, rctx->stream));
-            } else if (pos16) {
-                NODE_HIP(node, crp::launch_pos16_expand(rctx->stream, node->d_slo16[s] + soff[s][a.flat], n,
-                                                        node->d_sbstart[s] + boff[s][a.flat], sl.n_buckets, map_of(a), out));
+            uint32_t *out = reinterpret_cast<uint32_t *>(node->tables.at(crp::COL_POS, s, sl.foff[s]));
+            if (a.k == g.root) {
+                NODE_HIP(node, crp::launch_pos_rebase(rctx->stream, sl.arena->d_pos[s] + sl.first[s], n, map, out));
+                for (int i = 0; i < g.cols.n; ++i) {
+                    const int c = g.cols.col[i];
+                    if (c != crp::COL_POS)
+                        NODE_HIP(node, hipMemcpyAsync(node->tables.at(c, s, sl.foff[s]), crp::col_src(g.cols, c, sl.arena, s, sl.first[s]),
+                                                      n * crp::COL_BYTES[c], hipMemcpyDeviceToDevice, rctx->stream));
+                }
+            } else if (g.cols.pos16) {
+                NODE_HIP(node, crp::launch_pos16_expand(rctx->stream, node->tables.d_lo16[s] + g.soff[s][a.flat], n,
+                                                        node->tables.d_bstart[s] + g.boff[s][a.flat], sl.n_buckets, map, out));
             } else {
-                NODE_HIP(node, crp::launch_pos_rebase(rctx->stream, out, n, map_of(a), out));  // in place: a thread rewrites the rows it read
+                NODE_HIP(node, crp::launch_pos_rebase(rctx->stream, out, n, map, out));  // in place: a thread rewrites the rows it read
             }
         }
     }
+    return CRP_OK;
+}
+
+// the rows to the root over g's transport.  A grouped send/recv that does not complete in time is given up, and the rows
+// move once more as device-to-device copies, everything sized and queued afresh.
+static int gather_to_root(crp_node *node, Gather &g)
+{
+    int rc = gather_reserve_root(node, g);
+    if (rc == CRP_OK) rc = gather_pack_peers(node, g);
+    if (rc == CRP_OK) rc = gather_exchange(node, g);
+    if (rc == CRP_OK) rc = gather_expand(node, g);
+    if (rc != CRP_OK) return rc;
     // the receives, then the sends (they read the peers' tables: they must have left before the next scan) -- on RCCL every
     // wait has a bound
-    const double bound = r ? node->collective_timeout_s : 0.0;
-    int waited = wait_bounded(node, R, rctx->stream, bound);
-    for (int k = 0; k < world && waited == WAIT_OK; ++k) {
-        NodeDev &d = node->dev[(size_t)k];
-        if (k == root || !d.n_slots) continue;
-        waited = wait_bounded(node, d, d.ctx->stream, bound);
+    const double bound = g.rccl ? node->collective_timeout_s : 0.0;
+    int waited = wait_bounded(node, g.R(node), g.R(node).ctx->stream, bound);
+    for (size_t k = 0; k < node->dev.size() && waited == WAIT_OK; ++k) {
+        NodeDev &d = node->dev[k];
+        if ((int)k != g.root && d.n_slots) waited = wait_bounded(node, d, d.ctx->stream, bound);
     }
-    if (waited == WAIT_ERROR) return CRP_ERR_HIP;
-    if (waited == WAIT_TIMEOUT) {
-        const std::string why = timeout_text(node, "crp_node_gather: the grouped send/recv");
-        if (!abort_comms(node, why)) return CRP_ERR_COMM;
-        node->last_error = why;
-        if (node->transport_env == CRP_TRANSPORT_RCCL) return CRP_ERR_COMM;
-        // not asked for by name: the same call once more, as device-to-device copies, everything sized and queued afresh
-        node->last_error += "; device-to-device copies used instead";
-        const std::string keep = node->last_error;
-        const int rc = node_gather_impl(node, root, flags | CRP_NODE_PEER_COPY);
-        if (rc == CRP_OK) node->last_error = keep;
-        return rc;
-    }
-    node->ms_exchange = ms_since(t_x);
-    node->ms_total = ms_since(t_call);
-    node->bytes_to_root = moved;
-    node->transport = r ? CRP_TRANSPORT_RCCL : (world == 1 ? 0 : CRP_TRANSPORT_PEER_COPY);
-    node->total[0] = total[0];
-    node->total[1] = total[1];
+    return after_collective(node, waited, "crp_node_gather: the grouped send/recv", "; device-to-device copies used instead", [&] {
+        g.rccl = false;
+        g.t_call = std::chrono::steady_clock::now();
+        return gather_to_root(node, g);
+    });
+}
+
+static int node_gather_impl(crp_node *node, int root, int flags)
+{
+    crp::Range roctx_range("crp: node gatherv");
+    if (!node || root < 0 || (size_t)root >= node->dev.size() ||
+        (flags & ~(CRP_GATHER_PRE | CRP_GATHER_POS16 | CRP_NODE_PEER_COPY | CRP_GATHER_OFFTARGET | CRP_GATHER_FEATURES | CRP_NODE_HOST_GATHER)))
+        return CRP_ERR_INVALID;
+    if (!node->loaded) return CRP_ERR_STATE;
+    Gather g;
+    g.root = root;
+    g.cols = crp::gather_cols(flags);
+    g.act = active_slots(node);
+    for (const SlotRef &a : g.act)
+        if (!crp::tables_present(g.cols, a.sl->arena)) {
+            node->last_error = "crp_node_gather: logical device " + std::to_string(a.k) + " has no (matching) tables: scan first";
+            return CRP_ERR_STATE;
+        }
+    node->have_gather = false;
+    g.t_call = std::chrono::steady_clock::now();
+    int rc = gather_cuts(node, g);
+    const bool on_hosts = (flags & CRP_NODE_HOST_GATHER) != 0;
+    if (rc == CRP_OK && on_hosts) rc = gather_on_hosts(node, g);
+    if (rc == CRP_OK && !on_hosts) rc = choose_transport(node, flags, "crp_node_gather", &g.rccl);
+    if (rc == CRP_OK && !on_hosts) rc = gather_to_root(node, g);
+    if (rc != CRP_OK) return rc;
+    node->ms_exchange = ms_since(g.t_x);
+    node->ms_total = ms_since(g.t_call);
+    node->transport = on_hosts ? CRP_TRANSPORT_HOST_LINKS : g.rccl ? CRP_TRANSPORT_RCCL : (node->dev.size() == 1 ? 0 : CRP_TRANSPORT_PEER_COPY);
     node->gflags = flags;
     node->have_gather = true;
     return CRP_OK;
@@ -1243,15 +1245,10 @@ static int node_offtarget_impl(crp_node *node, int guide_len, uint64_t *n_sites)
     if (rc != CRP_OK) return rc;
     // 2. the histograms summed over the devices: RCCL all-reduce in one group, or through the first device
     if (world > 1) {
-        bool peer_copy = (node->duplicates && node->transport_env != CRP_TRANSPORT_RCCL && !node->try_rccl) || node->transport_env == CRP_TRANSPORT_PEER_COPY;
-        if (!peer_copy && !ensure_comms(node)) {
-            if (node->transport_env == CRP_TRANSPORT_RCCL) {
-                node->last_error = "crp_node_offtarget: RCCL asked for (CRP_NODE_TRANSPORT=rccl) but unavailable: " + node->comms_error;
-                return CRP_ERR_COMM;
-            }
-            peer_copy = true;
-        }
-        if (!peer_copy) {
+        bool use_rccl = false;
+        rc = choose_transport(node, 0, "crp_node_offtarget", &use_rccl);
+        if (rc != CRP_OK) return rc;
+        if (use_rccl) {
             const crp::Rccl *r = crp::rccl();
             ncclResult_t st = r->GroupStart();
             for (int k = 0; k < world && st == ncclSuccess; ++k) {
@@ -1259,27 +1256,13 @@ static int node_offtarget_impl(crp_node *node, int guide_len, uint64_t *n_sites)
                 st = r->AllReduce(ctx->d_ot_hist, ctx->d_ot_hist, crp::OT_HIST_ENTRIES, ncclUint32, ncclSum, node->comms[(size_t)k], ctx->stream);
             }
             const ncclResult_t st_end = r->GroupEnd();
-            if (st != ncclSuccess || st_end != ncclSuccess) {
-                const std::string why = std::string("crp_node_offtarget all-reduce: ") + r->GetErrorString(st != ncclSuccess ? st : st_end);
-                (void)abort_comms(node, why);
-                node->last_error = why;
-                return CRP_ERR_COMM;
-            }
+            if (st != ncclSuccess || st_end != ncclSuccess) return group_refused(node, "crp_node_offtarget all-reduce: ", st != ncclSuccess ? st : st_end);
             int waited = WAIT_OK;
             for (int k = 0; k < world && waited == WAIT_OK; ++k) waited = wait_bounded(node, node->dev[(size_t)k], node->dev[(size_t)k].ctx->stream, node->collective_timeout_s);
-            if (waited == WAIT_ERROR) return CRP_ERR_HIP;
-            if (waited == WAIT_TIMEOUT) {
-                const std::string why = timeout_text(node, "crp_node_offtarget: the histogram all-reduce");
-                if (!abort_comms(node, why)) return CRP_ERR_COMM;
-                node->last_error = why;
-                if (node->transport_env == CRP_TRANSPORT_RCCL) return CRP_ERR_COMM;
-                // the histograms may be half summed: the whole step once more (reset, sites, sum through device 0)
-                node->last_error += "; the histograms are summed through device 0 instead";
-                const std::string keep = node->last_error;
-                const int rc2 = node_offtarget_impl(node, guide_len, n_sites);
-                if (rc2 == CRP_OK) node->last_error = keep;
-                return rc2;
-            }
+            // (the histograms may be half summed: the whole step once more -- reset, sites, sum through device 0)
+            if (waited != WAIT_OK)
+                return after_collective(node, waited, "crp_node_offtarget: the histogram all-reduce", "; the histograms are summed through device 0 instead",
+                                        [&] { return node_offtarget_impl(node, guide_len, n_sites); });
         } else {
             // device 0 collects: every other histogram is copied beside its own and added, then the sum goes back.  A device
             // without an arena has only QUEUED the zeroing of its histogram (crp_offtarget_reset): wait for every stream first
@@ -1363,68 +1346,49 @@ static int node_annotate_impl(crp_node *node, const crp_annotation *annotation, 
     });
 }
 
-static int node_fetch_offtarget_impl(crp_node *node, uint32_t *ot_plus, uint32_t *ot_minus)
+// Columns of the last gather to the caller's arrays: out of the root's tables, or (CRP_NODE_HOST_GATHER) every device's
+// owned rows over ITS link into their place, one host thread per device.
+static int fetch_cols(crp_node *node, const crp::HostCol *want, int n_want, const char *what)
 {
-    if (!node) return CRP_ERR_INVALID;
-    if (!node->have_gather || !(node->gflags & CRP_GATHER_OFFTARGET)) return CRP_ERR_STATE;
-    if (node->host_mode) {
-        uint32_t *h[2] = {ot_plus, ot_minus};
-        return on_every_device(node, "crp_node_fetch_offtarget (host gather)", [&](int k) {
+    if (node->gflags & CRP_NODE_HOST_GATHER) {
+        const crp::GatherCols cols = crp::gather_cols(node->gflags);
+        return on_every_device(node, (std::string(what) + " (host gather)").c_str(), [&](int k) {
             NodeDev &d = node->dev[(size_t)k];
             for (size_t j = 0; j < d.n_slots; ++j) {
                 NodeSlot &sl = *d.slots[j];
-                for (int s = 0; s < 2; ++s) {
-                    const uint64_t n = sl.last[s] - sl.first[s];
-                    if (!n || !h[s]) continue;
-                    const int rc = crp::staged_d2h(d.ctx, h[s] + 4 * sl.foff[s], sl.arena->d_ot_cnt[s] + sl.first[s], n * sizeof(uint4));
-                    if (rc != CRP_OK) return rc;
-                }
+                for (int s = 0; s < 2; ++s)
+                    for (int i = 0; i < n_want; ++i) {
+                        const int c = want[i].col;
+                        const uint64_t n = owned_rows(sl, s);
+                        if (!n || !want[i].host[s]) continue;
+                        // (the positions of a host gather: rebased where they lie, gather_on_hosts)
+                        const void *src = c == crp::COL_POS ? (const void *)sl.d_lpos[s] : crp::col_src(cols, c, sl.arena, s, sl.first[s]);
+                        const int rc = crp::staged_d2h(d.ctx, static_cast<char *>(want[i].host[s]) + sl.foff[s] * crp::COL_BYTES[c], src, n * crp::COL_BYTES[c]);
+                        if (rc != CRP_OK) return rc;
+                    }
             }
             return crp_synchronize(d.ctx);
         });
     }
     crp_ctx *ctx = node->dev[(size_t)node->root].ctx;
     NODE_HIP(node, hipSetDevice(ctx->device));
-    uint32_t *h[2] = {ot_plus, ot_minus};
     for (int s = 0; s < 2; ++s)
-        if (h[s] && node->total[s]) {
-            const int rc = crp::staged_d2h(ctx, h[s], node->d_fot[s], node->total[s] * sizeof(uint4));
-            if (rc != CRP_OK) return dev_fail(node, node->root, rc, "crp_node_fetch_offtarget");
+        for (int i = 0; i < n_want; ++i) {
+            if (!want[i].host[s] || !node->total[s]) continue;
+            const int rc = crp::staged_d2h(ctx, want[i].host[s], node->tables.d_col[s][want[i].col], node->total[s] * crp::COL_BYTES[want[i].col]);
+            if (rc != CRP_OK) return dev_fail(node, node->root, rc, what);
         }
     NODE_HIP(node, hipStreamSynchronize(ctx->stream));
     return CRP_OK;
 }
 
-static int node_fetch_features_impl(crp_node *node, uint32_t *feat_plus, uint32_t *feat_minus)
+// the optional column that `flag` brought into the last gather
+static int node_fetch_optional_impl(crp_node *node, int col, int flag, const char *what, uint32_t *plus, uint32_t *minus)
 {
     if (!node) return CRP_ERR_INVALID;
-    if (!node->have_gather || !(node->gflags & CRP_GATHER_FEATURES)) return CRP_ERR_STATE;
-    if (node->host_mode) {
-        uint32_t *h[2] = {feat_plus, feat_minus};
-        return on_every_device(node, "crp_node_fetch_features (host gather)", [&](int k) {
-            NodeDev &d = node->dev[(size_t)k];
-            for (size_t j = 0; j < d.n_slots; ++j) {
-                NodeSlot &sl = *d.slots[j];
-                for (int s = 0; s < 2; ++s) {
-                    const uint64_t n = sl.last[s] - sl.first[s];
-                    if (!n || !h[s]) continue;
-                    const int rc = crp::staged_d2h(d.ctx, h[s] + sl.foff[s], sl.arena->d_feat[s] + sl.first[s], n * sizeof(uint32_t));
-                    if (rc != CRP_OK) return rc;
-                }
-            }
-            return crp_synchronize(d.ctx);
-        });
-    }
-    crp_ctx *ctx = node->dev[(size_t)node->root].ctx;
-    NODE_HIP(node, hipSetDevice(ctx->device));
-    uint32_t *h[2] = {feat_plus, feat_minus};
-    for (int s = 0; s < 2; ++s)
-        if (h[s] && node->total[s]) {
-            const int rc = crp::staged_d2h(ctx, h[s], node->d_ffeat[s], node->total[s] * sizeof(uint32_t));
-            if (rc != CRP_OK) return dev_fail(node, node->root, rc, "crp_node_fetch_features");
-        }
-    NODE_HIP(node, hipStreamSynchronize(ctx->stream));
-    return CRP_OK;
+    if (!node->have_gather || !(node->gflags & flag)) return CRP_ERR_STATE;
+    const crp::HostCol want{col, {plus, minus}};
+    return fetch_cols(node, &want, 1, what);
 }
 
 int crp_node_counts(const crp_node *node, uint64_t *per_contig, uint64_t *n_plus, uint64_t *n_minus)
@@ -1442,35 +1406,28 @@ static int node_count_scored_impl(crp_node *node, uint64_t *n_scored)
 {
     if (!node || !n_scored) return CRP_ERR_INVALID;
     if (!node->have_gather) return CRP_ERR_STATE;
-    if (node->host_mode) {  // the rows are still on their devices: every device counts its owned runs
-        const bool pre = (node->gflags & CRP_GATHER_PRE) != 0;
-        uint64_t sum = 0;
-        for (size_t k = 0; k < node->dev.size(); ++k) {
-            NodeDev &d = node->dev[k];
-            if (!d.n_slots) continue;
-            crp_ctx *c = d.ctx;
-            NODE_HIP(node, hipSetDevice(d.device));
-            NODE_HIP(node, hipMemsetAsync(c->d_scalar, 0, sizeof(uint64_t), c->stream));
-            for (size_t j = 0; j < d.n_slots; ++j) {
-                NodeSlot &sl = *d.slots[j];
-                for (int s = 0; s < 2; ++s)
-                    NODE_HIP(node, crp::launch_count_scored(c->stream, (pre ? sl.arena->d_pre[s] : sl.arena->d_score[s]) + sl.first[s],
-                                                            sl.last[s] - sl.first[s], c->d_scalar));
+    const crp::GatherCols cols = crp::gather_cols(node->gflags);
+    const bool on_hosts = (node->gflags & CRP_NODE_HOST_GATHER) != 0;
+    *n_scored = 0;
+    // the root counts its tables; after a host gather the rows are still on their devices and every device counts its owned runs
+    for (size_t k = 0; k < node->dev.size(); ++k) {
+        NodeDev &d = node->dev[k];
+        if (on_hosts ? !d.n_slots : (int)k != node->root) continue;
+        crp_ctx *c = d.ctx;
+        NODE_HIP(node, hipSetDevice(d.device));
+        NODE_HIP(node, hipMemsetAsync(c->d_scalar, 0, sizeof(uint64_t), c->stream));
+        for (int s = 0; s < 2 && !on_hosts; ++s)
+            NODE_HIP(node, crp::launch_count_scored(c->stream, static_cast<const double *>(node->tables.d_col[s][crp::COL_VALUE]), node->total[s], c->d_scalar));
+        for (size_t j = 0; j < d.n_slots && on_hosts; ++j)
+            for (int s = 0; s < 2; ++s) {
+                const NodeSlot &sl = *d.slots[j];
+                NODE_HIP(node, crp::launch_count_scored(c->stream, reinterpret_cast<const double *>(crp::col_src(cols, crp::COL_VALUE, sl.arena, s, sl.first[s])),
+                                                        owned_rows(sl, s), c->d_scalar));
             }
-            NODE_HIP(node, hipMemcpyAsync(c->h_scalar, c->d_scalar, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
-            NODE_HIP(node, hipStreamSynchronize(c->stream));
-            sum += c->h_scalar[0];
-        }
-        *n_scored = sum;
-        return CRP_OK;
+        NODE_HIP(node, hipMemcpyAsync(c->h_scalar, c->d_scalar, sizeof(uint64_t), hipMemcpyDeviceToHost, c->stream));
+        NODE_HIP(node, hipStreamSynchronize(c->stream));
+        *n_scored += c->h_scalar[0];
     }
-    crp_ctx *ctx = node->dev[(size_t)node->root].ctx;
-    NODE_HIP(node, hipSetDevice(ctx->device));
-    NODE_HIP(node, hipMemsetAsync(ctx->d_scalar, 0, sizeof(uint64_t), ctx->stream));
-    for (int s = 0; s < 2; ++s) NODE_HIP(node, crp::launch_count_scored(ctx->stream, node->d_fscore[s], node->total[s], ctx->d_scalar));
-    NODE_HIP(node, hipMemcpyAsync(ctx->h_scalar, ctx->d_scalar, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    NODE_HIP(node, hipStreamSynchronize(ctx->stream));
-    *n_scored = ctx->h_scalar[0];
     return CRP_OK;
 }
 
@@ -1479,52 +1436,18 @@ static int node_fetch_impl(crp_node *node, uint32_t *pos_plus, double *score_plu
     crp::Range roctx_range("crp: node D2H tables");
     if (!node) return CRP_ERR_INVALID;
     if (!node->have_gather) return CRP_ERR_STATE;
-    if (node->host_mode) {
-        // every device's owned rows over ITS link into their place in the caller's arrays, one host thread per device
-        const bool pre = (node->gflags & CRP_GATHER_PRE) != 0;
-        uint32_t *hp[2] = {pos_plus, pos_minus};
-        double *hs[2] = {score_plus, score_minus};
-        return on_every_device(node, "crp_node_fetch (host gather)", [&](int k) {
-            NodeDev &d = node->dev[(size_t)k];
-            for (size_t j = 0; j < d.n_slots; ++j) {
-                NodeSlot &sl = *d.slots[j];
-                for (int s = 0; s < 2; ++s) {
-                    const uint64_t n = sl.last[s] - sl.first[s];
-                    if (!n) continue;
-                    int rc = CRP_OK;
-                    if (hp[s]) rc = crp::staged_d2h(d.ctx, hp[s] + sl.foff[s], sl.d_lpos[s], n * sizeof(uint32_t));
-                    if (rc == CRP_OK && hs[s])
-                        rc = crp::staged_d2h(d.ctx, hs[s] + sl.foff[s], (pre ? sl.arena->d_pre[s] : sl.arena->d_score[s]) + sl.first[s], n * sizeof(double));
-                    if (rc != CRP_OK) return rc;
-                }
-            }
-            return crp_synchronize(d.ctx);
-        });
-    }
-    crp_ctx *ctx = node->dev[(size_t)node->root].ctx;
-    NODE_HIP(node, hipSetDevice(ctx->device));
-    uint32_t *hp[2] = {pos_plus, pos_minus};
-    double *hs[2] = {score_plus, score_minus};
-    for (int s = 0; s < 2; ++s) {
-        const uint64_t n = node->total[s];
-        if (!n) continue;
-        int rc = CRP_OK;
-        if (hp[s]) rc = crp::staged_d2h(ctx, hp[s], node->d_fpos[s], n * sizeof(uint32_t));
-        if (rc == CRP_OK && hs[s]) rc = crp::staged_d2h(ctx, hs[s], node->d_fscore[s], n * sizeof(double));
-        if (rc != CRP_OK) return dev_fail(node, node->root, rc, "crp_node_fetch");
-    }
-    NODE_HIP(node, hipStreamSynchronize(ctx->stream));
-    return CRP_OK;
+    const crp::HostCol want[2] = {{crp::COL_POS, {pos_plus, pos_minus}}, {crp::COL_VALUE, {score_plus, score_minus}}};
+    return fetch_cols(node, want, 2, "crp_node_fetch");
 }
 
 int crp_node_tables_device(crp_node *node, void **pos_plus, void **score_plus, void **pos_minus, void **score_minus)
 {
     if (!node) return CRP_ERR_INVALID;
-    if (!node->have_gather || node->host_mode) return CRP_ERR_STATE;  // (a host gather leaves no table on any one device)
-    if (pos_plus) *pos_plus = node->d_fpos[0];
-    if (score_plus) *score_plus = node->d_fscore[0];
-    if (pos_minus) *pos_minus = node->d_fpos[1];
-    if (score_minus) *score_minus = node->d_fscore[1];
+    if (!node->have_gather || (node->gflags & CRP_NODE_HOST_GATHER)) return CRP_ERR_STATE;  // (a host gather leaves no table on any one device)
+    if (pos_plus) *pos_plus = node->tables.d_col[0][crp::COL_POS];
+    if (score_plus) *score_plus = node->tables.d_col[0][crp::COL_VALUE];
+    if (pos_minus) *pos_minus = node->tables.d_col[1][crp::COL_POS];
+    if (score_minus) *score_minus = node->tables.d_col[1][crp::COL_VALUE];
     return CRP_OK;
 }
 
@@ -1554,8 +1477,8 @@ int crp_node_gather(crp_node *node, int root, int flags) { CRP_NODE_GUARD(node_g
 int crp_node_offtarget(crp_node *node, int guide_len, uint64_t *n_sites) { CRP_NODE_GUARD(node_offtarget_impl(node, guide_len, n_sites)); }
 int crp_node_annotate(crp_node *node, const crp_annotation *annotation, const uint64_t *seqid_of_contig, int dec) { CRP_NODE_GUARD(node_annotate_impl(node, annotation, seqid_of_contig, dec)); }
 int crp_node_fetch(crp_node *node, uint32_t *pos_plus, double *score_plus, uint32_t *pos_minus, double *score_minus) { CRP_NODE_GUARD(node_fetch_impl(node, pos_plus, score_plus, pos_minus, score_minus)); }
-int crp_node_fetch_offtarget(crp_node *node, uint32_t *ot_plus, uint32_t *ot_minus) { CRP_NODE_GUARD(node_fetch_offtarget_impl(node, ot_plus, ot_minus)); }
-int crp_node_fetch_features(crp_node *node, uint32_t *feat_plus, uint32_t *feat_minus) { CRP_NODE_GUARD(node_fetch_features_impl(node, feat_plus, feat_minus)); }
+int crp_node_fetch_offtarget(crp_node *node, uint32_t *ot_plus, uint32_t *ot_minus) { CRP_NODE_GUARD(node_fetch_optional_impl(node, crp::COL_OT, CRP_GATHER_OFFTARGET, "crp_node_fetch_offtarget", ot_plus, ot_minus)); }
+int crp_node_fetch_features(crp_node *node, uint32_t *feat_plus, uint32_t *feat_minus) { CRP_NODE_GUARD(node_fetch_optional_impl(node, crp::COL_FEAT, CRP_GATHER_FEATURES, "crp_node_fetch_features", feat_plus, feat_minus)); }
 int crp_node_count_scored(crp_node *node, uint64_t *n_scored) { CRP_NODE_GUARD(node_count_scored_impl(node, n_scored)); }
 
 }  // extern "C"

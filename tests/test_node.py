@@ -886,3 +886,157 @@ def test_cli_devices_command_line(tmp_path, manifest):
     p = subprocess.run([sys.executable, "-m", "cropsr_amd", "--devices", "0,0", "--gpus", "2", "-o", str(tmp_path / "x.csv")] + common,
                        capture_output=True, text=True, timeout=600, cwd=str(tmp_path), env=env)
     assert p.returncode != 0 and "give one of them" in p.stderr
+
+
+# ------------------------------------------------------------------ the gathered columns, one list for every path
+COLUMN_KEYS = ("pos_plus", "score_plus", "pos_minus", "score_minus", "ot_plus", "ot_minus", "feat_plus", "feat_minus")
+COLUMN_TRANSPORTS = {"peer": "device-to-device copies", "rccl": "RCCL (in-library, one process)", "host": "none: every device"}
+
+
+def _column_list_genome(gff_path=None):
+    """~200 kb in four contigs: random ACGT, a stretch of A/T alone (no PAM: no row), one without C (no CC: rows on the
+    plus strand only), random ACGT.  At world 3 a device's whole share lies in the last two kinds, at world 4 one's lies in
+    the A/T stretch.  gff_path: genes over all of it are written there."""
+    rng = np.random.default_rng(4242)
+    contigs = []
+    for k, (letters, n) in enumerate(((b"ACGT", 44_000), (b"AT", 62_000), (b"AGT", 70_000), (b"ACGT", 24_000))):
+        contigs.append(b"'" + rng.choice(np.frombuffer(letters, dtype=np.uint8), n).tobytes() + (b"')]" if k == 3 else b"'),"))
+    if gff_path is not None:
+        rows = ["##gff-version 3"]
+        for k, c in enumerate(contigs):
+            for g in range(len(c) // 5_000):
+                a = 1 + g * 5_000 + int(rng.integers(0, 1_000))
+                rows.append("c%d\tsrc\tgene\t%d\t%d\t.\t+\t.\tID=g%d_%d" % (k, a, min(len(c), a + int(rng.integers(300, 3_500))), k, g))
+        with open(gff_path, "w") as f:
+            f.write("\n".join(rows) + "\n")
+    return contigs
+
+
+def _owned_rows(pieces, positions):
+    """{device: [rows on '+', rows on '-']} -- a row belongs to the piece its position lies in.  pieces: plan_shares'
+    (contig, start, end, device); positions[contig] = (pos_plus, pos_minus)."""
+    rows = {}
+    for c, s, e, dev in pieces:
+        for strand in (0, 1):
+            pos = positions[c][strand]
+            rows.setdefault(dev, [0, 0])[strand] += int(((pos >= s) & (pos < e)).sum())
+    return rows
+
+
+def _wire_bytes(pieces, lengths, rows, root, pos16):
+    """What crp_node_gather's peers put on the wire with both optional columns: per peer and strand that has rows,
+    rows x (4 B position | 2 B packed, 8 B value, 16 B off-target counts, 4 B label-set id), and packed one u32 bucket start
+    per 65 536 positions of the peer's arena + 1.  The arena: one leading word, per piece the
+    words of its text (the piece and 128 characters either side) + 1, padded to 1 024 words."""
+    total = 0
+    for dev, n in rows.items():
+        if dev == root:
+            continue
+        words = 2
+        for c, s, e, d in pieces:
+            if d == dev:
+                words += (min(lengths[c], e + 128) - max(0, s - 128) + 63) // 64 + 1
+        buckets = ((-(-(words + 1) // 1024) * 1024 * 64) >> 16) + 1
+        for strand in (0, 1):
+            if n[strand]:
+                total += n[strand] * ((2 if pos16 else 4) + 8 + 16 + 4) + (4 * buckets if pos16 else 0)
+    return total
+
+
+def _column_list_cases(worlds, mode, ref, expected, gff_path):
+    """Every (world, pos16, pre) over one transport, both optional columns: each fetched column == the world-1 node's, and
+    bytes_to_root == what the rows of the peers weigh.  Returns the number of gathers checked."""
+    from cropsr_amd import annotate, node as nd
+    contigs = _column_list_genome()
+    ann = annotate.Annotation(gff_path)
+    req = annotate.Request(ann, ["c%d" % k for k in range(len(contigs))], 1)
+    checked = 0
+    for world in worlds:
+        with nd.Node([0] * world) as node:
+            node.load(contigs)
+            for pos16 in (False, True):
+                for pre in (False, True):
+                    root = world - 1 if pre else 0
+                    hits = node.scan(20, root=root, pre=pre, pos16=pos16, offtarget=True, annotation=req, to_host=mode == "host")
+                    ctx = (mode, world, pos16, pre)
+                    for key in COLUMN_KEYS:
+                        got, want = getattr(hits, key), ref["%d_%s" % (pre, key)]
+                        assert got.shape == want.shape and (bits(got) == bits(want)).all(), (ctx, key)
+                    st = node.gather_stats()
+                    print("column list", ctx, "bytes_to_root", st["bytes_to_root"], "transport", st["transport"])
+                    assert st["transport"].startswith(COLUMN_TRANSPORTS[mode]), (ctx, st)
+                    want_bytes = 0 if mode == "host" else expected["%d_%d_%d" % (world, root, pos16)]
+                    assert st["bytes_to_root"] == want_bytes, (ctx, st["bytes_to_root"], want_bytes)
+                    checked += 1
+    ann.close()
+    return checked
+
+
+def _column_list_child(out_path, ref_path, expected_path, gff_path):
+    """The RCCL cases, in a process that finds the loop-back double of librccl.so.1 (tests/fake_rccl.py)."""
+    import json
+    import fake_rccl
+    with open(expected_path) as f:
+        expected = json.load(f)
+    checked = _column_list_cases((3, 4), "rccl", dict(np.load(ref_path)), expected, gff_path)
+    with open(out_path, "w") as f:
+        json.dump({"checked": checked, "stats": fake_rccl.in_process_stats()}, f)
+
+
+@pytest.mark.gpu
+def test_node_gathered_columns_equal_world_one_on_every_transport(oracle, tmp_path):
+    """The column list (crp_gather_cols.h) is what every path of the gather walks: a column it drops, doubles or sizes
+    wrongly must show here.  One small genome on which, at world 3, one logical device owns rows of one strand only and, at
+    world 4, one owns none (both asserted from the oracle's rows before anything runs on the GPU); worlds 3 and 4; raw and
+    packed positions; score and pre-score; both optional columns after crp_node_offtarget and crp_node_annotate; over
+    device-to-device copies, over RCCL (the loop-back double, in a child process) and with CRP_NODE_HOST_GATHER.  Every
+    fetched column == the same column of a world-1 node, bit for bit; for the two transports that move rows,
+    bytes_to_root == the sum over peers and strands of rows x bytes per row (+ 4 x buckets when packed)."""
+    import json
+    import fake_rccl
+    from cropsr_amd import annotate, node as nd
+    gff = str(tmp_path / "columns.gff")
+    contigs = _column_list_genome(gff)
+    lengths = [len(c) for c in contigs]
+    assert 190_000 < sum(lengths) < 210_000
+    plans = {world: nd.plan_shares(lengths, world) for world in (3, 4)}
+    want = [oracle.scan_score(c, 20) for c in contigs]
+    by_oracle = {world: _owned_rows(plans[world], [(w["pos_plus"], w["pos_minus"]) for w in want]) for world in (3, 4)}
+    assert any((n[0] == 0) != (n[1] == 0) for n in by_oracle[3].values()), by_oracle[3]  # one strand only
+    assert any(n == [0, 0] for n in by_oracle[4].values()) and len(by_oracle[4]) == 4, by_oracle[4]  # no row at all
+    # the reference: the same genome on a one-device node (nothing to exchange)
+    ann = annotate.Annotation(gff)
+    req = annotate.Request(ann, ["c%d" % k for k in range(len(contigs))], 1)
+    ref = {}
+    with nd.Node([0]) as node:
+        node.load(contigs)
+        for pre in (False, True):
+            hits = node.scan(20, pre=pre, offtarget=True, annotation=req)
+            ref.update({"%d_%s" % (pre, key): getattr(hits, key) for key in COLUMN_KEYS})
+            if not pre:
+                positions = [(hits.contig(k)["pos_plus"], hits.contig(k)["pos_minus"]) for k in range(len(contigs))]
+    ann.close()
+    assert ref["0_pos_plus"].size + ref["0_pos_minus"].size > 5_000
+    assert int((ref["0_feat_plus"] != annotate.NO_FEATURE).sum()) > 500 and int(ref["0_ot_plus"].sum()) > 0
+    expected = {}
+    for world in (3, 4):
+        rows = _owned_rows(plans[world], positions)
+        assert rows == by_oracle[world]
+        for root in (0, world - 1):
+            for pos16 in (False, True):
+                expected["%d_%d_%d" % (world, root, pos16)] = _wire_bytes(plans[world], lengths, rows, root, pos16)
+    assert all(v > 0 for v in expected.values())
+    assert _column_list_cases((3, 4), "peer", ref, expected, gff) == 8
+    assert _column_list_cases((3, 4), "host", ref, expected, gff) == 8
+    np.savez(str(tmp_path / "ref.npz"), **ref)
+    with open(str(tmp_path / "expected.json"), "w") as f:
+        json.dump(expected, f)
+    out = str(tmp_path / "rccl.json")
+    with fake_rccl.Session(CRP_NODE_TRANSPORT="rccl") as s:
+        code = "import test_node as t; t._column_list_child(%r, %r, %r, %r)" % (out, str(tmp_path / "ref.npz"), str(tmp_path / "expected.json"), gff)
+        p = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, env=s.env(), cwd=os.path.join(ROOT, "tests"))
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    print(p.stdout)
+    with open(out) as f:
+        r = json.load(f)
+    assert r["checked"] == 8 and r["stats"]["mismatches"] == 0 and r["stats"]["pairs"] > 0, r
