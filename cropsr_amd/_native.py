@@ -31,6 +31,12 @@ class RowExtra(ctypes.Structure):
     _fields_ = [("self_counts", ctypes.c_void_p), ("n_counts", ctypes.c_int), ("self_hit_sum", ctypes.c_void_p)]
 
 
+class SelectParams(ctypes.Structure):
+    """crp_select_params (include/cropsr_hip.h): the thresholds and K of one crp_select_run."""
+    _fields_ = [("min_score", ctypes.c_double), ("max_hit_sum", ctypes.c_uint64), ("max_mm0", ctypes.c_uint32), ("k", ctypes.c_int32),
+                ("require_cds", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
 voidpp = ctypes.POINTER(ctypes.c_void_p)
 
 # every symbol include/cropsr_hip.h declares: name -> (restype, argtypes)
@@ -155,6 +161,18 @@ SIGNATURES = {
     "crp_search_self_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_search_self_join_hits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, u32p, u64p, u32p, u64p]),
     "crp_search_self_join_device": (ctypes.c_int, [ctypes.c_void_p, voidpp, voidpp, voidpp, voidpp]),
+    "crp_annotation_genes": (ctypes.c_int, [ctypes.c_void_p, u64p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), u8p, u64p,
+                                            u64p]),
+    "crp_annotation_gene_layout": (ctypes.c_int, [ctypes.c_void_p, u64p, ctypes.c_uint64, ctypes.c_int, u32p, u32p, u64p, ctypes.c_uint64,
+                                                  u64p]),
+    "crp_annotation_cds_flags": (ctypes.c_int, [ctypes.c_void_p, u8p]),
+    "crp_select_create": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, ctypes.c_uint64, voidpp]),
+    "crp_select_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "crp_select_set_flags": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_uint64]),
+    "crp_select_set_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64]),
+    "crp_select_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "crp_select_fetch": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, u32p]),
+    "crp_select_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_configure": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]),
     "crp_query": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     "crp_build_id": (ctypes.c_char_p, []),
@@ -191,6 +209,7 @@ SEARCH_SHAPE_DOUBLES = 288
 SEARCH_SELF_MAX_MM = 4
 SEARCH_PAIR_MAX_PAM = 3
 SELF_UNJOINED_COUNT, SELF_UNJOINED_SUM = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF  # crp_search_self_join_hits: a hit without a guide site's row
+SELECT_MAX_K, SELECT_DEFAULT_SLICE_ROWS, SELECT_MIN_SLICE_ROWS, SELECT_NONE = 64, 65536, 64, 0xFFFFFFFF
 CRP_ERR_INVALID = -1
 CRP_ERR_NO_DEVICE = -2
 CRP_ERR_UNSUPPORTED = -7

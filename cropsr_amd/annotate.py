@@ -136,6 +136,52 @@ class Annotation:
                                          ids.ctypes.data_as(nat.u32p), n.value, ctypes.byref(n)), "crp_annotation_track")
         return points, ids
 
+    def _entries(self, entries):
+        e = np.empty((len(entries), 4), dtype=np.uint64)
+        none = np.uint64(0xFFFFFFFFFFFFFFFF)
+        for r, (name, lo, length, off) in enumerate(entries):
+            k = self.seq_index.get(name)
+            e[r] = (none if k is None else k, lo, length, off)
+        return e
+
+    # ---- the gene rows (guide selection, cropsr_amd/select.py)
+    def genes(self):
+        """(labels, seqid names, start int64, end int64) of the GFF's `gene` rows in file order: the label is the
+        "gene:<ident>" text the join prints, without the annotation_info suffix; start / end as the file gives them."""
+        L, n = nat.lib(), int(self.n_genes)
+        nbytes = ctypes.c_uint64()
+        nat.check(L.crp_annotation_genes(self._h, None, None, None, None, None, ctypes.byref(nbytes)), "crp_annotation_genes")
+        seq, start, end = np.zeros(n, np.uint64), np.zeros(n, np.int64), np.zeros(n, np.int64)
+        blob, off = np.zeros(max(1, nbytes.value), np.uint8), np.zeros(n + 1, np.uint64)
+        i64p = ctypes.POINTER(ctypes.c_int64)
+        nat.check(L.crp_annotation_genes(self._h, seq.ctypes.data_as(nat.u64p), start.ctypes.data_as(i64p), end.ctypes.data_as(i64p),
+                                         blob.ctypes.data_as(nat.u8p), off.ctypes.data_as(nat.u64p), ctypes.byref(nbytes)),
+                  "crp_annotation_genes")
+        table = StringTable(blob, off)
+        names = {k: name for name, k in self.seq_index.items()}
+        return [table[g] for g in range(n)], [names[int(k)] for k in seq], start, end
+
+    def gene_layout(self, entries, dec):
+        """(lo uint32, hi uint32, gene uint64) of crp_annotation_gene_layout: the genes of one arena's texts as closed
+        ranges of arena positions (entries as arena_track takes them); gene = index into genes()."""
+        e = self._entries(entries)
+        n = ctypes.c_uint64()
+        L = nat.lib()
+        st = L.crp_annotation_gene_layout(self._h, e.ctypes.data_as(nat.u64p), e.shape[0], int(dec), None, None, None, 0, ctypes.byref(n))
+        if st not in (nat.CRP_OK, nat.CRP_ERR_CAPACITY):
+            nat.check(st, "crp_annotation_gene_layout")
+        lo, hi, gene = np.empty(n.value, np.uint32), np.empty(n.value, np.uint32), np.empty(n.value, np.uint64)
+        nat.check(L.crp_annotation_gene_layout(self._h, e.ctypes.data_as(nat.u64p), e.shape[0], int(dec), lo.ctypes.data_as(nat.u32p),
+                                               hi.ctypes.data_as(nat.u32p), gene.ctypes.data_as(nat.u64p), n.value, ctypes.byref(n)),
+                  "crp_annotation_gene_layout")
+        return lo, hi, gene
+
+    def cds_flags(self):
+        """uint8 per label-set string: 1 when the set holds a CDS label."""
+        flags = np.zeros(max(1, len(self.strings)), np.uint8)
+        nat.check(nat.lib().crp_annotation_cds_flags(self._h, flags.ctypes.data_as(nat.u8p)), "crp_annotation_cds_flags")
+        return flags[:len(self.strings)]
+
     def close(self):
         if self._h:
             nat.lib().crp_annotation_destroy(self._h)
@@ -171,6 +217,10 @@ class Request:
     def track(self, layout):
         """layout: [(text index, arena offset, length)] of ONE arena in arena order -> (points, ids)."""
         return self.annotation.arena_track([(self.names[t], self.starts[t], ln, off) for t, off, ln in layout], self.dec)
+
+    def gene_layout(self, layout):
+        """layout as track() takes it -> (lo, hi, gene) of Annotation.gene_layout: that arena's genes."""
+        return self.annotation.gene_layout([(self.names[t], self.starts[t], ln, off) for t, off, ln in layout], self.dec)
 
 
 def features_of(request, hits):

@@ -110,6 +110,22 @@ def build_parser():
                      help="NOT in the reference (which parses the GFF and drops it, CROPSR.py:375): fill the "
                           "`features` column with the gene/CDS rows of the GFF (-g) that contain the cut site, "
                           "named through the Phytozome annotation_info file (-p) when given")
+    eng.add_argument("--select", type=int, default=None, metavar="K",
+                     help="NOT in the reference: for every `gene` row of the GFF (-g), the K (1..64) best-scoring guides whose cut "
+                          "site lies in the gene and that pass the --select-* thresholds, chosen on the GPU and written to their own "
+                          "small CSV (gene, rank, passing, then the main table's fields without crispr_id); -l 20, one GPU")
+    eng.add_argument("--select-output", metavar="FILE", default=None,
+                     help="with --select: the selection file, default = the -o path + .selected.csv")
+    eng.add_argument("--select-min-score", type=float, default=None, metavar="X",
+                     help="with --select: only guides with on_site_score >= X (default 0)")
+    eng.add_argument("--select-max-perfect", type=int, default=None, metavar="N",
+                     help="with --select and --specificity: only guides with at most N other perfect copies (self_mm0 <= N)")
+    eng.add_argument("--select-min-specificity", type=float, default=None, metavar="S",
+                     help="with --select and --specificity: only guides whose specificity is at least S (S <= 0: no bound)")
+    eng.add_argument("--select-cds", action="store_true",
+                     help="with --select: only guides whose cut site lies in a CDS row of the GFF (positional, like --annotate)")
+    eng.add_argument("--select-only", action="store_true",
+                     help="with --select: write the selection file only, not the main table (no ids are drawn)")
     eng.add_argument("--bench-json", metavar="PATH", default=None,
                      help="write stage timings of this run (read, upload+scan, fetch, format+write) as one JSON object")
     return p
@@ -269,16 +285,18 @@ class EngineBackend:
             # code object (17-25 ms, otherwise paid by the genome's first slice)
             self.engine.scan_stream([np.frombuffer(b"ACGTTGCAAGGCCTTA" * 40, dtype=np.uint8)], 20)
 
-    def scan(self, contig_strings, guide_len, offtarget=False, annotation=None, specificity=None):
+    def scan(self, contig_strings, guide_len, offtarget=False, annotation=None, specificity=None, select=None):
         """One pass on the GPU for all contig strings (seam 1 + 2).  The plain scan goes through crp_scan_stream -- upload,
         scan and table fetch as a pipeline over slices of the genome, the host link busy in both directions (the reference's
         loop is produce-and-consume per contig too, CROPSR.py:409-474); CROPSR_STREAM=0, or the opt-in steps that work on
         resident tables (offtarget, annotation), take the arena calls: upload, one scan, fetch.  annotation
         (annotate.Request): the hit dicts also carry feat_plus / feat_minus, the label-set id of every row, joined on the GPU
         while the tables are resident.  specificity (the arguments of search.specificity_columns): the hit dicts also carry
-        self_counts_* / self_sum_*, the self search's rows joined onto the resident tables."""
+        self_counts_* / self_sum_*, the self search's rows joined onto the resident tables.  select (select.Request): the returned list is a
+        select.HitList whose .selection holds the best K guides of every gene, chosen on the GPU while the tables (and the
+        joined specificity columns) are resident."""
         import os
-        if not offtarget and annotation is None and specificity is None and os.environ.get("CROPSR_STREAM", "1") != "0":
+        if not offtarget and annotation is None and specificity is None and select is None and os.environ.get("CROPSR_STREAM", "1") != "0":
             want_pre = self.finalize == "host"
             hits = self.engine.scan_stream(contig_strings, guide_len, want_pre=want_pre)
             self.last_stream = hits.stream_stats  # (--bench-json)
@@ -292,9 +310,14 @@ class EngineBackend:
             return out
         genome = self.engine.genome(contig_strings)  # as many arenas as the genome needs
         try:
+            more = {} if select is None else dict(select=select)
             hits = genome.scan_score(guide_len, want_pre=self.finalize == "host", offtarget=offtarget, annotation=annotation,
-                                     specificity=specificity)
+                                     specificity=specificity, **more)
             out = [self._finalize(hits.contig(k)) for k in range(len(contig_strings))]
+            if select is not None:
+                from . import select as sel
+                out = sel.HitList(out)
+                out.selection = hits.selection
             self.last_annotate_s = genome.annotate_s
             self.last_specificity = getattr(hits.columns, "stats", None)  # (--bench-json)
         finally:
@@ -486,6 +509,78 @@ def specificity_request(args):
     return dict(max_mm=M, candidate_pam=pam.upper(), score=score)
 
 
+def select_request(args, spec, world=1):
+    """--select and its options, checked: None without it, else dict(params (select.Params), output, only).  Like
+    specificity_request, everything the command line alone can get wrong ends the run here, before any side effect."""
+    def refuse(msg):
+        sys.exit("cropsr_amd: --select: " + msg)
+
+    given = [o for o, k, unset in (("--select-output", "select_output", None), ("--select-min-score", "select_min_score", None),
+                                   ("--select-max-perfect", "select_max_perfect", None),
+                                   ("--select-min-specificity", "select_min_specificity", None), ("--select-cds", "select_cds", False),
+                                   ("--select-only", "select_only", False)) if getattr(args, k, unset) not in (unset, None)]
+    K = getattr(args, "select", None)
+    if K is None:
+        if given:
+            sys.exit("cropsr_amd: %s belongs to --select" % given[0])
+        return None
+    from . import select
+    if not args.g:
+        refuse("the genes come from the GFF: --select needs -g")
+    if not 1 <= K <= select.MAX_K:
+        refuse("K must be 1..%d, not %d" % (select.MAX_K, K))
+    if args.l != select.GUIDE_LEN:
+        refuse("guides are ranked by on_site_score, which exists for -l %d only, not -l %d" % (select.GUIDE_LEN, args.l))
+    for opt, key in (("--select-max-perfect", "select_max_perfect"), ("--select-min-specificity", "select_min_specificity")):
+        if getattr(args, key, None) is not None and spec is None:
+            refuse("%s is a threshold on the columns of --specificity: give --specificity too" % opt)
+    if len(_device_list(args)) > 1:
+        refuse("the selection runs on one GPU: --devices names %d" % len(_device_list(args)))
+    if getattr(args, "gpus", 1) > 1:
+        refuse("the selection runs on one GPU: drop --gpus %d" % args.gpus)
+    if world > 1:
+        refuse("the selection runs on one GPU, and a launcher started %d ranks" % world)
+    try:
+        params = select.Params(K, getattr(args, "select_min_score", None) or 0.0, getattr(args, "select_max_perfect", None),
+                               getattr(args, "select_min_specificity", None), bool(getattr(args, "select_cds", False)))
+    except ValueError as e:
+        refuse(str(e))
+    return dict(params=params, output=getattr(args, "select_output", None) or (args.o + ".selected.csv"),
+                only=bool(getattr(args, "select_only", False)))
+
+
+def write_selection(path, selection, names, strings, all_hits, guide_len, offtarget, spec_M, annotation):
+    """The selection file: a header, then per chosen row gene, rank (1-based), passing and the main table's own fields
+    for that row as rows.ContigRows builds them, without crispr_id (those ids are random per run).  Genes in GFF order;
+    genes with nothing selected are left out.  Python's csv module in the main table's dialect: the file is small."""
+    import csv
+    sel_rows = selection.rows
+    fields = [None] * sel_rows.size
+    for c in np.unique(sel_rows["contig"]).tolist():
+        mine = np.flatnonzero(sel_rows["contig"] == c)
+        minus = sel_rows["strand"][mine] == b"-"
+        mine = np.concatenate([mine[~minus], mine[minus]])  # ('+' rows first, as ContigRows holds a contig's rows)
+        n_plus = int((~minus).sum())
+        hits, mini = all_hits[c], {}
+        for key, col in hits.items():
+            if col is None or not (key.endswith("_plus") or key.endswith("_minus")):
+                continue
+            part = mine[:n_plus] if key.endswith("_plus") else mine[n_plus:]
+            mini[key] = np.asarray(col)[sel_rows["index"][part]]
+        feats = None
+        if annotation is not None:
+            feats = (annotation.strings, np.concatenate([mini["feat_plus"], mini["feat_minus"]]))
+        block = rows.ContigRows(names[c], bytes(strings[c]).decode("latin-1"), mini, guide_len, features=feats)
+        for k, at in enumerate(mine.tolist()):
+            fields[at] = block.row(k, "")[1:]
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(["gene", "rank", "passing"] + rows.HEADER[1:] + (rows.OFFTARGET_HEADER if offtarget else []) +
+                   ([] if spec_M is None else rows.SPECIFICITY_HEADER(spec_M)))
+        for r, rest in zip(sel_rows, fields):
+            w.writerow((selection.labels[int(r["gene"])], int(r["rank"]), int(selection.n_pass[int(r["gene"])])) + tuple(rest))
+
+
 class _Early:
     """fn() on a helper thread; get() joins and returns its result or raises what it raised."""
 
@@ -535,6 +630,7 @@ def run(args, backend=None, out=sys.stdout, group=None):
     if offtarget and not NATIVE_GUIDE_LENGTHS[0] <= args.l <= NATIVE_GUIDE_LENGTHS[1]:  # (before any side effect, on every rank)
         sys.exit("cropsr_amd: --offtarget needs a guide length between %d and %d (got %d)" % (NATIVE_GUIDE_LENGTHS + (args.l,)))
     spec = specificity_request(args)  # (before any side effect, on every rank)
+    selecting = select_request(args, spec, 1 if group is None else group.world)
     finalize = getattr(args, "score_finalize", "gpu")
     stages = {}  # --bench-json
     own_group = group is None
@@ -549,12 +645,15 @@ def run(args, backend=None, out=sys.stdout, group=None):
 
     if spec is not None and group is not None and group.world > 1:
         sys.exit("cropsr_amd: --specificity: the self search runs on one GPU, and a launcher started %d ranks" % group.world)
+    if selecting is not None and group is not None and group.world > 1:
+        select_request(args, spec, group.world)
+    one_gpu = spec is not None or selecting is not None  # the opt-in steps that take the arena path on one device
 
     def make_backend():
-        if getattr(args, "devices", None) and not (spec is not None and len(_device_list(args)) == 1):
+        if getattr(args, "devices", None) and not (one_gpu and len(_device_list(args)) == 1):
             return NodeBackend([int(d) for d in str(args.devices).split(",")], finalize)
         device = getattr(args, "device", None)
-        if spec is not None and getattr(args, "devices", None):  # (one device named the --devices way: the arena path on it)
+        if one_gpu and getattr(args, "devices", None):  # (one device named the --devices way: the arena path on it)
             device = int(_device_list(args)[0])
         if device is None:
             device = group.local_rank if group is not None else 0
@@ -563,7 +662,7 @@ def run(args, backend=None, out=sys.stdout, group=None):
             big = isinstance(args.f, str) and os.path.getsize(args.f) >= (256 << 20)
         except OSError:
             big = False
-        if big and not offtarget and spec is None and not getattr(args, "annotate", False):
+        if big and not offtarget and not one_gpu and not getattr(args, "annotate", False):
             b.warm_up()
         return b
 
@@ -581,7 +680,7 @@ def run(args, backend=None, out=sys.stdout, group=None):
         stages["annotation_build_s"] = time.perf_counter() - t0  # (on its own thread, beside the FASTA read and the GPU start-up)
         return a
 
-    early_annot = _Early(build_annotation, start=readable) if annotating else None
+    early_annot = _Early(build_annotation, start=readable) if annotating or selecting is not None else None
 
     def annotation_request(data, table):
         """annotate.Request for the contig strings of `table` (every rank builds the same one)."""
@@ -663,7 +762,7 @@ def run(args, backend=None, out=sys.stdout, group=None):
     table = fasta.table_from_bytes(data)  # == fasta.contig_table(text).items(), without printing the genome
     stages["read_fasta_s"] = time.perf_counter() - t_stage
     request, request_err = None, None
-    if annotating:
+    if annotating or selecting is not None:  # (--select names its genes through the same request)
         try:
             request = annotation_request(data, table)
         except Exception as e:  # (single process: raised below, after the reference's own GFF import had its say)
@@ -686,7 +785,9 @@ def run(args, backend=None, out=sys.stdout, group=None):
     if getattr(args, "seed", None) is not None:
         np.random.seed(args.seed)
 
-    rows.write_header(args.o, offtarget=offtarget, specificity=None if spec is None else spec["max_mm"])  # CROPSR.py:402-405
+    select_only = selecting is not None and selecting["only"]
+    if not select_only:
+        rows.write_header(args.o, offtarget=offtarget, specificity=None if spec is None else spec["max_mm"])  # CROPSR.py:402-405
 
     names = [k for k, _ in table]
     strings = [v for _, v in table]  # contig strings as bytes, one byte per character
@@ -698,10 +799,13 @@ def run(args, backend=None, out=sys.stdout, group=None):
         if request_err is not None:
             raise request_err
         extra = dict(offtarget=True) if offtarget else {}
-        if request is not None:
+        if request is not None and annotating:
             extra["annotation"] = request
         if spec is not None:
             extra["specificity"] = spec
+        if selecting is not None:  # (the keyword a backend only meets when selecting)
+            from . import select
+            extra["select"] = select.Request(selecting["params"], request)
         from .search import SelfCapacityError
         try:
             all_hits = backend.scan(strings, l_dev, **extra)
@@ -733,6 +837,15 @@ def run(args, backend=None, out=sys.stdout, group=None):
         group.close()
         group = None
     stages["upload_scan_fetch_s"] = time.perf_counter() - t_stage
+    if selecting is not None:
+        t_select = time.perf_counter()
+        selection = all_hits.selection
+        write_selection(selecting["output"], selection, names, strings, all_hits, args.l, offtarget, None if spec is None else spec["max_mm"],
+                        request.annotation if annotating else None)
+        stages["select"] = dict(selection.stats, write_s=time.perf_counter() - t_select, genes=len(selection.labels),
+                                rows_selected=int(selection.rows.size), k=selecting["params"].k)
+    if not annotating:
+        request = None  # (from here on the request means the `features` column)
     if request is not None:
         stages["annotation_join_s"] = getattr(backend, "last_annotate_s", None)  # part of upload_scan_fetch_s (this rank's share)
         stages["annotation_strings"] = len(request.annotation.strings)
@@ -742,7 +855,7 @@ def run(args, backend=None, out=sys.stdout, group=None):
     once = getattr(args, "each_contig_once", False)
     dataset = rows.NativeDataset() if native else rows.Dataset()  # Complete_dataset, CROPSR.py:407
     ids = None
-    if native:
+    if native and not select_only:
         # every pass draws its ids from one RNG stream, in order; the pass sizes are known now,
         # so a worker draws pass k+1's ids while pass k is formatted and written
         per_contig = [int(h["pos_plus"].size + h["pos_minus"].size) for h in all_hits]
@@ -795,6 +908,8 @@ def run(args, backend=None, out=sys.stdout, group=None):
         for name, s, hits in zip(names, strings, all_hits):
             print("Searching on Chromosome: ", name[:25], file=out)  # CROPSR.py:410-411
             print("With start of sequence: ", bytes(s[:25]).decode("latin-1"), file=out)
+            if select_only:  # the selection file is the output: no rows, no ids
+                continue
             feats = None
             if request is not None:  # the device's label-set id per row ('+' rows, then '-' rows) + the string table
                 feats = (request.annotation.strings, np.concatenate([hits["feat_plus"], hits["feat_minus"]]))
@@ -879,7 +994,7 @@ def main(argv=None):
     if getattr(args, "devices", None) and getattr(args, "gpus", 1) > 1:
         sys.exit("cropsr_amd: --devices (one process over several GPUs) and --gpus N (one process per GPU) are two ways to the "
                  "same result: give one of them")
-    specificity_request(args)  # (--gpus N: refused here, before any rank is started)
+    select_request(args, specificity_request(args))  # (--gpus N: refused here, before any rank is started)
     if launch.wanted(getattr(args, "gpus", 1)):
         # no launcher in the environment: this process (which never touches the GPU) starts the ranks as fresh
         # children of the same command line and leaves with their status (cropsr_amd/launch.py)

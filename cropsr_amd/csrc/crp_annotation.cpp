@@ -36,7 +36,18 @@ struct crp_annotation {
     std::vector<Seq> seqs;  // in order of first appearance in the GFF
     std::string blob;       // the distinct label-set strings, back to back
     std::vector<uint64_t> off{0};
+    std::vector<uint8_t> cds_flag;  // per label-set string: 1 when the set holds a CDS label
     uint64_t n_gene = 0, n_cds = 0;
+    // the gene rows, in file order (guide selection, cropsr_amd/select.py): 1-based closed range, index into seqs, and
+    // the label "gene:<ident>" without the annotation_info suffix
+    struct Gene {
+        int64_t start, end;
+        uint32_t seq;
+    };
+    std::vector<Gene> genes;
+    std::vector<std::vector<uint32_t>> genes_of;  // per seqid: its genes (indices into `genes`), file order
+    std::string gene_blob;
+    std::vector<uint64_t> gene_off{0};
 };
 
 namespace {
@@ -187,6 +198,7 @@ int crp_annotation_build(const uint8_t *gff, uint64_t gff_len, const uint8_t *in
             const sv ident = !id.empty() ? id : !name.empty() ? name : !parent.empty() ? parent : sv(".");
             label.assign(gene ? "gene:" : "CDS:");
             label.append(ident);
+            const size_t plain_len = label.size();  // (the gene's own label ends here: what follows names it further)
             if (have_info && gene) {
                 auto hit = info.find(std::string(name));
                 if (hit == info.end()) hit = info.find(std::string(id));
@@ -202,6 +214,7 @@ int crp_annotation_build(const uint8_t *gff, uint64_t gff_len, const uint8_t *in
                     an->seqs.emplace_back();
                     an->seqs.back().name.assign(cols[0]);
                     feats.emplace_back();
+                    an->genes_of.emplace_back();
                 }
                 last_seq = s->second;
                 have_last = true;
@@ -213,6 +226,12 @@ int crp_annotation_build(const uint8_t *gff, uint64_t gff_len, const uint8_t *in
             }
             feats[last_seq].push_back(Feature{start, end, l->second});
             (gene ? an->n_gene : an->n_cds) += 1;
+            if (gene) {
+                an->genes_of[last_seq].push_back((uint32_t)an->genes.size());
+                an->genes.push_back(crp_annotation::Gene{start, end, last_seq});
+                an->gene_blob.append(label, 0, plain_len);
+                an->gene_off.push_back(an->gene_blob.size());
+            }
         }
         // the sweep, seqid by seqid
         std::unordered_map<std::string, uint32_t> string_of;
@@ -246,15 +265,18 @@ int crp_annotation_build(const uint8_t *gff, uint64_t gff_len, const uint8_t *in
                 for (uint32_t a : active)
                     if (std::find(set.begin(), set.end(), f[a].label) == set.end()) set.push_back(f[a].label);
                 text.clear();
+                bool has_cds = false;
                 for (size_t j = 0; j < set.size(); ++j) {
                     if (j) text.push_back(';');
                     text.append(labels[set[j]]);
+                    has_cds = has_cds || labels[set[j]].compare(0, 4, "CDS:") == 0;
                 }
                 auto it = string_of.find(text);
                 if (it == string_of.end()) {
                     it = string_of.emplace(text, (uint32_t)(an->off.size() - 1)).first;
                     an->blob.append(text);
                     an->off.push_back(an->blob.size());
+                    an->cds_flag.push_back(has_cds ? 1 : 0);
                 }
                 seq.ids[i] = it->second;
             }
@@ -343,6 +365,58 @@ int crp_annotation_track(const crp_annotation *an, const uint64_t *entries, uint
     }
     *n_out = n;
     return n <= cap ? CRP_OK : CRP_ERR_CAPACITY;
+}
+
+int crp_annotation_genes(const crp_annotation *an, uint64_t *seqid, int64_t *start, int64_t *end, uint8_t *label_blob,
+                         uint64_t *label_off, uint64_t *label_bytes)
+{
+    if (!an) return CRP_ERR_INVALID;
+    for (size_t g = 0; g < an->genes.size(); ++g) {
+        if (seqid) seqid[g] = an->genes[g].seq;
+        if (start) start[g] = an->genes[g].start;
+        if (end) end[g] = an->genes[g].end;
+    }
+    if (label_blob && !an->gene_blob.empty()) std::memcpy(label_blob, an->gene_blob.data(), an->gene_blob.size());
+    if (label_off) std::memcpy(label_off, an->gene_off.data(), an->gene_off.size() * sizeof(uint64_t));
+    if (label_bytes) *label_bytes = an->gene_blob.size();
+    return CRP_OK;
+}
+
+int crp_annotation_gene_layout(const crp_annotation *an, const uint64_t *entries, uint64_t n_entries, int dec, uint32_t *lo,
+                               uint32_t *hi, uint64_t *gene, uint64_t cap, uint64_t *n_out)
+{
+    if (!an || (n_entries && !entries) || !n_out || (cap && (!lo || !hi || !gene))) return CRP_ERR_INVALID;
+    uint64_t n = 0, prev_base = 0, prev_end = 0;
+    for (uint64_t e = 0; e < n_entries; ++e) {
+        const uint64_t seq = entries[4 * e], first = entries[4 * e + 1], len = entries[4 * e + 2], base = entries[4 * e + 3];
+        if (base + len > 0x7fffffffull || (e && (base < prev_end || base <= prev_base))) return CRP_ERR_INVALID;  // as the track
+        prev_base = base;
+        prev_end = base + len;
+        if (seq >= an->seqs.size() || !len) continue;
+        // index of the 1-based genome coordinate p inside the text: p + dec - 1 - first (crp_annotation_track)
+        const int64_t shift = (int64_t)dec - 1 - (int64_t)first;
+        for (uint32_t g : an->genes_of[seq]) {
+            const crp_annotation::Gene &t = an->genes[g];
+            if (t.start > t.end) continue;
+            const int64_t a = std::max<int64_t>(t.start + shift, 0), b = std::min<int64_t>(t.end + shift, (int64_t)len - 1);
+            if (a > b) continue;  // the text holds none of it
+            if (n < cap) {
+                lo[n] = (uint32_t)(base + (uint64_t)a);
+                hi[n] = (uint32_t)(base + (uint64_t)b);
+                gene[n] = g;
+            }
+            n += 1;
+        }
+    }
+    *n_out = n;
+    return n <= cap ? CRP_OK : CRP_ERR_CAPACITY;
+}
+
+int crp_annotation_cds_flags(const crp_annotation *an, uint8_t *flags)
+{
+    if (!an || (!flags && !an->cds_flag.empty())) return CRP_ERR_INVALID;
+    if (!an->cds_flag.empty()) std::memcpy(flags, an->cds_flag.data(), an->cds_flag.size());
+    return CRP_OK;
 }
 
 }  // extern "C"

@@ -93,6 +93,7 @@ struct crp_search_self {
     unsigned long long *d_join_sum[2] = {nullptr, nullptr};
     uint64_t join_counts_cap[2] = {0, 0}, join_sum_cap[2] = {0, 0};
     bool have_join = false;
+    uint64_t join_rows[2] = {0, 0};  // the tables' rows at the time of the join
     double ms_join = 0;
 
     crp::SearchCands cands() const { return crp::SearchCands{d_cand, d_cand + n, d_cand + 2 * n, d_cand + 3 * n}; }
@@ -188,6 +189,23 @@ int extract(crp_search_self *s, uint64_t budget, uint64_t *needed)
 }
 
 }  // namespace
+
+namespace crp {
+
+bool self_joined(const crp_search_self *s, SelfJoined *out)
+{
+    if (!s || !s->have_join) return false;
+    for (int k = 0; k < 2; ++k) {
+        out->counts[k] = s->d_join_counts[k];
+        out->sum[k] = s->d_join_sum[k];
+        out->rows[k] = s->join_rows[k];
+    }
+    out->stride = s->max_mm + 1;
+    out->arena = s->arena;
+    return true;
+}
+
+}  // namespace crp
 
 extern "C" {
 
@@ -512,6 +530,8 @@ int crp_search_self_join_hits(crp_search_self *s, int guide_len, uint32_t *count
     CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     s->ms_join += elapsed(s->ev[0], s->ev[1]);
     s->have_join = true;
+    s->join_rows[0] = a->n_hits[0];
+    s->join_rows[1] = a->n_hits[1];
     uint32_t *hc[2] = {counts_plus, counts_minus};
     uint64_t *hs[2] = {hit_sum_plus, hit_sum_minus};
     for (int k = 0; k < 2; ++k) {

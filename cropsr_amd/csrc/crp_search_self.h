@@ -6,6 +6,9 @@
 
 #include "crp_search.h"
 
+struct crp_arena;
+struct crp_search_self;
+
 namespace crp {
 
 constexpr int SELF_MAX_MM = 4;         // M + 1 segments of at least 4 letters in a guide region of 20
@@ -64,5 +67,16 @@ hipError_t launch_self_pair_compare(hipStream_t s, const SelfOrder &q, const Sel
 hipError_t launch_self_join(hipStream_t s, const uint32_t *hit_pos, uint32_t n_hits, int strand, int guide_len, const SearchCands &c, uint32_t n_cand,
                             const uint8_t *flag, const uint32_t *counts, const unsigned long long *hit_sum, int max_mm, uint32_t *out_counts,
                             unsigned long long *out_sum);
+
+// The joined columns of a handle's last crp_search_self_join_hits, for the kernels that read them where they lie
+// (crp_select.cpp); false without a join.
+struct SelfJoined {
+    const uint32_t *counts[2];            // stride per row
+    const unsigned long long *sum[2];
+    uint64_t rows[2];                     // the tables' rows when they were joined
+    int stride;                           // max_mm + 1
+    const struct ::crp_arena *arena;
+};
+bool self_joined(const struct ::crp_search_self *s, SelfJoined *out);
 
 }  // namespace crp

@@ -1,0 +1,285 @@
+// crp_select.cpp -- host side of the guide selection (include/cropsr_hip.h, crp_select_*): the
+// handle, the checks of what a run needs to find in HBM, and the cut of the genes' runs into work items between the
+// bounds kernel and the select launches (crp_select.hip).
+#include <algorithm>
+#include <cmath>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "crp_internal.h"
+#include "crp_roctx.h"
+#include "crp_search_self.h"
+#include "crp_select.h"
+
+struct crp_select {
+    crp_arena *arena = nullptr;
+    crp_ctx *ctx = nullptr;
+    uint64_t n_genes = 0;
+    uint64_t slice_rows = CRP_SELECT_DEFAULT_SLICE_ROWS;
+    uint32_t *d_lo = nullptr, *d_hi = nullptr;
+    uint4 *d_bounds = nullptr;
+    uint8_t *d_flags = nullptr;
+    uint64_t flags_cap = 0, n_flags = 0;
+    bool have_flags = false;
+    crp::SelectItem *d_items = nullptr;
+    uint64_t items_cap = 0;
+    crp::SelectMerge *d_merge = nullptr;
+    uint64_t merge_cap = 0;
+    crp::SelectPartials part = {};
+    uint64_t part_entries_cap = 0, part_tie_cap = 0, part_row_cap = 0, part_cnt_cap = 0;
+    crp::SelectResult res = {};  // n_in, n_pass: n_genes; sel: n_genes * k of the last run
+    uint64_t sel_cap = 0;
+    int k = 0;  // of the last successful run (0: none)
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    double stats[9] = {};
+};
+
+namespace {
+
+double elapsed(hipEvent_t a, hipEvent_t b)
+{
+    float ms = 0.f;
+    return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : 0.0;
+}
+
+int fail(crp_ctx *ctx, int rc, const std::string &text)
+{
+    ctx->last_error = text;
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int crp_select_create(crp_arena *a, const uint32_t *lo, const uint32_t *hi, uint64_t n_genes, crp_select **out)
+{
+    if (!a || !out || (n_genes && (!lo || !hi)) || n_genes > 0x7fffffffull) return CRP_ERR_INVALID;
+    *out = nullptr;
+    if (!a->sealed) return CRP_ERR_STATE;
+    crp_ctx *ctx = a->ctx;
+    for (uint64_t g = 0; g < n_genes; ++g)
+        if (lo[g] > hi[g] || hi[g] > 0x7fffffffu)
+            return fail(ctx, CRP_ERR_INVALID, "crp_select_create: gene " + std::to_string(g) + " is no range of arena positions");
+    crp_select *s = new (std::nothrow) crp_select();
+    if (!s) return CRP_ERR_NOMEM;
+    s->arena = a;
+    s->ctx = ctx;
+    s->n_genes = n_genes;
+    int rc = CRP_OK;
+    if (hipSetDevice(ctx->device) != hipSuccess || hipEventCreate(&s->ev[0]) != hipSuccess || hipEventCreate(&s->ev[1]) != hipSuccess)
+        rc = fail(ctx, CRP_ERR_HIP, "crp_select_create: no HIP events");
+    uint64_t cap = 0;
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_lo), &cap, n_genes, sizeof(uint32_t));
+    cap = 0;
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_hi), &cap, n_genes, sizeof(uint32_t));
+    cap = 0;
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_bounds), &cap, n_genes, sizeof(uint4));
+    cap = 0;
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->res.n_in), &cap, n_genes, sizeof(uint32_t));
+    cap = 0;
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->res.n_pass), &cap, n_genes, sizeof(uint32_t));
+    if (rc == CRP_OK && n_genes) {
+        rc = crp::staged_h2d(ctx, s->d_lo, lo, n_genes * sizeof(uint32_t));
+        if (rc == CRP_OK) rc = crp::staged_h2d(ctx, s->d_hi, hi, n_genes * sizeof(uint32_t));
+        if (rc == CRP_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = CRP_ERR_HIP;
+    }
+    if (rc != CRP_OK) {
+        crp_select_destroy(s);
+        return rc;
+    }
+    *out = s;
+    return CRP_OK;
+}
+
+int crp_select_destroy(crp_select *s)
+{
+    if (!s) return CRP_OK;
+    (void)hipSetDevice(s->ctx->device);
+    (void)hipStreamSynchronize(s->ctx->stream);
+    void *bufs[] = {s->d_lo, s->d_hi, s->d_bounds, s->d_flags, s->d_items, s->d_merge, s->part.key, s->part.tie,
+                    s->part.row, s->part.cnt, s->res.n_in, s->res.n_pass, s->res.sel};
+    for (void *p : bufs) (void)hipFree(p);
+    for (hipEvent_t e : s->ev)
+        if (e) (void)hipEventDestroy(e);
+    delete s;
+    return CRP_OK;
+}
+
+int crp_select_set_flags(crp_select *s, const uint8_t *flags, uint64_t n_flags)
+{
+    if (!s || (n_flags && !flags) || n_flags > 0xfffffffeull) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    s->have_flags = false;
+    int rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_flags), &s->flags_cap, n_flags, 1);
+    if (rc == CRP_OK && n_flags) rc = crp::staged_h2d(ctx, s->d_flags, flags, n_flags);
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s->n_flags = n_flags;
+    s->have_flags = true;
+    return CRP_OK;
+}
+
+int crp_select_set_limits(crp_select *s, uint64_t slice_rows)
+{
+    if (!s) return CRP_ERR_INVALID;
+    if (slice_rows && (slice_rows < CRP_SELECT_MIN_SLICE_ROWS || slice_rows > 0x40000000ull)) return CRP_ERR_INVALID;
+    s->slice_rows = slice_rows ? slice_rows : CRP_SELECT_DEFAULT_SLICE_ROWS;
+    return CRP_OK;
+}
+
+int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *self)
+{
+    crp::Range roctx_range("crp: guide selection");
+    if (!s || !p) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    crp_arena *a = s->arena;
+    s->k = 0;
+    if (p->k < 1 || p->k > CRP_SELECT_MAX_K)
+        return fail(ctx, CRP_ERR_INVALID, "crp_select_run: k must be 1.." + std::to_string(CRP_SELECT_MAX_K) + ", not " + std::to_string(p->k));
+    if (std::isnan(p->min_score)) return fail(ctx, CRP_ERR_INVALID, "crp_select_run: min_score is not a number");
+    if (!a->have_hits || a->pend_guide_len != 20)
+        return fail(ctx, CRP_ERR_STATE, "crp_select_run: the arena has no hit tables of guide length 20 (the ranking key exists only there)");
+    if (p->require_cds && !s->have_flags) return fail(ctx, CRP_ERR_STATE, "crp_select_run: require_cds needs crp_select_set_flags");
+    if (p->require_cds && !a->have_feat)
+        return fail(ctx, CRP_ERR_STATE, "crp_select_run: require_cds needs the ids of a crp_annotate_lookup on the current tables");
+    crp::SelfJoined joined = {};
+    if (self) {
+        if (!crp::self_joined(self, &joined))
+            return fail(ctx, CRP_ERR_STATE, "crp_select_run: the self-search handle has no joined columns (crp_search_self_join_hits)");
+        if (joined.arena != a) return fail(ctx, CRP_ERR_INVALID, "crp_select_run: the self-search handle belongs to another arena");
+        if (joined.rows[0] != a->n_hits[0] || joined.rows[1] != a->n_hits[1])
+            return fail(ctx, CRP_ERR_STATE, "crp_select_run: the joined columns belong to an earlier scan's tables");
+    }
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    const int k = p->k;
+    const uint64_t G = s->n_genes;
+    int rc = crp::grow(ctx, reinterpret_cast<void **>(&s->res.sel), &s->sel_cap, G * k, sizeof(uint32_t));
+    if (rc != CRP_OK) return rc;
+    for (double &v : s->stats) v = 0;
+    if (!G) {
+        s->k = k;
+        return CRP_OK;
+    }
+    // (a table has fewer rows than the arena positions: below 2^31)
+    const uint32_t n_plus = (uint32_t)a->n_hits[0], n_minus = (uint32_t)a->n_hits[1];
+    CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    CRP_HIP(ctx, crp::launch_select_bounds(ctx->stream, a->d_pos[0], n_plus, a->d_pos[1], n_minus, s->d_lo, s->d_hi, (uint32_t)G, s->d_bounds));
+    CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+    std::vector<uint4> bounds;
+    std::vector<crp::SelectItem> items;
+    std::vector<crp::SelectMerge> merges;
+    uint64_t n_slots = 0, rows_covered = 0;
+    try {
+        bounds.resize(G);
+        rc = crp::staged_d2h(ctx, bounds.data(), s->d_bounds, G * sizeof(uint4));
+        if (rc != CRP_OK) return rc;
+        CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        s->stats[0] = elapsed(s->ev[0], s->ev[1]);
+        // every gene's rows -- its '+' run, then its '-' run -- in pieces of at most slice_rows rows; a gene without rows
+        // still gets one (empty) item, which writes its zeros
+        items.reserve(G + G / 8);
+        for (uint64_t g = 0; g < G; ++g) {
+            const uint4 b = bounds[g];
+            if (b.x > b.y || b.y > n_plus || b.z > b.w || b.w > n_minus)
+                return fail(ctx, CRP_ERR_HIP, "crp_select_run: the bounds of gene " + std::to_string(g) + " lie outside the tables");
+            const uint64_t np = b.y - b.x, nm = b.w - b.z, total = np + nm;
+            rows_covered += total;
+            const uint64_t pieces = std::max<uint64_t>(1, (total + s->slice_rows - 1) / s->slice_rows);
+            if (n_slots + pieces > 0xfffffff0ull || items.size() + pieces > 0xfffffff0ull) return CRP_ERR_UNSUPPORTED;
+            if (pieces > 1) merges.push_back(crp::SelectMerge{(uint32_t)g, (uint32_t)n_slots, (uint32_t)pieces});
+            for (uint64_t c = 0; c < pieces; ++c) {
+                // rows [r0, r1) of the gene's concatenated runs
+                const uint64_t r0 = c * s->slice_rows, r1 = std::min(total, r0 + s->slice_rows);
+                const uint64_t p0 = std::min(r0, np), p1 = std::min(r1, np);
+                const uint64_t m0 = std::max(r0, np) - np, m1 = std::max(r1, np) - np;
+                crp::SelectItem it;
+                it.gene = (uint32_t)g;
+                it.slot = pieces > 1 ? (uint32_t)(n_slots + c) : crp::SELECT_NONE;
+                it.first[0] = b.x + (uint32_t)p0;
+                it.rows[0] = (uint32_t)(p1 - p0);
+                it.first[1] = b.z + (uint32_t)m0;
+                it.rows[1] = (uint32_t)(m1 - m0);
+                items.push_back(it);
+            }
+            if (pieces > 1) n_slots += pieces;
+        }
+    } catch (const std::bad_alloc &) {
+        return CRP_ERR_NOMEM;
+    }
+    rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_items), &s->items_cap, items.size(), sizeof(crp::SelectItem));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_merge), &s->merge_cap, merges.size(), sizeof(crp::SelectMerge));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->part.key), &s->part_entries_cap, n_slots * k, sizeof(uint64_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->part.tie), &s->part_tie_cap, n_slots * k, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->part.row), &s->part_row_cap, n_slots * k, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->part.cnt), &s->part_cnt_cap, n_slots * 2, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::staged_h2d(ctx, s->d_items, items.data(), items.size() * sizeof(crp::SelectItem));
+    if (rc == CRP_OK && !merges.empty()) rc = crp::staged_h2d(ctx, s->d_merge, merges.data(), merges.size() * sizeof(crp::SelectMerge));
+    if (rc != CRP_OK) return rc;
+    crp::SelectTable tab[2];
+    for (int t = 0; t < 2; ++t)
+        tab[t] = crp::SelectTable{a->d_pos[t], a->d_score[t], p->require_cds ? a->d_feat[t] : nullptr, self ? joined.counts[t] : nullptr,
+                                  self ? joined.sum[t] : nullptr, (uint32_t)a->n_hits[t]};
+    crp::SelectPredicate pred = {};
+    pred.min_score = p->min_score;
+    pred.max_hit_sum = p->max_hit_sum;
+    pred.max_mm0 = p->max_mm0;
+    pred.stride = self ? (uint32_t)joined.stride : 0u;
+    pred.flags = p->require_cds ? s->d_flags : nullptr;
+    pred.n_flags = (uint32_t)s->n_flags;
+    pred.k = k;
+    // the bounded-launch rule: at most 2^20 items a launch, each timed on its own
+    for (uint64_t first = 0; first < items.size(); first += crp::SELECT_MAX_ITEMS) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(crp::SELECT_MAX_ITEMS, items.size() - first);
+        CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+        CRP_HIP(ctx, crp::launch_select_items(ctx->stream, tab[0], tab[1], pred, s->d_items + first, n, s->part, s->res));
+        CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+        CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const double ms = elapsed(s->ev[0], s->ev[1]);
+        s->stats[1] += ms;
+        s->stats[4] += 1;
+        s->stats[5] = std::max(s->stats[5], ms);
+    }
+    for (uint64_t first = 0; first < merges.size(); first += crp::SELECT_MAX_ITEMS) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(crp::SELECT_MAX_ITEMS, merges.size() - first);
+        CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+        CRP_HIP(ctx, crp::launch_select_merge(ctx->stream, s->d_merge + first, n, k, s->part, s->res));
+        CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+        CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        s->stats[2] += elapsed(s->ev[0], s->ev[1]);
+    }
+    s->stats[3] = (double)items.size();
+    s->stats[6] = (double)rows_covered;
+    // position + score, the label-set id under require_cds, and with joined columns counts[0] and hit_sum
+    s->stats[7] = 12.0 + (p->require_cds ? 4.0 : 0.0) + (self ? 12.0 : 0.0);
+    s->stats[8] = (double)merges.size();
+    s->k = k;
+    return CRP_OK;
+}
+
+int crp_select_fetch(crp_select *s, uint32_t *n_in, uint32_t *n_pass, uint32_t *sel)
+{
+    if (!s) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    if (!s->k) return fail(ctx, CRP_ERR_STATE, "crp_select_fetch: no crp_select_run has succeeded on this handle");
+    if (!s->n_genes) return CRP_OK;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = CRP_OK;
+    if (n_in) rc = crp::staged_d2h(ctx, n_in, s->res.n_in, s->n_genes * sizeof(uint32_t));
+    if (rc == CRP_OK && n_pass) rc = crp::staged_d2h(ctx, n_pass, s->res.n_pass, s->n_genes * sizeof(uint32_t));
+    if (rc == CRP_OK && sel) rc = crp::staged_d2h(ctx, sel, s->res.sel, s->n_genes * s->k * sizeof(uint32_t));
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CRP_OK;
+}
+
+int crp_select_stats(const crp_select *s, double *out, int n)
+{
+    if (!s || (n && !out) || n < 0 || n > 9) return CRP_ERR_INVALID;
+    for (int k = 0; k < n; ++k) out[k] = s->stats[k];
+    return CRP_OK;
+}
+
+}  // extern "C"

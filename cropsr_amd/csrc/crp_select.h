@@ -1,0 +1,64 @@
+// crp_select.h -- launch interface of crp_select.hip (guide selection: the best K rows of every gene, DESIGN section
+// 16), shared with its host side crp_select.cpp.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace crp {
+
+constexpr int SELECT_WAVES = 4;                 // work items per workgroup: one wave each
+constexpr uint32_t SELECT_NONE = 0xFFFFFFFFu;   // no row / an item that writes the gene's result itself
+constexpr uint32_t SELECT_MAX_ITEMS = 1u << 20; // work items per launch
+
+// The columns of one strand's table, as far as a run reads them (feat / counts / sum may be null).
+struct SelectTable {
+    const uint32_t *pos;
+    const double *score;
+    const uint32_t *feat;              // label-set ids (require_cds)
+    const uint32_t *counts;            // joined self-search counts, `stride` per row: counts[0] is read
+    const unsigned long long *sum;     // joined hit_sum
+    uint32_t n;
+};
+
+struct SelectPredicate {
+    double min_score;
+    unsigned long long max_hit_sum;
+    uint32_t max_mm0;
+    uint32_t stride;        // 0: no joined columns
+    const uint8_t *flags;   // null: no CDS filter
+    uint32_t n_flags;
+    int k;
+};
+
+// One wave's work: rows [first[s], first[s] + rows[s]) of strand s's table, all inside gene `gene`'s runs.  slot ==
+// SELECT_NONE: the item is the whole gene and writes its result; else it writes its partial list to that slot.
+struct SelectItem {
+    uint32_t gene, slot;
+    uint32_t first[2], rows[2];
+};
+
+// A gene that was cut into several items: their slots are consecutive.
+struct SelectMerge {
+    uint32_t gene, slot, n_slots;
+};
+
+// The partial lists: k entries per slot (key = the score's bits, tie = cut site << 1 | strand, row = row | strand << 31;
+// row SELECT_NONE: no entry) and two counts (rows in the gene, passing rows).
+struct SelectPartials {
+    unsigned long long *key;
+    uint32_t *tie, *row, *cnt;
+};
+
+struct SelectResult {
+    uint32_t *n_in, *n_pass, *sel;
+};
+
+// bounds[g] = {first '+' row with cut >= lo, first with cut > hi, the same for '-'}
+hipError_t launch_select_bounds(hipStream_t s, const uint32_t *pos_plus, uint32_t n_plus, const uint32_t *pos_minus, uint32_t n_minus,
+                                const uint32_t *lo, const uint32_t *hi, uint32_t n_genes, uint4 *bounds);
+hipError_t launch_select_items(hipStream_t s, const SelectTable &plus, const SelectTable &minus, const SelectPredicate &pred,
+                               const SelectItem *items, uint32_t n_items, const SelectPartials &part, const SelectResult &res);
+hipError_t launch_select_merge(hipStream_t s, const SelectMerge *genes, uint32_t n_genes, int k, const SelectPartials &part,
+                               const SelectResult &res);
+
+}  // namespace crp

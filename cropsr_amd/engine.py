@@ -728,16 +728,64 @@ class Genome:
         from . import search
         return search.specificity_columns(self, guide_len, max_mm=max_mm, candidate_pam=candidate_pam, score=score, budget=budget)
 
-    def scan_score(self, guide_len=20, want_pre=False, offtarget=False, seeds_from_scan=True, annotation=None, specificity=None):
+    def select(self, request, hits, counts=None, handle_of=None, joined=None, annotated=False):
+        """The best K guides of every gene (select.Request; the module's docstring has the definition) over the tables
+        of the last scan at guide length 20, which `hits` (GenomeHits) holds as host copies.  Runs after the annotation
+        look-up and -- with handle_of(arena index) -> the arena's joined search.ArenaSelfSearch and joined[arena index] =
+        its (counts_plus, sum_plus, counts_minus, sum_minus) -- between the specificity join and the closing of its
+        handles.  annotated: the arenas hold the ids of an annotation look-up on these tables (else require_cds runs one).
+        Returns select.Selection: for every gene of the GFF in file order its label, n_in, n_pass and the selected rows
+        (contig, position, strand, score, and the joined counts and sum when present)."""
+        from . import select as sel
+        if request.params.needs_specificity and handle_of is None:
+            raise ValueError("max_perfect / min_specificity need the specificity join (scan_score(specificity=...))")
+        labels = request.annotation.annotation.genes()[0]
+        if request.params.require_cds and not annotated:
+            keep = self.annotate_s
+            self.annotate(request.annotation, [(h.n_plus, h.n_minus) for h in hits.per_arena], fetch=False)
+            self.annotate_s = keep
+        flags = request.annotation.annotation.cds_flags() if request.params.require_cds else None
+        parts, stats = [], {}
+        for a, h in enumerate(hits.per_arena):
+            handle = handle_of(a) if handle_of is not None else None
+            lo, hi, gene, n_in, n_pass, picked, st = sel.select_arena(self, a, request, handle, flags)
+            part = dict(offsets=self.arenas[a].offsets, lengths=self.arenas[a].lengths, group=self.groups[a], pos_plus=h.pos_plus,
+                        score_plus=h.score_plus, pos_minus=h.pos_minus, score_minus=h.score_minus, gene=gene, n_in=n_in, n_pass=n_pass,
+                        sel=picked)
+            if joined is not None:
+                part["counts_plus"], part["sum_plus"], part["counts_minus"], part["sum_minus"] = joined[a]
+            parts.append(part)
+            sel.sum_stats(stats, st)
+        return sel.assemble(labels, request.params.k, parts, stats)
+
+    def scan_score(self, guide_len=20, want_pre=False, offtarget=False, seeds_from_scan=True, annotation=None, specificity=None,
+                   select=None):
         """Seam 1 + 2 for every contig.  offtarget=True also runs the genome-wide seed scan over all
         arenas (single process: no reduce) and attaches (n, 4) counts to every contig's hits;
         seeds_from_scan=False makes the off-target step derive its seeds from the planes itself (the
         path guide lengths other than 20 always take) instead of receiving them from the scan.
         specificity (a dict of specificity_columns' arguments, {} for the defaults): every contig's hits also carry the
-        self search's counts and sums, joined on the GPU while the tables are resident."""
+        self search's counts and sums, joined on the GPU while the tables are resident.
+        select (select.Request): hits.selection is the best K guides of every gene (Genome.select), chosen on the GPU after
+        the annotation look-up and, with specificity, between its join and the closing of the self-search handles."""
+        if select is not None and guide_len != 20:
+            raise ValueError("the guide selection ranks by the on-target score, which exists at guide length 20 only")
         hits = self._scan_score(guide_len, want_pre, offtarget, seeds_from_scan, annotation)
         if specificity is not None:  # (the tables of an arena stay valid until its next scan)
-            hits.columns = self.specificity_columns(guide_len, **specificity)
+            if select is None:
+                hits.columns = self.specificity_columns(guide_len, **specificity)
+            else:
+                from . import search
+                handles, joined = {}, {}
+
+                def after_join(a, handle, cols):
+                    handles[a], joined[a] = handle, cols
+                    if len(handles) == len(self.arenas):  # every arena has joined, no handle has closed yet
+                        hits.selection = self.select(select, hits, handle_of=handles.get, joined=joined, annotated=annotation is not None)
+
+                hits.columns = search.specificity_columns(self, guide_len, after_join=after_join, **specificity)
+        elif select is not None:
+            hits.selection = self.select(select, hits, annotated=annotation is not None)
         return hits
 
     def _scan_score(self, guide_len, want_pre, offtarget, seeds_from_scan, annotation):
@@ -799,6 +847,7 @@ class GenomeHits:
         self.n_plus = sum(h.n_plus for h in per_arena)
         self.n_minus = sum(h.n_minus for h in per_arena)
         self.columns = None  # per contig, further columns of its rows (Genome.scan_score(specificity=..))
+        self.selection = None  # select.Selection (Genome.scan_score(select=..))
 
     def contig(self, k):
         a, j = self._genome._where[k]

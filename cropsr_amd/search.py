@@ -1034,21 +1034,25 @@ def check_specificity(guide_len, max_mm=3, candidate_pam="NRG", score="hsu2013")
     return pattern, gp, M, scheme
 
 
-def specificity_columns(genome, guide_len, max_mm=3, candidate_pam="NRG", score="hsu2013", budget=None):
+def specificity_columns(genome, guide_len, max_mm=3, candidate_pam="NRG", score="hsu2013", budget=None, after_join=None):
     """The genome-wide specificity of every hit of a scanned `genome` (engine.Genome whose arenas hold the tables of a scan
     at guide_len): the self search of N * l + NGG guides among N * l + candidate_pam candidates over all arenas, then each
     arena's tables joined against its own handle on the GPU (the module's docstring, CSV join).  Returns one dict per
     contig, in contig order: self_counts_plus / self_counts_minus (n, M + 1) uint32 and self_sum_plus / self_sum_minus (n,)
     uint64, rows as Hits.contig(k) has them.  score=None: counts only (the sums are all-ones).  The dicts' list carries
-    .stats, the handles' times summed over the arenas (join_ms among them)."""
+    .stats, the handles' times summed over the arenas (join_ms among them).  after_join(arena index, handle, (counts_plus,
+    sum_plus, counts_minus, sum_minus)) is called for every arena while its joined columns are still in HBM on the handle
+    (the guide selection reads them there: they die when the handles close)."""
     pattern, gp, M, scheme = check_specificity(guide_len, max_mm, candidate_pam, score)
     out = [None] * genome.n_contigs
     handles, stats = [], {}
     try:
         _self_handles(genome, pattern, gp, SPECIFICITY_PAM_LEN, M, scheme, budget, None, handles)
         _self_compare_all(handles, M)
-        for h, a, group in zip(handles, genome.arenas, genome.groups):
+        for index, (h, a, group) in enumerate(zip(handles, genome.arenas, genome.groups)):
             cp, sp, cm, sm = h.join_hits(guide_len)
+            if after_join is not None:
+                after_join(index, h, (cp, sp, cm, sm))
             pos_plus, pos_minus = np.empty(len(sp), np.uint32), np.empty(len(sm), np.uint32)
             nat.check(nat.lib().crp_fetch_hits(a._h, pos_plus.ctypes.data_as(nat.u32p), None, None, pos_minus.ctypes.data_as(nat.u32p), None,
                                                None), "crp_fetch_hits", a._engine._ctx)

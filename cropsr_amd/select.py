@@ -1,0 +1,265 @@
+"""--select K: the best K guides of every gene, chosen on the GPU.
+
+Not in the reference, opt-in.  The guide table ends as one row per PAM hit; the question "which guides do I order for
+this gene?" is a reduction of it, and it is computed where the columns already are: a segmented top-K over runs of the
+resident hit tables (csrc/crp_select.hip).
+
+Definition, per arena, after a crp_scan_score at guide length 20 (tests/select_reference.py restates it twice):
+
+  genes     the GFF rows crp_annotation.cpp accepts with type `gene`, in file order.  A gene's label is the
+            "gene:<ident>" text the annotation join prints, without the Phytozome suffix.  Its range [start, end]
+            (1-based, closed) is mapped to arena positions by the rule of crp_annotation_track -- string index =
+            coordinate + dec - 1, plus the text's arena offset -- and clipped to the text.  A gene has NO RANGE when
+            start > end, when its seqid names no contig of the arena, or when clipping leaves nothing: it is still
+            listed, with zero rows.  Genes may overlap, nest or repeat; each is selected for on its own, so a row may
+            be chosen for several genes.
+  cut site  of a row: i - 3 on the '+' table, j on the '-' table (as annot_lookup_kernel); only rows whose score is
+            not -1 have one.
+  in        a row is IN a gene when it has a cut site and lo <= cut site <= hi.  The tables ascend in position, so a
+            gene's rows are one contiguous run per strand table.
+  passes    a row PASSES when it is in the gene; its score >= min_score (float64); with joined specificity columns it
+            is joined (counts[0] != 0xFFFFFFFF), counts[0] <= max_mm0 and hit_sum <= max_hit_sum (integer compares);
+            and with require_cds the flag byte of its label-set id is non-zero (NO_FEATURE fails; the flag is 1 for a
+            label-set string that holds a `CDS:` label, computed on the host from the string table).
+  order     among passing rows: higher score first -- scores are positive finite doubles, so their bit patterns order
+            as unsigned 64-bit integers --, ties (repeats give identical 30-mers) by smaller cut site, then '+' before
+            '-'.  The order is total: the result does not depend on how the work was cut.
+  result    per gene g, all exact: n_in[g] (rows in the gene), n_pass[g] (passing rows) and sel[g][0..K): the first
+            min(K, n_pass) passing rows in that order, each as row index | strand << 31, 0xFFFFFFFF beyond.  K = 1..64.
+
+This module lays the genes out per arena, converts a wanted specificity into the integer bound the kernel compares,
+drives crp_select_* and turns the per-arena results into one table over the genes of the GFF.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _native as nat
+
+MAX_K = nat.SELECT_MAX_K
+NONE = nat.SELECT_NONE
+NO_BOUND_MM0, NO_BOUND_SUM = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
+GUIDE_LEN = 20  # the ranking key, the on-target score, exists only there
+ROW_DTYPE = np.dtype([("gene", "<u4"), ("rank", "<u4"), ("contig", "<u4"), ("position", "<i8"), ("strand", "S1"), ("score", "<f8"),
+                      ("index", "<u4")])
+
+
+def max_hit_sum_for(S):
+    """The largest integer h with search.specificity(h) >= S, found by bisection on that very function (so that the
+    threshold agrees with the printed `specificity` column); S <= 0: no bound (2^64 - 1).  S > 1 has no such h."""
+    from .search import specificity
+    S = float(S)
+    if not S <= 1.0:
+        raise ValueError("a specificity threshold above 1 (or not a number) keeps no guide: %r" % (S,))
+    if S <= 0.0:
+        return NO_BOUND_SUM
+    ok = lambda h: bool(specificity(np.uint64(h)) >= S)
+    lo, hi = 0, NO_BOUND_SUM  # ok(lo) holds: specificity(0) = 1
+    if ok(hi):
+        return hi
+    while hi - lo > 1:  # ok(lo) and not ok(hi); specificity never rises with h
+        mid = (lo + hi) // 2
+        if ok(mid):
+            lo = mid
+        else:
+            hi = mid
+    return lo
+
+
+class Params:
+    """What a selection asks for: K, min_score, max_perfect (most other perfect copies, counts[0]; None: no bound),
+    min_specificity (None or <= 0: no bound) and require_cds.  The two specificity thresholds need joined columns."""
+
+    def __init__(self, k, min_score=0.0, max_perfect=None, min_specificity=None, require_cds=False):
+        self.k = int(k)
+        if not 1 <= self.k <= MAX_K:
+            raise ValueError("K must be 1..%d, not %d" % (MAX_K, self.k))
+        self.min_score = float(min_score)
+        if self.min_score != self.min_score:
+            raise ValueError("min_score is not a number")
+        self.max_mm0 = NO_BOUND_MM0 if max_perfect is None else int(max_perfect)
+        if not 0 <= self.max_mm0 <= NO_BOUND_MM0:
+            raise ValueError("max_perfect must be a count, not %r" % (max_perfect,))
+        self.max_hit_sum = NO_BOUND_SUM if min_specificity is None else max_hit_sum_for(min_specificity)
+        self.needs_specificity = max_perfect is not None or (min_specificity is not None and float(min_specificity) > 0.0)
+        self.require_cds = bool(require_cds)
+
+    def native(self):
+        return nat.SelectParams(self.min_score, self.max_hit_sum, self.max_mm0, self.k, int(self.require_cds), 0)
+
+
+class Request:
+    """A selection for a backend's scan: Params, the annotate.Request that names the genes, and slice_rows (None: the
+    library's default; results do not depend on it)."""
+
+    def __init__(self, params, annotation, slice_rows=None):
+        self.params, self.annotation, self.slice_rows = params, annotation, slice_rows
+
+
+class ArenaSelect:
+    """One crp_select handle: the genes of one arena as closed ranges of arena positions."""
+
+    def __init__(self, arena, lo, hi):
+        self._arena = arena
+        self._ctx = arena._engine._ctx
+        self._h = None
+        lo, hi = np.ascontiguousarray(lo, dtype=np.uint32), np.ascontiguousarray(hi, dtype=np.uint32)
+        if lo.shape != hi.shape or lo.ndim != 1:
+            raise ValueError("lo and hi must be 1-d arrays of one length")
+        self.n_genes, self.k = int(lo.size), 0
+        h = ctypes.c_void_p()
+        nat.check(nat.lib().crp_select_create(arena._h, lo.ctypes.data_as(nat.u32p), hi.ctypes.data_as(nat.u32p), lo.size, ctypes.byref(h)),
+                  "crp_select_create", self._ctx)
+        self._h = h
+
+    def close(self):
+        if self._h:
+            nat.lib().crp_select_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def set_flags(self, flags):
+        flags = np.ascontiguousarray(flags, dtype=np.uint8)
+        nat.check(nat.lib().crp_select_set_flags(self._h, flags.ctypes.data_as(nat.u8p), flags.size), "crp_select_set_flags", self._ctx)
+
+    def set_limits(self, slice_rows=0):
+        nat.check(nat.lib().crp_select_set_limits(self._h, int(slice_rows)), "crp_select_set_limits", self._ctx)
+
+    def run(self, params, self_search=None):
+        """params: Params; self_search: the search.ArenaSelfSearch of this arena after its join_hits, or None."""
+        p = params.native()
+        nat.check(nat.lib().crp_select_run(self._h, ctypes.byref(p), self_search._h if self_search is not None else None),
+                  "crp_select_run", self._ctx)
+        self.k = params.k
+
+    def fetch(self):
+        """(n_in uint32 (G,), n_pass uint32 (G,), sel uint32 (G, K)) of the last run."""
+        n_in, n_pass = np.empty(self.n_genes, np.uint32), np.empty(self.n_genes, np.uint32)
+        sel = np.empty((self.n_genes, max(1, self.k)), np.uint32)
+        nat.check(nat.lib().crp_select_fetch(self._h, n_in.ctypes.data_as(nat.u32p), n_pass.ctypes.data_as(nat.u32p),
+                                             sel.ctypes.data_as(nat.u32p)), "crp_select_fetch", self._ctx)
+        return n_in, n_pass, sel
+
+    def stats(self):
+        out = np.zeros(9, dtype=np.float64)
+        nat.check(nat.lib().crp_select_stats(self._h, out.ctypes.data_as(nat.f64p), 9), "crp_select_stats", self._ctx)
+        keys = ("bounds_ms", "select_ms", "merge_ms", "items", "launches", "longest_launch_ms", "rows_in_runs", "bytes_per_row",
+                "merged_genes")
+        return dict(zip(keys, (float(v) for v in out)))
+
+
+def arena_layout(genome, a):
+    """[(contig index, arena offset, length)] of arena `a` of an engine.Genome, as annotate.Request.track takes it."""
+    arena = genome.arenas[a]
+    return [(k, int(arena.offsets[j]), int(arena.lengths[j])) for j, k in enumerate(genome.groups[a])]
+
+
+class HitList(list):
+    """A backend's per-contig hit dicts, with .selection (Selection) when the scan was asked to select."""
+    selection = None
+
+
+class Selection:
+    """The selection over all genes of the GFF, in file order: labels, n_in, n_pass (per gene) and rows (ROW_DTYPE, gene
+    after gene, rank 1 first; `index` is the row's place in its contig's strand table, `position` its match index local
+    to the contig string), with counts (n, M + 1) uint32 and hit_sum (n,) uint64 of the rows when they were joined."""
+
+    def __init__(self, labels, n_in, n_pass, rows, counts=None, hit_sum=None, stats=None):
+        self.labels, self.n_in, self.n_pass, self.rows = labels, n_in, n_pass, rows
+        self.counts, self.hit_sum, self.stats = counts, hit_sum, stats or {}
+
+    def of_gene(self, g):
+        return self.rows[self.rows["gene"] == g]
+
+
+def _take(plus, minus, is_minus, row, dtype):
+    """plus[row] where the row is a '+' row, minus[row] where it is a '-' row."""
+    out = np.empty(row.size, dtype)
+    out[~is_minus] = np.asarray(plus)[row[~is_minus]]
+    out[is_minus] = np.asarray(minus)[row[is_minus]]
+    return out
+
+
+def assemble(labels, k, arenas, stats=None):
+    """One Selection from per-arena results.  arenas: dicts with offsets / lengths (of the arena's texts), group (their
+    contig indices), pos_plus / score_plus / pos_minus / score_minus (the tables, arena positions), gene (layout row ->
+    gene index), n_in, n_pass, sel (layout rows x K), and optionally counts_plus / sum_plus / counts_minus / sum_minus.
+    A gene that has rows in several texts (two contigs of one name) gets the sums of its counts and the first K of its
+    rows in the definition's order, texts in arena order."""
+    G = len(labels)
+    n_in, n_pass = np.zeros(G, np.int64), np.zeros(G, np.int64)
+    parts, cparts, sparts = [], [], []
+    joined = any(a.get("counts_plus") is not None for a in arenas)
+    for a in arenas:
+        gene = np.asarray(a["gene"], dtype=np.int64)
+        np.add.at(n_in, gene, np.asarray(a["n_in"], dtype=np.int64))
+        np.add.at(n_pass, gene, np.asarray(a["n_pass"], dtype=np.int64))
+        sel = np.asarray(a["sel"], dtype=np.uint32).reshape(gene.size, -1)[:, :k]
+        r, c = np.nonzero(sel != NONE)
+        packed = sel[r, c]
+        minus = (packed >> np.uint32(31)).astype(bool)
+        row = (packed & np.uint32(0x7FFFFFFF)).astype(np.int64)
+        part = np.empty(row.size, ROW_DTYPE)
+        offs = np.asarray(a["offsets"], dtype=np.int64)
+        pos = _take(a["pos_plus"], a["pos_minus"], minus, row, np.int64)
+        t = np.searchsorted(offs, pos, "right") - 1
+        part["gene"], part["rank"] = gene[r], c + 1
+        part["contig"] = np.asarray(a["group"], dtype=np.uint32)[t]
+        part["position"] = pos - offs[t]
+        part["strand"] = np.where(minus, b"-", b"+")
+        part["score"] = _take(a["score_plus"], a["score_minus"], minus, row, np.float64)
+        # the row's place in its contig's strand table: the rows of the texts before it, taken off
+        first_plus = np.searchsorted(np.asarray(a["pos_plus"]), offs.astype(np.uint32), "left")
+        first_minus = np.searchsorted(np.asarray(a["pos_minus"]), offs.astype(np.uint32), "left")
+        part["index"] = row - np.where(minus, first_minus[t], first_plus[t])
+        parts.append(part)
+        if joined:
+            cp, cm = np.asarray(a["counts_plus"], dtype=np.uint32), np.asarray(a["counts_minus"], dtype=np.uint32)
+            width = cp.shape[1] if cp.ndim == 2 else cm.shape[1]
+            cp, cm = cp.reshape(-1, width), cm.reshape(-1, width)
+            c_rows = np.empty((row.size, width), np.uint32)
+            c_rows[~minus], c_rows[minus] = cp[row[~minus]], cm[row[minus]]
+            cparts.append(c_rows)
+            sparts.append(_take(a["sum_plus"], a["sum_minus"], minus, row, np.uint64))
+    rows = np.concatenate(parts) if parts else np.empty(0, ROW_DTYPE)
+    counts = np.concatenate(cparts) if cparts else None
+    sums = np.concatenate(sparts) if sparts else None
+    # genes in file order; a gene met in several texts: its rows in the definition's order, the first K of them
+    key = rows["score"].view(np.uint64)
+    order = np.lexsort((np.arange(rows.size), np.iinfo(np.uint64).max - key, rows["gene"]))
+    rows = rows[order]
+    start = np.searchsorted(rows["gene"], rows["gene"], "left")
+    rank = np.arange(rows.size) - start
+    keep = rank < k
+    rows = rows[keep]
+    rows["rank"] = rank[keep] + 1
+    if counts is not None:
+        counts, sums = counts[order][keep], sums[order][keep]
+    return Selection(list(labels), n_in, n_pass, rows, counts, sums, stats)
+
+
+def select_arena(genome, a, request, handle=None, flags=None):
+    """The selection of one arena of an engine.Genome whose tables are resident: (lo, hi, gene, n_in, n_pass, sel, stats).
+    handle: the arena's search.ArenaSelfSearch after join_hits, or None."""
+    lo, hi, gene = request.annotation.gene_layout(arena_layout(genome, a))
+    sel = ArenaSelect(genome.arenas[a], lo, hi)
+    try:
+        if request.params.require_cds:
+            sel.set_flags(flags if flags is not None else request.annotation.annotation.cds_flags())
+        if request.slice_rows:
+            sel.set_limits(request.slice_rows)
+        sel.run(request.params, handle)
+        n_in, n_pass, picked = sel.fetch()
+        return lo, hi, gene, n_in, n_pass, picked, sel.stats()
+    finally:
+        sel.close()
+
+
+def sum_stats(total, one):
+    for key, v in one.items():
+        if key == "bytes_per_row":
+            total[key] = v
+        else:
+            total[key] = max(total.get(key, 0.0), v) if key == "longest_launch_ms" else total.get(key, 0.0) + v
+    return total

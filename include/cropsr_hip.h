@@ -758,6 +758,70 @@ int crp_search_self_join_hits(crp_search_self *self, int guide_len, uint32_t *co
 int crp_search_self_join_device(crp_search_self *self, void **counts_plus, void **hit_sum_plus, void **counts_minus,
                                 void **hit_sum_minus);
 
+/* ---- guide selection: the best K guides of every gene -------------------------------- */
+/* The gene rows of an annotation (type `gene`, file order): index of the seqid (crp_annotation_seqid), start and end
+ * as the GFF gives them (1-based, closed), and the labels "gene:<ident>" -- without the annotation_info suffix -- back
+ * to back in label_blob with n_genes + 1 offsets.  n_genes is crp_annotation_stats'; *label_bytes the blob's size.
+ * Any pointer may be NULL. */
+int crp_annotation_genes(const crp_annotation *an, uint64_t *seqid, int64_t *start, int64_t *end, uint8_t *label_blob,
+                         uint64_t *label_off, uint64_t *label_bytes);
+/* The genes of the texts of one arena, in arena positions: entries and dec as crp_annotation_track takes them (the
+ * same mapping: string index = coordinate + dec - 1 - first, plus the text's arena offset), each gene's range clipped
+ * to the text.  One row per (text, gene of its seqid) that keeps at least one position, texts in arena order, genes
+ * in file order: lo[], hi[] (closed) and gene[], the gene's index in crp_annotation_genes.  A gene with start > end,
+ * with a seqid no text names or outside its text has no row.  Capacity protocol as crp_annotation_track. */
+int crp_annotation_gene_layout(const crp_annotation *an, const uint64_t *entries, uint64_t n_entries, int dec, uint32_t *lo,
+                               uint32_t *hi, uint64_t *gene, uint64_t cap, uint64_t *n_out);
+/* One byte per label-set string (crp_annotation_stats' n_strings): 1 when the set holds a CDS label. */
+int crp_annotation_cds_flags(const crp_annotation *an, uint8_t *flags);
+
+/* A segmented top-K over the hit tables of an arena's last crp_scan_score at guide length 20.  Gene g is the closed
+ * range [lo[g], hi[g]] of arena positions.  A row has a cut site when its score is not -1: match index i - 3 on the
+ * '+' table, j on the '-' table (as crp_annotate_lookup).  It is IN gene g when lo[g] <= cut site <= hi[g], and it
+ * PASSES when also
+ *   score >= min_score                                                          (float64)
+ *   with a self-search handle: counts[0] != 0xFFFFFFFF (joined), counts[0] <= max_mm0 and hit_sum <= max_hit_sum
+ *   with require_cds: the flag of its label-set id is non-zero (CRP_NO_FEATURE fails)
+ * Passing rows are ordered by higher score (as its 64 bits, unsigned), then smaller cut site, then '+' before '-': a
+ * total order, so the result does not depend on how the work is cut.  Per gene: n_in (rows in it), n_pass (passing
+ * rows) and sel[g * K .. g * K + K): the first min(K, n_pass) passing rows as row index | strand << 31, 0xFFFFFFFF
+ * beyond.  Genes may overlap or repeat; each is selected for on its own. */
+typedef struct crp_select crp_select;
+typedef struct crp_select_params {
+    double min_score;
+    uint64_t max_hit_sum; /* read with a self-search handle only */
+    uint32_t max_mm0;     /* read with a self-search handle only */
+    int32_t k;            /* 1 .. CRP_SELECT_MAX_K */
+    int32_t require_cds;
+    int32_t reserved;
+} crp_select_params;
+#define CRP_SELECT_MAX_K 64
+#define CRP_SELECT_DEFAULT_SLICE_ROWS 65536
+#define CRP_SELECT_MIN_SLICE_ROWS 64
+#define CRP_SELECT_NONE 0xFFFFFFFFu
+/* lo / hi: n_genes closed ranges, lo <= hi < 2^31 (CRP_ERR_INVALID otherwise); CRP_ERR_STATE: arena not sealed.  The
+ * arena must outlive the handle. */
+int crp_select_create(crp_arena *arena, const uint32_t *lo, const uint32_t *hi, uint64_t n_genes, crp_select **out);
+int crp_select_destroy(crp_select *select);
+/* The CDS flag of every label-set id (crp_annotation_cds_flags), for require_cds. */
+int crp_select_set_flags(crp_select *select, const uint8_t *flags, uint64_t n_flags);
+/* A gene's rows are cut into work items of at most slice_rows rows, one wave each (0 = the default, 65 536; at
+ * least 64); one launch covers at most 2^20 items.  Results do not depend on it. */
+int crp_select_set_limits(crp_select *select, uint64_t slice_rows);
+/* self: NULL, or the self-search handle of the same arena after its crp_search_self_join_hits on the current tables.
+ * CRP_ERR_STATE with a crp_last_error text: no hit tables of guide length 20, require_cds without flags or without
+ * the ids of a crp_annotate_lookup on the current tables, a handle that has not joined.  CRP_ERR_INVALID: k out of
+ * range, a min_score that is NaN, a handle of another arena. */
+int crp_select_run(crp_select *select, const crp_select_params *params, crp_search_self *self);
+/* The results of the last run (CRP_ERR_STATE without one): n_in and n_pass (n_genes each) and sel (n_genes * k).
+ * Any pointer may be NULL. */
+int crp_select_fetch(crp_select *select, uint32_t *n_in, uint32_t *n_pass, uint32_t *sel);
+/* Measurement of the last run: out[0] ms of the bounds kernel, out[1] ms of the select launches, out[2] ms of the
+ * merge launches (HIP events), out[3] work items, out[4] select launches, out[5] the longest select launch in ms,
+ * out[6] table rows the items cover, out[7] bytes read per such row, out[8] genes that went through the merge.
+ * n: how many of these to write (<= 9). */
+int crp_select_stats(const crp_select *select, double *out, int n);
+
 /* ---- options -------------------------------------------------------------- */
 /* CRP_OPT_TWO_PASS (value 0/1, default 0): with 0 crp_scan_score is ONE kernel launch; the
  * table offsets come from a chained scan across workgroups inside it (decoupled look-back
