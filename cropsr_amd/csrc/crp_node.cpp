@@ -30,7 +30,6 @@
 #include <unistd.h>
 
 #include <algorithm>
-#include <array>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -51,20 +50,11 @@
 
 namespace {
 
-struct NodePiece {
-    uint64_t contig, start, end;  // the piece [start, end) of contig string `contig`
-    int dev;                      // logical device
-    uint32_t slot;                // which of that device's arenas
-    uint64_t text_lo, text_len;   // the characters uploaded for it: [text_lo, text_lo + text_len) of the contig (piece + halos)
-    uint64_t arena_off;           // arena offset of the text's first character in that arena
-};
-
 // One arena of a device and what the gatherv keeps beside it.  The buffers only grow and outlive the genome (a node serves
 // genome after genome); `arena` is what a load creates and the next one destroys.
 struct NodeSlot {
     crp_arena *arena = nullptr;
-    std::vector<uint32_t> pieces;  // indices into crp_node::pieces, arena order (= contig order)
-    uint64_t words = 1;            // arena words its texts need (crp_arena_words_total)
+    size_t piece0 = 0, n_pieces = 0;  // its pieces: [piece0, piece0 + n_pieces) of crp_node::pieces, arena order (= contig order)
     // ownership cuts: two needles per piece (begin and end of its owned arena positions), searched in both tables
     uint32_t *d_needles = nullptr, *d_bounds = nullptr;
     uint64_t needles_cap = 0, bounds_cap = 0;
@@ -194,7 +184,10 @@ std::atomic<int> g_boot_stuck{0};
 struct crp_node {
     std::vector<NodeDev> dev;
     std::vector<std::unique_ptr<NodeWorker>> workers;  // [k]: device k's scan thread (none for device 0), started by the first scan
-    std::vector<NodePiece> pieces;
+    // the pieces of the current genome, device after device and arena after arena (crp::Piece::group: which of its device's
+    // arenas), and for each the arena offset of its text's first character (load_device)
+    std::vector<crp::Piece> pieces;
+    std::vector<uint64_t> arena_off;
     uint64_t n_contigs = 0;
     bool loaded = false;
     bool duplicates = false;  // a device listed twice: RCCL cannot be used
@@ -289,12 +282,12 @@ void free_genome(crp_node *node)
         for (auto &sl : d.slots) {
             if (sl->arena) (void)crp_arena_destroy(sl->arena);
             sl->arena = nullptr;
-            sl->pieces.clear();
-            sl->words = 1;
+            sl->piece0 = sl->n_pieces = 0;
         }
         d.n_slots = 0;
     }
     node->pieces.clear();
+    node->arena_off.clear();
     node->n_contigs = 0;
     node->loaded = false;
     node->have_gather = false;
@@ -321,29 +314,26 @@ int load_device(crp_node *node, int k, const uint8_t *const *texts)
     crp_ctx *ctx = d.ctx;
     for (size_t j = 0; j < d.n_slots; ++j) {
         NodeSlot &sl = *d.slots[j];
-        const size_t np = sl.pieces.size();
+        const size_t np = sl.n_pieces;
+        const crp::Piece *pieces = node->pieces.data() + sl.piece0;
+        uint64_t *offs = node->arena_off.data() + sl.piece0;
         std::vector<const uint8_t *> ptrs(np);
-        std::vector<uint64_t> lens(np), offs(np);
+        std::vector<uint64_t> lens(np);
         uint64_t words = 0;
         for (size_t q = 0; q < np; ++q) {
-            const NodePiece &p = node->pieces[sl.pieces[q]];
+            const crp::Piece &p = pieces[q];
             ptrs[q] = texts[p.contig] + p.text_lo;
             lens[q] = p.text_len;
             words += crp_arena_words_for(p.text_len);
         }
         int rc = crp_arena_create(ctx, crp_arena_words_total(words), &sl.arena);
-        if (rc == CRP_OK) rc = crp_arena_add_contigs_ascii(sl.arena, ptrs.data(), lens.data(), np, offs.data());
+        if (rc == CRP_OK) rc = crp_arena_add_contigs_ascii(sl.arena, ptrs.data(), lens.data(), np, offs);
         if (rc == CRP_OK) rc = crp_arena_seal(sl.arena);
         if (rc != CRP_OK) return rc;
-        for (size_t q = 0; q < np; ++q) node->pieces[sl.pieces[q]].arena_off = offs[q];
-        // the ownership needles of this arena, resident from now on
-        std::vector<uint32_t> needles(2 * np);
-        for (size_t q = 0; q < np; ++q) {
-            const NodePiece &p = node->pieces[sl.pieces[q]];
-            const uint64_t begin = p.arena_off + (p.start - p.text_lo);
-            needles[2 * q] = (uint32_t)begin;
-            needles[2 * q + 1] = (uint32_t)(begin + (p.end - p.start));
-        }
+        // the ownership needles of this arena, resident from now on, and its own piece map (begin[], then sub[]): what turns an
+        // arena position of an owned row into the position inside its contig
+        std::vector<uint32_t> needles(2 * np), map(2 * np);
+        crp::piece_cuts(pieces, np, offs, needles.data(), map.data());
         CRP_HIP(ctx, hipSetDevice(ctx->device));
         rc = crp::grow(ctx, reinterpret_cast<void **>(&sl.d_needles), &sl.needles_cap, 2 * np, sizeof(uint32_t));
         if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&sl.d_bounds), &sl.bounds_cap, 4 * np, sizeof(uint32_t));
@@ -357,13 +347,6 @@ int load_device(crp_node *node, int k, const uint8_t *const *texts)
         }
         rc = crp::staged_h2d(ctx, sl.d_needles, needles.data(), 2 * np * sizeof(uint32_t));  // (never the runtime's path for pageable memory: crp_api.cpp)
         if (rc != CRP_OK) return rc;
-        // its own piece map (begin[], then sub[]): what turns an arena position of an owned row into the position inside its contig
-        std::vector<uint32_t> map(2 * np);
-        for (size_t q = 0; q < np; ++q) {
-            const NodePiece &p = node->pieces[sl.pieces[q]];
-            map[q] = needles[2 * q];
-            map[np + q] = (uint32_t)(p.arena_off + (p.start - p.text_lo) - p.start);  // (mod 2^32)
-        }
         rc = crp::grow(ctx, reinterpret_cast<void **>(&sl.d_map_self), &sl.map_self_cap, 2 * np, sizeof(uint32_t));
         if (rc != CRP_OK) return rc;
         rc = crp::staged_h2d(ctx, sl.d_map_self, map.data(), 2 * np * sizeof(uint32_t));
@@ -703,7 +686,7 @@ int crp_node_set_option(crp_node *node, int option, int64_t value)
         case CRP_NODE_OPT_ARENA_WORDS:
             if (value == 0) value = (int64_t)crp_arena_max_words();
             // (room for one piece of 64 owned characters between two halos)
-            if (value < (int64_t)(crp_arena_words_for(2 * CRP_HALO + 64) + 2) || (uint64_t)value > crp_arena_max_words()) return CRP_ERR_INVALID;
+            if (value < (int64_t)crp::slice_words_min(CRP_HALO) || (uint64_t)value > crp_arena_max_words()) return CRP_ERR_INVALID;
             node->arena_words = (uint64_t)value;
             return CRP_OK;
         case CRP_NODE_OPT_COMM_INIT_TIMEOUT_MS: node->comm_init_timeout_s = (double)value / 1000.0; return CRP_OK;
@@ -726,53 +709,26 @@ static int node_load_impl(crp_node *node, const uint8_t *const *texts, const uin
     free_genome(node);
     const int world = (int)node->dev.size();
     try {
-        std::vector<std::array<uint64_t, 4>> cut;
-        crp::plan_shares(lens, n, world, 4096, cut);
+        // every device's share (crp_plan_shares), packed into as many arenas as it needs
+        std::vector<crp::Piece> cut;
+        crp::plan_shares(lens, n, world, 4096, CRP_HALO, cut);
         node->pieces.reserve(cut.size());
-        const uint64_t limit = node->arena_words;
-        auto open_slot = [&](NodeDev &d) -> NodeSlot & {
-            if (d.n_slots == d.slots.size()) d.slots.emplace_back(new NodeSlot());
-            NodeSlot &sl = *d.slots[d.n_slots++];
-            sl.pieces.clear();
-            sl.words = 1;
-            return sl;
-        };
-        for (const auto &c : cut) {
-            NodeDev &d = node->dev[(size_t)c[3]];
-            uint64_t start = c[1];
-            const uint64_t end = c[2], len = lens[c[0]];
-            for (;;) {
-                NodePiece p;
-                p.contig = c[0];
-                p.start = start;
-                p.end = end;
-                p.dev = (int)c[3];
-                p.text_lo = p.start > CRP_HALO ? p.start - CRP_HALO : 0;
-                p.text_len = std::min<uint64_t>(len, p.end + CRP_HALO) - p.text_lo;
-                p.arena_off = 0;
-                uint64_t need = crp_arena_words_for(p.text_len);
-                NodeSlot *sl = d.n_slots ? d.slots[d.n_slots - 1].get() : nullptr;
-                if (!sl || sl->words + need > limit) {
-                    // the share goes on in a new arena; a piece that would not fit an empty one is cut to what one holds (the
-                    // rest follows in the next arena, with halos like every other piece)
-                    sl = &open_slot(d);
-                    if (sl->words + need > limit) {
-                        const uint64_t chars = (limit - sl->words - 1) * 64;  // characters of text this arena takes
-                        const uint64_t own = (chars - (p.start - p.text_lo) - CRP_HALO) & ~(uint64_t)63;
-                        p.end = p.start + own;
-                        p.text_len = std::min<uint64_t>(len, p.end + CRP_HALO) - p.text_lo;
-                        need = crp_arena_words_for(p.text_len);
-                    }
+        for (size_t q = 0; q < cut.size();) {
+            size_t n_run = 1;  // the pieces of one device follow each other
+            while (q + n_run < cut.size() && cut[q + n_run].group == cut[q].group) ++n_run;
+            NodeDev &d = node->dev[(size_t)cut[q].group];
+            size_t at = node->pieces.size();
+            crp::pack_pieces(&cut[q], n_run, lens, node->arena_words, CRP_HALO, node->pieces);
+            for (; at < node->pieces.size(); ++at) {
+                if (node->pieces[at].group == d.n_slots) {  // the device's next arena begins here
+                    if (d.n_slots == d.slots.size()) d.slots.emplace_back(new NodeSlot());
+                    d.slots[d.n_slots++]->piece0 = at;
                 }
-                p.slot = (uint32_t)(d.n_slots - 1);
-                sl->words += need;
-                if (p.end != end) sl->words = limit;  // a piece that ends inside its contig closes its arena: one run per table
-                sl->pieces.push_back((uint32_t)node->pieces.size());
-                node->pieces.push_back(p);
-                if (p.end == end) break;
-                start = p.end;
+                d.slots[d.n_slots - 1]->n_pieces += 1;
             }
+            q += n_run;
         }
+        node->arena_off.assign(node->pieces.size(), 0);
         node->n_contigs = n;
         node->contig_counts.assign(2 * n, 0);
     } catch (...) {
@@ -826,11 +782,15 @@ static int node_plan_impl(const crp_node *node, uint64_t *pieces, uint64_t cap, 
     if (!node->loaded) return CRP_ERR_STATE;
     *n_pieces = node->pieces.size();
     if (node->pieces.size() > cap) return CRP_ERR_CAPACITY;
-    for (size_t q = 0; q < node->pieces.size(); ++q) {
-        const NodePiece &p = node->pieces[q];
-        const uint64_t row[7] = {p.contig, p.start, p.end, (uint64_t)p.dev, p.arena_off, p.start - p.text_lo, p.slot};
-        std::memcpy(pieces + 7 * q, row, sizeof row);
-    }
+    for (size_t k = 0; k < node->dev.size(); ++k)
+        for (size_t j = 0; j < node->dev[k].n_slots; ++j) {
+            const NodeSlot &sl = *node->dev[k].slots[j];
+            for (size_t q = sl.piece0; q < sl.piece0 + sl.n_pieces; ++q) {
+                const crp::Piece &p = node->pieces[q];
+                const uint64_t row[7] = {p.contig, p.start, p.end, k, node->arena_off[q], crp::owned_begin(p, 0), p.group};
+                std::memcpy(pieces + 7 * q, row, sizeof row);
+            }
+        }
     return CRP_OK;
 }
 
@@ -922,7 +882,7 @@ static int gather_cuts(crp_node *node, Gather &g)
     for (const SlotRef &a : g.act) {
         NodeDev &d = node->dev[(size_t)a.k];
         NodeSlot &sl = *a.sl;
-        const uint32_t nn = (uint32_t)(2 * sl.pieces.size());
+        const uint32_t nn = (uint32_t)(2 * sl.n_pieces);
         NODE_HIP(node, hipSetDevice(d.device));
         for (int s = 0; s < 2; ++s)
             NODE_HIP(node, crp::launch_lower_bound(d.ctx->stream, sl.arena->d_pos[s], sl.arena->n_hits[s], sl.d_needles, nn, sl.d_bounds + (size_t)s * nn));
@@ -932,23 +892,20 @@ static int gather_cuts(crp_node *node, Gather &g)
     if (rc != CRP_OK) return rc;
     std::fill(node->contig_counts.begin(), node->contig_counts.end(), 0);
     node->total[0] = node->total[1] = 0;
+    std::vector<uint32_t> counts;
     for (const SlotRef &a : g.act) {
         NodeSlot &sl = *a.sl;
-        const size_t np = sl.pieces.size();
+        const size_t np = sl.n_pieces;
+        counts.resize(np);
         for (int s = 0; s < 2; ++s) {
-            const uint32_t *b = sl.h_bounds + (size_t)s * 2 * np;
-            sl.first[s] = b[0];
-            sl.last[s] = b[2 * np - 1];
-            sl.foff[s] = node->total[s];
-            for (size_t j = 0; j < np; ++j) {
-                // contiguous shares: only an arena's first piece has a left halo and only its last a right one, so its
-                // owned rows are ONE run of each table
-                if (b[2 * j + 1] < b[2 * j] || (j + 1 < np && b[2 * j + 2] != b[2 * j + 1])) {
-                    node->last_error = "crp_node_gather: the owned rows of logical device " + std::to_string(a.k) + " are not one run";
-                    return CRP_ERR_STATE;
-                }
-                node->contig_counts[2 * node->pieces[sl.pieces[j]].contig + (size_t)s] += b[2 * j + 1] - b[2 * j];
+            // contiguous shares: only an arena's first piece has a left halo and only its last a right one, so its owned rows
+            // are ONE run of each table
+            if (!crp::owned_run(sl.h_bounds + (size_t)s * 2 * np, np, &sl.first[s], &sl.last[s], counts.data())) {
+                node->last_error = "crp_node_gather: the owned rows of logical device " + std::to_string(a.k) + " are not one run";
+                return CRP_ERR_STATE;
             }
+            sl.foff[s] = node->total[s];
+            for (size_t j = 0; j < np; ++j) node->contig_counts[2 * node->pieces[sl.piece0 + j].contig + (size_t)s] += counts[j];
             node->total[s] += owned_rows(sl, s);
         }
     }
@@ -967,7 +924,7 @@ static int gather_on_hosts(crp_node *node, Gather &g)
         NodeSlot &sl = *a.sl;
         crp_ctx *ctx = d.ctx;
         NODE_HIP(node, hipSetDevice(d.device));
-        const size_t np = sl.pieces.size();
+        const size_t np = sl.n_pieces;
         for (int s = 0; s < 2; ++s) {
             const uint64_t n = owned_rows(sl, s);
             const int rc = crp::grow(ctx, reinterpret_cast<void **>(&sl.d_lpos[s]), &sl.lpos_cap[s], n, sizeof(uint32_t));
@@ -1003,14 +960,11 @@ static int gather_reserve_root(crp_node *node, Gather &g)
     if (rc != CRP_OK) return dev_fail(node, g.root, rc, "crp_node_gather (root's tables)");
     // piece maps: begin[] and sub[] per slot, one upload
     g.map_off.assign(g.act.size(), 0);
-    node->h_map.clear();
+    node->h_map.resize(2 * node->pieces.size());
     for (const SlotRef &a : g.act) {
-        g.map_off[a.flat] = node->h_map.size();
-        for (int sub = 0; sub < 2; ++sub)
-            for (uint32_t q : a.sl->pieces) {
-                const NodePiece &p = node->pieces[q];
-                node->h_map.push_back((uint32_t)(p.arena_off + (p.start - p.text_lo) - (sub ? p.start : 0)));  // (mod 2^32)
-            }
+        const NodeSlot &sl = *a.sl;
+        g.map_off[a.flat] = 2 * sl.piece0;
+        crp::piece_cuts(node->pieces.data() + sl.piece0, sl.n_pieces, node->arena_off.data() + sl.piece0, nullptr, node->h_map.data() + 2 * sl.piece0);
     }
     rc = crp::grow(rctx, reinterpret_cast<void **>(&node->d_map), &node->map_cap, node->h_map.size(), sizeof(uint32_t));
     if (rc != CRP_OK) return dev_fail(node, g.root, rc, "crp_node_gather (piece maps)");
@@ -1126,7 +1080,7 @@ static int gather_expand(crp_node *node, const Gather &g)
     NODE_HIP(node, hipSetDevice(rctx->device));
     for (const SlotRef &a : g.act) {
         NodeSlot &sl = *a.sl;
-        const size_t np = sl.pieces.size();
+        const size_t np = sl.n_pieces;
         const crp::PieceMap map{node->d_map + g.map_off[a.flat], node->d_map + g.map_off[a.flat] + np, (uint32_t)np};
         for (int s = 0; s < 2; ++s) {
             const uint64_t n = owned_rows(sl, s);
@@ -1229,14 +1183,14 @@ static int node_offtarget_impl(crp_node *node, int guide_len, uint64_t *n_sites)
         NodeDev &d = node->dev[(size_t)k];
         for (size_t j = 0; j < d.n_slots; ++j) {
             NodeSlot &sl = *d.slots[j];
-            std::vector<uint64_t> own(2 * sl.pieces.size());
-            for (size_t q = 0; q < sl.pieces.size(); ++q) {
-                const NodePiece &p = node->pieces[sl.pieces[q]];
-                own[2 * q] = p.arena_off + (p.start - p.text_lo);
+            std::vector<uint64_t> own(2 * sl.n_pieces);
+            for (size_t q = 0; q < sl.n_pieces; ++q) {
+                const crp::Piece &p = node->pieces[sl.piece0 + q];
+                own[2 * q] = crp::owned_begin(p, node->arena_off[sl.piece0 + q]);
                 own[2 * q + 1] = own[2 * q] + (p.end - p.start);
             }
             uint64_t n = 0;
-            const int r2 = crp_offtarget_add(sl.arena, guide_len, own.data(), sl.pieces.size(), &n);
+            const int r2 = crp_offtarget_add(sl.arena, guide_len, own.data(), sl.n_pieces, &n);
             if (r2 != CRP_OK) return r2;
             sites[(size_t)k] += n;
         }
@@ -1327,17 +1281,17 @@ static int node_annotate_impl(crp_node *node, const crp_annotation *annotation, 
         for (size_t j = 0; j < d.n_slots; ++j) {
             NodeSlot &sl = *d.slots[j];
             // the track of THIS arena: every text is a piece of a contig (with its halo), named by the contig's seqid
-            std::vector<uint64_t> entries(4 * sl.pieces.size());
-            for (size_t q = 0; q < sl.pieces.size(); ++q) {
-                const NodePiece &p = node->pieces[sl.pieces[q]];
-                const uint64_t e[4] = {seqid_of_contig[p.contig], p.text_lo, p.text_len, p.arena_off};
+            std::vector<uint64_t> entries(4 * sl.n_pieces);
+            for (size_t q = 0; q < sl.n_pieces; ++q) {
+                const crp::Piece &p = node->pieces[sl.piece0 + q];
+                const uint64_t e[4] = {seqid_of_contig[p.contig], p.text_lo, p.text_len, node->arena_off[sl.piece0 + q]};
                 std::memcpy(&entries[4 * q], e, sizeof e);
             }
             uint64_t n = 0;
-            int rc = crp_annotation_track(annotation, entries.data(), sl.pieces.size(), dec, nullptr, nullptr, 0, &n);
+            int rc = crp_annotation_track(annotation, entries.data(), sl.n_pieces, dec, nullptr, nullptr, 0, &n);
             if (rc != CRP_OK && rc != CRP_ERR_CAPACITY) return rc;
             std::vector<uint32_t> points(n), ids(n);
-            rc = crp_annotation_track(annotation, entries.data(), sl.pieces.size(), dec, points.data(), ids.data(), n, &n);
+            rc = crp_annotation_track(annotation, entries.data(), sl.n_pieces, dec, points.data(), ids.data(), n, &n);
             if (rc == CRP_OK) rc = crp_annotate_set_track(sl.arena, points.data(), ids.data(), n);
             if (rc == CRP_OK) rc = crp_annotate_lookup(sl.arena, nullptr, nullptr);
             if (rc != CRP_OK) return rc;

@@ -517,6 +517,59 @@ def test_node_several_arenas_per_device_vs_oracle(oracle, world, tmp_path):
     ann.close()
 
 
+def _pack_share(share, lengths, limit, halo):
+    """The packing rule (crp_plan.cpp pack_pieces) restated: one device's pieces (contig, start, end), in order, into arenas
+    of at most `limit` words -> [(contig, start, end, arena)]."""
+    words_for = lambda n: (n + 63) // 64 + 1
+    out, arena, used, holds_a_piece = [], 0, 1, False
+    for contig, start, last in share:
+        while True:
+            lo, end = max(0, start - halo), last
+            need = words_for(min(lengths[contig], end + halo) - lo)
+            cut = False
+            if used + need > limit:
+                if holds_a_piece:
+                    arena, used, holds_a_piece = arena + 1, 1, False
+                if used + need > limit:  # no arena holds it: cut to what one takes, in whole words of owned characters
+                    end = start + (((limit - used - 1) * 64 - (start - lo) - halo) & ~63)
+                    need = words_for(min(lengths[contig], end + halo) - lo)
+                    cut = True
+            out.append((contig, start, end, arena))
+            used, holds_a_piece = used + need, True
+            if cut:  # a piece that ends inside its contig closes its arena
+                arena, used, holds_a_piece = arena + 1, 1, False
+            if end == last:
+                break
+            start = end
+    return out
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("world", [2, 4])
+def test_node_smallest_arenas_plan_and_rows_vs_oracle(oracle, world):
+    """The smallest arenas crp_node_set_option accepts (one piece of 64 owned characters between two halos): every device's
+    share is cut again at every arena's end, and a one-character contig shares an arena with a cut piece.  The plan == the
+    packing rule restated in Python, applied per device to crp_plan_shares' pieces; the rows == the oracle's, per contig."""
+    from cropsr_amd import _native as nat, node as nd
+    rng = np.random.default_rng(4100 + world)
+    contigs = _genome(rng, [3000, 5, 0, 700, 64, 1, 1500])
+    lengths = [len(c) for c in contigs]
+    words = int(nat.lib().crp_arena_words_for(2 * nat.HALO + 64)) + 2  # crp_node_set_option's lower bound
+    want = []
+    for device in range(world):
+        share = [(c, s, e) for c, s, e, d in nd.plan_shares(lengths, world) if d == device]
+        want += [(c, s, e, device, a) for c, s, e, a in _pack_share(share, lengths, words, nat.HALO)]
+    assert len(want) > len(lengths) + world - 1
+    with nd.Node([0] * world) as node:
+        with pytest.raises(Exception):
+            node.set_option(arena_words=words - 1)
+        node.set_option(arena_words=words)
+        node.load(contigs)
+        assert [(p["contig"], p["start"], p["end"], p["device"], p["arena"]) for p in node.plan()] == want
+        for kw in ({}, {"to_host": True}):
+            _check_against_oracle(node.scan(20, **kw), contigs, oracle, 20, (world, words, kw))
+
+
 @pytest.mark.gpu
 @pytest.mark.slow
 def test_node_maize_size_genome_on_one_device_equals_engine_genome():

@@ -47,5 +47,7 @@ def test_annotation_builder_fuzz_under_sanitizers(tmp_path):
 
 def test_node_cut_fuzz_under_sanitizers(tmp_path):
     """20 000 random contig-length lists over 1..17 devices through crp_plan_shares under ASan + UBSan: coverage, order, at
-    most world - 1 cuts, and the one-run-per-table property crp_node_gather rests on."""
+    most world - 1 cuts, and the one-run-per-table property crp_node_gather rests on.  Then what the node handle and the
+    pipelined scan both cut by: plan_slices, pack_pieces on every device's share against a restatement of the node's former
+    loop, piece_cuts (needles and piece map, contigs up to 2^32 - 1 characters) and owned_run."""
     _build_and_run("address,undefined", tmp_path, "plan_driver", "crp_plan.cpp", defines=["-I", os.path.join(ROOT, "cropsr_amd", "csrc")])
