@@ -37,6 +37,12 @@ class SelectParams(ctypes.Structure):
                 ("require_cds", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class SelectPropertyLimits(ctypes.Structure):
+    """crp_select_property_limits (include/cropsr_hip.h): the bounds a selection puts on the guide properties."""
+    _fields_ = [("gc_min", ctypes.c_uint32), ("gc_max", ctypes.c_uint32), ("max_run", ctypes.c_uint32), ("max_t_run", ctypes.c_uint32),
+                ("max_stem", ctypes.c_uint32)]
+
+
 voidpp = ctypes.POINTER(ctypes.c_void_p)
 
 # every symbol include/cropsr_hip.h declares: name -> (restype, argtypes)
@@ -78,6 +84,8 @@ SIGNATURES = {
                                          f64p, u8p, ctypes.c_uint64, u8p, u64p, u32p, u32p, u64p, ctypes.c_int]),
     "crp_write_segments": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_uint64, u64p, ctypes.c_int]),
     "crp_write_segments_cols": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, u64p, ctypes.c_int]),
+    "crp_write_segments_props": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint64, u64p,
+                                                ctypes.c_int]),
     "crp_comm_unique_id": (ctypes.c_int, [u8p]),
     "crp_comm_init": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_int, ctypes.c_int]),
     "crp_comm_destroy": (ctypes.c_int, [ctypes.c_void_p]),
@@ -173,6 +181,9 @@ SIGNATURES = {
     "crp_select_run": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "crp_select_fetch": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, u32p]),
     "crp_select_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
+    "crp_select_set_property_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "crp_guide_properties": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p]),
+    "crp_guide_properties_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_configure": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]),
     "crp_query": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     "crp_build_id": (ctypes.c_char_p, []),
@@ -189,7 +200,7 @@ OPT_TWO_PASS, OPT_CHAIN_TIMEOUT_US, OPT_TILE_GEOMETRY = 1, 2, 3
 GEOMETRIES = {"auto": 0, "large": 1, "small": 2}
 Q_CHAIN_TIMEOUTS, Q_TWO_PASS_ACTIVE, Q_COMM_WORLD, Q_COMM_RANK, Q_HBM_FREE, Q_HBM_TOTAL, Q_GATHER_BYTES = 1, 2, 3, 4, 5, 6, 7
 KINDS = ("count", "tile_scan", "emit_score", "ot_seed", "ot_ball", "ot_lookup", "gatherv", "ot_reduce",
-         "annotate")  # CRP_K_*
+         "annotate", "properties")  # CRP_K_*
 REDUCE_SUM, REDUCE_MAX = 0, 1
 COMM_ID_BYTES = 128
 GATHER_OFFTARGET, GATHER_PRE, GATHER_FEATURES, GATHER_POS16 = 1, 2, 4, 8

@@ -126,6 +126,21 @@ def build_parser():
                      help="with --select: only guides whose cut site lies in a CDS row of the GFF (positional, like --annotate)")
     eng.add_argument("--select-only", action="store_true",
                      help="with --select: write the selection file only, not the main table (no ids are drawn)")
+    eng.add_argument("--properties", action="store_true",
+                     help="NOT in the reference: the guide's own sequence quality, computed on the GPU from the l letters of every "
+                          "row's guide; appends the columns guide_gc (letters that are C or G), guide_run (longest run of one base), "
+                          "guide_t_run (longest run of T in the spacer: TTTT ends Pol III transcription) and guide_stem (longest "
+                          "hairpin stem with a loop of at least 3); -l 1..50, one GPU")
+    eng.add_argument("--select-gc-min", type=int, default=None, metavar="PCT",
+                     help="with --select: only guides with at least PCT %% GC (an integer 0..100; as a count: ceil(PCT * l / 100))")
+    eng.add_argument("--select-gc-max", type=int, default=None, metavar="PCT",
+                     help="with --select: only guides with at most PCT %% GC (an integer 0..100; as a count: floor(PCT * l / 100))")
+    eng.add_argument("--select-max-run", type=int, default=None, metavar="N",
+                     help="with --select: only guides whose longest run of one base has at most N letters")
+    eng.add_argument("--select-max-t-run", type=int, default=None, metavar="N",
+                     help="with --select: only guides whose longest run of T has at most N letters (3 keeps TTTT out)")
+    eng.add_argument("--select-max-stem", type=int, default=None, metavar="N",
+                     help="with --select: only guides whose longest hairpin stem has at most N pairs")
     eng.add_argument("--bench-json", metavar="PATH", default=None,
                      help="write stage timings of this run (read, upload+scan, fetch, format+write) as one JSON object")
     return p
@@ -252,6 +267,7 @@ class EngineBackend:
         self.last_annotate_s = None  # --bench-json: seconds the last annotation join took on this rank
         self.last_stream = None      # --bench-json: crp_scan_stream's own numbers for the last plain scan
         self.last_specificity = None  # --bench-json: the self-search handles' times of the last --specificity scan
+        self.last_properties = None   # --bench-json: the property kernel's time and rows of the last scan that ran it
 
     def connect(self):
         """Collective over the group: create the RCCL communicator (transport "rccl")."""
@@ -285,7 +301,7 @@ class EngineBackend:
             # code object (17-25 ms, otherwise paid by the genome's first slice)
             self.engine.scan_stream([np.frombuffer(b"ACGTTGCAAGGCCTTA" * 40, dtype=np.uint8)], 20)
 
-    def scan(self, contig_strings, guide_len, offtarget=False, annotation=None, specificity=None, select=None):
+    def scan(self, contig_strings, guide_len, offtarget=False, annotation=None, specificity=None, select=None, properties=False):
         """One pass on the GPU for all contig strings (seam 1 + 2).  The plain scan goes through crp_scan_stream -- upload,
         scan and table fetch as a pipeline over slices of the genome, the host link busy in both directions (the reference's
         loop is produce-and-consume per contig too, CROPSR.py:409-474); CROPSR_STREAM=0, or the opt-in steps that work on
@@ -294,9 +310,10 @@ class EngineBackend:
         while the tables are resident.  specificity (the arguments of search.specificity_columns): the hit dicts also carry
         self_counts_* / self_sum_*, the self search's rows joined onto the resident tables.  select (select.Request): the returned list is a
         select.HitList whose .selection holds the best K guides of every gene, chosen on the GPU while the tables (and the
-        joined specificity columns) are resident."""
+        joined specificity columns) are resident.  properties: the hit dicts also carry props_plus / props_minus, the packed
+        guide properties of every row (properties.py), computed on the GPU while the tables are resident."""
         import os
-        if not offtarget and annotation is None and specificity is None and select is None and os.environ.get("CROPSR_STREAM", "1") != "0":
+        if not offtarget and annotation is None and specificity is None and select is None and not properties and os.environ.get("CROPSR_STREAM", "1") != "0":
             want_pre = self.finalize == "host"
             hits = self.engine.scan_stream(contig_strings, guide_len, want_pre=want_pre)
             self.last_stream = hits.stream_stats  # (--bench-json)
@@ -311,6 +328,8 @@ class EngineBackend:
         genome = self.engine.genome(contig_strings)  # as many arenas as the genome needs
         try:
             more = {} if select is None else dict(select=select)
+            if properties:
+                more["properties"] = True
             hits = genome.scan_score(guide_len, want_pre=self.finalize == "host", offtarget=offtarget, annotation=annotation,
                                      specificity=specificity, **more)
             out = [self._finalize(hits.contig(k)) for k in range(len(contig_strings))]
@@ -320,6 +339,7 @@ class EngineBackend:
                 out.selection = hits.selection
             self.last_annotate_s = genome.annotate_s
             self.last_specificity = getattr(hits.columns, "stats", None)  # (--bench-json)
+            self.last_properties = genome.properties_stats
         finally:
             genome.close()
         return out
@@ -518,7 +538,10 @@ def select_request(args, spec, world=1):
     given = [o for o, k, unset in (("--select-output", "select_output", None), ("--select-min-score", "select_min_score", None),
                                    ("--select-max-perfect", "select_max_perfect", None),
                                    ("--select-min-specificity", "select_min_specificity", None), ("--select-cds", "select_cds", False),
-                                   ("--select-only", "select_only", False)) if getattr(args, k, unset) not in (unset, None)]
+                                   ("--select-only", "select_only", False), ("--select-gc-min", "select_gc_min", None),
+                                   ("--select-gc-max", "select_gc_max", None), ("--select-max-run", "select_max_run", None),
+                                   ("--select-max-t-run", "select_max_t_run", None), ("--select-max-stem", "select_max_stem", None))
+             if getattr(args, k, unset) not in (unset, None)]
     K = getattr(args, "select", None)
     if K is None:
         if given:
@@ -540,16 +563,50 @@ def select_request(args, spec, world=1):
         refuse("the selection runs on one GPU: drop --gpus %d" % args.gpus)
     if world > 1:
         refuse("the selection runs on one GPU, and a launcher started %d ranks" % world)
+    for opt, key in (("--select-gc-min", "select_gc_min"), ("--select-gc-max", "select_gc_max")):
+        v = getattr(args, key, None)
+        if v is not None and not 0 <= v <= 100:
+            refuse("%s is a percentage, an integer 0..100, not %d" % (opt, v))
+    for opt, key in (("--select-max-run", "select_max_run"), ("--select-max-t-run", "select_max_t_run"), ("--select-max-stem", "select_max_stem")):
+        v = getattr(args, key, None)
+        if v is not None and v < 0:
+            refuse("%s is a number of letters, not %d" % (opt, v))
+    from . import properties
+    gc_min, gc_max = properties.gc_count_bounds(getattr(args, "select_gc_min", None), getattr(args, "select_gc_max", None), args.l)
+    limits = dict(gc_min=gc_min if getattr(args, "select_gc_min", None) is not None else None,
+                  gc_max=gc_max if getattr(args, "select_gc_max", None) is not None else None,
+                  max_run=getattr(args, "select_max_run", None), max_t_run=getattr(args, "select_max_t_run", None),
+                  max_stem=getattr(args, "select_max_stem", None))
     try:
         params = select.Params(K, getattr(args, "select_min_score", None) or 0.0, getattr(args, "select_max_perfect", None),
                                getattr(args, "select_min_specificity", None), bool(getattr(args, "select_cds", False)))
     except ValueError as e:
         refuse(str(e))
     return dict(params=params, output=getattr(args, "select_output", None) or (args.o + ".selected.csv"),
-                only=bool(getattr(args, "select_only", False)))
+                only=bool(getattr(args, "select_only", False)), limits=limits)
 
 
-def write_selection(path, selection, names, strings, all_hits, guide_len, offtarget, spec_M, annotation):
+def properties_request(args, world=1):
+    """--properties, checked like the other opt-in steps, before any side effect: True with it, False without."""
+    if not getattr(args, "properties", False):
+        return False
+
+    def refuse(msg):
+        sys.exit("cropsr_amd: --properties: " + msg)
+
+    from . import properties
+    if not properties.GUIDE_LENGTHS[0] <= args.l <= properties.GUIDE_LENGTHS[1]:
+        refuse("a guide of %d..%d letters has properties, not -l %d" % (properties.GUIDE_LENGTHS + (args.l,)))
+    if len(_device_list(args)) > 1:
+        refuse("the property column is not gathered: one GPU, and --devices names %d" % len(_device_list(args)))
+    if getattr(args, "gpus", 1) > 1:
+        refuse("the property column is not gathered: one GPU, drop --gpus %d" % args.gpus)
+    if world > 1:
+        refuse("the property column is not gathered: one GPU, and a launcher started %d ranks" % world)
+    return True
+
+
+def write_selection(path, selection, names, strings, all_hits, guide_len, offtarget, spec_M, annotation, properties=False):
     """The selection file: a header, then per chosen row gene, rank (1-based), passing and the main table's own fields
     for that row as rows.ContigRows builds them, without crispr_id (those ids are random per run).  Genes in GFF order;
     genes with nothing selected are left out.  Python's csv module in the main table's dialect: the file is small."""
@@ -575,8 +632,7 @@ def write_selection(path, selection, names, strings, all_hits, guide_len, offtar
             fields[at] = block.row(k, "")[1:]
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(["gene", "rank", "passing"] + rows.HEADER[1:] + (rows.OFFTARGET_HEADER if offtarget else []) +
-                   ([] if spec_M is None else rows.SPECIFICITY_HEADER(spec_M)))
+        w.writerow(["gene", "rank", "passing"] + rows.HEADER[1:] + rows.extra_header(offtarget, spec_M, properties))
         for r, rest in zip(sel_rows, fields):
             w.writerow((selection.labels[int(r["gene"])], int(r["rank"]), int(selection.n_pass[int(r["gene"])])) + tuple(rest))
 
@@ -631,6 +687,7 @@ def run(args, backend=None, out=sys.stdout, group=None):
         sys.exit("cropsr_amd: --offtarget needs a guide length between %d and %d (got %d)" % (NATIVE_GUIDE_LENGTHS + (args.l,)))
     spec = specificity_request(args)  # (before any side effect, on every rank)
     selecting = select_request(args, spec, 1 if group is None else group.world)
+    with_properties = properties_request(args, 1 if group is None else group.world)
     finalize = getattr(args, "score_finalize", "gpu")
     stages = {}  # --bench-json
     own_group = group is None
@@ -647,7 +704,9 @@ def run(args, backend=None, out=sys.stdout, group=None):
         sys.exit("cropsr_amd: --specificity: the self search runs on one GPU, and a launcher started %d ranks" % group.world)
     if selecting is not None and group is not None and group.world > 1:
         select_request(args, spec, group.world)
-    one_gpu = spec is not None or selecting is not None  # the opt-in steps that take the arena path on one device
+    if group is not None and group.world > 1:
+        properties_request(args, group.world)
+    one_gpu = spec is not None or selecting is not None or with_properties  # the opt-in steps that take the arena path on one device
 
     def make_backend():
         if getattr(args, "devices", None) and not (one_gpu and len(_device_list(args)) == 1):
@@ -787,7 +846,8 @@ def run(args, backend=None, out=sys.stdout, group=None):
 
     select_only = selecting is not None and selecting["only"]
     if not select_only:
-        rows.write_header(args.o, offtarget=offtarget, specificity=None if spec is None else spec["max_mm"])  # CROPSR.py:402-405
+        rows.write_header(args.o, offtarget=offtarget, specificity=None if spec is None else spec["max_mm"],
+                          properties=with_properties)  # CROPSR.py:402-405
 
     names = [k for k, _ in table]
     strings = [v for _, v in table]  # contig strings as bytes, one byte per character
@@ -805,7 +865,9 @@ def run(args, backend=None, out=sys.stdout, group=None):
             extra["specificity"] = spec
         if selecting is not None:  # (the keyword a backend only meets when selecting)
             from . import select
-            extra["select"] = select.Request(selecting["params"], request)
+            extra["select"] = select.Request(selecting["params"], request, **selecting["limits"])
+        if with_properties:  # (likewise: only a scan that is asked for the columns meets the keyword)
+            extra["properties"] = True
         from .search import SelfCapacityError
         try:
             all_hits = backend.scan(strings, l_dev, **extra)
@@ -841,7 +903,7 @@ def run(args, backend=None, out=sys.stdout, group=None):
         t_select = time.perf_counter()
         selection = all_hits.selection
         write_selection(selecting["output"], selection, names, strings, all_hits, args.l, offtarget, None if spec is None else spec["max_mm"],
-                        request.annotation if annotating else None)
+                        request.annotation if annotating else None, properties=with_properties)
         stages["select"] = dict(selection.stats, write_s=time.perf_counter() - t_select, genes=len(selection.labels),
                                 rows_selected=int(selection.rows.size), k=selecting["params"].k)
     if not annotating:
@@ -952,6 +1014,8 @@ def run(args, backend=None, out=sys.stdout, group=None):
         ids.close()
     if getattr(backend, "last_stream", None):  # the pipelined scan's own account of the upload + scan + fetch stage
         stages["scan_stream"] = backend.last_stream
+    if getattr(backend, "last_properties", None):  # --properties / the --select-* property filters: the kernel's time and rows
+        stages["properties"] = backend.last_properties
     if getattr(backend, "last_specificity", None):  # --specificity: the handles' kernel times, the join's among them
         stages["specificity"] = backend.last_specificity
     if getattr(backend, "last_gather", None):  # one process over several devices (--devices): the node's gatherv, in numbers
@@ -995,6 +1059,7 @@ def main(argv=None):
         sys.exit("cropsr_amd: --devices (one process over several GPUs) and --gpus N (one process per GPU) are two ways to the "
                  "same result: give one of them")
     select_request(args, specificity_request(args))  # (--gpus N: refused here, before any rank is started)
+    properties_request(args)
     if launch.wanted(getattr(args, "gpus", 1)):
         # no launcher in the environment: this process (which never touches the GPU) starts the ranks as fresh
         # children of the same command line and leaves with their status (cropsr_amd/launch.py)

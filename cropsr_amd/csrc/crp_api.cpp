@@ -450,6 +450,10 @@ int crp_arena_destroy(crp_arena *a)
     (void)hipFree(a->d_ann_bucket);
     (void)hipFree(a->d_feat[0]);
     (void)hipFree(a->d_feat[1]);
+    (void)hipFree(a->d_props[0]);
+    (void)hipFree(a->d_props[1]);
+    for (hipEvent_t e : a->ev_props)
+        if (e) (void)hipEventDestroy(e);
     delete a;
     return CRP_OK;
 }
@@ -870,7 +874,7 @@ int arena_reset(crp_arena *a)
     a->used_words = 1;
     a->n_contigs = a->n_chars = 0;
     a->sealed = false;
-    a->have_hits = a->have_pre = a->have_raw = a->have_feat = a->have_track = false;
+    a->have_hits = a->have_pre = a->have_raw = a->have_feat = a->have_props = a->have_track = false;
     a->n_hits[0] = a->n_hits[1] = 0;
     a->scan_pending = 0;
     a->ot_epoch = 0;
@@ -900,6 +904,7 @@ int scan_begin(crp_arena *a, int guide_len, int flags)
     a->have_hits = false;
     a->have_raw = false;
     a->have_feat = false;
+    a->have_props = false;
     a->scan_pending = 0;
     a->pend_guide_len = guide_len;
     a->pend_flags = flags;

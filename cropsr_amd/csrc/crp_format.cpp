@@ -178,6 +178,8 @@ struct Job {
     const uint32_t *self_counts = nullptr;
     int n_counts = 0;
     const uint64_t *self_hit_sum = nullptr;
+    // opt-in: the packed guide properties (crp_write_segments_props)
+    const uint32_t *props = nullptr;
     std::string chrom_field;  // the chromosome column as csv writes it
     size_t row_bound;         // no row is longer than this
 
@@ -263,6 +265,13 @@ char *format_range(const Job &j, uint64_t r0, uint64_t r1, char *o)
                 o = std::to_chars(o, o + 24, hs).ptr;
                 *o++ = ',';
                 o = put_repr(o, 1.0 / (1.0 + (double)hs / 1073741824.0));  // search.specificity
+            }
+        }
+        if (j.props) {  // opt-in: guide_gc, guide_run, guide_t_run, guide_stem
+            const uint32_t v = j.props[r];
+            for (int k = 0; k < 4; ++k) {
+                *o++ = ',';
+                o = put_int(o, (int64_t)(v >> (8 * k) & 255u));
             }
         }
         o = PUT_LIT(o, "\r\n");
@@ -351,8 +360,8 @@ extern "C" int crp_format_rows(const uint8_t *contig_text, uint64_t contig_len, 
 // worker formats into its buffer and commits with one write(2), in order -- holds up to kBlockRows rows and may span several
 // short segments, so a run of small contigs costs what one contig of their total size costs (the CLI used to make one call per
 // contig: 626 scaffold passes of 3 500 rows each, formatted by ONE thread and joined, took a fifth of the CSV stage).
-extern "C" int crp_write_segments_cols(int fd, int guide_len, const crp_row_segment *segs, const crp_row_extra *extras, uint64_t n_segs,
-                                       uint64_t *bytes_written, int n_threads)
+extern "C" int crp_write_segments_props(int fd, int guide_len, const crp_row_segment *segs, const crp_row_extra *extras,
+                                        const uint32_t *const *props, uint64_t n_segs, uint64_t *bytes_written, int n_threads)
 {
     crp::Range roctx_range("crp: format + write rows");
     if (fd < 0 || (n_segs && !segs)) return CRP_ERR_INVALID;
@@ -397,6 +406,10 @@ extern "C" int crp_write_segments_cols(int fd, int guide_len, const crp_row_segm
                 job.n_counts = extras[k].n_counts;
                 job.self_hit_sum = extras[k].self_hit_sum;
                 job.row_bound += 11 * (size_t)job.n_counts + 21 + 25;
+            }
+            if (props && props[k]) {
+                job.props = props[k];
+                job.row_bound += 4 * 4;
             }
             if (g.feat_idx) {  // the longest features entry a row can carry, quoted
                 uint64_t longest = 0;
@@ -463,9 +476,15 @@ extern "C" int crp_write_segments_cols(int fd, int guide_len, const crp_row_segm
     }
 }
 
+extern "C" int crp_write_segments_cols(int fd, int guide_len, const crp_row_segment *segs, const crp_row_extra *extras, uint64_t n_segs,
+                                       uint64_t *bytes_written, int n_threads)
+{
+    return crp_write_segments_props(fd, guide_len, segs, extras, nullptr, n_segs, bytes_written, n_threads);
+}
+
 extern "C" int crp_write_segments(int fd, int guide_len, const crp_row_segment *segs, uint64_t n_segs, uint64_t *bytes_written, int n_threads)
 {
-    return crp_write_segments_cols(fd, guide_len, segs, nullptr, n_segs, bytes_written, n_threads);
+    return crp_write_segments_props(fd, guide_len, segs, nullptr, nullptr, n_segs, bytes_written, n_threads);
 }
 
 extern "C" int crp_write_rows_ex(int fd, const uint8_t *contig_text, uint64_t contig_len, const uint8_t *chrom,

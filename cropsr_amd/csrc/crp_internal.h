@@ -115,6 +115,12 @@ struct crp_arena {
     uint64_t feat_cap[2] = {0, 0};
     bool have_track = false;
     bool have_feat = false;  // d_feat belongs to the current tables (cleared by the next scan)
+    // guide sequence properties (crp_properties.hip): one packed word per hit of the last crp_guide_properties
+    uint32_t *d_props[2] = {nullptr, nullptr};  // same order as the hit tables
+    uint64_t props_cap[2] = {0, 0};
+    bool have_props = false;  // d_props belongs to the current tables (cleared by the next scan)
+    hipEvent_t ev_props[2] = {nullptr, nullptr};
+    double props_ms = 0;  // the kernel of the last crp_guide_properties (HIP events)
 };
 
 #define CRP_HIP(ctx, call)                                                              \

@@ -31,6 +31,8 @@ struct crp_select {
     crp::SelectResult res = {};  // n_in, n_pass: n_genes; sel: n_genes * k of the last run
     uint64_t sel_cap = 0;
     int k = 0;  // of the last successful run (0: none)
+    bool have_prop_limits = false;
+    crp_select_property_limits prop_limits = {};
     hipEvent_t ev[2] = {nullptr, nullptr};
     double stats[9] = {};
 };
@@ -130,6 +132,14 @@ int crp_select_set_limits(crp_select *s, uint64_t slice_rows)
     return CRP_OK;
 }
 
+int crp_select_set_property_limits(crp_select *s, const crp_select_property_limits *limits)
+{
+    if (!s) return CRP_ERR_INVALID;
+    s->have_prop_limits = limits != nullptr;
+    if (limits) s->prop_limits = *limits;
+    return CRP_OK;
+}
+
 int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *self)
 {
     crp::Range roctx_range("crp: guide selection");
@@ -145,6 +155,8 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
     if (p->require_cds && !s->have_flags) return fail(ctx, CRP_ERR_STATE, "crp_select_run: require_cds needs crp_select_set_flags");
     if (p->require_cds && !a->have_feat)
         return fail(ctx, CRP_ERR_STATE, "crp_select_run: require_cds needs the ids of a crp_annotate_lookup on the current tables");
+    if (s->have_prop_limits && !a->have_props)
+        return fail(ctx, CRP_ERR_STATE, "crp_select_run: property limits need the column of a crp_guide_properties on the current tables");
     crp::SelfJoined joined = {};
     if (self) {
         if (!crp::self_joined(self, &joined))
@@ -221,7 +233,7 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
     crp::SelectTable tab[2];
     for (int t = 0; t < 2; ++t)
         tab[t] = crp::SelectTable{a->d_pos[t], a->d_score[t], p->require_cds ? a->d_feat[t] : nullptr, self ? joined.counts[t] : nullptr,
-                                  self ? joined.sum[t] : nullptr, (uint32_t)a->n_hits[t]};
+                                  self ? joined.sum[t] : nullptr, s->have_prop_limits ? a->d_props[t] : nullptr, (uint32_t)a->n_hits[t]};
     crp::SelectPredicate pred = {};
     pred.min_score = p->min_score;
     pred.max_hit_sum = p->max_hit_sum;
@@ -230,6 +242,11 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
     pred.flags = p->require_cds ? s->d_flags : nullptr;
     pred.n_flags = (uint32_t)s->n_flags;
     pred.k = k;
+    pred.gc_min = s->prop_limits.gc_min;
+    pred.gc_max = s->prop_limits.gc_max;
+    pred.max_run = s->prop_limits.max_run;
+    pred.max_t_run = s->prop_limits.max_t_run;
+    pred.max_stem = s->prop_limits.max_stem;
     // the bounded-launch rule: at most 2^20 items a launch, each timed on its own
     for (uint64_t first = 0; first < items.size(); first += crp::SELECT_MAX_ITEMS) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(crp::SELECT_MAX_ITEMS, items.size() - first);
@@ -252,8 +269,9 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
     }
     s->stats[3] = (double)items.size();
     s->stats[6] = (double)rows_covered;
-    // position + score, the label-set id under require_cds, and with joined columns counts[0] and hit_sum
-    s->stats[7] = 12.0 + (p->require_cds ? 4.0 : 0.0) + (self ? 12.0 : 0.0);
+    // position + score, the label-set id under require_cds, with joined columns counts[0] and hit_sum, and the packed
+    // properties under property limits
+    s->stats[7] = 12.0 + (p->require_cds ? 4.0 : 0.0) + (self ? 12.0 : 0.0) + (s->have_prop_limits ? 4.0 : 0.0);
     s->stats[8] = (double)merges.size();
     s->k = k;
     return CRP_OK;

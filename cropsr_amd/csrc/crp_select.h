@@ -17,6 +17,7 @@ struct SelectTable {
     const uint32_t *feat;              // label-set ids (require_cds)
     const uint32_t *counts;            // joined self-search counts, `stride` per row: counts[0] is read
     const unsigned long long *sum;     // joined hit_sum
+    const uint32_t *props;             // packed guide properties (property limits)
     uint32_t n;
 };
 
@@ -28,6 +29,8 @@ struct SelectPredicate {
     const uint8_t *flags;   // null: no CDS filter
     uint32_t n_flags;
     int k;
+    // with SelectTable::props: gc_min <= gc <= gc_max, run <= max_run, t_run <= max_t_run, stem <= max_stem (each one byte)
+    uint32_t gc_min, gc_max, max_run, max_t_run, max_stem;
 };
 
 // One wave's work: rows [first[s], first[s] + rows[s]) of strand s's table, all inside gene `gene`'s runs.  slot ==

@@ -127,6 +127,12 @@ __global__ __launch_bounds__(BLOCK) void select_items_kernel(SelectTable plus, S
                 const uint32_t id = in ? t.feat[row] : SELECT_NONE;
                 pass = pass && id < pred.n_flags && pred.flags[id] != 0;
             }
+            if (t.props) {  // (the packed word of crp_guide_properties: gc | run << 8 | t_run << 16 | stem << 24)
+                const uint32_t pr = in ? t.props[row] : 0u;
+                const uint32_t gc = pr & 255u;
+                pass = pass && gc >= pred.gc_min && gc <= pred.gc_max && (pr >> 8 & 255u) <= pred.max_run && (pr >> 16 & 255u) <= pred.max_t_run &&
+                       pr >> 24 <= pred.max_stem;
+            }
             n_in += (uint32_t)__popcll(__ballot(scored));
             n_pass += (uint32_t)__popcll(__ballot(pass));
             sel_insert(mine, lane, k, pass, (unsigned long long)__double_as_longlong(score), cut << 1 | (uint32_t)s,

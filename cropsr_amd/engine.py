@@ -60,6 +60,7 @@ class Hits:
         self.pos_minus, self.pre_minus, self.score_minus = cols[3:6]
         self.ot_plus = self.ot_minus = None  # (n, 4) uint32 once an off-target scan has run
         self.feat_plus = self.feat_minus = None  # uint32 label-set ids once the annotation join has run
+        self.props_plus = self.props_minus = None  # uint32 packed guide properties once crp_guide_properties has run
         # (needles in the tables' own dtype, uint32: arena positions stay below 2^31 -- otherwise numpy converts the tables)
         starts = np.asarray(offsets).astype(np.uint32)
         ends = (np.asarray(offsets) + np.asarray(lengths)).astype(np.uint32)
@@ -88,6 +89,8 @@ class Hits:
             out["ot_plus"], out["ot_minus"] = self.ot_plus[a:b], self.ot_minus[c:d]
         if self.feat_plus is not None:
             out["feat_plus"], out["feat_minus"] = self.feat_plus[a:b], self.feat_minus[c:d]
+        if self.props_plus is not None:
+            out["props_plus"], out["props_minus"] = self.props_plus[a:b], self.props_minus[c:d]
         return out
 
 
@@ -200,6 +203,25 @@ class Arena:
         nat.check(nat.lib().crp_annotate_lookup(self._h, fp.ctypes.data_as(nat.u32p), fm.ctypes.data_as(nat.u32p)),
                   "crp_annotate_lookup", self._engine._ctx)
         return fp, fm
+
+    # ---- guide sequence properties (opt-in; properties.py has the definition)
+    def guide_properties(self, n_plus, n_minus, fetch=True):
+        """The packed properties (gc | run << 8 | t_run << 16 | stem << 24) of every kept hit of the last scan, computed on
+        the GPU from the planes; fetch=False leaves the column in HBM (for a selection's property limits)."""
+        if not fetch:
+            nat.check(nat.lib().crp_guide_properties(self._h, None, None), "crp_guide_properties", self._engine._ctx)
+            return None
+        pp, pm = np.empty(n_plus, dtype=np.uint32), np.empty(n_minus, dtype=np.uint32)
+        nat.check(nat.lib().crp_guide_properties(self._h, pp.ctypes.data_as(nat.u32p), pm.ctypes.data_as(nat.u32p)),
+                  "crp_guide_properties", self._engine._ctx)
+        return pp, pm
+
+    def guide_properties_stats(self):
+        """dict(kernel_ms, rows, guide_len) of the last guide_properties() on the current tables."""
+        out = np.zeros(3, dtype=np.float64)
+        nat.check(nat.lib().crp_guide_properties_stats(self._h, out.ctypes.data_as(nat.f64p), 3), "crp_guide_properties_stats",
+                  self._engine._ctx)
+        return dict(kernel_ms=float(out[0]), rows=int(out[1]), guide_len=int(out[2]))
 
     # ---- off-target seed scan (opt-in; include/cropsr_hip.h)
     def offtarget_add(self, guide_len=20, own_ranges=None):
@@ -704,6 +726,7 @@ class Genome:
         self.arenas = [engine.arena([bufs[k] for k in g], pack=pack) for g in groups]
         self.groups = groups  # contig indices per arena, in arena order
         self.annotate_s = None
+        self.properties_stats = None  # dict(kernel_ms, rows, wall_s) of the last guide_properties()
         self._where = {}
         for a, g in enumerate(groups):
             for j, k in enumerate(g):
@@ -720,6 +743,19 @@ class Genome:
             a.annotate_set_track(*request.track([(k, int(a.offsets[j]), int(a.lengths[j])) for j, k in enumerate(g)]))
             out.append(a.annotate_lookup(n_plus, n_minus, fetch=fetch))
         self.annotate_s = time.perf_counter() - t0  # track lay-out + upload + look-up (+ the copy of the ids to the host)
+        return out if fetch else None
+
+    def guide_properties(self, counts, fetch=True):
+        """The guide properties over every arena's resident tables (counts: (n_plus, n_minus) per arena).  Returns
+        [(props_plus, props_minus)] per arena, or None with fetch=False (the columns stay in HBM)."""
+        import time
+        t0 = time.perf_counter()
+        out, ms, n_rows = [], 0.0, 0
+        for a, (n_plus, n_minus) in zip(self.arenas, counts):
+            out.append(a.guide_properties(n_plus, n_minus, fetch=fetch))
+            st = a.guide_properties_stats()
+            ms, n_rows = ms + st["kernel_ms"], n_rows + st["rows"]
+        self.properties_stats = dict(kernel_ms=ms, rows=n_rows, wall_s=time.perf_counter() - t0)
         return out if fetch else None
 
     def specificity_columns(self, guide_len=20, max_mm=3, candidate_pam="NRG", score="hsu2013", budget=None):
@@ -759,7 +795,7 @@ class Genome:
         return sel.assemble(labels, request.params.k, parts, stats)
 
     def scan_score(self, guide_len=20, want_pre=False, offtarget=False, seeds_from_scan=True, annotation=None, specificity=None,
-                   select=None):
+                   select=None, properties=False):
         """Seam 1 + 2 for every contig.  offtarget=True also runs the genome-wide seed scan over all
         arenas (single process: no reduce) and attaches (n, 4) counts to every contig's hits;
         seeds_from_scan=False makes the off-target step derive its seeds from the planes itself (the
@@ -767,10 +803,22 @@ class Genome:
         specificity (a dict of specificity_columns' arguments, {} for the defaults): every contig's hits also carry the
         self search's counts and sums, joined on the GPU while the tables are resident.
         select (select.Request): hits.selection is the best K guides of every gene (Genome.select), chosen on the GPU after
-        the annotation look-up and, with specificity, between its join and the closing of the self-search handles."""
+        the annotation look-up and, with specificity, between its join and the closing of the self-search handles.
+        properties=True: hits.properties holds, per contig, the packed guide properties (props_plus, props_minus) of its rows
+        (properties.unpack turns a column into gc, run, t_run, stem), and every contig's hit dict carries them.  The kernel runs
+        after the scan and before the selection and the specificity join; a select.Request with property limits runs it too
+        (the column then stays on the device unless properties=True)."""
+        if properties and not 1 <= guide_len <= 50:
+            raise ValueError("guide properties exist for guide lengths 1..50, not %d" % guide_len)
         if select is not None and guide_len != 20:
             raise ValueError("the guide selection ranks by the on-target score, which exists at guide length 20 only")
         hits = self._scan_score(guide_len, want_pre, offtarget, seeds_from_scan, annotation)
+        if properties or (select is not None and select.property_limits is not None):
+            cols = self.guide_properties([(h.n_plus, h.n_minus) for h in hits.per_arena], fetch=bool(properties))
+            if properties:
+                for h, (pp, pm) in zip(hits.per_arena, cols):
+                    h.props_plus, h.props_minus = pp, pm
+                hits.properties = [tuple(hits.contig(k)[key] for key in ("props_plus", "props_minus")) for k in range(self.n_contigs)]
         if specificity is not None:  # (the tables of an arena stay valid until its next scan)
             if select is None:
                 hits.columns = self.specificity_columns(guide_len, **specificity)
@@ -848,6 +896,7 @@ class GenomeHits:
         self.n_minus = sum(h.n_minus for h in per_arena)
         self.columns = None  # per contig, further columns of its rows (Genome.scan_score(specificity=..))
         self.selection = None  # select.Selection (Genome.scan_score(select=..))
+        self.properties = None  # per contig (props_plus, props_minus), packed (Genome.scan_score(properties=True))
 
     def contig(self, k):
         a, j = self._genome._where[k]

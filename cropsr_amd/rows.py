@@ -24,6 +24,7 @@ import numpy as np
 HEADER = ["crispr_id", "crispr_sys", "sequence", "long_sequence", "chromosome", "start_pos",
           "end_pos", "cutsite", "strand", "on_site_score", "features", "status"]
 OFFTARGET_HEADER = ["offtarget_seed_mm0", "offtarget_seed_mm1", "offtarget_seed_mm2", "offtarget_seed_mm3"]  # --offtarget
+PROPERTIES_HEADER = ["guide_gc", "guide_run", "guide_t_run", "guide_stem"]  # --properties (properties.py)
 NO_FEATURE = 0xFFFFFFFF
 UNJOINED_COUNT, UNJOINED_SUM = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF  # --specificity: a hit without a guide site's row (search.py, CSV join)
 
@@ -43,6 +44,15 @@ def _self_columns(hits):
     counts = np.ascontiguousarray(np.concatenate([cp.reshape(-1, width), cm.reshape(-1, width)]), dtype=np.uint32)
     sums = np.ascontiguousarray(np.concatenate([hits["self_sum_plus"], hits["self_sum_minus"]]), dtype=np.uint64)
     return counts, sums
+
+
+def _props_column(hits):
+    """The packed guide properties of a contig's rows ('+' rows, then '-' rows) when its hits carry them (--properties), else None."""
+    if hits.get("props_plus") is None:
+        return None
+    return np.ascontiguousarray(np.concatenate([hits["props_plus"], hits["props_minus"]]), dtype=np.uint32)
+
+
 CHUNK = 1000000  # CROPSR.py:453
 ORDER_BODY4, ORDER_TAIL2, ORDER_DOT1 = 0, 1, 2  # include/cropsr_hip.h CRP_ORDER_*
 
@@ -98,6 +108,7 @@ class ContigRows:
             self.ot = np.concatenate([hits["ot_plus"].reshape(-1, 4), hits["ot_minus"].reshape(-1, 4)]).astype(np.int64)
             self.ot[self.ot == 0xFFFFFFFF] = -1
         self.self_counts, self.self_sum = _self_columns(hits)  # (--specificity)
+        self.props = _props_column(hits)  # (--properties)
         ip = hits["pos_plus"].astype(np.int64)
         jm = hits["pos_minus"].astype(np.int64)
         self.n = int(ip.size + jm.size)
@@ -124,6 +135,8 @@ class ContigRows:
             extra += tuple(-1 if int(v) == UNJOINED_COUNT else int(v) for v in self.self_counts[k])
             hs = int(self.self_sum[k])
             extra += (-1, -1) if hs == UNJOINED_SUM else (hs, float(1.0 / (1.0 + np.float64(np.uint64(hs)) / float(1 << 30))))
+        if self.props is not None:  # guide_gc, guide_run, guide_t_run, guide_stem
+            extra += tuple(int(self.props[k]) >> (8 * b) & 255 for b in range(4))
         if len(self.long[k]) == 30:  # CROPSR.py:466
             feat = ""
             if self.features is not None and self.features[1][k] != NO_FEATURE:
@@ -218,11 +231,17 @@ class Dataset:
         return out
 
 
-def write_header(path, offtarget=False, specificity=None):
+def extra_header(offtarget=False, specificity=None, properties=False):
+    """The opt-in column names, in the order the rows carry them: off-target, --specificity at M mismatches, --properties."""
+    return ((OFFTARGET_HEADER if offtarget else []) + ([] if specificity is None else SPECIFICITY_HEADER(specificity)) +
+            (PROPERTIES_HEADER if properties else []))
+
+
+def write_header(path, offtarget=False, specificity=None, properties=False):
     """CROPSR.py:402-405 (plus the four opt-in off-target column names, then the opt-in --specificity names for
-    specificity = M mismatches)."""
+    specificity = M mismatches, then the four opt-in --properties names)."""
     with open(path, "w", newline="") as f:
-        csv.writer(f).writerow(HEADER + (OFFTARGET_HEADER if offtarget else []) + ([] if specificity is None else SPECIFICITY_HEADER(specificity)))
+        csv.writer(f).writerow(HEADER + extra_header(offtarget, specificity, properties))
 
 
 def write_pass(path, dataset, rescore):
@@ -262,6 +281,7 @@ class ContigTable:
             self.ot = np.ascontiguousarray(np.concatenate([hits["ot_plus"].reshape(-1, 4), hits["ot_minus"].reshape(-1, 4)]),
                                            dtype=np.uint32)
         self.self_counts, self.self_sum = _self_columns(hits)  # (--specificity)
+        self.props = _props_column(hits)  # (--properties)
         self.chrom = name_token[1:].encode("utf-8")
         self.chrom_u8 = np.frombuffer(self.chrom, dtype=np.uint8)  # (the pointer crp_write_segments reads the name through)
         self.text = np.frombuffer(s.encode("ascii", "replace") if isinstance(s, str) else s, dtype=np.uint8)
@@ -348,7 +368,8 @@ class NativeDataset:
                         seqs[r] = np.frombuffer(t.encode("ascii", "replace"), dtype=np.uint8)
                     score[fix] = rescore(seqs, order)
                 extras = (None if blk.feat_idx is None else blk.feat_idx[k0:k1], None if blk.ot is None else blk.ot[k0:k1],
-                          None if blk.self_counts is None else (blk.self_counts[k0:k1], blk.self_sum[k0:k1]))
+                          None if blk.self_counts is None else (blk.self_counts[k0:k1], blk.self_sum[k0:k1]),
+                          None if blk.props is None else blk.props[k0:k1])
                 yield blk, blk.pos[k0:k1], blk.minus[k0:k1], score, np.ascontiguousarray(sel[g - lo:g - lo + m]), extras
             g = base + blk.n
             b += 1
@@ -384,7 +405,7 @@ class NativeDataset:
         """The same chunk as crp_row_segment entries appended to `segs` (for write_segments); every array a segment points
         into is appended to `keep` and must outlive the call that writes them."""
         from . import _native as nat
-        for blk, pos, minus, score, ids_part, (feat_idx, ot, joined) in self._segments(lo, count, ids_u8, index_range, rescore, ids_rev):
+        for blk, pos, minus, score, ids_part, (feat_idx, ot, joined, props) in self._segments(lo, count, ids_u8, index_range, rescore, ids_rev):
             g = nat.RowSegment()
             score = np.ascontiguousarray(score)
             keep.extend((blk, pos, minus, score, ids_part))
@@ -403,6 +424,10 @@ class NativeDataset:
                 counts, sums = np.ascontiguousarray(joined[0]), np.ascontiguousarray(joined[1])
                 keep.extend((counts, sums))
                 g.extra = nat.RowExtra(counts.ctypes.data, counts.shape[1], sums.ctypes.data)
+            if props is not None:  # (--properties: the segment's packed column, the same way)
+                props = np.ascontiguousarray(props)
+                keep.append(props)
+                g.props = props.ctypes.data
             segs.append(g)
 
     def chunk_to_fd(self, fd, lo, count, ids_u8, index_range, rescore, ids_rev=None):
@@ -421,7 +446,16 @@ def write_segments(fd, segs, guide_len, n_threads):
     arr = (nat.RowSegment * len(segs))(*segs)
     written = ctypes.c_uint64()
     extras = [getattr(g, "extra", None) for g in segs]  # (--specificity: chunk_segments hangs a RowExtra on the segment)
-    if any(e is not None for e in extras):
+    props = [getattr(g, "props", None) for g in segs]  # (--properties: and the address of its packed column)
+    if any(p is not None for p in props):
+        what = "crp_write_segments_props"
+        ext = None
+        if any(e is not None for e in extras):
+            ext = (nat.RowExtra * len(segs))(*[e if e is not None else nat.RowExtra() for e in extras])
+        ptrs = (ctypes.c_void_p * len(segs))(*props)
+        st = nat.lib().crp_write_segments_props(fd, guide_len, ctypes.cast(arr, ctypes.c_void_p), None if ext is None else ctypes.cast(ext, ctypes.c_void_p),
+                                                ctypes.cast(ptrs, ctypes.c_void_p), len(segs), ctypes.byref(written), n_threads)
+    elif any(e is not None for e in extras):
         what = "crp_write_segments_cols"
         ext = (nat.RowExtra * len(segs))(*[e if e is not None else nat.RowExtra() for e in extras])
         st = nat.lib().crp_write_segments_cols(fd, guide_len, ctypes.cast(arr, ctypes.c_void_p), ctypes.cast(ext, ctypes.c_void_p), len(segs),

@@ -19,8 +19,9 @@ Definition, per arena, after a crp_scan_score at guide length 20 (tests/select_r
             gene's rows are one contiguous run per strand table.
   passes    a row PASSES when it is in the gene; its score >= min_score (float64); with joined specificity columns it
             is joined (counts[0] != 0xFFFFFFFF), counts[0] <= max_mm0 and hit_sum <= max_hit_sum (integer compares);
-            and with require_cds the flag byte of its label-set id is non-zero (NO_FEATURE fails; the flag is 1 for a
-            label-set string that holds a `CDS:` label, computed on the host from the string table).
+            with require_cds the flag byte of its label-set id is non-zero (NO_FEATURE fails; the flag is 1 for a
+            label-set string that holds a `CDS:` label, computed on the host from the string table); and with property
+            limits (properties.py) gc_min <= gc <= gc_max, run <= max_run, t_run <= max_t_run and stem <= max_stem.
   order     among passing rows: higher score first -- scores are positive finite doubles, so their bit patterns order
             as unsigned 64-bit integers --, ties (repeats give identical 30-mers) by smaller cut site, then '+' before
             '-'.  The order is total: the result does not depend on how the work was cut.
@@ -89,11 +90,16 @@ class Params:
 
 
 class Request:
-    """A selection for a backend's scan: Params, the annotate.Request that names the genes, and slice_rows (None: the
-    library's default; results do not depend on it)."""
+    """A selection for a backend's scan: Params, the annotate.Request that names the genes, slice_rows (None: the
+    library's default; results do not depend on it) and the limits on the guide properties (properties.py), as counts:
+    gc_min <= gc <= gc_max, run <= max_run, t_run <= max_t_run, stem <= max_stem.  With any of them given a row passes
+    only if all hold, and the scan runs the property kernel before the selection."""
 
-    def __init__(self, params, annotation, slice_rows=None):
+    def __init__(self, params, annotation, slice_rows=None, gc_min=None, gc_max=None, max_run=None, max_t_run=None, max_stem=None):
+        from .properties import Limits
         self.params, self.annotation, self.slice_rows = params, annotation, slice_rows
+        given = [v is not None for v in (gc_min, gc_max, max_run, max_t_run, max_stem)]
+        self.property_limits = Limits(gc_min, gc_max, max_run, max_t_run, max_stem) if any(given) else None
 
 
 class ArenaSelect:
@@ -125,6 +131,11 @@ class ArenaSelect:
 
     def set_limits(self, slice_rows=0):
         nat.check(nat.lib().crp_select_set_limits(self._h, int(slice_rows)), "crp_select_set_limits", self._ctx)
+
+    def set_property_limits(self, limits):
+        """limits: properties.Limits, or None to clear them."""
+        lim = None if limits is None else ctypes.byref(nat.SelectPropertyLimits(*limits.astuple()))
+        nat.check(nat.lib().crp_select_set_property_limits(self._h, lim), "crp_select_set_property_limits", self._ctx)
 
     def run(self, params, self_search=None):
         """params: Params; self_search: the search.ArenaSelfSearch of this arena after its join_hits, or None."""
@@ -249,6 +260,8 @@ def select_arena(genome, a, request, handle=None, flags=None):
             sel.set_flags(flags if flags is not None else request.annotation.annotation.cds_flags())
         if request.slice_rows:
             sel.set_limits(request.slice_rows)
+        if getattr(request, "property_limits", None) is not None:
+            sel.set_property_limits(request.property_limits)
         sel.run(request.params, handle)
         n_in, n_pass, picked = sel.fetch()
         return lo, hi, gene, n_in, n_pass, picked, sel.stats()

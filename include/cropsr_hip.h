@@ -280,6 +280,14 @@ typedef struct crp_row_extra {
 int crp_write_segments_cols(int fd, int guide_len, const crp_row_segment *segs, const crp_row_extra *extras, uint64_t n_segs,
                             uint64_t *bytes_written, int n_threads);
 
+/* The same with the OPT-IN guide property columns (crp_guide_properties): props, when not NULL, is an
+ * array parallel to segs of one pointer per segment -- the packed word of every row of the segment, or NULL, which adds
+ * nothing; with props == NULL the call is crp_write_segments_cols.  Every row of such a segment -- the 11-field rows too
+ * -- gets four more decimal integer fields, after the specificity fields if present: guide_gc, guide_run, guide_t_run,
+ * guide_stem. */
+int crp_write_segments_props(int fd, int guide_len, const crp_row_segment *segs, const crp_row_extra *extras,
+                             const uint32_t *const *props, uint64_t n_segs, uint64_t *bytes_written, int n_threads);
+
 /* ---- multi-GPU: one process per GPU, RCCL over xGMI ------------------------ */
 /* The reference has no parallelism (its only hint is the dead cropsr_functions.py:256-273).  The path
  * shards by contig with no collective on the data path; the one exchange is the final gatherv of the
@@ -821,6 +829,37 @@ int crp_select_fetch(crp_select *select, uint32_t *n_in, uint32_t *n_pass, uint3
  * out[6] table rows the items cover, out[7] bytes read per such row, out[8] genes that went through the merge.
  * n: how many of these to write (<= 9). */
 int crp_select_stats(const crp_select *select, double *out, int n);
+/* Property limits (the column of crp_guide_properties, below): with limits set a row PASSES only if also
+ * gc_min <= gc <= gc_max, run <= max_run, t_run <= max_t_run and stem <= max_stem; crp_select_run then reads 4 more
+ * bytes per row (crp_select_stats counts them) and returns CRP_ERR_STATE when the arena holds no property column for its
+ * current tables.  NULL clears the limits. */
+typedef struct crp_select_property_limits {
+    uint32_t gc_min, gc_max, max_run, max_t_run, max_stem;
+} crp_select_property_limits;
+int crp_select_set_property_limits(crp_select *select, const crp_select_property_limits *limits);
+
+/* ---- guide sequence properties (opt-in, absent from the reference) --------------------- */
+/* After crp_scan_score on `arena` at guide length l = 1 .. 50: four values per kept hit, each a pure function of the l
+ * letters of its guide WINDOW in the forward text -- s[i - l : i] for a '+' row with match index i, s[j + 3 : j + 3 + l]
+ * for a '-' row with match index j.  A window letter is a BASE when it is one of acgtACGT or U (case is ignored, U is A);
+ * everything else -- N, IUPAC letters, decoration, positions past the end of the contig string (a '-' row may have up
+ * to 10) -- is a non-base.
+ *   gc      window letters that are C or G
+ *   run     the longest run of equal bases (a non-base ends a run; 0 when the window holds no base)
+ *   t_run   the longest run of T in the spacer's own orientation: of T in a '+' window, of A in a '-' window (whose
+ *           spacer is the window's reverse complement)
+ *   stem    the largest s >= 0 for which indices a, b exist with w[a + t] complementary to w[b - t] (A-T or C-G, both
+ *           bases, no wobble pair) for t = 0 .. s - 1 and (b - s + 1) - (a + s) >= 3: at least three unpaired letters
+ *           in the loop.  At most (l - 3) / 2; the same for a window and its reverse complement.
+ * One uint32 per row: gc | run << 8 | t_run << 16 | stem << 24, table order.  The column stays in HBM until the arena's
+ * next scan (crp_select_set_property_limits reads it there) and is copied to props_plus / props_minus (n_plus / n_minus
+ * values; either may be NULL).  One kernel lane per row, one launch for both tables.  CRP_ERR_STATE: no tables;
+ * CRP_ERR_INVALID with a crp_last_error text: the tables were scanned at guide length 0. */
+int crp_guide_properties(crp_arena *arena, uint32_t *props_plus, uint32_t *props_minus);
+/* The last crp_guide_properties of the arena (CRP_ERR_STATE without a column for the current tables): out[0] ms of its
+ * kernel (HIP events), out[1] rows, out[2] the guide length.  n: how many of these to write (<= 3).  With
+ * crp_profile_enable(ctx, 2) the kernel is also accounted under CRP_K_PROPERTIES. */
+int crp_guide_properties_stats(const crp_arena *arena, double *out, int n);
 
 /* ---- options -------------------------------------------------------------- */
 /* CRP_OPT_TWO_PASS (value 0/1, default 0): with 0 crp_scan_score is ONE kernel launch; the
@@ -877,7 +916,8 @@ int crp_profile_read(crp_ctx *ctx, double ms[3], uint64_t launches[3], int reset
 #define CRP_K_GATHER 6       /* RCCL gatherv of the hit tables (count all-gather + grouped send/recv) */
 #define CRP_K_OT_REDUCE 7    /* RCCL all-reduce of the site histogram */
 #define CRP_K_ANNOTATE 8     /* annotation join: the look-up kernel of one crp_annotate_lookup (both tables, one launch) */
-#define CRP_K_KINDS 9
+#define CRP_K_PROPERTIES 9   /* guide properties: the kernel of one crp_guide_properties (both tables, one launch) */
+#define CRP_K_KINDS 10
 int crp_profile_read_kind(crp_ctx *ctx, int kind, double *ms, uint64_t *launches, int reset);
 /* Blocks until everything queued on the library's stream has finished. */
 int crp_synchronize(crp_ctx *ctx);
