@@ -33,7 +33,7 @@ import ctypes
 import numpy as np
 
 from . import _native as nat
-from . import fasta
+from . import fasta, hitcols
 
 NO_FEATURE = nat.NO_FEATURE
 
@@ -226,4 +226,4 @@ class Request:
 def features_of(request, hits):
     """(string table, idx) for rows.ContigTable / ContigRows from a contig's hit dict that carries the device's
     feat_plus / feat_minus columns (rows in the reference's order: '+' hits, then '-' hits)."""
-    return request.annotation.strings, np.concatenate([hits["feat_plus"], hits["feat_minus"]]).astype(np.uint32, copy=False)
+    return request.annotation.strings, hitcols.both(hits, "feat")

@@ -16,7 +16,7 @@ from multiprocessing import cpu_count
 
 import numpy as np
 
-from . import fasta, rows
+from . import fasta, hitcols, rows
 
 __version__ = "1.11b"  # the CROPSR version whose behaviour is reproduced
 
@@ -459,16 +459,14 @@ def refilter_hits(hits, n, l):
     """CROPSR.py:419 and :430, all four clauses each, on the hit tables of one contig string of n characters (match
     indices i of (?=.GG), j of (?=CC.)) -- for guide lengths the engine scanned with a clamped length
     (device_guide_length).  Every surviving row is unscored (-1), like the reference writes it."""
-    out = dict(hits)
-    for strand in ("plus", "minus"):
+    keep = {}
+    for strand in hitcols.STRANDS:
         p = np.asarray(hits["pos_" + strand]).astype(np.int64)
         a, b = (p - l, p) if strand == "plus" else (p + 3, p + 3 + l)  # pam_location (:418 / :429)
-        keep = (a >= 5) & (a + 5 <= n + 10) & (b >= 5) & (b <= n + 10)
-        for key in ("pos_", "score_", "pre_", "ot_", "feat_"):
-            col = hits.get(key + strand)
-            if col is not None:
-                out[key + strand] = np.asarray(col)[keep]
-        out["score_" + strand] = np.full(int(keep.sum()), -1.0)
+        keep[strand] = (a >= 5) & (a + 5 <= n + 10) & (b >= 5) & (b <= n + 10)
+    out = hitcols.take(hits, keep["plus"], keep["minus"])
+    for strand in hitcols.STRANDS:
+        out["score_" + strand] = np.full(int(keep[strand].sum()), -1.0)
     return out
 
 
@@ -618,15 +616,11 @@ def write_selection(path, selection, names, strings, all_hits, guide_len, offtar
         minus = sel_rows["strand"][mine] == b"-"
         mine = np.concatenate([mine[~minus], mine[minus]])  # ('+' rows first, as ContigRows holds a contig's rows)
         n_plus = int((~minus).sum())
-        hits, mini = all_hits[c], {}
-        for key, col in hits.items():
-            if col is None or not (key.endswith("_plus") or key.endswith("_minus")):
-                continue
-            part = mine[:n_plus] if key.endswith("_plus") else mine[n_plus:]
-            mini[key] = np.asarray(col)[sel_rows["index"][part]]
+        index = sel_rows["index"][mine]
+        mini = hitcols.take(all_hits[c], index[:n_plus], index[n_plus:])
         feats = None
         if annotation is not None:
-            feats = (annotation.strings, np.concatenate([mini["feat_plus"], mini["feat_minus"]]))
+            feats = (annotation.strings, hitcols.both(mini, "feat"))
         block = rows.ContigRows(names[c], bytes(strings[c]).decode("latin-1"), mini, guide_len, features=feats)
         for k, at in enumerate(mine.tolist()):
             fields[at] = block.row(k, "")[1:]
@@ -974,7 +968,7 @@ def run(args, backend=None, out=sys.stdout, group=None):
                 continue
             feats = None
             if request is not None:  # the device's label-set id per row ('+' rows, then '-' rows) + the string table
-                feats = (request.annotation.strings, np.concatenate([hits["feat_plus"], hits["feat_minus"]]))
+                feats = (request.annotation.strings, hitcols.both(hits, "feat"))
             block = (rows.ContigTable(name, s, hits, args.l, features=feats) if native
                      else rows.ContigRows(name, bytes(s).decode("latin-1"), hits, args.l, features=feats))
             if once:

@@ -17,6 +17,7 @@ import weakref
 import numpy as np
 
 from . import _native as nat
+from . import hitcols
 
 
 def _as_u8(s):
@@ -41,7 +42,7 @@ def _add_contigs(handle, bufs, ctx):
     return offs
 
 
-class Hits:
+class Hits(hitcols.Table):
     """Hit tables of one Arena.scan_score() call (host copies).
 
     pos_* are ARENA positions, ascending per strand; `contig(k)` returns the
@@ -49,7 +50,7 @@ class Hits:
     exactly the regex match indices the reference iterates over:
       '+': i of (?=.GG): start_pos = i-l, end_pos = i, cutsite = i-3   (CROPSR.py:418,157)
       '-': j of (?=CC.): start_pos = j+3+l, end_pos = j+3, cutsite = j  (CROPSR.py:429,433)
-    score == -1 marks rows whose 30-character window is incomplete (CROPSR.py:466-468).
+    score == -1 marks rows whose 30-character window is incomplete (CROPSR.py:466-468); ot_*, feat_*, props_* are None until set.
     """
 
     def __init__(self, offsets, lengths, guide_len, cols):
@@ -58,40 +59,11 @@ class Hits:
         self.guide_len = guide_len
         self.pos_plus, self.pre_plus, self.score_plus = cols[0:3]
         self.pos_minus, self.pre_minus, self.score_minus = cols[3:6]
-        self.ot_plus = self.ot_minus = None  # (n, 4) uint32 once an off-target scan has run
-        self.feat_plus = self.feat_minus = None  # uint32 label-set ids once the annotation join has run
-        self.props_plus = self.props_minus = None  # uint32 packed guide properties once crp_guide_properties has run
         # (needles in the tables' own dtype, uint32: arena positions stay below 2^31 -- otherwise numpy converts the tables)
         starts = np.asarray(offsets).astype(np.uint32)
         ends = (np.asarray(offsets) + np.asarray(lengths)).astype(np.uint32)
-        self._cut_plus = (np.searchsorted(self.pos_plus, starts, "left"), np.searchsorted(self.pos_plus, ends, "left"))
-        self._cut_minus = (np.searchsorted(self.pos_minus, starts, "left"), np.searchsorted(self.pos_minus, ends, "left"))
-
-    @property
-    def n_plus(self):
-        return int(self.pos_plus.size)
-
-    @property
-    def n_minus(self):
-        return int(self.pos_minus.size)
-
-    def contig(self, k):
-        off = int(self.offsets[k])
-        a, b = int(self._cut_plus[0][k]), int(self._cut_plus[1][k])
-        c, d = int(self._cut_minus[0][k]), int(self._cut_minus[1][k])
-        sl = lambda arr, x, y: None if arr is None else arr[x:y]
-        out = dict(
-            pos_plus=(self.pos_plus[a:b] - np.uint32(off)), pre_plus=sl(self.pre_plus, a, b),
-            score_plus=self.score_plus[a:b],
-            pos_minus=(self.pos_minus[c:d] - np.uint32(off)), pre_minus=sl(self.pre_minus, c, d),
-            score_minus=self.score_minus[c:d])
-        if self.ot_plus is not None:  # off-target counts travel with the rows they belong to
-            out["ot_plus"], out["ot_minus"] = self.ot_plus[a:b], self.ot_minus[c:d]
-        if self.feat_plus is not None:
-            out["feat_plus"], out["feat_minus"] = self.feat_plus[a:b], self.feat_minus[c:d]
-        if self.props_plus is not None:
-            out["props_plus"], out["props_minus"] = self.props_plus[a:b], self.props_minus[c:d]
-        return out
+        self._cuts = [(np.searchsorted(pos, starts, "left"), np.searchsorted(pos, ends, "left")) for pos in (self.pos_plus, self.pos_minus)]
+        self._origins = offsets
 
 
 class Arena:
@@ -193,28 +165,24 @@ class Arena:
         nat.check(nat.lib().crp_annotate_set_track(self._h, points.ctypes.data_as(nat.u32p), ids.ctypes.data_as(nat.u32p),
                                                    points.size), "crp_annotate_set_track", self._engine._ctx)
 
+    def _step(self, what, n_plus, n_minus, fetch, width=None):
+        """The library call `what`(arena, plus, minus): a device step over the last scan's tables that makes one uint32 column per
+        strand.  fetch: they come back as a (plus, minus) pair of host arrays, (n,) or (n, width); else they stay in HBM: None."""
+        pair = [np.empty(n if width is None else (n, width), dtype=np.uint32) for n in (n_plus, n_minus)] if fetch else [None, None]
+        nat.check(getattr(nat.lib(), what)(self._h, *[None if a is None else a.ctypes.data_as(nat.u32p) for a in pair]), what,
+                  self._engine._ctx)
+        return tuple(pair) if fetch else None
+
     def annotate_lookup(self, n_plus, n_minus, fetch=True):
         """Label-set id per kept hit of the last scan (NO_FEATURE: none / no cut site), computed on the GPU from the
         resident tables; fetch=False leaves them in HBM for gather_hits(features=True)."""
-        if not fetch:
-            nat.check(nat.lib().crp_annotate_lookup(self._h, None, None), "crp_annotate_lookup", self._engine._ctx)
-            return None
-        fp, fm = np.empty(n_plus, dtype=np.uint32), np.empty(n_minus, dtype=np.uint32)
-        nat.check(nat.lib().crp_annotate_lookup(self._h, fp.ctypes.data_as(nat.u32p), fm.ctypes.data_as(nat.u32p)),
-                  "crp_annotate_lookup", self._engine._ctx)
-        return fp, fm
+        return self._step("crp_annotate_lookup", n_plus, n_minus, fetch)
 
     # ---- guide sequence properties (opt-in; properties.py has the definition)
     def guide_properties(self, n_plus, n_minus, fetch=True):
         """The packed properties (gc | run << 8 | t_run << 16 | stem << 24) of every kept hit of the last scan, computed on
         the GPU from the planes; fetch=False leaves the column in HBM (for a selection's property limits)."""
-        if not fetch:
-            nat.check(nat.lib().crp_guide_properties(self._h, None, None), "crp_guide_properties", self._engine._ctx)
-            return None
-        pp, pm = np.empty(n_plus, dtype=np.uint32), np.empty(n_minus, dtype=np.uint32)
-        nat.check(nat.lib().crp_guide_properties(self._h, pp.ctypes.data_as(nat.u32p), pm.ctypes.data_as(nat.u32p)),
-                  "crp_guide_properties", self._engine._ctx)
-        return pp, pm
+        return self._step("crp_guide_properties", n_plus, n_minus, fetch)
 
     def guide_properties_stats(self):
         """dict(kernel_ms, rows, guide_len) of the last guide_properties() on the current tables."""
@@ -239,19 +207,10 @@ class Arena:
 
     def offtarget_counts(self, n_plus, n_minus, fetch=True):
         """(n, 4) uint32 per strand: other sites at seed distance 0..3 (0xFFFFFFFF: not a site)."""
-        if not fetch:
-            nat.check(nat.lib().crp_offtarget_counts(self._h, None, None), "crp_offtarget_counts", self._engine._ctx)
-            return None
-        cp, cm = np.empty((n_plus, 4), dtype=np.uint32), np.empty((n_minus, 4), dtype=np.uint32)
-        nat.check(nat.lib().crp_offtarget_counts(self._h, cp.ctypes.data_as(nat.u32p), cm.ctypes.data_as(nat.u32p)),
-                  "crp_offtarget_counts", self._engine._ctx)
-        return cp, cm
+        return self._step("crp_offtarget_counts", n_plus, n_minus, fetch, width=4)
 
     def offtarget_seeds(self, n_plus, n_minus):
-        sp, sm = np.empty(n_plus, dtype=np.uint32), np.empty(n_minus, dtype=np.uint32)
-        nat.check(nat.lib().crp_offtarget_seeds(self._h, sp.ctypes.data_as(nat.u32p), sm.ctypes.data_as(nat.u32p)),
-                  "crp_offtarget_seeds", self._engine._ctx)
-        return sp, sm
+        return self._step("crp_offtarget_seeds", n_plus, n_minus, True)
 
 
 class PinnedTables:
@@ -818,7 +777,6 @@ class Genome:
             if properties:
                 for h, (pp, pm) in zip(hits.per_arena, cols):
                     h.props_plus, h.props_minus = pp, pm
-                hits.properties = [tuple(hits.contig(k)[key] for key in ("props_plus", "props_minus")) for k in range(self.n_contigs)]
         if specificity is not None:  # (the tables of an arena stay valid until its next scan)
             if select is None:
                 hits.columns = self.specificity_columns(guide_len, **specificity)
@@ -837,27 +795,23 @@ class Genome:
         return hits
 
     def _scan_score(self, guide_len, want_pre, offtarget, seeds_from_scan, annotation):
+        # (the tables of an arena stay valid until its next scan: the opt-in steps work on them where they lie)
         if not offtarget:
             per_arena = [a.scan_score(guide_len, want_pre) for a in self.arenas]
-            if annotation is not None:  # (the tables of an arena stay valid until its next scan)
-                for h, f in zip(per_arena, self.annotate(annotation, [(h.n_plus, h.n_minus) for h in per_arena])):
-                    h.feat_plus, h.feat_minus = f
-            return GenomeHits(self, per_arena)
-        eng = self._engine
-        eng.offtarget_reset()
-        counts, per_arena = [], []
-        for a in self.arenas:
-            n = a.scan_score_device(guide_len, want_pre, want_seeds=seeds_from_scan)
-            a.offtarget_add(guide_len)
-            counts.append(n)
-        eng.offtarget_solve()
-        for a, (n_plus, n_minus) in zip(self.arenas, counts):
-            # (the tables of an arena stay valid until its next scan)
-            h = Hits(a.offsets, a.lengths, guide_len, a.fetch(n_plus, n_minus, want_pre))
-            h.ot_plus, h.ot_minus = a.offtarget_counts(n_plus, n_minus)
-            per_arena.append(h)
+        else:
+            eng = self._engine
+            eng.offtarget_reset()
+            counts, per_arena = [], []
+            for a in self.arenas:
+                counts.append(a.scan_score_device(guide_len, want_pre, want_seeds=seeds_from_scan))
+                a.offtarget_add(guide_len)
+            eng.offtarget_solve()
+            for a, (n_plus, n_minus) in zip(self.arenas, counts):
+                h = Hits(a.offsets, a.lengths, guide_len, a.fetch(n_plus, n_minus, want_pre))
+                h.ot_plus, h.ot_minus = a.offtarget_counts(n_plus, n_minus)
+                per_arena.append(h)
         if annotation is not None:
-            for h, f in zip(per_arena, self.annotate(annotation, counts)):
+            for h, f in zip(per_arena, self.annotate(annotation, [(h.n_plus, h.n_minus) for h in per_arena])):
                 h.feat_plus, h.feat_minus = f
         return GenomeHits(self, per_arena)
 
@@ -896,7 +850,6 @@ class GenomeHits:
         self.n_minus = sum(h.n_minus for h in per_arena)
         self.columns = None  # per contig, further columns of its rows (Genome.scan_score(specificity=..))
         self.selection = None  # select.Selection (Genome.scan_score(select=..))
-        self.properties = None  # per contig (props_plus, props_minus), packed (Genome.scan_score(properties=True))
 
     def contig(self, k):
         a, j = self._genome._where[k]
@@ -904,6 +857,13 @@ class GenomeHits:
         if self.columns is not None:
             out.update(self.columns[k])
         return out
+
+    @property
+    def properties(self):
+        """Per contig (props_plus, props_minus), packed: the contig slices' own (Genome.scan_score(properties=True)), else None."""
+        if any(h.props_plus is None for h in self.per_arena):
+            return None
+        return [tuple(self.contig(k)[key] for key in hitcols.keys(["props"])) for k in range(self._genome.n_contigs)]
 
 
 def pack_ascii(text, n_threads=1):

@@ -20,6 +20,7 @@ import ctypes
 import numpy as np
 
 from . import _native as nat
+from . import hitcols
 from .engine import _as_u8
 
 
@@ -44,38 +45,18 @@ def comm_stuck():
     return int(nat.lib().crp_node_comm_stuck())
 
 
-class NodeHits:
+class NodeHits(hitcols.Table):
     """The gathered tables of one Node.scan(): pos_* are positions LOCAL to their contig string (the regex match indices
-    of CROPSR.py:418 / :429), contig after contig; `contig(k)` slices contig k's rows like engine.Hits.contig(k)."""
+    of CROPSR.py:418 / :429), contig after contig; `contig(k)` slices contig k's rows like engine.Hits.contig(k).  ot_* and
+    feat_* are None unless the gather carried them."""
 
     def __init__(self, per_contig, cols, guide_len):
         self.guide_len = guide_len
         self.pos_plus, self.score_plus, self.pos_minus, self.score_minus = cols
-        self.ot_plus = self.ot_minus = None      # (n, 4) uint32 after a gather with offtarget=True
-        self.feat_plus = self.feat_minus = None  # uint32 label-set ids after a gather with features=True
         counts = np.asarray(per_contig, dtype=np.int64).reshape(-1, 2)
-        self._cut_plus = np.concatenate(([0], np.cumsum(counts[:, 0])))
-        self._cut_minus = np.concatenate(([0], np.cumsum(counts[:, 1])))
+        ends = np.cumsum(counts, axis=0)
+        self._cuts = [(ends[:, strand] - counts[:, strand], ends[:, strand]) for strand in (0, 1)]
         self.counts = counts
-
-    @property
-    def n_plus(self):
-        return int(self.pos_plus.size)
-
-    @property
-    def n_minus(self):
-        return int(self.pos_minus.size)
-
-    def contig(self, k):
-        a, b = int(self._cut_plus[k]), int(self._cut_plus[k + 1])
-        c, d = int(self._cut_minus[k]), int(self._cut_minus[k + 1])
-        out = dict(pos_plus=self.pos_plus[a:b], score_plus=self.score_plus[a:b],
-                   pos_minus=self.pos_minus[c:d], score_minus=self.score_minus[c:d])
-        if self.ot_plus is not None:
-            out["ot_plus"], out["ot_minus"] = self.ot_plus[a:b], self.ot_minus[c:d]
-        if self.feat_plus is not None:
-            out["feat_plus"], out["feat_minus"] = self.feat_plus[a:b], self.feat_minus[c:d]
-        return out
 
 
 class Node:

@@ -34,6 +34,8 @@ scan_resident(texts, guide_len, offtarget=False) -> Resident   (offtarget: the s
 """
 import numpy as np
 
+from . import hitcols
+
 COLUMNS = ("pos_plus", "score_plus", "pos_minus", "score_minus")
 
 
@@ -138,27 +140,18 @@ def stitch_pieces(piece_hits):
     pos_minus, score_minus[, pre_*]) with positions relative to the scanned characters of
     piece_view, shift = the second value piece_view returned.  A hit belongs to the piece whose
     [start, end) contains its match index (the regex match position of CROPSR.py:98-104)."""
-    out = {}
-    for strand in ("plus", "minus"):
-        cols = {c: [] for c in ("pos", "score", "pre", "ot", "feat")}
-        for start, end, shift, hits in piece_hits:
+    parts = []
+    for start, end, shift, hits in piece_hits:
+        own = []
+        for strand in hitcols.STRANDS:
             pos = np.asarray(hits["pos_" + strand]).astype(np.int64) - shift + start  # contig coordinates
-            own = (pos >= start) & (pos < end)
-            cols["pos"].append(pos[own].astype(np.uint32))
-            cols["score"].append(np.asarray(hits["score_" + strand])[own])
-            for extra in ("pre", "ot", "feat"):
-                if hits.get(extra + "_" + strand) is not None:
-                    cols[extra].append(np.asarray(hits[extra + "_" + strand])[own])
-        out["pos_" + strand] = np.concatenate(cols["pos"]) if cols["pos"] else np.empty(0, np.uint32)
-        out["score_" + strand] = np.concatenate(cols["score"]) if cols["score"] else np.empty(0)
-        for extra in ("pre", "ot", "feat"):
-            if cols[extra]:
-                out[extra + "_" + strand] = np.concatenate(cols[extra])
-    return out
+            own.append((pos >= start) & (pos < end))
+        parts.append(hitcols.take(hits, own[0], own[1], origin=shift - start))
+    return hitcols.concat(parts)
 
 
 def _table_keys(offtarget, features=False):
-    return COLUMNS + (("ot_plus", "ot_minus") if offtarget else ()) + (("feat_plus", "feat_minus") if features else ())
+    return COLUMNS + hitcols.keys([stem for stem, wanted in (("ot", offtarget), ("feat", features)) if wanted])
 
 
 def pack_pos16(pos):
@@ -227,13 +220,7 @@ def slice_piece(cols, off, ln):
     bounds = np.array([off, off + ln], dtype=np.uint32)
     a, b = np.searchsorted(pp, bounds)
     c, d = np.searchsorted(pm, bounds)
-    out = dict(pos_plus=pp[a:b] - np.uint32(off), score_plus=np.asarray(cols["score_plus"])[a:b],
-               pos_minus=pm[c:d] - np.uint32(off), score_minus=np.asarray(cols["score_minus"])[c:d])
-    if "ot_plus" in cols:
-        out["ot_plus"], out["ot_minus"] = np.asarray(cols["ot_plus"])[a:b], np.asarray(cols["ot_minus"])[c:d]
-    if "feat_plus" in cols:
-        out["feat_plus"], out["feat_minus"] = np.asarray(cols["feat_plus"])[a:b], np.asarray(cols["feat_minus"])[c:d]
-    return out
+    return hitcols.take(dict(cols, pos_plus=pp, pos_minus=pm), slice(a, b), slice(c, d), origin=off)
 
 
 def merge_gathered(gathered, layouts):

@@ -21,38 +21,12 @@ import os
 
 import numpy as np
 
+from . import hitcols
+from .hitcols import OFFTARGET_HEADER, PROPERTIES_HEADER, SPECIFICITY_HEADER, UNJOINED_COUNT, UNJOINED_SUM  # noqa: F401 (the names live there)
+
 HEADER = ["crispr_id", "crispr_sys", "sequence", "long_sequence", "chromosome", "start_pos",
           "end_pos", "cutsite", "strand", "on_site_score", "features", "status"]
-OFFTARGET_HEADER = ["offtarget_seed_mm0", "offtarget_seed_mm1", "offtarget_seed_mm2", "offtarget_seed_mm3"]  # --offtarget
-PROPERTIES_HEADER = ["guide_gc", "guide_run", "guide_t_run", "guide_stem"]  # --properties (properties.py)
 NO_FEATURE = 0xFFFFFFFF
-UNJOINED_COUNT, UNJOINED_SUM = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF  # --specificity: a hit without a guide site's row (search.py, CSV join)
-
-
-def SPECIFICITY_HEADER(M):
-    """The M + 3 opt-in column names of --specificity at M mismatches: self_mm0 .. self_mmM, self_hit_sum, specificity."""
-    return ["self_mm%d" % k for k in range(int(M) + 1)] + ["self_hit_sum", "specificity"]
-
-
-def _self_columns(hits):
-    """(counts (n, M + 1) uint32, hit_sum (n,) uint64) of a contig's rows ('+' rows, then '-' rows) when its hits carry the
-    CSV join's columns (search.specificity_columns), else (None, None)."""
-    if hits.get("self_counts_plus") is None:
-        return None, None
-    cp, cm = np.asarray(hits["self_counts_plus"], dtype=np.uint32), np.asarray(hits["self_counts_minus"], dtype=np.uint32)
-    width = cp.shape[1] if cp.ndim == 2 else cm.shape[1]
-    counts = np.ascontiguousarray(np.concatenate([cp.reshape(-1, width), cm.reshape(-1, width)]), dtype=np.uint32)
-    sums = np.ascontiguousarray(np.concatenate([hits["self_sum_plus"], hits["self_sum_minus"]]), dtype=np.uint64)
-    return counts, sums
-
-
-def _props_column(hits):
-    """The packed guide properties of a contig's rows ('+' rows, then '-' rows) when its hits carry them (--properties), else None."""
-    if hits.get("props_plus") is None:
-        return None
-    return np.ascontiguousarray(np.concatenate([hits["props_plus"], hits["props_minus"]]), dtype=np.uint32)
-
-
 CHUNK = 1000000  # CROPSR.py:453
 ORDER_BODY4, ORDER_TAIL2, ORDER_DOT1 = 0, 1, 2  # include/cropsr_hip.h CRP_ORDER_*
 
@@ -99,16 +73,12 @@ class ContigRows:
 
     def __init__(self, name_token, s, hits, guide_len, features=None):
         """features (opt-in, --annotate): (strings, idx) -- row k's `features` column is
-        strings[idx[k]] (NO_FEATURE: ''); hits may carry ot_plus / ot_minus (--offtarget)."""
+        strings[idx[k]] (NO_FEATURE: ''); hits may carry the opt-in CSV columns (hitcols.csv_columns())."""
         l = guide_len
         self.chrom = name_token[1:]  # CROPSR.py:422 chromosome[1::]
         self.features = features
-        self.ot = None
-        if hits.get("ot_plus") is not None:
-            self.ot = np.concatenate([hits["ot_plus"].reshape(-1, 4), hits["ot_minus"].reshape(-1, 4)]).astype(np.int64)
-            self.ot[self.ot == 0xFFFFFFFF] = -1
-        self.self_counts, self.self_sum = _self_columns(hits)  # (--specificity)
-        self.props = _props_column(hits)  # (--properties)
+        cols = [(c.fields, hitcols.both(hits, c.stem)) for c in hitcols.csv_columns()]
+        self.extra = [(fields, column) for fields, column in cols if column is not None]  # in CSV order
         ip = hits["pos_plus"].astype(np.int64)
         jm = hits["pos_minus"].astype(np.int64)
         self.n = int(ip.size + jm.size)
@@ -130,13 +100,7 @@ class ContigRows:
 
     def row(self, k, crispr_id):
         strand = "+" if k < self.n_plus else "-"
-        extra = () if self.ot is None else tuple(int(v) for v in self.ot[k])
-        if self.self_counts is not None:  # n counts, hit_sum, specificity (search.specificity's expression; csv writes repr(float))
-            extra += tuple(-1 if int(v) == UNJOINED_COUNT else int(v) for v in self.self_counts[k])
-            hs = int(self.self_sum[k])
-            extra += (-1, -1) if hs == UNJOINED_SUM else (hs, float(1.0 / (1.0 + np.float64(np.uint64(hs)) / float(1 << 30))))
-        if self.props is not None:  # guide_gc, guide_run, guide_t_run, guide_stem
-            extra += tuple(int(self.props[k]) >> (8 * b) & 255 for b in range(4))
+        extra = sum((fields(column[k]) for fields, column in self.extra), ())
         if len(self.long[k]) == 30:  # CROPSR.py:466
             feat = ""
             if self.features is not None and self.features[1][k] != NO_FEATURE:
@@ -233,8 +197,7 @@ class Dataset:
 
 def extra_header(offtarget=False, specificity=None, properties=False):
     """The opt-in column names, in the order the rows carry them: off-target, --specificity at M mismatches, --properties."""
-    return ((OFFTARGET_HEADER if offtarget else []) + ([] if specificity is None else SPECIFICITY_HEADER(specificity)) +
-            (PROPERTIES_HEADER if properties else []))
+    return hitcols.csv_header(offtarget=offtarget, specificity=specificity, properties=properties)
 
 
 def write_header(path, offtarget=False, specificity=None, properties=False):
@@ -276,20 +239,15 @@ class ContigTable:
                 self.feat_blob = np.frombuffer(b"".join(enc) or b"\0", dtype=np.uint8)
                 self.feat_off = np.concatenate([[0], np.cumsum([len(e) for e in enc])]).astype(np.uint64)
             self.feat_idx = np.ascontiguousarray(features[1], dtype=np.uint32)
-        self.ot = None
-        if hits.get("ot_plus") is not None:
-            self.ot = np.ascontiguousarray(np.concatenate([hits["ot_plus"].reshape(-1, 4), hits["ot_minus"].reshape(-1, 4)]),
-                                           dtype=np.uint32)
-        self.self_counts, self.self_sum = _self_columns(hits)  # (--specificity)
-        self.props = _props_column(hits)  # (--properties)
+        self.cols = {c.stem: hitcols.both(hits, c.stem) for c in hitcols.csv_columns()}  # (None: the hits do not carry it)
         self.chrom = name_token[1:].encode("utf-8")
         self.chrom_u8 = np.frombuffer(self.chrom, dtype=np.uint8)  # (the pointer crp_write_segments reads the name through)
         self.text = np.frombuffer(s.encode("ascii", "replace") if isinstance(s, str) else s, dtype=np.uint8)
         self.n_plus = int(hits["pos_plus"].size)
-        self.pos = np.ascontiguousarray(np.concatenate([hits["pos_plus"], hits["pos_minus"]]), dtype=np.uint32)
+        self.pos = hitcols.both(hits, "pos")
         self.minus = np.zeros(self.pos.size, dtype=np.uint8)
         self.minus[self.n_plus:] = 1
-        self.score = np.ascontiguousarray(np.concatenate([hits["score_plus"], hits["score_minus"]]), dtype=np.float64)
+        self.score = hitcols.both(hits, "score")
         self.n = int(self.pos.size)
 
     def long_text(self, k):
@@ -325,8 +283,8 @@ class NativeDataset:
 
     def _segments(self, lo, count, ids_u8, index_range, rescore, ids_rev=None):
         """dataset[lo:lo+count], one rs1_score batch of the reference, cut at contig borders:
-        yields (block, pos, minus, score, ids) per piece (ids consumed backwards, tail rows
-        re-scored: see Dataset.rows).  ids_rev, if given, is ids[::-1] as a contiguous array
+        yields (block, pos, minus, score, ids, opt-in columns by stem -- "feat" and hitcols.csv_columns(), None where the
+        block lacks one) per piece (ids consumed backwards, tail rows re-scored: see Dataset.rows).  ids_rev, if given, is ids[::-1] as a contiguous array
         and is used instead of ids_u8: row r takes ids[index_range - r - 1], i.e. consecutive
         rows of ids_rev."""
         size = len(self)
@@ -367,10 +325,8 @@ class NativeDataset:
                         t = blk.long_text(k0 + j).replace("U", "T").upper()  # CROPSR.py:458
                         seqs[r] = np.frombuffer(t.encode("ascii", "replace"), dtype=np.uint8)
                     score[fix] = rescore(seqs, order)
-                extras = (None if blk.feat_idx is None else blk.feat_idx[k0:k1], None if blk.ot is None else blk.ot[k0:k1],
-                          None if blk.self_counts is None else (blk.self_counts[k0:k1], blk.self_sum[k0:k1]),
-                          None if blk.props is None else blk.props[k0:k1])
-                yield blk, blk.pos[k0:k1], blk.minus[k0:k1], score, np.ascontiguousarray(sel[g - lo:g - lo + m]), extras
+                cols = {stem: None if col is None else col[k0:k1] for stem, col in dict(blk.cols, feat=blk.feat_idx).items()}
+                yield blk, blk.pos[k0:k1], blk.minus[k0:k1], score, np.ascontiguousarray(sel[g - lo:g - lo + m]), cols
             g = base + blk.n
             b += 1
 
@@ -379,8 +335,8 @@ class NativeDataset:
         from . import _native as nat
         L = nat.lib()
         out = []
-        for blk, pos, minus, score, ids_part, extras in self._segments(lo, count, ids_u8, index_range, rescore, ids_rev):
-            if any(e is not None for e in extras):
+        for blk, pos, minus, score, ids_part, cols in self._segments(lo, count, ids_u8, index_range, rescore, ids_rev):
+            if any(col is not None for col in cols.values()):
                 raise ValueError("chunk_bytes formats the reference's columns only (use chunk_to_fd)")
             m = pos.size
             cap = m * (170 + 2 * len(blk.chrom)) + 64
@@ -405,29 +361,24 @@ class NativeDataset:
         """The same chunk as crp_row_segment entries appended to `segs` (for write_segments); every array a segment points
         into is appended to `keep` and must outlive the call that writes them."""
         from . import _native as nat
-        for blk, pos, minus, score, ids_part, (feat_idx, ot, joined, props) in self._segments(lo, count, ids_u8, index_range, rescore, ids_rev):
+        for blk, pos, minus, score, ids_part, cols in self._segments(lo, count, ids_u8, index_range, rescore, ids_rev):
             g = nat.RowSegment()
             score = np.ascontiguousarray(score)
             keep.extend((blk, pos, minus, score, ids_part))
             g.contig_text, g.contig_len = blk.text.ctypes.data, blk.text.size
             g.chrom, g.chrom_len = (blk.chrom_u8.ctypes.data if len(blk.chrom) else None), len(blk.chrom)
             g.pos, g.minus, g.score, g.ids, g.n_rows = pos.ctypes.data, minus.ctypes.data, score.ctypes.data, ids_part.ctypes.data, pos.size
-            if feat_idx is not None:
-                feat_idx = np.ascontiguousarray(feat_idx)
-                keep.append(feat_idx)
-                g.feat_blob, g.feat_off, g.feat_idx = blk.feat_blob.ctypes.data, blk.feat_off.ctypes.data, feat_idx.ctypes.data
-            if ot is not None:
-                ot = np.ascontiguousarray(ot)
-                keep.append(ot)
-                g.offtarget = ot.ctypes.data
-            if joined is not None:  # the segment's crp_row_extra travels with it (write_segments lays them out side by side)
-                counts, sums = np.ascontiguousarray(joined[0]), np.ascontiguousarray(joined[1])
-                keep.extend((counts, sums))
-                g.extra = nat.RowExtra(counts.ctypes.data, counts.shape[1], sums.ctypes.data)
-            if props is not None:  # (--properties: the segment's packed column, the same way)
-                props = np.ascontiguousarray(props)
-                keep.append(props)
-                g.props = props.ctypes.data
+            # where crp_row_segment and its parallel arrays take each opt-in column (crp_format.cpp's Job prints them)
+            cols = {stem: np.ascontiguousarray(col) for stem, col in cols.items() if col is not None}
+            keep.extend(cols.values())
+            if "feat" in cols:
+                g.feat_blob, g.feat_off, g.feat_idx = blk.feat_blob.ctypes.data, blk.feat_off.ctypes.data, cols["feat"].ctypes.data
+            if "ot" in cols:
+                g.offtarget = cols["ot"].ctypes.data
+            if "self_counts" in cols:  # the segment's crp_row_extra travels with it (write_segments lays them out side by side)
+                g.extra = nat.RowExtra(cols["self_counts"].ctypes.data, cols["self_counts"].shape[1], cols["self_sum"].ctypes.data)
+            if "props" in cols:  # (and the address of its packed column, the same way)
+                g.props = cols["props"].ctypes.data
             segs.append(g)
 
     def chunk_to_fd(self, fd, lo, count, ids_u8, index_range, rescore, ids_rev=None):
@@ -438,31 +389,22 @@ class NativeDataset:
 
 
 def write_segments(fd, segs, guide_len, n_threads):
-    """crp_write_segments: the rows of all `segs` (RowSegment entries, in order) appended to fd by one team of formatter
-    threads; returns the byte count.  The caller keeps the arrays the segments point into alive."""
+    """The rows of all `segs` (RowSegment entries, in order) appended to fd by one team of formatter threads; returns the byte
+    count.  One call of the widest entry point, crp_write_segments_props: with NULL for a parallel array that no segment needs
+    it is the narrower calls (include/cropsr_hip.h).  The caller keeps the arrays the segments point into alive."""
     from . import _native as nat
     if not segs:
         return 0
+    what = "crp_write_segments_props"
     arr = (nat.RowSegment * len(segs))(*segs)
     written = ctypes.c_uint64()
     extras = [getattr(g, "extra", None) for g in segs]  # (--specificity: chunk_segments hangs a RowExtra on the segment)
     props = [getattr(g, "props", None) for g in segs]  # (--properties: and the address of its packed column)
-    if any(p is not None for p in props):
-        what = "crp_write_segments_props"
-        ext = None
-        if any(e is not None for e in extras):
-            ext = (nat.RowExtra * len(segs))(*[e if e is not None else nat.RowExtra() for e in extras])
-        ptrs = (ctypes.c_void_p * len(segs))(*props)
-        st = nat.lib().crp_write_segments_props(fd, guide_len, ctypes.cast(arr, ctypes.c_void_p), None if ext is None else ctypes.cast(ext, ctypes.c_void_p),
-                                                ctypes.cast(ptrs, ctypes.c_void_p), len(segs), ctypes.byref(written), n_threads)
-    elif any(e is not None for e in extras):
-        what = "crp_write_segments_cols"
-        ext = (nat.RowExtra * len(segs))(*[e if e is not None else nat.RowExtra() for e in extras])
-        st = nat.lib().crp_write_segments_cols(fd, guide_len, ctypes.cast(arr, ctypes.c_void_p), ctypes.cast(ext, ctypes.c_void_p), len(segs),
-                                               ctypes.byref(written), n_threads)
-    else:
-        what = "crp_write_segments"
-        st = nat.lib().crp_write_segments(fd, guide_len, ctypes.cast(arr, ctypes.c_void_p), len(segs), ctypes.byref(written), n_threads)
+    ext = (nat.RowExtra * len(segs))(*[e if e is not None else nat.RowExtra() for e in extras])
+    ptrs = (ctypes.c_void_p * len(segs))(*props)
+    void = lambda a, used: ctypes.cast(a, ctypes.c_void_p) if used else None
+    st = nat.lib().crp_write_segments_props(fd, guide_len, void(arr, True), void(ext, any(e is not None for e in extras)),
+                                            void(ptrs, any(p is not None for p in props)), len(segs), ctypes.byref(written), n_threads)
     if st == nat.CRP_ERR_IO:
         err = ctypes.get_errno()
         raise OSError(err, what + ": " + os.strerror(err))
