@@ -43,6 +43,11 @@ class SelectPropertyLimits(ctypes.Structure):
                 ("max_stem", ctypes.c_uint32)]
 
 
+class SelectRepairLimits(ctypes.Structure):
+    """crp_select_repair_limits (include/cropsr_hip.h): the bounds a selection puts on the repair scores."""
+    _fields_ = [("min_mh", ctypes.c_uint32), ("min_oof_pct", ctypes.c_uint32)]
+
+
 voidpp = ctypes.POINTER(ctypes.c_void_p)
 
 # every symbol include/cropsr_hip.h declares: name -> (restype, argtypes)
@@ -184,6 +189,9 @@ SIGNATURES = {
     "crp_select_set_property_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "crp_guide_properties": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p]),
     "crp_guide_properties_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
+    "crp_repair_scores": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, u64p, u64p]),
+    "crp_repair_scores_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
+    "crp_select_set_repair_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "crp_configure": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]),
     "crp_query": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     "crp_build_id": (ctypes.c_char_p, []),

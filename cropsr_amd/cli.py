@@ -141,6 +141,19 @@ def build_parser():
                      help="with --select: only guides whose longest run of T has at most N letters (3 keeps TTTT out)")
     eng.add_argument("--select-max-stem", type=int, default=None, metavar="N",
                      help="with --select: only guides whose longest hairpin stem has at most N pairs")
+    eng.add_argument("--repair-scores", action="store_true",
+                     help="with --select: what the cut does to the gene, predicted from the letters around it (microhomology-"
+                          "mediated end joining, Bae et al. 2014) on the GPU; every row of the selection file gets two more fields, "
+                          "mh_score (microhomology score) and oof_score (the share, in percent, of the predicted deletions "
+                          "that shift the frame; -1 where there is no microhomology); one GPU")
+    eng.add_argument("--repair-flank", default=None, metavar="F",
+                     help="with --repair-scores or a repair filter: letters looked at on either side of the cut (2..32, default 30)")
+    eng.add_argument("--select-min-oof", default=None, metavar="PCT",
+                     help="with --select: only guides whose out-of-frame score is at least PCT (an integer 0..100; above 0 a guide "
+                          "without any microhomology fails)")
+    eng.add_argument("--select-min-mh", default=None, metavar="X",
+                     help="with --select: only guides whose microhomology score is at least X (a decimal with at most one "
+                          "fractional digit)")
     eng.add_argument("--bench-json", metavar="PATH", default=None,
                      help="write stage timings of this run (read, upload+scan, fetch, format+write) as one JSON object")
     return p
@@ -268,6 +281,7 @@ class EngineBackend:
         self.last_stream = None      # --bench-json: crp_scan_stream's own numbers for the last plain scan
         self.last_specificity = None  # --bench-json: the self-search handles' times of the last --specificity scan
         self.last_properties = None   # --bench-json: the property kernel's time and rows of the last scan that ran it
+        self.last_repair = None       # --bench-json: the repair kernel's time, rows and flank of the last scan that ran it
 
     def connect(self):
         """Collective over the group: create the RCCL communicator (transport "rccl")."""
@@ -340,6 +354,7 @@ class EngineBackend:
             self.last_annotate_s = genome.annotate_s
             self.last_specificity = getattr(hits.columns, "stats", None)  # (--bench-json)
             self.last_properties = genome.properties_stats
+            self.last_repair = genome.repair_stats
         finally:
             genome.close()
         return out
@@ -538,7 +553,9 @@ def select_request(args, spec, world=1):
                                    ("--select-min-specificity", "select_min_specificity", None), ("--select-cds", "select_cds", False),
                                    ("--select-only", "select_only", False), ("--select-gc-min", "select_gc_min", None),
                                    ("--select-gc-max", "select_gc_max", None), ("--select-max-run", "select_max_run", None),
-                                   ("--select-max-t-run", "select_max_t_run", None), ("--select-max-stem", "select_max_stem", None))
+                                   ("--select-max-t-run", "select_max_t_run", None), ("--select-max-stem", "select_max_stem", None),
+                                   ("--repair-scores", "repair_scores", False), ("--repair-flank", "repair_flank", None),
+                                   ("--select-min-oof", "select_min_oof", None), ("--select-min-mh", "select_min_mh", None))
              if getattr(args, k, unset) not in (unset, None)]
     K = getattr(args, "select", None)
     if K is None:
@@ -575,13 +592,39 @@ def select_request(args, spec, world=1):
                   gc_max=gc_max if getattr(args, "select_gc_max", None) is not None else None,
                   max_run=getattr(args, "select_max_run", None), max_t_run=getattr(args, "select_max_t_run", None),
                   max_stem=getattr(args, "select_max_stem", None))
+    from . import repair
+    with_scores = bool(getattr(args, "repair_scores", False))
+    flank, min_oof, min_mh = (getattr(args, k, None) for k in ("repair_flank", "select_min_oof", "select_min_mh"))
+    if flank is not None and not (with_scores or min_oof is not None or min_mh is not None):
+        refuse("--repair-flank belongs to --repair-scores, --select-min-oof or --select-min-mh")
+
+    def integer(text):
+        t = str(text).strip()
+        return int(t) if t.isascii() and t.isdigit() else None
+
+    if flank is not None:
+        if integer(flank) is None or not repair.FLANKS[0] <= integer(flank) <= repair.FLANKS[1]:
+            refuse("--repair-flank is a number of letters %d..%d, not %s" % (repair.FLANKS + (flank,)))
+        flank = integer(flank)
+    if min_oof is not None:
+        if integer(min_oof) is None or integer(min_oof) > 100:
+            refuse("--select-min-oof is a percentage, an integer 0..100, not %s" % min_oof)
+        min_oof = integer(min_oof)
+    if min_mh is not None:
+        try:
+            min_mh = repair.parse_min_mh(min_mh)
+        except ValueError as e:
+            refuse("--select-min-mh: " + str(e))
+    # (a flank makes the scan fetch the column: only where the file prints it, or where the filters ask for another flank than the default)
+    repair_args = dict(min_mh=min_mh, min_oof=min_oof,
+                       repair_flank=(repair.DEFAULT_FLANK if flank is None else flank) if with_scores else flank)
     try:
         params = select.Params(K, getattr(args, "select_min_score", None) or 0.0, getattr(args, "select_max_perfect", None),
                                getattr(args, "select_min_specificity", None), bool(getattr(args, "select_cds", False)))
     except ValueError as e:
         refuse(str(e))
     return dict(params=params, output=getattr(args, "select_output", None) or (args.o + ".selected.csv"),
-                only=bool(getattr(args, "select_only", False)), limits=limits)
+                only=bool(getattr(args, "select_only", False)), limits=dict(limits, **repair_args), repair_scores=with_scores)
 
 
 def properties_request(args, world=1):
@@ -604,11 +647,14 @@ def properties_request(args, world=1):
     return True
 
 
-def write_selection(path, selection, names, strings, all_hits, guide_len, offtarget, spec_M, annotation, properties=False):
+def write_selection(path, selection, names, strings, all_hits, guide_len, offtarget, spec_M, annotation, properties=False,
+                    repair_scores=False):
     """The selection file: a header, then per chosen row gene, rank (1-based), passing and the main table's own fields
     for that row as rows.ContigRows builds them, without crispr_id (those ids are random per run).  Genes in GFF order;
-    genes with nothing selected are left out.  Python's csv module in the main table's dialect: the file is small."""
+    genes with nothing selected are left out.  Python's csv module in the main table's dialect: the file is small.
+    repair_scores: two more fields at the end of every row, mh_score and oof_score (repair.fields) of selection.mh / .oof."""
     import csv
+    from . import repair
     sel_rows = selection.rows
     fields = [None] * sel_rows.size
     for c in np.unique(sel_rows["contig"]).tolist():
@@ -626,9 +672,11 @@ def write_selection(path, selection, names, strings, all_hits, guide_len, offtar
             fields[at] = block.row(k, "")[1:]
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
-        w.writerow(["gene", "rank", "passing"] + rows.HEADER[1:] + rows.extra_header(offtarget, spec_M, properties))
-        for r, rest in zip(sel_rows, fields):
-            w.writerow((selection.labels[int(r["gene"])], int(r["rank"]), int(selection.n_pass[int(r["gene"])])) + tuple(rest))
+        w.writerow(["gene", "rank", "passing"] + rows.HEADER[1:] + rows.extra_header(offtarget, spec_M, properties)
+                   + (repair.HEADER if repair_scores else []))
+        for at, (r, rest) in enumerate(zip(sel_rows, fields)):
+            more = repair.fields(repair.pack(selection.mh[at], selection.oof[at])) if repair_scores else ()
+            w.writerow((selection.labels[int(r["gene"])], int(r["rank"]), int(selection.n_pass[int(r["gene"])])) + tuple(rest) + tuple(more))
 
 
 class _Early:
@@ -897,7 +945,7 @@ def run(args, backend=None, out=sys.stdout, group=None):
         t_select = time.perf_counter()
         selection = all_hits.selection
         write_selection(selecting["output"], selection, names, strings, all_hits, args.l, offtarget, None if spec is None else spec["max_mm"],
-                        request.annotation if annotating else None, properties=with_properties)
+                        request.annotation if annotating else None, properties=with_properties, repair_scores=selecting["repair_scores"])
         stages["select"] = dict(selection.stats, write_s=time.perf_counter() - t_select, genes=len(selection.labels),
                                 rows_selected=int(selection.rows.size), k=selecting["params"].k)
     if not annotating:
@@ -1010,6 +1058,8 @@ def run(args, backend=None, out=sys.stdout, group=None):
         stages["scan_stream"] = backend.last_stream
     if getattr(backend, "last_properties", None):  # --properties / the --select-* property filters: the kernel's time and rows
         stages["properties"] = backend.last_properties
+    if getattr(backend, "last_repair", None):  # --repair-scores / --select-min-oof / --select-min-mh: the repair kernel's time and rows
+        stages["repair"] = backend.last_repair
     if getattr(backend, "last_specificity", None):  # --specificity: the handles' kernel times, the join's among them
         stages["specificity"] = backend.last_specificity
     if getattr(backend, "last_gather", None):  # one process over several devices (--devices): the node's gatherv, in numbers

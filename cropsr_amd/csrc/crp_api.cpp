@@ -454,6 +454,10 @@ int crp_arena_destroy(crp_arena *a)
     (void)hipFree(a->d_props[1]);
     for (hipEvent_t e : a->ev_props)
         if (e) (void)hipEventDestroy(e);
+    (void)hipFree(a->d_repair[0]);
+    (void)hipFree(a->d_repair[1]);
+    for (hipEvent_t e : a->ev_repair)
+        if (e) (void)hipEventDestroy(e);
     delete a;
     return CRP_OK;
 }
@@ -874,7 +878,7 @@ int arena_reset(crp_arena *a)
     a->used_words = 1;
     a->n_contigs = a->n_chars = 0;
     a->sealed = false;
-    a->have_hits = a->have_pre = a->have_raw = a->have_feat = a->have_props = a->have_track = false;
+    a->have_hits = a->have_pre = a->have_raw = a->have_feat = a->have_props = a->have_repair = a->have_track = false;
     a->n_hits[0] = a->n_hits[1] = 0;
     a->scan_pending = 0;
     a->ot_epoch = 0;
@@ -905,6 +909,7 @@ int scan_begin(crp_arena *a, int guide_len, int flags)
     a->have_raw = false;
     a->have_feat = false;
     a->have_props = false;
+    a->have_repair = false;
     a->scan_pending = 0;
     a->pend_guide_len = guide_len;
     a->pend_flags = flags;

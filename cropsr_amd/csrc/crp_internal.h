@@ -121,6 +121,13 @@ struct crp_arena {
     bool have_props = false;  // d_props belongs to the current tables (cleared by the next scan)
     hipEvent_t ev_props[2] = {nullptr, nullptr};
     double props_ms = 0;  // the kernel of the last crp_guide_properties (HIP events)
+    // repair outcome (crp_repair.hip): mh | oof << 32 per hit of the last crp_repair_scores
+    uint64_t *d_repair[2] = {nullptr, nullptr};  // same order as the hit tables
+    uint64_t repair_cap[2] = {0, 0};
+    bool have_repair = false;  // d_repair belongs to the current tables (cleared by the next scan)
+    hipEvent_t ev_repair[2] = {nullptr, nullptr};
+    double repair_ms = 0;  // the kernel of the last crp_repair_scores (HIP events)
+    int repair_flank = 0;  // its flank
 };
 
 #define CRP_HIP(ctx, call)                                                              \

@@ -33,6 +33,8 @@ struct crp_select {
     int k = 0;  // of the last successful run (0: none)
     bool have_prop_limits = false;
     crp_select_property_limits prop_limits = {};
+    bool have_repair_limits = false;
+    crp_select_repair_limits repair_limits = {};
     hipEvent_t ev[2] = {nullptr, nullptr};
     double stats[9] = {};
 };
@@ -140,6 +142,17 @@ int crp_select_set_property_limits(crp_select *s, const crp_select_property_limi
     return CRP_OK;
 }
 
+int crp_select_set_repair_limits(crp_select *s, const crp_select_repair_limits *limits)
+{
+    if (!s) return CRP_ERR_INVALID;
+    if (limits && limits->min_oof_pct > 100u)
+        return fail(s->arena->ctx, CRP_ERR_INVALID,
+                    "crp_select_set_repair_limits: min_oof_pct is a percentage 0..100, not " + std::to_string(limits->min_oof_pct));
+    s->have_repair_limits = limits != nullptr;
+    s->repair_limits = limits ? *limits : crp_select_repair_limits{};
+    return CRP_OK;
+}
+
 int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *self)
 {
     crp::Range roctx_range("crp: guide selection");
@@ -157,6 +170,8 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
         return fail(ctx, CRP_ERR_STATE, "crp_select_run: require_cds needs the ids of a crp_annotate_lookup on the current tables");
     if (s->have_prop_limits && !a->have_props)
         return fail(ctx, CRP_ERR_STATE, "crp_select_run: property limits need the column of a crp_guide_properties on the current tables");
+    if (s->have_repair_limits && !a->have_repair)
+        return fail(ctx, CRP_ERR_STATE, "crp_select_run: repair limits need the column of a crp_repair_scores on the current tables");
     crp::SelfJoined joined = {};
     if (self) {
         if (!crp::self_joined(self, &joined))
@@ -233,7 +248,8 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
     crp::SelectTable tab[2];
     for (int t = 0; t < 2; ++t)
         tab[t] = crp::SelectTable{a->d_pos[t], a->d_score[t], p->require_cds ? a->d_feat[t] : nullptr, self ? joined.counts[t] : nullptr,
-                                  self ? joined.sum[t] : nullptr, s->have_prop_limits ? a->d_props[t] : nullptr, (uint32_t)a->n_hits[t]};
+                                  self ? joined.sum[t] : nullptr, s->have_prop_limits ? a->d_props[t] : nullptr,
+                                  s->have_repair_limits ? reinterpret_cast<const unsigned long long *>(a->d_repair[t]) : nullptr, (uint32_t)a->n_hits[t]};
     crp::SelectPredicate pred = {};
     pred.min_score = p->min_score;
     pred.max_hit_sum = p->max_hit_sum;
@@ -247,6 +263,8 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
     pred.max_run = s->prop_limits.max_run;
     pred.max_t_run = s->prop_limits.max_t_run;
     pred.max_stem = s->prop_limits.max_stem;
+    pred.min_mh = s->repair_limits.min_mh;
+    pred.min_oof_pct = s->repair_limits.min_oof_pct;
     // the bounded-launch rule: at most 2^20 items a launch, each timed on its own
     for (uint64_t first = 0; first < items.size(); first += crp::SELECT_MAX_ITEMS) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(crp::SELECT_MAX_ITEMS, items.size() - first);
@@ -270,8 +288,8 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
     s->stats[3] = (double)items.size();
     s->stats[6] = (double)rows_covered;
     // position + score, the label-set id under require_cds, with joined columns counts[0] and hit_sum, and the packed
-    // properties under property limits
-    s->stats[7] = 12.0 + (p->require_cds ? 4.0 : 0.0) + (self ? 12.0 : 0.0) + (s->have_prop_limits ? 4.0 : 0.0);
+    // properties under property limits, and the repair scores under repair limits
+    s->stats[7] = 12.0 + (p->require_cds ? 4.0 : 0.0) + (self ? 12.0 : 0.0) + (s->have_prop_limits ? 4.0 : 0.0) + (s->have_repair_limits ? 8.0 : 0.0);
     s->stats[8] = (double)merges.size();
     s->k = k;
     return CRP_OK;

@@ -18,6 +18,7 @@ struct SelectTable {
     const uint32_t *counts;            // joined self-search counts, `stride` per row: counts[0] is read
     const unsigned long long *sum;     // joined hit_sum
     const uint32_t *props;             // packed guide properties (property limits)
+    const unsigned long long *repair;  // mh | oof << 32 of crp_repair_scores (repair limits)
     uint32_t n;
 };
 
@@ -31,6 +32,8 @@ struct SelectPredicate {
     int k;
     // with SelectTable::props: gc_min <= gc <= gc_max, run <= max_run, t_run <= max_t_run, stem <= max_stem (each one byte)
     uint32_t gc_min, gc_max, max_run, max_t_run, max_stem;
+    // with SelectTable::repair: mh >= min_mh and 100 oof >= min_oof_pct mh, and mh > 0 where min_oof_pct > 0
+    uint32_t min_mh, min_oof_pct;
 };
 
 // One wave's work: rows [first[s], first[s] + rows[s]) of strand s's table, all inside gene `gene`'s runs.  slot ==

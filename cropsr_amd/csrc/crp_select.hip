@@ -95,7 +95,11 @@ __global__ __launch_bounds__(BLOCK) void select_bounds_kernel(const uint32_t *__
     bounds[g] = make_uint4(out[0], out[1], out[2], out[3]);
 }
 
-__global__ __launch_bounds__(BLOCK) void select_items_kernel(SelectTable plus, SelectTable minus, SelectPredicate pred,
+// (8 waves per SIMD, said out loud: with the repair column's pointers and limits among its arguments the kernel would take
+// 103 SGPRs and run at 7, which cost 5-7 % on the plain selection; held to 96 the compiler keeps 24 of them in VGPR lanes --
+// 23 VGPRs, no scratch -- and the time is the one of before: profiles/EXPERIMENTS.md, "Repair outcome")
+__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) void select_items_kernel(SelectTable plus, SelectTable minus,
+                                                                                                        SelectPredicate pred,
                                                              const SelectItem *__restrict__ items, uint32_t n_items,
                                                              SelectPartials part, SelectResult res)
 {
@@ -132,6 +136,11 @@ __global__ __launch_bounds__(BLOCK) void select_items_kernel(SelectTable plus, S
                 const uint32_t gc = pr & 255u;
                 pass = pass && gc >= pred.gc_min && gc <= pred.gc_max && (pr >> 8 & 255u) <= pred.max_run && (pr >> 16 & 255u) <= pred.max_t_run &&
                        pr >> 24 <= pred.max_stem;
+            }
+            if (t.repair) {  // (the value of crp_repair_scores: mh | oof << 32, both below 2^20)
+                const unsigned long long rp = in ? t.repair[row] : 0ull;
+                const uint32_t mh = (uint32_t)rp, oof = (uint32_t)(rp >> 32);
+                pass = pass && mh >= pred.min_mh && 100u * oof >= pred.min_oof_pct * mh && (mh != 0u || pred.min_oof_pct == 0u);
             }
             n_in += (uint32_t)__popcll(__ballot(scored));
             n_pass += (uint32_t)__popcll(__ballot(pass));

@@ -191,6 +191,24 @@ class Arena:
                   self._engine._ctx)
         return dict(kernel_ms=float(out[0]), rows=int(out[1]), guide_len=int(out[2]))
 
+    # ---- repair outcome of the cut (opt-in; repair.py has the definition)
+    def repair_scores(self, n_plus, n_minus, flank=30, fetch=True):
+        """The packed repair scores (mh | oof << 32) of every kept hit of the last scan, computed on the GPU from the 2 *
+        flank letters around its cut; fetch=False leaves the column in HBM (for a selection's repair limits)."""
+        if not fetch:
+            nat.check(nat.lib().crp_repair_scores(self._h, int(flank), None, None), "crp_repair_scores", self._engine._ctx)
+            return None
+        rp, rm = np.empty(n_plus, dtype=np.uint64), np.empty(n_minus, dtype=np.uint64)
+        nat.check(nat.lib().crp_repair_scores(self._h, int(flank), rp.ctypes.data_as(nat.u64p), rm.ctypes.data_as(nat.u64p)),
+                  "crp_repair_scores", self._engine._ctx)
+        return rp, rm
+
+    def repair_scores_stats(self):
+        """dict(kernel_ms, rows, flank) of the last repair_scores() on the current tables."""
+        out = np.zeros(3, dtype=np.float64)
+        nat.check(nat.lib().crp_repair_scores_stats(self._h, out.ctypes.data_as(nat.f64p), 3), "crp_repair_scores_stats", self._engine._ctx)
+        return dict(kernel_ms=float(out[0]), rows=int(out[1]), flank=int(out[2]))
+
     # ---- off-target seed scan (opt-in; include/cropsr_hip.h)
     def offtarget_add(self, guide_len=20, own_ranges=None):
         """Add the sites of the last scan to the engine's seed histogram; own_ranges: (n, 2) arena
@@ -686,6 +704,7 @@ class Genome:
         self.groups = groups  # contig indices per arena, in arena order
         self.annotate_s = None
         self.properties_stats = None  # dict(kernel_ms, rows, wall_s) of the last guide_properties()
+        self.repair_stats = None  # dict(kernel_ms, rows, flank, wall_s) of the last repair_scores()
         self._where = {}
         for a, g in enumerate(groups):
             for j, k in enumerate(g):
@@ -717,18 +736,33 @@ class Genome:
         self.properties_stats = dict(kernel_ms=ms, rows=n_rows, wall_s=time.perf_counter() - t0)
         return out if fetch else None
 
+    def repair_scores(self, counts, flank=30, fetch=True):
+        """The repair scores over every arena's resident tables (counts: (n_plus, n_minus) per arena).  Returns
+        [(repair_plus, repair_minus)] per arena, packed (repair.unpack), or None with fetch=False (the columns stay in HBM)."""
+        import time
+        t0 = time.perf_counter()
+        out, ms, n_rows = [], 0.0, 0
+        for a, (n_plus, n_minus) in zip(self.arenas, counts):
+            out.append(a.repair_scores(n_plus, n_minus, flank, fetch=fetch))
+            st = a.repair_scores_stats()
+            ms, n_rows = ms + st["kernel_ms"], n_rows + st["rows"]
+        self.repair_stats = dict(kernel_ms=ms, rows=n_rows, flank=int(flank), wall_s=time.perf_counter() - t0)
+        return out if fetch else None
+
     def specificity_columns(self, guide_len=20, max_mm=3, candidate_pam="NRG", score="hsu2013", budget=None):
         """The genome-wide specificity of every hit of the last scan at guide_len, joined on the GPU
         (search.specificity_columns): per contig self_counts_plus / _minus (n, M + 1) and self_sum_plus / _minus."""
         from . import search
         return search.specificity_columns(self, guide_len, max_mm=max_mm, candidate_pam=candidate_pam, score=score, budget=budget)
 
-    def select(self, request, hits, counts=None, handle_of=None, joined=None, annotated=False):
+    def select(self, request, hits, counts=None, handle_of=None, joined=None, annotated=False, repair=None):
         """The best K guides of every gene (select.Request; the module's docstring has the definition) over the tables
         of the last scan at guide length 20, which `hits` (GenomeHits) holds as host copies.  Runs after the annotation
         look-up and -- with handle_of(arena index) -> the arena's joined search.ArenaSelfSearch and joined[arena index] =
         its (counts_plus, sum_plus, counts_minus, sum_minus) -- between the specificity join and the closing of its
         handles.  annotated: the arenas hold the ids of an annotation look-up on these tables (else require_cds runs one).
+        repair: per arena (repair_plus, repair_minus), the fetched columns of repair_scores(): the Selection carries mh and
+        oof of its rows.  A request with repair limits needs the columns resident (repair_scores(fetch=False) is enough).
         Returns select.Selection: for every gene of the GFF in file order its label, n_in, n_pass and the selected rows
         (contig, position, strand, score, and the joined counts and sum when present)."""
         from . import select as sel
@@ -749,12 +783,14 @@ class Genome:
                         sel=picked)
             if joined is not None:
                 part["counts_plus"], part["sum_plus"], part["counts_minus"], part["sum_minus"] = joined[a]
+            if repair is not None:
+                part["repair_plus"], part["repair_minus"] = repair[a]
             parts.append(part)
             sel.sum_stats(stats, st)
         return sel.assemble(labels, request.params.k, parts, stats)
 
     def scan_score(self, guide_len=20, want_pre=False, offtarget=False, seeds_from_scan=True, annotation=None, specificity=None,
-                   select=None, properties=False):
+                   select=None, properties=False, repair=None):
         """Seam 1 + 2 for every contig.  offtarget=True also runs the genome-wide seed scan over all
         arenas (single process: no reduce) and attaches (n, 4) counts to every contig's hits;
         seeds_from_scan=False makes the off-target step derive its seeds from the planes itself (the
@@ -766,7 +802,17 @@ class Genome:
         properties=True: hits.properties holds, per contig, the packed guide properties (props_plus, props_minus) of its rows
         (properties.unpack turns a column into gc, run, t_run, stem), and every contig's hit dict carries them.  The kernel runs
         after the scan and before the selection and the specificity join; a select.Request with property limits runs it too
-        (the column then stays on the device unless properties=True)."""
+        (the column then stays on the device unless properties=True).
+        repair=F (a flank, 2..32): hits.repair holds, per ARENA, the packed repair scores (repair_plus, repair_minus) of its
+        tables' rows (repair.unpack turns a column into mh, oof).  They are deliberately not cut into the contig hit dicts.
+        A select.Request with repair limits or a repair flank runs the kernel too, right before the selection -- after the
+        scan, or inside the specificity join's after_join hook --; with limits alone the column stays on the device."""
+        from .repair import check_flank
+        want_repair = repair is not None or (select is not None and select.runs_repair)
+        if repair is not None:
+            repair = check_flank(repair)
+            if select is not None and select.repair_flank not in (None, repair):
+                raise ValueError("repair=%d and a selection with repair_flank=%d: one flank a scan" % (repair, select.repair_flank))
         if properties and not 1 <= guide_len <= 50:
             raise ValueError("guide properties exist for guide lengths 1..50, not %d" % guide_len)
         if select is not None and guide_len != 20:
@@ -777,6 +823,15 @@ class Genome:
             if properties:
                 for h, (pp, pm) in zip(hits.per_arena, cols):
                     h.props_plus, h.props_minus = pp, pm
+
+        def run_repair():
+            fetch = repair is not None or select.repair_flank is not None
+            cols = self.repair_scores([(h.n_plus, h.n_minus) for h in hits.per_arena], repair if repair is not None else select.flank, fetch=fetch)
+            if fetch:
+                hits.repair = cols
+
+        if want_repair and select is None:
+            run_repair()
         if specificity is not None:  # (the tables of an arena stay valid until its next scan)
             if select is None:
                 hits.columns = self.specificity_columns(guide_len, **specificity)
@@ -787,11 +842,16 @@ class Genome:
                 def after_join(a, handle, cols):
                     handles[a], joined[a] = handle, cols
                     if len(handles) == len(self.arenas):  # every arena has joined, no handle has closed yet
-                        hits.selection = self.select(select, hits, handle_of=handles.get, joined=joined, annotated=annotation is not None)
+                        if want_repair:
+                            run_repair()
+                        hits.selection = self.select(select, hits, handle_of=handles.get, joined=joined, annotated=annotation is not None,
+                                                     repair=hits.repair)
 
                 hits.columns = search.specificity_columns(self, guide_len, after_join=after_join, **specificity)
         elif select is not None:
-            hits.selection = self.select(select, hits, annotated=annotation is not None)
+            if want_repair:
+                run_repair()
+            hits.selection = self.select(select, hits, annotated=annotation is not None, repair=hits.repair)
         return hits
 
     def _scan_score(self, guide_len, want_pre, offtarget, seeds_from_scan, annotation):
@@ -850,6 +910,7 @@ class GenomeHits:
         self.n_minus = sum(h.n_minus for h in per_arena)
         self.columns = None  # per contig, further columns of its rows (Genome.scan_score(specificity=..))
         self.selection = None  # select.Selection (Genome.scan_score(select=..))
+        self.repair = None  # per arena (repair_plus, repair_minus), packed (Genome.scan_score(repair=F))
 
     def contig(self, k):
         a, j = self._genome._where[k]

@@ -21,7 +21,8 @@ Definition, per arena, after a crp_scan_score at guide length 20 (tests/select_r
             is joined (counts[0] != 0xFFFFFFFF), counts[0] <= max_mm0 and hit_sum <= max_hit_sum (integer compares);
             with require_cds the flag byte of its label-set id is non-zero (NO_FEATURE fails; the flag is 1 for a
             label-set string that holds a `CDS:` label, computed on the host from the string table); and with property
-            limits (properties.py) gc_min <= gc <= gc_max, run <= max_run, t_run <= max_t_run and stem <= max_stem.
+            limits (properties.py) gc_min <= gc <= gc_max, run <= max_run, t_run <= max_t_run and stem <= max_stem; and
+            with repair limits (repair.py) mh >= min_mh and 100 oof >= min_oof mh, and mh > 0 where min_oof > 0.
   order     among passing rows: higher score first -- scores are positive finite doubles, so their bit patterns order
             as unsigned 64-bit integers --, ties (repeats give identical 30-mers) by smaller cut site, then '+' before
             '-'.  The order is total: the result does not depend on how the work was cut.
@@ -93,10 +94,19 @@ class Request:
     """A selection for a backend's scan: Params, the annotate.Request that names the genes, slice_rows (None: the
     library's default; results do not depend on it) and the limits on the guide properties (properties.py), as counts:
     gc_min <= gc <= gc_max, run <= max_run, t_run <= max_t_run, stem <= max_stem.  With any of them given a row passes
-    only if all hold, and the scan runs the property kernel before the selection."""
+    only if all hold, and the scan runs the property kernel before the selection.  Likewise the repair scores
+    (repair.py): min_mh (tenths of the microhomology score) and min_oof (an integer percentage) are limits, repair_flank
+    is the kernel's flank (None: 30).  With a limit or a flank the scan runs the repair kernel before the selection; with a
+    flank the column is also fetched and the Selection carries mh and oof of its rows."""
 
-    def __init__(self, params, annotation, slice_rows=None, gc_min=None, gc_max=None, max_run=None, max_t_run=None, max_stem=None):
+    def __init__(self, params, annotation, slice_rows=None, gc_min=None, gc_max=None, max_run=None, max_t_run=None, max_stem=None,
+                 repair_flank=None, min_mh=None, min_oof=None):
+        from . import repair
         from .properties import Limits
+        self.repair_flank = None if repair_flank is None else repair.check_flank(repair_flank)
+        self.repair_limits = repair.Limits(min_mh, min_oof) if (min_mh is not None or min_oof is not None) else None
+        self.flank = repair.DEFAULT_FLANK if self.repair_flank is None else self.repair_flank
+        self.runs_repair = self.repair_flank is not None or self.repair_limits is not None
         self.params, self.annotation, self.slice_rows = params, annotation, slice_rows
         given = [v is not None for v in (gc_min, gc_max, max_run, max_t_run, max_stem)]
         self.property_limits = Limits(gc_min, gc_max, max_run, max_t_run, max_stem) if any(given) else None
@@ -137,6 +147,11 @@ class ArenaSelect:
         lim = None if limits is None else ctypes.byref(nat.SelectPropertyLimits(*limits.astuple()))
         nat.check(nat.lib().crp_select_set_property_limits(self._h, lim), "crp_select_set_property_limits", self._ctx)
 
+    def set_repair_limits(self, limits):
+        """limits: repair.Limits, or None to clear them."""
+        lim = None if limits is None else ctypes.byref(nat.SelectRepairLimits(*limits.astuple()))
+        nat.check(nat.lib().crp_select_set_repair_limits(self._h, lim), "crp_select_set_repair_limits", self._ctx)
+
     def run(self, params, self_search=None):
         """params: Params; self_search: the search.ArenaSelfSearch of this arena after its join_hits, or None."""
         p = params.native()
@@ -174,11 +189,13 @@ class HitList(list):
 class Selection:
     """The selection over all genes of the GFF, in file order: labels, n_in, n_pass (per gene) and rows (ROW_DTYPE, gene
     after gene, rank 1 first; `index` is the row's place in its contig's strand table, `position` its match index local
-    to the contig string), with counts (n, M + 1) uint32 and hit_sum (n,) uint64 of the rows when they were joined."""
+    to the contig string), with counts (n, M + 1) uint32 and hit_sum (n,) uint64 of the rows when they were joined, and
+    mh / oof (n,) uint32 of the rows when the repair scores were fetched (None otherwise)."""
 
-    def __init__(self, labels, n_in, n_pass, rows, counts=None, hit_sum=None, stats=None):
+    def __init__(self, labels, n_in, n_pass, rows, counts=None, hit_sum=None, stats=None, mh=None, oof=None):
         self.labels, self.n_in, self.n_pass, self.rows = labels, n_in, n_pass, rows
         self.counts, self.hit_sum, self.stats = counts, hit_sum, stats or {}
+        self.mh, self.oof = mh, oof
 
     def of_gene(self, g):
         return self.rows[self.rows["gene"] == g]
@@ -195,13 +212,16 @@ def _take(plus, minus, is_minus, row, dtype):
 def assemble(labels, k, arenas, stats=None):
     """One Selection from per-arena results.  arenas: dicts with offsets / lengths (of the arena's texts), group (their
     contig indices), pos_plus / score_plus / pos_minus / score_minus (the tables, arena positions), gene (layout row ->
-    gene index), n_in, n_pass, sel (layout rows x K), and optionally counts_plus / sum_plus / counts_minus / sum_minus.
+    gene index), n_in, n_pass, sel (layout rows x K), and optionally counts_plus / sum_plus / counts_minus / sum_minus
+    and repair_plus / repair_minus (the packed repair scores of the tables' rows).
     A gene that has rows in several texts (two contigs of one name) gets the sums of its counts and the first K of its
     rows in the definition's order, texts in arena order."""
     G = len(labels)
     n_in, n_pass = np.zeros(G, np.int64), np.zeros(G, np.int64)
     parts, cparts, sparts = [], [], []
     joined = any(a.get("counts_plus") is not None for a in arenas)
+    repaired = any(a.get("repair_plus") is not None for a in arenas)
+    rparts = []
     for a in arenas:
         gene = np.asarray(a["gene"], dtype=np.int64)
         np.add.at(n_in, gene, np.asarray(a["n_in"], dtype=np.int64))
@@ -233,9 +253,12 @@ def assemble(labels, k, arenas, stats=None):
             c_rows[~minus], c_rows[minus] = cp[row[~minus]], cm[row[minus]]
             cparts.append(c_rows)
             sparts.append(_take(a["sum_plus"], a["sum_minus"], minus, row, np.uint64))
+        if repaired:
+            rparts.append(_take(a["repair_plus"], a["repair_minus"], minus, row, np.uint64))
     rows = np.concatenate(parts) if parts else np.empty(0, ROW_DTYPE)
     counts = np.concatenate(cparts) if cparts else None
     sums = np.concatenate(sparts) if sparts else None
+    packed_repair = np.concatenate(rparts) if rparts else None
     # genes in file order; a gene met in several texts: its rows in the definition's order, the first K of them
     key = rows["score"].view(np.uint64)
     order = np.lexsort((np.arange(rows.size), np.iinfo(np.uint64).max - key, rows["gene"]))
@@ -247,7 +270,11 @@ def assemble(labels, k, arenas, stats=None):
     rows["rank"] = rank[keep] + 1
     if counts is not None:
         counts, sums = counts[order][keep], sums[order][keep]
-    return Selection(list(labels), n_in, n_pass, rows, counts, sums, stats)
+    mh = oof = None
+    if packed_repair is not None:
+        from .repair import unpack
+        mh, oof = unpack(packed_repair[order][keep])
+    return Selection(list(labels), n_in, n_pass, rows, counts, sums, stats, mh, oof)
 
 
 def select_arena(genome, a, request, handle=None, flags=None):
@@ -262,6 +289,8 @@ def select_arena(genome, a, request, handle=None, flags=None):
             sel.set_limits(request.slice_rows)
         if getattr(request, "property_limits", None) is not None:
             sel.set_property_limits(request.property_limits)
+        if getattr(request, "repair_limits", None) is not None:
+            sel.set_repair_limits(request.repair_limits)
         sel.run(request.params, handle)
         n_in, n_pass, picked = sel.fetch()
         return lo, hi, gene, n_in, n_pass, picked, sel.stats()

@@ -790,6 +790,7 @@ int crp_annotation_cds_flags(const crp_annotation *an, uint8_t *flags);
  *   score >= min_score                                                          (float64)
  *   with a self-search handle: counts[0] != 0xFFFFFFFF (joined), counts[0] <= max_mm0 and hit_sum <= max_hit_sum
  *   with require_cds: the flag of its label-set id is non-zero (CRP_NO_FEATURE fails)
+ *   with property limits (crp_select_set_property_limits) and with repair limits (crp_select_set_repair_limits): those hold
  * Passing rows are ordered by higher score (as its 64 bits, unsigned), then smaller cut site, then '+' before '-': a
  * total order, so the result does not depend on how the work is cut.  Per gene: n_in (rows in it), n_pass (passing
  * rows) and sel[g * K .. g * K + K): the first min(K, n_pass) passing rows as row index | strand << 31, 0xFFFFFFFF
@@ -860,6 +861,38 @@ int crp_guide_properties(crp_arena *arena, uint32_t *props_plus, uint32_t *props
  * kernel (HIP events), out[1] rows, out[2] the guide length.  n: how many of these to write (<= 3).  With
  * crp_profile_enable(ctx, 2) the kernel is also accounted under CRP_K_PROPERTIES. */
 int crp_guide_properties_stats(const crp_arena *arena, double *out, int n);
+
+/* ---- repair outcome of the cut (opt-in, absent from the reference) ---------------------- */
+/* After crp_scan_score on `arena` (any guide length; it is not used): what microhomology-mediated end joining is
+ * predicted to leave behind at the cut of every kept hit, after Bae, Kweon, Kim and Kim 2014 -- two integers per row,
+ * each a pure function of the 2 * flank letters around the cut in the forward text.
+ *   cut      the boundary c between s[c - 1] and s[c]: c = i - 3 for a '+' row with match index i, c = j + 6 for a '-' row
+ *            with match index j -- three letters into the protospacer from the PAM on either strand.  (NOT the CSV's
+ *            `cutsite` column, which for '-' rows is the reference's end_pos - 3 = j.)
+ *   window   w[p] = s[c - flank + p], p = 0 .. 2 flank - 1.  A letter is a BASE when it is one of acgtACGT or U (case is
+ *            ignored, U is A); N, IUPAC letters, decoration, positions outside the contig string are non-bases.
+ *   n_d      for a deletion length d = 1 .. 2 flank - 1: over every maximal run, of length k >= 2, of p in
+ *            [max(0, flank - d), min(flank, 2 flank - d)) with w[p] == w[p + d], both bases: k + (its letters that are C or G)
+ *   mh       sum over d of W[d] n_d, W[d] = floor(1000 exp(-d / 20) + 1/2) (csrc/microhomology_weights.def)
+ *   oof      the same sum over the d that are no multiple of 3
+ * One uint64 per row: mh | oof << 32 (both below 2^20), table order; 0 for a window without a microhomology.  The
+ * published quantities are mh / 10 (microhomology score) and 100 oof / mh (out-of-frame score).  The column stays in HBM
+ * until the arena's next scan (crp_select_set_repair_limits reads it there) and is copied to plus / minus (n_plus /
+ * n_minus values; either may be NULL).  One kernel lane per row, one launch for both tables; empty tables are fine.
+ * CRP_ERR_INVALID with a crp_last_error text: flank outside 2 .. 32; CRP_ERR_STATE: no tables. */
+int crp_repair_scores(crp_arena *arena, int flank, uint64_t *plus, uint64_t *minus);
+/* The last crp_repair_scores of the arena (CRP_ERR_STATE without a column for the current tables): out[0] ms of its
+ * kernel (HIP events), out[1] rows, out[2] the flank.  n: how many of these to write (<= 3). */
+int crp_repair_scores_stats(const crp_arena *arena, double *out, int n);
+/* Repair limits of a selection (the column of crp_repair_scores): with limits set a row PASSES only if also
+ * mh >= min_mh (tenths of the microhomology score) and 100 oof >= min_oof_pct mh (min_oof_pct 0 .. 100, else
+ * CRP_ERR_INVALID); with min_oof_pct > 0 a row with mh = 0, which has no out-of-frame score, fails.  crp_select_run then
+ * reads 8 more bytes per row (crp_select_stats counts them) and returns CRP_ERR_STATE when the arena holds no repair
+ * column for its current tables.  NULL clears the limits. */
+typedef struct crp_select_repair_limits {
+    uint32_t min_mh, min_oof_pct;
+} crp_select_repair_limits;
+int crp_select_set_repair_limits(crp_select *select, const crp_select_repair_limits *limits);
 
 /* ---- options -------------------------------------------------------------- */
 /* CRP_OPT_TWO_PASS (value 0/1, default 0): with 0 crp_scan_score is ONE kernel launch; the
