@@ -48,6 +48,13 @@ class SelectRepairLimits(ctypes.Structure):
     _fields_ = [("min_mh", ctypes.c_uint32), ("min_oof_pct", ctypes.c_uint32)]
 
 
+class SelectPairParams(ctypes.Structure):
+    """crp_select_pair_params (include/cropsr_hip.h): KP, the distance window, the orientation mask and frameshift of one
+    crp_select_run_pairs."""
+    _fields_ = [("k", ctypes.c_int32), ("dmin", ctypes.c_uint32), ("dmax", ctypes.c_uint32), ("orientation_mask", ctypes.c_uint32),
+                ("frameshift", ctypes.c_int32)]
+
+
 voidpp = ctypes.POINTER(ctypes.c_void_p)
 
 # every symbol include/cropsr_hip.h declares: name -> (restype, argtypes)
@@ -192,6 +199,10 @@ SIGNATURES = {
     "crp_repair_scores": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, u64p, u64p]),
     "crp_repair_scores_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_select_set_repair_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "crp_select_set_pair_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64]),
+    "crp_select_run_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "crp_select_fetch_pairs": (ctypes.c_int, [ctypes.c_void_p, u32p, u64p, u32p]),
+    "crp_select_pairs_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_configure": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]),
     "crp_query": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     "crp_build_id": (ctypes.c_char_p, []),
@@ -229,6 +240,7 @@ SEARCH_SELF_MAX_MM = 4
 SEARCH_PAIR_MAX_PAM = 3
 SELF_UNJOINED_COUNT, SELF_UNJOINED_SUM = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF  # crp_search_self_join_hits: a hit without a guide site's row
 SELECT_MAX_K, SELECT_DEFAULT_SLICE_ROWS, SELECT_MIN_SLICE_ROWS, SELECT_NONE = 64, 65536, 64, 0xFFFFFFFF
+SELECT_PAIRS_MAX_K, SELECT_PAIRS_MAX_DISTANCE, SELECT_DEFAULT_PAIR_SLICE_ROWS, SELECT_MIN_PAIR_SLICE_ROWS = 64, 65535, 1024, 64
 CRP_ERR_INVALID = -1
 CRP_ERR_NO_DEVICE = -2
 CRP_ERR_UNSUPPORTED = -7

@@ -131,6 +131,21 @@ def build_parser():
                           "row's guide; appends the columns guide_gc (letters that are C or G), guide_run (longest run of one base), "
                           "guide_t_run (longest run of T in the spacer: TTTT ends Pol III transcription) and guide_stem (longest "
                           "hairpin stem with a loop of at least 3); -l 1..50, one GPU")
+    eng.add_argument("--select-pairs", type=int, default=None, metavar="KP",
+                     help="with --select: also the best KP (1..64) PAIRS of passing guides of every gene -- two guides in one array that "
+                          "cut out the piece between them, ranked by the weaker guide's on_site_score -- chosen on the GPU and written "
+                          "to their own file; the deletion length is the distance between the two cut boundaries (for a PAM-out "
+                          "nickase pair the published offset is that length - 34)")
+    eng.add_argument("--pairs-min-distance", type=int, default=None, metavar="D",
+                     help="with --select-pairs: the shortest deletion, in letters (default 50; at least 1)")
+    eng.add_argument("--pairs-max-distance", type=int, default=None, metavar="D",
+                     help="with --select-pairs: the longest deletion, in letters (default 500; at most 65535)")
+    eng.add_argument("--pairs-frameshift", action="store_true",
+                     help="with --select-pairs: only deletions whose length is no multiple of 3")
+    eng.add_argument("--pairs-orientation", default=None, metavar="WHICH",
+                     help="with --select-pairs: any (default), pam-out ('-' guide left, '+' guide right: the nickase layout) or pam-in")
+    eng.add_argument("--pairs-output", metavar="FILE", default=None,
+                     help="with --select-pairs: the pairs file, default = the -o path + .pairs.csv")
     eng.add_argument("--select-gc-min", type=int, default=None, metavar="PCT",
                      help="with --select: only guides with at least PCT %% GC (an integer 0..100; as a count: ceil(PCT * l / 100))")
     eng.add_argument("--select-gc-max", type=int, default=None, metavar="PCT",
@@ -557,8 +572,17 @@ def select_request(args, spec, world=1):
                                    ("--repair-scores", "repair_scores", False), ("--repair-flank", "repair_flank", None),
                                    ("--select-min-oof", "select_min_oof", None), ("--select-min-mh", "select_min_mh", None))
              if getattr(args, k, unset) not in (unset, None)]
+    KP = getattr(args, "select_pairs", None)
+    pair_given = [o for o, k, unset in (("--pairs-min-distance", "pairs_min_distance", None), ("--pairs-max-distance", "pairs_max_distance", None),
+                                        ("--pairs-frameshift", "pairs_frameshift", False), ("--pairs-orientation", "pairs_orientation", None),
+                                        ("--pairs-output", "pairs_output", None))
+                  if getattr(args, k, unset) not in (unset, None)]
+    if KP is None and pair_given:
+        sys.exit("cropsr_amd: --select: %s belongs to --select-pairs" % pair_given[0])
     K = getattr(args, "select", None)
     if K is None:
+        if KP is not None:
+            sys.exit("cropsr_amd: --select-pairs belongs to --select")
         if given:
             sys.exit("cropsr_amd: %s belongs to --select" % given[0])
         return None
@@ -623,8 +647,17 @@ def select_request(args, spec, world=1):
                                getattr(args, "select_min_specificity", None), bool(getattr(args, "select_cds", False)))
     except ValueError as e:
         refuse(str(e))
+    pairs = None
+    if KP is not None:
+        dmin, dmax = getattr(args, "pairs_min_distance", None), getattr(args, "pairs_max_distance", None)
+        try:
+            pairs = select.PairParams(KP, 50 if dmin is None else dmin, 500 if dmax is None else dmax,
+                                      bool(getattr(args, "pairs_frameshift", False)), getattr(args, "pairs_orientation", None) or "any")
+        except ValueError as e:
+            refuse("--select-pairs: " + str(e))
     return dict(params=params, output=getattr(args, "select_output", None) or (args.o + ".selected.csv"),
-                only=bool(getattr(args, "select_only", False)), limits=dict(limits, **repair_args), repair_scores=with_scores)
+                only=bool(getattr(args, "select_only", False)), limits=dict(limits, **repair_args), repair_scores=with_scores,
+                pairs=pairs, pairs_output=getattr(args, "pairs_output", None) or (args.o + ".pairs.csv"))
 
 
 def properties_request(args, world=1):
@@ -677,6 +710,47 @@ def write_selection(path, selection, names, strings, all_hits, guide_len, offtar
         for at, (r, rest) in enumerate(zip(sel_rows, fields)):
             more = repair.fields(repair.pack(selection.mh[at], selection.oof[at])) if repair_scores else ()
             w.writerow((selection.labels[int(r["gene"])], int(r["rank"]), int(selection.n_pass[int(r["gene"])])) + tuple(rest) + tuple(more))
+
+
+PAIR_HEADER = ["gene", "rank", "qualifying_pairs", "deletion_length", "in_frame", "chromosome"]
+PAIR_GUIDE_FIELDS = ["start_pos", "end_pos", "cutsite", "strand", "sequence", "on_site_score"]
+
+
+def write_pairs(path, selection, names, strings, all_hits, guide_len, repair_scores=False):
+    """The pairs file: a header, then per chosen pair gene, rank (1-based), qualifying_pairs (all of the gene's),
+    deletion_length, in_frame (1 when the length is a multiple of 3), chromosome and, for the left guide a and the right
+    guide b, start_pos, end_pos, cutsite, strand, sequence and on_site_score as rows.ContigRows builds those fields (so
+    `cutsite` is the main table's column; deletion_length is measured between the cut BOUNDARIES, select.py).  Genes in GFF
+    order; genes without a pair are left out.  Python's csv module in the selection file's dialect.  repair_scores: mh_score
+    and oof_score (repair.fields) of a and of b at the end of every row."""
+    import csv
+    from . import repair
+    pairs = selection.pairs
+    guides, chrom = {"a": [None] * pairs.size, "b": [None] * pairs.size}, [None] * pairs.size
+    for c in np.unique(pairs["contig"]).tolist():
+        mine = np.flatnonzero(pairs["contig"] == c)
+        # both guides of the contig's pairs as one block of rows, '+' rows first, as ContigRows holds a contig's rows
+        side = np.concatenate([np.zeros(mine.size, np.int64), np.ones(mine.size, np.int64)])
+        at = np.concatenate([mine, mine])
+        minus = np.concatenate([pairs["strand_a"][mine], pairs["strand_b"][mine]]) == b"-"
+        index = np.concatenate([pairs["index_a"][mine], pairs["index_b"][mine]])
+        order = np.concatenate([np.flatnonzero(~minus), np.flatnonzero(minus)])
+        n_plus = int((~minus).sum())
+        mini = hitcols.take(all_hits[c], index[order][:n_plus], index[order][n_plus:])
+        block = rows.ContigRows(names[c], bytes(strings[c]).decode("latin-1"), mini, guide_len)
+        for k, j in enumerate(order.tolist()):
+            r = block.row(k, "")
+            guides["ab"[side[j]]][at[j]] = (r[5], r[6], r[7], r[8], r[2], r[9])
+            chrom[at[j]] = r[4]
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(PAIR_HEADER + [n + "_a" for n in PAIR_GUIDE_FIELDS] + [n + "_b" for n in PAIR_GUIDE_FIELDS]
+                   + ([n + s for s in ("_a", "_b") for n in repair.HEADER] if repair_scores else []))
+        for at, r in enumerate(pairs):
+            D = int(r["deletion_length"])
+            more = sum((repair.fields(v) for v in selection.pairs_repair[at]), ()) if repair_scores else ()
+            w.writerow((selection.labels[int(r["gene"])], int(r["rank"]), int(selection.n_pairs[int(r["gene"])]), D, int(D % 3 == 0),
+                        chrom[at]) + guides["a"][at] + guides["b"][at] + tuple(more))
 
 
 class _Early:
@@ -907,7 +981,8 @@ def run(args, backend=None, out=sys.stdout, group=None):
             extra["specificity"] = spec
         if selecting is not None:  # (the keyword a backend only meets when selecting)
             from . import select
-            extra["select"] = select.Request(selecting["params"], request, **selecting["limits"])
+            more = dict(pairs=selecting["pairs"]) if selecting["pairs"] is not None else {}  # (likewise: only with --select-pairs)
+            extra["select"] = select.Request(selecting["params"], request, **selecting["limits"], **more)
         if with_properties:  # (likewise: only a scan that is asked for the columns meets the keyword)
             extra["properties"] = True
         from .search import SelfCapacityError
@@ -948,6 +1023,11 @@ def run(args, backend=None, out=sys.stdout, group=None):
                         request.annotation if annotating else None, properties=with_properties, repair_scores=selecting["repair_scores"])
         stages["select"] = dict(selection.stats, write_s=time.perf_counter() - t_select, genes=len(selection.labels),
                                 rows_selected=int(selection.rows.size), k=selecting["params"].k)
+        if selecting["pairs"] is not None:
+            t_pairs = time.perf_counter()
+            write_pairs(selecting["pairs_output"], selection, names, strings, all_hits, args.l, repair_scores=selecting["repair_scores"])
+            stages["pairs"] = dict(selection.pairs_stats, write_s=time.perf_counter() - t_pairs, pairs_selected=int(selection.pairs.size),
+                                   kp=selecting["pairs"].k)
     if not annotating:
         request = None  # (from here on the request means the `features` column)
     if request is not None:

@@ -37,6 +37,22 @@ struct crp_select {
     crp_select_repair_limits repair_limits = {};
     hipEvent_t ev[2] = {nullptr, nullptr};
     double stats[9] = {};
+    // guide pairs: buffers and results of crp_select_run_pairs, apart from the selection's
+    uint64_t pair_slice_rows = CRP_SELECT_DEFAULT_PAIR_SLICE_ROWS;
+    unsigned long long *d_pass_key[2] = {nullptr, nullptr};
+    uint64_t pass_key_cap[2] = {0, 0};
+    crp::PairItem *d_pair_items = nullptr;
+    uint64_t pair_items_cap = 0;
+    crp::SelectMerge *d_pair_merge = nullptr;
+    uint64_t pair_merge_cap = 0;
+    unsigned long long *d_pair_evals = nullptr;
+    uint64_t pair_evals_cap = 0;
+    crp::PairPartials pair_part = {};
+    uint64_t pair_part_cap[7] = {};
+    crp::PairResult pair_res = {};  // n_pass, n_pairs: n_genes; pairs: n_genes * kp * 2 of the last run
+    uint64_t pair_res_cap[3] = {};
+    int kp = 0;  // of the last successful crp_select_run_pairs (0: none)
+    double pair_stats[8] = {};
 };
 
 namespace {
@@ -51,6 +67,63 @@ int fail(crp_ctx *ctx, int rc, const std::string &text)
 {
     ctx->last_error = text;
     return rc;
+}
+
+}  // namespace
+
+namespace {
+
+// What crp_select_run and crp_select_run_pairs ask of their arguments and of the arena (`who`: the caller's name).
+int check_run(crp_select *s, const crp_select_params *p, crp_search_self *self, crp::SelfJoined *joined, const char *who_c)
+{
+    crp_ctx *ctx = s->ctx;
+    crp_arena *a = s->arena;
+    const std::string who = who_c;
+    if (std::isnan(p->min_score)) return fail(ctx, CRP_ERR_INVALID, who + ": min_score is not a number");
+    if (!a->have_hits || a->pend_guide_len != 20)
+        return fail(ctx, CRP_ERR_STATE, who + ": the arena has no hit tables of guide length 20 (the ranking key exists only there)");
+    if (p->require_cds && !s->have_flags) return fail(ctx, CRP_ERR_STATE, who + ": require_cds needs crp_select_set_flags");
+    if (p->require_cds && !a->have_feat)
+        return fail(ctx, CRP_ERR_STATE, who + ": require_cds needs the ids of a crp_annotate_lookup on the current tables");
+    if (s->have_prop_limits && !a->have_props)
+        return fail(ctx, CRP_ERR_STATE, who + ": property limits need the column of a crp_guide_properties on the current tables");
+    if (s->have_repair_limits && !a->have_repair)
+        return fail(ctx, CRP_ERR_STATE, who + ": repair limits need the column of a crp_repair_scores on the current tables");
+    if (self) {
+        if (!crp::self_joined(self, joined))
+            return fail(ctx, CRP_ERR_STATE, who + ": the self-search handle has no joined columns (crp_search_self_join_hits)");
+        if (joined->arena != a) return fail(ctx, CRP_ERR_INVALID, who + ": the self-search handle belongs to another arena");
+        if (joined->rows[0] != a->n_hits[0] || joined->rows[1] != a->n_hits[1])
+            return fail(ctx, CRP_ERR_STATE, who + ": the joined columns belong to an earlier scan's tables");
+    }
+    return CRP_OK;
+}
+
+// The two tables and the predicate of a run, as the kernels take them (k: the selection's K; the pair kernels do not read it).
+void fill_predicate(const crp_select *s, const crp_select_params *p, bool with_self, const crp::SelfJoined &joined, int k,
+                    crp::SelectTable tab[2], crp::SelectPredicate *pred_out)
+{
+    const crp_arena *a = s->arena;
+    for (int t = 0; t < 2; ++t)
+        tab[t] = crp::SelectTable{a->d_pos[t], a->d_score[t], p->require_cds ? a->d_feat[t] : nullptr, with_self ? joined.counts[t] : nullptr,
+                                  with_self ? joined.sum[t] : nullptr, s->have_prop_limits ? a->d_props[t] : nullptr,
+                                  s->have_repair_limits ? reinterpret_cast<const unsigned long long *>(a->d_repair[t]) : nullptr, (uint32_t)a->n_hits[t]};
+    crp::SelectPredicate pred = {};
+    pred.min_score = p->min_score;
+    pred.max_hit_sum = p->max_hit_sum;
+    pred.max_mm0 = p->max_mm0;
+    pred.stride = with_self ? (uint32_t)joined.stride : 0u;
+    pred.flags = p->require_cds ? s->d_flags : nullptr;
+    pred.n_flags = (uint32_t)s->n_flags;
+    pred.k = k;
+    pred.gc_min = s->prop_limits.gc_min;
+    pred.gc_max = s->prop_limits.gc_max;
+    pred.max_run = s->prop_limits.max_run;
+    pred.max_t_run = s->prop_limits.max_t_run;
+    pred.max_stem = s->prop_limits.max_stem;
+    pred.min_mh = s->repair_limits.min_mh;
+    pred.min_oof_pct = s->repair_limits.min_oof_pct;
+    *pred_out = pred;
 }
 
 }  // namespace
@@ -103,7 +176,9 @@ int crp_select_destroy(crp_select *s)
     (void)hipSetDevice(s->ctx->device);
     (void)hipStreamSynchronize(s->ctx->stream);
     void *bufs[] = {s->d_lo, s->d_hi, s->d_bounds, s->d_flags, s->d_items, s->d_merge, s->part.key, s->part.tie,
-                    s->part.row, s->part.cnt, s->res.n_in, s->res.n_pass, s->res.sel};
+                    s->part.row, s->part.cnt, s->res.n_in, s->res.n_pass, s->res.sel, s->d_pass_key[0], s->d_pass_key[1], s->d_pair_items,
+                    s->d_pair_merge, s->d_pair_evals, s->pair_part.kmin, s->pair_part.kmax, s->pair_part.tie, s->pair_part.a, s->pair_part.b,
+                    s->pair_part.n_pass, s->pair_part.n_pairs, s->pair_res.n_pass, s->pair_res.n_pairs, s->pair_res.pairs};
     for (void *p : bufs) (void)hipFree(p);
     for (hipEvent_t e : s->ev)
         if (e) (void)hipEventDestroy(e);
@@ -162,28 +237,13 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
     s->k = 0;
     if (p->k < 1 || p->k > CRP_SELECT_MAX_K)
         return fail(ctx, CRP_ERR_INVALID, "crp_select_run: k must be 1.." + std::to_string(CRP_SELECT_MAX_K) + ", not " + std::to_string(p->k));
-    if (std::isnan(p->min_score)) return fail(ctx, CRP_ERR_INVALID, "crp_select_run: min_score is not a number");
-    if (!a->have_hits || a->pend_guide_len != 20)
-        return fail(ctx, CRP_ERR_STATE, "crp_select_run: the arena has no hit tables of guide length 20 (the ranking key exists only there)");
-    if (p->require_cds && !s->have_flags) return fail(ctx, CRP_ERR_STATE, "crp_select_run: require_cds needs crp_select_set_flags");
-    if (p->require_cds && !a->have_feat)
-        return fail(ctx, CRP_ERR_STATE, "crp_select_run: require_cds needs the ids of a crp_annotate_lookup on the current tables");
-    if (s->have_prop_limits && !a->have_props)
-        return fail(ctx, CRP_ERR_STATE, "crp_select_run: property limits need the column of a crp_guide_properties on the current tables");
-    if (s->have_repair_limits && !a->have_repair)
-        return fail(ctx, CRP_ERR_STATE, "crp_select_run: repair limits need the column of a crp_repair_scores on the current tables");
     crp::SelfJoined joined = {};
-    if (self) {
-        if (!crp::self_joined(self, &joined))
-            return fail(ctx, CRP_ERR_STATE, "crp_select_run: the self-search handle has no joined columns (crp_search_self_join_hits)");
-        if (joined.arena != a) return fail(ctx, CRP_ERR_INVALID, "crp_select_run: the self-search handle belongs to another arena");
-        if (joined.rows[0] != a->n_hits[0] || joined.rows[1] != a->n_hits[1])
-            return fail(ctx, CRP_ERR_STATE, "crp_select_run: the joined columns belong to an earlier scan's tables");
-    }
+    int rc = check_run(s, p, self, &joined, "crp_select_run");
+    if (rc != CRP_OK) return rc;
     CRP_HIP(ctx, hipSetDevice(ctx->device));
     const int k = p->k;
     const uint64_t G = s->n_genes;
-    int rc = crp::grow(ctx, reinterpret_cast<void **>(&s->res.sel), &s->sel_cap, G * k, sizeof(uint32_t));
+    rc = crp::grow(ctx, reinterpret_cast<void **>(&s->res.sel), &s->sel_cap, G * k, sizeof(uint32_t));
     if (rc != CRP_OK) return rc;
     for (double &v : s->stats) v = 0;
     if (!G) {
@@ -246,25 +306,8 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
     if (rc == CRP_OK && !merges.empty()) rc = crp::staged_h2d(ctx, s->d_merge, merges.data(), merges.size() * sizeof(crp::SelectMerge));
     if (rc != CRP_OK) return rc;
     crp::SelectTable tab[2];
-    for (int t = 0; t < 2; ++t)
-        tab[t] = crp::SelectTable{a->d_pos[t], a->d_score[t], p->require_cds ? a->d_feat[t] : nullptr, self ? joined.counts[t] : nullptr,
-                                  self ? joined.sum[t] : nullptr, s->have_prop_limits ? a->d_props[t] : nullptr,
-                                  s->have_repair_limits ? reinterpret_cast<const unsigned long long *>(a->d_repair[t]) : nullptr, (uint32_t)a->n_hits[t]};
-    crp::SelectPredicate pred = {};
-    pred.min_score = p->min_score;
-    pred.max_hit_sum = p->max_hit_sum;
-    pred.max_mm0 = p->max_mm0;
-    pred.stride = self ? (uint32_t)joined.stride : 0u;
-    pred.flags = p->require_cds ? s->d_flags : nullptr;
-    pred.n_flags = (uint32_t)s->n_flags;
-    pred.k = k;
-    pred.gc_min = s->prop_limits.gc_min;
-    pred.gc_max = s->prop_limits.gc_max;
-    pred.max_run = s->prop_limits.max_run;
-    pred.max_t_run = s->prop_limits.max_t_run;
-    pred.max_stem = s->prop_limits.max_stem;
-    pred.min_mh = s->repair_limits.min_mh;
-    pred.min_oof_pct = s->repair_limits.min_oof_pct;
+    crp::SelectPredicate pred;
+    fill_predicate(s, p, self != nullptr, joined, k, tab, &pred);
     // the bounded-launch rule: at most 2^20 items a launch, each timed on its own
     for (uint64_t first = 0; first < items.size(); first += crp::SELECT_MAX_ITEMS) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(crp::SELECT_MAX_ITEMS, items.size() - first);
@@ -315,6 +358,181 @@ int crp_select_stats(const crp_select *s, double *out, int n)
 {
     if (!s || (n && !out) || n < 0 || n > 9) return CRP_ERR_INVALID;
     for (int k = 0; k < n; ++k) out[k] = s->stats[k];
+    return CRP_OK;
+}
+
+/* ---- guide pairs ---- */
+
+int crp_select_set_pair_limits(crp_select *s, uint64_t pair_slice_rows)
+{
+    if (!s) return CRP_ERR_INVALID;
+    if (pair_slice_rows && (pair_slice_rows < CRP_SELECT_MIN_PAIR_SLICE_ROWS || pair_slice_rows > 0x40000000ull)) return CRP_ERR_INVALID;
+    s->pair_slice_rows = pair_slice_rows ? pair_slice_rows : CRP_SELECT_DEFAULT_PAIR_SLICE_ROWS;
+    return CRP_OK;
+}
+
+int crp_select_run_pairs(crp_select *s, const crp_select_params *p, const crp_select_pair_params *q, crp_search_self *self)
+{
+    crp::Range roctx_range("crp: guide pairs");
+    if (!s || !p || !q) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    crp_arena *a = s->arena;
+    s->kp = 0;
+    const std::string who = "crp_select_run_pairs";
+    if (q->k < 1 || q->k > CRP_SELECT_PAIRS_MAX_K)
+        return fail(ctx, CRP_ERR_INVALID, who + ": k must be 1.." + std::to_string(CRP_SELECT_PAIRS_MAX_K) + ", not " + std::to_string(q->k));
+    if (q->dmin < 1 || q->dmin > q->dmax || q->dmax > CRP_SELECT_PAIRS_MAX_DISTANCE)
+        return fail(ctx, CRP_ERR_INVALID, who + ": the distances must be 1 <= dmin <= dmax <= " + std::to_string(CRP_SELECT_PAIRS_MAX_DISTANCE) +
+                                              ", not " + std::to_string(q->dmin) + " and " + std::to_string(q->dmax));
+    if (q->orientation_mask < 1 || q->orientation_mask > 0xFu)
+        return fail(ctx, CRP_ERR_INVALID, who + ": the orientation mask must be 1..15, not " + std::to_string(q->orientation_mask));
+    crp::SelfJoined joined = {};
+    int rc = check_run(s, p, self, &joined, who.c_str());
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    const int k = q->k;
+    const uint64_t G = s->n_genes;
+    rc = crp::grow(ctx, reinterpret_cast<void **>(&s->pair_res.n_pass), &s->pair_res_cap[0], G, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->pair_res.n_pairs), &s->pair_res_cap[1], G, sizeof(uint64_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->pair_res.pairs), &s->pair_res_cap[2], G * k * 2, sizeof(uint32_t));
+    if (rc != CRP_OK) return rc;
+    for (double &v : s->pair_stats) v = 0;
+    if (!G) {
+        s->kp = k;
+        return CRP_OK;
+    }
+    // (a table has fewer rows than the arena positions: below 2^31)
+    const uint32_t n_plus = (uint32_t)a->n_hits[0], n_minus = (uint32_t)a->n_hits[1];
+    crp::SelectTable tab[2];
+    crp::SelectPredicate pred;
+    fill_predicate(s, p, self != nullptr, joined, 0, tab, &pred);
+    // the pass key of every row, once: the predicate apart from "in the gene" does not depend on the gene
+    for (int t = 0; t < 2; ++t) {
+        rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_pass_key[t]), &s->pass_key_cap[t], a->n_hits[t], sizeof(uint64_t));
+        if (rc != CRP_OK) return rc;
+    }
+    CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    for (int t = 0; t < 2; ++t) CRP_HIP(ctx, crp::launch_pair_pass_key(ctx->stream, tab[t], pred, s->d_pass_key[t]));
+    CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+    CRP_HIP(ctx, crp::launch_select_bounds(ctx->stream, a->d_pos[0], n_plus, a->d_pos[1], n_minus, s->d_lo, s->d_hi, (uint32_t)G, s->d_bounds));
+    std::vector<uint4> bounds;
+    std::vector<crp::PairItem> items;
+    std::vector<crp::SelectMerge> merges;
+    std::vector<unsigned long long> host64;
+    uint64_t n_slots = 0;
+    try {
+        bounds.resize(G);
+        rc = crp::staged_d2h(ctx, bounds.data(), s->d_bounds, G * sizeof(uint4));
+        if (rc != CRP_OK) return rc;
+        CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        s->pair_stats[0] = elapsed(s->ev[0], s->ev[1]);
+        // every gene's a-rows -- its '+' run, then its '-' run -- in pieces of at most pair_slice_rows rows; every piece
+        // carries the gene's whole runs, where its partners are; a gene without rows still gets one (empty) item, which
+        // writes its zeros
+        items.reserve(G + G / 8);
+        for (uint64_t g = 0; g < G; ++g) {
+            const uint4 b = bounds[g];
+            if (b.x > b.y || b.y > n_plus || b.z > b.w || b.w > n_minus)
+                return fail(ctx, CRP_ERR_HIP, who + ": the bounds of gene " + std::to_string(g) + " lie outside the tables");
+            const uint64_t np = b.y - b.x, nm = b.w - b.z, total = np + nm;
+            const uint64_t pieces = std::max<uint64_t>(1, (total + s->pair_slice_rows - 1) / s->pair_slice_rows);
+            if (n_slots + pieces > 0xfffffff0ull || items.size() + pieces > 0xfffffff0ull)
+                return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": more than 2^32 work items or slots (raise pair_slice_rows)");
+            if (pieces > 1) merges.push_back(crp::SelectMerge{(uint32_t)g, (uint32_t)n_slots, (uint32_t)pieces});
+            for (uint64_t c = 0; c < pieces; ++c) {
+                // rows [r0, r1) of the gene's concatenated runs
+                const uint64_t r0 = c * s->pair_slice_rows, r1 = std::min(total, r0 + s->pair_slice_rows);
+                const uint64_t p0 = std::min(r0, np), p1 = std::min(r1, np);
+                const uint64_t m0 = std::max(r0, np) - np, m1 = std::max(r1, np) - np;
+                crp::PairItem it;
+                it.gene = (uint32_t)g;
+                it.slot = pieces > 1 ? (uint32_t)(n_slots + c) : crp::SELECT_NONE;
+                it.first[0] = b.x + (uint32_t)p0;
+                it.rows[0] = (uint32_t)(p1 - p0);
+                it.first[1] = b.z + (uint32_t)m0;
+                it.rows[1] = (uint32_t)(m1 - m0);
+                it.run[0] = b.x;
+                it.run[1] = b.y;
+                it.run[2] = b.z;
+                it.run[3] = b.w;
+                items.push_back(it);
+            }
+            if (pieces > 1) n_slots += pieces;
+        }
+        host64.resize(std::max<uint64_t>(items.size(), G));
+    } catch (const std::bad_alloc &) {
+        return CRP_ERR_NOMEM;
+    }
+    crp::PairPartials &part = s->pair_part;
+    rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_pair_items), &s->pair_items_cap, items.size(), sizeof(crp::PairItem));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_pair_merge), &s->pair_merge_cap, merges.size(), sizeof(crp::SelectMerge));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_pair_evals), &s->pair_evals_cap, items.size(), sizeof(uint64_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&part.kmin), &s->pair_part_cap[0], n_slots * k, sizeof(uint64_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&part.kmax), &s->pair_part_cap[1], n_slots * k, sizeof(uint64_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&part.tie), &s->pair_part_cap[2], n_slots * k, sizeof(uint64_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&part.a), &s->pair_part_cap[3], n_slots * k, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&part.b), &s->pair_part_cap[4], n_slots * k, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&part.n_pass), &s->pair_part_cap[5], n_slots, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&part.n_pairs), &s->pair_part_cap[6], n_slots, sizeof(uint64_t));
+    if (rc == CRP_OK) rc = crp::staged_h2d(ctx, s->d_pair_items, items.data(), items.size() * sizeof(crp::PairItem));
+    if (rc == CRP_OK && !merges.empty()) rc = crp::staged_h2d(ctx, s->d_pair_merge, merges.data(), merges.size() * sizeof(crp::SelectMerge));
+    if (rc != CRP_OK) return rc;
+    const crp::PairParams pp = {k, q->dmin, q->dmax, q->orientation_mask, q->frameshift ? 1u : 0u};
+    // the bounded-launch rule: at most 2^20 items a launch, each timed on its own
+    for (uint64_t first = 0; first < items.size(); first += crp::SELECT_MAX_ITEMS) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(crp::SELECT_MAX_ITEMS, items.size() - first);
+        CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+        CRP_HIP(ctx, crp::launch_pair_items(ctx->stream, a->d_pos[0], a->d_pos[1], s->d_pass_key[0], s->d_pass_key[1], pp, s->d_pair_items + first,
+                                            n, s->d_pair_evals + first, part, s->pair_res));
+        CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+        CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        const double ms = elapsed(s->ev[0], s->ev[1]);
+        s->pair_stats[1] += ms;
+        s->pair_stats[4] += 1;
+        s->pair_stats[5] = std::max(s->pair_stats[5], ms);
+    }
+    for (uint64_t first = 0; first < merges.size(); first += crp::SELECT_MAX_ITEMS) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(crp::SELECT_MAX_ITEMS, merges.size() - first);
+        CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+        CRP_HIP(ctx, crp::launch_pair_merge(ctx->stream, s->d_pair_merge + first, n, k, part, s->pair_res));
+        CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+        CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        s->pair_stats[2] += elapsed(s->ev[0], s->ev[1]);
+    }
+    s->pair_stats[3] = (double)items.size();
+    // the two totals: partner rows streamed (per item) and qualifying pairs (per gene), summed here
+    rc = crp::staged_d2h(ctx, host64.data(), s->d_pair_evals, items.size() * sizeof(uint64_t));
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint64_t i = 0; i < items.size(); ++i) s->pair_stats[6] += (double)host64[i];
+    rc = crp::staged_d2h(ctx, host64.data(), s->pair_res.n_pairs, G * sizeof(uint64_t));
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint64_t g = 0; g < G; ++g) s->pair_stats[7] += (double)host64[g];
+    s->kp = k;
+    return CRP_OK;
+}
+
+int crp_select_fetch_pairs(crp_select *s, uint32_t *n_pass, uint64_t *n_pairs, uint32_t *pairs)
+{
+    if (!s) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    if (!s->kp) return fail(ctx, CRP_ERR_STATE, "crp_select_fetch_pairs: no crp_select_run_pairs has succeeded on this handle");
+    if (!s->n_genes) return CRP_OK;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = CRP_OK;
+    if (n_pass) rc = crp::staged_d2h(ctx, n_pass, s->pair_res.n_pass, s->n_genes * sizeof(uint32_t));
+    if (rc == CRP_OK && n_pairs) rc = crp::staged_d2h(ctx, n_pairs, s->pair_res.n_pairs, s->n_genes * sizeof(uint64_t));
+    if (rc == CRP_OK && pairs) rc = crp::staged_d2h(ctx, pairs, s->pair_res.pairs, s->n_genes * s->kp * 2 * sizeof(uint32_t));
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CRP_OK;
+}
+
+int crp_select_pairs_stats(const crp_select *s, double *out, int n)
+{
+    if (!s || (n && !out) || n < 0 || n > 8) return CRP_ERR_INVALID;
+    for (int k = 0; k < n; ++k) out[k] = s->pair_stats[k];
     return CRP_OK;
 }
 

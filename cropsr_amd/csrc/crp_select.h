@@ -67,4 +67,43 @@ hipError_t launch_select_items(hipStream_t s, const SelectTable &plus, const Sel
 hipError_t launch_select_merge(hipStream_t s, const SelectMerge *genes, uint32_t n_genes, int k, const SelectPartials &part,
                                const SelectResult &res);
 
+// ---- guide pairs (crp_select_pairs.hip): the best KP deletion pairs of every gene ----------------
+struct PairParams {
+    int k;                   // KP
+    uint32_t dmin, dmax;     // 1 <= dmin <= dmax <= 65 535
+    uint32_t mask;           // orientation bits, bit sa * 2 + sb
+    uint32_t frameshift;     // 1: D mod 3 != 0
+};
+
+// One wave's work: the a-rows [first[s], first[s] + rows[s]) of strand s's table, inside gene `gene`'s runs
+// run[0] .. run[1] ('+') and run[2] .. run[3] ('-'), where its partners are looked for.  slot as SelectItem's.
+struct PairItem {
+    uint32_t gene, slot;
+    uint32_t first[2], rows[2];
+    uint32_t run[4];
+};
+
+// The partial lists: k entries per slot -- kmin / kmax (the smaller and the larger score's bits), tie = c_a << 32 | c_b,
+// a / b (row | strand << 31; a SELECT_NONE: no entry) -- and per slot the passing a-rows and the qualifying pairs.
+struct PairPartials {
+    unsigned long long *kmin, *kmax, *tie;
+    uint32_t *a, *b, *n_pass;
+    unsigned long long *n_pairs;
+};
+
+struct PairResult {
+    uint32_t *n_pass;             // per gene
+    unsigned long long *n_pairs;  // per gene
+    uint32_t *pairs;              // per gene k * 2: a then b
+};
+
+// key[row] = the score's bits where the row passes the predicate, else 0 (one lane per row)
+hipError_t launch_pair_pass_key(hipStream_t s, const SelectTable &table, const SelectPredicate &pred, unsigned long long *key);
+// evals[item] = partner rows the item streamed
+hipError_t launch_pair_items(hipStream_t s, const uint32_t *pos_plus, const uint32_t *pos_minus, const unsigned long long *key_plus,
+                             const unsigned long long *key_minus, const PairParams &pp, const PairItem *items, uint32_t n_items,
+                             unsigned long long *evals, const PairPartials &part, const PairResult &res);
+hipError_t launch_pair_merge(hipStream_t s, const SelectMerge *genes, uint32_t n_genes, int k, const PairPartials &part,
+                             const PairResult &res);
+
 }  // namespace crp

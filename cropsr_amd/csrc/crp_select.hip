@@ -121,27 +121,7 @@ __global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8))) v
             const double score = in ? t.score[row] : -1.0;
             const uint32_t cut = in ? t.pos[row] - back : 0u;
             const bool scored = in && score != -1.0;  // an unscored row has no cut site: in no gene
-            bool pass = scored && score >= pred.min_score;
-            if (pred.stride) {
-                const uint32_t c0 = in ? t.counts[(uint64_t)row * pred.stride] : SELECT_NONE;
-                const unsigned long long sum = in ? t.sum[row] : ~0ull;
-                pass = pass && c0 != SELECT_NONE && c0 <= pred.max_mm0 && sum <= pred.max_hit_sum;
-            }
-            if (pred.flags) {
-                const uint32_t id = in ? t.feat[row] : SELECT_NONE;
-                pass = pass && id < pred.n_flags && pred.flags[id] != 0;
-            }
-            if (t.props) {  // (the packed word of crp_guide_properties: gc | run << 8 | t_run << 16 | stem << 24)
-                const uint32_t pr = in ? t.props[row] : 0u;
-                const uint32_t gc = pr & 255u;
-                pass = pass && gc >= pred.gc_min && gc <= pred.gc_max && (pr >> 8 & 255u) <= pred.max_run && (pr >> 16 & 255u) <= pred.max_t_run &&
-                       pr >> 24 <= pred.max_stem;
-            }
-            if (t.repair) {  // (the value of crp_repair_scores: mh | oof << 32, both below 2^20)
-                const unsigned long long rp = in ? t.repair[row] : 0ull;
-                const uint32_t mh = (uint32_t)rp, oof = (uint32_t)(rp >> 32);
-                pass = pass && mh >= pred.min_mh && 100u * oof >= pred.min_oof_pct * mh && (mh != 0u || pred.min_oof_pct == 0u);
-            }
+#include "crp_select_predicate.inc"
             n_in += (uint32_t)__popcll(__ballot(scored));
             n_pass += (uint32_t)__popcll(__ballot(pass));
             sel_insert(mine, lane, k, pass, (unsigned long long)__double_as_longlong(score), cut << 1 | (uint32_t)s,

@@ -764,7 +764,8 @@ class Genome:
         repair: per arena (repair_plus, repair_minus), the fetched columns of repair_scores(): the Selection carries mh and
         oof of its rows.  A request with repair limits needs the columns resident (repair_scores(fetch=False) is enough).
         Returns select.Selection: for every gene of the GFF in file order its label, n_in, n_pass and the selected rows
-        (contig, position, strand, score, and the joined counts and sum when present)."""
+        (contig, position, strand, score, and the joined counts and sum when present); with request.pairs also the best pairs
+        of every gene (Selection.pairs, n_pairs), selected right after the single guides while the same columns are resident."""
         from . import select as sel
         if request.params.needs_specificity and handle_of is None:
             raise ValueError("max_perfect / min_specificity need the specificity join (scan_score(specificity=...))")
@@ -774,10 +775,10 @@ class Genome:
             self.annotate(request.annotation, [(h.n_plus, h.n_minus) for h in hits.per_arena], fetch=False)
             self.annotate_s = keep
         flags = request.annotation.annotation.cds_flags() if request.params.require_cds else None
-        parts, stats = [], {}
+        parts, stats, pair_stats = [], {}, {}
         for a, h in enumerate(hits.per_arena):
             handle = handle_of(a) if handle_of is not None else None
-            lo, hi, gene, n_in, n_pass, picked, st = sel.select_arena(self, a, request, handle, flags)
+            lo, hi, gene, n_in, n_pass, picked, st, *paired = sel.select_arena(self, a, request, handle, flags)
             part = dict(offsets=self.arenas[a].offsets, lengths=self.arenas[a].lengths, group=self.groups[a], pos_plus=h.pos_plus,
                         score_plus=h.score_plus, pos_minus=h.pos_minus, score_minus=h.score_minus, gene=gene, n_in=n_in, n_pass=n_pass,
                         sel=picked)
@@ -785,9 +786,16 @@ class Genome:
                 part["counts_plus"], part["sum_plus"], part["counts_minus"], part["sum_minus"] = joined[a]
             if repair is not None:
                 part["repair_plus"], part["repair_minus"] = repair[a]
+            if paired:
+                _, part["pair_n_pairs"], part["pair_list"], pst = paired[0]
+                sel.sum_stats(pair_stats, pst)
             parts.append(part)
             sel.sum_stats(stats, st)
-        return sel.assemble(labels, request.params.k, parts, stats)
+        out = sel.assemble(labels, request.params.k, parts, stats)
+        if request.pairs is not None:
+            out.pairs, out.n_pairs, out.pairs_repair = sel.assemble_pairs(len(labels), request.pairs.k, parts)
+            out.pairs_stats = pair_stats
+        return out
 
     def scan_score(self, guide_len=20, want_pre=False, offtarget=False, seeds_from_scan=True, annotation=None, specificity=None,
                    select=None, properties=False, repair=None):

@@ -29,6 +29,27 @@ Definition, per arena, after a crp_scan_score at guide length 20 (tests/select_r
   result    per gene g, all exact: n_in[g] (rows in the gene), n_pass[g] (passing rows) and sel[g][0..K): the first
             min(K, n_pass) passing rows in that order, each as row index | strand << 31, 0xFFFFFFFF beyond.  K = 1..64.
 
+Guide pairs (csrc/crp_select_pairs.hip; tests/select_pairs_reference.py restates it twice): two
+guides in one array that cut out the piece between them.  Per arena, after a scan at guide length 20, for the genes of
+the same handle:
+
+  eligible  the rows that PASS for gene g, as above: membership by the cut site, i - 3 or j, in [lo, hi]; the predicate is
+            the full current one (min_score, joined columns, require_cds, property limits, repair limits).
+  boundary  c of a row, as repair.py defines it and NOT the CSV's `cutsite`: c = i - 3 for a '+' row, c = j + 6 for a '-' row.
+  pair      (a, b): two eligible rows of the same gene in the same arena text with c_a < c_b.  D = c_b - c_a is the
+            deletion's length: the letters s[c_a : c_b) go.
+  qualifies when dmin <= D <= dmax (1 <= dmin <= dmax <= 65 535); with frameshift, D mod 3 != 0; and the bit sa * 2 + sb
+            (0 for '+', 1 for '-') of a 4-bit orientation mask is set: "any" = 0xF, "pam-out" = '-' left and '+' right =
+            bit 2 only, "pam-in" = bit 1 only.  For a PAM-out pair at guide length 20 the published nickase offset -- the
+            distance between the two protospacers' PAM-distal ends -- is D - 34; the conversion is the user's, nothing
+            here applies it.
+  order     among qualifying pairs: higher min(score_a, score_b), compared as the doubles' bit patterns (unsigned 64-bit);
+            then higher max(score_a, score_b); then smaller c_a; then smaller c_b; then smaller strand bits sa * 2 + sb.
+            The order is total: the result does not depend on how the work was cut.
+  result    per gene g: n_pass[g] (uint32, as above), n_pairs[g] (uint64, all qualifying pairs) and pairs[g][0..KP): each
+            pair two uint32 in the packing of sel (row | strand << 31), a then b, 0xFFFFFFFF beyond.  KP = 1..64,
+            independent of K.  The top pairs may share one very good guide.
+
 This module lays the genes out per arena, converts a wanted specificity into the integer bound the kernel compares,
 drives crp_select_* and turns the per-arena results into one table over the genes of the GFF.
 """
@@ -42,6 +63,11 @@ MAX_K = nat.SELECT_MAX_K
 NONE = nat.SELECT_NONE
 NO_BOUND_MM0, NO_BOUND_SUM = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
 GUIDE_LEN = 20  # the ranking key, the on-target score, exists only there
+MAX_KP, MAX_DISTANCE = nat.SELECT_PAIRS_MAX_K, nat.SELECT_PAIRS_MAX_DISTANCE
+ORIENTATIONS = {"any": 0xF, "pam-out": 0x4, "pam-in": 0x2}  # bit sa * 2 + sb, 0 for '+' and 1 for '-'
+PAIR_DTYPE = np.dtype([("gene", "<u4"), ("rank", "<u4"), ("contig", "<u4"), ("position_a", "<i8"), ("strand_a", "S1"), ("score_a", "<f8"),
+                       ("index_a", "<u4"), ("position_b", "<i8"), ("strand_b", "S1"), ("score_b", "<f8"), ("index_b", "<u4"),
+                       ("deletion_length", "<u4")])
 ROW_DTYPE = np.dtype([("gene", "<u4"), ("rank", "<u4"), ("contig", "<u4"), ("position", "<i8"), ("strand", "S1"), ("score", "<f8"),
                       ("index", "<u4")])
 
@@ -90,6 +116,31 @@ class Params:
         return nat.SelectParams(self.min_score, self.max_hit_sum, self.max_mm0, self.k, int(self.require_cds), 0)
 
 
+class PairParams:
+    """What a pair selection asks for: KP, the window dmin <= D <= dmax on the deletion length, frameshift (D mod 3 != 0)
+    and the orientation: "any", "pam-out", "pam-in", or a 4-bit mask over (strand of a, strand of b), bit sa * 2 + sb."""
+
+    def __init__(self, k, dmin=50, dmax=500, frameshift=False, orientation="any"):
+        self.k = int(k)
+        if not 1 <= self.k <= MAX_KP:
+            raise ValueError("KP must be 1..%d, not %d" % (MAX_KP, self.k))
+        self.dmin, self.dmax = int(dmin), int(dmax)
+        if not 1 <= self.dmin <= self.dmax <= MAX_DISTANCE:
+            raise ValueError("the pair distances must be 1 <= dmin <= dmax <= %d, not %d and %d" % (MAX_DISTANCE, self.dmin, self.dmax))
+        self.frameshift = bool(frameshift)
+        if isinstance(orientation, str):
+            if orientation not in ORIENTATIONS:
+                raise ValueError("the pair orientation is one of %s, not %r" % (", ".join(sorted(ORIENTATIONS)), orientation))
+            self.mask = ORIENTATIONS[orientation]
+        else:
+            self.mask = int(orientation)
+        if not 1 <= self.mask <= 0xF:
+            raise ValueError("the orientation mask must be 1..15, not %r" % (orientation,))
+
+    def native(self):
+        return nat.SelectPairParams(self.k, self.dmin, self.dmax, self.mask, int(self.frameshift))
+
+
 class Request:
     """A selection for a backend's scan: Params, the annotate.Request that names the genes, slice_rows (None: the
     library's default; results do not depend on it) and the limits on the guide properties (properties.py), as counts:
@@ -97,10 +148,13 @@ class Request:
     only if all hold, and the scan runs the property kernel before the selection.  Likewise the repair scores
     (repair.py): min_mh (tenths of the microhomology score) and min_oof (an integer percentage) are limits, repair_flank
     is the kernel's flank (None: 30).  With a limit or a flank the scan runs the repair kernel before the selection; with a
-    flank the column is also fetched and the Selection carries mh and oof of its rows."""
+    flank the column is also fetched and the Selection carries mh and oof of its rows.  pairs (PairParams): the scan also
+    selects the best pairs of every gene, right after the single guides (Selection.pairs, Selection.n_pairs);
+    pair_slice_rows: the a-rows of one work item (None: the library's default; results do not depend on it)."""
 
     def __init__(self, params, annotation, slice_rows=None, gc_min=None, gc_max=None, max_run=None, max_t_run=None, max_stem=None,
-                 repair_flank=None, min_mh=None, min_oof=None):
+                 repair_flank=None, min_mh=None, min_oof=None, pairs=None, pair_slice_rows=None):
+        self.pairs, self.pair_slice_rows = pairs, pair_slice_rows
         from . import repair
         from .properties import Limits
         self.repair_flank = None if repair_flank is None else repair.check_flank(repair_flank)
@@ -122,7 +176,7 @@ class ArenaSelect:
         lo, hi = np.ascontiguousarray(lo, dtype=np.uint32), np.ascontiguousarray(hi, dtype=np.uint32)
         if lo.shape != hi.shape or lo.ndim != 1:
             raise ValueError("lo and hi must be 1-d arrays of one length")
-        self.n_genes, self.k = int(lo.size), 0
+        self.n_genes, self.k, self.kp = int(lo.size), 0, 0
         h = ctypes.c_void_p()
         nat.check(nat.lib().crp_select_create(arena._h, lo.ctypes.data_as(nat.u32p), hi.ctypes.data_as(nat.u32p), lo.size, ctypes.byref(h)),
                   "crp_select_create", self._ctx)
@@ -174,6 +228,30 @@ class ArenaSelect:
                 "merged_genes")
         return dict(zip(keys, (float(v) for v in out)))
 
+    def set_pair_limits(self, pair_slice_rows=0):
+        nat.check(nat.lib().crp_select_set_pair_limits(self._h, int(pair_slice_rows)), "crp_select_set_pair_limits", self._ctx)
+
+    def run_pairs(self, params, pair_params, self_search=None):
+        """params: Params (its thresholds; K is not read); pair_params: PairParams; self_search as run()."""
+        p, q = params.native(), pair_params.native()
+        nat.check(nat.lib().crp_select_run_pairs(self._h, ctypes.byref(p), ctypes.byref(q), self_search._h if self_search is not None else None),
+                  "crp_select_run_pairs", self._ctx)
+        self.kp = pair_params.k
+
+    def fetch_pairs(self):
+        """(n_pass uint32 (G,), n_pairs uint64 (G,), pairs uint32 (G, KP, 2)) of the last run_pairs."""
+        n_pass, n_pairs = np.empty(self.n_genes, np.uint32), np.empty(self.n_genes, np.uint64)
+        pairs = np.empty((self.n_genes, max(1, self.kp), 2), np.uint32)
+        nat.check(nat.lib().crp_select_fetch_pairs(self._h, n_pass.ctypes.data_as(nat.u32p), n_pairs.ctypes.data_as(nat.u64p),
+                                                   pairs.ctypes.data_as(nat.u32p)), "crp_select_fetch_pairs", self._ctx)
+        return n_pass, n_pairs, pairs
+
+    def pairs_stats(self):
+        out = np.zeros(8, dtype=np.float64)
+        nat.check(nat.lib().crp_select_pairs_stats(self._h, out.ctypes.data_as(nat.f64p), 8), "crp_select_pairs_stats", self._ctx)
+        keys = ("pass_key_ms", "pairs_ms", "merge_ms", "items", "launches", "longest_launch_ms", "pair_evaluations", "qualifying_pairs")
+        return dict(zip(keys, (float(v) for v in out)))
+
 
 def arena_layout(genome, a):
     """[(contig index, arena offset, length)] of arena `a` of an engine.Genome, as annotate.Request.track takes it."""
@@ -190,12 +268,16 @@ class Selection:
     """The selection over all genes of the GFF, in file order: labels, n_in, n_pass (per gene) and rows (ROW_DTYPE, gene
     after gene, rank 1 first; `index` is the row's place in its contig's strand table, `position` its match index local
     to the contig string), with counts (n, M + 1) uint32 and hit_sum (n,) uint64 of the rows when they were joined, and
-    mh / oof (n,) uint32 of the rows when the repair scores were fetched (None otherwise)."""
+    mh / oof (n,) uint32 of the rows when the repair scores were fetched (None otherwise).  With a pair selection: pairs
+    (PAIR_DTYPE, gene after gene, rank 1 first; a is the left guide), n_pairs (per gene, all qualifying pairs), pairs_stats
+    and, when the repair scores were fetched, pairs_repair (n, 2) uint64, packed, of a and b; None otherwise."""
 
     def __init__(self, labels, n_in, n_pass, rows, counts=None, hit_sum=None, stats=None, mh=None, oof=None):
         self.labels, self.n_in, self.n_pass, self.rows = labels, n_in, n_pass, rows
         self.counts, self.hit_sum, self.stats = counts, hit_sum, stats or {}
         self.mh, self.oof = mh, oof
+        self.pairs = self.n_pairs = self.pairs_repair = None
+        self.pairs_stats = {}
 
     def of_gene(self, g):
         return self.rows[self.rows["gene"] == g]
@@ -277,8 +359,75 @@ def assemble(labels, k, arenas, stats=None):
     return Selection(list(labels), n_in, n_pass, rows, counts, sums, stats, mh, oof)
 
 
+def assemble_pairs(n_genes, kp, arenas):
+    """(pairs PAIR_DTYPE, n_pairs int64 (n_genes,), repair (n, 2) uint64 or None) from per-arena results.  arenas: the dicts
+    assemble() takes, with pair_n_pairs and pair_list (layout rows x KP x 2) beside them.  A pair never spans texts; a gene
+    met in several texts gets the sum of its n_pairs and the first KP of its pairs in the definition's order."""
+    n_pairs = np.zeros(n_genes, np.int64)
+    parts, keys, rparts = [], [], []
+    repaired = any(a.get("repair_plus") is not None for a in arenas)
+    for a in arenas:
+        gene = np.asarray(a["gene"], dtype=np.int64)
+        np.add.at(n_pairs, gene, np.asarray(a["pair_n_pairs"]).astype(np.int64))
+        lst = np.asarray(a["pair_list"], dtype=np.uint32).reshape(gene.size, -1, 2)[:, :kp]
+        r, c = np.nonzero(lst[:, :, 0] != NONE)
+        part = np.empty(r.size, PAIR_DTYPE)
+        part["gene"], part["rank"] = gene[r], c + 1
+        offs = np.asarray(a["offsets"], dtype=np.int64)
+        first = {False: np.searchsorted(np.asarray(a["pos_plus"]), offs.astype(np.uint32), "left"),
+                 True: np.searchsorted(np.asarray(a["pos_minus"]), offs.astype(np.uint32), "left")}
+        cut, sbits, rep = [], [], []
+        for side, which in (("a", 0), ("b", 1)):
+            packed = lst[r, c, which]
+            minus = (packed >> np.uint32(31)).astype(bool)
+            row = (packed & np.uint32(0x7FFFFFFF)).astype(np.int64)
+            pos = _take(a["pos_plus"], a["pos_minus"], minus, row, np.int64)
+            t = np.searchsorted(offs, pos, "right") - 1
+            if which == 0:
+                part["contig"] = np.asarray(a["group"], dtype=np.uint32)[t] if r.size else 0
+            part["position_" + side] = pos - offs[t]
+            part["strand_" + side] = np.where(minus, b"-", b"+")
+            part["score_" + side] = _take(a["score_plus"], a["score_minus"], minus, row, np.float64)
+            part["index_" + side] = row - np.where(minus, first[True][t], first[False][t])
+            cut.append(part["position_" + side] + np.where(minus, 6, -3))
+            sbits.append(minus.astype(np.int64))
+            if repaired:
+                rep.append(_take(a["repair_plus"], a["repair_minus"], minus, row, np.uint64))
+        part["deletion_length"] = cut[1] - cut[0]
+        parts.append(part)
+        big = np.iinfo(np.uint64).max
+        ka, kb = part["score_a"].view(np.uint64), part["score_b"].view(np.uint64)
+        # (texts in arena order: a gene's pairs from different texts cannot tie on everything, and if two texts give equal
+        # keys the earlier text goes first, as assemble() has it)
+        keys.append(np.stack([big - np.minimum(ka, kb), big - np.maximum(ka, kb), cut[0].astype(np.uint64), cut[1].astype(np.uint64),
+                              (sbits[0] * 2 + sbits[1]).astype(np.uint64)], axis=1) if r.size else np.empty((0, 5), np.uint64))
+        if repaired:
+            rparts.append(np.stack(rep, axis=1) if r.size else np.empty((0, 2), np.uint64))
+    pairs = np.concatenate(parts) if parts else np.empty(0, PAIR_DTYPE)
+    key = np.concatenate(keys) if keys else np.empty((0, 5), np.uint64)
+    order = np.lexsort((np.arange(pairs.size), key[:, 4], key[:, 3], key[:, 2], key[:, 1], key[:, 0], pairs["gene"]))
+    pairs = pairs[order]
+    start = np.searchsorted(pairs["gene"], pairs["gene"], "left")
+    rank = np.arange(pairs.size) - start
+    keep = rank < kp
+    pairs = pairs[keep]
+    pairs["rank"] = rank[keep] + 1
+    repair = np.concatenate(rparts)[order][keep] if rparts else None
+    return pairs, n_pairs, repair
+
+
+def select_arena_pairs(sel, request, handle=None):
+    """The pair selection of one arena on the ArenaSelect that has just run the single-guide selection (its flags and
+    limits are set): (n_pass, n_pairs, pairs, stats)."""
+    if request.pair_slice_rows:
+        sel.set_pair_limits(request.pair_slice_rows)
+    sel.run_pairs(request.params, request.pairs, handle)
+    return sel.fetch_pairs() + (sel.pairs_stats(),)
+
+
 def select_arena(genome, a, request, handle=None, flags=None):
-    """The selection of one arena of an engine.Genome whose tables are resident: (lo, hi, gene, n_in, n_pass, sel, stats).
+    """The selection of one arena of an engine.Genome whose tables are resident: (lo, hi, gene, n_in, n_pass, sel, stats),
+    and with request.pairs one more element: (n_pass, n_pairs, pairs, pairs_stats) of the pair selection.
     handle: the arena's search.ArenaSelfSearch after join_hits, or None."""
     lo, hi, gene = request.annotation.gene_layout(arena_layout(genome, a))
     sel = ArenaSelect(genome.arenas[a], lo, hi)
@@ -293,7 +442,10 @@ def select_arena(genome, a, request, handle=None, flags=None):
             sel.set_repair_limits(request.repair_limits)
         sel.run(request.params, handle)
         n_in, n_pass, picked = sel.fetch()
-        return lo, hi, gene, n_in, n_pass, picked, sel.stats()
+        out = lo, hi, gene, n_in, n_pass, picked, sel.stats()
+        if getattr(request, "pairs", None) is not None:  # right after the single guides, on the same handle
+            out += (select_arena_pairs(sel, request, handle),)
+        return out
     finally:
         sel.close()
 

@@ -894,6 +894,46 @@ typedef struct crp_select_repair_limits {
 } crp_select_repair_limits;
 int crp_select_set_repair_limits(crp_select *select, const crp_select_repair_limits *limits);
 
+/* ---- guide pairs: the best KP deletion pairs of every gene (opt-in) --------------------- */
+/* Two guides in one array cut out the piece between them.  On a crp_select handle, over the same tables and genes:
+ *   eligible   the rows that PASS for gene g (crp_select_run's rule and predicate, unchanged)
+ *   boundary   c of a row, as crp_repair_scores defines it: i - 3 for a '+' row, j + 6 for a '-' row (NOT the cut site
+ *              that decides membership, nor the CSV's `cutsite`)
+ *   pair       (a, b): two eligible rows of one gene with c_a < c_b; D = c_b - c_a is the deletion's length, the letters
+ *              s[c_a : c_b) go
+ *   qualifies  dmin <= D <= dmax; with frameshift, D mod 3 != 0; and bit sa * 2 + sb of orientation_mask is set (s = 0
+ *              for '+', 1 for '-': 0xF any, 4 PAM-out = '-' left and '+' right, 2 PAM-in)
+ *   order      higher min(score_a, score_b) (the doubles' bits, unsigned), then higher max, then smaller c_a, then
+ *              smaller c_b, then smaller sa * 2 + sb: total
+ * Per gene: n_pass (eligible rows), n_pairs (all qualifying pairs, 64 bits) and pairs[g * KP * 2 ..): the first
+ * min(KP, n_pairs) pairs in that order, each as a then b in sel's packing (row | strand << 31), 0xFFFFFFFF beyond.
+ * Pairs may share a guide. */
+typedef struct crp_select_pair_params {
+    int32_t k;                 /* KP: 1 .. CRP_SELECT_PAIRS_MAX_K, independent of crp_select_params.k (which is not read) */
+    uint32_t dmin, dmax;       /* 1 <= dmin <= dmax <= CRP_SELECT_PAIRS_MAX_DISTANCE */
+    uint32_t orientation_mask; /* 1 .. 15 */
+    int32_t frameshift;
+} crp_select_pair_params;
+#define CRP_SELECT_PAIRS_MAX_K 64
+#define CRP_SELECT_PAIRS_MAX_DISTANCE 65535
+#define CRP_SELECT_DEFAULT_PAIR_SLICE_ROWS 1024
+#define CRP_SELECT_MIN_PAIR_SLICE_ROWS 64
+/* A gene's a-rows are cut into work items of at most pair_slice_rows rows, one wave each (0 = the default, 1 024; at
+ * least 64): a limit of its own, since an item costs rows x partners.  Results do not depend on it. */
+int crp_select_set_pair_limits(crp_select *select, uint64_t pair_slice_rows);
+/* Prerequisites and error codes as crp_select_run (params: its thresholds; params->k is not read).  CRP_ERR_INVALID
+ * with a crp_last_error text: KP outside 1 .. 64, dmin = 0, dmin > dmax, dmax > 65 535, a mask that is 0 or above 15.
+ * Leaves the results of crp_select_run alone. */
+int crp_select_run_pairs(crp_select *select, const crp_select_params *params, const crp_select_pair_params *pair_params,
+                         crp_search_self *self);
+/* The results of the last crp_select_run_pairs (CRP_ERR_STATE without one): n_pass and n_pairs (n_genes each) and pairs
+ * (n_genes * KP * 2).  Any pointer may be NULL. */
+int crp_select_fetch_pairs(crp_select *select, uint32_t *n_pass, uint64_t *n_pairs, uint32_t *pairs);
+/* Measurement of the last crp_select_run_pairs: out[0] ms of the pass-key kernel, out[1] ms of the pair launches,
+ * out[2] ms of the merge launches (HIP events), out[3] work items, out[4] pair launches, out[5] the longest pair launch
+ * in ms, out[6] pair evaluations (partner rows streamed), out[7] qualifying pairs.  n: how many to write (<= 8). */
+int crp_select_pairs_stats(const crp_select *select, double *out, int n);
+
 /* ---- options -------------------------------------------------------------- */
 /* CRP_OPT_TWO_PASS (value 0/1, default 0): with 0 crp_scan_score is ONE kernel launch; the
  * table offsets come from a chained scan across workgroups inside it (decoupled look-back
