@@ -48,6 +48,11 @@ class SelectRepairLimits(ctypes.Structure):
     _fields_ = [("min_mh", ctypes.c_uint32), ("min_oof_pct", ctypes.c_uint32)]
 
 
+class SelectCodingLimits(ctypes.Structure):
+    """crp_select_coding_limits (include/cropsr_hip.h): the bounds a selection puts on the coding position of the cut."""
+    _fields_ = [("min_pct", ctypes.c_uint32), ("max_pct", ctypes.c_uint32), ("min_transcripts_pct", ctypes.c_uint32)]
+
+
 class SelectPairParams(ctypes.Structure):
     """crp_select_pair_params (include/cropsr_hip.h): KP, the distance window, the orientation mask and frameshift of one
     crp_select_run_pairs."""
@@ -203,6 +208,13 @@ SIGNATURES = {
     "crp_select_run_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "crp_select_fetch_pairs": (ctypes.c_int, [ctypes.c_void_p, u32p, u64p, u32p]),
     "crp_select_pairs_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
+    "crp_annotation_gene_coding": (ctypes.c_int, [ctypes.c_void_p, u8p, u32p, u32p]),
+    "crp_annotation_coding_layout": (ctypes.c_int, [ctypes.c_void_p, u64p, ctypes.c_uint64, ctypes.c_int, u32p, u32p, u64p, ctypes.c_uint64, u64p,
+                                                    u32p, u32p, u32p, ctypes.c_uint64, u64p]),
+    "crp_select_set_coding": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, u64p, ctypes.c_uint64, u32p, u32p, u32p, ctypes.c_uint64]),
+    "crp_select_set_coding_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "crp_select_coding_eval": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, ctypes.c_uint64, u32p, u32p]),
+    "crp_select_coding_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_configure": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]),
     "crp_query": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     "crp_build_id": (ctypes.c_char_p, []),

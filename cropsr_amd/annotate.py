@@ -176,6 +176,37 @@ class Annotation:
                   "crp_annotation_gene_layout")
         return lo, hi, gene
 
+    # ---- the coding model (coding position of a cut, cropsr_amd/coding.py)
+    def gene_coding(self):
+        """(strand S1 -- '+', '-' or '.' --, n_tx uint32, length uint32) per gene of genes(): the gene's coding transcripts
+        and the coding length L_P of its primary one; both 0 for a gene without a model."""
+        n = int(self.n_genes)
+        strand, n_tx, length = np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+        nat.check(nat.lib().crp_annotation_gene_coding(self._h, strand.ctypes.data_as(nat.u8p), n_tx.ctypes.data_as(nat.u32p),
+                                                       length.ctypes.data_as(nat.u32p)), "crp_annotation_gene_coding")
+        return strand.view("S1"), n_tx, length
+
+    def coding_layout(self, entries, dec):
+        """The coding model of gene_layout's rows (the same rows in the same order) as crp_annotation_coding_layout gives
+        it: dict(info uint32, length uint32, first uint64 -- one more element than the rows, the last one the step count --,
+        at, word, cum uint32)."""
+        e = self._entries(entries)
+        n, m = ctypes.c_uint64(), ctypes.c_uint64()
+        L = nat.lib()
+        st = L.crp_annotation_coding_layout(self._h, e.ctypes.data_as(nat.u64p), e.shape[0], int(dec), None, None, None, 0, ctypes.byref(n),
+                                            None, None, None, 0, ctypes.byref(m))
+        if st not in (nat.CRP_OK, nat.CRP_ERR_CAPACITY):
+            nat.check(st, "crp_annotation_coding_layout")
+        rows, steps = int(n.value), int(m.value)
+        info, length, first = np.zeros(rows, np.uint32), np.zeros(rows, np.uint32), np.zeros(rows + 1, np.uint64)
+        at, word, cum = (np.zeros(steps, np.uint32) for _ in range(3))
+        nat.check(L.crp_annotation_coding_layout(self._h, e.ctypes.data_as(nat.u64p), e.shape[0], int(dec), info.ctypes.data_as(nat.u32p),
+                                                 length.ctypes.data_as(nat.u32p), first.ctypes.data_as(nat.u64p), rows, ctypes.byref(n),
+                                                 at.ctypes.data_as(nat.u32p), word.ctypes.data_as(nat.u32p), cum.ctypes.data_as(nat.u32p), steps,
+                                                 ctypes.byref(m)), "crp_annotation_coding_layout")
+        first[rows] = steps
+        return dict(info=info, length=length, first=first, at=at, word=word, cum=cum)
+
     def cds_flags(self):
         """uint8 per label-set string: 1 when the set holds a CDS label."""
         flags = np.zeros(max(1, len(self.strings)), np.uint8)
@@ -221,6 +252,10 @@ class Request:
     def gene_layout(self, layout):
         """layout as track() takes it -> (lo, hi, gene) of Annotation.gene_layout: that arena's genes."""
         return self.annotation.gene_layout([(self.names[t], self.starts[t], ln, off) for t, off, ln in layout], self.dec)
+
+    def coding_layout(self, layout):
+        """layout as track() takes it -> Annotation.coding_layout: the coding model of gene_layout's rows."""
+        return self.annotation.coding_layout([(self.names[t], self.starts[t], ln, off) for t, off, ln in layout], self.dec)
 
 
 def features_of(request, hits):

@@ -161,6 +161,20 @@ def build_parser():
                           "mediated end joining, Bae et al. 2014) on the GPU; every row of the selection file gets two more fields, "
                           "mh_score (microhomology score) and oof_score (the share, in percent, of the predicted deletions "
                           "that shift the frame; -1 where there is no microhomology); one GPU")
+    eng.add_argument("--coding", action="store_true",
+                     help="with --select: where in the gene's coding sequence every selected guide cuts, from the mRNA / CDS rows "
+                          "and Parent links of the GFF; every row of the selection file gets five more fields, cds_offset, cds_length, "
+                          "cds_percent (of the gene's longest coding transcript; empty when the cut is not inside it), transcripts_cut "
+                          "and transcripts; like its three filters, not together with --select-pairs")
+    eng.add_argument("--select-coding-min", default=None, metavar="PCT",
+                     help="with --select: only guides that cut inside the coding sequence of the gene's longest coding transcript, at "
+                          "least PCT %% of its length from its start (an integer 0..100); implies --coding")
+    eng.add_argument("--select-coding-max", default=None, metavar="PCT",
+                     help="with --select: ... and at most PCT %% of its length from its start (an integer 0..100; 65 keeps the last "
+                          "third out, where a frameshift leaves a nearly whole protein); implies --coding")
+    eng.add_argument("--select-transcripts", default=None, metavar="PCT",
+                     help="with --select: only guides that cut inside the coding sequence of at least PCT %% of the gene's coding "
+                          "transcripts (an integer 0..100; 100: every isoform); implies --coding")
     eng.add_argument("--repair-flank", default=None, metavar="F",
                      help="with --repair-scores or a repair filter: letters looked at on either side of the cut (2..32, default 30)")
     eng.add_argument("--select-min-oof", default=None, metavar="PCT",
@@ -570,7 +584,9 @@ def select_request(args, spec, world=1):
                                    ("--select-gc-max", "select_gc_max", None), ("--select-max-run", "select_max_run", None),
                                    ("--select-max-t-run", "select_max_t_run", None), ("--select-max-stem", "select_max_stem", None),
                                    ("--repair-scores", "repair_scores", False), ("--repair-flank", "repair_flank", None),
-                                   ("--select-min-oof", "select_min_oof", None), ("--select-min-mh", "select_min_mh", None))
+                                   ("--select-min-oof", "select_min_oof", None), ("--select-min-mh", "select_min_mh", None),
+                                   ("--coding", "coding", False), ("--select-coding-min", "select_coding_min", None),
+                                   ("--select-coding-max", "select_coding_max", None), ("--select-transcripts", "select_transcripts", None))
              if getattr(args, k, unset) not in (unset, None)]
     KP = getattr(args, "select_pairs", None)
     pair_given = [o for o, k, unset in (("--pairs-min-distance", "pairs_min_distance", None), ("--pairs-max-distance", "pairs_max_distance", None),
@@ -639,6 +655,27 @@ def select_request(args, spec, world=1):
             min_mh = repair.parse_min_mh(min_mh)
         except ValueError as e:
             refuse("--select-min-mh: " + str(e))
+    # the coding position: percentages, whole numbers 0..100, min <= max; the limits are relative to the gene, so not with pairs
+    pct = {}
+    for opt, key in (("--select-coding-min", "select_coding_min"), ("--select-coding-max", "select_coding_max"),
+                     ("--select-transcripts", "select_transcripts")):
+        v = getattr(args, key, None)
+        if v is not None:
+            if integer(v) is None or integer(v) > 100:
+                refuse("%s is a percentage, an integer 0..100, not %s" % (opt, v))
+            pct[key] = integer(v)
+    if pct.get("select_coding_min", 0) > pct.get("select_coding_max", 100):
+        refuse("--select-coding-min %d lies above --select-coding-max %d" % (pct.get("select_coding_min", 0), pct.get("select_coding_max", 100)))
+    with_coding = bool(getattr(args, "coding", False)) or bool(pct)
+    if with_coding and KP is not None:
+        refuse("%s: the coding position is relative to the gene and the pairs' eligibility is per table row: not together with --select-pairs"
+               % ([o for o, k in (("--select-coding-min", "select_coding_min"), ("--select-coding-max", "select_coding_max"),
+                                  ("--select-transcripts", "select_transcripts")) if k in pct] + ["--coding"])[0])
+    coding_args = {}
+    if with_coding:  # (the keywords a select.Request only meets with the coding position)
+        from . import coding
+        coding_args = dict(coding=True, coding_limits=coding.Limits(pct.get("select_coding_min", 0), pct.get("select_coding_max", 100),
+                                                                    pct.get("select_transcripts", 0)) if pct else None)
     # (a flank makes the scan fetch the column: only where the file prints it, or where the filters ask for another flank than the default)
     repair_args = dict(min_mh=min_mh, min_oof=min_oof,
                        repair_flank=(repair.DEFAULT_FLANK if flank is None else flank) if with_scores else flank)
@@ -656,8 +693,8 @@ def select_request(args, spec, world=1):
         except ValueError as e:
             refuse("--select-pairs: " + str(e))
     return dict(params=params, output=getattr(args, "select_output", None) or (args.o + ".selected.csv"),
-                only=bool(getattr(args, "select_only", False)), limits=dict(limits, **repair_args), repair_scores=with_scores,
-                pairs=pairs, pairs_output=getattr(args, "pairs_output", None) or (args.o + ".pairs.csv"))
+                only=bool(getattr(args, "select_only", False)), limits=dict(limits, **repair_args, **coding_args), repair_scores=with_scores,
+                coding=with_coding, pairs=pairs, pairs_output=getattr(args, "pairs_output", None) or (args.o + ".pairs.csv"))
 
 
 def properties_request(args, world=1):
@@ -681,12 +718,14 @@ def properties_request(args, world=1):
 
 
 def write_selection(path, selection, names, strings, all_hits, guide_len, offtarget, spec_M, annotation, properties=False,
-                    repair_scores=False):
+                    repair_scores=False, coding=False):
     """The selection file: a header, then per chosen row gene, rank (1-based), passing and the main table's own fields
     for that row as rows.ContigRows builds them, without crispr_id (those ids are random per run).  Genes in GFF order;
     genes with nothing selected are left out.  Python's csv module in the main table's dialect: the file is small.
-    repair_scores: two more fields at the end of every row, mh_score and oof_score (repair.fields) of selection.mh / .oof."""
+    repair_scores: two more fields at the end of every row, mh_score and oof_score (repair.fields) of selection.mh / .oof.
+    coding: five more after those, cds_offset, cds_length, cds_percent, transcripts_cut and transcripts (coding.fields)."""
     import csv
+    from . import coding as cod
     from . import repair
     sel_rows = selection.rows
     fields = [None] * sel_rows.size
@@ -706,9 +745,11 @@ def write_selection(path, selection, names, strings, all_hits, guide_len, offtar
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(["gene", "rank", "passing"] + rows.HEADER[1:] + rows.extra_header(offtarget, spec_M, properties)
-                   + (repair.HEADER if repair_scores else []))
+                   + (repair.HEADER if repair_scores else []) + (cod.HEADER if coding else []))
         for at, (r, rest) in enumerate(zip(sel_rows, fields)):
             more = repair.fields(repair.pack(selection.mh[at], selection.oof[at])) if repair_scores else ()
+            if coding:
+                more = tuple(more) + cod.fields(selection.cds_offset[at], selection.cds_length[at], selection.transcripts_cut[at], selection.transcripts[at])
             w.writerow((selection.labels[int(r["gene"])], int(r["rank"]), int(selection.n_pass[int(r["gene"])])) + tuple(rest) + tuple(more))
 
 
@@ -1020,7 +1061,8 @@ def run(args, backend=None, out=sys.stdout, group=None):
         t_select = time.perf_counter()
         selection = all_hits.selection
         write_selection(selecting["output"], selection, names, strings, all_hits, args.l, offtarget, None if spec is None else spec["max_mm"],
-                        request.annotation if annotating else None, properties=with_properties, repair_scores=selecting["repair_scores"])
+                        request.annotation if annotating else None, properties=with_properties, repair_scores=selecting["repair_scores"],
+                        coding=selecting["coding"])
         stages["select"] = dict(selection.stats, write_s=time.perf_counter() - t_select, genes=len(selection.labels),
                                 rows_selected=int(selection.rows.size), k=selecting["params"].k)
         if selecting["pairs"] is not None:

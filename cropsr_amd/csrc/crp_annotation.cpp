@@ -15,6 +15,11 @@
 //   set     for a 1-based coordinate x of a seqid: the labels of the rows with start <= x <= end, file order, each
 //           label once, joined with ';'
 //
+// The same pass keeps, for the coding position of a cut (cropsr_amd/coding.py has the definition),
+// the gene rows' strand, the `mRNA` / `transcript` rows and every row's ID and Parent: build_coding links them once the file
+// is read into every gene's coding transcripts, and crp_annotation_coding_layout lays those out beside the gene rows.  The
+// rows above do not see any of it: an mRNA row adds no label, no interval, no seqid and no count.
+//
 // The interval ends cut a seqid's axis into elementary intervals with a constant set: one sweep over the sorted
 // points builds one string per DISTINCT set (interned over the whole file) and the id of every interval.
 #include <algorithm>
@@ -48,6 +53,21 @@ struct crp_annotation {
     std::vector<std::vector<uint32_t>> genes_of;  // per seqid: its genes (indices into `genes`), file order
     std::string gene_blob;
     std::vector<uint64_t> gene_off{0};
+    // the coding model of every gene (cropsr_amd/coding.py states the definition): its coding
+    // transcripts in file order, each the merged closed ranges of its CDS rows in GFF coordinates
+    struct Transcript {
+        uint64_t seg_first, seg_n, len;
+    };
+    struct Coding {
+        uint8_t strand = 0;  // 1: '+', 2: '-', 0: anything else
+        bool model = false;
+        uint32_t n_tx = 0;  // (without a model: 0, and so is len)
+        uint64_t len = 0;   // L_P
+        uint64_t tx_first = 0, primary = 0;  // txs[tx_first .. tx_first + n_tx); the primary one among them
+    };
+    std::vector<Coding> coding;  // per gene
+    std::vector<Transcript> txs;
+    std::vector<std::pair<int64_t, int64_t>> segs;
 };
 
 namespace {
@@ -139,6 +159,107 @@ struct Feature {
     uint32_t label;  // index into the label table (equal strings share one)
 };
 
+// What the coding model keeps of a row until the whole file is read (children may come before their parents).  `seq`
+// numbers the seqids of these rows alone: an mRNA row must not add a seqid to the annotation's own list.
+struct ModelRow {
+    uint32_t seq;
+    uint64_t line;  // rows in file order
+    sv id, parent;
+    int64_t start, end;
+};
+
+// the values of a Parent attribute: a comma-separated list; empty values name nothing
+template <class F>
+void each_parent(sv list, F &&f)
+{
+    size_t a = 0;
+    for (;;) {
+        const size_t b = list.find(',', a);
+        const sv v = list.substr(a, b == sv::npos ? sv::npos : b - a);
+        if (!v.empty()) f(v);
+        if (b == sv::npos) return;
+        a = b + 1;
+    }
+}
+
+std::string model_key(uint32_t seq, sv id)
+{
+    std::string k = std::to_string(seq);
+    k.push_back('\t');
+    k.append(id);
+    return k;
+}
+
+// Links the rows and builds every gene's coding transcripts (cropsr_amd/coding.py has the definition).
+void build_coding(crp_annotation *an, const std::vector<ModelRow> &genes, const std::vector<uint8_t> &strands, const std::vector<ModelRow> &txs,
+                  const std::vector<ModelRow> &cds)
+{
+    using Ranges = std::vector<std::pair<int64_t, int64_t>>;
+    std::unordered_map<std::string, uint32_t> gene_by, tx_by;  // the first row of an ID owns the children
+    for (uint32_t g = 0; g < genes.size(); ++g)
+        if (!genes[g].id.empty()) gene_by.try_emplace(model_key(genes[g].seq, genes[g].id), g);
+    for (uint32_t t = 0; t < txs.size(); ++t)
+        if (!txs[t].id.empty()) tx_by.try_emplace(model_key(txs[t].seq, txs[t].id), t);
+    std::vector<Ranges> tx_ranges(txs.size()), own_ranges(genes.size());
+    std::vector<std::vector<uint32_t>> txs_of(genes.size());
+    for (uint32_t t = 0; t < txs.size(); ++t)
+        each_parent(txs[t].parent, [&](sv v) {
+            const auto g = gene_by.find(model_key(txs[t].seq, v));
+            if (g == gene_by.end()) return;
+            std::vector<uint32_t> &list = txs_of[g->second];
+            if (list.empty() || list.back() != t) list.push_back(t);  // (rows come in order: a value named twice is the last one)
+        });
+    for (const ModelRow &c : cds) {
+        if (c.start > c.end) continue;
+        each_parent(c.parent, [&](sv v) {
+            const std::string key = model_key(c.seq, v);
+            const auto t = tx_by.find(key);
+            if (t != tx_by.end()) tx_ranges[t->second].emplace_back(c.start, c.end);
+            const auto g = gene_by.find(key);
+            if (g != gene_by.end()) own_ranges[g->second].emplace_back(c.start, c.end);
+        });
+    }
+    an->coding.assign(genes.size(), crp_annotation::Coding());
+    std::vector<std::pair<uint64_t, Ranges *>> cand;  // (line, ranges): the gene's transcripts in file order
+    for (uint32_t g = 0; g < genes.size(); ++g) {
+        crp_annotation::Coding &c = an->coding[g];
+        c.strand = strands[g];
+        if (!c.strand || genes[g].id.empty()) continue;
+        cand.clear();
+        cand.emplace_back(genes[g].line, &own_ranges[g]);  // the implicit transcript stands at the gene row
+        for (uint32_t t : txs_of[g]) cand.emplace_back(txs[t].line, &tx_ranges[t]);  // (a row that owns no children has no ranges)
+        std::sort(cand.begin(), cand.end(), [](const auto &a, const auto &b) { return a.first < b.first; });
+        const uint64_t tx_first = an->txs.size(), seg_first = an->segs.size();
+        uint64_t best = 0, primary = 0;
+        for (const auto &one : cand) {
+            Ranges r = *one.second;  // (a transcript may serve several genes: a copy)
+            if (r.empty()) continue;
+            std::sort(r.begin(), r.end());
+            crp_annotation::Transcript tx{an->segs.size(), 0, 0};
+            for (const auto &ab : r) {
+                if (tx.seg_n && ab.first <= an->segs.back().second + 1) an->segs.back().second = std::max(an->segs.back().second, ab.second);
+                else an->segs.push_back(ab), tx.seg_n += 1;
+            }
+            // (merged segments are disjoint ranges of coordinates below 10^18, so the sum cannot wrap; it is capped all the same)
+            for (uint64_t k = 0; k < tx.seg_n; ++k)
+                tx.len = std::min<uint64_t>(tx.len + (uint64_t)(an->segs[tx.seg_first + k].second - an->segs[tx.seg_first + k].first) + 1, 1ull << 40);
+            if (tx.len > best) best = tx.len, primary = an->txs.size() - tx_first;  // (a tie: the earlier row stays)
+            an->txs.push_back(tx);
+        }
+        const uint64_t n_tx = an->txs.size() - tx_first;
+        if (!n_tx || best > 0xFFFFFFFFull) {  // no coding transcript, or a length no contig can hold: no model
+            an->txs.resize(tx_first);
+            an->segs.resize(seg_first);
+            continue;
+        }
+        c.model = true;
+        c.n_tx = (uint32_t)std::min<uint64_t>(n_tx, 0xFFFFFFFFull);
+        c.len = best;
+        c.tx_first = tx_first;
+        c.primary = primary;
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -163,6 +284,13 @@ int crp_annotation_build(const uint8_t *gff, uint64_t gff_len, const uint8_t *in
         // (sized for a typical GFF -- a gene / CDS row every ~250 bytes -- so the tables do not rehash on the way)
         label_of.reserve(gff_len / 256 + 16);
         labels.reserve(gff_len / 256 + 16);
+        std::unordered_map<std::string, uint32_t> model_seq_of;
+        std::vector<ModelRow> model_genes, model_txs, model_cds;
+        std::vector<uint8_t> model_strands;
+        uint32_t model_seq = 0;
+        sv model_seq_name;
+        bool have_model_seq = false;
+        uint64_t n_rows = 0;
         uint32_t last_seq = 0;  // consecutive rows usually share their seqid
         bool have_last = false;
         size_t p = 0;
@@ -175,7 +303,8 @@ int crp_annotation_build(const uint8_t *gff, uint64_t gff_len, const uint8_t *in
             split_tabs(line, cols);
             if (cols.size() < 9) continue;
             const bool gene = cols[2] == "gene";
-            if (!gene && cols[2] != "CDS") continue;
+            const bool transcript = cols[2] == "mRNA" || cols[2] == "transcript";  // (read by the coding model alone)
+            if (!gene && !transcript && cols[2] != "CDS") continue;
             int64_t start, end;
             if (!digits(cols[3], &start) || !digits(cols[4], &end)) continue;  // unreadable coordinates join nothing
             sv id, name, parent;
@@ -195,6 +324,21 @@ int crp_annotation_build(const uint8_t *gff, uint64_t gff_len, const uint8_t *in
                     a = b + 1;
                 }
             }
+            {
+                if (!have_model_seq || model_seq_name != cols[0]) {
+                    model_seq = model_seq_of.emplace(std::string(cols[0]), (uint32_t)model_seq_of.size()).first->second;
+                    model_seq_name = cols[0];
+                    have_model_seq = true;
+                }
+                const ModelRow row{model_seq, n_rows++, id, parent, start, end};
+                if (gene) {
+                    model_genes.push_back(row);
+                    model_strands.push_back(cols[6] == "+" ? 1 : cols[6] == "-" ? 2 : 0);
+                } else {
+                    (transcript ? model_txs : model_cds).push_back(row);
+                }
+            }
+            if (transcript) continue;  // labels, intervals and counts are the gene and CDS rows' alone
             const sv ident = !id.empty() ? id : !name.empty() ? name : !parent.empty() ? parent : sv(".");
             label.assign(gene ? "gene:" : "CDS:");
             label.append(ident);
@@ -233,6 +377,7 @@ int crp_annotation_build(const uint8_t *gff, uint64_t gff_len, const uint8_t *in
                 an->gene_off.push_back(an->gene_blob.size());
             }
         }
+        build_coding(an, model_genes, model_strands, model_txs, model_cds);
         // the sweep, seqid by seqid
         std::unordered_map<std::string, uint32_t> string_of;
         string_of.reserve(2 * labels.size() + 16);
@@ -410,6 +555,103 @@ int crp_annotation_gene_layout(const crp_annotation *an, const uint64_t *entries
     }
     *n_out = n;
     return n <= cap ? CRP_OK : CRP_ERR_CAPACITY;
+}
+
+int crp_annotation_gene_coding(const crp_annotation *an, uint8_t *strand, uint32_t *n_tx, uint32_t *length)
+{
+    if (!an) return CRP_ERR_INVALID;
+    for (size_t g = 0; g < an->coding.size(); ++g) {
+        const crp_annotation::Coding &c = an->coding[g];
+        if (strand) strand[g] = c.strand == 1 ? '+' : c.strand == 2 ? '-' : '.';
+        if (n_tx) n_tx[g] = c.n_tx;
+        if (length) length[g] = (uint32_t)c.len;
+    }
+    return CRP_OK;
+}
+
+int crp_annotation_coding_layout(const crp_annotation *an, const uint64_t *entries, uint64_t n_entries, int dec, uint32_t *info,
+                                 uint32_t *length, uint64_t *first, uint64_t cap_rows, uint64_t *n_rows, uint32_t *at, uint32_t *word,
+                                 uint32_t *cum, uint64_t cap_steps, uint64_t *n_steps)
+{
+    if (!an || (n_entries && !entries) || !n_rows || !n_steps || (cap_rows && (!info || !length || !first)) ||
+        (cap_steps && (!at || !word || !cum)))
+        return CRP_ERR_INVALID;
+    struct Event {
+        int64_t at;
+        int32_t cover, inside, grow;
+    };
+    std::vector<Event> ev;
+    uint64_t n = 0, m = 0, prev_base = 0, prev_end = 0;
+    try {
+        for (uint64_t e = 0; e < n_entries; ++e) {
+            const uint64_t seq = entries[4 * e], start = entries[4 * e + 1], len = entries[4 * e + 2], base = entries[4 * e + 3];
+            if (base + len > 0x7fffffffull || (e && (base < prev_end || base <= prev_base))) return CRP_ERR_INVALID;  // as the track
+            prev_base = base;
+            prev_end = base + len;
+            if (seq >= an->seqs.size() || !len) continue;
+            const int64_t shift = (int64_t)dec - 1 - (int64_t)start;  // (crp_annotation_gene_layout's mapping, and its rows)
+            for (uint32_t g : an->genes_of[seq]) {
+                const crp_annotation::Gene &t = an->genes[g];
+                if (t.start > t.end) continue;
+                if (std::max<int64_t>(t.start + shift, 0) > std::min<int64_t>(t.end + shift, (int64_t)len - 1)) continue;
+                const crp_annotation::Coding &c = an->coding[g];
+                if (c.n_tx > 0xFFFFu) return CRP_ERR_UNSUPPORTED;  // (the cover field of a step has 16 bits)
+                if (n < cap_rows) {
+                    info[n] = c.model ? c.n_tx | (c.strand == 2 ? 1u << 16 : 0u) | 1u << 17 : 0u;
+                    length[n] = (uint32_t)c.len;
+                    first[n] = m;
+                }
+                n += 1;
+                if (!c.model) continue;
+                // every merged segment, clipped to the text, as letters [a, b] of the text: the cut boundaries inside it are
+                // a + 1 .. b, and s[c] is one of its letters for c = a .. b
+                ev.clear();
+                for (uint64_t x = 0; x < c.n_tx; ++x) {
+                    const crp_annotation::Transcript &tx = an->txs[c.tx_first + x];
+                    const bool primary = x == c.primary;
+                    for (uint64_t k = 0; k < tx.seg_n; ++k) {
+                        const int64_t a = std::max<int64_t>(an->segs[tx.seg_first + k].first + shift, 0);
+                        const int64_t b = std::min<int64_t>(an->segs[tx.seg_first + k].second + shift, (int64_t)len - 1);
+                        if (a > b) continue;
+                        if (primary) ev.push_back(Event{a, 0, 0, 1});
+                        ev.push_back(Event{a + 1, 1, primary ? 1 : 0, 0});
+                        ev.push_back(Event{b + 1, -1, primary ? -1 : 0, primary ? -1 : 0});
+                    }
+                }
+                std::sort(ev.begin(), ev.end(), [](const Event &p, const Event &q) { return p.at < q.at; });
+                const crp_annotation::Transcript &P = an->txs[c.tx_first + c.primary];
+                // P's coding letters below the text's first letter, on the whole contig: where the running count starts
+                uint64_t before = 0;
+                for (uint64_t k = 0; k < P.seg_n; ++k) {
+                    const int64_t a = an->segs[P.seg_first + k].first + shift, b = an->segs[P.seg_first + k].second + shift;
+                    if (a < 0) before += (uint64_t)(std::min<int64_t>(0, b + 1) - a);
+                }
+                int32_t cover = 0, inside = 0, grow = 0;
+                int64_t at_x = 0;  // `before` counts the letters below text index at_x
+                uint32_t last = 0;  // the word of the step before: before the first one nothing holds
+                for (size_t i = 0; i < ev.size();) {
+                    const int64_t x = ev[i].at;
+                    if (grow) before += (uint64_t)(x - at_x);  // (inside the text P's letters are the clipped segments': grow says it all)
+                    at_x = x;
+                    for (; i < ev.size() && ev[i].at == x; ++i) cover += ev[i].cover, inside += ev[i].inside, grow += ev[i].grow;
+                    const uint32_t w = (uint32_t)cover | (inside ? 1u << 16 : 0u) | (grow ? 1u << 17 : 0u);
+                    if (w == last) continue;
+                    last = w;
+                    if (m < cap_steps) {
+                        at[m] = (uint32_t)(base + (uint64_t)x);
+                        word[m] = w;
+                        cum[m] = (uint32_t)before;
+                    }
+                    m += 1;
+                }
+            }
+        }
+    } catch (const std::bad_alloc &) {
+        return CRP_ERR_NOMEM;
+    }
+    *n_rows = n;
+    *n_steps = m;
+    return n <= cap_rows && m <= cap_steps ? CRP_OK : CRP_ERR_CAPACITY;
 }
 
 int crp_annotation_cds_flags(const crp_annotation *an, uint8_t *flags)

@@ -11,6 +11,7 @@
 #include "crp_roctx.h"
 #include "crp_search_self.h"
 #include "crp_select.h"
+#include "crp_select_coding.h"
 
 struct crp_select {
     crp_arena *arena = nullptr;
@@ -53,6 +54,17 @@ struct crp_select {
     uint64_t pair_res_cap[3] = {};
     int kp = 0;  // of the last successful crp_select_run_pairs (0: none)
     double pair_stats[8] = {};
+    // coding position: the model of the handle's genes -- info, length, first (n_genes + 1), at, word,
+    // cum -- the limits, and the queries and answers of crp_select_coding_eval
+    uint32_t *d_cod[6] = {};
+    uint64_t cod_cap[6] = {};
+    bool have_coding = false;
+    uint64_t coding_steps = 0;
+    bool have_coding_limits = false;
+    crp_select_coding_limits coding_limits = {};
+    uint32_t *d_eval[4] = {};
+    uint64_t eval_cap[4] = {};
+    double coding_stats[3] = {};
 };
 
 namespace {
@@ -178,7 +190,9 @@ int crp_select_destroy(crp_select *s)
     void *bufs[] = {s->d_lo, s->d_hi, s->d_bounds, s->d_flags, s->d_items, s->d_merge, s->part.key, s->part.tie,
                     s->part.row, s->part.cnt, s->res.n_in, s->res.n_pass, s->res.sel, s->d_pass_key[0], s->d_pass_key[1], s->d_pair_items,
                     s->d_pair_merge, s->d_pair_evals, s->pair_part.kmin, s->pair_part.kmax, s->pair_part.tie, s->pair_part.a, s->pair_part.b,
-                    s->pair_part.n_pass, s->pair_part.n_pairs, s->pair_res.n_pass, s->pair_res.n_pairs, s->pair_res.pairs};
+                    s->pair_part.n_pass, s->pair_part.n_pairs, s->pair_res.n_pass, s->pair_res.n_pairs, s->pair_res.pairs,
+                    s->d_cod[0], s->d_cod[1], s->d_cod[2], s->d_cod[3], s->d_cod[4], s->d_cod[5], s->d_eval[0], s->d_eval[1], s->d_eval[2],
+                    s->d_eval[3]};
     for (void *p : bufs) (void)hipFree(p);
     for (hipEvent_t e : s->ev)
         if (e) (void)hipEventDestroy(e);
@@ -240,6 +254,9 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
     crp::SelfJoined joined = {};
     int rc = check_run(s, p, self, &joined, "crp_select_run");
     if (rc != CRP_OK) return rc;
+    if (s->have_coding_limits && !s->have_coding)
+        return fail(ctx, CRP_ERR_STATE, "crp_select_run: coding limits need the model of a crp_select_set_coding");
+    s->coding_stats[0] = 0;
     CRP_HIP(ctx, hipSetDevice(ctx->device));
     const int k = p->k;
     const uint64_t G = s->n_genes;
@@ -308,14 +325,20 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
     crp::SelectTable tab[2];
     crp::SelectPredicate pred;
     fill_predicate(s, p, self != nullptr, joined, k, tab, &pred);
+    const crp::SelectCoding coding = {s->d_cod[0], s->d_cod[1], s->d_cod[2], s->d_cod[3], s->d_cod[4], s->d_cod[5]};
+    const crp::CodingLimits coding_lim = {s->coding_limits.min_pct, s->coding_limits.max_pct, s->coding_limits.min_transcripts_pct};
     // the bounded-launch rule: at most 2^20 items a launch, each timed on its own
     for (uint64_t first = 0; first < items.size(); first += crp::SELECT_MAX_ITEMS) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(crp::SELECT_MAX_ITEMS, items.size() - first);
         CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
-        CRP_HIP(ctx, crp::launch_select_items(ctx->stream, tab[0], tab[1], pred, s->d_items + first, n, s->part, s->res));
+        if (s->have_coding_limits)
+            CRP_HIP(ctx, crp::launch_select_items_coding(ctx->stream, tab[0], tab[1], pred, coding, coding_lim, s->d_items + first, n, s->part, s->res));
+        else
+            CRP_HIP(ctx, crp::launch_select_items(ctx->stream, tab[0], tab[1], pred, s->d_items + first, n, s->part, s->res));
         CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
         CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
         const double ms = elapsed(s->ev[0], s->ev[1]);
+        if (s->have_coding_limits) s->coding_stats[0] += ms;
         s->stats[1] += ms;
         s->stats[4] += 1;
         s->stats[5] = std::max(s->stats[5], ms);
@@ -386,6 +409,9 @@ int crp_select_run_pairs(crp_select *s, const crp_select_params *p, const crp_se
                                               ", not " + std::to_string(q->dmin) + " and " + std::to_string(q->dmax));
     if (q->orientation_mask < 1 || q->orientation_mask > 0xFu)
         return fail(ctx, CRP_ERR_INVALID, who + ": the orientation mask must be 1..15, not " + std::to_string(q->orientation_mask));
+    if (s->have_coding_limits)
+        return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": coding limits are relative to the gene and the pairs' eligibility key is per table row: "
+                                                    "clear them (crp_select_set_coding_limits(select, NULL)) for a pair selection");
     crp::SelfJoined joined = {};
     int rc = check_run(s, p, self, &joined, who.c_str());
     if (rc != CRP_OK) return rc;
@@ -533,6 +559,107 @@ int crp_select_pairs_stats(const crp_select *s, double *out, int n)
 {
     if (!s || (n && !out) || n < 0 || n > 8) return CRP_ERR_INVALID;
     for (int k = 0; k < n; ++k) out[k] = s->pair_stats[k];
+    return CRP_OK;
+}
+
+/* ---- coding position ---- */
+
+int crp_select_set_coding(crp_select *s, const uint32_t *info, const uint32_t *length, const uint64_t *first, uint64_t n_rows, const uint32_t *at,
+                          const uint32_t *word, const uint32_t *cum, uint64_t n_steps)
+{
+    if (!s) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    const std::string who = "crp_select_set_coding";
+    if (!n_rows && !info && !length && !first && !n_steps) {
+        s->have_coding = false;
+        return CRP_OK;
+    }
+    if (n_rows != s->n_genes)
+        return fail(ctx, CRP_ERR_INVALID, who + ": the model has " + std::to_string(n_rows) + " rows and the handle " + std::to_string(s->n_genes) + " genes");
+    if (!first || (n_rows && (!info || !length)) || (n_steps && (!at || !word || !cum)) || n_steps > 0xfffffff0ull) return CRP_ERR_INVALID;
+    s->have_coding = false;
+    std::vector<uint32_t> first32;
+    try {
+        first32.resize(n_rows + 1);
+    } catch (const std::bad_alloc &) {
+        return CRP_ERR_NOMEM;
+    }
+    // what the kernels rely on: every row's steps lie inside the arrays, and its change points ascend
+    for (uint64_t g = 0; g <= n_rows; ++g) {
+        if (first[g] > n_steps || (g && first[g] < first[g - 1]) || (g == n_rows && first[g] != n_steps) || (!g && first[g] != 0))
+            return fail(ctx, CRP_ERR_INVALID, who + ": first does not ascend from 0 to n_steps at row " + std::to_string(g));
+        first32[g] = (uint32_t)first[g];
+    }
+    for (uint64_t g = 0; g < n_rows; ++g)
+        for (uint64_t k = first[g] + 1; k < first[g + 1]; ++k)
+            if (at[k] <= at[k - 1]) return fail(ctx, CRP_ERR_INVALID, who + ": the change points of row " + std::to_string(g) + " do not ascend");
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    const void *src[6] = {info, length, first32.data(), at, word, cum};
+    const uint64_t count[6] = {n_rows, n_rows, n_rows + 1, n_steps, n_steps, n_steps};
+    int rc = CRP_OK;
+    for (int j = 0; j < 6 && rc == CRP_OK; ++j) {
+        rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_cod[j]), &s->cod_cap[j], count[j], sizeof(uint32_t));
+        if (rc == CRP_OK && count[j]) rc = crp::staged_h2d(ctx, s->d_cod[j], src[j], count[j] * sizeof(uint32_t));
+    }
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s->coding_steps = n_steps;
+    s->coding_stats[2] = (double)n_steps;
+    s->have_coding = true;
+    return CRP_OK;
+}
+
+int crp_select_set_coding_limits(crp_select *s, const crp_select_coding_limits *limits)
+{
+    if (!s) return CRP_ERR_INVALID;
+    if (limits && (limits->min_pct > limits->max_pct || limits->max_pct > 100u || limits->min_transcripts_pct > 100u))
+        return fail(s->ctx, CRP_ERR_INVALID,
+                    "crp_select_set_coding_limits: percentages 0..100 with min_pct <= max_pct, not " + std::to_string(limits->min_pct) + ", " +
+                        std::to_string(limits->max_pct) + " and " + std::to_string(limits->min_transcripts_pct));
+    s->have_coding_limits = limits != nullptr;
+    s->coding_limits = limits ? *limits : crp_select_coding_limits{};
+    return CRP_OK;
+}
+
+int crp_select_coding_eval(crp_select *s, const uint32_t *gene_row, const uint32_t *packed_row, uint64_t n, uint32_t *off, uint32_t *cover)
+{
+    if (!s || (n && (!gene_row || !packed_row || !off || !cover)) || n > 0x7fffffffull) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    crp_arena *a = s->arena;
+    const std::string who = "crp_select_coding_eval";
+    if (!s->have_coding) return fail(ctx, CRP_ERR_STATE, who + ": the handle has no model (crp_select_set_coding)");
+    if (!a->have_hits) return fail(ctx, CRP_ERR_STATE, who + ": the arena has no hit tables");
+    for (uint64_t q = 0; q < n; ++q) {
+        if (gene_row[q] >= s->n_genes)
+            return fail(ctx, CRP_ERR_INVALID, who + ": query " + std::to_string(q) + " names gene " + std::to_string(gene_row[q]) + " of " + std::to_string(s->n_genes));
+        if ((packed_row[q] & 0x7FFFFFFFu) >= a->n_hits[packed_row[q] >> 31])
+            return fail(ctx, CRP_ERR_INVALID, who + ": query " + std::to_string(q) + " names a row outside its table");
+    }
+    s->coding_stats[1] = 0;
+    if (!n) return CRP_OK;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = CRP_OK;
+    for (int j = 0; j < 4 && rc == CRP_OK; ++j) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_eval[j]), &s->eval_cap[j], n, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::staged_h2d(ctx, s->d_eval[0], gene_row, n * sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::staged_h2d(ctx, s->d_eval[1], packed_row, n * sizeof(uint32_t));
+    if (rc != CRP_OK) return rc;
+    const crp::SelectCoding coding = {s->d_cod[0], s->d_cod[1], s->d_cod[2], s->d_cod[3], s->d_cod[4], s->d_cod[5]};
+    CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    CRP_HIP(ctx, crp::launch_coding_eval(ctx->stream, a->d_pos[0], a->d_pos[1], coding, s->d_eval[0], s->d_eval[1], (uint32_t)n, s->d_eval[2],
+                                         s->d_eval[3]));
+    CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+    rc = crp::staged_d2h(ctx, off, s->d_eval[2], n * sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::staged_d2h(ctx, cover, s->d_eval[3], n * sizeof(uint32_t));
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s->coding_stats[1] = elapsed(s->ev[0], s->ev[1]);
+    return CRP_OK;
+}
+
+int crp_select_coding_stats(const crp_select *s, double *out, int n)
+{
+    if (!s || (n && !out) || n < 0 || n > 3) return CRP_ERR_INVALID;
+    for (int k = 0; k < n; ++k) out[k] = s->coding_stats[k];
     return CRP_OK;
 }
 

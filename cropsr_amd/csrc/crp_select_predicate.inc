@@ -1,6 +1,7 @@
 // crp_select_predicate.inc -- whether a table row PASSES, "in the gene" apart: the one statement of the selection's
-// predicate on the device.  Included, as it stands, in the row loop of select_items_kernel (crp_select.hip) and in
-// pair_pass_key_kernel (crp_select_pairs.hip).  A text fragment and not a function: as a __forceinline__ function the
+// predicate on the device.  Included, as it stands, in the row loop of select_items_kernel (crp_select.hip), in
+// pair_pass_key_kernel (crp_select_pairs.hip) and in the row loop of select_items_coding_kernel (crp_select_coding.hip), which
+// goes on to clear `pass` where the coding test fails: `pass` must stay a plain, non-const bool.  A text fragment and not a function: as a __forceinline__ function the
 // compiler built another select_items_kernel (601 instead of 630 instructions, other SGPR traffic), which could not be
 // shown to keep the plain selection's time inside the earlier build's run-to-run spread; included as text the kernel's
 // assembly is the earlier build's, instruction for instruction (DESIGN.md section 19).

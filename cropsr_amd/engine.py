@@ -778,7 +778,8 @@ class Genome:
         parts, stats, pair_stats = [], {}, {}
         for a, h in enumerate(hits.per_arena):
             handle = handle_of(a) if handle_of is not None else None
-            lo, hi, gene, n_in, n_pass, picked, st, *paired = sel.select_arena(self, a, request, handle, flags)
+            extras = {}  # (optional parts by name: the coding position of the selected rows, coding.py)
+            lo, hi, gene, n_in, n_pass, picked, st, *paired = sel.select_arena(self, a, request, handle, flags, extras=extras)
             part = dict(offsets=self.arenas[a].offsets, lengths=self.arenas[a].lengths, group=self.groups[a], pos_plus=h.pos_plus,
                         score_plus=h.score_plus, pos_minus=h.pos_minus, score_minus=h.score_minus, gene=gene, n_in=n_in, n_pass=n_pass,
                         sel=picked)
@@ -786,6 +787,8 @@ class Genome:
                 part["counts_plus"], part["sum_plus"], part["counts_minus"], part["sum_minus"] = joined[a]
             if repair is not None:
                 part["repair_plus"], part["repair_minus"] = repair[a]
+            if "coding" in extras:
+                part["coding"] = extras["coding"]
             if paired:
                 _, part["pair_n_pairs"], part["pair_list"], pst = paired[0]
                 sel.sum_stats(pair_stats, pst)

@@ -50,6 +50,11 @@ the same handle:
             pair two uint32 in the packing of sel (row | strand << 31), a then b, 0xFFFFFFFF beyond.  KP = 1..64,
             independent of K.  The top pairs may share one very good guide.
 
+Coding position (coding.py has the definition; csrc/crp_coding.h, csrc/crp_select_coding.hip): with
+coding limits a row passes for gene g only if, beyond the above, g has a coding model, the row's cut boundary (repair.py's c)
+is inside the coding sequence of g's primary transcript, its coding offset lies within the given percentages of that
+transcript's coding length, and the cut is inside enough of g's coding transcripts.  The pair selection is refused then.
+
 This module lays the genes out per arena, converts a wanted specificity into the integer bound the kernel compares,
 drives crp_select_* and turns the per-arena results into one table over the genes of the GFF.
 """
@@ -150,11 +155,18 @@ class Request:
     is the kernel's flank (None: 30).  With a limit or a flank the scan runs the repair kernel before the selection; with a
     flank the column is also fetched and the Selection carries mh and oof of its rows.  pairs (PairParams): the scan also
     selects the best pairs of every gene, right after the single guides (Selection.pairs, Selection.n_pairs);
-    pair_slice_rows: the a-rows of one work item (None: the library's default; results do not depend on it)."""
+    pair_slice_rows: the a-rows of one work item (None: the library's default; results do not depend on it).
+    coding / coding_limits (coding.Limits): the coding position of the cut (coding.py).  With either the selection sets
+    the genes' coding model and the Selection carries cds_offset, cds_length, transcripts_cut and transcripts of its rows;
+    with limits a row passes only if they hold for the gene it is selected for.  Pairs are refused with coding limits."""
 
     def __init__(self, params, annotation, slice_rows=None, gc_min=None, gc_max=None, max_run=None, max_t_run=None, max_stem=None,
-                 repair_flank=None, min_mh=None, min_oof=None, pairs=None, pair_slice_rows=None):
+                 repair_flank=None, min_mh=None, min_oof=None, pairs=None, pair_slice_rows=None, coding=False, coding_limits=None):
         self.pairs, self.pair_slice_rows = pairs, pair_slice_rows
+        self.coding_limits = coding_limits
+        self.coding = bool(coding) or coding_limits is not None
+        if coding_limits is not None and pairs is not None:
+            raise ValueError("coding limits are relative to the gene; the pair selection's eligibility is per table row: one or the other")
         from . import repair
         from .properties import Limits
         self.repair_flank = None if repair_flank is None else repair.check_flank(repair_flank)
@@ -228,6 +240,41 @@ class ArenaSelect:
                 "merged_genes")
         return dict(zip(keys, (float(v) for v in out)))
 
+    def set_coding(self, model):
+        """model: the dict of annotate.Request.coding_layout for this handle's genes, or None to clear it."""
+        if model is None:
+            nat.check(nat.lib().crp_select_set_coding(self._h, None, None, None, 0, None, None, None, 0), "crp_select_set_coding", self._ctx)
+            return
+        info, length, at, word, cum = (np.ascontiguousarray(model[key], dtype=np.uint32) for key in ("info", "length", "at", "word", "cum"))
+        first = np.ascontiguousarray(model["first"], dtype=np.uint64)
+        if first.size != info.size + 1 or length.size != info.size or not at.size == word.size == cum.size:
+            raise ValueError("a coding model has info and length per row, first with one more element, and at / word / cum per step")
+        nat.check(nat.lib().crp_select_set_coding(self._h, info.ctypes.data_as(nat.u32p), length.ctypes.data_as(nat.u32p),
+                                                  first.ctypes.data_as(nat.u64p), info.size, at.ctypes.data_as(nat.u32p),
+                                                  word.ctypes.data_as(nat.u32p), cum.ctypes.data_as(nat.u32p), at.size),
+                  "crp_select_set_coding", self._ctx)
+
+    def set_coding_limits(self, limits):
+        """limits: coding.Limits, or None to clear them."""
+        lim = None if limits is None else ctypes.byref(nat.SelectCodingLimits(*limits.astuple()))
+        nat.check(nat.lib().crp_select_set_coding_limits(self._h, lim), "crp_select_set_coding_limits", self._ctx)
+
+    def coding_eval(self, gene_row, packed_row):
+        """(off uint32, cover uint32) of the cuts of packed_row (sel's packing) for the genes gene_row of this handle;
+        off = coding.NOT_INSIDE where the cut is not inside the primary transcript's coding sequence."""
+        gene_row, packed_row = np.ascontiguousarray(gene_row, dtype=np.uint32), np.ascontiguousarray(packed_row, dtype=np.uint32)
+        if gene_row.shape != packed_row.shape or gene_row.ndim != 1:
+            raise ValueError("gene_row and packed_row must be 1-d arrays of one length")
+        off, cover = np.zeros(max(1, gene_row.size), np.uint32), np.zeros(max(1, gene_row.size), np.uint32)
+        nat.check(nat.lib().crp_select_coding_eval(self._h, gene_row.ctypes.data_as(nat.u32p), packed_row.ctypes.data_as(nat.u32p), gene_row.size,
+                                                   off.ctypes.data_as(nat.u32p), cover.ctypes.data_as(nat.u32p)), "crp_select_coding_eval", self._ctx)
+        return off[:gene_row.size], cover[:gene_row.size]
+
+    def coding_stats(self):
+        out = np.zeros(3, dtype=np.float64)
+        nat.check(nat.lib().crp_select_coding_stats(self._h, out.ctypes.data_as(nat.f64p), 3), "crp_select_coding_stats", self._ctx)
+        return dict(zip(("coding_select_ms", "coding_eval_ms", "coding_steps"), (float(v) for v in out)))
+
     def set_pair_limits(self, pair_slice_rows=0):
         nat.check(nat.lib().crp_select_set_pair_limits(self._h, int(pair_slice_rows)), "crp_select_set_pair_limits", self._ctx)
 
@@ -270,7 +317,9 @@ class Selection:
     to the contig string), with counts (n, M + 1) uint32 and hit_sum (n,) uint64 of the rows when they were joined, and
     mh / oof (n,) uint32 of the rows when the repair scores were fetched (None otherwise).  With a pair selection: pairs
     (PAIR_DTYPE, gene after gene, rank 1 first; a is the left guide), n_pairs (per gene, all qualifying pairs), pairs_stats
-    and, when the repair scores were fetched, pairs_repair (n, 2) uint64, packed, of a and b; None otherwise."""
+    and, when the repair scores were fetched, pairs_repair (n, 2) uint64, packed, of a and b; None otherwise.  With the
+    coding position (coding.py): cds_offset (coding.NOT_INSIDE where the cut is not inside the primary transcript),
+    cds_length, transcripts_cut and transcripts (n,) uint32 of the rows, for the gene each was selected for; None otherwise."""
 
     def __init__(self, labels, n_in, n_pass, rows, counts=None, hit_sum=None, stats=None, mh=None, oof=None):
         self.labels, self.n_in, self.n_pass, self.rows = labels, n_in, n_pass, rows
@@ -278,6 +327,7 @@ class Selection:
         self.mh, self.oof = mh, oof
         self.pairs = self.n_pairs = self.pairs_repair = None
         self.pairs_stats = {}
+        self.cds_offset = self.cds_length = self.transcripts_cut = self.transcripts = None
 
     def of_gene(self, g):
         return self.rows[self.rows["gene"] == g]
@@ -295,7 +345,8 @@ def assemble(labels, k, arenas, stats=None):
     """One Selection from per-arena results.  arenas: dicts with offsets / lengths (of the arena's texts), group (their
     contig indices), pos_plus / score_plus / pos_minus / score_minus (the tables, arena positions), gene (layout row ->
     gene index), n_in, n_pass, sel (layout rows x K), and optionally counts_plus / sum_plus / counts_minus / sum_minus
-    and repair_plus / repair_minus (the packed repair scores of the tables' rows).
+    and repair_plus / repair_minus (the packed repair scores of the tables' rows), and coding (dict: off and cover, layout
+    rows x K beside sel, and length and n_tx per layout row).
     A gene that has rows in several texts (two contigs of one name) gets the sums of its counts and the first K of its
     rows in the definition's order, texts in arena order."""
     G = len(labels)
@@ -303,7 +354,8 @@ def assemble(labels, k, arenas, stats=None):
     parts, cparts, sparts = [], [], []
     joined = any(a.get("counts_plus") is not None for a in arenas)
     repaired = any(a.get("repair_plus") is not None for a in arenas)
-    rparts = []
+    coded = any(a.get("coding") is not None for a in arenas)
+    rparts, kparts = [], []
     for a in arenas:
         gene = np.asarray(a["gene"], dtype=np.int64)
         np.add.at(n_in, gene, np.asarray(a["n_in"], dtype=np.int64))
@@ -337,6 +389,12 @@ def assemble(labels, k, arenas, stats=None):
             sparts.append(_take(a["sum_plus"], a["sum_minus"], minus, row, np.uint64))
         if repaired:
             rparts.append(_take(a["repair_plus"], a["repair_minus"], minus, row, np.uint64))
+        if coded:
+            cod = a["coding"]
+            kparts.append(np.stack([np.asarray(cod["off"], np.uint32).reshape(gene.size, -1)[r, c],
+                                    np.asarray(cod["length"], np.uint32)[r],
+                                    np.asarray(cod["cover"], np.uint32).reshape(gene.size, -1)[r, c],
+                                    np.asarray(cod["n_tx"], np.uint32)[r]], axis=1) if r.size else np.empty((0, 4), np.uint32))
     rows = np.concatenate(parts) if parts else np.empty(0, ROW_DTYPE)
     counts = np.concatenate(cparts) if cparts else None
     sums = np.concatenate(sparts) if sparts else None
@@ -356,7 +414,11 @@ def assemble(labels, k, arenas, stats=None):
     if packed_repair is not None:
         from .repair import unpack
         mh, oof = unpack(packed_repair[order][keep])
-    return Selection(list(labels), n_in, n_pass, rows, counts, sums, stats, mh, oof)
+    out = Selection(list(labels), n_in, n_pass, rows, counts, sums, stats, mh, oof)
+    if kparts:
+        cod = np.concatenate(kparts)[order][keep]
+        out.cds_offset, out.cds_length, out.transcripts_cut, out.transcripts = (cod[:, j].copy() for j in range(4))
+    return out
 
 
 def assemble_pairs(n_genes, kp, arenas):
@@ -425,9 +487,12 @@ def select_arena_pairs(sel, request, handle=None):
     return sel.fetch_pairs() + (sel.pairs_stats(),)
 
 
-def select_arena(genome, a, request, handle=None, flags=None):
+def select_arena(genome, a, request, handle=None, flags=None, extras=None):
     """The selection of one arena of an engine.Genome whose tables are resident: (lo, hi, gene, n_in, n_pass, sel, stats),
-    and with request.pairs one more element: (n_pass, n_pairs, pairs, pairs_stats) of the pair selection.
+    and with request.pairs one more element: (n_pass, n_pairs, pairs, pairs_stats) of the pair selection.  extras: a dict
+    that receives the optional parts by name -- with request.coding, extras["coding"] = dict(off, cover: of the selected
+    rows, beside sel; where sel has no row, coding.NOT_INSIDE and 0; length, n_tx: per layout row).  Without extras the model
+    and the limits are still set, and the selected rows are not evaluated.
     handle: the arena's search.ArenaSelfSearch after join_hits, or None."""
     lo, hi, gene = request.annotation.gene_layout(arena_layout(genome, a))
     sel = ArenaSelect(genome.arenas[a], lo, hi)
@@ -440,9 +505,24 @@ def select_arena(genome, a, request, handle=None, flags=None):
             sel.set_property_limits(request.property_limits)
         if getattr(request, "repair_limits", None) is not None:
             sel.set_repair_limits(request.repair_limits)
+        model = None
+        if getattr(request, "coding", False):
+            model = request.annotation.coding_layout(arena_layout(genome, a))
+            sel.set_coding(model)
+            if request.coding_limits is not None:
+                sel.set_coding_limits(request.coding_limits)
         sel.run(request.params, handle)
         n_in, n_pass, picked = sel.fetch()
-        out = lo, hi, gene, n_in, n_pass, picked, sel.stats()
+        stats = sel.stats()
+        if model is not None and extras is not None:
+            from .coding import NOT_INSIDE
+            r, c = np.nonzero(picked != NONE)
+            off, cover = np.full(picked.shape, NOT_INSIDE, np.uint32), np.zeros(picked.shape, np.uint32)
+            off[r, c], cover[r, c] = sel.coding_eval(r.astype(np.uint32), picked[r, c])
+            extras["coding"] = dict(off=off, cover=cover, length=model["length"], n_tx=model["info"] & np.uint32(0xFFFF))
+        if model is not None:
+            stats.update(sel.coding_stats())
+        out = lo, hi, gene, n_in, n_pass, picked, stats
         if getattr(request, "pairs", None) is not None:  # right after the single guides, on the same handle
             out += (select_arena_pairs(sel, request, handle),)
         return out

@@ -934,6 +934,61 @@ int crp_select_fetch_pairs(crp_select *select, uint32_t *n_pass, uint64_t *n_pai
  * in ms, out[6] pair evaluations (partner rows streamed), out[7] qualifying pairs.  n: how many to write (<= 8). */
 int crp_select_pairs_stats(const crp_select *select, double *out, int n);
 
+/* ---- coding position: where in the coding sequence a guide cuts (opt-in) ---------------- */
+/* crp_annotation_build also reads the `mRNA` / `transcript` rows, the Parent links and the gene rows' strand, and builds a
+ * CODING MODEL of every gene (cropsr_amd/coding.py states the definition):
+ *   transcripts  of gene G (non-empty ID): the mRNA / transcript rows on G's seqid with a Parent value equal to G's ID, each
+ *                with the CDS rows on that seqid whose Parent names its ID; plus one implicit transcript of the CDS rows
+ *                whose Parent names G itself.  Parent is a comma-separated list; links are resolved after the whole file is
+ *                read; of several rows with one ID the first owns the children; CDS rows with start > end are dropped
+ *   coding       the coding letters of a transcript are the union of its CDS rows' closed ranges (not clipped to the gene),
+ *                L_T their number; a transcript without one is not counted.  n_tx = the coding transcripts
+ *   primary P    the coding transcript with the largest L_T, on a tie the earlier row (the implicit one stands at the gene row)
+ *   no model     a strand (column 7 of the gene row) other than + or -, n_tx = 0, or L_P above 2^32 - 1
+ * Per gene of crp_annotation_genes: strand ('+', '-', or '.' for anything else), n_tx and L_P (both 0 without a model).  Any
+ * pointer may be NULL. */
+int crp_annotation_gene_coding(const crp_annotation *an, uint8_t *strand, uint32_t *n_tx, uint32_t *length);
+/* The coding model in arena positions, beside crp_annotation_gene_layout: the same entries and dec give EXACTLY the same
+ * rows in the same order.  Per row: info = n_tx | (strand '-') << 16 | (has a model) << 17, length = L_P, and first = the
+ * index of its first step; its steps end where the next row's begin (the last row's at *n_steps).  A row's steps are a
+ * function over the cut boundaries c of the arena (c lies between s[c - 1] and s[c]), clipped to the row's text:
+ *   at[k]    ascending change points; before at[0] nothing holds, step k is at[k] <= c < at[k + 1]
+ *   word[k]  cover (bits 0..15: the coding transcripts c is INSIDE -- s[c - 1] and s[c] both coding letters) |
+ *            (inside P) << 16 | (s[c] is a coding letter of P) << 17
+ *   cum[k]   P's coding letters with index below at[k], counted on the whole contig: inside step k the count below c is
+ *            cum[k] + (bit 17) * (c - at[k])
+ * A merged segment [a, b] contributes the change points a, a + 1 and b + 1; points that change nothing are left out.
+ * Capacity protocol as crp_annotation_track, for the rows and the steps at once: CRP_ERR_CAPACITY with the needed sizes in
+ * *n_rows / *n_steps.  CRP_ERR_UNSUPPORTED: a gene with more than 65 535 coding transcripts. */
+int crp_annotation_coding_layout(const crp_annotation *an, const uint64_t *entries, uint64_t n_entries, int dec, uint32_t *info,
+                                 uint32_t *length, uint64_t *first, uint64_t cap_rows, uint64_t *n_rows, uint32_t *at, uint32_t *word,
+                                 uint32_t *cum, uint64_t cap_steps, uint64_t *n_steps);
+/* The model of a crp_select handle: the arrays of crp_annotation_coding_layout for its genes, first with n_rows + 1
+ * elements (the last one n_steps).  CRP_ERR_INVALID with a crp_last_error text: n_rows is not the handle's n_genes, first
+ * does not ascend to n_steps, a row's change points do not ascend.  n_rows = 0 with NULL arrays clears the model. */
+int crp_select_set_coding(crp_select *select, const uint32_t *info, const uint32_t *length, const uint64_t *first, uint64_t n_rows,
+                          const uint32_t *at, const uint32_t *word, const uint32_t *cum, uint64_t n_steps);
+/* Coding limits: with limits set a row PASSES for gene g only if also g has a model, the row's cut -- the boundary c of
+ * crp_repair_scores, i - 3 on the '+' table and j + 6 on the '-' table, NOT the cut site that decides membership -- is
+ * inside P, min_pct L_P <= 100 off <= max_pct L_P and 100 cover >= min_transcripts_pct n_tx (64-bit integer products),
+ * where off = P's coding letters 5' of the cut in the gene's orientation: cum_P(c) for a '+' gene, L_P - cum_P(c) for a
+ * '-' gene.  Percentages 0 .. 100 with min_pct <= max_pct, else CRP_ERR_INVALID.  NULL clears the limits.  With limits
+ * and no model crp_select_run returns CRP_ERR_STATE; crp_select_run_pairs refuses coding limits (CRP_ERR_UNSUPPORTED):
+ * its eligibility key is per table row, not per gene. */
+typedef struct crp_select_coding_limits {
+    uint32_t min_pct, max_pct, min_transcripts_pct;
+} crp_select_coding_limits;
+int crp_select_set_coding_limits(crp_select *select, const crp_select_coding_limits *limits);
+/* off[q] and cover[q] of n queries (gene_row[q]: a gene of the handle; packed_row[q]: a table row in sel's packing, row |
+ * strand << 31), one kernel lane each; off = 0xFFFFFFFF where the cut is not inside P.  Needs the model and the arena's
+ * current tables, no limits and no run.  CRP_ERR_INVALID with a crp_last_error text: a gene or a row out of range
+ * (checked on the host; nothing is launched).  CRP_ERR_STATE: no model, no tables. */
+int crp_select_coding_eval(crp_select *select, const uint32_t *gene_row, const uint32_t *packed_row, uint64_t n, uint32_t *off,
+                           uint32_t *cover);
+/* out[0] ms of the select launches of the last crp_select_run that had coding limits (0: none), out[1] ms of the last
+ * crp_select_coding_eval's kernel (HIP events), out[2] the steps of the model.  n: how many to write (<= 3). */
+int crp_select_coding_stats(const crp_select *select, double *out, int n);
+
 /* ---- options -------------------------------------------------------------- */
 /* CRP_OPT_TWO_PASS (value 0/1, default 0): with 0 crp_scan_score is ONE kernel launch; the
  * table offsets come from a chained scan across workgroups inside it (decoupled look-back
