@@ -845,22 +845,35 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
         }
         __syncthreads();
         // ---- one hit per lane: extract the 30-window, score, store
-        const uint32_t n_round = hi_rank - lo_rank;
+        // A row of this round is named by a2 = 2 * (its rank - lo_rank): the byte offset of its list entry, half the
+        // distance of its position (and seed word) from the round's first row in a strand's table, a quarter of that
+        // of its score, and -- against a wave-uniform bound -- its strand.  The bound is the list offset of the first
+        // '-' row: 0 when the round begins at or above n_plus (the second strand's round, a late window of CAP ranks).
+        const uint32_t end2 = 2u * (hi_rank - lo_rank);
+        const uint32_t minus2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(2u * (n_plus > lo_rank ? n_plus - lo_rank : 0u)));
         struct Hit {
-            uint32_t e, r, seed;
+            uint32_t e, a2, seed;
+            bool plus;
             double pre, score;
         };
         // what a row needs from LDS before anything can be computed: its list entry and the four 31-bit windows
         struct Fetched {
-            uint32_t e, r, h, w, u, a;
+            uint32_t e, a2;
+            bool plus;  // computed once per row, here
+            uint32_t h, w, u, a;
         };
-        auto fetch = [&](uint32_t k) -> Fetched {  // list entry k of this round
-            Fetched f{list[k], lo_rank + k, 0, 0, 0, 0};
+        auto fetch = [&](uint32_t a2) -> Fetched {  // the row whose list entry is at byte a2 of the list
+            // ONE compare per row: the wave's mask of '+' rows, which the compiler cannot see through, so it does not
+            // make a second compare for the complement (it inverts the mask on the scalar unit where it needs that)
+            uint64_t plus_rows = __builtin_amdgcn_uicmp(a2, minus2, 36 /* ICMP_ULT */);
+            asm("" : "+s"(plus_rows));
+            Fetched f{*reinterpret_cast<const uint16_t *>(reinterpret_cast<const char *>(list) + a2), a2,
+                      __builtin_amdgcn_inverse_ballot_w64(plus_rows), 0, 0, 0, 0};
             // '+': long_sequence = T(s[i-l-5 : i+5])       (CROPSR.py:421)
             // '-': long_sequence = T(R(s[j-2 : j+l+8]))     (CROPSR.py:432)
             // PAM (l = 20): a '+' window is read from two positions earlier, so that it sits at bits 2..31 and a plain
             // v_bfrev moves it to bits 0..29 reversed -- where the '-' window is read -- with no shift after it.
-            const uint32_t q = 64u + f.e - (f.r >= n_plus ? 2u : PAM ? 27u : (uint32_t)(l + 5));
+            const uint32_t q = 64u + f.e - (f.plus ? (PAM ? 27u : (uint32_t)(l + 5)) : 2u);
             if (PAM) {
                 f.h = window32(sh[0], q);
                 f.w = window32(sh[1], q);
@@ -875,22 +888,30 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
             return f;
         };
         auto score = [&](const Fetched &f) -> Hit {
-            Hit hit{f.e, f.r, SEED_RAW_NONE, -1.0, -1.0};
-            const bool minus = hit.r >= n_plus;
+            Hit hit;
+            hit.e = f.e;
+            hit.a2 = f.a2;
+            hit.seed = SEED_RAW_NONE;
+            hit.plus = f.plus;
             // Python clamps the slice at len(s); the row is scored iff the result
             // has exactly 30 characters (CROPSR.py:458,466): for l = 20 a complete
             // window, for l > 20 a window cut to 30 by the end of the string, for
             // l < 20 never.
+            // Both the '+' orientation and the -1.0 of an unscored row are REGIONS, not selects: a 64-row chunk is of one
+            // strand except at the tile's seam, and incomplete windows are a handful per genome, so whole waves skip
+            // them (execz).  The empty asm statements keep the compiler from folding the regions back into selects that
+            // every row pays for; they emit nothing.
             if (PAM) {
                 // Both strands' windows at bits 0..29 after the orientation; bits 30 and 31 hold characters next to the
                 // window, which no gate or table index of the PAM scorer reads (gen_score_terms.py), so they stay.
                 const uint32_t u = f.u;
                 uint32_t h = f.h, w = f.w, valid = f.a | u;  // acgtACGT, U, Z
-                if (!minus) {
+                if (f.plus) {
                     // get_gRNA_sequence (CROPSR.py:128): complement upper-case bases only, then reverse.
                     h = __brev(h);
                     w = __brev(w ^ u);
                     valid = __brev(valid);
+                    asm volatile("; '+' rows oriented");
                 }
                 // void positions = h & w & ~u & ~a, oriented like the window ('+': u = 1 is valid, so w ^ u = w there)
                 const bool complete = (h & w & ~valid & 0x3fffffffu) == 0;
@@ -906,6 +927,10 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
                     const uint32_t mG = h & w, mC = h & ~w;
                     const uint32_t mT = ~h & w, mA = ~h & ~w & valid;
                     crp_score_masks<PAM>(mA, mT, mC, mG, exp_tab, score_tab, hit.pre, hit.score);
+                } else {
+                    double unscored = -1.0;
+                    asm volatile("; unscored rows" : "+v"(unscored));
+                    hit.pre = hit.score = unscored;
                 }
             } else if (l >= 20) {
                 uint32_t h = f.h, w = f.w, u = f.u, a = f.a;
@@ -916,32 +941,38 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
                 u &= 0x3fffffffu;
                 a &= 0x3fffffffu;
                 uint32_t valid = a | u;  // acgtACGT, U, Z
-                if (!minus) {
+                if (f.plus) {
                     // get_gRNA_sequence (CROPSR.py:128): complement upper-case
                     // bases only, then reverse.  Complement = flip the low code bit.
                     h = reverse30(h);
                     w = reverse30(w ^ u);
                     valid = reverse30(valid);
+                    asm volatile("; '+' rows oriented");
                 }
                 static_assert(!SEEDS || PAM, "seed words are emitted by the l = 20 variant only");
                 if (complete) {
                     const uint32_t mG = h & w & valid, mC = h & ~w & valid;
                     const uint32_t mT = ~h & w & valid, mA = ~h & ~w & valid;
                     crp_score_masks<PAM>(mA, mT, mC, mG, exp_tab, score_tab, hit.pre, hit.score);
+                } else {
+                    double unscored = -1.0;
+                    asm volatile("; unscored rows" : "+v"(unscored));
+                    hit.pre = hit.score = unscored;
                 }
+            } else {
+                hit.pre = hit.score = -1.0;  // l < 20: no row is scored
             }
             return hit;
         };
         auto store = [&](const Hit &hit) {
             const uint32_t pos = tile_pos + hit.e;
-            const int o4 = (int)(hit.r * 4u), o8 = (int)(hit.r * 8u);
-            const bool minus = hit.r >= n_plus;
+            const int o4 = (int)(4u * lo_rank + 2u * hit.a2), o8 = (int)(8u * lo_rank + 4u * hit.a2);
             // Two guarded regions, one per strand, NOT an if / else: the compiler would fold an if / else into one store
             // through a per-lane SELECTED descriptor, which no longer lives in SGPRs (a "waterfall" loop per store).
             // A 64-row chunk is of one strand except at the seam, so one of the regions is normally skipped (execz).
 #pragma unroll
             for (int st = 0; st < 2; ++st) {
-                if (minus == (st == 1)) {
+                if (hit.plus == (st == 0)) {
                     __builtin_amdgcn_raw_buffer_store_b32(pos, ts.pos[st], o4, 0, STORE_AUX);
                     __builtin_amdgcn_raw_buffer_store_b64(f64_words(hit.score), ts.score[st], o8, 0, STORE_AUX);
                     if (PRE) __builtin_amdgcn_raw_buffer_store_b64(f64_words(hit.pre), ts.pre[st], o8, 0, STORE_AUX);
@@ -956,13 +987,18 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
         // second row on a row is stored as soon as it is scored -- nothing is parked in registers.  (Issuing the next
         // row's LDS reads ahead of the current row's arithmetic was measured: +4 %, profiles/EXPERIMENTS.md.)
         auto run_rows = [&](uint32_t k, auto before_first_store) {
-            const bool any = k < n_round;
+            uint32_t a2 = 2u * k;
+            const bool any = a2 < end2;
             Hit first{};
-            if (any) first = score(fetch(k));
+            if (any) first = score(fetch(a2));
             before_first_store(any);
             if (any) {
                 store(first);
-                for (k += G::BLOCK; k < n_round; k += G::BLOCK) store(score(fetch(k)));
+                // (the loop's first offset is hidden from the compiler, which otherwise counts from the first row's and
+                // re-derives the current one on every trip: a copy and an add)
+                a2 += 2u * G::BLOCK;
+                asm("" : "+v"(a2));
+                for (; a2 < end2; a2 += 2u * G::BLOCK) store(score(fetch(a2)));
             }
         };
         if (!CHAINED) {

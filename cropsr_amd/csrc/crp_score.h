@@ -44,6 +44,17 @@ __device__ __forceinline__ double crp_tab_at(const double *tab, uint32_t base_by
 #define CRP_TERM2(acc, copy1, copy2, bit, wc) \
     acc = __builtin_fma(__hiloint2double((int)((copy1) & (copy2) & (1u << (bit))), 0), (wc), acc);
 
+// fma(a, b, c) with a wave-uniform b and a c that outlives the call (a constant of a loop): the three-address
+// v_fma_f64.  Left to itself the compiler picks the two-address v_fmac_f64 and copies c into the destination first,
+// one v_mov_b64 per call.  One scalar operand is what the constant bus allows.  Same operation, operands and
+// rounding as __builtin_fma.
+__device__ __forceinline__ double crp_fma_keep_c(double a, double b, double c)
+{
+    double d;
+    asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "s"(b), "v"(c));
+    return d;
+}
+
 // exp(x) for |x| < 512.  `tab` points at a copy of CRP_EXP_TAB (LDS).
 __device__ __forceinline__ double crp_exp(double x, const uint64_t *tab)
 {
@@ -66,8 +77,8 @@ __device__ __forceinline__ double crp_exp(double x, const uint64_t *tab)
     const double tail = __longlong_as_double((long long)tab[idx]);
     const uint64_t sbits = tab[idx + 1] + top;
     const double r2 = r * r;
-    const double p_lo = __builtin_fma(r, c3, c2);
-    const double p_hi = __builtin_fma(r, c5, c4);
+    const double p_lo = crp_fma_keep_c(r, c3, c2);
+    const double p_hi = crp_fma_keep_c(r, c5, c4);
     double tmp = __builtin_fma(r2, p_lo, tail + r);
     tmp = __builtin_fma(r2 * r2, p_hi, tmp);
     const double scale = __longlong_as_double((long long)sbits);
