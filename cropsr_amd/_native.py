@@ -53,6 +53,16 @@ class SelectCodingLimits(ctypes.Structure):
     _fields_ = [("min_pct", ctypes.c_uint32), ("max_pct", ctypes.c_uint32), ("min_transcripts_pct", ctypes.c_uint32)]
 
 
+class SelectEditWindow(ctypes.Structure):
+    """crp_select_edit_window (include/cropsr_hip.h): the base editor's window, protospacer positions from the PAM-distal end."""
+    _fields_ = [("lo", ctypes.c_uint32), ("hi", ctypes.c_uint32)]
+
+
+class SelectEditLimits(ctypes.Structure):
+    """crp_select_edit_limits (include/cropsr_hip.h): the bounds a selection puts on the stop codon a base editor writes."""
+    _fields_ = [("min_pct", ctypes.c_uint32), ("max_pct", ctypes.c_uint32), ("max_targets", ctypes.c_uint32)]
+
+
 class SelectPairParams(ctypes.Structure):
     """crp_select_pair_params (include/cropsr_hip.h): KP, the distance window, the orientation mask and frameshift of one
     crp_select_run_pairs."""
@@ -215,6 +225,9 @@ SIGNATURES = {
     "crp_select_set_coding_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "crp_select_coding_eval": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, ctypes.c_uint64, u32p, u32p]),
     "crp_select_coding_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
+    "crp_select_set_edit_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "crp_select_edit_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u32p, u32p, ctypes.c_uint64, u32p, u32p]),
+    "crp_select_edit_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_configure": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]),
     "crp_query": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     "crp_build_id": (ctypes.c_char_p, []),

@@ -1,0 +1,145 @@
+"""--base-edit / --select-stop: guides with which a cytosine base editor writes a stop codon.
+
+Not in the reference, opt-in.  The selection (select.py) designs knock-outs for a cutting Cas9: score, specificity,
+repair outcome, deletion pairs, the coding position of the cut.  A cytosine base editor (CBE) makes no cut: it deaminates
+the C's in a small window of the protospacer, which turns CAA, CAG, CGA into TAA, TAG, TGA -- or TGG into a stop from the
+other strand -- and leaves no indels (CRISPR-STOP, iSTOP).  Whether a guide does that needs the letters under its window
+(the arena's bit-planes) and their reading frame in the gene's primary transcript (coding.py's step function); the test
+of every row against the model of the gene it is being selected for runs on the device inside the selection
+(csrc/crp_edit.h, csrc/crp_select_edit.hip).  tests/base_edit_reference.py restates the definition.
+
+Definition.  The row is a row of an arena's hit tables after a scan at guide length 20.
+
+  window     Window(lo, hi), 1 <= lo <= hi <= 20, default 4..8: protospacer positions counted from the PAM-distal end.
+             Window letter p of a '+' row with match index i is the arena position x = i - 21 + p; of a '-' row (CC. at j)
+             it is x = j + 23 - p.
+  letters    a letter is a base when its `ac` bit is set; its code is (hi, lo); case is not read and U is A, as in
+             repair.py.  A position below 0, or in a plane word at or beyond the arena's word count, is a non-base and
+             is never read.
+  targets    on a '+' row the window letters that are base C: they become T.  On a '-' row the window letters that are
+             base G: they become A (the protospacer's C, read on the forward strand).  `targets` is their number, 0..20;
+             it depends on no gene.
+  codons     relative to a gene g with a coding model (coding.py: the primary transcript P, its length L_P, the gene row's
+             strand): letter x is a coding letter of P when the step function's grow bit holds at boundary x; its coding
+             index is cum_P(x) for a '+' gene and L_P - 1 - cum_P(x) for a '-' gene.  Codon q has the letters with
+             indices 3 q, 3 q + 1, 3 q + 2.  It is EVALUATED when all three indices are below L_P, its letters are three
+             adjacent arena positions and all three are bases: a codon split by an intron, clipped by the text, or a
+             trailing partial codon is not.  It is read in the gene's orientation, complemented for a '-' gene.
+  stops      the evaluated codons that are no stop (TAA, TAG, TGA) and whose edited form -- every target among their
+             letters converted -- is one.  `stop_off` is 3 q of the one with the smallest q, NO_STOP if there is none.  A gene
+             without a model has stops = 0.
+  closed     equivalently: where the edit reads C -> T in the gene's orientation, a codon CAA, CAG or CGA whose first
+  form       letter is a window letter; where it reads G -> A, TGG with its second or third letter in the window.
+  limits     Limits(min_pct=0, max_pct=100, max_targets=20): beyond select.py's predicate a row passes when stop_off is not
+             NO_STOP, min_pct L_P <= 100 stop_off <= max_pct L_P (64-bit products) and targets <= max_targets.  n_in is
+             unchanged, n_pass counts the rows that pass this too; order, ties and K are select.py's.
+
+Limits of the model: the CDS phase column is not read, split codons are skipped, CBE only (an
+adenine editor writes no stop), NGG rows only, all targets of the window convert together, one device.
+"""
+import numpy as np
+
+NO_STOP = 0xFFFFFFFF  # `stop_off` of a row whose edit writes no stop codon
+GUIDE_LEN = 20
+HEADER = ["edit_targets", "stop_codons", "stop_codon", "stop_percent"]
+STOPS = ("TAA", "TAG", "TGA")
+_BASE = {ord(c): b for c, b in zip("ACGTUacgtu", "ACGTAACGTA")}
+_COMPLEMENT = {"A": "T", "C": "G", "G": "C", "T": "A"}
+
+
+class Window:
+    """The editing window: protospacer positions lo..hi counted from the PAM-distal end, 1 <= lo <= hi <= 20."""
+
+    def __init__(self, lo=4, hi=8):
+        for name, v in (("lo", lo), ("hi", hi)):
+            if isinstance(v, bool) or int(v) != v:
+                raise ValueError("the window's %s is a protospacer position, an integer 1..%d, not %r" % (name, GUIDE_LEN, v))
+        self.lo, self.hi = int(lo), int(hi)
+        if not 1 <= self.lo <= self.hi <= GUIDE_LEN:
+            raise ValueError("the window is 1 <= lo <= hi <= %d, not %d-%d" % (GUIDE_LEN, self.lo, self.hi))
+
+    @classmethod
+    def parse(cls, text):
+        """Window from the command line's LO-HI."""
+        parts = str(text).split("-")
+        if len(parts) != 2 or not all(p.isdigit() and len(p) <= 3 for p in parts):
+            raise ValueError("a window is LO-HI, two protospacer positions 1..%d, not %r" % (GUIDE_LEN, text))
+        return cls(int(parts[0]), int(parts[1]))
+
+    def astuple(self):
+        return (self.lo, self.hi)
+
+    def __len__(self):
+        return self.hi - self.lo + 1
+
+    def positions(self, pos, minus):
+        """The arena positions of the window's letters of a row with match index pos, ascending."""
+        pos = int(pos)
+        return list(range(pos + 23 - self.hi, pos + 24 - self.lo)) if minus else list(range(pos - 21 + self.lo, pos - 20 + self.hi))
+
+
+class Limits:
+    """The bounds a selection puts on the stop codon: min_pct L_P <= 100 stop_off <= max_pct L_P (integer percentages
+    0..100) and targets <= max_targets (0..20)."""
+
+    def __init__(self, min_pct=0, max_pct=100, max_targets=GUIDE_LEN):
+        vals = []
+        for name, v, top in (("min_pct", min_pct, 100), ("max_pct", max_pct, 100), ("max_targets", max_targets, GUIDE_LEN)):
+            if isinstance(v, bool) or int(v) != v or not 0 <= int(v) <= top:
+                raise ValueError("%s is an integer 0..%d, not %r" % (name, top, v))
+            vals.append(int(v))
+        self.min_pct, self.max_pct, self.max_targets = vals
+        if self.min_pct > self.max_pct:
+            raise ValueError("min_pct %d lies above max_pct %d" % (self.min_pct, self.max_pct))
+
+    def astuple(self):
+        return (self.min_pct, self.max_pct, self.max_targets)
+
+    def passes(self, targets, stop_off, length):
+        """Boolean array from arrays: targets, stop_off (NO_STOP without a stop) and L_P."""
+        targets, stop_off, length = (np.asarray(v).astype(object) for v in (targets, stop_off, length))  # (exact integers)
+        ok = (self.min_pct * length <= 100 * stop_off) & (100 * stop_off <= self.max_pct * length) & (targets <= self.max_targets)
+        return (stop_off != NO_STOP) & ok.astype(bool)
+
+
+def outcome(text, pos, minus, window, index_of=None, length=0, gene_minus=False):
+    """(targets, stops, stop_off) of one row, by the definition's general statement.  text: the letters by arena position
+    (bytes; positions outside it are non-bases); pos, minus: the row's match index and strand; index_of: None for a gene
+    without a model, else a function from an arena position to the coding index of that letter in P, in the gene's
+    orientation, or None where the letter is no coding letter of P inside the text; length: L_P; gene_minus: the gene's
+    strand."""
+    text = bytes(text)
+    base = lambda x: _BASE.get(text[x]) if 0 <= x < len(text) else None
+    src, dst = ("G", "A") if minus else ("C", "T")
+    targets = [x for x in window.positions(pos, minus) if base(x) == src]
+    if index_of is None or not targets:
+        return len(targets), 0, NO_STOP
+    read = (lambda b: _COMPLEMENT[b]) if gene_minus else (lambda b: b)
+    found = []
+    step = -1 if gene_minus else 1
+    for x in range(min(targets, default=0) - 2, max(targets, default=-3) + 3):  # the first letter of a codon that holds a target
+        i = index_of(x)
+        if i is None or i % 3 or i + 2 >= length:
+            continue
+        xs = [x, x + step, x + 2 * step]
+        if [index_of(y) for y in xs] != [i, i + 1, i + 2] or any(base(y) is None for y in xs):
+            continue
+        before = "".join(read(base(y)) for y in xs)
+        after = "".join(read(dst if y in targets else base(y)) for y in xs)
+        if before not in STOPS and after in STOPS:
+            found.append(i)
+    return len(targets), len(found), min(found, default=NO_STOP)
+
+
+def percent(stop_off, length):
+    """stop_percent of the selection file: 100 stop_off / L_P with one decimal, as coding.percent rounds."""
+    from .coding import percent as pct
+    return pct(stop_off, length)
+
+
+def fields(targets, stops, stop_off, length):
+    """The four fields of a selection row: edit_targets, stop_codons, stop_codon (stop_off / 3 + 1) and stop_percent; the
+    last two are empty when the edit writes no stop."""
+    if int(stop_off) == NO_STOP:
+        return (int(targets), int(stops), "", "")
+    return (int(targets), int(stops), int(stop_off) // 3 + 1, percent(stop_off, length))

@@ -175,6 +175,27 @@ def build_parser():
     eng.add_argument("--select-transcripts", default=None, metavar="PCT",
                      help="with --select: only guides that cut inside the coding sequence of at least PCT %% of the gene's coding "
                           "transcripts (an integer 0..100; 100: every isoform); implies --coding")
+    eng.add_argument("--base-edit", action="store_true",
+                     help="with --select: what a cytosine base editor does under every selected guide: the C's of a window of the "
+                          "protospacer become T's, which can turn CAA, CAG, CGA or (from the other strand) TGG of the gene's longest "
+                          "coding transcript into a stop codon without a cut; every row of the selection file gets four more fields, "
+                          "edit_targets, stop_codons, stop_codon (the first one's number in the coding sequence) and stop_percent (the "
+                          "last two empty when no stop is written)")
+    eng.add_argument("--base-edit-window", default=None, metavar="LO-HI",
+                     help="with --select: the editing window in protospacer positions counted from the PAM-distal end (1..20, "
+                          "default 4-8); implies --base-edit")
+    eng.add_argument("--select-stop", action="store_true",
+                     help="with --select: only guides with which the base editor writes a stop codon into the gene's longest coding "
+                          "transcript; implies --base-edit; not together with the --select-coding filters or --select-pairs")
+    eng.add_argument("--select-stop-min", default=None, metavar="PCT",
+                     help="with --select: ... whose first stop codon lies at least PCT %% of the coding length from its start (an "
+                          "integer 0..100); implies --select-stop")
+    eng.add_argument("--select-stop-max", default=None, metavar="PCT",
+                     help="with --select: ... and at most PCT %% of the coding length from its start (an integer 0..100); implies "
+                          "--select-stop")
+    eng.add_argument("--select-max-edit-targets", default=None, metavar="N",
+                     help="with --select: ... and whose window holds at most N letters the editor converts (0..20: bystander "
+                          "edits); implies --select-stop")
     eng.add_argument("--repair-flank", default=None, metavar="F",
                      help="with --repair-scores or a repair filter: letters looked at on either side of the cut (2..32, default 30)")
     eng.add_argument("--select-min-oof", default=None, metavar="PCT",
@@ -586,7 +607,10 @@ def select_request(args, spec, world=1):
                                    ("--repair-scores", "repair_scores", False), ("--repair-flank", "repair_flank", None),
                                    ("--select-min-oof", "select_min_oof", None), ("--select-min-mh", "select_min_mh", None),
                                    ("--coding", "coding", False), ("--select-coding-min", "select_coding_min", None),
-                                   ("--select-coding-max", "select_coding_max", None), ("--select-transcripts", "select_transcripts", None))
+                                   ("--select-coding-max", "select_coding_max", None), ("--select-transcripts", "select_transcripts", None),
+                                   ("--base-edit", "base_edit", False), ("--base-edit-window", "base_edit_window", None),
+                                   ("--select-stop", "select_stop", False), ("--select-stop-min", "select_stop_min", None),
+                                   ("--select-stop-max", "select_stop_max", None), ("--select-max-edit-targets", "select_max_edit_targets", None))
              if getattr(args, k, unset) not in (unset, None)]
     KP = getattr(args, "select_pairs", None)
     pair_given = [o for o, k, unset in (("--pairs-min-distance", "pairs_min_distance", None), ("--pairs-max-distance", "pairs_max_distance", None),
@@ -676,6 +700,41 @@ def select_request(args, spec, world=1):
         from . import coding
         coding_args = dict(coding=True, coding_limits=coding.Limits(pct.get("select_coding_min", 0), pct.get("select_coding_max", 100),
                                                                     pct.get("select_transcripts", 0)) if pct else None)
+    # base editing: a window LO-HI, percentages, a count 0..20; the limits are relative to the gene and a kernel of their own, so
+    # neither with pairs nor with the coding filters
+    from . import baseedit
+    window = None
+    if getattr(args, "base_edit_window", None) is not None:
+        try:
+            window = baseedit.Window.parse(args.base_edit_window)
+        except ValueError as e:
+            refuse("--base-edit-window: " + str(e))
+    stop = {}
+    for opt, key, top, what in (("--select-stop-min", "select_stop_min", 100, "a percentage, an integer 0..100"),
+                                ("--select-stop-max", "select_stop_max", 100, "a percentage, an integer 0..100"),
+                                ("--select-max-edit-targets", "select_max_edit_targets", baseedit.GUIDE_LEN, "a number of letters 0..20")):
+        v = getattr(args, key, None)
+        if v is not None:
+            if integer(v) is None or integer(v) > top:
+                refuse("%s is %s, not %s" % (opt, what, v))
+            stop[key] = (opt, integer(v))
+    if "select_stop_min" in stop and "select_stop_max" in stop and stop["select_stop_min"][1] > stop["select_stop_max"][1]:
+        refuse("--select-stop-min %d lies above --select-stop-max %d" % (stop["select_stop_min"][1], stop["select_stop_max"][1]))
+    stop_limit = ([o for o, _ in stop.values()] + ["--select-stop"])[0] if stop or getattr(args, "select_stop", False) else None
+    if stop_limit is not None:
+        if pct:
+            refuse("%s and %s: the stop-codon filter and the coding-position filter are two kernels' predicates: one or the other"
+                   % (stop_limit, [o for o, k in (("--select-coding-min", "select_coding_min"), ("--select-coding-max", "select_coding_max"),
+                                                  ("--select-transcripts", "select_transcripts")) if k in pct][0]))
+        if KP is not None:
+            refuse("%s: the stop codon is relative to the gene and the pairs' eligibility is per table row: not together with --select-pairs"
+                   % stop_limit)
+    with_edit = bool(getattr(args, "base_edit", False)) or window is not None or stop_limit is not None
+    if with_edit:  # (the keywords a select.Request only meets with base editing)
+        val = lambda key, default: stop[key][1] if key in stop else default
+        coding_args = dict(coding_args, edit_window=window or baseedit.Window(),
+                           edit_limits=baseedit.Limits(val("select_stop_min", 0), val("select_stop_max", 100),
+                                                       val("select_max_edit_targets", baseedit.GUIDE_LEN)) if stop_limit is not None else None)
     # (a flank makes the scan fetch the column: only where the file prints it, or where the filters ask for another flank than the default)
     repair_args = dict(min_mh=min_mh, min_oof=min_oof,
                        repair_flank=(repair.DEFAULT_FLANK if flank is None else flank) if with_scores else flank)
@@ -694,7 +753,7 @@ def select_request(args, spec, world=1):
             refuse("--select-pairs: " + str(e))
     return dict(params=params, output=getattr(args, "select_output", None) or (args.o + ".selected.csv"),
                 only=bool(getattr(args, "select_only", False)), limits=dict(limits, **repair_args, **coding_args), repair_scores=with_scores,
-                coding=with_coding, pairs=pairs, pairs_output=getattr(args, "pairs_output", None) or (args.o + ".pairs.csv"))
+                coding=with_coding, base_edit=with_edit, pairs=pairs, pairs_output=getattr(args, "pairs_output", None) or (args.o + ".pairs.csv"))
 
 
 def properties_request(args, world=1):
@@ -718,13 +777,15 @@ def properties_request(args, world=1):
 
 
 def write_selection(path, selection, names, strings, all_hits, guide_len, offtarget, spec_M, annotation, properties=False,
-                    repair_scores=False, coding=False):
+                    repair_scores=False, coding=False, base_edit=False):
     """The selection file: a header, then per chosen row gene, rank (1-based), passing and the main table's own fields
     for that row as rows.ContigRows builds them, without crispr_id (those ids are random per run).  Genes in GFF order;
     genes with nothing selected are left out.  Python's csv module in the main table's dialect: the file is small.
     repair_scores: two more fields at the end of every row, mh_score and oof_score (repair.fields) of selection.mh / .oof.
-    coding: five more after those, cds_offset, cds_length, cds_percent, transcripts_cut and transcripts (coding.fields)."""
+    coding: five more after those, cds_offset, cds_length, cds_percent, transcripts_cut and transcripts (coding.fields).
+    base_edit: four more after those, edit_targets, stop_codons, stop_codon and stop_percent (baseedit.fields)."""
     import csv
+    from . import baseedit
     from . import coding as cod
     from . import repair
     sel_rows = selection.rows
@@ -745,11 +806,14 @@ def write_selection(path, selection, names, strings, all_hits, guide_len, offtar
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(["gene", "rank", "passing"] + rows.HEADER[1:] + rows.extra_header(offtarget, spec_M, properties)
-                   + (repair.HEADER if repair_scores else []) + (cod.HEADER if coding else []))
+                   + (repair.HEADER if repair_scores else []) + (cod.HEADER if coding else [])
+                   + (baseedit.HEADER if base_edit else []))
         for at, (r, rest) in enumerate(zip(sel_rows, fields)):
             more = repair.fields(repair.pack(selection.mh[at], selection.oof[at])) if repair_scores else ()
             if coding:
                 more = tuple(more) + cod.fields(selection.cds_offset[at], selection.cds_length[at], selection.transcripts_cut[at], selection.transcripts[at])
+            if base_edit:
+                more = tuple(more) + baseedit.fields(selection.edit_targets[at], selection.stop_codons[at], selection.stop_offset[at], selection.cds_length[at])
             w.writerow((selection.labels[int(r["gene"])], int(r["rank"]), int(selection.n_pass[int(r["gene"])])) + tuple(rest) + tuple(more))
 
 
@@ -1062,7 +1126,7 @@ def run(args, backend=None, out=sys.stdout, group=None):
         selection = all_hits.selection
         write_selection(selecting["output"], selection, names, strings, all_hits, args.l, offtarget, None if spec is None else spec["max_mm"],
                         request.annotation if annotating else None, properties=with_properties, repair_scores=selecting["repair_scores"],
-                        coding=selecting["coding"])
+                        coding=selecting["coding"], base_edit=selecting["base_edit"])
         stages["select"] = dict(selection.stats, write_s=time.perf_counter() - t_select, genes=len(selection.labels),
                                 rows_selected=int(selection.rows.size), k=selecting["params"].k)
         if selecting["pairs"] is not None:

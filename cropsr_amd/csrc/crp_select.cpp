@@ -12,6 +12,7 @@
 #include "crp_search_self.h"
 #include "crp_select.h"
 #include "crp_select_coding.h"
+#include "crp_select_edit.h"
 
 struct crp_select {
     crp_arena *arena = nullptr;
@@ -65,6 +66,11 @@ struct crp_select {
     uint32_t *d_eval[4] = {};
     uint64_t eval_cap[4] = {};
     double coding_stats[3] = {};
+    // base editing: the window and the limits of the selection, and what the last launches took
+    bool have_edit_limits = false;
+    crp_select_edit_window edit_window = {4, 8};
+    crp_select_edit_limits edit_limits = {};
+    double edit_stats[3] = {};
 };
 
 namespace {
@@ -136,6 +142,16 @@ void fill_predicate(const crp_select *s, const crp_select_params *p, bool with_s
     pred.min_mh = s->repair_limits.min_mh;
     pred.min_oof_pct = s->repair_limits.min_oof_pct;
     *pred_out = pred;
+}
+
+// A window of protospacer positions 1 <= lo <= hi <= 20 (NULL: the default, 4 .. 8).
+int check_window(crp_ctx *ctx, const crp_select_edit_window *w, const std::string &who, crp::EditWindow *out)
+{
+    *out = w ? crp::EditWindow{w->lo, w->hi} : crp::EditWindow{4u, 8u};
+    if (out->lo < 1u || out->lo > out->hi || out->hi > crp::EDIT_GUIDE_LEN)
+        return fail(ctx, CRP_ERR_INVALID, who + ": the window is 1 <= lo <= hi <= 20 in protospacer positions, not " + std::to_string(out->lo) +
+                                              " and " + std::to_string(out->hi));
+    return CRP_OK;
 }
 
 }  // namespace
@@ -256,7 +272,13 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
     if (rc != CRP_OK) return rc;
     if (s->have_coding_limits && !s->have_coding)
         return fail(ctx, CRP_ERR_STATE, "crp_select_run: coding limits need the model of a crp_select_set_coding");
+    if (s->have_edit_limits && s->have_coding_limits)
+        return fail(ctx, CRP_ERR_UNSUPPORTED, "crp_select_run: edit limits and coding limits are two kernels' predicates: clear one of them "
+                                              "(crp_select_set_coding_limits(select, NULL) or crp_select_set_edit_limits(select, NULL, NULL))");
+    if (s->have_edit_limits && !s->have_coding)
+        return fail(ctx, CRP_ERR_STATE, "crp_select_run: edit limits need the model of a crp_select_set_coding");
     s->coding_stats[0] = 0;
+    s->edit_stats[0] = 0;
     CRP_HIP(ctx, hipSetDevice(ctx->device));
     const int k = p->k;
     const uint64_t G = s->n_genes;
@@ -327,11 +349,18 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
     fill_predicate(s, p, self != nullptr, joined, k, tab, &pred);
     const crp::SelectCoding coding = {s->d_cod[0], s->d_cod[1], s->d_cod[2], s->d_cod[3], s->d_cod[4], s->d_cod[5]};
     const crp::CodingLimits coding_lim = {s->coding_limits.min_pct, s->coding_limits.max_pct, s->coding_limits.min_transcripts_pct};
+    const crp::EditPlanes edit_planes = {a->d_plane[0], a->d_plane[1], a->d_plane[3], a->padded_words};
+    const crp::EditWindow edit_win = {s->edit_window.lo, s->edit_window.hi};
+    const crp::EditLimits edit_lim = {s->edit_limits.min_pct, s->edit_limits.max_pct, s->edit_limits.max_targets};
+    if (s->have_edit_limits) s->edit_stats[2] = (double)(edit_win.hi - edit_win.lo + 1u);
     // the bounded-launch rule: at most 2^20 items a launch, each timed on its own
     for (uint64_t first = 0; first < items.size(); first += crp::SELECT_MAX_ITEMS) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(crp::SELECT_MAX_ITEMS, items.size() - first);
         CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
-        if (s->have_coding_limits)
+        if (s->have_edit_limits)
+            CRP_HIP(ctx, crp::launch_select_items_edit(ctx->stream, tab[0], tab[1], pred, coding, edit_planes, edit_win, edit_lim, s->d_items + first, n,
+                                                       s->part, s->res));
+        else if (s->have_coding_limits)
             CRP_HIP(ctx, crp::launch_select_items_coding(ctx->stream, tab[0], tab[1], pred, coding, coding_lim, s->d_items + first, n, s->part, s->res));
         else
             CRP_HIP(ctx, crp::launch_select_items(ctx->stream, tab[0], tab[1], pred, s->d_items + first, n, s->part, s->res));
@@ -339,6 +368,7 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
         CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
         const double ms = elapsed(s->ev[0], s->ev[1]);
         if (s->have_coding_limits) s->coding_stats[0] += ms;
+        if (s->have_edit_limits) s->edit_stats[0] += ms;
         s->stats[1] += ms;
         s->stats[4] += 1;
         s->stats[5] = std::max(s->stats[5], ms);
@@ -412,6 +442,9 @@ int crp_select_run_pairs(crp_select *s, const crp_select_params *p, const crp_se
     if (s->have_coding_limits)
         return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": coding limits are relative to the gene and the pairs' eligibility key is per table row: "
                                                     "clear them (crp_select_set_coding_limits(select, NULL)) for a pair selection");
+    if (s->have_edit_limits)
+        return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": edit limits are relative to the gene and the pairs' eligibility key is per table row: "
+                                                    "clear them (crp_select_set_edit_limits(select, NULL, NULL)) for a pair selection");
     crp::SelfJoined joined = {};
     int rc = check_run(s, p, self, &joined, who.c_str());
     if (rc != CRP_OK) return rc;
@@ -660,6 +693,76 @@ int crp_select_coding_stats(const crp_select *s, double *out, int n)
 {
     if (!s || (n && !out) || n < 0 || n > 3) return CRP_ERR_INVALID;
     for (int k = 0; k < n; ++k) out[k] = s->coding_stats[k];
+    return CRP_OK;
+}
+
+/* ---- base editing ---- */
+
+int crp_select_set_edit_limits(crp_select *s, const crp_select_edit_window *window, const crp_select_edit_limits *limits)
+{
+    if (!s) return CRP_ERR_INVALID;
+    if (!limits) {
+        s->have_edit_limits = false;
+        s->edit_limits = crp_select_edit_limits{};
+        return CRP_OK;
+    }
+    crp::EditWindow w;
+    const int rc = check_window(s->ctx, window, "crp_select_set_edit_limits", &w);
+    if (rc != CRP_OK) return rc;
+    if (limits->min_pct > limits->max_pct || limits->max_pct > 100u)
+        return fail(s->ctx, CRP_ERR_INVALID, "crp_select_set_edit_limits: percentages 0..100 with min_pct <= max_pct, not " +
+                                                 std::to_string(limits->min_pct) + " and " + std::to_string(limits->max_pct));
+    s->edit_window = crp_select_edit_window{w.lo, w.hi};
+    s->edit_limits = *limits;
+    s->have_edit_limits = true;
+    return CRP_OK;
+}
+
+int crp_select_edit_eval(crp_select *s, const crp_select_edit_window *window, const uint32_t *gene_row, const uint32_t *packed_row, uint64_t n,
+                         uint32_t *counts, uint32_t *stop_off)
+{
+    if (!s || (n && (!gene_row || !packed_row || !counts || !stop_off)) || n > 0x7fffffffull) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    crp_arena *a = s->arena;
+    const std::string who = "crp_select_edit_eval";
+    crp::EditWindow w;
+    int rc = check_window(ctx, window, who, &w);
+    if (rc != CRP_OK) return rc;
+    if (!s->have_coding) return fail(ctx, CRP_ERR_STATE, who + ": the handle has no model (crp_select_set_coding)");
+    if (!a->have_hits || a->pend_guide_len != (int)crp::EDIT_GUIDE_LEN)
+        return fail(ctx, CRP_ERR_STATE, who + ": the arena has no hit tables of guide length 20 (the window counts protospacer positions of 20)");
+    for (uint64_t q = 0; q < n; ++q) {
+        if (gene_row[q] >= s->n_genes)
+            return fail(ctx, CRP_ERR_INVALID, who + ": query " + std::to_string(q) + " names gene " + std::to_string(gene_row[q]) + " of " + std::to_string(s->n_genes));
+        if ((packed_row[q] & 0x7FFFFFFFu) >= a->n_hits[packed_row[q] >> 31])
+            return fail(ctx, CRP_ERR_INVALID, who + ": query " + std::to_string(q) + " names a row outside its table");
+    }
+    s->edit_stats[1] = 0;
+    if (!n) return CRP_OK;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    for (int j = 0; j < 4 && rc == CRP_OK; ++j) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_eval[j]), &s->eval_cap[j], n, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::staged_h2d(ctx, s->d_eval[0], gene_row, n * sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::staged_h2d(ctx, s->d_eval[1], packed_row, n * sizeof(uint32_t));
+    if (rc != CRP_OK) return rc;
+    const crp::SelectCoding coding = {s->d_cod[0], s->d_cod[1], s->d_cod[2], s->d_cod[3], s->d_cod[4], s->d_cod[5]};
+    const crp::EditPlanes planes = {a->d_plane[0], a->d_plane[1], a->d_plane[3], a->padded_words};
+    CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    CRP_HIP(ctx, crp::launch_edit_eval(ctx->stream, a->d_pos[0], a->d_pos[1], coding, planes, w, s->d_eval[0], s->d_eval[1], (uint32_t)n, s->d_eval[2],
+                                       s->d_eval[3]));
+    CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+    rc = crp::staged_d2h(ctx, counts, s->d_eval[2], n * sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::staged_d2h(ctx, stop_off, s->d_eval[3], n * sizeof(uint32_t));
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s->edit_stats[1] = elapsed(s->ev[0], s->ev[1]);
+    s->edit_stats[2] = (double)(w.hi - w.lo + 1u);
+    return CRP_OK;
+}
+
+int crp_select_edit_stats(const crp_select *s, double *out, int n)
+{
+    if (!s || (n && !out) || n < 0 || n > 3) return CRP_ERR_INVALID;
+    for (int k = 0; k < n; ++k) out[k] = s->edit_stats[k];
     return CRP_OK;
 }
 

@@ -789,6 +789,8 @@ class Genome:
                 part["repair_plus"], part["repair_minus"] = repair[a]
             if "coding" in extras:
                 part["coding"] = extras["coding"]
+            if "edit" in extras:
+                part["edit"] = extras["edit"]
             if paired:
                 _, part["pair_n_pairs"], part["pair_list"], pst = paired[0]
                 sel.sum_stats(pair_stats, pst)

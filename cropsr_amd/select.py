@@ -55,6 +55,11 @@ coding limits a row passes for gene g only if, beyond the above, g has a coding 
 is inside the coding sequence of g's primary transcript, its coding offset lies within the given percentages of that
 transcript's coding length, and the cut is inside enough of g's coding transcripts.  The pair selection is refused then.
 
+Base editing (baseedit.py has the definition; csrc/crp_edit.h, csrc/crp_select_edit.hip): with edit
+limits a row passes for gene g only if, beyond the above, a cytosine base editor turns a codon of g's primary transcript
+under the row's window into a stop, the codon lies within the given percentages of that transcript's coding length and
+the window holds no more than the given number of targets.  Not together with coding limits or the pair selection.
+
 This module lays the genes out per arena, converts a wanted specificity into the integer bound the kernel compares,
 drives crp_select_* and turns the per-arena results into one table over the genes of the GFF.
 """
@@ -158,11 +163,25 @@ class Request:
     pair_slice_rows: the a-rows of one work item (None: the library's default; results do not depend on it).
     coding / coding_limits (coding.Limits): the coding position of the cut (coding.py).  With either the selection sets
     the genes' coding model and the Selection carries cds_offset, cds_length, transcripts_cut and transcripts of its rows;
-    with limits a row passes only if they hold for the gene it is selected for.  Pairs are refused with coding limits."""
+    with limits a row passes only if they hold for the gene it is selected for.  Pairs are refused with coding limits.
+    edit_window / edit_limits (baseedit.Window, baseedit.Limits): base editing (baseedit.py).  With either the selection
+    sets the genes' coding model and the Selection carries edit_targets, stop_codons, stop_offset and cds_length of its
+    rows (the window defaults to 4..8); with limits a row passes only if the edit writes a stop codon inside them for the
+    gene it is selected for.  Edit limits are refused with coding limits and with pairs."""
 
     def __init__(self, params, annotation, slice_rows=None, gc_min=None, gc_max=None, max_run=None, max_t_run=None, max_stem=None,
-                 repair_flank=None, min_mh=None, min_oof=None, pairs=None, pair_slice_rows=None, coding=False, coding_limits=None):
+                 repair_flank=None, min_mh=None, min_oof=None, pairs=None, pair_slice_rows=None, coding=False, coding_limits=None,
+                 edit_window=None, edit_limits=None):
         self.pairs, self.pair_slice_rows = pairs, pair_slice_rows
+        self.edit = edit_window is not None or edit_limits is not None
+        self.edit_window, self.edit_limits = edit_window, edit_limits
+        if self.edit and edit_window is None:
+            from .baseedit import Window
+            self.edit_window = Window()
+        if edit_limits is not None and coding_limits is not None:
+            raise ValueError("edit limits and coding limits are two kernels' predicates: one or the other")
+        if edit_limits is not None and pairs is not None:
+            raise ValueError("edit limits are relative to the gene; the pair selection's eligibility is per table row: one or the other")
         self.coding_limits = coding_limits
         self.coding = bool(coding) or coding_limits is not None
         if coding_limits is not None and pairs is not None:
@@ -275,6 +294,30 @@ class ArenaSelect:
         nat.check(nat.lib().crp_select_coding_stats(self._h, out.ctypes.data_as(nat.f64p), 3), "crp_select_coding_stats", self._ctx)
         return dict(zip(("coding_select_ms", "coding_eval_ms", "coding_steps"), (float(v) for v in out)))
 
+    def set_edit_limits(self, window=None, limits=None):
+        """window: baseedit.Window (None: 4..8); limits: baseedit.Limits, or None to clear them."""
+        win = None if window is None else ctypes.byref(nat.SelectEditWindow(*window.astuple()))
+        lim = None if limits is None else ctypes.byref(nat.SelectEditLimits(*limits.astuple()))
+        nat.check(nat.lib().crp_select_set_edit_limits(self._h, win, lim), "crp_select_set_edit_limits", self._ctx)
+
+    def edit_eval(self, window, gene_row, packed_row):
+        """(targets, stops, stop_off), uint32 each, of the rows packed_row (sel's packing) for the genes gene_row of this
+        handle under window (baseedit.Window; None: 4..8); stop_off = baseedit.NO_STOP where the edit writes no stop."""
+        gene_row, packed_row = np.ascontiguousarray(gene_row, dtype=np.uint32), np.ascontiguousarray(packed_row, dtype=np.uint32)
+        if gene_row.shape != packed_row.shape or gene_row.ndim != 1:
+            raise ValueError("gene_row and packed_row must be 1-d arrays of one length")
+        win = None if window is None else ctypes.byref(nat.SelectEditWindow(*window.astuple()))
+        counts, off = np.zeros(max(1, gene_row.size), np.uint32), np.zeros(max(1, gene_row.size), np.uint32)
+        nat.check(nat.lib().crp_select_edit_eval(self._h, win, gene_row.ctypes.data_as(nat.u32p), packed_row.ctypes.data_as(nat.u32p), gene_row.size,
+                                                 counts.ctypes.data_as(nat.u32p), off.ctypes.data_as(nat.u32p)), "crp_select_edit_eval", self._ctx)
+        counts = counts[:gene_row.size]
+        return counts & np.uint32(0xFF), counts >> np.uint32(8), off[:gene_row.size]
+
+    def edit_stats(self):
+        out = np.zeros(3, dtype=np.float64)
+        nat.check(nat.lib().crp_select_edit_stats(self._h, out.ctypes.data_as(nat.f64p), 3), "crp_select_edit_stats", self._ctx)
+        return dict(zip(("edit_select_ms", "edit_eval_ms", "edit_targets_window"), (float(v) for v in out)))
+
     def set_pair_limits(self, pair_slice_rows=0):
         nat.check(nat.lib().crp_select_set_pair_limits(self._h, int(pair_slice_rows)), "crp_select_set_pair_limits", self._ctx)
 
@@ -319,7 +362,9 @@ class Selection:
     (PAIR_DTYPE, gene after gene, rank 1 first; a is the left guide), n_pairs (per gene, all qualifying pairs), pairs_stats
     and, when the repair scores were fetched, pairs_repair (n, 2) uint64, packed, of a and b; None otherwise.  With the
     coding position (coding.py): cds_offset (coding.NOT_INSIDE where the cut is not inside the primary transcript),
-    cds_length, transcripts_cut and transcripts (n,) uint32 of the rows, for the gene each was selected for; None otherwise."""
+    cds_length, transcripts_cut and transcripts (n,) uint32 of the rows, for the gene each was selected for; None otherwise.
+    With base editing (baseedit.py): edit_targets, stop_codons and stop_offset (baseedit.NO_STOP where the edit writes no
+    stop) (n,) uint32 of the rows, for the gene each was selected for, and cds_length; None otherwise."""
 
     def __init__(self, labels, n_in, n_pass, rows, counts=None, hit_sum=None, stats=None, mh=None, oof=None):
         self.labels, self.n_in, self.n_pass, self.rows = labels, n_in, n_pass, rows
@@ -328,6 +373,7 @@ class Selection:
         self.pairs = self.n_pairs = self.pairs_repair = None
         self.pairs_stats = {}
         self.cds_offset = self.cds_length = self.transcripts_cut = self.transcripts = None
+        self.edit_targets = self.stop_codons = self.stop_offset = None
 
     def of_gene(self, g):
         return self.rows[self.rows["gene"] == g]
@@ -346,7 +392,8 @@ def assemble(labels, k, arenas, stats=None):
     contig indices), pos_plus / score_plus / pos_minus / score_minus (the tables, arena positions), gene (layout row ->
     gene index), n_in, n_pass, sel (layout rows x K), and optionally counts_plus / sum_plus / counts_minus / sum_minus
     and repair_plus / repair_minus (the packed repair scores of the tables' rows), and coding (dict: off and cover, layout
-    rows x K beside sel, and length and n_tx per layout row).
+    rows x K beside sel, and length and n_tx per layout row) and edit (dict: targets, stops and stop_off, layout rows x K
+    beside sel, and length per layout row).
     A gene that has rows in several texts (two contigs of one name) gets the sums of its counts and the first K of its
     rows in the definition's order, texts in arena order."""
     G = len(labels)
@@ -355,7 +402,8 @@ def assemble(labels, k, arenas, stats=None):
     joined = any(a.get("counts_plus") is not None for a in arenas)
     repaired = any(a.get("repair_plus") is not None for a in arenas)
     coded = any(a.get("coding") is not None for a in arenas)
-    rparts, kparts = [], []
+    edited = any(a.get("edit") is not None for a in arenas)
+    rparts, kparts, eparts = [], [], []
     for a in arenas:
         gene = np.asarray(a["gene"], dtype=np.int64)
         np.add.at(n_in, gene, np.asarray(a["n_in"], dtype=np.int64))
@@ -395,6 +443,10 @@ def assemble(labels, k, arenas, stats=None):
                                     np.asarray(cod["length"], np.uint32)[r],
                                     np.asarray(cod["cover"], np.uint32).reshape(gene.size, -1)[r, c],
                                     np.asarray(cod["n_tx"], np.uint32)[r]], axis=1) if r.size else np.empty((0, 4), np.uint32))
+        if edited:
+            ed = a["edit"]
+            eparts.append(np.stack([np.asarray(ed[key], np.uint32).reshape(gene.size, -1)[r, c] for key in ("targets", "stops", "stop_off")]
+                                   + [np.asarray(ed["length"], np.uint32)[r]], axis=1) if r.size else np.empty((0, 4), np.uint32))
     rows = np.concatenate(parts) if parts else np.empty(0, ROW_DTYPE)
     counts = np.concatenate(cparts) if cparts else None
     sums = np.concatenate(sparts) if sparts else None
@@ -418,6 +470,9 @@ def assemble(labels, k, arenas, stats=None):
     if kparts:
         cod = np.concatenate(kparts)[order][keep]
         out.cds_offset, out.cds_length, out.transcripts_cut, out.transcripts = (cod[:, j].copy() for j in range(4))
+    if eparts:
+        ed = np.concatenate(eparts)[order][keep]
+        out.edit_targets, out.stop_codons, out.stop_offset, out.cds_length = (ed[:, j].copy() for j in range(4))
     return out
 
 
@@ -492,7 +547,9 @@ def select_arena(genome, a, request, handle=None, flags=None, extras=None):
     and with request.pairs one more element: (n_pass, n_pairs, pairs, pairs_stats) of the pair selection.  extras: a dict
     that receives the optional parts by name -- with request.coding, extras["coding"] = dict(off, cover: of the selected
     rows, beside sel; where sel has no row, coding.NOT_INSIDE and 0; length, n_tx: per layout row).  Without extras the model
-    and the limits are still set, and the selected rows are not evaluated.
+    and the limits are still set, and the selected rows are not evaluated.  With request.edit likewise extras["edit"] =
+    dict(targets, stops, stop_off: of the selected rows, beside sel; where sel has no row, 0, 0 and baseedit.NO_STOP; length:
+    per layout row).
     handle: the arena's search.ArenaSelfSearch after join_hits, or None."""
     lo, hi, gene = request.annotation.gene_layout(arena_layout(genome, a))
     sel = ArenaSelect(genome.arenas[a], lo, hi)
@@ -506,21 +563,32 @@ def select_arena(genome, a, request, handle=None, flags=None, extras=None):
         if getattr(request, "repair_limits", None) is not None:
             sel.set_repair_limits(request.repair_limits)
         model = None
-        if getattr(request, "coding", False):
+        edit = getattr(request, "edit", False)
+        if getattr(request, "coding", False) or edit:
             model = request.annotation.coding_layout(arena_layout(genome, a))
             sel.set_coding(model)
-            if request.coding_limits is not None:
+            if getattr(request, "coding_limits", None) is not None:
                 sel.set_coding_limits(request.coding_limits)
+            if edit and request.edit_limits is not None:
+                sel.set_edit_limits(request.edit_window, request.edit_limits)
         sel.run(request.params, handle)
         n_in, n_pass, picked = sel.fetch()
         stats = sel.stats()
-        if model is not None and extras is not None:
+        if edit and extras is not None:
+            from .baseedit import NO_STOP
+            r, c = np.nonzero(picked != NONE)
+            targets, stops, stop_off = np.zeros(picked.shape, np.uint32), np.zeros(picked.shape, np.uint32), np.full(picked.shape, NO_STOP, np.uint32)
+            targets[r, c], stops[r, c], stop_off[r, c] = sel.edit_eval(request.edit_window, r.astype(np.uint32), picked[r, c])
+            extras["edit"] = dict(targets=targets, stops=stops, stop_off=stop_off, length=model["length"])
+        if edit:
+            stats.update(sel.edit_stats())
+        if getattr(request, "coding", False) and extras is not None:
             from .coding import NOT_INSIDE
             r, c = np.nonzero(picked != NONE)
             off, cover = np.full(picked.shape, NOT_INSIDE, np.uint32), np.zeros(picked.shape, np.uint32)
             off[r, c], cover[r, c] = sel.coding_eval(r.astype(np.uint32), picked[r, c])
             extras["coding"] = dict(off=off, cover=cover, length=model["length"], n_tx=model["info"] & np.uint32(0xFFFF))
-        if model is not None:
+        if getattr(request, "coding", False):
             stats.update(sel.coding_stats())
         out = lo, hi, gene, n_in, n_pass, picked, stats
         if getattr(request, "pairs", None) is not None:  # right after the single guides, on the same handle
@@ -532,7 +600,7 @@ def select_arena(genome, a, request, handle=None, flags=None, extras=None):
 
 def sum_stats(total, one):
     for key, v in one.items():
-        if key == "bytes_per_row":
+        if key in ("bytes_per_row", "edit_targets_window"):
             total[key] = v
         else:
             total[key] = max(total.get(key, 0.0), v) if key == "longest_launch_ms" else total.get(key, 0.0) + v

@@ -989,6 +989,39 @@ int crp_select_coding_eval(crp_select *select, const uint32_t *gene_row, const u
  * crp_select_coding_eval's kernel (HIP events), out[2] the steps of the model.  n: how many to write (<= 3). */
 int crp_select_coding_stats(const crp_select *select, double *out, int n);
 
+/* ---- base editing: guides that write a stop codon (opt-in) ------------------------------ */
+/* A cytosine base editor makes no cut: it converts the C's of a small window of the protospacer (cropsr_amd/baseedit.py
+ * states the definition).  Of a row of the hit tables after a scan at guide length 20:
+ *   window   protospacer positions lo .. hi counted from the PAM-distal end, 1 <= lo <= hi <= 20; letter p is the arena
+ *            position i - 21 + p of a '+' row (match index i) and j + 23 - p of a '-' row
+ *   targets  the window's letters that are base C ('+' row) or base G ('-' row): they become T resp. A.  A base has its
+ *            `ac` bit set, its code is (hi, lo); case is not read; positions outside the planes are non-bases, never read
+ *   stops    relative to gene g with a model (crp_select_set_coding): the codons of the primary transcript P -- three
+ *            adjacent arena positions, all bases, coding letters of P with indices 3 q, 3 q + 1, 3 q + 2 in the gene's
+ *            orientation -- that are no stop and become TAA, TAG or TGA when every target among their letters is converted
+ *   stop_off 3 q of the one with the smallest q, 0xFFFFFFFF if there is none; a gene without a model has stops = 0
+ * Edit limits: with limits set a row PASSES for gene g only if also the edit writes a stop, min_pct L_P <= 100 stop_off <=
+ * max_pct L_P (64-bit integer products) and targets <= max_targets.  window NULL: 4 .. 8.  limits NULL clears the limits.
+ * CRP_ERR_INVALID with a crp_last_error text: a window out of range, a percentage above 100, min_pct > max_pct.  With edit
+ * limits crp_select_run needs the model (CRP_ERR_STATE without) and refuses coding limits set at the same time
+ * (CRP_ERR_UNSUPPORTED: one kernel per predicate); crp_select_run_pairs refuses edit limits (CRP_ERR_UNSUPPORTED). */
+typedef struct crp_select_edit_window {
+    uint32_t lo, hi;
+} crp_select_edit_window;
+typedef struct crp_select_edit_limits {
+    uint32_t min_pct, max_pct, max_targets;
+} crp_select_edit_limits;
+int crp_select_set_edit_limits(crp_select *select, const crp_select_edit_window *window, const crp_select_edit_limits *limits);
+/* counts[q] = targets | stops << 8 and stop_off[q] of n queries (gene_row[q]: a gene of the handle; packed_row[q]: a table
+ * row in sel's packing), one kernel lane each.  Needs the model and the arena's current tables of guide length 20, no
+ * limits and no run.  CRP_ERR_INVALID with a crp_last_error text: a window, a gene or a row out of range (checked on the
+ * host; nothing is launched).  CRP_ERR_STATE: no model, no tables, tables of another guide length. */
+int crp_select_edit_eval(crp_select *select, const crp_select_edit_window *window, const uint32_t *gene_row, const uint32_t *packed_row,
+                         uint64_t n, uint32_t *counts, uint32_t *stop_off);
+/* out[0] ms of the select launches of the last crp_select_run that had edit limits (0: none), out[1] ms of the last
+ * crp_select_edit_eval's kernel (HIP events), out[2] the letters of the window last used.  n: how many to write (<= 3). */
+int crp_select_edit_stats(const crp_select *select, double *out, int n);
+
 /* ---- options -------------------------------------------------------------- */
 /* CRP_OPT_TWO_PASS (value 0/1, default 0): with 0 crp_scan_score is ONE kernel launch; the
  * table offsets come from a chained scan across workgroups inside it (decoupled look-back
