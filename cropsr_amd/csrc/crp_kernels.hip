@@ -23,8 +23,10 @@
 // ascending arena position per strand (offsets from a chained scan across tiles, or
 // from the count / scan passes): bitwise reproducible, identical to the reference's row order.
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
+#include <tuple>
 #include <type_traits>
 
 #include "crp_kernels.h"
@@ -433,9 +435,8 @@ __device__ __forceinline__ void lookback_publish(uint64_t *desc, uint32_t tile, 
 }
 
 // lane k, slot j looks at tile base - k - 64*j; all loads in flight together
-__device__ __forceinline__ void lookback_load(const uint64_t *desc, int64_t base, uint64_t (&v)[LB_DEPTH])
+__device__ __forceinline__ void lookback_load(const uint64_t *desc, int64_t base, int lane, uint64_t (&v)[LB_DEPTH])
 {
-    const int lane = threadIdx.x & 63;
 #pragma unroll
     for (int j = 0; j < LB_DEPTH; ++j) {
         const int64_t idx = base - lane - 64 * j;
@@ -444,16 +445,16 @@ __device__ __forceinline__ void lookback_load(const uint64_t *desc, int64_t base
     }
 }
 
-// Called by ONE wave.  Returns the exclusive prefix in every lane and publishes the inclusive one.
+// Called by ONE wave (`lane`: the caller's lane index).  Returns the exclusive prefix in every lane and publishes the
+// inclusive one.
 __device__ __forceinline__ uint64_t lookback_resolve(uint64_t *desc, uint32_t tile, uint64_t total, uint32_t *fail,
-                                                     bool muted, uint32_t timeout_ticks)
+                                                     bool muted, uint32_t timeout_ticks, int lane)
 {
-    const int lane = threadIdx.x & 63;
     if (tile == 0) return 0;
     uint64_t v[LB_DEPTH];
     uint64_t excl = 0;
     int64_t base = (int64_t)tile - 1;
-    lookback_load(desc, base, v);
+    lookback_load(desc, base, lane, v);
     uint32_t spins = 0;
     uint64_t t_first_stall = 0;  // 100 MHz real-time counter at the first stalled look of this tile
     bool stalled_before = false;
@@ -514,40 +515,116 @@ __device__ __forceinline__ uint64_t lookback_resolve(uint64_t *desc, uint32_t ti
             if (found) break;
             base -= 64 * LB_DEPTH;
         }
-        lookback_load(desc, base, v);
+        lookback_load(desc, base, lane, v);
     }
     if (lane == 0 && !muted)
         __hip_atomic_store(&desc[tile], DESC_PREFIX | desc_pack(excl + total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return excl;
 }
 
-// what the single-pass mode needs inside emit_rounds
+// ---- kernel arguments read where they are used (single-launch emit kernel)
+// An argument that is first needed deep inside the kernel -- the hit tables when the store descriptors are built, the
+// chain pointers in the one wave that looks back -- would otherwise sit in SGPRs from the entry on, through the set-up
+// and the scorer's hoisted constants, and be spilled into VGPR lanes there (a VALU instruction per spill and reload).
+// Such arguments are loaded from the kernel-argument segment at the point of use instead: scalar loads from the
+// constant address space through a pointer the compiler cannot trace back to the entry, so it does not merge them
+// with the entry-time loads.  EmitKernArgs mirrors emit_kernel's parameter list: the segment holds the arguments in
+// declaration order, each at its natural alignment (EmitKernArgsMirror, behind the kernel, checks the struct against the
+// parameter list itself; the assertions here say what the late loads rely on).
+struct EmitKernArgs {
+    Planes pl;
+    uint64_t n_words_padded;
+    int l_arg;
+    const uint2 *tile_off;
+    uint64_t *chain;
+    uint64_t *chain_next;
+    HitTables out;
+    uint32_t mute_tile;
+    uint32_t timeout_ticks;
+};
+static_assert(offsetof(EmitKernArgs, chain) == offsetof(EmitKernArgs, tile_off) + sizeof(void *) &&
+                  offsetof(EmitKernArgs, chain_next) == offsetof(EmitKernArgs, chain) + sizeof(void *),
+              "the chain pointers follow tile_off");
+static_assert(offsetof(EmitKernArgs, out) == offsetof(EmitKernArgs, chain_next) + sizeof(void *) &&
+                  offsetof(EmitKernArgs, mute_tile) == offsetof(EmitKernArgs, out) + sizeof(HitTables) &&
+                  offsetof(EmitKernArgs, timeout_ticks) == offsetof(EmitKernArgs, mute_tile) + sizeof(uint32_t),
+              "the hit tables sit between chain_next and mute_tile, unpadded");
+static_assert(sizeof(HitTables) == 10 * 8 && alignof(HitTables) == 8, "ten 8-byte fields");
+static_assert(sizeof(EmitKernArgs) == sizeof(Planes) + 2 * 8 + 3 * sizeof(void *) + sizeof(HitTables) + 2 * sizeof(uint32_t),
+              "no padding but behind l_arg");
+
+typedef const EmitKernArgs __attribute__((address_space(4))) *LateArgs;
+__device__ __forceinline__ LateArgs late_args()
+{
+    LateArgs p = (LateArgs)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));  // opaque, and pinned to this point of the control flow
+    return p;
+}
+template <class T>
+__device__ __forceinline__ T late_arg(LateArgs args, size_t offset)
+{
+    return *reinterpret_cast<const T __attribute__((address_space(4))) *>(reinterpret_cast<const char __attribute__((address_space(4))) *>(args) + offset);
+}
+
+// the hit tables, field by field (scalar loads; a field that the kernel variant does not use is not loaded)
+__device__ __forceinline__ HitTables late_hit_tables(LateArgs args)
+{
+#define CRP_FIELD(f) late_arg<decltype(HitTables::f)>(args, offsetof(EmitKernArgs, out) + offsetof(HitTables, f))
+    return HitTables{CRP_FIELD(pos_plus),    CRP_FIELD(score_plus), CRP_FIELD(pre_plus), CRP_FIELD(pos_minus),
+                     CRP_FIELD(score_minus), CRP_FIELD(pre_minus),  CRP_FIELD(cap_plus), CRP_FIELD(cap_minus),
+                     CRP_FIELD(seed_plus),   CRP_FIELD(seed_minus)};
+#undef CRP_FIELD
+}
+
+// what the single-pass mode needs inside emit_rounds: no pointer travels through the set-up (the two LDS
+// addresses are constants, the chain pointers are read from the argument segment by the wave that uses them)
 struct ChainArgs {
-    uint64_t *desc;     // one descriptor per tile
-    uint32_t *fail;
-    uint64_t *totals;   // written by the last tile
     uint64_t *s_excl;   // LDS hand-over from the resolving wave to the workgroup
     uint32_t *s_flag;   // LDS: s_excl is valid
-    uint32_t tile, n_tiles;
-    uint64_t total;     // this tile's (plus | minus << 32)
-    bool muted;         // test hook: this tile publishes nothing
-    uint32_t timeout_ticks;  // look-back allowance in ticks of the 100 MHz real-time counter
+    uint32_t tile;
+    uint32_t n_plus, n_minus;  // this tile's counts
 };
 
 // ONE wave: look back, hand the tile's exclusive prefix to the workgroup through LDS, raise the flag;
-// the last tile also publishes the table totals
-__device__ __forceinline__ void chain_resolve(const ChainArgs &ch)
+// the last tile also publishes the table totals.  TILE_WORDS: the geometry's tile, of which the grid has
+// n_words_padded / TILE_WORDS (launch_emit_variant).
+// Everything the look-back derives from the tile index, the counts and the lane index -- the window's indices and
+// their range tests, the tile-0 and last-tile flags, the packed total -- is derived HERE, from copies the compiler
+// cannot trace back: it would otherwise compute them in the set-up of all eight waves and carry them, spilled, to
+// the one wave that looks back.
+template <int TILE_WORDS>
+__device__ __forceinline__ void chain_resolve(const ChainArgs &ch_in)
 {
-    const uint64_t e = lookback_resolve(ch.desc, ch.tile, ch.total, ch.fail, ch.muted, ch.timeout_ticks);
-    if ((threadIdx.x & 63) == 0) {
+    struct {
+        uint64_t *s_excl;
+        uint32_t *s_flag;
+        uint32_t tile;
+        uint64_t total;
+    } ch{ch_in.s_excl, ch_in.s_flag, ch_in.tile, 0};
+    uint32_t n_plus = ch_in.n_plus, n_minus = ch_in.n_minus;
+    int lane = threadIdx.x & 63;
+    asm volatile("" : "+s"(ch.tile), "+s"(n_plus), "+s"(n_minus), "+v"(lane));
+    ch.total = pair64(n_minus, n_plus);
+    const LateArgs args = late_args();
+    // the grid size, as launch_emit_variant computes it (emit_kernel's hit-free exit reads the same number from gridDim.x)
+    const uint32_t n_tiles = (uint32_t)(late_arg<uint64_t>(args, offsetof(EmitKernArgs, n_words_padded)) / TILE_WORDS);
+    uint64_t *const chain = late_arg<uint64_t *>(args, offsetof(EmitKernArgs, chain));
+    // (mute_tile: a test hook, the tile that publishes nothing; timeout_ticks: look-back allowance in ticks of the
+    // 100 MHz real-time counter)
+    const uint32_t mute_tile = late_arg<uint32_t>(args, offsetof(EmitKernArgs, mute_tile));
+    const uint32_t timeout_ticks = late_arg<uint32_t>(args, offsetof(EmitKernArgs, timeout_ticks));
+    uint64_t *const totals = chain + 1;  // header: unused | fail << 32, the two table totals, the host's word
+    const uint64_t e = lookback_resolve(chain + CHAIN_HEADER_WORDS, ch.tile, ch.total, reinterpret_cast<uint32_t *>(chain) + 1,
+                                        ch.tile == mute_tile, timeout_ticks, lane);
+    if (lane == 0) {
         *ch.s_excl = e;
-        if (ch.tile == ch.n_tiles - 1) {
+        if (ch.tile == n_tiles - 1) {
             const uint64_t all = e + ch.total;
-            ch.totals[0] = all & 0xffffffffull;
-            ch.totals[1] = all >> 32;
+            totals[0] = all & 0xffffffffull;
+            totals[1] = all >> 32;
             // header word 3 (set once by the host, never zeroed): a pinned host copy of the header, so that the
             // host needs no device-to-host copy between the launch and its synchronisation
-            uint64_t *const host = reinterpret_cast<uint64_t *>(ch.totals[2]);
+            uint64_t *const host = reinterpret_cast<uint64_t *>(totals[2]);
             if (host) {
                 host[1] = all & 0xffffffffull;
                 host[2] = all >> 32;
@@ -680,6 +757,8 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
 // PRE: the pre-sigmoid column is written too.  SEEDS: so is the off-target scan's raw seed word.
 // G: the tile geometry (crp_kernels.h): G::BLOCK threads on a tile of G::WORDS words, of which the first G::OWNERS threads
 //    own G::WPT words each (load them, derive their masks, build their part of the hit list); all threads score.
+// The parameter list is mirrored by EmitKernArgs (above), from whose offsets the single-launch kernel reads `out`, `chain`,
+// `n_words_padded`, `mute_tile` and `timeout_ticks` late; EmitKernArgsMirror (below the kernel) holds the two together.
 template <class G, bool CHAINED, int LFIX, bool PRE, bool SEEDS>
 __global__ __launch_bounds__(G::BLOCK) __attribute__((amdgpu_waves_per_eu(6, 8))) void emit_kernel(
     Planes pl, uint64_t n_words_padded, int l_arg, const uint2 *__restrict__ tile_off, uint64_t *chain,
@@ -751,11 +830,10 @@ __global__ __launch_bounds__(G::BLOCK) __attribute__((amdgpu_waves_per_eu(6, 8))
     uint64_t off_plus = 0, off_minus = 0;
     ChainArgs ch{};
     if (CHAINED) {
-        ch = ChainArgs{chain + CHAIN_HEADER_WORDS, reinterpret_cast<uint32_t *>(chain) + 1, chain + 1, &s_excl, &s_flag,
-                       tile, gridDim.x, total, tile == mute_tile, timeout_ticks};
+        ch = ChainArgs{&s_excl, &s_flag, tile, n_plus, n_minus};
         if (tid == 0) {
             // mute_tile (normally none): a tile that never publishes, to exercise the time-out path
-            if (tile != mute_tile) lookback_publish(ch.desc, tile, total);
+            if (tile != mute_tile) lookback_publish(chain + CHAIN_HEADER_WORDS, tile, total);
             // leave the OTHER descriptor buffer zeroed for the next launch (no memset between scans)
             chain_next[CHAIN_HEADER_WORDS + tile] = 0;
             if (tile == 0) chain_next[0] = chain_next[1] = chain_next[2] = 0;  // (word 3 is the host's)
@@ -763,8 +841,10 @@ __global__ __launch_bounds__(G::BLOCK) __attribute__((amdgpu_waves_per_eu(6, 8))
         __builtin_amdgcn_s_setprio(0);
         if (n_all == 0) {
             // nothing to store: the aggregate (0) is all later tiles need; only the last tile
-            // must still learn its prefix, to publish the totals
-            if (tile == ch.n_tiles - 1 && tid < 64) chain_resolve(ch);
+            // must still learn its prefix, to publish the totals.  (The last tile by the grid size here, by
+            // n_words_padded / TW in chain_resolve, which would carry the grid size through the set-up otherwise: one
+            // number, launch_emit_variant launches n_words_padded / G::WORDS workgroups.)
+            if (tile == gridDim.x - 1 && wave == 0) chain_resolve<TW>(ch);
             return;
         }
     } else {
@@ -797,23 +877,29 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
 {
     constexpr uint32_t CAP = G::LIST;
     const int tid = threadIdx.x;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint32_t n_all = n_plus + n_minus;
     TileStores ts;
-    bool resolved = !CHAINED;  // single pass: this wave has not picked up the tile's table offsets yet
     if (!CHAINED) tile_stores<PRE, SEEDS>(ts, out, uniform64(off_plus), uniform64(off_minus), n_plus);
     // A tile with more kept hits than the list holds takes several rounds.  When each STRAND's hits fit (the usual
     // overflow: an unmasked tile of a GC-rich genome has ~1 700 + 1 700 of them), the rounds are the two strands:
     // each round peels only its own strand's masks, without capacity tests -- one list build's work in all, not two.
-    const bool by_strand = n_all > CAP && n_plus <= CAP && n_minus <= CAP;
+    // (single launch: the round's wave-uniform flags are derived in the round, on the scalar unit, from copies of the
+    // counts that the compiler cannot trace back -- as loop invariants they are lane masks in SGPR pairs, carried
+    // through the set-up and the first row's scorer and spilled there)
     const uint32_t list_lds = (uint32_t)(uintptr_t)list;  // LDS byte address of the list
     uint32_t hi_rank = 0;
     for (uint32_t lo_rank = 0; lo_rank < n_all; lo_rank = hi_rank) {
+        uint32_t np = n_plus, nm = n_minus;
+        if (CHAINED) asm volatile("" : "+s"(np), "+s"(nm));
+        const bool over = np + nm > CAP;                     // more rounds than one
+        const bool by_strand = over && np <= CAP && nm <= CAP;
         hi_rank = by_strand ? (lo_rank == 0 ? n_plus : n_all) : min(lo_rank + CAP, n_all);
         if (lo_rank) __syncthreads();  // previous round's readers are done
         // ---- compact: rank -> tile-local position, '+' hits first, then '-'
         const uint32_t rp0 = ex_plus - lo_rank;            // window-relative rank of this thread's first '+' hit
         const uint32_t rm0 = ex_minus + (n_plus - lo_rank);  // same for '-'
-        if (n_all <= CAP || by_strand) {
+        if (!over || by_strand) {
             // every entry of this round fits: no per-entry capacity test
             const bool with_plus = !by_strand || lo_rank == 0, with_minus = !by_strand || lo_rank != 0;
             uint32_t ap = list_lds + 2 * rp0, am = list_lds + 2 * rm0;
@@ -837,9 +923,12 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
 #pragma unroll
             for (int k = 0; k < G::WPT; ++k) {
                 const uint32_t wbase = (uint32_t)(tid * G::WPT + k) * 64u;
-                for (uint64_t m = mp[k]; m; m &= m - 1, ++rp)
+                // (copies the compiler cannot trace back: the loops' entry tests stay here, off the common path)
+                uint64_t m_plus = mp[k], m_minus = mm[k];
+                if (CHAINED) asm volatile("" : "+v"(m_plus), "+v"(m_minus));
+                for (uint64_t m = m_plus; m; m &= m - 1, ++rp)
                     if (rp < CAP) list[rp] = (uint16_t)(wbase + __builtin_ctzll(m));
-                for (uint64_t m = mm[k]; m; m &= m - 1, ++rm)
+                for (uint64_t m = m_minus; m; m &= m - 1, ++rm)
                     if (rm < CAP) list[rm] = (uint16_t)(wbase + __builtin_ctzll(m));
             }
         }
@@ -851,10 +940,16 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
         // '-' row: 0 when the round begins at or above n_plus (the second strand's round, a late window of CAP ranks).
         const uint32_t end2 = 2u * (hi_rank - lo_rank);
         const uint32_t minus2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)(2u * (n_plus > lo_rank ? n_plus - lo_rank : 0u)));
+        // Single launch with the pre-sigmoid column: an unscored row's pre-sigmoid value is its score, -1.0, and is stored
+        // from the score's registers (`store`).  Kept as a second value, it is a register copy that every row runs, in
+        // the flow block between the scored and the unscored rows.  (The three-launch kernels, whose descriptors stay in
+        // SGPRs through all rounds, would spill the flag's SGPR pair: they keep the second value.)
+        constexpr bool PRE_FROM_SCORE = PRE && CHAINED;
         struct Hit {
             uint32_t e, a2, seed;
             bool plus;
-            double pre, score;
+            double pre, score;  // (pre: of a scored row only)
+            bool scored;        // PRE_FROM_SCORE: the row has a pre-sigmoid value of its own
         };
         // what a row needs from LDS before anything can be computed: its list entry and the four 31-bit windows
         struct Fetched {
@@ -889,6 +984,10 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
         };
         auto score = [&](const Fetched &f) -> Hit {
             Hit hit;
+            // (PRE_FROM_SCORE: hit.pre is set by the branches below that score a row and read for scored rows only; until
+            // then it is whatever its registers hold -- the empty asm defines it at no instruction)
+            if (PRE_FROM_SCORE) asm("" : "=v"(hit.pre));
+            hit.scored = false;
             hit.e = f.e;
             hit.a2 = f.a2;
             hit.seed = SEED_RAW_NONE;
@@ -927,10 +1026,12 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
                     const uint32_t mG = h & w, mC = h & ~w;
                     const uint32_t mT = ~h & w, mA = ~h & ~w & valid;
                     crp_score_masks<PAM>(mA, mT, mC, mG, exp_tab, score_tab, hit.pre, hit.score);
+                    hit.scored = true;
                 } else {
                     double unscored = -1.0;
                     asm volatile("; unscored rows" : "+v"(unscored));
-                    hit.pre = hit.score = unscored;
+                    hit.score = unscored;
+                    if (!PRE_FROM_SCORE) hit.pre = unscored;
                 }
             } else if (l >= 20) {
                 uint32_t h = f.h, w = f.w, u = f.u, a = f.a;
@@ -954,13 +1055,16 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
                     const uint32_t mG = h & w & valid, mC = h & ~w & valid;
                     const uint32_t mT = ~h & w & valid, mA = ~h & ~w & valid;
                     crp_score_masks<PAM>(mA, mT, mC, mG, exp_tab, score_tab, hit.pre, hit.score);
+                    hit.scored = true;
                 } else {
                     double unscored = -1.0;
                     asm volatile("; unscored rows" : "+v"(unscored));
-                    hit.pre = hit.score = unscored;
+                    hit.score = unscored;
+                    if (!PRE_FROM_SCORE) hit.pre = unscored;
                 }
             } else {
-                hit.pre = hit.score = -1.0;  // l < 20: no row is scored
+                hit.score = -1.0;  // l < 20: no row is scored
+                if (!PRE_FROM_SCORE) hit.pre = -1.0;
             }
             return hit;
         };
@@ -975,7 +1079,18 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
                 if (hit.plus == (st == 0)) {
                     __builtin_amdgcn_raw_buffer_store_b32(pos, ts.pos[st], o4, 0, STORE_AUX);
                     __builtin_amdgcn_raw_buffer_store_b64(f64_words(hit.score), ts.score[st], o8, 0, STORE_AUX);
-                    if (PRE) __builtin_amdgcn_raw_buffer_store_b64(f64_words(hit.pre), ts.pre[st], o8, 0, STORE_AUX);
+                    if (PRE && !PRE_FROM_SCORE) {
+                        __builtin_amdgcn_raw_buffer_store_b64(f64_words(hit.pre), ts.pre[st], o8, 0, STORE_AUX);
+                    } else if (PRE) {
+                        // (two regions with distinct tails, like the strands': not one store of selected data)
+                        if (hit.scored) {
+                            __builtin_amdgcn_raw_buffer_store_b64(f64_words(hit.pre), ts.pre[st], o8, 0, STORE_AUX);
+                            asm volatile("; scored rows' pre-sigmoid values stored" ::: "memory");
+                        } else {
+                            __builtin_amdgcn_raw_buffer_store_b64(f64_words(hit.score), ts.pre[st], o8, 0, STORE_AUX);
+                            asm volatile("; unscored rows' pre-sigmoid values stored" ::: "memory");
+                        }
+                    }
                     if (SEEDS) __builtin_amdgcn_raw_buffer_store_b32(hit.seed, ts.seed[st], o4, 0, STORE_AUX);
                     // (distinct tails keep the optimiser from sinking the two regions' stores into one)
                     if (st == 0) asm volatile("; '+' rows stored" ::: "memory");
@@ -1010,23 +1125,59 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
             // wave 0 that has one chunk less, not one more.
             const uint32_t k0 = (uint32_t)(tid & 63) | ((((uint32_t)tid >> 6) + (G::BLOCK / 64 - 1)) % (G::BLOCK / 64)) << 6;
             // the whole look-back BEFORE wave 0 scores anything (nothing of the scorer is live then)
-            if (lo_rank == 0 && tid < 64) chain_resolve(ch);
+            int first_wave = wave;
+            asm volatile("" : "+s"(first_wave));
+            if (lo_rank == 0 && first_wave == 0) chain_resolve<G::WORDS>(ch);
             // The other waves score their first rows meanwhile and need the offsets only to STORE them: by then
             // (one scoring iteration, ~4 us, after wave 0 started looking back) the flag is normally up.  From
             // the second iteration on a row is stored as soon as it is scored -- nothing is parked in registers.
             run_rows(k0, [&](bool any) {
-                // wave-uniform (the descriptors must stay in SGPRs): a wave with rows waits for the flag once per tile
-                if (!resolved && __ballot(any)) {
+                // wave-uniform (the descriptors must stay in SGPRs): a wave with rows waits for the flag, which is up from
+                // the tile's second round on, and builds its descriptors in every round: nothing of this is carried
+                // across the list build
+                if (__ballot(any)) {
+                    // the hit tables come from the argument segment only now (their loads fly during the wait below)
+                    const HitTables late = late_hit_tables(late_args());
                     while (__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(ch.s_flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) == 0)
                         __builtin_amdgcn_s_sleep(1);
                     const uint64_t e = uniform64(*ch.s_excl);
-                    tile_stores<PRE, SEEDS>(ts, out, e & 0xffffffffull, e >> 32, n_plus);
-                    resolved = true;
+                    tile_stores<PRE, SEEDS>(ts, late, e & 0xffffffffull, e >> 32, n_plus);
                 }
             });
         }
     }
 }
+
+// EmitKernArgs against emit_kernel's parameter list itself: the same types in the same order, and every member at the
+// offset the argument segment gives that parameter (declaration order, natural alignment).  A parameter added, removed
+// or moved without the mirror following does not compile.
+template <class F>
+struct EmitKernArgsMirror;
+template <class... A>
+struct EmitKernArgsMirror<void (*)(A...)> {
+#define CRP_MEMBERS(X) X(pl), X(n_words_padded), X(l_arg), X(tile_off), X(chain), X(chain_next), X(out), X(mute_tile), X(timeout_ticks)
+#define CRP_TYPE(m) decltype(EmitKernArgs::m)
+#define CRP_OFFSET(m) offsetof(EmitKernArgs, m)
+    static constexpr bool same_types = std::is_same<std::tuple<A...>, std::tuple<CRP_MEMBERS(CRP_TYPE)>>::value;
+    static constexpr bool same_offsets()
+    {
+        constexpr size_t member[] = {CRP_MEMBERS(CRP_OFFSET)}, size[] = {sizeof(A)...}, align[] = {alignof(A)...};
+        if (sizeof...(A) != sizeof(member) / sizeof(member[0])) return false;
+        size_t at = 0;
+        for (size_t k = 0; k < sizeof...(A); ++k) {
+            at = (at + align[k] - 1) / align[k] * align[k];
+            if (at != member[k]) return false;
+            at += size[k];
+        }
+        return at == sizeof(EmitKernArgs);
+    }
+#undef CRP_OFFSET
+#undef CRP_TYPE
+#undef CRP_MEMBERS
+};
+typedef EmitKernArgsMirror<decltype(&emit_kernel<GeoLarge, true, 20, false, false>)> EmitKernArgsCheck;
+static_assert(EmitKernArgsCheck::same_types, "EmitKernArgs: the members are emit_kernel's parameters, type for type");
+static_assert(EmitKernArgsCheck::same_offsets(), "EmitKernArgs: a member's offset is its parameter's in the argument segment");
 
 // ------------------------------------------------------------ seam 2 kernel
 // rs1_score on rows of 30 raw bytes: compare with 'A','T','C','G' exactly as
