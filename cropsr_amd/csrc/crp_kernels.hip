@@ -129,7 +129,10 @@ template <int WAVES>
 __device__ __forceinline__ TileScan block_exclusive_scan(uint32_t v16, uint32_t *wave_tot)
 {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t inc16 = wave_inclusive_scan_u32(v16);
+    uint32_t inc16 = wave_inclusive_scan_u32(v16);
+    // (hidden from the compiler, which otherwise takes the scan apart to rebuild the exclusive prefix below from its
+    // partial terms: six more adds)
+    asm("" : "+v"(inc16));
     if (lane == 63) wave_tot[wave] = inc16;
     __syncthreads();
     uint32_t base_p = 0, base_m = 0, tot_p = 0, tot_m = 0;
@@ -154,26 +157,35 @@ __device__ __forceinline__ TileScan block_exclusive_scan(uint32_t v16, uint32_t 
 // neighbours by wave shuffles of the DERIVED G / C / void masks, and the words
 // just outside the wave are two wave-uniform loads per plane.  A workgroup of eight
 // waves produces the counts of one emit tile.
-__device__ __forceinline__ void derive(uint64_t hi, uint64_t lo, uint64_t up, uint64_t ac, uint64_t &g,
-                                       uint64_t &c, uint64_t &v)
+__device__ __forceinline__ void derive_gc(uint64_t hi, uint64_t lo, uint64_t up, uint64_t ac, uint64_t &g, uint64_t &c)
 {
-    g = hi & lo & up & ac;
-    c = hi & ~lo & up & ac;
-    v = hi & lo & ~up & ~ac;
+    const uint64_t t = hi & (up & ac);  // G or C: four instructions per half-word, not six
+    g = t & lo;
+    c = t & ~lo;
 }
+// void, from `valid` = up | ac
+__device__ __forceinline__ void derive_void(uint64_t hi, uint64_t lo, uint64_t valid, uint64_t &v) { v = hi & lo & ~valid; }
 
 // Kept-hit masks of one 64-position word, from the derived G / C / void masks of the word and its neighbours:
 //   plus : (?=.GG) at i  <=>  G(i+1) & G(i+2);  keep  i - l >= 5   (CROPSR.py:419)
 //   minus: (?=CC.) at j  <=>  C(j) & C(j+1) & exists(j+2);
 //          keep  j+3 >= 5  and  j+3+l <= len+10               (CROPSR.py:430)
-// "exists" / "index >= 0" / "index < len" are void tests at fixed distances.
-__device__ __forceinline__ void masks_of(uint64_t g_c, uint64_t g_n, uint64_t c_c, uint64_t c_n, uint64_t v_p,
-                                         uint64_t v_c, uint64_t v_n, int l, uint64_t &mplus, uint64_t &mminus)
+// "exists" / "index >= 0" / "index < len" are void tests at fixed distances.  In two parts: the PAM itself, and the
+// void tests ANDed into it -- all-ones where no void bit is within their reach, so a wave without one skips them
+// (own_words_and_masks).
+__device__ __forceinline__ void pam_masks_of(uint64_t g_c, uint64_t g_n, uint64_t c_c, uint64_t c_n, uint64_t &mplus,
+                                             uint64_t &mminus)
 {
-    mplus = ahead(g_c, g_n, 1) & ahead(g_c, g_n, 2) & ~behind(v_p, v_c, l + 5);
-    uint64_t m = c_c & ahead(c_c, c_n, 1) & ~ahead(v_c, v_n, 2) & ~behind(v_p, v_c, 2);
-    if (l > 8) m &= ~ahead(v_c, v_n, l - 8);
-    mminus = m;
+    mplus = ahead(g_c, g_n, 1) & ahead(g_c, g_n, 2);
+    mminus = c_c & ahead(c_c, c_n, 1);
+}
+__device__ __forceinline__ void keep_clear_of_void(uint64_t v_p, uint64_t v_c, uint64_t v_n, int l, uint64_t &mplus,
+                                                   uint64_t &mminus)
+{
+    mplus &= ~behind(v_p, v_c, l + 5);
+    uint64_t v_near = ahead(v_c, v_n, 2) | behind(v_p, v_c, 2);
+    if (l > 8) v_near |= ahead(v_c, v_n, l - 8);
+    mminus &= ~v_near;
 }
 
 // One word of a plane at a wave-uniform index, by a scalar load (SCALAR = true).  The planes are read-only for the whole
@@ -208,12 +220,13 @@ struct EdgeWords {
 // in flight together with the lanes' own loads, whose latency covers theirs (pinning them ahead of those delays the
 // vector loads and measured +1.6 %: profiles/EXPERIMENTS.md) --, its masks are derived on the SALU, and lanes 0 / 63
 // get them as the value the wave shifts leave in the lane that has no source.  The planes are read-only for the
-// whole launch.  `edge` returns the eight words (a tile's halo is its first wave's left and its last wave's right ones).
+// whole launch.  `edge` returns the eight words (a tile's halo is its first wave's left and its last wave's right ones),
+// `valid` the own words' up | ac.
 // Must be called by whole waves.
 template <int WPT, bool SCALAR>
 __device__ __forceinline__ void own_words_and_masks(const Planes &pl, uint64_t n_words_padded, uint64_t w0, int lane, int l,
-                                                    uint64_t (&q)[4][WPT], uint64_t (&mp)[WPT], uint64_t (&mm)[WPT],
-                                                    EdgeWords &edge)
+                                                    uint64_t (&q)[4][WPT], uint64_t (&valid)[WPT], uint64_t (&mp)[WPT],
+                                                    uint64_t (&mm)[WPT], EdgeWords &edge)
 {
     static_assert(WPT == 1 || WPT == 2, "one or two words per owning lane");
     // always a word of the arena (w0 < n_words_padded), so the loads need no branch; out of range -> void below
@@ -241,20 +254,50 @@ __device__ __forceinline__ void own_words_and_masks(const Planes &pl, uint64_t n
         if (!has_left) edge.left[p] = voidw;
         if (!has_right) edge.right[p] = voidw;
     }
-    uint64_t ga, ca, va, gb, cb, vb, gl, cl, vl, gr, cr, vr;
-    derive(q[0][0], q[1][0], q[2][0], q[3][0], ga, ca, va);
-    derive(q[0][WPT - 1], q[1][WPT - 1], q[2][WPT - 1], q[3][WPT - 1], gb, cb, vb);  // (WPT = 1: the same word)
-    derive(edge.left[0], edge.left[1], edge.left[2], edge.left[3], gl, cl, vl);  // scalar; only vl is used
-    derive(edge.right[0], edge.right[1], edge.right[2], edge.right[3], gr, cr, vr);
-    // left neighbour's last word, right neighbour's first word; lanes 0 / 63 keep the word outside the wave
-    const uint64_t v_left = wave_shift<DPP_WAVE_SHR1>(vb, vl);
-    const uint64_t g_right = wave_shift<DPP_WAVE_SHL1>(ga, gr), c_right = wave_shift<DPP_WAVE_SHL1>(ca, cr),
-                   v_right = wave_shift<DPP_WAVE_SHL1>(va, vr);
+    // G and C masks of the own words and of the word to the right of the wave (scalar); the right neighbour's first
+    // word comes from the next lane, lane 63 keeps the word outside the wave
+    uint64_t ga, ca, gb, cb, gr, cr;
+    derive_gc(q[0][0], q[1][0], q[2][0], q[3][0], ga, ca);
+    derive_gc(q[0][WPT - 1], q[1][WPT - 1], q[2][WPT - 1], q[3][WPT - 1], gb, cb);  // (WPT = 1: the same word)
+    derive_gc(edge.right[0], edge.right[1], edge.right[2], edge.right[3], gr, cr);
+    const uint64_t g_right = wave_shift<DPP_WAVE_SHL1>(ga, gr), c_right = wave_shift<DPP_WAVE_SHL1>(ca, cr);
     if constexpr (WPT == 2) {
-        masks_of(ga, gb, ca, cb, v_left, va, vb, l, mp[0], mm[0]);
-        masks_of(gb, g_right, cb, c_right, va, vb, v_right, l, mp[WPT - 1], mm[WPT - 1]);
+        pam_masks_of(ga, gb, ca, cb, mp[0], mm[0]);
+        pam_masks_of(gb, g_right, cb, c_right, mp[WPT - 1], mm[WPT - 1]);
     } else {
-        masks_of(ga, g_right, ca, c_right, v_left, va, v_right, l, mp[0], mm[0]);
+        pam_masks_of(ga, g_right, ca, c_right, mp[0], mm[0]);
+    }
+    // The void tests reach at most 63 positions, so they are all-ones in a wave whose own words and two edge words hold no
+    // void bit: nearly every wave of a genome (void is word 0, the separator after a contig, its decoration and the
+    // padding).  Such a wave skips them -- deriving void, shifting it in from both neighbours, the four tests -- by one
+    // wave-uniform branch.  The test is conservative and cheap: every position of those words is a scoring base or an
+    // upper-case letter (`up | ac`, which the LDS copy's plane 3 holds anyway) -- void has neither bit.  A wave with N
+    // or another character of neither kind takes the full path, which is correct everywhere.  One compare into a lane
+    // mask, the rest on the scalar unit; beyond the arena the edge words are void (up = ac = 0).
+    valid[0] = q[2][0] | q[3][0];
+    valid[WPT - 1] = q[2][WPT - 1] | q[3][WPT - 1];
+    // (SCALAR: the lane mask of a full wave and the two edge words' bits meet in one scalar AND -- all-ones or not;
+    // otherwise the edge words are lane-held and go into the lanes' compare, whose lane mask is uniform either way)
+    const uint64_t edges_valid = (edge.left[2] | edge.left[3]) & (edge.right[2] | edge.right[3]);
+    uint64_t clear = valid[0] & valid[WPT - 1];
+    if constexpr (!SCALAR) clear &= edges_valid;
+    uint64_t lanes_clear = __builtin_amdgcn_uicmpl(clear, ALL, 32 /* ICMP_EQ */);
+    if constexpr (SCALAR) lanes_clear &= edges_valid;
+    const bool void_free = lanes_clear == ALL;
+    if (!void_free) {  // (wave-uniform: all 64 lanes are active on either side, as the wave shifts need)
+        uint64_t va, vb, vl, vr;
+        derive_void(q[0][0], q[1][0], valid[0], va);
+        derive_void(q[0][WPT - 1], q[1][WPT - 1], valid[WPT - 1], vb);
+        derive_void(edge.left[0], edge.left[1], edge.left[2] | edge.left[3], vl);  // scalar
+        derive_void(edge.right[0], edge.right[1], edge.right[2] | edge.right[3], vr);
+        // left neighbour's last word, right neighbour's first word; lanes 0 / 63 keep the word outside the wave
+        const uint64_t v_left = wave_shift<DPP_WAVE_SHR1>(vb, vl), v_right = wave_shift<DPP_WAVE_SHL1>(va, vr);
+        if constexpr (WPT == 2) {
+            keep_clear_of_void(v_left, va, vb, l, mp[0], mm[0]);
+            keep_clear_of_void(va, vb, v_right, l, mp[WPT - 1], mm[WPT - 1]);
+        } else {
+            keep_clear_of_void(v_left, va, v_right, l, mp[0], mm[0]);
+        }
     }
 }
 
@@ -272,9 +315,9 @@ __global__ __launch_bounds__(G::BLOCK) void count_kernel(Planes pl, uint64_t n_w
     uint64_t c = 0;
     const uint64_t w0 = (uint64_t)tile * G::WORDS + (uint64_t)wave * 64 * G::WPT;  // first word of this wave (uniform)
     if (wave < G::OWNERS / 64 && w0 < n_words_padded) {
-        uint64_t q[4][G::WPT], mp[G::WPT], mm[G::WPT];
+        uint64_t q[4][G::WPT], valid[G::WPT], mp[G::WPT], mm[G::WPT];
         EdgeWords edge;
-        own_words_and_masks<G::WPT, false>(pl, n_words_padded, w0, lane, l, q, mp, mm, edge);
+        own_words_and_masks<G::WPT, false>(pl, n_words_padded, w0, lane, l, q, valid, mp, mm, edge);
 #pragma unroll
         for (int k = 0; k < G::WPT; ++k) c += (uint64_t)__popcll(mp[k]) | ((uint64_t)__popcll(mm[k]) << 32);
     }
@@ -798,25 +841,27 @@ __global__ __launch_bounds__(G::BLOCK) __attribute__((amdgpu_waves_per_eu(6, 8))
     if (G::OWNERS == G::BLOCK || wave < G::OWNERS / 64) {  // (whole waves: OWNERS is a multiple of 64)
         const int lane = tid & 63;
         const uint64_t w0 = t0 + (uint64_t)(64 * G::WPT) * (uint64_t)wave;  // first word of this wave (uniform)
-        uint64_t q[4][G::WPT];
+        uint64_t q[4][G::WPT], valid[G::WPT];
         EdgeWords edge;
-        own_words_and_masks<G::WPT, CHAINED>(pl, n_words_padded, w0, lane, l, q, mp, mm, edge);
+        own_words_and_masks<G::WPT, CHAINED>(pl, n_words_padded, w0, lane, l, q, valid, mp, mm, edge);
+        // Plane 3 of the LDS copy is `up | ac`, not `ac`: its readers use it as that (a row's valid characters) or in
+        // h & w & ~u & ~a = h & w & ~(u | a) (its void ones), and the masks above have it already.
 #pragma unroll
         for (int p = 0; p < 4; ++p)
 #pragma unroll
-            for (int k = 0; k < G::WPT; ++k) sh[p][1 + G::WPT * tid + k] = q[p][k];
+            for (int k = 0; k < G::WPT; ++k) sh[p][1 + G::WPT * tid + k] = p == 3 ? valid[k] : q[p][k];
         // the tile's own halo words, for windows that reach across its ends: the first wave's left edge words and the
         // last owner wave's right ones, one lane each
         if (wave == 0) {
             if (lane == 0) {
 #pragma unroll
-                for (int p = 0; p < 4; ++p) sh[p][0] = edge.left[p];
+                for (int p = 0; p < 4; ++p) sh[p][0] = p == 3 ? edge.left[2] | edge.left[3] : edge.left[p];
             }
         }
         if (wave == G::OWNERS / 64 - 1) {
             if (lane == 63) {
 #pragma unroll
-                for (int p = 0; p < 4; ++p) sh[p][TW + 1] = edge.right[p];
+                for (int p = 0; p < 4; ++p) sh[p][TW + 1] = p == 3 ? edge.right[2] | edge.right[3] : edge.right[p];
             }
         }
     }
@@ -955,7 +1000,7 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
         struct Fetched {
             uint32_t e, a2;
             bool plus;  // computed once per row, here
-            uint32_t h, w, u, a;
+            uint32_t h, w, u, a;  // a: plane 3 of the LDS copy, up | ac
         };
         auto fetch = [&](uint32_t a2) -> Fetched {  // the row whose list entry is at byte a2 of the list
             // ONE compare per row: the wave's mask of '+' rows, which the compiler cannot see through, so it does not
@@ -1004,7 +1049,7 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
                 // Both strands' windows at bits 0..29 after the orientation; bits 30 and 31 hold characters next to the
                 // window, which no gate or table index of the PAM scorer reads (gen_score_terms.py), so they stay.
                 const uint32_t u = f.u;
-                uint32_t h = f.h, w = f.w, valid = f.a | u;  // acgtACGT, U, Z
+                uint32_t h = f.h, w = f.w, valid = f.a;  // acgtACGT, U, Z
                 if (f.plus) {
                     // get_gRNA_sequence (CROPSR.py:128): complement upper-case bases only, then reverse.
                     h = __brev(h);
@@ -1012,7 +1057,7 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
                     valid = __brev(valid);
                     asm volatile("; '+' rows oriented");
                 }
-                // void positions = h & w & ~u & ~a, oriented like the window ('+': u = 1 is valid, so w ^ u = w there)
+                // void positions = h & w & ~(u | a), oriented like the window ('+': u = 1 is valid, so w ^ u = w there)
                 const bool complete = (h & w & ~valid & 0x3fffffffu) == 0;
                 if (SEEDS) {
                     // Off-target scan (crp_offtarget.hip): seed character k (k = 0 next to the PAM) is character k of the
@@ -1034,6 +1079,8 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
                     if (!PRE_FROM_SCORE) hit.pre = unscored;
                 }
             } else if (l >= 20) {
+                // (a = up | ac here too; `~u & ~a` and `a | u` below hold as they stand and cost nothing: the OR is fused
+                // with a's AND, and without it this branch compiled to one instruction more per row)
                 uint32_t h = f.h, w = f.w, u = f.u, a = f.a;
                 const uint32_t vd = h & w & ~u & ~a;  // void positions
                 const bool complete = (vd & 0x3fffffffu) == 0 && (l == 20 || (vd >> 30));

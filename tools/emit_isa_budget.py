@@ -8,6 +8,8 @@ pre-sigmoid column, no seed words), splits it into basic blocks and prints
   row loop   the innermost loop that holds the f64 scorer: one trip through all its blocks
   set-up     every block laid out before the round loop (loads, masks, block scan, descriptors, table staging)
   rounds     the round loop outside the row loop (hit-list build, per-round and per-wave hand-over work)
+  void terms the part of the set-up that only a wave with a void bit in reach runs (the void tests of the hit masks),
+             and whether the branch around it is a scalar one
 
 as VALU / f64 / SALU instruction counts, plus the compiler's resource usage: VGPRs, SGPR spills, scratch, LDS and
 occupancy.  These are static counts: how often each block runs depends on the genome.
@@ -136,6 +138,32 @@ def counts(instrs):
     }
 
 
+def void_region(asm, name):
+    """The set-up's conditional region with the void terms of the hit masks: the basic blocks (labelled or fall-through)
+    ahead of the first loop that shift the void mask in from the left neighbour -- wave_shr:1, which nothing else in
+    the kernel uses.  `uniform`: every such block is entered past a scalar conditional branch (s_cbranch_scc / vcc on a
+    wave-uniform condition), not under an exec mask."""
+    lines = asm.splitlines()
+    start = next(i for i, l in enumerate(lines) if l.startswith(name + ":"))
+    subs = [[]]  # instructions of each basic block, in layout order
+    for l in lines[start + 1:]:
+        if l.startswith(".Lfunc_end") or "Loop Header" in l:
+            break
+        if l.startswith((".LBB", "; %bb.")):
+            subs.append([])
+            continue
+        s = l.split(";")[0].strip()
+        if s and not s.startswith(".") and not s.endswith(":"):
+            subs[-1].append(s)
+    region, uniform = [], True
+    for k, ins in enumerate(subs):
+        if any("wave_shr:1" in i for i in ins):
+            region += ins
+            last = subs[k - 1][-1] if k and subs[k - 1] else ""
+            uniform = uniform and last.startswith(("s_cbranch_scc", "s_cbranch_vcc"))
+    return dict(counts(region), uniform=bool(region) and uniform)
+
+
 def add(a, b):
     return {k: a.get(k, 0) + b[k] for k in b}
 
@@ -181,6 +209,7 @@ def budget(asm, remarks, name):
         "row_loop": row,
         "row_block": counts(scorer[3]),
         "setup": setup,
+        "setup_void": void_region(asm, name),
         "rounds": rounds,
         "whole": counts(all_ins),
         "vgprs": int(res["VGPRs"]),
@@ -213,6 +242,8 @@ def main():
         c = b[part]
         print("  %-10s VALU %4d  f64 %3d  SALU %4d  writelane %3d  readlane %3d"
               % (part, c["valu"], c["f64"], c["salu"], c["writelane"], c["readlane"]))
+    v = b["setup_void"]
+    print("  void terms VALU %4d of the set-up's, behind a %s branch" % (v["valu"], "scalar" if v["uniform"] else "NON-UNIFORM"))
     print("  VGPRs %d  SGPRs %d  SGPR spills %d  VGPR spills %d  scratch %d B  LDS %d B  occupancy %d waves/SIMD"
           % (b["vgprs"], b["sgprs"], b["sgpr_spills"], b["vgpr_spills"], b["scratch"], b["lds"], b["occupancy"]))
 
