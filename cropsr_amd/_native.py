@@ -63,6 +63,12 @@ class SelectEditLimits(ctypes.Structure):
     _fields_ = [("min_pct", ctypes.c_uint32), ("max_pct", ctypes.c_uint32), ("max_targets", ctypes.c_uint32)]
 
 
+class SelectSpliceLimits(ctypes.Structure):
+    """crp_select_splice_limits (include/cropsr_hip.h): the bounds a selection puts on the splice site a base editor destroys;
+    kinds: CRP_SPLICE_DONOR (1) | CRP_SPLICE_ACCEPTOR (2)."""
+    _fields_ = [("min_pct", ctypes.c_uint32), ("max_pct", ctypes.c_uint32), ("max_targets", ctypes.c_uint32), ("kinds", ctypes.c_uint32)]
+
+
 class SelectPairParams(ctypes.Structure):
     """crp_select_pair_params (include/cropsr_hip.h): KP, the distance window, the orientation mask and frameshift of one
     crp_select_run_pairs."""
@@ -228,6 +234,9 @@ SIGNATURES = {
     "crp_select_set_edit_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "crp_select_edit_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u32p, u32p, ctypes.c_uint64, u32p, u32p]),
     "crp_select_edit_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
+    "crp_select_set_splice_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    "crp_select_splice_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, u32p, u32p, ctypes.c_uint64, u32p, u32p]),
+    "crp_select_splice_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_configure": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int64]),
     "crp_query": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]),
     "crp_build_id": (ctypes.c_char_p, []),

@@ -196,6 +196,25 @@ def build_parser():
     eng.add_argument("--select-max-edit-targets", default=None, metavar="N",
                      help="with --select: ... and whose window holds at most N letters the editor converts (0..20: bystander "
                           "edits); implies --select-stop")
+    eng.add_argument("--base-editor", default=None, metavar="cbe|abe",
+                     help="with --select: the base editor of the splice-site test: cbe (cytosine, C -> T; the default) or abe "
+                          "(adenine, A -> G); abe writes no stop codon, so not together with --base-edit or the --select-stop options")
+    eng.add_argument("--splice-edit", action="store_true",
+                     help="with --select: what the base editor does to the splice sites of the gene's longest coding transcript under "
+                          "every selected guide: a converted letter in the GT that opens an intron or the AG that closes it destroys the "
+                          "site without a cut; every row of the selection file gets four more fields, splice_targets, splice_sites, "
+                          "donor_percent and acceptor_percent (the coding letters 5' of the intron in percent of the coding length; "
+                          "empty without a destroyed site of that kind); window: --base-edit-window")
+    eng.add_argument("--select-splice", nargs="?", const="any", default=None, metavar="donor|acceptor|any",
+                     help="with --select: only guides with which the base editor destroys a canonical splice site of that kind "
+                          "(default any) of the gene's longest coding transcript; implies --splice-edit; with the --select-stop "
+                          "options as well a guide passes by either test; not together with the --select-coding filters or --select-pairs")
+    eng.add_argument("--select-splice-min", default=None, metavar="PCT",
+                     help="with --select: ... whose intron lies behind at least PCT %% of the coding length (an integer 0..100); "
+                          "implies --select-splice")
+    eng.add_argument("--select-splice-max", default=None, metavar="PCT",
+                     help="with --select: ... and behind at most PCT %% of the coding length (an integer 0..100); implies --select-splice; "
+                          "--select-max-edit-targets bounds the window's converted letters of this test too")
     eng.add_argument("--repair-flank", default=None, metavar="F",
                      help="with --repair-scores or a repair filter: letters looked at on either side of the cut (2..32, default 30)")
     eng.add_argument("--select-min-oof", default=None, metavar="PCT",
@@ -610,7 +629,10 @@ def select_request(args, spec, world=1):
                                    ("--select-coding-max", "select_coding_max", None), ("--select-transcripts", "select_transcripts", None),
                                    ("--base-edit", "base_edit", False), ("--base-edit-window", "base_edit_window", None),
                                    ("--select-stop", "select_stop", False), ("--select-stop-min", "select_stop_min", None),
-                                   ("--select-stop-max", "select_stop_max", None), ("--select-max-edit-targets", "select_max_edit_targets", None))
+                                   ("--select-stop-max", "select_stop_max", None), ("--select-max-edit-targets", "select_max_edit_targets", None),
+                                   ("--base-editor", "base_editor", None), ("--splice-edit", "splice_edit", False),
+                                   ("--select-splice", "select_splice", None), ("--select-splice-min", "select_splice_min", None),
+                                   ("--select-splice-max", "select_splice_max", None))
              if getattr(args, k, unset) not in (unset, None)]
     KP = getattr(args, "select_pairs", None)
     pair_given = [o for o, k, unset in (("--pairs-min-distance", "pairs_min_distance", None), ("--pairs-max-distance", "pairs_max_distance", None),
@@ -720,7 +742,43 @@ def select_request(args, spec, world=1):
             stop[key] = (opt, integer(v))
     if "select_stop_min" in stop and "select_stop_max" in stop and stop["select_stop_min"][1] > stop["select_stop_max"][1]:
         refuse("--select-stop-min %d lies above --select-stop-max %d" % (stop["select_stop_min"][1], stop["select_stop_max"][1]))
+    # splice-site editing: the editor's name, a kind, percentages; --select-max-edit-targets bounds both tests, and next to a
+    # splice limit it no longer asks for the stop test by itself
+    editor = None
+    if getattr(args, "base_editor", None) is not None:
+        try:
+            editor = baseedit.Editor(args.base_editor)
+        except ValueError:
+            refuse("--base-editor is cbe or abe, not %s" % args.base_editor)
+    splice = {}
+    kind = getattr(args, "select_splice", None)
+    if kind is not None and kind not in baseedit.KINDS:
+        refuse("--select-splice is donor, acceptor or any, not %s" % kind)
+    for opt, key in (("--select-splice-min", "select_splice_min"), ("--select-splice-max", "select_splice_max")):
+        v = getattr(args, key, None)
+        if v is not None:
+            if integer(v) is None or integer(v) > 100:
+                refuse("%s is a percentage, an integer 0..100, not %s" % (opt, v))
+            splice[key] = (opt, integer(v))
+    if "select_splice_min" in splice and "select_splice_max" in splice and splice["select_splice_min"][1] > splice["select_splice_max"][1]:
+        refuse("--select-splice-min %d lies above --select-splice-max %d" % (splice["select_splice_min"][1], splice["select_splice_max"][1]))
+    splice_limit = ([o for o, _ in splice.values()] + ["--select-splice"])[0] if splice or kind is not None else None
+    max_targets = stop.get("select_max_edit_targets", (None, baseedit.GUIDE_LEN))[1]
+    if splice_limit is not None and not getattr(args, "select_stop", False) and "select_stop_min" not in stop and "select_stop_max" not in stop:
+        stop = {}
     stop_limit = ([o for o, _ in stop.values()] + ["--select-stop"])[0] if stop or getattr(args, "select_stop", False) else None
+    if editor is not None and editor.name == "abe":
+        if getattr(args, "base_edit", False) or stop_limit is not None:
+            refuse("--base-editor abe and %s: an adenine editor writes no stop codon; its knock-out route is --select-splice"
+                   % ("--base-edit" if getattr(args, "base_edit", False) else stop_limit))
+    if splice_limit is not None:
+        if pct:
+            refuse("%s and %s: the splice-site filter and the coding-position filter are two kernels' predicates: one or the other"
+                   % (splice_limit, [o for o, k in (("--select-coding-min", "select_coding_min"), ("--select-coding-max", "select_coding_max"),
+                                                    ("--select-transcripts", "select_transcripts")) if k in pct][0]))
+        if KP is not None:
+            refuse("%s: the splice site is relative to the gene and the pairs' eligibility is per table row: not together with --select-pairs"
+                   % splice_limit)
     if stop_limit is not None:
         if pct:
             refuse("%s and %s: the stop-codon filter and the coding-position filter are two kernels' predicates: one or the other"
@@ -729,12 +787,19 @@ def select_request(args, spec, world=1):
         if KP is not None:
             refuse("%s: the stop codon is relative to the gene and the pairs' eligibility is per table row: not together with --select-pairs"
                    % stop_limit)
-    with_edit = bool(getattr(args, "base_edit", False)) or window is not None or stop_limit is not None
+    with_splice = bool(getattr(args, "splice_edit", False)) or editor is not None or splice_limit is not None
+    abe = editor is not None and editor.name == "abe"
+    with_edit = bool(getattr(args, "base_edit", False)) or (window is not None and not abe) or stop_limit is not None
     if with_edit:  # (the keywords a select.Request only meets with base editing)
         val = lambda key, default: stop[key][1] if key in stop else default
         coding_args = dict(coding_args, edit_window=window or baseedit.Window(),
                            edit_limits=baseedit.Limits(val("select_stop_min", 0), val("select_stop_max", 100),
                                                        val("select_max_edit_targets", baseedit.GUIDE_LEN)) if stop_limit is not None else None)
+    if with_splice:
+        sval = lambda key, default: splice[key][1] if key in splice else default
+        coding_args = dict(coding_args, edit_window=window or baseedit.Window(), editor=editor or baseedit.Editor(), edit=with_edit,
+                           splice_limits=baseedit.SpliceLimits(sval("select_splice_min", 0), sval("select_splice_max", 100), max_targets,
+                                                               kind or "any") if splice_limit is not None else None)
     # (a flank makes the scan fetch the column: only where the file prints it, or where the filters ask for another flank than the default)
     repair_args = dict(min_mh=min_mh, min_oof=min_oof,
                        repair_flank=(repair.DEFAULT_FLANK if flank is None else flank) if with_scores else flank)
@@ -753,7 +818,7 @@ def select_request(args, spec, world=1):
             refuse("--select-pairs: " + str(e))
     return dict(params=params, output=getattr(args, "select_output", None) or (args.o + ".selected.csv"),
                 only=bool(getattr(args, "select_only", False)), limits=dict(limits, **repair_args, **coding_args), repair_scores=with_scores,
-                coding=with_coding, base_edit=with_edit, pairs=pairs, pairs_output=getattr(args, "pairs_output", None) or (args.o + ".pairs.csv"))
+                coding=with_coding, base_edit=with_edit, splice_edit=with_splice, pairs=pairs, pairs_output=getattr(args, "pairs_output", None) or (args.o + ".pairs.csv"))
 
 
 def properties_request(args, world=1):
@@ -777,13 +842,14 @@ def properties_request(args, world=1):
 
 
 def write_selection(path, selection, names, strings, all_hits, guide_len, offtarget, spec_M, annotation, properties=False,
-                    repair_scores=False, coding=False, base_edit=False):
+                    repair_scores=False, coding=False, base_edit=False, splice_edit=False):
     """The selection file: a header, then per chosen row gene, rank (1-based), passing and the main table's own fields
     for that row as rows.ContigRows builds them, without crispr_id (those ids are random per run).  Genes in GFF order;
     genes with nothing selected are left out.  Python's csv module in the main table's dialect: the file is small.
     repair_scores: two more fields at the end of every row, mh_score and oof_score (repair.fields) of selection.mh / .oof.
     coding: five more after those, cds_offset, cds_length, cds_percent, transcripts_cut and transcripts (coding.fields).
-    base_edit: four more after those, edit_targets, stop_codons, stop_codon and stop_percent (baseedit.fields)."""
+    base_edit: four more after those, edit_targets, stop_codons, stop_codon and stop_percent (baseedit.fields).
+    splice_edit: four more after those, splice_targets, splice_sites, donor_percent and acceptor_percent (baseedit.splice_fields)."""
     import csv
     from . import baseedit
     from . import coding as cod
@@ -807,13 +873,16 @@ def write_selection(path, selection, names, strings, all_hits, guide_len, offtar
         w = csv.writer(f)
         w.writerow(["gene", "rank", "passing"] + rows.HEADER[1:] + rows.extra_header(offtarget, spec_M, properties)
                    + (repair.HEADER if repair_scores else []) + (cod.HEADER if coding else [])
-                   + (baseedit.HEADER if base_edit else []))
+                   + (baseedit.HEADER if base_edit else []) + (baseedit.SPLICE_HEADER if splice_edit else []))
         for at, (r, rest) in enumerate(zip(sel_rows, fields)):
             more = repair.fields(repair.pack(selection.mh[at], selection.oof[at])) if repair_scores else ()
             if coding:
                 more = tuple(more) + cod.fields(selection.cds_offset[at], selection.cds_length[at], selection.transcripts_cut[at], selection.transcripts[at])
             if base_edit:
                 more = tuple(more) + baseedit.fields(selection.edit_targets[at], selection.stop_codons[at], selection.stop_offset[at], selection.cds_length[at])
+            if splice_edit:
+                more = tuple(more) + baseedit.splice_fields(selection.splice_targets[at], selection.donors[at], selection.acceptors[at],
+                                                            selection.donor_offset[at], selection.acceptor_offset[at], selection.cds_length[at])
             w.writerow((selection.labels[int(r["gene"])], int(r["rank"]), int(selection.n_pass[int(r["gene"])])) + tuple(rest) + tuple(more))
 
 
@@ -1126,7 +1195,7 @@ def run(args, backend=None, out=sys.stdout, group=None):
         selection = all_hits.selection
         write_selection(selecting["output"], selection, names, strings, all_hits, args.l, offtarget, None if spec is None else spec["max_mm"],
                         request.annotation if annotating else None, properties=with_properties, repair_scores=selecting["repair_scores"],
-                        coding=selecting["coding"], base_edit=selecting["base_edit"])
+                        coding=selecting["coding"], base_edit=selecting["base_edit"], splice_edit=selecting["splice_edit"])
         stages["select"] = dict(selection.stats, write_s=time.perf_counter() - t_select, genes=len(selection.labels),
                                 rows_selected=int(selection.rows.size), k=selecting["params"].k)
         if selecting["pairs"] is not None:

@@ -13,6 +13,7 @@
 #include "crp_select.h"
 #include "crp_select_coding.h"
 #include "crp_select_edit.h"
+#include "crp_select_splice.h"
 
 struct crp_select {
     crp_arena *arena = nullptr;
@@ -71,6 +72,12 @@ struct crp_select {
     crp_select_edit_window edit_window = {4, 8};
     crp_select_edit_limits edit_limits = {};
     double edit_stats[3] = {};
+    // splice-site editing: window, editor and limits of the selection, and what the last launches took
+    bool have_splice_limits = false;
+    crp_select_edit_window splice_window = {4, 8};
+    uint32_t splice_editor = CRP_EDITOR_CBE;
+    crp_select_splice_limits splice_limits = {};
+    double splice_stats[3] = {};
 };
 
 namespace {
@@ -277,8 +284,17 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
                                               "(crp_select_set_coding_limits(select, NULL) or crp_select_set_edit_limits(select, NULL, NULL))");
     if (s->have_edit_limits && !s->have_coding)
         return fail(ctx, CRP_ERR_STATE, "crp_select_run: edit limits need the model of a crp_select_set_coding");
+    if (s->have_splice_limits && s->have_coding_limits)
+        return fail(ctx, CRP_ERR_UNSUPPORTED, "crp_select_run: splice limits and coding limits are two kernels' predicates: clear one of them "
+                                              "(crp_select_set_coding_limits(select, NULL) or crp_select_set_splice_limits(select, NULL, 0, NULL))");
+    if (s->have_splice_limits && s->have_edit_limits && s->splice_editor != CRP_EDITOR_CBE)
+        return fail(ctx, CRP_ERR_UNSUPPORTED, "crp_select_run: an adenine editor writes no stop codon: clear the edit limits "
+                                              "(crp_select_set_edit_limits(select, NULL, NULL)) or set the splice limits for CRP_EDITOR_CBE");
+    if (s->have_splice_limits && !s->have_coding)
+        return fail(ctx, CRP_ERR_STATE, "crp_select_run: splice limits need the model of a crp_select_set_coding");
     s->coding_stats[0] = 0;
     s->edit_stats[0] = 0;
+    s->splice_stats[0] = 0;
     CRP_HIP(ctx, hipSetDevice(ctx->device));
     const int k = p->k;
     const uint64_t G = s->n_genes;
@@ -353,11 +369,19 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
     const crp::EditWindow edit_win = {s->edit_window.lo, s->edit_window.hi};
     const crp::EditLimits edit_lim = {s->edit_limits.min_pct, s->edit_limits.max_pct, s->edit_limits.max_targets};
     if (s->have_edit_limits) s->edit_stats[2] = (double)(edit_win.hi - edit_win.lo + 1u);
+    // with splice limits the window is theirs, and edit limits set as well are the alternative under it (stop or splice)
+    const crp::SpliceTest splice_test = {{s->splice_window.lo, s->splice_window.hi}, s->splice_editor,
+                                         {s->splice_limits.min_pct, s->splice_limits.max_pct, s->splice_limits.max_targets, s->splice_limits.kinds},
+                                         s->have_edit_limits ? 1u : 0u, edit_lim};
+    if (s->have_splice_limits) s->splice_stats[2] = (double)(splice_test.window.hi - splice_test.window.lo + 1u);
     // the bounded-launch rule: at most 2^20 items a launch, each timed on its own
     for (uint64_t first = 0; first < items.size(); first += crp::SELECT_MAX_ITEMS) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(crp::SELECT_MAX_ITEMS, items.size() - first);
         CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
-        if (s->have_edit_limits)
+        if (s->have_splice_limits)
+            CRP_HIP(ctx, crp::launch_select_items_splice(ctx->stream, tab[0], tab[1], pred, coding, edit_planes, splice_test, s->d_items + first, n, s->part,
+                                                         s->res));
+        else if (s->have_edit_limits)
             CRP_HIP(ctx, crp::launch_select_items_edit(ctx->stream, tab[0], tab[1], pred, coding, edit_planes, edit_win, edit_lim, s->d_items + first, n,
                                                        s->part, s->res));
         else if (s->have_coding_limits)
@@ -368,7 +392,8 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
         CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
         const double ms = elapsed(s->ev[0], s->ev[1]);
         if (s->have_coding_limits) s->coding_stats[0] += ms;
-        if (s->have_edit_limits) s->edit_stats[0] += ms;
+        if (s->have_splice_limits) s->splice_stats[0] += ms;
+        else if (s->have_edit_limits) s->edit_stats[0] += ms;
         s->stats[1] += ms;
         s->stats[4] += 1;
         s->stats[5] = std::max(s->stats[5], ms);
@@ -445,6 +470,9 @@ int crp_select_run_pairs(crp_select *s, const crp_select_params *p, const crp_se
     if (s->have_edit_limits)
         return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": edit limits are relative to the gene and the pairs' eligibility key is per table row: "
                                                     "clear them (crp_select_set_edit_limits(select, NULL, NULL)) for a pair selection");
+    if (s->have_splice_limits)
+        return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": splice limits are relative to the gene and the pairs' eligibility key is per table row: "
+                                                    "clear them (crp_select_set_splice_limits(select, NULL, 0, NULL)) for a pair selection");
     crp::SelfJoined joined = {};
     int rc = check_run(s, p, self, &joined, who.c_str());
     if (rc != CRP_OK) return rc;
@@ -763,6 +791,86 @@ int crp_select_edit_stats(const crp_select *s, double *out, int n)
 {
     if (!s || (n && !out) || n < 0 || n > 3) return CRP_ERR_INVALID;
     for (int k = 0; k < n; ++k) out[k] = s->edit_stats[k];
+    return CRP_OK;
+}
+
+/* ---- splice-site editing ---- */
+
+int crp_select_set_splice_limits(crp_select *s, const crp_select_edit_window *window, uint32_t editor, const crp_select_splice_limits *limits)
+{
+    if (!s) return CRP_ERR_INVALID;
+    if (!limits) {
+        s->have_splice_limits = false;
+        s->splice_limits = crp_select_splice_limits{};
+        return CRP_OK;
+    }
+    const std::string who = "crp_select_set_splice_limits";
+    crp::EditWindow w;
+    const int rc = check_window(s->ctx, window, who, &w);
+    if (rc != CRP_OK) return rc;
+    if (editor != CRP_EDITOR_CBE && editor != CRP_EDITOR_ABE)
+        return fail(s->ctx, CRP_ERR_INVALID, who + ": the editor is CRP_EDITOR_CBE or CRP_EDITOR_ABE, not " + std::to_string(editor));
+    if (limits->min_pct > limits->max_pct || limits->max_pct > 100u)
+        return fail(s->ctx, CRP_ERR_INVALID, who + ": percentages 0..100 with min_pct <= max_pct, not " + std::to_string(limits->min_pct) + " and " +
+                                                 std::to_string(limits->max_pct));
+    if (limits->kinds < 1u || limits->kinds > (CRP_SPLICE_DONOR | CRP_SPLICE_ACCEPTOR))
+        return fail(s->ctx, CRP_ERR_INVALID, who + ": kinds is CRP_SPLICE_DONOR, CRP_SPLICE_ACCEPTOR or both, not " + std::to_string(limits->kinds));
+    s->splice_window = crp_select_edit_window{w.lo, w.hi};
+    s->splice_editor = editor;
+    s->splice_limits = *limits;
+    s->have_splice_limits = true;
+    return CRP_OK;
+}
+
+int crp_select_splice_eval(crp_select *s, const crp_select_edit_window *window, uint32_t editor, const uint32_t *gene_row, const uint32_t *packed_row,
+                           uint64_t n, uint32_t *counts, uint32_t *off)
+{
+    if (!s || (n && (!gene_row || !packed_row || !counts || !off)) || n > 0x3fffffffull) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    crp_arena *a = s->arena;
+    const std::string who = "crp_select_splice_eval";
+    crp::EditWindow w;
+    int rc = check_window(ctx, window, who, &w);
+    if (rc != CRP_OK) return rc;
+    if (editor != CRP_EDITOR_CBE && editor != CRP_EDITOR_ABE)
+        return fail(ctx, CRP_ERR_INVALID, who + ": the editor is CRP_EDITOR_CBE or CRP_EDITOR_ABE, not " + std::to_string(editor));
+    if (!s->have_coding) return fail(ctx, CRP_ERR_STATE, who + ": the handle has no model (crp_select_set_coding)");
+    if (!a->have_hits || a->pend_guide_len != (int)crp::EDIT_GUIDE_LEN)
+        return fail(ctx, CRP_ERR_STATE, who + ": the arena has no hit tables of guide length 20 (the window counts protospacer positions of 20)");
+    for (uint64_t q = 0; q < n; ++q) {
+        if (gene_row[q] >= s->n_genes)
+            return fail(ctx, CRP_ERR_INVALID, who + ": query " + std::to_string(q) + " names gene " + std::to_string(gene_row[q]) + " of " + std::to_string(s->n_genes));
+        if ((packed_row[q] & 0x7FFFFFFFu) >= a->n_hits[packed_row[q] >> 31])
+            return fail(ctx, CRP_ERR_INVALID, who + ": query " + std::to_string(q) + " names a row outside its table");
+    }
+    s->splice_stats[1] = 0;
+    if (!n) return CRP_OK;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    // (the offs are two words a query: d_eval[3] holds 2 n)
+    for (int j = 0; j < 4 && rc == CRP_OK; ++j)
+        rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_eval[j]), &s->eval_cap[j], j == 3 ? 2 * n : n, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::staged_h2d(ctx, s->d_eval[0], gene_row, n * sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::staged_h2d(ctx, s->d_eval[1], packed_row, n * sizeof(uint32_t));
+    if (rc != CRP_OK) return rc;
+    const crp::SelectCoding coding = {s->d_cod[0], s->d_cod[1], s->d_cod[2], s->d_cod[3], s->d_cod[4], s->d_cod[5]};
+    const crp::EditPlanes planes = {a->d_plane[0], a->d_plane[1], a->d_plane[3], a->padded_words};
+    CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    CRP_HIP(ctx, crp::launch_splice_eval(ctx->stream, a->d_pos[0], a->d_pos[1], coding, planes, w, editor, s->d_eval[0], s->d_eval[1], (uint32_t)n,
+                                         s->d_eval[2], s->d_eval[3]));
+    CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+    rc = crp::staged_d2h(ctx, counts, s->d_eval[2], n * sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::staged_d2h(ctx, off, s->d_eval[3], 2 * n * sizeof(uint32_t));
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s->splice_stats[1] = elapsed(s->ev[0], s->ev[1]);
+    s->splice_stats[2] = (double)(w.hi - w.lo + 1u);
+    return CRP_OK;
+}
+
+int crp_select_splice_stats(const crp_select *s, double *out, int n)
+{
+    if (!s || (n && !out) || n < 0 || n > 3) return CRP_ERR_INVALID;
+    for (int k = 0; k < n; ++k) out[k] = s->splice_stats[k];
     return CRP_OK;
 }
 

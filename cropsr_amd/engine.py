@@ -791,6 +791,8 @@ class Genome:
                 part["coding"] = extras["coding"]
             if "edit" in extras:
                 part["edit"] = extras["edit"]
+            if "splice" in extras:
+                part["splice"] = extras["splice"]
             if paired:
                 _, part["pair_n_pairs"], part["pair_list"], pst = paired[0]
                 sel.sum_stats(pair_stats, pst)

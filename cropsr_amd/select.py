@@ -60,6 +60,12 @@ limits a row passes for gene g only if, beyond the above, a cytosine base editor
 under the row's window into a stop, the codon lies within the given percentages of that transcript's coding length and
 the window holds no more than the given number of targets.  Not together with coding limits or the pair selection.
 
+Splice-site editing (baseedit.py has the definition; csrc/crp_splice.h, csrc/crp_select_splice.hip):
+with splice limits a row passes for gene g only if, beyond the above, a cytosine or an adenine base editor changes a letter
+of a canonical donor or acceptor site of g's primary transcript under the row's window, the intron lies within the given
+percentages of that transcript's coding length and the window holds no more than the given number of targets.  With edit
+limits as well (cytosine editor only) the two tests are alternatives.  Not together with coding limits or the pair selection.
+
 This module lays the genes out per arena, converts a wanted specificity into the integer bound the kernel compares,
 drives crp_select_* and turns the per-arena results into one table over the genes of the GFF.
 """
@@ -167,13 +173,34 @@ class Request:
     edit_window / edit_limits (baseedit.Window, baseedit.Limits): base editing (baseedit.py).  With either the selection
     sets the genes' coding model and the Selection carries edit_targets, stop_codons, stop_offset and cds_length of its
     rows (the window defaults to 4..8); with limits a row passes only if the edit writes a stop codon inside them for the
-    gene it is selected for.  Edit limits are refused with coding limits and with pairs."""
+    gene it is selected for.  Edit limits are refused with coding limits and with pairs.
+    editor / splice_limits (baseedit.Editor or its name, baseedit.SpliceLimits): splice-site editing (baseedit.py).  With
+    either the selection sets the genes' coding model and the Selection carries splice_targets, donors, acceptors,
+    donor_offset, acceptor_offset and cds_length of its rows under edit_window (default 4..8) for that editor (default
+    cbe); with limits a row passes only if the edit destroys a splice site inside them for the gene it is selected for --
+    or, with edit_limits given as well, writes a stop codon inside those.  Splice limits are refused with coding limits and
+    with pairs, and the editor abe with edit limits.  edit: with the splice test, whether the stop-codon fields are wanted
+    too (they always come with edit limits)."""
 
     def __init__(self, params, annotation, slice_rows=None, gc_min=None, gc_max=None, max_run=None, max_t_run=None, max_stem=None,
                  repair_flank=None, min_mh=None, min_oof=None, pairs=None, pair_slice_rows=None, coding=False, coding_limits=None,
-                 edit_window=None, edit_limits=None):
+                 edit_window=None, edit_limits=None, editor=None, splice_limits=None, edit=None):
         self.pairs, self.pair_slice_rows = pairs, pair_slice_rows
-        self.edit = edit_window is not None or edit_limits is not None
+        self.splice = editor is not None or splice_limits is not None
+        self.splice_limits = splice_limits
+        self.editor = None
+        if self.splice:
+            from .baseedit import Editor, Window
+            self.editor = Editor("cbe" if editor is None else editor)
+            self.splice_window = Window() if edit_window is None else edit_window
+            if self.editor.name == "abe" and edit_limits is not None:
+                raise ValueError("an adenine editor writes no stop codon: edit limits belong to the editor cbe")
+        if splice_limits is not None and coding_limits is not None:
+            raise ValueError("splice limits and coding limits are two kernels' predicates: one or the other")
+        if splice_limits is not None and pairs is not None:
+            raise ValueError("splice limits are relative to the gene; the pair selection's eligibility is per table row: one or the other")
+        # (the window is shared by both tests: without the splice test it asks for the stop-codon fields by itself, with it `edit` says)
+        self.edit = edit_limits is not None or (bool(edit) if self.splice else edit_window is not None)
         self.edit_window, self.edit_limits = edit_window, edit_limits
         if self.edit and edit_window is None:
             from .baseedit import Window
@@ -318,6 +345,35 @@ class ArenaSelect:
         nat.check(nat.lib().crp_select_edit_stats(self._h, out.ctypes.data_as(nat.f64p), 3), "crp_select_edit_stats", self._ctx)
         return dict(zip(("edit_select_ms", "edit_eval_ms", "edit_targets_window"), (float(v) for v in out)))
 
+    def set_splice_limits(self, window=None, editor="cbe", limits=None):
+        """window: baseedit.Window (None: 4..8); editor: baseedit.Editor or its name; limits: baseedit.SpliceLimits, or None
+        to clear them."""
+        from .baseedit import Editor
+        win = None if window is None else ctypes.byref(nat.SelectEditWindow(*window.astuple()))
+        lim = None if limits is None else ctypes.byref(nat.SelectSpliceLimits(*limits.astuple()))
+        nat.check(nat.lib().crp_select_set_splice_limits(self._h, win, Editor(editor).code, lim), "crp_select_set_splice_limits", self._ctx)
+
+    def splice_eval(self, window, editor, gene_row, packed_row):
+        """(targets, donors, acceptors, donor_off, acceptor_off), uint32 each, of the rows packed_row (sel's packing) for the
+        genes gene_row of this handle under window (baseedit.Window; None: 4..8) and editor (baseedit.Editor or its name);
+        an off is baseedit.NO_SITE where the edit destroys no site of that kind."""
+        from .baseedit import Editor
+        gene_row, packed_row = np.ascontiguousarray(gene_row, dtype=np.uint32), np.ascontiguousarray(packed_row, dtype=np.uint32)
+        if gene_row.shape != packed_row.shape or gene_row.ndim != 1:
+            raise ValueError("gene_row and packed_row must be 1-d arrays of one length")
+        win = None if window is None else ctypes.byref(nat.SelectEditWindow(*window.astuple()))
+        counts, off = np.zeros(max(1, gene_row.size), np.uint32), np.zeros(2 * max(1, gene_row.size), np.uint32)
+        nat.check(nat.lib().crp_select_splice_eval(self._h, win, Editor(editor).code, gene_row.ctypes.data_as(nat.u32p), packed_row.ctypes.data_as(nat.u32p),
+                                                   gene_row.size, counts.ctypes.data_as(nat.u32p), off.ctypes.data_as(nat.u32p)),
+                  "crp_select_splice_eval", self._ctx)
+        counts, off = counts[:gene_row.size], off[:2 * gene_row.size].reshape(-1, 2)
+        return counts & np.uint32(0xFF), counts >> np.uint32(8) & np.uint32(0xFF), counts >> np.uint32(16), off[:, 0].copy(), off[:, 1].copy()
+
+    def splice_stats(self):
+        out = np.zeros(3, dtype=np.float64)
+        nat.check(nat.lib().crp_select_splice_stats(self._h, out.ctypes.data_as(nat.f64p), 3), "crp_select_splice_stats", self._ctx)
+        return dict(zip(("splice_select_ms", "splice_eval_ms", "splice_window"), (float(v) for v in out)))
+
     def set_pair_limits(self, pair_slice_rows=0):
         nat.check(nat.lib().crp_select_set_pair_limits(self._h, int(pair_slice_rows)), "crp_select_set_pair_limits", self._ctx)
 
@@ -364,7 +420,9 @@ class Selection:
     coding position (coding.py): cds_offset (coding.NOT_INSIDE where the cut is not inside the primary transcript),
     cds_length, transcripts_cut and transcripts (n,) uint32 of the rows, for the gene each was selected for; None otherwise.
     With base editing (baseedit.py): edit_targets, stop_codons and stop_offset (baseedit.NO_STOP where the edit writes no
-    stop) (n,) uint32 of the rows, for the gene each was selected for, and cds_length; None otherwise."""
+    stop) (n,) uint32 of the rows, for the gene each was selected for, and cds_length; None otherwise.  With splice-site
+    editing: splice_targets, donors, acceptors, donor_offset and acceptor_offset (baseedit.NO_SITE without a destroyed site of
+    that kind) (n,) uint32 likewise, and cds_length; None otherwise."""
 
     def __init__(self, labels, n_in, n_pass, rows, counts=None, hit_sum=None, stats=None, mh=None, oof=None):
         self.labels, self.n_in, self.n_pass, self.rows = labels, n_in, n_pass, rows
@@ -374,6 +432,7 @@ class Selection:
         self.pairs_stats = {}
         self.cds_offset = self.cds_length = self.transcripts_cut = self.transcripts = None
         self.edit_targets = self.stop_codons = self.stop_offset = None
+        self.splice_targets = self.donors = self.acceptors = self.donor_offset = self.acceptor_offset = None
 
     def of_gene(self, g):
         return self.rows[self.rows["gene"] == g]
@@ -393,7 +452,8 @@ def assemble(labels, k, arenas, stats=None):
     gene index), n_in, n_pass, sel (layout rows x K), and optionally counts_plus / sum_plus / counts_minus / sum_minus
     and repair_plus / repair_minus (the packed repair scores of the tables' rows), and coding (dict: off and cover, layout
     rows x K beside sel, and length and n_tx per layout row) and edit (dict: targets, stops and stop_off, layout rows x K
-    beside sel, and length per layout row).
+    beside sel, and length per layout row) and splice (dict: targets, donors, acceptors, donor_off and acceptor_off, layout
+    rows x K beside sel, and length per layout row).
     A gene that has rows in several texts (two contigs of one name) gets the sums of its counts and the first K of its
     rows in the definition's order, texts in arena order."""
     G = len(labels)
@@ -403,7 +463,8 @@ def assemble(labels, k, arenas, stats=None):
     repaired = any(a.get("repair_plus") is not None for a in arenas)
     coded = any(a.get("coding") is not None for a in arenas)
     edited = any(a.get("edit") is not None for a in arenas)
-    rparts, kparts, eparts = [], [], []
+    spliced = any(a.get("splice") is not None for a in arenas)
+    rparts, kparts, eparts, xparts = [], [], [], []
     for a in arenas:
         gene = np.asarray(a["gene"], dtype=np.int64)
         np.add.at(n_in, gene, np.asarray(a["n_in"], dtype=np.int64))
@@ -447,6 +508,11 @@ def assemble(labels, k, arenas, stats=None):
             ed = a["edit"]
             eparts.append(np.stack([np.asarray(ed[key], np.uint32).reshape(gene.size, -1)[r, c] for key in ("targets", "stops", "stop_off")]
                                    + [np.asarray(ed["length"], np.uint32)[r]], axis=1) if r.size else np.empty((0, 4), np.uint32))
+        if spliced:
+            sp = a["splice"]
+            xparts.append(np.stack([np.asarray(sp[key], np.uint32).reshape(gene.size, -1)[r, c]
+                                    for key in ("targets", "donors", "acceptors", "donor_off", "acceptor_off")]
+                                   + [np.asarray(sp["length"], np.uint32)[r]], axis=1) if r.size else np.empty((0, 6), np.uint32))
     rows = np.concatenate(parts) if parts else np.empty(0, ROW_DTYPE)
     counts = np.concatenate(cparts) if cparts else None
     sums = np.concatenate(sparts) if sparts else None
@@ -473,6 +539,9 @@ def assemble(labels, k, arenas, stats=None):
     if eparts:
         ed = np.concatenate(eparts)[order][keep]
         out.edit_targets, out.stop_codons, out.stop_offset, out.cds_length = (ed[:, j].copy() for j in range(4))
+    if xparts:
+        sp = np.concatenate(xparts)[order][keep]
+        out.splice_targets, out.donors, out.acceptors, out.donor_offset, out.acceptor_offset, out.cds_length = (sp[:, j].copy() for j in range(6))
     return out
 
 
@@ -549,7 +618,8 @@ def select_arena(genome, a, request, handle=None, flags=None, extras=None):
     rows, beside sel; where sel has no row, coding.NOT_INSIDE and 0; length, n_tx: per layout row).  Without extras the model
     and the limits are still set, and the selected rows are not evaluated.  With request.edit likewise extras["edit"] =
     dict(targets, stops, stop_off: of the selected rows, beside sel; where sel has no row, 0, 0 and baseedit.NO_STOP; length:
-    per layout row).
+    per layout row), and with request.splice extras["splice"] = dict(targets, donors, acceptors, donor_off, acceptor_off: of
+    the selected rows; where sel has no row, 0, 0, 0 and baseedit.NO_SITE twice; length: per layout row).
     handle: the arena's search.ArenaSelfSearch after join_hits, or None."""
     lo, hi, gene = request.annotation.gene_layout(arena_layout(genome, a))
     sel = ArenaSelect(genome.arenas[a], lo, hi)
@@ -564,13 +634,16 @@ def select_arena(genome, a, request, handle=None, flags=None, extras=None):
             sel.set_repair_limits(request.repair_limits)
         model = None
         edit = getattr(request, "edit", False)
-        if getattr(request, "coding", False) or edit:
+        splice = getattr(request, "splice", False)
+        if getattr(request, "coding", False) or edit or splice:
             model = request.annotation.coding_layout(arena_layout(genome, a))
             sel.set_coding(model)
             if getattr(request, "coding_limits", None) is not None:
                 sel.set_coding_limits(request.coding_limits)
             if edit and request.edit_limits is not None:
                 sel.set_edit_limits(request.edit_window, request.edit_limits)
+            if splice and request.splice_limits is not None:
+                sel.set_splice_limits(request.splice_window, request.editor, request.splice_limits)
         sel.run(request.params, handle)
         n_in, n_pass, picked = sel.fetch()
         stats = sel.stats()
@@ -582,6 +655,18 @@ def select_arena(genome, a, request, handle=None, flags=None, extras=None):
             extras["edit"] = dict(targets=targets, stops=stops, stop_off=stop_off, length=model["length"])
         if edit:
             stats.update(sel.edit_stats())
+        if splice and extras is not None:
+            from .baseedit import NO_SITE
+            r, c = np.nonzero(picked != NONE)
+            zero, none = (lambda: np.zeros(picked.shape, np.uint32)), (lambda: np.full(picked.shape, NO_SITE, np.uint32))
+            sp = dict(targets=zero(), donors=zero(), acceptors=zero(), donor_off=none(), acceptor_off=none(), length=model["length"])
+            got = sel.splice_eval(request.splice_window, request.editor, r.astype(np.uint32), picked[r, c])
+            for key, v in zip(("targets", "donors", "acceptors", "donor_off", "acceptor_off"), got):
+                sp[key][r, c] = v
+            extras["splice"] = sp
+        if splice:
+            stats.update(sel.splice_stats())
+            stats["editor"] = request.editor.name
         if getattr(request, "coding", False) and extras is not None:
             from .coding import NOT_INSIDE
             r, c = np.nonzero(picked != NONE)
@@ -600,7 +685,7 @@ def select_arena(genome, a, request, handle=None, flags=None, extras=None):
 
 def sum_stats(total, one):
     for key, v in one.items():
-        if key in ("bytes_per_row", "edit_targets_window"):
+        if key in ("bytes_per_row", "edit_targets_window", "splice_window", "editor"):
             total[key] = v
         else:
             total[key] = max(total.get(key, 0.0), v) if key == "longest_launch_ms" else total.get(key, 0.0) + v

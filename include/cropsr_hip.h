@@ -1022,6 +1022,47 @@ int crp_select_edit_eval(crp_select *select, const crp_select_edit_window *windo
  * crp_select_edit_eval's kernel (HIP events), out[2] the letters of the window last used.  n: how many to write (<= 3). */
 int crp_select_edit_stats(const crp_select *select, double *out, int n);
 
+/* ---- base editing: guides that destroy a splice site (opt-in) ---------------------------- */
+/* Both base-editor families can knock a gene out without a stop codon: by changing a letter of the canonical GT that opens
+ * an intron of the coding transcript or of the AG that closes it (cropsr_amd/baseedit.py states the definition).  Rows,
+ * window, letters and the model are those of the section above.
+ *   editor    CRP_EDITOR_CBE: the window's base C on a '+' row, base G on a '-' row; CRP_EDITOR_ABE: base A resp. base T
+ *   targets   their number, 0 .. 20; it depends on no gene
+ *   introns   relative to gene g with a model: in ascending positions an intron of the primary transcript P starts at a
+ *             boundary x where x - 1 is a coding letter of P, x is not and cum_P(x) < L_P, and ends at x' where x' - 1 is
+ *             not, x' is and cum_P(x') > 0; evidence comes from the steps inside the row's text alone
+ *   sites     the letters x, x + 1 and x' - 2, x' - 1, evaluated when both are bases, both are no coding letters of P and
+ *             they read GT resp. AG on a '+' gene (donor, acceptor), CT resp. AC on a '-' gene (acceptor, donor)
+ *   destroyed an evaluated site with a target among its two letters; donors, acceptors: their numbers
+ *   off       donor_off, acceptor_off: P's coding letters 5' of the intron of the destroyed site of that kind nearest the
+ *             gene's 5' end (cum_P at its boundary, L_P - cum_P on a '-' gene), 1 .. L_P - 1; 0xFFFFFFFF without one
+ * Splice limits: with limits set a row PASSES for gene g only if also, for a kind in `kinds`, off is not 0xFFFFFFFF and
+ * min_pct L_P <= 100 off <= max_pct L_P (64-bit integer products), and targets <= max_targets.  With edit limits set as
+ * well (CRP_EDITOR_CBE only) the two are alternatives: the row passes by either test under its own limits, both under the
+ * window given here.  window NULL: 4 .. 8.  limits NULL clears the limits.
+ * CRP_ERR_INVALID with a crp_last_error text: a window out of range, an unknown editor, a percentage above 100, min_pct >
+ * max_pct, kinds outside 1 .. 3.  With splice limits crp_select_run needs the model (CRP_ERR_STATE without) and refuses
+ * coding limits set at the same time and edit limits next to CRP_EDITOR_ABE (CRP_ERR_UNSUPPORTED); crp_select_run_pairs
+ * refuses splice limits (CRP_ERR_UNSUPPORTED). */
+#define CRP_EDITOR_CBE 0u
+#define CRP_EDITOR_ABE 1u
+#define CRP_SPLICE_DONOR 1u
+#define CRP_SPLICE_ACCEPTOR 2u
+typedef struct crp_select_splice_limits {
+    uint32_t min_pct, max_pct, max_targets, kinds;
+} crp_select_splice_limits;
+int crp_select_set_splice_limits(crp_select *select, const crp_select_edit_window *window, uint32_t editor, const crp_select_splice_limits *limits);
+/* counts[q] = targets | donors << 8 | acceptors << 16, off[2 q] = donor_off and off[2 q + 1] = acceptor_off of n queries
+ * (gene_row[q]: a gene of the handle; packed_row[q]: a table row in sel's packing), one kernel lane each; off holds 2 n
+ * words.  Needs the model and the arena's current tables of guide length 20, no limits and no run.  CRP_ERR_INVALID with a
+ * crp_last_error text: a window, an editor, a gene or a row out of range (checked on the host; nothing is launched).
+ * CRP_ERR_STATE: no model, no tables, tables of another guide length. */
+int crp_select_splice_eval(crp_select *select, const crp_select_edit_window *window, uint32_t editor, const uint32_t *gene_row,
+                           const uint32_t *packed_row, uint64_t n, uint32_t *counts, uint32_t *off);
+/* out[0] ms of the select launches of the last crp_select_run that had splice limits (0: none), out[1] ms of the last
+ * crp_select_splice_eval's kernel (HIP events), out[2] the letters of the window last used.  n: how many to write (<= 3). */
+int crp_select_splice_stats(const crp_select *select, double *out, int n);
+
 /* ---- options -------------------------------------------------------------- */
 /* CRP_OPT_TWO_PASS (value 0/1, default 0): with 0 crp_scan_score is ONE kernel launch; the
  * table offsets come from a chained scan across workgroups inside it (decoupled look-back
