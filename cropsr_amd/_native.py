@@ -53,6 +53,12 @@ class SelectCodingLimits(ctypes.Structure):
     _fields_ = [("min_pct", ctypes.c_uint32), ("max_pct", ctypes.c_uint32), ("min_transcripts_pct", ctypes.c_uint32)]
 
 
+class SelectFamilyLimits(ctypes.Structure):
+    """crp_select_family_limits (include/cropsr_hip.h): the bounds a selection puts on what a guide hits outside its gene's
+    family and on the members it covers; min_members SELECT_ALL_MEMBERS: the family's size."""
+    _fields_ = [("max_hit_sum_outside", ctypes.c_uint64), ("max_mm0_outside", ctypes.c_uint32), ("min_members", ctypes.c_uint32)]
+
+
 class SelectEditWindow(ctypes.Structure):
     """crp_select_edit_window (include/cropsr_hip.h): the base editor's window, protospacer positions from the PAM-distal end."""
     _fields_ = [("lo", ctypes.c_uint32), ("hi", ctypes.c_uint32)]
@@ -202,6 +208,13 @@ SIGNATURES = {
     "crp_search_self_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_search_self_join_hits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, u32p, u64p, u32p, u64p]),
     "crp_search_self_join_device": (ctypes.c_int, [ctypes.c_void_p, voidpp, voidpp, voidpp, voidpp]),
+    "crp_search_self_set_families": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, u32p, u32p, ctypes.c_uint64, ctypes.c_int]),
+    "crp_search_self_family_set_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32]),
+    "crp_search_self_family_assign": (ctypes.c_int, [ctypes.c_void_p]),
+    "crp_search_self_family_compare": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "crp_search_self_family_fetch": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, u32p, u64p, u64p, ctypes.c_uint64]),
+    "crp_search_self_family_join_hits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, u32p, u64p, u64p, u32p, u32p, u64p, u64p, u32p]),
+    "crp_search_self_family_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_annotation_genes": (ctypes.c_int, [ctypes.c_void_p, u64p, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64), u8p, u64p,
                                             u64p]),
     "crp_annotation_gene_layout": (ctypes.c_int, [ctypes.c_void_p, u64p, ctypes.c_uint64, ctypes.c_int, u32p, u32p, u64p, ctypes.c_uint64,
@@ -230,6 +243,10 @@ SIGNATURES = {
     "crp_select_set_coding": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, u64p, ctypes.c_uint64, u32p, u32p, u32p, ctypes.c_uint64]),
     "crp_select_set_coding_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "crp_select_coding_eval": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, ctypes.c_uint64, u32p, u32p]),
+    "crp_select_set_family": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, ctypes.c_uint64]),
+    "crp_select_set_family_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "crp_select_family_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u32p, u32p, ctypes.c_uint64, u32p, u64p, u32p, u32p, u64p]),
+    "crp_select_family_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_select_coding_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_select_set_edit_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "crp_select_edit_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u32p, u32p, ctypes.c_uint64, u32p, u32p]),
@@ -272,6 +289,7 @@ SEARCH_PAM_3PRIME, SEARCH_PAM_5PRIME = 0, 1
 SEARCH_SHAPE_DOUBLES = 288
 SEARCH_SELF_MAX_MM = 4
 SEARCH_PAIR_MAX_PAM = 3
+SELECT_ALL_MEMBERS = 0xFFFFFFFF  # crp_select_family_limits.min_members: the size of the gene's family
 SELF_UNJOINED_COUNT, SELF_UNJOINED_SUM = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF  # crp_search_self_join_hits: a hit without a guide site's row
 SELECT_MAX_K, SELECT_DEFAULT_SLICE_ROWS, SELECT_MIN_SLICE_ROWS, SELECT_NONE = 64, 65536, 64, 0xFFFFFFFF
 SELECT_PAIRS_MAX_K, SELECT_PAIRS_MAX_DISTANCE, SELECT_DEFAULT_PAIR_SLICE_ROWS, SELECT_MIN_PAIR_SLICE_ROWS = 64, 65535, 1024, 64

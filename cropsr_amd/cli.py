@@ -175,6 +175,22 @@ def build_parser():
     eng.add_argument("--select-transcripts", default=None, metavar="PCT",
                      help="with --select: only guides that cut inside the coding sequence of at least PCT %% of the gene's coding "
                           "transcripts (an integer 0..100; 100: every isoform); implies --coding")
+    eng.add_argument("--families", default=None, metavar="FILE",
+                     help="with --select and --specificity: gene families for polyploid genomes, a text file of gene<TAB>family "
+                          "lines (the gene as the selection file prints it after 'gene:'; homeolog or orthogroup tables).  Near copies "
+                          "inside the guide's own family are told from those outside it on the GPU; every row of the selection file "
+                          "gets seven more fields, family, family_size, members_hit, members, outside_mm0, outside_hit_sum and "
+                          "outside_specificity; a family has at most 64 members in the annotation; one GPU")
+    eng.add_argument("--family-cover-mismatches", default=None, metavar="C",
+                     help="with --families: a family member counts as hit when the guide has a site with NGG in it within C mismatches "
+                          "(0 .. --specificity-mismatches; default 0: exact copies)")
+    eng.add_argument("--select-min-members", default=None, metavar="N|all",
+                     help="with --families: only guides that hit at least N members of the gene's family (all: every member)")
+    eng.add_argument("--select-max-perfect-outside", default=None, metavar="N",
+                     help="with --families: only guides with at most N perfect copies outside the gene's family "
+                          "(--select-max-perfect counts the homeologs too)")
+    eng.add_argument("--select-min-specificity-outside", default=None, metavar="S",
+                     help="with --families: only guides whose specificity, with the hits inside the gene's family left out, is at least S")
     eng.add_argument("--base-edit", action="store_true",
                      help="with --select: what a cytosine base editor does under every selected guide: the C's of a window of the "
                           "protospacer become T's, which can turn CAA, CAG, CGA or (from the other strand) TGG of the gene's longest "
@@ -632,7 +648,11 @@ def select_request(args, spec, world=1):
                                    ("--select-stop-max", "select_stop_max", None), ("--select-max-edit-targets", "select_max_edit_targets", None),
                                    ("--base-editor", "base_editor", None), ("--splice-edit", "splice_edit", False),
                                    ("--select-splice", "select_splice", None), ("--select-splice-min", "select_splice_min", None),
-                                   ("--select-splice-max", "select_splice_max", None))
+                                   ("--select-splice-max", "select_splice_max", None), ("--families", "families", None),
+                                   ("--family-cover-mismatches", "family_cover_mismatches", None),
+                                   ("--select-min-members", "select_min_members", None),
+                                   ("--select-max-perfect-outside", "select_max_perfect_outside", None),
+                                   ("--select-min-specificity-outside", "select_min_specificity_outside", None))
              if getattr(args, k, unset) not in (unset, None)]
     KP = getattr(args, "select_pairs", None)
     pair_given = [o for o, k, unset in (("--pairs-min-distance", "pairs_min_distance", None), ("--pairs-max-distance", "pairs_max_distance", None),
@@ -800,6 +820,51 @@ def select_request(args, spec, world=1):
         coding_args = dict(coding_args, edit_window=window or baseedit.Window(), editor=editor or baseedit.Editor(), edit=with_edit,
                            splice_limits=baseedit.SpliceLimits(sval("select_splice_min", 0), sval("select_splice_max", 100), max_targets,
                                                                kind or "any") if splice_limit is not None else None)
+    # gene families: the file is read and checked here; its limits are relative to the gene and a kernel of their own, so neither
+    # with pairs nor with the coding, stop or splice filters
+    family_opts = [(o, getattr(args, k, None)) for o, k in (("--family-cover-mismatches", "family_cover_mismatches"),
+                                                           ("--select-min-members", "select_min_members"),
+                                                           ("--select-max-perfect-outside", "select_max_perfect_outside"),
+                                                           ("--select-min-specificity-outside", "select_min_specificity_outside"))]
+    family_limit = [o for o, v in family_opts[1:] if v is not None]
+    family_pairs = None
+    if getattr(args, "families", None) is None:
+        for o, v in family_opts:
+            if v is not None:
+                refuse("%s belongs to --families" % o)
+    else:
+        from . import families
+        if spec is None:
+            refuse("--families tells the hits of --specificity inside a gene's family from those outside it: give --specificity too")
+        for other, name in ((pct, "the coding-position filter"), (stop_limit, "the stop-codon filter"), (splice_limit, "the splice-site filter")):
+            if family_limit and other:
+                refuse("%s and %s are two kernels' predicates: one or the other" % (family_limit[0], name))
+        if family_limit and KP is not None:
+            refuse("%s: a family is relative to the gene and the pairs' eligibility is per table row: not together with --select-pairs"
+                   % family_limit[0])
+        cover, members, perfect, outside = (v for _, v in family_opts)
+        if cover is not None and (integer(cover) is None or integer(cover) > spec["max_mm"]):
+            refuse("--family-cover-mismatches is 0..%d (the mismatches of --specificity), not %s" % (spec["max_mm"], cover))
+        if members is not None and str(members).strip().lower() != "all":
+            if integer(members) is None or not 1 <= integer(members) <= families.MAX_MEMBERS:
+                refuse("--select-min-members is 1..%d or all, not %s" % (families.MAX_MEMBERS, members))
+            members = integer(members)
+        if perfect is not None:
+            if integer(perfect) is None:
+                refuse("--select-max-perfect-outside is a count, not %s" % perfect)
+            perfect = integer(perfect)
+        if outside is not None:
+            try:
+                outside = float(outside)
+                select.max_hit_sum_for(outside)
+            except ValueError:
+                refuse("--select-min-specificity-outside is a specificity 0..1, not %s" % outside)
+        try:
+            family_pairs = families.read_families(args.families)
+        except families.FamilyInputError as e:
+            refuse("--families: " + str(e))
+        coding_args = dict(coding_args, family_cover_mm=integer(cover) if cover is not None else 0, min_members=members,
+                           max_perfect_outside=perfect, min_specificity_outside=outside)
     # (a flank makes the scan fetch the column: only where the file prints it, or where the filters ask for another flank than the default)
     repair_args = dict(min_mh=min_mh, min_oof=min_oof,
                        repair_flank=(repair.DEFAULT_FLANK if flank is None else flank) if with_scores else flank)
@@ -818,7 +883,7 @@ def select_request(args, spec, world=1):
             refuse("--select-pairs: " + str(e))
     return dict(params=params, output=getattr(args, "select_output", None) or (args.o + ".selected.csv"),
                 only=bool(getattr(args, "select_only", False)), limits=dict(limits, **repair_args, **coding_args), repair_scores=with_scores,
-                coding=with_coding, base_edit=with_edit, splice_edit=with_splice, pairs=pairs, pairs_output=getattr(args, "pairs_output", None) or (args.o + ".pairs.csv"))
+                coding=with_coding, base_edit=with_edit, splice_edit=with_splice, families=family_pairs, pairs=pairs, pairs_output=getattr(args, "pairs_output", None) or (args.o + ".pairs.csv"))
 
 
 def properties_request(args, world=1):
@@ -842,14 +907,16 @@ def properties_request(args, world=1):
 
 
 def write_selection(path, selection, names, strings, all_hits, guide_len, offtarget, spec_M, annotation, properties=False,
-                    repair_scores=False, coding=False, base_edit=False, splice_edit=False):
+                    repair_scores=False, coding=False, base_edit=False, splice_edit=False, families=None):
     """The selection file: a header, then per chosen row gene, rank (1-based), passing and the main table's own fields
     for that row as rows.ContigRows builds them, without crispr_id (those ids are random per run).  Genes in GFF order;
     genes with nothing selected are left out.  Python's csv module in the main table's dialect: the file is small.
     repair_scores: two more fields at the end of every row, mh_score and oof_score (repair.fields) of selection.mh / .oof.
     coding: five more after those, cds_offset, cds_length, cds_percent, transcripts_cut and transcripts (coding.fields).
     base_edit: four more after those, edit_targets, stop_codons, stop_codon and stop_percent (baseedit.fields).
-    splice_edit: four more after those, splice_targets, splice_sites, donor_percent and acceptor_percent (baseedit.splice_fields)."""
+    splice_edit: four more after those, splice_targets, splice_sites, donor_percent and acceptor_percent (baseedit.splice_fields).
+    families (families.FamilyTable): seven more after those, family, family_size, members_hit, members (the covered members'
+    labels, ;-joined, GFF order), outside_mm0, outside_hit_sum and outside_specificity (FAMILY_HEADER)."""
     import csv
     from . import baseedit
     from . import coding as cod
@@ -873,7 +940,8 @@ def write_selection(path, selection, names, strings, all_hits, guide_len, offtar
         w = csv.writer(f)
         w.writerow(["gene", "rank", "passing"] + rows.HEADER[1:] + rows.extra_header(offtarget, spec_M, properties)
                    + (repair.HEADER if repair_scores else []) + (cod.HEADER if coding else [])
-                   + (baseedit.HEADER if base_edit else []) + (baseedit.SPLICE_HEADER if splice_edit else []))
+                   + (baseedit.HEADER if base_edit else []) + (baseedit.SPLICE_HEADER if splice_edit else [])
+                   + (FAMILY_HEADER if families is not None else []))
         for at, (r, rest) in enumerate(zip(sel_rows, fields)):
             more = repair.fields(repair.pack(selection.mh[at], selection.oof[at])) if repair_scores else ()
             if coding:
@@ -883,7 +951,26 @@ def write_selection(path, selection, names, strings, all_hits, guide_len, offtar
             if splice_edit:
                 more = tuple(more) + baseedit.splice_fields(selection.splice_targets[at], selection.donors[at], selection.acceptors[at],
                                                             selection.donor_offset[at], selection.acceptor_offset[at], selection.cds_length[at])
+            if families is not None:
+                more = tuple(more) + family_fields(families, selection, at)
             w.writerow((selection.labels[int(r["gene"])], int(r["rank"]), int(selection.n_pass[int(r["gene"])])) + tuple(rest) + tuple(more))
+
+
+FAMILY_HEADER = ["family", "family_size", "members_hit", "members", "outside_mm0", "outside_hit_sum", "outside_specificity"]
+
+
+def family_fields(table, selection, at):
+    """The seven family fields of row `at` of a selection (FAMILY_HEADER): hit_sum and specificity as the main table's
+    specificity columns print them; an unscored join has no sum and no specificity.  A selected row is always a joined one:
+    with families the selection runs on the joined columns, whose predicate fails every unjoined row, so no sentinel count
+    reaches this file."""
+    from .search import specificity
+    g = int(selection.rows["gene"][at])
+    hs = int(selection.outside_hit_sum[at])
+    scored = hs != 0xFFFFFFFFFFFFFFFF
+    return (table.family_name(g), int(selection.family_size[at]), int(selection.members_hit[at]), ";".join(selection.members[at]),
+            int(selection.outside_mm0[at]), "%.6f" % (hs / float(1 << 30)) if scored else "",
+            "%.6f" % float(specificity(np.uint64(hs))) if scored else "")
 
 
 PAIR_HEADER = ["gene", "rank", "qualifying_pairs", "deletion_length", "in_frame", "chromosome"]
@@ -1134,6 +1221,17 @@ def run(args, backend=None, out=sys.stdout, group=None):
     if getattr(args, "seed", None) is not None:
         np.random.seed(args.seed)
 
+    if selecting is not None and selecting["families"] is not None:  # the family table: before the output file is touched
+        from . import families
+        if request_err is not None:
+            raise request_err
+        try:
+            family_table = families.FamilyTable(selecting["families"], request.annotation.genes()[0])
+        except families.FamilyInputError as e:
+            sys.exit("cropsr_amd: --select: --families: " + str(e))
+        if family_table.n_unknown:
+            print("cropsr_amd: --families: %d names of %s are no gene of %s" % (family_table.n_unknown, args.families, args.g), file=sys.stderr)
+        selecting["limits"]["families"] = family_table
     select_only = selecting is not None and selecting["only"]
     if not select_only:
         rows.write_header(args.o, offtarget=offtarget, specificity=None if spec is None else spec["max_mm"],
@@ -1195,7 +1293,8 @@ def run(args, backend=None, out=sys.stdout, group=None):
         selection = all_hits.selection
         write_selection(selecting["output"], selection, names, strings, all_hits, args.l, offtarget, None if spec is None else spec["max_mm"],
                         request.annotation if annotating else None, properties=with_properties, repair_scores=selecting["repair_scores"],
-                        coding=selecting["coding"], base_edit=selecting["base_edit"], splice_edit=selecting["splice_edit"])
+                        coding=selecting["coding"], base_edit=selecting["base_edit"], splice_edit=selecting["splice_edit"],
+                        families=selecting["limits"].get("families"))
         stages["select"] = dict(selection.stats, write_s=time.perf_counter() - t_select, genes=len(selection.labels),
                                 rows_selected=int(selection.rows.size), k=selecting["params"].k)
         if selecting["pairs"] is not None:

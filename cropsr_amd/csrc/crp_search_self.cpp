@@ -11,6 +11,10 @@
 //          launches of at most pairs_per_launch pairs.  Hits add into the query handle's rows.
 // join     the rows of the guide sites onto the hit tables of the arena's last scan (CSV join): one
 //          launch per strand, the joined columns stay on the handle.
+// families (kernels in crp_search_family.hip) the family genes of the arena on the handle: assign gives
+//          every candidate its owner, compare fills a second row per guide site from the candidates of its own family
+//          (work planned from the genes' runs: tiles of SELF_TILE queries x slices of a member's run), join hands those
+//          rows to the hit tables like the plain ones.
 // A genome of several arenas is every ordered pair of handles, segment by segment (cropsr_amd/search.py: search_self).
 #include <algorithm>
 #include <cmath>
@@ -20,6 +24,7 @@
 #include <vector>
 
 #include "crp_internal.h"
+#include "crp_search_family.h"
 #include "crp_search_self.h"
 
 namespace {
@@ -29,6 +34,8 @@ constexpr uint64_t kItemsPerLaunch = 1ull << 20;  // work items one upload holds
 constexpr uint32_t kSliceMin = 2048;              // candidates per slice of a bucket, at least
 constexpr uint32_t kSlicesMax = 64;               // slices per bucket, at most: a huge bucket is tiles x 64 workgroups
 constexpr uint64_t kMaxCands = (1ull << 32) - 2 * crp::SELF_PAD;
+constexpr uint64_t kFamilyItemsPerLaunch = kItemsPerLaunch / 2;  // a family item is two uint4 of the same upload
+constexpr uint32_t kFamilySliceFloor = crp::SELF_UNROLL;          // the smallest slice crp_search_self_family_set_limits takes
 
 uint32_t iupac_set(char c)  // bit = code: A=0 T=1 C=2 G=3
 {
@@ -95,6 +102,46 @@ struct crp_search_self {
     bool have_join = false;
     uint64_t join_rows[2] = {0, 0};  // the tables' rows at the time of the join
     double ms_join = 0;
+    // gene families: crp_search_self_set_families .. crp_search_self_family_join_hits
+    uint64_t budget = 0;
+    std::vector<crp::FamilyRow> fam_rows;       // the arena's family genes, GFF order
+    std::vector<uint32_t> fam_by_family;        // row indices ordered by (family, row)
+    std::vector<uint2> fam_run;                 // per row: its candidates' run, after assign
+    int fam_cover_mm = 0;
+    bool fam_set = false, fam_assigned = false, fam_have_join = false;
+    uint64_t fam_bytes = 0, fam_pairs_per_launch = kPairsPerLaunch, fam_pairs = 0, fam_launches = 0;
+    uint32_t fam_slice_min = kSliceMin;
+    double ms_fam_assign = 0, ms_fam_compare = 0, ms_fam_join = 0;
+    crp::FamilyRow *d_fam_rows = nullptr;
+    uint2 *d_fam_run = nullptr;
+    uint32_t *d_fam_tag = nullptr, *d_fam_family = nullptr, *d_fam_counts = nullptr;
+    unsigned long long *d_fam_sum = nullptr, *d_fam_cover = nullptr;
+    uint32_t *d_fjoin_counts[2] = {nullptr, nullptr}, *d_fjoin_family[2] = {nullptr, nullptr};
+    unsigned long long *d_fjoin_sum[2] = {nullptr, nullptr}, *d_fjoin_cover[2] = {nullptr, nullptr};
+    uint64_t fjoin_cap[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
+    uint64_t fjoin_rows[2] = {0, 0};  // the tables' rows at the time of the family join
+
+    crp::FamilyCands family_cands() const { return crp::FamilyCands{d_cand, d_cand + n, d_cand + 2 * n, d_fam_tag}; }
+    void free_families()
+    {
+        (void)hipFree(d_fam_rows);
+        (void)hipFree(d_fam_run);
+        (void)hipFree(d_fam_tag);
+        (void)hipFree(d_fam_family);
+        (void)hipFree(d_fam_counts);
+        (void)hipFree(d_fam_sum);
+        (void)hipFree(d_fam_cover);
+        d_fam_rows = nullptr;
+        d_fam_run = nullptr;
+        d_fam_tag = d_fam_family = d_fam_counts = nullptr;
+        d_fam_sum = d_fam_cover = nullptr;
+        bytes -= fam_bytes;
+        fam_bytes = 0;
+        fam_rows.clear();
+        fam_by_family.clear();
+        fam_run.clear();
+        fam_set = fam_assigned = fam_have_join = false;
+    }
 
     crp::SearchCands cands() const { return crp::SearchCands{d_cand, d_cand + n, d_cand + 2 * n, d_cand + 3 * n}; }
     crp::SelfOrder order() const
@@ -205,6 +252,19 @@ bool self_joined(const crp_search_self *s, SelfJoined *out)
     return true;
 }
 
+bool self_family_joined(const crp_search_self *s, SelfFamilyJoined *out)
+{
+    if (!s || !s->fam_have_join) return false;
+    for (int k = 0; k < 2; ++k) {
+        out->counts[k] = s->d_fjoin_counts[k];
+        out->sum[k] = s->d_fjoin_sum[k];
+        out->cover[k] = s->d_fjoin_cover[k];
+        out->family[k] = s->d_fjoin_family[k];
+        out->rows[k] = s->fjoin_rows[k];
+    }
+    return true;
+}
+
 }  // namespace crp
 
 extern "C" {
@@ -272,7 +332,8 @@ int crp_search_self_create(crp_arena *a, const char *pattern, const char *guide_
     int rc = CRP_OK;
     for (int k = 0; k < 2 && rc == CRP_OK; ++k)
         if (hipEventCreate(&s->ev[k]) != hipSuccess) rc = CRP_ERR_HIP;
-    if (rc == CRP_OK) rc = extract(s, budget ? budget : CRP_SEARCH_SELF_DEFAULT_BUDGET, needed_bytes);
+    s->budget = budget ? budget : CRP_SEARCH_SELF_DEFAULT_BUDGET;
+    if (rc == CRP_OK) rc = extract(s, s->budget, needed_bytes);
     if (rc != CRP_OK) {
         crp_search_self_destroy(s);
         return rc;
@@ -294,9 +355,14 @@ int crp_search_self_destroy(crp_search_self *s)
     (void)hipFree(s->d_hit_sum);
     s->value.free();
     (void)hipFree(s->d_items);
+    s->free_families();
     for (int k = 0; k < 2; ++k) {
         (void)hipFree(s->d_join_counts[k]);
         (void)hipFree(s->d_join_sum[k]);
+        (void)hipFree(s->d_fjoin_counts[k]);
+        (void)hipFree(s->d_fjoin_family[k]);
+        (void)hipFree(s->d_fjoin_sum[k]);
+        (void)hipFree(s->d_fjoin_cover[k]);
     }
     for (hipEvent_t e : s->ev)
         if (e) (void)hipEventDestroy(e);
@@ -562,6 +628,299 @@ int crp_search_self_stats(const crp_search_self *s, double *out, int n)
     if (!s || (n && !out) || n < 0 || n > 9) return CRP_ERR_INVALID;
     const double v[9] = {s->ms_extract, s->ms_order, s->ms_compare, (double)s->n_compare, s->ms_longest,
                          (double)s->pairs, (double)s->bytes, (double)s->n_order, s->ms_join};
+    for (int k = 0; k < n; ++k) out[k] = v[k];
+    return CRP_OK;
+}
+
+// ---- gene families ----------------------------------------------------------------------------
+
+int crp_search_self_set_families(crp_search_self *s, const uint32_t *lo, const uint32_t *hi, const uint32_t *family, const uint32_t *member,
+                                 uint64_t n_rows, int cover_mm)
+{
+    if (!s) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    if (n_rows && (!lo || !hi || !family || !member)) return CRP_ERR_INVALID;
+    if (!s->pam3 || s->pam_len != 3) {
+        ctx->last_error = "crp_search_self_set_families: the handle's PAM must be the pattern's last 3 letters (the cut-site rule is that geometry's)";
+        return CRP_ERR_INVALID;
+    }
+    if (cover_mm < 0 || cover_mm > s->max_mm) {
+        ctx->last_error = "crp_search_self_set_families: cover limit " + std::to_string(cover_mm) + " is outside 0.." + std::to_string(s->max_mm);
+        return CRP_ERR_INVALID;
+    }
+    if (n_rows >= crp::FAMILY_NO_ROW) return CRP_ERR_UNSUPPORTED;
+    for (uint64_t r = 0; r < n_rows; ++r) {
+        if (member[r] >= (uint32_t)crp::FAMILY_MAX_MEMBERS) {
+            ctx->last_error = "crp_search_self_set_families: member bit " + std::to_string(member[r]) + " of row " + std::to_string(r) +
+                              ": a family has at most " + std::to_string(crp::FAMILY_MAX_MEMBERS) + " members";
+            return CRP_ERR_INVALID;
+        }
+        if (family[r] == crp::FAMILY_NONE) {
+            ctx->last_error = "crp_search_self_set_families: family id 0xFFFFFFFF of row " + std::to_string(r) + " means no family";
+            return CRP_ERR_INVALID;
+        }
+    }
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s->free_families();
+    if (!n_rows && !lo) return CRP_OK;  // families taken off the handle
+    const uint64_t stride = (uint64_t)s->max_mm + 1;
+    const uint64_t add = s->n * (4 * stride + 8 + 8 + 4 + 4) + n_rows * (sizeof(crp::FamilyRow) + sizeof(uint2));
+    if (s->bytes + add > s->budget) {
+        ctx->last_error = "crp_search_self_set_families: the handle with families needs " + std::to_string(s->bytes + add) +
+                          " bytes of device memory: more than the budget of " + std::to_string(s->budget);
+        return CRP_ERR_CAPACITY;
+    }
+    const uint64_t n1 = std::max<uint64_t>(s->n, 1), r1 = std::max<uint64_t>(n_rows, 1);
+    s->fam_bytes = add;
+    s->bytes += add;
+    s->fam_rows.resize(n_rows);
+    for (uint64_t r = 0; r < n_rows; ++r) s->fam_rows[r] = crp::FamilyRow{lo[r], hi[r], family[r], member[r]};
+    s->fam_by_family.resize(n_rows);
+    for (uint64_t r = 0; r < n_rows; ++r) s->fam_by_family[r] = (uint32_t)r;
+    std::stable_sort(s->fam_by_family.begin(), s->fam_by_family.end(),
+                     [&](uint32_t a, uint32_t b) { return s->fam_rows[a].family < s->fam_rows[b].family; });
+    int rc = CRP_OK;
+    const auto alloc = [&](void **p, uint64_t bytes) {
+        if (rc != CRP_OK) return;
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e != hipSuccess) {
+            ctx->last_error = std::string("crp_search_self_set_families: ") + hipGetErrorString(e);
+            rc = e == hipErrorOutOfMemory ? CRP_ERR_NOMEM : CRP_ERR_HIP;
+        }
+    };
+    alloc(reinterpret_cast<void **>(&s->d_fam_rows), r1 * sizeof(crp::FamilyRow));
+    alloc(reinterpret_cast<void **>(&s->d_fam_run), r1 * sizeof(uint2));
+    alloc(reinterpret_cast<void **>(&s->d_fam_tag), n1 * 4);
+    alloc(reinterpret_cast<void **>(&s->d_fam_family), n1 * 4);
+    alloc(reinterpret_cast<void **>(&s->d_fam_counts), n1 * 4 * stride);
+    alloc(reinterpret_cast<void **>(&s->d_fam_sum), n1 * 8);
+    alloc(reinterpret_cast<void **>(&s->d_fam_cover), n1 * 8);
+    if (rc == CRP_OK && n_rows &&
+        hipMemcpy(s->d_fam_rows, s->fam_rows.data(), n_rows * sizeof(crp::FamilyRow), hipMemcpyHostToDevice) != hipSuccess) {
+        ctx->last_error = "crp_search_self_set_families: upload of the family rows failed";
+        rc = CRP_ERR_HIP;
+    }
+    if (rc != CRP_OK) {
+        s->free_families();
+        return rc;
+    }
+    s->fam_cover_mm = cover_mm;
+    s->fam_set = true;
+    return CRP_OK;
+}
+
+int crp_search_self_family_set_limits(crp_search_self *s, uint64_t pairs_per_launch, uint32_t slice_min)
+{
+    if (!s) return CRP_ERR_INVALID;
+    s->fam_pairs_per_launch = pairs_per_launch ? std::min(pairs_per_launch, kPairsPerLaunch) : kPairsPerLaunch;
+    s->fam_slice_min = slice_min ? std::max(slice_min, kFamilySliceFloor) : kSliceMin;
+    return CRP_OK;
+}
+
+int crp_search_self_family_assign(crp_search_self *s)
+{
+    if (!s) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    if (!s->fam_set) {
+        ctx->last_error = "crp_search_self_family_assign: no families on the handle (crp_search_self_set_families)";
+        return CRP_ERR_STATE;
+    }
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    s->fam_assigned = s->fam_have_join = false;
+    const uint64_t stride = (uint64_t)s->max_mm + 1, n1 = std::max<uint64_t>(s->n, 1);
+    const uint32_t n_rows = (uint32_t)s->fam_rows.size(), n = (uint32_t)s->n;
+    const crp::SearchCands c = s->cands();
+    CRP_HIP(ctx, hipMemsetAsync(s->d_fam_tag, 0xFF, n1 * 4, ctx->stream));  // no owner
+    CRP_HIP(ctx, hipMemsetAsync(s->d_fam_counts, 0, n1 * 4 * stride, ctx->stream));
+    CRP_HIP(ctx, hipMemsetAsync(s->d_fam_sum, 0, n1 * 8, ctx->stream));
+    CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    CRP_HIP(ctx, crp::launch_family_bounds(ctx->stream, s->d_fam_rows, n_rows, c.pos, n, s->T, s->d_fam_run));
+    CRP_HIP(ctx, crp::launch_family_assign(ctx->stream, s->d_fam_rows, n_rows, s->d_fam_run, c.pos, s->T, s->d_fam_tag));
+    CRP_HIP(ctx, crp::launch_family_finish(ctx->stream, s->d_fam_rows, s->d_flag, n, s->d_fam_tag, s->d_fam_family, s->d_fam_cover));
+    CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+    s->fam_run.assign(n_rows, make_uint2(0, 0));
+    if (n_rows) CRP_HIP(ctx, hipMemcpyAsync(s->fam_run.data(), s->d_fam_run, n_rows * sizeof(uint2), hipMemcpyDeviceToHost, ctx->stream));
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s->ms_fam_assign += elapsed(s->ev[0], s->ev[1]);
+    for (const uint2 &r : s->fam_run)
+        if (r.x > r.y || r.y > s->n) {  // (cannot be: both ends come from one search over n candidates)
+            ctx->last_error = "crp_search_self_family_assign: a run outside the candidate list";
+            return CRP_ERR_HIP;
+        }
+    s->fam_assigned = true;
+    return CRP_OK;
+}
+
+int crp_search_self_family_compare(crp_search_self *q, crp_search_self *c)
+{
+    if (!q || !c) return CRP_ERR_INVALID;
+    if (q->ctx != c->ctx || q->T != c->T || q->pam_len != c->pam_len || q->max_mm != c->max_mm || q->rule.region != c->rule.region)
+        return CRP_ERR_INVALID;
+    crp_ctx *ctx = q->ctx;
+    if (!q->fam_assigned || !c->fam_assigned) {
+        ctx->last_error = "crp_search_self_family_compare: both handles need crp_search_self_family_assign first";
+        return CRP_ERR_STATE;
+    }
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    crp::FamilyCompare cmp = {};
+    cmp.region = q->rule.region;
+    cmp.max_mm = q->max_mm;
+    cmp.cover_mm = q->fam_cover_mm;
+    cmp.same = q == c;
+    const crp::SearchScore score = q->value.score(nullptr);
+    const crp::SearchPair pair = q->value.pair(nullptr);
+    std::vector<uint4> items;
+    uint64_t pairs = 0;
+    const auto flush = [&]() -> int {
+        if (items.empty()) return CRP_OK;
+        CRP_HIP(ctx, hipMemcpy(q->d_items, items.data(), items.size() * sizeof(uint4), hipMemcpyHostToDevice));
+        CRP_HIP(ctx, hipEventRecord(q->ev[0], ctx->stream));
+        CRP_HIP(ctx, crp::launch_family_compare(ctx->stream, q->family_cands(), c->family_cands(), q->d_items, (uint32_t)(items.size() / 2), cmp,
+                                                q->d_fam_counts, q->d_fam_sum, q->d_fam_cover, q->value.have_scheme ? &score : nullptr,
+                                                q->value.have_pair ? &pair : nullptr));
+        CRP_HIP(ctx, hipEventRecord(q->ev[1], ctx->stream));
+        CRP_HIP(ctx, hipEventSynchronize(q->ev[1]));
+        q->ms_fam_compare += elapsed(q->ev[0], q->ev[1]);
+        q->fam_launches += 1;
+        q->fam_pairs += pairs;
+        items.clear();
+        pairs = 0;
+        return CRP_OK;
+    };
+    // the candidates' rows by family: [first, end) of c->fam_by_family per family id met in q
+    const auto &order = c->fam_by_family;
+    for (uint32_t a = 0; a < q->fam_rows.size(); ++a) {
+        const uint2 qr = q->fam_run[a];
+        if (qr.x == qr.y) continue;
+        const uint32_t fam = q->fam_rows[a].family;
+        auto at = std::lower_bound(order.begin(), order.end(), fam, [&](uint32_t r, uint32_t f) { return c->fam_rows[r].family < f; });
+        for (; at != order.end() && c->fam_rows[*at].family == fam; ++at) {
+            const uint32_t b = *at;
+            const uint2 cr = c->fam_run[b];
+            const uint32_t nc = cr.y - cr.x;
+            if (!nc) continue;
+            const uint32_t slices = std::min<uint32_t>(kSlicesMax, std::max<uint32_t>(1, nc / q->fam_slice_min));
+            const uint32_t per = ((nc + slices - 1) / slices + crp::SELF_UNROLL - 1) / crp::SELF_UNROLL * crp::SELF_UNROLL;
+            for (uint32_t t = qr.x; t < qr.y; t += crp::SELF_TILE) {
+                const uint32_t tq = std::min<uint32_t>(crp::SELF_TILE, qr.y - t);
+                for (uint32_t c0 = 0; c0 < nc; c0 += per) {
+                    const uint32_t tc = std::min(per, nc - c0);
+                    const uint64_t p = (uint64_t)tq * tc;
+                    if (!items.empty() && (pairs + p > q->fam_pairs_per_launch || items.size() / 2 >= kFamilyItemsPerLaunch)) {
+                        const int rc = flush();
+                        if (rc != CRP_OK) return rc;
+                    }
+                    items.push_back(make_uint4(t, tq, cr.x + c0, tc));
+                    items.push_back(make_uint4(a, b, c->fam_rows[b].member, 0));
+                    pairs += p;
+                }
+            }
+        }
+    }
+    return flush();
+}
+
+int crp_search_self_family_fetch(crp_search_self *s, uint32_t *owner, uint32_t *family, uint32_t *counts, uint64_t *sum, uint64_t *cover,
+                                 uint64_t cap)
+{
+    if (!s) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    if (!s->fam_assigned) {
+        ctx->last_error = "crp_search_self_family_fetch: no assigned families on the handle";
+        return CRP_ERR_STATE;
+    }
+    if (cap < s->n_guides) return CRP_ERR_CAPACITY;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const uint64_t chunk = 1ull << 22, stride = (uint64_t)s->max_mm + 1;
+    const uint64_t m1 = std::min(chunk, std::max<uint64_t>(s->n, 1));
+    std::vector<uint32_t> tag(m1), fam(family ? m1 : 0), cnt(counts ? m1 * stride : 0);
+    std::vector<uint64_t> sm(sum ? m1 : 0), cv(cover ? m1 : 0);
+    uint64_t k = 0;
+    for (uint64_t i0 = 0; i0 < s->n; i0 += chunk) {
+        const uint64_t m = std::min(chunk, s->n - i0);
+        CRP_HIP(ctx, hipMemcpy(tag.data(), s->d_fam_tag + i0, m * 4, hipMemcpyDeviceToHost));
+        if (family) CRP_HIP(ctx, hipMemcpy(fam.data(), s->d_fam_family + i0, m * 4, hipMemcpyDeviceToHost));
+        if (counts) CRP_HIP(ctx, hipMemcpy(cnt.data(), s->d_fam_counts + i0 * stride, m * stride * 4, hipMemcpyDeviceToHost));
+        if (sum) CRP_HIP(ctx, hipMemcpy(sm.data(), s->d_fam_sum + i0, m * 8, hipMemcpyDeviceToHost));
+        if (cover) CRP_HIP(ctx, hipMemcpy(cv.data(), s->d_fam_cover + i0, m * 8, hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < m; ++i) {
+            if (!(tag[i] & crp::FAMILY_GUIDE)) continue;
+            if (k >= cap) return CRP_ERR_HIP;  // (cannot be: the tags carry the guide flags)
+            const uint32_t row = tag[i] & crp::FAMILY_NO_ROW;
+            if (owner) owner[k] = row == crp::FAMILY_NO_ROW ? crp::FAMILY_NONE : row;
+            if (family) family[k] = fam[i];
+            if (counts) std::memcpy(counts + k * stride, cnt.data() + i * stride, stride * sizeof(uint32_t));
+            if (sum) sum[k] = sm[i];
+            if (cover) cover[k] = cv[i];
+            ++k;
+        }
+    }
+    return k == s->n_guides ? CRP_OK : CRP_ERR_HIP;
+}
+
+int crp_search_self_family_join_hits(crp_search_self *s, int guide_len, uint32_t *counts_plus, uint64_t *sum_plus, uint64_t *cover_plus,
+                                     uint32_t *family_plus, uint32_t *counts_minus, uint64_t *sum_minus, uint64_t *cover_minus,
+                                     uint32_t *family_minus)
+{
+    if (!s) return CRP_ERR_INVALID;
+    uint32_t *const counts[2] = {counts_plus, counts_minus}, *const family[2] = {family_plus, family_minus};
+    uint64_t *const sum[2] = {sum_plus, sum_minus}, *const cover[2] = {cover_plus, cover_minus};
+    crp_ctx *ctx = s->ctx;
+    crp_arena *a = s->arena;
+    s->fam_have_join = false;
+    if (!s->fam_assigned) {
+        ctx->last_error = "crp_search_self_family_join_hits: no assigned families on the handle";
+        return CRP_ERR_STATE;
+    }
+    if (s->T != guide_len + 3) {
+        ctx->last_error = "crp_search_self_family_join_hits: a pattern of " + std::to_string(s->T) +
+                          " letters does not join hits of guide length " + std::to_string(guide_len);
+        return CRP_ERR_INVALID;
+    }
+    if (!a->have_hits || a->pend_guide_len != guide_len) {
+        ctx->last_error = "crp_search_self_family_join_hits: the arena has no hit tables of guide length " + std::to_string(guide_len);
+        return CRP_ERR_INVALID;
+    }
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t stride = (uint64_t)s->max_mm + 1;
+    for (int k = 0; k < 2; ++k) {
+        int rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_fjoin_counts[k]), &s->fjoin_cap[k][0], a->n_hits[k] * stride, sizeof(uint32_t));
+        if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_fjoin_sum[k]), &s->fjoin_cap[k][1], a->n_hits[k], sizeof(uint64_t));
+        if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_fjoin_cover[k]), &s->fjoin_cap[k][2], a->n_hits[k], sizeof(uint64_t));
+        if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_fjoin_family[k]), &s->fjoin_cap[k][3], a->n_hits[k], sizeof(uint32_t));
+        if (rc != CRP_OK) return rc;
+    }
+    CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    for (int k = 0; k < 2; ++k)
+        CRP_HIP(ctx, crp::launch_family_join(ctx->stream, a->d_pos[k], (uint32_t)a->n_hits[k], k, guide_len, s->cands().pos, (uint32_t)s->n,
+                                             s->d_fam_tag, s->d_fam_family, s->d_fam_counts, s->d_fam_sum, s->d_fam_cover, s->max_mm,
+                                             s->d_fjoin_counts[k], s->d_fjoin_sum[k], s->d_fjoin_cover[k], s->d_fjoin_family[k]));
+    CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s->ms_fam_join += elapsed(s->ev[0], s->ev[1]);
+    s->fam_have_join = true;
+    s->fjoin_rows[0] = a->n_hits[0];
+    s->fjoin_rows[1] = a->n_hits[1];
+    for (int k = 0; k < 2; ++k) {
+        const uint64_t n = a->n_hits[k];
+        if (!n) continue;
+        int rc = CRP_OK;
+        if (counts[k]) rc = crp::staged_d2h(ctx, counts[k], s->d_fjoin_counts[k], n * stride * sizeof(uint32_t));
+        if (rc == CRP_OK && sum[k]) rc = crp::staged_d2h(ctx, sum[k], s->d_fjoin_sum[k], n * sizeof(uint64_t));
+        if (rc == CRP_OK && cover[k]) rc = crp::staged_d2h(ctx, cover[k], s->d_fjoin_cover[k], n * sizeof(uint64_t));
+        if (rc == CRP_OK && family[k]) rc = crp::staged_d2h(ctx, family[k], s->d_fjoin_family[k], n * sizeof(uint32_t));
+        if (rc != CRP_OK) return rc;
+    }
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CRP_OK;
+}
+
+int crp_search_self_family_stats(const crp_search_self *s, double *out, int n)
+{
+    if (!s || (n && !out) || n < 0 || n > 6) return CRP_ERR_INVALID;
+    const double v[6] = {s->ms_fam_assign, s->ms_fam_compare, (double)s->fam_pairs, (double)s->fam_launches, (double)s->fam_bytes, s->ms_fam_join};
     for (int k = 0; k < n; ++k) out[k] = v[k];
     return CRP_OK;
 }

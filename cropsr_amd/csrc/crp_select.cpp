@@ -13,6 +13,8 @@
 #include "crp_select.h"
 #include "crp_select_coding.h"
 #include "crp_select_edit.h"
+#include "crp_select_family.h"
+#include "crp_search_family.h"
 #include "crp_select_splice.h"
 
 struct crp_select {
@@ -78,6 +80,14 @@ struct crp_select {
     uint32_t splice_editor = CRP_EDITOR_CBE;
     crp_select_splice_limits splice_limits = {};
     double splice_stats[3] = {};
+    // gene families: per gene its family and that family's size, the limits, the answers of the eval
+    uint32_t *d_gene_family = nullptr, *d_family_size = nullptr;
+    uint64_t gene_family_cap = 0, family_size_cap = 0;
+    bool have_family = false, have_family_limits = false;
+    crp_select_family_limits family_limits = {};
+    unsigned long long *d_family_eval_sum = nullptr;
+    uint64_t family_eval_sum_cap = 0;
+    double family_stats[2] = {};
 };
 
 namespace {
@@ -151,6 +161,37 @@ void fill_predicate(const crp_select *s, const crp_select_params *p, bool with_s
     *pred_out = pred;
 }
 
+// The joined plain and family columns of `self` and the handle's per-gene families, as the family kernels take them.
+int family_columns(crp_select *s, crp_search_self *self, const char *who_c, crp::SelectFamily *out)
+{
+    crp_ctx *ctx = s->ctx;
+    crp_arena *a = s->arena;
+    const std::string who = who_c;
+    if (!s->have_family) return fail(ctx, CRP_ERR_STATE, who + ": the handle has no families (crp_select_set_family)");
+    crp::SelfJoined joined = {};
+    crp::SelfFamilyJoined fj = {};
+    if (!self || !crp::self_joined(self, &joined))
+        return fail(ctx, CRP_ERR_STATE, who + ": families need a self-search handle with joined columns (crp_search_self_join_hits)");
+    if (!crp::self_family_joined(self, &fj))
+        return fail(ctx, CRP_ERR_STATE, who + ": the self-search handle has no joined family columns (crp_search_self_family_join_hits)");
+    if (joined.arena != a) return fail(ctx, CRP_ERR_INVALID, who + ": the self-search handle belongs to another arena");
+    for (int t = 0; t < 2; ++t)
+        if (joined.rows[t] != a->n_hits[t] || fj.rows[t] != a->n_hits[t])
+            return fail(ctx, CRP_ERR_STATE, who + ": the joined columns belong to an earlier scan's tables");
+    for (int t = 0; t < 2; ++t) {
+        out->counts[t] = joined.counts[t];
+        out->sum[t] = joined.sum[t];
+        out->fam_counts[t] = fj.counts[t];
+        out->fam_sum[t] = fj.sum[t];
+        out->fam_cover[t] = fj.cover[t];
+        out->site_family[t] = fj.family[t];
+    }
+    out->stride = (uint32_t)joined.stride;
+    out->gene_family = s->d_gene_family;
+    out->gene_size = s->d_family_size;
+    return CRP_OK;
+}
+
 // A window of protospacer positions 1 <= lo <= hi <= 20 (NULL: the default, 4 .. 8).
 int check_window(crp_ctx *ctx, const crp_select_edit_window *w, const std::string &who, crp::EditWindow *out)
 {
@@ -215,7 +256,7 @@ int crp_select_destroy(crp_select *s)
                     s->d_pair_merge, s->d_pair_evals, s->pair_part.kmin, s->pair_part.kmax, s->pair_part.tie, s->pair_part.a, s->pair_part.b,
                     s->pair_part.n_pass, s->pair_part.n_pairs, s->pair_res.n_pass, s->pair_res.n_pairs, s->pair_res.pairs,
                     s->d_cod[0], s->d_cod[1], s->d_cod[2], s->d_cod[3], s->d_cod[4], s->d_cod[5], s->d_eval[0], s->d_eval[1], s->d_eval[2],
-                    s->d_eval[3]};
+                    s->d_eval[3], s->d_gene_family, s->d_family_size, s->d_family_eval_sum};
     for (void *p : bufs) (void)hipFree(p);
     for (hipEvent_t e : s->ev)
         if (e) (void)hipEventDestroy(e);
@@ -292,6 +333,15 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
                                               "(crp_select_set_edit_limits(select, NULL, NULL)) or set the splice limits for CRP_EDITOR_CBE");
     if (s->have_splice_limits && !s->have_coding)
         return fail(ctx, CRP_ERR_STATE, "crp_select_run: splice limits need the model of a crp_select_set_coding");
+    crp::SelectFamily family = {};
+    if (s->have_family_limits) {
+        if (s->have_coding_limits || s->have_edit_limits || s->have_splice_limits)
+            return fail(ctx, CRP_ERR_UNSUPPORTED, "crp_select_run: family limits and coding, edit or splice limits are different kernels' "
+                                                  "predicates: clear one of them (crp_select_set_family_limits(select, NULL))");
+        rc = family_columns(s, self, "crp_select_run", &family);
+        if (rc != CRP_OK) return rc;
+    }
+    s->family_stats[0] = 0;
     s->coding_stats[0] = 0;
     s->edit_stats[0] = 0;
     s->splice_stats[0] = 0;
@@ -365,6 +415,7 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
     fill_predicate(s, p, self != nullptr, joined, k, tab, &pred);
     const crp::SelectCoding coding = {s->d_cod[0], s->d_cod[1], s->d_cod[2], s->d_cod[3], s->d_cod[4], s->d_cod[5]};
     const crp::CodingLimits coding_lim = {s->coding_limits.min_pct, s->coding_limits.max_pct, s->coding_limits.min_transcripts_pct};
+    const crp::FamilyLimits family_lim = {s->family_limits.max_hit_sum_outside, s->family_limits.max_mm0_outside, s->family_limits.min_members};
     const crp::EditPlanes edit_planes = {a->d_plane[0], a->d_plane[1], a->d_plane[3], a->padded_words};
     const crp::EditWindow edit_win = {s->edit_window.lo, s->edit_window.hi};
     const crp::EditLimits edit_lim = {s->edit_limits.min_pct, s->edit_limits.max_pct, s->edit_limits.max_targets};
@@ -386,12 +437,15 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
                                                        s->part, s->res));
         else if (s->have_coding_limits)
             CRP_HIP(ctx, crp::launch_select_items_coding(ctx->stream, tab[0], tab[1], pred, coding, coding_lim, s->d_items + first, n, s->part, s->res));
+        else if (s->have_family_limits)
+            CRP_HIP(ctx, crp::launch_select_items_family(ctx->stream, tab[0], tab[1], pred, family, family_lim, s->d_items + first, n, s->part, s->res));
         else
             CRP_HIP(ctx, crp::launch_select_items(ctx->stream, tab[0], tab[1], pred, s->d_items + first, n, s->part, s->res));
         CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
         CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
         const double ms = elapsed(s->ev[0], s->ev[1]);
         if (s->have_coding_limits) s->coding_stats[0] += ms;
+        if (s->have_family_limits) s->family_stats[0] += ms;
         if (s->have_splice_limits) s->splice_stats[0] += ms;
         else if (s->have_edit_limits) s->edit_stats[0] += ms;
         s->stats[1] += ms;
@@ -464,6 +518,9 @@ int crp_select_run_pairs(crp_select *s, const crp_select_params *p, const crp_se
                                               ", not " + std::to_string(q->dmin) + " and " + std::to_string(q->dmax));
     if (q->orientation_mask < 1 || q->orientation_mask > 0xFu)
         return fail(ctx, CRP_ERR_INVALID, who + ": the orientation mask must be 1..15, not " + std::to_string(q->orientation_mask));
+    if (s->have_family_limits)
+        return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": family limits are relative to the gene and the pairs' eligibility key is per table row: "
+                                                    "clear them (crp_select_set_family_limits(select, NULL)) for a pair selection");
     if (s->have_coding_limits)
         return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": coding limits are relative to the gene and the pairs' eligibility key is per table row: "
                                                     "clear them (crp_select_set_coding_limits(select, NULL)) for a pair selection");
@@ -721,6 +778,92 @@ int crp_select_coding_stats(const crp_select *s, double *out, int n)
 {
     if (!s || (n && !out) || n < 0 || n > 3) return CRP_ERR_INVALID;
     for (int k = 0; k < n; ++k) out[k] = s->coding_stats[k];
+    return CRP_OK;
+}
+
+/* ---- gene families ---- */
+
+int crp_select_set_family(crp_select *s, const uint32_t *gene_family, const uint32_t *family_size, uint64_t n_genes)
+{
+    if (!s) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    s->have_family = false;
+    if (!gene_family && !family_size && !n_genes) return CRP_OK;
+    if (!gene_family || !family_size) return CRP_ERR_INVALID;
+    if (n_genes != s->n_genes)
+        return fail(ctx, CRP_ERR_INVALID, "crp_select_set_family: " + std::to_string(n_genes) + " genes for a handle of " + std::to_string(s->n_genes));
+    for (uint64_t g = 0; g < n_genes; ++g)
+        if (!family_size[g])
+            return fail(ctx, CRP_ERR_INVALID, "crp_select_set_family: gene " + std::to_string(g) + " has a family of size 0 (a gene in no family has 1)");
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_gene_family), &s->gene_family_cap, n_genes, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_family_size), &s->family_size_cap, n_genes, sizeof(uint32_t));
+    if (rc == CRP_OK && n_genes) rc = crp::staged_h2d(ctx, s->d_gene_family, gene_family, n_genes * sizeof(uint32_t));
+    if (rc == CRP_OK && n_genes) rc = crp::staged_h2d(ctx, s->d_family_size, family_size, n_genes * sizeof(uint32_t));
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s->have_family = true;
+    return CRP_OK;
+}
+
+int crp_select_set_family_limits(crp_select *s, const crp_select_family_limits *limits)
+{
+    if (!s) return CRP_ERR_INVALID;
+    if (limits && limits->min_members != CRP_SELECT_ALL_MEMBERS && limits->min_members > 64u)
+        return fail(s->ctx, CRP_ERR_INVALID, "crp_select_set_family_limits: a family has at most 64 members, not " + std::to_string(limits->min_members));
+    s->have_family_limits = limits != nullptr;
+    s->family_limits = limits ? *limits : crp_select_family_limits{};
+    return CRP_OK;
+}
+
+int crp_select_family_eval(crp_select *s, crp_search_self *self, const uint32_t *gene_row, const uint32_t *packed_row, uint64_t n,
+                           uint32_t *outside_mm0, uint64_t *outside_hit_sum, uint32_t *members_hit, uint32_t *family_size, uint64_t *fam_cover)
+{
+    if (!s || (n && (!gene_row || !packed_row || !outside_mm0 || !outside_hit_sum || !members_hit || !family_size || !fam_cover)) ||
+        n > 0x7fffffffull)
+        return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    crp_arena *a = s->arena;
+    const std::string who = "crp_select_family_eval";
+    if (!a->have_hits) return fail(ctx, CRP_ERR_STATE, who + ": the arena has no hit tables");
+    crp::SelectFamily family = {};
+    int rc = family_columns(s, self, who.c_str(), &family);
+    if (rc != CRP_OK) return rc;
+    for (uint64_t q = 0; q < n; ++q) {
+        if (gene_row[q] >= s->n_genes)
+            return fail(ctx, CRP_ERR_INVALID, who + ": query " + std::to_string(q) + " names gene " + std::to_string(gene_row[q]) + " of " + std::to_string(s->n_genes));
+        if ((packed_row[q] & 0x7FFFFFFFu) >= a->n_hits[packed_row[q] >> 31])
+            return fail(ctx, CRP_ERR_INVALID, who + ": query " + std::to_string(q) + " names a row outside its table");
+    }
+    s->family_stats[1] = 0;
+    if (!n) return CRP_OK;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    for (int j = 0; j < 4 && rc == CRP_OK; ++j) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_eval[j]), &s->eval_cap[j], 2 * n, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_family_eval_sum), &s->family_eval_sum_cap, 2 * n, sizeof(uint64_t));
+    if (rc == CRP_OK) rc = crp::staged_h2d(ctx, s->d_eval[0], gene_row, n * sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::staged_h2d(ctx, s->d_eval[1], packed_row, n * sizeof(uint32_t));
+    if (rc != CRP_OK) return rc;
+    // (the eval buffers hold 2 n words each here: d_eval[2] carries outside_mm0 and, behind it, family_size)
+    uint32_t *d_mm0 = s->d_eval[2], *d_hit = s->d_eval[3], *d_size = s->d_eval[2] + n;
+    CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    CRP_HIP(ctx, crp::launch_family_eval(ctx->stream, family, s->d_eval[0], s->d_eval[1], (uint32_t)n, d_mm0, s->d_family_eval_sum, d_hit, d_size,
+                                         s->d_family_eval_sum + n));
+    CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+    rc = crp::staged_d2h(ctx, outside_mm0, d_mm0, n * sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::staged_d2h(ctx, outside_hit_sum, s->d_family_eval_sum, n * sizeof(uint64_t));
+    if (rc == CRP_OK) rc = crp::staged_d2h(ctx, members_hit, d_hit, n * sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::staged_d2h(ctx, family_size, d_size, n * sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::staged_d2h(ctx, fam_cover, s->d_family_eval_sum + n, n * sizeof(uint64_t));
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s->family_stats[1] = elapsed(s->ev[0], s->ev[1]);
+    return CRP_OK;
+}
+
+int crp_select_family_stats(const crp_select *s, double *out, int n)
+{
+    if (!s || (n && !out) || n < 0 || n > 2) return CRP_ERR_INVALID;
+    for (int k = 0; k < n; ++k) out[k] = s->family_stats[k];
     return CRP_OK;
 }
 

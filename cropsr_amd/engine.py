@@ -749,13 +749,16 @@ class Genome:
         self.repair_stats = dict(kernel_ms=ms, rows=n_rows, flank=int(flank), wall_s=time.perf_counter() - t0)
         return out if fetch else None
 
-    def specificity_columns(self, guide_len=20, max_mm=3, candidate_pam="NRG", score="hsu2013", budget=None):
+    def specificity_columns(self, guide_len=20, max_mm=3, candidate_pam="NRG", score="hsu2013", budget=None, families=None,
+                            family_cover_mm=0, family_limits=None):
         """The genome-wide specificity of every hit of the last scan at guide_len, joined on the GPU
-        (search.specificity_columns): per contig self_counts_plus / _minus (n, M + 1) and self_sum_plus / _minus."""
+        (search.specificity_columns): per contig self_counts_plus / _minus (n, M + 1) and self_sum_plus / _minus; with
+        families (one families.ArenaRows per arena) also the family columns fam_counts, fam_sum, fam_cover and site_family."""
         from . import search
-        return search.specificity_columns(self, guide_len, max_mm=max_mm, candidate_pam=candidate_pam, score=score, budget=budget)
+        return search.specificity_columns(self, guide_len, max_mm=max_mm, candidate_pam=candidate_pam, score=score, budget=budget,
+                                          families=families, family_cover_mm=family_cover_mm, family_limits=family_limits)
 
-    def select(self, request, hits, counts=None, handle_of=None, joined=None, annotated=False, repair=None):
+    def select(self, request, hits, counts=None, handle_of=None, joined=None, annotated=False, repair=None, family_joined=None):
         """The best K guides of every gene (select.Request; the module's docstring has the definition) over the tables
         of the last scan at guide length 20, which `hits` (GenomeHits) holds as host copies.  Runs after the annotation
         look-up and -- with handle_of(arena index) -> the arena's joined search.ArenaSelfSearch and joined[arena index] =
@@ -769,6 +772,8 @@ class Genome:
         from . import select as sel
         if request.params.needs_specificity and handle_of is None:
             raise ValueError("max_perfect / min_specificity need the specificity join (scan_score(specificity=...))")
+        if getattr(request, "families", None) is not None and (handle_of is None or family_joined is None):
+            raise ValueError("gene families need the specificity join with the family rows (scan_score(specificity=...))")
         labels = request.annotation.annotation.genes()[0]
         if request.params.require_cds and not annotated:
             keep = self.annotate_s
@@ -793,12 +798,17 @@ class Genome:
                 part["edit"] = extras["edit"]
             if "splice" in extras:
                 part["splice"] = extras["splice"]
+            if "family" in extras:  # (the device's values of the selected rows, the cover word among them)
+                part["family"] = extras["family"]
             if paired:
                 _, part["pair_n_pairs"], part["pair_list"], pst = paired[0]
                 sel.sum_stats(pair_stats, pst)
             parts.append(part)
             sel.sum_stats(stats, st)
         out = sel.assemble(labels, request.params.k, parts, stats)
+        if out.fam_cover is not None:  # the covered members' labels; the gene itself where the row's family is not the gene's
+            table = request.families
+            out.members = [table.member_labels(int(g), int(cv)) if cv else [labels[int(g)]] for g, cv in zip(out.rows["gene"], out.fam_cover)]
         if request.pairs is not None:
             out.pairs, out.n_pairs, out.pairs_repair = sel.assemble_pairs(len(labels), request.pairs.k, parts)
             out.pairs_stats = pair_stats
@@ -832,6 +842,13 @@ class Genome:
             raise ValueError("guide properties exist for guide lengths 1..50, not %d" % guide_len)
         if select is not None and guide_len != 20:
             raise ValueError("the guide selection ranks by the on-target score, which exists at guide length 20 only")
+        family_cols = {}
+        if select is not None and getattr(select, "families", None) is not None:
+            if specificity is None:
+                raise ValueError("gene families need the specificity join (scan_score(specificity=...))")
+            from . import families as fam
+            specificity = dict(specificity, families=fam.genome_rows(select.families, self, select.annotation),
+                               family_cover_mm=select.family_cover_mm)
         hits = self._scan_score(guide_len, want_pre, offtarget, seeds_from_scan, annotation)
         if properties or (select is not None and select.property_limits is not None):
             cols = self.guide_properties([(h.n_plus, h.n_minus) for h in hits.per_arena], fetch=bool(properties))
@@ -854,13 +871,15 @@ class Genome:
                 from . import search
                 handles, joined = {}, {}
 
-                def after_join(a, handle, cols):
+                def after_join(a, handle, cols, family_joined=None):
                     handles[a], joined[a] = handle, cols
+                    if family_cols is not None and family_joined is not None:
+                        family_cols[a] = family_joined
                     if len(handles) == len(self.arenas):  # every arena has joined, no handle has closed yet
                         if want_repair:
                             run_repair()
                         hits.selection = self.select(select, hits, handle_of=handles.get, joined=joined, annotated=annotation is not None,
-                                                     repair=hits.repair)
+                                                     repair=hits.repair, family_joined=family_cols or None)
 
                 hits.columns = search.specificity_columns(self, guide_len, after_join=after_join, **specificity)
         elif select is not None:
@@ -905,12 +924,16 @@ class Genome:
         return search.search_bulges(self, pattern, queries, max_mm, pam_len, dna_bulge, rna_bulge, site_cap=site_cap, budget=budget,
                                     score=score, sites=sites)
 
-    def search_self(self, pattern, max_mm, pam_len, guide_pattern=None, score=None, budget=None, pairs_per_launch=None):
+    def search_self(self, pattern, max_mm, pam_len, guide_pattern=None, score=None, budget=None, pairs_per_launch=None, families=None,
+                    family_cover_mm=0, family_limits=None):
         """Every guide site of the genome against every candidate site (search.search_self: the self search).  Returns
-        search.SelfSearchResult (.sites, .guides, .counts (n, M + 1), .hit_sum, .specificity, .candidates, .pairs)."""
+        search.SelfSearchResult (.sites, .guides, .counts (n, M + 1), .hit_sum, .specificity, .candidates, .pairs); with
+        families (one families.ArenaRows per arena, families.genome_rows) also .site_family, .site_gene, .fam_counts,
+        .fam_sum and .fam_cover."""
         from . import search
         return search.search_self(self, pattern, max_mm, pam_len, guide_pattern=guide_pattern, score=score, budget=budget,
-                                  pairs_per_launch=pairs_per_launch)
+                                  pairs_per_launch=pairs_per_launch, families=families, family_cover_mm=family_cover_mm,
+                                  family_limits=family_limits)
 
     def close(self):
         for a in self.arenas:

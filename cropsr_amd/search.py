@@ -928,8 +928,64 @@ class ArenaSelfSearch:
         self._check(nat.lib().crp_search_self_join_device(self._h, *[ctypes.byref(x) for x in p]), "crp_search_self_join_device")
         return tuple(x.value for x in p)
 
+    # ---- gene families (families.py has the definition)
+    def set_families(self, rows, cover_mm=0):
+        """crp_search_self_set_families: rows is a families.ArenaRows of this handle's arena (None takes families off)."""
+        L = nat.lib()
+        if rows is None:
+            self._check(L.crp_search_self_set_families(self._h, None, None, None, None, 0, 0), "crp_search_self_set_families")
+            return
+        cols = [np.ascontiguousarray(c, dtype=np.uint32) if len(rows) else np.zeros(1, np.uint32)  # (an arena without family genes)
+                for c in (rows.lo, rows.hi, rows.family, rows.member)]
+        self._check(L.crp_search_self_set_families(self._h, *[c.ctypes.data_as(nat.u32p) for c in cols], len(rows), int(cover_mm)),
+                    "crp_search_self_set_families")
+
+    def family_set_limits(self, pairs_per_launch=0, slice_min=0):
+        self._check(nat.lib().crp_search_self_family_set_limits(self._h, int(pairs_per_launch), int(slice_min)),
+                    "crp_search_self_family_set_limits")
+
+    def family_assign(self):
+        self._check(nat.lib().crp_search_self_family_assign(self._h), "crp_search_self_family_assign")
+
+    def family_compare(self, other):
+        self._check(nat.lib().crp_search_self_family_compare(self._h, other._h), "crp_search_self_family_compare")
+
+    def family_fetch(self, scored=True):
+        """(owner row u32, family u32, fam_counts (n, M + 1) u32, fam_sum u64 or None, fam_cover u64) of the guide sites, in
+        fetch()'s order; 0xFFFFFFFF is no owner / no family."""
+        n = self.sizes()[2]
+        owner, fam = np.empty(n, np.uint32), np.empty(n, np.uint32)
+        counts = np.empty((n, self.max_mm + 1), np.uint32)
+        fs = np.empty(n, np.uint64) if scored else None
+        cover = np.empty(n, np.uint64)
+        self._check(nat.lib().crp_search_self_family_fetch(self._h, owner.ctypes.data_as(nat.u32p), fam.ctypes.data_as(nat.u32p),
+                                                           counts.ctypes.data_as(nat.u32p), fs.ctypes.data_as(nat.u64p) if scored else None,
+                                                           cover.ctypes.data_as(nat.u64p), n), "crp_search_self_family_fetch")
+        return owner, fam, counts, fs, cover
+
+    def family_join_hits(self, guide_len):
+        """crp_search_self_family_join_hits: (counts, sum, cover, family) of the '+' table, then of the '-' table."""
+        L = nat.lib()
+        a, b = ctypes.c_uint64(), ctypes.c_uint64()
+        nat.check(L.crp_hits_counts(self._arena._h, ctypes.byref(a), ctypes.byref(b)), "crp_hits_counts")
+        cols, args = [], []
+        for n in (a.value, b.value):
+            part = [np.empty((n, self.max_mm + 1), np.uint32), np.empty(n, np.uint64), np.empty(n, np.uint64), np.empty(n, np.uint32)]
+            cols += part
+            args += [c.ctypes.data_as(t) for c, t in zip(part, (nat.u32p, nat.u64p, nat.u64p, nat.u32p))]
+        self._check(L.crp_search_self_family_join_hits(self._h, int(guide_len), *args), "crp_search_self_family_join_hits")
+        return tuple(cols)
+
+    def family_stats(self):
+        out = np.zeros(6, dtype=np.float64)
+        self._check(nat.lib().crp_search_self_family_stats(self._h, out.ctypes.data_as(nat.f64p), 6), "crp_search_self_family_stats")
+        keys = ("assign_ms", "family_compare_ms", "family_pairs", "family_compare_launches", "family_bytes", "family_join_ms")
+        return dict(zip(keys, (float(v) for v in out)))
+
 
 class SelfSearchResult:
+    site_family = site_gene = fam_counts = fam_sum = fam_cover = None  # with families=: per guide site (families.py)
+
     def __init__(self, sites, guides, counts, hit_sum, candidates, pairs, stats=None):
         self.sites = sites            # SELF_SITE_DTYPE, ordered by contig, position, strand
         self.guides = guides          # (n,) S<G>: each guide site's G guide-region letters
@@ -973,16 +1029,56 @@ def _self_compare_all(handles, max_mm):
                 hq.compare(hc)
 
 
-def search_self(genome, pattern, max_mm, pam_len, guide_pattern=None, score=None, budget=None, pairs_per_launch=None):
+def _family_compare_all(handles, rows, cover_mm=0, limits=None):
+    """The family rows over the handles of a genome (families.py): rows[a] is arena a's families.ArenaRows.  Owners first,
+    on every handle; then the guide sites of each arena against the family members of every arena (homeologs sit on
+    different chromosomes).  limits: (pairs per launch, smallest slice), lowered by tests."""
+    if len(rows) != len(handles):
+        raise SearchInputError("%d family layouts for %d arenas" % (len(rows), len(handles)))
+    for h, r in zip(handles, rows):
+        h.set_families(r, cover_mm)
+        if limits:
+            h.family_set_limits(*limits)
+        h.family_assign()
+    for hq in handles:
+        for hc in handles:
+            hq.family_compare(hc)
+
+
+def check_family_geometry(pattern, pam_len):
+    """The owner of a site is defined by the selection's cut-site rule: a PAM of 3 letters on the 3' side."""
+    lo, _, _ = guide_region(pattern, pam_len)
+    if int(pam_len) != SPECIFICITY_PAM_LEN or lo != 0:
+        raise SearchInputError("gene families need a pattern with a PAM of %d letters on the 3' side" % SPECIFICITY_PAM_LEN)
+
+
+def search_self(genome, pattern, max_mm, pam_len, guide_pattern=None, score=None, budget=None, pairs_per_launch=None, families=None,
+                family_cover_mm=0, family_limits=None):
     """The self search over all arenas of `genome` (engine.Genome): see the module's docstring.  budget: device bytes
     one arena's handle may take (None: the library's default); SelfCapacityError (.needed) beyond it.
-    pairs_per_launch: lowers the pairs one compare launch covers (results do not depend on it)."""
+    pairs_per_launch: lowers the pairs one compare launch covers (results do not depend on it).
+    families: one families.ArenaRows per arena; the result then carries site_family, site_gene (the owner's gene index),
+    fam_counts, fam_sum (None without score=) and fam_cover per guide site (families.py has the definition), with
+    family_cover_mm as the cover limit C."""
     pattern, gp, max_mm, pam_len, scheme = check_self(pattern, max_mm, pam_len, guide_pattern, score)
     lo, hi, _ = guide_region(pattern, pam_len)
+    if families is not None:
+        check_family_geometry(pattern, pam_len)
+        if not isinstance(family_cover_mm, (int, np.integer)) or not 0 <= int(family_cover_mm) <= max_mm:
+            raise SearchInputError("the family cover limit must be an integer 0..%d (the search's mismatches), not %r" % (max_mm, family_cover_mm))
     handles = []
     try:
         _self_handles(genome, pattern, gp, pam_len, max_mm, scheme, budget, pairs_per_launch, handles)
         _self_compare_all(handles, max_mm)
+        fam_parts = []
+        if families is not None:
+            _family_compare_all(handles, families, int(family_cover_mm), family_limits)
+            for h, r in zip(handles, families):
+                owner, fam, fc, fs, cover = h.family_fetch(scheme is not None)
+                gene = np.full(owner.size, 0xFFFFFFFF, np.uint32)
+                has = owner != np.uint32(0xFFFFFFFF)
+                gene[has] = np.asarray(r.gene, np.uint32)[owner[has]]
+                fam_parts.append((fam, gene, fc, fs, cover))
         parts, guides, counts, sums = [], [], [], []
         cand, n_guides, stats = [0, 0], 0, {}
         for h, a, group in zip(handles, genome.arenas, genome.groups):
@@ -1004,14 +1100,21 @@ def search_self(genome, pattern, max_mm, pam_len, guide_pattern=None, score=None
                 sums.append(hs)
             for key, v in h.stats().items():
                 stats[key] = max(stats.get(key, 0.0), v) if key == "longest_launch_ms" else stats.get(key, 0.0) + v
+            if families is not None:
+                for key, v in h.family_stats().items():
+                    stats[key] = stats.get(key, 0.0) + v
     finally:
         for h in handles:
             h.close()
     sites = np.concatenate(parts) if parts else np.empty(0, SELF_SITE_DTYPE)
     order = np.lexsort((sites["strand"] == b"-", sites["position"], sites["contig"]))
-    return SelfSearchResult(sites[order], np.concatenate(guides)[order], np.concatenate(counts)[order],
-                            np.concatenate(sums)[order] if scheme is not None else None, tuple(cand),
-                            (int(stats.get("pairs", 0)), n_guides * (cand[0] + cand[1])), stats)
+    res = SelfSearchResult(sites[order], np.concatenate(guides)[order], np.concatenate(counts)[order],
+                           np.concatenate(sums)[order] if scheme is not None else None, tuple(cand),
+                           (int(stats.get("pairs", 0)), n_guides * (cand[0] + cand[1])), stats)
+    if families is not None:
+        res.site_family, res.site_gene, res.fam_counts, res.fam_cover = (np.concatenate([p[k] for p in fam_parts])[order] for k in (0, 1, 2, 4))
+        res.fam_sum = np.concatenate([p[3] for p in fam_parts])[order] if scheme is not None else None
+    return res
 
 
 SPECIFICITY_PAM_LEN = 3  # the scan's PAM: .GG / CC.
@@ -1034,7 +1137,8 @@ def check_specificity(guide_len, max_mm=3, candidate_pam="NRG", score="hsu2013")
     return pattern, gp, M, scheme
 
 
-def specificity_columns(genome, guide_len, max_mm=3, candidate_pam="NRG", score="hsu2013", budget=None, after_join=None):
+def specificity_columns(genome, guide_len, max_mm=3, candidate_pam="NRG", score="hsu2013", budget=None, after_join=None, families=None,
+                        family_cover_mm=0, family_limits=None):
     """The genome-wide specificity of every hit of a scanned `genome` (engine.Genome whose arenas hold the tables of a scan
     at guide_len): the self search of N * l + NGG guides among N * l + candidate_pam candidates over all arenas, then each
     arena's tables joined against its own handle on the GPU (the module's docstring, CSV join).  Returns one dict per
@@ -1042,17 +1146,29 @@ def specificity_columns(genome, guide_len, max_mm=3, candidate_pam="NRG", score=
     uint64, rows as Hits.contig(k) has them.  score=None: counts only (the sums are all-ones).  The dicts' list carries
     .stats, the handles' times summed over the arenas (join_ms among them).  after_join(arena index, handle, (counts_plus,
     sum_plus, counts_minus, sum_minus)) is called for every arena while its joined columns are still in HBM on the handle
-    (the guide selection reads them there: they die when the handles close)."""
+    (the guide selection reads them there: they die when the handles close).
+    families: one families.ArenaRows per arena (families.py has the definition); the family rows are computed after the
+    self search and joined like the plain rows: the dicts also carry fam_counts_plus / _minus (n, M + 1) uint32, fam_sum_plus
+    / _minus, fam_cover_plus / _minus (n,) uint64 and site_family_plus / _minus (n,) uint32 (0xFFFFFFFF: none), and after_join
+    gets them as a fifth argument, (counts, sum, cover, family) of '+' and then of '-'.  An unscored handle's fam_sum is 0."""
     pattern, gp, M, scheme = check_specificity(guide_len, max_mm, candidate_pam, score)
+    if families is not None and (not isinstance(family_cover_mm, (int, np.integer)) or not 0 <= int(family_cover_mm) <= M):
+        raise SearchInputError("the family cover limit must be an integer 0..%d (the join's mismatches), not %r" % (M, family_cover_mm))
     out = [None] * genome.n_contigs
     handles, stats = [], {}
     try:
         _self_handles(genome, pattern, gp, SPECIFICITY_PAM_LEN, M, scheme, budget, None, handles)
         _self_compare_all(handles, M)
+        if families is not None:
+            _family_compare_all(handles, families, int(family_cover_mm), family_limits)
         for index, (h, a, group) in enumerate(zip(handles, genome.arenas, genome.groups)):
             cp, sp, cm, sm = h.join_hits(guide_len)
+            fam = h.family_join_hits(guide_len) if families is not None else None
             if after_join is not None:
-                after_join(index, h, (cp, sp, cm, sm))
+                if fam is None:
+                    after_join(index, h, (cp, sp, cm, sm))
+                else:
+                    after_join(index, h, (cp, sp, cm, sm), fam)
             pos_plus, pos_minus = np.empty(len(sp), np.uint32), np.empty(len(sm), np.uint32)
             nat.check(nat.lib().crp_fetch_hits(a._h, pos_plus.ctypes.data_as(nat.u32p), None, None, pos_minus.ctypes.data_as(nat.u32p), None,
                                                None), "crp_fetch_hits", a._engine._ctx)
@@ -1062,8 +1178,14 @@ def specificity_columns(genome, guide_len, max_mm=3, candidate_pam="NRG", score=
                 p0, p1 = np.searchsorted(pos_plus, [starts[j], ends[j]], "left")
                 m0, m1 = np.searchsorted(pos_minus, [starts[j], ends[j]], "left")
                 out[k] = dict(self_counts_plus=cp[p0:p1], self_sum_plus=sp[p0:p1], self_counts_minus=cm[m0:m1], self_sum_minus=sm[m0:m1])
+                if fam is not None:
+                    for name, plus, minus in zip(("fam_counts", "fam_sum", "fam_cover", "site_family"), fam[:4], fam[4:]):
+                        out[k][name + "_plus"], out[k][name + "_minus"] = plus[p0:p1], minus[m0:m1]
             for key, v in h.stats().items():
                 stats[key] = max(stats.get(key, 0.0), v) if key == "longest_launch_ms" else stats.get(key, 0.0) + v
+            if families is not None:
+                for key, v in h.family_stats().items():
+                    stats[key] = stats.get(key, 0.0) + v
     finally:
         for h in handles:
             h.close()

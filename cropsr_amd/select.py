@@ -66,6 +66,13 @@ of a canonical donor or acceptor site of g's primary transcript under the row's 
 percentages of that transcript's coding length and the window holds no more than the given number of targets.  With edit
 limits as well (cytosine editor only) the two tests are alternatives.  Not together with coding limits or the pair selection.
 
+Gene families (families.py has the definition; csrc/crp_select_family.hip): with a family table every
+(gene g, row) has outside_mm0, outside_hit_sum, members_hit and family_size -- where the row's joined site_family is g's
+family, counts[0] - fam_counts[0], hit_sum - fam_sum, popcount(fam_cover) and |F|; else counts[0], hit_sum, 1 and the size
+of g's family (1 for none).  Family limits are ANDed onto the predicate after the rest: outside_mm0 <= max_perfect_outside,
+outside_hit_sum <= max_hit_sum_for(min_specificity_outside), members_hit >= min_members ("all": family_size).  max_perfect
+and min_specificity keep their meaning on the full counts.  Not together with coding, edit or splice limits or pairs.
+
 This module lays the genes out per arena, converts a wanted specificity into the integer bound the kernel compares,
 drives crp_select_* and turns the per-arena results into one table over the genes of the GFF.
 """
@@ -157,6 +164,36 @@ class PairParams:
         return nat.SelectPairParams(self.k, self.dmin, self.dmax, self.mask, int(self.frameshift))
 
 
+class FamilyLimits:
+    """The family limits of a selection: min_members (an int 1..64 or "all": every member of the gene's family),
+    max_perfect_outside (perfect copies outside the family, at most) and min_specificity_outside (of what lies outside the
+    family, at least; the bound on outside_hit_sum comes from max_hit_sum_for, like min_specificity's).  None: no bound."""
+
+    def __init__(self, min_members=None, max_perfect_outside=None, min_specificity_outside=None):
+        if min_members is None:
+            self.min_members = 0
+        elif isinstance(min_members, str):
+            if min_members.strip().lower() != "all":
+                raise ValueError("min_members is a number of members or 'all', not %r" % (min_members,))
+            self.min_members = nat.SELECT_ALL_MEMBERS
+        elif isinstance(min_members, (int, np.integer)) and 1 <= int(min_members) <= 64:
+            self.min_members = int(min_members)
+        else:
+            raise ValueError("min_members is 1..64 (a family has at most 64 members) or 'all', not %r" % (min_members,))
+        if max_perfect_outside is not None and (not isinstance(max_perfect_outside, (int, np.integer)) or not 0 <= int(max_perfect_outside) < NO_BOUND_MM0):
+            raise ValueError("max_perfect_outside is a count, not %r" % (max_perfect_outside,))
+        self.max_mm0_outside = NO_BOUND_MM0 if max_perfect_outside is None else int(max_perfect_outside)
+        self.max_hit_sum_outside = NO_BOUND_SUM if min_specificity_outside is None else max_hit_sum_for(min_specificity_outside)
+
+    def astuple(self):
+        return self.max_hit_sum_outside, self.max_mm0_outside, self.min_members
+
+    def passes(self, outside_mm0, outside_hit_sum, members_hit, family_size):
+        """The host's statement of the device's test, on arrays or numbers."""
+        need = family_size if self.min_members == nat.SELECT_ALL_MEMBERS else self.min_members
+        return (outside_mm0 <= self.max_mm0_outside) & (outside_hit_sum <= self.max_hit_sum_outside) & (members_hit >= need)
+
+
 class Request:
     """A selection for a backend's scan: Params, the annotate.Request that names the genes, slice_rows (None: the
     library's default; results do not depend on it) and the limits on the guide properties (properties.py), as counts:
@@ -180,11 +217,28 @@ class Request:
     cbe); with limits a row passes only if the edit destroys a splice site inside them for the gene it is selected for --
     or, with edit_limits given as well, writes a stop codon inside those.  Splice limits are refused with coding limits and
     with pairs, and the editor abe with edit limits.  edit: with the splice test, whether the stop-codon fields are wanted
-    too (they always come with edit limits)."""
+    too (they always come with edit limits).
+    families (families.FamilyTable of the annotation's genes): gene families (families.py).  The scan's specificity join then
+    also computes and joins the family rows (family_cover_mm: the cover limit C), and the Selection carries family,
+    family_size, members_hit, members, outside_mm0, outside_hit_sum and fam_cover of its rows, for the gene each was selected
+    for.  min_members / max_perfect_outside / min_specificity_outside (FamilyLimits) are limits: a row passes only if they
+    hold for the gene it is selected for.  They need families, and are refused with coding, edit or splice limits and with
+    pairs: one kernel per predicate."""
 
     def __init__(self, params, annotation, slice_rows=None, gc_min=None, gc_max=None, max_run=None, max_t_run=None, max_stem=None,
                  repair_flank=None, min_mh=None, min_oof=None, pairs=None, pair_slice_rows=None, coding=False, coding_limits=None,
-                 edit_window=None, edit_limits=None, editor=None, splice_limits=None, edit=None):
+                 edit_window=None, edit_limits=None, editor=None, splice_limits=None, edit=None, families=None, family_cover_mm=0,
+                 min_members=None, max_perfect_outside=None, min_specificity_outside=None):
+        self.families, self.family_cover_mm = families, int(family_cover_mm)
+        self.family_limits = None
+        if any(v is not None for v in (min_members, max_perfect_outside, min_specificity_outside)):
+            if families is None:
+                raise ValueError("min_members, max_perfect_outside and min_specificity_outside need a family table (families=)")
+            if coding_limits is not None or edit_limits is not None or splice_limits is not None:
+                raise ValueError("family limits and coding, edit or splice limits are different kernels' predicates: one or the other")
+            if pairs is not None:
+                raise ValueError("family limits are relative to the gene; the pair selection's eligibility is per table row: one or the other")
+            self.family_limits = FamilyLimits(min_members, max_perfect_outside, min_specificity_outside)
         self.pairs, self.pair_slice_rows = pairs, pair_slice_rows
         self.splice = editor is not None or splice_limits is not None
         self.splice_limits = splice_limits
@@ -316,6 +370,45 @@ class ArenaSelect:
                                                    off.ctypes.data_as(nat.u32p), cover.ctypes.data_as(nat.u32p)), "crp_select_coding_eval", self._ctx)
         return off[:gene_row.size], cover[:gene_row.size]
 
+    def set_family(self, gene_family, family_size):
+        """Per gene of this handle its family id (families.NONE: none) and that family's size (1 for none); None, None clears."""
+        if gene_family is None:
+            nat.check(nat.lib().crp_select_set_family(self._h, None, None, 0), "crp_select_set_family", self._ctx)
+            return
+        f, n = np.ascontiguousarray(gene_family, dtype=np.uint32), np.ascontiguousarray(family_size, dtype=np.uint32)
+        if f.shape != n.shape or f.ndim != 1:
+            raise ValueError("gene_family and family_size must be 1-d arrays of one length")
+        pad = lambda a: a if a.size else np.zeros(1, np.uint32)  # (a handle without genes still gets pointers)
+        nat.check(nat.lib().crp_select_set_family(self._h, pad(f).ctypes.data_as(nat.u32p), pad(n).ctypes.data_as(nat.u32p), f.size),
+                  "crp_select_set_family", self._ctx)
+
+    def set_family_limits(self, limits):
+        """limits: FamilyLimits, or None to clear them."""
+        lim = None if limits is None else ctypes.byref(nat.SelectFamilyLimits(*limits.astuple()))
+        nat.check(nat.lib().crp_select_set_family_limits(self._h, lim), "crp_select_set_family_limits", self._ctx)
+
+    def family_eval(self, self_search, gene_row, packed_row):
+        """(outside_mm0 uint32, outside_hit_sum uint64, members_hit uint32, family_size uint32, fam_cover uint64) of the rows
+        packed_row (sel's packing) for the genes gene_row of this handle, from the joined columns of self_search
+        (search.ArenaSelfSearch); fam_cover is 0 where the row's family is not the gene's."""
+        gene_row, packed_row = np.ascontiguousarray(gene_row, dtype=np.uint32), np.ascontiguousarray(packed_row, dtype=np.uint32)
+        if gene_row.shape != packed_row.shape or gene_row.ndim != 1:
+            raise ValueError("gene_row and packed_row must be 1-d arrays of one length")
+        n = gene_row.size
+        mm0, hit, size = (np.zeros(max(1, n), np.uint32) for _ in range(3))
+        hs, cover = np.zeros(max(1, n), np.uint64), np.zeros(max(1, n), np.uint64)
+        nat.check(nat.lib().crp_select_family_eval(self._h, self_search._h if self_search is not None else None,
+                                                   gene_row.ctypes.data_as(nat.u32p), packed_row.ctypes.data_as(nat.u32p), n,
+                                                   mm0.ctypes.data_as(nat.u32p), hs.ctypes.data_as(nat.u64p), hit.ctypes.data_as(nat.u32p),
+                                                   size.ctypes.data_as(nat.u32p), cover.ctypes.data_as(nat.u64p)), "crp_select_family_eval",
+                  self._ctx)
+        return mm0[:n], hs[:n], hit[:n], size[:n], cover[:n]
+
+    def family_stats(self):
+        out = np.zeros(2, dtype=np.float64)
+        nat.check(nat.lib().crp_select_family_stats(self._h, out.ctypes.data_as(nat.f64p), 2), "crp_select_family_stats", self._ctx)
+        return dict(zip(("family_select_ms", "family_eval_ms"), (float(v) for v in out)))
+
     def coding_stats(self):
         out = np.zeros(3, dtype=np.float64)
         nat.check(nat.lib().crp_select_coding_stats(self._h, out.ctypes.data_as(nat.f64p), 3), "crp_select_coding_stats", self._ctx)
@@ -433,6 +526,9 @@ class Selection:
         self.cds_offset = self.cds_length = self.transcripts_cut = self.transcripts = None
         self.edit_targets = self.stop_codons = self.stop_offset = None
         self.splice_targets = self.donors = self.acceptors = self.donor_offset = self.acceptor_offset = None
+        # with gene families (families.py), for the gene each row was selected for: (n,) arrays, and members: per row the
+        # labels of the family members the guide covers (the gene itself where the row's family is not the gene's)
+        self.outside_mm0 = self.outside_hit_sum = self.members_hit = self.family_size = self.fam_cover = self.members = None
 
     def of_gene(self, g):
         return self.rows[self.rows["gene"] == g]
@@ -464,7 +560,8 @@ def assemble(labels, k, arenas, stats=None):
     coded = any(a.get("coding") is not None for a in arenas)
     edited = any(a.get("edit") is not None for a in arenas)
     spliced = any(a.get("splice") is not None for a in arenas)
-    rparts, kparts, eparts, xparts = [], [], [], []
+    familied = any(a.get("family") is not None for a in arenas)
+    rparts, kparts, eparts, xparts, fparts = [], [], [], [], []
     for a in arenas:
         gene = np.asarray(a["gene"], dtype=np.int64)
         np.add.at(n_in, gene, np.asarray(a["n_in"], dtype=np.int64))
@@ -513,6 +610,11 @@ def assemble(labels, k, arenas, stats=None):
             xparts.append(np.stack([np.asarray(sp[key], np.uint32).reshape(gene.size, -1)[r, c]
                                     for key in ("targets", "donors", "acceptors", "donor_off", "acceptor_off")]
                                    + [np.asarray(sp["length"], np.uint32)[r]], axis=1) if r.size else np.empty((0, 6), np.uint32))
+        if familied:
+            fm = a["family"]
+            fparts.append(np.stack([np.asarray(fm[key]).reshape(gene.size, -1)[r, c].astype(np.uint64)
+                                    for key in ("outside_mm0", "outside_hit_sum", "members_hit", "family_size", "fam_cover")], axis=1)
+                          if r.size else np.empty((0, 5), np.uint64))
     rows = np.concatenate(parts) if parts else np.empty(0, ROW_DTYPE)
     counts = np.concatenate(cparts) if cparts else None
     sums = np.concatenate(sparts) if sparts else None
@@ -539,6 +641,10 @@ def assemble(labels, k, arenas, stats=None):
     if eparts:
         ed = np.concatenate(eparts)[order][keep]
         out.edit_targets, out.stop_codons, out.stop_offset, out.cds_length = (ed[:, j].copy() for j in range(4))
+    if fparts:
+        fm = np.concatenate(fparts)[order][keep]
+        out.outside_mm0, out.members_hit, out.family_size = (fm[:, j].astype(np.uint32) for j in (0, 2, 3))
+        out.outside_hit_sum, out.fam_cover = fm[:, 1].copy(), fm[:, 4].copy()
     if xparts:
         sp = np.concatenate(xparts)[order][keep]
         out.splice_targets, out.donors, out.acceptors, out.donor_offset, out.acceptor_offset, out.cds_length = (sp[:, j].copy() for j in range(6))
@@ -644,9 +750,27 @@ def select_arena(genome, a, request, handle=None, flags=None, extras=None):
                 sel.set_edit_limits(request.edit_window, request.edit_limits)
             if splice and request.splice_limits is not None:
                 sel.set_splice_limits(request.splice_window, request.editor, request.splice_limits)
+        table = getattr(request, "families", None)
+        if table is not None:
+            g = np.asarray(gene, dtype=np.int64)
+            gene_family = table.gene_family[g] if g.size else np.zeros(0, np.uint32)
+            size = np.array([table.family_size(int(x)) for x in g.tolist()], dtype=np.uint32)
+            sel.set_family(gene_family, size)
+            sel.set_family_limits(request.family_limits)
         sel.run(request.params, handle)
         n_in, n_pass, picked = sel.fetch()
         stats = sel.stats()
+        if table is not None and extras is not None:
+            r, c = np.nonzero(picked != NONE)
+            fm = dict(outside_mm0=np.zeros(picked.shape, np.uint32), outside_hit_sum=np.zeros(picked.shape, np.uint64),
+                      members_hit=np.zeros(picked.shape, np.uint32), family_size=np.zeros(picked.shape, np.uint32),
+                      fam_cover=np.zeros(picked.shape, np.uint64))
+            got = sel.family_eval(handle, r.astype(np.uint32), picked[r, c])
+            for key, v in zip(("outside_mm0", "outside_hit_sum", "members_hit", "family_size", "fam_cover"), got):
+                fm[key][r, c] = v
+            extras["family"] = fm
+        if table is not None:
+            stats.update(sel.family_stats())
         if edit and extras is not None:
             from .baseedit import NO_STOP
             r, c = np.nonzero(picked != NONE)

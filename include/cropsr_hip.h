@@ -766,6 +766,49 @@ int crp_search_self_join_hits(crp_search_self *self, int guide_len, uint32_t *co
 int crp_search_self_join_device(crp_search_self *self, void **counts_plus, void **hit_sum_plus, void **counts_minus,
                                 void **hit_sum_minus);
 
+/* ---- gene families on a self-search handle ------------------------------------------- */
+/* In a polyploid a guide's near copies are mostly the gene's own homeologs.  With the family genes of its arena on
+ * the handle, the handle says which of them a candidate site cuts in and gives every guide site a second row that
+ * counts only the candidates of its own family, so the difference to the plain row is what lies outside the family.
+ * The handle's PAM must be its pattern's last 3 letters (T = l + 3): a '+' site at forward start p cuts at p + l - 3,
+ * a '-' site at forward start j cuts at j.
+ *
+ * Rows r = 0 .. n_rows - 1 are the family genes that have a range in this arena, in GFF order: the closed range
+ * [lo, hi] of arena positions, a family id (any value but 0xFFFFFFFF, the same id on every handle of a genome) and the
+ * gene's bit in its family's cover word (member < 64).  cover_mm (0 .. max_mm): a guide site within that many
+ * mismatches covers the gene it cuts in.  Replaces earlier families; n_rows = 0 with lo = NULL takes them off.
+ * Adds 4 (max_mm + 1) + 24 bytes per candidate and 24 per row to the handle, counted against its budget
+ * (CRP_ERR_CAPACITY).  CRP_ERR_INVALID with a crp_last_error text: another PAM geometry, cover_mm outside 0 .. max_mm,
+ * a member bit of 64 or more, family id 0xFFFFFFFF. */
+int crp_search_self_set_families(crp_search_self *self, const uint32_t *lo, const uint32_t *hi, const uint32_t *family,
+                                 const uint32_t *member, uint64_t n_rows, int cover_mm);
+/* Lowers the pairs one family compare launch covers and the smallest slice of a member's run (0: the defaults, 2^36
+ * and 2 048; a slice has at least 8 candidates).  Results do not depend on either. */
+int crp_search_self_family_set_limits(crp_search_self *self, uint64_t pairs_per_launch, uint32_t slice_min);
+/* Owner and family of every candidate: the owner is the smallest row whose range holds the site's cut.  Zeroes the
+ * family rows; a guide site's cover word starts with its owner's bit.  CRP_ERR_STATE without families. */
+int crp_search_self_family_assign(crp_search_self *self);
+/* The guide sites of `guides` that have an owner against the candidates of `candidates` that have an owner of the same
+ * family, all pairs, compared and valued as crp_search_self_compare does (the guides handle's scheme state and
+ * max_mm); adds into the family rows of `guides`.  Once per ordered pair of handles, after both were assigned
+ * (CRP_ERR_STATE otherwise); it needs no ordering. */
+int crp_search_self_family_compare(crp_search_self *guides, crp_search_self *candidates);
+/* The family rows of the guide sites, in the order of crp_search_self_fetch: the owner's row (0xFFFFFFFF: none), its
+ * family id (0xFFFFFFFF: none), fam_counts (max_mm + 1 per site: the candidates of the same family at k mismatches,
+ * the site itself not counted), fam_sum (their values) and fam_cover (bit m: the site cuts in member m, or a guide
+ * site that cuts in member m lies within cover_mm).  Any pointer may be NULL. */
+int crp_search_self_family_fetch(crp_search_self *self, uint32_t *owner, uint32_t *family, uint32_t *counts, uint64_t *sum,
+                                 uint64_t *cover, uint64_t cap);
+/* The family rows handed to the hits of the arena's last scan, as crp_search_self_join_hits hands the plain rows (the
+ * same sites join): counts, sum, cover and family id per hit of the '+' and the '-' table.  An unjoined hit gets
+ * all-ones counts and sum, cover 0 and family 0xFFFFFFFF; a joined hit without a family zeros and family 0xFFFFFFFF. */
+int crp_search_self_family_join_hits(crp_search_self *self, int guide_len, uint32_t *counts_plus, uint64_t *sum_plus,
+                                     uint64_t *cover_plus, uint32_t *family_plus, uint32_t *counts_minus, uint64_t *sum_minus,
+                                     uint64_t *cover_minus, uint32_t *family_minus);
+/* out[0] ms of the bounds and assign kernels, out[1] ms of family compare kernels, out[2] pairs compared, out[3]
+ * family compare launches, out[4] device bytes the families add, out[5] ms of the family join.  n <= 6. */
+int crp_search_self_family_stats(const crp_search_self *self, double *out, int n);
+
 /* ---- guide selection: the best K guides of every gene -------------------------------- */
 /* The gene rows of an annotation (type `gene`, file order): index of the seqid (crp_annotation_seqid), start and end
  * as the GFF gives them (1-based, closed), and the labels "gene:<ident>" -- without the annotation_info suffix -- back
@@ -1062,6 +1105,38 @@ int crp_select_splice_eval(crp_select *select, const crp_select_edit_window *win
 /* out[0] ms of the select launches of the last crp_select_run that had splice limits (0: none), out[1] ms of the last
  * crp_select_splice_eval's kernel (HIP events), out[2] the letters of the window last used.  n: how many to write (<= 3). */
 int crp_select_splice_stats(const crp_select *select, double *out, int n);
+
+/* ---- gene families in the selection (opt-in) ------------------------------------------- */
+/* Per gene of the handle (the rows of crp_select_create) its family id (0xFFFFFFFF: none; the ids of
+ * crp_search_self_set_families) and the size of that family (1 for none).  For gene g with family f and a table row whose
+ * joined site_family equals f (and is not none):
+ *   outside_mm0 = counts[0] - fam_counts[0]   outside_hit_sum = hit_sum - fam_sum   members_hit = popcount(fam_cover)
+ * and for every other row -- a gene in no family, a row that belongs to an overlapping gene of another family --
+ *   outside_mm0 = counts[0]                   outside_hit_sum = hit_sum             members_hit = 1
+ * n_genes must be the handle's; NULL, NULL, 0 takes the families off. */
+int crp_select_set_family(crp_select *select, const uint32_t *gene_family, const uint32_t *family_size, uint64_t n_genes);
+/* With limits a row passes crp_select_run for gene g only if, beyond the rest of the predicate, outside_mm0 <=
+ * max_mm0_outside, outside_hit_sum <= max_hit_sum_outside (0xFFFFFFFF / 2^64 - 1: no bound) and members_hit >=
+ * min_members, where CRP_SELECT_ALL_MEMBERS means the size of g's family.  The run then needs crp_select_set_family and a
+ * self-search handle with both joins (CRP_ERR_STATE otherwise).  Not together with coding, edit or splice limits, and not
+ * in crp_select_run_pairs (CRP_ERR_UNSUPPORTED): one kernel per predicate.  NULL clears the limits. */
+#define CRP_SELECT_ALL_MEMBERS 0xFFFFFFFFu
+typedef struct crp_select_family_limits {
+    uint64_t max_hit_sum_outside;
+    uint32_t max_mm0_outside, min_members;
+} crp_select_family_limits;
+int crp_select_set_family_limits(crp_select *select, const crp_select_family_limits *limits);
+/* The four values of n queries (gene_row[q]: a gene of the handle; packed_row[q]: a table row in sel's packing), one kernel
+ * lane each, from the joined columns of `self`, and fam_cover[q]: the row's cover word where the row's family is the
+ * gene's (the members behind members_hit), 0 where it is not and the gene itself is the one member.  Needs crp_select_set_family and both joins on the arena's current tables,
+ * no limits and no run.  CRP_ERR_INVALID with a crp_last_error text: a gene or a row out of range (checked on the host;
+ * nothing is launched). */
+int crp_select_family_eval(crp_select *select, crp_search_self *self, const uint32_t *gene_row, const uint32_t *packed_row, uint64_t n,
+                           uint32_t *outside_mm0, uint64_t *outside_hit_sum, uint32_t *members_hit, uint32_t *family_size,
+                           uint64_t *fam_cover);
+/* out[0] ms of the select launches of the last crp_select_run that had family limits (0: none), out[1] ms of the last
+ * crp_select_family_eval's kernel (HIP events).  n: how many to write (<= 2). */
+int crp_select_family_stats(const crp_select *select, double *out, int n);
 
 /* ---- options -------------------------------------------------------------- */
 /* CRP_OPT_TWO_PASS (value 0/1, default 0): with 0 crp_scan_score is ONE kernel launch; the
