@@ -1,7 +1,8 @@
 """Gene families of the self search (cropsr_amd/families.py, crp_search_self_set_families .. crp_search_self_family_*;
 DESIGN.md section 23): the parser and its refusals, the family table and the per-arena rows against restatements, the two
 statements of the definition on the case genome, and the ABI without a GPU; the device's family rows, their join and the
-error codes against the reference, exactly, on the GPU.  Everything compared is an integer."""
+error codes against the reference, exactly, on the GPU; the selection with family limits at the default slices and with its
+genes cut into slices of 64, alone and behind the predicate's other terms.  Everything compared is an integer."""
 import ctypes
 import os
 import re
@@ -492,19 +493,22 @@ def test_family_limits_and_request_refusals():
             sel.Request(params, None, families=table, max_perfect_outside=0, **other)
 
 
-def _reference_selection(case, tables, columns, fam_ref, row_of, K, max_perfect=None, max_hit_sum=None, limits=(None, None, None)):
+def _reference_selection(case, tables, columns, fam_ref, row_of, K, max_perfect=None, max_hit_sum=None, limits=(None, None, None),
+                         also=None, min_score=0.0):
     """Per gene (n_in, n_pass, [(contig, position, strand, (outside_mm0, outside_hit_sum, members_hit, family_size), the site's
     row in the reference)], [each row's index in its contig's strand table]): a plain
     loop over the genes and the rows of their contig's tables; the plain joined columns are the device's (tests/
-    test_specificity_join.py holds them), the family columns the reference's."""
+    test_specificity_join.py holds them), the family columns the reference's.  min_score and also(contig, strand, row index of
+    the contig's strand table) -> bool are the predicate's other terms: a row passes only if they hold as well."""
     out = []
+    more = lambda kc, strand, i, x: float(x) >= float(min_score) and (also is None or bool(also(kc, strand, i)))
     for g, (_, kc, lo, hi) in enumerate(case.genes):
         rows = []
         for strand, name in ((0, "plus"), (1, "minus")):
             pos, score = tables[kc]["pos_" + name], tables[kc]["score_" + name]
-            if columns is None:  # (no specificity join: every scored row of the gene passes)
+            if columns is None:  # (no specificity join: every scored row of the gene passes the joined terms)
                 cuts = [int(p) - (0 if strand else 3) for p in pos.tolist()]
-                rows += [(True, -int(np.float64(score[i]).view(np.uint64)), cuts[i], strand, int(pos[i]), None, None, i)
+                rows += [(more(kc, strand, i, score[i]), -int(np.float64(score[i]).view(np.uint64)), cuts[i], strand, int(pos[i]), None, None, i)
                          for i in range(pos.size) if score[i] != -1.0 and lo <= cuts[i] <= hi]
                 continue
             c0, hs = columns[kc]["self_counts_" + name][:, 0], columns[kc]["self_sum_" + name]
@@ -520,7 +524,7 @@ def _reference_selection(case, tables, columns, fam_ref, row_of, K, max_perfect=
                     values = fref.selection_values(g, case.gene_family, case.sizes, int(fam_ref["site_family"][r]), int(c0[i]), int(hs[i]),
                                                    int(fam_ref["fam_counts"][r][0]), fam_ref["fam_sum"][r], fam_ref["fam_cover"][r])
                     ok = ((max_perfect is None or int(c0[i]) <= max_perfect) and (max_hit_sum is None or int(hs[i]) <= max_hit_sum)
-                          and fref.passes_family(values, *limits))
+                          and fref.passes_family(values, *limits) and more(kc, strand, i, score[i]))
                 rows.append((ok, -int(np.float64(score[i]).view(np.uint64)), cut, strand, int(pos[i]), values, r, i))
         passing = sorted(r[1:] for r in rows if r[0])
         out.append((len(rows), len(passing), [(kc, p, st, v, r) for _, _, st, p, v, r, _ in passing[:K]], [r[-1] for r in passing[:K]]))
@@ -548,8 +552,52 @@ def _check_selection_file(case, got, want, fam_ref):
     return at
 
 
+SLICES = pytest.mark.parametrize("slice_rows", [None, 64], ids=["default-slices", "slices-of-64"])
+CUT_GENES = ("A1", "A2", "A3", "R255", "R256", "R257", "B_outer")  # more than 64 rows each: cut and merged at slices of 64
+
+
+def _assert_selection_equals(case, got, want):
+    """A device Selection with family fields against _reference_selection's rows, field by field."""
+    assert got.n_in.tolist() == [w[0] for w in want] and got.n_pass.tolist() == [w[1] for w in want]
+    at = 0
+    for gi, (_, _, rows, _) in enumerate(want):
+        for rank, (kc, pos, strand, values, _) in enumerate(rows):
+            row = got.rows[at]
+            assert (row["gene"], row["rank"], row["contig"], row["position"], row["strand"]) == (gi, rank + 1, kc, pos, b"+-"[strand:strand + 1])
+            assert (int(got.outside_mm0[at]), int(got.outside_hit_sum[at]), int(got.members_hit[at]), int(got.family_size[at])) == values
+            members = got.members[at]
+            assert len(members) == values[2] and all(m in got.labels for m in members)
+            if values[2] == 1 and case.gene_family[gi] == NONE:
+                assert members == [got.labels[gi]]
+            at += 1
+    assert at == len(got.rows)
+
+
+def _run_lengths(case, tables):
+    """Rows of every gene's two runs in its contig's tables, scored or not: what the kernel's runs hold (tests/test_select.py
+    has the same restatement per arena; a gene here lies in one contig, so in one arena)."""
+    out = []
+    for _, kc, lo, hi in case.genes:
+        cp, cm = tables[kc]["pos_plus"].astype(np.int64) - 3, tables[kc]["pos_minus"].astype(np.int64)
+        out.append(int(((cp >= lo) & (cp <= hi)).sum() + ((cm >= lo) & (cm <= hi)).sum()))
+    return np.array(out)
+
+
+def _assert_the_case_cuts(case, tables, stats, slice_rows):
+    """At slices of 64 the genes of more than 64 rows go through the merge, the named ones among them; merged_genes is their
+    number, summed over the arenas (select.sum_stats).  At the default nothing is cut."""
+    n = _run_lengths(case, tables)
+    if slice_rows is None:
+        assert n.max() < 65536 and stats["merged_genes"] == 0
+        return
+    assert all(n[case.idents.index(i)] > slice_rows for i in CUT_GENES)
+    assert stats["merged_genes"] == int((n > slice_rows).sum()) >= len(CUT_GENES)
+    assert stats["items"] == int(np.maximum(1, -(-n // slice_rows)).sum())
+
+
 @pytest.mark.gpu
-def test_gpu_selection_with_family_limits(engine, case):
+@SLICES
+def test_gpu_selection_with_family_limits(engine, case, slice_rows):
     from cropsr_amd import select as sel
     fam_ref = case.rows(3, "hsu2013", 0)
     row_of = {s: r for r, s in enumerate(fam_ref["sites"])}
@@ -563,26 +611,15 @@ def test_gpu_selection_with_family_limits(engine, case):
         s1_sums = None
 
         def run(K, params=None, **limits):
-            req = sel.Request(sel.Params(K, **(params or {})), areq, families=table, **limits)
+            req = sel.Request(sel.Params(K, **(params or {})), areq, slice_rows, families=table, **limits)
             got = g.scan_score(20, specificity={}, select=req).selection
             bound = None if limits.get("min_specificity_outside") is None else sel.max_hit_sum_for(limits["min_specificity_outside"])
             p = params or {}
             want = _reference_selection(case, tables, plain.columns, fam_ref, row_of, K, p.get("max_perfect"),
                                         None if p.get("min_specificity") is None else sel.max_hit_sum_for(p["min_specificity"]),
                                         (limits.get("min_members"), limits.get("max_perfect_outside"), bound))
-            assert got.n_in.tolist() == [w[0] for w in want] and got.n_pass.tolist() == [w[1] for w in want]
-            at = 0
-            for gi, (_, _, rows, _) in enumerate(want):
-                for rank, (kc, pos, strand, values, _) in enumerate(rows):
-                    row = got.rows[at]
-                    assert (row["gene"], row["rank"], row["contig"], row["position"], row["strand"]) == (gi, rank + 1, kc, pos, b"+-"[strand:strand + 1])
-                    assert (int(got.outside_mm0[at]), int(got.outside_hit_sum[at]), int(got.members_hit[at]), int(got.family_size[at])) == values
-                    members = got.members[at]
-                    assert len(members) == values[2] and all(m in got.labels for m in members)
-                    if values[2] == 1 and case.gene_family[gi] == NONE:
-                        assert members == [got.labels[gi]]
-                    at += 1
-            assert at == len(got.rows)
+            _assert_selection_equals(case, got, want)
+            _assert_the_case_cuts(case, tables, got.stats, slice_rows)
             return got, want
 
         for K in (1, 5, 64):
@@ -622,6 +659,169 @@ def test_gpu_selection_with_family_limits(engine, case):
     finally:
         g.close()
         ann.close()
+
+
+# ------------------------------------------------------------------ family limits with the predicate's other terms
+# CDS rows for require_cds, on a copy of the case GFF (family_cases.build()'s text stays what the other tests read): parts of
+# the three homeologs and of the nested pair
+CDS_ROWS = (("chrA", 1201, 1700, "A1.cds"), ("chrB", 2250, 2900, "A2.cds"), ("chrD", 3500, 4100, "A3.cds"), ("chrA", 2900, 3300, "B.cds"))
+FAMILY_LIMITS = dict(min_members=2, max_perfect_outside=0)
+REPAIR_LIMITS = dict(min_mh=300, min_oof=55)
+
+
+def _property_limits():
+    from test_select_pairs import PROPERTY_LIMITS as L
+    return dict(gc_min=L.gc_min, gc_max=L.gc_max, max_run=L.max_run, max_t_run=L.max_t_run, max_stem=L.max_stem)
+
+
+def _combinations():
+    """name -> (Params' keywords, Request's keywords): each of the other terms with the family limits, and all at once."""
+    one = {"min-score": (dict(min_score=0.2), {}), "specificity": (dict(max_perfect=1, min_specificity=0.3), {}),
+           "cds": (dict(require_cds=True), {}), "properties": ({}, _property_limits()), "repair": ({}, dict(REPAIR_LIMITS))}
+    everything = ({}, {})
+    for params, request in one.values():
+        everything[0].update(params)
+        everything[1].update(request)
+    return dict(one, all=everything)
+
+
+COMBINATIONS = ("min-score", "specificity", "cds", "properties", "repair", "all")
+
+
+class Combined:
+    """The case with CDS rows, and per contig the truth of the other terms for the rows of given tables: the packed
+    properties and repair scores from the references (tests/guide_properties_reference.py, tests/repair_reference.py) and the
+    CDS verdict from the annotation's label flags (oracle/annotate_oracle.host_join over the rows, select_reference.cds_flags
+    over the strings)."""
+
+    def __init__(self, case, tmp):
+        self.case = case
+        self.gff_path = os.path.join(tmp, "case_cds.gff")
+        with open(self.gff_path, "w") as f:
+            f.write(case.gff + "".join("%s\ttest\tCDS\t%d\t%d\t.\t+\t0\tID=%s\n" % (n, lo + 1, hi + 1, i) for n, lo, hi, i in CDS_ROWS))
+        self.ann = annotate.Annotation(self.gff_path)
+        assert self.ann.genes()[0] == ["gene:" + i for i in case.idents]  # the genes are what they were
+        self.table = fam.FamilyTable(fam.parse_families(case.families), self.ann.genes()[0])
+        self._want = {}
+
+    def close(self):
+        self.ann.close()
+
+    def truth(self, tables):
+        import guide_properties_reference as gpref
+        import repair_reference as rref
+        from oracle import annotate_oracle
+        flags = selref.cds_flags([self.ann.strings[k] for k in range(len(self.ann.strings))])
+        assert 0 < flags.sum() < flags.size
+        out = []
+        for k, (name, text) in enumerate(zip(self.case.names, self.case.contigs)):
+            h = tables[k]
+            feat = annotate_oracle.host_join(self.ann, name, 0, 0, h, 20, len(text))
+            t = {}
+            for strand, s in ((0, "plus"), (1, "minus")):
+                ids = np.asarray(feat[strand]).astype(np.int64)
+                t["cds_" + s] = (ids != NONE) & (np.concatenate([flags, [0]])[np.where(ids == NONE, flags.size, ids)] != 0)
+                t["props_" + s] = gpref.column_numpy(text, h["pos_" + s], bool(strand), 20)
+                t["repair_" + s] = rref.column_numpy(text, h["pos_" + s], bool(strand), 30)
+            out.append(t)
+        return out
+
+    def want(self, key, tables, columns, name):
+        """_reference_selection at K = 5 for a combination (None: the family limits alone), once per key; the assertion that
+        the combination's own terms pass a row and fail a row of some family gene that the family limits alone pass is made
+        here, on the reference, before any device result is looked at."""
+        from cropsr_amd import select as sel
+        import guide_properties_reference as gpref
+        import repair_reference as rref
+        if (key, name) in self._want:
+            return self._want[(key, name)]
+        case = self.case
+        fam_ref = case.rows(3, "hsu2013", 0)
+        row_of = {s: r for r, s in enumerate(fam_ref["sites"])}
+        limits = (FAMILY_LIMITS["min_members"], FAMILY_LIMITS["max_perfect_outside"], None)
+        if name is None:
+            out = _reference_selection(case, tables, columns, fam_ref, row_of, 5, limits=limits)
+        else:
+            if (key, "truth") not in self._want:
+                self._want[(key, "truth")] = self.truth(tables)
+            truth = self._want[(key, "truth")]
+            params, request = _combinations()[name]
+            strands = ("plus", "minus")
+            terms = []
+            if params.get("require_cds"):
+                terms.append(lambda kc, st, i: truth[kc]["cds_" + strands[st]][i])
+            if "gc_min" in request:
+                lim = tuple(request[k] for k in ("gc_min", "gc_max", "max_run", "max_t_run", "max_stem"))
+                terms.append(lambda kc, st, i: gpref.limits_pass(truth[kc]["props_" + strands[st]][i:i + 1], lim)[0])
+            if "min_mh" in request:
+                lim2 = (request["min_mh"], request["min_oof"])
+                terms.append(lambda kc, st, i: rref.limits_pass(truth[kc]["repair_" + strands[st]][i:i + 1], lim2)[0])
+            out = _reference_selection(case, tables, columns, fam_ref, row_of, 5, params.get("max_perfect"),
+                                       None if params.get("min_specificity") is None else sel.max_hit_sum_for(params["min_specificity"]),
+                                       limits, also=lambda kc, st, i: all(t(kc, st, i) for t in terms), min_score=params.get("min_score", 0.0))
+            alone = self.want(key, tables, columns, None)
+            in_family = [gi for gi in range(len(case.genes)) if case.gene_family[gi] != NONE]
+            assert all(out[gi][1] <= alone[gi][1] and out[gi][0] == alone[gi][0] for gi in range(len(case.genes)))
+            assert any(0 < out[gi][1] < alone[gi][1] for gi in in_family), name
+        self._want[(key, name)] = out
+        return out
+
+
+@pytest.fixture(scope="module")
+def combined(case, tmp_path_factory):
+    c = Combined(case, str(tmp_path_factory.mktemp("families_cds")))
+    yield c
+    c.close()
+
+
+def _oracle_view(case, orc):
+    """The tables of every contig from the CPU oracle and the plain joined columns from the CPU self search, as
+    FamilyOracleBackend.scan has them: what the loop statement needs without a GPU."""
+    import specificity_join_cases as jcases
+    tables = [orc.scan_score(t, 20) for t in case.contigs]
+    sites, _, counts, hs = selfref.search_self(case.contigs, PATTERN, 3, 3, GUIDE_PATTERN, sref.W_HSU)
+    arr = np.empty(len(sites), srch.SELF_SITE_DTYPE)
+    arr["contig"], arr["position"] = [s[0] for s in sites], [s[1] for s in sites]
+    arr["strand"] = [b"+-"[s[2]:s[2] + 1] for s in sites]
+    return tables, jcases.join_fast(tables, arr, counts.astype(np.uint32), np.array(hs, np.uint64), 20)
+
+
+def test_combined_limits_pass_and_fail_rows_on_the_reference(case, combined, oracle):
+    """Every combination of test_gpu_family_limits_combined_with_the_other_limits, on the CPU's tables and columns: its terms
+    take rows of a family gene away that the family limits alone pass, and leave some (Combined.want asserts it)."""
+    tables, columns = _oracle_view(case, oracle)
+    alone = combined.want("cpu", tables, columns, None)
+    gene = {ident: i for i, ident in enumerate(case.idents)}
+    assert all(alone[gene[i]][1] > 50 for i in ("A1", "A2", "A3")) and alone[gene["F1"]][1] == 0
+    for name in COMBINATIONS:
+        want = combined.want("cpu", tables, columns, name)
+        assert sum(w[1] for w in want) > 0
+    everything = combined.want("cpu", tables, columns, "all")
+    for name in COMBINATIONS[:-1]:  # all at once is at most each
+        assert all(a[1] <= w[1] for a, w in zip(everything, combined.want("cpu", tables, columns, name)))
+
+
+@pytest.mark.gpu
+@SLICES
+@pytest.mark.parametrize("name", COMBINATIONS)
+def test_gpu_family_limits_combined_with_the_other_limits(engine, case, combined, name, slice_rows):
+    """min_members = 2 and max_perfect_outside = 0 behind min_score, the specificity thresholds, require_cds, the property
+    limits and the repair limits, one at a time and all at once, at K = 5, with whole genes and with genes cut into slices."""
+    from cropsr_amd import select as sel
+    g = engine.genome(case.contigs, max_words=MAX_WORDS)
+    try:
+        areq = annotate.Request(combined.ann, case.names, 0)
+        plain = g.scan_score(20, specificity={})
+        tables = [plain.contig(k) for k in range(len(case.contigs))]
+        want = combined.want("gpu", tables, plain.columns, name)  # (asserts on the reference that the terms pass and fail rows)
+        params, request = _combinations()[name]
+        req = sel.Request(sel.Params(5, **params), areq, slice_rows, families=combined.table, **dict(FAMILY_LIMITS, **request))
+        got = g.scan_score(20, specificity={}, select=req).selection
+        _assert_selection_equals(case, got, want)
+        _assert_the_case_cuts(case, tables, got.stats, slice_rows)
+        assert got.stats["family_select_ms"] > 0.0
+    finally:
+        g.close()
 
 
 @pytest.mark.gpu
