@@ -1,0 +1,813 @@
+"""Arena positions with bit 30 set: the post-scan kernels behind a filler contig (tests/high_position_cases.py), at two
+placements -- "straddle", where arena position 2^30 falls between the two copies of the tie contig's block, and "top", where the
+arena is as long as the library accepts and every case position lies within 2^20 of 2^31.  Expected values come from the suite's
+references run on the case contigs alone (results are contig-relative); every comparison is exact.  The tests without a GPU
+prove on the references' own rows that the GPU tests are not vacuous: the ties, the keys on both sides of 2^30, the windows
+that reach past the last text word."""
+import numpy as np
+import pytest
+
+import base_edit_reference as eref
+import family_reference as fref
+import guide_properties_reference as gref
+import high_position_cases as hp
+import repair_reference as rref
+import search_bulge_reference as bref
+import search_pair_reference as pref
+import search_reference as ref
+import search_score_reference as sref
+import search_self_reference as selfref
+import select_coding_reference as cref
+import select_pairs_reference as pairs_ref
+import select_reference as selref
+import specificity_join_cases as join_cases
+import splice_edit_reference as spref
+from cropsr_amd import _native as nat
+from cropsr_amd import annotate, baseedit, coding
+from cropsr_amd import families as fam
+from cropsr_amd import search as srch
+from cropsr_amd import select as sel
+
+NONE = 0xFFFFFFFF
+L = 20
+KS = (1, 5, 33, 64)             # 5 and 33 are odd and below the tie gene's 52 pairs: the K-th pick and the first row left out tie
+TIE_KS = (1, 5, 33)
+KP = (1, 5)
+PAIR_WINDOW = (50, 500)
+FLANKS = (30, 32)
+PATTERN, GUIDE_PATTERN, SPCAS9 = "N" * L + "NRG", "N" * L + "NGG", "N" * 21 + "GG"
+WINDOW = (4, 8)
+CODING_LIMITS = (None, (0, 100, 0), (5, 65, 0))
+EDIT_LIMITS = (None, (0, 100, 20))
+SPLICE_LIMITS = (None, (0, 100, 20, "any"))
+FAMILY_LIMITS = dict(min_members=2, max_perfect_outside=0)
+FAMILY_TIE_LIMITS = dict(min_members=1)  # every joined row passes: the tie gene's pairs decide in the family item kernel
+BOUNDS = (0, sel.max_hit_sum_for(0.5))  # max_perfect 0, min_specificity 0.5
+
+
+class Case:
+    """The case contigs, their GFF and what the references say about them: computed once, never changed."""
+
+    def __init__(self, orc, tmp):
+        self.__dict__.update(hp.build(orc))
+        self.orc = orc
+        self.lengths = [len(t) for t in self.contigs]
+        self.gff_path = str(tmp / "cases.gff")
+        with open(self.gff_path, "w") as f:
+            f.write(self.gff)
+        self.annotation = annotate.Annotation(self.gff_path)
+        self.gff_genes = selref.gff_genes(self.gff)
+        self.models = cref.model_numpy(self.gff)
+        self.idents = [g[0] for g in self.genes]
+        self.fam_names, self.gene_family, self.gene_member, self.sizes, _ = fref.table(fref.parse(self.families), self.idents)
+        self.max_words = int(nat.lib().crp_arena_max_words())
+        self.pair = join_cases.pair_table(L)
+        self._cache = {}
+
+    def once(self, key, make):
+        if key not in self._cache:
+            self._cache[key] = make()
+        return self._cache[key]
+
+    # ---- the layout
+    def layout(self, placement):
+        """(filler length, offsets of the case contigs, words of the arena) by the restated rule."""
+        n = hp.filler_length(placement, self.lengths, self.max_words)
+        offsets, words = hp.offsets_of([n] + self.lengths)
+        return n, offsets[1:], words
+
+    def placed(self, placement):
+        return self.once(("placed", placement), lambda: Placed(self, placement))
+
+    # ---- per contig
+    def props(self):
+        return self.once("props", lambda: [(gref.column_numpy(t, h["pos_plus"], False, L), gref.column_numpy(t, h["pos_minus"], True, L))
+                                           for t, h in zip(self.contigs, self.hits)])
+
+    def repair(self, F):
+        return self.once(("repair", F), lambda: [(rref.column_numpy(t, h["pos_plus"], False, F), rref.column_numpy(t, h["pos_minus"], True, F))
+                                                 for t, h in zip(self.contigs, self.hits)])
+
+    def features(self):
+        from oracle import annotate_oracle
+        return self.once("features", lambda: [annotate_oracle.host_join(self.annotation, n, 0, 0, h, L, len(t))
+                                              for n, t, h in zip(self.names, self.contigs, self.hits)])
+
+    def offtarget(self):
+        return self.once("offtarget", lambda: self.orc.offtarget_genome(self.contigs, L))
+
+    # ---- the searches
+    def queries(self):
+        """The three planted guides of the join genome, and the guide of a '+' row in the middle of the tie block."""
+        h = self.hits[hp.TIE]
+        i = int(h["pos_plus"][len(hp.tie_pairs(self.hits, "plus")) // 2])
+        guides = [g.decode() for g in self.guides] + [self.contigs[hp.TIE][i - L:i].decode()]
+        return [srch.check_query(SPCAS9, g, 3) for g in guides]
+
+    def search(self, kind, M):
+        def make():
+            q = self.queries()
+            if kind == "plain":
+                counts, s = ref.search(self.contigs, SPCAS9, q, M)
+                return counts, s, None
+            assert kind == "hsu2013"
+            return sref.search(self.contigs, SPCAS9, q, M, 3, *sref.tables(sref.W_HSU))
+        return self.once(("search", kind, M), make)
+
+    def search_pair(self, M):
+        def make():
+            pair, pam = pref.random_table(np.random.default_rng(77), SPCAS9, 3, (1, 2))
+            return (pair, pam), pref.search(self.contigs, SPCAS9, self.queries(), M, 3, pair, (1, 2), pam)
+        return self.once(("search_pair", M), make)
+
+    def bulges(self, M):
+        return self.once(("bulges", M), lambda: bref.search(self.contigs, SPCAS9, self.queries(), M, 3, 1, 1))
+
+    def self_search(self, M, scored):
+        return self.once(("self", M, scored), lambda: selfref.search_self(self.contigs, PATTERN, M, 3, GUIDE_PATTERN, sref.W_HSU if scored else None))
+
+    def join(self, M, kind):
+        score = {"none": None, "hsu2013": "hsu2013", "pair": self.pair}[kind]
+        return self.once(("join", M, kind), lambda: join_cases.join(self.hits, join_cases.rows(self.contigs, L, M, "NRG", score), L, M))
+
+    def family_rows(self, M, C=0):
+        return self.once(("family", M, C), lambda: fref.family_rows(self.contigs, PATTERN, M, GUIDE_PATTERN, self.genes, self.gene_family,
+                                                                     self.gene_member, C, ("weights", sref.W_HSU)))
+
+
+class Placed:
+    """One placement as the references see it: the case contigs' tables at their arena positions, the genes' ranges and
+    coding rows there, and for the string references of the edits the same letters moved down by `base` (a multiple of 64:
+    their outcomes do not depend on where the arena begins)."""
+
+    def __init__(self, case, placement):
+        self.case, self.placement = case, placement
+        self.filler, self.offsets, self.words = case.layout(placement)
+        self.tables = hp.arena_tables(case.hits, self.offsets)
+        self.entries = [(n, 0, ln, o) for n, ln, o in zip(case.names, case.lengths, self.offsets)]
+        self.lo, self.hi, self.gene = selref.layout(case.gff_genes, self.entries, 0)
+        self.ids = [case.idents[int(g)] for g in self.gene]
+        self.rows = cref.layout_rows(case.gff, self.entries, 0)
+        self.member = cref.membership(self.tables, self.lo, self.hi)
+        self.n_plus = len(self.tables["pos_plus"])
+        self.rows_before = dict(plus=np.cumsum([0] + [len(h["pos_plus"]) for h in case.hits]),
+                                minus=np.cumsum([0] + [len(h["pos_minus"]) for h in case.hits]))
+        self.base = self.offsets[0] - 64
+        self.local_tables = dict(self.tables, pos_plus=self.tables["pos_plus"] - np.uint32(self.base),
+                                 pos_minus=self.tables["pos_minus"] - np.uint32(self.base))
+        self.local_rows = [(g, shift - self.base, a - self.base, b - self.base) for g, shift, a, b in self.rows]
+        self.local_arena = eref.make_arena(case.contigs, [o - self.base for o in self.offsets])
+        self._cache = {}
+
+    def once(self, key, make):
+        if key not in self._cache:
+            self._cache[key] = make()
+        return self._cache[key]
+
+    def cat(self, per_contig, strand):
+        """A column of the arena's table of one strand from per-contig (plus, minus) pairs."""
+        return np.concatenate([c[strand] for c in per_contig])
+
+    def spec(self, M=3, kind="hsu2013"):
+        cols = self.case.join(M, kind)
+        cat = lambda key: np.concatenate([c[key] for c in cols])
+        return dict(counts_plus=cat("self_counts_plus"), sum_plus=cat("self_sum_plus"), counts_minus=cat("self_counts_minus"),
+                    sum_minus=cat("self_sum_minus"))
+
+    def packed_members(self):
+        """(layout row, table row as sel packs it, index into the concatenated tables) of every (gene, row in the gene)."""
+        g, t = np.nonzero(self.member)
+        return g.astype(np.uint32), np.where(t < self.n_plus, t, (t - self.n_plus) | (1 << 31)).astype(np.uint32), t
+
+    def select(self, K, min_score=0.0, bounds=None):
+        """select_numpy; bounds: None, or (max_mm0, max_hit_sum) over the references' joined columns (M = 3, hsu2013)."""
+        spec = None if bounds is None else dict(self.spec(), max_mm0=bounds[0], max_hit_sum=bounds[1])
+        return self.once(("select", K, min_score, bounds), lambda: selref.select_numpy(self.tables, self.lo, self.hi, K, min_score, spec))
+
+    def pairs(self, K):
+        return self.once(("pairs", K), lambda: pairs_ref.pairs_numpy(self.tables, self.lo, self.hi, K, *PAIR_WINDOW))
+
+    def positions(self):
+        return self.once("positions", lambda: cref.positions_numpy(self.tables, self.case.models, self.rows))
+
+    def select_coding(self, K, limits):
+        return self.once(("coding", K, limits), lambda: cref.select_numpy(self.tables, self.lo, self.hi, self.case.models, self.rows, K, limits,
+                                                                           positions=self.positions()))
+
+    def edits(self):
+        return self.once("edits", lambda: eref.outcomes(self.local_tables, self.member, self.case.models, self.local_rows, self.local_arena, WINDOW))
+
+    def select_edit(self, K, limits):
+        return self.once(("edit", K, limits), lambda: eref.select_numpy(self.local_tables, self.member, self.case.models, self.local_rows, K,
+                                                                         self.edits(), limits))
+
+    def splices(self):
+        return self.once("splices", lambda: spref.outcomes(self.local_tables, self.member, self.case.models, self.local_rows, self.local_arena,
+                                                           WINDOW, "cbe"))
+
+    def select_splice(self, K, limits):
+        return self.once(("splice", K, limits), lambda: spref.select_numpy(self.local_tables, self.member, self.case.models, self.local_rows, K,
+                                                                            self.splices(), limits))
+
+    def select_family(self, K, limits):
+        """Per layout row (n_in, n_pass, sel as the device packs it, the reference's values of the selected rows), from the
+        family tests' plain loop over genes and rows; the joined columns are the references', not a device's."""
+        import test_families as tf
+
+        def make():
+            c = self.case
+            fam_ref = c.family_rows(3)
+            row_of = {s: r for r, s in enumerate(fam_ref["sites"])}
+            bound = None if limits.get("min_specificity_outside") is None else sel.max_hit_sum_for(limits["min_specificity_outside"])
+            want = tf._reference_selection(c, c.hits, c.join(3, "hsu2013"), fam_ref, row_of, K, None, None,
+                                           (limits.get("min_members"), limits.get("max_perfect_outside"), bound))
+            n_in, n_pass, picked, values = [], [], np.full((len(self.gene), K), NONE, np.uint32), []
+            for r, g in enumerate(self.gene):
+                w = want[int(g)]
+                n_in.append(w[0])
+                n_pass.append(w[1])
+                vals = []
+                for j, ((kc, _, strand, v, site), i) in enumerate(zip(w[2], w[3])):
+                    picked[r, j] = (int(self.rows_before["minus" if strand else "plus"][kc]) + i) | (strand << 31)
+                    vals.append(v + (fam_ref["fam_cover"][site] if c.gene_family[int(g)] != fref.NONE and
+                                     int(fam_ref["site_family"][site]) == c.gene_family[int(g)] else 0,))
+                values.append(vals)
+            return np.array(n_in, np.uint32), np.array(n_pass, np.uint32), picked, values
+        return self.once(("family", K, tuple(sorted(limits.items()))), make)
+
+
+@pytest.fixture(scope="module")
+def case(oracle, tmp_path_factory):
+    return Case(oracle, tmp_path_factory.mktemp("high_positions"))
+
+
+def _same(got, want, what=""):
+    for g, w, name in zip(got, want, ("n_in", "n_pass", "sel")):
+        assert np.array_equal(np.asarray(g, np.uint32), np.asarray(w, np.uint32)), (what, name)
+
+
+def _bits(a):
+    return np.asarray(a, np.float64).view(np.uint64)
+
+
+def _cut(tables, packed):
+    """Arena cut site of a row as sel packs it."""
+    minus, r = int(packed) >> 31, int(packed) & 0x7FFFFFFF
+    return int(tables["pos_minus"][r]) if minus else int(tables["pos_plus"][r]) - 3
+
+
+def _score_bits(tables, packed):
+    minus, r = int(packed) >> 31, int(packed) & 0x7FFFFFFF
+    return int(_bits(tables["score_minus" if minus else "score_plus"])[r])
+
+
+# ---------------------------------------------------------------------------------------------- without a GPU
+def test_the_filler_yields_nothing(oracle):
+    """A contig of A: no row, no candidate of any pattern used here on either strand, no guide site."""
+    stretch = bytes(hp.filler(5000))
+    h = oracle.scan_score(stretch, L)
+    assert h["pos_plus"].size == 0 and h["pos_minus"].size == 0
+    patterns = [PATTERN, GUIDE_PATTERN, SPCAS9] + [bref.kind_pattern(SPCAS9, 3, b, 1) for b in ("DNA", "RNA")]
+    for p in patterns:
+        assert "G" in p.rstrip("N")[-3:]  # every pattern's PAM holds a G: an all-N pattern would make every filler position a candidate
+        assert ref.candidates([stretch], p)[0].size == 0, p
+    (k, _, _, _), g = selfref.guide_sites([stretch], PATTERN, 3, GUIDE_PATTERN)
+    assert k.size == 0 and g.size == 0
+    assert all(o["seed_plus"].size == 0 and o["seed_minus"].size == 0 for o in oracle.offtarget_genome([stretch], L))
+
+
+def test_layout_of_both_placements(case):
+    s, t = case.placed("straddle"), case.placed("top")
+    for p in (s, t):
+        assert p.filler % 64 == 0 and p.filler > 2**30 - 2**20 and all(o % 64 == 0 for o in p.offsets)
+        assert p.offsets[-1] + case.lengths[-1] <= hp.TWO31 - 1
+    # straddle: 2^30 between the copies of the tie block; the join genome's first contig below it, everything else above
+    tie = s.offsets[hp.TIE]
+    assert tie + hp.TIE_AT == hp.TWO30 and tie + hp.COPY[0] + hp.BLOCK < hp.TWO30 <= tie + hp.COPY[1]
+    assert s.offsets[0] + case.lengths[0] < hp.TWO30 and all(o >= hp.TWO30 for o in s.offsets[hp.TIE + 1:])
+    k = s.ids.index("tie")
+    assert int(s.lo[k]) < hp.TWO30 <= int(s.hi[k]) and s.ids.index("tie_introns") == k + 1 and int(s.lo[k + 1]) < hp.TWO30 <= int(s.hi[k + 1])
+    # top: the arena has the most words the library takes, the last text word is the tail's last, all within 2^20 of 2^31
+    assert t.words == case.max_words
+    assert (t.offsets[-1] + hp.TAIL_LEN) // 64 == t.words - 1 and hp.TAIL_LEN % 64 == 0
+    for key in ("pos_plus", "pos_minus"):
+        assert (hp.TWO31 - t.tables[key].astype(np.int64) < 2**20).all() and (t.tables[key] >> 30 == 1).all()
+    assert hp.TWO31 - int(t.lo.min()) < 2**20
+    # ... and some row's farthest reach (a flank-32 repair window behind a '-' cut boundary) lies past the last text word
+    text_end = 64 * (t.words - 1)
+    reach = max(int(t.tables["pos_plus"].max()) - 3 + 32, int(t.tables["pos_minus"].max()) + 3 + L + 32)
+    assert reach >= text_end and int(t.tables["pos_plus"].max()) + 3 == text_end  # the tail's last '+' row: its PAM ends the text
+
+
+def test_straddle_ties_decide_the_selection(case):
+    """Every scored row of copy 1 has a bit-equal partner in copy 2 on the other side of 2^30; at K = 1 and the odd Ks the
+    reference's K-th pick and the first row it leaves out are such a pair -- a signed compare of cut << 1 | strand swaps them."""
+    s = case.placed("straddle")
+    k = s.ids.index("tie")
+    h = case.hits[hp.TIE]
+    n_pairs = 0
+    for strand in ("plus", "minus"):
+        pairs = hp.tie_pairs(case.hits, strand)
+        pos, score = h["pos_" + strand].astype(np.int64) + s.offsets[hp.TIE], h["score_" + strand]
+        assert 2 * len(pairs) == pos.size  # every row of the contig is in a pair: the filler letters around the copies hold none
+        for a, b in pairs:
+            assert _bits(score)[a] == _bits(score)[b] and score[a] != -1.0
+            assert pos[a] + 32 < hp.TWO30 <= pos[b] - 32
+        n_pairs += len(pairs)
+    assert n_pairs > max(TIE_KS) and s.member[k].sum() == 2 * n_pairs > 64  # (more than 64 rows: cut and merged at slices of 64)
+    for name, select in (("plain", lambda K: s.select(K)), ("coding", lambda K: s.select_coding(K, (0, 100, 0))),
+                         ("edit", lambda K: s.select_edit(K, (0, 100, 20))), ("family", lambda K: s.select_family(K, FAMILY_TIE_LIMITS)[:3])):
+        ks = [K for K in TIE_KS if select(K)[1][k] > K]  # (few rows write a stop codon: K = 1 at the least)
+        assert ks and (name == "edit" or ks == list(TIE_KS))
+        for K in ks:
+            n_in, n_pass, picked = select(K)
+            kth, left_out = picked[k][K - 1], select(K + 1)[2][k][K]
+            assert _score_bits(s.tables, kth) == _score_bits(s.tables, left_out), (name, K)
+            assert _cut(s.tables, kth) < hp.TWO30 <= _cut(s.tables, left_out), (name, K)
+    # the gene with an intron in either copy: a splice site that an edit destroys, in both copies
+    k = s.ids.index("tie_introns")
+    n_in, n_pass, picked = s.select_splice(1, (0, 100, 20, "any"))
+    assert n_pass[k] >= 2 and n_pass[k] % 2 == 0
+    kth, left_out = picked[k][0], s.select_splice(2, (0, 100, 20, "any"))[2][k][1]
+    assert _score_bits(s.tables, kth) == _score_bits(s.tables, left_out) and _cut(s.tables, kth) < hp.TWO30 <= _cut(s.tables, left_out)
+    # the pair selection: equal keys, one pair on either side; at odd KP the last pick and the first pair left out
+    k = s.ids.index("tie")
+    for K in KP:
+        n_pass, n_pairs, pairs = s.pairs(K)
+        assert n_pairs[k] > K
+        (a1, b1), (a2, b2) = pairs[k][K - 1], s.pairs(K + 1)[2][k][K]
+        assert sorted((_score_bits(s.tables, a1), _score_bits(s.tables, b1))) == sorted((_score_bits(s.tables, a2), _score_bits(s.tables, b2)))
+        assert _cut(s.tables, b1) < hp.TWO30 <= _cut(s.tables, a2)
+
+
+def test_straddle_keys_on_both_sides(case):
+    """The rows the specificity join and the family join must match, and the candidates their binary searches run over,
+    lie on both sides of the position where join_key and family_key gain bit 31."""
+    s = case.placed("straddle")
+    fam_ref = case.family_rows(3)
+    for M in (0, 3):
+        below = above = 0
+        for k, cols in enumerate(case.join(M, "hsu2013")):
+            for strand in ("plus", "minus"):
+                joined = cols["self_counts_" + strand][:, 0] != join_cases.NO_COUNT
+                pos = case.hits[k]["pos_" + strand].astype(np.int64)[joined] + s.offsets[k]
+                below, above = below + int((pos < hp.TWO30).sum()), above + int((pos >= hp.TWO30).sum())
+        assert below >= 64 and above >= 64, M
+    k, pos, strand = fam_ref["cand"]
+    arena_pos = pos + np.array(s.offsets)[k]
+    assert (arena_pos < hp.TWO30).sum() >= 64 and (arena_pos >= hp.TWO30).sum() >= 64
+    in_family = fam_ref["site_family"] != NONE
+    site_pos = np.array([p + s.offsets[kc] for kc, p, _ in fam_ref["sites"]])
+    assert (in_family & (site_pos < hp.TWO30)).sum() >= 64 and (in_family & (site_pos >= hp.TWO30)).sum() >= 64
+
+
+def test_expected_arrays_are_not_trivial(case):
+    """Every step's expectation holds something a wrong kernel would miss."""
+    for F in FLANKS:
+        assert all(np.unique(np.concatenate(r)).size > 5 for r in case.repair(F)[:4])
+    assert all(np.unique(np.concatenate(p)).size > 5 for p in case.props())
+    feats = case.features()
+    ids = np.concatenate([np.concatenate(f) for f in feats])
+    assert np.unique(ids).size >= 8 and (ids == NONE).any()
+    ot = case.offtarget()
+    assert sum(int((o["ot_plus"][:, 0] != NONE).sum()) for o in ot) > 300 and any((o["ot_plus"][:, 0] > 0).any() for o in ot)
+    for M in (0, 3):
+        counts, sites, _ = case.search("plain", M)
+        assert (counts.sum(axis=1) >= 1).all() and counts[-1].sum() >= 2  # (the tie block's guide: a site on either side of 2^30)
+        assert set(sites["contig"].tolist()) >= {0, 1, 2, 3} and set(sites["strand"].tolist()) == {0, 1}
+        _, (pc, _, hit_sum) = case.search_pair(M)
+        assert (pc == counts).all() and (M == 0 or sum(hit_sum) > 0)
+        bc, bs = case.bulges(M)
+        assert bc[:, 0].sum() == counts.sum() and (M == 0 or (bc[:, 1:].sum() > 0 and set(bs["kind"].tolist()) == {0, 1, 2}))
+        sites, _, counts, hit_sum = case.self_search(M, True)
+        assert len(sites) > 800 and counts[:, 0].sum() >= 100 and (M == 0 or (counts[:, 1:].sum() > 10 and sum(hit_sum) > 0))
+    f = case.family_rows(3)
+    assert f["fam_counts"][:, 0].sum() >= 100 and set(f["fam_cover"]) >= {0, 1, 7} and sum(f["fam_sum"]) > 0
+    for name in hp.PLACEMENTS:
+        p = case.placed(name)
+        off, cover = p.positions()
+        assert (off[p.member] != cref.NOT_INSIDE).sum() > 200 and (off[p.member] == cref.NOT_INSIDE).sum() > 20
+        assert sum(int((o[3] != eref.NO_STOP).sum()) for o in p.edits()) >= 4
+        assert sum(int((o[4] != spref.NO_SITE).sum() + (o[5] != spref.NO_SITE).sum()) for o in p.splices()) >= 4
+        for K in KS:
+            n_in, n_pass, picked = p.select(K)
+            assert (n_pass > 64).sum() >= 3 and (picked[:, 0] != NONE).all() and np.unique(picked[:, 0] >> 31).size == 2
+            assert (p.select(K, 0.0, BOUNDS)[1] < n_pass).any()
+        n_in, n_pass, picked, values = p.select_family(5, FAMILY_LIMITS)
+        assert 0 < n_pass.sum() < p.select(5)[1].sum() and any(v[2] >= 2 for vals in values for v in vals)
+        assert (p.pairs(5)[1] > 5).sum() >= 3
+
+
+# ---------------------------------------------------------------------------------------------- on the GPU
+@pytest.fixture(scope="module")
+def engine():
+    from cropsr_amd import Engine
+    eng = Engine(0)
+    yield eng
+    eng.close()
+
+
+class Device:
+    def __init__(self, engine, case, placement):
+        import time
+        self.case, self.ref = case, case.placed(placement)
+        t0 = time.perf_counter()
+        text = hp.filler(self.ref.filler)
+        self.genome = engine.genome([text] + case.contigs)
+        del text  # (a gigabyte or two of host memory: gone before the references need theirs)
+        self.upload_s = time.perf_counter() - t0
+        assert len(self.genome.arenas) == 1
+        self.arena = self.genome.arenas[0]
+        self.request = annotate.Request(case.annotation, [hp.FILLER_NAME] + case.names, 0)
+        self.scan()
+        print("high positions, %s: upload %.2f s, first scan %.2f s" % (placement, self.upload_s, time.perf_counter() - t0 - self.upload_s))
+
+    def scan(self):
+        self.hits = self.genome.scan_score(L)
+        self.counts = [(h.n_plus, h.n_minus) for h in self.hits.per_arena]
+        return self.hits
+
+    def select(self):
+        return sel.ArenaSelect(self.arena, self.ref.lo, self.ref.hi)
+
+    def model(self):
+        return self.request.coding_layout(sel.arena_layout(self.genome, 0))
+
+
+@pytest.fixture(scope="module", params=hp.PLACEMENTS)
+def dev(request, engine, case):
+    d = Device(engine, case, request.param)
+    yield d
+    d.genome.close()
+
+
+@pytest.mark.gpu
+def test_gpu_ground(dev, case):
+    """The layout is the restated one, the filler holds no row, the case contigs' rows are the oracle's, and the positions
+    are as high as claimed."""
+    p = dev.ref
+    assert [int(o) for o in dev.arena.offsets] == [64] + p.offsets and dev.arena.stats()["n_words"] == p.words
+    assert dev.arena.stats()["n_chars"] == p.filler + sum(case.lengths)
+    if p.placement == "top":
+        assert p.words == int(nat.lib().crp_arena_max_words())
+    filler = dev.hits.contig(0)
+    assert all(filler[key].size == 0 for key in ("pos_plus", "score_plus", "pos_minus", "score_minus"))
+    for k, want in enumerate(case.hits):
+        got = dev.hits.contig(k + 1)
+        for key in ("pos_plus", "pos_minus"):
+            assert np.array_equal(got[key], want[key]), (k, key)
+        for key in ("score_plus", "score_minus"):
+            assert np.array_equal(_bits(got[key]), _bits(want[key])), (k, key)
+    h = dev.hits.per_arena[0]
+    for key in ("pos_plus", "pos_minus"):
+        assert np.array_equal(getattr(h, key), p.tables[key]) and int(getattr(h, key).max()) <= hp.TWO31 - 1
+        high = getattr(h, key) >> 30 == 1
+        assert high.all() if p.placement == "top" else (high.sum() >= 64 and (~high).sum() >= 64)
+    lo, hi, gene = dev.request.gene_layout(sel.arena_layout(dev.genome, 0))
+    assert np.array_equal(lo, p.lo) and np.array_equal(hi, p.hi) and np.array_equal(gene, p.gene)
+
+
+@pytest.mark.gpu
+def test_gpu_properties_and_repair(dev, case):
+    p = dev.ref
+    (pp, pm), = dev.genome.guide_properties(dev.counts)
+    assert np.array_equal(pp, p.cat(case.props(), 0)) and np.array_equal(pm, p.cat(case.props(), 1))
+    for F in FLANKS:
+        (rp, rm), = dev.genome.repair_scores(dev.counts, F)
+        assert np.array_equal(rp, p.cat(case.repair(F), 0)) and np.array_equal(rm, p.cat(case.repair(F), 1)), F
+
+
+@pytest.mark.gpu
+def test_gpu_annotation_lookup(dev, case):
+    """Label-set ids per row: the numpy statement over the product's interval table, and every id's string against the
+    brute-force statement (all features of the GFF that contain the cut site, in file order)."""
+    from oracle import annotate_oracle
+    p = dev.ref
+    (fp, fm), = dev.genome.annotate(dev.request, dev.counts)
+    want = case.features()
+    assert np.array_equal(fp, p.cat(want, 0)) and np.array_equal(fm, p.cat(want, 1))
+    feats = list(annotate_oracle.gff_rows(case.gff_path))
+    strings = case.annotation.strings
+    n_labelled = 0
+    for got, key, before in ((fp, "plus", p.rows_before["plus"]), (fm, "minus", p.rows_before["minus"])):
+        for k, (name, h) in enumerate(zip(case.names, case.hits)):
+            pos = h["pos_" + key].astype(np.int64)
+            cut = pos - 3 if key == "plus" else pos
+            for r in np.flatnonzero(h["score_" + key] != -1.0):
+                labels = []
+                for seqid, ftype, start, end, attrs in feats:
+                    lab = annotate_oracle.label(ftype, attrs)
+                    if seqid == name and start <= cut[r] + 1 <= end and lab not in labels:
+                        labels.append(lab)
+                i = int(got[before[k] + r])
+                assert ("" if i == NONE else strings[i]) == ";".join(labels), (key, k, r)
+                n_labelled += bool(labels)
+    assert n_labelled > 500
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("seeds_from_scan", [True, False], ids=["seeds-from-scan", "seeds-from-planes"])
+def test_gpu_offtarget_seeds_and_counts(dev, case, seeds_from_scan):
+    want = case.offtarget()
+    try:
+        hits = dev.genome.scan_score(L, offtarget=True, seeds_from_scan=seeds_from_scan)
+        sp, sm = dev.arena.offtarget_seeds(hits.n_plus, hits.n_minus)
+        assert np.array_equal(sp, np.concatenate([w["seed_plus"] for w in want])) and np.array_equal(sm, np.concatenate([w["seed_minus"] for w in want]))
+        for k, w in enumerate(want):
+            got = hits.contig(k + 1)
+            assert np.array_equal(got["ot_plus"], w["ot_plus"]) and np.array_equal(got["ot_minus"], w["ot_minus"]), k
+    finally:
+        dev.scan()
+
+
+def _site_tuples(sites, fields):
+    cols = [(sites[f] == b"-").astype(int).tolist() if f == "strand" else sites[f].tolist() for f in fields]
+    return list(zip(*cols))
+
+
+def _want_tuples(s, fields):
+    """The reference's sites with the case contigs renumbered as the device's genome has them (the filler is contig 0)."""
+    cols = [(s[f] + 1).tolist() if f == "contig" else s[f].tolist() for f in fields]
+    return sorted(zip(*cols))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M", [0, 3])
+def test_gpu_given_guide_search(dev, case, M):
+    """Counts, hit sums and every site -- decoded on the host from start | strand << 31 -- of the plain, the hsu2013-scored
+    and the pair-table search, and of the search with one DNA and one RNA bulge."""
+    q = case.queries()
+    counts, s, _ = case.search("plain", M)
+    res = dev.genome.search(SPCAS9, q, M)
+    assert np.array_equal(res.counts, counts) and _site_tuples(res.sites, ref.SITE_FIELDS) == _want_tuples(s, ref.SITE_FIELDS)
+    assert res.sites.size == counts.sum() and sum(res.candidates) == ref.candidates(case.contigs, SPCAS9)[0].size
+    counts, s, hit_sum = case.search("hsu2013", M)
+    res = dev.genome.search(SPCAS9, q, M, pam_len=3, score="hsu2013")
+    assert np.array_equal(res.counts, counts) and [int(x) for x in res.hit_sum] == hit_sum
+    assert _site_tuples(res.sites, ref.SITE_FIELDS) == _want_tuples(s, ref.SITE_FIELDS)
+    (pair, pam), (counts, s, hit_sum) = case.search_pair(M)
+    res = dev.genome.search(SPCAS9, q, M, pam_len=3, score=srch.PairTable(pair, (1, 2), pam))
+    assert np.array_equal(res.counts, counts) and [int(x) for x in res.hit_sum] == hit_sum
+    assert _site_tuples(res.sites, ref.SITE_FIELDS) == _want_tuples(s, ref.SITE_FIELDS)
+    counts, s = case.bulges(M)
+    res = dev.genome.search_bulges(SPCAS9, q, M, 3, 1, 1)
+    assert np.array_equal(res.counts, counts) and _site_tuples(res.sites, bref.FIELDS) == _want_tuples(s, bref.FIELDS)
+    assert np.array_equal(res.sites["bulge_size"], np.array([size for _, size in res.kinds], np.uint8)[res.sites["kind"]])
+
+
+def _assert_joined(case, p, got, M, kind):
+    """The joined columns of the case contigs (got: per contig of the device's genome, the filler first)."""
+    want = case.join(M, kind)
+    assert all(v.shape[0] == 0 for v in got[0].values())
+    unjoined = 0
+    for k, w in enumerate(want):
+        for key in ("self_counts_plus", "self_counts_minus", "self_sum_plus", "self_sum_minus"):
+            g = got[k + 1][key]
+            assert g.dtype == w[key].dtype and g.shape == w[key].shape, (k, key)
+            if key.startswith("self_counts"):  # the failure of a misordered key search: a joined row with the sentinel
+                unjoined += int(((g[:, 0] == join_cases.NO_COUNT) & (w[key][:, 0] != join_cases.NO_COUNT)).sum())
+    assert unjoined == 0, "%d rows the join should have matched carry the unjoined sentinel" % unjoined
+    for k, w in enumerate(want):
+        for key in ("self_counts_plus", "self_counts_minus", "self_sum_plus", "self_sum_minus"):
+            assert np.array_equal(got[k + 1][key], w[key]), (k, key)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M", [0, 3])
+def test_gpu_self_search_and_specificity_join(dev, case, M):
+    sites, guides, counts, hit_sum = case.self_search(M, True)
+    res = dev.genome.search_self(PATTERN, M, 3, guide_pattern=GUIDE_PATTERN, score="hsu2013")
+    got = list(zip((res.sites["contig"].astype(np.int64) - 1).tolist(), res.sites["position"].tolist(), (res.sites["strand"] == b"-").astype(int).tolist()))
+    assert got == sites
+    assert [g.decode() for g in res.guides] == guides and np.array_equal(res.counts.astype(np.int64), counts)
+    assert [int(x) for x in res.hit_sum] == hit_sum
+    plain = dev.genome.search_self(PATTERN, M, 3, guide_pattern=GUIDE_PATTERN)
+    assert np.array_equal(plain.counts.astype(np.int64), case.self_search(M, False)[2]) and plain.hit_sum is None
+    for kind in ("hsu2013", "none", "pair"):
+        score = {"none": None, "hsu2013": "hsu2013", "pair": srch.PairTable(case.pair[0], case.pair[1], case.pair[2])}[kind]
+        _assert_joined(case, dev.ref, dev.genome.specificity_columns(L, max_mm=M, score=score), M, kind)
+
+
+def _family_table(case):
+    return fam.FamilyTable(fam.parse_families(case.families), case.annotation.genes()[0])
+
+
+@pytest.mark.gpu
+def test_gpu_families(dev, case):
+    """The family rows of the self search, the joined family columns, and the family selection through
+    scan_score(select=...) at K = 1 and 5."""
+    p = dev.ref
+    table = _family_table(case)
+    assert table.gene_family.tolist() == case.gene_family and table.size.tolist() == case.sizes
+    rows = fam.genome_rows(table, dev.genome, dev.request)
+    want = case.family_rows(3)
+    res = dev.genome.search_self(PATTERN, 3, 3, guide_pattern=GUIDE_PATTERN, score="hsu2013", families=rows)
+    got = list(zip((res.sites["contig"].astype(np.int64) - 1).tolist(), res.sites["position"].tolist(), (res.sites["strand"] == b"-").astype(int).tolist()))
+    assert got == want["sites"]
+    assert np.array_equal(res.site_family, want["site_family"]) and np.array_equal(res.site_gene, want["site_gene"])
+    assert np.array_equal(res.fam_counts.astype(np.int64), want["fam_counts"])
+    assert [int(x) for x in res.fam_sum] == want["fam_sum"] and [int(x) for x in res.fam_cover] == want["fam_cover"]
+    # the joined family columns, per row of the case contigs' tables
+    row_of = {s: r for r, s in enumerate(want["sites"])}
+    cols = dev.genome.specificity_columns(L, families=rows)
+    _assert_joined(case, p, cols, 3, "hsu2013")
+    missing = 0
+    for k, h in enumerate(case.hits):
+        for strand, name in ((0, "plus"), (1, "minus")):
+            pos = h["pos_" + name].astype(np.int64)
+            r = np.array([row_of.get((k, int(x), strand), -1) for x in (pos - L if strand == 0 else pos).tolist()], dtype=np.int64)
+            c = cols[k + 1]
+            joined = r >= 0
+            missing += int((c["fam_counts_" + name][joined][:, 0] == nat.SELF_UNJOINED_COUNT).sum())
+            assert np.array_equal(c["fam_counts_" + name][joined].astype(np.int64), want["fam_counts"][r[joined]]), (k, name)
+            assert [int(x) for x in c["fam_sum_" + name][joined]] == [want["fam_sum"][i] for i in r[joined].tolist()]
+            assert [int(x) for x in c["fam_cover_" + name][joined]] == [want["fam_cover"][i] for i in r[joined].tolist()]
+            assert np.array_equal(c["site_family_" + name][joined], want["site_family"][r[joined]])
+            assert (c["fam_counts_" + name][~joined] == nat.SELF_UNJOINED_COUNT).all() and (c["site_family_" + name][~joined] == NONE).all()
+    assert missing == 0
+    # the selection with family limits, through the genome-level call
+    try:
+        for K in (1, 5):
+            n_in, n_pass, picked, values = p.select_family(K, FAMILY_LIMITS)
+            req = sel.Request(sel.Params(K), dev.request, families=table, **FAMILY_LIMITS)
+            S = dev.genome.scan_score(L, specificity={}, select=req).selection
+            order = np.argsort(p.gene, kind="stable")  # the Selection lists genes in GFF order
+            assert np.array_equal(S.n_in, n_in[order]) and np.array_equal(S.n_pass, n_pass[order])
+            at = 0
+            for r in order:
+                for j, v in enumerate(values[r]):
+                    row = S.rows[at]
+                    packed = int(picked[r, j])
+                    minus, t = packed >> 31, packed & 0x7FFFFFFF
+                    kc = int(np.searchsorted(p.rows_before["minus" if minus else "plus"], t, "right")) - 1
+                    pos = int(p.tables["pos_minus" if minus else "pos_plus"][t]) - p.offsets[kc]
+                    assert (int(row["gene"]), int(row["rank"]), int(row["contig"]), int(row["position"]), row["strand"]) == \
+                        (int(p.gene[r]), j + 1, kc + 1, pos, b"-" if minus else b"+")
+                    assert (int(S.outside_mm0[at]), int(S.outside_hit_sum[at]), int(S.members_hit[at]), int(S.family_size[at]),
+                            int(S.fam_cover[at])) == v
+                    at += 1
+            assert at == len(S.rows) > 0
+    finally:
+        dev.scan()
+
+
+def _merged_genes(p, slice_rows):
+    t = p.tables
+    cp, cm = t["pos_plus"].astype(np.int64) - 3, t["pos_minus"].astype(np.int64)
+    n = sum(np.searchsorted(c, p.hi.astype(np.int64), "right") - np.searchsorted(c, p.lo.astype(np.int64), "left") for c in (cp, cm))
+    return int((n > (slice_rows or 65536)).sum())
+
+
+SLICES = pytest.mark.parametrize("slice_rows", [None, 64], ids=["default-slices", "slices-of-64"])
+
+
+KERNELS = ("plain", "pairs", "coding", "edit", "splice")
+
+
+@pytest.mark.gpu
+@SLICES
+@pytest.mark.parametrize("kernel", KERNELS)
+def test_gpu_selection(dev, case, kernel, slice_rows):
+    """n_in, n_pass and sel of every gene from the plain, the coding, the edit and the splice item kernels and the pair
+    selection, at the default slices and with the genes cut into slices of 64 rows and merged."""
+    p = dev.ref
+    h = dev.select()
+    try:
+        if slice_rows:
+            h.set_limits(slice_rows)
+            h.set_pair_limits(slice_rows)
+        if kernel == "plain":
+            for K in KS:
+                h.run(sel.Params(K))
+                _same(h.fetch(), p.select(K), "plain K=%d" % K)
+                assert h.stats()["merged_genes"] == _merged_genes(p, slice_rows) and (not slice_rows or _merged_genes(p, slice_rows) >= 4)
+            return
+        if kernel == "pairs":
+            for K in KP:
+                h.run_pairs(sel.Params(1), sel.PairParams(K, *PAIR_WINDOW))
+                n_pass, n_pairs, pairs = h.fetch_pairs()
+                want = p.pairs(K)
+                assert np.array_equal(n_pass, want[0]) and np.array_equal(n_pairs, want[1]) and np.array_equal(pairs, want[2]), K
+            return
+        h.set_coding(dev.model())
+        for K in KS:
+            if kernel == "coding":
+                for limits in CODING_LIMITS:
+                    h.set_coding_limits(None if limits is None else coding.Limits(*limits))
+                    h.run(sel.Params(K))
+                    _same(h.fetch(), p.select_coding(K, limits), "coding K=%d %s" % (K, limits))
+            elif kernel == "edit":
+                for limits in EDIT_LIMITS:
+                    h.set_edit_limits(baseedit.Window(*WINDOW), None if limits is None else baseedit.Limits(*limits))
+                    h.run(sel.Params(K))
+                    _same(h.fetch(), p.select_edit(K, limits), "edit K=%d %s" % (K, limits))
+            else:
+                for limits in SPLICE_LIMITS:
+                    h.set_splice_limits(baseedit.Window(*WINDOW), "cbe", None if limits is None else baseedit.SpliceLimits(*limits))
+                    h.run(sel.Params(K))
+                    _same(h.fetch(), p.select_splice(K, limits), "splice K=%d %s" % (K, limits))
+    finally:
+        h.close()
+
+
+@pytest.mark.gpu
+def test_gpu_eval_kernels(dev, case):
+    """coding_eval, edit_eval and splice_eval for every (gene, row in the gene): they read pos_minus[row] + 6 and
+    pos_plus[row] - 3 and the step tables at these positions."""
+    p = dev.ref
+    g, packed, t = p.packed_members()
+    h = dev.select()
+    try:
+        model = dev.model()
+        assert int(model["at"].max()) >> 30 == 1
+        h.set_coding(model)
+        off, cover = h.coding_eval(g, packed)
+        want = p.positions()
+        assert np.array_equal(off, want[0][g, t]) and np.array_equal(cover, want[1][g, t]) and g.size == int(p.member.sum()) > 500
+        targets, stops, stop_off = h.edit_eval(baseedit.Window(*WINDOW), g, packed)
+        five = h.splice_eval(baseedit.Window(*WINDOW), "cbe", g, packed)
+        at = 0
+        for r, (edit, splice) in enumerate(zip(p.edits(), p.splices())):
+            n = edit[0].size
+            assert np.array_equal(t[at:at + n], edit[0]) and np.array_equal(t[at:at + n], splice[0])
+            for got, want_col in zip((targets, stops, stop_off), edit[1:]):
+                assert np.array_equal(got[at:at + n], want_col), ("edit", r)
+            for got, want_col in zip(five, splice[1:]):
+                assert np.array_equal(got[at:at + n], want_col), ("splice", r)
+            at += n
+        assert at == g.size
+    finally:
+        h.close()
+
+
+@pytest.mark.gpu
+@SLICES
+def test_gpu_selection_behind_the_join(dev, case, slice_rows):
+    """The selection over the joined specificity columns, and the family item kernel with its evaluation, on one arena's
+    handles: the predicate reads the columns the join wrote at these rows."""
+    p = dev.ref
+    table = _family_table(case)
+    pattern, gp, M, scheme = srch.check_specificity(L, 3)
+    handles = []
+    h = None
+    try:
+        srch._self_handles(dev.genome, pattern, gp, srch.SPECIFICITY_PAM_LEN, M, scheme, None, None, handles)
+        srch._self_compare_all(handles, M)
+        srch._family_compare_all(handles, fam.genome_rows(table, dev.genome, dev.request), 0)
+        handles[0].join_hits(L)
+        handles[0].family_join_hits(L)
+        h = dev.select()
+        if slice_rows:
+            h.set_limits(slice_rows)
+        for K in KS:
+            params = sel.Params(K, 0.2)
+            params.max_mm0, params.max_hit_sum = BOUNDS
+            h.run(params, handles[0])
+            _same(h.fetch(), p.select(K, 0.2, BOUNDS), "joined K=%d" % K)
+        g = np.asarray(p.gene, np.int64)
+        h.set_family(table.gene_family[g], np.array([table.family_size(int(x)) for x in g], np.uint32))
+        for K, limits in [(K, FAMILY_LIMITS) for K in (1, 5, 64)] + [(K, FAMILY_TIE_LIMITS) for K in KS]:
+            h.set_family_limits(sel.FamilyLimits(**limits))
+            h.run(sel.Params(K), handles[0])
+            n_in, n_pass, picked, values = p.select_family(K, limits)
+            got = h.fetch()
+            _same(got, (n_in, n_pass, picked), "family K=%d" % K)
+            r, c = np.nonzero(picked != NONE)
+            ev = h.family_eval(handles[0], r.astype(np.uint32), picked[r, c])
+            assert [tuple(int(x[i]) for x in ev) for i in range(r.size)] == [values[a][b] for a, b in zip(r.tolist(), c.tolist())]
+    finally:
+        if h is not None:
+            h.close()
+        for x in handles:
+            x.close()
+
+
+@pytest.mark.gpu
+def test_gpu_genome_level_selection(dev, case):
+    """Genome.scan_score(select=...) with the specificity join, the CDS flag and the pairs: the Selection's rows are the
+    reference's picks, contig-relative."""
+    p = dev.ref
+    try:
+        params = sel.Params(5, 0.2, max_perfect=0, min_specificity=0.5)
+        hits = dev.genome.scan_score(L, specificity=dict(max_mm=3), select=sel.Request(params, dev.request, pairs=sel.PairParams(5, *PAIR_WINDOW)))
+        S = hits.selection
+        spec = dict(p.spec(), max_mm0=BOUNDS[0], max_hit_sum=BOUNDS[1])
+        n_in, n_pass, picked = p.select(5, 0.2, BOUNDS)
+        order = np.argsort(p.gene, kind="stable")
+        assert np.array_equal(S.n_in, n_in[order]) and np.array_equal(S.n_pass, n_pass[order]) and S.n_pass.sum() > 20
+        want = []
+        for r in order:
+            for j, packed in enumerate(picked[r]):
+                if packed == NONE:
+                    break
+                minus, t = int(packed) >> 31, int(packed) & 0x7FFFFFFF
+                kc = int(np.searchsorted(p.rows_before["minus" if minus else "plus"], t, "right")) - 1
+                want.append((int(p.gene[r]), j + 1, kc + 1, int(p.tables["pos_minus" if minus else "pos_plus"][t]) - p.offsets[kc],
+                             b"-" if minus else b"+", int(_bits(p.tables["score_minus" if minus else "score_plus"])[t])))
+        got = [(int(r["gene"]), int(r["rank"]), int(r["contig"]), int(r["position"]), r["strand"], int(_bits(r["score"]))) for r in S.rows]
+        assert got == want
+        pw = pairs_ref.pairs_numpy(p.tables, p.lo, p.hi, 5, *PAIR_WINDOW, min_score=0.2, spec=spec)
+        assert np.array_equal(S.n_pairs, pw[1][order]) and S.n_pairs.sum() > 0 and len(S.pairs) == int(np.minimum(pw[1], 5).sum())
+        _assert_joined(case, p, hits.columns, 3, "hsu2013")
+    finally:
+        dev.scan()
