@@ -274,6 +274,10 @@ int crp_init(int device_id, crp_ctx **out)
         crp_destroy(ctx);
         return CRP_ERR_NOMEM;
     }
+    if (const char *e = std::getenv("CRP_OPT_PREFETCH_TILES")) {
+        const long long v = std::strtoll(e, nullptr, 10);
+        if (v >= -1 && v <= 0x7fffffffll) ctx->prefetch_tiles = v;
+    }
     if (const char *e = std::getenv("CRP_TEST_MUTE_TILE")) ctx->mute_tile = (uint32_t)std::strtoul(e, nullptr, 10);
     {
         const unsigned hw = std::thread::hardware_concurrency();
@@ -646,6 +650,15 @@ static int chain_headers_point_at_host(crp_arena *a)
     return CRP_OK;
 }
 
+// The single-launch scan's prefetch distance on this GPU (CRP_OPT_PREFETCH_TILES = -1): PREFETCH_TILES_PER_CU tiles per
+// CU, against the three LARGE tiles a CU holds at once, rounded to a multiple of the 8 XCDs that workgroups are dealt
+// over, so that the tile asked for runs on the XCD whose L2 was asked (measured: profiles/EXPERIMENTS.md).
+constexpr int PREFETCH_TILES_PER_CU = 3;
+static uint32_t default_prefetch_tiles(const crp_ctx *ctx)
+{
+    return (uint32_t)(PREFETCH_TILES_PER_CU * std::max(1, ctx->n_cu) + 4) / 8 * 8;
+}
+
 // sync = false (crp_stream.cpp): nothing here needs the host to wait -- the scratch is zeroed and the headers written in
 // stream order, before whatever scan is queued next
 static int arena_seal_impl(crp_arena *a, bool sync)
@@ -663,6 +676,7 @@ static int arena_seal_impl(crp_arena *a, bool sync)
     const uint64_t tw = (uint64_t)crp::tile_words(a->geo);
     const uint64_t eff = round_up(a->used_words, tw);  // <= padded_words
     a->n_tiles = (uint32_t)(eff / tw);
+    a->prefetch_tiles = default_prefetch_tiles(ctx);
     if (a->n_tiles > a->tile_cap) {  // (an arena that is reset and filled again keeps its scratch: crp::arena_reset)
         (void)hipFree(a->d_tile_cnt);
         (void)hipFree(a->d_tile_off);
@@ -822,8 +836,9 @@ static int single_launch(crp_arena *a, const crp::Planes &pl, uint64_t eff_words
     uint64_t *cur = a->d_chain[a->chain_cur], *next = a->d_chain[a->chain_cur ^ 1];
     a->h_totals[0] = a->h_totals[1] = a->h_totals[2] = 0;
     prof_begin(ctx, 2);
+    const uint32_t prefetch_tiles = ctx->prefetch_tiles >= 0 ? (uint32_t)ctx->prefetch_tiles : a->prefetch_tiles;
     CRP_HIP(ctx, crp::launch_emit_chained(ctx->stream, a->geo, pl, eff_words, guide_len, cur, next, *out, ctx->mute_tile,
-                                          ctx->chain_timeout_ticks));
+                                          ctx->chain_timeout_ticks, prefetch_tiles));
     prof_end(ctx, 2);
     return CRP_OK;
 }
@@ -1122,6 +1137,10 @@ int crp_configure(crp_ctx *ctx, int option, int64_t value)
         case CRP_OPT_TILE_GEOMETRY:
             if (value < 0 || value > crp::GEO_COUNT) return CRP_ERR_INVALID;
             ctx->geometry = (int)value;  // arenas sealed from now on
+            return CRP_OK;
+        case CRP_OPT_PREFETCH_TILES:
+            if (value < -1 || value > 0x7fffffffll) return CRP_ERR_INVALID;
+            ctx->prefetch_tiles = value;  // scans launched from now on
             return CRP_OK;
         default: return CRP_ERR_INVALID;
     }

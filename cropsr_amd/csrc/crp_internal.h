@@ -32,6 +32,7 @@ struct crp_ctx {
     uint64_t chain_timeouts = 0;    // single-launch scans that were repeated with three launches
     uint32_t chain_timeout_ticks = 2000000;  // CRP_OPT_CHAIN_TIMEOUT_US in ticks of the 100 MHz real-time counter
     int geometry = 0;  // CRP_OPT_TILE_GEOMETRY: 0 = by arena size, else GEO_* + 1
+    int64_t prefetch_tiles = -1;  // CRP_OPT_PREFETCH_TILES: -1 = the arena's default (set at seal), else as given (0 = off)
     uint32_t mute_tile = 0xffffffffu;  // test hook (environment CRP_TEST_MUTE_TILE): see crp_kernels.h
     // host <-> device staging for large transfers from / to pageable caller memory (crp_api.cpp: staged_h2d / staged_d2h):
     // two pinned buffers, filled / drained by a few host threads while the other one is on the link
@@ -83,6 +84,7 @@ struct crp_arena {
     uint32_t n_tiles = 0;
     uint32_t tile_cap = 0;  // tiles the per-tile scratch has room for (an arena that is reset and refilled keeps it)
     int geo = 0;  // GEO_*: tile geometry, chosen at seal
+    uint32_t prefetch_tiles = 0;  // the single-launch scan's prefetch distance unless CRP_OPT_PREFETCH_TILES forces one; chosen at seal
     // hit tables: [0] = '+', [1] = '-'
     uint32_t *d_pos[2] = {nullptr, nullptr};
     double *d_score[2] = {nullptr, nullptr};

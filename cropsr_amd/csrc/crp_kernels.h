@@ -79,8 +79,10 @@ hipError_t launch_emit(hipStream_t s, int geo, const Planes &pl, uint64_t n_word
 size_t chain_bytes(uint32_t n_tiles);
 // mute_tile: 0xffffffff, or (tests) the index of a tile that withholds its counts so that the look-back times out
 // timeout_ticks: how long a look-back may wait, in ticks of the 100 MHz real-time counter
+// prefetch_tiles: tile t asks for the planes of tile t + prefetch_tiles while it scores (0: no prefetch; see emit_kernel)
 hipError_t launch_emit_chained(hipStream_t s, int geo, const Planes &pl, uint64_t n_words_padded, int l, uint64_t *chain,
-                               uint64_t *chain_next, const HitTables &out, uint32_t mute_tile, uint32_t timeout_ticks);
+                               uint64_t *chain_next, const HitTables &out, uint32_t mute_tile, uint32_t timeout_ticks,
+                               uint32_t prefetch_tiles);
 // adds the number of entries of score[0..n) that are not -1 to *out (device memory)
 hipError_t launch_count_scored(hipStream_t s, const double *score, uint64_t n, uint64_t *out);
 // adds the number of upper-case A/C/G/T characters of the planes' first n_words words to *out (device memory)

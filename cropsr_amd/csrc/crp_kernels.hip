@@ -584,17 +584,19 @@ struct EmitKernArgs {
     HitTables out;
     uint32_t mute_tile;
     uint32_t timeout_ticks;
+    uint32_t prefetch_tiles;
 };
 static_assert(offsetof(EmitKernArgs, chain) == offsetof(EmitKernArgs, tile_off) + sizeof(void *) &&
                   offsetof(EmitKernArgs, chain_next) == offsetof(EmitKernArgs, chain) + sizeof(void *),
               "the chain pointers follow tile_off");
 static_assert(offsetof(EmitKernArgs, out) == offsetof(EmitKernArgs, chain_next) + sizeof(void *) &&
                   offsetof(EmitKernArgs, mute_tile) == offsetof(EmitKernArgs, out) + sizeof(HitTables) &&
-                  offsetof(EmitKernArgs, timeout_ticks) == offsetof(EmitKernArgs, mute_tile) + sizeof(uint32_t),
+                  offsetof(EmitKernArgs, timeout_ticks) == offsetof(EmitKernArgs, mute_tile) + sizeof(uint32_t) &&
+                  offsetof(EmitKernArgs, prefetch_tiles) == offsetof(EmitKernArgs, timeout_ticks) + sizeof(uint32_t),
               "the hit tables sit between chain_next and mute_tile, unpadded");
 static_assert(sizeof(HitTables) == 10 * 8 && alignof(HitTables) == 8, "ten 8-byte fields");
-static_assert(sizeof(EmitKernArgs) == sizeof(Planes) + 2 * 8 + 3 * sizeof(void *) + sizeof(HitTables) + 2 * sizeof(uint32_t),
-              "no padding but behind l_arg");
+static_assert(sizeof(EmitKernArgs) == sizeof(Planes) + 2 * 8 + 3 * sizeof(void *) + sizeof(HitTables) + 4 * sizeof(uint32_t),
+              "no padding but behind l_arg and at the end");
 
 typedef const EmitKernArgs __attribute__((address_space(4))) *LateArgs;
 __device__ __forceinline__ LateArgs late_args()
@@ -675,6 +677,56 @@ __device__ __forceinline__ void chain_resolve(const ChainArgs &ch_in)
         }
     }
     __hip_atomic_store(ch.s_flag, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// ---- successor prefetch (single-launch emit kernel)
+// A tile's first act is to wait for four plane loads that nobody has asked for before: cold misses at the head of the
+// phase every later tile waits for.  Tile t therefore asks for plane `p` of tile t + prefetch_tiles while it scores: with
+// prefetch_tiles a multiple of 8 that tile runs on the same XCD, hence finds the lines in the same L2.  One dword per
+// 128-byte line, ONE wave-instruction per plane, issued by ONE wave (p = 0 ... 3: waves 1 ... 4; wave 0's look-back loads
+// would queue behind the miss) right behind the store of its first row in the tile's last round: the row loop that follows
+// waits for no vector memory access (its stores are not waited for), so the wave does not stall on the miss, and a
+// whole row loop, some microseconds, lies between the request and the end of the tile, when the slot's next tile
+// starts.  (Measured: before the first row the wave stalls at that row's s_waitcnt vmcnt(0), +2 to +6 %; as the
+// wave's last instruction the lines come too late or, from further ahead, are evicted before use, +1 to +9 %:
+// profiles/EXPERIMENTS.md.)
+// Nothing reads the loaded dwords, but the load writes its destination when it RETURNS, and the compiler does not know
+// that: the destination is the index register itself, `idx` -- the caller's round-invariant list offset, which keeps its
+// register through the row loop and which nothing reads after the last round's first row.
+//
+// No VALU: everything but the load is scalar.  The line is chosen by a VGPR the caller has anyway, idx = 2 * (lane + 64 * p)
+// -- the list offset of the wave's first row -- as the INDEX of a buffer load through a descriptor with a stride of
+// TILE_WORDS / 16 bytes (not swizzled: address = base + idx * stride), whose base is moved back by p tiles:
+//     address = plane + 8 * first word of the target tile + lane * TILE_WORDS / 8
+// which is lane * 128 (LARGE: 64 lines) or lane * 64 (SMALL: 32 lines, two dwords each) into the target tile's 8 *
+// TILE_WORDS bytes of that plane: every address lies INSIDE the target tile by construction.  The load is issued only
+// when the target is a tile of the grid (one scalar branch; the grid is n_words_padded / TILE_WORDS whole tiles, which the
+// arena's allocation covers), so no address leaves the planes whatever prefetch_tiles is: a target one past the grid or
+// far past the arena is not asked for.  The descriptor's num_records states the same end once more -- the bytes from the
+// moved base to the end of the grid -- so the hardware's range check would drop a load beyond it under either reading
+// of the field for an indexed load (bytes: the grid's end exactly; records: looser than the 510 indices in use).
+template <int TILE_WORDS>
+__device__ __forceinline__ void prefetch_successor_plane(uint32_t tile, uint32_t p, uint32_t &idx)
+{
+    constexpr uint32_t TILE_BYTES = TILE_WORDS * 8;  // of one plane
+    static_assert(TILE_WORDS % 16 == 0 && 63 * (TILE_WORDS / 8) + 4 <= TILE_BYTES, "a lane's dword lies inside the tile");
+    const LateArgs args = late_args();
+    const uint32_t ahead = late_arg<uint32_t>(args, offsetof(EmitKernArgs, prefetch_tiles));
+    // (the low half of n_words_padded: an arena's positions are 32 bits wide, its words 26)
+    const uint32_t n_tiles = late_arg<uint32_t>(args, offsetof(EmitKernArgs, n_words_padded)) / TILE_WORDS;
+    const uint32_t room = n_tiles - tile;  // >= 1: tiles from this one to the end of the grid
+    if (ahead == 0 || ahead >= room) return;  // off, or past the grid: wave-uniform
+    const uint64_t plane = late_arg<uint64_t>(args, offsetof(EmitKernArgs, pl) + sizeof(uint64_t) * p);
+    const uint64_t base = plane + ((uint64_t)(tile + ahead) - p) * TILE_BYTES;  // (modulo 2^64 where p > tile + ahead)
+    // (num_records is 32 bits wide: a grid of more than 4 GiB per plane is cut there, not wrapped)
+    const uint32_t bytes = (min(room - ahead, (0xffffffffu - 3 * TILE_BYTES) / TILE_BYTES) + p) * TILE_BYTES;
+    typedef uint32_t u32x4 __attribute__((__vector_size__(4 * sizeof(uint32_t))));
+    u32x4 rsrc;
+    rsrc[0] = (uint32_t)base;
+    rsrc[1] = ((uint32_t)(base >> 32) & 0xffffu) | ((uint32_t)(TILE_WORDS / 16) << 16);  // stride; not swizzled
+    rsrc[2] = bytes;
+    rsrc[3] = 0x00020000u;
+    asm volatile("buffer_load_dword %[idx], %[idx], %[rsrc], 0 idxen" : [idx] "+v"(idx) : [rsrc] "s"(rsrc) : "memory");
 }
 
 // exp table + chain-prefix tables as ONE image in global memory, in the order the emit kernel keeps them in LDS
@@ -801,11 +853,12 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
 // G: the tile geometry (crp_kernels.h): G::BLOCK threads on a tile of G::WORDS words, of which the first G::OWNERS threads
 //    own G::WPT words each (load them, derive their masks, build their part of the hit list); all threads score.
 // The parameter list is mirrored by EmitKernArgs (above), from whose offsets the single-launch kernel reads `out`, `chain`,
-// `n_words_padded`, `mute_tile` and `timeout_ticks` late; EmitKernArgsMirror (below the kernel) holds the two together.
+// `n_words_padded`, `mute_tile`, `timeout_ticks`, `prefetch_tiles` and (for the prefetch) the plane pointers late; EmitKernArgsMirror (below the kernel) holds the two together.
 template <class G, bool CHAINED, int LFIX, bool PRE, bool SEEDS>
 __global__ __launch_bounds__(G::BLOCK) __attribute__((amdgpu_waves_per_eu(6, 8))) void emit_kernel(
     Planes pl, uint64_t n_words_padded, int l_arg, const uint2 *__restrict__ tile_off, uint64_t *chain,
-    uint64_t *__restrict__ chain_next, HitTables out, uint32_t mute_tile, uint32_t timeout_ticks)
+    uint64_t *__restrict__ chain_next, HitTables out, uint32_t mute_tile, uint32_t timeout_ticks,
+    uint32_t prefetch_tiles)
 {
     const int l = LFIX > 0 ? LFIX : l_arg;
     constexpr int TW = G::WORDS;
@@ -933,6 +986,13 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
     // counts that the compiler cannot trace back -- as loop invariants they are lane masks in SGPR pairs, carried
     // through the set-up and the first row's scorer and spilled there)
     const uint32_t list_lds = (uint32_t)(uintptr_t)list;  // LDS byte address of the list
+    // Single pass.  The workgroup's slot (LDS, wave slots) is held until its LAST wave is done, and wave 0 also resolves
+    // the tile's prefix.  So wave 0 takes the chunks of 64 rows nobody would miss: waves 1 ... 7 own chunks 0 ... 6 (mod 8)
+    // and wave 0 chunk 7 -- when the row count is not a multiple of 512 it is wave 0 that has one chunk less, not one more.
+    // row0: the list offset of a lane's first row in every round, 2 * (lane + 64 * its chunk).  It is held in a register
+    // across the rounds -- the register the successor prefetch loads into, in the tile's last round (below).
+    uint32_t row0 = 2u * (uint32_t)tid;
+    if (CHAINED) row0 = 2u * ((uint32_t)(tid & 63) | ((((uint32_t)tid >> 6) + (G::BLOCK / 64 - 1)) % (G::BLOCK / 64)) << 6);
     uint32_t hi_rank = 0;
     for (uint32_t lo_rank = 0; lo_rank < n_all; lo_rank = hi_rank) {
         uint32_t np = n_plus, nm = n_minus;
@@ -1145,11 +1205,12 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
                 }
             }
         };
-        // Rows k, k + 256, ... of one lane.  `before_first_store` runs once, after the first row is scored: from the
-        // second row on a row is stored as soon as it is scored -- nothing is parked in registers.  (Issuing the next
-        // row's LDS reads ahead of the current row's arithmetic was measured: +4 %, profiles/EXPERIMENTS.md.)
-        auto run_rows = [&](uint32_t k, auto before_first_store) {
-            uint32_t a2 = 2u * k;
+        // The rows at list offsets row0, row0 + 2 * BLOCK, ... of one lane.  `before_first_store` runs once, after the
+        // first row is scored: from the second row on a row is stored as soon as it is scored -- nothing is parked in
+        // registers; `after_first_store` runs behind that store, in a wave that has rows.  (Issuing the next row's LDS
+        // reads ahead of the current row's arithmetic was measured: +4 %, profiles/EXPERIMENTS.md.)
+        auto run_rows = [&](auto before_first_store, auto after_first_store) {
+            uint32_t a2 = row0;
             const bool any = a2 < end2;
             Hit first{};
             if (any) first = score(fetch(a2));
@@ -1160,25 +1221,31 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
                 // re-derives the current one on every trip: a copy and an add)
                 a2 += 2u * G::BLOCK;
                 asm("" : "+v"(a2));
+                after_first_store();
                 for (; a2 < end2; a2 += 2u * G::BLOCK) store(score(fetch(a2)));
             }
         };
         if (!CHAINED) {
-            run_rows(tid, [](bool) {});
+            run_rows([](bool) {}, [] {});
         } else {
-            // Single pass.  The workgroup's slot (LDS, wave slots) is held until its LAST wave is done, and wave 0
-            // also resolves the tile's prefix.  So wave 0 takes the chunks of 64 rows nobody would miss: waves 1 ... 7
-            // own chunks 0 ... 6 (mod 8) and wave 0 chunk 7 -- when the row count is not a multiple of 512 it is
-            // wave 0 that has one chunk less, not one more.
-            const uint32_t k0 = (uint32_t)(tid & 63) | ((((uint32_t)tid >> 6) + (G::BLOCK / 64 - 1)) % (G::BLOCK / 64)) << 6;
             // the whole look-back BEFORE wave 0 scores anything (nothing of the scorer is live then)
             int first_wave = wave;
+            if (PRE && SEEDS) {
+                // (with both extra columns no scalar register is free to carry the wave index through the set-up and the
+                // list build to here and on to the prefetch: it would be spilled, two VALU instructions; read again, one)
+                int t = tid;
+                asm volatile("" : "+v"(t));
+                first_wave = __builtin_amdgcn_readfirstlane(t) >> 6;
+            }
             asm volatile("" : "+s"(first_wave));
             if (lo_rank == 0 && first_wave == 0) chain_resolve<G::WORDS>(ch);
+            // (tile and wave index in ONE register from here to the prefetch, behind the first row: a tile index has 17 bits)
+            uint32_t tile_wave = ch.tile | (uint32_t)first_wave << 24;
+            asm volatile("" : "+s"(tile_wave));
             // The other waves score their first rows meanwhile and need the offsets only to STORE them: by then
             // (one scoring iteration, ~4 us, after wave 0 started looking back) the flag is normally up.  From
             // the second iteration on a row is stored as soon as it is scored -- nothing is parked in registers.
-            run_rows(k0, [&](bool any) {
+            run_rows([&](bool any) {
                 // wave-uniform (the descriptors must stay in SGPRs): a wave with rows waits for the flag, which is up from
                 // the tile's second round on, and builds its descriptors in every round: nothing of this is carried
                 // across the list build
@@ -1190,6 +1257,16 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
                     const uint64_t e = uniform64(*ch.s_excl);
                     tile_stores<PRE, SEEDS>(ts, late, e & 0xffffffffull, e >> 32, n_plus);
                 }
+            }, [&] {
+                // Waves 1 ... 4, their first row stored, ask for one plane each of the tile that runs `prefetch_tiles`
+                // tiles after this one (prefetch_successor_plane).  Index and destination of the load are row0's
+                // register, which is = 2 * (lane + 64 * (wave - 1)) in these waves and, in the tile's LAST round, read by
+                // nothing any more: the row loop counts in a register of its own.  To the compiler row0 stays what it
+                // is on the way through the row loop, a value the next round reads, so it keeps its register to itself
+                // while the load is in flight (tools/emit_isa_budget.py looks: prefetch.dst_written_in_row_loop).
+                static_assert(G::BLOCK / 64 >= 5, "waves 1 ... 4 prefetch");
+                const uint32_t plane = (tile_wave >> 24) - 1;
+                if (hi_rank == n_all && plane < 4u) prefetch_successor_plane<G::WORDS>(tile_wave & 0xffffffu, plane, row0);
             });
         }
     }
@@ -1202,7 +1279,7 @@ template <class F>
 struct EmitKernArgsMirror;
 template <class... A>
 struct EmitKernArgsMirror<void (*)(A...)> {
-#define CRP_MEMBERS(X) X(pl), X(n_words_padded), X(l_arg), X(tile_off), X(chain), X(chain_next), X(out), X(mute_tile), X(timeout_ticks)
+#define CRP_MEMBERS(X) X(pl), X(n_words_padded), X(l_arg), X(tile_off), X(chain), X(chain_next), X(out), X(mute_tile), X(timeout_ticks), X(prefetch_tiles)
 #define CRP_TYPE(m) decltype(EmitKernArgs::m)
 #define CRP_OFFSET(m) offsetof(EmitKernArgs, m)
     static constexpr bool same_types = std::is_same<std::tuple<A...>, std::tuple<CRP_MEMBERS(CRP_TYPE)>>::value;
@@ -1216,7 +1293,7 @@ struct EmitKernArgsMirror<void (*)(A...)> {
             if (at != member[k]) return false;
             at += size[k];
         }
-        return at == sizeof(EmitKernArgs);
+        return (at + alignof(EmitKernArgs) - 1) / alignof(EmitKernArgs) * alignof(EmitKernArgs) == sizeof(EmitKernArgs);  // (tail padding)
     }
 #undef CRP_OFFSET
 #undef CRP_TYPE
@@ -1437,7 +1514,7 @@ hipError_t launch_tile_scan(hipStream_t s, const uint2 *tile_cnt, uint32_t n_til
 template <class G, bool CHAINED>
 static hipError_t launch_emit_variant(hipStream_t s, const Planes &pl, uint64_t n_words_padded, int l, const uint2 *tile_off,
                                       uint64_t *chain, uint64_t *chain_next, const HitTables &out, uint32_t mute_tile,
-                                      uint32_t timeout_ticks)
+                                      uint32_t timeout_ticks, uint32_t prefetch_tiles)
 {
     const uint32_t n_tiles = (uint32_t)(n_words_padded / G::WORDS);
     if (n_tiles == 0) return hipSuccess;
@@ -1445,7 +1522,7 @@ static hipError_t launch_emit_variant(hipStream_t s, const Planes &pl, uint64_t 
     if (seeds && l != 20) return hipErrorInvalidValue;
 #define CRP_LAUNCH(LFIX, PRE, SEEDS)                                                                                       \
     hipLaunchKernelGGL((emit_kernel<G, CHAINED, LFIX, PRE, SEEDS>), dim3(n_tiles), dim3(G::BLOCK), 0, s, pl, n_words_padded, l, \
-                       tile_off, chain, chain_next, out, mute_tile, timeout_ticks)
+                       tile_off, chain, chain_next, out, mute_tile, timeout_ticks, prefetch_tiles)
     if (l == 20) {
         if (seeds) {
             if (pre) CRP_LAUNCH(20, true, true);
@@ -1465,7 +1542,7 @@ static hipError_t launch_emit_variant(hipStream_t s, const Planes &pl, uint64_t 
 hipError_t launch_emit(hipStream_t s, int geo, const Planes &pl, uint64_t n_words_padded, int l, const uint2 *tile_off,
                        const HitTables &out)
 {
-#define CRP_CALL(G) launch_emit_variant<G, false>(s, pl, n_words_padded, l, tile_off, nullptr, nullptr, out, 0xffffffffu, 0u)
+#define CRP_CALL(G) launch_emit_variant<G, false>(s, pl, n_words_padded, l, tile_off, nullptr, nullptr, out, 0xffffffffu, 0u, 0u)
     CRP_BY_GEOMETRY(geo, CRP_CALL)
 #undef CRP_CALL
 }
@@ -1473,9 +1550,11 @@ hipError_t launch_emit(hipStream_t s, int geo, const Planes &pl, uint64_t n_word
 size_t chain_bytes(uint32_t n_tiles) { return (CHAIN_HEADER_WORDS + (size_t)n_tiles) * sizeof(uint64_t); }
 
 hipError_t launch_emit_chained(hipStream_t s, int geo, const Planes &pl, uint64_t n_words_padded, int l, uint64_t *chain,
-                               uint64_t *chain_next, const HitTables &out, uint32_t mute_tile, uint32_t timeout_ticks)
+                               uint64_t *chain_next, const HitTables &out, uint32_t mute_tile, uint32_t timeout_ticks,
+                               uint32_t prefetch_tiles)
 {
-#define CRP_CALL(G) launch_emit_variant<G, true>(s, pl, n_words_padded, l, nullptr, chain, chain_next, out, mute_tile, timeout_ticks)
+#define CRP_CALL(G) \
+    launch_emit_variant<G, true>(s, pl, n_words_padded, l, nullptr, chain, chain_next, out, mute_tile, timeout_ticks, prefetch_tiles)
     CRP_BY_GEOMETRY(geo, CRP_CALL)
 #undef CRP_CALL
 }

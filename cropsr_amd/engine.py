@@ -449,17 +449,21 @@ class Engine:
             score[base:base + 2] = self.score_30mers(sequences[base:base + 2], nat.ORDER_TAIL2)[1]
         return score
 
-    def configure(self, two_pass=None, chain_timeout_us=None, geometry=None):
+    def configure(self, two_pass=None, chain_timeout_us=None, geometry=None, prefetch_tiles=None):
         """two_pass=False (the default): one launch per scan, table offsets from the chained
         scan inside the emit kernel; True: the count / tile-scan / emit launch sequence.
         Same results either way (every GPU parity test runs in both modes).
-        chain_timeout_us: how long a single-launch workgroup may wait for a predecessor."""
+        chain_timeout_us: how long a single-launch workgroup may wait for a predecessor.
+        prefetch_tiles: how many tiles ahead a tile of the single-launch scan asks for planes (0: no prefetch; -1: the
+        arena's default for this GPU).  Same results at any value."""
         if two_pass is not None:
             nat.check(nat.lib().crp_configure(self._ctx, nat.OPT_TWO_PASS, int(bool(two_pass))), "crp_configure")
         if chain_timeout_us is not None:
             nat.check(nat.lib().crp_configure(self._ctx, nat.OPT_CHAIN_TIMEOUT_US, int(chain_timeout_us)), "crp_configure")
         if geometry is not None:  # "auto" | "large" | "small": the tile shape of arenas sealed from now on
             nat.check(nat.lib().crp_configure(self._ctx, nat.OPT_TILE_GEOMETRY, nat.GEOMETRIES[geometry]), "crp_configure")
+        if prefetch_tiles is not None:
+            nat.check(nat.lib().crp_configure(self._ctx, nat.OPT_PREFETCH_TILES, int(prefetch_tiles)), "crp_configure")
 
     def query(self):
         """Fallback and communicator state: chain_timeouts (single-launch scans repeated as three

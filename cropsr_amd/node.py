@@ -106,12 +106,14 @@ class Node:
         """Raw crp_ctx of logical device k (for crp_configure / crp_profile_* / crp_device_info)."""
         return ctypes.c_void_p(nat.lib().crp_node_ctx(self._h, int(k)))
 
-    def configure(self, two_pass=None, geometry=None):
+    def configure(self, two_pass=None, geometry=None, prefetch_tiles=None):
         for k in range(self.size):
             if two_pass is not None:
                 nat.check(nat.lib().crp_configure(self.ctx(k), nat.OPT_TWO_PASS, int(bool(two_pass))), "crp_configure")
             if geometry is not None:
                 nat.check(nat.lib().crp_configure(self.ctx(k), nat.OPT_TILE_GEOMETRY, nat.GEOMETRIES[geometry]), "crp_configure")
+            if prefetch_tiles is not None:
+                nat.check(nat.lib().crp_configure(self.ctx(k), nat.OPT_PREFETCH_TILES, int(prefetch_tiles)), "crp_configure")
 
     def device_info(self, k=0):
         name = ctypes.create_string_buffer(128)

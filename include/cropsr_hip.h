@@ -1160,6 +1160,12 @@ int crp_select_family_stats(const crp_select *select, double *out, int n);
  *   1  LARGE   512 threads on 1 024 words (65 536 positions), two words per lane: the throughput shape
  *   2  SMALL   512 threads on 512 words, one word per lane: half the rows per lane, half the tile's life */
 #define CRP_OPT_TILE_GEOMETRY 3
+/* CRP_OPT_PREFETCH_TILES (default -1; also read from the environment variable of the same name when the context is
+ * created): in the single-launch scan, a tile that is done with its rows asks for the planes of the tile that many tiles
+ * after it, so that the tile finds them in the L2.  -1: the distance crp_arena_seal chose for the
+ * arena from the GPU's size; 0: no prefetch; any other value is used as given (a multiple of 8 keeps requester and
+ * target on one XCD).  Results do not depend on it.  Applies to the scans launched after the call. */
+#define CRP_OPT_PREFETCH_TILES 4
 int crp_configure(crp_ctx *ctx, int option, int64_t value);
 
 /* Read-only state, for logs and bench output. */

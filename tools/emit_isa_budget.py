@@ -11,6 +11,9 @@ pre-sigmoid column, no seed words), splits it into basic blocks and prints
   void terms the part of the set-up that only a wave with a void bit in reach runs (the void tests of the hit masks),
              and whether the branch around it is a scalar one
 
+  vmem loads the vector-memory loads outside the set-up, by region (rounds, row loop, behind the round loop), and those of
+             them that are the successor prefetch: indexed buffer loads whose result nothing reads
+
 as VALU / f64 / SALU instruction counts, plus the compiler's resource usage: VGPRs, SGPR spills, scratch, LDS and
 occupancy.  These are static counts: how often each block runs depends on the genome.
 
@@ -81,7 +84,7 @@ def compile_asm(workdir, extra=()):
 
 def kernel_name(geo="large", chained=True, lfix=20, pre=False, seeds=False):
     b = lambda v: "Lb1E" if v else "Lb0E"
-    return ("_ZN3crp11emit_kernelINS_7TileGeoILi%sEE%sLi%dE%s%sEEvNS_6PlanesEmiPK15HIP_vector_typeIjLj2EEPmS8_NS_9HitTablesEjj"
+    return ("_ZN3crp11emit_kernelINS_7TileGeoILi%sEE%sLi%dE%s%sEEvNS_6PlanesEmiPK15HIP_vector_typeIjLj2EEPmS8_NS_9HitTablesEjjj"
             % (GEOMETRY[geo], b(chained), lfix, b(pre), b(seeds)))
 
 
@@ -164,6 +167,38 @@ def void_region(asm, name):
     return dict(counts(region), uniform=bool(region) and uniform)
 
 
+def vmem_loads(instrs):
+    """the vector-memory loads among `instrs`; `prefetch`: the indexed buffer loads (idxen), which only the successor prefetch
+    of the single-launch kernel issues -- every other buffer access of the kernel addresses by offset"""
+    loads = [i for i in instrs if i.split()[0].startswith(("buffer_load", "global_load", "flat_load", "scratch_load"))]
+    return {"count": len(loads), "prefetch": sum(i.split()[-1] == "idxen" for i in loads), "instructions": loads}
+
+
+def registers(operand):
+    """the VGPR numbers an operand names: v7 -> {7}, v[4:5] -> {4, 5}"""
+    m = re.fullmatch(r"v(\d+)", operand)
+    if m:
+        return {int(m.group(1))}
+    m = re.fullmatch(r"v\[(\d+):(\d+)\]", operand)
+    return set(range(int(m.group(1)), int(m.group(2)) + 1)) if m else set()
+
+
+def prefetch_dst_written(prefetch_ins, row_loop_ins):
+    """Row-loop instructions that write the register a prefetch loads into.  The load returns long after it was issued, and
+    the compiler does not know: the register must be one that nothing writes while the load is in flight.  (First operand =
+    destination of every VALU, LDS-read and load instruction; stores and LDS writes have none.)"""
+    dst = set()
+    for i in prefetch_ins:
+        dst |= registers(i.split()[1].rstrip(","))
+    hits = []
+    for i in row_loop_ins:
+        op = i.split()
+        if len(op) > 1 and not op[0].startswith(("buffer_store", "global_store", "flat_store", "ds_write", "s_", "v_cmp")) \
+                and registers(op[1].rstrip(",")) & dst:
+            hits.append(i)
+    return hits
+
+
 def add(a, b):
     return {k: a.get(k, 0) + b[k] for k in b}
 
@@ -189,6 +224,7 @@ def budget(asm, remarks, name):
         raise SystemExit("the scorer is not inside a loop")
     outer = loops_of(row_loop)[-1]
     row, setup, rounds = {}, {}, {}
+    region_ins = {"rounds": [], "row_loop": [], "tail": []}  # (tail: laid out behind the round loop's header, outside the loop)
     seen_outer = False
     zero = counts([])
     for label, header, _, ins in blocks:
@@ -198,10 +234,14 @@ def budget(asm, remarks, name):
             seen_outer = True
         if row_loop in in_loops:
             row = add(row or zero, c)
+            region_ins["row_loop"] += ins
         elif outer in in_loops:
             rounds = add(rounds or zero, c)
+            region_ins["rounds"] += ins
         elif not seen_outer:
             setup = add(setup or zero, c)
+        else:
+            region_ins["tail"] += ins
     res = resources(remarks, name)
     all_ins = [i for b in blocks for i in b[3]]
     return {
@@ -212,6 +252,9 @@ def budget(asm, remarks, name):
         "setup_void": void_region(asm, name),
         "rounds": rounds,
         "whole": counts(all_ins),
+        "vmem_loads": {region: vmem_loads(ins) for region, ins in region_ins.items()},
+        "prefetch": {"dst_written_in_row_loop": prefetch_dst_written(
+            [i for ins in region_ins.values() for i in vmem_loads(ins)["instructions"] if i.split()[-1] == "idxen"], region_ins["row_loop"])},
         "vgprs": int(res["VGPRs"]),
         "sgprs": int(res["TotalSGPRs"]),
         "sgpr_spills": int(res["SGPRs Spill"]),
@@ -244,6 +287,8 @@ def main():
               % (part, c["valu"], c["f64"], c["salu"], c["writelane"], c["readlane"]))
     v = b["setup_void"]
     print("  void terms VALU %4d of the set-up's, behind a %s branch" % (v["valu"], "scalar" if v["uniform"] else "NON-UNIFORM"))
+    for region, v in b["vmem_loads"].items():
+        print("  vmem loads in %-8s %d, of which prefetch %d" % (region, v["count"], v["prefetch"]))
     print("  VGPRs %d  SGPRs %d  SGPR spills %d  VGPR spills %d  scratch %d B  LDS %d B  occupancy %d waves/SIMD"
           % (b["vgprs"], b["sgprs"], b["sgpr_spills"], b["vgpr_spills"], b["scratch"], b["lds"], b["occupancy"]))
 
