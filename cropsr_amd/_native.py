@@ -247,6 +247,9 @@ SIGNATURES = {
     "crp_select_set_family_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "crp_select_family_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u32p, u32p, ctypes.c_uint64, u32p, u64p, u32p, u32p, u64p]),
     "crp_select_family_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
+    "crp_select_set_family_members": (ctypes.c_int, [ctypes.c_void_p, u32p, ctypes.c_uint64]),
+    "crp_select_family_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, u64p, ctypes.c_uint64, ctypes.c_void_p]),
+    "crp_select_family_step_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_select_coding_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_select_set_edit_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "crp_select_edit_eval": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, u32p, u32p, ctypes.c_uint64, u32p, u32p]),
@@ -289,6 +292,9 @@ SEARCH_PAM_3PRIME, SEARCH_PAM_5PRIME = 0, 1
 SEARCH_SHAPE_DOUBLES = 288
 SEARCH_SELF_MAX_MM = 4
 SEARCH_PAIR_MAX_PAM = 3
+FAMILY_SET_MAX_STEPS = 64  # CRP_FAMILY_SET_MAX_STEPS
+# crp_family_step_best (include/cropsr_hip.h): one proposal of crp_select_family_step
+FAMILY_STEP_BEST_DTYPE = [("key", "<u8"), ("cover", "<u8"), ("gain", "<u4"), ("tie", "<u4"), ("row", "<u4"), ("gene", "<u4")]
 SELECT_ALL_MEMBERS = 0xFFFFFFFF  # crp_select_family_limits.min_members: the size of the gene's family
 SELF_UNJOINED_COUNT, SELF_UNJOINED_SUM = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF  # crp_search_self_join_hits: a hit without a guide site's row
 SELECT_MAX_K, SELECT_DEFAULT_SLICE_ROWS, SELECT_MIN_SLICE_ROWS, SELECT_NONE = 64, 65536, 64, 0xFFFFFFFF

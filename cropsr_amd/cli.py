@@ -191,6 +191,13 @@ def build_parser():
                           "(--select-max-perfect counts the homeologs too)")
     eng.add_argument("--select-min-specificity-outside", default=None, metavar="S",
                      help="with --families: only guides whose specificity, with the hits inside the gene's family left out, is at least S")
+    eng.add_argument("--family-sets", default=None, metavar="S",
+                     help="with --families: per gene family, at most S guides (1..64) that together cut as many of its members as "
+                          "possible, chosen greedily on the GPU from the guides that pass the selection's filters: each step takes "
+                          "the guide that cuts the most members not cut yet (the multiplex set for a family whose copies have "
+                          "diverged); one row per chosen guide goes to --family-sets-output")
+    eng.add_argument("--family-sets-output", default=None, metavar="FILE",
+                     help="with --family-sets: where the family sets go (default: the -o path + .family_sets.csv)")
     eng.add_argument("--base-edit", action="store_true",
                      help="with --select: what a cytosine base editor does under every selected guide: the C's of a window of the "
                           "protospacer become T's, which can turn CAA, CAG, CGA or (from the other strand) TGG of the gene's longest "
@@ -652,7 +659,8 @@ def select_request(args, spec, world=1):
                                    ("--family-cover-mismatches", "family_cover_mismatches", None),
                                    ("--select-min-members", "select_min_members", None),
                                    ("--select-max-perfect-outside", "select_max_perfect_outside", None),
-                                   ("--select-min-specificity-outside", "select_min_specificity_outside", None))
+                                   ("--select-min-specificity-outside", "select_min_specificity_outside", None),
+                                   ("--family-sets", "family_sets", None), ("--family-sets-output", "family_sets_output", None))
              if getattr(args, k, unset) not in (unset, None)]
     KP = getattr(args, "select_pairs", None)
     pair_given = [o for o, k, unset in (("--pairs-min-distance", "pairs_min_distance", None), ("--pairs-max-distance", "pairs_max_distance", None),
@@ -828,11 +836,23 @@ def select_request(args, spec, world=1):
                                                            ("--select-min-specificity-outside", "select_min_specificity_outside"))]
     family_limit = [o for o, v in family_opts[1:] if v is not None]
     family_pairs = None
+    sets = getattr(args, "family_sets", None)
+    if sets is None and getattr(args, "family_sets_output", None) is not None:
+        refuse("--family-sets-output belongs to --family-sets")
     if getattr(args, "families", None) is None:
-        for o, v in family_opts:
+        for o, v in family_opts + [("--family-sets", sets)]:
             if v is not None:
                 refuse("%s belongs to --families" % o)
     else:
+        if sets is not None:  # the family sets: the greedy step is a kernel of its own, beside the family selection's
+            for other, name in ((pct, "the coding-position filter"), (stop_limit, "the stop-codon filter"), (splice_limit, "the splice-site filter")):
+                if other:
+                    refuse("--family-sets and %s are two kernels' predicates: one or the other" % name)
+            if KP is not None:
+                refuse("--family-sets: a family's guides are chosen one by one, not in pairs: not together with --select-pairs")
+            if integer(sets) is None or not 1 <= integer(sets) <= select.MAX_FAMILY_SET_STEPS:
+                refuse("--family-sets is a number of guides 1..%d, not %s" % (select.MAX_FAMILY_SET_STEPS, sets))
+            coding_args = dict(coding_args, family_sets=integer(sets))
         from . import families
         if spec is None:
             refuse("--families tells the hits of --specificity inside a gene's family from those outside it: give --specificity too")
@@ -883,7 +903,9 @@ def select_request(args, spec, world=1):
             refuse("--select-pairs: " + str(e))
     return dict(params=params, output=getattr(args, "select_output", None) or (args.o + ".selected.csv"),
                 only=bool(getattr(args, "select_only", False)), limits=dict(limits, **repair_args, **coding_args), repair_scores=with_scores,
-                coding=with_coding, base_edit=with_edit, splice_edit=with_splice, families=family_pairs, pairs=pairs, pairs_output=getattr(args, "pairs_output", None) or (args.o + ".pairs.csv"))
+                coding=with_coding, base_edit=with_edit, splice_edit=with_splice, families=family_pairs, pairs=pairs, pairs_output=getattr(args, "pairs_output", None) or (args.o + ".pairs.csv"),
+                family_sets=integer(sets) if sets is not None else None,
+                family_sets_output=getattr(args, "family_sets_output", None) or (args.o + ".family_sets.csv"))
 
 
 def properties_request(args, world=1):
@@ -906,6 +928,26 @@ def properties_request(args, world=1):
     return True
 
 
+def _table_fields(sel_rows, names, strings, all_hits, guide_len, annotation):
+    """Per row of sel_rows (its contig, strand and index fields name a table row) the main table's own fields for that row as
+    rows.ContigRows builds them, without crispr_id."""
+    fields = [None] * sel_rows.size
+    for c in np.unique(sel_rows["contig"]).tolist():
+        mine = np.flatnonzero(sel_rows["contig"] == c)
+        minus = sel_rows["strand"][mine] == b"-"
+        mine = np.concatenate([mine[~minus], mine[minus]])  # ('+' rows first, as ContigRows holds a contig's rows)
+        n_plus = int((~minus).sum())
+        index = sel_rows["index"][mine]
+        mini = hitcols.take(all_hits[c], index[:n_plus], index[n_plus:])
+        feats = None
+        if annotation is not None:
+            feats = (annotation.strings, hitcols.both(mini, "feat"))
+        block = rows.ContigRows(names[c], bytes(strings[c]).decode("latin-1"), mini, guide_len, features=feats)
+        for k, at in enumerate(mine.tolist()):
+            fields[at] = block.row(k, "")[1:]
+    return fields
+
+
 def write_selection(path, selection, names, strings, all_hits, guide_len, offtarget, spec_M, annotation, properties=False,
                     repair_scores=False, coding=False, base_edit=False, splice_edit=False, families=None):
     """The selection file: a header, then per chosen row gene, rank (1-based), passing and the main table's own fields
@@ -922,20 +964,7 @@ def write_selection(path, selection, names, strings, all_hits, guide_len, offtar
     from . import coding as cod
     from . import repair
     sel_rows = selection.rows
-    fields = [None] * sel_rows.size
-    for c in np.unique(sel_rows["contig"]).tolist():
-        mine = np.flatnonzero(sel_rows["contig"] == c)
-        minus = sel_rows["strand"][mine] == b"-"
-        mine = np.concatenate([mine[~minus], mine[minus]])  # ('+' rows first, as ContigRows holds a contig's rows)
-        n_plus = int((~minus).sum())
-        index = sel_rows["index"][mine]
-        mini = hitcols.take(all_hits[c], index[:n_plus], index[n_plus:])
-        feats = None
-        if annotation is not None:
-            feats = (annotation.strings, hitcols.both(mini, "feat"))
-        block = rows.ContigRows(names[c], bytes(strings[c]).decode("latin-1"), mini, guide_len, features=feats)
-        for k, at in enumerate(mine.tolist()):
-            fields[at] = block.row(k, "")[1:]
+    fields = _table_fields(sel_rows, names, strings, all_hits, guide_len, annotation)
     with open(path, "w", newline="") as f:
         w = csv.writer(f)
         w.writerow(["gene", "rank", "passing"] + rows.HEADER[1:] + rows.extra_header(offtarget, spec_M, properties)
@@ -971,6 +1000,43 @@ def family_fields(table, selection, at):
     return (table.family_name(g), int(selection.family_size[at]), int(selection.members_hit[at]), ";".join(selection.members[at]),
             int(selection.outside_mm0[at]), "%.6f" % (hs / float(1 << 30)) if scored else "",
             "%.6f" % float(specificity(np.uint64(hs))) if scored else "")
+
+
+FAMILY_SET_HEADER = ["family", "family_size", "step", "members_new", "members_covered", "complete", "new_members", "gene"]
+FAMILY_SET_TAIL = ["outside_mm0", "outside_hit_sum", "outside_specificity"]
+
+
+def write_family_sets(path, selection, table, names, strings, all_hits, guide_len, offtarget, spec_M, annotation, properties=False):
+    """The family-sets file (--family-sets): one row per pick, families in table order and steps ascending; families without
+    a pick are left out.  FAMILY_SET_HEADER -- new_members: the labels of the members the pick covers first, ;-joined, GFF
+    order; complete: 1 on every row of a family whose set covers all its members --, then the main table's own fields for the
+    row as write_selection builds them, then FAMILY_SET_TAIL: what the guide hits outside the family, for the gene it was
+    picked for.  Returns (families, complete, incomplete, without a passing guide)."""
+    import csv
+    from .search import specificity
+    picks = selection.family_sets
+    fields = _table_fields(picks, names, strings, all_hits, guide_len, annotation)
+    mm0, hit_sum = selection.family_sets_stats["outside_mm0"], selection.family_sets_stats["outside_hit_sum"]
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(FAMILY_SET_HEADER + rows.HEADER[1:] + rows.extra_header(offtarget, spec_M, properties) + FAMILY_SET_TAIL)
+        before = {}
+        for at, (p, rest) in enumerate(zip(picks, fields)):
+            fam = int(p["family"])
+            covered = int(p["covered"])
+            new = covered & ~before.get(fam, 0)
+            before[fam] = covered
+            members = table.members(fam).tolist()
+            hs = int(hit_sum[at])
+            scored = hs != 0xFFFFFFFFFFFFFFFF
+            w.writerow((table.names[fam], int(table.size[fam]), int(p["step"]), int(p["gain"]), bin(covered).count("1"),
+                        int(bool(selection.family_complete[fam])), ";".join(table.labels[m] for j, m in enumerate(members) if new >> j & 1),
+                        selection.labels[int(p["gene"])]) + tuple(rest)
+                       + (int(mm0[at]), "%.6f" % (hs / float(1 << 30)) if scored else "", "%.6f" % float(specificity(np.uint64(hs))) if scored else ""))
+    n = len(table.names)
+    picked = set(picks["family"].tolist())
+    complete = int(np.count_nonzero(selection.family_complete))
+    return n, complete, len(picked) - complete, n - len(picked)
 
 
 PAIR_HEADER = ["gene", "rank", "qualifying_pairs", "deletion_length", "in_frame", "chromosome"]
@@ -1297,6 +1363,15 @@ def run(args, backend=None, out=sys.stdout, group=None):
                         families=selecting["limits"].get("families"))
         stages["select"] = dict(selection.stats, write_s=time.perf_counter() - t_select, genes=len(selection.labels),
                                 rows_selected=int(selection.rows.size), k=selecting["params"].k)
+        if selecting["family_sets"] is not None:
+            t_sets = time.perf_counter()
+            counts = write_family_sets(selecting["family_sets_output"], selection, selecting["limits"]["families"], names, strings, all_hits,
+                                       args.l, offtarget, None if spec is None else spec["max_mm"], request.annotation if annotating else None,
+                                       properties=with_properties)
+            print("cropsr_amd: --family-sets %d: %d families, %d complete, %d incomplete, %d without a passing guide"
+                  % ((selecting["family_sets"],) + counts), file=sys.stderr)
+            stages["family_sets"] = dict({k: v for k, v in selection.family_sets_stats.items() if not k.startswith("outside_")},
+                                         write_s=time.perf_counter() - t_sets, picks=int(selection.family_sets.size))
         if selecting["pairs"] is not None:
             t_pairs = time.perf_counter()
             write_pairs(selecting["pairs_output"], selection, names, strings, all_hits, args.l, repair_scores=selecting["repair_scores"])

@@ -14,6 +14,7 @@
 #include "crp_select_coding.h"
 #include "crp_select_edit.h"
 #include "crp_select_family.h"
+#include "crp_select_family_set.h"
 #include "crp_search_family.h"
 #include "crp_select_splice.h"
 
@@ -88,6 +89,19 @@ struct crp_select {
     unsigned long long *d_family_eval_sum = nullptr;
     uint64_t family_eval_sum_cap = 0;
     double family_stats[2] = {};
+    // family sets: per gene its member bit, and the plan of crp_select_family_step -- the items of
+    // the family genes, their proposals, the family -> item list -- with what it was built for
+    uint32_t *d_gene_member = nullptr;
+    uint64_t gene_member_cap = 0;
+    bool have_members = false, set_plan_valid = false;
+    crp::SelectItem *d_set_items = nullptr;
+    crp::FamilyProposal *d_set_prop = nullptr, *d_set_best = nullptr;
+    uint32_t *d_set_start = nullptr, *d_set_slots = nullptr;
+    unsigned long long *d_set_covered = nullptr;
+    uint64_t set_cap[6] = {};
+    uint64_t set_items = 0, set_rows = 0, set_families = 0, set_plan_slice = 0, set_plan_hits[2] = {0, 0};
+    crp_select_params set_plan_params = {};
+    double set_stats[6] = {};
 };
 
 namespace {
@@ -256,7 +270,8 @@ int crp_select_destroy(crp_select *s)
                     s->d_pair_merge, s->d_pair_evals, s->pair_part.kmin, s->pair_part.kmax, s->pair_part.tie, s->pair_part.a, s->pair_part.b,
                     s->pair_part.n_pass, s->pair_part.n_pairs, s->pair_res.n_pass, s->pair_res.n_pairs, s->pair_res.pairs,
                     s->d_cod[0], s->d_cod[1], s->d_cod[2], s->d_cod[3], s->d_cod[4], s->d_cod[5], s->d_eval[0], s->d_eval[1], s->d_eval[2],
-                    s->d_eval[3], s->d_gene_family, s->d_family_size, s->d_family_eval_sum};
+                    s->d_eval[3], s->d_gene_family, s->d_family_size, s->d_family_eval_sum, s->d_gene_member, s->d_set_items, s->d_set_prop,
+                    s->d_set_best, s->d_set_start, s->d_set_slots, s->d_set_covered};
     for (void *p : bufs) (void)hipFree(p);
     for (hipEvent_t e : s->ev)
         if (e) (void)hipEventDestroy(e);
@@ -284,6 +299,7 @@ int crp_select_set_limits(crp_select *s, uint64_t slice_rows)
     if (!s) return CRP_ERR_INVALID;
     if (slice_rows && (slice_rows < CRP_SELECT_MIN_SLICE_ROWS || slice_rows > 0x40000000ull)) return CRP_ERR_INVALID;
     s->slice_rows = slice_rows ? slice_rows : CRP_SELECT_DEFAULT_SLICE_ROWS;
+    s->set_plan_valid = false;
     return CRP_OK;
 }
 
@@ -788,6 +804,8 @@ int crp_select_set_family(crp_select *s, const uint32_t *gene_family, const uint
     if (!s) return CRP_ERR_INVALID;
     crp_ctx *ctx = s->ctx;
     s->have_family = false;
+    s->have_members = false;  // (the member bits belong to the families: section 24)
+    s->set_plan_valid = false;
     if (!gene_family && !family_size && !n_genes) return CRP_OK;
     if (!gene_family || !family_size) return CRP_ERR_INVALID;
     if (n_genes != s->n_genes)
@@ -864,6 +882,192 @@ int crp_select_family_stats(const crp_select *s, double *out, int n)
 {
     if (!s || (n && !out) || n < 0 || n > 2) return CRP_ERR_INVALID;
     for (int k = 0; k < n; ++k) out[k] = s->family_stats[k];
+    return CRP_OK;
+}
+
+/* ---- family sets ---- */
+
+int crp_select_set_family_members(crp_select *s, const uint32_t *gene_member, uint64_t n_genes)
+{
+    if (!s) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    const std::string who = "crp_select_set_family_members";
+    s->have_members = false;
+    s->set_plan_valid = false;
+    if (!gene_member && !n_genes) return CRP_OK;
+    if (!gene_member) return CRP_ERR_INVALID;
+    if (!s->have_family) return fail(ctx, CRP_ERR_STATE, who + ": the handle has no families (crp_select_set_family)");
+    if (n_genes != s->n_genes)
+        return fail(ctx, CRP_ERR_INVALID, who + ": " + std::to_string(n_genes) + " genes for a handle of " + std::to_string(s->n_genes));
+    for (uint64_t g = 0; g < n_genes; ++g)
+        if (gene_member[g] >= 64u)
+            return fail(ctx, CRP_ERR_INVALID, who + ": gene " + std::to_string(g) + " is member " + std::to_string(gene_member[g]) +
+                                                  " of its family (a family has at most 64)");
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_gene_member), &s->gene_member_cap, n_genes, sizeof(uint32_t));
+    if (rc == CRP_OK && n_genes) rc = crp::staged_h2d(ctx, s->d_gene_member, gene_member, n_genes * sizeof(uint32_t));
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s->have_members = true;
+    return CRP_OK;
+}
+
+namespace {
+
+// The plan of crp_select_family_step: the bounds kernel's runs of the genes that have a family, cut at slice_rows as the
+// selection's items are, and per family the list of its items (CSR).  Built once per handle, tables and parameter set.
+int build_set_plan(crp_select *s, const crp_select_params *p, uint64_t n_families, const std::string &who)
+{
+    crp_ctx *ctx = s->ctx;
+    crp_arena *a = s->arena;
+    const uint64_t G = s->n_genes;
+    const uint32_t n_plus = (uint32_t)a->n_hits[0], n_minus = (uint32_t)a->n_hits[1];
+    std::vector<uint4> bounds;
+    std::vector<uint32_t> family, start, slots;
+    std::vector<crp::SelectItem> items;
+    uint64_t rows_covered = 0;
+    try {
+        bounds.resize(G);
+        family.resize(G);
+        start.assign(n_families + 1, 0u);
+        if (G) {
+            CRP_HIP(ctx, crp::launch_select_bounds(ctx->stream, a->d_pos[0], n_plus, a->d_pos[1], n_minus, s->d_lo, s->d_hi, (uint32_t)G, s->d_bounds));
+            int rc = crp::staged_d2h(ctx, bounds.data(), s->d_bounds, G * sizeof(uint4));
+            if (rc == CRP_OK) rc = crp::staged_d2h(ctx, family.data(), s->d_gene_family, G * sizeof(uint32_t));
+            if (rc != CRP_OK) return rc;
+            CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        }
+        for (uint64_t g = 0; g < G; ++g) {
+            if (family[g] == crp::SELECT_NONE) continue;
+            if (family[g] >= n_families)
+                return fail(ctx, CRP_ERR_INVALID, who + ": gene " + std::to_string(g) + " has family " + std::to_string(family[g]) + " of " +
+                                                      std::to_string(n_families));
+            const uint4 b = bounds[g];
+            if (b.x > b.y || b.y > n_plus || b.z > b.w || b.w > n_minus)
+                return fail(ctx, CRP_ERR_HIP, who + ": the bounds of gene " + std::to_string(g) + " lie outside the tables");
+            const uint64_t np = b.y - b.x, nm = b.w - b.z, total = np + nm;
+            if (!total) continue;  // (no row, no candidate)
+            rows_covered += total;
+            const uint64_t pieces = (total + s->slice_rows - 1) / s->slice_rows;
+            if (items.size() + pieces > 0xfffffff0ull) return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": more than 2^32 work items (raise slice_rows)");
+            for (uint64_t c = 0; c < pieces; ++c) {
+                // rows [r0, r1) of the gene's concatenated runs
+                const uint64_t r0 = c * s->slice_rows, r1 = std::min(total, r0 + s->slice_rows);
+                const uint64_t p0 = std::min(r0, np), p1 = std::min(r1, np);
+                const uint64_t m0 = std::max(r0, np) - np, m1 = std::max(r1, np) - np;
+                crp::SelectItem it;
+                it.gene = (uint32_t)g;
+                it.slot = (uint32_t)items.size();
+                it.first[0] = b.x + (uint32_t)p0;
+                it.rows[0] = (uint32_t)(p1 - p0);
+                it.first[1] = b.z + (uint32_t)m0;
+                it.rows[1] = (uint32_t)(m1 - m0);
+                items.push_back(it);
+                ++start[family[g] + 1];
+            }
+        }
+        for (uint64_t f = 0; f < n_families; ++f) start[f + 1] += start[f];
+        slots.resize(items.size());
+        std::vector<uint32_t> at(start.begin(), start.end() - 1);
+        for (uint64_t i = 0; i < items.size(); ++i) slots[at[family[items[i].gene]]++] = (uint32_t)i;
+    } catch (const std::bad_alloc &) {
+        return CRP_ERR_NOMEM;
+    }
+    int rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_set_items), &s->set_cap[0], items.size(), sizeof(crp::SelectItem));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_set_prop), &s->set_cap[1], items.size(), sizeof(crp::FamilyProposal));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_set_best), &s->set_cap[2], n_families, sizeof(crp::FamilyProposal));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_set_start), &s->set_cap[3], n_families + 1, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_set_slots), &s->set_cap[4], items.size(), sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_set_covered), &s->set_cap[5], n_families, sizeof(uint64_t));
+    if (rc == CRP_OK && !items.empty()) rc = crp::staged_h2d(ctx, s->d_set_items, items.data(), items.size() * sizeof(crp::SelectItem));
+    if (rc == CRP_OK && !items.empty()) rc = crp::staged_h2d(ctx, s->d_set_slots, slots.data(), slots.size() * sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::staged_h2d(ctx, s->d_set_start, start.data(), start.size() * sizeof(uint32_t));
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s->set_items = items.size();
+    s->set_rows = rows_covered;
+    s->set_families = n_families;
+    s->set_plan_slice = s->slice_rows;
+    s->set_plan_hits[0] = a->n_hits[0];
+    s->set_plan_hits[1] = a->n_hits[1];
+    s->set_plan_params = *p;
+    s->set_plan_valid = true;
+    s->set_stats[5] += 1;
+    return CRP_OK;
+}
+
+bool same_params(const crp_select_params &a, const crp_select_params &b)
+{
+    return a.min_score == b.min_score && a.max_hit_sum == b.max_hit_sum && a.max_mm0 == b.max_mm0 && a.k == b.k && a.require_cds == b.require_cds;
+}
+
+}  // namespace
+
+int crp_select_family_step(crp_select *s, const crp_select_params *p, crp_search_self *self, const uint64_t *covered, uint64_t n_families,
+                           crp_family_step_best *best)
+{
+    crp::Range roctx_range("crp: family set step");
+    if (!s || !p || (n_families && (!covered || !best)) || n_families > 0x7fffffffull) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    crp_arena *a = s->arena;
+    const std::string who = "crp_select_family_step";
+    if (s->have_coding_limits || s->have_edit_limits || s->have_splice_limits)
+        return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": the family step and coding, edit or splice limits are different kernels' predicates: "
+                                                    "clear them (one kernel per predicate)");
+    crp::SelfJoined joined = {};
+    int rc = check_run(s, p, self, &joined, who.c_str());
+    if (rc != CRP_OK) return rc;
+    crp::SelectFamily family = {};
+    rc = family_columns(s, self, who.c_str(), &family);
+    if (rc != CRP_OK) return rc;
+    if (!s->have_members) return fail(ctx, CRP_ERR_STATE, who + ": the handle has no member bits (crp_select_set_family_members)");
+    s->set_stats[0] = s->set_stats[1] = 0;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    if (!s->set_plan_valid || s->set_families != n_families || s->set_plan_slice != s->slice_rows || s->set_plan_hits[0] != a->n_hits[0] ||
+        s->set_plan_hits[1] != a->n_hits[1] || !same_params(s->set_plan_params, *p)) {
+        s->set_plan_valid = false;
+        rc = build_set_plan(s, p, n_families, who);
+        if (rc != CRP_OK) return rc;
+    }
+    s->set_stats[2] = (double)s->set_items;
+    s->set_stats[3] = (double)s->set_rows;
+    // the selection's columns (crp_select_stats) and, per row, site_family, fam_cover, fam_counts[0] and fam_sum
+    s->set_stats[4] = 24.0 + (p->require_cds ? 4.0 : 0.0) + (s->have_prop_limits ? 4.0 : 0.0) + (s->have_repair_limits ? 8.0 : 0.0) + 24.0;
+    if (!n_families) return CRP_OK;
+    rc = crp::staged_h2d(ctx, s->d_set_covered, covered, n_families * sizeof(uint64_t));
+    if (rc != CRP_OK) return rc;
+    crp::SelectTable tab[2];
+    crp::SelectPredicate pred;
+    fill_predicate(s, p, true, joined, 1, tab, &pred);
+    // without family limits: bounds that every row meets
+    const crp::FamilyLimits lim = s->have_family_limits
+                                      ? crp::FamilyLimits{s->family_limits.max_hit_sum_outside, s->family_limits.max_mm0_outside, s->family_limits.min_members}
+                                      : crp::FamilyLimits{~0ull, 0xFFFFFFFFu, 0u};
+    // the bounded-launch rule: at most 2^20 items a launch
+    CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    for (uint64_t first = 0; first < s->set_items; first += crp::SELECT_MAX_ITEMS) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(crp::SELECT_MAX_ITEMS, s->set_items - first);
+        CRP_HIP(ctx, crp::launch_family_set_step(ctx->stream, tab[0], tab[1], pred, family, lim, s->d_gene_member, s->d_set_covered, s->d_set_items + first,
+                                                 n, s->d_set_prop + first));
+    }
+    CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s->set_stats[0] = elapsed(s->ev[0], s->ev[1]);
+    CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    CRP_HIP(ctx, crp::launch_family_set_pick(ctx->stream, s->d_set_prop, s->d_set_start, s->d_set_slots, (uint32_t)n_families, s->d_set_best));
+    CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+    static_assert(sizeof(crp_family_step_best) == sizeof(crp::FamilyProposal), "one record");
+    rc = crp::staged_d2h(ctx, best, s->d_set_best, n_families * sizeof(crp::FamilyProposal));
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s->set_stats[1] = elapsed(s->ev[0], s->ev[1]);
+    return CRP_OK;
+}
+
+int crp_select_family_step_stats(const crp_select *s, double *out, int n)
+{
+    if (!s || (n && !out) || n < 0 || n > 6) return CRP_ERR_INVALID;
+    for (int k = 0; k < n; ++k) out[k] = s->set_stats[k];
     return CRP_OK;
 }
 

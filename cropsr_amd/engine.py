@@ -816,6 +816,8 @@ class Genome:
         if request.pairs is not None:
             out.pairs, out.n_pairs, out.pairs_repair = sel.assemble_pairs(len(labels), request.pairs.k, parts)
             out.pairs_stats = pair_stats
+        if getattr(request, "family_sets", None) is not None:  # after the per-gene selection, while the self-search handles are open
+            out.family_sets, out.family_complete, out.family_sets_stats = sel.family_sets(self, request, handle_of, hits, flags)
         return out
 
     def scan_score(self, guide_len=20, want_pre=False, offtarget=False, seeds_from_scan=True, annotation=None, specificity=None,

@@ -73,6 +73,10 @@ of g's family (1 for none).  Family limits are ANDed onto the predicate after th
 outside_hit_sum <= max_hit_sum_for(min_specificity_outside), members_hit >= min_members ("all": family_size).  max_perfect
 and min_specificity keep their meaning on the full counts.  Not together with coding, edit or splice limits or pairs.
 
+Family sets (family_sets.py has the definition; csrc/crp_select_family_set.hip): with family_sets = S
+the scan also chooses, per family, at most S passing rows of its member genes that together cover as many members as
+possible, greedily: each step takes the candidate with the largest gain over what is covered so far.
+
 This module lays the genes out per arena, converts a wanted specificity into the integer bound the kernel compares,
 drives crp_select_* and turns the per-arena results into one table over the genes of the GFF.
 """
@@ -93,6 +97,11 @@ PAIR_DTYPE = np.dtype([("gene", "<u4"), ("rank", "<u4"), ("contig", "<u4"), ("po
                        ("deletion_length", "<u4")])
 ROW_DTYPE = np.dtype([("gene", "<u4"), ("rank", "<u4"), ("contig", "<u4"), ("position", "<i8"), ("strand", "S1"), ("score", "<f8"),
                       ("index", "<u4")])
+# a pick of a family set (family_sets): ROW_DTYPE's fields with family and step for gene's rank, then the pick's gain, its
+# cover word c and the family's covered word after the step
+FAMILY_SET_DTYPE = np.dtype([("family", "<u4"), ("step", "<u4"), ("gene", "<u4"), ("contig", "<u4"), ("position", "<i8"), ("strand", "S1"),
+                             ("score", "<f8"), ("index", "<u4"), ("gain", "<u4"), ("cover", "<u8"), ("covered", "<u8")])
+MAX_FAMILY_SET_STEPS = nat.FAMILY_SET_MAX_STEPS
 
 
 def max_hit_sum_for(S):
@@ -223,13 +232,27 @@ class Request:
     family_size, members_hit, members, outside_mm0, outside_hit_sum and fam_cover of its rows, for the gene each was selected
     for.  min_members / max_perfect_outside / min_specificity_outside (FamilyLimits) are limits: a row passes only if they
     hold for the gene it is selected for.  They need families, and are refused with coding, edit or splice limits and with
-    pairs: one kernel per predicate."""
+    pairs: one kernel per predicate.
+    family_sets (S, 1..64): after the per-gene selection the scan also chooses, per family, at most S guides that together
+    cut as many members as possible (family_sets(); Selection.family_sets, Selection.family_complete).  Needs families, and
+    is refused with coding, edit or splice limits and with pairs."""
 
     def __init__(self, params, annotation, slice_rows=None, gc_min=None, gc_max=None, max_run=None, max_t_run=None, max_stem=None,
                  repair_flank=None, min_mh=None, min_oof=None, pairs=None, pair_slice_rows=None, coding=False, coding_limits=None,
                  edit_window=None, edit_limits=None, editor=None, splice_limits=None, edit=None, families=None, family_cover_mm=0,
-                 min_members=None, max_perfect_outside=None, min_specificity_outside=None):
+                 min_members=None, max_perfect_outside=None, min_specificity_outside=None, family_sets=None):
         self.families, self.family_cover_mm = families, int(family_cover_mm)
+        self.family_sets = None
+        if family_sets is not None:
+            if families is None:
+                raise ValueError("family_sets needs a family table (families=)")
+            if coding_limits is not None or edit_limits is not None or splice_limits is not None:
+                raise ValueError("family sets and coding, edit or splice limits are different kernels' predicates: one or the other")
+            if pairs is not None:
+                raise ValueError("family sets do not combine with the pair selection: one or the other")
+            if not isinstance(family_sets, (int, np.integer)) or not 1 <= int(family_sets) <= MAX_FAMILY_SET_STEPS:
+                raise ValueError("family_sets is a number of guides 1..%d, not %r" % (MAX_FAMILY_SET_STEPS, family_sets))
+            self.family_sets = int(family_sets)
         self.family_limits = None
         if any(v is not None for v in (min_members, max_perfect_outside, min_specificity_outside)):
             if families is None:
@@ -409,6 +432,37 @@ class ArenaSelect:
         nat.check(nat.lib().crp_select_family_stats(self._h, out.ctypes.data_as(nat.f64p), 2), "crp_select_family_stats", self._ctx)
         return dict(zip(("family_select_ms", "family_eval_ms"), (float(v) for v in out)))
 
+    def set_family_members(self, gene_member):
+        """Per gene of this handle its bit in its family's cover word (FamilyTable.gene_member); None clears.  After set_family."""
+        if gene_member is None:
+            nat.check(nat.lib().crp_select_set_family_members(self._h, None, 0), "crp_select_set_family_members", self._ctx)
+            return
+        m = np.ascontiguousarray(gene_member, dtype=np.uint32)
+        if m.ndim != 1:
+            raise ValueError("gene_member must be a 1-d array")
+        pad = m if m.size else np.zeros(1, np.uint32)  # (a handle without genes still gets a pointer)
+        nat.check(nat.lib().crp_select_set_family_members(self._h, pad.ctypes.data_as(nat.u32p), m.size), "crp_select_set_family_members",
+                  self._ctx)
+
+    def family_step(self, params, self_search, covered):
+        """One greedy step in this arena: per family id the best candidate against covered (uint64 per family), as records of
+        nat.FAMILY_STEP_BEST_DTYPE; gain 0: none."""
+        covered = np.ascontiguousarray(covered, dtype=np.uint64)
+        if covered.ndim != 1:
+            raise ValueError("covered must be a 1-d array, one word per family")
+        best = np.zeros(max(1, covered.size), dtype=nat.FAMILY_STEP_BEST_DTYPE)
+        pad = covered if covered.size else np.zeros(1, np.uint64)
+        p = params.native()
+        nat.check(nat.lib().crp_select_family_step(self._h, ctypes.byref(p), self_search._h if self_search is not None else None,
+                                                   pad.ctypes.data_as(nat.u64p), covered.size, best.ctypes.data_as(ctypes.c_void_p)),
+                  "crp_select_family_step", self._ctx)
+        return best[:covered.size]
+
+    def family_step_stats(self):
+        out = np.zeros(6, dtype=np.float64)
+        nat.check(nat.lib().crp_select_family_step_stats(self._h, out.ctypes.data_as(nat.f64p), 6), "crp_select_family_step_stats", self._ctx)
+        return dict(zip(("step_ms", "pick_ms", "items", "rows_in_runs", "bytes_per_row", "plan_builds"), (float(v) for v in out)))
+
     def coding_stats(self):
         out = np.zeros(3, dtype=np.float64)
         nat.check(nat.lib().crp_select_coding_stats(self._h, out.ctypes.data_as(nat.f64p), 3), "crp_select_coding_stats", self._ctx)
@@ -529,6 +583,10 @@ class Selection:
         # with gene families (families.py), for the gene each row was selected for: (n,) arrays, and members: per row the
         # labels of the family members the guide covers (the gene itself where the row's family is not the gene's)
         self.outside_mm0 = self.outside_hit_sum = self.members_hit = self.family_size = self.fam_cover = self.members = None
+        # with Request(family_sets=S): the picks (FAMILY_SET_DTYPE; families in table order, steps ascending), per family of the
+        # table whether its set covers every member, and the driver's stats
+        self.family_sets = self.family_complete = None
+        self.family_sets_stats = {}
 
     def of_gene(self, g):
         return self.rows[self.rows["gene"] == g]
@@ -717,6 +775,29 @@ def select_arena_pairs(sel, request, handle=None):
     return sel.fetch_pairs() + (sel.pairs_stats(),)
 
 
+def _set_row_limits(sel, request, flags=None):
+    """The terms of the predicate that do not depend on the gene, on an ArenaSelect: the CDS flags, the slices, the property
+    and the repair limits of a Request."""
+    if request.params.require_cds:
+        sel.set_flags(flags if flags is not None else request.annotation.annotation.cds_flags())
+    if request.slice_rows:
+        sel.set_limits(request.slice_rows)
+    if getattr(request, "property_limits", None) is not None:
+        sel.set_property_limits(request.property_limits)
+    if getattr(request, "repair_limits", None) is not None:
+        sel.set_repair_limits(request.repair_limits)
+
+
+def _set_families(sel, request, gene):
+    """The families of an ArenaSelect's layout rows (gene: layout row -> gene index) and the request's family limits."""
+    table = request.families
+    g = np.asarray(gene, dtype=np.int64)
+    gene_family = table.gene_family[g] if g.size else np.zeros(0, np.uint32)
+    size = np.array([table.family_size(int(x)) for x in g.tolist()], dtype=np.uint32)
+    sel.set_family(gene_family, size)
+    sel.set_family_limits(request.family_limits)
+
+
 def select_arena(genome, a, request, handle=None, flags=None, extras=None):
     """The selection of one arena of an engine.Genome whose tables are resident: (lo, hi, gene, n_in, n_pass, sel, stats),
     and with request.pairs one more element: (n_pass, n_pairs, pairs, pairs_stats) of the pair selection.  extras: a dict
@@ -730,14 +811,7 @@ def select_arena(genome, a, request, handle=None, flags=None, extras=None):
     lo, hi, gene = request.annotation.gene_layout(arena_layout(genome, a))
     sel = ArenaSelect(genome.arenas[a], lo, hi)
     try:
-        if request.params.require_cds:
-            sel.set_flags(flags if flags is not None else request.annotation.annotation.cds_flags())
-        if request.slice_rows:
-            sel.set_limits(request.slice_rows)
-        if getattr(request, "property_limits", None) is not None:
-            sel.set_property_limits(request.property_limits)
-        if getattr(request, "repair_limits", None) is not None:
-            sel.set_repair_limits(request.repair_limits)
+        _set_row_limits(sel, request, flags)
         model = None
         edit = getattr(request, "edit", False)
         splice = getattr(request, "splice", False)
@@ -752,11 +826,7 @@ def select_arena(genome, a, request, handle=None, flags=None, extras=None):
                 sel.set_splice_limits(request.splice_window, request.editor, request.splice_limits)
         table = getattr(request, "families", None)
         if table is not None:
-            g = np.asarray(gene, dtype=np.int64)
-            gene_family = table.gene_family[g] if g.size else np.zeros(0, np.uint32)
-            size = np.array([table.family_size(int(x)) for x in g.tolist()], dtype=np.uint32)
-            sel.set_family(gene_family, size)
-            sel.set_family_limits(request.family_limits)
+            _set_families(sel, request, gene)
         sel.run(request.params, handle)
         n_in, n_pass, picked = sel.fetch()
         stats = sel.stats()
@@ -805,6 +875,12 @@ def select_arena(genome, a, request, handle=None, flags=None, extras=None):
         return out
     finally:
         sel.close()
+
+
+def family_sets(genome, request, handle_of, hits, flags=None):
+    """The greedy family sets of a Request(family_sets=S): family_sets.py has the definition and the driver."""
+    from .family_sets import family_sets as run
+    return run(genome, request, handle_of, hits, flags)
 
 
 def sum_stats(total, one):

@@ -1138,6 +1138,38 @@ int crp_select_family_eval(crp_select *select, crp_search_self *self, const uint
  * crp_select_family_eval's kernel (HIP events).  n: how many to write (<= 2). */
 int crp_select_family_stats(const crp_select *select, double *out, int n);
 
+/* ---- family sets: the fewest guides that cut every member of a family (opt-in) ---------- */
+/* A CANDIDATE of family f is a pair (gene g of the handle with family f, table row r) where r is in g and passes for g
+ * exactly as crp_select_run counts n_pass for g with the handle's limits in force.  Its cover word is
+ *   c = (site_family[r] == f ? fam_cover[r] : 0) | 1 << member(g)
+ * and its gain against a word `covered` is popcount(c & ~covered).  One step picks, per family, the candidate of this
+ * arena with the largest gain; ties go to the higher score (its 64 bits, unsigned), then to the smaller cut << 1 | strand,
+ * then to the smaller gene row.  The greedy loop over the steps and the merge over the arenas are the caller's
+ * (cropsr_amd/select.py, family_sets). */
+#define CRP_FAMILY_SET_MAX_STEPS 64
+/* The member bit (0 .. 63) of every gene of the handle in its family's cover word (0 for a gene in no family).  Needs
+ * crp_select_set_family (CRP_ERR_STATE), which also clears the bits again; n_genes must be the handle's; NULL, 0 clears. */
+int crp_select_set_family_members(crp_select *select, const uint32_t *gene_member, uint64_t n_genes);
+/* gain 0: the family has no candidate in this arena that covers a new member (the other fields then mean nothing).  key:
+ * the score's bits; cover: c; tie: cut << 1 | strand; row: table row | strand << 31 (sel's packing); gene: the handle's row. */
+typedef struct crp_family_step_best {
+    uint64_t key, cover;
+    uint32_t gain, tie, row, gene;
+} crp_family_step_best;
+/* One step: best[f] for every family id f < n_families against covered[f] (host arrays).  params as crp_select_run takes
+ * them (k is not read).  The plan -- bounds, work items, the family -> item list -- is built by the first call and kept
+ * while the handle's families, slice_rows, the tables' sizes and params stay what they were: a later call launches the
+ * step kernel and the pick kernel and nothing else.  CRP_ERR_STATE with a crp_last_error text: no crp_select_set_family, no
+ * crp_select_set_family_members, no self-search handle with both joins on the current tables.  CRP_ERR_UNSUPPORTED: coding,
+ * edit or splice limits are set (one kernel per predicate).  CRP_ERR_INVALID: a handle of another arena, a min_score that
+ * is not a number, a gene whose family id is not below n_families. */
+int crp_select_family_step(crp_select *select, const crp_select_params *params, crp_search_self *self, const uint64_t *covered,
+                           uint64_t n_families, crp_family_step_best *best);
+/* Of the last crp_select_family_step: out[0] ms of its step launches, out[1] ms of its pick launch (HIP events), out[2] its
+ * work items, out[3] the table rows they cover, out[4] the bytes read per row; out[5] the plans built on this handle so far.
+ * n: how many to write (<= 6). */
+int crp_select_family_step_stats(const crp_select *select, double *out, int n);
+
 /* ---- options -------------------------------------------------------------- */
 /* CRP_OPT_TWO_PASS (value 0/1, default 0): with 0 crp_scan_score is ONE kernel launch; the
  * table offsets come from a chained scan across workgroups inside it (decoupled look-back
