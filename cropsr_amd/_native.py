@@ -48,6 +48,11 @@ class SelectRepairLimits(ctypes.Structure):
     _fields_ = [("min_mh", ctypes.c_uint32), ("min_oof_pct", ctypes.c_uint32)]
 
 
+class SelectVariantLimits(ctypes.Structure):
+    """crp_select_variant_limits (include/cropsr_hip.h): the bounds a selection puts on the variant counts."""
+    _fields_ = [("max_site", ctypes.c_uint32), ("max_guide", ctypes.c_uint32), ("max_seed", ctypes.c_uint32), ("max_pam", ctypes.c_uint32)]
+
+
 class SelectCodingLimits(ctypes.Structure):
     """crp_select_coding_limits (include/cropsr_hip.h): the bounds a selection puts on the coding position of the cut."""
     _fields_ = [("min_pct", ctypes.c_uint32), ("max_pct", ctypes.c_uint32), ("min_transcripts_pct", ctypes.c_uint32)]
@@ -233,6 +238,18 @@ SIGNATURES = {
     "crp_repair_scores": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, u64p, u64p]),
     "crp_repair_scores_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_select_set_repair_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "crp_variants_create": (ctypes.c_int, [ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint64, ctypes.c_int, voidpp]),
+    "crp_variants_add_bytes": (ctypes.c_int, [ctypes.c_void_p, u8p, ctypes.c_uint64]),
+    "crp_variants_finish": (ctypes.c_int, [ctypes.c_void_p]),
+    "crp_variants_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "crp_variants_error": (ctypes.c_char_p, [ctypes.c_void_p]),
+    "crp_variants_stats": (ctypes.c_int, [ctypes.c_void_p, u64p, ctypes.c_int]),
+    "crp_variants_chrom": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, voidpp, u64p]),
+    "crp_variants_track": (ctypes.c_int, [ctypes.c_void_p, u64p, ctypes.c_uint64, ctypes.c_int, u32p, u32p, ctypes.c_uint64, u64p]),
+    "crp_variant_set_track": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, ctypes.c_uint64]),
+    "crp_variant_counts": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, u32p, u32p]),
+    "crp_variant_counts_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
+    "crp_select_set_variant_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "crp_select_set_pair_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64]),
     "crp_select_run_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "crp_select_fetch_pairs": (ctypes.c_int, [ctypes.c_void_p, u32p, u64p, u32p]),

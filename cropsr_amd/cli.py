@@ -246,6 +246,22 @@ def build_parser():
     eng.add_argument("--select-min-mh", default=None, metavar="X",
                      help="with --select: only guides whose microhomology score is at least X (a decimal with at most one "
                           "fractional digit)")
+    eng.add_argument("--variants", default=None, metavar="FILE",
+                     help="with --select: a VCF (text or .gz) of the cultivar against this assembly; every selection-file row ends "
+                          "with var_site, var_guide, var_seed and var_pam, the variants that touch its target site, guide, seed and PAM")
+    eng.add_argument("--variants-samples", default=None, metavar="A,B",
+                     help="with --variants: only the ALT alleles that the GT of at least one of these samples holds")
+    eng.add_argument("--variants-pass-only", action="store_true", help="with --variants: only records whose FILTER is PASS or .")
+    eng.add_argument("--variant-seed", default=None, metavar="S",
+                     help="with --variants: the PAM-proximal letters of the guide that make the seed (1..-l, default 12)")
+    eng.add_argument("--select-max-variants", default=None, metavar="N",
+                     help="with --variants: only guides with at most N variants under guide + PAM")
+    eng.add_argument("--select-max-guide-variants", default=None, metavar="N",
+                     help="with --variants: only guides with at most N variants under the guide")
+    eng.add_argument("--select-max-seed-variants", default=None, metavar="N",
+                     help="with --variants: only guides with at most N variants under the seed")
+    eng.add_argument("--select-max-pam-variants", default=None, metavar="N",
+                     help="with --variants: only guides with at most N variants under the two fixed letters of the PAM")
     eng.add_argument("--bench-json", metavar="PATH", default=None,
                      help="write stage timings of this run (read, upload+scan, fetch, format+write) as one JSON object")
     return p
@@ -374,6 +390,7 @@ class EngineBackend:
         self.last_specificity = None  # --bench-json: the self-search handles' times of the last --specificity scan
         self.last_properties = None   # --bench-json: the property kernel's time and rows of the last scan that ran it
         self.last_repair = None       # --bench-json: the repair kernel's time, rows and flank of the last scan that ran it
+        self.last_variants = None     # --bench-json: the variant kernel's time, rows, seed and track size of the last scan that ran it
 
     def connect(self):
         """Collective over the group: create the RCCL communicator (transport "rccl")."""
@@ -447,6 +464,7 @@ class EngineBackend:
             self.last_specificity = getattr(hits.columns, "stats", None)  # (--bench-json)
             self.last_properties = genome.properties_stats
             self.last_repair = genome.repair_stats
+            self.last_variants = genome.variant_stats
         finally:
             genome.close()
         return out
@@ -908,6 +926,64 @@ def select_request(args, spec, world=1):
                 family_sets_output=getattr(args, "family_sets_output", None) or (args.o + ".family_sets.csv"))
 
 
+def variants_request(args, world=1):
+    """--variants and its options, checked like the other opt-in steps, before any side effect: None without it, else
+    dict(path, samples, pass_only, seed, limits -- the keywords of select.Request)."""
+    def refuse(msg):
+        sys.exit("cropsr_amd: --variants: " + msg)
+
+    limit_opts = (("--select-max-variants", "select_max_variants", "max_variants"),
+                  ("--select-max-guide-variants", "select_max_guide_variants", "max_guide_variants"),
+                  ("--select-max-seed-variants", "select_max_seed_variants", "max_seed_variants"),
+                  ("--select-max-pam-variants", "select_max_pam_variants", "max_pam_variants"))
+    given = [o for o, k, unset in [(o, k, None) for o, k, _ in limit_opts] + [("--variants-samples", "variants_samples", None),
+                                                                             ("--variants-pass-only", "variants_pass_only", False),
+                                                                             ("--variant-seed", "variant_seed", None)]
+             if getattr(args, k, unset) not in (unset, None)]
+    path = getattr(args, "variants", None)
+    if path is None:
+        if given:
+            sys.exit("cropsr_amd: %s belongs to --variants" % given[0])
+        return None
+    from . import variants
+
+    def integer(text):
+        t = str(text).strip()
+        return int(t) if t.isascii() and t.isdigit() else None
+
+    if not 1 <= args.l <= variants.MAX_GUIDE:
+        refuse("a guide of 1..%d letters has windows, not -l %d" % (variants.MAX_GUIDE, args.l))
+    seed = getattr(args, "variant_seed", None)
+    if seed is not None:
+        if integer(seed) is None or not 1 <= integer(seed) <= args.l:
+            refuse("--variant-seed is a number of letters 1..%d (-l), not %s" % (args.l, seed))
+        seed = integer(seed)
+    limits = {}
+    for opt, key, kw in limit_opts:
+        v = getattr(args, key, None)
+        if v is not None:
+            if integer(v) is None or integer(v) > 0xFFFFFFFF:
+                refuse("%s is a number of variants, not %s" % (opt, v))
+            limits[kw] = integer(v)
+    samples = getattr(args, "variants_samples", None)
+    if samples is not None:
+        samples = [t for t in str(samples).split(",")]
+        if not all(samples):
+            refuse("--variants-samples is a comma-separated list of sample names, not %r" % getattr(args, "variants_samples"))
+    if len(_device_list(args)) > 1:
+        refuse("the variant column is not gathered: one GPU, and --devices names %d" % len(_device_list(args)))
+    if getattr(args, "gpus", 1) > 1:
+        refuse("the variant column is not gathered: one GPU, drop --gpus %d" % args.gpus)
+    if world > 1:
+        refuse("the variant column is not gathered: one GPU, and a launcher started %d ranks" % world)
+    if getattr(args, "select", None) is None:
+        refuse("the counts are printed in the selection file and bound the selection: --variants belongs to --select")
+    import os
+    if not os.path.isfile(path):
+        refuse("no such file: %s" % path)
+    return dict(path=path, samples=samples, pass_only=bool(getattr(args, "variants_pass_only", False)), seed=seed, limits=limits)
+
+
 def properties_request(args, world=1):
     """--properties, checked like the other opt-in steps, before any side effect: True with it, False without."""
     if not getattr(args, "properties", False):
@@ -949,7 +1025,7 @@ def _table_fields(sel_rows, names, strings, all_hits, guide_len, annotation):
 
 
 def write_selection(path, selection, names, strings, all_hits, guide_len, offtarget, spec_M, annotation, properties=False,
-                    repair_scores=False, coding=False, base_edit=False, splice_edit=False, families=None):
+                    repair_scores=False, coding=False, base_edit=False, splice_edit=False, families=None, variants=False):
     """The selection file: a header, then per chosen row gene, rank (1-based), passing and the main table's own fields
     for that row as rows.ContigRows builds them, without crispr_id (those ids are random per run).  Genes in GFF order;
     genes with nothing selected are left out.  Python's csv module in the main table's dialect: the file is small.
@@ -958,8 +1034,10 @@ def write_selection(path, selection, names, strings, all_hits, guide_len, offtar
     base_edit: four more after those, edit_targets, stop_codons, stop_codon and stop_percent (baseedit.fields).
     splice_edit: four more after those, splice_targets, splice_sites, donor_percent and acceptor_percent (baseedit.splice_fields).
     families (families.FamilyTable): seven more after those, family, family_size, members_hit, members (the covered members'
-    labels, ;-joined, GFF order), outside_mm0, outside_hit_sum and outside_specificity (FAMILY_HEADER)."""
+    labels, ;-joined, GFF order), outside_mm0, outside_hit_sum and outside_specificity (FAMILY_HEADER).
+    variants: four more after everything else, var_site, var_guide, var_seed and var_pam (variants.fields) of selection.variants."""
     import csv
+    from . import variants as var
     from . import baseedit
     from . import coding as cod
     from . import repair
@@ -970,7 +1048,7 @@ def write_selection(path, selection, names, strings, all_hits, guide_len, offtar
         w.writerow(["gene", "rank", "passing"] + rows.HEADER[1:] + rows.extra_header(offtarget, spec_M, properties)
                    + (repair.HEADER if repair_scores else []) + (cod.HEADER if coding else [])
                    + (baseedit.HEADER if base_edit else []) + (baseedit.SPLICE_HEADER if splice_edit else [])
-                   + (FAMILY_HEADER if families is not None else []))
+                   + (FAMILY_HEADER if families is not None else []) + (var.HEADER if variants else []))
         for at, (r, rest) in enumerate(zip(sel_rows, fields)):
             more = repair.fields(repair.pack(selection.mh[at], selection.oof[at])) if repair_scores else ()
             if coding:
@@ -982,6 +1060,8 @@ def write_selection(path, selection, names, strings, all_hits, guide_len, offtar
                                                             selection.donor_offset[at], selection.acceptor_offset[at], selection.cds_length[at])
             if families is not None:
                 more = tuple(more) + family_fields(families, selection, at)
+            if variants:
+                more = tuple(more) + var.fields(selection.variants[at])
             w.writerow((selection.labels[int(r["gene"])], int(r["rank"]), int(selection.n_pass[int(r["gene"])])) + tuple(rest) + tuple(more))
 
 
@@ -1131,8 +1211,18 @@ def run(args, backend=None, out=sys.stdout, group=None):
     spec = specificity_request(args)  # (before any side effect, on every rank)
     selecting = select_request(args, spec, 1 if group is None else group.world)
     with_properties = properties_request(args, 1 if group is None else group.world)
+    varying = variants_request(args, 1 if group is None else group.world)
     finalize = getattr(args, "score_finalize", "gpu")
     stages = {}  # --bench-json
+    variant_set = None
+    if varying is not None:  # the VCF is read here, before any side effect: a malformed line or an unknown sample ends the run
+        from . import variants
+        t_vcf = time.perf_counter()
+        try:
+            variant_set = variants.VariantSet(varying["path"], samples=varying["samples"], pass_only=varying["pass_only"])
+        except (ValueError, OSError, EOFError) as e:
+            sys.exit("cropsr_amd: --variants: %s: %s" % (varying["path"], e))
+        stages["variants"] = dict(parse_s=time.perf_counter() - t_vcf, **variant_set.stats)
     own_group = group is None
     if own_group:
         group = _distributed()
@@ -1149,6 +1239,7 @@ def run(args, backend=None, out=sys.stdout, group=None):
         select_request(args, spec, group.world)
     if group is not None and group.world > 1:
         properties_request(args, group.world)
+        variants_request(args, group.world)
     one_gpu = spec is not None or selecting is not None or with_properties  # the opt-in steps that take the arena path on one device
 
     def make_backend():
@@ -1298,6 +1389,15 @@ def run(args, backend=None, out=sys.stdout, group=None):
         if family_table.n_unknown:
             print("cropsr_amd: --families: %d names of %s are no gene of %s" % (family_table.n_unknown, args.families, args.g), file=sys.stderr)
         selecting["limits"]["families"] = family_table
+    if varying is not None:
+        from . import variants
+        if request_err is not None:
+            raise request_err
+        unknown = [c for c in variant_set.chrom_index if c not in set(request.names)]
+        if unknown:
+            print("cropsr_amd: --variants: %d CHROMs of %s name no contig of %s" % (len(unknown), varying["path"], args.f), file=sys.stderr)
+        selecting["limits"].update(variants=variants.Request(variant_set, request.names, request.dec), variant_seed=varying["seed"],
+                                   **varying["limits"])
     select_only = selecting is not None and selecting["only"]
     if not select_only:
         rows.write_header(args.o, offtarget=offtarget, specificity=None if spec is None else spec["max_mm"],
@@ -1360,7 +1460,7 @@ def run(args, backend=None, out=sys.stdout, group=None):
         write_selection(selecting["output"], selection, names, strings, all_hits, args.l, offtarget, None if spec is None else spec["max_mm"],
                         request.annotation if annotating else None, properties=with_properties, repair_scores=selecting["repair_scores"],
                         coding=selecting["coding"], base_edit=selecting["base_edit"], splice_edit=selecting["splice_edit"],
-                        families=selecting["limits"].get("families"))
+                        families=selecting["limits"].get("families"), variants=varying is not None)
         stages["select"] = dict(selection.stats, write_s=time.perf_counter() - t_select, genes=len(selection.labels),
                                 rows_selected=int(selection.rows.size), k=selecting["params"].k)
         if selecting["family_sets"] is not None:
@@ -1489,6 +1589,8 @@ def run(args, backend=None, out=sys.stdout, group=None):
         stages["properties"] = backend.last_properties
     if getattr(backend, "last_repair", None):  # --repair-scores / --select-min-oof / --select-min-mh: the repair kernel's time and rows
         stages["repair"] = backend.last_repair
+    if getattr(backend, "last_variants", None):  # --variants: the VCF's parse time and counts, the track's size, the kernel's time and rows
+        stages["variants"] = dict(stages.get("variants", {}), **backend.last_variants)
     if getattr(backend, "last_specificity", None):  # --specificity: the handles' kernel times, the join's among them
         stages["specificity"] = backend.last_specificity
     if getattr(backend, "last_gather", None):  # one process over several devices (--devices): the node's gatherv, in numbers
@@ -1533,6 +1635,7 @@ def main(argv=None):
                  "same result: give one of them")
     select_request(args, specificity_request(args))  # (--gpus N: refused here, before any rank is started)
     properties_request(args)
+    variants_request(args)
     if launch.wanted(getattr(args, "gpus", 1)):
         # no launcher in the environment: this process (which never touches the GPU) starts the ranks as fresh
         # children of the same command line and leaves with their status (cropsr_amd/launch.py)

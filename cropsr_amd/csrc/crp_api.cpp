@@ -462,6 +462,14 @@ int crp_arena_destroy(crp_arena *a)
     (void)hipFree(a->d_repair[1]);
     for (hipEvent_t e : a->ev_repair)
         if (e) (void)hipEventDestroy(e);
+    (void)hipFree(a->d_var_starts);
+    (void)hipFree(a->d_var_ends1);
+    for (int s = 0; s < 2; ++s) {
+        (void)hipFree(a->d_var_bucket[s]);
+        (void)hipFree(a->d_variants[s]);
+    }
+    for (hipEvent_t e : a->ev_variants)
+        if (e) (void)hipEventDestroy(e);
     delete a;
     return CRP_OK;
 }
@@ -894,6 +902,7 @@ int arena_reset(crp_arena *a)
     a->n_contigs = a->n_chars = 0;
     a->sealed = false;
     a->have_hits = a->have_pre = a->have_raw = a->have_feat = a->have_props = a->have_repair = a->have_track = false;
+    a->have_variants = a->have_var_track = false;
     a->n_hits[0] = a->n_hits[1] = 0;
     a->scan_pending = 0;
     a->ot_epoch = 0;
@@ -925,6 +934,7 @@ int scan_begin(crp_arena *a, int guide_len, int flags)
     a->have_feat = false;
     a->have_props = false;
     a->have_repair = false;
+    a->have_variants = false;
     a->scan_pending = 0;
     a->pend_guide_len = guide_len;
     a->pend_flags = flags;

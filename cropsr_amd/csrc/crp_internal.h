@@ -130,6 +130,19 @@ struct crp_arena {
     hipEvent_t ev_repair[2] = {nullptr, nullptr};
     double repair_ms = 0;  // the kernel of the last crp_repair_scores (HIP events)
     int repair_flank = 0;  // its flank
+    // variant counts (crp_variants.hip): the arena's variant track -- starts and ends + 1, each ascending on its own, with a
+    // bucket index each -- and one packed word per hit of the last crp_variant_counts
+    uint32_t *d_var_starts = nullptr, *d_var_ends1 = nullptr;
+    uint64_t var_cap = 0, n_var = 0;
+    uint32_t *d_var_bucket[2] = {nullptr, nullptr};  // values below every bucket of 2 048 arena positions: [0] starts, [1] ends1
+    uint64_t var_bucket_cap[2] = {0, 0}, n_var_entries = 0;
+    bool have_var_track = false;
+    uint32_t *d_variants[2] = {nullptr, nullptr};  // same order as the hit tables
+    uint64_t variants_cap[2] = {0, 0};
+    bool have_variants = false;  // d_variants belongs to the current tables (cleared by the next scan)
+    hipEvent_t ev_variants[2] = {nullptr, nullptr};
+    double variants_ms = 0;  // the kernel of the last crp_variant_counts (HIP events)
+    int variants_seed = 0;   // its seed length
 };
 
 #define CRP_HIP(ctx, call)                                                              \

@@ -20,6 +20,7 @@ struct SelectTable {
     const uint32_t *props;             // packed guide properties (property limits)
     const unsigned long long *repair;  // mh | oof << 32 of crp_repair_scores (repair limits)
     uint32_t n;
+    const uint32_t *variants;          // packed variant counts of crp_variant_counts (variant limits)
 };
 
 struct SelectPredicate {
@@ -34,6 +35,8 @@ struct SelectPredicate {
     uint32_t gc_min, gc_max, max_run, max_t_run, max_stem;
     // with SelectTable::repair: mh >= min_mh and 100 oof >= min_oof_pct mh, and mh > 0 where min_oof_pct > 0
     uint32_t min_mh, min_oof_pct;
+    // with SelectTable::variants: site <= max_var_site, guide <= max_var_guide, seed <= max_var_seed, pam <= max_var_pam (each one byte)
+    uint32_t max_var_site, max_var_guide, max_var_seed, max_var_pam;
 };
 
 // One wave's work: rows [first[s], first[s] + rows[s]) of strand s's table, all inside gene `gene`'s runs.  slot ==

@@ -30,3 +30,8 @@
                 const uint32_t mh = (uint32_t)rp, oof = (uint32_t)(rp >> 32);
                 pass = pass && mh >= pred.min_mh && 100u * oof >= pred.min_oof_pct * mh && (mh != 0u || pred.min_oof_pct == 0u);
             }
+            if (t.variants) {  // (the packed word of crp_variant_counts: site | guide << 8 | seed << 16 | pam << 24, each saturated at 255)
+                const uint32_t vr = in ? t.variants[row] : 0u;
+                pass = pass && (vr & 255u) <= pred.max_var_site && (vr >> 8 & 255u) <= pred.max_var_guide && (vr >> 16 & 255u) <= pred.max_var_seed &&
+                       vr >> 24 <= pred.max_var_pam;
+            }

@@ -74,6 +74,7 @@ class Arena:
         self._h = handle
         self.offsets = offsets
         self.lengths = lengths
+        self.guide_len = None  # of the last scan_score_device()
 
     def close(self):
         if self._h:
@@ -108,6 +109,7 @@ class Arena:
         planes)."""
         npl, nmi = ctypes.c_uint64(), ctypes.c_uint64()
         flags = (nat.SCAN_PRE if want_pre else 0) | (nat.SCAN_SEEDS if want_seeds else 0)
+        self.guide_len = int(guide_len)  # of the last scan (Genome.variant_counts' default seed is min(12, l))
         nat.check(nat.lib().crp_scan_score(self._h, guide_len, flags,
                                            ctypes.byref(npl), ctypes.byref(nmi)),
                   "crp_scan_score", self._engine._ctx)
@@ -208,6 +210,32 @@ class Arena:
         out = np.zeros(3, dtype=np.float64)
         nat.check(nat.lib().crp_repair_scores_stats(self._h, out.ctypes.data_as(nat.f64p), 3), "crp_repair_scores_stats", self._engine._ctx)
         return dict(kernel_ms=float(out[0]), rows=int(out[1]), flank=int(out[2]))
+
+    # ---- variant counts (opt-in; variants.py has the definition)
+    def variant_set_track(self, starts, ends1):
+        """The arena's variant track: every interval's start and every interval's end + 1, arena positions, each array
+        ascending on its own (variants.VariantSet.track builds them).  Empty arrays are a valid track."""
+        starts = np.ascontiguousarray(starts, dtype=np.uint32)
+        ends1 = np.ascontiguousarray(ends1, dtype=np.uint32)
+        if starts.shape != ends1.shape or starts.ndim != 1:
+            raise ValueError("starts and ends1 must be 1-d arrays of one length")
+        nat.check(nat.lib().crp_variant_set_track(self._h, starts.ctypes.data_as(nat.u32p), ends1.ctypes.data_as(nat.u32p), starts.size),
+                  "crp_variant_set_track", self._engine._ctx)
+
+    def variant_counts(self, n_plus, n_minus, seed, fetch=True):
+        """The packed variant counts (site | guide << 8 | seed << 16 | pam << 24, each saturating at 255) of every kept hit
+        of the last scan against the arena's variant track; fetch=False leaves the column in HBM (for a selection's variant
+        limits)."""
+        pair = [np.empty(n, dtype=np.uint32) for n in (n_plus, n_minus)] if fetch else [None, None]
+        nat.check(nat.lib().crp_variant_counts(self._h, int(seed), *[None if a is None else a.ctypes.data_as(nat.u32p) for a in pair]),
+                  "crp_variant_counts", self._engine._ctx)
+        return tuple(pair) if fetch else None
+
+    def variant_counts_stats(self):
+        """dict(kernel_ms, rows, guide_len, seed, variants) of the last variant_counts() on the current tables."""
+        out = np.zeros(5, dtype=np.float64)
+        nat.check(nat.lib().crp_variant_counts_stats(self._h, out.ctypes.data_as(nat.f64p), 5), "crp_variant_counts_stats", self._engine._ctx)
+        return dict(kernel_ms=float(out[0]), rows=int(out[1]), guide_len=int(out[2]), seed=int(out[3]), variants=int(out[4]))
 
     # ---- off-target seed scan (opt-in; include/cropsr_hip.h)
     def offtarget_add(self, guide_len=20, own_ranges=None):
@@ -709,6 +737,7 @@ class Genome:
         self.annotate_s = None
         self.properties_stats = None  # dict(kernel_ms, rows, wall_s) of the last guide_properties()
         self.repair_stats = None  # dict(kernel_ms, rows, flank, wall_s) of the last repair_scores()
+        self.variant_stats = None  # dict(kernel_ms, rows, seed, variants, track_s, wall_s) of the last variant_counts()
         self._where = {}
         for a, g in enumerate(groups):
             for j, k in enumerate(g):
@@ -753,6 +782,28 @@ class Genome:
         self.repair_stats = dict(kernel_ms=ms, rows=n_rows, flank=int(flank), wall_s=time.perf_counter() - t0)
         return out if fetch else None
 
+    def variant_counts(self, request, counts, seed=None, fetch=True):
+        """The variant counts over every arena's resident tables (variants.Request -- laid out per arena from the piece
+        layout the annotation request uses; counts: (n_plus, n_minus) per arena; seed: the seed length, None: the request's,
+        else min(12, guide length) -- the library refuses one outside 1..guide length).  Returns [(var_plus, var_minus)] per
+        arena, packed (variants.unpack), or None with fetch=False (the columns stay in HBM)."""
+        import time
+        from . import variants as var
+        t0 = time.perf_counter()
+        out, ms, n_rows, n_var, track_s, used = [], 0.0, 0, 0, 0.0, None
+        for a, g, (n_plus, n_minus) in zip(self.arenas, self.groups, counts):
+            t1 = time.perf_counter()
+            a.variant_set_track(*request.track([(k, int(a.offsets[j]), int(a.lengths[j])) for j, k in enumerate(g)]))
+            track_s += time.perf_counter() - t1
+            s = seed if seed is not None else request.seed
+            if s is None:  # (min(12, l) of the arena's last scan)
+                s = var.default_seed(a.guide_len) if a.guide_len else var.DEFAULT_SEED
+            out.append(a.variant_counts(n_plus, n_minus, s, fetch=fetch))
+            st = a.variant_counts_stats()
+            ms, n_rows, n_var, used = ms + st["kernel_ms"], n_rows + st["rows"], n_var + st["variants"], st["seed"]
+        self.variant_stats = dict(kernel_ms=ms, rows=n_rows, seed=used, variants=n_var, track_s=track_s, wall_s=time.perf_counter() - t0)
+        return out if fetch else None
+
     def specificity_columns(self, guide_len=20, max_mm=3, candidate_pam="NRG", score="hsu2013", budget=None, families=None,
                             family_cover_mm=0, family_limits=None):
         """The genome-wide specificity of every hit of the last scan at guide_len, joined on the GPU
@@ -762,7 +813,8 @@ class Genome:
         return search.specificity_columns(self, guide_len, max_mm=max_mm, candidate_pam=candidate_pam, score=score, budget=budget,
                                           families=families, family_cover_mm=family_cover_mm, family_limits=family_limits)
 
-    def select(self, request, hits, counts=None, handle_of=None, joined=None, annotated=False, repair=None, family_joined=None):
+    def select(self, request, hits, counts=None, handle_of=None, joined=None, annotated=False, repair=None, family_joined=None,
+               variants=None):
         """The best K guides of every gene (select.Request; the module's docstring has the definition) over the tables
         of the last scan at guide length 20, which `hits` (GenomeHits) holds as host copies.  Runs after the annotation
         look-up and -- with handle_of(arena index) -> the arena's joined search.ArenaSelfSearch and joined[arena index] =
@@ -770,6 +822,8 @@ class Genome:
         handles.  annotated: the arenas hold the ids of an annotation look-up on these tables (else require_cds runs one).
         repair: per arena (repair_plus, repair_minus), the fetched columns of repair_scores(): the Selection carries mh and
         oof of its rows.  A request with repair limits needs the columns resident (repair_scores(fetch=False) is enough).
+        variants: per arena (var_plus, var_minus), the fetched columns of variant_counts(): the Selection carries the packed
+        counts of its rows.  A request with variant limits needs the columns resident (variant_counts(fetch=False) is enough).
         Returns select.Selection: for every gene of the GFF in file order its label, n_in, n_pass and the selected rows
         (contig, position, strand, score, and the joined counts and sum when present); with request.pairs also the best pairs
         of every gene (Selection.pairs, n_pairs), selected right after the single guides while the same columns are resident."""
@@ -796,6 +850,8 @@ class Genome:
                 part["counts_plus"], part["sum_plus"], part["counts_minus"], part["sum_minus"] = joined[a]
             if repair is not None:
                 part["repair_plus"], part["repair_minus"] = repair[a]
+            if variants is not None:
+                part["var_plus"], part["var_minus"] = variants[a]
             if "coding" in extras:
                 part["coding"] = extras["coding"]
             if "edit" in extras:
@@ -837,7 +893,9 @@ class Genome:
         repair=F (a flank, 2..32): hits.repair holds, per ARENA, the packed repair scores (repair_plus, repair_minus) of its
         tables' rows (repair.unpack turns a column into mh, oof).  They are deliberately not cut into the contig hit dicts.
         A select.Request with repair limits or a repair flank runs the kernel too, right before the selection -- after the
-        scan, or inside the specificity join's after_join hook --; with limits alone the column stays on the device."""
+        scan, or inside the specificity join's after_join hook --; with limits alone the column stays on the device.
+        A select.Request with variants runs the variant count kernel right after the scan (hits.variants: per ARENA the packed
+        (var_plus, var_minus), variants.unpack); its variant limits hold in every selection that follows."""
         from .repair import check_flank
         want_repair = repair is not None or (select is not None and select.runs_repair)
         if repair is not None:
@@ -856,6 +914,8 @@ class Genome:
             specificity = dict(specificity, families=fam.genome_rows(select.families, self, select.annotation),
                                family_cover_mm=select.family_cover_mm)
         hits = self._scan_score(guide_len, want_pre, offtarget, seeds_from_scan, annotation)
+        if select is not None and getattr(select, "variants", None) is not None:
+            hits.variants = self.variant_counts(select.variants, [(h.n_plus, h.n_minus) for h in hits.per_arena], seed=select.variant_seed)
         if properties or (select is not None and select.property_limits is not None):
             cols = self.guide_properties([(h.n_plus, h.n_minus) for h in hits.per_arena], fetch=bool(properties))
             if properties:
@@ -885,13 +945,13 @@ class Genome:
                         if want_repair:
                             run_repair()
                         hits.selection = self.select(select, hits, handle_of=handles.get, joined=joined, annotated=annotation is not None,
-                                                     repair=hits.repair, family_joined=family_cols or None)
+                                                     repair=hits.repair, family_joined=family_cols or None, variants=hits.variants)
 
                 hits.columns = search.specificity_columns(self, guide_len, after_join=after_join, **specificity)
         elif select is not None:
             if want_repair:
                 run_repair()
-            hits.selection = self.select(select, hits, annotated=annotation is not None, repair=hits.repair)
+            hits.selection = self.select(select, hits, annotated=annotation is not None, repair=hits.repair, variants=hits.variants)
         return hits
 
     def _scan_score(self, guide_len, want_pre, offtarget, seeds_from_scan, annotation):
@@ -955,6 +1015,7 @@ class GenomeHits:
         self.columns = None  # per contig, further columns of its rows (Genome.scan_score(specificity=..))
         self.selection = None  # select.Selection (Genome.scan_score(select=..))
         self.repair = None  # per arena (repair_plus, repair_minus), packed (Genome.scan_score(repair=F))
+        self.variants = None  # per arena (var_plus, var_minus), packed (a select.Request with variants)
 
     def contig(self, k):
         a, j = self._genome._where[k]

@@ -235,12 +235,26 @@ class Request:
     pairs: one kernel per predicate.
     family_sets (S, 1..64): after the per-gene selection the scan also chooses, per family, at most S guides that together
     cut as many members as possible (family_sets(); Selection.family_sets, Selection.family_complete).  Needs families, and
-    is refused with coding, edit or splice limits and with pairs."""
+    is refused with coding, edit or splice limits and with pairs.
+    variants (variants.Request): the scan counts the cultivar's variants under every hit (variants.py) before the selection --
+    variant_seed is the seed length (None: min(12, guide length)) -- and the Selection carries the packed counts of its rows
+    (Selection.variants).  max_variants / max_guide_variants / max_seed_variants / max_pam_variants (variants.Limits) are
+    limits on the site, guide, seed and PAM counts: a row passes only if all hold, in every selection the request runs --
+    single guides, pairs, coding, edit, splice, family limits and family sets.  They need variants."""
 
     def __init__(self, params, annotation, slice_rows=None, gc_min=None, gc_max=None, max_run=None, max_t_run=None, max_stem=None,
                  repair_flank=None, min_mh=None, min_oof=None, pairs=None, pair_slice_rows=None, coding=False, coding_limits=None,
                  edit_window=None, edit_limits=None, editor=None, splice_limits=None, edit=None, families=None, family_cover_mm=0,
-                 min_members=None, max_perfect_outside=None, min_specificity_outside=None, family_sets=None):
+                 min_members=None, max_perfect_outside=None, min_specificity_outside=None, family_sets=None, variants=None,
+                 variant_seed=None, max_variants=None, max_guide_variants=None, max_seed_variants=None, max_pam_variants=None):
+        self.variants, self.variant_seed, self.variant_limits = variants, variant_seed, None
+        if any(v is not None for v in (max_variants, max_guide_variants, max_seed_variants, max_pam_variants)):
+            if variants is None:
+                raise ValueError("max_variants, max_guide_variants, max_seed_variants and max_pam_variants need a variant set (variants=)")
+            from .variants import Limits as VariantLimits
+            self.variant_limits = VariantLimits(max_variants, max_guide_variants, max_seed_variants, max_pam_variants)
+        if variant_seed is not None and variants is None:
+            raise ValueError("variant_seed needs a variant set (variants=)")
         self.families, self.family_cover_mm = families, int(family_cover_mm)
         self.family_sets = None
         if family_sets is not None:
@@ -340,6 +354,11 @@ class ArenaSelect:
         """limits: repair.Limits, or None to clear them."""
         lim = None if limits is None else ctypes.byref(nat.SelectRepairLimits(*limits.astuple()))
         nat.check(nat.lib().crp_select_set_repair_limits(self._h, lim), "crp_select_set_repair_limits", self._ctx)
+
+    def set_variant_limits(self, limits):
+        """limits: variants.Limits, or None to clear them."""
+        lim = None if limits is None else ctypes.byref(nat.SelectVariantLimits(*limits.astuple()))
+        nat.check(nat.lib().crp_select_set_variant_limits(self._h, lim), "crp_select_set_variant_limits", self._ctx)
 
     def run(self, params, self_search=None):
         """params: Params; self_search: the search.ArenaSelfSearch of this arena after its join_hits, or None."""
@@ -575,6 +594,7 @@ class Selection:
         self.labels, self.n_in, self.n_pass, self.rows = labels, n_in, n_pass, rows
         self.counts, self.hit_sum, self.stats = counts, hit_sum, stats or {}
         self.mh, self.oof = mh, oof
+        self.variants = None  # (n,) uint32, packed (variants.unpack), of the rows when the variant counts were fetched
         self.pairs = self.n_pairs = self.pairs_repair = None
         self.pairs_stats = {}
         self.cds_offset = self.cds_length = self.transcripts_cut = self.transcripts = None
@@ -615,6 +635,8 @@ def assemble(labels, k, arenas, stats=None):
     parts, cparts, sparts = [], [], []
     joined = any(a.get("counts_plus") is not None for a in arenas)
     repaired = any(a.get("repair_plus") is not None for a in arenas)
+    varied = any(a.get("var_plus") is not None for a in arenas)
+    vparts = []
     coded = any(a.get("coding") is not None for a in arenas)
     edited = any(a.get("edit") is not None for a in arenas)
     spliced = any(a.get("splice") is not None for a in arenas)
@@ -653,6 +675,8 @@ def assemble(labels, k, arenas, stats=None):
             sparts.append(_take(a["sum_plus"], a["sum_minus"], minus, row, np.uint64))
         if repaired:
             rparts.append(_take(a["repair_plus"], a["repair_minus"], minus, row, np.uint64))
+        if varied:
+            vparts.append(_take(a["var_plus"], a["var_minus"], minus, row, np.uint32))
         if coded:
             cod = a["coding"]
             kparts.append(np.stack([np.asarray(cod["off"], np.uint32).reshape(gene.size, -1)[r, c],
@@ -693,6 +717,8 @@ def assemble(labels, k, arenas, stats=None):
         from .repair import unpack
         mh, oof = unpack(packed_repair[order][keep])
     out = Selection(list(labels), n_in, n_pass, rows, counts, sums, stats, mh, oof)
+    if vparts:
+        out.variants = np.concatenate(vparts)[order][keep]
     if kparts:
         cod = np.concatenate(kparts)[order][keep]
         out.cds_offset, out.cds_length, out.transcripts_cut, out.transcripts = (cod[:, j].copy() for j in range(4))
@@ -776,8 +802,8 @@ def select_arena_pairs(sel, request, handle=None):
 
 
 def _set_row_limits(sel, request, flags=None):
-    """The terms of the predicate that do not depend on the gene, on an ArenaSelect: the CDS flags, the slices, the property
-    and the repair limits of a Request."""
+    """The terms of the predicate that do not depend on the gene, on an ArenaSelect: the CDS flags, the slices, the property,
+    the repair and the variant limits of a Request."""
     if request.params.require_cds:
         sel.set_flags(flags if flags is not None else request.annotation.annotation.cds_flags())
     if request.slice_rows:
@@ -786,6 +812,8 @@ def _set_row_limits(sel, request, flags=None):
         sel.set_property_limits(request.property_limits)
     if getattr(request, "repair_limits", None) is not None:
         sel.set_repair_limits(request.repair_limits)
+    if getattr(request, "variant_limits", None) is not None:
+        sel.set_variant_limits(request.variant_limits)
 
 
 def _set_families(sel, request, gene):

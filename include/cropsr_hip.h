@@ -1170,6 +1170,95 @@ int crp_select_family_step(crp_select *select, const crp_select_params *params, 
  * n: how many to write (<= 6). */
 int crp_select_family_step_stats(const crp_select *select, double *out, int n);
 
+/* ---- variant-aware guides: cultivar variants under every target site (opt-in) ------------- */
+/* The guides are scanned from a reference assembly; the plant that is transformed carries SNPs and indels against it.
+ * Per kept hit: how many variants of a VCF touch its target site, its guide, its PAM-proximal seed and its PAM.
+ *
+ * VARIANT INTERVALS.  For every VCF record and every kept ALT allele: strip the common prefix of REF and ALT (letters
+ * compared without case), then the common suffix of what is left: REF', ALT' and p, the 1-based coordinate of the first
+ * letter after the stripped prefix.  The allele is the closed interval [s, e] of contig coordinates, s = p,
+ * e = p + len(REF') - 1.  A pure insertion (REF' empty) is [p, p - 1]: an empty interval at the junction between p - 1
+ * and p.  An allele with REF' and ALT' both empty is dropped.  Always e >= s - 1.
+ *
+ * ARENA LAYOUT.  entries and dec as crp_annotation_track takes them, the first value of an entry being the index of the
+ * text's CHROM among crp_variants_chrom's (any value >= their number: the text has no variants; a CHROM names a contig
+ * when it equals its FASTA name exactly).  Coordinate c has string index c + dec - 1; inside a text that begins at
+ * string index `first`, has `length` characters and lies at arena offset `offset` it has arena position index - first +
+ * offset.  An interval is clipped to the text in string indices: s' = max(s, first), e' = min(e, first + length - 1); it
+ * is kept when e' >= s' - 1.  Equal (s', e') pairs of one arena count once (a multi-allelic SNP is one variant).  The
+ * track of an arena is two uint32 arrays of one length n, EACH ASCENDING ON ITS OWN: starts holds every s', ends1 every
+ * e' + 1 (so it stays unsigned); all values are below 2^31.
+ *
+ * WINDOWS of a hit, after a scan at guide length l = 1 .. 50, with seed length S, 1 <= S <= l: closed ranges of arena
+ * positions in the forward text; pos is the match index i ('+' row, .GG at i) or j ('-' row, CC. at j):
+ *               '+' row               '-' row
+ *   site        [i - l, i + 2]        [j, j + 2 + l]          guide + PAM
+ *   guide       [i - l, i - 1]        [j + 3, j + 2 + l]
+ *   seed        [i - S, i - 1]        [j + 3, j + 2 + S]      the PAM-proximal S letters of the guide
+ *   pam         [i + 1, i + 2]        [j, j + 1]              the two fixed letters
+ * A variant [s, e] TOUCHES a window [a, b] when s <= b and e >= a; an insertion touches it exactly when both letters
+ * around its junction lie inside (an insertion between guide and PAM counts for `site` only).  The count of a window is
+ * #(starts <= b) - #(ends1 <= a), exact because e >= s - 1.  Every row has a value, the unscored rows and the '-' rows
+ * whose window runs past the contig's end included: the void between texts carries no variant.  A substitution at the
+ * PAM's N counts in `site` only.
+ * One uint32 per row: site | guide << 8 | seed << 16 | pam << 24, each SATURATING at 255. */
+/* Host side (no GPU needed): the VCF reader.  Text VCF bytes in any number of chunks (a .gz is unpacked by the caller).
+ *   lines     end with LF or CRLF; the last one may lack its line end; empty lines are skipped
+ *   # lines   are skipped, except that #CHROM names the samples (columns 10 ...)
+ *   columns   tab-separated, at least CHROM POS ID REF ALT; POS a plain digit string >= 1 (at most 15 digits); REF and
+ *             every ALT letters of ACGTNacgtn
+ *   ALT       comma-separated; `.`, `*`, a symbolic <...> and a breakend (holds [ or ]) are skipped and counted
+ *   pass_only the record is kept only if FILTER (column 7) is PASS or `.`
+ *   samples   (n_samples > 0; an unknown name is an error, as is a data line before any #CHROM line): ALT allele k is kept
+ *             only when the GT of at least one named sample holds k -- GT is found through FORMAT (column 9), its alleles
+ *             are split at / and |, `.` is ignored, an index beyond the ALT list is malformed.  Without samples every ALT
+ *             allele is kept: a sites-only VCF works.
+ * A malformed line is CRP_ERR_INVALID with a crp_variants_error text that names the line number; the handle then refuses
+ * further bytes.  Allele-frequency filters and symbolic structural variants (END=) are not read. */
+typedef struct crp_variants crp_variants;
+int crp_variants_create(const char *const *samples, uint64_t n_samples, int pass_only, crp_variants **out);
+int crp_variants_add_bytes(crp_variants *variants, const uint8_t *bytes, uint64_t n);
+int crp_variants_finish(crp_variants *variants);
+int crp_variants_destroy(crp_variants *variants);
+/* The text of the handle's error ("" without one); valid until the handle's next call. */
+const char *crp_variants_error(const crp_variants *variants);
+/* out[0] lines read, [1] records (data lines), [2] records dropped by pass_only, [3] ALT alleles kept, [4] ALT alleles
+ * skipped (`.`, `*`, symbolic, breakend), [5] ALT alleles no named sample carries, [6] ALT alleles equal to REF after
+ * stripping, [7] CHROMs with at least one kept allele.  n: how many of these to write (<= 8). */
+int crp_variants_stats(const crp_variants *variants, uint64_t *out, int n);
+/* CHROM k (order of first appearance among the kept alleles): its name.  The pointer stays valid until
+ * crp_variants_destroy.  After crp_variants_finish. */
+int crp_variants_chrom(const crp_variants *variants, uint64_t k, const uint8_t **name, uint64_t *name_len);
+/* The track of one arena for crp_variant_set_track, after crp_variants_finish (ARENA LAYOUT above).  Capacity protocol
+ * of crp_annotation_track: CRP_ERR_CAPACITY with the needed size in *n_out when cap is too small (cap 0: sizing call). */
+int crp_variants_track(const crp_variants *variants, const uint64_t *entries, uint64_t n_entries, int dec, uint32_t *starts,
+                       uint32_t *ends1, uint64_t cap, uint64_t *n_out);
+/* Device side.  The arena keeps a copy of the track in HBM (8 B per variant) with one bucket index per array: entry b is
+ * the number of values below b << 11 (the annotation track's scheme), built on the GPU.  n = 0 is a valid, empty track.
+ * CRP_ERR_INVALID: an array that is not ascending or holds a value >= 2^31; CRP_ERR_STATE: the arena is not sealed. */
+int crp_variant_set_track(crp_arena *arena, const uint32_t *starts, const uint32_t *ends1, uint64_t n);
+/* After crp_scan_score on `arena` and crp_variant_set_track: the packed counts of every kept hit, table order.  The
+ * column stays in HBM until the arena's next scan (crp_select_set_variant_limits reads it there) and is copied to plus /
+ * minus (n_plus / n_minus values; either may be NULL).  One kernel lane per four rows, one launch for both tables; five
+ * ranks per row, each two bucket entries and a binary search inside the bucket.  With a crp_last_error text:
+ * CRP_ERR_STATE without tables or without a track, CRP_ERR_INVALID for tables scanned at guide length 0 and for a
+ * seed_len outside 1 .. l. */
+int crp_variant_counts(crp_arena *arena, int seed_len, uint32_t *plus, uint32_t *minus);
+/* The last crp_variant_counts of the arena (CRP_ERR_STATE without a column for the current tables): out[0] ms of its
+ * kernel (HIP events), out[1] rows, out[2] the guide length, out[3] the seed length, out[4] the track's variants.
+ * n: how many of these to write (<= 5). */
+int crp_variant_counts_stats(const crp_arena *arena, double *out, int n);
+/* Variant limits of a selection (the column of crp_variant_counts): with limits set a row PASSES only if also
+ * site <= max_site, guide <= max_guide, seed <= max_seed and pam <= max_pam (the saturated bytes: a limit of 255 or more
+ * holds for every row).  Every kernel that evaluates the selection's predicate -- crp_select_run, crp_select_run_pairs,
+ * the coding / edit / splice / family evaluations and crp_select_family_step -- then reads 4 more bytes per row
+ * (crp_select_stats counts them) and the run returns CRP_ERR_STATE when the arena holds no variant column for its current
+ * tables.  NULL clears the limits. */
+typedef struct crp_select_variant_limits {
+    uint32_t max_site, max_guide, max_seed, max_pam;
+} crp_select_variant_limits;
+int crp_select_set_variant_limits(crp_select *select, const crp_select_variant_limits *limits);
+
 /* ---- options -------------------------------------------------------------- */
 /* CRP_OPT_TWO_PASS (value 0/1, default 0): with 0 crp_scan_score is ONE kernel launch; the
  * table offsets come from a chained scan across workgroups inside it (decoupled look-back
