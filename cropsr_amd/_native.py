@@ -254,6 +254,9 @@ SIGNATURES = {
     "crp_select_run_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "crp_select_fetch_pairs": (ctypes.c_int, [ctypes.c_void_p, u32p, u64p, u32p]),
     "crp_select_pairs_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
+    "crp_select_run_spaced": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
+    "crp_select_fetch_spaced": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, u32p]),
+    "crp_select_spaced_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_annotation_gene_coding": (ctypes.c_int, [ctypes.c_void_p, u8p, u32p, u32p]),
     "crp_annotation_coding_layout": (ctypes.c_int, [ctypes.c_void_p, u64p, ctypes.c_uint64, ctypes.c_int, u32p, u32p, u64p, ctypes.c_uint64, u64p,
                                                     u32p, u32p, u32p, ctypes.c_uint64, u64p]),
@@ -316,6 +319,7 @@ SELECT_ALL_MEMBERS = 0xFFFFFFFF  # crp_select_family_limits.min_members: the siz
 SELF_UNJOINED_COUNT, SELF_UNJOINED_SUM = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF  # crp_search_self_join_hits: a hit without a guide site's row
 SELECT_MAX_K, SELECT_DEFAULT_SLICE_ROWS, SELECT_MIN_SLICE_ROWS, SELECT_NONE = 64, 65536, 64, 0xFFFFFFFF
 SELECT_PAIRS_MAX_K, SELECT_PAIRS_MAX_DISTANCE, SELECT_DEFAULT_PAIR_SLICE_ROWS, SELECT_MIN_PAIR_SLICE_ROWS = 64, 65535, 1024, 64
+SELECT_MAX_SPACING = 0x7FFFFFFF  # crp_select_run_spaced's largest minimum distance: cut sites lie below 2^31
 CRP_ERR_INVALID = -1
 CRP_ERR_NO_DEVICE = -2
 CRP_ERR_UNSUPPORTED = -7

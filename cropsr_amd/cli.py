@@ -126,6 +126,12 @@ def build_parser():
                      help="with --select: only guides whose cut site lies in a CDS row of the GFF (positional, like --annotate)")
     eng.add_argument("--select-only", action="store_true",
                      help="with --select: write the selection file only, not the main table (no ids are drawn)")
+    eng.add_argument("--select-min-spacing", type=int, default=None, metavar="D",
+                     help="with --select: the K guides of a gene cut at least D letters of the assembly apart -- the guides are taken "
+                          "best first, and one whose cut site lies within D - 1 letters of a guide already taken is passed over -- "
+                          "chosen on the GPU (1..2147483647; 1 only forbids two guides with one cut site); the selection file keeps its "
+                          "columns, `rank` is the pick order and `passing` counts all passing guides; not together with the coding-"
+                          "position, stop-codon, splice-site or family filters")
     eng.add_argument("--properties", action="store_true",
                      help="NOT in the reference: the guide's own sequence quality, computed on the GPU from the l letters of every "
                           "row's guide; appends the columns guide_gc (letters that are C or G), guide_run (longest run of one base), "
@@ -661,7 +667,8 @@ def select_request(args, spec, world=1):
     given = [o for o, k, unset in (("--select-output", "select_output", None), ("--select-min-score", "select_min_score", None),
                                    ("--select-max-perfect", "select_max_perfect", None),
                                    ("--select-min-specificity", "select_min_specificity", None), ("--select-cds", "select_cds", False),
-                                   ("--select-only", "select_only", False), ("--select-gc-min", "select_gc_min", None),
+                                   ("--select-only", "select_only", False), ("--select-min-spacing", "select_min_spacing", None),
+                                   ("--select-gc-min", "select_gc_min", None),
                                    ("--select-gc-max", "select_gc_max", None), ("--select-max-run", "select_max_run", None),
                                    ("--select-max-t-run", "select_max_t_run", None), ("--select-max-stem", "select_max_stem", None),
                                    ("--repair-scores", "repair_scores", False), ("--repair-flank", "repair_flank", None),
@@ -903,6 +910,20 @@ def select_request(args, spec, world=1):
             refuse("--families: " + str(e))
         coding_args = dict(coding_args, family_cover_mm=integer(cover) if cover is not None else 0, min_members=members,
                            max_perfect_outside=perfect, min_specificity_outside=outside)
+    # the minimum spacing: its rounds read one pass key per table row, so not with the filters that are relative to the gene
+    spacing = getattr(args, "select_min_spacing", None)
+    if spacing is not None:
+        if not 1 <= spacing <= select.MAX_SPACING:
+            refuse("--select-min-spacing is a number of letters 1..%d, not %d" % (select.MAX_SPACING, spacing))
+        for other, name in (([o for o, k in (("--select-coding-min", "select_coding_min"), ("--select-coding-max", "select_coding_max"),
+                                             ("--select-transcripts", "select_transcripts")) if k in pct], "the coding-position filter"),
+                            ([stop_limit] if stop_limit is not None else [], "the stop-codon filter"),
+                            ([splice_limit] if splice_limit is not None else [], "the splice-site filter"),
+                            (family_limit, "the family filter")):
+            if other:
+                refuse("--select-min-spacing and %s: %s is relative to the gene and the spacing's eligibility is per table row: one or the other"
+                       % (other[0], name))
+        coding_args = dict(coding_args, min_spacing=spacing)
     # (a flank makes the scan fetch the column: only where the file prints it, or where the filters ask for another flank than the default)
     repair_args = dict(min_mh=min_mh, min_oof=min_oof,
                        repair_flank=(repair.DEFAULT_FLANK if flank is None else flank) if with_scores else flank)

@@ -16,6 +16,7 @@
 #include "crp_select_family.h"
 #include "crp_select_family_set.h"
 #include "crp_search_family.h"
+#include "crp_select_spaced.h"
 #include "crp_select_splice.h"
 
 struct crp_select {
@@ -104,6 +105,15 @@ struct crp_select {
     uint64_t set_items = 0, set_rows = 0, set_families = 0, set_plan_slice = 0, set_plan_hits[2] = {0, 0};
     crp_select_params set_plan_params = {};
     double set_stats[6] = {};
+    // spaced selection: results and buffers of crp_select_run_spaced, apart from the selection's; the
+    // pass keys are the pair path's (d_pass_key)
+    crp::SpacedResult spaced_res = {};  // n_pass, n_spaced: n_genes; sel: n_genes * ks of the last run
+    crp::SpacedRounds spaced_rounds = {};
+    crp::SelectItem *d_spaced_items = nullptr;
+    crp::SelectMerge *d_spaced_merge = nullptr;
+    uint64_t spaced_cap[10] = {};
+    int ks = 0;  // of the last successful crp_select_run_spaced (0: none)
+    double spaced_stats[9] = {};
 };
 
 namespace {
@@ -280,7 +290,9 @@ int crp_select_destroy(crp_select *s)
                     s->pair_part.n_pass, s->pair_part.n_pairs, s->pair_res.n_pass, s->pair_res.n_pairs, s->pair_res.pairs,
                     s->d_cod[0], s->d_cod[1], s->d_cod[2], s->d_cod[3], s->d_cod[4], s->d_cod[5], s->d_eval[0], s->d_eval[1], s->d_eval[2],
                     s->d_eval[3], s->d_gene_family, s->d_family_size, s->d_family_eval_sum, s->d_gene_member, s->d_set_items, s->d_set_prop,
-                    s->d_set_best, s->d_set_start, s->d_set_slots, s->d_set_covered};
+                    s->d_set_best, s->d_set_start, s->d_set_slots, s->d_set_covered, s->spaced_res.n_pass, s->spaced_res.n_spaced, s->spaced_res.sel,
+                    s->spaced_rounds.cuts, s->spaced_rounds.last, s->spaced_rounds.prop, s->spaced_rounds.slot_pass, s->spaced_rounds.picked,
+                    s->d_spaced_items, s->d_spaced_merge};
     for (void *p : bufs) (void)hipFree(p);
     for (hipEvent_t e : s->ev)
         if (e) (void)hipEventDestroy(e);
@@ -711,6 +723,187 @@ int crp_select_pairs_stats(const crp_select *s, double *out, int n)
 {
     if (!s || (n && !out) || n < 0 || n > 8) return CRP_ERR_INVALID;
     for (int k = 0; k < n; ++k) out[k] = s->pair_stats[k];
+    return CRP_OK;
+}
+
+/* ---- spaced selection ---- */
+
+int crp_select_run_spaced(crp_select *s, const crp_select_params *p, uint32_t min_distance, crp_search_self *self)
+{
+    crp::Range roctx_range("crp: spaced selection");
+    if (!s || !p) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    crp_arena *a = s->arena;
+    s->ks = 0;
+    const std::string who = "crp_select_run_spaced";
+    if (p->k < 1 || p->k > CRP_SELECT_MAX_K)
+        return fail(ctx, CRP_ERR_INVALID, who + ": k must be 1.." + std::to_string(CRP_SELECT_MAX_K) + ", not " + std::to_string(p->k));
+    if (min_distance > CRP_SELECT_MAX_SPACING)
+        return fail(ctx, CRP_ERR_INVALID, who + ": the minimum distance must be 0.." + std::to_string(CRP_SELECT_MAX_SPACING) + " (cut sites lie below 2^31), not " +
+                                              std::to_string(min_distance));
+    if (s->have_family_limits)
+        return fail(ctx, CRP_ERR_INVALID, who + ": family limits are relative to the gene and the spaced selection's eligibility key is per table row: "
+                                                "clear them (crp_select_set_family_limits(select, NULL)) for a spaced selection");
+    if (s->have_coding_limits)
+        return fail(ctx, CRP_ERR_INVALID, who + ": coding limits are relative to the gene and the spaced selection's eligibility key is per table row: "
+                                                "clear them (crp_select_set_coding_limits(select, NULL)) for a spaced selection");
+    if (s->have_edit_limits)
+        return fail(ctx, CRP_ERR_INVALID, who + ": edit limits are relative to the gene and the spaced selection's eligibility key is per table row: "
+                                                "clear them (crp_select_set_edit_limits(select, NULL, NULL)) for a spaced selection");
+    if (s->have_splice_limits)
+        return fail(ctx, CRP_ERR_INVALID, who + ": splice limits are relative to the gene and the spaced selection's eligibility key is per table row: "
+                                                "clear them (crp_select_set_splice_limits(select, NULL, 0, NULL)) for a spaced selection");
+    crp::SelfJoined joined = {};
+    int rc = check_run(s, p, self, &joined, who.c_str());
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    const int k = p->k;
+    const uint64_t G = s->n_genes;
+    crp::SpacedResult &res = s->spaced_res;
+    crp::SpacedRounds &rounds = s->spaced_rounds;
+    rc = crp::grow(ctx, reinterpret_cast<void **>(&res.n_pass), &s->spaced_cap[0], G, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&res.n_spaced), &s->spaced_cap[1], G, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&res.sel), &s->spaced_cap[2], G * k, sizeof(uint32_t));
+    if (rc != CRP_OK) return rc;
+    for (double &v : s->spaced_stats) v = 0;
+    if (!G) {
+        s->ks = k;
+        return CRP_OK;
+    }
+    // (a table has fewer rows than the arena positions: below 2^31)
+    const uint32_t n_plus = (uint32_t)a->n_hits[0], n_minus = (uint32_t)a->n_hits[1];
+    crp::SelectTable tab[2];
+    crp::SelectPredicate pred;
+    fill_predicate(s, p, self != nullptr, joined, 0, tab, &pred);
+    // the pass key of every row, once, in the pair path's buffers: the rounds then read position and key, 12 bytes a row
+    for (int t = 0; t < 2; ++t) {
+        rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_pass_key[t]), &s->pass_key_cap[t], a->n_hits[t], sizeof(uint64_t));
+        if (rc != CRP_OK) return rc;
+    }
+    CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    for (int t = 0; t < 2; ++t) CRP_HIP(ctx, crp::launch_pair_pass_key(ctx->stream, tab[t], pred, s->d_pass_key[t]));
+    CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+    s->spaced_stats[5] += 2;
+    CRP_HIP(ctx, crp::launch_select_bounds(ctx->stream, a->d_pos[0], n_plus, a->d_pos[1], n_minus, s->d_lo, s->d_hi, (uint32_t)G, s->d_bounds));
+    std::vector<uint4> bounds;
+    std::vector<crp::SelectItem> whole, pieces;
+    std::vector<crp::SelectMerge> merges;
+    std::vector<uint32_t> picked;
+    try {
+        bounds.resize(G);
+        rc = crp::staged_d2h(ctx, bounds.data(), s->d_bounds, G * sizeof(uint4));
+        if (rc != CRP_OK) return rc;
+        CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        s->spaced_stats[0] = elapsed(s->ev[0], s->ev[1]);
+        // crp_select_run's cut of the genes' rows into items of at most slice_rows rows; the whole genes and the pieces of
+        // the cut genes in two lists, because only the pieces come back round after round
+        whole.reserve(G);
+        for (uint64_t g = 0; g < G; ++g) {
+            const uint4 b = bounds[g];
+            if (b.x > b.y || b.y > n_plus || b.z > b.w || b.w > n_minus)
+                return fail(ctx, CRP_ERR_HIP, who + ": the bounds of gene " + std::to_string(g) + " lie outside the tables");
+            const uint64_t np = b.y - b.x, nm = b.w - b.z, total = np + nm;
+            const uint64_t n_pieces = std::max<uint64_t>(1, (total + s->slice_rows - 1) / s->slice_rows);
+            if (pieces.size() + n_pieces > 0xfffffff0ull) return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": more than 2^32 work items (raise slice_rows)");
+            if (n_pieces > 1) merges.push_back(crp::SelectMerge{(uint32_t)g, (uint32_t)pieces.size(), (uint32_t)n_pieces});
+            for (uint64_t c = 0; c < n_pieces; ++c) {
+                // rows [r0, r1) of the gene's concatenated runs
+                const uint64_t r0 = c * s->slice_rows, r1 = std::min(total, r0 + s->slice_rows);
+                const uint64_t p0 = std::min(r0, np), p1 = std::min(r1, np);
+                const uint64_t m0 = std::max(r0, np) - np, m1 = std::max(r1, np) - np;
+                crp::SelectItem it;
+                it.gene = (uint32_t)g;
+                it.slot = n_pieces > 1 ? (uint32_t)pieces.size() : crp::SELECT_NONE;
+                it.first[0] = b.x + (uint32_t)p0;
+                it.rows[0] = (uint32_t)(p1 - p0);
+                it.first[1] = b.z + (uint32_t)m0;
+                it.rows[1] = (uint32_t)(m1 - m0);
+                (n_pieces > 1 ? pieces : whole).push_back(it);
+            }
+        }
+        picked.resize(merges.size());
+    } catch (const std::bad_alloc &) {
+        return CRP_ERR_NOMEM;
+    }
+    const uint64_t n_whole = whole.size(), n_pieces = pieces.size(), n_cut = merges.size();
+    rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_spaced_items), &s->spaced_cap[3], n_whole + n_pieces, sizeof(crp::SelectItem));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_spaced_merge), &s->spaced_cap[4], n_cut, sizeof(crp::SelectMerge));
+    if (rc == CRP_OK && n_cut) rc = crp::grow(ctx, reinterpret_cast<void **>(&rounds.cuts), &s->spaced_cap[5], G * k, sizeof(uint32_t));
+    if (rc == CRP_OK && n_cut) rc = crp::grow(ctx, reinterpret_cast<void **>(&rounds.last), &s->spaced_cap[6], G, sizeof(crp::SpacedProposal));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&rounds.prop), &s->spaced_cap[7], n_pieces, sizeof(crp::SpacedProposal));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&rounds.slot_pass), &s->spaced_cap[8], n_pieces, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&rounds.picked), &s->spaced_cap[9], n_cut, sizeof(uint32_t));
+    if (rc == CRP_OK && n_whole) rc = crp::staged_h2d(ctx, s->d_spaced_items, whole.data(), n_whole * sizeof(crp::SelectItem));
+    if (rc == CRP_OK && n_pieces) rc = crp::staged_h2d(ctx, s->d_spaced_items + n_whole, pieces.data(), n_pieces * sizeof(crp::SelectItem));
+    if (rc == CRP_OK && n_cut) rc = crp::staged_h2d(ctx, s->d_spaced_merge, merges.data(), n_cut * sizeof(crp::SelectMerge));
+    if (rc != CRP_OK) return rc;
+    const auto timed = [&](double *sum) {
+        const double ms = elapsed(s->ev[0], s->ev[1]);
+        *sum += ms;
+        s->spaced_stats[5] += 1;
+        s->spaced_stats[6] = std::max(s->spaced_stats[6], ms);
+    };
+    // the whole genes: every round inside one launch; the bounded-launch rule: at most 2^20 items a launch, each timed on its own
+    for (uint64_t first = 0; first < n_whole; first += crp::SELECT_MAX_ITEMS) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(crp::SELECT_MAX_ITEMS, n_whole - first);
+        CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+        CRP_HIP(ctx, crp::launch_spaced_items(ctx->stream, a->d_pos[0], a->d_pos[1], s->d_pass_key[0], s->d_pass_key[1], k, min_distance, 0u,
+                                              s->d_spaced_items + first, n, rounds, res));
+        CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+        CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        timed(&s->spaced_stats[1]);
+    }
+    // the cut genes: a step launch and a pick launch a round, until a round picks nothing
+    for (uint32_t round = 0; n_cut && round < (uint32_t)k; ++round) {
+        for (uint64_t first = 0; first < n_pieces; first += crp::SELECT_MAX_ITEMS) {
+            const uint32_t n = (uint32_t)std::min<uint64_t>(crp::SELECT_MAX_ITEMS, n_pieces - first);
+            CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+            CRP_HIP(ctx, crp::launch_spaced_items(ctx->stream, a->d_pos[0], a->d_pos[1], s->d_pass_key[0], s->d_pass_key[1], k, min_distance, round,
+                                                  s->d_spaced_items + n_whole + first, n, rounds, res));
+            CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+            CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            timed(&s->spaced_stats[2]);
+        }
+        for (uint64_t first = 0; first < n_cut; first += crp::SELECT_MAX_ITEMS) {
+            const uint32_t n = (uint32_t)std::min<uint64_t>(crp::SELECT_MAX_ITEMS, n_cut - first);
+            CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+            CRP_HIP(ctx, crp::launch_spaced_pick(ctx->stream, s->d_spaced_merge + first, n, (uint32_t)first, k, round, rounds, res));
+            CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+            CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            timed(&s->spaced_stats[3]);
+        }
+        s->spaced_stats[4] += 1;
+        rc = crp::staged_d2h(ctx, picked.data(), rounds.picked, n_cut * sizeof(uint32_t));
+        if (rc != CRP_OK) return rc;
+        CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (std::none_of(picked.begin(), picked.end(), [](uint32_t v) { return v != 0u; })) break;
+    }
+    s->spaced_stats[7] = (double)(n_whole + n_pieces);
+    s->spaced_stats[8] = (double)n_cut;
+    s->ks = k;
+    return CRP_OK;
+}
+
+int crp_select_fetch_spaced(crp_select *s, uint32_t *n_pass, uint32_t *n_spaced, uint32_t *sel)
+{
+    if (!s) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    if (!s->ks) return fail(ctx, CRP_ERR_STATE, "crp_select_fetch_spaced: no crp_select_run_spaced has succeeded on this handle");
+    if (!s->n_genes) return CRP_OK;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = CRP_OK;
+    if (n_pass) rc = crp::staged_d2h(ctx, n_pass, s->spaced_res.n_pass, s->n_genes * sizeof(uint32_t));
+    if (rc == CRP_OK && n_spaced) rc = crp::staged_d2h(ctx, n_spaced, s->spaced_res.n_spaced, s->n_genes * sizeof(uint32_t));
+    if (rc == CRP_OK && sel) rc = crp::staged_d2h(ctx, sel, s->spaced_res.sel, s->n_genes * s->ks * sizeof(uint32_t));
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CRP_OK;
+}
+
+int crp_select_spaced_stats(const crp_select *s, double *out, int n)
+{
+    if (!s || (n && !out) || n < 0 || n > 9) return CRP_ERR_INVALID;
+    for (int k = 0; k < n; ++k) out[k] = s->spaced_stats[k];
     return CRP_OK;
 }
 

@@ -77,6 +77,25 @@ Family sets (family_sets.py has the definition; csrc/crp_s
 the scan also chooses, per family, at most S passing rows of its member genes that together cover as many members as
 possible, greedily: each step takes the candidate with the largest gain over what is covered so far.
 
+Spaced selection (csrc/crp_select_spaced.hip; tests/select_spacing_reference.py restates it twice): the
+K best rows of a gene cluster -- a good 30-mer context lifts its neighbours, a reverse palindrome gives two rows with one cut
+site -- and guides that cut within a few letters of each other fail together.  With min_spacing = D (0 <= D <= 2^31 - 1), per
+arena and per layout row g, after a scan at guide length 20:
+
+  passing   the rows that PASS for gene g, as above: exactly those n_pass[g] counts under the handle's current row limits
+            (min_score, joined columns, require_cds, property, repair and variant limits).
+  order     the selection's: higher score bits as unsigned 64-bit, then smaller cut site, then '+' before '-'.  The cut site is
+            i - 3 for '+' and j for '-': NOT the pairs' cut boundary.
+  spaced    walk the passing rows of g in that order; take a row iff |cut - cut(p)| >= D for EVERY row p already taken; stop at
+            K taken.  Equivalently: round t takes the best passing row that is not within D - 1 of any earlier pick.
+  result    per gene g: n_pass[g], unchanged by D; n_spaced[g], the rows taken, at most min(K, n_pass); sel[g][0..K) in the
+            packing above, in pick order, 0xFFFFFFFF beyond n_spaced.  Exact and integer-only: it does not depend on how the
+            work was cut.  D = 0 is the plain selection bit for bit; D = 1 forbids only equal cut sites.
+
+Spacing holds inside one arena text; a gene met in several texts keeps the rule above (the first K of the concatenation).  It
+is greedy by score, not a maximum-weight spread, and D counts letters of the assembly.  Not together with coding, edit, splice
+or family limits: their kernels own a predicate per gene and row, and the spaced rounds read one pass key per table row.
+
 This module lays the genes out per arena, converts a wanted specificity into the integer bound the kernel compares,
 drives crp_select_* and turns the per-arena results into one table over the genes of the GFF.
 """
@@ -91,6 +110,7 @@ NONE = nat.SELECT_NONE
 NO_BOUND_MM0, NO_BOUND_SUM = 0xFFFFFFFF, 0xFFFFFFFFFFFFFFFF
 GUIDE_LEN = 20  # the ranking key, the on-target score, exists only there
 MAX_KP, MAX_DISTANCE = nat.SELECT_PAIRS_MAX_K, nat.SELECT_PAIRS_MAX_DISTANCE
+MAX_SPACING = nat.SELECT_MAX_SPACING
 ORIENTATIONS = {"any": 0xF, "pam-out": 0x4, "pam-in": 0x2}  # bit sa * 2 + sb, 0 for '+' and 1 for '-'
 PAIR_DTYPE = np.dtype([("gene", "<u4"), ("rank", "<u4"), ("contig", "<u4"), ("position_a", "<i8"), ("strand_a", "S1"), ("score_a", "<f8"),
                        ("index_a", "<u4"), ("position_b", "<i8"), ("strand_b", "S1"), ("score_b", "<f8"), ("index_b", "<u4"),
@@ -240,13 +260,27 @@ class Request:
     variant_seed is the seed length (None: min(12, guide length)) -- and the Selection carries the packed counts of its rows
     (Selection.variants).  max_variants / max_guide_variants / max_seed_variants / max_pam_variants (variants.Limits) are
     limits on the site, guide, seed and PAM counts: a row passes only if all hold, in every selection the request runs --
-    single guides, pairs, coding, edit, splice, family limits and family sets.  They need variants."""
+    single guides, pairs, coding, edit, splice, family limits and family sets.  They need variants.
+    min_spacing (D, 0..2^31 - 1): the guides of a gene cut at least D letters apart (the module's text has the definition): the
+    scan runs the plain selection, which supplies n_in and n_pass, and then the spaced selection, whose rows the Selection
+    carries in pick order.  The per-pick fields (coding, edit, splice, families) are those of the spaced picks; pairs and
+    family sets are not affected.  Refused with coding, edit, splice or family limits."""
 
     def __init__(self, params, annotation, slice_rows=None, gc_min=None, gc_max=None, max_run=None, max_t_run=None, max_stem=None,
                  repair_flank=None, min_mh=None, min_oof=None, pairs=None, pair_slice_rows=None, coding=False, coding_limits=None,
                  edit_window=None, edit_limits=None, editor=None, splice_limits=None, edit=None, families=None, family_cover_mm=0,
                  min_members=None, max_perfect_outside=None, min_specificity_outside=None, family_sets=None, variants=None,
-                 variant_seed=None, max_variants=None, max_guide_variants=None, max_seed_variants=None, max_pam_variants=None):
+                 variant_seed=None, max_variants=None, max_guide_variants=None, max_seed_variants=None, max_pam_variants=None,
+                 min_spacing=None):
+        self.min_spacing = None
+        if min_spacing is not None:
+            if isinstance(min_spacing, bool) or not isinstance(min_spacing, (int, np.integer)) or not 0 <= int(min_spacing) <= MAX_SPACING:
+                raise ValueError("min_spacing is a number of letters 0..%d, not %r" % (MAX_SPACING, min_spacing))
+            for given, name in ((coding_limits, "coding"), (edit_limits, "edit"), (splice_limits, "splice"),
+                                (next((v for v in (min_members, max_perfect_outside, min_specificity_outside) if v is not None), None), "family")):
+                if given is not None:
+                    raise ValueError("%s limits are relative to the gene; the spaced selection's eligibility is per table row: one or the other" % name)
+            self.min_spacing = int(min_spacing)
         self.variants, self.variant_seed, self.variant_limits = variants, variant_seed, None
         if any(v is not None for v in (max_variants, max_guide_variants, max_seed_variants, max_pam_variants)):
             if variants is None:
@@ -325,7 +359,7 @@ class ArenaSelect:
         lo, hi = np.ascontiguousarray(lo, dtype=np.uint32), np.ascontiguousarray(hi, dtype=np.uint32)
         if lo.shape != hi.shape or lo.ndim != 1:
             raise ValueError("lo and hi must be 1-d arrays of one length")
-        self.n_genes, self.k, self.kp = int(lo.size), 0, 0
+        self.n_genes, self.k, self.kp, self.ks = int(lo.size), 0, 0, 0
         h = ctypes.c_void_p()
         nat.check(nat.lib().crp_select_create(arena._h, lo.ctypes.data_as(nat.u32p), hi.ctypes.data_as(nat.u32p), lo.size, ctypes.byref(h)),
                   "crp_select_create", self._ctx)
@@ -380,6 +414,30 @@ class ArenaSelect:
         nat.check(nat.lib().crp_select_stats(self._h, out.ctypes.data_as(nat.f64p), 9), "crp_select_stats", self._ctx)
         keys = ("bounds_ms", "select_ms", "merge_ms", "items", "launches", "longest_launch_ms", "rows_in_runs", "bytes_per_row",
                 "merged_genes")
+        return dict(zip(keys, (float(v) for v in out)))
+
+    def run_spaced(self, params, min_spacing, self_search=None):
+        """params: Params (its thresholds and K); min_spacing: D, 0..MAX_SPACING; self_search as run()."""
+        if isinstance(min_spacing, bool) or not isinstance(min_spacing, (int, np.integer)) or not 0 <= int(min_spacing) <= 0xFFFFFFFF:
+            raise ValueError("min_spacing is a number of letters 0..%d, not %r" % (MAX_SPACING, min_spacing))
+        p = params.native()
+        nat.check(nat.lib().crp_select_run_spaced(self._h, ctypes.byref(p), int(min_spacing), self_search._h if self_search is not None else None),
+                  "crp_select_run_spaced", self._ctx)
+        self.ks = params.k
+
+    def fetch_spaced(self):
+        """(n_pass uint32 (G,), n_spaced uint32 (G,), sel uint32 (G, K)) of the last run_spaced."""
+        n_pass, n_spaced = np.empty(self.n_genes, np.uint32), np.empty(self.n_genes, np.uint32)
+        sel = np.empty((self.n_genes, max(1, self.ks)), np.uint32)
+        nat.check(nat.lib().crp_select_fetch_spaced(self._h, n_pass.ctypes.data_as(nat.u32p), n_spaced.ctypes.data_as(nat.u32p),
+                                                    sel.ctypes.data_as(nat.u32p)), "crp_select_fetch_spaced", self._ctx)
+        return n_pass, n_spaced, sel
+
+    def spaced_stats(self):
+        out = np.zeros(9, dtype=np.float64)
+        nat.check(nat.lib().crp_select_spaced_stats(self._h, out.ctypes.data_as(nat.f64p), 9), "crp_select_spaced_stats", self._ctx)
+        keys = ("spaced_key_ms", "spaced_items_ms", "spaced_step_ms", "spaced_pick_ms", "spaced_rounds", "spaced_launches",
+                "spaced_longest_launch_ms", "spaced_items", "spaced_cut_genes")
         return dict(zip(keys, (float(v) for v in out)))
 
     def set_coding(self, model):
@@ -858,6 +916,11 @@ def select_arena(genome, a, request, handle=None, flags=None, extras=None):
         sel.run(request.params, handle)
         n_in, n_pass, picked = sel.fetch()
         stats = sel.stats()
+        if getattr(request, "min_spacing", None) is not None:  # the plain run gave n_in and n_pass; the picks are the spaced run's
+            sel.run_spaced(request.params, request.min_spacing, handle)
+            spaced_pass, _, picked = sel.fetch_spaced()
+            assert np.array_equal(spaced_pass, n_pass), "the spaced selection and the plain selection count different passing rows"
+            stats.update(sel.spaced_stats())
         if table is not None and extras is not None:
             r, c = np.nonzero(picked != NONE)
             fm = dict(outside_mm0=np.zeros(picked.shape, np.uint32), outside_hit_sum=np.zeros(picked.shape, np.uint64),
@@ -913,7 +976,9 @@ def family_sets(genome, request, handle_of, hits, flags=None):
 
 def sum_stats(total, one):
     for key, v in one.items():
-        if key in ("bytes_per_row", "edit_targets_window", "splice_window", "editor"):
+        if key == "spaced_longest_launch_ms":
+            total[key] = max(total.get(key, 0.0), v)
+        elif key in ("bytes_per_row", "edit_targets_window", "splice_window", "editor"):
             total[key] = v
         else:
             total[key] = max(total.get(key, 0.0), v) if key == "longest_launch_ms" else total.get(key, 0.0) + v

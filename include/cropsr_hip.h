@@ -977,6 +977,37 @@ int crp_select_fetch_pairs(crp_select *select, uint32_t *n_pass, uint64_t *n_pai
  * in ms, out[6] pair evaluations (partner rows streamed), out[7] qualifying pairs.  n: how many to write (<= 8). */
 int crp_select_pairs_stats(const crp_select *select, double *out, int n);
 
+/* ---- spaced selection: K guides per gene whose cut sites lie at least D apart (opt-in) --- */
+/* crp_select_run's K best rows of a gene cluster: a good 30-mer context lifts its neighbours.  On a crp_select handle,
+ * over the same tables and genes, per layout row g:
+ *   passing    the rows that PASS for gene g: exactly those crp_select_run counts in n_pass[g] under the handle's flags,
+ *              property, repair and variant limits
+ *   order      crp_select_run's: higher score bits (unsigned 64-bit), then smaller cut site, then '+' before '-'; the
+ *              cut site is i - 3 for a '+' row and j for a '-' row (NOT the pairs' cut boundary)
+ *   spaced     walk the passing rows of g in that order; take a row iff |cut - cut(p)| >= min_distance for EVERY row p
+ *              already taken; stop at K taken.  (Round t takes the best passing row that is not within
+ *              min_distance - 1 of any earlier pick.)
+ * Per gene: n_pass (as crp_select_run's, whatever the distance), n_spaced (the rows taken, at most min(K, n_pass)) and
+ * sel[g * K ..): the rows taken in pick order, in crp_select_run's packing (row | strand << 31), 0xFFFFFFFF beyond
+ * n_spaced.  Exact and integer-only: the result does not depend on how the work was cut.  min_distance = 0 is
+ * crp_select_run's sel bit for bit; 1 forbids only equal cut sites.  Greedy by score, not a maximum-weight spread. */
+#define CRP_SELECT_MAX_SPACING 0x7FFFFFFFu
+/* Prerequisites and their error codes as crp_select_run (params: its thresholds and K).  CRP_ERR_INVALID with a
+ * crp_last_error text: K outside 1 .. 64, min_distance > CRP_SELECT_MAX_SPACING, and coding, edit, splice or family
+ * limits in force on the handle (their kernels own a predicate per gene and row; the spaced rounds read one key per
+ * row).  Genes are cut into items by crp_select_set_limits' slice_rows; a gene in one item runs all its rounds in one
+ * launch, the others take a step launch and a pick launch a round: at most 2 K + 3 launches per 2^20 items.  Leaves
+ * the results of crp_select_run and crp_select_run_pairs alone. */
+int crp_select_run_spaced(crp_select *select, const crp_select_params *params, uint32_t min_distance, crp_search_self *self);
+/* The results of the last crp_select_run_spaced (CRP_ERR_STATE without one): n_pass and n_spaced (n_genes each) and sel
+ * (n_genes * K).  Any pointer may be NULL. */
+int crp_select_fetch_spaced(crp_select *select, uint32_t *n_pass, uint32_t *n_spaced, uint32_t *sel);
+/* Measurement of the last crp_select_run_spaced: out[0] ms of the pass-key kernel, out[1] ms of the whole-gene item
+ * launches, out[2] ms of the cut genes' step launches, out[3] ms of their pick launches (HIP events), out[4] host rounds,
+ * out[5] kernel launches, out[6] the longest launch in ms, out[7] work items, out[8] cut genes.  n: how many to write
+ * (<= 9). */
+int crp_select_spaced_stats(const crp_select *select, double *out, int n);
+
 /* ---- coding position: where in the coding sequence a guide cuts (opt-in) ---------------- */
 /* crp_annotation_build also reads the `mRNA` / `transcript` rows, the Parent links and the gene rows' strand, and builds a
  * CODING MODEL of every gene (cropsr_amd/coding.py states the definition):
