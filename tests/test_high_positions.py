@@ -9,6 +9,7 @@ import pytest
 
 import base_edit_reference as eref
 import family_reference as fref
+import family_set_reference as fsr
 import guide_properties_reference as gref
 import high_position_cases as hp
 import repair_reference as rref
@@ -22,6 +23,7 @@ import select_pairs_reference as pairs_ref
 import select_reference as selref
 import specificity_join_cases as join_cases
 import splice_edit_reference as spref
+import variant_reference as vref
 from cropsr_amd import _native as nat
 from cropsr_amd import annotate, baseedit, coding
 from cropsr_amd import families as fam
@@ -43,13 +45,17 @@ SPLICE_LIMITS = (None, (0, 100, 20, "any"))
 FAMILY_LIMITS = dict(min_members=2, max_perfect_outside=0)
 FAMILY_TIE_LIMITS = dict(min_members=1)  # every joined row passes: the tie gene's pairs decide in the family item kernel
 BOUNDS = (0, sel.max_hit_sum_for(0.5))  # max_perfect 0, min_specificity 0.5
+VARIANT_SEED = 12
+ALL_ONES = (1 << 64) - 1
+NO_FILLER = "no-filler"  # Case.layout's third placement: the case contigs alone (tests/test_select_predicate_matrix.py); not in hp.PLACEMENTS
 
 
 class Case:
     """The case contigs, their GFF and what the references say about them: computed once, never changed."""
 
-    def __init__(self, orc, tmp):
-        self.__dict__.update(hp.build(orc))
+    def __init__(self, orc, tmp, built=None):
+        """built: None for hp.build(orc), or another case genome as a dict of hp.build's keys."""
+        self.__dict__.update(hp.build(orc) if built is None else built)
         self.orc = orc
         self.lengths = [len(t) for t in self.contigs]
         self.gff_path = str(tmp / "cases.gff")
@@ -72,6 +78,8 @@ class Case:
     # ---- the layout
     def layout(self, placement):
         """(filler length, offsets of the case contigs, words of the arena) by the restated rule."""
+        if placement == NO_FILLER:
+            return (0,) + hp.offsets_of(self.lengths)
         n = hp.filler_length(placement, self.lengths, self.max_words)
         offsets, words = hp.offsets_of([n] + self.lengths)
         return n, offsets[1:], words
@@ -133,6 +141,20 @@ class Case:
     def family_rows(self, M, C=0):
         return self.once(("family", M, C), lambda: fref.family_rows(self.contigs, PATTERN, M, GUIDE_PATTERN, self.genes, self.gene_family,
                                                                      self.gene_member, C, ("weights", sref.W_HSU)))
+
+    def step_candidates(self):
+        """The candidates of the family sets (family_set_reference.FIELDS; contig-relative, every contig in arena 0): every
+        joined, scored row of every family gene, from the family tests' plain loop (M = 3, hsu2013, no limits)."""
+        import test_families as tf
+
+        def make():
+            fam_ref = self.family_rows(3)
+            row_of = {s: r for r, s in enumerate(fam_ref["sites"])}
+            want = tf._reference_selection(self, self.hits, self.join(3, "hsu2013"), fam_ref, row_of, 10 ** 9)
+            passing = [[(kc, pos, st, r, i) for (kc, pos, st, _, r), i in zip(w[2], w[3])] for w in want]
+            key_of = lambda kc, st, i: int(np.float64(self.hits[kc]["score_minus" if st else "score_plus"][i]).view(np.uint64))
+            return fsr.candidates(self.genes, self.gene_family, self.gene_member, passing, fam_ref, {k: 0 for k in range(len(self.contigs))}, key_of)
+        return self.once("step_candidates", make)
 
 
 class Placed:
@@ -209,9 +231,43 @@ class Placed:
         return self.once(("splice", K, limits), lambda: spref.select_numpy(self.local_tables, self.member, self.case.models, self.local_rows, K,
                                                                             self.splices(), limits))
 
-    def select_family(self, K, limits):
+    def variants(self):
+        """The variant track of test_gpu_variant_counts in arena positions -- dict(intervals, starts, ends1) -- with the
+        expected columns plus and minus (variant_reference.column_numpy over the tables, seed 12) and `filled`: the arena
+        position of the '+' row of the tie block whose site window holds more than 255 intervals.
+          background  under every case contig an interval every 40 letters: SNPs, deletions, insertions -- at `straddle` on
+                      both sides of 2^30
+          spanning    one deletion from the last rows of the tie block's first copy to the first rows of its second: at
+                      `straddle` it spans 2^30 (at `top` 2^30 lies in the filler, and so does this interval)
+          filled      every interval [s, e] inside the site window of one '+' row in the middle of the first copy: 276 distinct
+                      ones in one bucket of 2 048 positions, so its site and guide counts saturate
+          tail        two deletions from hp_tail's first letters to 2^31 - 2 and 2^31 - 3, the largest ends a track takes
+                      (ends1 = 2^31 - 1), and an insertion before hp_tail's last letter"""
+        def make():
+            c, t = self.case, self.tables
+            rng = np.random.default_rng(25)
+            iv = set()
+            for off, n in zip(self.offsets, c.lengths):
+                for s in (rng.integers(1, n - 13, n // 40) + off).tolist():
+                    kind = rng.random()
+                    iv.add((s, s) if kind < 0.7 else (s, s + int(rng.integers(1, 12))) if kind < 0.85 else (s, s - 1))
+            tie = self.offsets[hp.TIE]
+            iv.add((tie + hp.COPY[0] + hp.BLOCK - 20, tie + hp.COPY[1] + 20))
+            pairs = hp.tie_pairs(c.hits, "plus")
+            filled = int(c.hits[hp.TIE]["pos_plus"][pairs[len(pairs) // 2][0]]) + tie
+            iv.update((s, e) for s in range(filled - L, filled + 3) for e in range(s, filled + 3))
+            tail = self.offsets[-1]
+            iv.update([(tail + 1, hp.TWO31 - 2), (tail + 2, hp.TWO31 - 3), (tail + hp.TAIL_LEN - 1, tail + hp.TAIL_LEN - 2)])
+            starts, ends1 = vref.track(sorted(iv))
+            return dict(intervals=sorted(iv), starts=starts, ends1=ends1, filled=filled,
+                        plus=vref.column_numpy(t["pos_plus"], False, L, VARIANT_SEED, starts, ends1),
+                        minus=vref.column_numpy(t["pos_minus"], True, L, VARIANT_SEED, starts, ends1))
+        return self.once("variants", make)
+
+    def select_family(self, K, limits, also=None, key=None):
         """Per layout row (n_in, n_pass, sel as the device packs it, the reference's values of the selected rows), from the
-        family tests' plain loop over genes and rows; the joined columns are the references', not a device's."""
+        family tests' plain loop over genes and rows; the joined columns are the references', not a device's.  also: None, or
+        a boolean per row of the concatenated tables -- the predicate's other terms --, cached under `key`."""
         import test_families as tf
 
         def make():
@@ -219,8 +275,10 @@ class Placed:
             fam_ref = c.family_rows(3)
             row_of = {s: r for r, s in enumerate(fam_ref["sites"])}
             bound = None if limits.get("min_specificity_outside") is None else sel.max_hit_sum_for(limits["min_specificity_outside"])
+            more = None if also is None else (lambda kc, strand, i: also[int(self.rows_before["minus" if strand else "plus"][kc]) + i +
+                                                                         (self.n_plus if strand else 0)])
             want = tf._reference_selection(c, c.hits, c.join(3, "hsu2013"), fam_ref, row_of, K, None, None,
-                                           (limits.get("min_members"), limits.get("max_perfect_outside"), bound))
+                                           (limits.get("min_members"), limits.get("max_perfect_outside"), bound), also=more)
             n_in, n_pass, picked, values = [], [], np.full((len(self.gene), K), NONE, np.uint32), []
             for r, g in enumerate(self.gene):
                 w = want[int(g)]
@@ -233,7 +291,8 @@ class Placed:
                                      int(fam_ref["site_family"][site]) == c.gene_family[int(g)] else 0,))
                 values.append(vals)
             return np.array(n_in, np.uint32), np.array(n_pass, np.uint32), picked, values
-        return self.once(("family", K, tuple(sorted(limits.items()))), make)
+        assert (also is None) == (key is None)
+        return self.once(("family", K, tuple(sorted(limits.items())), key), make)
 
 
 @pytest.fixture(scope="module")
@@ -396,6 +455,74 @@ def test_expected_arrays_are_not_trivial(case):
         n_in, n_pass, picked, values = p.select_family(5, FAMILY_LIMITS)
         assert 0 < n_pass.sum() < p.select(5)[1].sum() and any(v[2] >= 2 for vals in values for v in vals)
         assert (p.pairs(5)[1] > 5).sum() >= 3
+
+
+def test_variant_track_holds_its_cases(case):
+    """On the reference's column: rows with a count on both sides of 2^30 at `straddle`, the spanning deletion among what
+    they count; a saturated field over a bucket of more than 255 entries; hp_tail's rows counted, under ends1 = 2^31 - 1."""
+    for name in hp.PLACEMENTS:
+        p = case.placed(name)
+        v, t = p.variants(), p.tables
+        col = np.concatenate([v["plus"], v["minus"]])
+        pos = np.concatenate([t["pos_plus"], t["pos_minus"]]).astype(np.int64)
+        assert (np.concatenate([vref.column_loop(t["pos_plus"][::7], False, L, VARIANT_SEED, v["intervals"]),
+                                vref.column_loop(t["pos_minus"][::7], True, L, VARIANT_SEED, v["intervals"])]) ==
+                np.concatenate([v["plus"][::7], v["minus"][::7]])).all()  # (the touch rule, variant by variant, on every 7th row)
+        assert v["starts"].size == len(v["intervals"]) > 400 and int(v["ends1"].max()) == hp.TWO31 - 1
+        kinds = [(e == s, e > s, e < s) for s, e in v["intervals"]]
+        assert all(sum(k[i] for k in kinds) >= 10 for i in range(3))
+        spanning = (p.offsets[hp.TIE] + hp.COPY[0] + hp.BLOCK - 20, p.offsets[hp.TIE] + hp.COPY[1] + 20)
+        assert spanning in v["intervals"]
+        if name == "straddle":
+            assert ((col != 0) & (pos < hp.TWO30)).sum() >= 64 and ((col != 0) & (pos >= hp.TWO30)).sum() >= 64
+            assert spanning[0] < hp.TWO30 - 500 and hp.TWO30 + 400 < spanning[1]
+            st, en = vref.track([x for x in v["intervals"] if x != spanning])
+            without = np.concatenate([vref.column_numpy(t["pos_plus"], False, L, VARIANT_SEED, st, en),
+                                      vref.column_numpy(t["pos_minus"], True, L, VARIANT_SEED, st, en)])
+            assert ((without != col) & (pos < hp.TWO30)).any() and ((without != col) & (pos >= hp.TWO30)).any()
+        else:
+            assert (pos >= hp.TWO30).all() and (col != 0).sum() >= 128
+        # the filled bucket: one bucket of the starts' index holds the 276 intervals, and the row's site and guide fields saturate
+        filled = v["filled"]
+        assert (filled - L) >> 11 == (filled + 2) >> 11 and int((v["starts"] >> 11 == filled >> 11).sum()) > 255
+        r = int(np.flatnonzero(t["pos_plus"] == filled)[0])
+        assert v["plus"][r] & 0xFFFF == 0xFFFF and sum(1 for s, e in v["intervals"] if s <= filled + 2 and e >= filled - L) >= 276
+        assert p.offsets[hp.TIE] + hp.COPY[0] < filled - L and filled + 2 < p.offsets[hp.TIE] + hp.COPY[0] + hp.BLOCK
+        # hp_tail: every row counts the deletions that run to the top
+        for strand in ("plus", "minus"):
+            mine = v[strand][p.rows_before[strand][-2]:]
+            assert mine.size >= 2 and ((mine & 255) >= 2).all() and mine[-1] >> 24 >= 1
+
+
+def test_family_step_ties_lie_across_two30(case):
+    """twins has one member, tie: every candidate gains 1, the best score occurs once in either copy of the block, and
+    cut << 1 | strand decides between the two.  At `straddle` the winner's word has bit 31 clear and the loser's has it set -- a
+    signed compare takes the loser --; at `top` every word has bit 31 set.  homeo's candidates lie on both sides of 2^30."""
+    cands = case.step_candidates()
+    twins, homeo = case.fam_names.index("twins"), case.fam_names.index("homeo")
+    assert case.sizes[twins] == 1 and case.sizes[homeo] == 3
+    mine = [c for c in cands if c[0] == twins]
+    best = mine[fsr.best_loop(mine, 0)]
+    tied = [c for c in mine if c[6] == best[6]]
+    assert len(tied) == 2 and best[6] == max(c[6] for c in mine)
+    loser = [c for c in tied if c != best][0]
+    for name in hp.PLACEMENTS:
+        p = case.placed(name)
+        word = lambda c: ((c[3] + p.offsets[c[2]]) << 1 | c[4]) & 0xFFFFFFFF
+        assert word(best) < word(loser)
+        if name == "straddle":
+            assert best[3] + p.offsets[best[2]] < hp.TWO30 <= loser[3] + p.offsets[loser[2]]
+            assert word(best) >> 31 == 0 and word(loser) >> 31 == 1
+            cuts = np.array([c[3] + p.offsets[c[2]] for c in cands if c[0] == homeo])
+            assert (cuts < hp.TWO30).sum() >= 64 and (cuts >= hp.TWO30).sum() >= 64
+        else:
+            assert word(best) >> 31 == 1 and word(loser) >> 31 == 1
+    # against all ones but one member's bit only the rows that cover that member gain: other proposals than against nothing
+    for bit in range(3):
+        covered = [ALL_ONES ^ 1 << bit] * len(case.sizes)
+        want = fsr.arena_best(cands, case.sizes, covered, 0)
+        assert want[homeo] is not None and want[homeo]["gain"] == 1 and (want[twins] is None) == (bit != 0)
+    assert fsr.arena_best(cands, case.sizes, [0, 0], 0)[homeo]["gain"] == 3
 
 
 # ---------------------------------------------------------------------------------------------- on the GPU
@@ -811,3 +938,66 @@ def test_gpu_genome_level_selection(dev, case):
         _assert_joined(case, p, hits.columns, 3, "hsu2013")
     finally:
         dev.scan()
+
+
+@pytest.mark.gpu
+def test_gpu_variant_counts(dev, case):
+    """crp_variant_counts behind the filler: the bucket index of a position with bit 30 set, the last bucket, the windows'
+    far ends j + 2 + l and ends1 up to 2^31 - 1 -- every row against variant_reference.column_numpy -- and an empty track."""
+    v = dev.ref.variants()
+    n_plus, n_minus = dev.counts[0]
+    dev.arena.variant_set_track(np.empty(0, np.uint32), np.empty(0, np.uint32))
+    zp, zm = dev.arena.variant_counts(n_plus, n_minus, VARIANT_SEED)
+    assert zp.size == n_plus and zm.size == n_minus and not zp.any() and not zm.any()
+    dev.arena.variant_set_track(v["starts"], v["ends1"])
+    for got, strand in zip(dev.arena.variant_counts(n_plus, n_minus, VARIANT_SEED), ("plus", "minus")):
+        bad = np.flatnonzero(got != v[strand])
+        assert bad.size == 0, (strand, bad[:5], got[bad[:5]], v[strand][bad[:5]], dev.ref.tables["pos_" + strand][bad[:5]])
+    assert dev.arena.variant_counts_stats()["variants"] == len(v["intervals"])
+
+
+@pytest.mark.gpu
+def test_gpu_family_step(dev, case):
+    """crp_select_family_step behind the filler, whole genes and slices of 64: the proposals of homeo and twins against
+    nothing covered and against all ones but one member's bit, from family_set_reference.arena_best.  The tie gene's bit-equal
+    scores on either side of 2^30 leave the choice to the word cut << 1 | strand, in the step kernel and in the pick kernel."""
+    p = dev.ref
+    cands = case.step_candidates()
+    table = _family_table(case)
+    F = len(case.sizes)
+    words = [[0] * F] + [[ALL_ONES ^ 1 << bit] * F for bit in range(3)]
+    pattern, gp, M, scheme = srch.check_specificity(L, 3)
+    handles = []
+    h = None
+    try:
+        srch._self_handles(dev.genome, pattern, gp, srch.SPECIFICITY_PAM_LEN, M, scheme, None, None, handles)
+        srch._self_compare_all(handles, M)
+        srch._family_compare_all(handles, fam.genome_rows(table, dev.genome, dev.request), 0)
+        handles[0].join_hits(L)
+        handles[0].family_join_hits(L)
+        h = dev.select()
+        g = np.asarray(p.gene, np.int64)
+        h.set_family(table.gene_family[g], np.array([table.family_size(int(x)) for x in g], np.uint32))
+        h.set_family_members(table.gene_member[g])
+        for slice_rows in (0, 64):
+            h.set_limits(slice_rows)
+            for covered in words:
+                best = h.family_step(sel.Params(1), handles[0], np.array(covered, np.uint64))
+                want = fsr.arena_best(cands, case.sizes, covered, 0)
+                for f, w in enumerate(want):
+                    what = (slice_rows, covered[f], case.fam_names[f])
+                    if w is None:
+                        assert best["gain"][f] == 0, what
+                        continue
+                    row = int(p.rows_before["minus" if w["strand"] else "plus"][w["contig"]]) + w["index"] | w["strand"] << 31
+                    tie = ((w["cut"] + p.offsets[w["contig"]]) << 1 | w["strand"]) & 0xFFFFFFFF
+                    got = (int(best["gain"][f]), int(best["key"][f]), int(best["cover"][f]), int(g[int(best["gene"][f])]), int(best["row"][f]),
+                           int(best["tie"][f]))
+                    assert got == (w["gain"], w["key"], w["cover"], w["gene"], row, tie), what
+            if slice_rows:
+                assert h.family_step_stats()["items"] > len(g)  # the genes of more than 64 rows are cut
+    finally:
+        if h is not None:
+            h.close()
+        for x in handles:
+            x.close()

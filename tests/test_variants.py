@@ -3,11 +3,9 @@ The definition is restated twice in tests/variant_reference.py; the inputs come 
 selection tests from tests/select_coding_cases.py, the selection's own definition from tests/select_reference.py,
 tests/select_pairs_reference.py and tests/select_coding_reference.py (imported, not edited).
 
-Predicate kernels of DESIGN sections 20-24 and what checks them here: the coding kernel (section 20) in
-test_gpu_coding_selection_honours_the_limits.  NOT checked here, because their references need the coding model's edit
-windows or a joined self search with family rows, which would each double this file's fixtures: the edit kernel (21), the
-splice kernel (22), the family kernel (23) and the family step kernel (24).  All four include the same text fragment
-(csrc/crp_select_predicate.inc) and take their tables from the same fill_predicate as the three kernels that are checked."""
+The variant limits under the plain, the pair and the coding kernel are checked here; under every kernel that includes
+csrc/crp_select_predicate.inc -- the edit, splice, family and family step kernels and the spaced selection as well -- in
+tests/test_select_predicate_matrix.py, whose docstring has the table of kernels and terms."""
 import csv
 import ctypes
 import hashlib
