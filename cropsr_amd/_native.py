@@ -250,6 +250,10 @@ SIGNATURES = {
     "crp_variant_counts": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, u32p, u32p]),
     "crp_variant_counts_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_select_set_variant_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
+    "crp_sites_set_enzymes": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64, ctypes.POINTER(ctypes.c_char_p), u32p, u32p, u32p, ctypes.c_uint64]),
+    "crp_site_columns": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, u64p, u64p]),
+    "crp_site_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
+    "crp_select_set_site_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint32]),
     "crp_select_set_pair_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64]),
     "crp_select_run_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "crp_select_fetch_pairs": (ctypes.c_int, [ctypes.c_void_p, u32p, u64p, u32p]),

@@ -268,6 +268,18 @@ def build_parser():
                      help="with --variants: only guides with at most N variants under the seed")
     eng.add_argument("--select-max-pam-variants", default=None, metavar="N",
                      help="with --variants: only guides with at most N variants under the two fixed letters of the PAM")
+    eng.add_argument("--sites", action="store_true",
+                     help="with --select: every row of the selection file ends with guide_sites and assay_enzymes, the restriction enzymes "
+                          "whose recognition site lies inside the guide and those that give a cut-site assay (names joined by ;)")
+    eng.add_argument("--enzymes", default=None, metavar="FILE",
+                     help="with --select: an enzyme set of your own (name<TAB>motif lines, # comments) in place of the built-in 32")
+    eng.add_argument("--select-no-site", default=None, metavar="NAMES",
+                     help="with --select: only guides without a recognition site of these enzymes (comma list; `cloning`: BsaI, BbsI, "
+                          "BsmBI, SapI and AarI of the built-in set)")
+    eng.add_argument("--select-assay", default=None, metavar="NAMES|any",
+                     help="with --select: only guides whose edit can be read by a cut-site assay with one of these enzymes")
+    eng.add_argument("--assay-flank", default=None, metavar="A",
+                     help="with --sites / --select-assay: the amplicon reaches A letters to either side of the cut (default 300)")
     eng.add_argument("--bench-json", metavar="PATH", default=None,
                      help="write stage timings of this run (read, upload+scan, fetch, format+write) as one JSON object")
     return p
@@ -396,6 +408,7 @@ class EngineBackend:
         self.last_specificity = None  # --bench-json: the self-search handles' times of the last --specificity scan
         self.last_properties = None   # --bench-json: the property kernel's time and rows of the last scan that ran it
         self.last_repair = None       # --bench-json: the repair kernel's time, rows and flank of the last scan that ran it
+        self.last_sites = None        # --bench-json: the site kernels' times, rows, enzymes, flank and bytes of the last scan that ran them
         self.last_variants = None     # --bench-json: the variant kernel's time, rows, seed and track size of the last scan that ran it
 
     def connect(self):
@@ -471,6 +484,7 @@ class EngineBackend:
             self.last_properties = genome.properties_stats
             self.last_repair = genome.repair_stats
             self.last_variants = genome.variant_stats
+            self.last_sites = genome.site_stats
         finally:
             genome.close()
         return out
@@ -1005,6 +1019,66 @@ def variants_request(args, world=1):
     return dict(path=path, samples=samples, pass_only=bool(getattr(args, "variants_pass_only", False)), seed=seed, limits=limits)
 
 
+def sites_request(args, world=1):
+    """--sites, --enzymes, --select-no-site, --select-assay and --assay-flank, checked like the other opt-in steps, before any
+    side effect: None without them, else dict(fields -- print the two fields --, limits -- the keywords of select.Request).  The
+    enzyme file is read here."""
+    opts = (("--sites", "sites", False), ("--enzymes", "enzymes", None), ("--select-no-site", "select_no_site", None),
+            ("--select-assay", "select_assay", None), ("--assay-flank", "assay_flank", None))
+    given = [o for o, k, unset in opts if getattr(args, k, unset) not in (unset, None)]
+    if not given:
+        return None
+
+    def refuse(msg):
+        sys.exit("cropsr_amd: %s: %s" % (given[0], msg))
+
+    from . import sites
+    if not 1 <= args.l <= sites.MAX_GUIDE:
+        refuse("a guide of 1..%d letters has a window, not -l %d" % (sites.MAX_GUIDE, args.l))
+    if getattr(args, "select", None) is None:
+        refuse("the enzymes are printed in the selection file and bound the selection: %s belongs to --select" % given[0])
+    if len(_device_list(args)) > 1:
+        refuse("the site column is not gathered: one GPU, and --devices names %d" % len(_device_list(args)))
+    if getattr(args, "gpus", 1) > 1:
+        refuse("the site column is not gathered: one GPU, drop --gpus %d" % args.gpus)
+    if world > 1:
+        refuse("the site column is not gathered: one GPU, and a launcher started %d ranks" % world)
+    path = getattr(args, "enzymes", None)
+    if path is None:
+        enzymes = sites.EnzymeSet()
+    else:
+        import os
+        if not os.path.isfile(path):
+            sys.exit("cropsr_amd: --enzymes: no such file: %s" % path)
+        try:
+            enzymes = sites.load(path)
+        except (ValueError, OSError, UnicodeDecodeError) as e:
+            sys.exit("cropsr_amd: --enzymes: %s: %s" % (path, e))
+    masks = {}
+    for opt, key, kw in (("--select-no-site", "select_no_site", "forbid_sites"), ("--select-assay", "select_assay", "need_assay")):
+        text = getattr(args, key, None)
+        if text is None:
+            continue
+        names = [t.strip() for t in str(text).split(",")]
+        if not all(names) or (kw == "forbid_sites" and "any" in [n.lower() for n in names]) or \
+                (kw == "need_assay" and "cloning" in [n.lower() for n in names]):
+            sys.exit("cropsr_amd: %s: a comma-separated list of enzyme names%s, not %r" % (opt, " or `any`" if kw == "need_assay" else " or `cloning`", text))
+        try:
+            masks[kw] = enzymes.mask(names)
+        except ValueError as e:
+            sys.exit("cropsr_amd: %s: %s" % (opt, e))
+    flank = getattr(args, "assay_flank", None)
+    t = None if flank is None else str(flank).strip()
+    if t is not None and not (t.isascii() and t.isdigit()):
+        sys.exit("cropsr_amd: --assay-flank: a number of letters %d..%d, not %s" % (enzymes.m_max, sites.MAX_FLANK, flank))
+    try:
+        flank = enzymes.check_flank(None if t is None else int(t))
+    except ValueError as e:
+        sys.exit("cropsr_amd: --assay-flank: %s" % e)
+    fields = bool(getattr(args, "sites", False))
+    return dict(fields=fields, names=list(enzymes.names), limits=dict(enzymes=enzymes, assay_flank=flank, site_fields=fields, **masks))
+
+
 def properties_request(args, world=1):
     """--properties, checked like the other opt-in steps, before any side effect: True with it, False without."""
     if not getattr(args, "properties", False):
@@ -1046,7 +1120,7 @@ def _table_fields(sel_rows, names, strings, all_hits, guide_len, annotation):
 
 
 def write_selection(path, selection, names, strings, all_hits, guide_len, offtarget, spec_M, annotation, properties=False,
-                    repair_scores=False, coding=False, base_edit=False, splice_edit=False, families=None, variants=False):
+                    repair_scores=False, coding=False, base_edit=False, splice_edit=False, families=None, variants=False, sites=None):
     """The selection file: a header, then per chosen row gene, rank (1-based), passing and the main table's own fields
     for that row as rows.ContigRows builds them, without crispr_id (those ids are random per run).  Genes in GFF order;
     genes with nothing selected are left out.  Python's csv module in the main table's dialect: the file is small.
@@ -1056,8 +1130,11 @@ def write_selection(path, selection, names, strings, all_hits, guide_len, offtar
     splice_edit: four more after those, splice_targets, splice_sites, donor_percent and acceptor_percent (baseedit.splice_fields).
     families (families.FamilyTable): seven more after those, family, family_size, members_hit, members (the covered members'
     labels, ;-joined, GFF order), outside_mm0, outside_hit_sum and outside_specificity (FAMILY_HEADER).
-    variants: four more after everything else, var_site, var_guide, var_seed and var_pam (variants.fields) of selection.variants."""
+    variants: four more after everything else, var_site, var_guide, var_seed and var_pam (variants.fields) of selection.variants.
+    sites (the enzyme set's names): two more after the variant fields, guide_sites and assay_enzymes (sites.fields) of
+    selection.guide_sites / .assay_enzymes."""
     import csv
+    from . import sites as site
     from . import variants as var
     from . import baseedit
     from . import coding as cod
@@ -1069,7 +1146,8 @@ def write_selection(path, selection, names, strings, all_hits, guide_len, offtar
         w.writerow(["gene", "rank", "passing"] + rows.HEADER[1:] + rows.extra_header(offtarget, spec_M, properties)
                    + (repair.HEADER if repair_scores else []) + (cod.HEADER if coding else [])
                    + (baseedit.HEADER if base_edit else []) + (baseedit.SPLICE_HEADER if splice_edit else [])
-                   + (FAMILY_HEADER if families is not None else []) + (var.HEADER if variants else []))
+                   + (FAMILY_HEADER if families is not None else []) + (var.HEADER if variants else [])
+                   + (site.HEADER if sites is not None else []))
         for at, (r, rest) in enumerate(zip(sel_rows, fields)):
             more = repair.fields(repair.pack(selection.mh[at], selection.oof[at])) if repair_scores else ()
             if coding:
@@ -1083,6 +1161,8 @@ def write_selection(path, selection, names, strings, all_hits, guide_len, offtar
                 more = tuple(more) + family_fields(families, selection, at)
             if variants:
                 more = tuple(more) + var.fields(selection.variants[at])
+            if sites is not None:
+                more = tuple(more) + site.fields(int(selection.guide_sites[at]) | int(selection.assay_enzymes[at]) << 32, sites)
             w.writerow((selection.labels[int(r["gene"])], int(r["rank"]), int(selection.n_pass[int(r["gene"])])) + tuple(rest) + tuple(more))
 
 
@@ -1233,6 +1313,7 @@ def run(args, backend=None, out=sys.stdout, group=None):
     selecting = select_request(args, spec, 1 if group is None else group.world)
     with_properties = properties_request(args, 1 if group is None else group.world)
     varying = variants_request(args, 1 if group is None else group.world)
+    siting = sites_request(args, 1 if group is None else group.world)
     finalize = getattr(args, "score_finalize", "gpu")
     stages = {}  # --bench-json
     variant_set = None
@@ -1261,6 +1342,7 @@ def run(args, backend=None, out=sys.stdout, group=None):
     if group is not None and group.world > 1:
         properties_request(args, group.world)
         variants_request(args, group.world)
+        sites_request(args, group.world)
     one_gpu = spec is not None or selecting is not None or with_properties  # the opt-in steps that take the arena path on one device
 
     def make_backend():
@@ -1419,6 +1501,8 @@ def run(args, backend=None, out=sys.stdout, group=None):
             print("cropsr_amd: --variants: %d CHROMs of %s name no contig of %s" % (len(unknown), varying["path"], args.f), file=sys.stderr)
         selecting["limits"].update(variants=variants.Request(variant_set, request.names, request.dec), variant_seed=varying["seed"],
                                    **varying["limits"])
+    if siting is not None:
+        selecting["limits"].update(siting["limits"])
     select_only = selecting is not None and selecting["only"]
     if not select_only:
         rows.write_header(args.o, offtarget=offtarget, specificity=None if spec is None else spec["max_mm"],
@@ -1481,7 +1565,8 @@ def run(args, backend=None, out=sys.stdout, group=None):
         write_selection(selecting["output"], selection, names, strings, all_hits, args.l, offtarget, None if spec is None else spec["max_mm"],
                         request.annotation if annotating else None, properties=with_properties, repair_scores=selecting["repair_scores"],
                         coding=selecting["coding"], base_edit=selecting["base_edit"], splice_edit=selecting["splice_edit"],
-                        families=selecting["limits"].get("families"), variants=varying is not None)
+                        families=selecting["limits"].get("families"), variants=varying is not None,
+                        sites=siting["names"] if siting is not None and siting["fields"] else None)
         stages["select"] = dict(selection.stats, write_s=time.perf_counter() - t_select, genes=len(selection.labels),
                                 rows_selected=int(selection.rows.size), k=selecting["params"].k)
         if selecting["family_sets"] is not None:
@@ -1610,6 +1695,8 @@ def run(args, backend=None, out=sys.stdout, group=None):
         stages["properties"] = backend.last_properties
     if getattr(backend, "last_repair", None):  # --repair-scores / --select-min-oof / --select-min-mh: the repair kernel's time and rows
         stages["repair"] = backend.last_repair
+    if getattr(backend, "last_sites", None):  # --sites / --select-no-site / --select-assay: plane build, rank build and column kernel
+        stages["sites"] = backend.last_sites
     if getattr(backend, "last_variants", None):  # --variants: the VCF's parse time and counts, the track's size, the kernel's time and rows
         stages["variants"] = dict(stages.get("variants", {}), **backend.last_variants)
     if getattr(backend, "last_specificity", None):  # --specificity: the handles' kernel times, the join's among them
@@ -1657,6 +1744,7 @@ def main(argv=None):
     select_request(args, specificity_request(args))  # (--gpus N: refused here, before any rank is started)
     properties_request(args)
     variants_request(args)
+    sites_request(args)
     if launch.wanted(getattr(args, "gpus", 1)):
         # no launcher in the environment: this process (which never touches the GPU) starts the ranks as fresh
         # children of the same command line and leaves with their status (cropsr_amd/launch.py)

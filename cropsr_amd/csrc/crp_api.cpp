@@ -470,6 +470,16 @@ int crp_arena_destroy(crp_arena *a)
     }
     for (hipEvent_t e : a->ev_variants)
         if (e) (void)hipEventDestroy(e);
+    (void)hipFree(a->d_site_occ);
+    (void)hipFree(a->d_site_rank);
+    (void)hipFree(a->d_site_chunk);
+    (void)hipFree(a->d_site_enz);
+    for (int s = 0; s < 2; ++s) {
+        (void)hipFree(a->d_site_text[s]);
+        (void)hipFree(a->d_sites[s]);
+    }
+    for (hipEvent_t e : a->ev_sites)
+        if (e) (void)hipEventDestroy(e);
     delete a;
     return CRP_OK;
 }
@@ -903,6 +913,7 @@ int arena_reset(crp_arena *a)
     a->sealed = false;
     a->have_hits = a->have_pre = a->have_raw = a->have_feat = a->have_props = a->have_repair = a->have_track = false;
     a->have_variants = a->have_var_track = false;
+    a->have_sites = a->have_site_col = false;
     a->n_hits[0] = a->n_hits[1] = 0;
     a->scan_pending = 0;
     a->ot_epoch = 0;
@@ -935,6 +946,7 @@ int scan_begin(crp_arena *a, int guide_len, int flags)
     a->have_props = false;
     a->have_repair = false;
     a->have_variants = false;
+    a->have_site_col = false;
     a->scan_pending = 0;
     a->pend_guide_len = guide_len;
     a->pend_flags = flags;

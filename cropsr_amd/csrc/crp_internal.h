@@ -12,6 +12,9 @@
 #include "crp_kernels.h"
 
 struct crp_comm;  // crp_comm.cpp: the RCCL communicator and its scratch
+namespace crp {
+struct SiteEnzyme;  // crp_sites.h
+}
 
 struct crp_ctx {
     int device = -1;
@@ -143,6 +146,26 @@ struct crp_arena {
     hipEvent_t ev_variants[2] = {nullptr, nullptr};
     double variants_ms = 0;  // the kernel of the last crp_variant_counts (HIP events)
     int variants_seed = 0;   // its seed length
+    // restriction sites (crp_sites.hip): per enzyme of the arena's set an occurrence plane over the sealed text and its rank
+    // index -- they outlive re-scans, like the variant track -- and in_guide | assay << 32 per hit of the last crp_site_columns
+    unsigned long long *d_site_occ = nullptr;  // n_site_enzymes planes of site_words words
+    uint32_t *d_site_rank = nullptr;           // n_site_enzymes rows of site_words + 1 values
+    uint32_t *d_site_chunk = nullptr;          // the rank build's chunk sums
+    uint64_t site_index_bytes = 0;             // of the three
+    uint64_t site_alloc_enzymes = 0, site_alloc_words = 0;  // what the three were allocated for: reused only for the same pair
+    crp::SiteEnzyme *d_site_enz = nullptr;
+    uint64_t site_enz_cap = 0;
+    uint32_t *d_site_text[2] = {nullptr, nullptr};  // text starts and ends, ascending
+    uint64_t site_text_cap[2] = {0, 0};
+    uint32_t n_site_enzymes = 0, site_m_max = 0, n_site_texts = 0;
+    uint64_t site_words = 0;
+    bool have_sites = false;  // planes and ranks belong to the sealed text (cleared by a reset)
+    uint64_t *d_sites[2] = {nullptr, nullptr};  // same order as the hit tables
+    uint64_t sites_cap[2] = {0, 0};
+    bool have_site_col = false;  // d_sites belongs to the current tables and the current set (cleared by the next scan and by a new set)
+    hipEvent_t ev_sites[4] = {nullptr, nullptr, nullptr, nullptr};
+    double site_ms[3] = {0, 0, 0};  // plane build, rank build, column kernel (HIP events)
+    int site_flank = 0;             // of the last crp_site_columns
 };
 
 #define CRP_HIP(ctx, call)                                                              \

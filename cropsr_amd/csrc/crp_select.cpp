@@ -44,6 +44,8 @@ struct crp_select {
     crp_select_repair_limits repair_limits = {};
     bool have_variant_limits = false;
     crp_select_variant_limits variant_limits = {};
+    bool have_site_limits = false;
+    uint32_t forbid_sites = 0, need_assay = 0;
     hipEvent_t ev[2] = {nullptr, nullptr};
     double stats[9] = {};
     // guide pairs: buffers and results of crp_select_run_pairs, apart from the selection's
@@ -152,6 +154,8 @@ int check_run(crp_select *s, const crp_select_params *p, crp_search_self *self, 
         return fail(ctx, CRP_ERR_STATE, who + ": repair limits need the column of a crp_repair_scores on the current tables");
     if (s->have_variant_limits && !a->have_variants)
         return fail(ctx, CRP_ERR_STATE, who + ": variant limits need the column of a crp_variant_counts on the current tables");
+    if (s->have_site_limits && !a->have_site_col)
+        return fail(ctx, CRP_ERR_STATE, who + ": site limits need the column of a crp_site_columns on the current tables");
     if (self) {
         if (!crp::self_joined(self, joined))
             return fail(ctx, CRP_ERR_STATE, who + ": the self-search handle has no joined columns (crp_search_self_join_hits)");
@@ -171,7 +175,8 @@ void fill_predicate(const crp_select *s, const crp_select_params *p, bool with_s
         tab[t] = crp::SelectTable{a->d_pos[t], a->d_score[t], p->require_cds ? a->d_feat[t] : nullptr, with_self ? joined.counts[t] : nullptr,
                                   with_self ? joined.sum[t] : nullptr, s->have_prop_limits ? a->d_props[t] : nullptr,
                                   s->have_repair_limits ? reinterpret_cast<const unsigned long long *>(a->d_repair[t]) : nullptr, (uint32_t)a->n_hits[t],
-                                  s->have_variant_limits ? a->d_variants[t] : nullptr};
+                                  s->have_variant_limits ? a->d_variants[t] : nullptr,
+                                  s->have_site_limits ? reinterpret_cast<const unsigned long long *>(a->d_sites[t]) : nullptr};
     crp::SelectPredicate pred = {};
     pred.min_score = p->min_score;
     pred.max_hit_sum = p->max_hit_sum;
@@ -191,6 +196,8 @@ void fill_predicate(const crp_select *s, const crp_select_params *p, bool with_s
     pred.max_var_guide = s->variant_limits.max_guide;
     pred.max_var_seed = s->variant_limits.max_seed;
     pred.max_var_pam = s->variant_limits.max_pam;
+    pred.forbid_sites = s->forbid_sites;
+    pred.need_assay = s->need_assay;
     *pred_out = pred;
 }
 
@@ -348,6 +355,15 @@ int crp_select_set_variant_limits(crp_select *s, const crp_select_variant_limits
     if (!s) return CRP_ERR_INVALID;
     s->have_variant_limits = limits != nullptr;
     s->variant_limits = limits ? *limits : crp_select_variant_limits{};
+    return CRP_OK;
+}
+
+int crp_select_set_site_limits(crp_select *s, uint32_t forbid_mask, uint32_t need_mask)
+{
+    if (!s) return CRP_ERR_INVALID;
+    s->have_site_limits = forbid_mask != 0 || need_mask != 0;
+    s->forbid_sites = forbid_mask;
+    s->need_assay = need_mask;
     return CRP_OK;
 }
 
@@ -510,7 +526,7 @@ int crp_select_run(crp_select *s, const crp_select_params *p, crp_search_self *s
     // position + score, the label-set id under require_cds, with joined columns counts[0] and hit_sum, and the packed
     // properties under property limits, and the repair scores under repair limits
     s->stats[7] = 12.0 + (p->require_cds ? 4.0 : 0.0) + (self ? 12.0 : 0.0) + (s->have_prop_limits ? 4.0 : 0.0) + (s->have_repair_limits ? 8.0 : 0.0) +
-                  (s->have_variant_limits ? 4.0 : 0.0);
+                  (s->have_variant_limits ? 4.0 : 0.0) + (s->have_site_limits ? 8.0 : 0.0);
     s->stats[8] = (double)merges.size();
     s->k = k;
     return CRP_OK;
@@ -1244,7 +1260,7 @@ int crp_select_family_step(crp_select *s, const crp_select_params *p, crp_search
     s->set_stats[3] = (double)s->set_rows;
     // the selection's columns (crp_select_stats) and, per row, site_family, fam_cover, fam_counts[0] and fam_sum
     s->set_stats[4] = 24.0 + (p->require_cds ? 4.0 : 0.0) + (s->have_prop_limits ? 4.0 : 0.0) + (s->have_repair_limits ? 8.0 : 0.0) +
-                      (s->have_variant_limits ? 4.0 : 0.0) + 24.0;
+                      (s->have_variant_limits ? 4.0 : 0.0) + (s->have_site_limits ? 8.0 : 0.0) + 24.0;
     if (!n_families) return CRP_OK;
     rc = crp::staged_h2d(ctx, s->d_set_covered, covered, n_families * sizeof(uint64_t));
     if (rc != CRP_OK) return rc;

@@ -21,6 +21,7 @@ struct SelectTable {
     const unsigned long long *repair;  // mh | oof << 32 of crp_repair_scores (repair limits)
     uint32_t n;
     const uint32_t *variants;          // packed variant counts of crp_variant_counts (variant limits)
+    const unsigned long long *sites;   // in_guide | assay << 32 of crp_site_columns (site limits)
 };
 
 struct SelectPredicate {
@@ -37,6 +38,8 @@ struct SelectPredicate {
     uint32_t min_mh, min_oof_pct;
     // with SelectTable::variants: site <= max_var_site, guide <= max_var_guide, seed <= max_var_seed, pam <= max_var_pam (each one byte)
     uint32_t max_var_site, max_var_guide, max_var_seed, max_var_pam;
+    // with SelectTable::sites: no enzyme of forbid_sites inside the guide, and -- need_assay != 0 -- an assay with one of need_assay's
+    uint32_t forbid_sites, need_assay;
 };
 
 // One wave's work: rows [first[s], first[s] + rows[s]) of strand s's table, all inside gene `gene`'s runs.  slot ==

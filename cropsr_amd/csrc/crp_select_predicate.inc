@@ -35,3 +35,7 @@
                 pass = pass && (vr & 255u) <= pred.max_var_site && (vr >> 8 & 255u) <= pred.max_var_guide && (vr >> 16 & 255u) <= pred.max_var_seed &&
                        vr >> 24 <= pred.max_var_pam;
             }
+            if (t.sites) {  // (the value of crp_site_columns: in_guide | assay << 32, one bit per enzyme)
+                const unsigned long long st = in ? t.sites[row] : 0ull;
+                pass = pass && !((uint32_t)st & pred.forbid_sites) && (!pred.need_assay || ((uint32_t)(st >> 32) & pred.need_assay));
+            }

@@ -75,6 +75,7 @@ class Arena:
         self.offsets = offsets
         self.lengths = lengths
         self.guide_len = None  # of the last scan_score_device()
+        self.site_set = None  # the motifs of the last set_enzymes()
 
     def close(self):
         if self._h:
@@ -236,6 +237,42 @@ class Arena:
         out = np.zeros(5, dtype=np.float64)
         nat.check(nat.lib().crp_variant_counts_stats(self._h, out.ctypes.data_as(nat.f64p), 5), "crp_variant_counts_stats", self._engine._ctx)
         return dict(kernel_ms=float(out[0]), rows=int(out[1]), guide_len=int(out[2]), seed=int(out[3]), variants=int(out[4]))
+
+    # ---- restriction sites (opt-in; sites.py has the definition)
+    def set_enzymes(self, enzymes, text_bounds=None):
+        """The arena's enzyme set (sites.EnzymeSet, or an iterable of motifs): builds the occurrence planes and the rank
+        index over the sealed text on the GPU; they outlive re-scans.  text_bounds: (starts, ends) of the arena's texts,
+        ascending arena positions (None: offsets and lengths of the arena's contigs)."""
+        import ctypes as ct
+        motifs = [m.encode("ascii", "replace") if isinstance(m, str) else bytes(m) for m in getattr(enzymes, "motifs", enzymes)]
+        self.site_set = None  # (a refused set leaves the arena without one the genome level knows)
+        arr = (ct.c_char_p * max(len(motifs), 1))(*motifs)
+        lens = np.array([len(m) for m in motifs], dtype=np.uint32)
+        if text_bounds is None:
+            starts = np.asarray(self.offsets, dtype=np.int64)
+            text_bounds = (starts, starts + np.asarray(self.lengths, dtype=np.int64))
+        starts = np.ascontiguousarray(text_bounds[0], dtype=np.uint32)
+        ends = np.ascontiguousarray(text_bounds[1], dtype=np.uint32)
+        if starts.shape != ends.shape or starts.ndim != 1:
+            raise ValueError("text starts and ends must be 1-d arrays of one length")
+        nat.check(nat.lib().crp_sites_set_enzymes(self._h, len(motifs), arr, lens.ctypes.data_as(nat.u32p), starts.ctypes.data_as(nat.u32p),
+                                                  ends.ctypes.data_as(nat.u32p), starts.size), "crp_sites_set_enzymes", self._engine._ctx)
+        self.site_set = tuple(m.decode("ascii", "replace") for m in motifs)
+
+    def site_columns(self, n_plus, n_minus, flank=300, fetch=True):
+        """in_guide | assay << 32 (sites.unpack) of every kept hit of the last scan against the arena's enzyme set, with
+        amplicon half-width `flank`; fetch=False leaves the column in HBM (for a selection's site limits)."""
+        pair = [np.empty(n, dtype=np.uint64) for n in (n_plus, n_minus)] if fetch else [None, None]
+        nat.check(nat.lib().crp_site_columns(self._h, int(flank), *[None if a is None else a.ctypes.data_as(nat.u64p) for a in pair]),
+                  "crp_site_columns", self._engine._ctx)
+        return tuple(pair) if fetch else None
+
+    def site_stats(self):
+        """dict(planes_ms, rank_ms, kernel_ms, rows, enzymes, flank, bytes) of the arena's enzyme set and its last site_columns()."""
+        out = np.zeros(7, dtype=np.float64)
+        nat.check(nat.lib().crp_site_stats(self._h, out.ctypes.data_as(nat.f64p), 7), "crp_site_stats", self._engine._ctx)
+        return dict(planes_ms=float(out[0]), rank_ms=float(out[1]), kernel_ms=float(out[2]), rows=int(out[3]), enzymes=int(out[4]),
+                    flank=int(out[5]), bytes=int(out[6]))
 
     # ---- off-target seed scan (opt-in; include/cropsr_hip.h)
     def offtarget_add(self, guide_len=20, own_ranges=None):
@@ -738,6 +775,7 @@ class Genome:
         self.properties_stats = None  # dict(kernel_ms, rows, wall_s) of the last guide_properties()
         self.repair_stats = None  # dict(kernel_ms, rows, flank, wall_s) of the last repair_scores()
         self.variant_stats = None  # dict(kernel_ms, rows, seed, variants, track_s, wall_s) of the last variant_counts()
+        self.site_stats = None  # dict(planes_ms, rank_ms, kernel_ms, rows, enzymes, flank, bytes, wall_s) of the last site_columns()
         self._where = {}
         for a, g in enumerate(groups):
             for j, k in enumerate(g):
@@ -804,6 +842,27 @@ class Genome:
         self.variant_stats = dict(kernel_ms=ms, rows=n_rows, seed=used, variants=n_var, track_s=track_s, wall_s=time.perf_counter() - t0)
         return out if fetch else None
 
+    def site_columns(self, enzymes, counts, flank=None, fetch=True):
+        """The restriction-site masks over every arena's resident tables (enzymes: sites.EnzymeSet; counts: (n_plus, n_minus)
+        per arena; flank: the amplicon half-width, None: sites.DEFAULT_FLANK).  The planes and ranks of an arena are built
+        when its set is another one -- the texts' bounds are the arena's own offsets and lengths, which are the piece
+        layout's -- and kept across scans.  Returns [(sites_plus,
+        sites_minus)] per arena, packed (sites.unpack), or None with fetch=False (the columns stay in HBM)."""
+        import time
+        t0 = time.perf_counter()
+        flank = enzymes.check_flank(flank)
+        key = tuple(enzymes.motifs)
+        out, tot = [], dict(planes_ms=0.0, rank_ms=0.0, kernel_ms=0.0, rows=0, bytes=0)
+        for a, (n_plus, n_minus) in zip(self.arenas, counts):
+            if a.site_set != key:
+                a.set_enzymes(enzymes)
+            out.append(a.site_columns(n_plus, n_minus, flank, fetch=fetch))
+            st = a.site_stats()
+            for k in tot:
+                tot[k] += st[k]
+        self.site_stats = dict(tot, enzymes=len(enzymes), flank=flank, wall_s=time.perf_counter() - t0)
+        return out if fetch else None
+
     def specificity_columns(self, guide_len=20, max_mm=3, candidate_pam="NRG", score="hsu2013", budget=None, families=None,
                             family_cover_mm=0, family_limits=None):
         """The genome-wide specificity of every hit of the last scan at guide_len, joined on the GPU
@@ -814,7 +873,7 @@ class Genome:
                                           families=families, family_cover_mm=family_cover_mm, family_limits=family_limits)
 
     def select(self, request, hits, counts=None, handle_of=None, joined=None, annotated=False, repair=None, family_joined=None,
-               variants=None):
+               variants=None, sites=None):
         """The best K guides of every gene (select.Request; the module's docstring has the definition) over the tables
         of the last scan at guide length 20, which `hits` (GenomeHits) holds as host copies.  Runs after the annotation
         look-up and -- with handle_of(arena index) -> the arena's joined search.ArenaSelfSearch and joined[arena index] =
@@ -824,6 +883,8 @@ class Genome:
         oof of its rows.  A request with repair limits needs the columns resident (repair_scores(fetch=False) is enough).
         variants: per arena (var_plus, var_minus), the fetched columns of variant_counts(): the Selection carries the packed
         counts of its rows.  A request with variant limits needs the columns resident (variant_counts(fetch=False) is enough).
+        sites: per arena (sites_plus, sites_minus), the fetched columns of site_columns(): the Selection carries the two masks
+        of its rows.  A request with site limits needs the columns resident (site_columns(fetch=False) is enough).
         Returns select.Selection: for every gene of the GFF in file order its label, n_in, n_pass and the selected rows
         (contig, position, strand, score, and the joined counts and sum when present); with request.pairs also the best pairs
         of every gene (Selection.pairs, n_pairs), selected right after the single guides while the same columns are resident."""
@@ -852,6 +913,8 @@ class Genome:
                 part["repair_plus"], part["repair_minus"] = repair[a]
             if variants is not None:
                 part["var_plus"], part["var_minus"] = variants[a]
+            if sites is not None:
+                part["sites_plus"], part["sites_minus"] = sites[a]
             if "coding" in extras:
                 part["coding"] = extras["coding"]
             if "edit" in extras:
@@ -895,7 +958,9 @@ class Genome:
         A select.Request with repair limits or a repair flank runs the kernel too, right before the selection -- after the
         scan, or inside the specificity join's after_join hook --; with limits alone the column stays on the device.
         A select.Request with variants runs the variant count kernel right after the scan (hits.variants: per ARENA the packed
-        (var_plus, var_minus), variants.unpack); its variant limits hold in every selection that follows."""
+        (var_plus, var_minus), variants.unpack); its variant limits hold in every selection that follows.
+        A select.Request with enzymes runs the restriction-site kernel right before the selection, in the same two places as
+        the repair kernel (hits.sites: per ARENA the packed (sites_plus, sites_minus), sites.unpack)."""
         from .repair import check_flank
         want_repair = repair is not None or (select is not None and select.runs_repair)
         if repair is not None:
@@ -928,6 +993,11 @@ class Genome:
             if fetch:
                 hits.repair = cols
 
+        def run_sites():
+            if select is not None and getattr(select, "enzymes", None) is not None:
+                hits.sites = self.site_columns(select.enzymes, [(h.n_plus, h.n_minus) for h in hits.per_arena], flank=select.assay_flank,
+                                               fetch=select.site_fields)
+
         if want_repair and select is None:
             run_repair()
         if specificity is not None:  # (the tables of an arena stay valid until its next scan)
@@ -944,14 +1014,18 @@ class Genome:
                     if len(handles) == len(self.arenas):  # every arena has joined, no handle has closed yet
                         if want_repair:
                             run_repair()
+                        run_sites()
                         hits.selection = self.select(select, hits, handle_of=handles.get, joined=joined, annotated=annotation is not None,
-                                                     repair=hits.repair, family_joined=family_cols or None, variants=hits.variants)
+                                                     repair=hits.repair, family_joined=family_cols or None, variants=hits.variants,
+                                                     sites=hits.sites)
 
                 hits.columns = search.specificity_columns(self, guide_len, after_join=after_join, **specificity)
         elif select is not None:
             if want_repair:
                 run_repair()
-            hits.selection = self.select(select, hits, annotated=annotation is not None, repair=hits.repair, variants=hits.variants)
+            run_sites()
+            hits.selection = self.select(select, hits, annotated=annotation is not None, repair=hits.repair, variants=hits.variants,
+                                         sites=hits.sites)
         return hits
 
     def _scan_score(self, guide_len, want_pre, offtarget, seeds_from_scan, annotation):
@@ -1016,6 +1090,7 @@ class GenomeHits:
         self.selection = None  # select.Selection (Genome.scan_score(select=..))
         self.repair = None  # per arena (repair_plus, repair_minus), packed (Genome.scan_score(repair=F))
         self.variants = None  # per arena (var_plus, var_minus), packed (a select.Request with variants)
+        self.sites = None  # per arena (sites_plus, sites_minus), packed (a select.Request with enzymes)
 
     def contig(self, k):
         a, j = self._genome._where[k]

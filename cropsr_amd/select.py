@@ -261,6 +261,12 @@ class Request:
     (Selection.variants).  max_variants / max_guide_variants / max_seed_variants / max_pam_variants (variants.Limits) are
     limits on the site, guide, seed and PAM counts: a row passes only if all hold, in every selection the request runs --
     single guides, pairs, coding, edit, splice, family limits and family sets.  They need variants.
+    enzymes (sites.EnzymeSet): the scan runs the restriction-site kernel (sites.py) right before the selection, with amplicon
+    half-width assay_flank (None: 300), and the Selection carries the two masks of its rows (Selection.guide_sites,
+    Selection.assay_enzymes).  forbid_sites / need_assay (masks over the set, or lists of names for EnzymeSet.mask) are limits: a
+    row passes only if no enzyme of forbid_sites lies inside its guide and -- need_assay given -- it has an assay with one of
+    need_assay's, in every selection the request runs.  They need enzymes.  site_fields: whether the Selection carries the masks
+    (None: only a request without limits; with limits alone the column stays on the device, like the repair column).
     min_spacing (D, 0..2^31 - 1): the guides of a gene cut at least D letters apart (the module's text has the definition): the
     scan runs the plain selection, which supplies n_in and n_pass, and then the spaced selection, whose rows the Selection
     carries in pick order.  The per-pick fields (coding, edit, splice, families) are those of the spaced picks; pairs and
@@ -271,6 +277,7 @@ class Request:
                  edit_window=None, edit_limits=None, editor=None, splice_limits=None, edit=None, families=None, family_cover_mm=0,
                  min_members=None, max_perfect_outside=None, min_specificity_outside=None, family_sets=None, variants=None,
                  variant_seed=None, max_variants=None, max_guide_variants=None, max_seed_variants=None, max_pam_variants=None,
+                 enzymes=None, assay_flank=None, forbid_sites=None, need_assay=None, site_fields=None,
                  min_spacing=None):
         self.min_spacing = None
         if min_spacing is not None:
@@ -281,6 +288,22 @@ class Request:
                 if given is not None:
                     raise ValueError("%s limits are relative to the gene; the spaced selection's eligibility is per table row: one or the other" % name)
             self.min_spacing = int(min_spacing)
+        self.enzymes, self.assay_flank, self.site_limits = enzymes, None, None
+        if enzymes is None:
+            if any(v is not None for v in (assay_flank, forbid_sites, need_assay)):
+                raise ValueError("assay_flank, forbid_sites and need_assay need an enzyme set (enzymes=)")
+        else:
+            self.assay_flank = enzymes.check_flank(assay_flank)
+            masks = []
+            for name, v in (("forbid_sites", forbid_sites), ("need_assay", need_assay)):
+                m = 0 if v is None else (int(v) if isinstance(v, (int, np.integer)) else enzymes.mask(v))
+                if not 0 <= m < 1 << len(enzymes):
+                    raise ValueError("%s is a mask over the set's %d enzymes, not %r" % (name, len(enzymes), v))
+                masks.append(m)
+            if any(masks):
+                self.site_limits = tuple(masks)
+        # the column comes to the host (Selection.guide_sites / assay_enzymes) unless it only bounds the selection
+        self.site_fields = enzymes is not None and (self.site_limits is None if site_fields is None else bool(site_fields))
         self.variants, self.variant_seed, self.variant_limits = variants, variant_seed, None
         if any(v is not None for v in (max_variants, max_guide_variants, max_seed_variants, max_pam_variants)):
             if variants is None:
@@ -388,6 +411,11 @@ class ArenaSelect:
         """limits: repair.Limits, or None to clear them."""
         lim = None if limits is None else ctypes.byref(nat.SelectRepairLimits(*limits.astuple()))
         nat.check(nat.lib().crp_select_set_repair_limits(self._h, lim), "crp_select_set_repair_limits", self._ctx)
+
+    def set_site_limits(self, limits):
+        """limits: (forbid_sites, need_assay) masks over the arena's enzyme set, or None to clear them."""
+        forbid, need = (0, 0) if limits is None else limits
+        nat.check(nat.lib().crp_select_set_site_limits(self._h, int(forbid), int(need)), "crp_select_set_site_limits", self._ctx)
 
     def set_variant_limits(self, limits):
         """limits: variants.Limits, or None to clear them."""
@@ -653,6 +681,7 @@ class Selection:
         self.counts, self.hit_sum, self.stats = counts, hit_sum, stats or {}
         self.mh, self.oof = mh, oof
         self.variants = None  # (n,) uint32, packed (variants.unpack), of the rows when the variant counts were fetched
+        self.guide_sites = self.assay_enzymes = None  # (n,) uint32 masks (sites.unpack) of the rows when the site column was fetched
         self.pairs = self.n_pairs = self.pairs_repair = None
         self.pairs_stats = {}
         self.cds_offset = self.cds_length = self.transcripts_cut = self.transcripts = None
@@ -695,6 +724,8 @@ def assemble(labels, k, arenas, stats=None):
     repaired = any(a.get("repair_plus") is not None for a in arenas)
     varied = any(a.get("var_plus") is not None for a in arenas)
     vparts = []
+    sited = any(a.get("sites_plus") is not None for a in arenas)
+    stparts = []
     coded = any(a.get("coding") is not None for a in arenas)
     edited = any(a.get("edit") is not None for a in arenas)
     spliced = any(a.get("splice") is not None for a in arenas)
@@ -735,6 +766,8 @@ def assemble(labels, k, arenas, stats=None):
             rparts.append(_take(a["repair_plus"], a["repair_minus"], minus, row, np.uint64))
         if varied:
             vparts.append(_take(a["var_plus"], a["var_minus"], minus, row, np.uint32))
+        if sited:
+            stparts.append(_take(a["sites_plus"], a["sites_minus"], minus, row, np.uint64))
         if coded:
             cod = a["coding"]
             kparts.append(np.stack([np.asarray(cod["off"], np.uint32).reshape(gene.size, -1)[r, c],
@@ -777,6 +810,9 @@ def assemble(labels, k, arenas, stats=None):
     out = Selection(list(labels), n_in, n_pass, rows, counts, sums, stats, mh, oof)
     if vparts:
         out.variants = np.concatenate(vparts)[order][keep]
+    if stparts:
+        from .sites import unpack as unpack_sites
+        out.guide_sites, out.assay_enzymes = unpack_sites(np.concatenate(stparts)[order][keep])
     if kparts:
         cod = np.concatenate(kparts)[order][keep]
         out.cds_offset, out.cds_length, out.transcripts_cut, out.transcripts = (cod[:, j].copy() for j in range(4))
@@ -872,6 +908,8 @@ def _set_row_limits(sel, request, flags=None):
         sel.set_repair_limits(request.repair_limits)
     if getattr(request, "variant_limits", None) is not None:
         sel.set_variant_limits(request.variant_limits)
+    if getattr(request, "site_limits", None) is not None:
+        sel.set_site_limits(request.site_limits)
 
 
 def _set_families(sel, request, gene):

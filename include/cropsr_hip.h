@@ -1290,6 +1290,62 @@ typedef struct crp_select_variant_limits {
 } crp_select_variant_limits;
 int crp_select_set_variant_limits(crp_select *select, const crp_select_variant_limits *limits);
 
+/* ---- restriction sites: cloning-safe guides and cut-site assays (opt-in) ------------------ */
+/* Two questions per kept hit about the recognition sequences of a set of restriction enzymes: does one lie inside the
+ * guide (the Golden Gate enzyme of the vector would cut the spacer), and does one span the Cas9 cut while being the only
+ * one of its enzyme in the amplicon around it (an indel destroys it: a PCR / restriction-enzyme assay reads the edit).
+ *
+ * ENZYME SET.  E enzymes, 1 <= E <= 32; enzyme e is bit e of every mask.  An enzyme is a recognition motif M of m
+ * letters, 4 <= m <= 16, over the 15 IUPAC letters ACGTRYSWKMBDHVN (case ignored, U read as T); a motif letter stands
+ * for a set of bases (R = AG, Y = CT, S = CG, W = AT, K = GT, M = AC, B = CGT, D = AGT, H = ACT, V = ACG, N = ACGT).
+ * rc(M) reverses the motif and complements each set (A <-> T, C <-> G).
+ *
+ * OCCURRENCE.  Enzyme e occurs at arena position q when every letter of s[q : q + m] is a base and lies in the set of
+ * the motif letter at its place, for M or for rc(M).  A base is a letter whose `ac` bit is set, with code (hi, lo); the
+ * `up` plane is not read (soft-masked text matches like upper case) and a genome U is A as packed.  A non-base matches
+ * nothing, not even a motif N: N, IUPAC letters, decoration, void, a position below 0 and a position in a plane word at
+ * or beyond the arena's word count.  A palindromic motif occurring at q is ONE occurrence.  Occurrences cannot contain
+ * void, so a footprint [q, q + m) always lies inside one text.
+ *
+ * PER ROW of the hit tables after a scan at guide length l, 1 <= l <= 50, with amplicon half-width A, m_max <= A <=
+ * 100 000 (m_max: the set's longest motif); pos is the match index i ('+' row) or j ('-' row):
+ *   cut boundary c      i - 3 ('+'), j + 6 ('-'): letters c - 1 and c lie around the cut (section 18's, not the CSV's cutsite)
+ *   guide window        [g0, g0 + l), g0 = i - l ('+'), j + 3 ('-') (section 17's: the protospacer without the PAM)
+ *   text [t0, t1)       the text of crp_sites_set_enzymes that contains c; where none does the amplicon is empty
+ *   in_guide bit e      an occurrence with g0 <= q and q + m <= g0 + l exists (never when m > l)
+ *   span_e              occurrences with c - m + 1 <= q <= c - 1: both letters around the cut belong to the site
+ *   amp_e               occurrences with max(c - A, t0) <= q and q + m <= min(c + A, t1)
+ *   assay bit e         span_e >= 1 and amp_e == 1: the one site of the amplicon is the one across the cut (two
+ *                       overlapping sites across the cut give amp_e = 2 and no bit)
+ * One uint64 per row: in_guide | assay << 32.  Every row has a value, the unscored rows and the '-' rows whose windows run
+ * past the text included; nothing saturates.
+ *
+ * crp_sites_set_enzymes: the arena (sealed) builds, on the GPU, one occurrence plane per enzyme over its plane words (bit p
+ * of word w: an occurrence at 64 w + p) and a rank index (uint32 per word: the occurrences below 64 w), and keeps the
+ * texts' bounds: 12 B per plane word and enzyme of device memory, held until the arena is reset or destroyed -- re-scans
+ * keep them.  motifs[e] holds lens[e] letters (no terminator needed); text_starts / text_ends: n_texts half-open ranges
+ * of arena positions, ascending and disjoint.  CRP_ERR_INVALID with a crp_last_error text: E outside 1 .. 32, m outside
+ * 4 .. 16, a letter outside the alphabet, bounds that do not ascend or leave the arena; CRP_ERR_STATE: not sealed;
+ * CRP_ERR_NOMEM with a text that names the size when the planes do not fit.  A new set drops the column of the old one. */
+int crp_sites_set_enzymes(crp_arena *arena, uint64_t n, const char *const *motifs, const uint32_t *lens, const uint32_t *text_starts,
+                          const uint32_t *text_ends, uint64_t n_texts);
+/* After crp_scan_score and crp_sites_set_enzymes: the value of every kept hit, table order.  The column stays in HBM until
+ * the arena's next scan or enzyme set (crp_select_set_site_limits reads it there) and is copied to plus / minus (n_plus /
+ * n_minus values; either may be NULL).  One kernel lane per row, one launch for both tables.  With a crp_last_error text:
+ * CRP_ERR_STATE without tables or without an enzyme set, CRP_ERR_INVALID for tables scanned at a guide length outside
+ * 1 .. 50 and for a flank outside m_max .. 100 000.  Empty tables are fine. */
+int crp_site_columns(crp_arena *arena, int flank, uint64_t *plus, uint64_t *minus);
+/* The arena's enzyme set and its last crp_site_columns (CRP_ERR_STATE without a set): out[0] ms of the plane build,
+ * out[1] ms of the rank build, out[2] ms of the column kernel (HIP events), out[3] rows, out[4] E, out[5] A, out[6] bytes of
+ * device memory the planes and ranks hold; [2], [3] and [5] are 0 without a column for the current tables.  n: how many of
+ * these to write (<= 7). */
+int crp_site_stats(const crp_arena *arena, double *out, int n);
+/* Site limits of a selection (the column of crp_site_columns): with a mask set a row PASSES only if also no enzyme of
+ * forbid_mask lies inside its guide and -- need_mask != 0 -- it has an assay with at least one enzyme of need_mask.  Every
+ * kernel that evaluates the selection's predicate then reads 8 more bytes per row (crp_select_stats counts them) and the
+ * run returns CRP_ERR_STATE when the arena holds no site column for its current tables.  0 / 0 clears the limits. */
+int crp_select_set_site_limits(crp_select *select, uint32_t forbid_mask, uint32_t need_mask);
+
 /* ---- options -------------------------------------------------------------- */
 /* CRP_OPT_TWO_PASS (value 0/1, default 0): with 0 crp_scan_score is ONE kernel launch; the
  * table offsets come from a chained scan across workgroups inside it (decoupled look-back
