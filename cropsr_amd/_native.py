@@ -37,6 +37,13 @@ class SelectParams(ctypes.Structure):
                 ("require_cds", ctypes.c_int32), ("reserved", ctypes.c_int32)]
 
 
+class SelectSelfParams(ctypes.Structure):
+    """crp_select_self_params (include/cropsr_hip.h): the thresholds, the cut offset and K of one crp_select_run_self."""
+    _fields_ = [("max_hit_sum", ctypes.c_uint64), ("max_mm0", ctypes.c_uint32), ("k", ctypes.c_int32), ("cut_offset", ctypes.c_int32),
+                ("require_cds", ctypes.c_int32), ("gc_min", ctypes.c_uint32), ("gc_max", ctypes.c_uint32), ("max_t_run", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32)]
+
+
 class SelectPropertyLimits(ctypes.Structure):
     """crp_select_property_limits (include/cropsr_hip.h): the bounds a selection puts on the guide properties."""
     _fields_ = [("gc_min", ctypes.c_uint32), ("gc_max", ctypes.c_uint32), ("max_run", ctypes.c_uint32), ("max_t_run", ctypes.c_uint32),
@@ -261,6 +268,10 @@ SIGNATURES = {
     "crp_select_run_spaced": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "crp_select_fetch_spaced": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, u32p]),
     "crp_select_spaced_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
+    "crp_select_run_self": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "crp_select_set_self_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64]),
+    "crp_select_fetch_self": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, u32p, u32p, u8p, u32p, u32p, u32p, u64p]),
+    "crp_select_self_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_annotation_gene_coding": (ctypes.c_int, [ctypes.c_void_p, u8p, u32p, u32p]),
     "crp_annotation_coding_layout": (ctypes.c_int, [ctypes.c_void_p, u64p, ctypes.c_uint64, ctypes.c_int, u32p, u32p, u64p, ctypes.c_uint64, u64p,
                                                     u32p, u32p, u32p, ctypes.c_uint64, u64p]),

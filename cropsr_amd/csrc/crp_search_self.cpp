@@ -26,6 +26,7 @@
 #include "crp_internal.h"
 #include "crp_search_family.h"
 #include "crp_search_self.h"
+#include "crp_select_self.h"
 
 namespace {
 
@@ -92,6 +93,7 @@ struct crp_search_self {
     // the current ordering
     int segment = -1;
     std::vector<uint32_t> hist, start;  // per key: entries, first slot
+    uint32_t compared = 0;  // bit j: a crp_search_self_compare with this handle's guide sites as queries has run on segment j
     hipEvent_t ev[2] = {nullptr, nullptr};
     double ms_extract = 0, ms_order = 0, ms_compare = 0, ms_longest = 0;
     uint64_t n_compare = 0, n_order = 0, pairs = 0;
@@ -250,6 +252,22 @@ bool self_joined(const crp_search_self *s, SelfJoined *out)
     out->stride = s->max_mm + 1;
     out->arena = s->arena;
     return true;
+}
+
+void self_select_handle(const crp_search_self *s, SelfSelectHandle *out, bool *compared)
+{
+    const SearchCands c = s->cands();
+    out->rows = SelfSelectRows{c.hi, c.lo, c.pos, s->d_flag, s->d_counts, s->value.any() ? s->d_hit_sum : nullptr, (uint32_t)s->n,
+                               (uint32_t)s->max_mm + 1u};
+    out->arena = s->arena;
+    out->T = s->T;
+    out->pam_len = s->pam_len;
+    out->max_mm = s->max_mm;
+    out->pam3 = s->pam3;
+    out->scored = s->value.any();
+    out->region = s->rule.region;
+    out->n = s->n;
+    *compared = s->compared == (2u << s->max_mm) - 1u;
 }
 
 bool self_family_joined(const crp_search_self *s, SelfFamilyJoined *out)
@@ -511,7 +529,9 @@ int crp_search_self_compare(crp_search_self *q, crp_search_self *c)
             }
         }
     }
-    return flush();
+    const int rc = flush();
+    if (rc == CRP_OK) q->compared |= 1u << q->segment;
+    return rc;
 }
 
 int crp_search_self_fetch(crp_search_self *s, uint32_t *arena_pos, uint8_t *strand, uint32_t *hi, uint32_t *lo, uint32_t *counts,

@@ -16,6 +16,7 @@
 #include "crp_select_family.h"
 #include "crp_select_family_set.h"
 #include "crp_search_family.h"
+#include "crp_select_self.h"
 #include "crp_select_spaced.h"
 #include "crp_select_splice.h"
 
@@ -116,6 +117,16 @@ struct crp_select {
     uint64_t spaced_cap[10] = {};
     int ks = 0;  // of the last successful crp_select_run_spaced (0: none)
     double spaced_stats[9] = {};
+    // self selection: results and buffers of crp_select_run_self, apart from the selection's; the
+    // items, the merge list and the partial lists are the selection's (scratch of one run)
+    crp::SelectResult self_res = {};  // n_in, n_pass: n_genes; sel: n_genes * kself of the last run
+    crp::SelfSelectGathered self_got = {};  // n_genes * kself entries, beside sel
+    uint2 *d_self_run = nullptr;
+    uint64_t self_cap[10] = {};
+    uint64_t self_items_per_launch = crp::SELECT_MAX_ITEMS;
+    int kself = 0;        // of the last successful crp_select_run_self (0: none)
+    int self_stride = 0;  // M + 1 of that run's handle
+    double self_stats[7] = {};
 };
 
 namespace {
@@ -299,7 +310,8 @@ int crp_select_destroy(crp_select *s)
                     s->d_eval[3], s->d_gene_family, s->d_family_size, s->d_family_eval_sum, s->d_gene_member, s->d_set_items, s->d_set_prop,
                     s->d_set_best, s->d_set_start, s->d_set_slots, s->d_set_covered, s->spaced_res.n_pass, s->spaced_res.n_spaced, s->spaced_res.sel,
                     s->spaced_rounds.cuts, s->spaced_rounds.last, s->spaced_rounds.prop, s->spaced_rounds.slot_pass, s->spaced_rounds.picked,
-                    s->d_spaced_items, s->d_spaced_merge};
+                    s->d_spaced_items, s->d_spaced_merge, s->self_res.n_in, s->self_res.n_pass, s->self_res.sel, s->self_got.pos,
+                    s->self_got.hi, s->self_got.lo, s->self_got.counts, s->self_got.strand, s->self_got.sum, s->d_self_run};
     for (void *p : bufs) (void)hipFree(p);
     for (hipEvent_t e : s->ev)
         if (e) (void)hipEventDestroy(e);
@@ -920,6 +932,192 @@ int crp_select_spaced_stats(const crp_select *s, double *out, int n)
 {
     if (!s || (n && !out) || n < 0 || n > 9) return CRP_ERR_INVALID;
     for (int k = 0; k < n; ++k) out[k] = s->spaced_stats[k];
+    return CRP_OK;
+}
+
+/* ---- self selection ---- */
+
+int crp_select_set_self_limits(crp_select *s, uint64_t items_per_launch)
+{
+    if (!s || items_per_launch > crp::SELECT_MAX_ITEMS) return CRP_ERR_INVALID;
+    s->self_items_per_launch = items_per_launch ? items_per_launch : crp::SELECT_MAX_ITEMS;
+    return CRP_OK;
+}
+
+int crp_select_run_self(crp_select *s, const crp_select_self_params *p, crp_search_self *self)
+{
+    crp::Range roctx_range("crp: self selection");
+    if (!s || !p || !self) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    crp_arena *a = s->arena;
+    s->kself = 0;
+    const std::string who = "crp_select_run_self";
+    if (p->k < 1 || p->k > CRP_SELECT_MAX_K)
+        return fail(ctx, CRP_ERR_INVALID, who + ": k must be 1.." + std::to_string(CRP_SELECT_MAX_K) + ", not " + std::to_string(p->k));
+    crp::SelfSelectHandle h = {};
+    bool compared = false;
+    crp::self_select_handle(self, &h, &compared);
+    if (h.arena != a) return fail(ctx, CRP_ERR_INVALID, who + ": the self-search handle belongs to another arena");
+    if (!compared)
+        return fail(ctx, CRP_ERR_STATE, who + ": the self-search handle has not been through the compare of every segment 0.." +
+                                            std::to_string(h.max_mm) + " (crp_search_self_order, crp_search_self_compare)");
+    if (p->cut_offset < 1 || p->cut_offset > h.T - 1)
+        return fail(ctx, CRP_ERR_INVALID, who + ": the cut offset must be 1.." + std::to_string(h.T - 1) + " (pattern positions), not " +
+                                              std::to_string(p->cut_offset));
+    if (p->require_cds && !s->have_flags) return fail(ctx, CRP_ERR_STATE, who + ": require_cds needs crp_select_set_flags");
+    if (p->require_cds && !a->have_track) return fail(ctx, CRP_ERR_STATE, who + ": require_cds needs a track on the arena (crp_annotate_set_track)");
+    if (p->gc_min > p->gc_max)
+        return fail(ctx, CRP_ERR_INVALID, who + ": gc_min " + std::to_string(p->gc_min) + " is above gc_max " + std::to_string(p->gc_max));
+    if (h.n > 0xfffffffeull) return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": more than 2^32 - 2 candidates: a candidate index is 32 bits");
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    const int k = p->k;
+    const uint64_t G = s->n_genes, stride = (uint64_t)h.max_mm + 1;
+    int rc = crp::grow(ctx, reinterpret_cast<void **>(&s->self_res.n_in), &s->self_cap[0], G, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->self_res.n_pass), &s->self_cap[1], G, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->self_res.sel), &s->self_cap[2], G * k, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->self_got.pos), &s->self_cap[3], G * k, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->self_got.hi), &s->self_cap[4], G * k, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->self_got.lo), &s->self_cap[5], G * k, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->self_got.counts), &s->self_cap[6], G * k * stride, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->self_got.strand), &s->self_cap[7], G * k, sizeof(uint8_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->self_got.sum), &s->self_cap[8], G * k, sizeof(uint64_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_self_run), &s->self_cap[9], G, sizeof(uint2));
+    if (rc != CRP_OK) return rc;
+    for (double &v : s->self_stats) v = 0;
+    s->self_stride = (int)stride;
+    if (!G) {
+        s->kself = k;
+        return CRP_OK;
+    }
+    const uint32_t n_cand = h.rows.n;
+    CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    CRP_HIP(ctx, crp::launch_select_self_bounds(ctx->stream, h.rows.pos, n_cand, (uint32_t)h.T, s->d_lo, s->d_hi, (uint32_t)G, s->d_self_run));
+    CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+    std::vector<uint2> runs;
+    std::vector<crp::SelectItem> items;
+    std::vector<crp::SelectMerge> merges;
+    uint64_t n_slots = 0, rows_covered = 0;
+    try {
+        runs.resize(G);
+        rc = crp::staged_d2h(ctx, runs.data(), s->d_self_run, G * sizeof(uint2));
+        if (rc != CRP_OK) return rc;
+        CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        s->self_stats[0] = elapsed(s->ev[0], s->ev[1]);
+        // every gene's run in pieces of at most slice_rows candidates; a gene without rows still gets one (empty) item,
+        // which writes its zeros
+        items.reserve(G + G / 8);
+        for (uint64_t g = 0; g < G; ++g) {
+            const uint2 b = runs[g];
+            if (b.x > b.y || b.y > n_cand) return fail(ctx, CRP_ERR_HIP, who + ": the run of gene " + std::to_string(g) + " lies outside the candidates");
+            const uint64_t total = b.y - b.x;
+            rows_covered += total;
+            const uint64_t pieces = std::max<uint64_t>(1, (total + s->slice_rows - 1) / s->slice_rows);
+            if (n_slots + pieces > 0xfffffff0ull || items.size() + pieces > 0xfffffff0ull)
+                return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": more than 2^32 work items or slots (raise slice_rows)");
+            if (pieces > 1) merges.push_back(crp::SelectMerge{(uint32_t)g, (uint32_t)n_slots, (uint32_t)pieces});
+            for (uint64_t c = 0; c < pieces; ++c) {
+                const uint64_t r0 = c * s->slice_rows, r1 = std::min(total, r0 + s->slice_rows);
+                crp::SelectItem it;
+                it.gene = (uint32_t)g;
+                it.slot = pieces > 1 ? (uint32_t)(n_slots + c) : crp::SELECT_NONE;
+                it.first[0] = b.x + (uint32_t)r0;
+                it.rows[0] = (uint32_t)(r1 - r0);
+                it.first[1] = 0;
+                it.rows[1] = 0;
+                items.push_back(it);
+            }
+            if (pieces > 1) n_slots += pieces;
+        }
+    } catch (const std::bad_alloc &) {
+        return CRP_ERR_NOMEM;
+    }
+    rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_items), &s->items_cap, items.size(), sizeof(crp::SelectItem));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_merge), &s->merge_cap, merges.size(), sizeof(crp::SelectMerge));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->part.key), &s->part_entries_cap, n_slots * k, sizeof(uint64_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->part.tie), &s->part_tie_cap, n_slots * k, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->part.row), &s->part_row_cap, n_slots * k, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->part.cnt), &s->part_cnt_cap, n_slots * 2, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::staged_h2d(ctx, s->d_items, items.data(), items.size() * sizeof(crp::SelectItem));
+    if (rc == CRP_OK && !merges.empty()) rc = crp::staged_h2d(ctx, s->d_merge, merges.data(), merges.size() * sizeof(crp::SelectMerge));
+    if (rc != CRP_OK) return rc;
+    const uint32_t G_letters = (uint32_t)(h.T - h.pam_len);
+    crp::SelfSelectPredicate pred = {};
+    pred.max_hit_sum = p->max_hit_sum;
+    pred.max_mm0 = p->max_mm0;
+    pred.T = (uint32_t)h.T;
+    pred.cut = (uint32_t)p->cut_offset;
+    pred.region = h.region;
+    pred.gc_min = p->gc_min;
+    pred.gc_max = p->gc_max;
+    pred.max_t_run = p->max_t_run;
+    pred.seq_limits = (p->gc_min > 0 || p->gc_max < G_letters || p->max_t_run < G_letters) ? 1u : 0u;
+    pred.k = k;
+    crp::SelfSelectTrack track = {};
+    if (p->require_cds) {
+        track.points = a->d_ann_points;
+        track.ids = a->d_ann_ids;
+        track.bucket = a->d_ann_bucket;
+        track.last_bucket = (uint32_t)(a->n_ann_entries - 2);
+        track.flags = s->d_flags;
+        track.n_flags = (uint32_t)s->n_flags;
+    }
+    // the bounded-launch rule: at most self_items_per_launch (2^20) items a launch, each timed on its own
+    for (uint64_t first = 0; first < items.size(); first += s->self_items_per_launch) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(s->self_items_per_launch, items.size() - first);
+        CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+        CRP_HIP(ctx, crp::launch_select_self_items(ctx->stream, h.rows, track, pred, s->d_lo, s->d_hi, s->d_items + first, n, s->part, s->self_res));
+        CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+        CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        s->self_stats[1] += elapsed(s->ev[0], s->ev[1]);
+        s->self_stats[4] += 1;
+    }
+    for (uint64_t first = 0; first < merges.size(); first += crp::SELECT_MAX_ITEMS) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(crp::SELECT_MAX_ITEMS, merges.size() - first);
+        CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+        CRP_HIP(ctx, crp::launch_select_merge(ctx->stream, s->d_merge + first, n, k, s->part, s->self_res));
+        CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+        CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        s->self_stats[2] += elapsed(s->ev[0], s->ev[1]);
+    }
+    CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    CRP_HIP(ctx, crp::launch_select_self_gather(ctx->stream, h.rows, s->self_res.sel, G * k, s->self_got));
+    CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s->self_stats[3] = elapsed(s->ev[0], s->ev[1]);
+    s->self_stats[5] = (double)items.size();
+    s->self_stats[6] = (double)rows_covered;
+    s->kself = k;
+    return CRP_OK;
+}
+
+int crp_select_fetch_self(crp_select *s, uint32_t *n_in, uint32_t *n_pass, uint32_t *sel, uint32_t *arena_pos, uint8_t *strand, uint32_t *hi,
+                          uint32_t *lo, uint32_t *counts, uint64_t *hit_sum)
+{
+    if (!s) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    if (!s->kself) return fail(ctx, CRP_ERR_STATE, "crp_select_fetch_self: no crp_select_run_self has succeeded on this handle");
+    if (!s->n_genes) return CRP_OK;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    const uint64_t G = s->n_genes, E = G * s->kself;
+    int rc = CRP_OK;
+    if (n_in) rc = crp::staged_d2h(ctx, n_in, s->self_res.n_in, G * sizeof(uint32_t));
+    if (rc == CRP_OK && n_pass) rc = crp::staged_d2h(ctx, n_pass, s->self_res.n_pass, G * sizeof(uint32_t));
+    if (rc == CRP_OK && sel) rc = crp::staged_d2h(ctx, sel, s->self_res.sel, E * sizeof(uint32_t));
+    if (rc == CRP_OK && arena_pos) rc = crp::staged_d2h(ctx, arena_pos, s->self_got.pos, E * sizeof(uint32_t));
+    if (rc == CRP_OK && strand) rc = crp::staged_d2h(ctx, strand, s->self_got.strand, E * sizeof(uint8_t));
+    if (rc == CRP_OK && hi) rc = crp::staged_d2h(ctx, hi, s->self_got.hi, E * sizeof(uint32_t));
+    if (rc == CRP_OK && lo) rc = crp::staged_d2h(ctx, lo, s->self_got.lo, E * sizeof(uint32_t));
+    if (rc == CRP_OK && counts) rc = crp::staged_d2h(ctx, counts, s->self_got.counts, E * s->self_stride * sizeof(uint32_t));
+    if (rc == CRP_OK && hit_sum) rc = crp::staged_d2h(ctx, hit_sum, s->self_got.sum, E * sizeof(uint64_t));
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CRP_OK;
+}
+
+int crp_select_self_stats(const crp_select *s, double *out, int n)
+{
+    if (!s || (n && !out) || n < 0 || n > 7) return CRP_ERR_INVALID;
+    for (int k = 0; k < n; ++k) out[k] = s->self_stats[k];
     return CRP_OK;
 }
 

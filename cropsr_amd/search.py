@@ -985,6 +985,8 @@ class ArenaSelfSearch:
 
 class SelfSearchResult:
     site_family = site_gene = fam_counts = fam_sum = fam_cover = None  # with families=: per guide site (families.py)
+    selection = None  # with select=: the select_self.Selection
+    n_guides = None   # the guide sites of the genome (len(sites), also where sites=False left them on the device)
 
     def __init__(self, sites, guides, counts, hit_sum, candidates, pairs, stats=None):
         self.sites = sites            # SELF_SITE_DTYPE, ordered by contig, position, strand
@@ -1053,15 +1055,29 @@ def check_family_geometry(pattern, pam_len):
 
 
 def search_self(genome, pattern, max_mm, pam_len, guide_pattern=None, score=None, budget=None, pairs_per_launch=None, families=None,
-                family_cover_mm=0, family_limits=None):
+                family_cover_mm=0, family_limits=None, select=None, sites=True):
     """The self search over all arenas of `genome` (engine.Genome): see the module's docstring.  budget: device bytes
     one arena's handle may take (None: the library's default); SelfCapacityError (.needed) beyond it.
     pairs_per_launch: lowers the pairs one compare launch covers (results do not depend on it).
     families: one families.ArenaRows per arena; the result then carries site_family, site_gene (the owner's gene index),
     fam_counts, fam_sum (None without score=) and fam_cover per guide site (families.py has the definition), with
-    family_cover_mm as the cover limit C."""
+    family_cover_mm as the cover limit C.
+    select: a select_self.Request; the K most specific guide sites of every gene of its annotation are then chosen on the
+    GPU between the compares and the closing of the handles (select_self.py has the definition), and the result carries
+    them as .selection (select_self.Selection).  sites=False (with select=, without families=): the per-site rows are not
+    copied to the host -- the result's sites, guides, counts and hit_sum are empty and only .selection, .candidates, .n_guides
+    and .pairs are filled."""
     pattern, gp, max_mm, pam_len, scheme = check_self(pattern, max_mm, pam_len, guide_pattern, score)
-    lo, hi, _ = guide_region(pattern, pam_len)
+    lo, hi, pam3 = guide_region(pattern, pam_len)
+    if not sites and (select is None or families is not None):
+        raise SearchInputError("sites=False keeps only the selection: it needs select= and goes without families=")
+    if select is not None:
+        if select.params.needs_score and scheme is None:
+            raise SearchInputError("a specificity threshold needs a scored search (score=)")
+        try:
+            select.params.resolve(len(pattern), pam_len, pam3)
+        except ValueError as e:
+            raise SearchInputError(str(e))
     if families is not None:
         check_family_geometry(pattern, pam_len)
         if not isinstance(family_cover_mm, (int, np.integer)) or not 0 <= int(family_cover_mm) <= max_mm:
@@ -1079,6 +1095,19 @@ def search_self(genome, pattern, max_mm, pam_len, guide_pattern=None, score=None
                 has = owner != np.uint32(0xFFFFFFFF)
                 gene[has] = np.asarray(r.gene, np.uint32)[owner[has]]
                 fam_parts.append((fam, gene, fc, fs, cover))
+        selection = None
+        if select is not None:
+            from . import select_self
+            flags = select.annotation.annotation.cds_flags() if select.params.require_cds else None
+            sel_parts, sel_stats = [], {}
+            for k, (h, a, group) in enumerate(zip(handles, genome.arenas, genome.groups)):
+                gene, got, st = select_self.select_arena(genome, k, select, h, flags)
+                sel_parts.append(dict(got, offsets=a.offsets, lengths=a.lengths, group=group, gene=gene))
+                for key, v in st.items():
+                    sel_stats[key] = sel_stats.get(key, 0.0) + v
+            selection = select_self.assemble(select.annotation.annotation.genes()[0], select.params.k, len(pattern),
+                                             select.params.cut_offset, lo, hi - lo, scheme is not None, sel_parts)
+            selection.stats = sel_stats
         parts, guides, counts, sums = [], [], [], []
         cand, n_guides, stats = [0, 0], 0, {}
         for h, a, group in zip(handles, genome.arenas, genome.groups):
@@ -1086,6 +1115,10 @@ def search_self(genome, pattern, max_mm, pam_len, guide_pattern=None, score=None
             cand[0] += npl
             cand[1] += nmi
             n_guides += ng
+            for key, v in h.stats().items():
+                stats[key] = max(stats.get(key, 0.0), v) if key == "longest_launch_ms" else stats.get(key, 0.0) + v
+            if not sites:
+                continue
             pos, strand, fh, fl, c, hs = h.fetch(scheme is not None)
             offs = np.asarray(a.offsets, dtype=np.int64)
             k = np.searchsorted(offs, pos.astype(np.int64), "right") - 1
@@ -1098,19 +1131,21 @@ def search_self(genome, pattern, max_mm, pam_len, guide_pattern=None, score=None
             counts.append(c)
             if hs is not None:
                 sums.append(hs)
-            for key, v in h.stats().items():
-                stats[key] = max(stats.get(key, 0.0), v) if key == "longest_launch_ms" else stats.get(key, 0.0) + v
             if families is not None:
                 for key, v in h.family_stats().items():
                     stats[key] = stats.get(key, 0.0) + v
     finally:
         for h in handles:
             h.close()
-    sites = np.concatenate(parts) if parts else np.empty(0, SELF_SITE_DTYPE)
+    if not parts:  # (sites=False, or a genome without arenas)
+        parts, guides = [np.empty(0, SELF_SITE_DTYPE)], [np.empty(0, "S%d" % (hi - lo))]
+        counts, sums = [np.empty((0, max_mm + 1), np.uint32)], [np.empty(0, np.uint64)]
+    sites = np.concatenate(parts)
     order = np.lexsort((sites["strand"] == b"-", sites["position"], sites["contig"]))
     res = SelfSearchResult(sites[order], np.concatenate(guides)[order], np.concatenate(counts)[order],
                            np.concatenate(sums)[order] if scheme is not None else None, tuple(cand),
                            (int(stats.get("pairs", 0)), n_guides * (cand[0] + cand[1])), stats)
+    res.selection, res.n_guides = selection, n_guides
     if families is not None:
         res.site_family, res.site_gene, res.fam_counts, res.fam_cover = (np.concatenate([p[k] for p in fam_parts])[order] for k in (0, 1, 2, 4))
         res.fam_sum = np.concatenate([p[3] for p in fam_parts])[order] if scheme is not None else None
@@ -1371,7 +1406,32 @@ def main(argv=None):
                          "letter and site letter; values per PAM letters; see parse_pair_table, tools/cfd_to_table.py)")
     ap.add_argument("--no-sites", action="store_true", help="keep and write no site list: only --counts (with the scores, if asked for)")
     ap.add_argument("--device", type=int, default=0, help="HIP device")
+    sg = ap.add_argument_group("guide selection for any nuclease (with --self; DESIGN.md section 28)")
+    sg.add_argument("-g", "--gff", metavar="FILE", help="with --select: the GFF3 whose `gene` rows are selected for")
+    sg.add_argument("--select", type=int, default=None, metavar="K",
+                    help="with --self and -g: also choose, on the GPU, the K (1..64) most specific guide sites of every gene -- "
+                         "ranked by hit_sum when scored, by the mismatch counts otherwise -- and write them to --select-output")
+    sg.add_argument("--select-output", metavar="FILE", help="the selection TSV (default: the -o name + .selected.tsv)")
+    sg.add_argument("--cut-offset", type=int, default=None, metavar="C",
+                    help="with --select: the cut lies before pattern position C (1..T-1) of the oriented site; default G-3 with "
+                         "the PAM on the 3' side, P+min(18, G-1) with the PAM on the 5' side")
+    sg.add_argument("--select-max-perfect", type=int, default=None, metavar="N", help="with --select: only sites with at most N other perfect copies (n0)")
+    sg.add_argument("--select-min-specificity", type=float, default=None, metavar="S",
+                    help="with --select: only sites of specificity at least S (needs --score, --weights or --score-table)")
+    sg.add_argument("--select-cds", action="store_true", help="with --select: only sites whose cut letter lies in a CDS of the GFF")
+    sg.add_argument("--select-gc-min", type=int, default=None, metavar="PCT",
+                    help="with --select: only guides with at least PCT %% GC (an integer 0..100; as a count: ceil(PCT * G / 100))")
+    sg.add_argument("--select-gc-max", type=int, default=None, metavar="PCT",
+                    help="with --select: only guides with at most PCT %% GC (an integer 0..100; as a count: floor(PCT * G / 100))")
+    sg.add_argument("--select-max-t-run", type=int, default=None, metavar="N", help="with --select: only guides whose longest run of T is at most N")
+    sg.add_argument("--select-only", action="store_true", help="with --select: write only the selection, no sites TSV (-o is then not required)")
     args = ap.parse_args(argv)
+    if args.select is None:
+        for opt, given in _select_options(args):
+            if given:
+                ap.error("%s belongs to --select" % opt)
+    elif not args.self_search:
+        ap.error("--select belongs to --self (the scan's selection is python -m cropsr_amd --select)")
     if args.self_search:
         return _main_self(ap, args)
     if not args.guides:
@@ -1427,6 +1487,40 @@ def main(argv=None):
     return 0
 
 
+def _select_options(args):
+    """[(option, whether it was given)] of the options that belong to --select."""
+    return [("-g/--gff", args.gff is not None), ("--select-output", args.select_output is not None), ("--cut-offset", args.cut_offset is not None),
+            ("--select-max-perfect", args.select_max_perfect is not None), ("--select-min-specificity", args.select_min_specificity is not None),
+            ("--select-cds", args.select_cds), ("--select-gc-min", args.select_gc_min is not None),
+            ("--select-gc-max", args.select_gc_max is not None), ("--select-max-t-run", args.select_max_t_run is not None),
+            ("--select-only", args.select_only)]
+
+
+def _self_select_params(args, pattern, pam_len, scored):
+    """The select_self.Params of --select and its options, checked against the pattern; SearchInputError otherwise."""
+    from . import select_self
+    if not args.gff:
+        raise SearchInputError("--select needs -g/--gff: the genes to select for")
+    if not 1 <= args.select <= select_self.MAX_K:
+        raise SearchInputError("--select K must be 1..%d, not %d" % (select_self.MAX_K, args.select))
+    if args.select_min_specificity is not None and not scored:
+        raise SearchInputError("--select-min-specificity needs a scored search (--score, --weights or --score-table)")
+    lo, hi, pam3 = guide_region(pattern, pam_len)
+    for name, v in (("--select-gc-min", args.select_gc_min), ("--select-gc-max", args.select_gc_max)):
+        if v is not None and not 0 <= v <= 100:
+            raise SearchInputError("%s is a percentage 0..100, not %d" % (name, v))
+    for name, v in (("--select-max-perfect", args.select_max_perfect), ("--select-max-t-run", args.select_max_t_run)):
+        if v is not None and v < 0:
+            raise SearchInputError("%s is a count, not %d" % (name, v))
+    gc_min, gc_max = select_self.gc_bounds(args.select_gc_min, args.select_gc_max, hi - lo)
+    try:
+        params = select_self.Params(args.select, args.cut_offset, args.select_max_perfect, args.select_min_specificity, args.select_cds,
+                                    gc_min, gc_max, args.select_max_t_run)
+        return params.resolve(len(pattern), pam_len, pam3)
+    except ValueError as e:
+        raise SearchInputError("--select: %s" % e)
+
+
 def _main_self(ap, args):
     """--self: checks, then search_self and the TSV."""
     try:
@@ -1434,8 +1528,8 @@ def _main_self(ap, args):
                            ("--no-sites", args.no_sites), ("--counts", args.counts)):
             if given:
                 raise SearchInputError("--self does not go with %s" % opt)
-        if not args.output:
-            raise SearchInputError("--self needs -o/--output")
+        if not args.output and not (args.select is not None and args.select_only and args.select_output):
+            raise SearchInputError("--self needs -o/--output" + (" (or --select-only with --select-output)" if args.select is not None else ""))
         score = args.score
         if args.weights:
             with open(args.weights, "rb") as f:
@@ -1443,22 +1537,44 @@ def _main_self(ap, args):
         if args.score_table:
             with open(args.score_table, "rb") as f:
                 score = parse_pair_table(f.read())
-        pattern, gp, max_mm, pam_len, _ = check_self(args.pattern, args.mismatches, args.pam_length, args.guide_pattern, score)
+        pattern, gp, max_mm, pam_len, scheme = check_self(args.pattern, args.mismatches, args.pam_length, args.guide_pattern, score)
+        params = None if args.select is None else _self_select_params(args, pattern, pam_len, scheme is not None)
+        if params is not None:
+            with open(args.gff, "rb"):  # (unreadable: refused here, before the GPU is opened)
+                pass
         contig_names, contigs = read_fasta(args.fasta)
     except (SearchInputError, OSError, UnicodeDecodeError) as e:
         ap.error(str(e))
     from .engine import Engine
-    with Engine(args.device) as eng:
-        g = eng.genome(contigs)
-        try:
-            res = search_self(g, pattern, max_mm, pam_len, guide_pattern=gp, score=score)
-        finally:
-            g.close()
-    with open(args.output, "w") as f:
-        for text in format_self(contig_names, res):
-            f.write(text)
+    request = annotation = None
+    if params is not None:
+        from . import annotate, select_self
+        annotation = annotate.Annotation(args.gff)
+        request = select_self.Request(params, annotate.Request(annotation, contig_names, 0))
+    try:
+        with Engine(args.device) as eng:
+            g = eng.genome(contigs)
+            try:
+                res = search_self(g, pattern, max_mm, pam_len, guide_pattern=gp, score=score, select=request,
+                                  sites=not (params is not None and args.select_only))
+            finally:
+                g.close()
+    finally:
+        if annotation is not None:
+            annotation.close()
+    if not (params is not None and args.select_only):
+        with open(args.output, "w") as f:
+            for text in format_self(contig_names, res):
+                f.write(text)
     print("%d guide sites, %d + %d candidate sites, %d of %d pairs compared" % (
-        len(res.sites), res.candidates[0], res.candidates[1], res.pairs[0], res.pairs[1]), file=sys.stderr)
+        res.n_guides, res.candidates[0], res.candidates[1], res.pairs[0], res.pairs[1]), file=sys.stderr)
+    if params is not None:
+        from . import select_self
+        sel = res.selection
+        with open(args.select_output or args.output + ".selected.tsv", "w") as f:
+            f.write(select_self.format_selection(contig_names, sel))
+        print("%d genes, %d guide sites inside them, %d passing, %d selected" % (
+            len(sel.labels), int(sel.n_in.sum()), int(sel.n_pass.sum()), len(sel.rows)), file=sys.stderr)
     return 0
 
 

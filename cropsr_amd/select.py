@@ -383,6 +383,7 @@ class ArenaSelect:
         if lo.shape != hi.shape or lo.ndim != 1:
             raise ValueError("lo and hi must be 1-d arrays of one length")
         self.n_genes, self.k, self.kp, self.ks = int(lo.size), 0, 0, 0
+        self.kself, self._self_stride = 0, 1  # of the last run_self
         h = ctypes.c_void_p()
         nat.check(nat.lib().crp_select_create(arena._h, lo.ctypes.data_as(nat.u32p), hi.ctypes.data_as(nat.u32p), lo.size, ctypes.byref(h)),
                   "crp_select_create", self._ctx)
@@ -466,6 +467,38 @@ class ArenaSelect:
         nat.check(nat.lib().crp_select_spaced_stats(self._h, out.ctypes.data_as(nat.f64p), 9), "crp_select_spaced_stats", self._ctx)
         keys = ("spaced_key_ms", "spaced_items_ms", "spaced_step_ms", "spaced_pick_ms", "spaced_rounds", "spaced_launches",
                 "spaced_longest_launch_ms", "spaced_items", "spaced_cut_genes")
+        return dict(zip(keys, (float(v) for v in out)))
+
+    # ---- self selection (select_self.py has the definition)
+    def set_self_limits(self, items_per_launch=0):
+        nat.check(nat.lib().crp_select_set_self_limits(self._h, int(items_per_launch)), "crp_select_set_self_limits", self._ctx)
+
+    def run_self(self, params, self_search):
+        """params: select_self.Params (or a nat.SelectSelfParams); self_search: the search.ArenaSelfSearch of this arena after
+        all of its orders and compares."""
+        p = params.native() if hasattr(params, "native") else params
+        nat.check(nat.lib().crp_select_run_self(self._h, ctypes.byref(p), self_search._h), "crp_select_run_self", self._ctx)
+        self.kself, self._self_stride = int(p.k), self_search.max_mm + 1
+
+    def fetch_self(self):
+        """dict of the last run_self: n_in, n_pass uint32 (G,), sel uint32 (G, K) -- candidate indices in extraction order --
+        and of the selected candidates, beside sel: arena_pos, hi, lo uint32 (G, K), strand uint8 (G, K), counts uint32
+        (G, K, M + 1), hit_sum uint64 (G, K); all-ones where sel has no candidate."""
+        G, K = self.n_genes, max(1, self.kself)
+        out = dict(n_in=np.empty(G, np.uint32), n_pass=np.empty(G, np.uint32), sel=np.empty((G, K), np.uint32),
+                   arena_pos=np.empty((G, K), np.uint32), strand=np.empty((G, K), np.uint8), hi=np.empty((G, K), np.uint32),
+                   lo=np.empty((G, K), np.uint32), counts=np.empty((G, K, self._self_stride), np.uint32),
+                   hit_sum=np.empty((G, K), np.uint64))
+        types = dict(strand=nat.u8p, hit_sum=nat.u64p)
+        order = ("n_in", "n_pass", "sel", "arena_pos", "strand", "hi", "lo", "counts", "hit_sum")
+        nat.check(nat.lib().crp_select_fetch_self(self._h, *[out[key].ctypes.data_as(types.get(key, nat.u32p)) for key in order]),
+                  "crp_select_fetch_self", self._ctx)
+        return out
+
+    def self_stats(self):
+        out = np.zeros(7, dtype=np.float64)
+        nat.check(nat.lib().crp_select_self_stats(self._h, out.ctypes.data_as(nat.f64p), 7), "crp_select_self_stats", self._ctx)
+        keys = ("self_bounds_ms", "self_items_ms", "self_merge_ms", "self_gather_ms", "self_launches", "self_items", "self_rows_in_runs")
         return dict(zip(keys, (float(v) for v in out)))
 
     def set_coding(self, model):

@@ -1008,6 +1008,57 @@ int crp_select_fetch_spaced(crp_select *select, uint32_t *n_pass, uint32_t *n_sp
  * (<= 9). */
 int crp_select_spaced_stats(const crp_select *select, double *out, int n);
 
+/* ---- self selection: the K most specific guide sites of every gene, for any nuclease (opt-in) --- */
+/* crp_select_run ranks the rows of the NGG scan by their on-target score.  This run ranks the rows of a self-search handle
+ * (crp_search_self_*: any pattern of up to 32 letters, the PAM on either side) by their specificity, where they lie in HBM.
+ * It reads no scan tables.  Per arena, on a crp_select handle (its genes lo[] / hi[], its flags, its slice_rows), with a
+ * handle of T pattern letters, P PAM letters, G = T - P guide-region letters and M mismatches:
+ *   cut letter  of a guide site with forward start s, for a cut offset c (1 <= c <= T - 1, in pattern coordinates: the cut
+ *               lies before pattern position c of the oriented window): s + c on '+', s + T - c on '-'.  With ...NGG (T = 23)
+ *               and c = 17 a '+' site's cut letter is crp_select_run's i - 3; the '-' rule is the true mirror, j + 6, where
+ *               crp_select_run keeps the reference's j
+ *   in          only guide sites count (a candidate that is no guide site is ignored): in gene g when lo <= cut <= hi
+ *   passes      counts[0] <= max_mm0; on a scored handle hit_sum <= max_hit_sum; with require_cds the flag byte
+ *               (crp_select_set_flags) of the label-set id of the track interval (crp_annotate_set_track) under the cut
+ *               letter is non-zero; gc_min <= GC letters of the guide region <= gc_max; the longest run of T in the guide
+ *               region <= max_t_run
+ *   order       smaller e first, then the smaller cut letter, then '+' before '-'.  Scored handle: e = hit_sum +
+ *               ((uint64)counts[0] << 30), a perfect copy elsewhere weighing like a hit of full value.  Unscored handle: e =
+ *               min(counts[0], 65 535) << 48 | min(counts[j], 4 095) << (48 - 12 j) for j = 1 .. M
+ *   result      per gene: n_in (guide sites in the gene), n_pass (passing ones) and sel[g * K ..): the first min(K, n_pass)
+ *               passing sites in that order, each as its candidate index in extraction order, 0xFFFFFFFF beyond
+ * Exact and integer-only: the result does not depend on how the work was cut. */
+typedef struct crp_select_self_params {
+    uint64_t max_hit_sum; /* 0xFFFFFFFFFFFFFFFF: no bound; not read on an unscored handle */
+    uint32_t max_mm0;     /* 0xFFFFFFFF: no bound */
+    int32_t k;            /* 1 .. CRP_SELECT_MAX_K */
+    int32_t cut_offset;   /* c: 1 .. T - 1 */
+    int32_t require_cds;
+    uint32_t gc_min, gc_max; /* counts of letters; 0 and 0xFFFFFFFF: no bound */
+    uint32_t max_t_run;      /* 0xFFFFFFFF: no bound */
+    uint32_t reserved;
+} crp_select_self_params;
+/* The run.  CRP_ERR_INVALID with a crp_last_error text: K outside 1 .. 64, c outside 1 .. T - 1, gc_min > gc_max, a handle of
+ * another arena.  CRP_ERR_STATE: a handle that has not been the query of a crp_search_self_compare on every segment 0 .. M
+ * (with several arenas the caller compares it against every arena's handle: only "at least once per segment" is tracked),
+ * require_cds without crp_select_set_flags or without a track on the arena.  CRP_ERR_UNSUPPORTED: more than 2^32 - 2
+ * candidates.  Genes are cut into items by crp_select_set_limits' slice_rows, at most crp_select_set_self_limits'
+ * items a launch; cut genes are merged by crp_select_run's merge.  Leaves the results of the handle's other runs alone. */
+int crp_select_run_self(crp_select *select, const crp_select_self_params *params, crp_search_self *self);
+/* Work items per launch of crp_select_run_self (0: the default, 2^20; more is CRP_ERR_INVALID).  Results do not depend on it;
+ * tests lower it to put a cut gene's items on both sides of a launch boundary. */
+int crp_select_set_self_limits(crp_select *select, uint64_t items_per_launch);
+/* The results of the last crp_select_run_self (CRP_ERR_STATE without one): n_in, n_pass (n_genes each), sel (n_genes * K), and
+ * of the selected candidates, entry by entry beside sel (gathered on the device: K rows a gene are copied, never a column):
+ * arena_pos (forward start), strand (0 '+', 1 '-'), hi, lo (the oriented window's code bits), counts (M + 1 each) and
+ * hit_sum (all-ones on an unscored handle).  All-ones where sel has no candidate.  Any pointer may be NULL. */
+int crp_select_fetch_self(crp_select *select, uint32_t *n_in, uint32_t *n_pass, uint32_t *sel, uint32_t *arena_pos, uint8_t *strand,
+                          uint32_t *hi, uint32_t *lo, uint32_t *counts, uint64_t *hit_sum);
+/* Measurement of the last crp_select_run_self: out[0] ms of the bounds kernel, out[1] ms of the item launches, out[2] ms of the
+ * merge launches, out[3] ms of the gather kernel (HIP events), out[4] item launches, out[5] work items, out[6] candidates
+ * streamed (the runs' rows).  n: how many to write (<= 7). */
+int crp_select_self_stats(const crp_select *select, double *out, int n);
+
 /* ---- coding position: where in the coding sequence a guide cuts (opt-in) ---------------- */
 /* crp_annotation_build also reads the `mRNA` / `transcript` rows, the Parent links and the gene rows' strand, and builds a
  * CODING MODEL of every gene (cropsr_amd/coding.py states the definition):
