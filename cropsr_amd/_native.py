@@ -265,6 +265,10 @@ SIGNATURES = {
     "crp_select_run_pairs": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     "crp_select_fetch_pairs": (ctypes.c_int, [ctypes.c_void_p, u32p, u64p, u32p]),
     "crp_select_pairs_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
+    "crp_select_run_pairs_distinct": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "crp_select_fetch_pairs_distinct": (ctypes.c_int, [ctypes.c_void_p, u32p, u64p, u32p, u32p]),
+    "crp_select_pairs_distinct_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
+    "crp_select_set_pair_distinct_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64]),
     "crp_select_run_spaced": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p]),
     "crp_select_fetch_spaced": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, u32p]),
     "crp_select_spaced_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),

@@ -148,6 +148,9 @@ def build_parser():
                      help="with --select-pairs: the longest deletion, in letters (default 500; at most 65535)")
     eng.add_argument("--pairs-frameshift", action="store_true",
                      help="with --select-pairs: only deletions whose length is no multiple of 3")
+    eng.add_argument("--pairs-distinct", action="store_true",
+                     help="with --select-pairs: the KP pairs of a gene share no guide -- the pairs are taken greedily in rank order, and "
+                          "a pair is taken only if neither of its guides belongs to a pair taken before it; `rank` is the pick order")
     eng.add_argument("--pairs-orientation", default=None, metavar="WHICH",
                      help="with --select-pairs: any (default), pam-out ('-' guide left, '+' guide right: the nickase layout) or pam-in")
     eng.add_argument("--pairs-output", metavar="FILE", default=None,
@@ -704,7 +707,7 @@ def select_request(args, spec, world=1):
     KP = getattr(args, "select_pairs", None)
     pair_given = [o for o, k, unset in (("--pairs-min-distance", "pairs_min_distance", None), ("--pairs-max-distance", "pairs_max_distance", None),
                                         ("--pairs-frameshift", "pairs_frameshift", False), ("--pairs-orientation", "pairs_orientation", None),
-                                        ("--pairs-output", "pairs_output", None))
+                                        ("--pairs-output", "pairs_output", None), ("--pairs-distinct", "pairs_distinct", False))
                   if getattr(args, k, unset) not in (unset, None)]
     if KP is None and pair_given:
         sys.exit("cropsr_amd: --select: %s belongs to --select-pairs" % pair_given[0])
@@ -951,7 +954,8 @@ def select_request(args, spec, world=1):
         dmin, dmax = getattr(args, "pairs_min_distance", None), getattr(args, "pairs_max_distance", None)
         try:
             pairs = select.PairParams(KP, 50 if dmin is None else dmin, 500 if dmax is None else dmax,
-                                      bool(getattr(args, "pairs_frameshift", False)), getattr(args, "pairs_orientation", None) or "any")
+                                      bool(getattr(args, "pairs_frameshift", False)), getattr(args, "pairs_orientation", None) or "any",
+                                      distinct=bool(getattr(args, "pairs_distinct", False)))
         except ValueError as e:
             refuse("--select-pairs: " + str(e))
     return dict(params=params, output=getattr(args, "select_output", None) or (args.o + ".selected.csv"),
@@ -1583,6 +1587,8 @@ def run(args, backend=None, out=sys.stdout, group=None):
             write_pairs(selecting["pairs_output"], selection, names, strings, all_hits, args.l, repair_scores=selecting["repair_scores"])
             stages["pairs"] = dict(selection.pairs_stats, write_s=time.perf_counter() - t_pairs, pairs_selected=int(selection.pairs.size),
                                    kp=selecting["pairs"].k)
+            if selecting["pairs"].distinct:
+                stages["pairs"]["distinct"] = True
     if not annotating:
         request = None  # (from here on the request means the `features` column)
     if request is not None:

@@ -15,6 +15,7 @@
 #include "crp_select_edit.h"
 #include "crp_select_family.h"
 #include "crp_select_family_set.h"
+#include "crp_select_pairs_distinct.h"
 #include "crp_search_family.h"
 #include "crp_select_self.h"
 #include "crp_select_spaced.h"
@@ -127,6 +128,17 @@ struct crp_select {
     int kself = 0;        // of the last successful crp_select_run_self (0: none)
     int self_stride = 0;  // M + 1 of that run's handle
     double self_stats[7] = {};
+    // distinct pairs: results and buffers of crp_select_run_pairs_distinct, apart from the pair run's;
+    // the pass keys are the pair path's (d_pass_key)
+    crp::PairDistinctResult pd_res = {};  // n_pass, n_pairs, n_distinct: n_genes; pairs: n_genes * kpd * 2 of the last run
+    crp::PairDistinctRounds pd_rounds = {};
+    crp::PairItem *d_pd_items = nullptr;
+    crp::SelectMerge *d_pd_merge = nullptr;
+    unsigned long long *d_pd_evals = nullptr;
+    uint64_t pd_cap[11] = {};
+    uint64_t pd_items_per_launch = crp::SELECT_MAX_ITEMS;
+    int kpd = 0;  // of the last successful crp_select_run_pairs_distinct (0: none)
+    double pd_stats[12] = {};
 };
 
 namespace {
@@ -175,6 +187,34 @@ int check_run(crp_select *s, const crp_select_params *p, crp_search_self *self, 
             return fail(ctx, CRP_ERR_STATE, who + ": the joined columns belong to an earlier scan's tables");
     }
     return CRP_OK;
+}
+
+// What crp_select_run_pairs and crp_select_run_pairs_distinct ask of their arguments, of the handle's limits and of the arena.
+int check_pair_run(crp_select *s, const crp_select_params *p, const crp_select_pair_params *q, crp_search_self *self, crp::SelfJoined *joined,
+                   const char *who_c)
+{
+    crp_ctx *ctx = s->ctx;
+    const std::string who = who_c;
+    if (q->k < 1 || q->k > CRP_SELECT_PAIRS_MAX_K)
+        return fail(ctx, CRP_ERR_INVALID, who + ": k must be 1.." + std::to_string(CRP_SELECT_PAIRS_MAX_K) + ", not " + std::to_string(q->k));
+    if (q->dmin < 1 || q->dmin > q->dmax || q->dmax > CRP_SELECT_PAIRS_MAX_DISTANCE)
+        return fail(ctx, CRP_ERR_INVALID, who + ": the distances must be 1 <= dmin <= dmax <= " + std::to_string(CRP_SELECT_PAIRS_MAX_DISTANCE) +
+                                              ", not " + std::to_string(q->dmin) + " and " + std::to_string(q->dmax));
+    if (q->orientation_mask < 1 || q->orientation_mask > 0xFu)
+        return fail(ctx, CRP_ERR_INVALID, who + ": the orientation mask must be 1..15, not " + std::to_string(q->orientation_mask));
+    if (s->have_family_limits)
+        return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": family limits are relative to the gene and the pairs' eligibility key is per table row: "
+                                                    "clear them (crp_select_set_family_limits(select, NULL)) for a pair selection");
+    if (s->have_coding_limits)
+        return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": coding limits are relative to the gene and the pairs' eligibility key is per table row: "
+                                                    "clear them (crp_select_set_coding_limits(select, NULL)) for a pair selection");
+    if (s->have_edit_limits)
+        return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": edit limits are relative to the gene and the pairs' eligibility key is per table row: "
+                                                    "clear them (crp_select_set_edit_limits(select, NULL, NULL)) for a pair selection");
+    if (s->have_splice_limits)
+        return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": splice limits are relative to the gene and the pairs' eligibility key is per table row: "
+                                                    "clear them (crp_select_set_splice_limits(select, NULL, 0, NULL)) for a pair selection");
+    return check_run(s, p, self, joined, who_c);
 }
 
 // The two tables and the predicate of a run, as the kernels take them (k: the selection's K; the pair kernels do not read it).
@@ -311,7 +351,9 @@ int crp_select_destroy(crp_select *s)
                     s->d_set_best, s->d_set_start, s->d_set_slots, s->d_set_covered, s->spaced_res.n_pass, s->spaced_res.n_spaced, s->spaced_res.sel,
                     s->spaced_rounds.cuts, s->spaced_rounds.last, s->spaced_rounds.prop, s->spaced_rounds.slot_pass, s->spaced_rounds.picked,
                     s->d_spaced_items, s->d_spaced_merge, s->self_res.n_in, s->self_res.n_pass, s->self_res.sel, s->self_got.pos,
-                    s->self_got.hi, s->self_got.lo, s->self_got.counts, s->self_got.strand, s->self_got.sum, s->d_self_run};
+                    s->self_got.hi, s->self_got.lo, s->self_got.counts, s->self_got.strand, s->self_got.sum, s->d_self_run,
+                    s->pd_res.n_pass, s->pd_res.n_pairs, s->pd_res.n_distinct, s->pd_res.pairs, s->pd_rounds.prop, s->pd_rounds.slot_pass,
+                    s->pd_rounds.slot_pairs, s->pd_rounds.picked, s->d_pd_items, s->d_pd_merge, s->d_pd_evals};
     for (void *p : bufs) (void)hipFree(p);
     for (hipEvent_t e : s->ev)
         if (e) (void)hipEventDestroy(e);
@@ -585,27 +627,8 @@ int crp_select_run_pairs(crp_select *s, const crp_select_params *p, const crp_se
     crp_arena *a = s->arena;
     s->kp = 0;
     const std::string who = "crp_select_run_pairs";
-    if (q->k < 1 || q->k > CRP_SELECT_PAIRS_MAX_K)
-        return fail(ctx, CRP_ERR_INVALID, who + ": k must be 1.." + std::to_string(CRP_SELECT_PAIRS_MAX_K) + ", not " + std::to_string(q->k));
-    if (q->dmin < 1 || q->dmin > q->dmax || q->dmax > CRP_SELECT_PAIRS_MAX_DISTANCE)
-        return fail(ctx, CRP_ERR_INVALID, who + ": the distances must be 1 <= dmin <= dmax <= " + std::to_string(CRP_SELECT_PAIRS_MAX_DISTANCE) +
-                                              ", not " + std::to_string(q->dmin) + " and " + std::to_string(q->dmax));
-    if (q->orientation_mask < 1 || q->orientation_mask > 0xFu)
-        return fail(ctx, CRP_ERR_INVALID, who + ": the orientation mask must be 1..15, not " + std::to_string(q->orientation_mask));
-    if (s->have_family_limits)
-        return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": family limits are relative to the gene and the pairs' eligibility key is per table row: "
-                                                    "clear them (crp_select_set_family_limits(select, NULL)) for a pair selection");
-    if (s->have_coding_limits)
-        return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": coding limits are relative to the gene and the pairs' eligibility key is per table row: "
-                                                    "clear them (crp_select_set_coding_limits(select, NULL)) for a pair selection");
-    if (s->have_edit_limits)
-        return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": edit limits are relative to the gene and the pairs' eligibility key is per table row: "
-                                                    "clear them (crp_select_set_edit_limits(select, NULL, NULL)) for a pair selection");
-    if (s->have_splice_limits)
-        return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": splice limits are relative to the gene and the pairs' eligibility key is per table row: "
-                                                    "clear them (crp_select_set_splice_limits(select, NULL, 0, NULL)) for a pair selection");
     crp::SelfJoined joined = {};
-    int rc = check_run(s, p, self, &joined, who.c_str());
+    int rc = check_pair_run(s, p, q, self, &joined, who.c_str());
     if (rc != CRP_OK) return rc;
     CRP_HIP(ctx, hipSetDevice(ctx->device));
     const int k = q->k;
@@ -751,6 +774,202 @@ int crp_select_pairs_stats(const crp_select *s, double *out, int n)
 {
     if (!s || (n && !out) || n < 0 || n > 8) return CRP_ERR_INVALID;
     for (int k = 0; k < n; ++k) out[k] = s->pair_stats[k];
+    return CRP_OK;
+}
+
+/* ---- distinct pairs ---- */
+
+int crp_select_set_pair_distinct_limits(crp_select *s, uint64_t items_per_launch)
+{
+    if (!s || items_per_launch > crp::SELECT_MAX_ITEMS) return CRP_ERR_INVALID;
+    s->pd_items_per_launch = items_per_launch ? items_per_launch : crp::SELECT_MAX_ITEMS;
+    return CRP_OK;
+}
+
+int crp_select_run_pairs_distinct(crp_select *s, const crp_select_params *p, const crp_select_pair_params *q, crp_search_self *self)
+{
+    crp::Range roctx_range("crp: distinct guide pairs");
+    if (!s || !p || !q) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    crp_arena *a = s->arena;
+    s->kpd = 0;
+    const std::string who = "crp_select_run_pairs_distinct";
+    crp::SelfJoined joined = {};
+    int rc = check_pair_run(s, p, q, self, &joined, who.c_str());
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    const int k = q->k;
+    const uint64_t G = s->n_genes;
+    crp::PairDistinctResult &res = s->pd_res;
+    crp::PairDistinctRounds &rounds = s->pd_rounds;
+    rc = crp::grow(ctx, reinterpret_cast<void **>(&res.n_pass), &s->pd_cap[0], G, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&res.n_pairs), &s->pd_cap[1], G, sizeof(uint64_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&res.n_distinct), &s->pd_cap[2], G, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&res.pairs), &s->pd_cap[3], G * k * 2, sizeof(uint32_t));
+    if (rc != CRP_OK) return rc;
+    for (double &v : s->pd_stats) v = 0;
+    if (!G) {
+        s->kpd = k;
+        return CRP_OK;
+    }
+    // (a table has fewer rows than the arena positions: below 2^31)
+    const uint32_t n_plus = (uint32_t)a->n_hits[0], n_minus = (uint32_t)a->n_hits[1];
+    crp::SelectTable tab[2];
+    crp::SelectPredicate pred;
+    fill_predicate(s, p, self != nullptr, joined, 0, tab, &pred);
+    // the pass key of every row, once, in the pair path's buffers: this run writes them before it reads them
+    for (int t = 0; t < 2; ++t) {
+        rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_pass_key[t]), &s->pass_key_cap[t], a->n_hits[t], sizeof(uint64_t));
+        if (rc != CRP_OK) return rc;
+    }
+    CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    for (int t = 0; t < 2; ++t) CRP_HIP(ctx, crp::launch_pair_pass_key(ctx->stream, tab[t], pred, s->d_pass_key[t]));
+    CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+    s->pd_stats[5] += 2;
+    CRP_HIP(ctx, crp::launch_select_bounds(ctx->stream, a->d_pos[0], n_plus, a->d_pos[1], n_minus, s->d_lo, s->d_hi, (uint32_t)G, s->d_bounds));
+    std::vector<uint4> bounds;
+    std::vector<crp::PairItem> whole, pieces;
+    std::vector<crp::SelectMerge> merges;
+    std::vector<uint32_t> picked;
+    std::vector<unsigned long long> host64;
+    try {
+        bounds.resize(G);
+        rc = crp::staged_d2h(ctx, bounds.data(), s->d_bounds, G * sizeof(uint4));
+        if (rc != CRP_OK) return rc;
+        CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        s->pd_stats[0] = elapsed(s->ev[0], s->ev[1]);
+        // crp_select_run_pairs' cut of every gene's a-rows into pieces of at most pair_slice_rows rows, each with the gene's
+        // whole runs; the whole genes and the pieces of the cut genes in two lists, because only the pieces come back round
+        // after round.  The runs are checked against the tables here, before anything reads through them
+        whole.reserve(G);
+        for (uint64_t g = 0; g < G; ++g) {
+            const uint4 b = bounds[g];
+            if (b.x > b.y || b.y > n_plus || b.z > b.w || b.w > n_minus)
+                return fail(ctx, CRP_ERR_HIP, who + ": the bounds of gene " + std::to_string(g) + " lie outside the tables");
+            const uint64_t np = b.y - b.x, nm = b.w - b.z, total = np + nm;
+            const uint64_t n_pieces = std::max<uint64_t>(1, (total + s->pair_slice_rows - 1) / s->pair_slice_rows);
+            if (pieces.size() + n_pieces > 0xfffffff0ull)
+                return fail(ctx, CRP_ERR_UNSUPPORTED, who + ": more than 2^32 work items (raise pair_slice_rows)");
+            if (n_pieces > 1) merges.push_back(crp::SelectMerge{(uint32_t)g, (uint32_t)pieces.size(), (uint32_t)n_pieces});
+            for (uint64_t c = 0; c < n_pieces; ++c) {
+                // rows [r0, r1) of the gene's concatenated runs
+                const uint64_t r0 = c * s->pair_slice_rows, r1 = std::min(total, r0 + s->pair_slice_rows);
+                const uint64_t p0 = std::min(r0, np), p1 = std::min(r1, np);
+                const uint64_t m0 = std::max(r0, np) - np, m1 = std::max(r1, np) - np;
+                crp::PairItem it;
+                it.gene = (uint32_t)g;
+                it.slot = n_pieces > 1 ? (uint32_t)pieces.size() : crp::SELECT_NONE;
+                it.first[0] = b.x + (uint32_t)p0;
+                it.rows[0] = (uint32_t)(p1 - p0);
+                it.first[1] = b.z + (uint32_t)m0;
+                it.rows[1] = (uint32_t)(m1 - m0);
+                it.run[0] = b.x;
+                it.run[1] = b.y;
+                it.run[2] = b.z;
+                it.run[3] = b.w;
+                (n_pieces > 1 ? pieces : whole).push_back(it);
+            }
+        }
+        picked.resize(merges.size());
+        host64.resize(std::max<uint64_t>(whole.size() + pieces.size(), G));
+    } catch (const std::bad_alloc &) {
+        return CRP_ERR_NOMEM;
+    }
+    const uint64_t n_whole = whole.size(), n_pieces = pieces.size(), n_cut = merges.size(), per_launch = s->pd_items_per_launch;
+    rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_pd_items), &s->pd_cap[4], n_whole + n_pieces, sizeof(crp::PairItem));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_pd_merge), &s->pd_cap[5], n_cut, sizeof(crp::SelectMerge));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_pd_evals), &s->pd_cap[6], n_whole + n_pieces, sizeof(uint64_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&rounds.prop), &s->pd_cap[7], n_pieces, sizeof(crp::PairProposal));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&rounds.slot_pass), &s->pd_cap[8], n_pieces, sizeof(uint32_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&rounds.slot_pairs), &s->pd_cap[9], n_pieces, sizeof(uint64_t));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&rounds.picked), &s->pd_cap[10], n_cut, sizeof(uint32_t));
+    if (rc == CRP_OK && n_whole) rc = crp::staged_h2d(ctx, s->d_pd_items, whole.data(), n_whole * sizeof(crp::PairItem));
+    if (rc == CRP_OK && n_pieces) rc = crp::staged_h2d(ctx, s->d_pd_items + n_whole, pieces.data(), n_pieces * sizeof(crp::PairItem));
+    if (rc == CRP_OK && n_cut) rc = crp::staged_h2d(ctx, s->d_pd_merge, merges.data(), n_cut * sizeof(crp::SelectMerge));
+    if (rc != CRP_OK) return rc;
+    const crp::PairParams pp = {k, q->dmin, q->dmax, q->orientation_mask, q->frameshift ? 1u : 0u};
+    const auto timed = [&](double *sum) {
+        const double ms = elapsed(s->ev[0], s->ev[1]);
+        *sum += ms;
+        s->pd_stats[5] += 1;
+        s->pd_stats[6] = std::max(s->pd_stats[6], ms);
+    };
+    // the whole genes: every round inside one launch; the bounded-launch rule: at most 2^20 items a launch, each timed on its own
+    for (uint64_t first = 0; first < n_whole; first += per_launch) {
+        const uint32_t n = (uint32_t)std::min<uint64_t>(per_launch, n_whole - first);
+        CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+        CRP_HIP(ctx, crp::launch_pair_distinct_items(ctx->stream, a->d_pos[0], a->d_pos[1], s->d_pass_key[0], s->d_pass_key[1], pp, 0u,
+                                                     s->d_pd_items + first, n, s->d_pd_evals + first, rounds, res));
+        CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+        CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        timed(&s->pd_stats[1]);
+    }
+    // the cut genes: a step launch and a pick launch a round, until a round picks nothing
+    for (uint32_t round = 0; n_cut && round < (uint32_t)k; ++round) {
+        for (uint64_t first = 0; first < n_pieces; first += per_launch) {
+            const uint32_t n = (uint32_t)std::min<uint64_t>(per_launch, n_pieces - first);
+            CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+            CRP_HIP(ctx, crp::launch_pair_distinct_items(ctx->stream, a->d_pos[0], a->d_pos[1], s->d_pass_key[0], s->d_pass_key[1], pp, round,
+                                                         s->d_pd_items + n_whole + first, n, s->d_pd_evals + n_whole + first, rounds, res));
+            CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+            CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            timed(&s->pd_stats[2]);
+        }
+        for (uint64_t first = 0; first < n_cut; first += per_launch) {
+            const uint32_t n = (uint32_t)std::min<uint64_t>(per_launch, n_cut - first);
+            CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+            CRP_HIP(ctx, crp::launch_pair_distinct_pick(ctx->stream, s->d_pd_merge + first, n, (uint32_t)first, k, round, rounds, res));
+            CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+            CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            timed(&s->pd_stats[3]);
+        }
+        s->pd_stats[4] += 1;
+        rc = crp::staged_d2h(ctx, picked.data(), rounds.picked, n_cut * sizeof(uint32_t));
+        if (rc != CRP_OK) return rc;
+        CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (std::none_of(picked.begin(), picked.end(), [](uint32_t v) { return v != 0u; })) break;
+    }
+    s->pd_stats[7] = (double)(n_whole + n_pieces);
+    s->pd_stats[8] = (double)n_cut;
+    // the totals: partner rows streamed (per item, over all rounds), pairs taken and qualifying pairs (per gene), summed here
+    rc = crp::staged_d2h(ctx, host64.data(), s->d_pd_evals, (n_whole + n_pieces) * sizeof(uint64_t));
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint64_t i = 0; i < n_whole + n_pieces; ++i) s->pd_stats[9] += (double)host64[i];
+    rc = crp::staged_d2h(ctx, host64.data(), res.n_distinct, G * sizeof(uint32_t));
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint64_t g = 0; g < G; ++g) s->pd_stats[10] += (double)reinterpret_cast<const uint32_t *>(host64.data())[g];
+    rc = crp::staged_d2h(ctx, host64.data(), res.n_pairs, G * sizeof(uint64_t));
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (uint64_t g = 0; g < G; ++g) s->pd_stats[11] += (double)host64[g];
+    s->kpd = k;
+    return CRP_OK;
+}
+
+int crp_select_fetch_pairs_distinct(crp_select *s, uint32_t *n_pass, uint64_t *n_pairs, uint32_t *n_distinct, uint32_t *pairs)
+{
+    if (!s) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    if (!s->kpd)
+        return fail(ctx, CRP_ERR_STATE, "crp_select_fetch_pairs_distinct: no crp_select_run_pairs_distinct has succeeded on this handle");
+    if (!s->n_genes) return CRP_OK;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = CRP_OK;
+    if (n_pass) rc = crp::staged_d2h(ctx, n_pass, s->pd_res.n_pass, s->n_genes * sizeof(uint32_t));
+    if (rc == CRP_OK && n_pairs) rc = crp::staged_d2h(ctx, n_pairs, s->pd_res.n_pairs, s->n_genes * sizeof(uint64_t));
+    if (rc == CRP_OK && n_distinct) rc = crp::staged_d2h(ctx, n_distinct, s->pd_res.n_distinct, s->n_genes * sizeof(uint32_t));
+    if (rc == CRP_OK && pairs) rc = crp::staged_d2h(ctx, pairs, s->pd_res.pairs, s->n_genes * s->kpd * 2 * sizeof(uint32_t));
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CRP_OK;
+}
+
+int crp_select_pairs_distinct_stats(const crp_select *s, double *out, int n)
+{
+    if (!s || (n && !out) || n < 0 || n > 12) return CRP_ERR_INVALID;
+    for (int k = 0; k < n; ++k) out[k] = s->pd_stats[k];
     return CRP_OK;
 }
 

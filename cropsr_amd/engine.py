@@ -924,7 +924,9 @@ class Genome:
             if "family" in extras:  # (the device's values of the selected rows, the cover word among them)
                 part["family"] = extras["family"]
             if paired:
-                _, part["pair_n_pairs"], part["pair_list"], pst = paired[0]
+                _, part["pair_n_pairs"], part["pair_list"], pst, *distinct = paired[0]
+                if distinct:
+                    part["pair_n_distinct"] = distinct[0]
                 sel.sum_stats(pair_stats, pst)
             parts.append(part)
             sel.sum_stats(stats, st)
@@ -935,6 +937,8 @@ class Genome:
         if request.pairs is not None:
             out.pairs, out.n_pairs, out.pairs_repair = sel.assemble_pairs(len(labels), request.pairs.k, parts)
             out.pairs_stats = pair_stats
+            if request.pairs.distinct:
+                out.n_pairs_distinct = sel.assemble_n_distinct(len(labels), request.pairs.k, parts)
         if getattr(request, "family_sets", None) is not None:  # after the per-gene selection, while the self-search handles are open
             out.family_sets, out.family_complete, out.family_sets_stats = sel.family_sets(self, request, handle_of, hits, flags)
         return out

@@ -50,6 +50,25 @@ the same handle:
             pair two uint32 in the packing of sel (row | strand << 31), a then b, 0xFFFFFFFF beyond.  KP = 1..64,
             independent of K.  The top pairs may share one very good guide.
 
+Distinct pairs (csrc/crp_select_pairs_distinct.hip; tests/select_pairs_distinct_reference.py restates
+it twice): everything of the guide pairs stands -- eligible rows, the boundary c, qualifying pairs, the total order, n_pass
+and n_pairs.  New, per arena text and per layout row g:
+
+  distinct  walk the qualifying pairs of g in the pairs' order; take a pair iff NEITHER of its two rows is a row of a pair
+            already taken; stop at KP taken.  By rounds: round t takes the first qualifying pair in the order that has no
+            row among the picks of rounds < t.
+  row       a table row of one strand, in sel's packing row | strand << 31.  Two rows with equal boundaries (a '+' row at
+            i and the '-' row at i - 9) are different guides.  A row taken as the left guide a of one pair shuts out the
+            pairs that offer it as b, and the other way round.
+  result    per gene g: n_pass[g] and n_pairs[g] exactly as the pair selection gives them, whatever the picks;
+            n_distinct[g], the pairs taken, at most min(KP, n_pairs, n_pass // 2); and pairs[g][0..KP) in pick order,
+            0xFFFFFFFF beyond n_distinct.  The walk never goes back, so the picks are in the pairs' order.  At KP = 1 the
+            result is the pair selection's at KP = 1, bit for bit.
+  greedy    the best pair is always taken, whatever it shuts out.  A maximum-weight matching is another problem.
+  texts     a pair never spans texts, so pairs of different texts share no row: the greedy over a gene's union is the
+            merge of the per-text greedy lists in the pairs' order, and assemble_pairs takes its first KP as it does for
+            the plain pairs.  The summed n_distinct is capped at KP.
+
 Coding position (coding.py has the definition; csrc/crp_coding.h, csrc/crp_select_coding.hip): with
 coding limits a row passes for gene g only if, beyond the above, g has a coding model, the row's cut boundary (repair.py's c)
 is inside the coding sequence of g's primary transcript, its coding offset lies within the given percentages of that
@@ -170,9 +189,14 @@ class Params:
 
 class PairParams:
     """What a pair selection asks for: KP, the window dmin <= D <= dmax on the deletion length, frameshift (D mod 3 != 0)
-    and the orientation: "any", "pam-out", "pam-in", or a 4-bit mask over (strand of a, strand of b), bit sa * 2 + sb."""
+    and the orientation: "any", "pam-out", "pam-in", or a 4-bit mask over (strand of a, strand of b), bit sa * 2 + sb.
+    distinct: the KP pairs of a gene share no guide (the module's "Distinct pairs"); a scan then runs the distinct pair
+    selection instead of the plain one."""
 
-    def __init__(self, k, dmin=50, dmax=500, frameshift=False, orientation="any"):
+    def __init__(self, k, dmin=50, dmax=500, frameshift=False, orientation="any", distinct=False):
+        if not isinstance(distinct, (bool, np.bool_)):
+            raise ValueError("distinct is True or False, not %r" % (distinct,))
+        self.distinct = bool(distinct)
         self.k = int(k)
         if not 1 <= self.k <= MAX_KP:
             raise ValueError("KP must be 1..%d, not %d" % (MAX_KP, self.k))
@@ -383,6 +407,7 @@ class ArenaSelect:
         if lo.shape != hi.shape or lo.ndim != 1:
             raise ValueError("lo and hi must be 1-d arrays of one length")
         self.n_genes, self.k, self.kp, self.ks = int(lo.size), 0, 0, 0
+        self.kpd = 0  # KP of the last run_pairs_distinct
         self.kself, self._self_stride = 0, 1  # of the last run_self
         h = ctypes.c_void_p()
         nat.check(nat.lib().crp_select_create(arena._h, lo.ctypes.data_as(nat.u32p), hi.ctypes.data_as(nat.u32p), lo.size, ctypes.byref(h)),
@@ -683,6 +708,33 @@ class ArenaSelect:
         keys = ("pass_key_ms", "pairs_ms", "merge_ms", "items", "launches", "longest_launch_ms", "pair_evaluations", "qualifying_pairs")
         return dict(zip(keys, (float(v) for v in out)))
 
+    def set_pair_distinct_limits(self, items_per_launch=0):
+        nat.check(nat.lib().crp_select_set_pair_distinct_limits(self._h, int(items_per_launch)), "crp_select_set_pair_distinct_limits", self._ctx)
+
+    def run_pairs_distinct(self, params, pair_params, self_search=None):
+        """As run_pairs(); the KP pairs of a gene share no guide (pair_params.distinct is not read)."""
+        p, q = params.native(), pair_params.native()
+        nat.check(nat.lib().crp_select_run_pairs_distinct(self._h, ctypes.byref(p), ctypes.byref(q),
+                                                          self_search._h if self_search is not None else None),
+                  "crp_select_run_pairs_distinct", self._ctx)
+        self.kpd = pair_params.k
+
+    def fetch_pairs_distinct(self):
+        """(n_pass uint32 (G,), n_pairs uint64 (G,), n_distinct uint32 (G,), pairs uint32 (G, KP, 2)) of the last run_pairs_distinct."""
+        n_pass, n_pairs, n_distinct = np.empty(self.n_genes, np.uint32), np.empty(self.n_genes, np.uint64), np.empty(self.n_genes, np.uint32)
+        pairs = np.empty((self.n_genes, max(1, self.kpd), 2), np.uint32)
+        nat.check(nat.lib().crp_select_fetch_pairs_distinct(self._h, n_pass.ctypes.data_as(nat.u32p), n_pairs.ctypes.data_as(nat.u64p),
+                                                            n_distinct.ctypes.data_as(nat.u32p), pairs.ctypes.data_as(nat.u32p)),
+                  "crp_select_fetch_pairs_distinct", self._ctx)
+        return n_pass, n_pairs, n_distinct, pairs
+
+    def pairs_distinct_stats(self):
+        out = np.zeros(12, dtype=np.float64)
+        nat.check(nat.lib().crp_select_pairs_distinct_stats(self._h, out.ctypes.data_as(nat.f64p), 12), "crp_select_pairs_distinct_stats", self._ctx)
+        keys = ("pass_key_ms", "distinct_items_ms", "distinct_step_ms", "distinct_pick_ms", "distinct_rounds", "launches", "longest_launch_ms",
+                "items", "cut_genes", "pair_evaluations", "pairs_taken", "qualifying_pairs")
+        return dict(zip(keys, (float(v) for v in out)))
+
 
 def arena_layout(genome, a):
     """[(contig index, arena offset, length)] of arena `a` of an engine.Genome, as annotate.Request.track takes it."""
@@ -701,6 +753,7 @@ class Selection:
     to the contig string), with counts (n, M + 1) uint32 and hit_sum (n,) uint64 of the rows when they were joined, and
     mh / oof (n,) uint32 of the rows when the repair scores were fetched (None otherwise).  With a pair selection: pairs
     (PAIR_DTYPE, gene after gene, rank 1 first; a is the left guide), n_pairs (per gene, all qualifying pairs), pairs_stats
+    (with PairParams(distinct=True) the distinct run's, and n_pairs_distinct: per gene the pairs taken, at most KP)
     and, when the repair scores were fetched, pairs_repair (n, 2) uint64, packed, of a and b; None otherwise.  With the
     coding position (coding.py): cds_offset (coding.NOT_INSIDE where the cut is not inside the primary transcript),
     cds_length, transcripts_cut and transcripts (n,) uint32 of the rows, for the gene each was selected for; None otherwise.
@@ -715,7 +768,7 @@ class Selection:
         self.mh, self.oof = mh, oof
         self.variants = None  # (n,) uint32, packed (variants.unpack), of the rows when the variant counts were fetched
         self.guide_sites = self.assay_enzymes = None  # (n,) uint32 masks (sites.unpack) of the rows when the site column was fetched
-        self.pairs = self.n_pairs = self.pairs_repair = None
+        self.pairs = self.n_pairs = self.pairs_repair = self.n_pairs_distinct = None
         self.pairs_stats = {}
         self.cds_offset = self.cds_length = self.transcripts_cut = self.transcripts = None
         self.edit_targets = self.stop_codons = self.stop_offset = None
@@ -919,11 +972,25 @@ def assemble_pairs(n_genes, kp, arenas):
     return pairs, n_pairs, repair
 
 
+def assemble_n_distinct(n_genes, kp, arenas):
+    """Per gene the distinct pairs taken (int64): the sum of pair_n_distinct over the gene's texts, capped at KP -- pairs of
+    different texts share no row, so the merged list holds that many."""
+    total = np.zeros(n_genes, np.int64)
+    for a in arenas:
+        np.add.at(total, np.asarray(a["gene"], dtype=np.int64), np.asarray(a["pair_n_distinct"]).astype(np.int64))
+    return np.minimum(total, kp)
+
+
 def select_arena_pairs(sel, request, handle=None):
     """The pair selection of one arena on the ArenaSelect that has just run the single-guide selection (its flags and
-    limits are set): (n_pass, n_pairs, pairs, stats)."""
+    limits are set): (n_pass, n_pairs, pairs, stats).  With request.pairs.distinct the distinct run INSTEAD of the plain
+    one -- it returns n_pass and n_pairs itself -- and a fifth element, n_distinct."""
     if request.pair_slice_rows:
         sel.set_pair_limits(request.pair_slice_rows)
+    if getattr(request.pairs, "distinct", False):
+        sel.run_pairs_distinct(request.params, request.pairs, handle)
+        n_pass, n_pairs, n_distinct, pairs = sel.fetch_pairs_distinct()
+        return n_pass, n_pairs, pairs, sel.pairs_distinct_stats(), n_distinct
     sel.run_pairs(request.params, request.pairs, handle)
     return sel.fetch_pairs() + (sel.pairs_stats(),)
 

@@ -977,6 +977,40 @@ int crp_select_fetch_pairs(crp_select *select, uint32_t *n_pass, uint64_t *n_pai
  * in ms, out[6] pair evaluations (partner rows streamed), out[7] qualifying pairs.  n: how many to write (<= 8). */
 int crp_select_pairs_stats(const crp_select *select, double *out, int n);
 
+/* ---- distinct pairs: KP pairs per gene that share no guide (opt-in) ----------------------- */
+/* crp_select_run_pairs ranks a gene's pairs one by one, and its best pairs may share one very good guide: constructs that
+ * fail together when that guide fails.  Everything of the pair selection stands -- eligible rows, the boundary c, qualifying
+ * pairs, the total order, n_pass and n_pairs.  New, per layout row g:
+ *   distinct   walk the qualifying pairs of g in that order; take a pair iff NEITHER of its two rows is a row of a pair
+ *              already taken; stop at KP taken.  (Round t takes the first qualifying pair in the order that has no row
+ *              among the picks of rounds < t.)
+ *   row        a table row of one strand, in sel's packing row | strand << 31: a '+' row at i and the '-' row at i - 9 have
+ *              equal boundaries and are different guides.  A row taken as the left guide a of one pair shuts out the
+ *              pairs that offer it as b, and the other way round.
+ * Per gene: n_pass and n_pairs exactly as crp_select_run_pairs gives them, whatever the picks; n_distinct, the pairs
+ * taken, at most min(KP, n_pairs, n_pass / 2); and pairs[g * KP * 2 ..) in pick order, which is the pairs' order,
+ * 0xFFFFFFFF beyond n_distinct.  At KP = 1 the result is crp_select_run_pairs' at KP = 1 bit for bit.  Exact and
+ * integer-only: the result does not depend on how the work was cut.  Greedy: the best pair is always taken, whatever it
+ * shuts out; not a maximum-weight matching. */
+/* Prerequisites, parameter checks, refusals and error codes are exactly crp_select_run_pairs' (one host function checks
+ * both).  Genes are cut into items by crp_select_set_pair_limits' pair_slice_rows; a gene in one item runs all its rounds
+ * in one launch, the others take a step launch and a pick launch a round: at most 2 KP + 3 launches per block of
+ * items_per_launch items.  The run has buffers and results of its own: those of crp_select_run, _run_pairs, _run_spaced,
+ * _run_self and the family step stay valid before and after it. */
+int crp_select_run_pairs_distinct(crp_select *select, const crp_select_params *params, const crp_select_pair_params *pair_params,
+                                  crp_search_self *self);
+/* The results of the last crp_select_run_pairs_distinct (CRP_ERR_STATE without one): n_pass, n_pairs and n_distinct
+ * (n_genes each) and pairs (n_genes * KP * 2).  Any pointer may be NULL. */
+int crp_select_fetch_pairs_distinct(crp_select *select, uint32_t *n_pass, uint64_t *n_pairs, uint32_t *n_distinct, uint32_t *pairs);
+/* Measurement of the last crp_select_run_pairs_distinct: out[0] ms of the pass-key kernel, out[1] ms of the whole-gene item
+ * launches, out[2] ms of the cut genes' step launches, out[3] ms of their pick launches (HIP events), out[4] host rounds,
+ * out[5] kernel launches, out[6] the longest launch in ms, out[7] work items, out[8] cut genes, out[9] partner rows
+ * streamed, summed over all rounds, out[10] pairs taken, out[11] qualifying pairs.  n: how many to write (<= 12). */
+int crp_select_pairs_distinct_stats(const crp_select *select, double *out, int n);
+/* At most items_per_launch work items per launch of the distinct pair run (0 = the default and the most, 2^20; more:
+ * CRP_ERR_INVALID).  Results do not depend on it. */
+int crp_select_set_pair_distinct_limits(crp_select *select, uint64_t items_per_launch);
+
 /* ---- spaced selection: K guides per gene whose cut sites lie at least D apart (opt-in) --- */
 /* crp_select_run's K best rows of a gene cluster: a good 30-mer context lifts its neighbours.  On a crp_select handle,
  * over the same tables and genes, per layout row g:
