@@ -14,7 +14,9 @@ LAYOUT    restated here as the device lays an arena out: word 0 is a separator, 
 PLACEMENT straddle: the filler's length puts hp_tie at 2^30 - TIE_AT;  top: it makes the arena exactly max_words words long,
           so hp_tail's text ends in the last word that holds text.
 Results are contig-relative, so the references of the suite run on the case contigs alone; contig k of the cases is contig
-k + 1 of the device's genome."""
+k + 1 of the device's genome.  The references that take arena positions -- the spaced selection, the distinct pairs, the self
+selection -- run on the case contigs' tables at their placed positions (arena_tables), and the restriction-site reference on the
+same letters moved down by a multiple of 64 (tests/high_position_site_cases.py has its enzymes and flanks)."""
 import numpy as np
 
 import specificity_join_cases as join_cases

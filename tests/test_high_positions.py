@@ -3,7 +3,16 @@ placements -- "straddle", where arena position 2^30 falls between the two copies
 arena is as long as the library accepts and every case position lies within 2^20 of 2^31.  Expected values come from the suite's
 references run on the case contigs alone (results are contig-relative); every comparison is exact.  The tests without a GPU
 prove on the references' own rows that the GPU tests are not vacuous: the ties, the keys on both sides of 2^30, the windows
-that reach past the last text word."""
+that reach past the last text word.
+
+Covered on the GPU, each at both placements on one upload and one scan: the hit tables; guide properties and repair scores;
+the annotation look-up; the off-target seeds and counts; the given-guide searches (plain, scored, pair table, bulges); the self
+search and the specificity join; the family rows, join and selection; the plain, pair, coding, edit and splice selections and
+their evaluation kernels; the selection behind the join; the variant counts; the family step; the restriction-site planes,
+ranks and columns (crp_sites.hip: eight enzymes of tests/high_position_site_cases.py, every flank, the index over every word of
+the arena, and the plain selection over the resident column); the spaced selection (crp_select_spaced.hip); the distinct
+pairs (crp_select_pairs_distinct.hip); and the self selection (crp_select_self.hip), at the handle and through
+search.search_self(select=...)."""
 import numpy as np
 import pytest
 
@@ -12,6 +21,7 @@ import family_reference as fref
 import family_set_reference as fsr
 import guide_properties_reference as gref
 import high_position_cases as hp
+import high_position_site_cases as hs
 import repair_reference as rref
 import search_bulge_reference as bref
 import search_pair_reference as pref
@@ -19,8 +29,13 @@ import search_reference as ref
 import search_score_reference as sref
 import search_self_reference as selfref
 import select_coding_reference as cref
+import select_pairs_distinct_reference as dref
 import select_pairs_reference as pairs_ref
 import select_reference as selref
+import select_self_cases as self_cases
+import select_self_reference as ssref
+import select_spacing_reference as spacing_ref
+import site_reference as site_ref
 import specificity_join_cases as join_cases
 import splice_edit_reference as spref
 import variant_reference as vref
@@ -29,6 +44,8 @@ from cropsr_amd import annotate, baseedit, coding
 from cropsr_amd import families as fam
 from cropsr_amd import search as srch
 from cropsr_amd import select as sel
+from cropsr_amd import select_self as ss
+from cropsr_amd import sites
 
 NONE = 0xFFFFFFFF
 L = 20
@@ -48,6 +65,20 @@ BOUNDS = (0, sel.max_hit_sum_for(0.5))  # max_perfect 0, min_specificity 0.5
 VARIANT_SEED = 12
 ALL_ONES = (1 << 64) - 1
 NO_FILLER = "no-filler"  # Case.layout's third placement: the case contigs alone (tests/test_select_predicate_matrix.py); not in hp.PLACEMENTS
+TWIN = hp.COPY[1] - hp.COPY[0]  # a row of the tie block and its twin in the other copy lie exactly this far apart
+SPACINGS = (0, 1, 30, TWIN, TWIN + 1)
+KP_DISTINCT = (1, 5, 33)
+SELF_T, SELF_P, SELF_CUT = L + 3, 3, 17  # PATTERN's geometry: the cut letter is i - 3 of a '+' site and j + 6 of a '-' site
+SELF_REGION = ssref.region_mask(SELF_T, SELF_P, True)
+SELF_HANDLES = [(0, True), (0, False), (3, True), (3, False)]  # (M, scored)
+# the limit runs of the self selection, and n_pass of every layout row under each (None: no limit; without mismatches every
+# hit sum is 0 and the bound drops nothing) -- test_self_selection_holds_its_cases
+SELF_LIMITS = dict(perfect=dict(max_mm0=0), hit_sum=dict(max_hit_sum=BOUNDS[1]), sequence=dict(gc_min=9, gc_max=12, max_t_run=2), cds=dict(cds=True))
+SELF_N_PASS = {None: [362, 107, 107, 110, 149, 21], "perfect": [357, 0, 0, 104, 146, 21], "hit_sum": [358, 107, 107, 108, 147, 21],
+               "sequence": [144, 28, 28, 64, 62, 12], "cds": [227, 107, 107, 0, 122, 0]}
+# of the tie gene's 107 guide sites, this many of the first copy and one fewer of the second share the best e: at this K the
+# K-th site and the first one left out lie on either side of 2^30, below it both lie in the first copy
+SELF_TIE_K = {0: 54, 3: 53}
 
 
 class Case:
@@ -134,6 +165,22 @@ class Case:
     def self_search(self, M, scored):
         return self.once(("self", M, scored), lambda: selfref.search_self(self.contigs, PATTERN, M, 3, GUIDE_PATTERN, sref.W_HSU if scored else None))
 
+    def self_columns(self, M, scored):
+        """The rows of self_search(M, scored) as select_self_reference takes them, but for the arena positions: contig, forward
+        start in the contig, strand, hi, lo (the guide's letters, A = 00 T = 01 C = 10 G = 11, letter k at bit k), counts, hit_sum."""
+        def make():
+            sites, guides, counts, hit_sum = self.self_search(M, scored)
+            code = {"A": 0, "T": 1, "C": 2, "G": 3}
+            hi = np.array([sum((code[ch] >> 1) << k for k, ch in enumerate(g)) for g in guides], np.uint32)
+            lo = np.array([sum((code[ch] & 1) << k for k, ch in enumerate(g)) for g in guides], np.uint32)
+            contig, start, strand = (np.array(x, np.int64) for x in zip(*sites))
+            return dict(contig=contig, start=start, strand=strand.astype(np.uint8), hi=hi, lo=lo, counts=np.asarray(counts, np.uint32),
+                        hit_sum=None if hit_sum is None else np.array([int(x) for x in hit_sum], np.uint64))
+        return self.once(("self_columns", M, scored), make)
+
+    def enzymes(self):
+        return self.once("enzymes", lambda: hs.enzymes(self.contigs, self.hits))
+
     def join(self, M, kind):
         score = {"none": None, "hsu2013": "hsu2013", "pair": self.pair}[kind]
         return self.once(("join", M, kind), lambda: join_cases.join(self.hits, join_cases.rows(self.contigs, L, M, "NRG", score), L, M))
@@ -208,6 +255,68 @@ class Placed:
 
     def pairs(self, K):
         return self.once(("pairs", K), lambda: pairs_ref.pairs_numpy(self.tables, self.lo, self.hi, K, *PAIR_WINDOW))
+
+    def joined_spec(self, bounds):
+        return None if bounds is None else dict(self.spec(), max_mm0=bounds[0], max_hit_sum=bounds[1])
+
+    def spaced(self, K, D, min_score=0.0, bounds=None):
+        """spaced_numpy; bounds as select()."""
+        return self.once(("spaced", K, D, min_score, bounds),
+                         lambda: spacing_ref.spaced_numpy(self.tables, self.lo, self.hi, K, D, min_score, self.joined_spec(bounds)))
+
+    def distinct(self, K):
+        return self.once(("distinct", K), lambda: dref.distinct_numpy(self.tables, self.lo, self.hi, K, *PAIR_WINDOW))
+
+    def site_columns(self, flank):
+        """Per strand site_reference.columns_numpy of Case.enzymes() over the letters moved down by `base`."""
+        return self.once(("sites", flank), lambda: hs.columns(self, [m for _, m in self.case.enzymes()], flank))
+
+    def select_sites(self, K, flank, forbid, need):
+        """select_numpy over the rows whose reference masks at `flank` pass (forbid, need)."""
+        def make():
+            col = self.site_columns(flank)
+            also = {s: site_ref.passes_numpy(col[s]["value"], forbid, need) for s in ("plus", "minus")}
+            cds = dict(feat_plus=also["plus"].astype(np.uint32), feat_minus=also["minus"].astype(np.uint32), flags=np.array([0, 1], np.uint8))
+            return selref.select_numpy(self.tables, self.lo, self.hi, K, 0.0, None, cds)
+        return self.once(("select_sites", K, flank, forbid, need), make)
+
+    def candidates(self):
+        """(arena start, strand) of every candidate of PATTERN in extraction order: the case contigs' (the filler has none)."""
+        return self.once("candidates", lambda: self_cases.candidates(self.case.contigs, self.offsets, PATTERN))
+
+    def self_rows(self, M, scored):
+        """The reference's guide sites at their arena positions, as select_self_reference's rows: in the device's extraction
+        order, with each site's index among the candidates of PATTERN on the case contigs (the filler has none)."""
+        def make():
+            c = self.case.self_columns(M, scored)
+            pos = c["start"] + np.array(self.offsets, np.int64)[c["contig"]]
+            key = ((pos >> 6) << 7) | (c["strand"].astype(np.int64) << 6) | (pos & 63)  # by (64-position word, strand, position)
+            order = np.argsort(key, kind="stable")
+            assert np.unique(key).size == key.size
+            cpos, cstrand = self.candidates()
+            where = {(int(a), int(b)): i for i, (a, b) in enumerate(zip(cpos, cstrand))}
+            cand = np.array([where[(int(a), int(b))] for a, b in zip(pos[order], c["strand"][order])], np.uint32)
+            assert (np.diff(cand.astype(np.int64)) > 0).all()
+            return dict(pos=pos[order].astype(np.uint32), strand=c["strand"][order], hi=c["hi"][order], lo=c["lo"][order], counts=c["counts"][order],
+                        hit_sum=None if c["hit_sum"] is None else c["hit_sum"][order], cand=cand)
+        return self.once(("self_rows", M, scored), make)
+
+    def cds_track(self):
+        """(points, ids, flags): the module's annotation over the device's layout -- the filler, then the case contigs at
+        their arena positions -- and its CDS flags."""
+        def make():
+            c = self.case
+            request = annotate.Request(c.annotation, [hp.FILLER_NAME] + c.names, 0)
+            layout = [(0, 64, self.filler)] + [(k + 1, o, n) for k, (o, n) in enumerate(zip(self.offsets, c.lengths))]
+            return tuple(request.track(layout)) + (c.annotation.cds_flags(),)
+        return self.once("cds_track", make)
+
+    def self_spec(self, K, cds=False, **limits):
+        return ssref.spec(SELF_T, SELF_CUT, SELF_REGION, K, track=self.cds_track() if cds else None, **limits)
+
+    def self_select(self, M, scored, K, **limits):
+        key = ("self_select", M, scored, K, tuple(sorted(limits.items())))
+        return self.once(key, lambda: ssref.select_numpy(self.self_rows(M, scored), self.lo, self.hi, self.self_spec(K, **limits)))
 
     def positions(self):
         return self.once("positions", lambda: cref.positions_numpy(self.tables, self.case.models, self.rows))
@@ -523,6 +632,215 @@ def test_family_step_ties_lie_across_two30(case):
         want = fsr.arena_best(cands, case.sizes, covered, 0)
         assert want[homeo] is not None and want[homeo]["gain"] == 1 and (want[twins] is None) == (bit != 0)
     assert fsr.arena_best(cands, case.sizes, [0, 0], 0)[homeo]["gain"] == 3
+
+
+def _bit(mask, e):
+    return (np.asarray(mask, np.uint32) >> np.uint32(e)) & np.uint32(1)
+
+
+def test_site_columns_hold_their_cases(case):
+    """On site_reference's own columns.  The two cut-out motifs occur once in either copy of the tie block and nowhere else;
+    every other enzyme has rows with its in_guide bit set and clear on both strands.  At `straddle` and flank 1000 four rows per
+    strand have a cut-out site across their cut and an amplicon that crosses 2^30 -- a_lo < 2^30 <= the last start a_hi - m -- with
+    exactly one occurrence in it, so their assay bit stands on rank(q_hi) - rank(a_lo) across the chunk whose scanned sum
+    begins another trip of the rank scan (2^30 is a multiple of 256 chunks of 1 024 words); no other enzyme has such a row.  At
+    flank 100000 the same rows count 2 and lose the bit, at 300 they count 1 without crossing."""
+    enzymes = case.enzymes()
+    names, motifs = [n for n, _ in enzymes], [m for _, m in enzymes]
+    assert names == [n for n, _ in hs.FIXED] + list(hs.CUT_OUT) and len(enzymes) == 8 and len(set(motifs)) == 8
+    for m in motifs[-2:]:
+        assert len(m) == 8 and set(m) <= set("ACGT") and [hs.count_in(t, m) for t in case.contigs] == [0, 2, 0, 0, 0], m
+    stretch = bytes(hp.filler(5000))
+    assert [hs.count_in(stretch, m) for m in motifs] == [4997, 4985, 0, 0, 0, 0, 0, 0]  # poly_a and span16 at every filler position
+    assert sites.is_palindrome("AGCT") and not sites.is_palindrome("CCTC") and not sites.is_palindrome("AAAA") and sites.is_palindrome("CCWGG")
+    rows_of = hs.cut_out_rows(case.hits)
+    for name in hp.PLACEMENTS:
+        p = case.placed(name)
+        for flank in hs.FLANKS:
+            col = p.site_columns(flank)
+            assert col["plus"]["value"].size == 414 and col["minus"]["value"].size == 462
+            # in_guide does not depend on the flank or on the placement
+            assert [int(_bit(col["plus"]["in_guide"], e).sum()) for e in range(8)] == [63, 193, 26, 61, 19, 16, 4, 0], (name, flank)
+            assert [int(_bit(col["minus"]["in_guide"], e).sum()) for e in range(8)] == [83, 213, 50, 54, 13, 20, 4, 0], (name, flank)
+        assert [int(_bit(p.site_columns(16)[s]["assay"], 1).sum()) for s in ("plus", "minus")] == [105, 119]  # span16 at the smallest flank
+        # the plain loop over strings on every third row, at the flank of the crossing rows
+        occ = site_ref.occurrences_loop(p.local_arena, motifs)
+        for s in ("plus", "minus"):
+            pos = p.local_tables["pos_" + s][::3]
+            assert np.array_equal(site_ref.column_loop(p.local_arena, hs.local_bounds(p), pos, s == "minus", L, hs.CROSSING_FLANK, motifs, occ),
+                                  p.site_columns(hs.CROSSING_FLANK)[s]["value"][::3]), (name, s)
+        for s, e in (("plus", 6), ("minus", 7)):
+            first = int(p.rows_before[s][hp.TIE])
+            for flank, crossing, amp in ((300, False, 1), (hs.CROSSING_FLANK, name == "straddle", 1), (100000, name == "straddle", 2)):
+                col = p.site_columns(flank)[s]
+                a_lo, last_start, cut = hs.amplicon(p, s, flank, 8)
+                cross = (a_lo < hp.TWO30) & (hp.TWO30 <= last_start)
+                spanning = np.flatnonzero(col["span"][:, e] >= 1)
+                assert spanning.size == 4 and first + rows_of[s] in spanning.tolist(), (name, s, flank)  # two rows at either copy
+                assert (col["amp"][spanning, e] == amp).all() and (_bit(col["assay"], e)[spanning] == (amp == 1)).all(), (name, s, flank)
+                assert int(_bit(col["assay"], e).sum()) == (4 if amp == 1 else 0)
+                assert (cross[spanning] == crossing).all(), (name, s, flank)
+                if flank == hs.CROSSING_FLANK:  # the six other enzymes: rows cross, none with a spanning site and a count of 1
+                    for other in range(6):
+                        a_lo, last_start, _ = hs.amplicon(p, s, flank, len(motifs[other]))
+                        cross = (a_lo < hp.TWO30) & (hp.TWO30 <= last_start)
+                        assert int(cross.sum()) == ((44 if s == "plus" else 64) if name == "straddle" else 0)
+                        assert not (cross & (col["span"][:, other] >= 1) & (col["amp"][:, other] == 1)).any()
+        # the selection of test_gpu_site_columns: eight rows of either tie gene have a cut-out assay at flank 1000, four of them a
+        # four-cutter in their guide; the four left are '-' rows, two in either copy
+        forbid, need = hs.mask(names, hs.FOUR_CUTTERS), hs.mask(names, hs.CUT_OUT)
+        assert (forbid, need) == (0b1100, 0b11000000)
+        assert p.select_sites(5, hs.CROSSING_FLANK, 0, need)[1].tolist() == [0, 8, 8, 0, 0, 0]
+        assert p.select_sites(5, hs.CROSSING_FLANK, forbid, 0)[1].tolist() == [279, 84, 84, 84, 127, 14] and p.select(5)[1].tolist() == [360, 108, 108, 118, 149, 20]
+        n_in, n_pass, picked = p.select_sites(5, hs.CROSSING_FLANK, forbid, need)
+        assert n_pass.tolist() == [0, 4, 4, 0, 0, 0] and (picked[1][:4] >> 31 == 1).all() and picked[1][4] == NONE
+        assert sorted(_cut(p.tables, x) < hp.TWO30 for x in picked[1][:4]) == ([False, False, True, True] if name == "straddle" else [False] * 4)
+    # top: the last '+' row of hp_tail has its window of the occurrence planes in the last word that holds text, and its
+    # amplicon ends at the text's end at every flank
+    t = case.placed("top")
+    pos = int(t.tables["pos_plus"][-1])
+    cut, end = pos - 3, t.offsets[-1] + hp.TAIL_LEN
+    assert min(pos - L, cut - 15) >> 6 == t.words - 2 == (end - 1) >> 6 and all(cut + flank >= end for flank in hs.FLANKS)
+    assert hs.amplicon(t, "plus", 16, 4)[1][-1] == end - 4
+
+
+def test_site_columns_need_the_texts_bounds(case):
+    """Clipping the amplicon at the text's start decides masks.  Stated on the moved-down letters with a run of A and a separator
+    word in front of sj_c0, as the filler lies on the device: with the bounds replaced by one text over everything, at flank 300
+    one row per strand gets another mask.  It is a row of hp_tail, whose amplicon then reaches over the separator word into
+    sj_c2; no row of sj_c0 within 300 letters of its start has a site across its cut and a count of 1, so none of them changes
+    (the issue expected them there; the reference says otherwise)."""
+    p = case.placed("straddle")
+    motifs = [m for _, m in case.enzymes()]
+    lead = 1024
+    arena = b"\0" * 64 + b"A" * (lead - 128) + b"\0" * 64 + p.local_arena[64:]
+    bounds = [(a + lead - 64, b + lead - 64) for a, b in hs.local_bounds(p)]
+    assert arena[bounds[0][0]:bounds[0][1]] == case.contigs[0] and arena[bounds[-1][0]:bounds[-1][1]] == case.contigs[-1]
+    real = hs.columns(p, motifs, 300, bounds, arena, lead - 64)
+    for s in ("plus", "minus"):
+        assert np.array_equal(real[s]["value"], p.site_columns(300)[s]["value"])  # what lies in front of the first text changes nothing
+    one = hs.columns(p, motifs, 300, [(0, len(arena))], arena, lead - 64)
+    for s, row, was, now in (("plus", 405, 0x80000000B, 0xB), ("minus", 455, 0x10000000B, 0xB)):
+        changed = np.flatnonzero(real[s]["value"] != one[s]["value"])
+        assert changed.tolist() == [row] and row >= p.rows_before[s][-2], s
+        assert (int(real[s]["value"][row]), int(one[s]["value"][row])) == (was, now)
+        a_lo, _, cut = hs.amplicon(p, s, 300, 4)
+        assert a_lo[row] == p.offsets[-1] > cut[row] - 300  # clipped at the start of its text
+
+
+def test_spaced_selection_holds_its_cases(case):
+    """spaced_numpy equals spaced_loop; D = 0 is the plain selection; at `straddle` the tie gene's picks lie on both sides of
+    2^30 for every D; a row's twin is exactly TWIN away, so D = TWIN takes it second and D = TWIN + 1 cannot; at D = 0 the K-th
+    pick and the first row left out have bit-equal scores and cut sites on either side of 2^30."""
+    for name in hp.PLACEMENTS:
+        p = case.placed(name)
+        k = p.ids.index("tie")
+        for K in KS:
+            for D in SPACINGS:
+                want = p.spaced(K, D)
+                loop = spacing_ref.spaced_loop(p.tables, p.lo, p.hi, K, D)
+                assert all(np.array_equal(a, b) for a, b in zip(want, loop)), (name, K, D)
+                picks = want[2][k][want[2][k] != NONE]
+                below = sum(_cut(p.tables, x) < hp.TWO30 for x in picks)
+                if name == "straddle":
+                    expected = {0: {1: (1, 0), 5: (3, 2), 33: (17, 16), 64: (32, 32)}[K], 1: {1: (1, 0), 5: (3, 2), 33: (17, 16), 64: (32, 32)}[K],
+                                30: {1: (1, 0), 5: (3, 2), 33: (9, 9), 64: (9, 9)}[K]}.get(D, (1, 0) if K == 1 else (1, 1))
+                    assert (below, len(picks) - below) == expected, (K, D)
+                else:
+                    assert below == 0 and len(picks) == int(want[1][k]) > 0
+            n_in, n_pass, picked = p.select(K)
+            assert np.array_equal(p.spaced(K, 0)[0], n_pass) and np.array_equal(p.spaced(K, 0)[2], picked)
+            assert np.array_equal(p.spaced(K, 0)[1], np.minimum(n_pass, K))
+            bounded = p.spaced(K, 30, 0.2, BOUNDS)
+            assert (bounded[0] < p.spaced(K, 30)[0]).any() and bounded[1].sum() > 0
+        # the twin
+        at, beyond = p.spaced(5, TWIN)[2][k], p.spaced(5, TWIN + 1)[2][k]
+        assert at[0] == beyond[0] and at[1] != beyond[1] and at[2] == beyond[2] == NONE
+        assert _cut(p.tables, at[1]) - _cut(p.tables, at[0]) == TWIN and _score_bits(p.tables, at[0]) == _score_bits(p.tables, at[1])
+        assert abs(_cut(p.tables, beyond[1]) - _cut(p.tables, beyond[0])) > TWIN
+        if name == "straddle":
+            for K in TIE_KS:
+                kth, left_out = p.spaced(K, 0)[2][k][K - 1], p.spaced(K + 1, 0)[2][k][K]
+                assert _score_bits(p.tables, kth) == _score_bits(p.tables, left_out) and _cut(p.tables, kth) < hp.TWO30 <= _cut(p.tables, left_out)
+
+
+def test_distinct_pairs_hold_their_cases(case):
+    """distinct_numpy equals distinct_walk; KP = 1 is the plain pair selection; at KP = 5 and 33 the distinct pairs are other
+    pairs than the plain ones; at `straddle` the tie gene's distinct pairs lie on both sides of 2^30, none across it; hp_tail's
+    gene runs out of pairs before KP = 33."""
+    for name in hp.PLACEMENTS:
+        p = case.placed(name)
+        k, tail = p.ids.index("tie"), p.ids.index("tail_gene")
+        for K in KP_DISTINCT:
+            want = p.distinct(K)
+            walk = dref.distinct_walk(p.tables, p.lo, p.hi, K, *PAIR_WINDOW)
+            assert all(np.array_equal(np.asarray(a, np.uint64), np.asarray(b, np.uint64)) for a, b in zip(want, walk)), (name, K)
+            plain = pairs_ref.pairs_numpy(p.tables, p.lo, p.hi, K, *PAIR_WINDOW)
+            assert np.array_equal(want[0], plain[0]) and np.array_equal(want[1], plain[1])
+            assert np.array_equal(want[3], plain[2]) == (K == 1), (name, K)
+            assert want[1].tolist() == [17532, 2182, 2182, 4528, 7437, 49] and want[2].tolist() == [min(K, 33)] * 5 + [min(K, 6)]
+            mine = want[3][k][:int(want[2][k])]
+            sides = [(_cut(p.tables, a) < hp.TWO30, _cut(p.tables, b) < hp.TWO30) for a, b in mine]
+            assert all(a == b for a, b in sides)
+            below = sum(a for a, _ in sides)
+            assert (below, len(sides) - below) == ({1: (1, 0), 5: (3, 2), 33: (17, 16)}[K] if name == "straddle" else (0, K))
+        assert int(p.distinct(33)[2][tail]) == 6 < 33 and (p.distinct(33)[3][tail][6:] == NONE).all()
+
+
+def _self_cut(rows, i):
+    return int(ssref.cut_letters(rows["pos"][i], rows["strand"][i], SELF_T, SELF_CUT))
+
+
+def test_self_selection_holds_its_cases(case):
+    """select_numpy equals select_loop.  Every site of the tie block has its twin as its one perfect copy, so some 53 sites of
+    either copy share the gene's best e and the word cut << 1 | strand alone orders them: at `straddle` the first copy's words
+    have bit 31 clear and the second copy's have it set -- a signed compare takes the second copy first.  For K in TIE_KS the
+    K-th site and the first one left out tie in the first copy; at K = SELF_TIE_K they tie across 2^30.  tail_gene holds '+' and
+    '-' sites; at `top` the word of every selected site has bit 31 set; the CDS, perfect-copy and sequence limits each change
+    some gene's sel, the hit-sum bound lowers n_pass."""
+    for name in hp.PLACEMENTS:
+        p = case.placed(name)
+        k, tail = p.ids.index("tie"), p.ids.index("tail_gene")
+        for M, scored in SELF_HANDLES:
+            rows = p.self_rows(M, scored)
+            assert rows["pos"].size == 867 and (rows["hit_sum"] is not None) == scored and rows["counts"].shape == (867, M + 1)
+            row_of = {int(c): i for i, c in enumerate(rows["cand"])}
+            e = ssref.row_keys(rows)
+            for K in KS:
+                want = p.self_select(M, scored, K)
+                if K in (1, 33):
+                    loop = ssref.select_loop(rows, p.lo, p.hi, p.self_spec(K))
+                    assert all(np.array_equal(a, b) for a, b in zip(want, loop)), (name, M, scored, K)
+                assert (want[2][:, 0] != NONE).all() and (want[0] == want[1]).all()
+                if name == "top":
+                    for c in want[2][want[2] != NONE]:
+                        i = row_of[int(c)]
+                        assert (_self_cut(rows, i) << 1 | int(rows["strand"][i])) >> 31 == 1
+            inside = [i for i in range(867) if int(p.lo[tail]) <= _self_cut(rows, i) <= int(p.hi[tail])]
+            assert int(p.self_select(M, scored, 1)[0][tail]) == len(inside) == 21 and sum(int(rows["strand"][i]) for i in inside) == 10  # 11 '+' sites and 10 '-'
+            if name == "straddle":
+                cut = ssref.cut_letters(rows["pos"], rows["strand"], SELF_T, SELF_CUT)
+                mine = (cut >= int(p.lo[k])) & (cut <= int(p.hi[k]))
+                best = mine & (e == min(e[mine]))
+                below, above = int((best & (cut < hp.TWO30)).sum()), int((best & (cut >= hp.TWO30)).sum())
+                assert (int(mine.sum()), below, above) == (107, SELF_TIE_K[M], SELF_TIE_K[M] - 1)
+                for K in TIE_KS + (SELF_TIE_K[M],):
+                    kth, left_out = row_of[int(p.self_select(M, scored, K)[2][k][K - 1])], row_of[int(p.self_select(M, scored, K + 1)[2][k][K])]
+                    assert best[kth] and best[left_out] and _self_cut(rows, kth) < hp.TWO30, (M, scored, K)
+                    assert (_self_cut(rows, left_out) >= hp.TWO30) == (K == SELF_TIE_K[M]), (M, scored, K)
+            plain = p.self_select(M, scored, 5)
+            for what, limits in SELF_LIMITS.items():
+                if what == "hit_sum" and not scored:
+                    continue
+                got = p.self_select(M, scored, 5, **limits)
+                loop = ssref.select_loop(rows, p.lo, p.hi, p.self_spec(5, **limits))
+                assert all(np.array_equal(a, b) for a, b in zip(got, loop)), (name, M, scored, what)
+                assert got[1].tolist() == SELF_N_PASS[what if what != "hit_sum" or M else None], (name, M, scored, what)
+                # (a hit-sum bound drops a gene's least specific sites: it lowers n_pass and, while K sites pass, leaves sel)
+                assert np.array_equal(got[2], plain[2]) == (what == "hit_sum"), (name, M, scored, what)
+            assert plain[1].tolist() == SELF_N_PASS[None]
+        points, ids, flags = p.cds_track()
+        assert int(points.max()) >> 30 == 1 and flags.any() and not flags.all()
 
 
 # ---------------------------------------------------------------------------------------------- on the GPU
@@ -1001,3 +1319,216 @@ def test_gpu_family_step(dev, case):
             h.close()
         for x in handles:
             x.close()
+
+
+def _same_named(got, want, names, what=""):
+    for g, w, name in zip(got, want, names):
+        assert np.array_equal(np.asarray(g, np.uint64), np.asarray(w, np.uint64)), (what, name)
+
+
+@pytest.mark.gpu
+def test_gpu_site_columns(dev, case):
+    """crp_sites.hip behind the filler: the planes and the three rank kernels over every word of the arena -- 64 trips of the
+    scan over the chunk sums at `straddle`, 128 at `top`, each from a non-zero carry (poly_a, span16) --, and the column kernel
+    at every flank against site_reference over the moved-down letters.  The index's size is the stated formula; planes and
+    ranks survive a re-scan; the plain selection reads this column."""
+    p = dev.ref
+    es = sites.EnzymeSet(case.enzymes())
+    assert es.names == [n for n, _ in case.enzymes()] and es.m_max == 16
+    try:
+        first = {}
+        for flank in hs.FLANKS:
+            (gp, gm), = dev.genome.site_columns(es, dev.counts, flank)
+            want = p.site_columns(flank)
+            for got, s in ((gp, "plus"), (gm, "minus")):
+                bad = np.flatnonzero(got != want[s]["value"])
+                assert bad.size == 0, (flank, s, bad[:5], [hex(int(x)) for x in got[bad[:5]]], [hex(int(x)) for x in want[s]["value"][bad[:5]]])
+            first[flank] = (gp, gm)
+            st = dev.arena.site_stats()
+            assert (st["rows"], st["enzymes"], st["flank"]) == (p.n_plus + len(p.tables["pos_minus"]), 8, flank)
+            assert st["bytes"] == hs.index_bytes(8, p.words) == dev.genome.site_stats["bytes"]
+        print("high positions, %s: site index of 8 enzymes %d bytes, planes %.2f ms, ranks %.2f ms" %
+              (p.placement, st["bytes"], st["planes_ms"], st["rank_ms"]))
+        built = (st["planes_ms"], st["rank_ms"])
+        dev.scan()
+        assert dev.arena.site_stats()["rows"] == 0  # the column is gone with the tables it belonged to
+        for flank in (hs.CROSSING_FLANK, 16):
+            (gp, gm), = dev.genome.site_columns(es, dev.counts, flank)
+            assert np.array_equal(gp, first[flank][0]) and np.array_equal(gm, first[flank][1]), flank
+        st = dev.arena.site_stats()
+        assert (st["planes_ms"], st["rank_ms"]) == built  # nothing was built again
+        # the plain selection over the resident column: no four-cutter in the guide, an assay with a cut-out motif at flank 1000
+        dev.genome.site_columns(es, dev.counts, hs.CROSSING_FLANK, fetch=False)
+        forbid, need = es.mask(list(hs.FOUR_CUTTERS)), es.mask(list(hs.CUT_OUT))
+        h = dev.select()
+        try:
+            h.set_site_limits((forbid, need))
+            for slice_rows in (0, 64):
+                h.set_limits(slice_rows)
+                for K in (1, 5):
+                    h.run(sel.Params(K))
+                    _same(h.fetch(), p.select_sites(K, hs.CROSSING_FLANK, forbid, need), "sites K=%d, slices of %d" % (K, slice_rows))
+        finally:
+            h.close()
+    finally:
+        dev.scan()
+
+
+@pytest.mark.gpu
+@SLICES
+def test_gpu_spaced_selection(dev, case, slice_rows):
+    """crp_select_spaced.hip behind the filler, whole genes and the piece path (slices of 64: one round per launch and the
+    pick kernel): the tie words cut << 1 | strand on either side of bit 31 and the unsigned distances |cut - cut(p)| up to the
+    twin's TWIN and one more."""
+    p = dev.ref
+    h = dev.select()
+    try:
+        if slice_rows:
+            h.set_limits(slice_rows)
+        for K in KS:
+            for D in SPACINGS:
+                h.run_spaced(sel.Params(K), D)
+                _same_named(h.fetch_spaced(), p.spaced(K, D), ("n_pass", "n_spaced", "sel"), "spaced K=%d D=%d" % (K, D))
+                assert h.spaced_stats()["spaced_cut_genes"] == (_merged_genes(p, slice_rows) if slice_rows else 0)
+        assert not slice_rows or _merged_genes(p, slice_rows) >= 4
+    finally:
+        h.close()
+
+
+@pytest.mark.gpu
+@SLICES
+def test_gpu_spaced_selection_behind_the_join(dev, case, slice_rows):
+    """The spaced selection with the specificity bounds over the joined columns (test_gpu_selection_behind_the_join's set-up)."""
+    p = dev.ref
+    pattern, gp, M, scheme = srch.check_specificity(L, 3)
+    handles = []
+    h = None
+    try:
+        srch._self_handles(dev.genome, pattern, gp, srch.SPECIFICITY_PAM_LEN, M, scheme, None, None, handles)
+        srch._self_compare_all(handles, M)
+        handles[0].join_hits(L)
+        h = dev.select()
+        if slice_rows:
+            h.set_limits(slice_rows)
+        for K in KS:
+            params = sel.Params(K, 0.2)
+            params.max_mm0, params.max_hit_sum = BOUNDS
+            h.run_spaced(params, 30, handles[0])
+            _same_named(h.fetch_spaced(), p.spaced(K, 30, 0.2, BOUNDS), ("n_pass", "n_spaced", "sel"), "joined spaced K=%d" % K)
+    finally:
+        if h is not None:
+            h.close()
+        for x in handles:
+            x.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pair_slice_rows, per_launch", [(0, 0), (64, 0), (64, 1)], ids=["default-slices", "slices-of-64", "slices-of-64-one-item-a-launch"])
+def test_gpu_distinct_pairs(dev, case, pair_slice_rows, per_launch):
+    """crp_select_pairs_distinct.hip behind the filler: partner runs streamed by position and the later rounds' skip over keys
+    whose ties the cut sites decide, whole genes, cut genes, and one item a launch (the step and pick launches of every round).
+    KP = 1 is the plain pair run bit for bit."""
+    p = dev.ref
+    h = dev.select()
+    try:
+        h.set_pair_limits(pair_slice_rows)
+        h.set_pair_distinct_limits(per_launch)
+        for K in KP_DISTINCT:
+            h.run_pairs_distinct(sel.Params(1), sel.PairParams(K, *PAIR_WINDOW, distinct=True))
+            got = h.fetch_pairs_distinct()
+            _same_named(got, p.distinct(K), ("n_pass", "n_pairs", "n_distinct", "pairs"), "distinct KP=%d" % K)
+            stats = h.pairs_distinct_stats()
+            assert not pair_slice_rows or stats["cut_genes"] >= 4
+            if K == 1:
+                h.run_pairs(sel.Params(1), sel.PairParams(1, *PAIR_WINDOW))
+                plain = h.fetch_pairs()
+                assert np.array_equal(got[0], plain[0]) and np.array_equal(got[1], plain[1]) and np.array_equal(got[3], plain[2])
+    finally:
+        h.close()
+
+
+class SelfSession:
+    """The self search of the device's genome under PATTERN, as tests/test_select_self.py's Session: the open handle and the
+    fetched rows of its guide sites -- which must be the reference's at their arena positions."""
+
+    def __init__(self, dev, M, scored):
+        self.genome, self.handles = dev.genome, []
+        try:
+            pattern, gp, M, P, scheme = srch.check_self(PATTERN, M, SELF_P, GUIDE_PATTERN, "hsu2013" if scored else None)
+            srch._self_handles(dev.genome, pattern, gp, P, M, scheme, None, None, self.handles)
+            srch._self_compare_all(self.handles, M)
+            pos, strand, hi, lo, counts, hit_sum = self.handles[0].fetch(scored)
+            want = dev.ref.self_rows(M, scored)
+            cpos, cstrand = dev.ref.candidates()
+            assert tuple(self.handles[0].sizes()) == (int((cstrand == 0).sum()), int((cstrand == 1).sum()), want["pos"].size)
+            assert np.array_equal(pos, want["pos"]) and np.array_equal(strand, want["strand"])
+            assert np.array_equal(counts, want["counts"]) and (not scored or np.array_equal(hit_sum, want["hit_sum"]))
+            assert np.array_equal(hi & np.uint32(SELF_REGION), want["hi"]) and np.array_equal(lo & np.uint32(SELF_REGION), want["lo"])
+            self.rows = [dict(pos=pos, strand=strand, hi=hi, lo=lo, counts=counts, hit_sum=hit_sum if scored else None, cand=want["cand"])]
+        except BaseException:
+            self.close()
+            raise
+
+    def close(self):
+        for h in self.handles:
+            h.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("M, scored", SELF_HANDLES, ids=["M%d-%s" % (m, "scored" if s else "counts") for m, s in SELF_HANDLES])
+def test_gpu_self_selection(dev, case, M, scored):
+    """crp_select_self.hip behind the filler: the keys position << 1, the bounds kernel's one word past the last, the item
+    kernel's cut << 1 | strand and the CDS look-up's bucket cut >> 11 (at `top` the last one), whole genes, slices of 64 and one
+    item a launch, against select_self_reference over the reference's rows."""
+    import test_select_self as tss
+    p = dev.ref
+    s = SelfSession(dev, M, scored)
+    try:
+        for K in KS + (SELF_TIE_K[M],):
+            sp = p.self_spec(K)
+            for slice_rows in (0, 64):
+                got, stats = tss.run_gpu(s, 0, p.lo, p.hi, sp, slice_rows)
+                tss.assert_equal(s, 0, got, p.self_select(M, scored, K), sp)
+                assert not slice_rows or stats["self_items"] > len(p.lo)
+        got, stats = tss.run_gpu(s, 0, p.lo, p.hi, p.self_spec(5), 64, 1)
+        tss.assert_equal(s, 0, got, p.self_select(M, scored, 5), p.self_spec(5))
+        assert stats["self_launches"] == stats["self_items"] > len(p.lo)
+        for what, limits in SELF_LIMITS.items():
+            if what == "hit_sum" and not scored:
+                continue
+            sp = p.self_spec(5, **limits)
+            for slice_rows in (0, 64):
+                got, _ = tss.run_gpu(s, 0, p.lo, p.hi, sp, slice_rows)
+                tss.assert_equal(s, 0, got, p.self_select(M, scored, 5, **limits), sp)
+    finally:
+        s.close()
+
+
+@pytest.mark.gpu
+def test_gpu_genome_level_self_selection(dev, case):
+    """search.search_self(genome, select=...) -- Genome.search_self does not take select= --: the Selection's rows are the
+    handle-level picks, contig-relative -- gene, rank, contig, position, strand and cut -- without and with require_cds."""
+    import test_select_self as tss
+    p = dev.ref
+    offsets = np.array(p.offsets, np.int64)
+    for cds in (False, True):
+        s = SelfSession(dev, 3, True)
+        try:
+            sp = p.self_spec(5, cds=cds)
+            got, _ = tss.run_gpu(s, 0, p.lo, p.hi, sp)
+            tss.assert_equal(s, 0, got, p.self_select(3, True, 5, **(dict(cds=True) if cds else {})), sp)
+        finally:
+            s.close()
+        request = ss.Request(ss.Params(5, require_cds=cds), dev.request, slice_rows=64 if cds else None)
+        S = srch.search_self(dev.genome, PATTERN, 3, SELF_P, guide_pattern=GUIDE_PATTERN, score="hsu2013", select=request).selection
+        order = np.argsort(p.gene, kind="stable")  # the Selection lists genes in GFF order
+        assert np.array_equal(S.n_in, got["n_in"][order]) and np.array_equal(S.n_pass, got["n_pass"][order])
+        want = []
+        for r in order:
+            for j in np.flatnonzero(got["sel"][r] != NONE):
+                pos, minus = int(got["arena_pos"][r, j]), int(got["strand"][r, j])
+                kc = int(np.searchsorted(offsets, pos, "right")) - 1
+                cut = pos + (SELF_T - SELF_CUT if minus else SELF_CUT)
+                want.append((int(p.gene[r]), int(j) + 1, kc + 1, pos - p.offsets[kc], b"-" if minus else b"+", cut - p.offsets[kc]))
+        rows = [(int(r["gene"]), int(r["rank"]), int(r["contig"]), int(r["position"]), r["strand"], int(r["cut"])) for r in S.rows]
+        assert rows == want and len(rows) == (20 if cds else 30)
