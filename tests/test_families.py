@@ -661,6 +661,79 @@ def test_gpu_selection_with_family_limits(engine, case, slice_rows):
         ann.close()
 
 
+@pytest.mark.gpu
+def test_gpu_more_genes_than_one_launch(engine, case):
+    """The family kernel behind the driver's launch loop (crp_select_run hands every launch `d_items + first`): the genes of a
+    one-arena build tiled to more than 2^20 (tests/select_scale_cases.py), their family ids and sizes taken through the tiling,
+    under min_members = 2 and max_perfect_outside = 0.  At the default slices the second launch begins at gene 2^20; at slices
+    of 64 a cut gene's pieces -- the genes of 255, 256 and 257 sites are among the cut ones -- lie on both sides of every launch
+    boundary.  n_in, n_pass and sel whole, against the loop statement's selection of the base genes taken through the tiling."""
+    import select_scale_cases as scale
+    from cropsr_amd import select as sel
+    K, G = 5, scale.G
+    fam_ref = case.rows(3, "hsu2013", 0)
+    row_of = {s: r for r, s in enumerate(fam_ref["sites"])}
+    ann, table = case.table()
+    g = engine.genome(case.contigs)
+    try:
+        assert len(g.arenas) == 1 and g.groups == [list(range(len(case.contigs)))]
+        areq = annotate.Request(ann, case.names, 0)
+        plain = g.scan_score(20, specificity={})
+        tables = [plain.contig(k) for k in range(len(case.contigs))]
+        want = _reference_selection(case, tables, plain.columns, fam_ref, row_of, K, limits=(2, 0, None))
+        # (the limits pass a row and fail a row of the three homeologs: test_gpu_selection_with_family_limits shows each alone)
+        assert all(0 < want[case.idents.index(i)][1] < want[case.idents.index(i)][0] for i in ("A1", "A3"))
+        # the reference per layout row, sel packed as the device packs it: strand << 31 | the row in the arena's strand table
+        lo, hi, gene = areq.gene_layout(sel.arena_layout(g, 0))
+        gi = np.asarray(gene, dtype=np.int64)
+        assert sorted(gi.tolist()) == list(range(len(case.genes)))  # whole contigs in one arena: one layout row a gene
+        before = [np.cumsum([0] + [len(t["pos_" + name]) for t in tables]) for name in ("plus", "minus")]
+        n_base = gi.size
+        base = [np.zeros(n_base, np.uint32), np.zeros(n_base, np.uint32), np.full((n_base, K), NONE, np.uint32)]
+        for r, x in enumerate(gi.tolist()):
+            base[0][r], base[1][r] = want[x][0], want[x][1]
+            for rank, ((kc, _, strand, _, _), index) in enumerate(zip(want[x][2], want[x][3])):
+                base[2][r, rank] = strand << 31 | (int(before[strand][kc]) + index)
+        total = _run_lengths(case, tables)[gi]
+        assert sorted(total[[gi.tolist().index(case.idents.index(i)) for i in ("R255", "R256", "R257")]].tolist()) == [255, 256, 257]
+        family = np.asarray(table.gene_family)[gi]
+        size = np.array([table.family_size(int(x)) for x in gi], np.uint32)
+        done = []
+
+        ids = scale.tiling(range(n_base), G, scale.boundary_start(total, list(range(n_base)), 64))
+        assert scale.straddles(total[ids], 64)
+
+        def after_join(a, handle, cols, family_joined=None):
+            for slice_rows in (None, 64):
+                cut = scale.host_cut(total[ids], slice_rows or 65536)
+                h = sel.ArenaSelect(g.arenas[0], lo[ids], hi[ids])
+                try:
+                    if slice_rows:
+                        h.set_limits(slice_rows)
+                    h.set_family(family[ids], size[ids])
+                    h.set_family_limits(sel.FamilyLimits(2, 0))
+                    h.run(sel.Params(K), handle)
+                    got, stats, fstats = h.fetch(), h.stats(), h.family_stats()
+                finally:
+                    h.close()
+                for x, w, name in zip(got, base, ("n_in", "n_pass", "sel")):
+                    assert np.array_equal(x, w[ids]), (slice_rows, name, int((x != w[ids]).reshape(G, -1).any(axis=1).sum()))
+                assert stats["items"] == cut["items"] and stats["launches"] == -(-cut["items"] // scale.MAX_ITEMS) >= 2
+                assert stats["merged_genes"] == cut["cut_genes"] and fstats["family_select_ms"] > 0
+                if slice_rows is None:
+                    assert stats["items"] == G and stats["launches"] == 2
+                else:
+                    assert stats["items"] > G and cut["cut_genes"] > 0
+            done.append(True)
+
+        g._scan_score(20, False, False, True, None)
+        srch.specificity_columns(g, 20, after_join=after_join, families=fam.genome_rows(table, g, areq))
+        assert done
+    finally:
+        g.close()
+        ann.close()
+
+
 # ------------------------------------------------------------------ family limits with the predicate's other terms
 # CDS rows for require_cds, on a copy of the case GFF (family_cases.build()'s text stays what the other tests read): parts of
 # the three homeologs and of the nested pair

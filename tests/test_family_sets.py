@@ -13,7 +13,8 @@ from conftest import ROOT
 import family_reference as fref
 import family_set_cases as cases
 import family_set_reference as sref_sets
-from test_families import VALUES, FamilyOracleBackend, _oracle_view, _reference_selection, _run_cli, _md5
+import select_scale_cases as scale
+from test_families import VALUES, FamilyOracleBackend, _oracle_view, _reference_selection, _run_cli, _run_lengths, _md5
 from cropsr_amd import _native as nat
 from cropsr_amd import annotate, families as fam
 from cropsr_amd import search as srch
@@ -175,6 +176,93 @@ def test_candidates_are_the_rows_behind_n_pass(case, cpu):
             assert per_gene[g] == (n_pass[g] if case.gene_family[g] != NONE else 0)
         assert len({(c[5], c[2], c[3], c[4]) for c in cands}) == len(cands)  # each (gene, row) once
     assert case.gene_family[case.gene("free")] == NONE and cpu["free"][1][case.gene("free")] > 0
+
+
+# ------------------------------------------------------------------ the step past one launch (2^20 items): the list and its reference
+LATE_FAMILIES = ("gain", "three")  # more than one step each: they have a best candidate under both covered words
+
+
+def _family_best_gene(cands, covered, f):
+    mine = [c for c in cands if c[0] == f]
+    b = sref_sets.best_loop(mine, covered[f])
+    return None if b is None else mine[b][5]
+
+
+def _late_case(case, cands, total, n_genes=scale.G, head=scale.MAX_ITEMS + 64):
+    """The gene list of the step past one launch, in indices of case.genes: the family genes that have rows, tiled by
+    select_scale_cases.late_list so that the genes holding the best candidate of LATE_FAMILIES -- under nothing covered and
+    under what the reference greedy's first pick covers -- occur first behind position 2^20.  total: rows per gene."""
+    F = len(case.sizes)
+    base = [g for g in range(len(case.genes)) if case.gene_family[g] != NONE and total[g] > 0]
+    after = {f: ps[-1]["covered"] for f, ps in _by_family(sref_sets.greedy_loop(cands, case.sizes, 1)[0]).items()}
+    words = [[0] * F, [after.get(f, 0) for f in range(F)]]
+    late = sorted({_family_best_gene(cands, w, case.family(name)) for w in words for name in LATE_FAMILIES})
+    assert None not in late and len(late) >= 2
+    glist = scale.late_list(base, late, n_genes, head)
+    return dict(base=base, late=late, glist=glist, words=words, first=scale.first_occurrence(glist, len(case.genes)))
+
+
+def _expected_step(case, cands, covered, first, place):
+    """Per family the record crp_select_family_step returns for a handle over the list: best_loop over the base candidates with
+    each candidate's gene relabelled to the first position of its gene in the list.  This is exact: the copies of a gene are
+    equal in gain, key and tie -- they are the same table rows --, so among them the order's last term, the smaller layout
+    row, decides for the first copy; and two different genes compare as their first copies do.  place(contig, cut, strand,
+    index) -> (tie, row) as the device packs them, or None (then they are left out of the record)."""
+    out = []
+    for f in range(len(case.sizes)):
+        mine = [c[:5] + (int(first[c[5]]),) + c[6:] for c in cands if c[0] == f]
+        assert all(c[5] >= 0 for c in mine)
+        b = sref_sets.best_loop(mine, covered[f])
+        if b is None:
+            out.append(dict(gain=0, key=0, cover=0, gene=NONE, tie=NONE, row=NONE))
+            continue
+        _, _, contig, cut, strand, gene, key, cover, _, index = mine[b]
+        tie, row = place(contig, cut, strand, index) if place else (None, None)
+        out.append(dict(gain=bin(cover & ~covered[f]).count("1"), key=key, cover=cover, gene=gene, tie=tie, row=row))
+    return out
+
+
+def test_the_late_list_puts_the_best_genes_behind_the_first_launch(case, cpu):
+    """On the CPU's candidates, before any device is asked: the list's properties, the families whose best candidate lies
+    behind item 2^20 and those whose best lies in front of it, and the relabelling argument by brute force on a short list."""
+    cands = cpu["free"][0]
+    total = _run_lengths(case, cpu["tables"])
+    L = _late_case(case, cands, total)
+    base, late, glist, first = L["base"], L["late"], L["glist"], L["first"]
+    # late_list: G genes, the late genes first at or above 2^20 + 64, every other base gene in the first cycle, all in the tail
+    assert glist.size == scale.G and set(glist.tolist()) == set(base) and len(base) > 30
+    assert all(first[g] >= scale.MAX_ITEMS + 64 for g in late) and all(0 <= first[g] < len(base) for g in base if g not in late)
+    assert not np.isin(glist[:scale.MAX_ITEMS + 64], late).any() and set(glist[scale.MAX_ITEMS + 64:].tolist()) == set(base)
+    assert all(glist[first[g]] == g for g in base) and all(first[g] == -1 for g in range(len(case.genes)) if g not in base)
+    # one item a gene at the default slices (items == G, two launches), more at slices of 64
+    assert (total[glist] > 0).all() and int((-(-total[glist] // 64)).sum()) > scale.G > scale.MAX_ITEMS
+    for covered in L["words"]:
+        best = {f: _family_best_gene(cands, covered, f) for f in range(len(case.sizes))}
+        behind = [f for f, g in best.items() if g is not None and g in late]
+        front = [f for f, g in best.items() if g is not None and g not in late]
+        assert len(behind) >= 2 and len(front) >= 2 and set(case.family(n) for n in LATE_FAMILIES) <= set(behind)
+        # (the second launch holds items of the `front` families too: the tail tiles every base gene)
+        want = _expected_step(case, cands, covered, first, None)
+        assert all(want[f]["gene"] >= scale.MAX_ITEMS for f in behind) and all(want[f]["gene"] < len(base) for f in front)
+    assert L["words"][1] != L["words"][0] and sum(1 for w in L["words"][1] if w) >= 10
+    # the relabelling against brute force: a short list, every copy of every candidate with its own position as its gene
+    S = _late_case(case, cands, total, n_genes=3 * len(base) + 7, head=len(base) + 5)
+    copies = [c[:5] + (p,) + c[6:] for p, g in enumerate(S["glist"].tolist()) for c in cands if c[5] == g]
+    for covered in S["words"]:
+        want = _expected_step(case, cands, covered, S["first"], None)
+        for f in range(len(case.sizes)):
+            mine = [c for c in copies if c[0] == f]
+            b = _best_with_copies(mine, covered[f])
+            assert (None if b is None else (b[5], b[6], b[7])) == (None if want[f]["gain"] == 0 else (want[f]["gene"], want[f]["key"], want[f]["cover"]))
+
+
+def _best_with_copies(cands, covered):
+    """best_loop's order over candidates among which copies of one table row occur (equal in everything but the gene): a
+    plain minimum over the order's terms."""
+    live = [c for c in cands if bin(c[7] & ~covered).count("1")]
+    if not live:
+        return None
+    return min(live, key=lambda c: (-bin(c[7] & ~covered).count("1"), -c[6], c[1], c[2], c[3] << 1 | c[4], c[5]))
 
 
 def test_host_helpers():
@@ -527,6 +615,58 @@ def test_gpu_step_by_step(engine, case, device, max_words):
                     s.close()
 
     _with_joined_handles(engine, case, max_words, body)
+
+
+@pytest.mark.gpu
+def test_gpu_step_past_one_launch(engine, case, device):
+    """crp_select_family_step over more than 2^20 items: its loop hands the second launch `d_set_items + first` and
+    `d_set_prop + first`, and the pick kernel reads the proposals by absolute slot.  The handle's genes are _late_case's list:
+    for LATE_FAMILIES the best candidate's gene occurs first behind item 2^20, so the second launch writes the winning
+    proposal; for the other families the winner lies in the first launch while the second holds items of theirs too.  Every
+    field of every family's record against _expected_step, with nothing covered and with the greedy's first pick covered, at
+    the default slices (one item a gene) and at slices of 64."""
+    from cropsr_amd import select as sel
+    cands, _ = device.candidates(3, "hsu2013", 0, ONE_ARENA, False)
+    tables, _ = device.plain(3, "hsu2013")
+    total = _run_lengths(case, tables)
+    L = _late_case(case, cands, total)
+    glist, F = L["glist"], len(case.sizes)
+    before = [np.cumsum([0] + [len(t["pos_" + name]) for t in tables]) for name in ("plus", "minus")]
+
+    def body(g, hits, handles, areq, table):
+        assert g.groups == ONE_ARENA
+        offsets = [int(o) for o in g.arenas[0].offsets]  # (one arena: the contigs in genome order)
+        place = lambda contig, cut, strand, index: ((offsets[contig] + cut) << 1 | strand, strand << 31 | (int(before[strand][contig]) + index))
+        lo, hi, gene = areq.gene_layout(sel.arena_layout(g, 0))
+        gi = np.asarray(gene, dtype=np.int64)
+        assert sorted(gi.tolist()) == list(range(len(case.genes)))  # whole contigs in one arena: one layout row a gene
+        row_of_gene = np.empty(gi.size, np.int64)
+        row_of_gene[gi] = np.arange(gi.size)
+        lay = row_of_gene[glist]
+        size = np.array([table.family_size(x) for x in range(len(case.genes))], np.uint32)
+        for slice_rows in (None, 64):
+            items = int(np.maximum(1, -(-total[glist] // (slice_rows or 65536))).sum())
+            s = sel.ArenaSelect(g.arenas[0], lo[lay], hi[lay])
+            try:
+                if slice_rows:
+                    s.set_limits(slice_rows)
+                s.set_family(np.asarray(table.gene_family)[glist], size[glist])
+                s.set_family_members(np.asarray(table.gene_member)[glist])
+                for n, covered in enumerate(L["words"]):
+                    best = s.family_step(sel.Params(1), handles[0], np.array(covered, np.uint64))
+                    want = _expected_step(case, cands, covered, L["first"], place)
+                    for f in range(F):
+                        for field in ("gain", "key", "cover", "gene", "tie", "row"):
+                            assert int(best[field][f]) == want[f][field], (slice_rows, n, case.fam_names[f], field)
+                    assert sum(1 for w in want if w["gain"] and w["gene"] >= scale.MAX_ITEMS) >= 2
+                    assert sum(1 for w in want if w["gain"] and w["gene"] < scale.MAX_ITEMS) >= 2
+                    st = s.family_step_stats()
+                    assert st["items"] == items and st["plan_builds"] == 1
+                assert items == scale.G if slice_rows is None else items > scale.G
+            finally:
+                s.close()
+
+    _with_joined_handles(engine, case, None, body)
 
 
 @pytest.mark.gpu

@@ -17,6 +17,7 @@ from conftest import OracleBackend
 import select_coding_cases as cases
 import select_coding_reference as cref
 import select_reference as sref
+import select_scale_cases as scale
 from cropsr_amd import _native as nat
 from cropsr_amd import annotate, cli, coding
 from cropsr_amd import select as sel
@@ -219,6 +220,56 @@ def test_selection_statements_agree_on_the_case_genome(case):
         for g, w, name in zip(got, want, ("n_in", "n_pass", "sel")):
             assert np.array_equal(g, w), (K, limits, name)
         assert got[1].any() == (limits != (0, 0, 0))
+
+
+def test_a_tiled_model_holds_the_base_rows(case):
+    """select_scale_cases.tile_model over the case genome's host layout: every tiled row is its base row -- info, length,
+    the step slices, and the (off, cover) they give --, and first is a running sum.  Twice: the list of the GPU test, more
+    than 2^20 genes over the rows of few steps, and a short list over all rows, those of 129 and 257 steps among them."""
+    tables, entries = _host_arena(case)
+    request = annotate.Request(case["annotation"], case["names"], 0)
+    model = request.coding_layout([(k, e[3], e[2]) for k, e in enumerate(entries)])
+    base_first = model["first"].astype(np.int64)
+    n_rows = model["info"].size
+    lo, hi, _ = sref.layout(case["genes"], entries, 0)
+    total = scale.rows_in(tables, lo.astype(np.int64), hi.astype(np.int64))
+    few = scale.few_steps(model)
+    assert n_rows == len(lo) and 10 < len(few) < n_rows and np.diff(base_first).max() >= 129 and (np.diff(base_first)[few] == 0).any()
+    rng = np.random.default_rng(20)
+    pos = np.concatenate([tables["pos_plus"].astype(np.int64) - 3, tables["pos_minus"].astype(np.int64) + 6])
+    c = pos[rng.choice(pos.size, 64, replace=False)]  # the cut boundaries of 64 sampled table rows
+    off = np.concatenate([cref.steps_position(model, b, c)[0] for b in few])
+    assert (off != cref.NOT_INSIDE).any() and (off == cref.NOT_INSIDE).any()
+    for base, n_genes in ((few, scale.G), (list(range(n_rows)), 5 * n_rows + 3)):
+        start = scale.boundary_start(total, base, 64, n_genes) if n_genes == scale.G else 3
+        ids = scale.tiling(base, n_genes, start)
+        tiled = scale.tile_model(model, ids)
+        print("tiled model: %d rows, %d steps, %.1f MB" % (ids.size, tiled["at"].size, sum(v.nbytes for v in tiled.values()) / 1e6))
+        first = tiled["first"].astype(np.int64)
+        assert first.size == n_genes + 1 and first[0] == 0 and first[-1] == tiled["at"].size == tiled["word"].size == tiled["cum"].size
+        assert (np.diff(first) >= 0).all() and np.array_equal(np.diff(first), np.diff(base_first)[ids])
+        assert np.array_equal(tiled["info"], model["info"][ids]) and np.array_equal(tiled["length"], model["length"][ids])
+        assert tiled["first"].dtype == np.uint64 and all(tiled[key].dtype == model[key].dtype for key in ("info", "length", "at", "word", "cum"))
+        # the step slices, by plain slicing: every base row at the list's start, on both sides of 2^20 and at its end
+        n = len(base)
+        where = set(range(min(2 * n, n_genes))) | set(range(n_genes - 2 * n, n_genes))
+        if n_genes > scale.MAX_ITEMS:
+            where |= set(range(scale.MAX_ITEMS - n, scale.MAX_ITEMS + n))
+        seen = set()
+        for g in sorted(where):
+            b = int(ids[g])
+            for key in ("at", "word", "cum"):
+                assert np.array_equal(tiled[key][first[g]:first[g + 1]], model[key][base_first[b]:base_first[b + 1]]), (g, key)
+            if (b, g > scale.MAX_ITEMS) not in seen:  # (the step function itself: once per base row and side of 2^20)
+                seen.add((b, g > scale.MAX_ITEMS))
+                got, want = cref.steps_position(tiled, g, c), cref.steps_position(model, b, c)
+                assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1]), g
+        assert len(seen) == (2 if n_genes > scale.MAX_ITEMS else 1) * n
+    # the list of the GPU test reaches a second launch, and at slices of 64 a cut gene lies across every launch boundary
+    assert total[few].max() > 64
+    ids = scale.tiling(few, scale.G, scale.boundary_start(total, few, 64))
+    cut = scale.host_cut(total[ids], 64)
+    assert cut["items"] > scale.G > scale.MAX_ITEMS and 0 < cut["cut_genes"] and scale.straddles(total[ids], 64)
 
 
 def test_coding_driver_under_sanitizers(zoo, tmp_path):
@@ -441,6 +492,47 @@ def test_gpu_selection_equals_the_reference(scanned, K, slice_rows):
         got, _, cstats = _device(scanned, a, K, slice_rows, None)
         _same(got, _reference(scanned, a, K, None), "arena %d K %d no limits" % (a, K))
         assert cstats["coding_select_ms"] == 0
+
+
+@pytest.mark.gpu
+def test_gpu_more_genes_than_one_launch(engine, case):
+    """The coding kernel behind the driver's launch loop (crp_select_run hands every launch `d_items + first`): the arena's
+    genes of few steps tiled to more than 2^20 (tests/select_scale_cases.py), with the tiled model, under limits that pass a
+    row and fail a row of some gene.  At the default slices the second launch begins at gene 2^20; at slices of 64 a cut
+    gene's pieces lie on both sides of every launch boundary (the list begins where boundary_start says, for both slicings).
+    n_in, n_pass and sel whole, against the reference taken through the tiling."""
+    s = _scanned(engine, case, None)
+    try:
+        A, K, limits = s["arenas"][0], 5, (5, 65, 0)
+        want, plain = _reference(s, 0, K, limits), _reference(s, 0, K, None)
+        base = scale.few_steps(A["model"])
+        assert ((0 < want[1][base]) & (want[1][base] < plain[1][base])).any()  # the limits pass a row and fail a row of some gene
+        total = scale.rows_in(A["tables"], A["lo"].astype(np.int64), A["hi"].astype(np.int64))
+        assert total[base].max() > 64  # runs that the slices of 64 cut
+        ids = scale.tiling(base, scale.G, scale.boundary_start(total, base, 64))
+        assert scale.straddles(total[ids], 64)
+        model = scale.tile_model(A["model"], ids)
+        for slice_rows in (None, 64):
+            cut = scale.host_cut(total[ids], slice_rows or 65536)
+            h = sel.ArenaSelect(s["genome"].arenas[0], A["lo"][ids], A["hi"][ids])
+            try:
+                if slice_rows:
+                    h.set_limits(slice_rows)
+                h.set_coding(model)
+                h.set_coding_limits(coding.Limits(*limits))
+                h.run(sel.Params(K))
+                got, stats, cstats = h.fetch(), h.stats(), h.coding_stats()
+            finally:
+                h.close()
+            _same(got, [np.asarray(w)[ids] for w in want], "slices %r" % slice_rows)
+            assert stats["items"] == cut["items"] and stats["launches"] == -(-cut["items"] // scale.MAX_ITEMS) >= 2
+            assert stats["merged_genes"] == cut["cut_genes"] and cstats["coding_select_ms"] > 0
+            if slice_rows is None:
+                assert stats["items"] == scale.G and stats["launches"] == 2
+            else:
+                assert stats["items"] > scale.G and cut["cut_genes"] > 0
+    finally:
+        s["genome"].close()
 
 
 @pytest.mark.gpu

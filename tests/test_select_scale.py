@@ -11,16 +11,24 @@ arrays, bit for bit.  The second part keeps one handle through a sequence of run
 larger one, a pair run that rewrites the shared bounds, limits set and cleared, a rescan -- and compares every step with
 the reference and with a fresh handle.
 
-Out of scope: the coding, edit, splice and family kernels take the same `d_items + first` from the same loop, and feeding
-them 2^20 genes needs a coding model or a family table for a million genes.  Their cut and merge paths are covered at small
-size (tests/test_select_coding.py, test_base_edit.py, test_splice_edit.py, test_families.py); the launch loop is covered
-here through the plain kernel."""
+The spaced selection (crp_select_run_spaced) has three such loops: over the whole genes (`d_spaced_items + first`), per round
+over the pieces of the cut genes, which lie behind the whole ones (`d_spaced_items + n_whole + first`), and per round over the
+cut genes (`d_spaced_merge + first`, with `first` also as the pick kernel's index into `picked`, which the host reads whole to
+end the rounds).  The same lists, with the spaced driver's cut restated (select_scale_cases.spaced_cut), take each loop past
+one launch, and a fourth list lets only its first genes pick in the late rounds, so that the exit depends on their entries of
+`picked`; the reference is tests/select_spacing_reference.py over the 16 ranges and one `take`.
+
+The other loops past one launch: the coding, edit, splice and family kernels get `d_items + first` from crp_select_run's
+loop, each through its own call; tests/test_select_coding.py, test_base_edit.py, test_splice_edit.py and test_families.py
+each tile their own genes to 2^20 + 4 099 (select_scale_cases.tile_model tiles the coding model) and compare with their own
+reference.  crp_select_family_step's loop is in tests/test_family_sets.py, on select_scale_cases.late_list."""
 import numpy as np
 import pytest
 
 import select_pairs_reference as pref
 import select_reference as ref
 import select_scale_cases as cases
+import select_spacing_reference as sp
 import guide_properties_reference as gpref
 import repair_reference as rref
 from cropsr_amd import _native as nat
@@ -34,6 +42,14 @@ CUT = [j for j, n in enumerate(cases.ROWS) if n >= 65]             # list B: eve
 PAIR_SMALL = [j for j, n in enumerate(cases.ROWS) if n <= 130]     # one item a gene at the default pair slices
 PAIR_CUT = [j for j, n in enumerate(cases.ROWS) if 65 <= n <= 130]  # two or three items a gene at pair slices of 64
 PAIR_WINDOW = (20, 120)
+SPACING = 150  # the spaced selection's D > 0: at K = 5 some ranges end early and some fill K (proved on the reference below)
+HEAD_SPACING = 300  # list C's D: cut ranges of at most 2, of 3 and of 4 picks at K = 5 (proved on the reference below)
+HEAD_GENES = 4096   # list C's head: fewer genes than the second pick launch holds (G - 2^20)
+
+
+def _picks_class(n_spaced, counts):
+    """The cut ranges whose pick count at K = 5 is one of `counts`."""
+    return [j for j in CUT if int(n_spaced[j]) in counts]
 
 
 @pytest.fixture(scope="module")
@@ -71,6 +87,9 @@ def test_the_lists_reach_a_second_launch(case):
         # its slots are consecutive from slot_first: they run across the boundary with its items
         assert cut["slot_first"][g] >= 0 and cut["slot_first"][g] + cut["pieces"][g] <= cut["slots"]
     assert cut["cut_genes"] < MAX_ITEMS  # (list A's merges fit one launch: list B is there for the merge loop)
+    # boundary_start looks a boundary up by its place in a cycle; on the whole lists: its start does, no smaller one does
+    assert cases.straddles(case["total"][cases.tiling(ALL, G, start)], 64)
+    assert not any(cases.straddles(case["total"][cases.tiling(ALL, G, s)], 64) for s in range(start))
     # the restated cut against a plain loop, on one cycle of the tiling
     items, slots = [], 0
     for g, n in enumerate(case["total"].tolist()):
@@ -103,6 +122,69 @@ def test_the_lists_reach_a_second_launch(case):
     for which in (PAIR_SMALL, PAIR_CUT):
         _neighbours_differ(which, (n_pass, n_pairs, pairs[:, 0, 0]))
         assert (n_pairs[which] > 3).sum() >= 6 and n_pairs[empty] == 0 and (pairs[empty] == NONE).all()
+
+
+def test_the_spaced_lists_reach_a_second_launch(case):
+    """On the oracle's rows, with the spaced driver's cut restated (select_scale_cases.spaced_cut): the whole genes, the pieces
+    and the cut genes each need a second launch under one of the lists, a cut gene's pieces lie on both sides of every
+    boundary of the pieces list behind a non-zero n_whole, and at SPACING some ranges end early and some fill K."""
+    total = case["total"]
+    # list A at the default slices: every gene whole, two item launches
+    whole = cases.spaced_cut(total[cases.tiling(ALL)], 65536)
+    assert whole["n_whole"] == G > MAX_ITEMS and whole["n_cut"] == 0 and whole["n_pieces"] == 0
+    # list A at slices of 64: whole genes in front of the pieces, three step launches, one pick launch
+    start = cases.spaced_boundary_start(total, ALL, 64)
+    ids = cases.tiling(ALL, G, start)
+    cut = cases.spaced_cut(total[ids], 64)
+    assert 0 < cut["n_whole"] < MAX_ITEMS and cut["n_whole"] == int((total[ids] <= 64).sum())
+    assert cut["n_pieces"] > 2 * MAX_ITEMS and 0 < cut["n_cut"] < MAX_ITEMS and cut["n_whole"] + cut["n_cut"] == G
+    for b in range(MAX_ITEMS, cut["n_pieces"], MAX_ITEMS):
+        j = int(np.searchsorted(cut["piece_first"], b, "right") - 1)
+        assert cut["piece_first"][j] < b < cut["piece_first"][j] + cut["pieces"][j], (b, j)
+    # list B at slices of 64: every gene cut, two pick launches
+    merged = cases.spaced_cut(total[cases.tiling(CUT)], 64)
+    assert merged["n_cut"] == G > MAX_ITEMS and merged["n_whole"] == 0 and merged["n_pieces"] > 3 * MAX_ITEMS
+    # the restated cut against a plain loop, on one cycle of the tiling
+    n_whole, pieces, merges = 0, [], []
+    for g, n in enumerate(total.tolist()):
+        p = max(1, -(-n // 64))
+        if p == 1:
+            n_whole += 1
+            continue
+        merges.append((g, len(pieces), p))
+        pieces += [(g, min(n, 64 * c), min(n, 64 * (c + 1))) for c in range(p)]
+    one = cases.spaced_cut(total, 64)
+    assert (one["n_whole"], one["n_pieces"], one["n_cut"]) == (n_whole, len(pieces), len(merges))
+    assert list(zip(one["cut_genes"].tolist(), one["piece_first"].tolist(), one["pieces"].tolist())) == merges
+    assert all(pieces[f][0] == g and pieces[f + p - 1][0] == g for g, f, p in merges)
+    # the launch count, restated from the three loops; one launch each is test_select_spacing.py's identity 2 + 1 + 2 * rounds
+    assert cases.spaced_launches(dict(n_whole=10, n_pieces=100, n_cut=7), 4) == 2 + 1 + 2 * 4
+    assert cases.spaced_launches(cut, 5) == 2 + 1 + 5 * (3 + 1) and cases.spaced_launches(merged, 5) == 2 + 0 + 5 * (4 + 2)
+    assert cases.spaced_launches(whole, 0) == 2 + 2
+    # the answers at K = 5: SPACING ends at least three ranges early although K rows pass, and at least three fill K
+    tables = _tables(case["hits"], 64)
+    n_pass, n_spaced, picked = sp.spaced_numpy(tables, case["lo"] + 64, case["hi"] + 64, 5, SPACING)
+    early, full = (n_spaced < 5) & (n_pass >= 5), n_spaced == 5
+    print("SPACING", SPACING, "n_pass", n_pass.tolist(), "n_spaced", n_spaced.tolist())
+    assert early.sum() >= 3 and full.sum() >= 3 and early[CUT].any() and full[CUT].any()
+    # list C, for the host's exit over `picked`: at HEAD_SPACING the cut ranges fall into classes by their pick count, all with
+    # K passing rows; the head's class outlasts the rest's, and the head fits below the genes of the second pick launch
+    n_pass, n_spaced, picked = sp.spaced_numpy(tables, case["lo"] + 64, case["hi"] + 64, 5, HEAD_SPACING)
+    print("HEAD_SPACING", HEAD_SPACING, "n_spaced", n_spaced.tolist())
+    rest = _picks_class(n_spaced, (1, 2))
+    assert len(rest) >= 2 and (n_pass[CUT] >= 5).all() and 0 < HEAD_GENES <= G - MAX_ITEMS
+    for picks in (3, 4):
+        head = _picks_class(n_spaced, (picks,))
+        assert len(head) >= 2 and picks < 5
+        ids = cases.head_list(head, rest, HEAD_GENES)
+        assert ids.size == G and set(ids[:HEAD_GENES].tolist()) == set(head) and set(ids[HEAD_GENES:].tolist()) == set(rest)
+        assert cases.spaced_cut(total[ids], 64)["n_cut"] == G
+    # neighbours in every tiling differ in what the GPU tests compare.  The ranges overlap, and the ranges of 129 and of 130
+    # rows share their best row: n_spaced and sel[:, 0] alone do not tell them apart at D = 0, n_pass and the whole row of sel do
+    for K, D in ((5, 0), (5, SPACING), (1, 0), (1, SPACING)):
+        n_pass, n_spaced, picked = sp.spaced_numpy(tables, case["lo"] + 64, case["hi"] + 64, K, D)
+        for which in (ALL, CUT):
+            _neighbours_differ(which, (n_pass, n_spaced, picked))
 
 
 # ---------------------------------------------------------------------------------------------- on the GPU
@@ -239,6 +321,102 @@ def test_gpu_pair_merges_of_more_genes_than_one_launch(scanned):
     _same(got, want, ids)
     assert stats["items"] == cut["items"] >= 2 * G and cut["cut_genes"] == G > MAX_ITEMS
     assert stats["launches"] == -(-cut["items"] // MAX_ITEMS) >= 3
+
+
+# ---------------------------------------------------------------------------------------------- the spaced selection
+def _spaced_reference(s, K, D):
+    """spaced_numpy over the D ranges, once per (K, D)."""
+    key = ("spaced", K, D)
+    if key not in s["cache"]:
+        s["cache"][key] = sp.spaced_numpy(s["tables"], s["lo"], s["hi"], K, D)
+    return s["cache"][key]
+
+
+def _run_spaced(s, ids, K, D, slice_rows=None):
+    h = sel.ArenaSelect(s["arena"], s["lo"][ids], s["hi"][ids])
+    try:
+        if slice_rows:
+            h.set_limits(slice_rows)
+        h.run_spaced(sel.Params(K), D)
+        return h.fetch_spaced(), h.spaced_stats()
+    finally:
+        h.close()
+
+
+def _spaced_stats_hold(stats, cut, want, ids, K):
+    """The item and gene counts are the restated cut's, and the launches are those of the three loops: a cut gene is picked
+    for in rounds 0 .. n_spaced - 1, and the loop ends behind the first round that picks nothing, or at K."""
+    assert stats["spaced_items"] == cut["n_whole"] + cut["n_pieces"] and stats["spaced_cut_genes"] == cut["n_cut"]
+    rounds = min(K, int(np.asarray(want[1])[ids][cut["cut_genes"]].max()) + 1) if cut["n_cut"] else 0
+    assert stats["spaced_rounds"] == rounds
+    assert stats["spaced_launches"] == cases.spaced_launches(cut, rounds)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("D", [0, SPACING], ids=["D0", "spaced"])
+@pytest.mark.parametrize("K", [1, 5])
+def test_gpu_spaced_more_genes_than_one_launch(scanned, K, D):
+    """List A at the default slices: every gene whole, the second item launch begins at gene 2^20."""
+    s = scanned
+    ids = cases.tiling(ALL)
+    cut = cases.spaced_cut(s["total"][ids], 65536)
+    want = _spaced_reference(s, K, D)
+    got, stats = _run_spaced(s, ids, K, D)
+    _same(got, want, ids)
+    assert cut["n_whole"] == G and stats["spaced_launches"] == 2 + 2
+    _spaced_stats_hold(stats, cut, want, ids, K)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("D", [0, SPACING], ids=["D0", "spaced"])
+def test_gpu_spaced_pieces_across_the_launch_boundaries(scanned, D):
+    """List A at slices of 64: the pieces lie behind n_whole whole genes and take three step launches a round, a cut gene's
+    pieces on both sides of each boundary; the cut genes take one pick launch."""
+    s = scanned
+    start = cases.spaced_boundary_start(s["total"], ALL, 64)
+    ids = cases.tiling(ALL, G, start)
+    cut = cases.spaced_cut(s["total"][ids], 64)
+    want = _spaced_reference(s, 5, D)
+    got, stats = _run_spaced(s, ids, 5, D, 64)
+    _same(got, want, ids)
+    assert 0 < cut["n_whole"] and cut["n_pieces"] > 2 * MAX_ITEMS and cut["n_cut"] < MAX_ITEMS
+    _spaced_stats_hold(stats, cut, want, ids, 5)
+    assert stats["spaced_launches"] == 2 + 1 + stats["spaced_rounds"] * (3 + 1)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("D", [0, SPACING], ids=["D0", "spaced"])
+def test_gpu_spaced_more_cut_genes_than_one_launch(scanned, D):
+    """List B at slices of 64: every gene is cut, two pick launches a round, and `picked` spans both."""
+    s = scanned
+    ids = cases.tiling(CUT)
+    cut = cases.spaced_cut(s["total"][ids], 64)
+    want = _spaced_reference(s, 5, D)
+    got, stats = _run_spaced(s, ids, 5, D, 64)
+    _same(got, want, ids)
+    assert cut["n_cut"] == G > MAX_ITEMS and cut["n_whole"] == 0
+    _spaced_stats_hold(stats, cut, want, ids, 5)
+    assert stats["spaced_launches"] == 2 + stats["spaced_rounds"] * (-(-cut["n_pieces"] // MAX_ITEMS) + 2)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("picks", [3, 4])
+def test_gpu_spaced_exit_reads_the_picks_of_both_launches(scanned, picks):
+    """List C at slices of 64 and HEAD_SPACING: every gene is cut; the first HEAD_GENES genes tile the ranges of `picks` picks,
+    all others the ranges of at most 2.  From round 2 on only the head picks, and its entries of `picked` are the first
+    HEAD_GENES -- where a second pick launch that numbered its genes from 0 would write its own zeros.  The host's exit reads
+    the whole array: the run takes picks + 1 rounds -- no fewer, which would also cost the head a pick, and no more."""
+    s = scanned
+    want = _spaced_reference(s, 5, HEAD_SPACING)
+    head, rest = _picks_class(want[1], (picks,)), _picks_class(want[1], (1, 2))
+    assert len(head) >= 2 and len(rest) >= 2
+    ids = cases.head_list(head, rest, HEAD_GENES)
+    cut = cases.spaced_cut(s["total"][ids], 64)
+    got, stats = _run_spaced(s, ids, 5, HEAD_SPACING, 64)
+    _same(got, want, ids)
+    assert cut["n_cut"] == G and HEAD_GENES <= G - MAX_ITEMS
+    _spaced_stats_hold(stats, cut, want, ids, 5)
+    assert stats["spaced_rounds"] == picks + 1 <= 5
 
 
 # ---------------------------------------------------------------------------------------------- one handle, many runs

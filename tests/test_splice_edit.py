@@ -19,6 +19,7 @@ import base_edit_reference as eref
 import select_coding_cases as coding_cases
 import select_coding_reference as cref
 import select_reference as sref
+import select_scale_cases as scale
 import splice_edit_cases as cases
 import splice_edit_reference as xref
 from cropsr_amd import _native as nat
@@ -712,6 +713,47 @@ def test_gpu_selection_equals_the_reference(scanned, K, slice_rows):
     for most in (0, 1):
         few = np.concatenate([_reference(scanned, a, K, (0, 100, most, "any"))[1] for a in range(len(scanned["arenas"]))])
         assert (few.sum() == 0) == (most == 0) and few.sum() < passing.sum()
+
+
+@pytest.mark.gpu
+def test_gpu_more_genes_than_one_launch(engine, case):
+    """The splice kernel behind the driver's launch loop (crp_select_run hands every launch `d_items + first`): the arena's
+    genes of few steps tiled to more than 2^20 (tests/select_scale_cases.py), with the tiled model, under limits that pass a
+    row and fail a row of some gene.  At the default slices the second launch begins at gene 2^20; at slices of 64 a cut
+    gene's pieces lie on both sides of every launch boundary (the list begins where boundary_start says, for both slicings).
+    n_in, n_pass and sel whole, against the reference taken through the tiling."""
+    s = _scanned(engine, case, None)
+    try:
+        A, K, limits = s["arenas"][0], 5, (0, 100, 20, "any")
+        want, plain = _reference(s, 0, K, limits), _reference(s, 0, K, None)
+        base = scale.few_steps(A["model"])
+        assert ((0 < want[1][base]) & (want[1][base] < plain[1][base])).any()  # the limits pass a row and fail a row of some gene
+        total = A["everyone"].sum(axis=1)  # the rows of a gene's two runs, scored or not
+        assert total[base].max() > 64  # runs that the slices of 64 cut
+        ids = scale.tiling(base, scale.G, scale.boundary_start(total, base, 64))
+        assert scale.straddles(total[ids], 64)
+        model = scale.tile_model(A["model"], ids)
+        for slice_rows in (None, 64):
+            cut = scale.host_cut(total[ids], slice_rows or 65536)
+            h = sel.ArenaSelect(s["genome"].arenas[0], A["lo"][ids], A["hi"][ids])
+            try:
+                if slice_rows:
+                    h.set_limits(slice_rows)
+                h.set_coding(model)
+                h.set_splice_limits(baseedit.Window(*cases.WINDOW), "cbe", baseedit.SpliceLimits(*limits))
+                h.run(sel.Params(K))
+                got, stats, splice = h.fetch(), h.stats(), h.splice_stats()
+            finally:
+                h.close()
+            _same(got, [np.asarray(w)[ids] for w in want], "slices %r" % slice_rows)
+            assert stats["items"] == cut["items"] and stats["launches"] == -(-cut["items"] // scale.MAX_ITEMS) >= 2
+            assert stats["merged_genes"] == cut["cut_genes"] and splice["splice_select_ms"] > 0
+            if slice_rows is None:
+                assert stats["items"] == scale.G and stats["launches"] == 2
+            else:
+                assert stats["items"] > scale.G and cut["cut_genes"] > 0
+    finally:
+        s["genome"].close()
 
 
 @pytest.mark.gpu
