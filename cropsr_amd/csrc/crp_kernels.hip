@@ -469,7 +469,16 @@ __device__ __forceinline__ uint64_t desc_unpack(uint64_t v)
 // sequence instead of using the result -- a wrong assumption about dispatch order would cost
 // time once, never a wrong table.
 constexpr int CHAIN_HEADER_WORDS = 4;
-constexpr int LB_DEPTH = 2;  // descriptors per lane and round trip: 128 tiles (measured: 1 and 2 equal, 4 and 8 slower)
+// Descriptors per lane and look (one round trip past this XCD's L2): LB_DEPTH slots of 64 tiles.  Measured with every
+// request of a look in flight (profiles/EXPERIMENTS.md): 1 is faster than 2 (-3 %), 4 slower than 2 (+5 %); why a
+// wider look costs that much was not traced.  (The old "1 and 2 equal, 4 and 8 slower" was measured while the slots'
+// loads ran one after the other.)  With the pre-sigmoid column AND the seed words the depth-1 look-back compiles to 4
+// to 8 SGPR spills where the budget is 2 (register allocation, not need): that instantiation keeps depth 2, which was
+// not timed.
+#ifndef CRP_LB_DEPTH  // (A/B builds: EXTRA=-DCRP_LB_DEPTH=4)
+#define CRP_LB_DEPTH 1
+#endif
+constexpr int LB_DEPTH = CRP_LB_DEPTH, LB_DEPTH_BOTH_COLUMNS = 2;
 
 __device__ __forceinline__ void lookback_publish(uint64_t *desc, uint32_t tile, uint64_t total)
 {
@@ -477,24 +486,35 @@ __device__ __forceinline__ void lookback_publish(uint64_t *desc, uint32_t tile, 
     __hip_atomic_store(&desc[tile], tag | desc_pack(total), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
-// lane k, slot j looks at tile base - k - 64*j; all loads in flight together
-__device__ __forceinline__ void lookback_load(const uint64_t *desc, int64_t base, int lane, uint64_t (&v)[LB_DEPTH])
+// lane k, slot j looks at tile base - k - 64*j; all loads in flight together.
+// No load is conditional: a load under a lane mask is a branch of its own, and the compiler joins its result with the
+// masked-off lanes' value behind a wait of its own -- a second slot's request then leaves after the first slot's
+// answer, two round trips where one was meant.  A lane whose index lies before tile 0 reads tile 0's
+// descriptor instead, which serves as the empty prefix such a lane stands for: tile 0 only ever publishes a PREFIX, and
+// the lanes behind it in the window are never summed (lane <= p) nor needed (need ends at the nearest prefix).  While
+// tile 0 has not published, those lanes are "not ready" like tile 0 itself, whose lane is the nearest of them: the
+// window stalls on the same descriptor as it would with empty prefixes behind it.  A slot that lies before tile 0 as a
+// whole follows the slot that holds tile 0, which either stalls or ends the look-back: it is never looked at.
+// (32-bit byte offsets from a uniform base: `base` is a tile number of the grid, and a grid of 2^29 tiles is 8 TiB of planes.)
+template <int DEPTH>
+__device__ __forceinline__ void lookback_load(const uint64_t *desc, int64_t base, int lane, uint64_t (&v)[DEPTH])
 {
 #pragma unroll
-    for (int j = 0; j < LB_DEPTH; ++j) {
-        const int64_t idx = base - lane - 64 * j;
-        v[j] = DESC_PREFIX;  // before tile 0: an empty prefix
-        if (idx >= 0) v[j] = __hip_atomic_load(&desc[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int j = 0; j < DEPTH; ++j) {
+        const uint32_t at = 8u * (uint32_t)max((int32_t)base - lane - 64 * j, 0);
+        v[j] = __hip_atomic_load(reinterpret_cast<const uint64_t *>(reinterpret_cast<const char *>(desc) + at), __ATOMIC_RELAXED,
+                                 __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
 // Called by ONE wave (`lane`: the caller's lane index).  Returns the exclusive prefix in every lane and publishes the
 // inclusive one.
+template <int DEPTH>
 __device__ __forceinline__ uint64_t lookback_resolve(uint64_t *desc, uint32_t tile, uint64_t total, uint32_t *fail,
                                                      bool muted, uint32_t timeout_ticks, int lane)
 {
     if (tile == 0) return 0;
-    uint64_t v[LB_DEPTH];
+    uint64_t v[DEPTH];
     uint64_t excl = 0;
     int64_t base = (int64_t)tile - 1;
     lookback_load(desc, base, lane, v);
@@ -506,7 +526,7 @@ __device__ __forceinline__ uint64_t lookback_resolve(uint64_t *desc, uint32_t ti
         bool found = false, stall = false;
         int64_t missing = 0;  // the nearest tile that has not published yet
 #pragma unroll
-        for (int j = 0; j < LB_DEPTH; ++j) {
+        for (int j = 0; j < DEPTH; ++j) {
             const uint64_t st = v[j] >> 62;
             const uint64_t not_ready = __ballot(st == 0);
             const uint64_t is_prefix = __ballot(st == 2);
@@ -556,7 +576,7 @@ __device__ __forceinline__ uint64_t lookback_resolve(uint64_t *desc, uint32_t ti
             // both fields of the sum stay below 2^31 (they are parts of a table total): one 32-bit wave sum per field
             excl += pair64(wave_sum_u32((uint32_t)(contrib >> 32)), wave_sum_u32((uint32_t)contrib));
             if (found) break;
-            base -= 64 * LB_DEPTH;
+            base -= 64 * DEPTH;
         }
         lookback_load(desc, base, lane, v);
     }
@@ -637,7 +657,7 @@ struct ChainArgs {
 // their range tests, the tile-0 and last-tile flags, the packed total -- is derived HERE, from copies the compiler
 // cannot trace back: it would otherwise compute them in the set-up of all eight waves and carry them, spilled, to
 // the one wave that looks back.
-template <int TILE_WORDS>
+template <int TILE_WORDS, int DEPTH>
 __device__ __forceinline__ void chain_resolve(const ChainArgs &ch_in)
 {
     struct {
@@ -659,7 +679,7 @@ __device__ __forceinline__ void chain_resolve(const ChainArgs &ch_in)
     const uint32_t mute_tile = late_arg<uint32_t>(args, offsetof(EmitKernArgs, mute_tile));
     const uint32_t timeout_ticks = late_arg<uint32_t>(args, offsetof(EmitKernArgs, timeout_ticks));
     uint64_t *const totals = chain + 1;  // header: unused | fail << 32, the two table totals, the host's word
-    const uint64_t e = lookback_resolve(chain + CHAIN_HEADER_WORDS, ch.tile, ch.total, reinterpret_cast<uint32_t *>(chain) + 1,
+    const uint64_t e = lookback_resolve<DEPTH>(chain + CHAIN_HEADER_WORDS, ch.tile, ch.total, reinterpret_cast<uint32_t *>(chain) + 1,
                                         ch.tile == mute_tile, timeout_ticks, lane);
     if (lane == 0) {
         *ch.s_excl = e;
@@ -942,7 +962,7 @@ __global__ __launch_bounds__(G::BLOCK) __attribute__((amdgpu_waves_per_eu(6, 8))
             // must still learn its prefix, to publish the totals.  (The last tile by the grid size here, by
             // n_words_padded / TW in chain_resolve, which would carry the grid size through the set-up otherwise: one
             // number, launch_emit_variant launches n_words_padded / G::WORDS workgroups.)
-            if (tile == gridDim.x - 1 && wave == 0) chain_resolve<TW>(ch);
+            if (tile == gridDim.x - 1 && wave == 0) chain_resolve<TW, PRE && SEEDS ? LB_DEPTH_BOTH_COLUMNS : LB_DEPTH>(ch);
             return;
         }
     } else {
@@ -957,8 +977,25 @@ __global__ __launch_bounds__(G::BLOCK) __attribute__((amdgpu_waves_per_eu(6, 8))
     // slower: profiles/EXPERIMENTS.md.)
     // (16-byte units at 32-bit offsets; the chain tables for l = 20 only)
     constexpr uint32_t TAB_UNITS = (LFIX == 20 ? sizeof(TabsImage) : sizeof(CRP_TABS.exp_tab)) / 16;
-    for (uint32_t k = tid; k < TAB_UNITS; k += G::BLOCK)
-        reinterpret_cast<uint4 *>(tabs)[k] = reinterpret_cast<const uint4 *>(&CRP_TABS)[k];
+    // Every request of a thread leaves before the first answer is waited for: a loop of load, wait, write is one
+    // dependent L2 round trip per trip for the threads that take more than one unit.  The trip count is a compile-time
+    // number; a thread without a unit in the last trip asks for the table's last unit again and does not write it.
+    constexpr uint32_t TAB_TRIPS = (TAB_UNITS + G::BLOCK - 1) / G::BLOCK;
+    static_assert(TAB_TRIPS == 1 || TAB_TRIPS == 2, "the empty asm below names every staged unit");
+    typedef uint32_t Unit __attribute__((ext_vector_type(4)));
+    Unit staged[TAB_TRIPS];
+#pragma unroll
+    for (uint32_t t = 0; t < TAB_TRIPS; ++t)
+        staged[t] = reinterpret_cast<const Unit *>(&CRP_TABS)[min((uint32_t)tid + t * G::BLOCK, TAB_UNITS - 1)];
+    // All units pass through ONE empty asm: the tables are constant memory, whose loads the compiler moves freely, and it
+    // would sink the last one into the branch around its write, behind the wait for the one before.
+    if constexpr (TAB_TRIPS == 2) asm volatile("" : "+v"(staged[0]), "+v"(staged[TAB_TRIPS - 1]));
+    else asm volatile("" : "+v"(staged[0]));
+#pragma unroll
+    for (uint32_t t = 0; t < TAB_TRIPS; ++t) {
+        const uint32_t k = (uint32_t)tid + t * G::BLOCK;
+        if ((t + 1) * G::BLOCK <= TAB_UNITS || k < TAB_UNITS) reinterpret_cast<Unit *>(tabs)[k] = staged[t];
+    }
     emit_rounds<G, LFIX == 20, CHAINED, PRE, SEEDS>(sh, list, exp_tab, score_tab, mp, mm, sc.ex_plus, sc.ex_minus, n_plus, n_minus, l,
                                                  (uint32_t)(t0 * 64),
                                                  off_plus, off_minus, out, ch);
@@ -1230,15 +1267,15 @@ __device__ __forceinline__ void emit_rounds(uint64_t (*sh)[G::WORDS + 2], uint16
         } else {
             // the whole look-back BEFORE wave 0 scores anything (nothing of the scorer is live then)
             int first_wave = wave;
-            if (PRE && SEEDS) {
-                // (with both extra columns no scalar register is free to carry the wave index through the set-up and the
+            if (SEEDS) {
+                // (with the seed words no scalar register is free to carry the wave index through the set-up and the
                 // list build to here and on to the prefetch: it would be spilled, two VALU instructions; read again, one)
                 int t = tid;
                 asm volatile("" : "+v"(t));
                 first_wave = __builtin_amdgcn_readfirstlane(t) >> 6;
             }
             asm volatile("" : "+s"(first_wave));
-            if (lo_rank == 0 && first_wave == 0) chain_resolve<G::WORDS>(ch);
+            if (lo_rank == 0 && first_wave == 0) chain_resolve<G::WORDS, PRE && SEEDS ? LB_DEPTH_BOTH_COLUMNS : LB_DEPTH>(ch);
             // (tile and wave index in ONE register from here to the prefetch, behind the first row: a tile index has 17 bits)
             uint32_t tile_wave = ch.tile | (uint32_t)first_wave << 24;
             asm volatile("" : "+s"(tile_wave));

@@ -13,6 +13,8 @@ pre-sigmoid column, no seed words), splits it into basic blocks and prints
 
   vmem loads the vector-memory loads outside the set-up, by region (rounds, row loop, behind the round loop), and those of
              them that are the successor prefetch: indexed buffer loads whose result nothing reads
+  head loads whether the loads at the head of a tile's serial chain leave together: the `s_waitcnt vmcnt` between the
+             descriptor loads of the look-back's first look, and the scorer-table loads issued before the first wait
 
 as VALU / f64 / SALU instruction counts, plus the compiler's resource usage: VGPRs, SGPR spills, scratch, LDS and
 occupancy.  These are static counts: how often each block runs depends on the genome.
@@ -199,6 +201,50 @@ def prefetch_dst_written(prefetch_ins, row_loop_ins):
     return hits
 
 
+def is_vmcnt_wait(instr):
+    return instr.startswith("s_waitcnt") and "vmcnt" in instr
+
+
+def is_descriptor_load(instr):
+    """an 8-byte load past this XCD's L2: what the single-launch kernel's look-back reads tile descriptors with"""
+    return instr.startswith("global_load_dwordx2") and instr.split()[-1] == "sc1"
+
+
+def first_window(round_blocks):
+    """The look-back's first look: the descriptor loads of the round loop that are laid out ahead of the look-back's own
+    loop (whose header follows them; the spin on one descriptor and the loop's re-load lie inside it).  `round_blocks`:
+    the round loop's (label, is a loop header, instructions) in layout order.  Returns (loads, `s_waitcnt vmcnt` between
+    the first and the last of them) -- 0 waits: all of the window's requests are out before any answer is waited for --,
+    or (0, None) where the kernel has no look-back."""
+    ins, seen = [], False
+    for label, is_header, block in round_blocks:
+        if seen and is_header:
+            break
+        for i in block:
+            seen = seen or is_descriptor_load(i)
+            if seen:
+                ins.append(i)
+    at = [k for k, i in enumerate(ins) if is_descriptor_load(i)]
+    if not at:
+        return 0, None
+    return len(at), sum(is_vmcnt_wait(i) for i in ins[at[0]:at[-1]])
+
+
+def staging_loads_before_first_wait(all_ins):
+    """The scorer tables' way into LDS: 16-byte loads from CRP_TABS.  Counts the `global_load_dwordx4` from the instruction
+    that takes the table's address to the first `s_waitcnt vmcnt` behind a load: a thread's requests in flight together."""
+    start = next((k for k, i in enumerate(all_ins) if "CRP_TABS" in i), None)
+    if start is None:
+        return None
+    n = 0
+    for i in all_ins[start:]:
+        if i.startswith("global_load_dwordx4"):
+            n += 1
+        elif n and is_vmcnt_wait(i):
+            break
+    return n
+
+
 def add(a, b):
     return {k: a.get(k, 0) + b[k] for k in b}
 
@@ -224,6 +270,7 @@ def budget(asm, remarks, name):
         raise SystemExit("the scorer is not inside a loop")
     outer = loops_of(row_loop)[-1]
     row, setup, rounds = {}, {}, {}
+    round_blocks = []
     region_ins = {"rounds": [], "row_loop": [], "tail": []}  # (tail: laid out behind the round loop's header, outside the loop)
     seen_outer = False
     zero = counts([])
@@ -238,6 +285,7 @@ def budget(asm, remarks, name):
         elif outer in in_loops:
             rounds = add(rounds or zero, c)
             region_ins["rounds"] += ins
+            round_blocks.append((label, label == header, ins))
         elif not seen_outer:
             setup = add(setup or zero, c)
         else:
@@ -255,6 +303,8 @@ def budget(asm, remarks, name):
         "vmem_loads": {region: vmem_loads(ins) for region, ins in region_ins.items()},
         "prefetch": {"dst_written_in_row_loop": prefetch_dst_written(
             [i for ins in region_ins.values() for i in vmem_loads(ins)["instructions"] if i.split()[-1] == "idxen"], region_ins["row_loop"])},
+        "lookback": dict(zip(("first_window_loads", "first_window_waits_between_loads"), first_window(round_blocks))),
+        "staging": {"loads_before_first_wait": staging_loads_before_first_wait(all_ins)},
         "vgprs": int(res["VGPRs"]),
         "sgprs": int(res["TotalSGPRs"]),
         "sgpr_spills": int(res["SGPRs Spill"]),
@@ -289,6 +339,8 @@ def main():
     print("  void terms VALU %4d of the set-up's, behind a %s branch" % (v["valu"], "scalar" if v["uniform"] else "NON-UNIFORM"))
     for region, v in b["vmem_loads"].items():
         print("  vmem loads in %-8s %d, of which prefetch %d" % (region, v["count"], v["prefetch"]))
+    print("  look-back: %s vmcnt waits between the first window's %d descriptor loads; staging: %s table loads before the first wait"
+          % (b["lookback"]["first_window_waits_between_loads"], b["lookback"]["first_window_loads"], b["staging"]["loads_before_first_wait"]))
     print("  VGPRs %d  SGPRs %d  SGPR spills %d  VGPR spills %d  scratch %d B  LDS %d B  occupancy %d waves/SIMD"
           % (b["vgprs"], b["sgprs"], b["sgpr_spills"], b["vgpr_spills"], b["scratch"], b["lds"], b["occupancy"]))
 
