@@ -31,14 +31,21 @@ BUCKET = 65536  # arena positions per bucket of the 16-bit position exchange
 _ALPHA = {"dense": b"ACGTACGTacgtN", "at": b"ATat", "plus": b"AGGT", "minus": b"ACCT", "isolated": b"ATat"}
 
 
-def emit_block_sizes():
-    """{tile words: threads of the emit workgroup} read from the geometry lines of crp_kernels.h (TileGeo<BLOCK, WORDS, ...>)"""
+def emit_geometries():
+    """{"large" | "small": dict(block, words, list)} read from the geometry lines of crp_kernels.h
+    (TileGeo<BLOCK, WORDS, WPT, LIST, ...>): threads of the emit workgroup, words per tile, hit-list entries per round"""
     path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cropsr_amd", "csrc", "crp_kernels.h")
     with open(path) as f:
         text = f.read()
-    large = re.search(r"using GeoLarge = TileGeo<(\d+), (\d+),", text)
-    small = re.search(r"#define CRP_GEO_SMALL (\d+), (\d+),", text)
-    out = {int(m.group(2)): int(m.group(1)) for m in (large, small)}
+    large = re.search(r"using GeoLarge = TileGeo<(\d+), (\d+), (\d+), (\d+),", text)
+    small = re.search(r"#define CRP_GEO_SMALL (\d+), (\d+), (\d+), (\d+),", text)
+    return {name: dict(block=int(m.group(1)), words=int(m.group(2)), list=int(m.group(4)))
+            for name, m in (("large", large), ("small", small))}
+
+
+def emit_block_sizes():
+    """{tile words: threads of the emit workgroup} from emit_geometries()"""
+    out = {geo["words"]: geo["block"] for geo in emit_geometries().values()}
     assert set(out) == {TILE_S, TILE_L}, out
     return out
 
