@@ -218,6 +218,10 @@ SIGNATURES = {
     "crp_search_self_compare": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),
     "crp_search_self_fetch": (ctypes.c_int, [ctypes.c_void_p, u32p, u8p, u32p, u32p, u32p, u64p, ctypes.c_uint64]),
     "crp_search_self_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
+    "crp_search_self_set_model": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double, f64p, f64p, f64p, ctypes.c_int]),
+    "crp_search_self_run_model": (ctypes.c_int, [ctypes.c_void_p]),
+    "crp_search_self_fetch_model": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_uint64]),
+    "crp_search_self_model_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
     "crp_search_self_join_hits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, u32p, u64p, u32p, u64p]),
     "crp_search_self_join_device": (ctypes.c_int, [ctypes.c_void_p, voidpp, voidpp, voidpp, voidpp]),
     "crp_search_self_set_families": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, u32p, u32p, ctypes.c_uint64, ctypes.c_int]),
@@ -276,6 +280,8 @@ SIGNATURES = {
     "crp_select_set_self_limits": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_uint64]),
     "crp_select_fetch_self": (ctypes.c_int, [ctypes.c_void_p, u32p, u32p, u32p, u32p, u8p, u32p, u32p, u32p, u64p]),
     "crp_select_self_stats": (ctypes.c_int, [ctypes.c_void_p, f64p, ctypes.c_int]),
+    "crp_select_set_self_model": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_double]),
+    "crp_select_fetch_self_model": (ctypes.c_int, [ctypes.c_void_p, f64p]),
     "crp_annotation_gene_coding": (ctypes.c_int, [ctypes.c_void_p, u8p, u32p, u32p]),
     "crp_annotation_coding_layout": (ctypes.c_int, [ctypes.c_void_p, u64p, ctypes.c_uint64, ctypes.c_int, u32p, u32p, u64p, ctypes.c_uint64, u64p,
                                                     u32p, u32p, u32p, ctypes.c_uint64, u64p]),

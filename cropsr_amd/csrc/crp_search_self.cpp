@@ -15,6 +15,9 @@
 //          every candidate its owner, compare fills a second row per guide site from the candidates of its own family
 //          (work planned from the genes' runs: tiles of SELF_TILE queries x slices of a member's run), join hands those
 //          rows to the hit tables like the plain ones.
+// model    (kernel in crp_ontarget.hip) a position-specific linear on-target model on the handle: set_model
+//          uploads its tables, run_model leaves one f64 sum per candidate (NaN where a candidate is no guide site or its
+//          window holds a non-base), fetch_model returns the guide sites' sums in fetch's order.  It needs no compare.
 // A genome of several arenas is every ordered pair of handles, segment by segment (cropsr_amd/search.py: search_self).
 #include <algorithm>
 #include <cmath>
@@ -24,6 +27,7 @@
 #include <vector>
 
 #include "crp_internal.h"
+#include "crp_ontarget.h"
 #include "crp_search_family.h"
 #include "crp_search_self.h"
 #include "crp_select_self.h"
@@ -122,6 +126,13 @@ struct crp_search_self {
     unsigned long long *d_fjoin_sum[2] = {nullptr, nullptr}, *d_fjoin_cover[2] = {nullptr, nullptr};
     uint64_t fjoin_cap[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};
     uint64_t fjoin_rows[2] = {0, 0};  // the tables' rows at the time of the family join
+    // the on-target model: crp_search_self_set_model .. crp_search_self_model_stats
+    crp::ModelShape model = {};
+    bool model_set = false, model_run = false;
+    double *d_model_table = nullptr;  // MODEL_TABLE: single, pair, gc
+    double *d_model = nullptr;        // n: the sums, in extraction order
+    uint64_t model_bytes = 0;
+    double ms_model = 0;
 
     crp::FamilyCands family_cands() const { return crp::FamilyCands{d_cand, d_cand + n, d_cand + 2 * n, d_fam_tag}; }
     void free_families()
@@ -257,8 +268,8 @@ bool self_joined(const crp_search_self *s, SelfJoined *out)
 void self_select_handle(const crp_search_self *s, SelfSelectHandle *out, bool *compared)
 {
     const SearchCands c = s->cands();
-    out->rows = SelfSelectRows{c.hi, c.lo, c.pos, s->d_flag, s->d_counts, s->value.any() ? s->d_hit_sum : nullptr, (uint32_t)s->n,
-                               (uint32_t)s->max_mm + 1u};
+    out->rows = SelfSelectRows{c.hi, c.lo, c.pos, s->d_flag, s->d_counts, s->value.any() ? s->d_hit_sum : nullptr,
+                               s->model_run ? s->d_model : nullptr, (uint32_t)s->n, (uint32_t)s->max_mm + 1u};
     out->arena = s->arena;
     out->T = s->T;
     out->pam_len = s->pam_len;
@@ -373,6 +384,8 @@ int crp_search_self_destroy(crp_search_self *s)
     (void)hipFree(s->d_hit_sum);
     s->value.free();
     (void)hipFree(s->d_items);
+    (void)hipFree(s->d_model_table);
+    (void)hipFree(s->d_model);
     s->free_families();
     for (int k = 0; k < 2; ++k) {
         (void)hipFree(s->d_join_counts[k]);
@@ -648,6 +661,129 @@ int crp_search_self_stats(const crp_search_self *s, double *out, int n)
     if (!s || (n && !out) || n < 0 || n > 9) return CRP_ERR_INVALID;
     const double v[9] = {s->ms_extract, s->ms_order, s->ms_compare, (double)s->n_compare, s->ms_longest,
                          (double)s->pairs, (double)s->bytes, (double)s->n_order, s->ms_join};
+    for (int k = 0; k < n; ++k) out[k] = v[k];
+    return CRP_OK;
+}
+
+// ---- on-target model ---------------------------------------------------------------------------
+
+int crp_search_self_set_model(crp_search_self *s, int window, int left, double intercept, const double *single, const double *pair,
+                              const double *gc, int n_gc)
+{
+    if (!s) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    const std::string who = "crp_search_self_set_model";
+    const auto refuse = [&](const std::string &text) {
+        ctx->last_error = who + ": " + text;
+        return CRP_ERR_INVALID;
+    };
+    const int G = s->T - s->pam_len;
+    if (window < 1 || window > crp::MODEL_MAX_W)
+        return refuse("a window of 1.." + std::to_string(crp::MODEL_MAX_W) + " letters is scored, not " + std::to_string(window));
+    if (left < 0 || left >= window)
+        return refuse("left must be 0.." + std::to_string(window - 1) + " (the window holds at least pattern position 0), not " +
+                      std::to_string(left));
+    if (gc && n_gc != G + 1)
+        return refuse("the gc table has " + std::to_string(n_gc) + " weights, the guide region " + std::to_string(G) + " letters (" +
+                      std::to_string(G + 1) + " counts)");
+    // terms not given are 0.0; the device always reads full tables
+    std::vector<double> table(crp::MODEL_TABLE, 0.0);
+    const auto copy = [&](const double *src, int n, int at) {
+        for (int i = 0; src && i < n; ++i) {
+            if (!std::isfinite(src[i])) return false;
+            table[at + i] = src[i];
+        }
+        return true;
+    };
+    if (!std::isfinite(intercept)) return refuse("the intercept is not a finite number");
+    if (!copy(single, window * 4, 0)) return refuse("a single-letter weight is not a finite number");
+    if (!copy(pair, (window - 1) * 16, crp::MODEL_SINGLE)) return refuse("a pair weight is not a finite number");
+    if (!copy(gc, G + 1, crp::MODEL_SINGLE + crp::MODEL_PAIR)) return refuse("a gc weight is not a finite number");
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    if (!s->d_model_table) {
+        const uint64_t n1 = std::max<uint64_t>(s->n, 1);
+        const uint64_t add = n1 * sizeof(double) + crp::MODEL_TABLE * sizeof(double);
+        if (s->bytes + add > s->budget) {
+            ctx->last_error = who + ": the handle with a model column needs " + std::to_string(s->bytes + add) +
+                              " bytes of device memory: more than the budget of " + std::to_string(s->budget);
+            return CRP_ERR_CAPACITY;
+        }
+        double *tab = nullptr, *col = nullptr;
+        hipError_t e = hipMalloc(reinterpret_cast<void **>(&tab), crp::MODEL_TABLE * sizeof(double));
+        if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&col), n1 * sizeof(double));
+        if (e != hipSuccess) {
+            (void)hipFree(tab);
+            ctx->last_error = who + ": " + hipGetErrorString(e);
+            return e == hipErrorOutOfMemory ? CRP_ERR_NOMEM : CRP_ERR_HIP;
+        }
+        s->d_model_table = tab;
+        s->d_model = col;
+        s->model_bytes = add;
+        s->bytes += add;
+    }
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));  // (an earlier run of the model has read the table)
+    s->model_set = s->model_run = false;
+    CRP_HIP(ctx, hipMemcpy(s->d_model_table, table.data(), crp::MODEL_TABLE * sizeof(double), hipMemcpyHostToDevice));
+    s->model = crp::ModelShape{window, left, s->T, s->rule.region, intercept};
+    s->model_set = true;
+    return CRP_OK;
+}
+
+int crp_search_self_run_model(crp_search_self *s)
+{
+    if (!s) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    crp_arena *a = s->arena;
+    if (!s->model_set) {
+        ctx->last_error = "crp_search_self_run_model: no model on the handle (crp_search_self_set_model)";
+        return CRP_ERR_STATE;
+    }
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    s->model_run = false;
+    const crp::SearchCands c = s->cands();
+    const crp::ModelPlanes planes{a->d_plane[0], a->d_plane[1], a->d_plane[3], a->padded_words};
+    CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
+    CRP_HIP(ctx, crp::launch_self_model(ctx->stream, c.pos, c.hi, s->d_flag, (uint32_t)s->n, planes, s->model, s->d_model_table, s->d_model));
+    CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    s->ms_model = elapsed(s->ev[0], s->ev[1]);
+    s->model_run = true;
+    return CRP_OK;
+}
+
+int crp_search_self_fetch_model(crp_search_self *s, double *sum, uint64_t cap)
+{
+    if (!s || !sum) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    if (!s->model_run) {
+        ctx->last_error = "crp_search_self_fetch_model: the handle's model has not been run (crp_search_self_run_model)";
+        return CRP_ERR_STATE;
+    }
+    if (cap < s->n_guides) return CRP_ERR_CAPACITY;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const uint64_t chunk = 1ull << 22, m1 = std::min(chunk, std::max<uint64_t>(s->n, 1));
+    std::vector<uint8_t> flag(m1);
+    std::vector<double> v(m1);
+    uint64_t k = 0;
+    for (uint64_t i0 = 0; i0 < s->n; i0 += chunk) {
+        const uint64_t m = std::min(chunk, s->n - i0);
+        CRP_HIP(ctx, hipMemcpy(flag.data(), s->d_flag + i0, m, hipMemcpyDeviceToHost));
+        CRP_HIP(ctx, hipMemcpy(v.data(), s->d_model + i0, m * sizeof(double), hipMemcpyDeviceToHost));
+        for (uint64_t i = 0; i < m; ++i) {
+            if (!flag[i]) continue;
+            if (k >= cap) return CRP_ERR_HIP;  // (cannot be: the flags were counted at create)
+            sum[k++] = v[i];
+        }
+    }
+    return k == s->n_guides ? CRP_OK : CRP_ERR_HIP;
+}
+
+int crp_search_self_model_stats(const crp_search_self *s, double *out, int n)
+{
+    if (!s || (n && !out) || n < 0 || n > 2) return CRP_ERR_INVALID;
+    if (!s->model_run) return CRP_ERR_STATE;
+    const double v[2] = {s->ms_model, (double)s->n};
     for (int k = 0; k < n; ++k) out[k] = v[k];
     return CRP_OK;
 }

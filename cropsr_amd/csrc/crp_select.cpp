@@ -123,8 +123,10 @@ struct crp_select {
     crp::SelectResult self_res = {};  // n_in, n_pass: n_genes; sel: n_genes * kself of the last run
     crp::SelfSelectGathered self_got = {};  // n_genes * kself entries, beside sel
     uint2 *d_self_run = nullptr;
-    uint64_t self_cap[10] = {};
+    uint64_t self_cap[11] = {};
     uint64_t self_items_per_launch = crp::SELECT_MAX_ITEMS;
+    bool self_rank_model = false, self_has_min = false;  // crp_select_set_self_model
+    double self_min_sum = 0.0;
     int kself = 0;        // of the last successful crp_select_run_self (0: none)
     int self_stride = 0;  // M + 1 of that run's handle
     double self_stats[7] = {};
@@ -351,7 +353,7 @@ int crp_select_destroy(crp_select *s)
                     s->d_set_best, s->d_set_start, s->d_set_slots, s->d_set_covered, s->spaced_res.n_pass, s->spaced_res.n_spaced, s->spaced_res.sel,
                     s->spaced_rounds.cuts, s->spaced_rounds.last, s->spaced_rounds.prop, s->spaced_rounds.slot_pass, s->spaced_rounds.picked,
                     s->d_spaced_items, s->d_spaced_merge, s->self_res.n_in, s->self_res.n_pass, s->self_res.sel, s->self_got.pos,
-                    s->self_got.hi, s->self_got.lo, s->self_got.counts, s->self_got.strand, s->self_got.sum, s->d_self_run,
+                    s->self_got.hi, s->self_got.lo, s->self_got.counts, s->self_got.strand, s->self_got.sum, s->self_got.model, s->d_self_run,
                     s->pd_res.n_pass, s->pd_res.n_pairs, s->pd_res.n_distinct, s->pd_res.pairs, s->pd_rounds.prop, s->pd_rounds.slot_pass,
                     s->pd_rounds.slot_pairs, s->pd_rounds.picked, s->d_pd_items, s->d_pd_merge, s->d_pd_evals};
     for (void *p : bufs) (void)hipFree(p);
@@ -1163,6 +1165,16 @@ int crp_select_set_self_limits(crp_select *s, uint64_t items_per_launch)
     return CRP_OK;
 }
 
+int crp_select_set_self_model(crp_select *s, int rank_by_model, int has_min, double min_sum)
+{
+    if (!s) return CRP_ERR_INVALID;
+    if (has_min && std::isnan(min_sum)) return fail(s->ctx, CRP_ERR_INVALID, "crp_select_set_self_model: min_sum is not a number");
+    s->self_rank_model = rank_by_model != 0;
+    s->self_has_min = has_min != 0;
+    s->self_min_sum = has_min ? min_sum : 0.0;
+    return CRP_OK;
+}
+
 int crp_select_run_self(crp_select *s, const crp_select_self_params *p, crp_search_self *self)
 {
     crp::Range roctx_range("crp: self selection");
@@ -1180,6 +1192,10 @@ int crp_select_run_self(crp_select *s, const crp_select_self_params *p, crp_sear
     if (!compared)
         return fail(ctx, CRP_ERR_STATE, who + ": the self-search handle has not been through the compare of every segment 0.." +
                                             std::to_string(h.max_mm) + " (crp_search_self_order, crp_search_self_compare)");
+    const bool by_model = s->self_rank_model || s->self_has_min;
+    if (by_model && !h.rows.model)
+        return fail(ctx, CRP_ERR_STATE, who + ": ranking or bounding by the on-target model needs the handle's model run first "
+                                              "(crp_search_self_set_model, crp_search_self_run_model)");
     if (p->cut_offset < 1 || p->cut_offset > h.T - 1)
         return fail(ctx, CRP_ERR_INVALID, who + ": the cut offset must be 1.." + std::to_string(h.T - 1) + " (pattern positions), not " +
                                               std::to_string(p->cut_offset));
@@ -1201,6 +1217,7 @@ int crp_select_run_self(crp_select *s, const crp_select_self_params *p, crp_sear
     if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->self_got.strand), &s->self_cap[7], G * k, sizeof(uint8_t));
     if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->self_got.sum), &s->self_cap[8], G * k, sizeof(uint64_t));
     if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->d_self_run), &s->self_cap[9], G, sizeof(uint2));
+    if (rc == CRP_OK) rc = crp::grow(ctx, reinterpret_cast<void **>(&s->self_got.model), &s->self_cap[10], G * k, sizeof(double));
     if (rc != CRP_OK) return rc;
     for (double &v : s->self_stats) v = 0;
     s->self_stride = (int)stride;
@@ -1271,6 +1288,9 @@ int crp_select_run_self(crp_select *s, const crp_select_self_params *p, crp_sear
     pred.max_t_run = p->max_t_run;
     pred.seq_limits = (p->gc_min > 0 || p->gc_max < G_letters || p->max_t_run < G_letters) ? 1u : 0u;
     pred.k = k;
+    pred.min_sum = s->self_min_sum;
+    pred.rank_model = s->self_rank_model ? 1u : 0u;
+    pred.has_min = s->self_has_min ? 1u : 0u;
     crp::SelfSelectTrack track = {};
     if (p->require_cds) {
         track.points = a->d_ann_points;
@@ -1284,7 +1304,8 @@ int crp_select_run_self(crp_select *s, const crp_select_self_params *p, crp_sear
     for (uint64_t first = 0; first < items.size(); first += s->self_items_per_launch) {
         const uint32_t n = (uint32_t)std::min<uint64_t>(s->self_items_per_launch, items.size() - first);
         CRP_HIP(ctx, hipEventRecord(s->ev[0], ctx->stream));
-        CRP_HIP(ctx, crp::launch_select_self_items(ctx->stream, h.rows, track, pred, s->d_lo, s->d_hi, s->d_items + first, n, s->part, s->self_res));
+        CRP_HIP(ctx, crp::launch_select_self_items(ctx->stream, h.rows, track, pred, s->d_lo, s->d_hi, s->d_items + first, n, s->part, s->self_res,
+                                                   by_model));
         CRP_HIP(ctx, hipEventRecord(s->ev[1], ctx->stream));
         CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
         s->self_stats[1] += elapsed(s->ev[0], s->ev[1]);
@@ -1328,6 +1349,19 @@ int crp_select_fetch_self(crp_select *s, uint32_t *n_in, uint32_t *n_pass, uint3
     if (rc == CRP_OK && lo) rc = crp::staged_d2h(ctx, lo, s->self_got.lo, E * sizeof(uint32_t));
     if (rc == CRP_OK && counts) rc = crp::staged_d2h(ctx, counts, s->self_got.counts, E * s->self_stride * sizeof(uint32_t));
     if (rc == CRP_OK && hit_sum) rc = crp::staged_d2h(ctx, hit_sum, s->self_got.sum, E * sizeof(uint64_t));
+    if (rc != CRP_OK) return rc;
+    CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return CRP_OK;
+}
+
+int crp_select_fetch_self_model(crp_select *s, double *model_sum)
+{
+    if (!s) return CRP_ERR_INVALID;
+    crp_ctx *ctx = s->ctx;
+    if (!s->kself) return fail(ctx, CRP_ERR_STATE, "crp_select_fetch_self_model: no crp_select_run_self has succeeded on this handle");
+    if (!s->n_genes || !model_sum) return CRP_OK;
+    CRP_HIP(ctx, hipSetDevice(ctx->device));
+    const int rc = crp::staged_d2h(ctx, model_sum, s->self_got.model, s->n_genes * s->kself * sizeof(double));
     if (rc != CRP_OK) return rc;
     CRP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return CRP_OK;

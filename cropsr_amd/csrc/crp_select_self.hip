@@ -10,7 +10,11 @@
 //            a trip, coalesced -- position, guide flag, the counts row, the hit sum, and the code bits only under a GC or a
 //            T-run limit.  The wave keeps its top K sorted across its lanes (crp_select_insert.h) under the key ~e, so the
 //            most specific site is the highest key, with the tie word cut << 1 | strand
-//   gather   one lane per selected entry: its position, strand, code bits, counts and hit sum into compact arrays
+//   gather   one lane per selected entry: its position, strand, code bits, counts, hit sum and on-target sum into compact arrays
+//
+// With an on-target model on the handle the items kernel's model form also reads the candidate's f64
+// sum: as a bound, as the ranking key (larger sum first, self_select_model_key; the tie word is unchanged) or both.  The
+// other form is section 28's, bit for bit.
 //
 // A cut gene's partial lists are merged by crp_select.hip's merge kernel, as they are.  The CDS test is an inline look-up
 // through the arena's track and bucket table (annot_lookup_kernel's scheme), paid only by the lanes that pass every other
@@ -94,6 +98,17 @@ __device__ __forceinline__ bool self_select_cds(uint32_t cut, const SelfSelectTr
     return id < t.n_flags && t.flags[id] != 0;
 }
 
+// The list key of an on-target sum s: a larger s is a higher key.  With b the bits of s, -0.0 first
+// replaced by +0.0: b ^ 0x8000000000000000 for b >= 0 as a signed value, ~b otherwise.
+__device__ __forceinline__ unsigned long long self_select_model_key(double s)
+{
+    long long b = __double_as_longlong(s);
+    if (b == (long long)0x8000000000000000ull) b = 0;
+    return b >= 0 ? (unsigned long long)b ^ 0x8000000000000000ull : ~(unsigned long long)b;
+}
+
+// MODEL: the form that reads the on-target sum -- as a threshold (pred.has_min), as the ranking key (pred.rank_model) or both.
+template <bool MODEL>
 __global__ __launch_bounds__(BLOCK) void select_self_items_kernel(SelfSelectRows rows, SelfSelectTrack track, SelfSelectPredicate pred,
                                                                   const uint32_t *__restrict__ gene_lo, const uint32_t *__restrict__ gene_hi,
                                                                   const SelectItem *__restrict__ items, uint32_t n_items, SelectPartials part,
@@ -136,10 +151,19 @@ __global__ __launch_bounds__(BLOCK) void select_self_items_kernel(SelfSelectRows
             const uint32_t gc = (uint32_t)__popc(h & pred.region);
             pass = pass && gc >= pred.gc_min && gc <= pred.gc_max && self_select_run(~h & l & pred.region) <= pred.max_t_run;
         }
+        unsigned long long key = ~e;
+        if (MODEL) {
+            const double s = inside ? rows.model[row] : 0.0;
+            if (pred.has_min) pass = pass && s >= pred.min_sum;  // (uniform; false for a NaN)
+            if (pred.rank_model) {                                // (uniform)
+                pass = pass && s == s;
+                key = self_select_model_key(s);
+            }
+        }
         if (track.flags && pass) pass = self_select_cds(cut, track);
         n_in += (uint32_t)__popcll(__ballot(inside));
         n_pass += (uint32_t)__popcll(__ballot(pass));
-        sel_insert(mine, lane, k, pass, ~e, cut << 1 | strand, (uint32_t)row);
+        sel_insert(mine, lane, k, pass, key, cut << 1 | strand, (uint32_t)row);
     }
     if (it.slot == SELECT_NONE) {
         if (lane < k) res.sel[(uint64_t)it.gene * k + lane] = mine.row;
@@ -175,6 +199,7 @@ __global__ __launch_bounds__(BLOCK) void select_self_gather_kernel(SelfSelectRow
     out.lo[i] = have ? rows.lo[c] : SELECT_NONE;
     for (uint32_t j = 0; j < rows.stride; ++j) out.counts[i * rows.stride + j] = have ? rows.counts[(uint64_t)c * rows.stride + j] : SELECT_NONE;
     out.sum[i] = have && rows.sum ? rows.sum[c] : ~0ull;
+    out.model[i] = have && rows.model ? rows.model[c] : __longlong_as_double(0x7ff8000000000000ll);
 }
 
 }  // namespace
@@ -190,11 +215,16 @@ hipError_t launch_select_self_bounds(hipStream_t s, const uint32_t *cand_pos, ui
 
 hipError_t launch_select_self_items(hipStream_t s, const SelfSelectRows &rows, const SelfSelectTrack &track, const SelfSelectPredicate &pred,
                                     const uint32_t *gene_lo, const uint32_t *gene_hi, const SelectItem *items, uint32_t n_items,
-                                    const SelectPartials &part, const SelectResult &res)
+                                    const SelectPartials &part, const SelectResult &res, bool model)
 {
     if (!n_items) return hipSuccess;
-    hipLaunchKernelGGL(select_self_items_kernel, dim3((n_items + SELECT_WAVES - 1) / SELECT_WAVES), dim3(BLOCK), 0, s, rows, track, pred,
-                       gene_lo, gene_hi, items, n_items, part, res);
+    const dim3 grid((n_items + SELECT_WAVES - 1) / SELECT_WAVES);
+    if (model)
+        hipLaunchKernelGGL(select_self_items_kernel<true>, grid, dim3(BLOCK), 0, s, rows, track, pred, gene_lo, gene_hi, items, n_items, part,
+                           res);
+    else
+        hipLaunchKernelGGL(select_self_items_kernel<false>, grid, dim3(BLOCK), 0, s, rows, track, pred, gene_lo, gene_hi, items, n_items, part,
+                           res);
     return hipGetLastError();
 }
 

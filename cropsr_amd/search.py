@@ -904,6 +904,29 @@ class ArenaSelfSearch:
                 "join_ms")
         return dict(zip(keys, (float(v) for v in out)))
 
+    def set_model(self, model, guide_letters):
+        """crp_search_self_set_model: an ontarget.Model for this handle's pattern (guide_letters: its G)."""
+        gc = model.gc_table(guide_letters)
+        single, pair = np.ascontiguousarray(model.single, np.float64), np.ascontiguousarray(model.pair, np.float64)
+        self._check(nat.lib().crp_search_self_set_model(self._h, model.window, model.left, model.intercept, single.ctypes.data_as(nat.f64p),
+                                                        pair.ctypes.data_as(nat.f64p) if pair.size else None,
+                                                        gc.ctypes.data_as(nat.f64p) if gc is not None else None,
+                                                        0 if gc is None else gc.size), "crp_search_self_set_model")
+
+    def run_model(self):
+        self._check(nat.lib().crp_search_self_run_model(self._h), "crp_search_self_run_model")
+
+    def fetch_model(self):
+        """(n,) float64: the on-target sum of every guide site in fetch()'s order, NaN where a site has none."""
+        out = np.empty(self.sizes()[2], np.float64)
+        self._check(nat.lib().crp_search_self_fetch_model(self._h, out.ctypes.data_as(nat.f64p), out.size), "crp_search_self_fetch_model")
+        return out
+
+    def model_stats(self):
+        out = np.zeros(2, dtype=np.float64)
+        self._check(nat.lib().crp_search_self_model_stats(self._h, out.ctypes.data_as(nat.f64p), 2), "crp_search_self_model_stats")
+        return dict(model_ms=float(out[0]), model_rows=float(out[1]))
+
     def join_hits(self, guide_len, fetch=True):
         """crp_search_self_join_hits: this handle's rows handed to the hits of its arena's last scan at guide_len (the
         module's docstring, CSV join).  Returns (counts_plus (n_plus, M + 1) uint32, sum_plus (n_plus,) uint64, counts_minus,
@@ -987,6 +1010,7 @@ class SelfSearchResult:
     site_family = site_gene = fam_counts = fam_sum = fam_cover = None  # with families=: per guide site (families.py)
     selection = None  # with select=: the select_self.Selection
     n_guides = None   # the guide sites of the genome (len(sites), also where sites=False left them on the device)
+    on_target_sum = on_target = None  # with on_target=: per guide site, the model's sum (NaN: none) and its value under the link
 
     def __init__(self, sites, guides, counts, hit_sum, candidates, pairs, stats=None):
         self.sites = sites            # SELF_SITE_DTYPE, ordered by contig, position, strand
@@ -1055,7 +1079,7 @@ def check_family_geometry(pattern, pam_len):
 
 
 def search_self(genome, pattern, max_mm, pam_len, guide_pattern=None, score=None, budget=None, pairs_per_launch=None, families=None,
-                family_cover_mm=0, family_limits=None, select=None, sites=True):
+                family_cover_mm=0, family_limits=None, select=None, sites=True, on_target=None):
     """The self search over all arenas of `genome` (engine.Genome): see the module's docstring.  budget: device bytes
     one arena's handle may take (None: the library's default); SelfCapacityError (.needed) beyond it.
     pairs_per_launch: lowers the pairs one compare launch covers (results do not depend on it).
@@ -1066,9 +1090,23 @@ def search_self(genome, pattern, max_mm, pam_len, guide_pattern=None, score=None
     GPU between the compares and the closing of the handles (select_self.py has the definition), and the result carries
     them as .selection (select_self.Selection).  sites=False (with select=, without families=): the per-site rows are not
     copied to the host -- the result's sites, guides, counts and hit_sum are empty and only .selection, .candidates, .n_guides
-    and .pairs are filled."""
+    and .pairs are filled.
+    on_target: an ontarget.Model of the pattern's geometry; its sum is then evaluated on the GPU for every guide site of every
+    arena (ontarget.py has the definition) and the result carries on_target_sum (float64, NaN where a site has none) and
+    on_target (the value under the model's link) in the result's site order; a selection may rank and bound by it
+    (select_self.Params: rank, min_on_target)."""
     pattern, gp, max_mm, pam_len, scheme = check_self(pattern, max_mm, pam_len, guide_pattern, score)
     lo, hi, pam3 = guide_region(pattern, pam_len)
+    if on_target is not None:
+        try:
+            on_target.check_geometry(len(pattern), pam_len, pam3)
+        except ValueError as e:
+            raise SearchInputError(str(e))
+    if select is not None:
+        try:
+            select.params.bind_model(on_target)
+        except ValueError as e:
+            raise SearchInputError(str(e))
     if not sites and (select is None or families is not None):
         raise SearchInputError("sites=False keeps only the selection: it needs select= and goes without families=")
     if select is not None:
@@ -1086,6 +1124,10 @@ def search_self(genome, pattern, max_mm, pam_len, guide_pattern=None, score=None
     try:
         _self_handles(genome, pattern, gp, pam_len, max_mm, scheme, budget, pairs_per_launch, handles)
         _self_compare_all(handles, max_mm)
+        if on_target is not None:
+            for h in handles:
+                h.set_model(on_target, hi - lo)
+                h.run_model()
         fam_parts = []
         if families is not None:
             _family_compare_all(handles, families, int(family_cover_mm), family_limits)
@@ -1106,9 +1148,10 @@ def search_self(genome, pattern, max_mm, pam_len, guide_pattern=None, score=None
                 for key, v in st.items():
                     sel_stats[key] = sel_stats.get(key, 0.0) + v
             selection = select_self.assemble(select.annotation.annotation.genes()[0], select.params.k, len(pattern),
-                                             select.params.cut_offset, lo, hi - lo, scheme is not None, sel_parts)
+                                             select.params.cut_offset, lo, hi - lo, scheme is not None, sel_parts,
+                                             rank=select.params.rank, link=None if on_target is None else on_target.link)
             selection.stats = sel_stats
-        parts, guides, counts, sums = [], [], [], []
+        parts, guides, counts, sums, model_sums = [], [], [], [], []
         cand, n_guides, stats = [0, 0], 0, {}
         for h, a, group in zip(handles, genome.arenas, genome.groups):
             npl, nmi, ng = h.sizes()
@@ -1117,8 +1160,13 @@ def search_self(genome, pattern, max_mm, pam_len, guide_pattern=None, score=None
             n_guides += ng
             for key, v in h.stats().items():
                 stats[key] = max(stats.get(key, 0.0), v) if key == "longest_launch_ms" else stats.get(key, 0.0) + v
+            if on_target is not None:
+                for key, v in h.model_stats().items():
+                    stats[key] = stats.get(key, 0.0) + v
             if not sites:
                 continue
+            if on_target is not None:
+                model_sums.append(h.fetch_model())
             pos, strand, fh, fl, c, hs = h.fetch(scheme is not None)
             offs = np.asarray(a.offsets, dtype=np.int64)
             k = np.searchsorted(offs, pos.astype(np.int64), "right") - 1
@@ -1146,6 +1194,10 @@ def search_self(genome, pattern, max_mm, pam_len, guide_pattern=None, score=None
                            np.concatenate(sums)[order] if scheme is not None else None, tuple(cand),
                            (int(stats.get("pairs", 0)), n_guides * (cand[0] + cand[1])), stats)
     res.selection, res.n_guides = selection, n_guides
+    if on_target is not None:
+        from . import ontarget
+        res.on_target_sum = np.concatenate(model_sums)[order] if model_sums else np.empty(0, np.float64)
+        res.on_target = ontarget.value(res.on_target_sum, on_target.link)
     if families is not None:
         res.site_family, res.site_gene, res.fam_counts, res.fam_cover = (np.concatenate([p[k] for p in fam_parts])[order] for k in (0, 1, 2, 4))
         res.fam_sum = np.concatenate([p[3] for p in fam_parts])[order] if scheme is not None else None
@@ -1236,10 +1288,12 @@ class _Columns(list):
 def format_self(contig_names, res, block=1 << 16):
     """The TSV of a self search, as an iterator of text blocks: contig, position, strand, guide, n0 .. nM and, when
     scored, hit_sum (as a sum of hit scores, hit_sum / 2^30) and specificity.  The columns are formatted with numpy, a
-    block of rows at a time."""
+    block of rows at a time.  With an on-target model every row ends with on_target: repr of the value, empty for a site
+    without a sum."""
     M1 = res.counts.shape[1]
     head = ["contig", "position", "strand", "guide"] + ["n%d" % k for k in range(M1)]
-    yield "\t".join(head + ([] if res.hit_sum is None else ["hit_sum", "specificity"])) + "\n"
+    model = getattr(res, "on_target", None) is not None
+    yield "\t".join(head + ([] if res.hit_sum is None else ["hit_sum", "specificity"]) + (["on_target"] if model else [])) + "\n"
     names = np.array(list(contig_names) or [""], dtype=object)
     for i0 in range(0, len(res.sites), block):
         s = res.sites[i0:i0 + block]
@@ -1248,6 +1302,8 @@ def format_self(contig_names, res, block=1 << 16):
         if res.hit_sum is not None:
             hs = res.hit_sum[i0:i0 + block].astype(np.float64) / float(1 << SCORE_SHIFT)
             cols += [np.char.mod("%.6f", hs), np.char.mod("%.6f", res.specificity[i0:i0 + block])]
+        if model:
+            cols.append(np.array(["" if v != v else repr(v) for v in res.on_target[i0:i0 + block].tolist()], dtype=str))
         line = cols[0]
         for c in cols[1:]:
             line = np.char.add(np.char.add(line, "\t"), c)
@@ -1425,7 +1481,18 @@ def main(argv=None):
                     help="with --select: only guides with at most PCT %% GC (an integer 0..100; as a count: floor(PCT * G / 100))")
     sg.add_argument("--select-max-t-run", type=int, default=None, metavar="N", help="with --select: only guides whose longest run of T is at most N")
     sg.add_argument("--select-only", action="store_true", help="with --select: write only the selection, no sites TSV (-o is then not required)")
+    og = ap.add_argument_group("on-target model for any nuclease (with --self; DESIGN.md section 30)")
+    og.add_argument("--on-target", metavar="FILE|rs1",
+                    help="with --self: evaluate, on the GPU, the position-specific linear model of FILE (window, left, link, intercept, "
+                         "single, pair, gc statements; cropsr_amd/ontarget.py) for every guide site, or the built-in rs1 (the scan's own "
+                         "model, N20 NGG only); both TSVs then end every row with on_target")
+    og.add_argument("--select-rank", choices=["specificity", "on-target"], default=None,
+                    help="with --select: the order inside a gene (default specificity; on-target needs --on-target: larger model sum first)")
+    og.add_argument("--select-min-on-target", type=float, default=None, metavar="X",
+                    help="with --select and --on-target: only sites whose on_target is at least X (in (0, 1) under a logistic link)")
     args = ap.parse_args(argv)
+    if args.on_target is not None and not args.self_search:
+        ap.error("--on-target belongs to --self")
     if args.select is None:
         for opt, given in _select_options(args):
             if given:
@@ -1493,14 +1560,21 @@ def _select_options(args):
             ("--select-max-perfect", args.select_max_perfect is not None), ("--select-min-specificity", args.select_min_specificity is not None),
             ("--select-cds", args.select_cds), ("--select-gc-min", args.select_gc_min is not None),
             ("--select-gc-max", args.select_gc_max is not None), ("--select-max-t-run", args.select_max_t_run is not None),
-            ("--select-only", args.select_only)]
+            ("--select-only", args.select_only), ("--select-rank", args.select_rank is not None),
+            ("--select-min-on-target", args.select_min_on_target is not None)]
 
 
-def _self_select_params(args, pattern, pam_len, scored):
-    """The select_self.Params of --select and its options, checked against the pattern; SearchInputError otherwise."""
+def _self_select_params(args, pattern, pam_len, scored, model=None):
+    """The select_self.Params of --select and its options, checked against the pattern and the --on-target model;
+    SearchInputError otherwise."""
     from . import select_self
     if not args.gff:
         raise SearchInputError("--select needs -g/--gff: the genes to select for")
+    if model is None:
+        if args.select_rank == "on-target":
+            raise SearchInputError("--select-rank on-target needs --on-target: the model to rank by")
+        if args.select_min_on_target is not None:
+            raise SearchInputError("--select-min-on-target needs --on-target: the model to bound")
     if not 1 <= args.select <= select_self.MAX_K:
         raise SearchInputError("--select K must be 1..%d, not %d" % (select_self.MAX_K, args.select))
     if args.select_min_specificity is not None and not scored:
@@ -1515,8 +1589,9 @@ def _self_select_params(args, pattern, pam_len, scored):
     gc_min, gc_max = select_self.gc_bounds(args.select_gc_min, args.select_gc_max, hi - lo)
     try:
         params = select_self.Params(args.select, args.cut_offset, args.select_max_perfect, args.select_min_specificity, args.select_cds,
-                                    gc_min, gc_max, args.select_max_t_run)
-        return params.resolve(len(pattern), pam_len, pam3)
+                                    gc_min, gc_max, args.select_max_t_run, rank=args.select_rank or "specificity",
+                                    min_on_target=args.select_min_on_target)
+        return params.bind_model(model).resolve(len(pattern), pam_len, pam3)
     except ValueError as e:
         raise SearchInputError("--select: %s" % e)
 
@@ -1538,7 +1613,16 @@ def _main_self(ap, args):
             with open(args.score_table, "rb") as f:
                 score = parse_pair_table(f.read())
         pattern, gp, max_mm, pam_len, scheme = check_self(args.pattern, args.mismatches, args.pam_length, args.guide_pattern, score)
-        params = None if args.select is None else _self_select_params(args, pattern, pam_len, scheme is not None)
+        model = None
+        if args.on_target is not None:
+            from . import ontarget
+            lo, hi, pam3 = guide_region(pattern, pam_len)
+            try:
+                model = ontarget.load(args.on_target, hi - lo)
+                model.check_geometry(len(pattern), pam_len, pam3)
+            except ValueError as e:
+                raise SearchInputError("--on-target %s: %s" % (args.on_target, e))
+        params = None if args.select is None else _self_select_params(args, pattern, pam_len, scheme is not None, model)
         if params is not None:
             with open(args.gff, "rb"):  # (unreadable: refused here, before the GPU is opened)
                 pass
@@ -1556,7 +1640,7 @@ def _main_self(ap, args):
             g = eng.genome(contigs)
             try:
                 res = search_self(g, pattern, max_mm, pam_len, guide_pattern=gp, score=score, select=request,
-                                  sites=not (params is not None and args.select_only))
+                                  sites=not (params is not None and args.select_only), on_target=model)
             finally:
                 g.close()
     finally:

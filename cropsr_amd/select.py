@@ -520,6 +520,18 @@ class ArenaSelect:
                   "crp_select_fetch_self", self._ctx)
         return out
 
+    def set_self_model(self, rank_by_model=False, min_sum=None):
+        """crp_select_set_self_model, for the later run_self calls: rank by the on-target sum of the handle's model, and / or
+        pass only sites whose sum is at least min_sum (None: no bound)."""
+        nat.check(nat.lib().crp_select_set_self_model(self._h, int(bool(rank_by_model)), int(min_sum is not None),
+                                                      0.0 if min_sum is None else float(min_sum)), "crp_select_set_self_model", self._ctx)
+
+    def fetch_self_model(self):
+        """float64 (G, K) beside fetch_self(): the on-target sums of the selected candidates, NaN where there is none."""
+        out = np.empty((self.n_genes, max(1, self.kself)), np.float64)
+        nat.check(nat.lib().crp_select_fetch_self_model(self._h, out.ctypes.data_as(nat.f64p)), "crp_select_fetch_self_model", self._ctx)
+        return out
+
     def self_stats(self):
         out = np.zeros(7, dtype=np.float64)
         nat.check(nat.lib().crp_select_self_stats(self._h, out.ctypes.data_as(nat.f64p), 7), "crp_select_self_stats", self._ctx)

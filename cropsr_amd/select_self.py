@@ -31,8 +31,13 @@ a guide region of G = T - P, M mismatches -- (tests/select_self_reference.py res
               as its candidate index in extraction order, 0xFFFFFFFF beyond.  K = 1..64.  A gene met in several texts gets
               the sums of its counts and the first K of its rows.
 
-Limits: one device; ranking by specificity only (there is no on-target model for other nucleases); no pairs, spacing, coding,
-edit, family or variant filters on this path; one representative cut offset for staggered cutters.
+On-target models (ontarget.py): with a model on the search, Params(rank="on-target") orders by the model's
+sum, larger first, in place of e, and Params(min_on_target=) bounds its value; every test above stays a filter, and a site
+without a sum does not pass either of the two.  rank="specificity" without a bound is the selection above, bit for bit.
+
+Limits: one device; on-target models are linear ones with adjacent pairs over one window of at most 64 letters, one
+cut-independent model per run; no pairs, spacing, coding, edit, family or variant filters on this path; one representative
+cut offset for staggered cutters.
 """
 import numpy as np
 
@@ -93,10 +98,22 @@ def gc_bounds(pct_min, pct_max, guide_letters):
 class Params:
     """What a self selection asks for: K, the cut offset c (None: the default of the handle's geometry, filled in by
     resolve()), max_perfect (most other perfect copies, counts[0]; None: no bound), min_specificity (None or <= 0: no bound;
-    needs a scored search), require_cds, gc_min / gc_max (counts of guide letters) and max_t_run."""
+    needs a scored search), require_cds, gc_min / gc_max (counts of guide letters) and max_t_run.  With an on-target model on
+    the search (search_self(on_target=), ontarget.py): rank, "specificity" (the order above) or "on-target" (larger sum first,
+    then the smaller cut letter, then '+' before '-'; a site without a sum does not pass), and min_on_target, a bound on the
+    model's VALUE (a site passes only with a sum, and a value at least this), converted once to a bound on the sum --
+    min_sum -- by bind_model()."""
+
+    RANKS = ("specificity", "on-target")
 
     def __init__(self, k, cut_offset=None, max_perfect=None, min_specificity=None, require_cds=False, gc_min=None, gc_max=None,
-                 max_t_run=None):
+                 max_t_run=None, rank="specificity", min_on_target=None):
+        if rank not in self.RANKS:
+            raise ValueError("rank is specificity or on-target, not %r" % (rank,))
+        self.rank, self.min_on_target, self.min_sum = rank, min_on_target, None
+        if min_on_target is not None and (isinstance(min_on_target, bool) or not isinstance(min_on_target, (int, float, np.integer, np.floating))
+                                          or float(min_on_target) != float(min_on_target)):
+            raise ValueError("min_on_target is a number, not %r" % (min_on_target,))
         self.k = int(k)
         if not 1 <= self.k <= MAX_K:
             raise ValueError("K must be 1..%d, not %d" % (MAX_K, self.k))
@@ -122,6 +139,22 @@ class Params:
         self.cut_offset = check_cut(self.cut_offset, pattern_len, pam_len, pam3)
         return self
 
+    @property
+    def uses_model(self):
+        return self.rank == "on-target" or self.min_on_target is not None
+
+    def bind_model(self, model):
+        """Checks rank and min_on_target against the search's ontarget.Model (None: no model) and converts the bound on the
+        value to min_sum, the bound on the sum: itself under identity, log(x / (1 - x)) under logistic, where it must lie in
+        (0, 1).  ValueError otherwise."""
+        from . import ontarget
+        if model is None:
+            if self.uses_model:
+                raise ValueError("%s needs an on-target model (on_target=)" % ("rank on-target" if self.rank == "on-target" else "min_on_target"))
+            return self
+        self.min_sum = None if self.min_on_target is None else ontarget.min_sum(self.min_on_target, model.link)
+        return self
+
     def native(self):
         return nat.SelectSelfParams(self.max_hit_sum, self.max_mm0, self.k, int(self.cut_offset), int(self.require_cds), self.gc_min,
                                     self.gc_max, self.max_t_run, 0)
@@ -140,13 +173,19 @@ class Selection:
     """The self selection over all genes of the GFF, in file order: labels, n_in, n_pass (per gene) and, of the selected
     sites, gene after gene, rank 1 first: rows (ROW_DTYPE: position and cut are local to the contig string, 0-based), guides
     (S<G>), counts (n, M + 1) uint32, hit_sum (n,) uint64 and specificity (n,) float64 (both None when unscored), e (n,) uint64
-    (the ranking key), and stats (the handles' kernel times and launch counts, summed over the arenas)."""
+    (the specificity ranking's key), and stats (the handles' kernel times and launch counts, summed over the arenas).  With an
+    on-target model on the search: on_target_sum (n,) float64 (NaN: the site has none) and on_target (n,), its value under the
+    model's link; both None without a model."""
 
-    def __init__(self, labels, n_in, n_pass, rows, guides, counts, hit_sum, e, stats=None):
+    def __init__(self, labels, n_in, n_pass, rows, guides, counts, hit_sum, e, stats=None, on_target_sum=None, link=None):
         from .search import specificity
         self.labels, self.n_in, self.n_pass, self.rows, self.guides, self.counts = labels, n_in, n_pass, rows, guides, counts
         self.hit_sum, self.e, self.stats = hit_sum, e, stats or {}
         self.specificity = None if hit_sum is None else specificity(hit_sum)
+        self.on_target_sum = self.on_target = None
+        if on_target_sum is not None and link is not None:
+            from . import ontarget
+            self.on_target_sum, self.on_target = on_target_sum, ontarget.value(on_target_sum, link)
 
     def of_gene(self, g):
         return self.rows[self.rows["gene"] == g]
@@ -166,20 +205,30 @@ def select_arena(genome, a, request, handle, flags=None):
             sel.set_limits(request.slice_rows)
         if request.items_per_launch:
             sel.set_self_limits(request.items_per_launch)
-        sel.run_self(request.params, handle)
-        return gene, sel.fetch_self(), sel.self_stats()
+        p = request.params
+        if p.uses_model:
+            if p.min_on_target is not None and p.min_sum is None:
+                raise ValueError("min_on_target has not been converted to a bound on the sum (Params.bind_model)")
+            sel.set_self_model(p.rank == "on-target", p.min_sum)
+        sel.run_self(p, handle)
+        got = sel.fetch_self()
+        got["on_target_sum"] = sel.fetch_self_model()
+        return gene, got, sel.self_stats()
     finally:
         sel.close()
 
 
-def assemble(labels, k, pattern_len, cut_offset, region_lo, guide_letters, scored, arenas):
+def assemble(labels, k, pattern_len, cut_offset, region_lo, guide_letters, scored, arenas, rank="specificity", link=None):
     """One Selection from per-arena results.  arenas: dicts with offsets / lengths (of the arena's texts), group (their contig
     indices), gene (layout row -> gene index) and fetch_self()'s arrays.  A gene that has rows in several texts gets the sums of
-    its counts and the first K of its rows in the definition's order, texts in arena order."""
+    its counts and the first K of its rows in the definition's order, texts in arena order.  rank "on-target": the order is by
+    the on-target sum, larger first, in place of e.  link: the search's model's (None: no model; the arenas' on_target_sum is
+    then not read)."""
+    from . import ontarget
     from .search import _guide_letters
     G = len(labels)
     n_in, n_pass = np.zeros(G, np.int64), np.zeros(G, np.int64)
-    parts, gparts, cparts, sparts, eparts, tparts, aparts = [], [], [], [], [], [], []
+    parts, gparts, cparts, sparts, eparts, tparts, aparts, mparts = [], [], [], [], [], [], [], []
     stride = 1
     for a_index, a in enumerate(arenas):
         gene = np.asarray(a["gene"], dtype=np.int64)
@@ -210,6 +259,9 @@ def assemble(labels, k, pattern_len, cut_offset, region_lo, guide_letters, score
         eparts.append(scored_e(counts[:, 0], sums) if scored else packed_e(counts))
         tparts.append((cut.astype(np.uint64) << np.uint64(1)) | (strand != 0).astype(np.uint64))
         aparts.append(np.full(r.size, a_index, np.int64))
+        if link is not None:
+            mparts.append(np.asarray(a["on_target_sum"], dtype=np.float64).reshape(gene.size, -1)[r, c])
+    msum = (np.concatenate(mparts) if mparts else np.empty(0, np.float64)) if link is not None else None
     rows = np.concatenate(parts) if parts else np.empty(0, ROW_DTYPE)
     guides = np.concatenate(gparts) if gparts else np.empty(0, "S%d" % guide_letters)
     counts = np.concatenate(cparts) if cparts else np.empty((0, stride), np.uint32)
@@ -220,24 +272,33 @@ def assemble(labels, k, pattern_len, cut_offset, region_lo, guide_letters, score
     # genes in file order; a gene met in several texts: its rows by e; on equal e the texts in genome order -- the arenas in
     # order, and inside an arena the cut letter, which ascends with the texts -- then '+' before '-'.  (A cut letter is an
     # arena position: it is only compared inside one arena, so the order does not depend on how the genome was cut into arenas.)
-    order = np.lexsort((tie, arena_of, e, rows["gene"]))
+    # Ranked by the model, the on-target sum takes e's place: larger first (~key ascends as the sum descends).
+    if rank == "on-target":
+        if msum is None:
+            raise ValueError("rank on-target needs the model's link and the arenas' on_target_sum")
+        first = ~ontarget.sort_key(msum)
+    else:
+        first = e
+    order = np.lexsort((tie, arena_of, first, rows["gene"]))
     rows, guides, counts, sums, e = rows[order], guides[order], counts[order], sums[order], e[order]
     start = np.searchsorted(rows["gene"], rows["gene"], "left")
-    rank = np.arange(rows.size) - start
-    keep = rank < k
+    at = np.arange(rows.size) - start
+    keep = at < k
     rows = rows[keep]
-    rows["rank"] = rank[keep] + 1
-    return Selection(list(labels), n_in, n_pass, rows, guides[keep], counts[keep], sums[keep] if scored else None, e[keep])
+    rows["rank"] = at[keep] + 1
+    return Selection(list(labels), n_in, n_pass, rows, guides[keep], counts[keep], sums[keep] if scored else None, e[keep],
+                     on_target_sum=None if msum is None else msum[order][keep], link=link)
 
 
 def format_selection(contig_names, selection):
     """The selection file, as text: tab-separated gene, rank, passing, contig, position, strand, guide, cut, n0 .. nM and, when
     scored, hit_sum (as a sum of hit scores, hit_sum / 2^30) and specificity.  Genes in GFF order; a gene with nothing selected
-    has no line."""
+    has no line.  With an on-target model every row ends with on_target: repr of the value, empty for a site without a sum."""
     M1 = selection.counts.shape[1]
     head = ["gene", "rank", "passing", "contig", "position", "strand", "guide", "cut"] + ["n%d" % j for j in range(M1)]
     scored = selection.hit_sum is not None
-    lines = ["\t".join(head + (["hit_sum", "specificity"] if scored else []))]
+    model = selection.on_target is not None
+    lines = ["\t".join(head + (["hit_sum", "specificity"] if scored else []) + (["on_target"] if model else []))]
     for i, row in enumerate(selection.rows):
         g = int(row["gene"])
         f = [selection.labels[g], str(int(row["rank"])), str(int(selection.n_pass[g])), contig_names[int(row["contig"])],
@@ -245,5 +306,8 @@ def format_selection(contig_names, selection):
         f += [str(int(v)) for v in selection.counts[i]]
         if scored:
             f += ["%.6f" % (float(selection.hit_sum[i]) / float(1 << SCORE_SHIFT)), "%.6f" % float(selection.specificity[i])]
+        if model:
+            v = float(selection.on_target[i])
+            f.append("" if v != v else repr(v))
         lines.append("\t".join(f))
     return "\n".join(lines) + "\n"

@@ -747,6 +747,34 @@ int crp_search_self_fetch(crp_search_self *self, uint32_t *arena_pos, uint8_t *s
  * the longest compare launch in ms, out[5] pairs compared, out[6] device bytes of the handle, out[7] ordering
  * launches, out[8] ms of the join kernels (crp_search_self_join_hits).  n: how many of these to write (<= 9). */
 int crp_search_self_stats(const crp_search_self *self, double *out, int n);
+/* ---- on-target model of every guide site (opt-in) ---- */
+/* A position-specific linear model over the oriented site and the letters around it, for the handle's pattern of T letters
+ * with a guide region of G = T - P:
+ *   window   W letters (1 .. 64), `left` of them before pattern position 0 of the oriented site (0 <= left < W): window
+ *            position w is pattern position w - left.  A '+' site with forward start s reads forward positions s - left ..
+ *            s - left + W - 1; a '-' site reads s + T - 1 + left down to s + T + left - W, each complemented
+ *   tables   single[w * 4 + b] (W x 4), pair[w * 16 + b1 * 4 + b2] ((W - 1) x 16, window letters w and w + 1) and gc[0 .. G]
+ *            (n_gc = G + 1 weights, one per GC count of the guide region); letters in the order A T C G.  A NULL table is
+ *            all 0.0
+ *   sum      ((intercept + gc[GC]) + single[0] + .. + single[W - 1]) + pair[0] + .. + pair[W - 2] in f64, one add per term in
+ *            that order, no fused multiply-add, no reassociation: a host loop in the same order gives the same bits
+ *   no sum   a window position that is no base (its `ac` bit is clear: N, IUPAC letters, decoration, void, positions outside
+ *            the planes) leaves the site without a sum: a quiet NaN (0x7FF8000000000000)
+ * A link (logistic) is the caller's: the device never calls exp.
+ * set_model: CRP_ERR_INVALID with a crp_last_error text and no side effect for W outside 1 .. 64, left outside 0 .. W - 1,
+ * a gc table whose length is not G + 1, a weight that is not finite; CRP_ERR_CAPACITY when the sums' column (8 bytes a
+ * candidate) does not fit the handle's budget.  A new model replaces the old one and its sums. */
+int crp_search_self_set_model(crp_search_self *self, int window, int left, double intercept, const double *single, const double *pair,
+                              const double *gc, int n_gc);
+/* One f64 per candidate, on the device (one kernel).  Valid once the handle exists: it needs no order and no compare.
+ * CRP_ERR_STATE without a model. */
+int crp_search_self_run_model(crp_search_self *self);
+/* The sums of the guide sites, in crp_search_self_fetch's order.  CRP_ERR_STATE before crp_search_self_run_model,
+ * CRP_ERR_CAPACITY when cap < the number of guide sites. */
+int crp_search_self_fetch_model(crp_search_self *self, double *sum, uint64_t cap);
+/* Measurement of the last crp_search_self_run_model: out[0] ms of the kernel (HIP events), out[1] rows (candidates).  n: how
+ * many to write (<= 2). */
+int crp_search_self_model_stats(const crp_search_self *self, double *out, int n);
 /* The CSV join (CSV join): the rows of the handle's guide sites, handed to the hits of the arena's
  * last crp_scan_score at guide length guide_len, after the handle's orders and compares.  The handle's pattern must have
  * guide_len + 3 letters with a PAM of 3 on the 3' side, so its guide region is what the scan calls `sequence`:
@@ -1092,6 +1120,17 @@ int crp_select_fetch_self(crp_select *select, uint32_t *n_in, uint32_t *n_pass, 
  * merge launches, out[3] ms of the gather kernel (HIP events), out[4] item launches, out[5] work items, out[6] candidates
  * streamed (the runs' rows).  n: how many to write (<= 7). */
 int crp_select_self_stats(const crp_select *select, double *out, int n);
+/* The on-target model in the self selection.  Held on the select handle for its later
+ * crp_select_run_self calls, which then refuse (CRP_ERR_STATE) a self-search handle whose model has not been run.
+ *   has_min        a site passes only if it has a sum and the sum is >= min_sum (NaN min_sum: CRP_ERR_INVALID)
+ *   rank_by_model  a site passes only if it has a sum, and the order is larger sum first, then the smaller cut letter, then
+ *                  '+' before '-'.  The list key is computed from the bits b of the sum, -0.0 first replaced by +0.0:
+ *                  b ^ 0x8000000000000000 for b >= 0 as a signed value, ~b otherwise
+ * Every test of crp_select_run_self stays a filter.  With both 0 (the default) every result bit is what it is without a model. */
+int crp_select_set_self_model(crp_select *select, int rank_by_model, int has_min, double min_sum);
+/* Beside crp_select_fetch_self: the on-target sum of every selected candidate (n_genes * K), NaN where sel has no candidate,
+ * where the site has no sum or where the handle's model had not been run. */
+int crp_select_fetch_self_model(crp_select *select, double *model_sum);
 
 /* ---- coding position: where in the coding sequence a guide cuts (opt-in) ---------------- */
 /* crp_annotation_build also reads the `mRNA` / `transcript` rows, the Parent links and the gene rows' strand, and builds a
